@@ -6,18 +6,28 @@ LJSpeech-shaped batches (100 phones, 60 sub-word tokens, 400 frames) — BASELIN
 with --gpus N: configs[2] (data parallel over RCCL, weak scaling, one process per GPU).
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--workload train|infer|gta] [--attention sma|lsa]
+                  [--full] [--dump-outputs DIR]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
       --master-port P bench.py --gpus N --steps K --warmup W
 
 --workload infer = configs[3] (autoregressive inference(), B=32, 1000 decoder steps, stop disabled; metric
 decode_steps_per_sec), --workload gta = configs[4] (teacher-forced forward under no_grad, eval, B=128/GPU; replicas
-only, no collective).  The default train line also carries a short "decode" measurement (N=1).
+only, no collective).  With --full the train line also carries a short "decode" measurement (N=1).
 
 `--gpus N` without a launcher (no WORLD_SIZE in the environment) starts the N ranks itself — fresh processes, before
 anything touches a GPU, as the reference's distributed.py:181-200 does — and rank 0 prints the line.
 
-Rank 0 prints ONE JSON line.  Extra objects (N = 1 unless noted):
-  roofline      dominant decoder kernel: algorithmic bytes (or FLOPs) per launch / its average duration, measured with
+A plain run sets up, warms up, times the K steps, writes --dump-outputs if given, and prints the line; `ms_per_step` is
+the wall time of one timed step.  --dump-outputs DIR: rank 0 writes what the last timed step computed as DIR/<name>.npy
+(float32; float64 for integer data) — train: `loss`, the forward's `mel`, `mel_postnet`, `gate`, `alignments`,
+`alignments_bert`, and a fixed sample of every parameter after the update (`param.<key>`) and of its gradient
+(`grad.<key>`); infer / gta: what inference() / forward returned.  Batches and weights are seeded, so runs with the same
+arguments get the same inputs; an array larger than a fixed size is written as a fixed, seeded sample of its elements.
+
+Rank 0 prints ONE JSON line: the headline figures, `config`, `host`, `loss`, `rccl_world_size` (the size of the process
+group the ranks formed, backend nccl = RCCL; 1 without one) and, for N > 1, `ranks`.  Extra objects, only with --full
+(N = 1 unless noted; --no-extras / --no-cpu-baseline drop some of them again):
+  roofline      (every N) dominant decoder kernel: algorithmic bytes (or FLOPs) per launch / its average duration, measured with
                 HIP events on the launch stream in one extra (untimed) profiled step
   fresh_batches the same loop fed like train.py:286-316: every step collates the next ragged batch out of its dataset items
                 (data_utils.collate_batch into a page-locked stage), uploads it (batch_to_device) and runs parse_batch +
@@ -28,7 +38,7 @@ Rank 0 prints ONE JSON line.  Extra objects (N = 1 unless noted):
   gta           BASELINE configs[4]: teacher-forced forward, eval, no_grad, B=128
   cpu_baseline  the CPU oracle (torch-CPU restatement of the reference, oracle/) timed on this box's host cores on a
                 bounded sample of the same workload
-  rccl_world_size (every N) the size of the process group the ranks formed (backend nccl = RCCL), 1 without one
+  kernels       (every N) per-kernel launches / durations of that profiled step
 """
 import argparse
 import json
@@ -48,6 +58,36 @@ ATTENTION_NAMES = {"sma": "StepwiseMonotonicAttention", "lsa": "LSA", "fa2": "Fo
 PEAK_F32_MFMA_TFLOPS = 157.3
 PEAK_HBM_GBS = 8000.0
 PEAK_BF16_TFLOPS = 2500.0          # dense bf16 MFMA peak (MI355X_MICROARCH.md; AMD's 5 PF headline is 2:1 sparse)
+
+DUMP_LIMIT_BYTES = 64 << 20        # --dump-outputs: all files together
+DUMP_MAX_ELEMS = 1 << 21           # an output larger than this is written as a fixed sample of this many elements
+DUMP_PARAM_ELEMS = 4096            # per parameter / gradient tensor
+OUTPUT_NAMES = ("mel", "mel_postnet", "gate", "alignments", "alignments_bert")      # BERT_Tacotron2.forward / inference results
+
+
+def dump_outputs(d, arrays):
+    """--dump-outputs: each (name, tensor, max_elems) as d/<name>.npy — float32 (float64 for integer / bool data).  A
+    tensor of more than max_elems elements is written flat as the elements at max_elems fixed positions (drawn from a
+    generator seeded with the element count, in ascending order), so that the same shape always gives the same sample."""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    total = 0
+    for name, t, cap in arrays:
+        t = t.detach()
+        v = t.float() if t.is_floating_point() else t.double()
+        if v.numel() > cap:
+            idx = np.sort(np.random.default_rng(v.numel()).choice(v.numel(), cap, replace=False))
+            v = v.reshape(-1)[torch.from_numpy(idx).to(v.device)]
+        a = v.cpu().numpy()
+        total += a.nbytes
+        if total > DUMP_LIMIT_BYTES:
+            raise SystemExit(f"--dump-outputs: more than {DUMP_LIMIT_BYTES >> 20} MB at {name}")
+        np.save(os.path.join(d, name + ".npy"), a)
+
+
+def output_arrays(names, outs):
+    """(name, tensor, DUMP_MAX_ELEMS) for the tensors of a model call's result (non-tensor entries are left out)."""
+    return [(n, o, DUMP_MAX_ELEMS) for n, o in zip(names, outs) if torch.is_tensor(o)]
 
 
 def decoder_step_flops(hp, B, Tin, Tsub):
@@ -153,6 +193,8 @@ def side_workload(a, rank, world, local):
     if world > 1:
         import torch.distributed as dist
         dist.init_process_group(backend=os.environ.get("T2_DIST_BACKEND", "nccl"), init_method="env://", world_size=world, rank=rank)
+    torch.manual_seed(hp.seed)                                          # the same weights in every run, as make_training_objects
+    torch.cuda.manual_seed(hp.seed)
     model = T.load_model(hp)
 
     def sync():
@@ -187,9 +229,11 @@ def side_workload(a, rank, world, local):
         sync()
         t0 = time.perf_counter()
         for _ in range(a.steps):
-            run()
+            res = run()
         sync()
         dt = time.perf_counter() - t0
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, output_arrays(OUTPUT_NAMES, res))
     if world > 1:
         tt = torch.tensor([dt], device="cuda", dtype=torch.float64)
         torch.distributed.all_reduce(tt, op=torch.distributed.ReduceOp.MAX)
@@ -260,9 +304,12 @@ def main():
     ap.add_argument("--attention", choices=["sma", "lsa", "fa2", "gmm", "dca"], default="sma",
                     help="sma = the reference's default hparams (StepwiseMonotonicAttention); lsa = LocationSensitiveAttention; "
                          "fa2 / gmm / dca = ForwardAttentionV2 / GMMAttention / DynamicConvolutionAttention")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="train workload: only the timed loop and the roofline (no fresh-batch, "
-                                                             "fp32, decode, gta legs)")
+    ap.add_argument("--full", action="store_true", help="train workload: also the roofline / kernels profiled step, the fresh-batch, "
+                                                        "fp32, decode, gta and gemm legs and the CPU baseline (off: the headline only)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: no CPU baseline")
+    ap.add_argument("--no-extras", action="store_true", help="with --full, train workload: only the timed loop and the roofline (no "
+                                                             "fresh-batch, fp32, decode, gta legs)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step computed as DIR/<name>.npy")
     ap.add_argument("--dtype", choices=["f32", "bf16"], default="bf16",
                     help="GEMM operand type: f32 = exact fp32 (parity path); bf16 = bf16 operands, fp32 accumulate/state")
     a = ap.parse_args()
@@ -318,6 +365,8 @@ def main():
     arena = getattr(model, "_t2_arena", None)
     if arena is not None:
         arena.exposed = []                                              # (events only: nothing synchronises inside the loop)
+    last = {}
+    hook = model.register_forward_hook(lambda m, i, o: last.update(out=o)) if a.dump_outputs and rank == 0 else None
     sync()
     t0 = time.perf_counter()
     for _ in range(a.steps):
@@ -327,6 +376,13 @@ def main():
     dt_local = time.perf_counter() - t0                                 # this rank's own loop, before the closing barrier
     sync()
     dt = time.perf_counter() - t0
+    if hook is not None:
+        # the last timed step: the loss train_step returned, the forward's outputs, and the parameters / gradients it left
+        hook.remove()
+        params = list(model.named_parameters())
+        dump_outputs(a.dump_outputs, [("loss", loss, 1)] + output_arrays(OUTPUT_NAMES, last["out"])
+                     + [("param." + k, p, DUMP_PARAM_ELEMS) for k, p in params]
+                     + [("grad." + k, p.grad, DUMP_PARAM_ELEMS) for k, p in params if p.grad is not None])
     ranks = None
     if world > 1:
         tt = torch.tensor([dt], device="cuda", dtype=torch.float64)
@@ -346,7 +402,7 @@ def main():
                  "note": "ms_per_step: each rank's own timed loop (before the closing barrier); exposed_allreduce_ms: mean time per step its "
                          "launch stream waited for the bucketed RCCL reductions at the end of backward (HIP events) — what the overlap did not hide"}
     loss_val = float(loss.item())
-    extras = world == 1 and not a.no_extras
+    extras = a.full and world == 1 and not a.no_extras
 
     # the same loop fed from the host, as train.py:286-316 feeds it: every step collates the next model batch out of its B
     # dataset items (data_utils.collate_batch, straight into a page-locked stage of the ring), uploads it
@@ -389,12 +445,13 @@ def main():
                           "maxima, no .item()) + the training iteration; PCIe-inclusive, never `value`.  step_ms = GPU-side time between "
                           "the ends of consecutive steps (HIP events), host_ms_per_step = host time to collate + enqueue one step")
 
-    # one extra, untimed, profiled step: HIP events around every per-step decoder kernel launch
+    # --full: one extra, untimed, profiled step: HIP events around every per-step decoder kernel launch
     roof, kernels = None, None
-    if rank == 0:
-        L.prof_enable(8 * Tn + 64)
-    T.train_step(model, criterion, optimizer, x, y, hp, it)      # every rank takes the step (it contains collectives)
-    if rank == 0:
+    if a.full:
+        if rank == 0:
+            L.prof_enable(8 * Tn + 64)
+        T.train_step(model, criterion, optimizer, x, y, hp, it)  # every rank takes the step (it contains collectives)
+    if a.full and rank == 0:
         prof = L.prof_collect()
         torch.cuda.synchronize()
         bf = a.dtype == "bf16"
@@ -475,8 +532,9 @@ def main():
         "host": {"cpus_visible": os.cpu_count(), "cpu_quota": round(cpu_quota(), 1), "torch_threads": host_threads},
         "ranks": ranks,
         "loss": round(loss_val, 5),
-        "roofline": roof, "kernels": kernels,
     }
+    if a.full:
+        out["roofline"], out["kernels"] = roof, kernels
     if a.dtype == "bf16" and B > 128:
         out["config"]["note"] = "B > 128: the recurrent per-step GEMMs fall back to fp32 operands (bf16 steps cover B <= 128)"
     if fresh is not None:
@@ -514,7 +572,7 @@ def main():
         out["gta"] = gta_bench(model, hp, T, 128, Tin, Tsub, Tn, reps=3)
         if a.dtype == "bf16":
             out["gemm"] = gemm_bench(B, Tn)
-    if world == 1 and not a.no_cpu_baseline:
+    if a.full and world == 1 and not a.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline()
     print(json.dumps(out), flush=True)
 

@@ -1,7 +1,7 @@
 """Summarise a rocprofv3 PMC pass with the LDS counters: which kernels lose LDS cycles to bank conflicts.
 
   rocprofv3 --kernel-trace --pmc SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE --output-format csv -d gpurun_out/pmc_lds -o p -- \
-      python3 bench.py --steps 1 --warmup 1 --no-cpu-baseline --no-extras
+      python3 bench.py --full --steps 1 --warmup 1 --no-cpu-baseline --no-extras
   python scripts/pmc_lds.py gpurun_out/pmc_lds profiles/rNN_pmc_lds.json
 
 Per kernel name: launches, summed SQ_LDS_BANK_CONFLICT (extra LDS cycles) and SQ_LDS_IDX_ACTIVE (all LDS-array cycles) over all
