@@ -168,8 +168,9 @@ typedef struct t2_decoder_layout {
     size_t w16a, w16as, w16d, wt16a, wt16as, wt16d, din16, dh16;
     size_t gemm_ws; size_t gemm_ws_floats;
     size_t chain; size_t chain_floats;   /* exchange buffers of the persistent chain kernels (t2_set_chain): word 0 = status of
-                                          * the attention chain, word 1 = status of the decoder-LSTM chain (0 = OK), then arrival
-                                          * counters, fragment-ordered h / ctx buffers, query partials */
+                                          * the attention chain, word 1 = status of the decoder-LSTM chain (0 = OK), then query
+                                          * partials, fragment-ordered h / ctx buffers of both chains, and the decode loop's mel
+                                          * fragments and arrival counters */
     size_t usave, usaves;             /* LSA: tanh(q + pm + location term) of every step [T,B,A,Tin4], [T,B,A,Tsub4] (Tin4 = Tin rounded up to 4) and ... */
     size_t locsave, locsaves;         /* ... the location features [T,B,Tin,F], [T,B,Tsub,F]: written by the persistent forward
                                        * chain for the persistent backward chain (size 0 for the other attention kinds) */
@@ -220,7 +221,7 @@ typedef struct t2_decoder_bwd_layout {
     size_t carryc, carrycs, dlconv, dlconvs, dldense, dldenses;   /* LSA: cumulative carry, per-item location-layer gradients; GMM: mean carry, per-item db2 / dW2; zero-sized for SMA */
     size_t dcd, dca, dcas, partd, parta, dp2, dp2s, dp1, dmel_t, dgate_t, dg16a, dg16d, colsum_ws, gemm_ws, gemm_ws_floats;
     size_t chain, chain_floats;   /* exchange buffers of the persistent backward chains (gate-gradient fragments, K-split partials,
-                                   * arrival counters); their status words are words 2 (decoder-LSTM chain) and 3 (attention chain)
+                                   * boundary carries); their status words are words 2 (decoder-LSTM chain) and 3 (attention chain)
                                    * of the forward workspace's t2_decoder_layout.chain block */
 } t2_decoder_bwd_layout;
 int t2_decoder_bwd_layout_query(const t2_dims* dims, int B, int T, int Tin, int Tsub, t2_decoder_bwd_layout* out);

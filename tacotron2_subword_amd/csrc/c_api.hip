@@ -260,31 +260,8 @@ InferShadows infer_shadows(const Sizes& z, size_t base) {
     return m;
 }
 
-// Persistent chains: [status word | counters A | counters B | X of chain A | X of chain B | Q], each part 256-byte aligned.
-// Sized for the largest tiling chain_plan can choose at this batch size.
-struct ChainBufs { unsigned* err; unsigned* cnt_a; unsigned* cnt_b; unsigned char* xa; unsigned char* xb; unsigned char* xm; float* q; size_t xa_bytes, xb_bytes, q_bytes; };
-constexpr size_t kChainXmBytes = 16 * 1024;     // decode loop: mel fragments [2][8][1 KB]
-size_t chain_part_bytes(const Sizes& z, size_t* xa, size_t* xb, size_t* q) {
-    const size_t MT = (z.B + 31) / 32;
-    *xa = (size_t)2 * z.NS * ((z.Ha + z.E + z.P) / 16) * MT * 1024;      // (+ the prenet segment of the decode loop)
-    *xb = (size_t)2 * (z.Hd / 16) * MT * 1024;
-    *q = (size_t)z.NS * MT * 32 * (z.Ha / 8) * z.A * sizeof(float);
-    return 256 + 2 * kChainCntBytes + *xa + *xb + kChainXmBytes + *q;
-}
-size_t chain_region_bytes(const Sizes& z) { size_t a, b, q; return (chain_part_bytes(z, &a, &b, &q) + 255) & ~(size_t)255; }
-ChainBufs chain_bufs(const Sizes& z, const t2_decoder_layout& L, float* ws) {
-    ChainBufs b{};
-    chain_part_bytes(z, &b.xa_bytes, &b.xb_bytes, &b.q_bytes);
-    unsigned char* p = reinterpret_cast<unsigned char*>(ws + L.chain);
-    b.err = reinterpret_cast<unsigned*>(p); p += 256;
-    b.cnt_a = reinterpret_cast<unsigned*>(p); p += kChainCntBytes;
-    b.cnt_b = reinterpret_cast<unsigned*>(p); p += kChainCntBytes;
-    b.xa = p; p += b.xa_bytes;
-    b.xb = p; p += b.xb_bytes;
-    b.xm = p; p += kChainXmBytes;
-    b.q = reinterpret_cast<float*>(p);
-    return b;
-}
+// The status words of a pass (ChainStatus, kernels.h): the head of the forward workspace's chain region
+unsigned* status_words(const float* ws, const t2_decoder_layout& L) { return reinterpret_cast<unsigned*>(const_cast<float*>(ws) + L.chain); }
 
 void layout_of(const t2_dims& d, const Sizes& z, t2_decoder_layout* L) {
     size_t off = 0;
@@ -315,8 +292,8 @@ void layout_of(const t2_dims& d, const Sizes& z, t2_decoder_layout* L) {
     L->din16 = take(BT * z.WD / 2 + 4); L->dh16 = take(BT * z.Hd / 2 + 4);
     L->gemm_ws_floats = (size_t)16 << 20;                     // 64 MiB of split-K scratch
     L->gemm_ws = take(L->gemm_ws_floats);
-    // exchange buffers of the persistent chain kernels (chain.hip), see chain_bufs()
-    L->chain_floats = chain_region_bytes(z) / sizeof(float);
+    // exchange space of the persistent chain kernels (chain.hip), the pass's status words at its head
+    L->chain_floats = chain_fwd_ws_floats(z.NS, z.B, z.Ha, z.E, z.P, z.Hd, z.A);
     L->chain = take(L->chain_floats);
     // LSA: tanh tile and location features of every step, written by the forward chain for the backward chain (which then
     // repeats neither the location conv nor the tile: 1.3 GB + 0.33 GB per stream at B = 64, T = 400 — HBM is what this part has)
@@ -544,6 +521,7 @@ bool chain_a_desc(const Dec& c, ChainDesc* out) {
     if (c.d.attention_kind != T2_ATTN_SMA && c.d.attention_kind != T2_ATTN_LSA) return false;
     ChainDesc d{};
     d.NS = z.NS; d.B = z.B; d.T = z.T; d.H = z.Ha; d.E = z.E; d.A = z.A; d.WD = z.WD; d.WO = z.WO;
+    d.P = z.P; d.Hd = z.Hd;                                           // (read by the exchange-space carve only: dec = 0)
     d.din = c.P(L.din); d.din16 = c.P16(L.din16); d.dout = c.P(L.dout);
     d.kind = c.d.attention_kind == T2_ATTN_SMA ? CHAIN_SMA : CHAIN_LSA;
     d.F = c.d.loc_filters; d.Kc = c.d.loc_kernel; d.max_pos = c.max_pos;
@@ -570,11 +548,7 @@ bool chain_a_desc(const Dec& c, ChainDesc* out) {
         st.mask_value = mask_value_of(c.d, s);
     }
     if (!chain_plan(d)) return false;
-    const ChainBufs b = chain_bufs(z, L, c.ws);
-    size_t xb = 0, qb = 0;
-    chain_exchange_bytes(d, &xb, &qb);
-    if (xb > b.xa_bytes || qb > b.q_bytes) return false;
-    d.X = b.xa; d.Q = b.q; d.cnt = b.cnt_a; d.err = b.err; d.q_bytes = (unsigned)qb;
+    d.err = status_words(c.ws, L) + CHAIN_STATUS_FWD_ATT;
     *out = d;
     return true;
 }
@@ -592,11 +566,7 @@ bool chain_b_desc(const Dec& c, ChainDesc* out) {
     st.h_out = c.P(L.dout); st.ldh = z.WO; st.h16_out = c.P16(L.dh16); st.ldh16 = z.Hd;
     st.site_h = T2_SITE_DEC_H; st.site_c = T2_SITE_DEC_C; st.Tin = 4;
     if (!chain_plan(d)) return false;
-    const ChainBufs b = chain_bufs(z, L, c.ws);
-    size_t xb = 0, qb = 0;
-    chain_exchange_bytes(d, &xb, &qb);
-    if (xb > b.xb_bytes) return false;
-    d.X = b.xb; d.Q = nullptr; d.cnt = b.cnt_b; d.err = b.err + 1; d.q_bytes = 0;
+    d.err = status_words(c.ws, L) + CHAIN_STATUS_FWD_LSTM;
     *out = d;
     return true;
 }
@@ -635,11 +605,7 @@ bool chain_dec_desc(const Dec& c, const t2_decoder_weights& w, const t2_decoder_
     d.thr = a.gate_threshold; d.stop_index = a.stop_index; d.done = a.done_count;
     d.pdrop = c.prenet_dropout ? c.d.p_prenet_dropout : 0.f;
     if (!chain_plan(d)) return false;
-    const ChainBufs b = chain_bufs(z, L, c.ws);
-    size_t xb = 0, qb = 0;
-    chain_exchange_bytes(d, &xb, &qb);
-    if (xb > b.xa_bytes || qb > b.q_bytes || (size_t)2 * (z.Hd / 16) * 1024 > b.xb_bytes) return false;
-    d.X = b.xa; d.Q = b.q; d.cnt = b.cnt_a; d.err = b.err; d.q_bytes = (unsigned)qb; d.XD = b.xb; d.XM = b.xm;
+    d.err = status_words(c.ws, L) + CHAIN_STATUS_FWD_ATT;
     *out = d;
     return true;
 }
@@ -709,18 +675,9 @@ void bwd_layout_of(const t2_dims& d, const Sizes& z, t2_decoder_bwd_layout* L) {
     L->colsum_ws = take((size_t)64 * 4 * (z.Ha > z.Hd ? z.Ha : z.Hd));
     L->gemm_ws_floats = (size_t)192 << 20;                    // 768 MiB: split-K partials + bf16 operand staging (gemm.hip)
     L->gemm_ws = take(L->gemm_ws_floats);
-    {   // persistent backward chains (chain_bwd.hip): [counters | dg fragments | K-split partials] of the decoder-LSTM chain,
-        // then [counters | dg fragments | h partials | ctx partials | dq partials | boundary carries] of the attention chain
-        ChainBwdDesc cd{}; cd.kind = CHAIN_LSTM; cd.B = z.B; cd.H = z.Hd;
-        size_t xb = 0, pb = 0;
-        chain_bwd_exchange_bytes(cd, &xb, &pb);
-        ChainBwdDesc ca{}; ca.kind = lsa ? CHAIN_LSA : CHAIN_SMA; ca.B = z.B; ca.H = z.Ha; ca.E = z.E; ca.A = z.A; ca.NS = z.NS;
-        ca.F = d.loc_filters; ca.Kc = d.loc_kernel;
-        size_t x2, ph, pc, dq, cr;
-        const size_t att = chain_bwd_att_exchange_bytes(ca, &x2, &ph, &pc, &dq, &cr);
-        L->chain_floats = (2 * kChainBwdCntBytes + xb + pb + att + 255) / sizeof(float);
-        L->chain = take(L->chain_floats);
-    }
+    // exchange space of the persistent backward chains (chain_bwd.hip); their status words are in the forward workspace
+    L->chain_floats = chain_bwd_ws_floats(lsa ? CHAIN_LSA : CHAIN_SMA, z.NS, z.B, z.Ha, z.E, z.A, d.loc_filters, d.loc_kernel, z.Hd);
+    L->chain = take(L->chain_floats);
     L->total_floats = off;
 }
 
@@ -801,14 +758,7 @@ bool chain_b_bwd_desc(const Bwd& c, ChainBwdDesc* out) {
     st.dbias_part = c.S(c.BL.partd);                                 // (the launch path's K-split scratch: idle when the chain runs) [MT][4Hd]
     st.site_h = T2_SITE_DEC_H; st.site_c = T2_SITE_DEC_C;
     if (!chain_bwd_plan(d)) return false;
-    size_t xb = 0, pb = 0;
-    chain_bwd_exchange_bytes(d, &xb, &pb);
-    if ((2 * kChainBwdCntBytes + xb + pb + 3) / 4 > c.BL.chain_floats) return false;
-    unsigned char* p = reinterpret_cast<unsigned char*>(c.S(c.BL.chain));
-    d.cnt = reinterpret_cast<unsigned*>(p); p += kChainBwdCntBytes;
-    d.X = p; p += xb;
-    d.PB = p; d.pb_bytes = (unsigned)pb;
-    d.err = reinterpret_cast<unsigned*>(const_cast<float*>(c.a.ws) + c.L.chain) + 2;      // status word 2 of the forward block
+    d.err = status_words(c.a.ws, c.L) + CHAIN_STATUS_BWD_LSTM;
     *out = d;
     return true;
 }
@@ -865,23 +815,7 @@ bool chain_a_bwd_desc(const Bwd& c, ChainBwdDesc* out) {
         }
     }
     if (!chain_bwd_plan(d)) return false;
-    ChainBwdDesc cd{}; cd.kind = CHAIN_LSTM; cd.B = z.B; cd.H = z.Hd;
-    size_t xb0 = 0, pb0 = 0;
-    chain_bwd_exchange_bytes(cd, &xb0, &pb0);
-    size_t xb, ph, pc, dq, cr;
-    const size_t att = chain_bwd_att_exchange_bytes(d, &xb, &ph, &pc, &dq, &cr);
-    if ((2 * kChainBwdCntBytes + xb0 + pb0 + att + 3) / 4 > c.BL.chain_floats) return false;
-    unsigned char* p = reinterpret_cast<unsigned char*>(c.S(c.BL.chain)) + kChainBwdCntBytes + xb0 + pb0;
-    d.cnt = reinterpret_cast<unsigned*>(p); p += kChainBwdCntBytes;
-    d.X = p; p += xb;
-    d.PB = p; p += ph; d.pb_bytes = (unsigned)ph;
-    d.PBC = p; p += pc; d.pbc_bytes = (unsigned)(2 * (size_t)z.NS * 4 * z.B * z.E * sizeof(float));
-    d.DQX = reinterpret_cast<float*>(p); p += dq;
-    d.CARRYX = reinterpret_cast<float*>(p);
-    if (lsa)                                                              // bf16 Wd^T copies behind the tagged part (filled by the caller)
-        for (int s = 0; s < z.NS; ++s)
-            d.st[s].wdt16 = reinterpret_cast<const __bf16*>(p + chain_bwd_lsa_tagged_bytes(d)) + (size_t)s * d.F * d.A;
-    d.err = reinterpret_cast<unsigned*>(const_cast<float*>(c.a.ws) + c.L.chain) + 3;      // status word 3 of the forward block
+    d.err = status_words(c.a.ws, c.L) + CHAIN_STATUS_BWD_ATT;
     *out = d;
     return true;
 }
@@ -1127,11 +1061,8 @@ int t2_decoder_forward(const t2_dims* dims_in, const t2_decoder_weights* w, cons
     ChainDesc ca{}, cb{};
     const bool chain_a = g_chain && chain_a_desc(c, &ca), chain_b = g_chain && chain_b_desc(c, &cb);
     saved_tiles_note(a->ws, chain_a && ca.kind == CHAIN_LSA);
-    {   // status words always (0 = OK / not used); counters and the zero state of step -1 when a chain runs
-        const ChainBufs bufs = chain_bufs(z, L, a->ws);
-        // (the query partials carry step tags: their buffer starts out cleared too)
-        T2_CHECK_HIP(hipMemsetAsync(bufs.err, 0, (chain_a || chain_b) ? 256 + 2 * kChainCntBytes + bufs.xa_bytes + bufs.xb_bytes + kChainXmBytes + bufs.q_bytes : 256, c.s));
-    }
+    // status words always (0 = OK / not used); the tagged exchange buffers (zero state of step -1) when a chain runs
+    T2_TRY(chain_fwd_ws_clear(c.P(L.chain), L.chain_floats, chain_a || chain_b ? CHAIN_WS_TEACHER : CHAIN_WS_STATUS, c.s));
     Side* side = nullptr;
     const bool overlap = g_overlap && z.T >= 32 && !chain_a && !chain_b;
     if (overlap) { T2_TRY(side_get(&side)); c.sd = side->s; }
@@ -1142,7 +1073,7 @@ int t2_decoder_forward(const t2_dims* dims_in, const t2_decoder_weights* w, cons
         if (chain_a) {
             ca.t0 = t0; ca.t1 = t1;
             ProfScope ps(PK_CHAIN_A_FWD, c.s);
-            T2_TRY(chain_fwd(ca, c.s));
+            T2_TRY(chain_fwd(ca, c.P(L.chain), L.chain_floats, c.s));
         } else {
             for (int t = t0; t < t1; ++t) {
                 T2_TRY(att_lstm_step(c, t));
@@ -1164,7 +1095,7 @@ int t2_decoder_forward(const t2_dims* dims_in, const t2_decoder_weights* w, cons
         if (chain_b) {
             cb.t0 = t0; cb.t1 = t1;
             ProfScope ps(PK_CHAIN_B_FWD, sb);
-            T2_TRY(chain_fwd(cb, sb));
+            T2_TRY(chain_fwd(cb, c.P(L.chain), L.chain_floats, sb));
         } else {
             for (int t = t0; t < t1; ++t) T2_TRY(dec_lstm_step(c, t));
         }
@@ -1172,8 +1103,9 @@ int t2_decoder_forward(const t2_dims* dims_in, const t2_decoder_weights* w, cons
     if (overlap) T2_TRY(stream_edge(*side, ne++, side->s, c.s));         // join
     // projections over all frames
     T2_TRY(projection(c, c.P(L.dout), z.WO, BT, a->mel_out, z.M, a->gate_out, 1, true));
-    if (chain_a || chain_b) {            // an aborted chain must not pass for data (its status words: 0 and 1 of the block)
-        hipLaunchKernelGGL(poison_if_aborted_kernel, dim3(64), dim3(256), 0, c.s, chain_bufs(z, L, a->ws).err, 2, a->mel_out, (size_t)BT * z.M, a->gate_out, (size_t)BT);
+    if (chain_a || chain_b) {            // an aborted chain must not pass for data (its status words: CHAIN_STATUS_FWD_ATT and _FWD_LSTM)
+        hipLaunchKernelGGL(poison_if_aborted_kernel, dim3(64), dim3(256), 0, c.s, status_words(a->ws, L), CHAIN_STATUS_FWD_LSTM + 1,
+                           a->mel_out, (size_t)BT * z.M, a->gate_out, (size_t)BT);
         T2_LAUNCH_CHECK();
     }
     return 0;
@@ -1255,7 +1187,7 @@ int t2_decoder_backward(const t2_dims* dims_in, const t2_decoder_weights* w, con
         if (chain_b) {
             cbb.t0 = t0; cbb.t1 = t1;
             ProfScope ps(PK_CHAIN_B_BWD, sb);
-            T2_TRY(chain_bwd(cbb, sb));
+            T2_TRY(chain_bwd(cbb, c.S(BL.chain), BL.chain_floats, sb));
         } else {
             for (int t = t1 - 1; t >= t0; --t) T2_TRY(dec_bwd_step(c, t));
         }
@@ -1297,11 +1229,8 @@ int t2_decoder_backward(const t2_dims* dims_in, const t2_decoder_weights* w, con
         }
         if (chain_a) {
             cab.t0 = t0; cab.t1 = t1;
-            if (cab.kind == CHAIN_LSA)
-                for (int s = 0; s < z.NS; ++s)                            // [A][F] -> bf16 [F][A]
-                    T2_TRY(cast_transpose_bf16(cab.st[s].loc_dense, cab.F, const_cast<__bf16*>(cab.st[s].wdt16), z.A, z.A, cab.F, c.s));
             ProfScope ps(PK_CHAIN_A_BWD, c.s);
-            T2_TRY(chain_bwd(cab, c.s));
+            T2_TRY(chain_bwd(cab, c.S(BL.chain), BL.chain_floats, c.s));
         } else {
             for (int t = t1 - 1; t >= t0; --t) T2_TRY(att_bwd_step(c, t));
         }
@@ -1500,20 +1429,15 @@ int t2_decoder_infer(const t2_dims* dims_in, const t2_decoder_weights* w, const 
     ChainDesc cdec{};
     const bool chain = g_chain && chain_dec_desc(c, *w, *a, &cdec);
     if (chain && a->poll_every <= 0) poll = 32;                      // one persistent launch per polling interval: 32 steps amortise its start-up
-    if (chain) {                                                     // status, counters, zero state of step -1 (h, ctx, dec_h, go-frame prenet = 0)
-        const ChainBufs bufs = chain_bufs(z, L, a->ws);
-        T2_CHECK_HIP(hipMemsetAsync(bufs.err, 0, 256 + 2 * kChainCntBytes + bufs.xa_bytes + bufs.xb_bytes + kChainXmBytes + bufs.q_bytes, c.s));   // (+ the tagged query partials)
-    } else {
-        const ChainBufs bufs = chain_bufs(z, L, a->ws);
-        T2_CHECK_HIP(hipMemsetAsync(bufs.err, 0, 256, c.s));
-        T2_TRY(tail(0, false));                                      // prenet of the go frame (model.py:444-450)
-    }
+    // status words always; with the chain its whole exchange space (zero state of step -1: h, ctx, dec_h, go-frame prenet = 0)
+    T2_TRY(chain_fwd_ws_clear(c.P(L.chain), L.chain_floats, chain ? CHAIN_WS_DECODE : CHAIN_WS_STATUS, c.s));
+    if (!chain) T2_TRY(tail(0, false));                              // prenet of the go frame (model.py:444-450)
     for (int t = 0; t < T; ++t) {
         if (chain) {
             if (t % poll == 0) {                                     // one persistent launch per polling interval
                 cdec.t0 = t; cdec.t1 = std::min(T, t + poll);
                 ProfScope ps(PK_CHAIN_DEC, c.s);
-                T2_TRY(chain_fwd(cdec, c.s));
+                T2_TRY(chain_fwd(cdec, c.P(L.chain), L.chain_floats, c.s));
             }
         } else {
             T2_TRY(att_lstm_step(c, t));
@@ -1539,7 +1463,8 @@ int t2_decoder_infer(const t2_dims* dims_in, const t2_decoder_weights* w, const 
     }
     *a->steps_run_host = steps;
     if (chain) {
-        hipLaunchKernelGGL(poison_if_aborted_kernel, dim3(64), dim3(256), 0, c.s, chain_bufs(z, L, a->ws).err, 1, a->mel_out, (size_t)z.B * T * z.M, a->gate_out, (size_t)z.B * T);
+        hipLaunchKernelGGL(poison_if_aborted_kernel, dim3(64), dim3(256), 0, c.s, status_words(a->ws, L), CHAIN_STATUS_FWD_ATT + 1,
+                           a->mel_out, (size_t)z.B * T * z.M, a->gate_out, (size_t)z.B * T);
         T2_LAUNCH_CHECK();
     }
     return 0;

@@ -11,12 +11,13 @@
 //   h_t   (bf16, MFMA-fragment order)        units -> every workgroup of the same stream and row group
 //   q_t   (fp32 partial query projections)   units -> the item's attention workgroups
 //   ctx_t (bf16, MFMA-fragment order)        items -> every LSTM workgroup of the same stream and row group
-// exchanged through L2-bypassing write-through stores (sc1) and sc1 loads.  Decode loop: one arrival counter per (stream,
-// row group, kind) — MI355X_MICROARCH.md "Valid forms": every payload store drained by every storing wave before the
-// workgroup barrier, one lane signals with an agent-scope atomic, one wave polls with relaxed agent loads, the other waves
-// load behind the workgroup barrier (scripts/persist_probe.hip measures this pattern).  Teacher-forced chains (round 3): NO
-// counters — every 16-byte unit carries a step tag in the lowest bit of its first word, the buffers are cleared per launch,
-// a consumer loads until its units show the step's tag (see TAG / TAGQ in the kernel): one round trip per hop, two hops per step.
+// exchanged through L2-bypassing write-through stores (sc1) and sc1 loads.  Teacher-forced chains: no counters — every
+// 16-byte unit carries a step tag in the lowest bit of its first word, the buffers are cleared before the chain starts, a
+// consumer loads until its units show the step's tag: one round trip per hop, two hops per step.  Decode loop: one arrival
+// counter per (stream, row group, kind) — MI355X_MICROARCH.md "Valid forms": every payload store drained by every storing
+// wave before the workgroup barrier, one lane signals with an agent-scope atomic, one wave polls with relaxed agent loads,
+// the other waves load behind the workgroup barrier (scripts/persist_probe.hip measures this pattern); only its query
+// partials carry tags instead.
 //
 // Work items (one workgroup of 512 threads per CU, grid = 256):
 //   L item (s, ug, rg): stream s, unit group ug (8*UT hidden units = 32*UT gate columns), row group rg (32*RT batch rows).
@@ -112,20 +113,12 @@ template <int UT, int RT, int KH, int KC, int KIND, int KPN = 0>
 __global__ __launch_bounds__(NTH) void chain_fwd_kernel(ChainDesc d) {
     constexpr int NTILE = UT * RT, NSLOT = (NTILE + 1) / 2, HSP = UT * 8 + 4;
     constexpr bool DEC = KPN > 0;                       // decode loop: prenet segment in the LSTM product + decoder LSTM, projections, prenets in the launch
-    // Teacher-forced chains (every kind): NO arrival counters.  Fragments of step t carry bit 1 of t (inverted) in the lowest bit of
-    // their first word, the exchange buffers are cleared per launch, and a consumer loads its fragments and loads them again until
-    // they show the step's tag (bounded): one round trip per hop instead of a counter poll followed by the loads, no drain and no
-    // atomic on the producer's side.  (Round 3, first try: tags checked BEHIND the polls — the attention kinds, at the 256-register
-    // cap, spilled 32-58 registers and got slower; without the polls they spill 3-8 and gain 0.6 us per step.)  The decode loop
-    // keeps the drained protocol with counters (its 8-byte dec_h pieces and five hops are not converted).
-    constexpr bool TAG = !DEC;
-    // Attention kinds, teacher-forced: the QUERY PARTIALS alone are tagged (bit 0 of the step count, inverted, in the first word of every
-    // 16-byte unit; one buffer, rewritten every step, cleared per launch).  The A items then do not poll the h counter at all: they
-    // load the partials and load again until the tags are this step's — one round trip instead of two behind the L items' publish,
-    // and not behind its drain.  (The L items poll the h counter themselves, inside their wait for the contexts.)
-    constexpr bool TAGQ = KIND != CHAIN_LSTM;             // (the decode loop too: its A items have just finished their L items — a short wait)
-    auto tag_x = [](int step) { return (unsigned)(((step >> 1) & 1) ^ 1); };
-    auto tag_q = [](int step) { return (unsigned)((step & 1) ^ 1); };
+    // Hand-offs.  Decode loop: arrival counters (chain_common.h: poll_counter / publish) on every hop but the query partials.
+    // Teacher-forced chains (every kind): no counters — fragments of step t carry step_tag(t) in the lowest bit of their first
+    // word, the exchange buffers are cleared before the chain starts, and a consumer loads its fragments and loads them again
+    // until they show the step's tag (bounded).  Query partials (attention kinds, the decode loop too): tag_q(t) in the first word
+    // of every 16-byte unit (one buffer, rewritten every step); the A items load them until the tags are this step's.
+    auto tag_q = [](int step) { return (unsigned)((step & 1) ^ 1); };                // bit 0 of the step, inverted
     const Geo G = geo_of(d, UT, RT);
     const int wg = blockIdx.x, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, r = lane & 31, hk = lane >> 5;
     const int B = d.B, H = d.H, A = d.A;
@@ -166,10 +159,10 @@ __global__ __launch_bounds__(NTH) void chain_fwd_kernel(ChainDesc d) {
 
     auto rsX = __builtin_amdgcn_make_buffer_rsrc(d.X, 0, (int)(2u * d.NS * G.xs_bytes), 0x00020000);
     auto rsQ = __builtin_amdgcn_make_buffer_rsrc(d.Q, 0, (int)d.q_bytes, 0x00020000);
-    unsigned* cntH_L = d.cnt + (size_t)((ls * G.NRG + rg) * 2 + 0) * CNT_STRIDE;
-    unsigned* cntC_L = d.cnt + (size_t)((ls * G.NRG + rg) * 2 + 1) * CNT_STRIDE;
-    unsigned* cntH_A = d.cnt + (size_t)((as * G.NRG + arg) * 2 + 0) * CNT_STRIDE;
-    unsigned* cntC_A = d.cnt + (size_t)((as * G.NRG + arg) * 2 + 1) * CNT_STRIDE;
+    // decode loop: arrival counters of the L item's row group (h, ctx) and of the A item's (ctx)
+    unsigned* cntH_L = DEC ? d.cnt + (size_t)((ls * G.NRG + rg) * 2 + 0) * CNT_STRIDE : nullptr;
+    unsigned* cntC_L = DEC ? d.cnt + (size_t)((ls * G.NRG + rg) * 2 + 1) * CNT_STRIDE : nullptr;
+    unsigned* cntC_A = DEC ? d.cnt + (size_t)((as * G.NRG + arg) * 2 + 1) * CNT_STRIDE : nullptr;
     const unsigned rows_in_rg = (unsigned)min(32 * RT, B - row0);      // valid rows of the L item's row group
     const unsigned nA_per_step = rows_in_rg * (unsigned)d.CS;
 
@@ -282,7 +275,7 @@ __global__ __launch_bounds__(NTH) void chain_fwd_kernel(ChainDesc d) {
     auto gemm_part = [&](int step, int rt, int kt0, int i0, auto nk) {
         constexpr int NK = decltype(nk)::value;
         u32x4 af[NK > 0 ? NK : 1];
-        const bool chk = TAG && step >= d.t0;               // (fragments of step t0 - 1: a finished launch or the zero state)
+        const bool chk = !DEC && step >= d.t0;              // (fragments of step t0 - 1: a finished launch or the zero state)
         const bool rowpad = min(rg * RT + rt, G.MT - 1) * 32 + (int)(threadIdx.x & 31) >= B;
         const unsigned long long tsp = chk ? __builtin_amdgcn_s_memrealtime() : 0ull;
         for (;;) {
@@ -290,7 +283,7 @@ __global__ __launch_bounds__(NTH) void chain_fwd_kernel(ChainDesc d) {
 #pragma unroll
             for (int i = 0; i < NK; ++i) {
                 af[i] = __builtin_amdgcn_raw_buffer_load_b128(rsX, frag_offset(step, rt, kt0 + i), 0, SC1);
-                okw &= ((af[i].x & 1u) == tag_x(step) || rowpad) ? 1u : 0u;   // (ctx units of padding rows are never written; h fragments: every row is)
+                okw &= ((af[i].x & 1u) == step_tag(step) || rowpad) ? 1u : 0u;   // (ctx units of padding rows are never written; h fragments: every row is)
             }
             if (!chk || __all(okw != 0u)) break;
             if (__builtin_amdgcn_s_memrealtime() - tsp > SPIN_TICKS) { if ((threadIdx.x & 63) == 0) { report_abort(d.err, 17u); *abortw = 1; } break; }
@@ -310,12 +303,12 @@ __global__ __launch_bounds__(NTH) void chain_fwd_kernel(ChainDesc d) {
         for (int i = 0; i < (EARLY ? KH : 1); ++i) hf[i] = __builtin_amdgcn_raw_buffer_load_b128(rsX, frag_offset(step, 0, wave * KH + i), 0, SC1);
     };
     auto mfma_h = [&](int step) {
-        if (TAG && step >= d.t0) {                          // requested before the wait for the contexts: long landed, but checked like every fragment
+        if (!DEC && step >= d.t0) {                         // requested before the wait for the contexts: long landed, but checked like every fragment
             const unsigned long long tsp = __builtin_amdgcn_s_memrealtime();
             for (;;) {
                 unsigned okw = 1u;
 #pragma unroll
-                for (int i = 0; i < (EARLY ? KH : 1); ++i) okw &= ((hf[i].x & 1u) == tag_x(step)) ? 1u : 0u;
+                for (int i = 0; i < (EARLY ? KH : 1); ++i) okw &= ((hf[i].x & 1u) == step_tag(step)) ? 1u : 0u;
                 if (__all(okw != 0u)) break;
                 if (__builtin_amdgcn_s_memrealtime() - tsp > SPIN_TICKS) { if ((threadIdx.x & 63) == 0) { report_abort(d.err, 18u); *abortw = 1; } break; }
                 issue_h(step);
@@ -475,18 +468,17 @@ __global__ __launch_bounds__(NTH) void chain_fwd_kernel(ChainDesc d) {
 #pragma unroll
                 for (int g = 0; g < 4; ++g) pre[sl][g] = pre_next[sl][g];
             T2_CSTAMP(15);
-            if ((!EARLY || !hasA || TAGQ) && !TAG) {   // (decode loop: an attention item's workgroup has polled this counter in its A phase;
-                                                        //  decoder-LSTM chain: no counter at all, the h fragments are loaded until they carry this step's tag)
+            if (DEC) {                                  // (teacher-forced: the h fragments are loaded until they carry the step's tag)
                 if (wave == 0 && !poll_counter(cntH_L, ep, (unsigned)G.NUG, d.err, 1u) && lane == 0) *abortw = 1;
                 __syncthreads();
                 if (*abortw) return;
             }
             T2_CSTAMP(0);
             if (EARLY) issue_h(t - 1);
-            if (KC > 0 && !TAG) {
+            if (DEC) {
                 if (wave == 0) {
                     bool ok = poll_counter(cntC_L, ep, nA_per_step, d.err, 2u);
-                    if (ok && DEC) ok = poll_counter(d.cnt + (size_t)(10 + ls) * CNT_STRIDE, ep, (unsigned)(d.P / 16), d.err, 11u);   // prenet output of this step
+                    if (ok) ok = poll_counter(d.cnt + (size_t)(10 + ls) * CNT_STRIDE, ep, (unsigned)(d.P / 16), d.err, 11u);   // prenet output of this step
                     if (!ok && lane == 0) *abortw = 1;
                 }
                 __syncthreads();
@@ -550,7 +542,7 @@ __global__ __launch_bounds__(NTH) void chain_fwd_kernel(ChainDesc d) {
 #pragma unroll
                     for (int j = 0; j < 4; ++j) { o[j] = (__bf16)lo[j]; o[4 + j] = (__bf16)hi[j]; }
                     u32x4 ow = __builtin_bit_cast(u32x4, o);
-                    if (TAG) ow.x = (ow.x & ~1u) | tag_x(t);
+                    if (!DEC) ow.x = (ow.x & ~1u) | step_tag(t);
                     __builtin_amdgcn_raw_buffer_store_b128(ow, rsX,
                         xout + (unsigned)ls * G.xs_bytes + (unsigned)((((u0 >> 4) * G.MT + rtg) * 64 + kh8 * 32 + r) * 16), 0, SC1);
                 }
@@ -574,12 +566,12 @@ __global__ __launch_bounds__(NTH) void chain_fwd_kernel(ChainDesc d) {
                     const int row = i / (A / 4), a4 = (i % (A / 4)) * 4;
                     const f32x4 v4 = *reinterpret_cast<const f32x4*>(qsL + row * (A + 4) + a4);
                     u32x4 vw = __builtin_bit_cast(u32x4, v4);
-                    if (TAGQ) vw.x = (vw.x & ~1u) | tag_q(t);          // (absolute step: the decode loop's launches continue each other)
+                    vw.x = (vw.x & ~1u) | tag_q(t);                    // (absolute step: the decode loop's launches continue each other)
                     __builtin_amdgcn_raw_buffer_store_b128(vw, rsQ, qb + (unsigned)((row * A + a4) * 4), 0, SC1);
                 }
             }
             T2_CSTAMP(4);
-            if (TAG) { __syncthreads(); if (*abortw) return; } else publish(cntH_L, (unsigned)ug);   // (TAG: no arrival counter, the fragments carry the step's tag)
+            if (DEC) publish(cntH_L, (unsigned)ug); else { __syncthreads(); if (*abortw) return; }
             T2_CSTAMP(5);
             // saved activations: issued here, in the slack before the next poll is answered (issuing scattered stores costs
             // the wave hundreds of cycles; behind the next phase's loads they sat on the critical path: measured +1.2 us/step)
@@ -642,14 +634,7 @@ __global__ __launch_bounds__(NTH) void chain_fwd_kernel(ChainDesc d) {
                     }
                 }
             }
-            // (LSA: the last wave polls — it has no tile of the location conv above (4 tiles at Tin <= 128), so the poll's round trip
-            // runs underneath the other waves' MFMA chains instead of behind them)
-            if (!TAGQ && wave == (KIND == CHAIN_LSA ? NWV - 1 : 0)) {   // h_t of the item's row group, and (one request) of the L item's for step t+1
-                const bool ok = (EARLY && hasL && more) ? poll_counters2(cntH_A, ep + 1, (unsigned)G.NUG, cntH_L, ep + 1, (unsigned)G.NUG, d.err, 3u)
-                                                        : poll_counter(cntH_A, ep + 1, (unsigned)G.NUG, d.err, 3u);
-                if (!ok && lane == 0) *abortw = 1;
-            }
-            if (!TAGQ || KIND == CHAIN_LSA) __syncthreads();       // (LSA: the conv's bf16 pair is complete behind this barrier)
+            if (KIND == CHAIN_LSA) __syncthreads();                 // (the conv's bf16 pair is complete behind this barrier)
             if (*abortw) return;
             T2_CSTAMP(7);
             // ---- query = ordered sum of the unit groups' partials.  Request order: query partials (needed now), h fragments
@@ -661,7 +646,7 @@ __global__ __launch_bounds__(NTH) void chain_fwd_kernel(ChainDesc d) {
                 u32x4 pv[QU];
                 // (tagged hand-off: a partial that still shows last step's tag has not landed yet: load the batch again)
                 auto load_q = [&](int i0) {
-                    const unsigned long long tsp = TAGQ ? __builtin_amdgcn_s_memrealtime() : 0ull;
+                    const unsigned long long tsp = __builtin_amdgcn_s_memrealtime();
                     for (;;) {
                         unsigned okw = 1u;
 #pragma unroll
@@ -669,7 +654,7 @@ __global__ __launch_bounds__(NTH) void chain_fwd_kernel(ChainDesc d) {
                             pv[k] = __builtin_amdgcn_raw_buffer_load_b128(rsQ, qb + (unsigned)min(i0 + 16 * k, G.NUG - 1) * (unsigned)(32 * RT * A * 4), 0, SC1);
                             okw &= ((pv[k].x & 1u) == tag_q(t)) ? 1u : 0u;
                         }
-                        if (!TAGQ || __all(okw != 0u)) break;
+                        if (__all(okw != 0u)) break;
                         if (__builtin_amdgcn_s_memrealtime() - tsp > SPIN_TICKS) { if ((tid & 63) == 0) { report_abort(d.err, 19u); *abortw = 1; } break; }
                     }
                 };
@@ -905,12 +890,12 @@ __global__ __launch_bounds__(NTH) void chain_fwd_kernel(ChainDesc d) {
                 for (int j = 0; j < 4; ++j) { o[j] = (__bf16)lo[j]; o[4 + j] = (__bf16)hi[j]; }
                 const int kt = H / 16 + pc / 2;
                 u32x4 ow = __builtin_bit_cast(u32x4, o);
-                if (TAG) ow.x = (ow.x & ~1u) | tag_x(t);
+                if (!DEC) ow.x = (ow.x & ~1u) | step_tag(t);
                 __builtin_amdgcn_raw_buffer_store_b128(ow, rsX,
                     xout + (unsigned)as * G.xs_bytes + (unsigned)(((kt * G.MT + ab_ / 32) * 64 + (pc & 1) * 32 + (ab_ & 31)) * 16), 0, SC1);
             }
             T2_CSTAMP(11);
-            if (TAG) { __syncthreads(); if (*abortw) return; } else publish(cntC_A, (unsigned)(arow * d.CS + part));
+            if (DEC) publish(cntC_A, (unsigned)(arow * d.CS + part)); else { __syncthreads(); if (*abortw) return; }
             T2_CSTAMP(12);
             store_A_saved(t, tid);
         }
@@ -1143,6 +1128,31 @@ int chain_device_cus() {
     return c;
 }
 
+// Exchange space of a forward pass (chain_fwd_ws_floats), every part sized for the largest tiling chain_plan can choose:
+//   [status words | query partials | fragments of the attention chain ...... fragments of the decoder-LSTM chain | mel fragments | counters]
+// The attention chain's parts are carved from the front, the decoder-LSTM chain's (decode loop: dec_h) from the back, so that each
+// chain finds its own from its descriptor; the mel fragments and the arrival counters are the decode loop's.
+static constexpr size_t kStatusBytes = 256;                                        // ChainStatus words (kernels.h)
+static constexpr size_t kXmBytes = 16 * 1024;                                      // mel fragments [2][8][1 KB]
+static constexpr size_t kCntBytes = (size_t)16 * CNT_STRIDE * sizeof(unsigned);    // counters 0-3 (h / ctx of each stream), 8 (dec_h), 9 (mel), 10-11 (prenets)
+// fragment-ordered operands of a K-wide product: [parity][stream][k tile of 16][row tile of 32][1 KB]
+static size_t x_part_bytes(int NS, int B, int K) { return (size_t)2 * NS * (K / 16) * ((B + 31) / 32) * 1024; }
+// query partials: one 32-row tile per 32 batch rows, one unit group per 8 hidden units
+static size_t q_part_bytes(int NS, int B, int H, int A) { return (size_t)NS * ((B + 31) / 32) * 32 * (H / 8) * A * sizeof(float); }
+// query partials of a tiling: [stream][row group][unit group][32 RT rows][A]
+static size_t q_bytes_of(const ChainDesc& d, const Geo& g) { return (size_t)d.NS * g.NRG * g.NUG * 32 * d.RT * d.A * sizeof(float); }
+
+size_t chain_fwd_ws_floats(int NS, int B, int Ha, int E, int P, int Hd, int A) {
+    return (kStatusBytes + q_part_bytes(NS, B, Ha, A) + x_part_bytes(NS, B, Ha + E + P) + x_part_bytes(1, B, Hd) + kXmBytes + kCntBytes) / sizeof(float);
+}
+
+int chain_fwd_ws_clear(float* ws, size_t ws_floats, ChainWsClear what, hipStream_t s) {
+    const size_t bytes = ws_floats * sizeof(float);
+    T2_REQUIRE(ws && bytes >= kStatusBytes + kXmBytes + kCntBytes, "chain_fwd_ws_clear: exchange space too small");
+    T2_CHECK_HIP(hipMemsetAsync(ws, 0, what == CHAIN_WS_STATUS ? kStatusBytes : what == CHAIN_WS_TEACHER ? bytes - kXmBytes - kCntBytes : bytes, s));
+    return 0;
+}
+
 // Picks the tiling for a shape; returns false when the persistent kernel does not cover it.
 bool chain_plan(ChainDesc& d) {
     if (d.H != 1024 || d.B < 1 || d.B > 128) return false;
@@ -1161,6 +1171,8 @@ bool chain_plan(ChainDesc& d) {
     const Geo g = geo_of(d, d.UT, d.RT);
     if (g.nL > 256 || g.nA > 256) return false;
     if (chain_device_cus() < 256 || !chain_device_claim()) return false;
+    // (one stream at 65-96 rows: two row groups of two row tiles pad the query partials beyond their part of the exchange space)
+    if (d.kind != CHAIN_LSTM && q_bytes_of(d, g) > q_part_bytes(d.NS, d.B, d.H, d.A)) return false;
     // LDS residency: processed-memory rows first, then (bf16) memory rows, in what the largest stream leaves free
     const int budget = (160 * 1024 - 256) / 4;
     int tmax = 4;
@@ -1182,13 +1194,6 @@ bool chain_plan(ChainDesc& d) {
     return true;
 }
 
-size_t chain_exchange_bytes(const ChainDesc& d, size_t* x_bytes, size_t* q_bytes) {
-    const Geo g = geo_of(d, d.UT, d.RT);
-    *x_bytes = (size_t)2 * d.NS * g.xs_bytes;
-    *q_bytes = d.kind == CHAIN_LSTM ? 16 : (size_t)d.NS * g.NRG * g.NUG * 32 * d.RT * d.A * 4;
-    return *x_bytes + *q_bytes;
-}
-
 template <int UT, int RT, int KC, int KIND, int KPN = 0>
 static int chain_launch(const ChainDesc& d, hipStream_t s) {
     const Lds m = lds_of(d, UT, RT, d.lds_Tin, d.lds_Jp, d.lds_Jm);
@@ -1197,22 +1202,36 @@ static int chain_launch(const ChainDesc& d, hipStream_t s) {
     const Geo g = geo_of(d, UT, RT);
     const int grid = KPN > 0 ? 256 : std::max(g.nL, g.nA);
     T2_TRY_RC(persistent_prepare(kernel, grid, smem));
-    T2_CHECK_HIP(hipMemsetAsync(d.cnt, 0, KPN > 0 ? kChainCntBytes : (size_t)d.NS * g.NRG * 2 * CNT_STRIDE * sizeof(unsigned), s));
+    if (KPN > 0) T2_CHECK_HIP(hipMemsetAsync(d.cnt, 0, kCntBytes, s));         // (the decode loop's counters count the steps of one launch)
     hipLaunchKernelGGL(kernel, dim3(grid), dim3(NTH), smem, s, d);
     T2_LAUNCH_CHECK();
     return 0;
 }
 
-int chain_fwd(const ChainDesc& d, hipStream_t s) {
+int chain_fwd(ChainDesc d, float* ws, size_t ws_floats, hipStream_t s) {
     T2_REQUIRE(d.t1 > d.t0 && d.t0 >= 0, "chain_fwd: bad step range [%d,%d)", d.t0, d.t1);
-    T2_REQUIRE(d.X && d.cnt && d.err && (d.kind == CHAIN_LSTM || d.Q), "chain_fwd: exchange buffers missing");
+    const size_t bytes = ws_floats * sizeof(float);
+    T2_REQUIRE(ws && d.err && bytes >= kStatusBytes + kXmBytes + kCntBytes, "chain_fwd: exchange space or status word missing");
+    unsigned char* const front = reinterpret_cast<unsigned char*>(ws) + kStatusBytes;
+    unsigned char* const back = reinterpret_cast<unsigned char*>(ws) + bytes - kXmBytes - kCntBytes;
     if (d.kind == CHAIN_LSTM) {
+        d.X = back - x_part_bytes(1, d.B, d.H);
+        T2_REQUIRE(d.X >= front, "chain_fwd: exchange space too small");
         if (d.RT == 1) return chain_launch<1, 1, 0, CHAIN_LSTM>(d, s);
         return chain_launch<1, 2, 0, CHAIN_LSTM>(d, s);
     }
     T2_REQUIRE(d.kind == CHAIN_SMA || d.kind == CHAIN_LSA, "chain_fwd: attention kind %d not covered", d.kind);
+    // (the attention chain's descriptor carries the pass's whole shape, P and Hd included: a space of at least the size
+    //  chain_fwd_ws_floats gives it keeps the parts carved below clear of the decoder-LSTM chain's part at the back)
+    T2_REQUIRE(bytes >= chain_fwd_ws_floats(d.NS, d.B, d.H, d.E, d.P, d.Hd, d.A) * sizeof(float), "chain_fwd: exchange space too small");
+    const Geo g = geo_of(d, d.UT, d.RT);
+    d.Q = reinterpret_cast<float*>(front); d.q_bytes = (unsigned)q_bytes_of(d, g);
+    d.X = front + q_part_bytes(d.NS, d.B, d.H, d.A);
+    T2_REQUIRE(d.q_bytes <= q_part_bytes(d.NS, d.B, d.H, d.A) && (size_t)2 * d.NS * g.xs_bytes <= x_part_bytes(d.NS, d.B, d.H + d.E + d.P),
+               "chain_fwd: tiling UT=%d RT=%d outgrows its exchange buffers", d.UT, d.RT);
     if (d.dec) {
-        T2_REQUIRE(d.UT == 1 && d.RT == 1 && d.XD && d.XM, "chain_fwd: decode loop needs one row tile and its exchange buffers");
+        d.XD = back - x_part_bytes(1, d.B, d.Hd); d.XM = back; d.cnt = reinterpret_cast<unsigned*>(back + kXmBytes);
+        T2_REQUIRE(d.UT == 1 && d.RT == 1, "chain_fwd: the decode loop needs one row tile");
         return d.kind == CHAIN_LSA ? chain_launch<1, 1, 4, CHAIN_LSA, 2>(d, s) : chain_launch<1, 1, 4, CHAIN_SMA, 2>(d, s);
     }
     if (d.kind == CHAIN_LSA) {

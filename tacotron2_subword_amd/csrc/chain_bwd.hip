@@ -1202,7 +1202,32 @@ __global__ __launch_bounds__(NTH) void chain_bwd_att_kernel(ChainBwdDesc d) {
     }
 }
 
+// Exchange space of the backward pass (chain_bwd_ws_floats): the attention chain's parts from the front — dg fragments, h and ctx
+// K-split partials, dq partials, boundary carries (all of them tagged), then (LSA) the bf16 Wd^T copies — and the decoder-LSTM
+// chain's from the back — dg fragments, K-split partials — so that each chain finds its own from its descriptor.
+size_t al256(size_t n) { return (n + 255) & ~(size_t)255; }
+struct AttParts { size_t x, pbh, pbc, dqx, carry, wdt; };
+AttParts att_parts(int kind, int NS, int B, int H, int E, int A, int F, int Kc) {
+    const size_t MT = (B + 31) / 32;
+    AttParts p;
+    p.x = (size_t)2 * NS * (4 * H / 16) * MT * 1024;
+    p.pbh = (size_t)2 * NS * AKP * (H / PU) * MT * 32 * PU * sizeof(float);
+    p.pbc = al256((size_t)2 * NS * AKP * B * E * sizeof(float));
+    p.dqx = al256((size_t)NS * 2 * B * A * sizeof(float));
+    // SMA: one carry per (parity, stream, item); LSA: halo rows of dloc and softmax-dot slots (rsK in chain_bwd_att_kernel)
+    p.carry = al256(kind == CHAIN_LSA ? (size_t)(((Kc - 1) / 2) * F + 2) * 2 * NS * B * 2 * sizeof(float) : (size_t)2 * NS * B * sizeof(float));
+    p.wdt = kind == CHAIN_LSA ? al256((size_t)NS * F * A * sizeof(__bf16)) : 0;
+    return p;
+}
+size_t lstm_x_bytes(int B, int H) { return (size_t)2 * (4 * H / 16) * ((B + 31) / 32) * 1024; }                           // [2][4H/16][MT][1 KB]
+size_t lstm_pb_bytes(int B, int H) { return (size_t)2 * GKP * (H / PU) * ((B + 31) / 32) * 32 * PU * sizeof(float); }     // [2][GKP][H/PU][MT][32][PU]
+
 }  // namespace
+
+size_t chain_bwd_ws_floats(int kind, int NS, int B, int Ha, int E, int A, int F, int Kc, int Hd) {
+    const AttParts p = att_parts(kind, NS, B, Ha, E, A, F, Kc);
+    return (p.x + p.pbh + p.pbc + p.dqx + p.carry + p.wdt + lstm_x_bytes(B, Hd) + lstm_pb_bytes(B, Hd)) / sizeof(float);
+}
 
 bool chain_bwd_plan(ChainBwdDesc& d) {
     if (d.H != 1024 || d.B < 1 || d.B > 64) return false;
@@ -1225,55 +1250,29 @@ bool chain_bwd_plan(ChainBwdDesc& d) {
     return (size_t)bwd_lds_of(d.A, d.E, tc, (d.B + 31) / 32, d.kind, d.F, d.Kc).total * sizeof(float) <= 160 * 1024;
 }
 
-size_t chain_bwd_exchange_bytes(const ChainBwdDesc& d, size_t* x_bytes, size_t* pb_bytes) {
-    const size_t MT = (d.B + 31) / 32;
-    *x_bytes = (size_t)2 * (4 * d.H / 16) * MT * 1024;
-    *pb_bytes = (size_t)2 * GKP * (d.H / PU) * MT * 32 * PU * sizeof(float);
-    return *x_bytes + *pb_bytes;
-}
-
-size_t chain_bwd_lsa_tagged_bytes(const ChainBwdDesc& d) {
-    return ((size_t)(((d.Kc - 1) / 2) * d.F + 2) * 2 * d.NS * d.B * 2 * sizeof(float) + 255) & ~(size_t)255;
-}
-
-size_t chain_bwd_att_exchange_bytes(const ChainBwdDesc& d, size_t* x_bytes, size_t* pbh_bytes, size_t* pbc_bytes, size_t* dqx_bytes, size_t* carry_bytes) {
-    const size_t MT = (d.B + 31) / 32, al = 255;
-    *x_bytes = (size_t)2 * d.NS * (4 * d.H / 16) * MT * 1024;
-    *pbh_bytes = (size_t)2 * d.NS * AKP * (d.H / PU) * MT * 32 * PU * sizeof(float);
-    *pbc_bytes = ((size_t)2 * d.NS * AKP * d.B * d.E * sizeof(float) + al) & ~al;
-    *dqx_bytes = ((size_t)d.NS * 2 * d.B * d.A * sizeof(float) + al) & ~al;
-    *carry_bytes = ((size_t)2 * d.NS * d.B * sizeof(float) + al) & ~al;
-    if (d.kind == CHAIN_LSA)      // halo rows + softmax-dot slots (cleared per launch), then the bf16 Wd^T copies [NS][F][A]
-        *carry_bytes = chain_bwd_lsa_tagged_bytes(d) + (((size_t)d.NS * d.F * d.A * sizeof(__bf16) + al) & ~al);
-    return *x_bytes + *pbh_bytes + *pbc_bytes + *dqx_bytes + *carry_bytes;
-}
-
-int chain_bwd(const ChainBwdDesc& d, hipStream_t s) {
+int chain_bwd(ChainBwdDesc d, float* ws, size_t ws_floats, hipStream_t s) {
     T2_REQUIRE(d.t1 > d.t0 && d.t0 >= 0, "chain_bwd: bad step range [%d,%d)", d.t0, d.t1);
-    T2_REQUIRE(d.X && d.PB && d.cnt && d.err, "chain_bwd: exchange buffers missing");
+    T2_REQUIRE(ws && d.err, "chain_bwd: exchange space or status word missing");
     const int MT = (d.B + 31) / 32;
-    T2_CHECK_HIP(hipMemsetAsync(d.cnt, 0, kChainBwdCntBytes, s));
+    unsigned char* const base = reinterpret_cast<unsigned char*>(ws);
+    const size_t bytes = ws_floats * sizeof(float);
     if (d.kind == CHAIN_SMA || d.kind == CHAIN_LSA) {
         T2_REQUIRE(d.t0 == 0 && d.t1 == d.T, "chain_bwd: the attention chain runs its whole step range in one launch");
-        T2_REQUIRE(d.PBC && d.DQX && d.CARRYX, "chain_bwd: exchange buffers missing");
+        const AttParts p = att_parts(d.kind, d.NS, d.B, d.H, d.E, d.A, d.F, d.Kc);
+        const size_t tagged = p.x + p.pbh + p.pbc + p.dqx + p.carry;
+        T2_REQUIRE(tagged + p.wdt <= bytes, "chain_bwd: exchange space too small");
+        d.X = base; d.PB = d.X + p.x; d.PBC = d.PB + p.pbh;
+        d.DQX = reinterpret_cast<float*>(d.PBC + p.pbc); d.CARRYX = reinterpret_cast<float*>(d.PBC + p.pbc + p.dqx);
+        d.pb_bytes = (unsigned)p.pbh; d.pbc_bytes = (unsigned)((size_t)2 * d.NS * AKP * d.B * d.E * sizeof(float));
+        T2_CHECK_HIP(hipMemsetAsync(base, 0, tagged, s));           // every buffer but Wd^T carries step tags (tag 0 = not written yet)
+        if (d.kind == CHAIN_LSA)
+            for (int i = 0; i < d.NS; ++i) {                            // loc_dense [A][F] -> bf16 [F][A]
+                __bf16* wdt = reinterpret_cast<__bf16*>(base + tagged) + (size_t)i * d.F * d.A;
+                T2_TRY_RC(cast_transpose_bf16(d.st[i].loc_dense, d.F, wdt, d.A, d.A, d.F, s));
+                d.st[i].wdt16 = wdt;
+            }
         const size_t smem = (size_t)bwd_lds_of(d.A, d.E, d.lds_Tc, MT, d.kind, d.F, d.Kc).total * sizeof(float);
         const int grid = std::max(std::max(d.NS * (d.E + d.H) / ANC * AKP, d.NS * (d.H / PU) * MT), d.NS * d.B * 2);
-        {   // every exchange buffer carries step tags (tag 0 = not written yet): clear them
-            size_t xb, ph, pc, dq, cr;
-            chain_bwd_att_exchange_bytes(d, &xb, &ph, &pc, &dq, &cr);
-            const size_t carry = d.kind == CHAIN_LSA ? chain_bwd_lsa_tagged_bytes(d) : cr;      // (LSA: the caller's bf16 Wd^T copies follow)
-            unsigned char* c0 = reinterpret_cast<unsigned char*>(d.cnt);
-            if (d.X == c0 + kChainBwdCntBytes && d.PB == d.X + xb && d.PBC == d.PB + ph && reinterpret_cast<unsigned char*>(d.DQX) == d.PBC + pc &&
-                reinterpret_cast<unsigned char*>(d.CARRYX) == reinterpret_cast<unsigned char*>(d.DQX) + dq) {
-                T2_CHECK_HIP(hipMemsetAsync(d.X, 0, xb + ph + pc + dq + carry, s));             // (one region, as c_api.hip lays it out)
-            } else {
-                T2_CHECK_HIP(hipMemsetAsync(d.X, 0, xb, s));
-                T2_CHECK_HIP(hipMemsetAsync(d.PB, 0, ph, s));
-                T2_CHECK_HIP(hipMemsetAsync(d.PBC, 0, pc, s));
-                T2_CHECK_HIP(hipMemsetAsync(d.DQX, 0, dq, s));
-                T2_CHECK_HIP(hipMemsetAsync(d.CARRYX, 0, carry, s));
-            }
-        }
         auto launch = [&](auto kernel) -> int {
             T2_TRY_RC(persistent_prepare(kernel, grid, smem));
             hipLaunchKernelGGL(kernel, dim3(grid), dim3(NTH), smem, s, d);
@@ -1288,11 +1287,10 @@ int chain_bwd(const ChainBwdDesc& d, hipStream_t s) {
     }
     T2_REQUIRE(d.kind == CHAIN_LSTM, "chain_bwd: kind %d not covered", d.kind);
     T2_REQUIRE(d.t1 == d.T, "chain_bwd: the decoder-LSTM chain runs its whole step range in one launch (tagged hand-offs count steps from the launch)");
-    {   // tagged hand-offs: fragments and partials start out with tag 0 (= invalid for the first two steps)
-        size_t xb = 0, pb = 0;
-        chain_bwd_exchange_bytes(d, &xb, &pb);
-        T2_CHECK_HIP(hipMemsetAsync(d.X, 0, xb + pb, s));
-    }
+    const size_t xb = lstm_x_bytes(d.B, d.H), pb = lstm_pb_bytes(d.B, d.H);
+    T2_REQUIRE(xb + pb <= bytes, "chain_bwd: exchange space too small");
+    d.X = base + bytes - xb - pb; d.PB = d.X + xb; d.pb_bytes = (unsigned)pb;
+    T2_CHECK_HIP(hipMemsetAsync(d.X, 0, xb + pb, s));                 // tagged hand-offs: tag 0 = invalid for the first two steps
     const size_t smem = (size_t)(4 + NWV * MT * 32 * PPR) * sizeof(float);
     const int grid = (d.H / GNC) * GKP;
     if (MT == 1) {

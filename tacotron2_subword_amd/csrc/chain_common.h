@@ -1,7 +1,8 @@
-// Shared device helpers of the persistent chain kernels (chain.hip, chain_bwd.hip): the hand-off protocol of
-// MI355X_MICROARCH.md "Valid forms" (write-through payload stores drained by every storing wave, workgroup barrier,
-// one lane signals with an agent-scope atomic; one wave polls with relaxed agent-scope loads, the other waves load
-// behind the workgroup barrier, every payload load sc1) and the hardware-exp activations.
+// Shared device helpers of the persistent chain kernels (chain.hip, chain_bwd.hip, chain_enc.hip): the two hand-off
+// protocols and the hardware-exp activations.  Arrival counters, in the decode loop and the encoder BiLSTM chains: the
+// protocol of MI355X_MICROARCH.md "Valid forms" (write-through payload stores drained by every storing wave, workgroup
+// barrier, one lane signals with an agent-scope atomic; one wave polls with relaxed agent-scope loads, the other waves load
+// behind the workgroup barrier, every payload load sc1).  Step tags, in the teacher-forced decoder chains: below.
 #pragma once
 #include "kernels.h"
 
@@ -59,24 +60,6 @@ __device__ __forceinline__ bool poll_counter(const unsigned* cnt, unsigned steps
         __builtin_amdgcn_s_sleep(2);
     }
 }
-// two counters in one request: lanes 0..31 read cnt0's shards, lanes 32..63 cnt1's
-__device__ __forceinline__ bool poll_counters2(const unsigned* cnt0, unsigned steps0, unsigned P0, const unsigned* cnt1, unsigned steps1, unsigned P1,
-                                               unsigned* err, unsigned code) {
-    const bool first = (threadIdx.x & 63) < 32;
-    const unsigned sh = threadIdx.x & (NSH - 1);
-    const unsigned* p = (first ? cnt0 : cnt1) + sh * CNT_LINE;
-    const unsigned want = (first ? steps0 : steps1) * shard_share(first ? P0 : P1, sh);
-    const unsigned long long t0 = __builtin_amdgcn_s_memrealtime();
-    for (;;) {
-        const unsigned v = __hip_atomic_load(p, T2_RLX_AGENT);
-        if (__all(v >= want)) return true;
-        if (__builtin_amdgcn_s_memrealtime() - t0 > SPIN_TICKS) {
-            if ((threadIdx.x & 63) == 0) report_abort(err, code);
-            return false;
-        }
-        __builtin_amdgcn_s_sleep(2);
-    }
-}
 // after the payload stores of every wave: drain (every storing wave), workgroup barrier, one lane signals (producer `pidx` of its group)
 __device__ __forceinline__ void publish(unsigned* cnt, unsigned pidx) {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -84,20 +67,13 @@ __device__ __forceinline__ void publish(unsigned* cnt, unsigned pidx) {
     if (threadIdx.x == 0) __hip_atomic_fetch_add(cnt + (pidx & (NSH - 1)) * CNT_LINE, 1u, T2_RLX_AGENT);
 }
 
-// ---- tagged hand-offs (round 3) ------------------------------------------------------------------------------------------
-// First form (kept for reference: publish_hint): counters as hints + validated payloads.  Final form, every teacher-forced chain:
-// NO counter at all — the consumers load their operands until the tags below are this step's (see chain.hip / chain_bwd.hip).
-// The producer's s_waitcnt vmcnt(0) in front of its arrival add costs the consumers the store round trip of the slowest
-// producer.  Here the add goes out right behind the stores (a HINT), and the payload validates itself: bit 0 of every stored
-// 32-bit word (fp32 payloads) or of the first word of every 16-byte unit (bf16 fragments) is a tag that flips each time a
-// slot is rewritten (slots alternate by step parity, so the tag is bit 1 of the step count, inverted: buffers are zeroed per
-// launch and the first valid tag is 1).  A consumer whose loads still show the old tag loads again (bounded).  16-byte sc1
-// stores have been observed untorn on gfx950 (MI355X_MICROARCH.md, Valid forms; scripts/persist_probe: 0 torn units).
-__device__ __forceinline__ unsigned step_tag(unsigned steps_done) { return ((steps_done >> 1) & 1u) ^ 1u; }
-__device__ __forceinline__ void publish_hint(unsigned* cnt, unsigned pidx) {
-    __syncthreads();                                         // every wave has ISSUED its payload stores
-    if (threadIdx.x == 0) __hip_atomic_fetch_add(cnt + (pidx & (NSH - 1)) * CNT_LINE, 1u, T2_RLX_AGENT);
-}
+// ---- step tags: the teacher-forced decoder chains (chain.hip, chain_bwd.hip) ---------------------------------------------
+// No counter: the payload validates itself.  Bit 0 of every stored 32-bit word (fp32 payloads) or of the first word of every
+// 16-byte unit (bf16 fragments) is a tag that flips each time a slot is rewritten (slots alternate by step parity, so the tag is
+// bit 1 of the step count, inverted: the buffers are zeroed before the chain starts and the first valid tag is 1).  A consumer
+// loads its operands and loads them again (bounded) until every tag is this step's.  16-byte sc1 stores have been observed
+// untorn on gfx950 (MI355X_MICROARCH.md, Valid forms; scripts/persist_probe: 0 torn units).
+__device__ __forceinline__ unsigned step_tag(unsigned step) { return ((step >> 1) & 1u) ^ 1u; }
 __device__ __forceinline__ float tag_f32(float v, unsigned tag) { return __builtin_bit_cast(float, (__builtin_bit_cast(unsigned, v) & ~1u) | tag); }
 
 }  // namespace chain

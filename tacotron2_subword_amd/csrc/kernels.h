@@ -210,11 +210,11 @@ struct ChainDesc {
     float* din; __bf16* din16; float* dout;        // [T][B][WD] (fp32 + bf16 shadow), [T][B][WO]
     int kind, F, Kc, max_pos;
     float drop_p, noise_std; uint64_t seed;
-    unsigned char* X; float* Q; unsigned* cnt; unsigned* err; unsigned q_bytes;   // exchange buffers (chain_exchange_bytes)
+    unsigned char* X; float* Q; unsigned* cnt; unsigned* err; unsigned q_bytes;   // exchange buffers (chain_fwd; cnt: decode loop only), status word
     int UT, RT, CS;                                // tiling chosen by chain_plan
     // decode loop (dec = 1; Decoder.inference, model.py:430-492): whole-cell shadows [W_hh | W_ih[:,P:] | W_ih[:,:P]] in st[].w16,
     // biases instead of hoisted pre-activations, and the decoder LSTM, the projections + stop rule and both prenets inside the launch
-    int dec, P, M, Hd;
+    int dec, P, M, Hd;                              // (P, Hd: set in every attention-chain descriptor, they place its exchange buffers)
     const float* bias1[2]; const float* bias2[2];  // attention-LSTM biases [4H]
     float* att_c[2];                               // [B][H] attention cell states carried between launches
     const __bf16* wd16; long ldwd;                 // decoder-LSTM shadow [4Hd][WD + Hd] = [W_ih | W_hh]
@@ -228,10 +228,18 @@ struct ChainDesc {
     int lds_Tin, lds_Jp, lds_Jm; int Jp[2], Jm[2]; // LDS residency: processed-memory / memory rows kept on chip
 };
 bool chain_plan(ChainDesc& d);                     // fills UT/RT/CS and the residency fields; false = shape not covered
-size_t chain_exchange_bytes(const ChainDesc& d, size_t* x_bytes, size_t* q_bytes);
 constexpr int kCntShards = 16;                     // every arrival counter is kept as 16 shards, each on a 128-byte line of its own (chain_common.h)
-constexpr size_t kChainCntBytes = (size_t)2 * 4 * 2 * 128 * kCntShards; // arrival counters: [NS][row groups <= 4][2] sharded counters
-int chain_fwd(const ChainDesc& d, hipStream_t s);
+// Status words of a pass (0 = completed or not used, else the code of the hand-off that timed out): the 256-byte block at the head
+// of the forward workspace's chain region (t2amd.h t2_decoder_layout.chain, ops.DecoderPass.chain_status); the decode loop
+// reports in the attention chain's word
+enum ChainStatus : int { CHAIN_STATUS_FWD_ATT = 0, CHAIN_STATUS_FWD_LSTM = 1, CHAIN_STATUS_BWD_LSTM = 2, CHAIN_STATUS_BWD_ATT = 3 };
+// Exchange space of a pass's forward chains and decode loop, the status words at its head: sized for the largest tiling chain_plan
+// can choose; chain_fwd carves its buffers out of it.  chain_fwd_ws_clear, once per pass: the status words, + the teacher-forced
+// chains' tagged buffers (query partials, fragments), or + (decode loop) every buffer: they carry across its step-range launches.
+enum ChainWsClear : int { CHAIN_WS_STATUS = 0, CHAIN_WS_TEACHER = 1, CHAIN_WS_DECODE = 2 };
+size_t chain_fwd_ws_floats(int NS, int B, int Ha, int E, int P, int Hd, int A);
+int chain_fwd_ws_clear(float* ws, size_t ws_floats, ChainWsClear what, hipStream_t s);
+int chain_fwd(ChainDesc d, float* ws, size_t ws_floats, hipStream_t s);
 int chain_device_cus();
 // c_api.hip: the current device's sticky status words (page-locked host memory the device writes directly; the pointer is
 // valid on both sides), and this process's claim on the device's persistent kernels (one process per GPU)
@@ -264,22 +272,21 @@ struct ChainBwdStream {
     const float* usave; const float* locsave;        // saved by the forward chain: tanh tile [T][B][A][Tin rounded up to 4], location features [T][B][Tin][F]
     const float* loc_conv; const float* loc_dense;   // [F][2][Kc], [A][F]
     float* dconv_acc; float* ddense_acc;  // [2][B][F][2Kc], [2][B][A][F]
-    const __bf16* wdt16;                  // [F][A] bf16 transpose of loc_dense (made by the caller in the exchange area)
+    const __bf16* wdt16;                  // [F][A] bf16 transpose of loc_dense (made by chain_bwd in its exchange space)
 };
 struct ChainBwdDesc {
     ChainBwdStream st[2]; int NS, B, T, t0, t1, H, kind;
     int E, A, F, Kc;
     float drop_p; uint64_t seed;
-    unsigned char* X; unsigned char* PB; unsigned* cnt; unsigned* err; unsigned pb_bytes;   // exchange: dg fragments, K-split partials
+    unsigned char* X; unsigned char* PB; unsigned* err; unsigned pb_bytes;                   // exchange (chain_bwd): dg fragments, K-split partials; status word
     unsigned char* PBC; unsigned pbc_bytes; float* DQX; float* CARRYX;                       // attention chain: ctx partials, dq partials, boundary carry (LSA: halo rows of dloc + softmax-dot partials)
     int lds_Tc;                                                                              // positions per split of the longest memory (LDS carve)
 };
-constexpr size_t kChainBwdCntBytes = (size_t)64 * 128 * kCntShards;     // 64 sharded arrival counters
 bool chain_bwd_plan(ChainBwdDesc& d);
-size_t chain_bwd_exchange_bytes(const ChainBwdDesc& d, size_t* x_bytes, size_t* pb_bytes);
-size_t chain_bwd_lsa_tagged_bytes(const ChainBwdDesc& d);   // LSA: leading part of the carry area (halo rows, tagged softmax-dot slots)
-size_t chain_bwd_att_exchange_bytes(const ChainBwdDesc& d, size_t* x_bytes, size_t* pbh_bytes, size_t* pbc_bytes, size_t* dqx_bytes, size_t* carry_bytes);
-int chain_bwd(const ChainBwdDesc& d, hipStream_t s);
+// Exchange space of the backward chains (kind: the attention chain's, CHAIN_SMA or CHAIN_LSA); chain_bwd carves its buffers out of
+// it and clears them per launch
+size_t chain_bwd_ws_floats(int kind, int NS, int B, int Ha, int E, int A, int F, int Kc, int Hd);
+int chain_bwd(ChainBwdDesc d, float* ws, size_t ws_floats, hipStream_t s);
 
 // Persistent encoder BiLSTM chains (chain_enc.hip): all steps of up to two directions in one launch, exact fp32
 struct EncChainDesc {
