@@ -1177,6 +1177,15 @@ int t2_decoder_backward(const t2_dims* dims_in, const t2_decoder_weights* w, con
     const size_t wt_bytes = ((size_t)4 * z.Hd * z.WD * sizeof(__bf16) + 255) & ~(size_t)255;
     const bool pre16 = get_precision() == 1 && (4 * z.Hd) % 64 == 0 && z.WD % 64 == 0 && c.gemm_ws_bytes() > 2 * wt_bytes;
     if (pre16) T2_TRY(stage_bf16(w->dec.w_ih, false, z.WD, reinterpret_cast<__bf16*>(ws8), z.WD, 4 * z.Hd, overlap ? side->s : c.s));
+    // bf16 mode: ONE row-major bf16 copy of dG ([BT][4Hd], behind W_ih^T) serves both of its consumers: K-contiguous A of
+    // the dDIN product of each chunk, k-major A of the two weight-gradient products (the shifted one starts B rows in)
+    const size_t dgt_bytes = ((size_t)4 * z.Hd * BT * sizeof(__bf16) + 255) & ~(size_t)255;
+    const size_t dg16_off = pre16 ? wt_bytes : 0;
+    const bool share = get_precision() == 1 && BT % 64 == 0 && z.B % 8 == 0 && (4 * z.Hd) % 128 == 0 && z.T > 1 &&
+                       c.gemm_ws_bytes() >= dg16_off + dgt_bytes + ((size_t)z.WD * BT * sizeof(__bf16) + 256);
+    __bf16* const dg16 = reinterpret_cast<__bf16*>(ws8 + dg16_off);
+    bool chunk_cast = share && pre16;                                     // cast chunk by chunk, in front of each dDIN product
+    for (size_t ci = 1; ci < bounds.size(); ++ci) if (((bounds[ci] - bounds[ci - 1]) * z.B) % 64 != 0) chunk_cast = false;
     ChainBwdDesc cbb{};
     // (next to per-step launches of the attention chain a persistent decoder-LSTM grid only takes CUs away from them:
     //  measured 24.8 -> 26.3 ms; it runs when the attention chain is persistent too)
@@ -1198,29 +1207,31 @@ int t2_decoder_backward(const t2_dims* dims_in, const t2_decoder_weights* w, con
             dd.B16 = reinterpret_cast<const __bf16*>(ws8); dd.ldb16 = 4 * z.Hd;
             dd.ws = reinterpret_cast<float*>(ws8 + wt_bytes); dd.ws_bytes -= wt_bytes;
         }
+        if (chunk_cast) {
+            T2_TRY(stage_bf16(DGd + c.R(t0) * 4 * z.Hd, true, 4 * z.Hd, dg16 + c.R(t0) * 4 * z.Hd, (t1 - t0) * z.B, 4 * z.Hd, sb));
+            dd.A16 = dg16 + c.R(t0) * 4 * z.Hd; dd.lda16 = 4 * z.Hd;
+            dd.ws = reinterpret_cast<float*>(ws8 + dg16_off + dgt_bytes); dd.ws_bytes = c.gemm_ws_bytes() - dg16_off - dgt_bytes;
+        }
         T2_TRY(gemm(dd, sb));
         if (overlap) T2_TRY(stream_edge(*side, ne++, sb, c.s));
         if (t0 == 0) {
             // the decoder LSTM's weight gradients need nothing from chain A: they run on chain B's stream once its
             // recurrence is done, underneath the rest of chain A (whose launches leave most CUs idle)
             const float* DG = DGd;
-            // bf16 mode: both products read ONE bf16 transpose of dG (the shifted one starts B columns in)
-            const size_t dgt_bytes = ((size_t)4 * z.Hd * BT * sizeof(__bf16) + 255) & ~(size_t)255;
-            const bool share = get_precision() == 1 && BT % 64 == 0 && z.B % 8 == 0 && (4 * z.Hd) % 128 == 0 && z.T > 1 &&
-                               c.gemm_ws_bytes() >= dgt_bytes + ((size_t)z.WD * BT * sizeof(__bf16) + 256);
-            __bf16* dgT = reinterpret_cast<__bf16*>(ws8);
-            if (share) T2_TRY(stage_bf16(DG, false, 4 * z.Hd, dgT, 4 * z.Hd, BT, sb));
-            auto with_dgT = [&](GemmDesc m, long col0) {
+            if (share && !chunk_cast) T2_TRY(stage_bf16(DG, true, 4 * z.Hd, dg16, BT, 4 * z.Hd, sb));
+            auto with_dg16 = [&](GemmDesc m, long row0) {
                 if (share) {
-                    m.A16 = dgT + col0; m.lda16 = BT;
-                    m.ws = reinterpret_cast<float*>(ws8 + dgt_bytes); m.ws_bytes = c.gemm_ws_bytes() - dgt_bytes;
+                    m.A16 = dg16 + row0 * 4 * z.Hd; m.lda16 = 4 * z.Hd; m.a16_kmajor = 1;
+                    m.ws = reinterpret_cast<float*>(ws8 + dg16_off + dgt_bytes); m.ws_bytes = c.gemm_ws_bytes() - dg16_off - dgt_bytes;
                 }
                 return m;
             };
-            // dW_ih = dG^T . DIN ; recurrent half: dW_hh = dG^T . dec_h(t-1)
-            T2_TRY(gemm(with_dgT(matmul_tn(c, DG, 4 * z.Hd, c.W(L.din), z.WD, g->dec.w_ih, z.WD, 4 * z.Hd, z.WD, BT), 0), sb));
+            // dW_ih = dG^T . DIN (bf16 steps: the forward pass left DIN's bf16 shadow) ; recurrent half: dW_hh = dG^T . dec_h(t-1)
+            GemmDesc mih = with_dg16(matmul_tn(c, DG, 4 * z.Hd, c.W(L.din), z.WD, g->dec.w_ih, z.WD, 4 * z.Hd, z.WD, BT), 0);
+            if (share && c.use16) { mih.B16 = c.W16(L.din16); mih.ldb16 = z.WD; mih.b16_kmajor = 1; }
+            T2_TRY(gemm(mih, sb));
             // h(t-1) pairs with dG(t): drop the first step's rows of dG and the last step's rows of dec_h
-            if (z.T > 1) T2_TRY(gemm(with_dgT(matmul_tn(c, DG + (long)z.B * 4 * z.Hd, 4 * z.Hd, c.W(L.dout), z.WO, g->dec.w_hh, z.Hd, 4 * z.Hd, z.Hd, BT - z.B), z.B), sb));
+            if (z.T > 1) T2_TRY(gemm(with_dg16(matmul_tn(c, DG + (long)z.B * 4 * z.Hd, 4 * z.Hd, c.W(L.dout), z.WO, g->dec.w_hh, z.Hd, 4 * z.Hd, z.Hd, BT - z.B), z.B), sb));
             else T2_TRY(fill_f32(g->dec.w_hh, 0.f, (size_t)4 * z.Hd * z.Hd, sb));
             if (chain_b) {                                                // the chain summed dG over steps and rows: add the row tiles
                 T2_TRY(batch_sum(cbb.st[0].dbias_part, (z.B + 31) / 32, 4 * z.Hd, g->dec.b_ih, sb));
@@ -1259,26 +1270,31 @@ int t2_decoder_backward(const t2_dims* dims_in, const t2_decoder_weights* w, con
         const float* P1 = c.W(s ? L.p1s : L.p1); const float* P2 = c.W(s ? L.p2s : L.p2);
         float* dP2 = c.S(s ? BL.dp2s : BL.dp2); float* dP1 = c.S(BL.dp1);
         const long ldw = z.P + z.E;
-        // LSTM weights: W_ih = [prenet part | ctx part], W_hh, biases.  bf16 mode: the three products share ONE bf16
-        // transpose of dG ([4Ha][BT] at the head of the scratch; the shifted products start B columns in)
+        // LSTM weights: W_ih = [prenet part | ctx part], W_hh, biases.  bf16 mode: ONE row-major bf16 copy of dG ([BT][4Ha]
+        // at the head of the scratch) is the k-major A operand of the three weight-gradient products (the shifted ones
+        // start B rows in) and the K-contiguous A operand of the prenet's input gradient below; the ctx / h operands are
+        // read from DIN's bf16 shadow where the forward pass left one
         const size_t dgt_bytes = ((size_t)4 * z.Ha * BT * sizeof(__bf16) + 255) & ~(size_t)255;
         const bool share = get_precision() == 1 && BT % 64 == 0 && z.B % 8 == 0 && (4 * z.Ha) % 128 == 0 && z.T > 1 &&
                            c.gemm_ws_bytes() >= 2 * dgt_bytes;
-        __bf16* dgT = reinterpret_cast<__bf16*>(c.gemm_ws());
-        if (share) T2_TRY(stage_bf16(DG, false, 4 * z.Ha, dgT, 4 * z.Ha, BT, ts));
-        auto dw_gemm = [&](const float* G, long col0, const float* X, long ldx, float* Y, long ldy, int N, int K) -> int {
+        __bf16* dg16 = reinterpret_cast<__bf16*>(c.gemm_ws());
+        float* const ws_rest = reinterpret_cast<float*>(reinterpret_cast<unsigned char*>(c.gemm_ws()) + dgt_bytes);
+        if (share) T2_TRY(stage_bf16(DG, true, 4 * z.Ha, dg16, BT, 4 * z.Ha, ts));
+        const __bf16* DIN16 = share && c.use16 ? c.W16(L.din16) : nullptr;
+        auto dw_gemm = [&](const float* G, long row0, const float* X, const __bf16* X16, long ldx, float* Y, long ldy, int N, int K) -> int {
             GemmDesc m = matmul_tn(c, G, 4 * z.Ha, X, ldx, Y, ldy, 4 * z.Ha, N, K);
             if (share) {
-                m.A16 = dgT + col0; m.lda16 = BT;
-                m.ws = reinterpret_cast<float*>(reinterpret_cast<unsigned char*>(c.gemm_ws()) + dgt_bytes); m.ws_bytes = c.gemm_ws_bytes() - dgt_bytes;
+                m.A16 = dg16 + row0 * 4 * z.Ha; m.lda16 = 4 * z.Ha; m.a16_kmajor = 1;
+                if (X16) { m.B16 = X16; m.ldb16 = ldx; m.b16_kmajor = 1; }
+                m.ws = ws_rest; m.ws_bytes = c.gemm_ws_bytes() - dgt_bytes;
             }
             return gemm(m, ts);
         };
-        T2_TRY(dw_gemm(DG, 0, P2, z.P, lg.w_ih, ldw, z.P, BT));
+        T2_TRY(dw_gemm(DG, 0, P2, nullptr, z.P, lg.w_ih, ldw, z.P, BT));
         if (z.T > 1) {
             const float* DG1 = DG + (long)z.B * 4 * z.Ha;             // rows of steps 1..T-1 pair with ctx/h of steps 0..T-2
-            T2_TRY(dw_gemm(DG1, z.B, DIN + coff, z.WD, lg.w_ih + z.P, ldw, z.E, BT - z.B));
-            T2_TRY(dw_gemm(DG1, z.B, DIN + hoff, z.WD, lg.w_hh, z.Ha, z.Ha, BT - z.B));
+            T2_TRY(dw_gemm(DG1, z.B, DIN + coff, DIN16 ? DIN16 + coff : nullptr, z.WD, lg.w_ih + z.P, ldw, z.E, BT - z.B));
+            T2_TRY(dw_gemm(DG1, z.B, DIN + hoff, DIN16 ? DIN16 + hoff : nullptr, z.WD, lg.w_hh, z.Ha, z.Ha, BT - z.B));
         } else {
             GemmDesc zc = matmul_tn(c, DG, 4 * z.Ha, DIN + coff, z.WD, lg.w_ih + z.P, ldw, 4 * z.Ha, z.E, BT);
             zc.alpha = 0.f;
@@ -1293,6 +1309,7 @@ int t2_decoder_backward(const t2_dims* dims_in, const t2_decoder_weights* w, con
         const float scale = a->prenet_dropout ? 1.0f / (1.0f - dims->p_prenet_dropout) : 1.0f;
         GemmDesc gp = matmul_nn(DG, 4 * z.Ha, lw.w_ih, ldw, dP2, z.P, BT, z.P, 4 * z.Ha);
         gp.ws = c.gemm_ws(); gp.ws_bytes = c.gemm_ws_bytes();
+        if (share) { gp.A16 = dg16; gp.lda16 = 4 * z.Ha; gp.ws = ws_rest; gp.ws_bytes -= dgt_bytes; }
         T2_TRY(gemm(gp, ts));
         T2_TRY(relu_drop_bwd(dP2, P2, dP2, scale, (size_t)BT * z.P, ts));
         T2_TRY(gemm(matmul_tn(c, dP2, z.P, P1, z.P, s ? g->prenet_sub_w2 : g->prenet_w2, z.P, z.P, z.P, BT), ts));
@@ -1641,13 +1658,15 @@ int t2_prof_gemm(const t2_gemm_args* a, int reps, float* ms_total, float* ms_ker
         unsigned char* w8 = reinterpret_cast<unsigned char*>(a->ws);
         __bf16* a16 = reinterpret_cast<__bf16*>(w8); __bf16* b16 = reinterpret_cast<__bf16*>(w8 + na);
         const bool akc = a->sak == 1, bkc = a->sbk == 1;
-        rc = stage_bf16(a->A, akc, akc ? a->sam : a->sak, a16, a->M, a->K, s);
-        if (rc == 0) rc = stage_bf16(a->B, bkc, bkc ? a->sbn : a->sbk, b16, a->N, a->K, s);
+        const bool km = !akc && !bkc && a->M % 256 == 0 && a->N % 256 == 0;      // both k-major, whole 256-tiles: copies stay k-major
+        rc = km ? stage_bf16(a->A, true, a->sak, a16, a->K, a->M, s) : stage_bf16(a->A, akc, akc ? a->sam : a->sak, a16, a->M, a->K, s);
+        if (rc == 0) rc = km ? stage_bf16(a->B, true, a->sbk, b16, a->K, a->N, s) : stage_bf16(a->B, bkc, bkc ? a->sbn : a->sbk, b16, a->N, a->K, s);
         GemmDesc g = gemm_desc();
         g.A = a->A; g.B = a->B; g.C = a->C; g.M = a->M; g.N = a->N; g.K = a->K;
         g.sam = a->sam; g.sak = a->sak; g.sbn = a->sbn; g.sbk = a->sbk; g.ldc = a->ldc;
         g.alpha = a->alpha; g.beta = a->beta; g.bias1 = a->bias; g.act = a->act; g.splitk = a->splitk;
-        g.A16 = a16; g.lda16 = a->K; g.B16 = b16; g.ldb16 = a->K;
+        g.A16 = a16; g.lda16 = km ? a->M : a->K; g.B16 = b16; g.ldb16 = km ? a->N : a->K;
+        g.a16_kmajor = g.b16_kmajor = km;
         g.ws = reinterpret_cast<float*>(w8 + na + nb); g.ws_bytes = a->ws_bytes - na - nb;
         if (rc == 0) rc = gemm(g, s);
         T2_CHECK_HIP(hipEventRecord(e0, s));

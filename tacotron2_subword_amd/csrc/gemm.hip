@@ -788,10 +788,43 @@ int launch_bf16src(const GemmK& g, const __bf16* pa, long lda, const __bf16* pb,
 //   read.  The two wave rows run one barrier apart (wave row 1 enters through an extra barrier), so on each SIMD one wave
 //   reads fragments while the other one issues MFMAs.  The last two K-tiles drain with vmcnt 4 / 2 / 0.
 // ---------------------------------------------------------------------------------------------
+//
+// KM (k-major operands): A16 is [K][lda] (element (m, k) at k * lda + m), B16 is [K][ldb], the layout the weight-gradient
+// products find their operands in (K = frames).  A half-tile is then 64 k-rows of 128 columns = 256-byte rows, still 16 KB,
+// staged by the same LDS-DMA instructions (1 KB = 4 k-rows per wave) and read with ds_read_b64_tr_b16: a 16-lane group
+// reads 4 k-rows x 16 columns and each lane receives the 4 k of ITS column, so two reads (k rows 8 hk .. + 3, + 4 .. + 7)
+// give a lane exactly the 8 k of the ds_read_b128 fragment in the same slots: the products are bit-identical to the
+// K-contiguous path.  Rows are 64 dwords, so the 4 k-rows of a read would share their banks; 16-byte chunk c of k-row kr
+// is kept at chunk c ^ ((kr & 3) << 2) (on the source offsets, like the K-contiguous swizzle), which spreads the 4 rows
+// x 64 bytes of a half-wave over all 64 banks.  kr & 3 is a function of the lane alone, so the K-step and the 4-row
+// half of a fragment are immediate offsets on one address register per MFMA tile.  The B half-tiles take the columns
+// h * 64 .. + 63 of each 128-column half of the tile (wave column wc: 32 of them), not h * 32 .. + 31 of each 64, so that
+// every k-row of a half-tile is made of whole 128-byte lines, as in the A half-tiles (64-byte pieces measured the same).
+// CONV_B (with KM): B16 holds the frames X[K][C] and the operand is their implicit im2col [K][taps * C]; a workgroup's
+// 256 columns lie inside one tap (C % 256 == 0), so its B tile is X with the ROWS shifted by tap - pad (folded into the
+// buffer base) and k-rows that leave their utterance read as zero through an offset past the buffer's range.
 #ifndef T2_G256_PRIO
 #define T2_G256_PRIO 1
 #endif
-template <bool CONV_A>
+typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
+// One 8-k fragment of a k-major tile: two transposed reads (k rows + 0 .. 3 and + 4 .. 7 of the 16-k step at byte OFF).
+// Inline assembly, not __builtin_amdgcn_ds_read_tr16_b64: the compiler orders the builtin behind every LDS-DMA in flight
+// (s_waitcnt vmcnt(0) in front of each group of reads, which empties the staging pipeline: 0.66 instead of 0.56 ms on
+// 4096 x 3072 x 25600).  Nor does it count these reads in lgkmcnt: lds_tr_wait() stands between them and their MFMAs.
+template <int OFF>
+__device__ __forceinline__ bf16x8 lds_read_tr16(unsigned addr) {
+    bf16x4 lo, hi;
+    asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(lo) : "v"(addr), "n"(OFF));
+    asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(hi) : "v"(addr), "n"(OFF + 1024));
+    return __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
+}
+// waits until at most N of the LDS reads issued so far are outstanding; the fragments pass through it so that no MFMA
+// that reads them moves in front
+template <int N>
+__device__ __forceinline__ void lds_tr_wait(bf16x8& a0, bf16x8& a1, bf16x8& b) {
+    asm volatile("s_waitcnt lgkmcnt(%3)" : "+v"(a0), "+v"(a1), "+v"(b) : "n"(N));
+}
+template <bool CONV_A, bool KM, bool CONV_B>
 __global__ __launch_bounds__(512) void gemm_bf16src256_kernel(GemmK g, const __bf16* __restrict__ A16, long lda, const __bf16* __restrict__ B16, long ldb) {
     const GemmDesc& d = g.d;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem16[];
@@ -820,9 +853,16 @@ __global__ __launch_bounds__(512) void gemm_bf16src256_kernel(GemmK g, const __b
     for (int h = 0; h < 2; ++h)
 #pragma unroll
         for (int i = 0; i < 2; ++i) {
-            const int s = i * 512 + tid, hr = s >> 3, gc = (s & 7) ^ ((hr >> 1) & 7);
-            offA[h][i] = (unsigned)((((hr >> 6) * 128 + h * 64 + (hr & 63)) * lda + gc * 8) * 2);
-            offB[h][i] = (unsigned)((((hr >> 5) * 64 + h * 32 + (hr & 31)) * ldb + gc * 8) * 2);
+            const int s = i * 512 + tid;
+            if constexpr (KM) {                            // LDS slot s: k-row kr, chunk s & 15 holds logical chunk ch (8 columns)
+                const int kr = s >> 4, ch = (s & 15) ^ ((kr & 3) << 2);
+                offA[h][i] = (unsigned)((kr * lda + (ch >> 3) * 128 + h * 64 + (ch & 7) * 8) * 2);
+                offB[h][i] = (unsigned)((kr * ldb + (ch >> 3) * 128 + h * 64 + (ch & 7) * 8) * 2);
+            } else {
+                const int hr = s >> 3, gc = (s & 7) ^ ((hr >> 1) & 7);
+                offA[h][i] = (unsigned)((((hr >> 6) * 128 + h * 64 + (hr & 63)) * lda + gc * 8) * 2);
+                offB[h][i] = (unsigned)((((hr >> 5) * 64 + h * 32 + (hr & 31)) * ldb + gc * 8) * 2);
+            }
         }
     // CONV_A: A16 holds the frames X[M][C] (lda = C) and the operand is their implicit im2col: K-tile k0 lies inside tap
     // dk = k0 / C (C % 64 == 0), so its rows are the frame rows shifted by dk - pad; a row that leaves its utterance gets
@@ -839,13 +879,26 @@ __global__ __launch_bounds__(512) void gemm_bf16src256_kernel(GemmK g, const __b
     int cdk[2], cka[2];                                    // tap and channel offset of the next K-tile of A half 0 / 1
     cdk[0] = cdk[1] = CONV_A ? kbeg / cva.C : 0;
     cka[0] = cka[1] = CONV_A ? kbeg % cva.C : 0;
+    // CONV_B: tap of this workgroup's columns, its first channel, and the position in its utterance of the k-row each
+    // LDS-DMA instruction of B half 0 / 1 fetches next (k-row i * 32 + tid / 16 of the K-tile; 64 further per K-tile)
+    const int bdk = CONV_B ? n0 / cva.C : 0, bshift = bdk - cva.pad, bstep = CONV_B ? 64 % cva.T : 0;
+    int tposB[2][2];
+#pragma unroll
+    for (int h = 0; h < 2; ++h)
+#pragma unroll
+        for (int i = 0; i < 2; ++i) tposB[h][i] = CONV_B ? (kbeg + i * 32 + (tid >> 4)) % cva.T : 0;
+    // KM: the buffers span the split's k-rows of the tile's 256 columns, the K-tile is the scalar offset
+    const long krange = nkt * 64 - 1;
     auto rsA = CONV_A ? __builtin_amdgcn_make_buffer_rsrc(const_cast<__bf16*>(A16), 0, (int)((long)d.M * lda * 2), 0x00020000)
+               : KM   ? __builtin_amdgcn_make_buffer_rsrc(const_cast<__bf16*>(A16 + (long)kbeg * lda + m0), 0, (int)((krange * lda + 256) * 2), 0x00020000)
                       : __builtin_amdgcn_make_buffer_rsrc(const_cast<__bf16*>(A16 + (long)m0 * lda + kbeg), 0, (int)(256 * lda * 2), 0x00020000);
-    auto rsB = __builtin_amdgcn_make_buffer_rsrc(const_cast<__bf16*>(B16 + (long)n0 * ldb + kbeg), 0, (int)(256 * ldb * 2), 0x00020000);
+    auto rsB = CONV_B ? __builtin_amdgcn_make_buffer_rsrc(const_cast<__bf16*>(B16 + (long)(kbeg + bshift) * ldb + (n0 - bdk * cva.C)), 0, (int)((krange * ldb + 256) * 2), 0x00020000)
+               : KM   ? __builtin_amdgcn_make_buffer_rsrc(const_cast<__bf16*>(B16 + (long)kbeg * ldb + n0), 0, (int)((krange * ldb + 256) * 2), 0x00020000)
+                      : __builtin_amdgcn_make_buffer_rsrc(const_cast<__bf16*>(B16 + (long)n0 * ldb + kbeg), 0, (int)(256 * ldb * 2), 0x00020000);
+    const int ktA = KM ? (int)(lda * 128) : 128, ktB = KM ? (int)(ldb * 128) : 128;        // bytes from one K-tile to the next
     // half-tile ht (0: A0, 1: A1, 2: B0, 3: B1) of K-tile kt -> LDS slot (kt & 1, ht); the calls of one half come in kt order
     auto stage = [&](int ht, int kt) {
         unsigned char* dst = smem16 + (((kt & 1) * 4 + ht) << 14) + wave * 1024;
-        const int ko = kt * 128;
         const bool live = kt < nkt;                        // (the padding K-tile of an odd count: offsets past the range read zeros)
         if (ht < 2) {
             if constexpr (CONV_A) {
@@ -858,12 +911,20 @@ __global__ __launch_bounds__(512) void gemm_bf16src256_kernel(GemmK g, const __b
                 cka[ht] += 64;
                 if (cka[ht] == cva.C) { cka[ht] = 0; ++cdk[ht]; }
             } else {
-                __builtin_amdgcn_raw_ptr_buffer_load_lds(rsA, (lds_ptr)dst, 16, live ? offA[ht][0] : 0x80000000u, ko, 0, 0);
-                __builtin_amdgcn_raw_ptr_buffer_load_lds(rsA, (lds_ptr)(dst + 8192), 16, live ? offA[ht][1] : 0x80000000u, ko, 0, 0);
+                __builtin_amdgcn_raw_ptr_buffer_load_lds(rsA, (lds_ptr)dst, 16, live ? offA[ht][0] : 0x80000000u, kt * ktA, 0, 0);
+                __builtin_amdgcn_raw_ptr_buffer_load_lds(rsA, (lds_ptr)(dst + 8192), 16, live ? offA[ht][1] : 0x80000000u, kt * ktA, 0, 0);
             }
+        } else if constexpr (CONV_B) {
+            int (&tp)[2] = tposB[ht - 2];
+            const unsigned o0 = live && (unsigned)(tp[0] + bshift) < (unsigned)cva.T ? offB[ht - 2][0] : 0x80000000u;
+            const unsigned o1 = live && (unsigned)(tp[1] + bshift) < (unsigned)cva.T ? offB[ht - 2][1] : 0x80000000u;
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(rsB, (lds_ptr)dst, 16, o0, kt * ktB, 0, 0);
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(rsB, (lds_ptr)(dst + 8192), 16, o1, kt * ktB, 0, 0);
+#pragma unroll
+            for (int i = 0; i < 2; ++i) { tp[i] += bstep; if (tp[i] >= cva.T) tp[i] -= cva.T; }
         } else {
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(rsB, (lds_ptr)dst, 16, live ? offB[ht - 2][0] : 0x80000000u, ko, 0, 0);
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(rsB, (lds_ptr)(dst + 8192), 16, live ? offB[ht - 2][1] : 0x80000000u, ko, 0, 0);
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(rsB, (lds_ptr)dst, 16, live ? offB[ht - 2][0] : 0x80000000u, kt * ktB, 0, 0);
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(rsB, (lds_ptr)(dst + 8192), 16, live ? offB[ht - 2][1] : 0x80000000u, kt * ktB, 0, 0);
         }
     };
     // fragment addresses inside a half-tile: row hr, 16-byte chunk c at hr * 128 + ((c ^ ((hr >> 1) & 7)) << 4)
@@ -872,6 +933,15 @@ __global__ __launch_bounds__(512) void gemm_bf16src256_kernel(GemmK g, const __b
 #pragma unroll
     for (int ks = 0; ks < 4; ++ks) cofs[ks] = (unsigned)(((2 * ks + hk) ^ sw) << 4);
     const unsigned rowA = (unsigned)((wr * 64 + r) * 128), rowB = (unsigned)((wc * 32 + r) * 128);
+    // KM: lane 4q + p of 16-lane group (hk, gc) gives the address of k-row 8 hk + q (+ 16 ks + 4 u as an immediate), columns
+    // 16 gc + 4 p .. + 3 of the MFMA tile, and receives column 16 gc + 4 q + p = r
+    const int tq = (lane >> 2) & 3, tp = lane & 3, tgc = (lane >> 4) & 1;
+    auto tr_addr = [&](int chunk0) { return (unsigned)(256 * (8 * hk + tq) + 16 * ((chunk0 + 2 * tgc + (tp >> 1)) ^ (tq << 2)) + 8 * (tp & 1)); };
+    const unsigned trA[2] = {tr_addr(wr * 8), tr_addr(wr * 8 + 4)}, trB = tr_addr(wc * 4);
+    const unsigned lds0 = (unsigned)(uintptr_t)(__attribute__((address_space(3))) unsigned char*)smem16;
+    auto read_tr = [&](bf16x8 (&f)[4], unsigned addr) {
+        f[0] = lds_read_tr16<0>(addr); f[1] = lds_read_tr16<4096>(addr); f[2] = lds_read_tr16<8192>(addr); f[3] = lds_read_tr16<12288>(addr);
+    };
 
     f32x16 acc[4][2];
 #pragma unroll
@@ -883,16 +953,21 @@ __global__ __launch_bounds__(512) void gemm_bf16src256_kernel(GemmK g, const __b
     bf16x8 Af[2][4], Bf[2][4];
 
     auto read_a = [&](int buf, int h) {
-        const unsigned char* base = smem16 + ((buf * 4 + h) << 14) + rowA;
+        const unsigned char* base = smem16 + ((buf * 4 + h) << 14);
 #pragma unroll
-        for (int i = 0; i < 2; ++i)
+        for (int i = 0; i < 2; ++i) {
+            if constexpr (KM) read_tr(Af[i], lds0 + ((buf * 4 + h) << 14) + trA[i]);
+            else
 #pragma unroll
-            for (int ks = 0; ks < 4; ++ks) Af[i][ks] = *reinterpret_cast<const bf16x8*>(base + i * 4096 + cofs[ks]);
+                for (int ks = 0; ks < 4; ++ks) Af[i][ks] = *reinterpret_cast<const bf16x8*>(base + rowA + i * 4096 + cofs[ks]);
+        }
     };
     auto read_b = [&](int buf, int h) {
-        const unsigned char* base = smem16 + ((buf * 4 + 2 + h) << 14) + rowB;
+        const unsigned char* base = smem16 + ((buf * 4 + 2 + h) << 14);
+        if constexpr (KM) read_tr(Bf[h], lds0 + ((buf * 4 + 2 + h) << 14) + trB);
+        else
 #pragma unroll
-        for (int ks = 0; ks < 4; ++ks) Bf[h][ks] = *reinterpret_cast<const bf16x8*>(base + cofs[ks]);
+            for (int ks = 0; ks < 4; ++ks) Bf[h][ks] = *reinterpret_cast<const bf16x8*>(base + rowB + cofs[ks]);
     };
     auto mma = [&](int a, int b) {
 #if T2_G256_PRIO
@@ -900,6 +975,23 @@ __global__ __launch_bounds__(512) void gemm_bf16src256_kernel(GemmK g, const __b
 #else
         __builtin_amdgcn_sched_barrier(0);
 #endif
+        // KM: whatever a phase reads (B: 8 reads; A: 16; both: 24, B first), the fragments of step ks are complete once at
+        // most 6 - 2 ks reads are outstanding (LDS reads return in order and the loop issues no other LDS operation; a
+        // scalar load still in flight only makes the count conservative)
+        if constexpr (KM) {
+            lds_tr_wait<6>(Af[0][0], Af[1][0], Bf[b][0]);
+#pragma unroll
+            for (int i = 0; i < 2; ++i) acc[a * 2 + i][b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Af[i][0], Bf[b][0], acc[a * 2 + i][b], 0, 0, 0);
+            lds_tr_wait<4>(Af[0][1], Af[1][1], Bf[b][1]);
+#pragma unroll
+            for (int i = 0; i < 2; ++i) acc[a * 2 + i][b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Af[i][1], Bf[b][1], acc[a * 2 + i][b], 0, 0, 0);
+            lds_tr_wait<2>(Af[0][2], Af[1][2], Bf[b][2]);
+#pragma unroll
+            for (int i = 0; i < 2; ++i) acc[a * 2 + i][b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Af[i][2], Bf[b][2], acc[a * 2 + i][b], 0, 0, 0);
+            lds_tr_wait<0>(Af[0][3], Af[1][3], Bf[b][3]);
+#pragma unroll
+            for (int i = 0; i < 2; ++i) acc[a * 2 + i][b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Af[i][3], Bf[b][3], acc[a * 2 + i][b], 0, 0, 0);
+        } else
 #pragma unroll
         for (int ks = 0; ks < 4; ++ks)
 #pragma unroll
@@ -962,7 +1054,9 @@ __global__ __launch_bounds__(512) void gemm_bf16src256_kernel(GemmK g, const __b
     float* stg = reinterpret_cast<float*>(smem16) + wave * 4096;
     const bool vec_ok = ws || ((reinterpret_cast<uintptr_t>(d.C) & 15) == 0 && d.ldc % 4 == 0);
     const float inv_keep = d.drop_p > 0.f ? 1.0f / (1.0f - d.drop_p) : 1.0f;
-    const int c4 = (lane & 15) * 4, n = n0 + wc * 64 + c4;
+    // (KM: wave column wc owns columns (wc >> 1) * 128 + j * 64 + (wc & 1) * 32 + r, so that a B half-tile's k-rows are whole
+    // 128-byte lines in memory like the A half-tile's)
+    const int c4 = (lane & 15) * 4, n = n0 + (KM ? (wc >> 1) * 128 + (c4 >> 5) * 64 + (wc & 1) * 32 + (c4 & 31) : wc * 64 + c4);
     f32x4 bias = {0.f, 0.f, 0.f, 0.f};
     if (!ws) {
 #pragma unroll
@@ -1004,14 +1098,14 @@ __global__ __launch_bounds__(512) void gemm_bf16src256_kernel(GemmK g, const __b
     }
 }
 
-template <bool CONV_A>
+template <bool CONV_A, bool KM, bool CONV_B>
 int launch_bf16src256(const GemmK& g, const __bf16* pa, long lda, const __bf16* pb, long ldb, int splitk, hipStream_t s) {
     constexpr size_t smem = 128 * 1024;
-    T2_TRY_RC(t2_allow_dynamic_lds(reinterpret_cast<const void*>(gemm_bf16src256_kernel<CONV_A>), smem));
+    T2_TRY_RC(t2_allow_dynamic_lds(reinterpret_cast<const void*>(gemm_bf16src256_kernel<CONV_A, KM, CONV_B>), smem));
     GemmK gk = g;
     const int gx = g.d.N / 256, gy = g.d.M / 256;
     gk.xcd_swizzle = (gx * gy) % 8 == 0 && gy >= 4;
-    hipLaunchKernelGGL((gemm_bf16src256_kernel<CONV_A>), dim3(gx, gy, splitk), dim3(512), smem, s, gk, pa, lda, pb, ldb);
+    hipLaunchKernelGGL((gemm_bf16src256_kernel<CONV_A, KM, CONV_B>), dim3(gx, gy, splitk), dim3(512), smem, s, gk, pa, lda, pb, ldb);
     T2_LAUNCH_CHECK();
     return 0;
 }
@@ -1036,31 +1130,6 @@ __global__ __launch_bounds__(256) void stage_mc_kernel(const float* __restrict__
     for (int i = 0; i < 4; ++i) {
         const int k = (threadIdx.x >> 4) + 16 * i, r4 = (threadIdx.x & 15) * 4;
         const f32x4 v = *reinterpret_cast<const f32x4*>(src + (long)(k0 + k) * ld + r0 + r4);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) tile[k][r4 + j] = v[j];
-    }
-    __syncthreads();
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-        const int kg = threadIdx.x & 7, row = (threadIdx.x >> 3) + 32 * i;
-        bf16x8 o;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) o[j] = (__bf16)tile[kg * 8 + j][row];
-        *reinterpret_cast<bf16x8*>(dst + (long)(r0 + row) * K + k0 + kg * 8) = o;
-    }
-}
-
-// implicit-im2col B operand (k = frame m, row n = tap*C + ci): dst[n][m] = X[m + tap - pad][ci] inside the utterance, else 0
-__global__ __launch_bounds__(256) void stage_conv_mc_kernel(const float* __restrict__ X, ConvAddr cv, __bf16* __restrict__ dst, int K) {
-    __shared__ float tile[64][65];
-    const int r0 = blockIdx.x * 64, k0 = blockIdx.y * 64;
-    const int dk = r0 / cv.C, ci0 = r0 - dk * cv.C, shift = dk - cv.pad;          // C % 64 == 0: one tap per row tile
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int k = (threadIdx.x >> 4) + 16 * i, r4 = (threadIdx.x & 15) * 4;
-        const int m = k0 + k;
-        f32x4 v = {0.f, 0.f, 0.f, 0.f};
-        if ((unsigned)(m % cv.T + shift) < (unsigned)cv.T) v = *reinterpret_cast<const f32x4*>(X + (long)(m + shift) * cv.C + ci0 + r4);
 #pragma unroll
         for (int j = 0; j < 4; ++j) tile[k][r4 + j] = v[j];
     }
@@ -1134,12 +1203,24 @@ int gemm(const GemmDesc& din, hipStream_t s) {
     bool staged = false;
     __bf16* a16 = nullptr; __bf16* b16 = nullptr;
     const bool conv_any = d.conv_a || d.conv_b;
-    if (use_bf16 && g_stage && (!conv_any || (d.conv_C % 64 == 0 && !d.A16 && !d.B16)) && d.batch == 1 && d.M % 128 == 0 && d.N % 128 == 0 && d.K % 64 == 0) {
-        // implicit-conv A: only the frames [M][C] are staged (the kernel shifts rows per tap); implicit-conv B: the whole
-        // im2col transpose [N][K] is written out (N = taps*C rows of K frames)
+    // 256 x 256 tiles (gemm_bf16src256_kernel) when the staged operands are whole 256-tiles and K splits into an even
+    // number of 64-wide K-tiles.  Its k-major variant reads both operands as they lie in memory when BOTH are k-major
+    // (the weight-gradient products): they are staged by the plain cast, [K][M] and [K][N]; an implicit-conv B operand
+    // is then the bf16 copy of the frames [K][C] alone.  A bf16 copy the caller hands over in the layout the product
+    // does not take is ignored (the fp32 operand is staged instead).
+    static const int g_t256 = env_int("T2_GEMM_256", 1);
+    const bool shape256 = g_t256 && d.M % 256 == 0 && d.N % 256 == 0 && d.K >= 128;
+    const long ld_km = std::max(std::max((long)d.M, d.A16 && d.a16_kmajor ? d.lda16 : 0l), std::max((long)(d.conv_b ? d.conv_C : d.N), d.B16 && d.b16_kmajor ? d.ldb16 : 0l));
+    const bool km = shape256 && !akc && !bkc && !d.conv_a && (!d.conv_b || d.conv_C % 256 == 0) && (long)d.K * ld_km * 2 < (1l << 31);
+    if (d.A16 && (d.a16_kmajor != 0) != km) d.A16 = nullptr;
+    if (d.B16 && (d.b16_kmajor != 0) != km) d.B16 = nullptr;
+    const bool conv_ok = !conv_any || (d.conv_a && d.conv_C % 64 == 0 && !d.A16 && !d.B16) || (d.conv_b && km);
+    if (use_bf16 && g_stage && conv_ok && d.batch == 1 && d.M % 128 == 0 && d.N % 128 == 0 && d.K % 64 == 0) {
+        // implicit-conv operands: only the frames [rows][C] are staged (the kernel shifts rows per tap)
         const size_t a_elems = d.conv_a ? (size_t)d.M * d.conv_C : (size_t)d.M * d.K;
+        const size_t b_elems = d.conv_b ? (size_t)d.K * d.conv_C : (size_t)d.N * d.K;
         const size_t need_a = d.A16 ? 0 : ((a_elems * sizeof(__bf16) + 255) & ~(size_t)255);
-        const size_t need_b = d.B16 ? 0 : (((size_t)d.N * d.K * sizeof(__bf16) + 255) & ~(size_t)255);
+        const size_t need_b = d.B16 ? 0 : ((b_elems * sizeof(__bf16) + 255) & ~(size_t)255);
         const bool big = (d.A16 || d.N >= g_stage_min) && (d.B16 || d.M >= g_stage_min);
         const bool ok_src = (d.A16 || g.avec) && (d.B16 || g.bvec) &&
                             (!d.A16 || (aligned16(d.A16) && d.lda16 % 8 == 0)) && (!d.B16 || (aligned16(d.B16) && d.ldb16 % 8 == 0));
@@ -1151,10 +1232,8 @@ int gemm(const GemmDesc& din, hipStream_t s) {
             if (need_a + need_b) { d.ws = reinterpret_cast<float*>(base + need_a + need_b); d.ws_bytes -= need_a + need_b; }
         }
     }
-    // 256 x 256 tiles (gemm_bf16src256_kernel) when the staged operands are whole 256-tiles and K splits into an even
-    // number of 64-wide K-tiles; its split-K factor fills whole rounds of one workgroup per CU
-    static const int g_t256 = env_int("T2_GEMM_256", 1);
-    const bool use256 = staged && g_t256 && d.M % 256 == 0 && d.N % 256 == 0 && d.K >= 128 && (!d.conv_a || (long)d.M * d.conv_C * 2 < (1l << 31));
+    // the 256-tile kernel's split-K factor fills whole rounds of one workgroup per CU
+    const bool use256 = staged && shape256 && (!d.conv_a || (long)d.M * d.conv_C * 2 < (1l << 31));
     int split256 = 1;
     if (use256) {
         const long tiles = (long)(d.M / 256) * (d.N / 256);
@@ -1212,28 +1291,31 @@ int gemm(const GemmDesc& din, hipStream_t s) {
     static const int g_log = env_int("T2_GEMM_LOG", 0);      // dev: one line per product (shape, kernel, split, which operands get staged)
     if (g_log)
         fprintf(stderr, "t2gemm M=%d N=%d K=%d batch=%d %s%s kernel=%s splitk=%d stageA=%d stageB=%d convA=%d convB=%d beta=%g\n", d.M, d.N, d.K, d.batch,
-                akc ? "A[m][k]" : "A[k][m]", bkc ? " B[n][k]" : " B[k][n]", staged ? (use256 ? "src256" : "src128") : use_bf16 ? "bf16conv" : small ? "f32_64" : "f32_128",
+                akc ? "A[m][k]" : "A[k][m]", bkc ? " B[n][k]" : " B[k][n]", staged ? (use256 ? (km ? "src256km" : "src256") : "src128") : use_bf16 ? "bf16conv" : small ? "f32_64" : "f32_128",
                 splitk, a16 != nullptr, b16 != nullptr, d.conv_a, d.conv_b, (double)d.beta);
     T2_REQUIRE((long)d.batch * splitk <= 65535, "gemm: batch*splitk too large (%d*%d)", d.batch, splitk);
     dim3 grid(tn, tm, d.batch * splitk);
     if (staged) {
+        const bool km256 = km && use256;                   // (km implies use256 once staged; the k-major copies are [K][rows])
         if (a16) {
             if (d.conv_a) T2_TRY_RC(stage_operand(d.A, true, d.conv_C, a16, d.M, d.conv_C, s));
+            else if (km256) T2_TRY_RC(stage_operand(d.A, true, d.sak, a16, d.K, d.M, s));
             else T2_TRY_RC(stage_operand(d.A, akc, akc ? d.sam : d.sak, a16, d.M, d.K, s));
         }
         if (b16) {
-            if (d.conv_b) {
-                hipLaunchKernelGGL(stage_conv_mc_kernel, dim3(d.N / 64, d.K / 64), dim3(256), 0, s, d.B, ConvAddr{d.conv_T, d.conv_C, d.conv_pad}, b16, d.K);
-                T2_LAUNCH_CHECK();
-            } else T2_TRY_RC(stage_operand(d.B, bkc, bkc ? d.sbn : d.sbk, b16, d.N, d.K, s));
+            if (d.conv_b) T2_TRY_RC(stage_operand(d.B, true, d.conv_C, b16, d.K, d.conv_C, s));
+            else if (km256) T2_TRY_RC(stage_operand(d.B, true, d.sbk, b16, d.K, d.N, s));
+            else T2_TRY_RC(stage_operand(d.B, bkc, bkc ? d.sbn : d.sbk, b16, d.N, d.K, s));
         }
-        const __bf16* pa = d.A16 ? d.A16 : a16; const long lda = d.A16 ? d.lda16 : (d.conv_a ? d.conv_C : d.K);
-        const __bf16* pb = d.B16 ? d.B16 : b16; const long ldb = d.B16 ? d.ldb16 : d.K;
+        const __bf16* pa = d.A16 ? d.A16 : a16; const long lda = d.A16 ? d.lda16 : d.conv_a ? d.conv_C : km256 ? d.M : d.K;
+        const __bf16* pb = d.B16 ? d.B16 : b16; const long ldb = d.B16 ? d.ldb16 : d.conv_b ? d.conv_C : km256 ? d.N : d.K;
         // 128x128 block tile, two k-steps in flight.  Measured alternatives (same template, other parameters): 256x128 with
         // 8 waves 5-12 % slower, 256x256 with 128x64 wave tiles and one k-step in flight 4.6x slower (one workgroup per CU:
         // nothing overlaps its barriers) — the kernel is bound by latency hiding, not by operand bytes per CU
-        if (use256 && d.conv_a) T2_TRY_RC((launch_bf16src256<true>(g, pa, lda, pb, ldb, splitk, s)));
-        else if (use256) T2_TRY_RC((launch_bf16src256<false>(g, pa, lda, pb, ldb, splitk, s)));
+        if (km256 && d.conv_b) T2_TRY_RC((launch_bf16src256<false, true, true>(g, pa, lda, pb, ldb, splitk, s)));
+        else if (km256) T2_TRY_RC((launch_bf16src256<false, true, false>(g, pa, lda, pb, ldb, splitk, s)));
+        else if (use256 && d.conv_a) T2_TRY_RC((launch_bf16src256<true, false, false>(g, pa, lda, pb, ldb, splitk, s)));
+        else if (use256) T2_TRY_RC((launch_bf16src256<false, false, false>(g, pa, lda, pb, ldb, splitk, s)));
         else if (d.conv_a) T2_TRY_RC((launch_bf16src<true, 2, 2, 2, 2, 2>(g, pa, lda, pb, ldb, splitk, s)));
         else T2_TRY_RC((launch_bf16src<false, 2, 2, 2, 2, 2>(g, pa, lda, pb, ldb, splitk, s)));
     } else if (use_bf16) {

@@ -28,6 +28,9 @@ struct GemmDesc {
     int fp32_only;                                // never use the bf16-operand kernel for this product
     const __bf16* A16; long lda16;                // optional pre-staged bf16 copies of the operands, K contiguous:
     const __bf16* B16; long ldb16;                // A16[m*lda16 + k], B16[n*ldb16 + k] (bf16 mode, whole 128x128x64 tiles)
+    int a16_kmajor, b16_kmajor;                   // the copy is k-major instead: A16[k*lda16 + m], B16[k*ldb16 + n] (conv_b: the
+                                                  // frames, B16[k*ldb16 + ci]).  Only the 256-tile kernel's k-major variant reads
+                                                  // such a copy (both operands k-major, whole 256-tiles); otherwise it is ignored
     int crow_mod; long crow_mul;                  // output row = (m % crow_mod) * crow_mul + m / crow_mod (0 = identity):
                                                   // writes time-major rows (t,b) in batch-major order (b,t) or back
 };
