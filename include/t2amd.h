@@ -45,8 +45,10 @@ const char* t2_last_error(void);
 /* ABI version: bumped whenever a struct below grows or an argument changes meaning.  2 (round 3): t2_dims carries
  * score_mask_value[_sub], the layouts carry chain / chain_floats, norm_out of t2_adam_* is 4 floats.  A caller compiled
  * against another version passes structs of another size: check t2_version() == T2_ABI_VERSION before anything else.
- * 3: t2_decoder_layout carries usave / usaves / locsave / locsaves (LSA: tanh tile and location features of every step). */
-#define T2_ABI_VERSION 3
+ * 3: t2_decoder_layout carries usave / usaves / locsave / locsaves (LSA: tanh tile and location features of every step).
+ * 4: t2_set_precision accepts mode 2 (split-bf16), the layout queries depend on the mode in force, t2_gemm_counts,
+ *    t2_set_gemm_split_min_mflop. */
+#define T2_ABI_VERSION 4
 int t2_version(void);
 /* Sticky status of the persistent kernels of the current device (the reference's nearest analogue: train.py:335-340,
  * which at least notices a NaN gradient norm).  A chain whose hand-off timed out writes a non-zero code into a word in
@@ -66,9 +68,32 @@ int t2_debug_occupy(int workgroups, int milliseconds, void* stream);
 int t2_chain_claimed(void);
 /* Arithmetic type of the GEMM operands: 0 = fp32 (exact fp32 fma chains; the parity path, default),
  * 1 = bf16 operands with fp32 accumulation for the large GEMMs (fp32 storage, converted while
- * staging); recurrent state, BatchNorm statistics and attention recurrences stay fp32. */
+ * staging); recurrent state, BatchNorm statistics and attention recurrences stay fp32.
+ * 2 = split-bf16: everything as in mode 0 except the large GEMMs (whole 128- or 256-tiles, K % 64 == 0, batch 1, both
+ * extents >= 256, scratch given, at least 2^31 FLOP: t2_set_gemm_split_min_mflop), which run on the bf16 matrix pipe at
+ * fp32-grade accuracy: each fp32 operand is staged as hi = bf16(x), lo = bf16(x - hi) (finite for |x| < 3.39e38) and
+ * the product is hi.hi + lo.hi + hi.lo with fp32 accumulation, in one launch
+ * (error per product about 3 * sqrt(K) * 2^-17 for unit-scale operands, a dozen times the fp32 kernel's own; whole-model
+ * outputs stay within 1e-4 of the reference).  A product that does not qualify runs the exact fp32 kernel of mode 0; the
+ * recurrent steps, the attention kernels, BatchNorm and the decode loop are mode 0's, and the persistent chains do not
+ * run in this mode.  The staged operands take 6 bytes per element (mode 1: 2), so the scratch is larger:
+ * t2_decoder_layout_query / t2_decoder_bwd_layout_query answer for the mode in force (B=64, T=400: forward +0.6 GB,
+ * backward +0.6 GB), and the precision must NOT change between a layout query and the calls that use a workspace of that
+ * size.  Callers of t2_conv_bn_* / t2_lstm_seq_* / t2_gemm_ex who want their products on the split path size the
+ * scratch for 6 bytes per staged operand element; with less the product runs the exact kernel.  (In every mode the exact
+ * kernel's automatic split-K factor is clamped by the scratch it is given, so "bit-identical to mode 0" means: to mode 0
+ * with the same scratch size; no product of the model reaches that clamp.) */
 int t2_set_precision(int mode);
 int t2_get_precision(void);
+/* Which kernel family the products took: calls of the GEMM layer since the last reset that launched [0] an exact fp32
+ * kernel, [1] the converting bf16 kernel, [2] a bf16-source kernel on single-bf16 operands, [3] a bf16-source kernel on
+ * split-bf16 operands.  Host counters, no synchronisation; reset != 0 clears them after the read. */
+int t2_gemm_counts(uint64_t* out_host /* [4] */, int reset);
+/* Mode 2: a qualifying product still runs the exact fp32 kernel when 2*M*N*K is below mflop * 1e6 (the split path's
+ * two staging launches and tripled K do not pay on small products; default 2147, i.e. 2^31 FLOP, from the measured
+ * break-even).  mflop < 0 restores the default; 0 sends every qualifying product to the split path (kernel tests on
+ * small shapes). */
+int t2_set_gemm_split_min_mflop(int mflop);
 /* 1 (default): teacher-forced passes run the decoder-LSTM chain on an internal side stream, one chunk of steps
  * apart from the attention chain (fork/join inside the call; the caller's stream semantics are unchanged).  0: one stream. */
 int t2_set_overlap(int on);
@@ -358,7 +383,9 @@ typedef struct t2_gemm_args {
 int t2_gemm_ex(const t2_gemm_args* a, void* stream);
 /* Measurement (bench.py): average milliseconds of `reps` launches of this product on `stream`, bracketed by HIP events —
  * ms_total as t2_gemm_ex runs it (fp32 operands in: bf16 staging casts included), ms_kernel with both bf16 operand copies
- * made beforehand (the matrix kernel and its split-K reduce alone).  bf16 mode, M, N multiples of 128, K of 64, scratch given. */
+ * made beforehand (the matrix kernel and its split-K reduce alone).  bf16 mode or split-bf16 mode (there: the hi / lo
+ * staging, resp. both hi / lo copies made beforehand; scratch for 6 bytes per operand element), M, N multiples of 128, K of
+ * 64, scratch given; refused in mode 0. */
 int t2_prof_gemm(const t2_gemm_args* a, int reps, float* ms_total, float* ms_kernel, void* stream);
 /* out[n] = sum_m x[m*ld + n]; scratch >= 64*N floats */
 int t2_colsum(const float* x, long ld, int M, int N, float* out, float* scratch, void* stream);

@@ -150,9 +150,9 @@ class GemmArgs(C.Structure):
 
 
 # every symbol include/t2amd.h declares (tests/test_abi.py checks the library exports them all)
-ABI_VERSION = 3      # include/t2amd.h T2_ABI_VERSION: struct sizes below match that header and nothing else
+ABI_VERSION = 4      # include/t2amd.h T2_ABI_VERSION: struct sizes below match that header and nothing else
 
-EXPORTS = ["t2_last_error", "t2_version", "t2_chain_status", "t2_chain_status_clear", "t2_debug_report_abort", "t2_debug_occupy", "t2_chain_claimed", "t2_set_precision", "t2_get_precision", "t2_set_overlap", "t2_set_chain", "t2_get_chain", "t2_set_chain_bwd", "t2_set_gemm_staging", "t2_side_join", "t2_decoder_layout_query", "t2_decoder_forward", "t2_decoder_infer",
+EXPORTS = ["t2_last_error", "t2_version", "t2_chain_status", "t2_chain_status_clear", "t2_debug_report_abort", "t2_debug_occupy", "t2_chain_claimed", "t2_set_precision", "t2_get_precision", "t2_gemm_counts", "t2_set_gemm_split_min_mflop", "t2_set_overlap", "t2_set_chain", "t2_get_chain", "t2_set_chain_bwd", "t2_set_gemm_staging", "t2_side_join", "t2_decoder_layout_query", "t2_decoder_forward", "t2_decoder_infer",
            "t2_decoder_bwd_layout_query", "t2_decoder_backward", "t2_prof_enable", "t2_prof_collect", "t2_adam_chunks", "t2_adam_step", "t2_adam_norm",
            "t2_conv_bn_forward", "t2_conv_bn_backward", "t2_embedding_forward", "t2_embedding_backward",
            "t2_lstm_seq_forward", "t2_lstm_seq_backward", "t2_lstm_seq_chain_ws_floats", "t2_gemm_ex", "t2_prof_gemm", "t2_colsum", "t2_mask_btc",
@@ -198,6 +198,8 @@ def lib() -> C.CDLL:
         L.t2_colsum.argtypes = [C.c_void_p, C.c_long, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
         L.t2_mask_btc.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_float, C.c_void_p]
         L.t2_prof_enable.argtypes = [C.c_int]
+        L.t2_gemm_counts.argtypes = [C.POINTER(C.c_uint64), C.c_int]
+        L.t2_set_gemm_split_min_mflop.argtypes = [C.c_int]
         L.t2_prof_collect.argtypes = [C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_int)]
         L.t2_finalize_bct.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_float, C.c_void_p]
         L.t2_mask_bt.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_float, C.c_void_p]
@@ -400,10 +402,29 @@ def get_chain() -> bool:
     return bool(lib().t2_get_chain())
 
 
+PRECISION_MODES = {"f32": 0, "fp32": 0, "bf16": 1, "bf16x3": 2}
+
+
 def set_precision(mode: str) -> None:
-    """"f32": exact fp32 GEMMs (parity path, default).  "bf16": bf16 operands / fp32 accumulate for large GEMMs."""
-    check(lib().t2_set_precision({"f32": 0, "fp32": 0, "bf16": 1}[mode]))
+    """"f32": exact fp32 GEMMs (parity path, default).  "bf16": bf16 operands / fp32 accumulate for large GEMMs and the
+    recurrent steps (throughput mode).  "bf16x3": split-bf16 — the fp32 mode's arithmetic everywhere except the large
+    GEMMs, which run as three bf16 products (hi.hi + lo.hi + hi.lo, fp32 accumulate) at fp32-grade accuracy.
+    Workspaces are sized for the mode in force: set the mode before a pass is allocated, not between its calls."""
+    check(lib().t2_set_precision(PRECISION_MODES[mode]))
 
 
 def get_precision() -> str:
-    return "bf16" if lib().t2_get_precision() == 1 else "f32"
+    return {0: "f32", 1: "bf16", 2: "bf16x3"}[lib().t2_get_precision()]
+
+
+def gemm_counts(reset: bool = False):
+    """(exact fp32, converting bf16, bf16-source on single-bf16 operands, bf16-source on split operands): products of the
+    GEMM layer since the last reset, by the kernel family they launched."""
+    out = (C.c_uint64 * 4)()
+    check(lib().t2_gemm_counts(out, int(bool(reset))))
+    return tuple(int(v) for v in out)
+
+
+def set_gemm_split_min_mflop(mflop: int = -1) -> None:
+    """"bf16x3": products below 2*M*N*K = mflop * 1e6 stay on the exact fp32 kernel (include/t2amd.h); -1 = the default."""
+    check(lib().t2_set_gemm_split_min_mflop(int(mflop)))

@@ -31,9 +31,14 @@ def _scratch(dev, n_floats: int) -> torch.Tensor:
     return t
 
 
+def _stage_terms() -> int:
+    """bf16 terms per staged operand element: the split-bf16 mode stages hi / lo parts in a K' = 3K layout (gemm.hip)."""
+    return 3 if L.get_precision() == "bf16x3" else 1
+
+
 def gemm_ex(A, Bm, out, M, N, K, sam, sak, sbn, sbk, ldc, *, bias=None, act=0, alpha=1.0, beta=0.0, crow_mod=0, crow_mul=0,
             batch=1, bsA=0, bsB=0, bsC=0, splitk_ws=True):
-    ws = _scratch(out.device, 8 << 20) if splitk_ws and beta == 0.0 else None
+    ws = _scratch(out.device, (8 << 20) * _stage_terms()) if splitk_ws and beta == 0.0 else None
     a = L.GemmArgs(L.ptr(A), L.ptr(Bm), L.ptr(out), M, N, K, sam, sak, sbn, sbk, ldc, batch, bsA, bsB, bsC, alpha, beta,
                    L.ptr(bias), act, crow_mod, crow_mul, L.ptr(ws), 0 if ws is None else ws.numel() * 4, 0)
     L.check(L.lib().t2_gemm_ex(C.byref(a), L.stream()))
@@ -130,7 +135,7 @@ class _ConvStackFn(torch.autograd.Function):
             z = torch.empty(M, Cout, dtype=torch.float32, device=dev)
             y = torch.empty(B, T, Cout, dtype=torch.float32, device=dev)
             st = torch.empty(3, Cout, dtype=torch.float32, device=dev)      # mean, invstd, var
-            nws = Cout * Cin * K + 4 + 128 * Cout + (M * Cin + Cout * Cin * K) // 2 + 4096    # + bf16 operand staging + split-K
+            nws = Cout * Cin * K + 4 + 128 * Cout + _stage_terms() * ((M * Cin + Cout * Cin * K) // 2) + 4096    # + bf16 operand staging + split-K
             ws = _scratch(dev, nws)
             res = x if (cfg["residual"] and i == n - 1) else None
             a = L.ConvBnArgs(B, T, Cin, Cout, K, L.ptr(cur), L.ptr(w.detach()), L.ptr(bias.detach()), L.ptr(gamma.detach()),
@@ -161,7 +166,7 @@ class _ConvStackFn(torch.autograd.Function):
             dg, dbt = torch.empty_like(gamma), torch.empty_like(beta)
             need_dx = i > 0 or ctx.needs_input_grad[0]
             dx = torch.empty(B, T, Cin, dtype=torch.float32, device=dev) if need_dx else None
-            nws = M * Cout + Cout * Cin * K + 128 * Cout + 16 + (8 << 20) + (M * (Cout + K * max(Cin, Cout))) // 2 + Cout * Cin * K
+            nws = M * Cout + Cout * Cin * K + 128 * Cout + 16 + (8 << 20) + _stage_terms() * ((M * (Cout + K * max(Cin, Cout))) // 2) + Cout * Cin * K
             ws = _scratch(dev, nws)
             a = L.ConvBnBwdArgs(B, T, Cin, Cout, K, L.ptr(xin), L.ptr(w), L.ptr(gamma), L.ptr(beta), L.ptr(z), L.ptr(st[0]), L.ptr(st[1]),
                                 int(cfg["training"]), 1e-5, cfg["acts"][i], cfg["drop_p"] if cfg["training"] else 0.0, cfg["seed"],
@@ -233,7 +238,7 @@ class _BiLstmFn(torch.autograd.Function):
         dh = dout.transpose(0, 1).contiguous()                           # [T,B,2H]
         dpre = torch.empty(2, T * B, 4 * H, dtype=torch.float32, device=dev)
         dwhh = torch.empty(2, 4 * H, H, dtype=torch.float32, device=dev)
-        nws = max(2 * (B * H + 8 * B * H) + 64, int(L.lib().t2_lstm_seq_chain_ws_floats(2, B, H, 1))) + (8 << 20)
+        nws = max(2 * (B * H + 8 * B * H) + 64, int(L.lib().t2_lstm_seq_chain_ws_floats(2, B, H, 1))) + (8 << 20) * _stage_terms()
         ws = _scratch(dev, nws)
         a = L.LstmSeqBwdArgs()
         a.nstreams, a.B, a.T, a.H = 2, B, T, H

@@ -291,6 +291,12 @@ void layout_of(const t2_dims& d, const Sizes& z, t2_decoder_layout* L) {
     L->wt16a = L->w16d + nd; L->wt16as = L->wt16a + na; L->wt16d = L->wt16as + na;
     L->din16 = take(BT * z.WD / 2 + 4); L->dh16 = take(BT * z.Hd / 2 + 4);
     L->gemm_ws_floats = (size_t)16 << 20;                     // 64 MiB of split-K scratch
+    // split-bf16 mode: the hoisted LSTM-input products stage both operands as three bf16 terms (6 bytes per element; the
+    // decoder LSTM's takes up to all B*T rows when the chains are not overlapped), in front of the split-K partials
+    if (get_precision() == 2) {
+        const size_t wd = std::max(z.WD, z.P), h4 = (size_t)4 * std::max(z.Ha, z.Hd);
+        L->gemm_ws_floats += align4((6 * (BT + h4) * wd + 1024) / sizeof(float));
+    }
     L->gemm_ws = take(L->gemm_ws_floats);
     // exchange space of the persistent chain kernels (chain.hip), the pass's status words at its head
     L->chain_floats = chain_fwd_ws_floats(z.NS, z.B, z.Ha, z.E, z.P, z.Hd, z.A);
@@ -674,6 +680,12 @@ void bwd_layout_of(const t2_dims& d, const Sizes& z, t2_decoder_bwd_layout* L) {
     L->dg16a = take((size_t)2 * z.B * 4 * z.Ha / 2 + 4); L->dg16d = take((size_t)z.B * 4 * z.Hd / 2 + 4);
     L->colsum_ws = take((size_t)64 * 4 * (z.Ha > z.Hd ? z.Ha : z.Hd));
     L->gemm_ws_floats = (size_t)192 << 20;                    // 768 MiB: split-K partials + bf16 operand staging (gemm.hip)
+    // split-bf16 mode: the largest weight-gradient product (dW_ih of an LSTM: K = B*T rows of dG [4H] and of its input
+    // [WD]) stages 6 bytes per operand element; 256 MiB stay for its split-K partials
+    if (get_precision() == 2) {
+        const size_t h4 = (size_t)4 * std::max(z.Ha, z.Hd), need = 6 * BT * (h4 + z.WD) + ((size_t)256 << 20);
+        L->gemm_ws_floats = std::max(L->gemm_ws_floats, align4(need / sizeof(float)));
+    }
     L->gemm_ws = take(L->gemm_ws_floats);
     // exchange space of the persistent backward chains (chain_bwd.hip); their status words are in the forward workspace
     L->chain_floats = chain_bwd_ws_floats(lsa ? CHAIN_LSA : CHAIN_SMA, z.NS, z.B, z.Ha, z.E, z.A, d.loc_filters, d.loc_kernel, z.Hd);
@@ -976,11 +988,17 @@ int t2_debug_occupy(int workgroups, int milliseconds, void* stream) {
     return 0;
 }
 int t2_set_precision(int mode) {
-    T2_REQUIRE(mode == 0 || mode == 1, "t2_set_precision: mode must be 0 (fp32) or 1 (bf16 operands)");
+    T2_REQUIRE(mode >= 0 && mode <= 2, "t2_set_precision: mode must be 0 (fp32), 1 (bf16 operands) or 2 (split-bf16 large GEMMs), not %d", mode);
     set_precision(mode);
     return 0;
 }
 int t2_get_precision(void) { return get_precision(); }
+int t2_set_gemm_split_min_mflop(int mflop) { set_gemm_split_min_mflop(mflop); return 0; }
+int t2_gemm_counts(uint64_t* out_host, int reset) {
+    T2_REQUIRE(out_host, "null argument");
+    gemm_counts(out_host, reset);
+    return 0;
+}
 int t2_set_overlap(int on) { g_overlap = on != 0; return 0; }
 int t2_set_chain(int on) { g_chain = on != 0; return 0; }
 int t2_get_chain(void) { return g_chain; }
@@ -1640,8 +1658,9 @@ int t2_gemm_ex(const t2_gemm_args* a, void* stream) {
 // so that the second figure is the matrix kernel (+ its split-K reduce) alone.
 int t2_prof_gemm(const t2_gemm_args* a, int reps, float* ms_total, float* ms_kernel, void* stream) {
     T2_REQUIRE(a && reps > 0 && ms_total && ms_kernel, "t2_prof_gemm: bad arguments");
-    T2_REQUIRE(get_precision() == 1 && a->M % 128 == 0 && a->N % 128 == 0 && a->K % 64 == 0 && (a->batch <= 1) && a->ws,
-               "t2_prof_gemm: bf16 mode, whole-tile shapes and scratch only");
+    const bool x3 = get_precision() == 2;                                  // split-bf16: three bf16 terms per operand element
+    T2_REQUIRE(get_precision() != 0 && a->M % 128 == 0 && a->N % 128 == 0 && a->K % 64 == 0 && (a->batch <= 1) && a->ws,
+               "t2_prof_gemm: bf16 or split-bf16 mode, whole-tile shapes and scratch only");
     hipStream_t s = (hipStream_t)stream;
     hipEvent_t e0, e1;
     T2_CHECK_HIP(hipEventCreate(&e0)); T2_CHECK_HIP(hipEventCreate(&e1));
@@ -1653,20 +1672,28 @@ int t2_prof_gemm(const t2_gemm_args* a, int reps, float* ms_total, float* ms_ker
     T2_CHECK_HIP(hipEventElapsedTime(ms_total, e0, e1));
     *ms_total /= reps;
     if (rc == 0) {
-        const size_t na = ((size_t)a->M * a->K * sizeof(__bf16) + 255) & ~(size_t)255, nb = ((size_t)a->N * a->K * sizeof(__bf16) + 255) & ~(size_t)255;
+        const size_t per = (x3 ? 3 : 1) * sizeof(__bf16);
+        const size_t na = ((size_t)a->M * a->K * per + 255) & ~(size_t)255, nb = ((size_t)a->N * a->K * per + 255) & ~(size_t)255;
         T2_REQUIRE(a->ws_bytes > na + nb, "t2_prof_gemm: scratch too small");
         unsigned char* w8 = reinterpret_cast<unsigned char*>(a->ws);
         __bf16* a16 = reinterpret_cast<__bf16*>(w8); __bf16* b16 = reinterpret_cast<__bf16*>(w8 + na);
         const bool akc = a->sak == 1, bkc = a->sbk == 1;
-        const bool km = !akc && !bkc && a->M % 256 == 0 && a->N % 256 == 0;      // both k-major, whole 256-tiles: copies stay k-major
-        rc = km ? stage_bf16(a->A, true, a->sak, a16, a->K, a->M, s) : stage_bf16(a->A, akc, akc ? a->sam : a->sak, a16, a->M, a->K, s);
-        if (rc == 0) rc = km ? stage_bf16(a->B, true, a->sbk, b16, a->K, a->N, s) : stage_bf16(a->B, bkc, bkc ? a->sbn : a->sbk, b16, a->N, a->K, s);
+        const bool km = !akc && !bkc && a->M % 256 == 0 && a->N % 256 == 0 &&   // both k-major, whole 256-tiles: copies stay k-major
+                        (!x3 || 6l * a->K * std::max(a->M, a->N) < (1l << 31));
+        if (x3) {
+            rc = km ? stage_split_bf16(a->A, true, a->sak, a16, a->K, a->M, 1, 64, s) : stage_split_bf16(a->A, akc, akc ? a->sam : a->sak, a16, a->M, a->K, 1, 0, s);
+            if (rc == 0) rc = km ? stage_split_bf16(a->B, true, a->sbk, b16, a->K, a->N, 2, 64, s) : stage_split_bf16(a->B, bkc, bkc ? a->sbn : a->sbk, b16, a->N, a->K, 2, 0, s);
+        } else {
+            rc = km ? stage_bf16(a->A, true, a->sak, a16, a->K, a->M, s) : stage_bf16(a->A, akc, akc ? a->sam : a->sak, a16, a->M, a->K, s);
+            if (rc == 0) rc = km ? stage_bf16(a->B, true, a->sbk, b16, a->K, a->N, s) : stage_bf16(a->B, bkc, bkc ? a->sbn : a->sbk, b16, a->N, a->K, s);
+        }
         GemmDesc g = gemm_desc();
         g.A = a->A; g.B = a->B; g.C = a->C; g.M = a->M; g.N = a->N; g.K = a->K;
         g.sam = a->sam; g.sak = a->sak; g.sbn = a->sbn; g.sbk = a->sbk; g.ldc = a->ldc;
         g.alpha = a->alpha; g.beta = a->beta; g.bias1 = a->bias; g.act = a->act; g.splitk = a->splitk;
-        g.A16 = a16; g.lda16 = km ? a->M : a->K; g.B16 = b16; g.ldb16 = km ? a->N : a->K;
-        g.a16_kmajor = g.b16_kmajor = km;
+        const long kk = x3 ? 3l * a->K : a->K;
+        g.A16 = a16; g.lda16 = km ? a->M : kk; g.B16 = b16; g.ldb16 = km ? a->N : kk;
+        g.a16_kmajor = g.b16_kmajor = km; g.split16 = x3;
         g.ws = reinterpret_cast<float*>(w8 + na + nb); g.ws_bytes = a->ws_bytes - na - nb;
         if (rc == 0) rc = gemm(g, s);
         T2_CHECK_HIP(hipEventRecord(e0, s));

@@ -15,15 +15,27 @@
 
 namespace t2 {
 
-static int g_precision = 0;       // 0: fp32 operands (parity path), 1: bf16 operands for large GEMMs
+static int g_precision = 0;       // 0: fp32 operands (parity path), 1: bf16 operands for large GEMMs, 2: split-bf16 (hi + lo) operands
 // bf16 mode: stage fp32 operands as bf16 copies when both extents reach g_stage_min (T2_GEMM_STAGE=0 switches it off,
 // T2_GEMM_STAGE_MIN overrides the extent)
 static int env_int(const char* name, int dflt) { const char* v = getenv(name); return v && *v ? atoi(v) : dflt; }
 static int g_stage = env_int("T2_GEMM_STAGE", 1);
 void set_gemm_staging(int on) { g_stage = on != 0; }
 static const int g_stage_min = env_int("T2_GEMM_STAGE_MIN", 256);
+// split-bf16 mode: a product whose 2*M*N*K is below this many MFLOP runs the exact fp32 kernel instead: three staged terms
+// and two staging launches cost 20 - 50 us whatever the shape, which the exact kernel beats up to about 2 GFLOP
+// (break-even between 1.6 and 5.4 GFLOP: profiles/r05_split_threshold.txt).  set_gemm_split_min_mflop()
+// changes it (tests of the kernels on small shapes set 0).
+constexpr int kSplitMinMflopDefault = 2147;          // 2^31 FLOP
+static double g_split_min_flop = 1e6 * kSplitMinMflopDefault;
+void set_gemm_split_min_mflop(int mflop) { g_split_min_flop = 1e6 * (mflop < 0 ? kSplitMinMflopDefault : mflop); }
 void set_precision(int p) { g_precision = p; }
 int get_precision() { return g_precision; }
+// calls of gemm() by kernel family: exact fp32, converting bf16, bf16-source on single-bf16 operands, bf16-source on split operands
+static uint64_t g_counts[4] = {0, 0, 0, 0};
+void gemm_counts(uint64_t* out, int reset) {
+    for (int i = 0; i < 4; ++i) { out[i] = g_counts[i]; if (reset) g_counts[i] = 0; }
+}
 
 namespace {
 
@@ -1156,6 +1168,81 @@ int stage_operand(const float* src, bool kc, long ld, __bf16* dst, int rows, int
     return 0;
 }
 
+// ---------------------------------------------------------------------------------------------
+// split-bf16 staging (precision mode 2): x = hi + lo with hi = RN-bf16(x), lo = RN-bf16(x - hi) (the subtraction is exact
+// in fp32), and x.w ~ hi.hi + lo.hi + hi.lo.  The three terms become ONE product of the bf16-source kernels with K' = 3K:
+// per 64-wide K-tile j the staged A holds the tiles (hi_j lo_j hi_j) and the staged B (hi_j hi_j lo_j), so the small terms
+// are accumulated (fp32) right next to their large term and the repeated hi tile is an L2 hit.  lo_slot names the slot
+// (1: A, 2: B) that takes lo.
+//   row_group == 0: K-concatenation, dst[row][3K]: source column k of term t at (k / 64) * 192 + t * 64 + k % 64
+//   row_group  > 0: the k-major copies, dst[3 rows][K]: source row r of term t at row (r / G) * 3G + t * G + r % G
+//                   (G = 64: K-tile interleave; G = rows: three whole copies, which the implicit-conv B operand of the
+//                   k-major route needs: its kernel shifts k-rows per tap inside an utterance)
+// ---------------------------------------------------------------------------------------------
+// (an |x| above 3.39e38 rounds to a bf16 infinity, so its lo part is the opposite infinity and the product NaN where the
+// exact kernel stays finite: the last 0.4 % of the fp32 range is outside this mode's contract, infinities as in fp32 give NaN/inf)
+__device__ __forceinline__ void split8(const f32x4& lo4, const f32x4& hi4, bf16x8& h, bf16x8& l) {
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        const float x = j < 4 ? lo4[j] : hi4[j - 4];
+        const __bf16 xh = (__bf16)x;
+        h[j] = xh; l[j] = (__bf16)(x - (float)xh);
+    }
+}
+// source contiguous along K (src[row * ld + k]): 8 elements per task, three 16-byte stores
+__global__ void stage_split_kc_kernel(const float* __restrict__ src, long ld, __bf16* __restrict__ dst, int rows, int K, int lo_slot, int row_group) {
+    const int k8 = K >> 3;
+    const long total = (long)rows * k8;
+    for (long t = blockIdx.x * (long)blockDim.x + threadIdx.x; t < total; t += (long)gridDim.x * blockDim.x) {
+        const long row = t / k8; const int k = (int)(t - row * k8) * 8;
+        const float* p = src + row * ld + k;
+        bf16x8 h, l;
+        split8(*reinterpret_cast<const f32x4*>(p), *reinterpret_cast<const f32x4*>(p + 4), h, l);
+        long o, step;
+        if (row_group) { o = ((row / row_group) * 3 * row_group + row % row_group) * (long)K + k; step = (long)row_group * K; }
+        else { o = row * 3 * (long)K + (k >> 6) * 192 + (k & 63); step = 64; }
+#pragma unroll
+        for (int slot = 0; slot < 3; ++slot) *reinterpret_cast<bf16x8*>(dst + o + slot * step) = slot == lo_slot ? l : h;
+    }
+}
+// source contiguous along the rows (src[k * ld + row]) -> dst[row][3K]: 64 k x 64 rows per workgroup through LDS
+__global__ __launch_bounds__(256) void stage_split_mc_kernel(const float* __restrict__ src, long ld, __bf16* __restrict__ dst, int rows, int K, int lo_slot) {
+    __shared__ float tile[64][65];
+    const int r0 = blockIdx.x * 64, k0 = blockIdx.y * 64;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const int k = (threadIdx.x >> 4) + 16 * i, r4 = (threadIdx.x & 15) * 4;
+        const f32x4 v = *reinterpret_cast<const f32x4*>(src + (long)(k0 + k) * ld + r0 + r4);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) tile[k][r4 + j] = v[j];
+    }
+    __syncthreads();
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+        const int kg = threadIdx.x & 7, row = (threadIdx.x >> 3) + 32 * i;
+        f32x4 a, b;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) { a[j] = tile[kg * 8 + j][row]; b[j] = tile[kg * 8 + 4 + j][row]; }
+        bf16x8 h, l;
+        split8(a, b, h, l);
+        __bf16* o = dst + (long)(r0 + row) * 3 * K + 3 * (long)k0 + kg * 8;
+#pragma unroll
+        for (int slot = 0; slot < 3; ++slot) *reinterpret_cast<bf16x8*>(o + slot * 64) = slot == lo_slot ? l : h;
+    }
+}
+// kc: the source is contiguous along its second index; row_group as above (0 with !kc)
+int stage_split_operand(const float* src, bool kc, long ld, __bf16* dst, int rows, int K, int lo_slot, int row_group, hipStream_t s) {
+    if (kc) {
+        long blocks = ((long)rows * (K >> 3) + 255) / 256;
+        if (blocks > 8192) blocks = 8192;
+        hipLaunchKernelGGL(stage_split_kc_kernel, dim3((unsigned)blocks), dim3(256), 0, s, src, ld, dst, rows, K, lo_slot, row_group);
+    } else {
+        hipLaunchKernelGGL(stage_split_mc_kernel, dim3(rows / 64, K / 64), dim3(256), 0, s, src, ld, dst, rows, K, lo_slot);
+    }
+    T2_LAUNCH_CHECK();
+    return 0;
+}
+
 template <int BM, int BN>
 void launch_cfg(const GemmK& g, bool akc, bool bkc, dim3 grid, hipStream_t s) {
     if (akc && bkc) hipLaunchKernelGGL((gemm_kernel<BM, BN, true, true>), grid, dim3(256), 0, s, g);
@@ -1172,6 +1259,13 @@ int stage_bf16(const float* src, bool kc, long ld, __bf16* dst, int rows, int K,
     T2_REQUIRE(rows > 0 && K > 0 && rows % 64 == 0 && K % 64 == 0 && ld % 4 == 0 && aligned16(src) && aligned16(dst),
                "stage_bf16: rows=%d K=%d ld=%ld must be whole 64-tiles of 16-byte aligned rows", rows, K, ld);
     return stage_operand(src, kc, ld, dst, rows, K, s);
+}
+
+int stage_split_bf16(const float* src, bool kc, long ld, __bf16* dst, int rows, int K, int lo_slot, int row_group, hipStream_t s) {
+    T2_REQUIRE(rows > 0 && K > 0 && rows % 64 == 0 && K % 64 == 0 && ld % 4 == 0 && aligned16(src) && aligned16(dst) &&
+               (lo_slot == 1 || lo_slot == 2) && row_group >= 0 && (!row_group || (kc && rows % row_group == 0)),
+               "stage_split_bf16: rows=%d K=%d ld=%ld must be whole 64-tiles of 16-byte aligned rows", rows, K, ld);
+    return stage_split_operand(src, kc, ld, dst, rows, K, lo_slot, row_group, s);
 }
 
 int gemm(const GemmDesc& din, hipStream_t s) {
@@ -1196,8 +1290,14 @@ int gemm(const GemmDesc& din, hipStream_t s) {
     // 128x128 tiles whenever both extents allow it (4 MFMAs per 4 LDS fragment reads); a grid that
     // would not fill the chip is completed by split-K when scratch is available, else by 64x64 tiles.
     // bf16-operand mode: large GEMMs only (both extents >= 64), conv operands need C % 8 == 0
-    const bool use_bf16 = g_precision == 1 && !d.fp32_only && d.M >= 64 && d.N >= 64 && d.K >= 64 &&
-                          (!(d.conv_a || d.conv_b) || d.conv_C % 8 == 0);
+    const bool large = !d.fp32_only && d.M >= 64 && d.N >= 64 && d.K >= 64 && (!(d.conv_a || d.conv_b) || d.conv_C % 8 == 0);
+    const bool use_bf16 = g_precision == 1 && large;
+    // split-bf16 mode: only the bf16-source kernels, on operands staged as hi / lo parts (K' = 3K, see stage_split_kc_kernel);
+    // whatever does not qualify for them below runs exactly what mode 0 runs.  Single-bf16 copies from the caller are not
+    // used; split16 marks copies that are already in the split layout of this product (t2_prof_gemm).
+    const bool want_split = g_precision == 2 && large && 2.0 * d.M * d.N * d.K >= g_split_min_flop;
+    if (g_precision == 2 && !(want_split && d.split16)) d.A16 = d.B16 = nullptr;
+    const int kmul = want_split ? 3 : 1;
     // bf16-source path: both operands staged as bf16 [rows][K] in front of the split-K scratch (or handed over by the
     // caller); pays when each staged element is reused by many tiles, i.e. when both extents are large
     bool staged = false;
@@ -1211,16 +1311,17 @@ int gemm(const GemmDesc& din, hipStream_t s) {
     static const int g_t256 = env_int("T2_GEMM_256", 1);
     const bool shape256 = g_t256 && d.M % 256 == 0 && d.N % 256 == 0 && d.K >= 128;
     const long ld_km = std::max(std::max((long)d.M, d.A16 && d.a16_kmajor ? d.lda16 : 0l), std::max((long)(d.conv_b ? d.conv_C : d.N), d.B16 && d.b16_kmajor ? d.ldb16 : 0l));
-    const bool km = shape256 && !akc && !bkc && !d.conv_a && (!d.conv_b || d.conv_C % 256 == 0) && (long)d.K * ld_km * 2 < (1l << 31);
+    const bool km = shape256 && !akc && !bkc && !d.conv_a && (!d.conv_b || d.conv_C % 256 == 0) && (long)d.K * kmul * ld_km * 2 < (1l << 31);
     if (d.A16 && (d.a16_kmajor != 0) != km) d.A16 = nullptr;
     if (d.B16 && (d.b16_kmajor != 0) != km) d.B16 = nullptr;
-    const bool conv_ok = !conv_any || (d.conv_a && d.conv_C % 64 == 0 && !d.A16 && !d.B16) || (d.conv_b && km);
-    if (use_bf16 && g_stage && conv_ok && d.batch == 1 && d.M % 128 == 0 && d.N % 128 == 0 && d.K % 64 == 0) {
+    // (split: the k-major conv_b copies are three whole stacks of the frames, so the stack height must keep k % conv_T)
+    const bool conv_ok = !conv_any || (d.conv_a && d.conv_C % 64 == 0 && !d.A16 && !d.B16) || (d.conv_b && km && (!want_split || d.K % d.conv_T == 0));
+    if ((use_bf16 || want_split) && g_stage && conv_ok && d.batch == 1 && d.M % 128 == 0 && d.N % 128 == 0 && d.K % 64 == 0) {
         // implicit-conv operands: only the frames [rows][C] are staged (the kernel shifts rows per tap)
         const size_t a_elems = d.conv_a ? (size_t)d.M * d.conv_C : (size_t)d.M * d.K;
         const size_t b_elems = d.conv_b ? (size_t)d.K * d.conv_C : (size_t)d.N * d.K;
-        const size_t need_a = d.A16 ? 0 : ((a_elems * sizeof(__bf16) + 255) & ~(size_t)255);
-        const size_t need_b = d.B16 ? 0 : ((b_elems * sizeof(__bf16) + 255) & ~(size_t)255);
+        const size_t need_a = d.A16 ? 0 : ((kmul * a_elems * sizeof(__bf16) + 255) & ~(size_t)255);
+        const size_t need_b = d.B16 ? 0 : ((kmul * b_elems * sizeof(__bf16) + 255) & ~(size_t)255);
         const bool big = (d.A16 || d.N >= g_stage_min) && (d.B16 || d.M >= g_stage_min);
         const bool ok_src = (d.A16 || g.avec) && (d.B16 || g.bvec) &&
                             (!d.A16 || (aligned16(d.A16) && d.lda16 % 8 == 0)) && (!d.B16 || (aligned16(d.B16) && d.ldb16 % 8 == 0));
@@ -1232,6 +1333,10 @@ int gemm(const GemmDesc& din, hipStream_t s) {
             if (need_a + need_b) { d.ws = reinterpret_cast<float*>(base + need_a + need_b); d.ws_bytes -= need_a + need_b; }
         }
     }
+    // split operands: from here on the product is the bf16-source kernels' K' = 3K one (conv_a: 3C channels per tap)
+    const bool split = want_split && staged, bf16_path = use_bf16 || split;
+    const int K0 = d.K, C0 = d.conv_C;
+    if (split) { d.K *= 3; if (d.conv_a) d.conv_C *= 3; }
     // the 256-tile kernel's split-K factor fills whole rounds of one workgroup per CU
     const bool use256 = staged && shape256 && (!d.conv_a || (long)d.M * d.conv_C * 2 < (1l << 31));
     int split256 = 1;
@@ -1258,7 +1363,7 @@ int gemm(const GemmDesc& din, hipStream_t s) {
     const int kch = (d.K + BK - 1) / BK;
     const bool can_split = d.ws && d.beta == 0.f && kch >= 64;
     const long tiles128 = (long)((d.M + 127) / 128) * ((d.N + 127) / 128) * d.batch;
-    const bool small = !use_bf16 && ((d.M <= 64 || d.N <= 64) || (tiles128 < 256 && !can_split));
+    const bool small = !bf16_path && ((d.M <= 64 || d.N <= 64) || (tiles128 < 256 && !can_split));
     const int BMN = small ? 64 : 128;
     const int tm = (d.M + BMN - 1) / BMN, tn = (d.N + BMN - 1) / BMN;
     int splitk = 1;
@@ -1280,7 +1385,7 @@ int gemm(const GemmDesc& din, hipStream_t s) {
     }
     if (use256) splitk = split256;
     g.kchunks = (kch + splitk - 1) / splitk;
-    if (use_bf16) g.kchunks = (g.kchunks + 3) & ~3;   // whole 64-wide chunks per split
+    if (bf16_path) g.kchunks = (g.kchunks + 3) & ~3;   // whole 64-wide chunks per split
     splitk = (kch + g.kchunks - 1) / g.kchunks;     // drop empty splits
     if (use256 && splitk > 1 && kch - (splitk - 1) * g.kchunks < 8) {   // the 256-tile kernel needs two K-tiles in every split
         --splitk;
@@ -1290,22 +1395,37 @@ int gemm(const GemmDesc& din, hipStream_t s) {
     d.splitk = splitk;
     static const int g_log = env_int("T2_GEMM_LOG", 0);      // dev: one line per product (shape, kernel, split, which operands get staged)
     if (g_log)
-        fprintf(stderr, "t2gemm M=%d N=%d K=%d batch=%d %s%s kernel=%s splitk=%d stageA=%d stageB=%d convA=%d convB=%d beta=%g\n", d.M, d.N, d.K, d.batch,
-                akc ? "A[m][k]" : "A[k][m]", bkc ? " B[n][k]" : " B[k][n]", staged ? (use256 ? (km ? "src256km" : "src256") : "src128") : use_bf16 ? "bf16conv" : small ? "f32_64" : "f32_128",
+        fprintf(stderr, "t2gemm M=%d N=%d K=%d batch=%d %s%s kernel=%s splitk=%d stageA=%d stageB=%d convA=%d convB=%d beta=%g\n", d.M, d.N, K0, d.batch,
+                akc ? "A[m][k]" : "A[k][m]", bkc ? " B[n][k]" : " B[k][n]", split ? (use256 ? (km ? "x3src256km" : "x3src256") : "x3src128") : staged ? (use256 ? (km ? "src256km" : "src256") : "src128") : use_bf16 ? "bf16conv" : small ? "f32_64" : "f32_128",
                 splitk, a16 != nullptr, b16 != nullptr, d.conv_a, d.conv_b, (double)d.beta);
     T2_REQUIRE((long)d.batch * splitk <= 65535, "gemm: batch*splitk too large (%d*%d)", d.batch, splitk);
     dim3 grid(tn, tm, d.batch * splitk);
+    ++g_counts[split ? 3 : staged ? 2 : use_bf16 ? 1 : 0];
     if (staged) {
         const bool km256 = km && use256;                   // (km implies use256 once staged; the k-major copies are [K][rows])
-        if (a16) {
-            if (d.conv_a) T2_TRY_RC(stage_operand(d.A, true, d.conv_C, a16, d.M, d.conv_C, s));
-            else if (km256) T2_TRY_RC(stage_operand(d.A, true, d.sak, a16, d.K, d.M, s));
-            else T2_TRY_RC(stage_operand(d.A, akc, akc ? d.sam : d.sak, a16, d.M, d.K, s));
-        }
-        if (b16) {
-            if (d.conv_b) T2_TRY_RC(stage_operand(d.B, true, d.conv_C, b16, d.K, d.conv_C, s));
-            else if (km256) T2_TRY_RC(stage_operand(d.B, true, d.sbk, b16, d.K, d.N, s));
-            else T2_TRY_RC(stage_operand(d.B, bkc, bkc ? d.sbn : d.sbk, b16, d.N, d.K, s));
+        if (split) {
+            const int grp = d.conv_b ? K0 : 64;            // k-major copies: K-tile interleave, or whole stacks next to conv_b
+            if (a16) {
+                if (d.conv_a) T2_TRY_RC(stage_split_operand(d.A, true, C0, a16, d.M, C0, 1, 0, s));
+                else if (km256) T2_TRY_RC(stage_split_operand(d.A, true, d.sak, a16, K0, d.M, 1, grp, s));
+                else T2_TRY_RC(stage_split_operand(d.A, akc, akc ? d.sam : d.sak, a16, d.M, K0, 1, 0, s));
+            }
+            if (b16) {
+                if (d.conv_b) T2_TRY_RC(stage_split_operand(d.B, true, C0, b16, K0, C0, 2, grp, s));
+                else if (km256) T2_TRY_RC(stage_split_operand(d.B, true, d.sbk, b16, K0, d.N, 2, grp, s));
+                else T2_TRY_RC(stage_split_operand(d.B, bkc, bkc ? d.sbn : d.sbk, b16, d.N, K0, 2, 0, s));
+            }
+        } else {
+            if (a16) {
+                if (d.conv_a) T2_TRY_RC(stage_operand(d.A, true, d.conv_C, a16, d.M, d.conv_C, s));
+                else if (km256) T2_TRY_RC(stage_operand(d.A, true, d.sak, a16, d.K, d.M, s));
+                else T2_TRY_RC(stage_operand(d.A, akc, akc ? d.sam : d.sak, a16, d.M, d.K, s));
+            }
+            if (b16) {
+                if (d.conv_b) T2_TRY_RC(stage_operand(d.B, true, d.conv_C, b16, d.K, d.conv_C, s));
+                else if (km256) T2_TRY_RC(stage_operand(d.B, true, d.sbk, b16, d.K, d.N, s));
+                else T2_TRY_RC(stage_operand(d.B, bkc, bkc ? d.sbn : d.sbk, b16, d.N, d.K, s));
+            }
         }
         const __bf16* pa = d.A16 ? d.A16 : a16; const long lda = d.A16 ? d.lda16 : d.conv_a ? d.conv_C : km256 ? d.M : d.K;
         const __bf16* pb = d.B16 ? d.B16 : b16; const long ldb = d.B16 ? d.ldb16 : d.conv_b ? d.conv_C : km256 ? d.N : d.K;

@@ -31,6 +31,9 @@ struct GemmDesc {
     int a16_kmajor, b16_kmajor;                   // the copy is k-major instead: A16[k*lda16 + m], B16[k*ldb16 + n] (conv_b: the
                                                   // frames, B16[k*ldb16 + ci]).  Only the 256-tile kernel's k-major variant reads
                                                   // such a copy (both operands k-major, whole 256-tiles); otherwise it is ignored
+    int split16;                                  // split-bf16 mode: A16 / B16 are hi / lo copies in gemm()'s own K' = 3K layout
+                                                  // (stage_split_bf16; lda16 / ldb16 = 3K, k-major: M / N); otherwise the
+                                                  // copies are single-bf16 data and that mode ignores them
     int crow_mod; long crow_mul;                  // output row = (m % crow_mod) * crow_mul + m / crow_mod (0 = identity):
                                                   // writes time-major rows (t,b) in batch-major order (b,t) or back
 };
@@ -41,8 +44,18 @@ int gemm(const GemmDesc& d, hipStream_t s);
 // bf16 copy of an fp32 operand, K contiguous: dst[row*K + k] = src[row*ld + k] (kc) or src[k*ld + row] (!kc);
 // rows % 64 == 0, K % 64 == 0, 16-byte aligned rows.  For GemmDesc::A16 / B16 shared by several products.
 int stage_bf16(const float* src, bool kc, long ld, __bf16* dst, int rows, int K, hipStream_t s);
-void set_precision(int p);   // 0 fp32 operands, 1 bf16 operands (fp32 accumulate) for large GEMMs and LSTM steps
+// hi / lo copy of an fp32 operand for the split-bf16 mode (gemm.hip, stage_split_kc_kernel): three bf16 terms per element.
+// kc && !row_group: dst[row][3K]; !kc: the same from src[k*ld + row]; row_group > 0 (kc only): dst[3 rows][K], stacked in
+// groups of row_group source rows (64 for a k-major operand).  lo_slot: 1 for an A operand, 2 for a B operand.
+int stage_split_bf16(const float* src, bool kc, long ld, __bf16* dst, int rows, int K, int lo_slot, int row_group, hipStream_t s);
+void set_precision(int p);   // 0 fp32 operands, 1 bf16 operands (fp32 accumulate) for large GEMMs and LSTM steps,
+                             // 2 split-bf16 operands (three bf16 terms, fp32-grade) for the large GEMMs, everything else as 0
 int get_precision();
+// calls of gemm() since the last reset that launched [0] an exact fp32 kernel, [1] the converting bf16 kernel, [2] a
+// bf16-source kernel on single-bf16 operands, [3] a bf16-source kernel on split operands (host counters)
+void gemm_counts(uint64_t* out, int reset);
+// split-bf16 mode: products below 2*M*N*K = mflop * 1e6 run the exact fp32 kernel (mflop < 0: the built-in default)
+void set_gemm_split_min_mflop(int mflop);
 void set_gemm_staging(int on);   // bf16 mode: stage fp32 operands as bf16 copies for the bf16-source kernel (default on)
 
 // ------------------------------------------------------------------ LSTM (lstm.hip)

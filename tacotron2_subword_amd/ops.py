@@ -89,12 +89,21 @@ class DecoderPass:
 
     def __init__(self, dims, B, T, Tin, Tsub, device):
         self.dims, self.B, self.T, self.Tin, self.Tsub = dims, B, T, Tin, Tsub
+        self.precision = L.get_precision()                 # the layout (scratch sizes) belongs to this mode
         self.layout = L.decoder_layout(dims, B, T, Tin, Tsub)
         self.ws = torch.empty(self.layout.total_floats, dtype=torch.float32, device=device)
         self.mel = torch.empty(B, T, dims.n_mel, dtype=torch.float32, device=device)
         self.gate = torch.empty(B, T, dtype=torch.float32, device=device)
         self.align = torch.empty(B, T, Tin, dtype=torch.float32, device=device)
         self.align_sub = torch.empty(B, T, Tsub, dtype=torch.float32, device=device)
+
+    def check_precision(self, who: str) -> None:
+        """The library recomputes the layout from the mode in force and the C ABI carries no workspace size: a pass sized in
+        one mode must not be used in another."""
+        now = L.get_precision()
+        if now != self.precision:
+            raise RuntimeError(f"t2amd: {who}: this pass was allocated in precision mode {self.precision!r}, the library is in "
+                               f"{now!r} now; workspaces are sized per mode (set_precision before the pass is created)")
 
     def chain_status(self):
         """Status words of the persistent kernels — (forward attention chain, forward decoder-LSTM chain, backward
@@ -122,6 +131,7 @@ def decoder_forward(W: L.DecoderWeights, dims: L.Dims, memory, memory_sub, mem_l
     if dp is None:
         dp = DecoderPass(dims, B, T, Tin, Tsub, memory.device)
     assert (dp.B, dp.T, dp.Tin, dp.Tsub) == (B, T, Tin, Tsub)
+    dp.check_precision("decoder_forward")
     ml, sl = _i32(mem_lengths), _i32(sub_lengths)
     a = L.DecoderFwdArgs(B, T, Tin, Tsub, L.ptr(memory), L.ptr(memory_sub), L.ptr(ml), L.ptr(sl), L.ptr(mels),
                          L.ptr(dp.mel), L.ptr(dp.gate), L.ptr(dp.align), L.ptr(dp.align_sub), L.ptr(dp.ws),
@@ -135,6 +145,7 @@ def decoder_prologue(W: L.DecoderWeights, dims: L.Dims, dp: DecoderPass, mels, *
                      seed: int) -> None:
     """The part of decoder_forward that needs no encoder output (teacher inputs, prenets, hoisted attention-LSTM input
     GEMMs, bf16 shadows), on the CURRENT stream: t2_decoder_forward phase 1."""
+    dp.check_precision("decoder_prologue")
     a = L.DecoderFwdArgs(dp.B, dp.T, dp.Tin, dp.Tsub, None, None, None, None, L.ptr(mels),
                          L.ptr(dp.mel), L.ptr(dp.gate), L.ptr(dp.align), L.ptr(dp.align_sub), L.ptr(dp.ws),
                          int(training), int(prenet_dropout), seed, 1)
@@ -154,6 +165,7 @@ def decoder_backward(W: L.DecoderWeights, P: dict, dims: L.Dims, dp: DecoderPass
     library's side stream (d_memory* are complete on the current stream); the tensors that stream still uses are appended
     to the list and the caller must call side_join() before reading a gradient or dropping the list."""
     check_chain_status()
+    dp.check_precision("decoder_backward")
     single = dims.n_streams == 1
     dev = memory.device
     G = {prefix + k: torch.empty_like(P[prefix + k]) for k in L.decoder_param_keys(dims.attention_kind, single)}
@@ -181,6 +193,7 @@ def decoder_infer(W: L.DecoderWeights, dims: L.Dims, memory, memory_sub, *, max_
     B, Tin, _ = memory.shape
     Tsub = 1 if memory_sub is None else memory_sub.shape[1]
     dp = DecoderPass(dims, B, max_steps, Tin, Tsub, memory.device)
+    dp.check_precision("decoder_infer")
     stop = torch.empty(B, dtype=torch.int32, device=memory.device)
     done = torch.empty(1, dtype=torch.int32, device=memory.device)
     steps = C.c_int(0)
