@@ -385,8 +385,28 @@ int t2_gemm_ex(const t2_gemm_args* a, void* stream);
  * ms_total as t2_gemm_ex runs it (fp32 operands in: bf16 staging casts included), ms_kernel with both bf16 operand copies
  * made beforehand (the matrix kernel and its split-K reduce alone).  bf16 mode or split-bf16 mode (there: the hi / lo
  * staging, resp. both hi / lo copies made beforehand; scratch for 6 bytes per operand element), M, N multiples of 128, K of
- * 64, scratch given; refused in mode 0. */
+ * 64, scratch given; refused in mode 0, and for a product that the mode in force does not run on a bf16-source kernel
+ * reading both copies (t2_gemm_plan tells): nothing else is timed under these names. */
 int t2_prof_gemm(const t2_gemm_args* a, int reps, float* ms_total, float* ms_kernel, void* stream);
+/* What the GEMM layer would do with a product, decided on the host: launches nothing, needs no device, answers for the
+ * precision mode, split threshold and staging switch in force.  The pointers of `a` are looked at for their alignment only.
+ * opts (nullable) carries what t2_gemm_args cannot: an implicit-conv operand, fp32_only, and bf16 copies the caller would
+ * hand over (a16 / b16 != 0: a copy with leading dimension lda16 / ldb16, k-major or K-contiguous; split16: the copies are
+ * hi / lo parts in the split-bf16 layout).  A product the GEMM layer refuses returns its error code and message. */
+enum { T2_GEMM_F32_64 = 0, T2_GEMM_F32_128, T2_GEMM_BF16CONV, T2_GEMM_SRC128, T2_GEMM_SRC256, T2_GEMM_SRC256KM };   /* kernel */
+enum { T2_GEMM_OPERAND_FP32 = 0, T2_GEMM_OPERAND_STAGED, T2_GEMM_OPERAND_CALLER };                                  /* a_src, b_src */
+typedef struct t2_gemm_plan_opts {
+    int conv_a, conv_b, conv_T, conv_C, fp32_only;
+    int a16, b16; long lda16, ldb16; int a16_kmajor, b16_kmajor, split16;
+} t2_gemm_plan_opts;
+typedef struct t2_gemm_plan_info {
+    int kernel; const char* name;        /* name: as T2_GEMM_LOG prints it, "x3" in front when split (static string) */
+    int split;                           /* the kernel reads hi / lo copies, K' = 3K */
+    int splitk, kchunks;                 /* split-K factor; 16-wide K-chunks per split */
+    int a_src, b_src;                    /* the kernel reads the fp32 operand, a copy staged into the scratch, the caller's copy */
+    size_t stage_bytes_a, stage_bytes_b; /* scratch the staged copies take in front of the split-K partials */
+} t2_gemm_plan_info;
+int t2_gemm_plan(const t2_gemm_args* a, const t2_gemm_plan_opts* opts, t2_gemm_plan_info* out);
 /* out[n] = sum_m x[m*ld + n]; scratch >= 64*N floats */
 int t2_colsum(const float* x, long ld, int M, int N, float* out, float* scratch, void* stream);
 int t2_mask_btc(float* x, int B, int T, int C, const int32_t* lengths, float fill, void* stream);

@@ -149,13 +149,24 @@ class GemmArgs(C.Structure):
                 ("crow_mod", C.c_int), ("crow_mul", C.c_long), ("ws", C.c_void_p), ("ws_bytes", C.c_size_t), ("splitk", C.c_int)]
 
 
+class GemmPlanOpts(C.Structure):
+    _fields_ = [("conv_a", C.c_int), ("conv_b", C.c_int), ("conv_T", C.c_int), ("conv_C", C.c_int), ("fp32_only", C.c_int),
+                ("a16", C.c_int), ("b16", C.c_int), ("lda16", C.c_long), ("ldb16", C.c_long),
+                ("a16_kmajor", C.c_int), ("b16_kmajor", C.c_int), ("split16", C.c_int)]
+
+
+class GemmPlanInfo(C.Structure):
+    _fields_ = [("kernel", C.c_int), ("name", C.c_char_p), ("split", C.c_int), ("splitk", C.c_int), ("kchunks", C.c_int),
+                ("a_src", C.c_int), ("b_src", C.c_int), ("stage_bytes_a", C.c_size_t), ("stage_bytes_b", C.c_size_t)]
+
+
 # every symbol include/t2amd.h declares (tests/test_abi.py checks the library exports them all)
 ABI_VERSION = 4      # include/t2amd.h T2_ABI_VERSION: struct sizes below match that header and nothing else
 
 EXPORTS = ["t2_last_error", "t2_version", "t2_chain_status", "t2_chain_status_clear", "t2_debug_report_abort", "t2_debug_occupy", "t2_chain_claimed", "t2_set_precision", "t2_get_precision", "t2_gemm_counts", "t2_set_gemm_split_min_mflop", "t2_set_overlap", "t2_set_chain", "t2_get_chain", "t2_set_chain_bwd", "t2_set_gemm_staging", "t2_side_join", "t2_decoder_layout_query", "t2_decoder_forward", "t2_decoder_infer",
            "t2_decoder_bwd_layout_query", "t2_decoder_backward", "t2_prof_enable", "t2_prof_collect", "t2_adam_chunks", "t2_adam_step", "t2_adam_norm",
            "t2_conv_bn_forward", "t2_conv_bn_backward", "t2_embedding_forward", "t2_embedding_backward",
-           "t2_lstm_seq_forward", "t2_lstm_seq_backward", "t2_lstm_seq_chain_ws_floats", "t2_gemm_ex", "t2_prof_gemm", "t2_colsum", "t2_mask_btc",
+           "t2_lstm_seq_forward", "t2_lstm_seq_backward", "t2_lstm_seq_chain_ws_floats", "t2_gemm_ex", "t2_prof_gemm", "t2_gemm_plan", "t2_colsum", "t2_mask_btc",
            "t2_finalize_bct", "t2_mask_bt", "t2_gemm", "t2_rng_keep_mask", "t2_rng_normal"]
 
 _lib = None
@@ -195,6 +206,7 @@ def lib() -> C.CDLL:
         L.t2_lstm_seq_chain_ws_floats.argtypes, L.t2_lstm_seq_chain_ws_floats.restype = [C.c_int, C.c_int, C.c_int, C.c_int], C.c_size_t
         L.t2_gemm_ex.argtypes = [C.POINTER(GemmArgs), C.c_void_p]
         L.t2_prof_gemm.argtypes = [C.POINTER(GemmArgs), C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_void_p]
+        L.t2_gemm_plan.argtypes = [C.POINTER(GemmArgs), C.POINTER(GemmPlanOpts), C.POINTER(GemmPlanInfo)]
         L.t2_colsum.argtypes = [C.c_void_p, C.c_long, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
         L.t2_mask_btc.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_float, C.c_void_p]
         L.t2_prof_enable.argtypes = [C.c_int]
@@ -423,6 +435,16 @@ def gemm_counts(reset: bool = False):
     out = (C.c_uint64 * 4)()
     check(lib().t2_gemm_counts(out, int(bool(reset))))
     return tuple(int(v) for v in out)
+
+
+def gemm_plan(args: GemmArgs, **opts) -> dict:
+    """What the GEMM layer would do with the product `args` in the modes in force (t2_gemm_plan: nothing is launched, no
+    device needed; the pointers count for their alignment only).  opts: the fields of t2_gemm_plan_opts.  Operand sources:
+    0 fp32 operand, 1 copy staged into the scratch, 2 the caller's copy."""
+    o, info = GemmPlanOpts(**opts), GemmPlanInfo()
+    check(lib().t2_gemm_plan(C.byref(args), C.byref(o), C.byref(info)))
+    return dict(kernel=info.kernel, name=info.name.decode(), split=bool(info.split), splitk=info.splitk, kchunks=info.kchunks,
+                a_src=info.a_src, b_src=info.b_src, stage_bytes_a=info.stage_bytes_a, stage_bytes_b=info.stage_bytes_b)
 
 
 def set_gemm_split_min_mflop(mflop: int = -1) -> None:

@@ -1642,69 +1642,73 @@ int t2_lstm_seq_backward(const t2_lstm_seq_bwd_args* a, void* stream) {
     return 0;
 }
 
+static GemmDesc desc_of(const t2_gemm_args& a) {
+    GemmDesc g = gemm_desc();
+    g.A = a.A; g.B = a.B; g.C = a.C; g.M = a.M; g.N = a.N; g.K = a.K;
+    g.sam = a.sam; g.sak = a.sak; g.sbn = a.sbn; g.sbk = a.sbk; g.ldc = a.ldc;
+    g.batch = a.batch > 0 ? a.batch : 1; g.bsA = a.bsA; g.bsB = a.bsB; g.bsC = a.bsC;
+    g.alpha = a.alpha; g.beta = a.beta; g.bias1 = a.bias; g.act = a.act;
+    g.crow_mod = a.crow_mod; g.crow_mul = a.crow_mul;
+    g.ws = a.ws; g.ws_bytes = a.ws_bytes; g.splitk = a.splitk;
+    return g;
+}
 int t2_gemm_ex(const t2_gemm_args* a, void* stream) {
     T2_REQUIRE(a, "null argument");
-    GemmDesc g = gemm_desc();
-    g.A = a->A; g.B = a->B; g.C = a->C; g.M = a->M; g.N = a->N; g.K = a->K;
-    g.sam = a->sam; g.sak = a->sak; g.sbn = a->sbn; g.sbk = a->sbk; g.ldc = a->ldc;
-    g.batch = a->batch > 0 ? a->batch : 1; g.bsA = a->bsA; g.bsB = a->bsB; g.bsC = a->bsC;
-    g.alpha = a->alpha; g.beta = a->beta; g.bias1 = a->bias; g.act = a->act;
-    g.crow_mod = a->crow_mod; g.crow_mul = a->crow_mul;
-    g.ws = a->ws; g.ws_bytes = a->ws_bytes; g.splitk = a->splitk;
-    return gemm(g, (hipStream_t)stream);
+    return gemm(desc_of(*a), (hipStream_t)stream);
+}
+int t2_gemm_plan(const t2_gemm_args* a, const t2_gemm_plan_opts* o, t2_gemm_plan_info* out) {
+    T2_REQUIRE(a && out, "null argument");
+    GemmDesc g = desc_of(*a);
+    if (o) {
+        g.conv_a = o->conv_a; g.conv_b = o->conv_b; g.conv_T = o->conv_T; g.conv_C = o->conv_C; g.fp32_only = o->fp32_only;
+        const __bf16* copy = reinterpret_cast<const __bf16*>(uintptr_t(256));          // only its alignment is looked at
+        if (o->a16) { g.A16 = copy; g.lda16 = o->lda16; g.a16_kmajor = o->a16_kmajor; }
+        if (o->b16) { g.B16 = copy; g.ldb16 = o->ldb16; g.b16_kmajor = o->b16_kmajor; }
+        g.split16 = o->split16;
+    }
+    GemmPlan p;
+    T2_TRY(gemm_plan(g, &p));
+    *out = t2_gemm_plan_info{(int)p.kernel, gemm_plan_name(p), p.split, p.splitk, p.kchunks, (int)p.a.src, (int)p.b.src, p.a.bytes, p.b.bytes};
+    return 0;
 }
 // bench.py's GEMM roofline figure: `reps` launches of one product bracketed by HIP events on the launch stream, once as
 // t2_gemm_ex runs it (fp32 operands in, staging casts included) and once with both bf16 operand copies made beforehand,
 // so that the second figure is the matrix kernel (+ its split-K reduce) alone.
+static int time_gemm(const GemmDesc& g, int reps, float* ms, hipStream_t s) {
+    hipEvent_t e0, e1;
+    T2_CHECK_HIP(hipEventCreate(&e0)); T2_CHECK_HIP(hipEventCreate(&e1));
+    int rc = gemm(g, s);                                                  // warm-up
+    T2_CHECK_HIP(hipEventRecord(e0, s));
+    for (int i = 0; i < reps && rc == 0; ++i) rc = gemm(g, s);
+    T2_CHECK_HIP(hipEventRecord(e1, s));
+    T2_CHECK_HIP(hipEventSynchronize(e1));
+    T2_CHECK_HIP(hipEventElapsedTime(ms, e0, e1));
+    *ms /= reps;
+    hipEventDestroy(e0); hipEventDestroy(e1);
+    return rc;
+}
 int t2_prof_gemm(const t2_gemm_args* a, int reps, float* ms_total, float* ms_kernel, void* stream) {
     T2_REQUIRE(a && reps > 0 && ms_total && ms_kernel, "t2_prof_gemm: bad arguments");
-    const bool x3 = get_precision() == 2;                                  // split-bf16: three bf16 terms per operand element
     T2_REQUIRE(get_precision() != 0 && a->M % 128 == 0 && a->N % 128 == 0 && a->K % 64 == 0 && (a->batch <= 1) && a->ws,
                "t2_prof_gemm: bf16 or split-bf16 mode, whole-tile shapes and scratch only");
     hipStream_t s = (hipStream_t)stream;
-    hipEvent_t e0, e1;
-    T2_CHECK_HIP(hipEventCreate(&e0)); T2_CHECK_HIP(hipEventCreate(&e1));
-    int rc = t2_gemm_ex(a, stream);                                       // warm-up
-    T2_CHECK_HIP(hipEventRecord(e0, s));
-    for (int i = 0; i < reps && rc == 0; ++i) rc = t2_gemm_ex(a, stream);
-    T2_CHECK_HIP(hipEventRecord(e1, s));
-    T2_CHECK_HIP(hipEventSynchronize(e1));
-    T2_CHECK_HIP(hipEventElapsedTime(ms_total, e0, e1));
-    *ms_total /= reps;
-    if (rc == 0) {
-        const size_t per = (x3 ? 3 : 1) * sizeof(__bf16);
-        const size_t na = ((size_t)a->M * a->K * per + 255) & ~(size_t)255, nb = ((size_t)a->N * a->K * per + 255) & ~(size_t)255;
-        T2_REQUIRE(a->ws_bytes > na + nb, "t2_prof_gemm: scratch too small");
-        unsigned char* w8 = reinterpret_cast<unsigned char*>(a->ws);
-        __bf16* a16 = reinterpret_cast<__bf16*>(w8); __bf16* b16 = reinterpret_cast<__bf16*>(w8 + na);
-        const bool akc = a->sak == 1, bkc = a->sbk == 1;
-        const bool km = !akc && !bkc && a->M % 256 == 0 && a->N % 256 == 0 &&   // both k-major, whole 256-tiles: copies stay k-major
-                        (!x3 || 6l * a->K * std::max(a->M, a->N) < (1l << 31));
-        if (x3) {
-            rc = km ? stage_split_bf16(a->A, true, a->sak, a16, a->K, a->M, 1, 64, s) : stage_split_bf16(a->A, akc, akc ? a->sam : a->sak, a16, a->M, a->K, 1, 0, s);
-            if (rc == 0) rc = km ? stage_split_bf16(a->B, true, a->sbk, b16, a->K, a->N, 2, 64, s) : stage_split_bf16(a->B, bkc, bkc ? a->sbn : a->sbk, b16, a->N, a->K, 2, 0, s);
-        } else {
-            rc = km ? stage_bf16(a->A, true, a->sak, a16, a->K, a->M, s) : stage_bf16(a->A, akc, akc ? a->sam : a->sak, a16, a->M, a->K, s);
-            if (rc == 0) rc = km ? stage_bf16(a->B, true, a->sbk, b16, a->K, a->N, s) : stage_bf16(a->B, bkc, bkc ? a->sbn : a->sbk, b16, a->N, a->K, s);
-        }
-        GemmDesc g = gemm_desc();
-        g.A = a->A; g.B = a->B; g.C = a->C; g.M = a->M; g.N = a->N; g.K = a->K;
-        g.sam = a->sam; g.sak = a->sak; g.sbn = a->sbn; g.sbk = a->sbk; g.ldc = a->ldc;
-        g.alpha = a->alpha; g.beta = a->beta; g.bias1 = a->bias; g.act = a->act; g.splitk = a->splitk;
-        const long kk = x3 ? 3l * a->K : a->K;
-        g.A16 = a16; g.lda16 = km ? a->M : kk; g.B16 = b16; g.ldb16 = km ? a->N : kk;
-        g.a16_kmajor = g.b16_kmajor = km; g.split16 = x3;
-        g.ws = reinterpret_cast<float*>(w8 + na + nb); g.ws_bytes = a->ws_bytes - na - nb;
-        if (rc == 0) rc = gemm(g, s);
-        T2_CHECK_HIP(hipEventRecord(e0, s));
-        for (int i = 0; i < reps && rc == 0; ++i) rc = gemm(g, s);
-        T2_CHECK_HIP(hipEventRecord(e1, s));
-        T2_CHECK_HIP(hipEventSynchronize(e1));
-        T2_CHECK_HIP(hipEventElapsedTime(ms_kernel, e0, e1));
-        *ms_kernel /= reps;
-    }
-    hipEventDestroy(e0); hipEventDestroy(e1);
-    return rc;
+    GemmDesc g = desc_of(*a);
+    GemmPlan p, q;
+    T2_TRY(gemm_plan(g, &p));
+    T2_REQUIRE(p.a.src == GemmSrc::staged && p.b.src == GemmSrc::staged, "t2_prof_gemm: refused, gemm() runs this product on kernel %s, which stages no bf16 copies", gemm_plan_name(p));
+    T2_TRY(time_gemm(g, reps, ms_total, s));
+    // the copies as the plan lays them out, made once in front of the scratch and handed over
+    unsigned char* w8 = reinterpret_cast<unsigned char*>(a->ws);
+    __bf16* a16 = reinterpret_cast<__bf16*>(w8); __bf16* b16 = reinterpret_cast<__bf16*>(w8 + p.a.bytes);
+    T2_TRY(stage_planned(g.A, p.a, p.split, a16, s));
+    T2_TRY(stage_planned(g.B, p.b, p.split, b16, s));
+    g.A16 = a16; g.lda16 = p.a.ld; g.B16 = b16; g.ldb16 = p.b.ld;
+    g.a16_kmajor = g.b16_kmajor = p.kernel == GemmKernel::src256km; g.split16 = p.split;
+    g.ws = reinterpret_cast<float*>(w8 + p.a.bytes + p.b.bytes); g.ws_bytes = a->ws_bytes - p.a.bytes - p.b.bytes;
+    T2_TRY(gemm_plan(g, &q));
+    T2_REQUIRE(q.kernel == p.kernel && q.split == p.split && q.a.src == GemmSrc::caller && q.b.src == GemmSrc::caller,
+               "t2_prof_gemm: refused, with both copies handed over gemm() would run kernel %s and not read both", gemm_plan_name(q));
+    return time_gemm(g, reps, ms_kernel, s);
 }
 int t2_colsum(const float* x, long ld, int M, int N, float* out, float* scratch, void* stream) {
     return colsum(x, ld, M, N, out, nullptr, scratch, (hipStream_t)stream);

@@ -16,12 +16,11 @@
 namespace t2 {
 
 static int g_precision = 0;       // 0: fp32 operands (parity path), 1: bf16 operands for large GEMMs, 2: split-bf16 (hi + lo) operands
-// bf16 mode: stage fp32 operands as bf16 copies when both extents reach g_stage_min (T2_GEMM_STAGE=0 switches it off,
-// T2_GEMM_STAGE_MIN overrides the extent)
+// bf16 mode: stage fp32 operands as bf16 copies when both extents reach kStageMin (T2_GEMM_STAGE=0 switches it off)
 static int env_int(const char* name, int dflt) { const char* v = getenv(name); return v && *v ? atoi(v) : dflt; }
 static int g_stage = env_int("T2_GEMM_STAGE", 1);
 void set_gemm_staging(int on) { g_stage = on != 0; }
-static const int g_stage_min = env_int("T2_GEMM_STAGE_MIN", 256);
+constexpr int kStageMin = 256;
 // split-bf16 mode: a product whose 2*M*N*K is below this many MFLOP runs the exact fp32 kernel instead: three staged terms
 // and two staging launches cost 20 - 50 us whatever the shape, which the exact kernel beats up to about 2 GFLOP
 // (break-even between 1.6 and 5.4 GFLOP: profiles/r05_split_threshold.txt).  set_gemm_split_min_mflop()
@@ -767,14 +766,14 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_bf16src_kernel(GemmK g, con
 }
 
 template <bool CONV_A, int WM, int WN, int TM, int TN, int PF>
-int launch_bf16src(const GemmK& g, const __bf16* pa, long lda, const __bf16* pb, long ldb, int splitk, hipStream_t s) {
+int launch_bf16src(const GemmK& g, const __bf16* pa, long lda, const __bf16* pb, long ldb, dim3 grid, hipStream_t s) {
     constexpr int BM = 32 * TM * WM, BN = 32 * TN * WN;
     const size_t smem = (size_t)2 * (BM + BN) * PK16 * sizeof(__bf16);
     T2_TRY_RC(t2_allow_dynamic_lds(reinterpret_cast<const void*>(gemm_bf16src_kernel<CONV_A, WM, WN, TM, TN, PF>), smem));   // (per device and kernel)
     GemmK gk = g;
     static const int swz = getenv("T2_GEMM_XCD") ? atoi(getenv("T2_GEMM_XCD")) : 1;
-    gk.xcd_swizzle = swz && ((g.d.N / BN) * (g.d.M / BM)) % 8 == 0 && (g.d.M / BM) >= 8;
-    hipLaunchKernelGGL((gemm_bf16src_kernel<CONV_A, WM, WN, TM, TN, PF>), dim3(g.d.N / BN, g.d.M / BM, splitk), dim3(64 * WM * WN), smem, s, gk, pa, lda, pb, ldb);
+    gk.xcd_swizzle = swz && (grid.x * grid.y) % 8 == 0 && grid.y >= 8;
+    hipLaunchKernelGGL((gemm_bf16src_kernel<CONV_A, WM, WN, TM, TN, PF>), grid, dim3(64 * WM * WN), smem, s, gk, pa, lda, pb, ldb);
     T2_LAUNCH_CHECK();
     return 0;
 }
@@ -1111,13 +1110,12 @@ __global__ __launch_bounds__(512) void gemm_bf16src256_kernel(GemmK g, const __b
 }
 
 template <bool CONV_A, bool KM, bool CONV_B>
-int launch_bf16src256(const GemmK& g, const __bf16* pa, long lda, const __bf16* pb, long ldb, int splitk, hipStream_t s) {
+int launch_bf16src256(const GemmK& g, const __bf16* pa, long lda, const __bf16* pb, long ldb, dim3 grid, hipStream_t s) {
     constexpr size_t smem = 128 * 1024;
     T2_TRY_RC(t2_allow_dynamic_lds(reinterpret_cast<const void*>(gemm_bf16src256_kernel<CONV_A, KM, CONV_B>), smem));
     GemmK gk = g;
-    const int gx = g.d.N / 256, gy = g.d.M / 256;
-    gk.xcd_swizzle = (gx * gy) % 8 == 0 && gy >= 4;
-    hipLaunchKernelGGL((gemm_bf16src256_kernel<CONV_A, KM, CONV_B>), dim3(gx, gy, splitk), dim3(512), smem, s, gk, pa, lda, pb, ldb);
+    gk.xcd_swizzle = (grid.x * grid.y) % 8 == 0 && grid.y >= 4;
+    hipLaunchKernelGGL((gemm_bf16src256_kernel<CONV_A, KM, CONV_B>), grid, dim3(512), smem, s, gk, pa, lda, pb, ldb);
     T2_LAUNCH_CHECK();
     return 0;
 }
@@ -1243,15 +1241,99 @@ int stage_split_operand(const float* src, bool kc, long ld, __bf16* dst, int row
     return 0;
 }
 
-template <int BM, int BN>
-void launch_cfg(const GemmK& g, bool akc, bool bkc, dim3 grid, hipStream_t s) {
-    if (akc && bkc) hipLaunchKernelGGL((gemm_kernel<BM, BN, true, true>), grid, dim3(256), 0, s, g);
-    else if (akc && !bkc) hipLaunchKernelGGL((gemm_kernel<BM, BN, true, false>), grid, dim3(256), 0, s, g);
-    else if (!akc && bkc) hipLaunchKernelGGL((gemm_kernel<BM, BN, false, true>), grid, dim3(256), 0, s, g);
-    else hipLaunchKernelGGL((gemm_kernel<BM, BN, false, false>), grid, dim3(256), 0, s, g);
+inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+inline size_t round256(size_t n) { return (n + 255) & ~(size_t)255; }
+
+int check_gemm(const GemmDesc& d) {
+    T2_REQUIRE(d.M > 0 && d.N > 0 && d.K > 0 && d.batch > 0, "gemm: bad shape M=%d N=%d K=%d batch=%d", d.M, d.N, d.K, d.batch);
+    if (d.conv_a || d.conv_b) {
+        T2_REQUIRE(d.conv_T > 0 && d.conv_C > 0 && d.conv_C % 4 == 0 && !(d.conv_a && d.conv_b), "gemm: bad implicit-conv operand (T=%d C=%d)", d.conv_T, d.conv_C);
+        T2_REQUIRE(d.batch == 1, "gemm: implicit-conv operands need batch == 1");
+        if (d.conv_a) T2_REQUIRE(d.K % d.conv_C == 0 && aligned16(d.A), "gemm: conv A operand: K=%d C=%d", d.K, d.conv_C);
+        if (d.conv_b) T2_REQUIRE(d.N % d.conv_C == 0 && aligned16(d.B), "gemm: conv B operand: N=%d C=%d", d.N, d.conv_C);
+    }
+    T2_REQUIRE(d.conv_a || d.sam == 1 || d.sak == 1, "gemm: A needs one unit stride (sam=%ld sak=%ld)", d.sam, d.sak);
+    T2_REQUIRE(d.conv_b || d.sbn == 1 || d.sbk == 1, "gemm: B needs one unit stride (sbn=%ld sbk=%ld)", d.sbn, d.sbk);
+    T2_REQUIRE(d.drop_p == 0.f || (d.batch == 1 && (long)d.M * d.N < (1l << 32)), "gemm: dropout epilogue needs batch==1 and M*N < 2^32");
+    return 0;
 }
 
-inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+// The split-K factor of a kernel family (`tiles` workgroups without it, kch 16-wide K-chunks), clamped by the scratch
+int choose_splitk(const GemmDesc& d, bool tile256, long tiles, int kch, size_t ws_bytes) {
+    if (!(d.ws && d.beta == 0.f)) return 1;
+    int sp = 1;
+    if (tile256) {
+        // the 256-tile kernels: the factor that fills whole rounds of one workgroup per CU (a forced one leaves two K-tiles per split)
+        const int nkt = kch / 4;
+        if (d.splitk > 0) sp = std::min(d.splitk, std::max(1, nkt / 2));
+        else if (tiles < 512) {
+            double best = 0.0;
+            for (int c = 1; c <= 16; ++c) {
+                if (c > 1 && nkt / c < 16) break;
+                const long wgs = tiles * c, rounds = (wgs + 255) / 256;
+                const double eff = (double)wgs / (256.0 * rounds);
+                if (eff > best * 1.05) { best = eff; sp = c; }
+            }
+        }
+    } else if (d.splitk > 0) sp = d.splitk;
+    // fewer than two tile-waves over the 256 CUs and a long K: split so that every CU holds several workgroups
+    // (a lone 128x128 workgroup per CU cannot cover its own operand latency)
+    else if (tiles < 512 && kch >= 64) sp = std::min((int)((1024 + tiles - 1) / tiles), kch / 16);
+    const size_t per = (size_t)d.batch * d.M * d.N * sizeof(float);
+    if ((size_t)sp * per > ws_bytes) sp = (int)(ws_bytes / per);
+    return std::max(sp, 1);
+}
+
+int run_gemm(const GemmDesc& d, const GemmPlan& p, hipStream_t s) {
+    // the descriptor as the kernels take it: the plan's K / conv_C / splitk, the partials behind the staged copies, the
+    // implied strides of an implicit-conv operand and the default dropout row stride filled in
+    GemmK g{};
+    g.d = d;
+    g.kchunks = p.kchunks; g.avec = p.avec; g.bvec = p.bvec;
+    if (d.conv_a) { g.d.sam = 0; g.d.sak = 1; }
+    if (d.conv_b) { g.d.sbk = 0; g.d.sbn = 1; }
+    if (d.drop_mstride == 0) g.d.drop_mstride = (uint32_t)d.N;
+    g.d.K = p.K; g.d.conv_C = p.conv_C; g.d.splitk = p.splitk;
+    const size_t staged = p.a.bytes + p.b.bytes;
+    if (staged) { g.d.ws = reinterpret_cast<float*>(reinterpret_cast<unsigned char*>(d.ws) + staged); g.d.ws_bytes = d.ws_bytes - staged; }
+    const int tile = p.kernel == GemmKernel::f32_64 ? 64 : p.kernel >= GemmKernel::src256 ? 256 : 128;
+    const dim3 grid((d.N + tile - 1) / tile, (d.M + tile - 1) / tile, d.batch * p.splitk);
+    if (gemm_reads_bf16_copies(p.kernel)) {
+        // both operands as bf16 copies: the caller's, or staged in front of the split-K scratch
+        __bf16* a16 = reinterpret_cast<__bf16*>(d.ws), * b16 = reinterpret_cast<__bf16*>(reinterpret_cast<unsigned char*>(d.ws) + p.a.bytes);
+        if (p.a.src == GemmSrc::staged) T2_TRY_RC(stage_planned(d.A, p.a, p.split, a16, s));
+        if (p.b.src == GemmSrc::staged) T2_TRY_RC(stage_planned(d.B, p.b, p.split, b16, s));
+        const __bf16* pa = p.a.src == GemmSrc::caller ? d.A16 : a16, * pb = p.b.src == GemmSrc::caller ? d.B16 : b16;
+        // 128x128 block tile, two k-steps in flight.  Measured alternatives (same template, other parameters): 256x128 with
+        // 8 waves 5-12 % slower, 256x256 with 128x64 wave tiles and one k-step in flight 4.6x slower (one workgroup per CU:
+        // nothing overlaps its barriers) — the kernel is bound by latency hiding, not by operand bytes per CU
+        if (p.kernel == GemmKernel::src256km && d.conv_b) T2_TRY_RC((launch_bf16src256<false, true, true>(g, pa, p.a.ld, pb, p.b.ld, grid, s)));
+        else if (p.kernel == GemmKernel::src256km) T2_TRY_RC((launch_bf16src256<false, true, false>(g, pa, p.a.ld, pb, p.b.ld, grid, s)));
+        else if (p.kernel == GemmKernel::src256 && d.conv_a) T2_TRY_RC((launch_bf16src256<true, false, false>(g, pa, p.a.ld, pb, p.b.ld, grid, s)));
+        else if (p.kernel == GemmKernel::src256) T2_TRY_RC((launch_bf16src256<false, false, false>(g, pa, p.a.ld, pb, p.b.ld, grid, s)));
+        else if (d.conv_a) T2_TRY_RC((launch_bf16src<true, 2, 2, 2, 2, 2>(g, pa, p.a.ld, pb, p.b.ld, grid, s)));
+        else T2_TRY_RC((launch_bf16src<false, 2, 2, 2, 2, 2>(g, pa, p.a.ld, pb, p.b.ld, grid, s)));
+    } else {
+        // one instantiation per pair of unit strides, K-contiguous first: [A k-contiguous ? 0 : 2] + [B k-contiguous ? 0 : 1]
+        using Kernel = void (*)(GemmK);
+        static const Kernel bf16conv[] = {gemm_bf16_kernel<true, true>, gemm_bf16_kernel<true, false>, gemm_bf16_kernel<false, true>, gemm_bf16_kernel<false, false>};
+        static const Kernel f32_64[] = {gemm_kernel<64, 64, true, true>, gemm_kernel<64, 64, true, false>, gemm_kernel<64, 64, false, true>, gemm_kernel<64, 64, false, false>};
+        static const Kernel f32_128[] = {gemm_kernel<128, 128, true, true>, gemm_kernel<128, 128, true, false>, gemm_kernel<128, 128, false, true>, gemm_kernel<128, 128, false, false>};
+        const bool conv16 = p.kernel == GemmKernel::bf16conv;
+        const size_t smem = conv16 ? (size_t)4 * 128 * PK16 * sizeof(__bf16) : 0;     // (64 KB: needs no t2_allow_dynamic_lds)
+        const Kernel kernel = (conv16 ? bf16conv : p.kernel == GemmKernel::f32_64 ? f32_64 : f32_128)[(g.d.sak == 1 ? 0 : 2) + (g.d.sbk == 1 ? 0 : 1)];
+        hipLaunchKernelGGL(kernel, grid, dim3(256), smem, s, g);
+    }
+    T2_LAUNCH_CHECK();
+    if (p.splitk > 1) {
+        const long total = (long)d.batch * d.M * d.N;
+        int blocks = (int)((total + 255) / 256);
+        if (blocks > 2048) blocks = 2048;
+        hipLaunchKernelGGL(splitk_reduce_kernel, dim3(blocks), dim3(256), 0, s, g.d);
+        T2_LAUNCH_CHECK();
+    }
+    return 0;
+}
 
 }  // namespace
 
@@ -1268,41 +1350,36 @@ int stage_split_bf16(const float* src, bool kc, long ld, __bf16* dst, int rows, 
     return stage_split_operand(src, kc, ld, dst, rows, K, lo_slot, row_group, s);
 }
 
-int gemm(const GemmDesc& din, hipStream_t s) {
-    GemmK g{};
-    g.d = din;
-    GemmDesc& d = g.d;
-    T2_REQUIRE(d.M > 0 && d.N > 0 && d.K > 0 && d.batch > 0, "gemm: bad shape M=%d N=%d K=%d batch=%d", d.M, d.N, d.K, d.batch);
-    if (d.conv_a || d.conv_b) {
-        T2_REQUIRE(d.conv_T > 0 && d.conv_C > 0 && d.conv_C % 4 == 0 && !(d.conv_a && d.conv_b), "gemm: bad implicit-conv operand (T=%d C=%d)", d.conv_T, d.conv_C);
-        T2_REQUIRE(d.batch == 1, "gemm: implicit-conv operands need batch == 1");
-        if (d.conv_a) { d.sam = 0; d.sak = 1; T2_REQUIRE(d.K % d.conv_C == 0 && aligned16(d.A), "gemm: conv A operand: K=%d C=%d", d.K, d.conv_C); }
-        if (d.conv_b) { d.sbk = 0; d.sbn = 1; T2_REQUIRE(d.N % d.conv_C == 0 && aligned16(d.B), "gemm: conv B operand: N=%d C=%d", d.N, d.conv_C); }
-    }
-    T2_REQUIRE(d.sam == 1 || d.sak == 1, "gemm: A needs one unit stride (sam=%ld sak=%ld)", d.sam, d.sak);
-    T2_REQUIRE(d.sbn == 1 || d.sbk == 1, "gemm: B needs one unit stride (sbn=%ld sbk=%ld)", d.sbn, d.sbk);
-    T2_REQUIRE(d.drop_p == 0.f || (d.batch == 1 && (long)d.M * d.N < (1l << 32)), "gemm: dropout epilogue needs batch==1 and M*N < 2^32");
-    const bool akc = d.sak == 1, bkc = d.sbk == 1;
-    if (d.drop_mstride == 0) d.drop_mstride = (uint32_t)d.N;
-    g.avec = aligned16(d.A) && (d.bsA % 4 == 0) && ((akc ? d.sam : d.sak) % 4 == 0);
-    g.bvec = aligned16(d.B) && (d.bsB % 4 == 0) && ((bkc ? d.sbn : d.sbk) % 4 == 0);
+int stage_planned(const float* src, const GemmOperandPlan& o, bool split, __bf16* dst, hipStream_t s) {
+    return split ? stage_split_operand(src, o.kc, o.ld_src, dst, o.rows, o.K, o.lo_slot, o.row_group, s)
+                 : stage_operand(src, o.kc, o.ld_src, dst, o.rows, o.K, s);
+}
 
-    // 128x128 tiles whenever both extents allow it (4 MFMAs per 4 LDS fragment reads); a grid that
-    // would not fill the chip is completed by split-K when scratch is available, else by 64x64 tiles.
+const char* gemm_plan_name(const GemmPlan& p) {
+    static const char* const names[] = {"f32_64", "f32_128", "bf16conv", "src128", "src256", "src256km", "x3src128", "x3src256", "x3src256km"};
+    return names[(int)p.kernel + (p.split ? 3 : 0)];
+}
+
+GemmPlan plan_gemm(const GemmDesc& d) {
+    GemmPlan p{};
+    const bool conv_any = d.conv_a || d.conv_b;
+    const bool akc = d.conv_a || d.sak == 1, bkc = !d.conv_b && d.sbk == 1;   // K is the contiguous stride (conv: A's frames are rows, B's are k-rows)
+    const long lda = d.conv_a ? d.conv_C : akc ? d.sam : d.sak;               // leading dimension of the fp32 operand (conv: of the frames)
+    const long ldb = d.conv_b ? d.conv_C : bkc ? d.sbn : d.sbk;
+    p.avec = aligned16(d.A) && d.bsA % 4 == 0 && lda % 4 == 0;
+    p.bvec = aligned16(d.B) && d.bsB % 4 == 0 && ldb % 4 == 0;
+    p.K = d.K; p.conv_C = d.conv_C;
+
     // bf16-operand mode: large GEMMs only (both extents >= 64), conv operands need C % 8 == 0
-    const bool large = !d.fp32_only && d.M >= 64 && d.N >= 64 && d.K >= 64 && (!(d.conv_a || d.conv_b) || d.conv_C % 8 == 0);
+    const bool large = !d.fp32_only && d.M >= 64 && d.N >= 64 && d.K >= 64 && (!conv_any || d.conv_C % 8 == 0);
     const bool use_bf16 = g_precision == 1 && large;
     // split-bf16 mode: only the bf16-source kernels, on operands staged as hi / lo parts (K' = 3K, see stage_split_kc_kernel);
     // whatever does not qualify for them below runs exactly what mode 0 runs.  Single-bf16 copies from the caller are not
     // used; split16 marks copies that are already in the split layout of this product (t2_prof_gemm).
     const bool want_split = g_precision == 2 && large && 2.0 * d.M * d.N * d.K >= g_split_min_flop;
-    if (g_precision == 2 && !(want_split && d.split16)) d.A16 = d.B16 = nullptr;
     const int kmul = want_split ? 3 : 1;
-    // bf16-source path: both operands staged as bf16 [rows][K] in front of the split-K scratch (or handed over by the
-    // caller); pays when each staged element is reused by many tiles, i.e. when both extents are large
-    bool staged = false;
-    __bf16* a16 = nullptr; __bf16* b16 = nullptr;
-    const bool conv_any = d.conv_a || d.conv_b;
+    const bool copies = g_precision != 2 || (want_split && d.split16);
+    bool a_caller = copies && d.A16, b_caller = copies && d.B16;
     // 256 x 256 tiles (gemm_bf16src256_kernel) when the staged operands are whole 256-tiles and K splits into an even
     // number of 64-wide K-tiles.  Its k-major variant reads both operands as they lie in memory when BOTH are k-major
     // (the weight-gradient products): they are staged by the plain cast, [K][M] and [K][N]; an implicit-conv B operand
@@ -1310,155 +1387,85 @@ int gemm(const GemmDesc& din, hipStream_t s) {
     // does not take is ignored (the fp32 operand is staged instead).
     static const int g_t256 = env_int("T2_GEMM_256", 1);
     const bool shape256 = g_t256 && d.M % 256 == 0 && d.N % 256 == 0 && d.K >= 128;
-    const long ld_km = std::max(std::max((long)d.M, d.A16 && d.a16_kmajor ? d.lda16 : 0l), std::max((long)(d.conv_b ? d.conv_C : d.N), d.B16 && d.b16_kmajor ? d.ldb16 : 0l));
+    const long ld_km = std::max(std::max((long)d.M, a_caller && d.a16_kmajor ? d.lda16 : 0l), std::max((long)(d.conv_b ? d.conv_C : d.N), b_caller && d.b16_kmajor ? d.ldb16 : 0l));
     const bool km = shape256 && !akc && !bkc && !d.conv_a && (!d.conv_b || d.conv_C % 256 == 0) && (long)d.K * kmul * ld_km * 2 < (1l << 31);
-    if (d.A16 && (d.a16_kmajor != 0) != km) d.A16 = nullptr;
-    if (d.B16 && (d.b16_kmajor != 0) != km) d.B16 = nullptr;
+    a_caller = a_caller && (d.a16_kmajor != 0) == km;
+    b_caller = b_caller && (d.b16_kmajor != 0) == km;
     // (split: the k-major conv_b copies are three whole stacks of the frames, so the stack height must keep k % conv_T)
-    const bool conv_ok = !conv_any || (d.conv_a && d.conv_C % 64 == 0 && !d.A16 && !d.B16) || (d.conv_b && km && (!want_split || d.K % d.conv_T == 0));
+    const bool conv_ok = !conv_any || (d.conv_a && d.conv_C % 64 == 0 && !a_caller && !b_caller) || (d.conv_b && km && (!want_split || d.K % d.conv_T == 0));
+    // bf16-source kernels: both operands staged as bf16 in front of the split-K scratch (or handed over by the caller);
+    // pays when each staged element is reused by many tiles, i.e. when both extents are large
+    bool staged = false;
+    size_t ws_bytes = d.ws_bytes;                           // what is left for the split-K partials
     if ((use_bf16 || want_split) && g_stage && conv_ok && d.batch == 1 && d.M % 128 == 0 && d.N % 128 == 0 && d.K % 64 == 0) {
         // implicit-conv operands: only the frames [rows][C] are staged (the kernel shifts rows per tap)
         const size_t a_elems = d.conv_a ? (size_t)d.M * d.conv_C : (size_t)d.M * d.K;
         const size_t b_elems = d.conv_b ? (size_t)d.K * d.conv_C : (size_t)d.N * d.K;
-        const size_t need_a = d.A16 ? 0 : ((kmul * a_elems * sizeof(__bf16) + 255) & ~(size_t)255);
-        const size_t need_b = d.B16 ? 0 : ((kmul * b_elems * sizeof(__bf16) + 255) & ~(size_t)255);
-        const bool big = (d.A16 || d.N >= g_stage_min) && (d.B16 || d.M >= g_stage_min);
-        const bool ok_src = (d.A16 || g.avec) && (d.B16 || g.bvec) &&
-                            (!d.A16 || (aligned16(d.A16) && d.lda16 % 8 == 0)) && (!d.B16 || (aligned16(d.B16) && d.ldb16 % 8 == 0));
+        const size_t need_a = a_caller ? 0 : round256(kmul * a_elems * sizeof(__bf16));
+        const size_t need_b = b_caller ? 0 : round256(kmul * b_elems * sizeof(__bf16));
+        const bool big = (a_caller || d.N >= kStageMin) && (b_caller || d.M >= kStageMin);
+        const bool ok_src = (a_caller ? aligned16(d.A16) && d.lda16 % 8 == 0 : p.avec != 0) && (b_caller ? aligned16(d.B16) && d.ldb16 % 8 == 0 : p.bvec != 0);
         if (big && ok_src && (need_a + need_b == 0 || (d.ws && aligned16(d.ws) && d.ws_bytes >= need_a + need_b))) {
             staged = true;
-            unsigned char* base = reinterpret_cast<unsigned char*>(d.ws);
-            if (need_a) a16 = reinterpret_cast<__bf16*>(base);
-            if (need_b) b16 = reinterpret_cast<__bf16*>(base + need_a);
-            if (need_a + need_b) { d.ws = reinterpret_cast<float*>(base + need_a + need_b); d.ws_bytes -= need_a + need_b; }
+            p.a.bytes = need_a; p.b.bytes = need_b;
+            ws_bytes -= need_a + need_b;
         }
     }
-    // split operands: from here on the product is the bf16-source kernels' K' = 3K one (conv_a: 3C channels per tap)
-    const bool split = want_split && staged, bf16_path = use_bf16 || split;
-    const int K0 = d.K, C0 = d.conv_C;
-    if (split) { d.K *= 3; if (d.conv_a) d.conv_C *= 3; }
-    // the 256-tile kernel's split-K factor fills whole rounds of one workgroup per CU
-    const bool use256 = staged && shape256 && (!d.conv_a || (long)d.M * d.conv_C * 2 < (1l << 31));
-    int split256 = 1;
-    if (use256) {
-        const long tiles = (long)(d.M / 256) * (d.N / 256);
-        const int nkt = d.K / 64;
-        if (d.splitk > 0) split256 = std::min(d.splitk, std::max(1, nkt / 2));
-        else if (d.ws && d.beta == 0.f && tiles < 512) {
-            double best = 0.0;
-            for (int sp = 1; sp <= 16; ++sp) {
-                if (sp > 1 && nkt / sp < 16) break;
-                const long wgs = tiles * sp, rounds = (wgs + 255) / 256;
-                const double eff = (double)wgs / (256.0 * rounds);
-                if (eff > best * 1.05) { best = eff; split256 = sp; }
-            }
-        }
-        if (split256 > 1 && !(d.ws && d.beta == 0.f)) split256 = 1;
-        if (split256 > 1) {
-            const size_t per = (size_t)d.M * d.N * sizeof(float);
-            if ((size_t)split256 * per > d.ws_bytes) split256 = (int)(d.ws_bytes / per);
-            if (split256 < 1) split256 = 1;
-        }
+    // split operands: the product is the bf16-source kernels' K' = 3K one (conv_a: 3C channels per tap)
+    p.split = want_split && staged;
+    if (p.split) { p.K = 3 * d.K; if (d.conv_a) p.conv_C = 3 * d.conv_C; }
+    const int kch = (p.K + BK - 1) / BK;
+    int splitk;
+    if (staged) {
+        const bool use256 = shape256 && (!d.conv_a || (long)d.M * p.conv_C * 2 < (1l << 31));
+        p.kernel = !use256 ? GemmKernel::src128 : km ? GemmKernel::src256km : GemmKernel::src256;    // (km implies use256)
+        const int lo_grp = !p.split ? 0 : d.conv_b ? d.K : 64;   // split k-major copies: K-tile interleave, or whole stacks next to conv_b
+        const int lo = p.split ? 1 : 0;                           // lo slot of a split copy: 1 for A, 2 for B
+        if (a_caller) p.a = {GemmSrc::caller, d.lda16};
+        else if (d.conv_a) p.a = {GemmSrc::staged, p.conv_C, true, lda, d.M, d.conv_C, lo, 0, p.a.bytes};
+        else if (km) p.a = {GemmSrc::staged, d.M, true, lda, d.K, d.M, lo, lo_grp, p.a.bytes};         // the k-major copies are [K][rows]
+        else p.a = {GemmSrc::staged, p.K, akc, lda, d.M, d.K, lo, 0, p.a.bytes};
+        if (b_caller) p.b = {GemmSrc::caller, d.ldb16};
+        else if (d.conv_b) p.b = {GemmSrc::staged, d.conv_C, true, ldb, d.K, d.conv_C, 2 * lo, lo_grp, p.b.bytes};
+        else if (km) p.b = {GemmSrc::staged, d.N, true, ldb, d.K, d.N, 2 * lo, lo_grp, p.b.bytes};
+        else p.b = {GemmSrc::staged, p.K, bkc, ldb, d.N, d.K, 2 * lo, 0, p.b.bytes};
+        splitk = use256 ? choose_splitk(d, true, (long)(d.M / 256) * (d.N / 256), kch, ws_bytes) : choose_splitk(d, false, (long)(d.M / 128) * (d.N / 128), kch, ws_bytes);
+    } else {
+        // 128x128 tiles whenever both extents allow it (4 MFMAs per 4 LDS fragment reads); a grid that
+        // would not fill the chip is completed by split-K when scratch is available, else by 64x64 tiles.
+        const bool can_split = d.ws && d.beta == 0.f && kch >= 64;
+        const long tiles128 = (long)((d.M + 127) / 128) * ((d.N + 127) / 128) * d.batch;
+        const bool small = !use_bf16 && ((d.M <= 64 || d.N <= 64) || (tiles128 < 256 && !can_split));
+        p.kernel = use_bf16 ? GemmKernel::bf16conv : small ? GemmKernel::f32_64 : GemmKernel::f32_128;
+        splitk = choose_splitk(d, false, small ? (long)((d.M + 63) / 64) * ((d.N + 63) / 64) * d.batch : tiles128, kch, ws_bytes);
     }
-    const int kch = (d.K + BK - 1) / BK;
-    const bool can_split = d.ws && d.beta == 0.f && kch >= 64;
-    const long tiles128 = (long)((d.M + 127) / 128) * ((d.N + 127) / 128) * d.batch;
-    const bool small = !bf16_path && ((d.M <= 64 || d.N <= 64) || (tiles128 < 256 && !can_split));
-    const int BMN = small ? 64 : 128;
-    const int tm = (d.M + BMN - 1) / BMN, tn = (d.N + BMN - 1) / BMN;
-    int splitk = 1;
-    if (d.ws && d.beta == 0.f) {
-        splitk = d.splitk;
-        if (splitk <= 0) {
-            const long tiles = (long)tm * tn * d.batch;
-            splitk = 1;
-            // fewer than two tile-waves over the 256 CUs and a long K: split so that every CU holds several workgroups
-            // (a lone 128x128 workgroup per CU cannot cover its own operand latency)
-            if (tiles < 512 && kch >= 64) {
-                splitk = (int)((1024 + tiles - 1) / tiles);
-                if (splitk > kch / 16) splitk = kch / 16;
-            }
-        }
-        const size_t per = (size_t)d.batch * d.M * d.N * sizeof(float);
-        if ((size_t)splitk * per > d.ws_bytes) splitk = (int)(d.ws_bytes / per);
-        if (splitk < 1) splitk = 1;
+    const int round = p.kernel >= GemmKernel::bf16conv ? 3 : 0;                 // bf16 kernels: whole 64-wide chunks per split
+    p.kchunks = ((kch + splitk - 1) / splitk + round) & ~round;
+    p.splitk = (kch + p.kchunks - 1) / p.kchunks;                               // drop empty splits
+    if (p.kernel >= GemmKernel::src256 && p.splitk > 1 && kch - (p.splitk - 1) * p.kchunks < 8) {   // the 256-tile kernel needs two K-tiles in every split
+        p.kchunks = ((kch + p.splitk - 2) / (p.splitk - 1) + 3) & ~3;
+        p.splitk = (kch + p.kchunks - 1) / p.kchunks;
     }
-    if (use256) splitk = split256;
-    g.kchunks = (kch + splitk - 1) / splitk;
-    if (bf16_path) g.kchunks = (g.kchunks + 3) & ~3;   // whole 64-wide chunks per split
-    splitk = (kch + g.kchunks - 1) / g.kchunks;     // drop empty splits
-    if (use256 && splitk > 1 && kch - (splitk - 1) * g.kchunks < 8) {   // the 256-tile kernel needs two K-tiles in every split
-        --splitk;
-        g.kchunks = ((kch + splitk - 1) / splitk + 3) & ~3;
-        splitk = (kch + g.kchunks - 1) / g.kchunks;
-    }
-    d.splitk = splitk;
+    return p;
+}
+
+int gemm_plan(const GemmDesc& d, GemmPlan* out) {
+    T2_TRY_RC(check_gemm(d));
+    *out = plan_gemm(d);
+    T2_REQUIRE((long)d.batch * out->splitk <= 65535, "gemm: batch*splitk too large (%d*%d)", d.batch, out->splitk);
+    return 0;
+}
+
+int gemm(const GemmDesc& d, hipStream_t s) {
+    GemmPlan p;
+    T2_TRY_RC(gemm_plan(d, &p));
     static const int g_log = env_int("T2_GEMM_LOG", 0);      // dev: one line per product (shape, kernel, split, which operands get staged)
     if (g_log)
-        fprintf(stderr, "t2gemm M=%d N=%d K=%d batch=%d %s%s kernel=%s splitk=%d stageA=%d stageB=%d convA=%d convB=%d beta=%g\n", d.M, d.N, K0, d.batch,
-                akc ? "A[m][k]" : "A[k][m]", bkc ? " B[n][k]" : " B[k][n]", split ? (use256 ? (km ? "x3src256km" : "x3src256") : "x3src128") : staged ? (use256 ? (km ? "src256km" : "src256") : "src128") : use_bf16 ? "bf16conv" : small ? "f32_64" : "f32_128",
-                splitk, a16 != nullptr, b16 != nullptr, d.conv_a, d.conv_b, (double)d.beta);
-    T2_REQUIRE((long)d.batch * splitk <= 65535, "gemm: batch*splitk too large (%d*%d)", d.batch, splitk);
-    dim3 grid(tn, tm, d.batch * splitk);
-    ++g_counts[split ? 3 : staged ? 2 : use_bf16 ? 1 : 0];
-    if (staged) {
-        const bool km256 = km && use256;                   // (km implies use256 once staged; the k-major copies are [K][rows])
-        if (split) {
-            const int grp = d.conv_b ? K0 : 64;            // k-major copies: K-tile interleave, or whole stacks next to conv_b
-            if (a16) {
-                if (d.conv_a) T2_TRY_RC(stage_split_operand(d.A, true, C0, a16, d.M, C0, 1, 0, s));
-                else if (km256) T2_TRY_RC(stage_split_operand(d.A, true, d.sak, a16, K0, d.M, 1, grp, s));
-                else T2_TRY_RC(stage_split_operand(d.A, akc, akc ? d.sam : d.sak, a16, d.M, K0, 1, 0, s));
-            }
-            if (b16) {
-                if (d.conv_b) T2_TRY_RC(stage_split_operand(d.B, true, C0, b16, K0, C0, 2, grp, s));
-                else if (km256) T2_TRY_RC(stage_split_operand(d.B, true, d.sbk, b16, K0, d.N, 2, grp, s));
-                else T2_TRY_RC(stage_split_operand(d.B, bkc, bkc ? d.sbn : d.sbk, b16, d.N, K0, 2, 0, s));
-            }
-        } else {
-            if (a16) {
-                if (d.conv_a) T2_TRY_RC(stage_operand(d.A, true, d.conv_C, a16, d.M, d.conv_C, s));
-                else if (km256) T2_TRY_RC(stage_operand(d.A, true, d.sak, a16, d.K, d.M, s));
-                else T2_TRY_RC(stage_operand(d.A, akc, akc ? d.sam : d.sak, a16, d.M, d.K, s));
-            }
-            if (b16) {
-                if (d.conv_b) T2_TRY_RC(stage_operand(d.B, true, d.conv_C, b16, d.K, d.conv_C, s));
-                else if (km256) T2_TRY_RC(stage_operand(d.B, true, d.sbk, b16, d.K, d.N, s));
-                else T2_TRY_RC(stage_operand(d.B, bkc, bkc ? d.sbn : d.sbk, b16, d.N, d.K, s));
-            }
-        }
-        const __bf16* pa = d.A16 ? d.A16 : a16; const long lda = d.A16 ? d.lda16 : d.conv_a ? d.conv_C : km256 ? d.M : d.K;
-        const __bf16* pb = d.B16 ? d.B16 : b16; const long ldb = d.B16 ? d.ldb16 : d.conv_b ? d.conv_C : km256 ? d.N : d.K;
-        // 128x128 block tile, two k-steps in flight.  Measured alternatives (same template, other parameters): 256x128 with
-        // 8 waves 5-12 % slower, 256x256 with 128x64 wave tiles and one k-step in flight 4.6x slower (one workgroup per CU:
-        // nothing overlaps its barriers) — the kernel is bound by latency hiding, not by operand bytes per CU
-        if (km256 && d.conv_b) T2_TRY_RC((launch_bf16src256<false, true, true>(g, pa, lda, pb, ldb, splitk, s)));
-        else if (km256) T2_TRY_RC((launch_bf16src256<false, true, false>(g, pa, lda, pb, ldb, splitk, s)));
-        else if (use256 && d.conv_a) T2_TRY_RC((launch_bf16src256<true, false, false>(g, pa, lda, pb, ldb, splitk, s)));
-        else if (use256) T2_TRY_RC((launch_bf16src256<false, false, false>(g, pa, lda, pb, ldb, splitk, s)));
-        else if (d.conv_a) T2_TRY_RC((launch_bf16src<true, 2, 2, 2, 2, 2>(g, pa, lda, pb, ldb, splitk, s)));
-        else T2_TRY_RC((launch_bf16src<false, 2, 2, 2, 2, 2>(g, pa, lda, pb, ldb, splitk, s)));
-    } else if (use_bf16) {
-        const size_t smem = (size_t)4 * 128 * PK16 * sizeof(__bf16);
-        T2_TRY_RC(t2_allow_dynamic_lds(reinterpret_cast<const void*>(gemm_bf16_kernel<true, true>), smem));
-        T2_TRY_RC(t2_allow_dynamic_lds(reinterpret_cast<const void*>(gemm_bf16_kernel<true, false>), smem));
-        T2_TRY_RC(t2_allow_dynamic_lds(reinterpret_cast<const void*>(gemm_bf16_kernel<false, true>), smem));
-        T2_TRY_RC(t2_allow_dynamic_lds(reinterpret_cast<const void*>(gemm_bf16_kernel<false, false>), smem));
-        if (akc && bkc) hipLaunchKernelGGL((gemm_bf16_kernel<true, true>), grid, dim3(256), smem, s, g);
-        else if (akc && !bkc) hipLaunchKernelGGL((gemm_bf16_kernel<true, false>), grid, dim3(256), smem, s, g);
-        else if (!akc && bkc) hipLaunchKernelGGL((gemm_bf16_kernel<false, true>), grid, dim3(256), smem, s, g);
-        else hipLaunchKernelGGL((gemm_bf16_kernel<false, false>), grid, dim3(256), smem, s, g);
-    } else if (small) launch_cfg<64, 64>(g, akc, bkc, grid, s);
-    else launch_cfg<128, 128>(g, akc, bkc, grid, s);
-    T2_LAUNCH_CHECK();
-    if (splitk > 1) {
-        const long total = (long)d.batch * d.M * d.N;
-        int blocks = (int)((total + 255) / 256);
-        if (blocks > 2048) blocks = 2048;
-        hipLaunchKernelGGL(splitk_reduce_kernel, dim3(blocks), dim3(256), 0, s, d);
-        T2_LAUNCH_CHECK();
-    }
-    return 0;
+        fprintf(stderr, "t2gemm M=%d N=%d K=%d batch=%d %s%s kernel=%s splitk=%d stageA=%d stageB=%d convA=%d convB=%d beta=%g\n", d.M, d.N, d.K, d.batch,
+                d.conv_a || d.sak == 1 ? "A[m][k]" : "A[k][m]", !d.conv_b && d.sbk == 1 ? " B[n][k]" : " B[k][n]", gemm_plan_name(p),
+                p.splitk, p.a.src == GemmSrc::staged, p.b.src == GemmSrc::staged, d.conv_a, d.conv_b, (double)d.beta);
+    ++g_counts[p.split ? 3 : gemm_reads_bf16_copies(p.kernel) ? 2 : p.kernel == GemmKernel::bf16conv ? 1 : 0];
+    return run_gemm(d, p, s);
 }
 
 }  // namespace t2

@@ -41,6 +41,41 @@ inline GemmDesc gemm_desc() {
     GemmDesc d{}; d.batch = 1; d.alpha = 1.f; d.beta = 0.f; d.act = ACT_NONE; d.drop_p = 0.f; return d;
 }
 int gemm(const GemmDesc& d, hipStream_t s);
+
+// What gemm() does with a descriptor, decided on the host before anything is launched (gemm.hip plan_gemm).
+enum class GemmKernel : int {
+    f32_64, f32_128,    // exact fp32 kernel, 64x64 / 128x128 tiles, fp32 operands
+    bf16conv,           // mode 1: bf16 MFMAs on fp32 operands converted in the kernel (128x128 tiles)
+    src128,             // bf16 operand copies, 128x128 tiles, both copies K-contiguous
+    src256,             // bf16 operand copies, 256x256 tiles, both copies K-contiguous
+    src256km            // bf16 operand copies, 256x256 tiles, both copies k-major (conv_b: only here or in an fp32 kernel)
+};
+inline bool gemm_reads_bf16_copies(GemmKernel k) { return k >= GemmKernel::src128; }
+enum class GemmSrc : int { fp32, staged, caller };   // the kernel reads the fp32 operand / a copy gemm() stages into the scratch /
+                                                     // the caller's A16 or B16.  fp32 for both operands unless the kernel is src*
+struct GemmOperandPlan {
+    GemmSrc src;
+    long ld;                  // src != fp32: leading dimension of the copy the kernel reads
+    // src == staged: the arguments of stage_bf16 / stage_split_bf16 (lo_slot, row_group: split copies only) and the scratch taken
+    bool kc; long ld_src; int rows, K, lo_slot, row_group;
+    size_t bytes;
+};
+struct GemmPlan {
+    GemmKernel kernel;
+    bool split;               // mode 2: the copies are hi / lo parts and the kernel sees K' = 3K ("x3" in the log name)
+    int splitk, kchunks;      // grid.z = batch * splitk; 16-wide K-chunks per split
+    int K, conv_C;            // the reduction length and the conv channel count as the kernel sees them (split: tripled)
+    GemmOperandPlan a, b;     // staged copies lie in front of the split-K partials: A's, then B's
+    int avec, bvec;           // fp32 kernels: 16-byte loads are legal for A / B
+};
+// Pure host function: reads the descriptor and the process-wide switches (precision mode, staging switch, split threshold,
+// T2_GEMM_256), touches no device.  The descriptor must have passed gemm()'s checks: gemm_plan() runs them first and
+// returns what gemm() would return for a descriptor it refuses.
+GemmPlan plan_gemm(const GemmDesc& d);
+int gemm_plan(const GemmDesc& d, GemmPlan* out);
+const char* gemm_plan_name(const GemmPlan& p);       // the T2_GEMM_LOG name: f32_64 ... src256km, "x3" in front when split
+// makes the copy a plan asks for (o.src == staged) at dst; split: GemmPlan::split
+int stage_planned(const float* src, const GemmOperandPlan& o, bool split, __bf16* dst, hipStream_t s);
 // bf16 copy of an fp32 operand, K contiguous: dst[row*K + k] = src[row*ld + k] (kc) or src[k*ld + row] (!kc);
 // rows % 64 == 0, K % 64 == 0, 16-byte aligned rows.  For GemmDesc::A16 / B16 shared by several products.
 int stage_bf16(const float* src, bool kc, long ld, __bf16* dst, int rows, int K, hipStream_t s);

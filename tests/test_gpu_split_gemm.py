@@ -279,3 +279,15 @@ def test_prof_gemm_in_split_mode(env, ta, tb):
     assert 0.0 < mk.value <= mt.value * 1.5 and mt.value < 50.0
     with pytest.raises(RuntimeError):                                   # fp32 mode: still refused
         L.check(L.lib().t2_prof_gemm(C.byref(a), 5, C.byref(mt), C.byref(mk), L.stream()))
+    # default threshold: this product (0.8 GFLOP) runs the exact kernel in mode bf16x3, so there is no bf16-source kernel
+    # to time: refused with a message, nothing launched, instead of the exact kernel's time under the name ms_kernel
+    L.set_precision("bf16x3")
+    L.set_gemm_split_min_mflop(-1)
+    try:
+        L.gemm_counts(reset=True)
+        with pytest.raises(RuntimeError, match="t2_prof_gemm.*f32_64"):
+            L.check(L.lib().t2_prof_gemm(C.byref(a), 5, C.byref(mt), C.byref(mk), L.stream()))
+        assert L.gemm_counts() == (0, 0, 0, 0)
+    finally:
+        L.set_gemm_split_min_mflop(0)
+        L.set_precision("f32")
