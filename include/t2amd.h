@@ -320,6 +320,12 @@ typedef struct t2_conv_bn_args {
     float* z; float* mean; float* invstd; float* var;   /* saved: [B*T,Cout], [Cout] x3 */
     float* y;                          /* [B*T, Cout] */
     float* ws; size_t ws_floats;       /* scratch >= Cout*Cin*K + 128*Cout floats; anything beyond is used for bf16 operand staging (bf16 mode) */
+    /* Optional bf16 hand-offs through a stack of layers (all zero: every GEMM operand is cast by the GEMM layer, as before).
+     * y16: also write y as bf16 [B*T, Cout] (round to nearest even), for the next layer's x16.  handoff != 0, bf16 mode: the
+     * conv product reads x16 (the previous layer's y16, [B*T, Cin]; may be NULL) and weights re-laid-out straight into bf16
+     * instead of casting them, wherever that leaves the product's kernel and split-K unchanged (t2_conv_handoff_plan):
+     * results are bit-identical either way.  Ignored in the other precision modes. */
+    const void* x16; void* y16; int handoff;
 } t2_conv_bn_args;
 int t2_conv_bn_forward(const t2_conv_bn_args* a, void* stream);
 typedef struct t2_conv_bn_bwd_args {
@@ -331,6 +337,9 @@ typedef struct t2_conv_bn_bwd_args {
     float* dw; float* dbias; float* dgamma; float* dbeta;
     float* dx; int dx_accumulate;      /* [B*T, Cin] or NULL */
     float* ws; size_t ws_floats;       /* scratch >= B*T*Cout + Cout*Cin*K + 128*Cout + split-K / bf16 staging space */
+    /* Optional, as in t2_conv_bn_args: handoff != 0 (bf16 mode) writes dz once as bf16 for both products and the flipped
+     * weights straight into bf16; x16 is the bf16 copy of x saved by the forward pass (NULL: x is cast). */
+    const void* x16; int handoff;
 } t2_conv_bn_bwd_args;
 int t2_conv_bn_backward(const t2_conv_bn_bwd_args* a, void* stream);
 
@@ -407,6 +416,11 @@ typedef struct t2_gemm_plan_info {
     size_t stage_bytes_a, stage_bytes_b; /* scratch the staged copies take in front of the split-K partials */
 } t2_gemm_plan_info;
 int t2_gemm_plan(const t2_gemm_args* a, const t2_gemm_plan_opts* opts, t2_gemm_plan_info* out);
+/* The hand-over rule of the conv stacks for the product (a, opts), opts->a16 / b16 naming the copies on offer: *taken = 1
+ * and *out = the plan with them iff the product without copies stages every operand a copy is offered for, and with them
+ * takes every copy and keeps its kernel, split-K factor and K-chunks per split; otherwise *taken = 0 and *out = the plan
+ * without copies.  Launches nothing. */
+int t2_conv_handoff_plan(const t2_gemm_args* a, const t2_gemm_plan_opts* opts, int* taken, t2_gemm_plan_info* out);
 /* out[n] = sum_m x[m*ld + n]; scratch >= 64*N floats */
 int t2_colsum(const float* x, long ld, int M, int N, float* out, float* scratch, void* stream);
 int t2_mask_btc(float* x, int B, int T, int C, const int32_t* lengths, float fill, void* stream);

@@ -112,7 +112,8 @@ class ConvBnArgs(C.Structure):
                 ("training", C.c_int), ("eps", C.c_float), ("act", C.c_int), ("drop_p", C.c_float), ("seed", C.c_uint64),
                 ("site", C.c_uint32), ("residual", C.c_void_p),
                 ("z", C.c_void_p), ("mean", C.c_void_p), ("invstd", C.c_void_p), ("var", C.c_void_p), ("y", C.c_void_p),
-                ("ws", C.c_void_p), ("ws_floats", C.c_size_t)]
+                ("ws", C.c_void_p), ("ws_floats", C.c_size_t),
+                ("x16", C.c_void_p), ("y16", C.c_void_p), ("handoff", C.c_int)]      # optional bf16 hand-offs (zero: none)
 
 
 class ConvBnBwdArgs(C.Structure):
@@ -122,7 +123,8 @@ class ConvBnBwdArgs(C.Structure):
                 ("training", C.c_int), ("eps", C.c_float), ("act", C.c_int), ("drop_p", C.c_float), ("seed", C.c_uint64),
                 ("site", C.c_uint32), ("dy", C.c_void_p),
                 ("dw", C.c_void_p), ("dbias", C.c_void_p), ("dgamma", C.c_void_p), ("dbeta", C.c_void_p),
-                ("dx", C.c_void_p), ("dx_accumulate", C.c_int), ("ws", C.c_void_p), ("ws_floats", C.c_size_t)]
+                ("dx", C.c_void_p), ("dx_accumulate", C.c_int), ("ws", C.c_void_p), ("ws_floats", C.c_size_t),
+                ("x16", C.c_void_p), ("handoff", C.c_int)]
 
 
 _P4 = C.c_void_p * 4
@@ -166,7 +168,7 @@ ABI_VERSION = 4      # include/t2amd.h T2_ABI_VERSION: struct sizes below match 
 EXPORTS = ["t2_last_error", "t2_version", "t2_chain_status", "t2_chain_status_clear", "t2_debug_report_abort", "t2_debug_occupy", "t2_chain_claimed", "t2_set_precision", "t2_get_precision", "t2_gemm_counts", "t2_set_gemm_split_min_mflop", "t2_set_overlap", "t2_set_chain", "t2_get_chain", "t2_set_chain_bwd", "t2_set_gemm_staging", "t2_side_join", "t2_decoder_layout_query", "t2_decoder_forward", "t2_decoder_infer",
            "t2_decoder_bwd_layout_query", "t2_decoder_backward", "t2_prof_enable", "t2_prof_collect", "t2_adam_chunks", "t2_adam_step", "t2_adam_norm",
            "t2_conv_bn_forward", "t2_conv_bn_backward", "t2_embedding_forward", "t2_embedding_backward",
-           "t2_lstm_seq_forward", "t2_lstm_seq_backward", "t2_lstm_seq_chain_ws_floats", "t2_gemm_ex", "t2_prof_gemm", "t2_gemm_plan", "t2_colsum", "t2_mask_btc",
+           "t2_lstm_seq_forward", "t2_lstm_seq_backward", "t2_lstm_seq_chain_ws_floats", "t2_gemm_ex", "t2_prof_gemm", "t2_gemm_plan", "t2_conv_handoff_plan", "t2_colsum", "t2_mask_btc",
            "t2_finalize_bct", "t2_mask_bt", "t2_gemm", "t2_rng_keep_mask", "t2_rng_normal"]
 
 _lib = None
@@ -207,6 +209,7 @@ def lib() -> C.CDLL:
         L.t2_gemm_ex.argtypes = [C.POINTER(GemmArgs), C.c_void_p]
         L.t2_prof_gemm.argtypes = [C.POINTER(GemmArgs), C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_void_p]
         L.t2_gemm_plan.argtypes = [C.POINTER(GemmArgs), C.POINTER(GemmPlanOpts), C.POINTER(GemmPlanInfo)]
+        L.t2_conv_handoff_plan.argtypes = [C.POINTER(GemmArgs), C.POINTER(GemmPlanOpts), C.POINTER(C.c_int), C.POINTER(GemmPlanInfo)]
         L.t2_colsum.argtypes = [C.c_void_p, C.c_long, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
         L.t2_mask_btc.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_float, C.c_void_p]
         L.t2_prof_enable.argtypes = [C.c_int]
@@ -445,6 +448,15 @@ def gemm_plan(args: GemmArgs, **opts) -> dict:
     check(lib().t2_gemm_plan(C.byref(args), C.byref(o), C.byref(info)))
     return dict(kernel=info.kernel, name=info.name.decode(), split=bool(info.split), splitk=info.splitk, kchunks=info.kchunks,
                 a_src=info.a_src, b_src=info.b_src, stage_bytes_a=info.stage_bytes_a, stage_bytes_b=info.stage_bytes_b)
+
+
+def conv_handoff_plan(args: GemmArgs, **opts) -> dict:
+    """The conv stacks' hand-over rule for the product `args` with the bf16 copies opts offers (t2_conv_handoff_plan): the
+    plan as gemm_plan returns it plus taken = whether the copies are handed over."""
+    o, info, taken = GemmPlanOpts(**opts), GemmPlanInfo(), C.c_int(0)
+    check(lib().t2_conv_handoff_plan(C.byref(args), C.byref(o), C.byref(taken), C.byref(info)))
+    return dict(taken=bool(taken.value), kernel=info.kernel, name=info.name.decode(), split=bool(info.split), splitk=info.splitk,
+                kchunks=info.kchunks, a_src=info.a_src, b_src=info.b_src, stage_bytes_a=info.stage_bytes_a, stage_bytes_b=info.stage_bytes_b)
 
 
 def set_gemm_split_min_mflop(mflop: int = -1) -> None:

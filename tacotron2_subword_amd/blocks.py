@@ -17,6 +17,7 @@ import torch
 from . import _lib as L
 
 ACT_NONE, ACT_RELU, ACT_TANH = 0, 1, 2
+CONV_HANDOFF = True     # bf16 mode: the conv stacks pass bf16 copies from layer to layer instead of having them cast (same bits)
 _WS = {}
 
 
@@ -126,7 +127,8 @@ class _ConvStackFn(torch.autograd.Function):
         B, T, _ = x.shape
         n = len(cfg["acts"])
         dev = x.device
-        saved, cur = [], x
+        saved, cur, cur16 = [], x, None
+        handoff = CONV_HANDOFF and L.get_precision() == "bf16"
         for i in range(n):
             w, bias, gamma, beta = params[4 * i:4 * i + 4]
             rm, rv = cfg["buffers"][i]
@@ -138,14 +140,16 @@ class _ConvStackFn(torch.autograd.Function):
             nws = Cout * Cin * K + 4 + 128 * Cout + _stage_terms() * ((M * Cin + Cout * Cin * K) // 2) + 4096    # + bf16 operand staging + split-K
             ws = _scratch(dev, nws)
             res = x if (cfg["residual"] and i == n - 1) else None
+            y16 = torch.empty(B, T, Cout, dtype=torch.bfloat16, device=dev) if handoff and i + 1 < n else None
             a = L.ConvBnArgs(B, T, Cin, Cout, K, L.ptr(cur), L.ptr(w.detach()), L.ptr(bias.detach()), L.ptr(gamma.detach()),
                              L.ptr(beta.detach()), L.ptr(rm), L.ptr(rv), int(cfg["training"]), 1e-5, cfg["acts"][i],
                              cfg["drop_p"] if cfg["training"] else 0.0, cfg["seed"], cfg["site0"] + i, L.ptr(res),
-                             L.ptr(z), L.ptr(st[0]), L.ptr(st[1]), L.ptr(st[2]), L.ptr(y), L.ptr(ws), ws.numel())
+                             L.ptr(z), L.ptr(st[0]), L.ptr(st[1]), L.ptr(st[2]), L.ptr(y), L.ptr(ws), ws.numel(),
+                             L.ptr(cur16), L.ptr(y16), int(handoff))
             L.check(L.lib().t2_conv_bn_forward(C.byref(a), L.stream()))
-            saved.append((cur, z, st))
-            cur = y
-        ctx.cfg, ctx.saved_acts, ctx.params = cfg, saved, [p.detach() for p in params]
+            saved.append((cur, z, st, cur16))
+            cur, cur16 = y, y16
+        ctx.cfg, ctx.saved_acts, ctx.params, ctx.handoff = cfg, saved, [p.detach() for p in params], handoff
         return cur
 
     @staticmethod
@@ -158,7 +162,7 @@ class _ConvStackFn(torch.autograd.Function):
         grads = [None] * (4 * n)
         for i in range(n - 1, -1, -1):
             w, bias, gamma, beta = params[4 * i:4 * i + 4]
-            xin, z, st = ctx.saved_acts[i]
+            xin, z, st, xin16 = ctx.saved_acts[i]
             B, T, Cin = xin.shape
             Cout, _, K = w.shape
             M = B * T
@@ -171,7 +175,7 @@ class _ConvStackFn(torch.autograd.Function):
             a = L.ConvBnBwdArgs(B, T, Cin, Cout, K, L.ptr(xin), L.ptr(w), L.ptr(gamma), L.ptr(beta), L.ptr(z), L.ptr(st[0]), L.ptr(st[1]),
                                 int(cfg["training"]), 1e-5, cfg["acts"][i], cfg["drop_p"] if cfg["training"] else 0.0, cfg["seed"],
                                 cfg["site0"] + i, L.ptr(dy), L.ptr(dw), L.ptr(db), L.ptr(dg), L.ptr(dbt), L.ptr(dx), 0,
-                                L.ptr(ws), ws.numel())
+                                L.ptr(ws), ws.numel(), L.ptr(xin16), int(ctx.handoff and L.get_precision() == "bf16"))
             L.check(L.lib().t2_conv_bn_backward(C.byref(a), L.stream()))
             grads[4 * i:4 * i + 4] = [dw, db, dg, dbt]
             dy = dx

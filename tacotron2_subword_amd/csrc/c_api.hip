@@ -1518,6 +1518,7 @@ int t2_conv_bn_forward(const t2_conv_bn_args* a, void* stream) {
     f.wperm = a->ws; f.scratch = a->ws + align4(nw);
     const size_t used = align4(nw) + 128 * (size_t)a->Cout;
     if (a->ws_floats > used) { f.gemm_ws = a->ws + used; f.gemm_ws_bytes = (a->ws_floats - used) * sizeof(float); }
+    f.handoff = a->handoff; f.x16 = static_cast<const __bf16*>(a->x16); f.y16 = static_cast<__bf16*>(a->y16);
     return conv_bn_fwd(f, (hipStream_t)stream);
 }
 
@@ -1533,6 +1534,7 @@ int t2_conv_bn_backward(const t2_conv_bn_bwd_args* a, void* stream) {
     f.dx = a->dx; f.dx_accumulate = a->dx_accumulate;
     f.dz = a->ws; f.wperm = a->ws + ndz; f.scratch = a->ws + ndz + nw;
     f.gemm_ws = a->ws + ndz + nw + nsc; f.gemm_ws_bytes = (a->ws_floats - (ndz + nw + nsc)) * sizeof(float);
+    f.handoff = a->handoff; f.x16 = static_cast<const __bf16*>(a->x16);
     return conv_bn_bwd(f, (hipStream_t)stream);
 }
 
@@ -1656,9 +1658,8 @@ int t2_gemm_ex(const t2_gemm_args* a, void* stream) {
     T2_REQUIRE(a, "null argument");
     return gemm(desc_of(*a), (hipStream_t)stream);
 }
-int t2_gemm_plan(const t2_gemm_args* a, const t2_gemm_plan_opts* o, t2_gemm_plan_info* out) {
-    T2_REQUIRE(a && out, "null argument");
-    GemmDesc g = desc_of(*a);
+static GemmDesc desc_of(const t2_gemm_args& a, const t2_gemm_plan_opts* o) {
+    GemmDesc g = desc_of(a);
     if (o) {
         g.conv_a = o->conv_a; g.conv_b = o->conv_b; g.conv_T = o->conv_T; g.conv_C = o->conv_C; g.fp32_only = o->fp32_only;
         const __bf16* copy = reinterpret_cast<const __bf16*>(uintptr_t(256));          // only its alignment is looked at
@@ -1666,9 +1667,27 @@ int t2_gemm_plan(const t2_gemm_args* a, const t2_gemm_plan_opts* o, t2_gemm_plan
         if (o->b16) { g.B16 = copy; g.ldb16 = o->ldb16; g.b16_kmajor = o->b16_kmajor; }
         g.split16 = o->split16;
     }
+    return g;
+}
+static t2_gemm_plan_info info_of(const GemmPlan& p) {
+    return t2_gemm_plan_info{(int)p.kernel, gemm_plan_name(p), p.split, p.splitk, p.kchunks, (int)p.a.src, (int)p.b.src, p.a.bytes, p.b.bytes};
+}
+int t2_gemm_plan(const t2_gemm_args* a, const t2_gemm_plan_opts* o, t2_gemm_plan_info* out) {
+    T2_REQUIRE(a && out, "null argument");
     GemmPlan p;
-    T2_TRY(gemm_plan(g, &p));
-    *out = t2_gemm_plan_info{(int)p.kernel, gemm_plan_name(p), p.split, p.splitk, p.kchunks, (int)p.a.src, (int)p.b.src, p.a.bytes, p.b.bytes};
+    T2_TRY(gemm_plan(desc_of(*a, o), &p));
+    *out = info_of(p);
+    return 0;
+}
+int t2_conv_handoff_plan(const t2_gemm_args* a, const t2_gemm_plan_opts* o, int* taken, t2_gemm_plan_info* out) {
+    T2_REQUIRE(a && taken && out, "null argument");
+    const GemmDesc offered = desc_of(*a, o);
+    GemmDesc plain = offered;
+    plain.A16 = plain.B16 = nullptr; plain.a16_kmajor = plain.b16_kmajor = 0; plain.lda16 = plain.ldb16 = 0;
+    GemmPlan p;
+    T2_TRY(gemm_plan(plain, &p));                       // the checks of gemm(), and its refusals
+    *taken = gemm_handoff(plain, offered, &p);
+    *out = info_of(p);
     return 0;
 }
 // bench.py's GEMM roofline figure: `reps` launches of one product bracketed by HIP events on the launch stream, once as

@@ -63,6 +63,68 @@ __device__ __forceinline__ float wave_max(float v) {
     return v;
 }
 
+// ---------------------------------------------------------------------------------------------
+// Stage 1 of the fixed-order column reductions (colsum, the BatchNorm statistics).  The sum of a
+// column over a slab of rows is defined as ((p0 + p1) + p2) + p3, where phase p adds rows
+// m0+p, m0+p+4, ... one after the other.  That order fixes the bits; how many loads are in flight
+// does not, so a lane owns V adjacent columns (one 16-byte load per row for V = 4), requests R rows
+// before it consumes the first, and has the next R on their way while it consumes.
+// A workgroup is 4 phases x kColLanes lanes and covers kColLanes*V columns of one slab.
+// ---------------------------------------------------------------------------------------------
+constexpr int kColLanes = 32;
+constexpr int kColThreads = 4 * kColLanes;
+
+template <int V> struct ColVec { float v[V]; };
+template <int V> __device__ __forceinline__ ColVec<V> load_cols(const float* p) {
+    static_assert(V == 1 || V == 4, "one column or one 16-byte group per lane");
+    ColVec<V> r;
+    if constexpr (V == 4) {
+        const f32x4 t = *reinterpret_cast<const f32x4*>(p);
+        r.v[0] = t.x; r.v[1] = t.y; r.v[2] = t.z; r.v[3] = t.w;
+    } else r.v[0] = *p;
+    return r;
+}
+template <int V> __device__ __forceinline__ void store_cols(float* p, const ColVec<V>& r) {
+    if constexpr (V == 4) { f32x4 t; t.x = r.v[0]; t.y = r.v[1]; t.z = r.v[2]; t.w = r.v[3]; *reinterpret_cast<f32x4*>(p) = t; }
+    else *p = r.v[0];
+}
+// use(m, load(m)) for m = m, m+4, ... < m1, in that order.  The tail requests a full group too (rows past the end
+// repeat the last valid one and are not used), so no load sits behind a branch of its own.
+template <int R, class Row, class Load, class Use>
+__device__ __forceinline__ void rows_in_flight(int m, const int m1, Load load, Use use) {
+    int left = m < m1 ? (m1 - m + 3) / 4 : 0;
+    Row a[R], b[R];                                        // two groups by name: a copy between them would wait for the loads
+    auto request = [&](Row (&x)[R], int mm) {
+#pragma unroll
+        for (int j = 0; j < R; ++j) x[j] = load(mm + 4 * j);
+    };
+    auto consume = [&](const Row (&x)[R]) {
+#pragma unroll
+        for (int j = 0; j < R; ++j) use(m + 4 * j, x[j]);
+        m += 4 * R;
+        left -= R;
+    };
+    if (left >= R) request(a, m);
+    while (left >= R) {
+        if (left >= 2 * R) request(b, m + 4 * R);
+        consume(a);
+        if (left < R) break;
+        if (left >= 2 * R) request(a, m + 4 * R);
+        consume(b);
+    }
+    if (left > 0) {
+#pragma unroll
+        for (int j = 0; j < R; ++j) a[j] = load(m + 4 * (j < left ? j : left - 1));
+#pragma unroll
+        for (int j = 0; j < R; ++j) if (j < left) use(m + 4 * j, a[j]);
+    }
+}
+// the partition both stages agree on
+__host__ __device__ inline int col_slabs(int M) { return M >= 64 * 64 ? 64 : (M >= 64 ? M / 64 : 1); }
+inline bool cols_vectorisable(const void* p, long ld, int N) {
+    return N % 4 == 0 && ld % 4 == 0 && (reinterpret_cast<uintptr_t>(p) & 15) == 0;
+}
+
 }  // namespace t2
 
 // ---------------------------------------------------------------------------------------------

@@ -2,11 +2,19 @@
 // (Postnet.forward, model.py:65-70; the conv part of Encoder.forward, model.py:97-99), forward and
 // backward, plus the embedding gather / gradient.
 //
-// The convolution is an implicit-im2col GEMM on the fp32 matrix cores (gemm.hip, ConvAddr): no
-// column matrix is materialised.  Weights are re-laid-out per call from the reference's
-// [Cout, Cin, k] to [Cout, k*Cin] (and flipped/transposed for the data gradient) — 5 MB per layer.
+// The convolution is an implicit-im2col GEMM (gemm.hip, ConvAddr): no column matrix is
+// materialised.  Which kernel runs it is plan_gemm's decision: the exact fp32 kernels in mode f32,
+// in mode bf16 the bf16-source kernels on bf16 copies of the frames and the weights (forward and
+// d(input): conv_a, 256- or 128-tiles; d(weight): the k-major 256-tile kernel with the frames as
+// conv_b) or the converting kernel for shapes that are no whole tiles, in mode bf16x3 the same
+// routes on split copies.  Weights are re-laid-out per call from the reference's [Cout, Cin, k] to
+// [Cout, k*Cin] (and flipped/transposed for the data gradient) — 5 MB per layer.
+// bf16 hand-offs (mode bf16, on request): instead of leaving every cast to gemm(), a layer writes
+// its output also as bf16 for the next layer's product, dz once as bf16 for both backward
+// products, and the re-laid-out weights straight as bf16 — only where gemm_handoff (gemm.hip)
+// finds that the product keeps its kernel and split-K, so the results are the same bits.
 // BatchNorm statistics use two passes (mean, then centred sum of squares) over two-stage
-// fixed-order column reductions, so results are reproducible run to run.
+// fixed-order column reductions (common.h), so results are reproducible run to run.
 #include "kernels.h"
 
 namespace t2 {
@@ -18,20 +26,24 @@ inline int grid_for(size_t n, int block = 256, int cap = 8192) {
     return (int)(g < 1 ? 1 : (g > (size_t)cap ? cap : g));
 }
 
+// The re-laid-out weights are written as fp32, or straight as the bf16 copy when the product takes one (OUT = __bf16: the
+// round-to-nearest cast the staging kernels apply to the fp32 array).
 // wp[co][dk*Ci + ci] = w[co][ci][dk]
-__global__ void permute_w_fwd_kernel(const float* __restrict__ w, float* __restrict__ wp, int Co, int Ci, int K) {
+template <class OUT>
+__global__ void permute_w_fwd_kernel(const float* __restrict__ w, OUT* __restrict__ wp, int Co, int Ci, int K) {
     const size_t n = (size_t)Co * Ci * K;
     for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
         const int ci = (int)(i % Ci); const size_t r = i / Ci; const int dk = (int)(r % K), co = (int)(r / K);
-        wp[i] = w[((size_t)co * Ci + ci) * K + dk];
+        wp[i] = (OUT)w[((size_t)co * Ci + ci) * K + dk];
     }
 }
 // wt[ci][dk*Co + co] = w[co][ci][K-1-dk]     (data gradient = correlation with the flipped kernel)
-__global__ void permute_w_bwd_kernel(const float* __restrict__ w, float* __restrict__ wt, int Co, int Ci, int K) {
+template <class OUT>
+__global__ void permute_w_bwd_kernel(const float* __restrict__ w, OUT* __restrict__ wt, int Co, int Ci, int K) {
     const size_t n = (size_t)Co * Ci * K;
     for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
         const int co = (int)(i % Co); const size_t r = i / Co; const int dk = (int)(r % K), ci = (int)(r / K);
-        wt[i] = w[((size_t)co * Ci + ci) * K + (K - 1 - dk)];
+        wt[i] = (OUT)w[((size_t)co * Ci + ci) * K + (K - 1 - dk)];
     }
 }
 // dw[co][ci][dk] = dwp[co][dk*Ci + ci]
@@ -53,42 +65,73 @@ __device__ __forceinline__ float act_fwd(float u, int act) {
 
 // Two-stage column reductions.  MODE 0: sum z.  MODE 1: sum (z-mean)^2.
 // MODE 2 (backward): du = dy * keep/(1-p) * act'(u), written to `du`; s0 = sum du, s1 = sum du*xhat.
+// One term of a column.  Which products are fused into the following add is part of the result's bits, so it is
+// written out (fmaf) and nothing else is contracted: MODE 1 accumulates fma(d, d, a0); MODE 2 forms u and 1 - t*t
+// with one fma each and adds the rounded product g*xh.
+struct BnCol { float mean, inv, ga, be; };
 template <int MODE>
-__global__ void colreduce_stage1_kernel(BnElem e, const float* __restrict__ dy, float* __restrict__ du, int M, int slabs,
-                                        float* __restrict__ scratch) {
+__device__ __forceinline__ float colreduce_term(const BnElem& e, const BnCol& k, float scale, float z, float g, uint32_t i,
+                                                float& a0, float& a1) {
+#pragma clang fp contract(off)
+    if (MODE == 0) a0 += z;
+    else if (MODE == 1) { const float d = z - k.mean; a0 = fmaf(d, d, a0); }
+    else {
+        const float xh = (z - k.mean) * k.inv, u = fmaf(xh, k.ga, k.be);
+        if (e.drop_p > 0.f) g = rng_keep(e.key, i, e.drop_p) ? g * scale : 0.f;
+        if (e.act == ACT_RELU) g = u > 0.f ? g : 0.f;
+        else if (e.act == ACT_TANH) { const float t = tanhf(u); g *= fmaf(-t, t, 1.0f); }
+        const float gx = g * xh;
+        a0 += g; a1 += gx;
+    }
+    return g;
+}
+template <int MODE, int V>
+__global__ void __launch_bounds__(kColThreads) colreduce_stage1_kernel(BnElem e, const float* __restrict__ dy, float* __restrict__ du,
+                                                                       int M, int slabs, float* __restrict__ scratch) {
+    constexpr int R = MODE == 2 ? 8 : 16;      // rows requested ahead: 16 x 16 bytes per lane, twice (MODE 2 reads z and dy)
     const int C = e.C;
-    const int c = blockIdx.x * 64 + (threadIdx.x & 63);
-    const int sub = threadIdx.x >> 6;
+    const int lane = threadIdx.x % kColLanes, sub = threadIdx.x / kColLanes;
+    const int c = (blockIdx.x * kColLanes + lane) * V;
     const int rows = (M + slabs - 1) / slabs;
     const int m0 = blockIdx.y * rows, m1 = min(M, m0 + rows);
-    __shared__ float p0[4][64], p1[4][64];
-    float a0 = 0.f, a1 = 0.f;
+    __shared__ float p0[4][kColLanes * V], p1[4][kColLanes * V];
+    float a0[V] = {}, a1[V] = {};
     if (c < C) {
-        const float mean = MODE >= 1 ? e.mean[c] : 0.f;
-        const float inv = MODE == 2 ? e.invstd[c] : 0.f, ga = MODE == 2 ? e.gamma[c] : 0.f, be = MODE == 2 ? e.beta[c] : 0.f;
-        const float scale = e.drop_p > 0.f ? 1.0f / (1.0f - e.drop_p) : 1.0f;
-        for (int m = m0 + sub; m < m1; m += 4) {
-            const size_t i = (size_t)m * C + c;
-            const float z = e.z[i];
-            if (MODE == 0) a0 += z;
-            else if (MODE == 1) { const float d = z - mean; a0 += d * d; }
-            else {
-                const float xh = (z - mean) * inv, u = xh * ga + be;
-                float g = dy[i];
-                if (e.drop_p > 0.f) g = rng_keep(e.key, (uint32_t)i, e.drop_p) ? g * scale : 0.f;
-                if (e.act == ACT_RELU) g = u > 0.f ? g : 0.f;
-                else if (e.act == ACT_TANH) { const float t = tanhf(u); g *= 1.0f - t * t; }
-                du[i] = g;
-                a0 += g; a1 += g * xh;
-            }
+        BnCol col[V];
+#pragma unroll
+        for (int k = 0; k < V; ++k) {
+            col[k].mean = MODE >= 1 ? e.mean[c + k] : 0.f;
+            col[k].inv = MODE == 2 ? e.invstd[c + k] : 0.f; col[k].ga = MODE == 2 ? e.gamma[c + k] : 0.f; col[k].be = MODE == 2 ? e.beta[c + k] : 0.f;
         }
+        const float scale = e.drop_p > 0.f ? 1.0f / (1.0f - e.drop_p) : 1.0f;
+        struct Row { ColVec<V> z, g; };
+        rows_in_flight<R, Row>(m0 + sub, m1,
+            [&](int m) {
+                const size_t i = (size_t)m * C + c;
+                Row r;
+                r.z = load_cols<V>(e.z + i);
+                if (MODE == 2) r.g = load_cols<V>(dy + i);
+                return r;
+            },
+            [&](int m, const Row& r) {
+                const size_t i = (size_t)m * C + c;
+                ColVec<V> g;
+#pragma unroll
+                for (int k = 0; k < V; ++k)
+                    g.v[k] = colreduce_term<MODE>(e, col[k], scale, r.z.v[k], MODE == 2 ? r.g.v[k] : 0.f, (uint32_t)(i + k), a0[k], a1[k]);
+                if (MODE == 2) store_cols<V>(du + i, g);
+            });
     }
-    p0[sub][threadIdx.x & 63] = a0; p1[sub][threadIdx.x & 63] = a1;
+#pragma unroll
+    for (int k = 0; k < V; ++k) { p0[sub][lane * V + k] = a0[k]; p1[sub][lane * V + k] = a1[k]; }
     __syncthreads();
     if (sub == 0 && c < C) {
-        const int l = threadIdx.x;
-        scratch[(size_t)blockIdx.y * C + c] = p0[0][l] + p0[1][l] + p0[2][l] + p0[3][l];
-        if (MODE == 2) scratch[(size_t)(slabs + blockIdx.y) * C + c] = p1[0][l] + p1[1][l] + p1[2][l] + p1[3][l];
+#pragma unroll
+        for (int k = 0; k < V; ++k) {
+            const int l = lane * V + k;
+            scratch[(size_t)blockIdx.y * C + c + k] = p0[0][l] + p0[1][l] + p0[2][l] + p0[3][l];
+            if (MODE == 2) scratch[(size_t)(slabs + blockIdx.y) * C + c + k] = p1[0][l] + p1[1][l] + p1[2][l] + p1[3][l];
+        }
     }
 }
 // out0[c] = f(sum over slabs); MODE 0: mean = s/M ; MODE 1: invstd = rsqrt(s/M + eps), var_out = s/M ; MODE 2: raw sums
@@ -118,29 +161,74 @@ __global__ void colreduce_stage2_kernel(const float* __restrict__ scratch, int C
 }
 
 // y = dropout(act((z-mean)*invstd*gamma + beta)) (+ residual)
-__global__ void bn_apply_kernel(BnElem e, const float* __restrict__ residual, float* __restrict__ y, size_t n) {
+// A lane handles V adjacent channels per step (V = 4: 16-byte accesses).  The channel of a lane's first element is
+// divided out once and then stepped, so the loop holds no division.  As in the reductions, the fused products are
+// written out: u = fma(xhat, gamma, beta); the two mean corrections of dz are one fma each.
+typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
+// the bf16 copy of V adjacent values for the next GEMM (round to nearest even, as the staging cast of the fp32 array)
+template <int V> __device__ __forceinline__ void store_cols16(__bf16* p, const ColVec<V>& r) {
+    if constexpr (V == 4) { bf16x4 t; t[0] = (__bf16)r.v[0]; t[1] = (__bf16)r.v[1]; t[2] = (__bf16)r.v[2]; t[3] = (__bf16)r.v[3]; *reinterpret_cast<bf16x4*>(p) = t; }
+    else *p = (__bf16)r.v[0];
+}
+__device__ __forceinline__ float bn_apply_term(const BnElem& e, float scale, float z, float mean, float inv, float ga, float be, uint32_t i) {
+#pragma clang fp contract(off)
+    float v = act_fwd(fmaf((z - mean) * inv, ga, be), e.act);
+    if (e.drop_p > 0.f) v = rng_keep(e.key, i, e.drop_p) ? v * scale : 0.f;
+    return v;
+}
+template <int V>
+__global__ void bn_apply_kernel(BnElem e, const float* __restrict__ residual, float* __restrict__ y, __bf16* __restrict__ y16, size_t n) {
     const float scale = e.drop_p > 0.f ? 1.0f / (1.0f - e.drop_p) : 1.0f;
-    for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
-        const int c = (int)(i % e.C);
-        float v = act_fwd((e.z[i] - e.mean[c]) * e.invstd[c] * e.gamma[c] + e.beta[c], e.act);
-        if (e.drop_p > 0.f) v = rng_keep(e.key, (uint32_t)i, e.drop_p) ? v * scale : 0.f;
-        if (residual) v += residual[i];
-        y[i] = v;
+    const size_t stride = (size_t)gridDim.x * blockDim.x * V;
+    size_t i = (blockIdx.x * (size_t)blockDim.x + threadIdx.x) * V;
+    int c = (int)(i % e.C);
+    const int cstep = (int)(stride % e.C);
+    for (; i < n; i += stride) {
+        const ColVec<V> z = load_cols<V>(e.z + i), mean = load_cols<V>(e.mean + c), inv = load_cols<V>(e.invstd + c),
+                        ga = load_cols<V>(e.gamma + c), be = load_cols<V>(e.beta + c);
+        ColVec<V> v;
+#pragma unroll
+        for (int k = 0; k < V; ++k) v.v[k] = bn_apply_term(e, scale, z.v[k], mean.v[k], inv.v[k], ga.v[k], be.v[k], (uint32_t)(i + k));
+        if (residual) {
+            const ColVec<V> r = load_cols<V>(residual + i);
+#pragma unroll
+            for (int k = 0; k < V; ++k) v.v[k] += r.v[k];
+        }
+        store_cols<V>(y + i, v);
+        if (y16) store_cols16<V>(y16 + i, v);
+        c += cstep;
+        if (c >= e.C) c -= e.C;
     }
 }
 // training: dz = gamma*invstd*(du - sum_du/M - xhat*sum_duxh/M) ; eval: dz = du*gamma*invstd
-__global__ void bn_bwd_dz_kernel(BnElem e, const float* __restrict__ du, const float* __restrict__ sdu, const float* __restrict__ sduxh,
-                                 int M, int training, float* __restrict__ dz, size_t n) {
+__device__ __forceinline__ float bn_bwd_dz_term(float g, float z, float mean, float inv, float ga, float sdu, float sduxh, float invM, int training) {
+#pragma clang fp contract(off)
+    if (training) {
+        const float xh = (z - mean) * inv;
+        g = fmaf(-invM, sdu, g);
+        g = fmaf(-invM, xh * sduxh, g);
+    }
+    return g * ga * inv;
+}
+template <int V>
+__global__ void bn_bwd_dz_kernel(BnElem e, const float* du, const float* __restrict__ sdu, const float* __restrict__ sduxh,
+                                 int M, int training, float* dz, __bf16* __restrict__ dz16, size_t n) {
     const float invM = 1.0f / (float)M;
-    for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
-        const int c = (int)(i % e.C);
-        const float inv = e.invstd[c], ga = e.gamma[c];
-        float g = du[i];
-        if (training) {
-            const float xh = (e.z[i] - e.mean[c]) * inv;
-            g = g - sdu[c] * invM - xh * sduxh[c] * invM;
-        }
-        dz[i] = g * ga * inv;
+    const size_t stride = (size_t)gridDim.x * blockDim.x * V;
+    size_t i = (blockIdx.x * (size_t)blockDim.x + threadIdx.x) * V;
+    int c = (int)(i % e.C);
+    const int cstep = (int)(stride % e.C);
+    for (; i < n; i += stride) {
+        const ColVec<V> g = load_cols<V>(du + i), inv = load_cols<V>(e.invstd + c), ga = load_cols<V>(e.gamma + c);
+        ColVec<V> z{}, mean{}, s0{}, s1{};
+        if (training) { z = load_cols<V>(e.z + i); mean = load_cols<V>(e.mean + c); s0 = load_cols<V>(sdu + c); s1 = load_cols<V>(sduxh + c); }
+        ColVec<V> o;
+#pragma unroll
+        for (int k = 0; k < V; ++k) o.v[k] = bn_bwd_dz_term(g.v[k], z.v[k], mean.v[k], inv.v[k], ga.v[k], s0.v[k], s1.v[k], invM, training);
+        store_cols<V>(dz + i, o);
+        if (dz16) store_cols16<V>(dz16 + i, o);
+        c += cstep;
+        if (c >= e.C) c -= e.C;
     }
 }
 // running statistics (momentum 0.1, unbiased variance), model.py:42 nn.BatchNorm1d defaults
@@ -206,10 +294,23 @@ __global__ void embedding_bwd_kernel(const long* __restrict__ ids, const float* 
     }
 }
 
+// 16-byte accesses need C % 4 == 0 and every array on a 16-byte boundary (p, q: the kernel's other arrays, may be null)
+bool bn_vectorisable(const BnElem& e, const void* p, const void* q) {
+    for (const void* a : {(const void*)e.z, (const void*)e.mean, (const void*)e.invstd, (const void*)e.gamma, (const void*)e.beta, p, q})
+        if (!cols_vectorisable(a, e.C, e.C)) return false;
+    return true;
+}
+inline bool aligned8(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 7) == 0; }
+inline size_t round256(size_t n) { return (n + 255) & ~(size_t)255; }
+inline bool same_route(const GemmPlan& p, const GemmPlan& q) { return p.kernel == q.kernel && p.split == q.split && p.splitk == q.splitk && p.kchunks == q.kchunks; }
+
 template <int MODE>
 int colreduce(const BnElem& e, const float* dy, float* du, int M, float eps, float* out0, float* out1, float* scratch, hipStream_t s) {
-    const int slabs = M >= 64 * 64 ? 64 : (M >= 64 ? M / 64 : 1);
-    hipLaunchKernelGGL(colreduce_stage1_kernel<MODE>, dim3((e.C + 63) / 64, slabs), dim3(256), 0, s, e, dy, du, M, slabs, scratch);
+    const int slabs = col_slabs(M);
+    if (cols_vectorisable(e.z, e.C, e.C) && cols_vectorisable(dy, e.C, e.C) && cols_vectorisable(du, e.C, e.C))
+        hipLaunchKernelGGL((colreduce_stage1_kernel<MODE, 4>), dim3((e.C + 4 * kColLanes - 1) / (4 * kColLanes), slabs), dim3(kColThreads), 0, s, e, dy, du, M, slabs, scratch);
+    else
+        hipLaunchKernelGGL((colreduce_stage1_kernel<MODE, 1>), dim3((e.C + kColLanes - 1) / kColLanes, slabs), dim3(kColThreads), 0, s, e, dy, du, M, slabs, scratch);
     T2_LAUNCH_CHECK();
     hipLaunchKernelGGL(colreduce_stage2_kernel, dim3((e.C + 255) / 256), dim3(256), 0, s, scratch, e.C, slabs, M, MODE, eps, out0, out1);
     T2_LAUNCH_CHECK();
@@ -223,13 +324,22 @@ int conv_bn_fwd(const ConvBnFwd& a, hipStream_t s) {
     T2_REQUIRE(a.Cin % 4 == 0 && a.K % 2 == 1, "conv_bn_fwd: Cin=%d must be a multiple of 4 and the kernel size odd (%d)", a.Cin, a.K);
     T2_REQUIRE((size_t)M * a.Cout < (1ull << 32), "conv_bn_fwd: B*T*Cout too large for 32-bit RNG indices");
     const size_t nw = (size_t)a.Cout * a.Cin * a.K;
-    hipLaunchKernelGGL(permute_w_fwd_kernel, dim3(grid_for(nw)), dim3(256), 0, s, a.w, a.wperm, a.Cout, a.Cin, a.K);
-    T2_LAUNCH_CHECK();
     GemmDesc g = gemm_desc();
     g.A = a.x; g.conv_a = 1; g.conv_T = a.T; g.conv_C = a.Cin; g.conv_pad = (a.K - 1) / 2;
     g.B = a.wperm; g.sbn = (long)a.K * a.Cin; g.sbk = 1;
     g.C = a.z; g.ldc = a.Cout; g.M = M; g.N = a.Cout; g.K = a.K * a.Cin; g.bias1 = a.bias;
     g.ws = a.gemm_ws; g.ws_bytes = a.gemm_ws_bytes;
+    // bf16 hand-offs (a.handoff: a stack in bf16 mode): the frames an earlier layer wrote next to its y (x16, if any),
+    // and the weights re-laid-out straight into bf16 — if gemm_handoff says the product is the same with them
+    GemmDesc g16 = g;
+    g16.A16 = a.x16; g16.lda16 = a.Cin;
+    g16.B16 = reinterpret_cast<const __bf16*>(a.wperm); g16.ldb16 = (long)a.K * a.Cin;
+    if (a.handoff && gemm_handoff(g, g16)) {
+        g = g16;
+        hipLaunchKernelGGL(permute_w_fwd_kernel<__bf16>, dim3(grid_for(nw)), dim3(256), 0, s, a.w, reinterpret_cast<__bf16*>(a.wperm), a.Cout, a.Cin, a.K);
+    } else
+        hipLaunchKernelGGL(permute_w_fwd_kernel<float>, dim3(grid_for(nw)), dim3(256), 0, s, a.w, a.wperm, a.Cout, a.Cin, a.K);
+    T2_LAUNCH_CHECK();
     T2_TRY_RC(gemm(g, s));
     BnElem e{a.z, a.mean, a.invstd, a.gamma, a.beta, a.Cout, a.act, a.drop_p, rng_key(a.seed, a.site)};
     if (a.training) {
@@ -245,7 +355,10 @@ int conv_bn_fwd(const ConvBnFwd& a, hipStream_t s) {
         T2_LAUNCH_CHECK();
     }
     const size_t n = (size_t)M * a.Cout;
-    hipLaunchKernelGGL(bn_apply_kernel, dim3(grid_for(n)), dim3(256), 0, s, e, a.residual, a.y, n);
+    if (bn_vectorisable(e, a.residual, a.y) && aligned8(a.y16))
+        hipLaunchKernelGGL(bn_apply_kernel<4>, dim3(grid_for(n / 4)), dim3(256), 0, s, e, a.residual, a.y, a.y16, n);
+    else
+        hipLaunchKernelGGL(bn_apply_kernel<1>, dim3(grid_for(n)), dim3(256), 0, s, e, a.residual, a.y, a.y16, n);
     T2_LAUNCH_CHECK();
     return 0;
 }
@@ -254,32 +367,63 @@ int conv_bn_bwd(const ConvBnBwd& a, hipStream_t s) {
     const int M = a.B * a.T;
     const size_t n = (size_t)M * a.Cout;
     BnElem e{a.z, a.mean, a.invstd, a.gamma, a.beta, a.Cout, a.act, a.drop_p, rng_key(a.seed, a.site)};
-    // du (into a.dz) + the two column sums; d(gamma) = sum du*xhat, d(beta) = sum du
-    T2_TRY_RC(colreduce<2>(e, a.dy, a.dz, M, a.eps, a.dbeta, a.dgamma, a.scratch, s));
-    hipLaunchKernelGGL(bn_bwd_dz_kernel, dim3(grid_for(n)), dim3(256), 0, s, e, a.dz, a.dbeta, a.dgamma, M, a.training, a.dz, n);
-    T2_LAUNCH_CHECK();
-    T2_TRY_RC(colsum(a.dz, a.Cout, M, a.Cout, a.dbias, nullptr, a.scratch, s));
     // d(weight)[co][dk*Ci+ci] = sum_m dz[m,co] * V[m, dk*Ci+ci]   (implicit im2col on the B side)
     GemmDesc g = gemm_desc();
     g.A = a.dz; g.sam = 1; g.sak = a.Cout;
     g.B = a.x; g.conv_b = 1; g.conv_T = a.T; g.conv_C = a.Cin; g.conv_pad = (a.K - 1) / 2;
     g.C = a.wperm; g.ldc = (long)a.K * a.Cin; g.M = a.Cout; g.N = a.K * a.Cin; g.K = M;
     g.ws = a.gemm_ws; g.ws_bytes = a.gemm_ws_bytes;
+    // d(input) = correlation of dz with the flipped, transposed kernel
+    GemmDesc h = gemm_desc();
+    h.A = a.dz; h.conv_a = 1; h.conv_T = a.T; h.conv_C = a.Cout; h.conv_pad = (a.K - 1) / 2;
+    h.B = a.wperm; h.sbn = (long)a.K * a.Cout; h.sbk = 1;
+    h.C = a.dx; h.ldc = a.Cin; h.M = M; h.N = a.Cin; h.K = a.K * a.Cout;
+    h.beta = a.dx_accumulate ? 1.f : 0.f;
+    h.ws = a.gemm_ws; h.ws_bytes = a.gemm_ws_bytes;
+    if (a.dx) T2_REQUIRE(a.Cout % 4 == 0, "conv_bn_bwd: Cout=%d must be a multiple of 4", a.Cout);
+    // bf16 hand-offs (a.handoff: a stack in bf16 mode).  dz16, the bf16 copy of dz, is written once by bn_bwd_dz_kernel
+    // at the head of the GEMM scratch — where d(weight) would stage its A operand and d(input) its frames, the same
+    // bytes — and serves both products; the saved x16 is d(weight)'s frames, the flipped weights go straight to bf16.
+    // Each product takes its copies only if gemm_handoff allows it, and d(weight), if it runs without them while dz16
+    // is alive, must plan the same on the scratch behind it (d(input) runs after dz16's last reader).
+    __bf16* dz16 = nullptr;
+    bool w16 = false;
+    const size_t dz16_bytes = round256(n * sizeof(__bf16));
+    if (a.handoff && a.gemm_ws && (reinterpret_cast<uintptr_t>(a.gemm_ws) & 15) == 0 && a.gemm_ws_bytes >= dz16_bytes) {
+        float* behind = a.gemm_ws + dz16_bytes / sizeof(float);
+        GemmDesc g16 = g, h16 = h;
+        g16.ws = h16.ws = behind; g16.ws_bytes = h16.ws_bytes = a.gemm_ws_bytes - dz16_bytes;
+        g16.A16 = h16.A16 = reinterpret_cast<const __bf16*>(a.gemm_ws);
+        g16.lda16 = a.Cout; g16.a16_kmajor = 1; h16.lda16 = a.Cout;
+        g16.B16 = a.x16; g16.ldb16 = a.Cin; g16.b16_kmajor = 1;
+        h16.B16 = reinterpret_cast<const __bf16*>(a.wperm); h16.ldb16 = (long)a.K * a.Cout;
+        const bool tw = gemm_handoff(g, g16);
+        bool tx = a.dx && gemm_handoff(h, h16);
+        if (tx && !tw) {                                   // d(weight) runs on fp32 operands next to a live dz16
+            GemmDesc gb = g;
+            gb.ws = behind; gb.ws_bytes = g16.ws_bytes;
+            if (same_route(plan_gemm(g), plan_gemm(gb))) g = gb; else tx = false;
+        }
+        if (tw) g = g16;
+        if (tx) { h = h16; w16 = true; }
+        if (tw || tx) dz16 = reinterpret_cast<__bf16*>(a.gemm_ws);
+    }
+    // du (into a.dz) + the two column sums; d(gamma) = sum du*xhat, d(beta) = sum du
+    T2_TRY_RC(colreduce<2>(e, a.dy, a.dz, M, a.eps, a.dbeta, a.dgamma, a.scratch, s));
+    if (bn_vectorisable(e, a.dz, a.dbeta) && cols_vectorisable(a.dgamma, e.C, e.C))
+        hipLaunchKernelGGL(bn_bwd_dz_kernel<4>, dim3(grid_for(n / 4)), dim3(256), 0, s, e, a.dz, a.dbeta, a.dgamma, M, a.training, a.dz, dz16, n);
+    else
+        hipLaunchKernelGGL(bn_bwd_dz_kernel<1>, dim3(grid_for(n)), dim3(256), 0, s, e, a.dz, a.dbeta, a.dgamma, M, a.training, a.dz, dz16, n);
+    T2_LAUNCH_CHECK();
+    T2_TRY_RC(colsum(a.dz, a.Cout, M, a.Cout, a.dbias, nullptr, a.scratch, s));
     T2_TRY_RC(gemm(g, s));
     const size_t nw = (size_t)a.Cout * a.Cin * a.K;
     hipLaunchKernelGGL(unpermute_dw_kernel, dim3(grid_for(nw)), dim3(256), 0, s, a.wperm, a.dw, a.Cout, a.Cin, a.K);
     T2_LAUNCH_CHECK();
     if (a.dx) {
-        // d(input) = correlation of dz with the flipped, transposed kernel
-        T2_REQUIRE(a.Cout % 4 == 0, "conv_bn_bwd: Cout=%d must be a multiple of 4", a.Cout);
-        hipLaunchKernelGGL(permute_w_bwd_kernel, dim3(grid_for(nw)), dim3(256), 0, s, a.w, a.wperm, a.Cout, a.Cin, a.K);
+        if (w16) hipLaunchKernelGGL(permute_w_bwd_kernel<__bf16>, dim3(grid_for(nw)), dim3(256), 0, s, a.w, reinterpret_cast<__bf16*>(a.wperm), a.Cout, a.Cin, a.K);
+        else hipLaunchKernelGGL(permute_w_bwd_kernel<float>, dim3(grid_for(nw)), dim3(256), 0, s, a.w, a.wperm, a.Cout, a.Cin, a.K);
         T2_LAUNCH_CHECK();
-        GemmDesc h = gemm_desc();
-        h.A = a.dz; h.conv_a = 1; h.conv_T = a.T; h.conv_C = a.Cout; h.conv_pad = (a.K - 1) / 2;
-        h.B = a.wperm; h.sbn = (long)a.K * a.Cout; h.sbk = 1;
-        h.C = a.dx; h.ldc = a.Cin; h.M = M; h.N = a.Cin; h.K = a.K * a.Cout;
-        h.beta = a.dx_accumulate ? 1.f : 0.f;
-        h.ws = a.gemm_ws; h.ws_bytes = a.gemm_ws_bytes;
         T2_TRY_RC(gemm(h, s));
     }
     return 0;

@@ -91,18 +91,32 @@ __global__ void relu_drop_bwd_kernel(const float* __restrict__ dy, const float* 
         dz[i] = y[i] > 0.f ? dy[i] * scale : 0.f;
 }
 
-// stage 1: block (x = column tile of 64, y = row slab) sums its slab; stage 2 sums the slabs in order
-__global__ void colsum_stage1_kernel(const float* __restrict__ X, long ld, int M, int N, int slabs, float* scratch) {
-    const int n = blockIdx.x * 64 + (threadIdx.x & 63);
-    const int sub = threadIdx.x >> 6;                                  // 4 row phases per block
+// stage 1: block (x = column tile, y = row slab) sums its slab in the order common.h fixes; stage 2 sums the slabs in order
+template <int V>
+__global__ void __launch_bounds__(kColThreads) colsum_stage1_kernel(const float* __restrict__ X, long ld, int M, int N, int slabs,
+                                                                    float* __restrict__ scratch) {
+    const int lane = threadIdx.x % kColLanes, sub = threadIdx.x / kColLanes;   // 4 row phases per block
+    const int n = (blockIdx.x * kColLanes + lane) * V;
     const int rows = (M + slabs - 1) / slabs;
     const int m0 = blockIdx.y * rows, m1 = min(M, m0 + rows);
-    __shared__ float part[4][64];
-    float acc = 0.f;
-    if (n < N) for (int m = m0 + sub; m < m1; m += 4) acc += X[(long)m * ld + n];
-    part[sub][threadIdx.x & 63] = acc;
+    __shared__ float part[4][kColLanes * V];
+    ColVec<V> acc{};
+    if (n < N)
+        rows_in_flight<16, ColVec<V>>(m0 + sub, m1, [&](int m) { return load_cols<V>(X + (long)m * ld + n); },
+                                      [&](int, const ColVec<V>& x) {
+#pragma unroll
+                                          for (int k = 0; k < V; ++k) acc.v[k] += x.v[k];
+                                      });
+#pragma unroll
+    for (int k = 0; k < V; ++k) part[sub][lane * V + k] = acc.v[k];
     __syncthreads();
-    if (sub == 0 && n < N) scratch[(long)blockIdx.y * N + n] = part[0][threadIdx.x] + part[1][threadIdx.x] + part[2][threadIdx.x] + part[3][threadIdx.x];
+    if (sub == 0 && n < N) {
+#pragma unroll
+        for (int k = 0; k < V; ++k) {
+            const int l = lane * V + k;
+            scratch[(long)blockIdx.y * N + n + k] = part[0][l] + part[1][l] + part[2][l] + part[3][l];
+        }
+    }
 }
 // sum_{s < count} p[s * stride], terms requested 16 at a time and added in index order (a dependent load per term
 // costs ~0.3 us each: 20 us for 64 slabs)
@@ -153,8 +167,11 @@ int relu_drop_bwd(const float* dy, const float* y, float* dz, float scale, size_
     return 0;
 }
 int colsum(const float* X, long ld, int M, int N, float* out, float* out2, float* scratch, hipStream_t s) {
-    const int slabs = M >= 64 * 64 ? 64 : (M >= 64 ? M / 64 : 1);
-    hipLaunchKernelGGL(colsum_stage1_kernel, dim3((N + 63) / 64, slabs), dim3(256), 0, s, X, ld, M, N, slabs, scratch);
+    const int slabs = col_slabs(M);
+    if (cols_vectorisable(X, ld, N))
+        hipLaunchKernelGGL(colsum_stage1_kernel<4>, dim3((N + 4 * kColLanes - 1) / (4 * kColLanes), slabs), dim3(kColThreads), 0, s, X, ld, M, N, slabs, scratch);
+    else
+        hipLaunchKernelGGL(colsum_stage1_kernel<1>, dim3((N + kColLanes - 1) / kColLanes, slabs), dim3(kColThreads), 0, s, X, ld, M, N, slabs, scratch);
     T2_LAUNCH_CHECK();
     hipLaunchKernelGGL(colsum_stage2_kernel, dim3((N + 255) / 256), dim3(256), 0, s, scratch, N, slabs, out, out2);
     T2_LAUNCH_CHECK();

@@ -1392,7 +1392,12 @@ GemmPlan plan_gemm(const GemmDesc& d) {
     a_caller = a_caller && (d.a16_kmajor != 0) == km;
     b_caller = b_caller && (d.b16_kmajor != 0) == km;
     // (split: the k-major conv_b copies are three whole stacks of the frames, so the stack height must keep k % conv_T)
-    const bool conv_ok = !conv_any || (d.conv_a && d.conv_C % 64 == 0 && !a_caller && !b_caller) || (d.conv_b && km && (!want_split || d.K % d.conv_T == 0));
+    // conv_a: a caller copy of A is the bf16 frames [M][conv_C], exactly what gemm() would stage (any other pitch is ignored);
+    // the kernel's buffer resource spans M * conv_C elements and relies on rows outside it reading zero.  Split copies of a
+    // conv_a product have a layout of their own (3C channels per tap): with them the product stays on the exact kernel
+    a_caller = a_caller && (!d.conv_a || d.lda16 == d.conv_C);
+    const bool conv_ok = !conv_any || (d.conv_a && d.conv_C % 64 == 0 && (!want_split || (!a_caller && !b_caller))) ||
+                         (d.conv_b && km && (!want_split || d.K % d.conv_T == 0));
     // bf16-source kernels: both operands staged as bf16 in front of the split-K scratch (or handed over by the caller);
     // pays when each staged element is reused by many tiles, i.e. when both extents are large
     bool staged = false;
@@ -1454,6 +1459,18 @@ int gemm_plan(const GemmDesc& d, GemmPlan* out) {
     *out = plan_gemm(d);
     T2_REQUIRE((long)d.batch * out->splitk <= 65535, "gemm: batch*splitk too large (%d*%d)", d.batch, out->splitk);
     return 0;
+}
+
+bool gemm_handoff(const GemmDesc& plain, const GemmDesc& offered, GemmPlan* plan) {
+    const GemmPlan p0 = plan_gemm(plain);
+    if (plan) *plan = p0;
+    if (g_precision != 1 || !gemm_reads_bf16_copies(p0.kernel) || !(offered.A16 || offered.B16)) return false;
+    if ((offered.A16 && p0.a.src != GemmSrc::staged) || (offered.B16 && p0.b.src != GemmSrc::staged)) return false;
+    const GemmPlan p1 = plan_gemm(offered);
+    if (p1.kernel != p0.kernel || p1.split != p0.split || p1.splitk != p0.splitk || p1.kchunks != p0.kchunks) return false;
+    if ((offered.A16 && p1.a.src != GemmSrc::caller) || (offered.B16 && p1.b.src != GemmSrc::caller)) return false;
+    if (plan) *plan = p1;
+    return true;
 }
 
 int gemm(const GemmDesc& d, hipStream_t s) {

@@ -73,6 +73,12 @@ struct GemmPlan {
 // returns what gemm() would return for a descriptor it refuses.
 GemmPlan plan_gemm(const GemmDesc& d);
 int gemm_plan(const GemmDesc& d, GemmPlan* out);
+// The hand-over rule for bf16 copies a caller could write itself instead of letting gemm() cast them (conv.hip).  `plain` is
+// the product without copies, `offered` the same product with the copies in A16 / B16 and the scratch it would be left
+// with.  True (and *plan, if given, the plan of `offered`) iff, in bf16 mode, `plain` stages every operand a copy is offered
+// for and `offered` takes every copy and names the same kernel, split-K factor and K-chunks per split: then the product
+// computes exactly what it computes without them.  Otherwise the copies must not be handed over (*plan = plan of `plain`).
+bool gemm_handoff(const GemmDesc& plain, const GemmDesc& offered, GemmPlan* plan = nullptr);
 const char* gemm_plan_name(const GemmPlan& p);       // the T2_GEMM_LOG name: f32_64 ... src256km, "x3" in front when split
 // makes the copy a plan asks for (o.src == staged) at dst; split: GemmPlan::split
 int stage_planned(const float* src, const GemmOperandPlan& o, bool split, __bf16* dst, hipStream_t s);
@@ -391,6 +397,8 @@ struct ConvBnFwd {
     float* y;                                    // [B*T, Cout]
     float* wperm; float* scratch;                // [Cout*Cin*K], [128*Cout]
     float* gemm_ws; size_t gemm_ws_bytes;        // optional: bf16 operand staging (gemm.hip)
+    int handoff;                                 // bf16 hand-offs where gemm_handoff allows them (0: every operand is cast by gemm())
+    const __bf16* x16; __bf16* y16;              // optional: the copy of x an earlier layer wrote (used with handoff), the copy of y to write
 };
 int conv_bn_fwd(const ConvBnFwd& a, hipStream_t s);
 struct ConvBnBwd {
@@ -403,6 +411,8 @@ struct ConvBnBwd {
     float* dw; float* dbias; float* dgamma; float* dbeta;
     float* dx; int dx_accumulate;                // [B*T, Cin], nullable
     float* wperm; float* scratch; float* gemm_ws; size_t gemm_ws_bytes;
+    int handoff;                                 // as in ConvBnFwd: dz and the flipped weights are written as bf16 for the two products
+    const __bf16* x16;                           // optional: the bf16 copy of x saved by the forward pass (used with handoff)
 };
 int conv_bn_bwd(const ConvBnBwd& a, hipStream_t s);
 int embedding_fwd(const long* ids, const float* table, float* out, int rows, int D, hipStream_t s);
