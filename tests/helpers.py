@@ -48,3 +48,32 @@ def oracle_memories(P, hp, x, training=False, rnd=None):
         mem = O.front_end(P, hp, text, tl, pcls, "phone", training, rnd)
         mem_sub = O.front_end(P, hp, sub_ids, bl, bcls, "sub", training, rnd)
     return mem, mem_sub
+
+
+def _partition(M):
+    """The row partition of the fixed-order column reductions (csrc/common.h, col_slabs): (slabs, rows per slab)."""
+    slabs = 64 if M >= 64 * 64 else (M // 64 if M >= 64 else 1)
+    return slabs, (M + slabs - 1) // slabs
+
+
+def ordered_colsum(X):
+    """X: [M, N] float32 on the CPU -> the column sums in the documented order, float32."""
+    assert X.dtype == torch.float32 and X.device.type == "cpu"
+    M, N = X.shape
+    slabs, rows = _partition(M)
+    steps = (rows + 3) // 4
+    pad = torch.zeros(slabs * steps * 4 + rows * slabs, N)          # row index m0 + 4*k + p may run past the slab: masked below
+    pad[:M] = X
+    s = torch.arange(slabs).view(slabs, 1)
+    p = torch.arange(4).view(1, 4)
+    acc = torch.zeros(slabs, 4, N)
+    for k in range(steps):
+        r = 4 * k + p                                               # row inside the slab, [1, 4]
+        m = s * rows + r                                            # [slabs, 4]
+        valid = (r < rows) & (m < M)
+        acc = torch.where(valid.unsqueeze(-1), acc + pad[m], acc)
+    slab = ((acc[:, 0] + acc[:, 1]) + acc[:, 2]) + acc[:, 3]
+    out = torch.zeros(N)
+    for i in range(slabs):
+        out = out + slab[i]
+    return out

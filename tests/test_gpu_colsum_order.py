@@ -15,6 +15,8 @@ import ctypes as C
 import pytest
 import torch
 
+from helpers import _partition, ordered_colsum
+
 pytestmark = pytest.mark.gpu
 
 U = 2.0 ** -24
@@ -24,34 +26,6 @@ U = 2.0 ** -24
 def env():
     from tacotron2_subword_amd import _lib as L, blocks
     return L, blocks
-
-
-def _partition(M):
-    slabs = 64 if M >= 64 * 64 else (M // 64 if M >= 64 else 1)
-    return slabs, (M + slabs - 1) // slabs
-
-
-def ordered_colsum(X):
-    """X: [M, N] float32 on the CPU -> the column sums in the documented order, float32."""
-    assert X.dtype == torch.float32 and X.device.type == "cpu"
-    M, N = X.shape
-    slabs, rows = _partition(M)
-    steps = (rows + 3) // 4
-    pad = torch.zeros(slabs * steps * 4 + rows * slabs, N)          # row index m0 + 4*k + p may run past the slab: masked below
-    pad[:M] = X
-    s = torch.arange(slabs).view(slabs, 1)
-    p = torch.arange(4).view(1, 4)
-    acc = torch.zeros(slabs, 4, N)
-    for k in range(steps):
-        r = 4 * k + p                                               # row inside the slab, [1, 4]
-        m = s * rows + r                                            # [slabs, 4]
-        valid = (r < rows) & (m < M)
-        acc = torch.where(valid.unsqueeze(-1), acc + pad[m], acc)
-    slab = ((acc[:, 0] + acc[:, 1]) + acc[:, 2]) + acc[:, 3]
-    out = torch.zeros(N)
-    for i in range(slabs):
-        out = out + slab[i]
-    return out
 
 
 def _gpu_colsum(L, base, off, M, N, ld):
@@ -70,6 +44,25 @@ def _gpu_colsum(L, base, off, M, N, ld):
     (4160, 1, 1, 0),
     (300, 64, 128, 0),        # ld != N
     (260, 64, 64, 1),         # base 4 bytes off a 16-byte boundary
+    # The row loop (rows_in_flight, 16 rows per group, two groups a / b in flight) by rows per phase: a phase of a slab of
+    # `rows` rows has ceil((rows - p) / 4) of them.  N = 4: one 16-byte group per lane; N = 6, 1: one column per lane.
+    (127, 4, 4, 0),           # one slab, phases 32 32 32 31: two groups exactly (a, b, no tail) / one group + a 15-row tail
+    (127, 6, 6, 0),
+    (8192, 4, 4, 0),          # 64 slabs of 128 rows: 32 per phase
+    (8200, 6, 6, 0),          # 129 rows: 33 32 32 32 (a, b, a tail of one row); the last slab has 73
+    (8200, 1, 1, 0),
+    (12288, 1, 1, 0),         # 192 rows: 48 per phase, b consumed and a requested again
+    (12288, 4, 4, 0),
+    (12289, 4, 4, 0),         # 193 rows: 49 48 48 48
+    (12289, 6, 6, 0),
+    (16384, 6, 6, 0),         # 256 rows: 64 per phase, two full rounds
+    (16384, 4, 4, 0),
+    (16390, 4, 4, 0),         # 257 rows: 65 64 64 64
+    (16390, 1, 1, 0),
+    (25600, 4, 4, 0),         # the workload's M: 400 rows, 100 per phase (six groups and a 4-row tail)
+    (25600, 6, 6, 0),
+    (8200, 132, 132, 0),      # the second 128-column tile of the 16-byte kernel is partly outside N
+    (12289, 4, 4, 1),         # base 4 bytes off a 16-byte boundary: the one-column kernel through the refill
 ])
 def test_colsum_matches_documented_order(env, M, N, ld, off):
     L, _ = env
@@ -80,11 +73,19 @@ def test_colsum_matches_documented_order(env, M, N, ld, off):
     assert torch.equal(got, ordered_colsum(X))
 
 
-@pytest.mark.parametrize("B,T,Cin,Cout", [(16, 260, 16, 132), (3, 50, 16, 80)])
-def test_batchnorm_statistics_order(env, B, T, Cin, Cout):
+# The ladder of the colsum test for the BatchNorm reductions: 16 rows per group for mean / var (phases of 31/32, 32/33, 47/48,
+# 48/49, 64/65 and 100 rows), 8 per group for the backward sums (16/17, 24/25, 32/33 rows: M = 64 * 65, 64 * 97, 64 * 129).
+_BN_LADDER = [(1, 127, 4, 4, 5), (4, 1040, 4, 4, 1), (4, 1552, 4, 8, 5), (8, 1032, 4, 4, 1), (8, 1024, 4, 8, 1), (8, 1025, 4, 4, 5),
+              (8, 1536, 4, 4, 1), (1, 12289, 4, 8, 5), (16, 1024, 4, 4, 5), (2, 8195, 4, 8, 1), (64, 400, 4, 4, 5), (64, 400, 4, 8, 1),
+              (64, 400, 4, 6, 1)]      # Cout = 6: one column per lane (no d(input): the ABI wants Cout % 4 == 0 for it)
+
+
+@pytest.mark.parametrize("B,T,Cin,Cout,K", [pytest.param(16, 260, 16, 132, 5, id="16-260-16-132"), pytest.param(3, 50, 16, 80, 5, id="3-50-16-80")]
+                         + _BN_LADDER)
+def test_batchnorm_statistics_order(env, B, T, Cin, Cout, K):
     L, blocks = env
     assert L.get_precision() == "f32"
-    K, M, eps = 5, B * T, 1e-5
+    M, eps = B * T, 1e-5
     g = torch.Generator().manual_seed(B * 7 + Cout)
     dev = "cuda"
     x = torch.randn(B, T, Cin, generator=g).to(dev)
@@ -104,7 +105,7 @@ def test_batchnorm_statistics_order(env, B, T, Cin, Cout):
     dy = torch.randn(B, T, Cout, generator=g).to(dev)
     dw, db = torch.empty_like(w), torch.empty_like(bias)
     dg, dbt = torch.empty_like(gamma), torch.empty_like(beta)
-    dx = torch.empty(B, T, Cin, device=dev)
+    dx = torch.empty(B, T, Cin, device=dev) if Cout % 4 == 0 else None
     ws2 = torch.empty(M * Cout + 2 * Cout * Cin * K + 128 * Cout + 16 + (1 << 20) + M * K * max(Cin, Cout), device=dev)
     b = L.ConvBnBwdArgs(B, T, Cin, Cout, K, L.ptr(x), L.ptr(w), L.ptr(gamma), L.ptr(beta), L.ptr(z), L.ptr(st[0]), L.ptr(st[1]), 1, eps,
                         blocks.ACT_NONE, 0.0, 1, L.SITE["ENC0"], L.ptr(dy), L.ptr(dw), L.ptr(db), L.ptr(dg), L.ptr(dbt), L.ptr(dx), 0,
