@@ -75,8 +75,8 @@ int t2_chain_claimed(void);
  * the product is hi.hi + lo.hi + hi.lo with fp32 accumulation, in one launch
  * (error per product about 3 * sqrt(K) * 2^-17 for unit-scale operands, a dozen times the fp32 kernel's own; whole-model
  * outputs stay within 1e-4 of the reference).  A product that does not qualify runs the exact fp32 kernel of mode 0; the
- * recurrent steps, the attention kernels, BatchNorm and the decode loop are mode 0's, and the persistent chains do not
- * run in this mode.  The staged operands take 6 bytes per element (mode 1: 2), so the scratch is larger:
+ * recurrent steps (unless t2_set_split_steps is on), the attention kernels, BatchNorm and the decode loop are mode 0's,
+ * and the persistent chains do not run in this mode.  The staged operands take 6 bytes per element (mode 1: 2), so the scratch is larger:
  * t2_decoder_layout_query / t2_decoder_bwd_layout_query answer for the mode in force (B=64, T=400: forward +0.6 GB,
  * backward +0.6 GB), and the precision must NOT change between a layout query and the calls that use a workspace of that
  * size.  Callers of t2_conv_bn_* / t2_lstm_seq_* / t2_gemm_ex who want their products on the split path size the
@@ -94,6 +94,26 @@ int t2_gemm_counts(uint64_t* out_host /* [4] */, int reset);
  * break-even).  mflop < 0 restores the default; 0 sends every qualifying product to the split path (kernel tests on
  * small shapes). */
 int t2_set_gemm_split_min_mflop(int mflop);
+/* Split-bf16 recurrent steps, opt-in: 0 (default; env T2_SPLIT_STEPS=1 sets the initial value) leaves everything as
+ * described above.  1, and ONLY while the precision mode is 2: the teacher-forced passes (t2_decoder_forward /
+ * t2_decoder_backward, B <= 128, recurrent widths multiples of 256) run the per-step recurrent products of both
+ * attention LSTMs and of the decoder LSTM, and the recurrent-input gradients of their BPTT, as three bf16 MFMA terms
+ * with fp32 accumulation (hi.hi + lo.hi + hi.lo per 16-wide K step): hi / lo bf16 shadows of the recurrent weights
+ * are cast once per pass, the fp32 activations / gate gradients are split inside the kernels.  Everything else keeps
+ * mode 2's kernels: t2_decoder_infer (the decode loop keeps its bit-exact stop frame), the encoders' t2_lstm_seq_*,
+ * the attention kernels, and the persistent chains (which do not run in mode 2).  In modes 0 and 1 the switch changes
+ * no result and no layout.  With it on in mode 2 the shadow arena of the forward workspace holds a lo plane behind each
+ * of the six shadows (w16a ... wt16d then name the hi planes), so t2_decoder_layout_query / t2_decoder_bwd_layout_query
+ * answer for the pair (precision mode, this switch), and NEITHER may change between a layout query and the calls that
+ * use a workspace of that size.  A pass that does not meet the shape conditions runs the exact kernels. */
+int t2_set_split_steps(int on);
+int t2_get_split_steps(void);
+/* Which kernel family the per-step LSTM launches of the decoder entry points (t2_decoder_forward, t2_decoder_backward,
+ * t2_decoder_infer) took since the last reset: forward steps [0] exact fp32, [1] bf16 operands, [2] split-bf16;
+ * recurrent-input gradient products [3] exact fp32, [4] bf16 operands, [5] split-bf16.  The attention LSTMs of both
+ * streams share one launch.  The persistent chains are not per-step launches and t2_lstm_seq_* is not a decoder entry
+ * point: neither is counted.  Host counters, no synchronisation; reset != 0 clears them after the read. */
+int t2_step_counts(uint64_t* out_host /* [6] */, int reset);
 /* 1 (default): teacher-forced passes run the decoder-LSTM chain on an internal side stream, one chunk of steps
  * apart from the attention chain (fork/join inside the call; the caller's stream semantics are unchanged).  0: one stream. */
 int t2_set_overlap(int on);

@@ -165,7 +165,7 @@ class GemmPlanInfo(C.Structure):
 # every symbol include/t2amd.h declares (tests/test_abi.py checks the library exports them all)
 ABI_VERSION = 4      # include/t2amd.h T2_ABI_VERSION: struct sizes below match that header and nothing else
 
-EXPORTS = ["t2_last_error", "t2_version", "t2_chain_status", "t2_chain_status_clear", "t2_debug_report_abort", "t2_debug_occupy", "t2_chain_claimed", "t2_set_precision", "t2_get_precision", "t2_gemm_counts", "t2_set_gemm_split_min_mflop", "t2_set_overlap", "t2_set_chain", "t2_get_chain", "t2_set_chain_bwd", "t2_set_gemm_staging", "t2_side_join", "t2_decoder_layout_query", "t2_decoder_forward", "t2_decoder_infer",
+EXPORTS = ["t2_last_error", "t2_version", "t2_chain_status", "t2_chain_status_clear", "t2_debug_report_abort", "t2_debug_occupy", "t2_chain_claimed", "t2_set_precision", "t2_get_precision", "t2_gemm_counts", "t2_set_gemm_split_min_mflop", "t2_set_split_steps", "t2_get_split_steps", "t2_step_counts", "t2_set_overlap", "t2_set_chain", "t2_get_chain", "t2_set_chain_bwd", "t2_set_gemm_staging", "t2_side_join", "t2_decoder_layout_query", "t2_decoder_forward", "t2_decoder_infer",
            "t2_decoder_bwd_layout_query", "t2_decoder_backward", "t2_prof_enable", "t2_prof_collect", "t2_adam_chunks", "t2_adam_step", "t2_adam_norm",
            "t2_conv_bn_forward", "t2_conv_bn_backward", "t2_embedding_forward", "t2_embedding_backward",
            "t2_lstm_seq_forward", "t2_lstm_seq_backward", "t2_lstm_seq_chain_ws_floats", "t2_gemm_ex", "t2_prof_gemm", "t2_gemm_plan", "t2_conv_handoff_plan", "t2_colsum", "t2_mask_btc",
@@ -214,6 +214,8 @@ def lib() -> C.CDLL:
         L.t2_mask_btc.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_float, C.c_void_p]
         L.t2_prof_enable.argtypes = [C.c_int]
         L.t2_gemm_counts.argtypes = [C.POINTER(C.c_uint64), C.c_int]
+        L.t2_set_split_steps.argtypes = [C.c_int]
+        L.t2_step_counts.argtypes = [C.POINTER(C.c_uint64), C.c_int]
         L.t2_set_gemm_split_min_mflop.argtypes = [C.c_int]
         L.t2_prof_collect.argtypes = [C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_int)]
         L.t2_finalize_bct.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_float, C.c_void_p]
@@ -437,6 +439,24 @@ def gemm_counts(reset: bool = False):
     GEMM layer since the last reset, by the kernel family they launched."""
     out = (C.c_uint64 * 4)()
     check(lib().t2_gemm_counts(out, int(bool(reset))))
+    return tuple(int(v) for v in out)
+
+
+def set_split_steps(on: bool) -> None:
+    """Split-bf16 recurrent LSTM steps of the teacher-forced passes (include/t2amd.h: t2_set_split_steps).  Acts only in
+    precision mode "bf16x3"; workspaces are sized per (mode, switch): set it before a DecoderPass is created."""
+    check(lib().t2_set_split_steps(int(bool(on))))
+
+
+def get_split_steps() -> bool:
+    return bool(lib().t2_get_split_steps())
+
+
+def step_counts(reset: bool = False):
+    """Per-step LSTM launches of the decoder entry points since the last reset: forward (exact, bf16, split), then
+    recurrent-input gradient (exact, bf16, split)."""
+    out = (C.c_uint64 * 6)()
+    check(lib().t2_step_counts(out, int(bool(reset))))
     return tuple(int(v) for v in out)
 
 

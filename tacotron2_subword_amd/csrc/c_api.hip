@@ -69,6 +69,11 @@ static Side g_side[16];
 static int g_overlap = 1;
 static int g_chain = getenv("T2_CHAIN") ? atoi(getenv("T2_CHAIN")) : 1;   // persistent chain kernels (chain.hip)
 static int g_chain_bwd = getenv("T2_CHAIN_BWD") ? atoi(getenv("T2_CHAIN_BWD")) : 1;   // ... of the backward pass (chain_bwd.hip)
+// per-step LSTM launches of the decoder drivers since the last reset (t2_step_counts): forward step {exact, bf16, split},
+// recurrent-input gradient {exact, bf16, split}, as the launchers report them
+static uint64_t g_step_counts[6] = {0, 0, 0, 0, 0, 0};
+static int counted(int rc, int base, int family) { if (rc == 0) ++g_step_counts[base + family]; return rc; }
+static int g_split_steps = getenv("T2_SPLIT_STEPS") ? atoi(getenv("T2_SPLIT_STEPS")) != 0 : 0;   // split-bf16 recurrent steps (mode 2 only)
 static int side_get(Side** out) {
     int dev = 0;
     T2_CHECK_HIP(hipGetDevice(&dev));
@@ -263,6 +268,12 @@ InferShadows infer_shadows(const Sizes& z, size_t base) {
 // The status words of a pass (ChainStatus, kernels.h): the head of the forward workspace's chain region
 unsigned* status_words(const float* ws, const t2_decoder_layout& L) { return reinterpret_cast<unsigned*>(const_cast<float*>(ws) + L.chain); }
 
+// The layout carries lo planes for the split-bf16 steps: decided by (mode, switch) alone, whatever the batch size
+bool split_steps_layout() { return get_precision() == 2 && g_split_steps != 0; }
+// lo plane of an attention-LSTM shadow (w16a, w16as, wt16a, wt16as) / a decoder-LSTM shadow (w16d, wt16d), in floats
+size_t split_lo_a(const Sizes& z, size_t hi) { return hi + (size_t)4 * z.Ha * (z.Ha + z.E) / 2; }
+size_t split_lo_d(const Sizes& z, size_t hi) { return hi + (size_t)4 * z.Hd * z.Hd / 2; }
+
 void layout_of(const t2_dims& d, const Sizes& z, t2_decoder_layout* L) {
     size_t off = 0;
     auto take = [&](size_t n) { size_t o = off; off += align4(n); return o; };
@@ -285,10 +296,13 @@ void layout_of(const t2_dims& d, const Sizes& z, t2_decoder_layout* L) {
     // bf16 shadow arena: teacher-forced passes keep [W_hh | W_ih[:,P:]] (+ transposes) per attention stream and W_hh of
     // the decoder LSTM; the decode loop keeps whole-cell shadows and ping-pong input rows (InferShadows) in the same space
     const size_t na = (size_t)4 * z.Ha * (z.Ha + z.E) / 2, nd = (size_t)4 * z.Hd * z.Hd / 2;      // bf16 pairs per float
-    const size_t train16 = 4 * na + 2 * nd, infer16 = infer_shadows(z, 0).total_floats;
+    // split-bf16 steps (mode 2 with t2_set_split_steps on): a lo plane of the same size right behind each of the six
+    // shadows; the fields name the hi planes (split_lo_a / split_lo_d give the lo plane)
+    const size_t planes = split_steps_layout() ? 2 : 1;
+    const size_t train16 = planes * (4 * na + 2 * nd), infer16 = infer_shadows(z, 0).total_floats;
     const size_t arena = take(train16 > infer16 ? train16 : infer16);
-    L->w16a = arena; L->w16as = arena + na; L->w16d = arena + 2 * na;
-    L->wt16a = L->w16d + nd; L->wt16as = L->wt16a + na; L->wt16d = L->wt16as + na;
+    L->w16a = arena; L->w16as = L->w16a + planes * na; L->w16d = L->w16as + planes * na;
+    L->wt16a = L->w16d + planes * nd; L->wt16as = L->wt16a + planes * na; L->wt16d = L->wt16as + planes * na;
     L->din16 = take(BT * z.WD / 2 + 4); L->dh16 = take(BT * z.Hd / 2 + 4);
     L->gemm_ws_floats = (size_t)16 << 20;                     // 64 MiB of split-K scratch
     // split-bf16 mode: the hoisted LSTM-input products stage both operands as three bf16 terms (6 bytes per element; the
@@ -315,6 +329,7 @@ struct Dec {
     float* mel_out; float* gate_out; float* align; float* align_sub;
     bool training; bool prenet_dropout; bool teacher; uint64_t seed; hipStream_t s;
     bool use16 = false;                              // bf16-operand recurrent steps (t2_set_precision(1))
+    bool split = false;                              // split-bf16 recurrent steps (use_split_steps; teacher-forced passes only)
     hipStream_t sd = nullptr;                        // stream of the decoder-LSTM chain (== s unless overlapped)
     int max_pos = 0;                                 // > 0: attention restricted to the first max_pos positions (ForwardAttentionV2)
     InferShadows I{};                                // decode loop only (teacher == false && use16)
@@ -356,6 +371,10 @@ int prenet(const Dec& c, bool sub, const float* X, long ldx, int M, float* P1, f
 bool use_bf16_steps(const t2_dims& d, const Sizes& z) {
     return get_precision() == 1 && z.B <= 128 && (z.Ha + z.E) % 256 == 0 && z.Hd % 256 == 0 && (4 * z.Ha) % 2048 == 0 && (4 * z.Hd) % 2048 == 0;
 }
+// split-bf16 recurrent steps: precision mode 2 with t2_set_split_steps on, and the shape conditions of the bf16 steps
+bool use_split_steps(const t2_dims& d, const Sizes& z) {
+    return split_steps_layout() && z.B <= 128 && (z.Ha + z.E) % 256 == 0 && z.Hd % 256 == 0 && (4 * z.Ha) % 2048 == 0 && (4 * z.Hd) % 2048 == 0;
+}
 // weight shadows for one pass: [W_hh | W_ih[:,P:]] (K-contiguous, forward) and its transpose laid out
 // [ctx columns | h columns] x 4H (backward), per attention stream; W_hh and W_hh^T of the decoder LSTM
 int cast_shadows(const t2_dims& d, const t2_decoder_weights& w, const Sizes& z, const t2_decoder_layout& L, float* ws, hipStream_t s) {
@@ -372,6 +391,23 @@ int cast_shadows(const t2_dims& d, const t2_decoder_weights& w, const Sizes& z, 
     }
     T2_TRY(cast_rows_bf16(w.dec.w_hh, z.Hd, P16(L.w16d), z.Hd, 4 * z.Hd, z.Hd, s));
     T2_TRY(cast_transpose_bf16(w.dec.w_hh, z.Hd, P16(L.wt16d), 4 * z.Hd, 4 * z.Hd, z.Hd, s));
+    return 0;
+}
+// the same shadows as hi / lo planes for the split-bf16 steps (the layout then has a lo plane behind each shadow)
+int cast_shadows_split(const t2_dims& d, const t2_decoder_weights& w, const Sizes& z, const t2_decoder_layout& L, float* ws, hipStream_t s) {
+    auto P16 = [&](size_t off) { return reinterpret_cast<__bf16*>(ws + off); };
+    const long K = z.Ha + z.E, ldi = z.P + z.E;
+    for (int st = 0; st < z.NS; ++st) {
+        const t2_lstm_weights& lw = st ? w.att_sub : w.att;
+        const size_t fo = st ? L.w16as : L.w16a, to = st ? L.wt16as : L.wt16a;
+        __bf16 *f = P16(fo), *fl = P16(split_lo_a(z, fo)), *tr = P16(to), *trl = P16(split_lo_a(z, to));
+        T2_TRY(cast_rows_split_bf16(lw.w_hh, z.Ha, f, fl, K, 4 * z.Ha, z.Ha, s));
+        T2_TRY(cast_rows_split_bf16(lw.w_ih + z.P, ldi, f + z.Ha, fl + z.Ha, K, 4 * z.Ha, z.E, s));
+        T2_TRY(cast_transpose_split_bf16(lw.w_ih + z.P, ldi, tr, trl, 4 * z.Ha, 4 * z.Ha, z.E, s));
+        T2_TRY(cast_transpose_split_bf16(lw.w_hh, z.Ha, tr + (long)z.E * 4 * z.Ha, trl + (long)z.E * 4 * z.Ha, 4 * z.Ha, 4 * z.Ha, z.Ha, s));
+    }
+    T2_TRY(cast_rows_split_bf16(w.dec.w_hh, z.Hd, P16(L.w16d), P16(split_lo_d(z, L.w16d)), z.Hd, 4 * z.Hd, z.Hd, s));
+    T2_TRY(cast_transpose_split_bf16(w.dec.w_hh, z.Hd, P16(L.wt16d), P16(split_lo_d(z, L.wt16d)), 4 * z.Hd, 4 * z.Hd, z.Hd, s));
     return 0;
 }
 
@@ -423,10 +459,16 @@ int att_lstm_step(const Dec& c, int t) {
             st.x16 = D16 + (t > 0 ? c.R(t - 1) * z.WD + hoff : 0); st.ldx16 = z.WD;
             st.w16 = c.P16(s ? L.w16as : L.w16a); st.ldw16 = z.Ha + z.E; st.k16 = t > 0 ? z.Ha + z.E : 0;
             st.h16_out = D16 + c.R(t) * z.WD + hoff; st.ldh16 = z.WD;
+        } else if (c.split && c.teacher) {           // the same product on fp32 rows [h | ctx] of DIN and hi / lo shadows
+            const size_t wo = s ? L.w16as : L.w16a;
+            st.nseg = 0;
+            st.xs = DIN + (t > 0 ? c.R(t - 1) * z.WD + hoff : 0); st.ldxs = z.WD;
+            st.w16 = c.P16(wo); st.w16lo = c.P16(split_lo_a(z, wo)); st.ldw16 = z.Ha + z.E; st.k16 = t > 0 ? z.Ha + z.E : 0;
         }
     }
     ProfScope ps(PK_LSTM_ATT_FWD, c.s);
-    return lstm_step_fwd(d, c.s);
+    int family = 0;
+    return counted(lstm_step_fwd(d, c.s, &family), 0, family);
 }
 
 int attention_step(const Dec& c, int t) {
@@ -513,10 +555,15 @@ int dec_lstm_step(const Dec& c, int t) {
         st.x16 = H16 + (t > 0 ? c.R(t - 1) * z.Hd : 0); st.ldx16 = z.Hd;
         st.w16 = c.P16(L.w16d); st.ldw16 = z.Hd; st.k16 = t > 0 ? z.Hd : 0;
         st.h16_out = H16 + c.R(t) * z.Hd; st.ldh16 = z.Hd;
+    } else if (c.split && c.teacher) {               // fp32 dec_h rows of DOUT, hi / lo shadows of W_hh
+        st.nseg = 0;
+        st.xs = c.P(L.dout) + (t > 0 ? c.R(t - 1) * z.WO : 0); st.ldxs = z.WO;
+        st.w16 = c.P16(L.w16d); st.w16lo = c.P16(split_lo_d(z, L.w16d)); st.ldw16 = z.Hd; st.k16 = t > 0 ? z.Hd : 0;
     }
     hipStream_t sd = c.sd ? c.sd : c.s;
     ProfScope ps(PK_LSTM_DEC_FWD, sd);
-    return lstm_step_fwd(d, sd);
+    int family = 0;
+    return counted(lstm_step_fwd(d, sd, &family), 0, family);
 }
 
 // Persistent-kernel descriptors of the two teacher-forced chains (chain.hip).  Returns false when the shape, mode or
@@ -700,6 +747,7 @@ struct Bwd {
     float* S(size_t off) const { return a.bws + off; }
     long R(int t) const { return (long)t * z.B; }
     bool use16 = false;
+    bool split = false;                              // split-bf16 recurrent-input gradients (use_split_steps)
     hipStream_t sd = nullptr;                        // stream of the decoder-LSTM chain (== s unless overlapped)
     const __bf16* W16(size_t off) const { return reinterpret_cast<const __bf16*>(a.ws + off); }
     __bf16* S16(size_t off) const { return reinterpret_cast<__bf16*>(a.bws + off); }
@@ -751,8 +799,10 @@ int dec_bwd_step(const Bwd& c, int t) {
     g.st[0].seg[0] = LstmBwdSeg{c.w.dec.w_hh, (long)z.Hd, z.Hd}; g.st[0].nseg = 1;
     g.st[0].part = c.S(c.BL.partd);
     if (c.use16) { g.st[0].dg16 = c.S16(c.BL.dg16d); g.st[0].wt16 = c.W16(c.L.wt16d); }
+    else if (c.split) { g.st[0].wt16 = c.W16(c.L.wt16d); g.st[0].wt16lo = c.W16(split_lo_d(z, c.L.wt16d)); }
     ProfScope ps(PK_LSTM_DEC_BWD_GEMM, sd);
-    return lstm_bwd_gemm(g, sd);
+    int family = 0;
+    return counted(lstm_bwd_gemm(g, sd, &family), 3, family);
 }
 
 // Persistent BPTT of the decoder LSTM (chain_bwd.hip); false = not covered, per-step launches instead
@@ -924,9 +974,11 @@ int att_bwd_step(const Bwd& c, int t) {
         g.st[s].nseg = 2;
         g.st[s].part = c.S(c.BL.parta) + (size_t)s * ks * z.B * NC;
         if (c.use16) { g.st[s].dg16 = c.S16(c.BL.dg16a) + (size_t)s * z.B * 4 * z.Ha; g.st[s].wt16 = c.W16(s ? c.L.wt16as : c.L.wt16a); }
+        else if (c.split) { const size_t to = s ? c.L.wt16as : c.L.wt16a; g.st[s].wt16 = c.W16(to); g.st[s].wt16lo = c.W16(split_lo_a(z, to)); }
     }
     ProfScope ps(PK_LSTM_ATT_BWD_GEMM, c.s);
-    return lstm_bwd_gemm(g, c.s);
+    int family = 0;
+    return counted(lstm_bwd_gemm(g, c.s, &family), 3, family);
 }
 
 }  // namespace
@@ -999,6 +1051,13 @@ int t2_gemm_counts(uint64_t* out_host, int reset) {
     gemm_counts(out_host, reset);
     return 0;
 }
+int t2_set_split_steps(int on) { g_split_steps = on != 0; return 0; }
+int t2_get_split_steps(void) { return g_split_steps; }
+int t2_step_counts(uint64_t* out_host, int reset) {
+    T2_REQUIRE(out_host, "null argument");
+    for (int i = 0; i < 6; ++i) { out_host[i] = g_step_counts[i]; if (reset) g_step_counts[i] = 0; }
+    return 0;
+}
 int t2_set_overlap(int on) { g_overlap = on != 0; return 0; }
 int t2_set_chain(int on) { g_chain = on != 0; return 0; }
 int t2_get_chain(void) { return g_chain; }
@@ -1046,6 +1105,7 @@ int t2_decoder_forward(const t2_dims* dims_in, const t2_decoder_weights* w, cons
 
     T2_REQUIRE(a->phase >= 0 && a->phase <= 2, "t2_decoder_forward: phase must be 0, 1 or 2");
     c.use16 = use_bf16_steps(*dims, z);
+    c.split = use_split_steps(*dims, z);
     // bf16 steps keep a bf16 shadow of every DIN row (din16): with one bf16 copy of W_ih at the head of the scratch the
     // decoder-LSTM input GEMMs below read both operands as bf16 and stage nothing
     const size_t w16_bytes = ((size_t)4 * z.Hd * z.WD * sizeof(__bf16) + 255) & ~(size_t)255;
@@ -1053,6 +1113,7 @@ int t2_decoder_forward(const t2_dims* dims_in, const t2_decoder_weights* w, cons
     __bf16* w16 = reinterpret_cast<__bf16*>(c.P(L.gemm_ws));
     if (a->phase != 2) {                                                // ---- everything that does not read the memories
         if (c.use16) T2_TRY(cast_shadows(*dims, *w, z, L, a->ws, c.s));
+        if (c.split) T2_TRY(cast_shadows_split(*dims, *w, z, L, a->ws, c.s));
         // teacher inputs and both prenets over all frames (model.py:407-413)
         T2_TRY(teacher_inputs(a->mels, c.P(L.x), z.B, z.M, z.T, c.s));
         T2_TRY(prenet(c, false, c.P(L.x), z.M, BT, c.P(L.p1), c.P(L.p2), z.P, 0, 0));      // rows time-major: (t,b)
@@ -1154,6 +1215,7 @@ int t2_decoder_backward(const t2_dims* dims_in, const t2_decoder_weights* w, con
     layout_of(*dims, c.z, &c.L);
     bwd_layout_of(*dims, c.z, &c.BL);
     c.use16 = use_bf16_steps(*dims, c.z);          // must match the forward pass (the shadows live in its workspace)
+    c.split = use_split_steps(*dims, c.z);         // likewise
     const Sizes& z = c.z; const t2_decoder_layout& L = c.L; const t2_decoder_bwd_layout& BL = c.BL;
     const int BT = z.B * z.T;
     float* cws = c.S(BL.colsum_ws);

@@ -120,10 +120,15 @@ struct LstmStream {
     const __bf16* x16; long ldx16; const __bf16* w16; long ldw16; int k16;
     __bf16* h16_out; long ldh16;
     __bf16* h16_out2; long ldh16_2;       // second bf16 destination (decode loop: the decoder LSTM's input row)
+    // split-bf16 step (w16lo given; nseg = 0): fp32 activation rows xs [B,k16], split into hi / lo inside the kernel, and
+    // the lo plane of the weight shadow behind w16 (= the hi plane), same ldw16
+    const float* xs; long ldxs; const __bf16* w16lo;
 };
 constexpr int kMaxLstmStreams = 4;
 struct LstmStepDesc { LstmStream st[kMaxLstmStreams]; int nstreams; int B, H; float drop_p; uint64_t seed; };
-int lstm_step_fwd(const LstmStepDesc& d, hipStream_t s);
+// family (nullable): which kernel family the launch took, for t2_step_counts
+enum LstmFamily : int { LSTM_EXACT = 0, LSTM_BF16 = 1, LSTM_SPLIT = 2 };
+int lstm_step_fwd(const LstmStepDesc& d, hipStream_t s, int* family = nullptr);
 
 // Backward of one LSTM step, part 1 (pointwise): total dL/dh_out(t), dL/dc_out(t) -> dL/d(gate pre-activations).
 struct LstmBwdStream {
@@ -150,13 +155,17 @@ struct LstmBwdSeg { const float* w; long ldw; int ncols; };
 struct LstmBwdGemmStream {
     const float* dg; long lddg; LstmBwdSeg seg[3]; int nseg; float* part;
     const __bf16* dg16; const __bf16* wt16;   // bf16 variant: dense [B,4H] gradient copy, transposed weight shadow [NC,4H]
+    const __bf16* wt16lo;                     // split-bf16 variant (given: dg is read as fp32 and split in the kernel): lo plane of wt16
 };
 struct LstmBwdGemmDesc { LstmBwdGemmStream st[kMaxLstmStreams]; int nstreams; int B, H4, KS, NC; };
-int lstm_bwd_gemm(const LstmBwdGemmDesc& d, hipStream_t s);
+int lstm_bwd_gemm(const LstmBwdGemmDesc& d, hipStream_t s, int* family = nullptr);
 int lstm_bwd_ksplit(int H4);
 // bf16 shadows: dst[r*ld_dst + c] = bf16(src[r*ld_src + c]) ; transposed: dst[c*ld_dst + r]
 int cast_rows_bf16(const float* src, long ld_src, __bf16* dst, long ld_dst, int R, int C, hipStream_t s);
 int cast_transpose_bf16(const float* src, long ld_src, __bf16* dst, long ld_dst, int R, int C, hipStream_t s);
+// the same in one pass for the split-bf16 steps: hi = bf16(x), lo = bf16(x - hi), both planes indexed as dst above
+int cast_rows_split_bf16(const float* src, long ld_src, __bf16* hi, __bf16* lo, long ld_dst, int R, int C, hipStream_t s);
+int cast_transpose_split_bf16(const float* src, long ld_src, __bf16* hi, __bf16* lo, long ld_dst, int R, int C, hipStream_t s);
 
 // ------------------------------------------------------------------ attention (attention.hip)
 // DynamicConvolutionAttention (attention.py:195-289): 8 static + 8 dynamic channels, 21 taps, 11-tap prior

@@ -442,6 +442,124 @@ __global__ __launch_bounds__(NTH) void lstm_step_fwd_bf16_kernel(LstmStepDesc d)
 }
 
 // ---------------------------------------------------------------------------------------------
+// split-bf16 step (t2_set_precision(2) with t2_set_split_steps(1), teacher-forced passes): the recurrent product at
+// fp32-grade accuracy on the bf16 matrix pipe.  Weights come from hi / lo bf16 shadows (hi = bf16(w), lo = bf16(w - hi),
+// cast once per pass: the same 4 bytes per element as fp32), activations are read as fp32 rows and split in registers
+// on their way into LDS.  Per 16-wide K step and row tile: acc += a_hi.b_hi, += a_lo.b_hi, += a_hi.b_lo, in that order
+// (lo.lo is below fp32 rounding).  Same work split, K order across waves and tail as the bf16 step.
+// ---------------------------------------------------------------------------------------------
+typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
+
+template <int MT, int BKT> struct TileS {
+    static constexpr int P = BKT + 8;                          // bf16 pitch of every plane, as in Tile16
+    static constexpr int A_ELEMS = MT * 32 * P, B_ELEMS = 32 * P;           // ONE plane; hi and lo planes are adjacent
+    static constexpr int QA = MT * 32 * (BKT / 4) / NTH;       // float4 per thread, fp32 A rows
+    static constexpr int QB = 32 * (BKT / 8) / NTH;            // bf16x8 per thread and plane, B rows
+    static constexpr int STAGE_FLOATS = A_ELEMS + B_ELEMS;     // two planes each, two bf16 per float
+    static constexpr int PART_FLOATS = (MT >= 2 ? 2 : 1) * NW * 32 * PP;
+    static constexpr int SMEM_FLOATS = (STAGE_FLOATS > PART_FLOATS ? STAGE_FLOATS : PART_FLOATS);
+    static_assert(QA >= 1 && QB >= 1 && BKT % (NW * 16) == 0, "stage too narrow for 8 waves");
+    static_assert((size_t)(SMEM_FLOATS + MT * 32 * HU) * 4 <= 160 * 1024, "stage does not fit the 160 KB of LDS");
+};
+// stage widths by row-tile count: the widest that keeps A and B (two planes each) within LDS
+template <int MT> struct SplitBkt { static constexpr int fwd = MT == 1 ? 512 : MT == 2 ? 256 : 128, bwd = MT <= 2 ? 256 : 128; };
+
+// fp32 rows -> hi / lo planes: row-major [rows][P] each, the lo plane `plane` elements behind the hi plane
+template <int BKT, int Q>
+__device__ __forceinline__ void store_rows_split(__bf16* __restrict__ lds, int plane, const f32x4 (&regs)[Q]) {
+    constexpr int P = BKT + 8;
+#pragma unroll
+    for (int i = 0; i < Q; ++i) {
+        const int q = threadIdx.x + i * NTH, row = q / (BKT / 4), k = (q % (BKT / 4)) * 4;
+        bf16x4 hi, lo;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            hi[j] = (__bf16)regs[i][j];
+            lo[j] = (__bf16)(regs[i][j] - (float)hi[j]);
+        }
+        *reinterpret_cast<bf16x4*>(lds + row * P + k) = hi;
+        *reinterpret_cast<bf16x4*>(lds + plane + row * P + k) = lo;
+    }
+}
+template <int MT, int BKT>
+__device__ __forceinline__ void compute_stage_split(const __bf16* __restrict__ As, const __bf16* __restrict__ Bs, int wave, int r, int hk,
+                                                    f32x16 (&acc)[MT]) {
+    using TL = TileS<MT, BKT>;
+    constexpr int P = TL::P;
+#pragma unroll
+    for (int kk = 0; kk < BKT / NW; kk += 16) {
+        const int k = wave * (BKT / NW) + kk + 8 * hk;
+        const bf16x8 bh = *reinterpret_cast<const bf16x8*>(Bs + r * P + k);
+        const bf16x8 bl = *reinterpret_cast<const bf16x8*>(Bs + TL::B_ELEMS + r * P + k);
+#pragma unroll
+        for (int m = 0; m < MT; ++m) {
+            const bf16x8 ah = *reinterpret_cast<const bf16x8*>(As + (m * 32 + r) * P + k);
+            const bf16x8 al = *reinterpret_cast<const bf16x8*>(As + TL::A_ELEMS + (m * 32 + r) * P + k);
+            acc[m] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bh, acc[m], 0, 0, 0);
+            acc[m] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, bh, acc[m], 0, 0, 0);
+            acc[m] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bl, acc[m], 0, 0, 0);
+        }
+    }
+}
+
+template <int MT, int BKT>
+__global__ __launch_bounds__(NTH) void lstm_step_fwd_split_kernel(LstmStepDesc d) {
+    using TL = TileS<MT, BKT>;
+    const LstmStream& st = d.st[blockIdx.y];
+    const int B = d.B, H = d.H;
+    const int u0 = blockIdx.x * HU;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int r = lane & 31, hk = lane >> 5;
+
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    __bf16* As = reinterpret_cast<__bf16*>(smem);              // [hi | lo][MT*32][P]
+    __bf16* Bs = As + 2 * TL::A_ELEMS;                         // [hi | lo][32][P]
+    float* part = smem;
+    float* hs = smem + TL::SMEM_FLOATS;
+
+    f32x16 acc[MT];
+#pragma unroll
+    for (int m = 0; m < MT; ++m)
+#pragma unroll
+        for (int e = 0; e < 16; ++e) acc[m][e] = 0.f;
+
+    // two register stage buffers, as in the bf16 step; t = 0 has k16 = 0 and goes straight to the tail
+    const int nstages = st.k16 / BKT;
+    f32x4 ra0[TL::QA], ra1[TL::QA];
+    bf16x8 rh0[TL::QB], rl0[TL::QB], rh1[TL::QB], rl1[TL::QB];
+    auto load_stage = [&](int c, f32x4 (&ra)[TL::QA], bf16x8 (&rh)[TL::QB], bf16x8 (&rl)[TL::QB]) {
+        load_rows<MT * 32, BKT, TL::QA>([&](int row, bool& ok) { ok = row < B; return st.xs + (long)(ok ? row : 0) * st.ldxs; }, c * BKT, ra);
+        load_rows16<BKT, TL::QB>([&](int n, bool& ok) { ok = true; return st.w16 + (long)((n >> 3) * H + u0 + (n & 7)) * st.ldw16; }, c * BKT, rh);
+        load_rows16<BKT, TL::QB>([&](int n, bool& ok) { ok = true; return st.w16lo + (long)((n >> 3) * H + u0 + (n & 7)) * st.ldw16; }, c * BKT, rl);
+    };
+    auto store_stage = [&](const f32x4 (&ra)[TL::QA], const bf16x8 (&rh)[TL::QB], const bf16x8 (&rl)[TL::QB]) {
+        store_rows_split<BKT, TL::QA>(As, TL::A_ELEMS, ra);
+        store_rows16<BKT, TL::QB>(Bs, rh);
+        store_rows16<BKT, TL::QB>(Bs + TL::B_ELEMS, rl);
+    };
+    if (nstages > 0) load_stage(0, ra0, rh0, rl0);
+    if (nstages > 1) load_stage(1, ra1, rh1, rl1);
+    TailRegs<MT> tr;
+    tail_prefetch<MT>(d, st, u0, tr);
+    if (nstages > 0) store_stage(ra0, rh0, rl0);
+    __syncthreads();
+    for (int c = 0; c < nstages; c += 2) {
+        if (c + 2 < nstages) load_stage(c + 2, ra0, rh0, rl0);
+        compute_stage_split<MT, BKT>(As, Bs, wave, r, hk, acc);
+        __syncthreads();
+        if (c + 1 < nstages) {
+            store_stage(ra1, rh1, rl1);
+            __syncthreads();
+            if (c + 3 < nstages) load_stage(c + 3, ra1, rh1, rl1);
+            compute_stage_split<MT, BKT>(As, Bs, wave, r, hk, acc);
+            __syncthreads();
+            if (c + 2 < nstages) { store_stage(ra0, rh0, rl0); __syncthreads(); }
+        }
+    }
+    lstm_tail<MT>(d, st, u0, wave, r, hk, acc, part, hs, tr);
+}
+
+// ---------------------------------------------------------------------------------------------
 // backward, part 1: pointwise.  One thread per (b, u).
 //   dh  = direct sources + sum of recurrent partials (+ dq . Wq)          gradient on h_out(t)
 //   dhn = dh * keep_h/(1-p) ;  dcn = dc_out * keep_c/(1-p) + dhn * o * (1 - tanh(cn)^2)
@@ -692,6 +810,103 @@ __global__ __launch_bounds__(NTH) void lstm_bwd_gemm_bf16_kernel(LstmBwdGemmDesc
     }
 }
 
+// split-bf16 variant of the recurrent-input gradient: A = the fp32 dg(t) rows, split into hi / lo on their way into LDS,
+// B = hi / lo transposed weight shadows wt16[n][k]; three MFMA terms per K step as in the forward split step.  Same
+// K-split grid and part[z][b][n] partials as the other two variants.
+template <int MT>
+__global__ __launch_bounds__(NTH) void lstm_bwd_gemm_split_kernel(LstmBwdGemmDesc d) {
+    constexpr int BKT = SplitBkt<MT>::bwd;
+    using TL = TileS<MT, BKT>;
+    const LstmBwdGemmStream& st = d.st[blockIdx.z];
+    const int B = d.B;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int r = lane & 31, hk = lane >> 5;
+    const int col0 = blockIdx.x * 32;
+    const int kspan = d.H4 / d.KS, kbeg = blockIdx.y * kspan, nstages = kspan / BKT;
+
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    __bf16* As = reinterpret_cast<__bf16*>(smem);
+    __bf16* Bs = As + 2 * TL::A_ELEMS;
+    float* part = smem;
+
+    f32x16 acc[MT];
+#pragma unroll
+    for (int m = 0; m < MT; ++m)
+#pragma unroll
+        for (int e = 0; e < 16; ++e) acc[m][e] = 0.f;
+    f32x4 ra[TL::QA];
+    bf16x8 rh[TL::QB], rl[TL::QB];
+    auto load_stage = [&](int c) {
+        load_rows<MT * 32, BKT, TL::QA>([&](int row, bool& ok) { ok = row < B; return st.dg + (long)(ok ? row : 0) * st.lddg + kbeg; }, c * BKT, ra);
+        load_rows16<BKT, TL::QB>([&](int n, bool& ok) { ok = true; return st.wt16 + (long)(col0 + n) * d.H4 + kbeg; }, c * BKT, rh);
+        load_rows16<BKT, TL::QB>([&](int n, bool& ok) { ok = true; return st.wt16lo + (long)(col0 + n) * d.H4 + kbeg; }, c * BKT, rl);
+    };
+    auto store_stage = [&]() {
+        store_rows_split<BKT, TL::QA>(As, TL::A_ELEMS, ra);
+        store_rows16<BKT, TL::QB>(Bs, rh);
+        store_rows16<BKT, TL::QB>(Bs + TL::B_ELEMS, rl);
+    };
+    load_stage(0);
+    store_stage();
+    __syncthreads();
+    for (int c = 0; c < nstages; ++c) {
+        const bool more = c + 1 < nstages;
+        if (more) load_stage(c + 1);
+        compute_stage_split<MT, BKT>(As, Bs, wave, r, hk, acc);
+        __syncthreads();
+        if (more) { store_stage(); __syncthreads(); }
+    }
+    float* out = st.part + (long)blockIdx.y * B * d.NC;
+#pragma unroll
+    for (int m = 0; m < MT; ++m) {
+        if (m > 0) __syncthreads();
+#pragma unroll
+        for (int e = 0; e < 16; ++e)
+            part[(wave * 32 + (e & 3) + 8 * (e >> 2) + 4 * hk) * PP + r] = acc[m][e];
+        __syncthreads();
+        for (int i = threadIdx.x; i < 32 * 32; i += NTH) {
+            const int bl = i >> 5, c = i & 31, b = m * 32 + bl;
+            if (b < B) {
+                float sum = 0.f;
+#pragma unroll
+                for (int w = 0; w < NW; ++w) sum += part[(w * 32 + bl) * PP + c];
+                out[(long)b * d.NC + col0 + c] = sum;
+            }
+        }
+    }
+}
+
+// split casts, one pass for both planes: hi[..] = bf16(x), lo[..] = bf16(x - hi), indexed as in the two kernels below
+__global__ void cast_rows_split_kernel(const float* __restrict__ src, long lds_, __bf16* __restrict__ hi, __bf16* __restrict__ lo, long ldd, int R, int C) {
+    const size_t n = (size_t)R * C;
+    for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+        const int c = (int)(i % C); const size_t rr = i / C;
+        const float x = src[rr * lds_ + c];
+        const __bf16 h = (__bf16)x;
+        hi[rr * ldd + c] = h;
+        lo[rr * ldd + c] = (__bf16)(x - (float)h);
+    }
+}
+__global__ void cast_transpose_split_kernel(const float* __restrict__ src, long lds_, __bf16* __restrict__ hi, __bf16* __restrict__ lo, long ldd, int R, int C) {
+    __shared__ float tile[32][33];
+    const int r0 = blockIdx.y * 32, c0 = blockIdx.x * 32;
+    const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
+    for (int i = ty; i < 32; i += 8) {
+        const int rr = r0 + i, c = c0 + tx;
+        tile[i][tx] = (rr < R && c < C) ? src[(size_t)rr * lds_ + c] : 0.f;
+    }
+    __syncthreads();
+    for (int i = ty; i < 32; i += 8) {
+        const int c = c0 + i, rr = r0 + tx;
+        if (c < C && rr < R) {
+            const float x = tile[tx][i];
+            const __bf16 h = (__bf16)x;
+            hi[(size_t)c * ldd + rr] = h;
+            lo[(size_t)c * ldd + rr] = (__bf16)(x - (float)h);
+        }
+    }
+}
+
 // dst[r*ldd + c] = bf16(src[r*lds + c])
 __global__ void cast_rows_kernel(const float* __restrict__ src, long lds_, __bf16* __restrict__ dst, long ldd, int R, int C) {
     const size_t n = (size_t)R * C;
@@ -719,6 +934,9 @@ __global__ void cast_transpose_kernel(const float* __restrict__ src, long lds_, 
 template <int MT, int BKT> size_t fwd_smem() { return (size_t)(Tile<MT, BKT>::FWD_FLOATS + MT * 32 * HU) * sizeof(float); }
 template <int MT, int BKT> size_t bwd_smem() { return (size_t)Tile<MT, BKT>::BWD_FLOATS * sizeof(float); }
 
+// split-bf16 kernels: the stage (or the partial tiles), + the forward step's post-dropout h rows
+template <int MT, int BKT> size_t split_smem(bool fwd) { return (size_t)(TileS<MT, BKT>::SMEM_FLOATS + (fwd ? MT * 32 * HU : 0)) * sizeof(float); }
+
 template <typename K>
 int allow_big_lds(K kernel, size_t smem) { return t2_allow_dynamic_lds(reinterpret_cast<const void*>(kernel), smem); }
 
@@ -740,7 +958,7 @@ int allow_big_lds(K kernel, size_t smem) { return t2_allow_dynamic_lds(reinterpr
 
 }  // namespace
 
-int lstm_step_fwd(const LstmStepDesc& d, hipStream_t s) {
+int lstm_step_fwd(const LstmStepDesc& d, hipStream_t s, int* family) {
     T2_REQUIRE(d.nstreams >= 1 && d.nstreams <= kMaxLstmStreams, "lstm_step: nstreams=%d", d.nstreams);
     T2_REQUIRE(d.B >= 1 && d.B <= 256, "lstm_step: batch %d not in [1,256]", d.B);
     T2_REQUIRE(d.H % HU == 0, "lstm_step: H=%d must be a multiple of %d", d.H, HU);
@@ -757,6 +975,32 @@ int lstm_step_fwd(const LstmStepDesc& d, hipStream_t s) {
     }
     const int MT = (d.B + 31) / 32;
     dim3 grid(d.H / HU, d.nstreams), block(NTH);
+    if (d.st[0].w16lo) {                                 // split-bf16 step: fp32 activation rows, hi / lo weight shadows
+        for (int i = 0; i < d.nstreams; ++i) {
+            const LstmStream& st = d.st[i];
+            T2_REQUIRE(st.xs && st.w16 && st.w16lo && st.nseg == 0 && st.k16 % 256 == 0 && st.ldxs % 4 == 0 && st.ldw16 % 8 == 0 &&
+                       ((uintptr_t)st.xs & 15) == 0 && ((uintptr_t)st.w16 & 15) == 0 && ((uintptr_t)st.w16lo & 15) == 0,
+                       "lstm_step: bad split-bf16 operands");
+        }
+        T2_REQUIRE(MT <= 4, "lstm_step: the split-bf16 step supports B <= 128");
+        const bool wide = d.st[0].k16 % 512 == 0 && (d.nstreams < 2 || d.st[1].k16 % 512 == 0);
+        auto go = [&](auto kernel, size_t smem) -> int {
+            T2_TRY_RC(allow_big_lds(kernel, smem));
+            hipLaunchKernelGGL(kernel, grid, block, smem, s, d);
+            return 0;
+        };
+        if (MT <= 1) {
+            if (wide) T2_TRY_RC(go(lstm_step_fwd_split_kernel<1, 512>, split_smem<1, 512>(true)));
+            else T2_TRY_RC(go(lstm_step_fwd_split_kernel<1, 256>, split_smem<1, 256>(true)));
+        } else if (MT <= 2) {
+            T2_TRY_RC(go(lstm_step_fwd_split_kernel<2, SplitBkt<2>::fwd>, split_smem<2, SplitBkt<2>::fwd>(true)));
+        } else {                                         // 65..128 rows: 128-wide stages keep both planes of A within LDS
+            T2_TRY_RC(go(lstm_step_fwd_split_kernel<4, SplitBkt<4>::fwd>, split_smem<4, SplitBkt<4>::fwd>(true)));
+        }
+        T2_LAUNCH_CHECK();
+        if (family) *family = LSTM_SPLIT;
+        return 0;
+    }
     bool bf = d.st[0].x16 != nullptr;
     if (bf) {
         for (int i = 0; i < d.nstreams; ++i)
@@ -779,6 +1023,7 @@ int lstm_step_fwd(const LstmStepDesc& d, hipStream_t s) {
             T2_TRY_RC(go(lstm_step_fwd_bf16_kernel<4, 256>, (size_t)(Tile16<4, 256>::SMEM_FLOATS + 128 * HU) * 4));
         }
         T2_LAUNCH_CHECK();
+        if (family) *family = LSTM_BF16;
         return 0;
     }
     int kdiv = 0;                                    // gcd-like: every segment width must be a multiple of the stage width
@@ -787,6 +1032,7 @@ int lstm_step_fwd(const LstmStepDesc& d, hipStream_t s) {
     if (kdiv == 0) kdiv = 256;
     LAUNCH_MT(lstm_step_fwd_kernel, fwd_smem, kdiv, grid, block, s, d);
     T2_LAUNCH_CHECK();
+    if (family) *family = LSTM_EXACT;
     return 0;
 }
 
@@ -818,7 +1064,7 @@ int lstm_bwd_ksplit(int H4) {
     return ks;
 }
 
-int lstm_bwd_gemm(const LstmBwdGemmDesc& d, hipStream_t s) {
+int lstm_bwd_gemm(const LstmBwdGemmDesc& d, hipStream_t s, int* family) {
     T2_REQUIRE(d.nstreams >= 1 && d.nstreams <= kMaxLstmStreams, "lstm_bwd_gemm: nstreams=%d", d.nstreams);
     T2_REQUIRE(d.B >= 1 && d.B <= 256, "lstm_bwd_gemm: batch %d", d.B);
     T2_REQUIRE(d.KS >= 1 && d.H4 % (d.KS * 64) == 0, "lstm_bwd_gemm: 4H=%d not divisible by KS*64 (KS=%d)", d.H4, d.KS);
@@ -831,6 +1077,23 @@ int lstm_bwd_gemm(const LstmBwdGemmDesc& d, hipStream_t s) {
     }
     const int MT = (d.B + 31) / 32;
     dim3 grid(d.NC / 32, d.KS, d.nstreams), block(NTH);
+    if (d.st[0].wt16lo) {                                // split-bf16 variant: fp32 dg rows, hi / lo transposed shadows
+        T2_REQUIRE(MT <= 4 && (d.H4 / d.KS) % 256 == 0, "lstm_bwd_gemm: split-bf16 variant needs B <= 128 and K-split spans of 256");
+        for (int i = 0; i < d.nstreams; ++i)
+            T2_REQUIRE(d.st[i].wt16 && d.st[i].wt16lo && ((uintptr_t)d.st[i].wt16 & 15) == 0 && ((uintptr_t)d.st[i].wt16lo & 15) == 0,
+                       "lstm_bwd_gemm: bad split-bf16 operands");
+        auto go = [&](auto kernel, size_t smem) -> int {
+            T2_TRY_RC(allow_big_lds(kernel, smem));
+            hipLaunchKernelGGL(kernel, grid, block, smem, s, d);
+            return 0;
+        };
+        if (MT <= 1) T2_TRY_RC(go(lstm_bwd_gemm_split_kernel<1>, split_smem<1, SplitBkt<1>::bwd>(false)));
+        else if (MT <= 2) T2_TRY_RC(go(lstm_bwd_gemm_split_kernel<2>, split_smem<2, SplitBkt<2>::bwd>(false)));
+        else T2_TRY_RC(go(lstm_bwd_gemm_split_kernel<4>, split_smem<4, SplitBkt<4>::bwd>(false)));
+        T2_LAUNCH_CHECK();
+        if (family) *family = LSTM_SPLIT;
+        return 0;
+    }
     if (d.st[0].dg16) {
         T2_REQUIRE(MT <= 4 && (d.H4 / d.KS) % 256 == 0, "lstm_bwd_gemm: bf16 variant needs B <= 128 and K-split spans of 256");
         if (MT <= 1) {
@@ -847,18 +1110,34 @@ int lstm_bwd_gemm(const LstmBwdGemmDesc& d, hipStream_t s) {
             hipLaunchKernelGGL(lstm_bwd_gemm_bf16_kernel<4>, grid, block, smem, s, d);
         }
         T2_LAUNCH_CHECK();
+        if (family) *family = LSTM_BF16;
         return 0;
     }
     LAUNCH_MT(lstm_bwd_gemm_kernel, bwd_smem, d.H4 / d.KS, grid, block, s, d);
     T2_LAUNCH_CHECK();
+    if (family) *family = LSTM_EXACT;
     return 0;
 }
+
 
 int cast_rows_bf16(const float* src, long ld_src, __bf16* dst, long ld_dst, int R, int C, hipStream_t s) {
     const size_t n = (size_t)R * C;
     size_t g = (n + 255) / 256;
     if (g > 4096) g = 4096;
     hipLaunchKernelGGL(cast_rows_kernel, dim3((unsigned)g), dim3(256), 0, s, src, ld_src, dst, ld_dst, R, C);
+    T2_LAUNCH_CHECK();
+    return 0;
+}
+int cast_rows_split_bf16(const float* src, long ld_src, __bf16* hi, __bf16* lo, long ld_dst, int R, int C, hipStream_t s) {
+    const size_t n = (size_t)R * C;
+    size_t g = (n + 255) / 256;
+    if (g > 4096) g = 4096;
+    hipLaunchKernelGGL(cast_rows_split_kernel, dim3((unsigned)g), dim3(256), 0, s, src, ld_src, hi, lo, ld_dst, R, C);
+    T2_LAUNCH_CHECK();
+    return 0;
+}
+int cast_transpose_split_bf16(const float* src, long ld_src, __bf16* hi, __bf16* lo, long ld_dst, int R, int C, hipStream_t s) {
+    hipLaunchKernelGGL(cast_transpose_split_kernel, dim3((C + 31) / 32, (R + 31) / 32), dim3(256), 0, s, src, ld_src, hi, lo, ld_dst, R, C);
     T2_LAUNCH_CHECK();
     return 0;
 }

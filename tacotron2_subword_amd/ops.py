@@ -89,7 +89,8 @@ class DecoderPass:
 
     def __init__(self, dims, B, T, Tin, Tsub, device):
         self.dims, self.B, self.T, self.Tin, self.Tsub = dims, B, T, Tin, Tsub
-        self.precision = L.get_precision()                 # the layout (scratch sizes) belongs to this mode
+        self.precision = L.get_precision()                 # the layout (scratch sizes) belongs to this mode ...
+        self.split_steps = L.get_split_steps()             # ... and to this state of the split-steps switch
         self.layout = L.decoder_layout(dims, B, T, Tin, Tsub)
         self.ws = torch.empty(self.layout.total_floats, dtype=torch.float32, device=device)
         self.mel = torch.empty(B, T, dims.n_mel, dtype=torch.float32, device=device)
@@ -99,11 +100,15 @@ class DecoderPass:
 
     def check_precision(self, who: str) -> None:
         """The library recomputes the layout from the mode in force and the C ABI carries no workspace size: a pass sized in
-        one mode must not be used in another."""
+        one mode, or under one state of the split-steps switch, must not be used in another."""
         now = L.get_precision()
         if now != self.precision:
             raise RuntimeError(f"t2amd: {who}: this pass was allocated in precision mode {self.precision!r}, the library is in "
                                f"{now!r} now; workspaces are sized per mode (set_precision before the pass is created)")
+        if L.get_split_steps() != self.split_steps:
+            raise RuntimeError(f"t2amd: {who}: this pass was allocated with split steps {'on' if self.split_steps else 'off'}, the "
+                               f"switch is {'off' if self.split_steps else 'on'} now; workspaces are sized per (mode, switch) "
+                               f"(set_split_steps before the pass is created)")
 
     def chain_status(self):
         """Status words of the persistent kernels — (forward attention chain, forward decoder-LSTM chain, backward
