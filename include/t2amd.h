@@ -445,6 +445,75 @@ int t2_conv_handoff_plan(const t2_gemm_args* a, const t2_gemm_plan_opts* opts, i
 int t2_colsum(const float* x, long ld, int M, int N, float* out, float* scratch, void* stream);
 int t2_mask_btc(float* x, int B, int T, int C, const int32_t* lengths, float fill, void* stream);
 
+/* ---- Soft-DTW (checkpoint scoring) ---------------------------------------------------------------
+ * Replaces the reference's soft_dtw_cuda.py: compute_softdtw_cuda (:34-75) / compute_softdtw_backward_cuda (:78-111),
+ * the host loops it uses above 1024 frames (:185-239), and SoftDTW._euclidean_dist_func (:320-329) with its autograd
+ * graph.  Indices are 1-based over a padded (N+2) x (M+2) grid, R[0,0] = 0, every other border cell +infinity;
+ * R[i,j] = D[i-1,j-1] + softmin_gamma(R[i-1,j-1], R[i-1,j], R[i,j-1]); cells with 0 < bandwidth < |i - j| are skipped.
+ * One workgroup per pair walks a skewed wavefront; a cell is a fixed function of its neighbours, so results are
+ * bit-identical whatever the batch, the padding and the partition.  N, M <= 8192 each, any d >= 1, gamma > 0; larger
+ * sizes are refused (there is no host detour).
+ * Per-pair lengths (an extension, the reference has none): x_lengths[b] = n_b <= N, y_lengths[b] = m_b <= M (both or
+ * neither; NULL = N, M).  Pair b is the problem x[b,:n_b], y[b,:m_b]: its value is R[n_b,m_b], E and the gradients are
+ * zero in the padding.  A length below 1 gives value +infinity and zero gradients.
+ * An unreachable end cell (0 < bandwidth < |n_b - m_b|) gives value +infinity and an all-zero E.
+ *
+ * t2_softdtw_plan is pure (no device): the partition of a pair and the scratch the calls below need.  Fails, with the
+ * limit in the message, for N or M outside 1..8192, B < 1 and gamma <= 0. */
+typedef struct t2_softdtw_plan_info {
+    int threads;          /* per workgroup: whole 64-lane waves, at most 1024 */
+    int rows_per_thread;  /* consecutive rows a thread owns: 1, 2, 4 or 8, the smallest with rows_per_thread * 1024 >= N */
+    int passes;           /* of the wavefront: M + ceil(N / rows_per_thread) - 1 */
+    size_t d_floats;      /* internal distance scratch Ds: B * passes * threads * rows_per_thread */
+    size_t r_floats;      /* stored R (same layout); 0 when need_grad == 0: the forward then keeps O(N) state only */
+    size_t e_floats;      /* E, [B,N,M] row-major; 0 when need_grad == 0 */
+} t2_softdtw_plan_info;
+int t2_softdtw_plan(int B, int N, int M, float gamma, int need_grad, t2_softdtw_plan_info* out);
+/* Ds = pairwise squared Euclidean distances sum_c (x[b,i,c] - y[b,j,c])^2 (c ascending, fused multiply-adds), in the
+ * internal layout [B][passes][threads][rows_per_thread] the wavefront reads with adjacent lanes on adjacent addresses. */
+typedef struct t2_softdtw_dist_args {
+    int B, N, M, d;
+    const float* x;       /* [B,N,d] */
+    const float* y;       /* [B,M,d] */
+    float* Ds;            /* d_floats */
+} t2_softdtw_dist_args;
+int t2_softdtw_dist(const t2_softdtw_dist_args* a, void* stream);
+/* value[b] = R[n_b, m_b].  Exactly one of D (a caller's distance matrix, row-major [B,N,M]: SoftDTW(dist_func=...)) and
+ * Ds (t2_softdtw_dist's output) is given.  R == NULL: nothing but value is written.  R given (r_floats): R is stored
+ * for t2_softdtw_backward. */
+typedef struct t2_softdtw_fwd_args {
+    int B, N, M;
+    float gamma, bandwidth;           /* bandwidth 0 = off (SoftDTW(bandwidth=None)) */
+    const float* D; const float* Ds;
+    const int32_t* x_lengths; const int32_t* y_lengths;   /* [B] each, or both NULL */
+    float* R;
+    float* value;                     /* [B] */
+} t2_softdtw_fwd_args;
+int t2_softdtw_forward(const t2_softdtw_fwd_args* a, void* stream);
+/* E[b,i,j] = d value[b] / d D[b,i,j], [B,N,M] row-major, from the R a forward call with the same arguments stored
+ * (soft_dtw_cuda.py:158-174 without the multiplication by grad_output).  Enqueues a memset of E before the kernel. */
+typedef struct t2_softdtw_bwd_args {
+    int B, N, M;
+    float gamma, bandwidth;
+    const float* D; const float* Ds;
+    const int32_t* x_lengths; const int32_t* y_lengths;
+    const float* R;
+    float* E;
+} t2_softdtw_bwd_args;
+int t2_softdtw_backward(const t2_softdtw_bwd_args* a, void* stream);
+/* Gradient of value through the Euclidean distances, G = grad_out[b] * E:
+ * dX[b,i,:] = 2 sum_j G[b,i,j] (x[b,i,:] - y[b,j,:]), dY[b,j,:] = -2 sum_i G[b,i,j] (x[b,i,:] - y[b,j,:]); sums in
+ * ascending order, no atomics. */
+typedef struct t2_softdtw_dist_bwd_args {
+    int B, N, M, d;
+    const float* x; const float* y;
+    const float* E;                   /* [B,N,M] */
+    const float* grad_out;            /* [B] */
+    const int32_t* x_lengths; const int32_t* y_lengths;
+    float* dX; float* dY;             /* [B,N,d], [B,M,d] */
+} t2_softdtw_dist_bwd_args;
+int t2_softdtw_dist_backward(const t2_softdtw_dist_bwd_args* a, void* stream);
+
 /* Gradient-norm clipping + Adam over a list of fp32 tensors — replaces torch.nn.utils.clip_grad_norm_ +
  * torch.optim.Adam.step of the training loop (train.py:322-330; Adam with weight decay added to the gradient).
  * `table` is a DEVICE array of n_tensors rows; row i covers chunks [first_chunk, first_chunk + t2_adam_chunks(numel))

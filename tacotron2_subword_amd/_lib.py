@@ -162,6 +162,33 @@ class GemmPlanInfo(C.Structure):
                 ("a_src", C.c_int), ("b_src", C.c_int), ("stage_bytes_a", C.c_size_t), ("stage_bytes_b", C.c_size_t)]
 
 
+class SoftDtwPlanInfo(C.Structure):
+    _fields_ = [("threads", C.c_int), ("rows_per_thread", C.c_int), ("passes", C.c_int),
+                ("d_floats", C.c_size_t), ("r_floats", C.c_size_t), ("e_floats", C.c_size_t)]
+
+
+class SoftDtwDistArgs(C.Structure):
+    _fields_ = [("B", C.c_int), ("N", C.c_int), ("M", C.c_int), ("d", C.c_int), ("x", C.c_void_p), ("y", C.c_void_p), ("Ds", C.c_void_p)]
+
+
+class SoftDtwFwdArgs(C.Structure):
+    _fields_ = [("B", C.c_int), ("N", C.c_int), ("M", C.c_int), ("gamma", C.c_float), ("bandwidth", C.c_float),
+                ("D", C.c_void_p), ("Ds", C.c_void_p), ("x_lengths", C.c_void_p), ("y_lengths", C.c_void_p),
+                ("R", C.c_void_p), ("value", C.c_void_p)]
+
+
+class SoftDtwBwdArgs(C.Structure):
+    _fields_ = [("B", C.c_int), ("N", C.c_int), ("M", C.c_int), ("gamma", C.c_float), ("bandwidth", C.c_float),
+                ("D", C.c_void_p), ("Ds", C.c_void_p), ("x_lengths", C.c_void_p), ("y_lengths", C.c_void_p),
+                ("R", C.c_void_p), ("E", C.c_void_p)]
+
+
+class SoftDtwDistBwdArgs(C.Structure):
+    _fields_ = [("B", C.c_int), ("N", C.c_int), ("M", C.c_int), ("d", C.c_int), ("x", C.c_void_p), ("y", C.c_void_p),
+                ("E", C.c_void_p), ("grad_out", C.c_void_p), ("x_lengths", C.c_void_p), ("y_lengths", C.c_void_p),
+                ("dX", C.c_void_p), ("dY", C.c_void_p)]
+
+
 # every symbol include/t2amd.h declares (tests/test_abi.py checks the library exports them all)
 ABI_VERSION = 4      # include/t2amd.h T2_ABI_VERSION: struct sizes below match that header and nothing else
 
@@ -169,7 +196,8 @@ EXPORTS = ["t2_last_error", "t2_version", "t2_chain_status", "t2_chain_status_cl
            "t2_decoder_bwd_layout_query", "t2_decoder_backward", "t2_prof_enable", "t2_prof_collect", "t2_adam_chunks", "t2_adam_step", "t2_adam_norm",
            "t2_conv_bn_forward", "t2_conv_bn_backward", "t2_embedding_forward", "t2_embedding_backward",
            "t2_lstm_seq_forward", "t2_lstm_seq_backward", "t2_lstm_seq_chain_ws_floats", "t2_gemm_ex", "t2_prof_gemm", "t2_gemm_plan", "t2_conv_handoff_plan", "t2_colsum", "t2_mask_btc",
-           "t2_finalize_bct", "t2_mask_bt", "t2_gemm", "t2_rng_keep_mask", "t2_rng_normal"]
+           "t2_finalize_bct", "t2_mask_bt", "t2_gemm", "t2_rng_keep_mask", "t2_rng_normal",
+           "t2_softdtw_plan", "t2_softdtw_dist", "t2_softdtw_forward", "t2_softdtw_backward", "t2_softdtw_dist_backward"]
 
 _lib = None
 
@@ -220,6 +248,11 @@ def lib() -> C.CDLL:
         L.t2_prof_collect.argtypes = [C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_int)]
         L.t2_finalize_bct.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_float, C.c_void_p]
         L.t2_mask_bt.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_float, C.c_void_p]
+        L.t2_softdtw_plan.argtypes = [C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, C.POINTER(SoftDtwPlanInfo)]
+        L.t2_softdtw_dist.argtypes = [C.POINTER(SoftDtwDistArgs), C.c_void_p]
+        L.t2_softdtw_forward.argtypes = [C.POINTER(SoftDtwFwdArgs), C.c_void_p]
+        L.t2_softdtw_backward.argtypes = [C.POINTER(SoftDtwBwdArgs), C.c_void_p]
+        L.t2_softdtw_dist_backward.argtypes = [C.POINTER(SoftDtwDistBwdArgs), C.c_void_p]
         _lib = L
     return _lib
 
@@ -482,3 +515,11 @@ def conv_handoff_plan(args: GemmArgs, **opts) -> dict:
 def set_gemm_split_min_mflop(mflop: int = -1) -> None:
     """"bf16x3": products below 2*M*N*K = mflop * 1e6 stay on the exact fp32 kernel (include/t2amd.h); -1 = the default."""
     check(lib().t2_set_gemm_split_min_mflop(int(mflop)))
+
+
+def softdtw_plan(B: int, N: int, M: int, gamma: float = 1.0, need_grad: bool = False) -> SoftDtwPlanInfo:
+    """The partition and scratch sizes of a soft-DTW batch (t2_softdtw_plan: nothing is launched, no device needed);
+    raises for sizes over the limit and for gamma <= 0."""
+    info = SoftDtwPlanInfo()
+    check(lib().t2_softdtw_plan(B, N, M, gamma, int(bool(need_grad)), C.byref(info)))
+    return info

@@ -1799,6 +1799,34 @@ int t2_mask_btc(float* x, int B, int T, int C, const int32_t* lengths, float fil
     return mask_btc(x, B, T, C, lengths, fill, (hipStream_t)stream);
 }
 
+int t2_softdtw_plan(int B, int N, int M, float gamma, int need_grad, t2_softdtw_plan_info* out) {
+    SoftDtwPlan p;
+    T2_TRY(softdtw_plan(B, N, M, gamma, need_grad, &p));
+    T2_REQUIRE(out, "t2_softdtw_plan: null output");
+    out->threads = p.threads; out->rows_per_thread = p.rows_per_thread; out->passes = p.passes;
+    out->d_floats = p.d_floats; out->r_floats = p.r_floats; out->e_floats = p.e_floats;
+    return 0;
+}
+int t2_softdtw_dist(const t2_softdtw_dist_args* a, void* stream) {
+    T2_REQUIRE(a, "t2_softdtw_dist: null arguments");
+    return softdtw_dist(SoftDtwDist{a->B, a->N, a->M, a->d, a->x, a->y, a->Ds}, (hipStream_t)stream);
+}
+int t2_softdtw_forward(const t2_softdtw_fwd_args* a, void* stream) {
+    T2_REQUIRE(a, "t2_softdtw_forward: null arguments");
+    return softdtw_fwd(SoftDtwArgs{a->B, a->N, a->M, a->gamma, a->bandwidth, a->D, a->Ds, a->x_lengths, a->y_lengths, a->R, a->value, nullptr},
+                       (hipStream_t)stream);
+}
+int t2_softdtw_backward(const t2_softdtw_bwd_args* a, void* stream) {
+    T2_REQUIRE(a, "t2_softdtw_backward: null arguments");
+    return softdtw_bwd(SoftDtwArgs{a->B, a->N, a->M, a->gamma, a->bandwidth, a->D, a->Ds, a->x_lengths, a->y_lengths,
+                                   const_cast<float*>(a->R), nullptr, a->E}, (hipStream_t)stream);
+}
+int t2_softdtw_dist_backward(const t2_softdtw_dist_bwd_args* a, void* stream) {
+    T2_REQUIRE(a, "t2_softdtw_dist_backward: null arguments");
+    return softdtw_dist_bwd(SoftDtwDistBwd{a->B, a->N, a->M, a->d, a->x, a->y, a->E, a->grad_out, a->x_lengths, a->y_lengths, a->dX, a->dY},
+                            (hipStream_t)stream);
+}
+
 int t2_prof_enable(int max_launches) {
     if (max_launches <= 0) { g_prof.on = false; return 0; }
     const size_t need = (size_t)max_launches * 2;

@@ -427,6 +427,31 @@ int conv_bn_bwd(const ConvBnBwd& a, hipStream_t s);
 int embedding_fwd(const long* ids, const float* table, float* out, int rows, int D, hipStream_t s);
 int embedding_bwd(const long* ids, const float* dout, float* dtable, int rows, int D, int vocab, hipStream_t s);
 
+// ------------------------------------------------------------------ soft-DTW (softdtw.hip)
+constexpr int kSoftDtwMaxLen = 8192;             // frames per sequence: 1024 threads x 8 rows
+// The partition of one pair's recurrence, decided on the host (no device needed): `threads` per workgroup (whole waves),
+// each owning rows_per_thread consecutive rows (1, 2, 4 or 8: the smallest that fits N into 1024 threads), `passes` of the
+// skewed wavefront (M + owning threads - 1), and the floats of the internal D / R scratch ([B][passes][threads][rows]) and
+// of E ([B,N,M]); R and E are zero-sized without gradient.
+struct SoftDtwPlan { int threads, rows_per_thread, passes; size_t d_floats, r_floats, e_floats; };
+int softdtw_plan(int B, int N, int M, float gamma, int need_grad, SoftDtwPlan* out);
+struct SoftDtwDist { int B, N, M, d; const float* x; const float* y; float* Ds; };     // x [B,N,d], y [B,M,d] -> Ds (d_floats)
+int softdtw_dist(const SoftDtwDist& a, hipStream_t s);
+// forward: value[b] = R[n_b, m_b]; R != null stores the whole R (r_floats) for softdtw_bwd.  backward: E [B,N,M] (zeroed
+// here first).  Exactly one of D (caller's row-major [B,N,M]) and Ds (softdtw_dist's output) is given; lengths nullable.
+struct SoftDtwArgs {
+    int B, N, M; float gamma, bandwidth;
+    const float* D; const float* Ds; const int* x_lengths; const int* y_lengths;
+    float* R; float* value; float* E;
+};
+int softdtw_fwd(const SoftDtwArgs& a, hipStream_t s);
+int softdtw_bwd(const SoftDtwArgs& a, hipStream_t s);
+struct SoftDtwDistBwd {
+    int B, N, M, d; const float* x; const float* y; const float* E; const float* grad_out;
+    const int* x_lengths; const int* y_lengths; float* dX; float* dY;
+};
+int softdtw_dist_bwd(const SoftDtwDistBwd& a, hipStream_t s);
+
 // ------------------------------------------------------------------ optimizer (optim.hip)
 struct AdamTensor { float* p; const float* g; float* m; float* v; long numel; int first_chunk; int pad_; };   // 48 bytes, mirrors t2_adam_tensor
 int adam_chunks(long numel);
