@@ -514,6 +514,67 @@ typedef struct t2_softdtw_dist_bwd_args {
 } t2_softdtw_dist_bwd_args;
 int t2_softdtw_dist_backward(const t2_softdtw_dist_bwd_args* a, void* stream);
 
+/* ---- HiFi-GAN generator (mel spectrogram -> waveform) ----------------------------------------------
+ * Replaces the reference's hifigan_infer/hifigan_model.py: Generator.forward (:100-116), ResBlock1.forward (:35-42),
+ * ResBlock2.forward (:63-68), as inference.py:172-206, best_checkpoint.py:191-228, streamlitNews.py:115-160 and
+ * logger.py:19-33 call it.  Unlike the rest of this header the vocoder keeps torch's [B, C, L] layout (time contiguous)
+ * and ignores t2_set_precision: it always computes in exact fp32 on the matrix cores.  Weights are the folded ones (after
+ * remove_weight_norm, hifigan_model.py:118-124) in torch layout, Conv1d [Cout][Cin][k], ConvTranspose1d [Cin][Cout][k].
+ * Supported: resblock kind 1 or 2; 80 mel channels; channel counts that are multiples of 8, up to 512; Conv1d kernels
+ * 3, 5, 7, 11 at dilations 1, 2, 3, 5, 6, 12; ConvTranspose1d with kernel = 2 * stride, stride even and <= 16 (covers
+ * (16,8), (8,4), (4,2)).  Everything else is refused with the offending value in t2_last_error; nothing else is ever
+ * computed in its place.  No atomics, a fixed order for every sum: results are bit-identical from run to run and for an
+ * item alone or inside a batch.  Ordinary launches on `stream`. */
+#define T2_HIFIGAN_MAX_UPS 6
+#define T2_HIFIGAN_MAX_KERNELS 6
+#define T2_HIFIGAN_MAX_DILATIONS 3
+#define T2_VOCODER_TIME_TILE 128 /* time positions per workgroup of the conv kernels (tests probe its edges) */
+typedef struct t2_hifigan_config {       /* the fields of the reference's config_v*.json that Generator reads */
+    int resblock;                        /* 1 or 2 (the json's "1" / "2") */
+    int n_mel;                           /* 80: conv_pre's input channels (hifigan_model.py:81) */
+    int upsample_initial_channel;
+    int num_upsamples, upsample_rates[T2_HIFIGAN_MAX_UPS], upsample_kernel_sizes[T2_HIFIGAN_MAX_UPS];
+    int num_kernels, resblock_kernel_sizes[T2_HIFIGAN_MAX_KERNELS];
+    int num_dilations;                   /* per resblock: 3 for kind 1, 2 for kind 2 */
+    int resblock_dilation_sizes[T2_HIFIGAN_MAX_KERNELS][T2_HIFIGAN_MAX_DILATIONS];
+} t2_hifigan_config;
+typedef struct t2_hifigan_plan_info {
+    long out_len;            /* samples per item: T * product of the rates */
+    size_t workspace_bytes;  /* five activation buffers of the widest stage */
+    size_t packed_bytes;     /* all layers' weights in fragment order, and the biases */
+    int n_layers;            /* conv_pre, ups[i], every resblock conv, conv_post: the order of the state dict */
+    int time_tile;           /* T2_VOCODER_TIME_TILE */
+} t2_hifigan_plan_info;
+/* Pure host call (no device): validates cfg, B >= 1 and T >= 1 and sizes the buffers. */
+int t2_hifigan_plan(const t2_hifigan_config* cfg, int B, int T, t2_hifigan_plan_info* out);
+/* weights_host / biases_host: HOST arrays of n_layers DEVICE pointers in layer order.  Writes `packed` (packed_bytes); done
+ * once per set of weights, not per call. */
+int t2_hifigan_pack(const t2_hifigan_config* cfg, const float* const* weights_host, const float* const* biases_host, int n_layers,
+                    float* packed, void* stream);
+typedef struct t2_hifigan_fwd_args {
+    int B, T, n_mel;         /* n_mel: channels of the tensor given, checked against cfg */
+    const float* packed;
+    const float* mel;        /* [B, n_mel, T] */
+    float* workspace;        /* workspace_bytes */
+    float* audio;            /* [B, 1, out_len] */
+    float* pre_tanh;         /* debug output, nullable: conv_post's output before the tanh, [B, 1, out_len] */
+} t2_hifigan_fwd_args;
+int t2_hifigan_forward(const t2_hifigan_config* cfg, const t2_hifigan_fwd_args* a, void* stream);
+/* Single layers, for the tests only (the generator runs the same kernels).  w in torch layout; packed_ws receives the
+ * packed weights first: t2_vocoder_packed_floats(Cin, Cout, k, u) floats, u = 0 for Conv1d.
+ * conv1d (stride 1, padding (k*d - d)/2): y = ((accumulate ? y : 0) + conv(leaky_relu(x, slope)) + bias + residual) * scale,
+ *   x, y, residual [B, C, L]; bias and residual nullable.
+ * conv_transpose1d (stride u, padding (k - u)/2): y [B, Cout, L*u] = convT(leaky_relu(x, slope)) + bias. */
+typedef struct t2_vocoder_conv_args {
+    int B, Cin, Cout, L, k, d, u;
+    const float* x; const float* w; const float* bias; const float* residual;
+    float* y; float* packed_ws;
+    float slope; int accumulate; float scale;
+} t2_vocoder_conv_args;
+size_t t2_vocoder_packed_floats(int Cin, int Cout, int k, int u);
+int t2_vocoder_conv1d(const t2_vocoder_conv_args* a, void* stream);              /* a->u must be 0 */
+int t2_vocoder_conv_transpose1d(const t2_vocoder_conv_args* a, void* stream);    /* a->d, residual, accumulate unused */
+
 /* Gradient-norm clipping + Adam over a list of fp32 tensors — replaces torch.nn.utils.clip_grad_norm_ +
  * torch.optim.Adam.step of the training loop (train.py:322-330; Adam with weight decay added to the gradient).
  * `table` is a DEVICE array of n_tensors rows; row i covers chunks [first_chunk, first_chunk + t2_adam_chunks(numel))

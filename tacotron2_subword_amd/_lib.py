@@ -189,6 +189,35 @@ class SoftDtwDistBwdArgs(C.Structure):
                 ("dX", C.c_void_p), ("dY", C.c_void_p)]
 
 
+_I6 = C.c_int * 6
+
+
+class HifiganConfig(C.Structure):
+    _fields_ = [("resblock", C.c_int), ("n_mel", C.c_int), ("upsample_initial_channel", C.c_int),
+                ("num_upsamples", C.c_int), ("upsample_rates", _I6), ("upsample_kernel_sizes", _I6),
+                ("num_kernels", C.c_int), ("resblock_kernel_sizes", _I6),
+                ("num_dilations", C.c_int), ("resblock_dilation_sizes", (C.c_int * 3) * 6)]
+
+
+class HifiganPlanInfo(C.Structure):
+    _fields_ = [("out_len", C.c_long), ("workspace_bytes", C.c_size_t), ("packed_bytes", C.c_size_t),
+                ("n_layers", C.c_int), ("time_tile", C.c_int)]
+
+
+class HifiganFwdArgs(C.Structure):
+    _fields_ = [("B", C.c_int), ("T", C.c_int), ("n_mel", C.c_int), ("packed", C.c_void_p), ("mel", C.c_void_p),
+                ("workspace", C.c_void_p), ("audio", C.c_void_p), ("pre_tanh", C.c_void_p)]
+
+
+class VocoderConvArgs(C.Structure):
+    _fields_ = [("B", C.c_int), ("Cin", C.c_int), ("Cout", C.c_int), ("L", C.c_int), ("k", C.c_int), ("d", C.c_int), ("u", C.c_int),
+                ("x", C.c_void_p), ("w", C.c_void_p), ("bias", C.c_void_p), ("residual", C.c_void_p),
+                ("y", C.c_void_p), ("packed_ws", C.c_void_p),
+                ("slope", C.c_float), ("accumulate", C.c_int), ("scale", C.c_float)]
+
+
+VOCODER_TIME_TILE = 128      # include/t2amd.h T2_VOCODER_TIME_TILE
+
 # every symbol include/t2amd.h declares (tests/test_abi.py checks the library exports them all)
 ABI_VERSION = 4      # include/t2amd.h T2_ABI_VERSION: struct sizes below match that header and nothing else
 
@@ -197,7 +226,8 @@ EXPORTS = ["t2_last_error", "t2_version", "t2_chain_status", "t2_chain_status_cl
            "t2_conv_bn_forward", "t2_conv_bn_backward", "t2_embedding_forward", "t2_embedding_backward",
            "t2_lstm_seq_forward", "t2_lstm_seq_backward", "t2_lstm_seq_chain_ws_floats", "t2_gemm_ex", "t2_prof_gemm", "t2_gemm_plan", "t2_conv_handoff_plan", "t2_colsum", "t2_mask_btc",
            "t2_finalize_bct", "t2_mask_bt", "t2_gemm", "t2_rng_keep_mask", "t2_rng_normal",
-           "t2_softdtw_plan", "t2_softdtw_dist", "t2_softdtw_forward", "t2_softdtw_backward", "t2_softdtw_dist_backward"]
+           "t2_softdtw_plan", "t2_softdtw_dist", "t2_softdtw_forward", "t2_softdtw_backward", "t2_softdtw_dist_backward",
+           "t2_hifigan_plan", "t2_hifigan_pack", "t2_hifigan_forward", "t2_vocoder_packed_floats", "t2_vocoder_conv1d", "t2_vocoder_conv_transpose1d"]
 
 _lib = None
 
@@ -253,6 +283,12 @@ def lib() -> C.CDLL:
         L.t2_softdtw_forward.argtypes = [C.POINTER(SoftDtwFwdArgs), C.c_void_p]
         L.t2_softdtw_backward.argtypes = [C.POINTER(SoftDtwBwdArgs), C.c_void_p]
         L.t2_softdtw_dist_backward.argtypes = [C.POINTER(SoftDtwDistBwdArgs), C.c_void_p]
+        L.t2_hifigan_plan.argtypes = [C.POINTER(HifiganConfig), C.c_int, C.c_int, C.POINTER(HifiganPlanInfo)]
+        L.t2_hifigan_pack.argtypes = [C.POINTER(HifiganConfig), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_int, C.c_void_p, C.c_void_p]
+        L.t2_hifigan_forward.argtypes = [C.POINTER(HifiganConfig), C.POINTER(HifiganFwdArgs), C.c_void_p]
+        L.t2_vocoder_packed_floats.argtypes, L.t2_vocoder_packed_floats.restype = [C.c_int, C.c_int, C.c_int, C.c_int], C.c_size_t
+        L.t2_vocoder_conv1d.argtypes = [C.POINTER(VocoderConvArgs), C.c_void_p]
+        L.t2_vocoder_conv_transpose1d.argtypes = [C.POINTER(VocoderConvArgs), C.c_void_p]
         _lib = L
     return _lib
 
@@ -522,4 +558,40 @@ def softdtw_plan(B: int, N: int, M: int, gamma: float = 1.0, need_grad: bool = F
     raises for sizes over the limit and for gamma <= 0."""
     info = SoftDtwPlanInfo()
     check(lib().t2_softdtw_plan(B, N, M, gamma, int(bool(need_grad)), C.byref(info)))
+    return info
+
+
+def hifigan_config(h) -> HifiganConfig:
+    """The C-side configuration from the reference's ``h`` (attribute or key access on the fields Generator reads).
+    Raises for what the struct cannot hold; everything else is for t2_hifigan_plan to judge."""
+    g = (lambda k: h[k]) if isinstance(h, dict) else (lambda k: getattr(h, k))
+    rates, ukernels = list(g("upsample_rates")), list(g("upsample_kernel_sizes"))
+    rkernels, rdil = list(g("resblock_kernel_sizes")), [list(d) for d in g("resblock_dilation_sizes")]
+    kind = str(g("resblock"))
+    if not kind.lstrip("-").isdigit():
+        raise RuntimeError(f"hifigan: resblock \"{kind}\" is not \"1\" or \"2\"")
+    if len(rates) != len(ukernels) or len(rkernels) != len(rdil):
+        raise RuntimeError("hifigan: upsample_rates / upsample_kernel_sizes and resblock_kernel_sizes / resblock_dilation_sizes must pair up")
+    if len(rates) > 6 or len(rkernels) > 6:
+        raise RuntimeError(f"hifigan: {len(rates)} upsampling stages / {len(rkernels)} resblock kernels, at most 6 each")
+    nd = len(rdil[0]) if rdil else 0
+    if any(len(d) != nd for d in rdil) or nd > 3:
+        raise RuntimeError(f"hifigan: resblock_dilation_sizes={rdil} must hold equally many (at most 3) dilations per kernel")
+    c = HifiganConfig()
+    c.resblock, c.n_mel, c.upsample_initial_channel = int(kind), 80, int(g("upsample_initial_channel"))
+    c.num_upsamples, c.num_kernels, c.num_dilations = len(rates), len(rkernels), nd
+    for i, (u, k) in enumerate(zip(rates, ukernels)):
+        c.upsample_rates[i], c.upsample_kernel_sizes[i] = int(u), int(k)
+    for j, (k, ds) in enumerate(zip(rkernels, rdil)):
+        c.resblock_kernel_sizes[j] = int(k)
+        for m, d in enumerate(ds):
+            c.resblock_dilation_sizes[j][m] = int(d)
+    return c
+
+
+def hifigan_plan(cfg: HifiganConfig, B: int, T: int) -> HifiganPlanInfo:
+    """Output length and buffer sizes of a generator call (t2_hifigan_plan: pure host, no device needed); raises with the
+    library's message for a configuration it refuses."""
+    info = HifiganPlanInfo()
+    check(lib().t2_hifigan_plan(C.byref(cfg), B, T, C.byref(info)))
     return info

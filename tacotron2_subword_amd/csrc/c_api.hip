@@ -1827,6 +1827,44 @@ int t2_softdtw_dist_backward(const t2_softdtw_dist_bwd_args* a, void* stream) {
                             (hipStream_t)stream);
 }
 
+static_assert(sizeof(t2_hifigan_config) == sizeof(HifiganConfig) && T2_HIFIGAN_MAX_UPS == kHifiganMaxUps && T2_HIFIGAN_MAX_KERNELS == kHifiganMaxKernels &&
+              T2_HIFIGAN_MAX_DILATIONS == kHifiganMaxDilations && T2_VOCODER_TIME_TILE == kVocTT, "t2_hifigan_config mirrors HifiganConfig");
+int t2_hifigan_plan(const t2_hifigan_config* cfg, int B, int T, t2_hifigan_plan_info* out) {
+    T2_REQUIRE(cfg && out, "t2_hifigan_plan: null pointer");
+    HifiganPlan p;
+    T2_TRY(hifigan_plan(*reinterpret_cast<const HifiganConfig*>(cfg), B, T, &p));
+    out->out_len = p.out_len; out->workspace_bytes = p.workspace_bytes; out->packed_bytes = p.packed_bytes;
+    out->n_layers = p.n_layers; out->time_tile = kVocTT;
+    return 0;
+}
+int t2_hifigan_pack(const t2_hifigan_config* cfg, const float* const* weights_host, const float* const* biases_host, int n_layers,
+                    float* packed, void* stream) {
+    T2_REQUIRE(cfg, "t2_hifigan_pack: null configuration");
+    return hifigan_pack(*reinterpret_cast<const HifiganConfig*>(cfg), weights_host, biases_host, n_layers, packed, (hipStream_t)stream);
+}
+int t2_hifigan_forward(const t2_hifigan_config* cfg, const t2_hifigan_fwd_args* a, void* stream) {
+    T2_REQUIRE(cfg && a, "t2_hifigan_forward: null pointer");
+    return hifigan_forward(*reinterpret_cast<const HifiganConfig*>(cfg),
+                           HifiganFwd{a->B, a->T, a->n_mel, a->packed, a->mel, a->workspace, a->audio, a->pre_tanh}, (hipStream_t)stream);
+}
+size_t t2_vocoder_packed_floats(int Cin, int Cout, int k, int u) { return voc_packed_floats(Cin, Cout, k, u); }
+static int vocoder_layer(const t2_vocoder_conv_args* a, int u, void* stream) {
+    T2_REQUIRE(a->w && a->packed_ws, "t2_vocoder: null weights or packing scratch");
+    T2_TRY(voc_pack(a->w, a->packed_ws, a->Cin, a->Cout, a->k, u, (hipStream_t)stream));
+    return voc_conv(VocConv{a->B, a->Cin, a->Cout, (long)a->L, a->k, a->d, u, a->x, a->packed_ws, a->bias, u ? nullptr : a->residual, a->y,
+                            a->slope, u ? 0 : a->accumulate, u ? 1.f : a->scale}, (hipStream_t)stream);
+}
+int t2_vocoder_conv1d(const t2_vocoder_conv_args* a, void* stream) {
+    T2_REQUIRE(a, "t2_vocoder_conv1d: null arguments");
+    T2_REQUIRE(a->u == 0, "t2_vocoder_conv1d: stride u=%d given, a Conv1d has none", a->u);
+    return vocoder_layer(a, 0, stream);
+}
+int t2_vocoder_conv_transpose1d(const t2_vocoder_conv_args* a, void* stream) {
+    T2_REQUIRE(a, "t2_vocoder_conv_transpose1d: null arguments");
+    T2_REQUIRE(a->u >= 1, "t2_vocoder_conv_transpose1d: stride u=%d must be positive", a->u);
+    return vocoder_layer(a, a->u, stream);
+}
+
 int t2_prof_enable(int max_launches) {
     if (max_launches <= 0) { g_prof.on = false; return 0; }
     const size_t need = (size_t)max_launches * 2;

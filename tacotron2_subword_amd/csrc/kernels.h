@@ -452,6 +452,37 @@ struct SoftDtwDistBwd {
 };
 int softdtw_dist_bwd(const SoftDtwDistBwd& a, hipStream_t s);
 
+// ------------------------------------------------------------------ HiFi-GAN vocoder (vocoder.hip)
+constexpr int kVocTT = 128;                      // time positions per workgroup
+constexpr int kVocMaxPad = 60;                   // (k*d - d)/2 at k = 11, d = 12
+constexpr int kHifiganMaxUps = 6, kHifiganMaxKernels = 6, kHifiganMaxDilations = 3;
+// One layer on packed weights.  u == 0: Conv1d, kernel k, dilation d, stride 1, padding (k*d - d)/2, x [B,Cin,L] ->
+// y [B,Cout,L];  y = ((accumulate ? y : 0) + conv(lrelu(x, slope)) + bias + res) * scale, bias and res nullable.
+// u > 0: ConvTranspose1d, kernel k = 2u, stride u, padding (k - u)/2, x [B,Cin,L] -> y [B,Cout,L*u]; no res / accumulate.
+struct VocConv {
+    int B, Cin, Cout; long L; int k, d, u;
+    const float* x; const float* packed; const float* bias; const float* res; float* y;
+    float slope; int accumulate; float scale;
+};
+size_t voc_packed_floats(int Cin, int Cout, int k, int u);
+int voc_pack(const float* w, float* packed, int Cin, int Cout, int k, int u, hipStream_t s);     // w in torch layout
+int voc_conv(const VocConv& a, hipStream_t s);
+struct HifiganConfig {                           // mirrors t2_hifigan_config
+    int resblock, n_mel, upsample_initial_channel;
+    int num_upsamples, upsample_rates[kHifiganMaxUps], upsample_kernel_sizes[kHifiganMaxUps];
+    int num_kernels, resblock_kernel_sizes[kHifiganMaxKernels];
+    int num_dilations, resblock_dilation_sizes[kHifiganMaxKernels][kHifiganMaxDilations];
+};
+// kind 0 Conv1d, 1 ConvTranspose1d, 2 conv_post; offsets in floats into the packed weights.  Order: conv_pre, ups[i],
+// resblocks[n] (ResBlock1: convs1[m] then convs2[m]; ResBlock2: convs[m]), conv_post: the order of the state dict.
+struct HifiganLayer { int kind, cin, cout, k, d, u; size_t w_off, b_off; };
+struct HifiganPlan { long out_len; size_t buf_floats, workspace_bytes, packed_bytes; int n_layers; };
+int hifigan_layers(const HifiganConfig& c, std::vector<HifiganLayer>* out, size_t* packed_floats);   // validates; no device
+int hifigan_plan(const HifiganConfig& c, int B, int T, HifiganPlan* out);
+int hifigan_pack(const HifiganConfig& c, const float* const* weights, const float* const* biases, int n_layers, float* packed, hipStream_t s);
+struct HifiganFwd { int B, T, n_mel; const float* packed; const float* mel; float* workspace; float* audio; float* pre_tanh; };
+int hifigan_forward(const HifiganConfig& c, const HifiganFwd& a, hipStream_t s);
+
 // ------------------------------------------------------------------ optimizer (optim.hip)
 struct AdamTensor { float* p; const float* g; float* m; float* v; long numel; int first_chunk; int pad_; };   // 48 bytes, mirrors t2_adam_tensor
 int adam_chunks(long numel);

@@ -1,0 +1,349 @@
+// HiFi-GAN generator (Kong et al. 2020), inference: mel spectrogram -> waveform.  Replaces the reference's
+// hifigan_infer/hifigan_model.py: Generator.forward (:100-116), ResBlock1.forward (:35-42), ResBlock2.forward (:63-68).
+//
+// Activations are [B][C][L] with time contiguous, as torch lays them out; nothing is transposed.  Arithmetic is exact fp32
+// on the matrix cores (v_mfma_f32_32x32x2_f32: a k-ordered fmaf chain), whatever t2_set_precision says.
+//
+// One kernel serves the dilated Conv1d and the ConvTranspose1d.  Both are the GEMM  Y[co][q] = sum_{ci,j} W[co][ci,j] *
+// act(X[ci][q + off_j])  with M = Cout, N = time and K = Cin * taps:
+//   Conv1d (stride 1, "same" padding pad = (k*d - d)/2):   off_j = j*d - pad, one output per q;
+//   ConvTranspose1d (stride u, kernel k = 2u, padding u/2), polyphase: output sample u*q + r reads only the taps
+//     j = (r + pad) % u + m*u (m = 0, 1) at input q + (r + pad)/u - m, so phase r is a two-tap GEMM of its own whose
+//     outputs land u apart.  No zero-stuffed input, no atomics: every output element is written once.
+// A workgroup owns kVocTT = 128 time positions of up to 128 output channels of one batch item (and one phase).  Per chunk
+// of 16 input channels it stages the slab [16][128 + halo] of the input in LDS once, with the leaky ReLU applied and zeros
+// outside [0, L); every tap reads that slab at a shifted column: lanes along time, the two k-rows of an MFMA step 288
+// floats apart (32 banks), so the reads are conflict-free, and each global load is used by all taps.  A wave computes a
+// 32 (channels) x 64 (time) tile: two accumulators share each weight fragment.  The weights are packed once (voc_pack_kernel)
+// into the order the lanes consume them, four k-steps per 16-byte load, zero-padded to whole 32-channel tiles / 16-channel
+// chunks (Cout = 8 wastes three quarters of its tile: accepted).  Epilogue: bias, optional residual, optional
+// accumulate-into-destination, scale.  The order of every sum is fixed: same bits from run to run and for an item alone
+// or in a batch.  Element offsets are 64-bit throughout.
+#include <algorithm>
+
+#include "kernels.h"
+
+namespace t2 {
+
+constexpr int kVocCK = 16;                        // input channels per slab
+constexpr int kVocStride = 288;                   // slab row stride in floats: = 32 mod 64 banks, >= kVocTT + 2*kVocMaxPad
+static_assert(kVocStride % 64 == 32 && kVocStride >= kVocTT + 2 * kVocMaxPad, "slab row stride");
+
+struct VocGemm {
+    const float* x; const float* wp; const float* bias; const float* res; float* y;
+    int Cin, Cout, Lin;                           // outputs per phase = Lin; the output row has Lin * ostride elements
+    int taps, d, pad, u, transposed;              // transposed: taps = 2, phases = ostride = u
+    int halo_lo, sw;                              // slab column c holds input t0 + c - halo_lo; sw columns are staged
+    int mtiles, nchunks, ostride;
+    float slope, scale; int accumulate;
+};
+
+template <int WM>
+__global__ void __launch_bounds__(WM * 128) voc_gemm_kernel(VocGemm p) {
+    __shared__ float slab[kVocCK * kVocStride];
+    constexpr int kWaves = WM * 2;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int wm = wave % WM, wt = wave / WM;
+    const int mblocks = (p.mtiles + WM - 1) / WM;
+    const int phase = blockIdx.y / mblocks, mt = (blockIdx.y % mblocks) * WM + wm;
+    const bool active = mt < p.mtiles;             // uniform over the wave
+    const int b = blockIdx.z;
+    const long t0 = (long)blockIdx.x * kVocTT;
+    // slab column of tap j for output q = t0 + c: c + coff0 + j*cstep
+    const int coff0 = p.transposed ? (phase + p.pad) / p.u + 1 : 0, cstep = p.transposed ? -1 : p.d;
+    const float* xb = p.x + (size_t)b * p.Cin * p.Lin;
+    const f32x4* wp = reinterpret_cast<const f32x4*>(p.wp) + (size_t)(phase * p.mtiles + (active ? mt : 0)) * p.nchunks * p.taps * 128;
+    const int tc = wt * 64 + (lane & 31), hk = lane >> 5;
+    f32x16 acc0 = {0}, acc1 = {0};
+
+    for (int c = 0; c < p.nchunks; ++c) {
+        if (c) __syncthreads();                    // every wave is done reading the previous slab
+        for (int row = wave; row < kVocCK; row += kWaves) {
+            const int ci = c * kVocCK + row;
+            const float* xr = xb + (size_t)ci * p.Lin;
+            for (int col = lane; col < p.sw; col += 64) {
+                const long t = t0 + col - p.halo_lo;
+                float v = 0.f;
+                if (ci < p.Cin && t >= 0 && t < p.Lin) {
+                    v = xr[t];
+                    v = v > 0.f ? v : v * p.slope;
+                }
+                slab[row * kVocStride + col] = v;
+            }
+        }
+        __syncthreads();
+        if (active) {
+            for (int j = 0; j < p.taps; ++j) {
+                const float* sb = slab + hk * kVocStride + tc + coff0 + j * cstep;
+                const f32x4* wj = wp + ((size_t)c * p.taps + j) * 128 + lane;
+#pragma unroll
+                for (int pg = 0; pg < 2; ++pg) {
+                    const f32x4 a = wj[pg * 64];
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) {
+                        const float* s2 = sb + (pg * 4 + i) * 2 * kVocStride;
+                        const float b0 = s2[0], b1 = s2[32];
+                        acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(a[i], b0, acc0, 0, 0, 0);
+                        acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(a[i], b1, acc1, 0, 0, 0);
+                    }
+                }
+            }
+        }
+    }
+    if (!active) return;
+    // lane holds time column lane & 31 and rows (e&3) + 8*(e>>2) + 4*hk of each 32x32 tile
+    const size_t lout = (size_t)p.Lin * p.ostride;
+#pragma unroll
+    for (int n = 0; n < 2; ++n) {
+        const long q = t0 + wt * 64 + n * 32 + (lane & 31);
+        if (q >= p.Lin) continue;
+#pragma unroll
+        for (int e = 0; e < 16; ++e) {
+            const int co = mt * 32 + (e & 3) + 8 * (e >> 2) + 4 * hk;
+            if (co >= p.Cout) continue;
+            const size_t o = ((size_t)b * p.Cout + co) * lout + (size_t)q * p.ostride + phase;
+            float v = n == 0 ? acc0[e] : acc1[e];
+            if (p.bias) v += p.bias[co];
+            if (p.res) v += p.res[o];
+            if (p.accumulate) v = p.y[o] + v;
+            p.y[o] = v * p.scale;
+        }
+    }
+}
+
+// packed[phase][mtile][chunk][tap][pg][lane][i] = W[co = 32*mtile + (lane & 31)][ci = 16*chunk + 2*(4*pg + i) + (lane >> 5)][tap]
+// (zero outside the matrix); torch layouts: Conv1d [Cout][Cin][k], ConvTranspose1d [Cin][Cout][k]
+__global__ void __launch_bounds__(256) voc_pack_kernel(const float* __restrict__ w, float* __restrict__ out, int cin, int cout, int k,
+                                                      int transposed, int u, int pad, int mtiles, int nchunks, int taps, size_t total) {
+    const size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= total) return;
+    const int i = idx & 3, lane = (idx >> 2) & 63, pg = (idx >> 8) & 1;
+    size_t rest = idx >> 9;
+    const int j = rest % taps; rest /= taps;
+    const int c = rest % nchunks; rest /= nchunks;
+    const int mt = rest % mtiles;
+    const int phase = (int)(rest / mtiles);
+    const int co = mt * 32 + (lane & 31), ci = c * kVocCK + 2 * (4 * pg + i) + (lane >> 5);
+    float v = 0.f;
+    if (co < cout && ci < cin)
+        v = transposed ? w[((size_t)ci * cout + co) * k + (phase + pad) % u + j * u] : w[((size_t)co * cin + ci) * k + j];
+    out[idx] = v;
+}
+
+// conv_post: y[b,0,t] = tanh(bias + sum_ci sum_j w[ci][j] * lrelu(x[b,ci,t+j-3])), ci then j ascending, one fused multiply-add
+// per term.  Cout = 1 makes it a reduction: one thread per output sample, the weights in LDS, loads coalesced along time.
+constexpr int kVocPostK = 7;
+__global__ void __launch_bounds__(256) voc_post_kernel(const float* __restrict__ x, const float* __restrict__ w, const float* __restrict__ bias,
+                                                      float* __restrict__ audio, float* __restrict__ pre, int C, long L, float slope) {
+    extern __shared__ float ws[];
+    for (int i = threadIdx.x; i < C * kVocPostK; i += 256) ws[i] = w[i];
+    __syncthreads();
+    const long t = (long)blockIdx.x * 256 + threadIdx.x;
+    if (t >= L) return;
+    const int b = blockIdx.y;
+    const float* xb = x + (size_t)b * C * L;
+    float acc = 0.f;
+    for (int ci = 0; ci < C; ++ci) {
+        const float* xr = xb + (size_t)ci * L;
+#pragma unroll
+        for (int j = 0; j < kVocPostK; ++j) {
+            const long tt = t + j - kVocPostK / 2;
+            float v = (tt >= 0 && tt < L) ? xr[tt] : 0.f;
+            v = v > 0.f ? v : v * slope;
+            acc = fmaf(ws[ci * kVocPostK + j], v, acc);
+        }
+    }
+    acc += bias[0];
+    const size_t o = (size_t)b * L + t;
+    if (pre) pre[o] = acc;
+    audio[o] = tanhf(acc);
+}
+
+// ------------------------------------------------------------------------------------------------------------------
+// host
+// ------------------------------------------------------------------------------------------------------------------
+static int voc_shape_check(const char* who, int Cin, int Cout, int k, int d, int u) {
+    T2_REQUIRE(Cin >= 8 && Cin <= 512 && Cin % 8 == 0, "%s: %d input channels, must be a multiple of 8 from 8 to 512", who, Cin);
+    T2_REQUIRE(Cout >= 8 && Cout <= 512 && Cout % 8 == 0, "%s: %d output channels, must be a multiple of 8 from 8 to 512", who, Cout);
+    if (u == 0) {
+        T2_REQUIRE(k == 3 || k == 5 || k == 7 || k == 11, "%s: kernel size %d is not one of 3, 5, 7, 11", who, k);
+        T2_REQUIRE(d == 1 || d == 2 || d == 3 || d == 5 || d == 6 || d == 12, "%s: dilation %d is not one of 1, 2, 3, 5, 6, 12", who, d);
+        static_assert(5 * 12 <= kVocMaxPad, "the largest kernel at the largest dilation fits the slab");
+    } else {
+        T2_REQUIRE((k - u) % 2 == 0, "%s: kernel %d minus stride %d is odd: the padding (k - u)/2 would not give u outputs per input", who, k, u);
+        T2_REQUIRE(u >= 2 && u <= 16 && k == 2 * u, "%s: kernel %d with stride %d is not implemented (kernel = 2 * stride, stride 2..16)", who, k, u);
+    }
+    return 0;
+}
+
+size_t voc_packed_floats(int Cin, int Cout, int k, int u) {
+    const size_t mtiles = (Cout + 31) / 32, nchunks = (Cin + kVocCK - 1) / kVocCK;
+    return u ? (size_t)u * mtiles * nchunks * 2 * 512 : mtiles * nchunks * k * 512;
+}
+
+int voc_pack(const float* w, float* packed, int Cin, int Cout, int k, int u, hipStream_t s) {
+    T2_TRY_RC(voc_shape_check("vocoder pack", Cin, Cout, k, 1, u));
+    T2_REQUIRE(w && packed, "vocoder pack: null pointer");
+    const size_t total = voc_packed_floats(Cin, Cout, k, u);
+    hipLaunchKernelGGL(voc_pack_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, w, packed, Cin, Cout, k, u != 0, u ? u : 1,
+                       u ? (k - u) / 2 : 0, (Cout + 31) / 32, (Cin + kVocCK - 1) / kVocCK, u ? 2 : k, total);
+    T2_LAUNCH_CHECK();
+    return 0;
+}
+
+int voc_conv(const VocConv& a, hipStream_t s) {
+    const char* who = a.u ? "vocoder conv_transpose1d" : "vocoder conv1d";
+    T2_TRY_RC(voc_shape_check(who, a.Cin, a.Cout, a.k, a.u ? 1 : a.d, a.u));
+    T2_REQUIRE(a.B >= 1 && a.B <= 65535, "%s: B=%d outside 1..65535", who, a.B);
+    T2_REQUIRE(a.L >= 1, "%s: L=%ld must be at least 1", who, a.L);
+    T2_REQUIRE(a.L <= (long)INT32_MAX / 2, "%s: L=%ld exceeds the limit of %d samples per row", who, a.L, INT32_MAX / 2);
+    T2_REQUIRE(a.x && a.packed && a.y, "%s: null pointer", who);
+    T2_REQUIRE(!(a.u && (a.res || a.accumulate)), "%s: residual / accumulate are Conv1d fusions", who);
+    VocGemm p;
+    p.x = a.x; p.wp = a.packed; p.bias = a.bias; p.res = a.res; p.y = a.y;
+    p.Cin = a.Cin; p.Cout = a.Cout; p.Lin = (int)a.L;
+    p.transposed = a.u != 0; p.u = a.u ? a.u : 1; p.ostride = p.u;
+    p.taps = a.u ? 2 : a.k; p.d = a.u ? 1 : a.d; p.pad = a.u ? (a.k - a.u) / 2 : (a.k * a.d - a.d) / 2;
+    p.halo_lo = a.u ? 1 : p.pad; p.sw = kVocTT + 2 * p.halo_lo;
+    p.mtiles = (a.Cout + 31) / 32; p.nchunks = (a.Cin + kVocCK - 1) / kVocCK;
+    p.slope = a.slope; p.scale = a.scale; p.accumulate = a.accumulate;
+    T2_REQUIRE(p.sw <= kVocStride, "%s: halo %d does not fit the slab", who, p.halo_lo);
+    const int wm = p.mtiles >= 4 ? 4 : (p.mtiles >= 2 ? 2 : 1);
+    const long tiles = (a.L + kVocTT - 1) / kVocTT;
+    const int mblocks = (p.mtiles + wm - 1) / wm;
+    dim3 grid((unsigned)tiles, (unsigned)(mblocks * p.u), (unsigned)a.B);
+    if (wm == 4) hipLaunchKernelGGL(voc_gemm_kernel<4>, grid, dim3(512), 0, s, p);
+    else if (wm == 2) hipLaunchKernelGGL(voc_gemm_kernel<2>, grid, dim3(256), 0, s, p);
+    else hipLaunchKernelGGL(voc_gemm_kernel<1>, grid, dim3(128), 0, s, p);
+    T2_LAUNCH_CHECK();
+    return 0;
+}
+
+// ------------------------------------------------------------------------------------------------------------------
+// the generator
+// ------------------------------------------------------------------------------------------------------------------
+static size_t round4(size_t n) { return (n + 3) / 4 * 4; }
+
+int hifigan_layers(const HifiganConfig& c, std::vector<HifiganLayer>* out, size_t* packed_floats) {
+    T2_REQUIRE(c.resblock == 1 || c.resblock == 2, "hifigan: resblock \"%d\" is not \"1\" or \"2\"", c.resblock);
+    T2_REQUIRE(c.n_mel == 80, "hifigan: %d mel channels, conv_pre takes 80", c.n_mel);
+    T2_REQUIRE(c.num_upsamples >= 1 && c.num_upsamples <= kHifiganMaxUps, "hifigan: %d upsampling stages outside 1..%d", c.num_upsamples, kHifiganMaxUps);
+    T2_REQUIRE(c.num_kernels >= 1 && c.num_kernels <= kHifiganMaxKernels, "hifigan: %d resblock kernels outside 1..%d", c.num_kernels, kHifiganMaxKernels);
+    const int want_d = c.resblock == 1 ? 3 : 2;
+    T2_REQUIRE(c.num_dilations == want_d, "hifigan: %d dilations per resblock, ResBlock%d takes %d", c.num_dilations, c.resblock, want_d);
+    const int c0 = c.upsample_initial_channel;
+    T2_REQUIRE(c0 >= 8 && c0 <= 512 && c0 % ((1 << c.num_upsamples) * 8) == 0,
+               "hifigan: upsample_initial_channel=%d must be at most 512 and leave a multiple of 8 channels after %d halvings", c0, c.num_upsamples);
+    std::vector<HifiganLayer> L;
+    size_t off = 0;
+    auto add = [&](int kind, int cin, int cout, int k, int d, int u) -> int {
+        if (kind != 2) T2_TRY_RC(voc_shape_check("hifigan", cin, cout, k, d, u));
+        HifiganLayer l{kind, cin, cout, k, d, u, 0, 0};
+        l.w_off = off; off += kind == 2 ? round4((size_t)cin * k) : voc_packed_floats(cin, cout, k, u);
+        l.b_off = off; off += round4(cout);
+        L.push_back(l);
+        return 0;
+    };
+    T2_TRY_RC(add(0, c.n_mel, c0, 7, 1, 0));
+    for (int i = 0; i < c.num_upsamples; ++i) T2_TRY_RC(add(1, c0 >> i, c0 >> (i + 1), c.upsample_kernel_sizes[i], 1, c.upsample_rates[i]));
+    for (int i = 0; i < c.num_upsamples; ++i) {
+        const int ch = c0 >> (i + 1);
+        for (int j = 0; j < c.num_kernels; ++j) {
+            const int k = c.resblock_kernel_sizes[j];
+            for (int m = 0; m < c.num_dilations; ++m) T2_TRY_RC(add(0, ch, ch, k, c.resblock_dilation_sizes[j][m], 0));
+            if (c.resblock == 1) for (int m = 0; m < 3; ++m) T2_TRY_RC(add(0, ch, ch, k, 1, 0));
+        }
+    }
+    T2_TRY_RC(add(2, c0 >> c.num_upsamples, 1, kVocPostK, 1, 0));
+    if (out) *out = L;
+    if (packed_floats) *packed_floats = off;
+    return 0;
+}
+
+int hifigan_plan(const HifiganConfig& c, int B, int T, HifiganPlan* out) {
+    T2_REQUIRE(out, "hifigan: null plan");
+    std::vector<HifiganLayer> L;
+    size_t packed = 0;
+    T2_TRY_RC(hifigan_layers(c, &L, &packed));
+    T2_REQUIRE(B >= 1 && B <= 65535, "hifigan: B=%d outside 1..65535", B);
+    T2_REQUIRE(T >= 1, "hifigan: T=%d frames, must be at least 1", T);
+    long len = T;
+    size_t buf = (size_t)c.upsample_initial_channel * T;
+    for (int i = 0; i < c.num_upsamples; ++i) {
+        len *= c.upsample_rates[i];
+        T2_REQUIRE(len <= (long)INT32_MAX / 2, "hifigan: %ld samples after stage %d exceed the limit of %d per row", len, i, INT32_MAX / 2);
+        buf = std::max(buf, (size_t)(c.upsample_initial_channel >> (i + 1)) * len);
+    }
+    out->out_len = len;
+    out->buf_floats = round4(buf * B);
+    out->workspace_bytes = 5 * out->buf_floats * sizeof(float);      // XS, X, T, P, Q of the widest stage
+    out->packed_bytes = packed * sizeof(float);
+    out->n_layers = (int)L.size();
+    return 0;
+}
+
+int hifigan_pack(const HifiganConfig& c, const float* const* weights, const float* const* biases, int n_layers, float* packed, hipStream_t s) {
+    std::vector<HifiganLayer> L;
+    T2_TRY_RC(hifigan_layers(c, &L, nullptr));
+    T2_REQUIRE(weights && biases && packed, "hifigan_pack: null pointer");
+    T2_REQUIRE(n_layers == (int)L.size(), "hifigan_pack: %d layers given, the configuration has %d", n_layers, (int)L.size());
+    for (int i = 0; i < n_layers; ++i) {
+        const HifiganLayer& l = L[i];
+        T2_REQUIRE(weights[i] && biases[i], "hifigan_pack: layer %d has a null weight or bias", i);
+        if (l.kind == 2) T2_CHECK_HIP(hipMemcpyAsync(packed + l.w_off, weights[i], (size_t)l.cin * l.k * sizeof(float), hipMemcpyDeviceToDevice, s));
+        else T2_TRY_RC(voc_pack(weights[i], packed + l.w_off, l.cin, l.cout, l.k, l.u, s));
+        T2_CHECK_HIP(hipMemcpyAsync(packed + l.b_off, biases[i], (size_t)l.cout * sizeof(float), hipMemcpyDeviceToDevice, s));
+    }
+    return 0;
+}
+
+int hifigan_forward(const HifiganConfig& c, const HifiganFwd& a, hipStream_t s) {
+    std::vector<HifiganLayer> L;
+    HifiganPlan pl;
+    T2_TRY_RC(hifigan_layers(c, &L, nullptr));
+    T2_REQUIRE(a.n_mel == c.n_mel, "hifigan_forward: the mel has %d channels, the generator takes %d", a.n_mel, c.n_mel);
+    T2_TRY_RC(hifigan_plan(c, a.B, a.T, &pl));
+    T2_REQUIRE(a.packed && a.mel && a.workspace && a.audio, "hifigan_forward: null pointer");
+    float* XS = a.workspace; float* X = XS + pl.buf_floats; float* Tb = X + pl.buf_floats; float* P = Tb + pl.buf_floats; float* Q = P + pl.buf_floats;
+    const float kSlope = 0.1f;                                       // LRELU_SLOPE, hifigan_model.py:8
+    auto run = [&](const HifiganLayer& l, const float* x, float* y, long len, float slope, const float* res, int accumulate, float scale) {
+        return voc_conv(VocConv{a.B, l.cin, l.cout, len, l.k, l.d, l.u, x, a.packed + l.w_off, a.packed + l.b_off, res, y, slope, accumulate, scale}, s);
+    };
+    size_t li = 0;
+    long len = a.T;
+    T2_TRY_RC(run(L[li++], a.mel, XS, len, 1.f, nullptr, 0, 1.f));                     // conv_pre: no activation in front
+    size_t rb = 1 + c.num_upsamples;                                                   // first resblock layer
+    for (int i = 0; i < c.num_upsamples; ++i) {
+        T2_TRY_RC(run(L[li++], XS, X, len, kSlope, nullptr, 0, 1.f));                  // x = ups[i](leaky_relu(x))
+        len *= c.upsample_rates[i];
+        for (int j = 0; j < c.num_kernels; ++j) {
+            // xs = r0; xs += r1; ...; x = xs / num_kernels: the last conv of block j adds into XS, the last block scales
+            const int acc = j > 0;
+            const float scale = j == c.num_kernels - 1 ? 1.f / (float)c.num_kernels : 1.f;
+            const float* cur = X;
+            float* pp[2] = {P, Q};
+            for (int m = 0; m < c.num_dilations; ++m) {
+                const bool last = m == c.num_dilations - 1;
+                float* dst = last ? XS : pp[m & 1];
+                if (c.resblock == 1) {
+                    T2_TRY_RC(run(L[rb + m], cur, Tb, len, kSlope, nullptr, 0, 1.f));                                     // c1(leaky_relu(x))
+                    T2_TRY_RC(run(L[rb + 3 + m], Tb, dst, len, kSlope, cur, last ? acc : 0, last ? scale : 1.f));        // c2(leaky_relu(xt)) + x
+                } else {
+                    T2_TRY_RC(run(L[rb + m], cur, dst, len, kSlope, cur, last ? acc : 0, last ? scale : 1.f));           // c(leaky_relu(x)) + x
+                }
+                cur = dst;
+            }
+            rb += c.resblock == 1 ? 6 : 2;
+        }
+    }
+    const HifiganLayer& post = L.back();
+    T2_REQUIRE(rb + 1 == L.size(), "hifigan_forward: layer table out of step");
+    // F.leaky_relu(x) in front of conv_post is torch's default slope 0.01, not LRELU_SLOPE (hifigan_model.py:112)
+    dim3 grid((unsigned)((len + 255) / 256), (unsigned)a.B);
+    hipLaunchKernelGGL(voc_post_kernel, grid, dim3(256), (size_t)post.cin * kVocPostK * sizeof(float), s, XS, a.packed + post.w_off,
+                       a.packed + post.b_off, a.audio, a.pre_tanh, post.cin, len, 0.01f);
+    T2_LAUNCH_CHECK();
+    return 0;
+}
+
+}  // namespace t2

@@ -1,0 +1,205 @@
+"""Drop-in for the reference's ``hifigan_infer.hifigan_model.Generator`` (hifigan_model.py:75-124) on the MI355X.
+
+The modules below only hold parameters, under the names and shapes the reference's checkpoints use; ``Generator.forward``
+hands the folded weights to the HIP library (csrc/vocoder.hip) once, packed into the order its kernels read, and then
+runs the whole generator through ``t2_hifigan_forward``.  So the reference's three lines work verbatim::
+
+    generator = Generator(h)
+    generator.load_state_dict(state_dict_g['generator'])
+    generator.eval(); generator.remove_weight_norm()
+    audio = generator(mel)            # mel [B, 80, T] fp32 on the GPU -> [B, 1, T * prod(upsample_rates)]
+
+Inference only and always fp32 (``set_precision`` does not reach the vocoder); no CPU path; no discriminators."""
+from __future__ import annotations
+
+import ctypes as C
+import math
+
+import torch
+from torch import nn
+
+from .. import _lib as L
+from .hifigan_utils import get_padding
+
+LRELU_SLOPE = 0.1
+
+
+class _WNConv(nn.Module):
+    """Parameters of a weight-normed Conv1d / ConvTranspose1d as torch.nn.utils.weight_norm leaves them: ``bias``,
+    ``weight_g`` [shape[0], 1, 1], ``weight_v``; after remove_weight_norm(): ``bias``, ``weight``.  Conv1d weights are
+    [Cout, Cin, k], ConvTranspose1d weights [Cin, Cout, k], so the norm runs over dim 0 = the input channels there."""
+
+    def __init__(self, cin, cout, k, transposed=False, dilation=1, stride=1, std=0.01):
+        super().__init__()
+        self.in_channels, self.out_channels, self.kernel_size = cin, cout, k
+        self.transposed, self.dilation, self.stride = transposed, dilation, stride
+        shape = (cin, cout, k) if transposed else (cout, cin, k)
+        fan_in = shape[1] * k
+        v = torch.empty(shape)
+        if std is None:                                  # conv_pre keeps torch's default initialisation
+            nn.init.kaiming_uniform_(v, a=math.sqrt(5))
+        else:                                            # init_weights, hifigan_utils.py:22-25
+            v.normal_(0.0, std)
+        bound = 1.0 / math.sqrt(fan_in)
+        self.bias = nn.Parameter(torch.empty(cout).uniform_(-bound, bound))
+        self.weight_g = nn.Parameter(v.flatten(1).norm(dim=1).view(-1, 1, 1))
+        self.weight_v = nn.Parameter(v)
+
+    @property
+    def weight_normed(self) -> bool:
+        return "weight_g" in self._parameters
+
+    def folded_weight(self) -> torch.Tensor:
+        """g * v / ||v|| over dim 0, as weight_norm computes it; the plain weight once the norm is removed."""
+        if self.weight_normed:
+            return torch._weight_norm(self.weight_v.detach(), self.weight_g.detach(), 0)
+        return self.weight.detach()
+
+    def remove_weight_norm(self):
+        if not self.weight_normed:
+            raise ValueError("weight_norm of 'weight' not found in {}".format(self))
+        w = self.folded_weight()
+        del self._parameters["weight_g"], self._parameters["weight_v"]
+        self.weight = nn.Parameter(w)
+
+    def forward(self, x):
+        raise RuntimeError("this module only holds parameters: Generator.forward runs the layers in HIP")
+
+
+def _resconv(channels, k, d):
+    assert get_padding(k, d) * 2 == k * d - d
+    return _WNConv(channels, channels, k, dilation=d)
+
+
+class ResBlock1(nn.Module):
+    """Parameters of hifigan_model.py:11-33."""
+
+    def __init__(self, h, channels, kernel_size=3, dilation=(1, 3, 5)):
+        super().__init__()
+        self.h = h
+        self.convs1 = nn.ModuleList([_resconv(channels, kernel_size, d) for d in dilation])
+        self.convs2 = nn.ModuleList([_resconv(channels, kernel_size, 1) for _ in dilation])
+
+    def layers(self):
+        return list(self.convs1) + list(self.convs2)
+
+    def remove_weight_norm(self):
+        for l in self.layers():
+            l.remove_weight_norm()
+
+
+class ResBlock2(nn.Module):
+    """Parameters of hifigan_model.py:51-61."""
+
+    def __init__(self, h, channels, kernel_size=3, dilation=(1, 3)):
+        super().__init__()
+        self.h = h
+        self.convs = nn.ModuleList([_resconv(channels, kernel_size, d) for d in dilation])
+
+    def layers(self):
+        return list(self.convs)
+
+    def remove_weight_norm(self):
+        for l in self.layers():
+            l.remove_weight_norm()
+
+
+class Generator(nn.Module):
+    def __init__(self, h):
+        super().__init__()
+        self.h = h
+        self.num_kernels = len(h.resblock_kernel_sizes)
+        self.num_upsamples = len(h.upsample_rates)
+        self._cfg = L.hifigan_config(h)
+        L.hifigan_plan(self._cfg, 1, 1)                  # refuses an unsupported configuration here, by name
+        c0 = h.upsample_initial_channel
+        self.conv_pre = _WNConv(80, c0, 7, std=None)
+        resblock = ResBlock1 if str(h.resblock) == "1" else ResBlock2
+        self.ups = nn.ModuleList()
+        for i, (u, k) in enumerate(zip(h.upsample_rates, h.upsample_kernel_sizes)):
+            self.ups.append(_WNConv(c0 // (2 ** i), c0 // (2 ** (i + 1)), k, transposed=True, stride=u))
+        self.resblocks = nn.ModuleList()
+        for i in range(len(self.ups)):
+            ch = c0 // (2 ** (i + 1))
+            for k, d in zip(h.resblock_kernel_sizes, h.resblock_dilation_sizes):
+                self.resblocks.append(resblock(h, ch, k, d))
+        self.conv_post = _WNConv(ch, 1, 7)
+        self.upsample_factor = math.prod(int(u) for u in h.upsample_rates)
+        self._packed = None
+        self._packed_key = None
+
+    # ---- the order t2_hifigan_pack takes the layers in: the order of the state dict
+    def _layers(self):
+        out = [self.conv_pre] + list(self.ups)
+        for rb in self.resblocks:
+            out += rb.layers()
+        return out + [self.conv_post]
+
+    def remove_weight_norm(self):
+        for l in self.ups:
+            l.remove_weight_norm()
+        for l in self.resblocks:
+            l.remove_weight_norm()
+        self.conv_pre.remove_weight_norm()
+        self.conv_post.remove_weight_norm()
+        self._packed = None
+
+    def load_state_dict(self, *args, **kwargs):
+        out = super().load_state_dict(*args, **kwargs)
+        self._packed = None
+        return out
+
+    def _apply(self, fn, *args, **kwargs):               # .to() / .cuda() / .float()
+        out = super()._apply(fn, *args, **kwargs)
+        self._packed = None
+        return out
+
+    def _key(self):
+        return tuple((p.data_ptr(), p._version) for p in self.parameters())
+
+    def repack(self):
+        """Fold and pack the weights again.  forward() does this by itself after load_state_dict, remove_weight_norm, .to()
+        and in-place updates that autograd sees; call it after editing parameters behind autograd's back (``.data``)."""
+        layers = self._layers()
+        dev = layers[0].bias.device
+        if dev.type != "cuda":
+            raise RuntimeError("hifigan Generator: the parameters must live on the GPU (the product path has no CPU fallback)")
+        plan = L.hifigan_plan(self._cfg, 1, 1)
+        with torch.no_grad():
+            ws = [l.folded_weight().to(torch.float32).contiguous() for l in layers]
+            bs = [l.bias.detach().to(torch.float32).contiguous() for l in layers]
+        packed = torch.empty(plan.packed_bytes // 4, device=dev, dtype=torch.float32)
+        n = len(layers)
+        wp = (C.c_void_p * n)(*[L.ptr(w) for w in ws])
+        bp = (C.c_void_p * n)(*[L.ptr(b) for b in bs])
+        with torch.cuda.device(dev):
+            L.check(L.lib().t2_hifigan_pack(C.byref(self._cfg), wp, bp, n, L.ptr(packed), L.stream()))
+        self._packed, self._packed_key = packed, self._key()
+        return self
+
+    def forward(self, x, return_pre_tanh=False):
+        """mel [B, 80, T], fp32, on the GPU -> audio [B, 1, T * prod(upsample_rates)].  return_pre_tanh=True (a debug output,
+        used by the tests) also returns conv_post's output before the tanh, same shape."""
+        if not x.is_cuda:
+            raise RuntimeError("hifigan Generator: the mel must live on the GPU (the product path has no CPU fallback)")
+        if torch.is_grad_enabled() and x.requires_grad:
+            raise RuntimeError("hifigan Generator is inference only: the input requires grad and grad mode is on; "
+                               "call it under torch.no_grad() or detach the mel")
+        if x.dim() != 3:
+            raise RuntimeError(f"hifigan Generator: expected a mel of shape [B, 80, T], got {tuple(x.shape)}")
+        if x.dtype != torch.float32:
+            raise RuntimeError(f"hifigan Generator: the mel must be float32, got {x.dtype}")
+        if self._packed is None or self._packed.device != x.device or self._packed_key != self._key():
+            self.repack()
+            if self._packed.device != x.device:
+                raise RuntimeError(f"hifigan Generator: the mel is on {x.device}, the parameters on {self._packed.device}")
+        B, n_mel, T = x.shape
+        mel = x.detach().contiguous()
+        plan = L.hifigan_plan(self._cfg, B, T)
+        with torch.cuda.device(x.device):
+            ws = torch.empty(plan.workspace_bytes // 4, device=x.device, dtype=torch.float32)
+            audio = torch.empty(B, 1, plan.out_len, device=x.device, dtype=torch.float32)
+            pre = torch.empty_like(audio) if return_pre_tanh else None
+            a = L.HifiganFwdArgs(B, T, n_mel, L.ptr(self._packed), L.ptr(mel), L.ptr(ws), L.ptr(audio), L.ptr(pre))
+            L.check(L.lib().t2_hifigan_forward(C.byref(self._cfg), C.byref(a), L.stream()))
+        return (audio, pre) if return_pre_tanh else audio
