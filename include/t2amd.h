@@ -589,7 +589,8 @@ int t2_adam_chunks(long numel);
 int t2_adam_step(const t2_adam_tensor* table, int n_tensors, int n_chunks, float* partial, float* norm_out, float max_norm,
                  float lr, float beta1, float beta2, float eps, float weight_decay, int step, void* stream);
 int t2_adam_norm(const t2_adam_tensor* table, int n_tensors, int n_chunks, float* partial, float* norm_out, float max_norm, void* stream);
-/* norm_out: FOUR floats — [0] total gradient norm, [1] clip coefficient, [2] 1.0 when the update was skipped because the
+/* norm_out: FOUR floats — [0] total gradient norm, [1] clip coefficient (NaN when the norm is NaN, as clip_grad_norm_
+ * makes it: every stepped parameter then turns NaN; 0 when the norm is infinite), [2] 1.0 when the update was skipped because the
  * device's sticky status word (t2_chain_status) was set, [3] reserved. */
 
 /* In-situ kernel timing for bench.py's roofline figures: after t2_prof_enable(n) the decoder

@@ -45,7 +45,7 @@ __global__ __launch_bounds__(256) void sumsq_kernel(const AdamTensor* __restrict
     if (threadIdx.x == 0) partial[chunk] = (red[0] + red[1]) + (red[2] + red[3]);
 }
 
-// out[0] = total norm, out[1] = clip coefficient = min(1, max_norm / (norm + 1e-6))   (max_norm <= 0: no clipping),
+// out[0] = total norm, out[1] = clip coefficient = min(1, max_norm / (norm + 1e-6))   (max_norm <= 0: no clipping; NaN when the norm is NaN),
 // out[2] = 1 when the update must be skipped
 __global__ __launch_bounds__(1024) void norm_finish_kernel(const float* __restrict__ partial, int n, float max_norm, float* __restrict__ out,
                                                            const unsigned* __restrict__ sticky) {
@@ -61,7 +61,9 @@ __global__ __launch_bounds__(1024) void norm_finish_kernel(const float* __restri
         for (int i = 0; i < 16; ++i) tot += red[i];
         const float norm = (float)sqrt(tot);
         out[0] = norm;
-        out[1] = max_norm > 0.f ? fminf(1.0f, max_norm / (norm + 1e-6f)) : 1.0f;
+        // a NaN norm gives a NaN coefficient (fminf would drop it): every stepped parameter turns NaN, as after clip_grad_norm_
+        const float c = max_norm / (norm + 1e-6f);
+        out[1] = max_norm > 0.f ? (c < 1.0f ? c : (c != c ? c : 1.0f)) : 1.0f;
         // an aborted persistent kernel (chain_common.h) left invalid gradients behind: no parameter may move
         out[2] = (sticky && __hip_atomic_load(sticky, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) != 0u) ? 1.0f : 0.0f;
     }

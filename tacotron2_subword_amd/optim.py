@@ -8,7 +8,9 @@ optimizer states interchange with torch.optim.Adam and with the reference's chec
     grad_norm = opt.step(max_norm=hparams.grad_clip_thresh)     # returns the total gradient norm (device scalar)
 
 Differences from clip_grad_norm_ + Adam.step: gradients are not rescaled in place (the clip coefficient is applied
-while they are read); parameters without a gradient are skipped, as in torch."""
+while they are read); parameters without a gradient are skipped, as in torch.  A NaN gradient gives a NaN norm and a NaN
+clip coefficient (`last_clip`), so every stepped parameter turns NaN, as after clip_grad_norm_; an Inf gradient gives
+coefficient 0."""
 import ctypes as C
 
 import torch
@@ -32,6 +34,7 @@ class FusedAdam(torch.optim.Adam):
         self._dev = None
         self._partial = None
         self.last_norm = None
+        self.last_clip = None          # the clip coefficient the last step applied (device scalar, norm_out[1])
 
     def _table(self, nbytes):
         """Next pinned table of at least nbytes; waits (host side) for the upload that last used it."""
@@ -78,7 +81,8 @@ class FusedAdam(torch.optim.Adam):
         # a parameter or a moment replaced by load_state_dict invalidates the cache (object identity), and so does storage
         # that moved under the same object (p.data = ..., model.float()/.to()): the cached addresses are compared with
         # the live ones every step
-        if any(id(p) != a or id(self.state[p]["exp_avg"]) != b for p, (a, b) in zip(ps, c["ids"])) or \
+        # (.get: a state emptied by a partial load_state_dict has no moments; it invalidates like a replaced one)
+        if any(id(p) != a or id(self.state[p].get("exp_avg")) != b for p, (a, b) in zip(ps, c["ids"])) or \
                 [p.data_ptr() for p in ps] != c["rows"][:, 0].tolist() or \
                 [self.state[p]["exp_avg"].data_ptr() for p in ps] != c["rows"][:, 2].tolist() or \
                 [self.state[p]["exp_avg_sq"].data_ptr() for p in ps] != c["rows"][:, 3].tolist():
@@ -106,7 +110,7 @@ class FusedAdam(torch.optim.Adam):
         L.check(lib.t2_adam_step(self._dev.data_ptr(), n, c["chunks"], self._partial.data_ptr(), norm_out.data_ptr(),
                                  float(max_norm) if max_norm else 0.0, float(group["lr"]), float(b1), float(b2),
                                  float(group["eps"]), float(group["weight_decay"]), c["step"], L.stream()))
-        self.last_norm = norm_out[0]
+        self.last_norm, self.last_clip = norm_out[0], norm_out[1]
         return self.last_norm
 
     @torch.no_grad()
@@ -124,6 +128,7 @@ class FusedAdam(torch.optim.Adam):
         fast = self._fast_step(lib, max_norm)
         if fast is not None:
             return loss if closure is not None else fast
+        self._fast = None      # the general path moves step counts behind a cached table's back: the fast path rebuilds from the states
         # One gradient norm over ALL parameter groups (clip_grad_norm_(model.parameters()), train.py:322-323).  Rows are
         # grouped by (hyper-parameters, step count): torch.optim.Adam corrects the bias with each parameter's own step,
         # which differs between parameters once one of them starts receiving gradients later or a state is partly restored.
@@ -142,7 +147,7 @@ class FusedAdam(torch.optim.Adam):
                 st["step"] += 1
                 batches.setdefault((gi, int(st["step"].item())), []).append(p)
         if not batches:
-            self.last_norm = None
+            self.last_norm = self.last_clip = None
             return loss if closure is not None else None
         order = sorted(batches)
         rows, spans, chunk = [], [], 0
@@ -180,5 +185,5 @@ class FusedAdam(torch.optim.Adam):
             L.check(lib.t2_adam_step(self._dev.data_ptr() + first * 48, cnt, nchunks, self._partial.data_ptr(), norm_out.data_ptr(),
                                      (float(max_norm) if max_norm else 0.0) if single else -1.0, float(group["lr"]), float(b1), float(b2),
                                      float(group["eps"]), float(group["weight_decay"]), step, L.stream()))
-        self.last_norm = norm_out[0]
+        self.last_norm, self.last_clip = norm_out[0], norm_out[1]
         return loss if closure is not None else self.last_norm
