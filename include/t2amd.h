@@ -575,6 +575,65 @@ size_t t2_vocoder_packed_floats(int Cin, int Cout, int k, int u);
 int t2_vocoder_conv1d(const t2_vocoder_conv_args* a, void* stream);              /* a->u must be 0 */
 int t2_vocoder_conv_transpose1d(const t2_vocoder_conv_args* a, void* stream);    /* a->d, residual, accumulate unused */
 
+/* ---- STFT analysis / synthesis and vocoder bias removal ---------------------------------------------
+ * Replaces the reference's stft.py: STFT.transform (:77-105), STFT.inverse (:107-136) and STFT.forward (:138-141), with
+ * audio_processing.py: window_sumsquare (:7-56), and the element-wise middle of bias_remover.py:
+ * hifiganBiasRemover.forward (:31-36).  torch's [B, C, frames] layout, time contiguous; always exact fp32 on the matrix
+ * cores, whatever t2_set_precision says.  No atomics, a fixed order for every sum: bit-identical from run to run and for
+ * an item alone or inside a batch.  Ordinary launches on `stream`.
+ * Supported: even filter_length N up to 4096, hop_length dividing N with N / hop <= 64.  Everything else is refused with
+ * the offending values in t2_last_error. */
+#define T2_STFT_FRAME_TILE 32 /* frames (analysis) / hop-sized output blocks (synthesis) per workgroup (tests probe its edges) */
+#define T2_STFT_POLAR 0
+#define T2_STFT_DENOISE 1
+typedef struct t2_stft_plan_info {
+    int bins;                /* N/2 + 1 */
+    int overlap;             /* N / hop */
+    int frame_tile;          /* T2_STFT_FRAME_TILE */
+    int bin_tile;            /* 16: bins per 32-row basis tile (real and imaginary rows interleaved) */
+    long out_len;            /* samples per item the synthesis writes: hop * (nf - 1) */
+    size_t fwd_floats;       /* packed forward basis */
+    size_t inv_floats;       /* packed inverse basis */
+    size_t wsq_floats;       /* squared window: N doubles */
+    size_t packed_bytes;     /* all three, in that order */
+} t2_stft_plan_info;
+/* Pure host call (no device).  Fails, with the values in the message, for odd N, N % hop != 0, N > 4096, N / hop > 64
+ * and nf < 1. */
+int t2_stft_plan(int N, int hop, int nf, t2_stft_plan_info* out);
+/* forward_basis, inverse_basis: the module's windowed buffers, [2*(N/2+1)][N] (stft.py:74-75).  window_sq: the squared
+ * window, centre-padded to N, in fp64 as window_sumsquare forms it (audio_processing.py:48-50; fp64 because numpy adds
+ * it to the fp32 envelope in fp64); NULL for STFT(window=None).  All device pointers.  Writes `packed` (packed_bytes);
+ * done once per module, not per call. */
+int t2_stft_pack(int N, int hop, const float* forward_basis, const float* inverse_basis, const double* window_sq, float* packed, void* stream);
+/* x [B, n], n > N/2, reflect-padded by N/2 per side in the loader (stft.py:84-89) -> [B, N/2+1, 1 + n/hop] each:
+ * re, im = the conv1d of stft.py:91-99; mag = sqrt(re^2 + im^2), phase = atan2(im, re) (stft.py:101-103).  Every output
+ * is nullable; at least one is given.
+ * Accuracy: each element is a sequential fp32 chain of N fused multiply-adds.  Against fp64 it stays within 1e-6 * S
+ * (S = sum |x_k| |basis_k|) when the products mix signs; that is a statistical bound, not a worst case.  A chain of one-signed
+ * products -- the bin of a strong stationary tone, the DC bin under an offset -- errs by about 0.6 * sqrt(N) * 2^-24 * S
+ * (0.9e-6 * S seen at N = 1024) and can exceed it; the worst case is N * 2^-24 * S. */
+typedef struct t2_stft_analysis_args {
+    int B, N, hop; long n;
+    const float* x; const float* packed;
+    float* re; float* im; float* mag; float* phase;
+} t2_stft_analysis_args;
+int t2_stft_analysis(const t2_stft_analysis_args* a, void* stream);
+/* a, b [B, N/2+1, nf] -> y [B, 1, hop*(nf-1)]: conv_transpose1d with the inverse basis as an overlap-add GEMM, the
+ * envelope division, the N/hop scale and the trim of stft.py:111-134.
+ * mode T2_STFT_POLAR: a = magnitude, b = phase, X = (a cos b, a sin b) (stft.py:108-109).
+ * mode T2_STFT_DENOISE: a = re, b = im of t2_stft_analysis; X = g * (re, im), g = max(|z| - strength*bias[k], 0) / |z|
+ *   (0 where |z| = 0): bias_remover.py:32-35 without the atan2 and the sincos.  bias [N/2+1].
+ * windowed = 0: STFT(window=None), no envelope and no scale (stft.py:117); y is then the trimmed overlap-add sum itself.
+ * Precondition, not checked: windowed != 0 needs tables packed with a window_sq.  Tables packed with window_sq == NULL hold
+ * an all-zero envelope, so the division would be skipped and the N/hop scale still applied: call with windowed = 0 then. */
+typedef struct t2_stft_synthesis_args {
+    int B, N, hop, nf, mode, windowed;
+    const float* a; const float* b; const float* bias; float strength;
+    const float* packed;
+    float* y;
+} t2_stft_synthesis_args;
+int t2_stft_synthesis(const t2_stft_synthesis_args* a, void* stream);
+
 /* Gradient-norm clipping + Adam over a list of fp32 tensors — replaces torch.nn.utils.clip_grad_norm_ +
  * torch.optim.Adam.step of the training loop (train.py:322-330; Adam with weight decay added to the gradient).
  * `table` is a DEVICE array of n_tensors rows; row i covers chunks [first_chunk, first_chunk + t2_adam_chunks(numel))

@@ -218,6 +218,26 @@ class VocoderConvArgs(C.Structure):
 
 VOCODER_TIME_TILE = 128      # include/t2amd.h T2_VOCODER_TIME_TILE
 
+
+class StftPlanInfo(C.Structure):
+    _fields_ = [("bins", C.c_int), ("overlap", C.c_int), ("frame_tile", C.c_int), ("bin_tile", C.c_int), ("out_len", C.c_long),
+                ("fwd_floats", C.c_size_t), ("inv_floats", C.c_size_t), ("wsq_floats", C.c_size_t), ("packed_bytes", C.c_size_t)]
+
+
+class StftAnalysisArgs(C.Structure):
+    _fields_ = [("B", C.c_int), ("N", C.c_int), ("hop", C.c_int), ("n", C.c_long), ("x", C.c_void_p), ("packed", C.c_void_p),
+                ("re", C.c_void_p), ("im", C.c_void_p), ("mag", C.c_void_p), ("phase", C.c_void_p)]
+
+
+class StftSynthesisArgs(C.Structure):
+    _fields_ = [("B", C.c_int), ("N", C.c_int), ("hop", C.c_int), ("nf", C.c_int), ("mode", C.c_int), ("windowed", C.c_int),
+                ("a", C.c_void_p), ("b", C.c_void_p), ("bias", C.c_void_p), ("strength", C.c_float),
+                ("packed", C.c_void_p), ("y", C.c_void_p)]
+
+
+STFT_FRAME_TILE = 32         # include/t2amd.h T2_STFT_FRAME_TILE
+STFT_POLAR, STFT_DENOISE = 0, 1
+
 # every symbol include/t2amd.h declares (tests/test_abi.py checks the library exports them all)
 ABI_VERSION = 4      # include/t2amd.h T2_ABI_VERSION: struct sizes below match that header and nothing else
 
@@ -227,7 +247,8 @@ EXPORTS = ["t2_last_error", "t2_version", "t2_chain_status", "t2_chain_status_cl
            "t2_lstm_seq_forward", "t2_lstm_seq_backward", "t2_lstm_seq_chain_ws_floats", "t2_gemm_ex", "t2_prof_gemm", "t2_gemm_plan", "t2_conv_handoff_plan", "t2_colsum", "t2_mask_btc",
            "t2_finalize_bct", "t2_mask_bt", "t2_gemm", "t2_rng_keep_mask", "t2_rng_normal",
            "t2_softdtw_plan", "t2_softdtw_dist", "t2_softdtw_forward", "t2_softdtw_backward", "t2_softdtw_dist_backward",
-           "t2_hifigan_plan", "t2_hifigan_pack", "t2_hifigan_forward", "t2_vocoder_packed_floats", "t2_vocoder_conv1d", "t2_vocoder_conv_transpose1d"]
+           "t2_hifigan_plan", "t2_hifigan_pack", "t2_hifigan_forward", "t2_vocoder_packed_floats", "t2_vocoder_conv1d", "t2_vocoder_conv_transpose1d",
+           "t2_stft_plan", "t2_stft_pack", "t2_stft_analysis", "t2_stft_synthesis"]
 
 _lib = None
 
@@ -289,6 +310,10 @@ def lib() -> C.CDLL:
         L.t2_vocoder_packed_floats.argtypes, L.t2_vocoder_packed_floats.restype = [C.c_int, C.c_int, C.c_int, C.c_int], C.c_size_t
         L.t2_vocoder_conv1d.argtypes = [C.POINTER(VocoderConvArgs), C.c_void_p]
         L.t2_vocoder_conv_transpose1d.argtypes = [C.POINTER(VocoderConvArgs), C.c_void_p]
+        L.t2_stft_plan.argtypes = [C.c_int, C.c_int, C.c_int, C.POINTER(StftPlanInfo)]
+        L.t2_stft_pack.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.t2_stft_analysis.argtypes = [C.POINTER(StftAnalysisArgs), C.c_void_p]
+        L.t2_stft_synthesis.argtypes = [C.POINTER(StftSynthesisArgs), C.c_void_p]
         _lib = L
     return _lib
 
@@ -594,4 +619,12 @@ def hifigan_plan(cfg: HifiganConfig, B: int, T: int) -> HifiganPlanInfo:
     library's message for a configuration it refuses."""
     info = HifiganPlanInfo()
     check(lib().t2_hifigan_plan(C.byref(cfg), B, T, C.byref(info)))
+    return info
+
+
+def stft_plan(N: int, hop: int, nf: int = 1) -> StftPlanInfo:
+    """Tile sizes, packed-table sizes and the synthesis output length (t2_stft_plan: pure host, no device needed); raises with
+    the reason for odd N, N % hop != 0 and sizes the kernels do not take."""
+    info = StftPlanInfo()
+    check(lib().t2_stft_plan(N, hop, nf, C.byref(info)))
     return info

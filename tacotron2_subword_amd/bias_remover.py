@@ -1,0 +1,38 @@
+"""Drop-in for the reference's ``bias_remover.hifiganBiasRemover`` (bias_remover.py:6-36): subtracts the spectrum of what the
+vocoder emits for an all-zero mel from the magnitudes of its output, as inference.py:199-202 does before writing the wav.
+
+``forward`` is two launches of csrc/stft.hip: the analysis kernel writes (re, im), and the synthesis kernel applies
+``clamp(|z| - strength * bias, 0)`` as a gain on (re, im) in its loader, so no magnitude, phase or denoised-magnitude
+tensor exists in between.  ``waveglowBiasRemover`` is not built: WaveGlow stays out of scope."""
+import torch
+
+from . import stft as _stft
+from .stft import STFT
+
+
+class hifiganBiasRemover(torch.nn.Module):
+    """Removes model bias from audio produced with HiFi-GAN.  `model`: any callable mel [1, 80, 88] -> audio [1, 1, T].
+    `device` (an addition; the reference hard-codes .cuda()): "cpu" runs the torch formula, for comparison with the
+    reference on a box without a GPU."""
+
+    def __init__(self, model, filter_length=1024, n_overlap=4, win_length=1024, mode='zeros', device="cuda"):
+        super().__init__()
+        if mode not in ("zeros", "normal"):
+            raise ValueError(f"hifiganBiasRemover: mode {mode!r} is neither 'zeros' nor 'normal'")
+        hop = int(filter_length / n_overlap)
+        self.stft = STFT(filter_length=filter_length, hop_length=hop, win_length=win_length).to(device)
+        mel = (torch.zeros if mode == "zeros" else torch.randn)(1, 80, 88).to(device)
+        with torch.no_grad():
+            spec, _ = self.stft.transform(model(mel).float().squeeze(0))    # what the vocoder emits for that mel: [1, 1, T] -> [1, N/2+1, frames]
+        self.register_buffer("bias_spec", spec[:, :, :1].clone())            # the first frame, [1, N/2+1, 1]
+
+    def forward(self, audio, strength=0.1):
+        """audio [B, T] -> [B, 1, hop * (T // hop)]."""
+        audio = audio.to(self.bias_spec.device).float()
+        if not audio.is_cuda:
+            spec, angles = self.stft.transform(audio)
+            return self.stft.inverse(torch.clamp(spec - self.bias_spec * strength, 0.0), angles)
+        s = self.stft
+        re, im = _stft.analysis(audio, s.tables(), s.filter_length, s.hop_length, want=("re", "im"))
+        return _stft.synthesis(re, im, s.tables(), s.filter_length, s.hop_length, mode=1, bias=self.bias_spec, strength=strength,
+                               windowed=s.window is not None)

@@ -1865,6 +1865,28 @@ int t2_vocoder_conv_transpose1d(const t2_vocoder_conv_args* a, void* stream) {
     return vocoder_layer(a, a->u, stream);
 }
 
+static_assert(T2_STFT_FRAME_TILE == kStftTile, "t2amd.h mirrors the STFT frame tile");
+int t2_stft_plan(int N, int hop, int nf, t2_stft_plan_info* out) {
+    T2_REQUIRE(out, "t2_stft_plan: null pointer");
+    StftPlan p;
+    T2_TRY(stft_plan(N, hop, nf, &p));
+    out->bins = p.cutoff; out->overlap = p.overlap; out->frame_tile = kStftTile; out->bin_tile = 16; out->out_len = p.out_len;
+    out->fwd_floats = p.fwd_floats; out->inv_floats = p.inv_floats; out->wsq_floats = p.wsq_floats;
+    out->packed_bytes = (p.fwd_floats + p.inv_floats + p.wsq_floats) * sizeof(float);
+    return 0;
+}
+int t2_stft_pack(int N, int hop, const float* forward_basis, const float* inverse_basis, const double* window_sq, float* packed, void* stream) {
+    return stft_pack(N, hop, forward_basis, inverse_basis, window_sq, packed, (hipStream_t)stream);
+}
+int t2_stft_analysis(const t2_stft_analysis_args* a, void* stream) {
+    T2_REQUIRE(a, "t2_stft_analysis: null arguments");
+    return stft_analysis(StftAnalysis{a->B, a->N, a->hop, a->n, a->x, a->packed, a->re, a->im, a->mag, a->phase}, (hipStream_t)stream);
+}
+int t2_stft_synthesis(const t2_stft_synthesis_args* a, void* stream) {
+    T2_REQUIRE(a, "t2_stft_synthesis: null arguments");
+    return stft_synthesis(StftSynthesis{a->B, a->N, a->hop, a->nf, a->mode, a->windowed, a->a, a->b, a->bias, a->strength, a->packed, a->y}, (hipStream_t)stream);
+}
+
 int t2_prof_enable(int max_launches) {
     if (max_launches <= 0) { g_prof.on = false; return 0; }
     const size_t need = (size_t)max_launches * 2;

@@ -483,6 +483,24 @@ int hifigan_pack(const HifiganConfig& c, const float* const* weights, const floa
 struct HifiganFwd { int B, T, n_mel; const float* packed; const float* mel; float* workspace; float* audio; float* pre_tanh; };
 int hifigan_forward(const HifiganConfig& c, const HifiganFwd& a, hipStream_t s);
 
+// ------------------------------------------------------------------ STFT analysis / synthesis (stft.hip)
+constexpr int kStftTile = 32;                    // frames (analysis) / hop-blocks q (synthesis) per workgroup
+constexpr int kStftMaxN = 4096;                  // filter_length
+constexpr int kStftMaxOverlap = 64;              // filter_length / hop_length
+// Sizes in floats; the packed buffer is [forward | inverse | window^2 as N doubles].
+struct StftPlan { int cutoff, overlap, bin_tiles, kchunks, col_tiles; long out_len; size_t fwd_floats, inv_floats, wsq_floats; };
+int stft_plan(int N, int hop, int nf, StftPlan* out);   // validates; no device
+// fwd, inv: the windowed bases [2*(N/2+1)][N] (the module's buffers without their middle dimension); wsq: the squared,
+// centre-padded window [N] in fp64, nullable (no window: synthesis must then run with windowed = 0)
+int stft_pack(int N, int hop, const float* fwd, const float* inv, const double* wsq, float* packed, hipStream_t s);
+// x [B, n] -> re, im, mag, phase [B, N/2+1, 1 + n/hop], each nullable
+struct StftAnalysis { int B, N, hop; long n; const float* x; const float* packed; float* re; float* im; float* mag; float* phase; };
+int stft_analysis(const StftAnalysis& a, hipStream_t s);
+// mode 0 (polar): a = magnitude, b = phase;  mode 1 (denoise): a = re, b = im, bias [N/2+1], strength.  a, b [B, N/2+1, nf] ->
+// y [B, 1, hop*(nf-1)].  windowed = 0 skips the envelope division and the N/hop scale (STFT(window=None), stft.py:117).
+struct StftSynthesis { int B, N, hop, nf, mode, windowed; const float* a; const float* b; const float* bias; float strength; const float* packed; float* y; };
+int stft_synthesis(const StftSynthesis& a, hipStream_t s);
+
 // ------------------------------------------------------------------ optimizer (optim.hip)
 struct AdamTensor { float* p; const float* g; float* m; float* v; long numel; int first_chunk; int pad_; };   // 48 bytes, mirrors t2_adam_tensor
 int adam_chunks(long numel);

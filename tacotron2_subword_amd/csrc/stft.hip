@@ -1,0 +1,295 @@
+// STFT analysis and synthesis.  Replaces the reference's stft.py: STFT.transform (:77-105) and STFT.inverse (:107-136) with
+// audio_processing.py: window_sumsquare (:7-56), and the element-wise middle of bias_remover.py: hifiganBiasRemover.forward
+// (:31-36).
+//
+// Tensors keep torch's [B, C, frames] layout with time contiguous.  Arithmetic is exact fp32 on the matrix cores
+// (v_mfma_f32_32x32x2_f32: a k-ordered fmaf chain), whatever t2_set_precision says.  Both kernels are GEMMs of one shape:
+// one operand is a table packed once into the order the lanes consume it (four k-steps per 16-byte load, zero-padded to whole
+// tiles), the other is staged per chunk of 32 k in an LDS slab whose loader does the element-wise work.  A wave owns one
+// 32 x 32 accumulator; the waves of a workgroup share the slab.
+//
+// Analysis:  Y[c][f] = sum_k basis[c][k] * xpad[f*hop + k]  (M = 2*(N/2+1) basis rows, columns = frames, K = N).
+//   The loader reads the waveform itself: xpad[i] = x[reflect(i - N/2)] is index arithmetic, there is no padded copy and no
+//   frame matrix.  A 32-row tile holds 16 bins, real rows and imaginary rows interleaved in groups of 8, so that a lane's
+//   accumulator holds re and im of the same (bin, frame) and the epilogue can write magnitude and phase too.
+// Synthesis: overlap-add as a GEMM, no atomics.  With R = N/hop and output sample t = q*hop + r,
+//   y[q*hop + r] = sum_{j<R} sum_c X[c][q-j] * inv[c][j*hop + r],  X zero outside [0, nf):
+//   rows = q, columns = r, K = R * 2*(N/2+1).  Per chunk of 16 bins the slab holds (re, im) of frames q0-(R-1) .. q0+31 and
+//   every overlap j reads it at a shifted column, so X is formed once per chunk: from (magnitude, phase) with sincosf, or from
+//   (re, im) with the bias remover's gain  g = max(|z| - strength*bias, 0) / |z|.  The epilogue divides by the window
+//   sum-square envelope where it exceeds FLT_MIN, scales by N/hop and writes only the samples the reference keeps.
+// The order of every sum is fixed: same bits from run to run and for an item alone or in a batch.  Offsets are 64-bit.
+#include <cfloat>
+
+#include "kernels.h"
+
+namespace t2 {
+
+constexpr int kStftKC = 32;                                   // k per slab
+constexpr int kStftAnaStride = kStftTile + 1;                 // odd: the loader's lanes run along k, one bank each
+constexpr int kStftSynStride = kStftTile + kStftMaxOverlap + 1;
+static_assert(kStftSynStride >= kStftTile + kStftMaxOverlap - 1, "the slab holds the frames of every overlap");
+
+struct StftAna {
+    const float* x; const float* pf; float* re; float* im; float* mag; float* phase;
+    long n; int nf, N, hop, cutoff, bin_tiles, kchunks;
+};
+
+__global__ void __launch_bounds__(256) stft_analysis_kernel(StftAna p) {
+    __shared__ float slab[kStftKC * kStftAnaStride];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, hk = lane >> 5;
+    const int mt = blockIdx.y * 4 + wave;
+    const bool active = mt < p.bin_tiles;                      // uniform over the wave
+    const int b = blockIdx.z;
+    const long f0 = (long)blockIdx.x * kStftTile;
+    const float* xb = p.x + (size_t)b * p.n;
+    const f32x4* pf = reinterpret_cast<const f32x4*>(p.pf) + (size_t)(active ? mt : 0) * p.kchunks * 256;
+    const int half = p.N / 2;
+    f32x16 acc = {0};
+
+    for (int c = 0; c < p.kchunks; ++c) {
+        if (c) __syncthreads();                                // every wave is done reading the previous slab
+        const int kl = threadIdx.x & 31, k = c * kStftKC + kl;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int fl = (threadIdx.x >> 5) + 8 * i;
+            const long f = f0 + fl;
+            float v = 0.f;
+            if (f < p.nf && k < p.N) {
+                long t = f * p.hop + k - half;                 // reflect padding: n > N/2 keeps both mirrors inside [0, n)
+                if (t < 0) t = -t;
+                else if (t >= p.n) t = 2 * (p.n - 1) - t;
+                v = xb[t];
+            }
+            slab[kl * kStftAnaStride + fl] = v;
+        }
+        __syncthreads();
+        if (active) {
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+                const f32x4 a = pf[(size_t)c * 256 + g * 64 + lane];
+#pragma unroll
+                for (int i = 0; i < 4; ++i)
+                    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[i], slab[(8 * g + 2 * i + hk) * kStftAnaStride + (lane & 31)], acc, 0, 0, 0);
+            }
+        }
+    }
+    if (!active) return;
+    // lane holds frame lane & 31 and tile rows (e&3) + 8*(e>>2) + 4*hk; row r is part (r>>3)&1 of bin 8*(r>>4) + (r&7):
+    // element e (bit 2 clear) is re, e + 4 is im of bin 8*(e>>3) + 4*hk + (e&3)
+    const long f = f0 + (lane & 31);
+    if (f >= p.nf) return;
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int bin = mt * 16 + 8 * h + 4 * hk + i;
+            if (bin >= p.cutoff) continue;
+            const size_t o = ((size_t)b * p.cutoff + bin) * p.nf + f;
+            const float re = acc[8 * h + i], im = acc[8 * h + i + 4];
+            if (p.re) p.re[o] = re;
+            if (p.im) p.im[o] = im;
+            if (p.mag) p.mag[o] = sqrtf(__fadd_rn(__fmul_rn(re, re), __fmul_rn(im, im)));   // torch.sqrt(re**2 + im**2), no contraction
+            if (p.phase) p.phase[o] = atan2f(im, re);
+        }
+    }
+}
+
+struct StftSyn {
+    const float* a; const float* b; const float* bias; const float* pi; const double* wsq; float* y;
+    int nf, N, hop, R, cutoff, nchunks, col_tiles, mode, windowed;
+    long qbase, out_len;
+    float strength, scale;
+};
+
+template <int WN>
+__global__ void __launch_bounds__(WN * 64) stft_synthesis_kernel(StftSyn p) {
+    __shared__ float slab[kStftKC * kStftSynStride];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, hk = lane >> 5;
+    const int ct = blockIdx.y * WN + wave;
+    const bool active = ct < p.col_tiles;                      // uniform over the wave
+    const int bi = blockIdx.z;
+    const long q0 = p.qbase + (long)blockIdx.x * kStftTile;
+    const long fbase = q0 - (p.R - 1);                         // frame of slab column 0
+    const int W = kStftTile + p.R - 1;
+    const float* pa = p.a + (size_t)bi * p.cutoff * p.nf;
+    const float* pb = p.b + (size_t)bi * p.cutoff * p.nf;
+    const f32x4* pi = reinterpret_cast<const f32x4*>(p.pi) + (size_t)(active ? ct : 0) * p.nchunks * p.R * 256;
+    f32x16 acc = {0};
+
+    for (int c = 0; c < p.nchunks; ++c) {
+        if (c) __syncthreads();
+        for (int item = threadIdx.x; item < 16 * W; item += WN * 64) {
+            const int bl = item / W, col = item - bl * W;
+            const int bin = c * 16 + bl;
+            const long f = fbase + col;
+            float xr = 0.f, xi = 0.f;
+            if (bin < p.cutoff && f >= 0 && f < p.nf) {
+                const size_t o = (size_t)bin * p.nf + f;
+                const float u = pa[o], v = pb[o];
+                if (p.mode == 0) {                             // polar: u = magnitude, v = phase
+                    float sn, cs;
+                    sincosf(v, &sn, &cs);
+                    xr = u * cs; xi = u * sn;
+                } else {                                       // denoise: u = re, v = im
+                    const float m = sqrtf(__fadd_rn(__fmul_rn(u, u), __fmul_rn(v, v)));
+                    const float d = fmaxf(__fsub_rn(m, __fmul_rn(p.bias[bin], p.strength)), 0.f);
+                    const float g = m > 0.f ? d / m : 0.f;
+                    xr = g * u; xi = g * v;
+                }
+            }
+            slab[(2 * bl) * kStftSynStride + col] = xr;
+            slab[(2 * bl + 1) * kStftSynStride + col] = xi;
+        }
+        __syncthreads();
+        if (active) {
+            for (int j = 0; j < p.R; ++j) {
+                const f32x4* pj = pi + ((size_t)c * p.R + j) * 256 + lane;
+                const float* sj = slab + hk * kStftSynStride + (lane & 31) + p.R - 1 - j;   // row q reads frame q - j
+#pragma unroll
+                for (int g = 0; g < 4; ++g) {
+                    const f32x4 w = pj[g * 64];
+#pragma unroll
+                    for (int i = 0; i < 4; ++i)
+                        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(sj[(8 * g + 2 * i) * kStftSynStride], w[i], acc, 0, 0, 0);
+                }
+            }
+        }
+    }
+    if (!active) return;
+    const int r = ct * 32 + (lane & 31);
+    if (r >= p.hop) return;
+#pragma unroll
+    for (int e = 0; e < 16; ++e) {
+        const long q = q0 + (e & 3) + 8 * (e >> 2) + 4 * hk;
+        const long t = q * p.hop + r, o = t - p.N / 2;          // stft.py:133-134: N/2 samples dropped at each end
+        if (o < 0 || o >= p.out_len) continue;
+        float v = acc[e];
+        if (p.windowed) {
+            // window_sumsquare: frames i*hop <= t < i*hop + N in ascending order, each "+=" a float64 add rounded to float32
+            const long lo = q - (p.R - 1) > 0 ? q - (p.R - 1) : 0, hi = q < p.nf - 1 ? q : p.nf - 1;
+            float env = 0.f;
+            for (long i = lo; i <= hi; ++i) env = (float)((double)env + p.wsq[t - i * p.hop]);
+            if (env > FLT_MIN) v = v / env;                    // tiny(window_sum), stft.py:123-128
+            v *= p.scale;
+        }
+        p.y[(size_t)bi * p.out_len + o] = v;
+    }
+}
+
+// forward:  [bin_tile][chunk][g][lane][i] = fwd[part*cutoff + bin][k],  row r = lane & 31: part = (r>>3)&1,
+//           bin = 16*bin_tile + 8*(r>>4) + (r&7),  k = 32*chunk + 8*g + 2*i + (lane>>5)
+__global__ void __launch_bounds__(256) stft_pack_fwd_kernel(const float* __restrict__ fwd, float* __restrict__ out, int N, int cutoff, int kchunks, size_t total) {
+    const size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= total) return;
+    const int i = idx & 3, lane = (idx >> 2) & 63, g = (idx >> 8) & 3;
+    const size_t rest = idx >> 10;
+    const int c = (int)(rest % kchunks), mt = (int)(rest / kchunks);
+    const int r = lane & 31, part = (r >> 3) & 1, bin = mt * 16 + 8 * (r >> 4) + (r & 7);
+    const int k = c * kStftKC + 8 * g + 2 * i + (lane >> 5);
+    out[idx] = (bin < cutoff && k < N) ? fwd[((size_t)part * cutoff + bin) * N + k] : 0.f;
+}
+
+// inverse:  [col_tile][chunk][j][g][lane][i] = inv[part*cutoff + bin][j*hop + r],  kk = 8*g + 2*i + (lane>>5): bin = 16*chunk + kk/2,
+//           part = kk & 1,  r = 32*col_tile + (lane & 31)
+__global__ void __launch_bounds__(256) stft_pack_inv_kernel(const float* __restrict__ inv, float* __restrict__ out, int N, int hop, int cutoff, int nchunks, size_t total) {
+    const size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= total) return;
+    const int R = N / hop;
+    const int i = idx & 3, lane = (idx >> 2) & 63, g = (idx >> 8) & 3;
+    size_t rest = idx >> 10;
+    const int j = (int)(rest % R); rest /= R;
+    const int c = (int)(rest % nchunks), ct = (int)(rest / nchunks);
+    const int kk = 8 * g + 2 * i + (lane >> 5), bin = c * 16 + (kk >> 1), part = kk & 1;
+    const int r = ct * 32 + (lane & 31);
+    out[idx] = (bin < cutoff && r < hop) ? inv[((size_t)part * cutoff + bin) * N + (size_t)j * hop + r] : 0.f;
+}
+
+// ------------------------------------------------------------------------------------------------------------------
+// host
+// ------------------------------------------------------------------------------------------------------------------
+int stft_plan(int N, int hop, int nf, StftPlan* out) {
+    T2_REQUIRE(out, "stft: null plan");
+    T2_REQUIRE(N >= 2 && N <= kStftMaxN, "stft: filter_length=%d outside 2..%d", N, kStftMaxN);
+    T2_REQUIRE(N % 2 == 0, "stft: filter_length=%d is odd: the reflect padding and the trim take N/2 samples per side", N);
+    T2_REQUIRE(hop >= 1 && hop <= N, "stft: hop_length=%d outside 1..filter_length=%d", hop, N);
+    T2_REQUIRE(N % hop == 0, "stft: filter_length=%d is not a multiple of hop_length=%d: the overlap-add GEMM needs whole overlaps", N, hop);
+    T2_REQUIRE(N / hop <= kStftMaxOverlap, "stft: filter_length=%d over hop_length=%d is %d overlaps, at most %d", N, hop, N / hop, kStftMaxOverlap);
+    T2_REQUIRE(nf >= 1 && nf <= INT32_MAX / 2 / hop, "stft: %d frames outside 1..%d at hop_length=%d", nf, INT32_MAX / 2 / hop, hop);
+    StftPlan p;
+    p.cutoff = N / 2 + 1;
+    p.overlap = N / hop;
+    p.bin_tiles = (p.cutoff + 15) / 16;
+    p.kchunks = (N + kStftKC - 1) / kStftKC;
+    p.col_tiles = (hop + 31) / 32;
+    p.out_len = (long)hop * (nf - 1);
+    p.fwd_floats = (size_t)p.bin_tiles * p.kchunks * 1024;
+    p.inv_floats = (size_t)p.col_tiles * p.bin_tiles * p.overlap * 1024;
+    p.wsq_floats = (size_t)(2 * N + 3) / 4 * 4;
+    *out = p;
+    return 0;
+}
+
+int stft_pack(int N, int hop, const float* fwd, const float* inv, const double* wsq, float* packed, hipStream_t s) {
+    StftPlan pl;
+    T2_TRY_RC(stft_plan(N, hop, 1, &pl));
+    T2_REQUIRE(fwd && inv && packed, "stft_pack: null pointer");
+    hipLaunchKernelGGL(stft_pack_fwd_kernel, dim3((unsigned)((pl.fwd_floats + 255) / 256)), dim3(256), 0, s, fwd, packed, N, pl.cutoff, pl.kchunks, pl.fwd_floats);
+    T2_LAUNCH_CHECK();
+    hipLaunchKernelGGL(stft_pack_inv_kernel, dim3((unsigned)((pl.inv_floats + 255) / 256)), dim3(256), 0, s, inv, packed + pl.fwd_floats, N, hop, pl.cutoff,
+                       pl.bin_tiles, pl.inv_floats);
+    T2_LAUNCH_CHECK();
+    float* w = packed + pl.fwd_floats + pl.inv_floats;
+    if (wsq) T2_CHECK_HIP(hipMemcpyAsync(w, wsq, (size_t)N * sizeof(double), hipMemcpyDeviceToDevice, s));
+    else T2_CHECK_HIP(hipMemsetAsync(w, 0, pl.wsq_floats * sizeof(float), s));
+    return 0;
+}
+
+int stft_analysis(const StftAnalysis& a, hipStream_t s) {
+    T2_REQUIRE(a.B >= 1 && a.B <= 65535, "stft analysis: B=%d outside 1..65535", a.B);
+    T2_REQUIRE(a.N >= 2 && a.N % 2 == 0, "stft analysis: filter_length=%d must be even", a.N);
+    T2_REQUIRE(a.n > a.N / 2, "stft analysis: Padding size should be less than the corresponding input dimension, but got: padding (%d, %d) at dimension 1 "
+               "of a signal of %ld samples", a.N / 2, a.N / 2, a.n);
+    T2_REQUIRE(a.hop >= 1 && a.n / a.hop < INT32_MAX / 2 / a.hop, "stft analysis: %ld samples at hop_length=%d exceed the limit of %d per row", a.n, a.hop, INT32_MAX / 2);
+    const int nf = 1 + (int)(a.n / a.hop);
+    StftPlan pl;
+    T2_TRY_RC(stft_plan(a.N, a.hop, nf, &pl));
+    T2_REQUIRE(a.x && a.packed, "stft analysis: null pointer");
+    T2_REQUIRE(a.re || a.im || a.mag || a.phase, "stft analysis: no output requested");
+    StftAna p;
+    p.x = a.x; p.pf = a.packed; p.re = a.re; p.im = a.im; p.mag = a.mag; p.phase = a.phase;
+    p.n = a.n; p.nf = nf; p.N = a.N; p.hop = a.hop; p.cutoff = pl.cutoff; p.bin_tiles = pl.bin_tiles; p.kchunks = pl.kchunks;
+    dim3 grid((unsigned)((nf + kStftTile - 1) / kStftTile), (unsigned)((pl.bin_tiles + 3) / 4), (unsigned)a.B);
+    hipLaunchKernelGGL(stft_analysis_kernel, grid, dim3(256), 0, s, p);
+    T2_LAUNCH_CHECK();
+    return 0;
+}
+
+int stft_synthesis(const StftSynthesis& a, hipStream_t s) {
+    T2_REQUIRE(a.B >= 1 && a.B <= 65535, "stft synthesis: B=%d outside 1..65535", a.B);
+    StftPlan pl;
+    T2_TRY_RC(stft_plan(a.N, a.hop, a.nf, &pl));
+    T2_REQUIRE(a.mode == 0 || a.mode == 1, "stft synthesis: mode %d is neither polar (0) nor denoise (1)", a.mode);
+    T2_REQUIRE(a.a && a.b && a.packed, "stft synthesis: null pointer");
+    T2_REQUIRE(a.mode == 0 || a.bias, "stft synthesis: the denoise mode needs the bias spectrum");
+    if (pl.out_len == 0) return 0;                             // a single frame: everything falls into the trimmed margins
+    T2_REQUIRE(a.y, "stft synthesis: null output");
+    StftSyn p;
+    p.a = a.a; p.b = a.b; p.bias = a.bias; p.pi = a.packed + pl.fwd_floats; p.y = a.y;
+    p.wsq = reinterpret_cast<const double*>(a.packed + pl.fwd_floats + pl.inv_floats);
+    p.nf = a.nf; p.N = a.N; p.hop = a.hop; p.R = pl.overlap; p.cutoff = pl.cutoff; p.nchunks = pl.bin_tiles; p.col_tiles = pl.col_tiles;
+    p.mode = a.mode; p.windowed = a.windowed != 0;
+    p.qbase = (a.N / 2) / a.hop; p.out_len = pl.out_len;
+    p.strength = a.strength; p.scale = (float)a.N / (float)a.hop;
+    const long qlast = (a.N / 2 + pl.out_len - 1) / a.hop;
+    const int wn = pl.col_tiles >= 8 ? 8 : (pl.col_tiles >= 4 ? 4 : (pl.col_tiles >= 2 ? 2 : 1));
+    dim3 grid((unsigned)((qlast - p.qbase) / kStftTile + 1), (unsigned)((pl.col_tiles + wn - 1) / wn), (unsigned)a.B);
+    if (wn == 8) hipLaunchKernelGGL(stft_synthesis_kernel<8>, grid, dim3(512), 0, s, p);
+    else if (wn == 4) hipLaunchKernelGGL(stft_synthesis_kernel<4>, grid, dim3(256), 0, s, p);
+    else if (wn == 2) hipLaunchKernelGGL(stft_synthesis_kernel<2>, grid, dim3(128), 0, s, p);
+    else hipLaunchKernelGGL(stft_synthesis_kernel<1>, grid, dim3(64), 0, s, p);
+    T2_LAUNCH_CHECK();
+    return 0;
+}
+
+}  // namespace t2

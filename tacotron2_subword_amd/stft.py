@@ -1,11 +1,18 @@
 """Mel front end used for real (non-synthetic) GTA extraction (reference: stft.py:42-105,
-layers.py:42-80, audio_processing.py:78-93).
+layers.py:42-80, audio_processing.py:78-93), and the synthesis side the vocoder's bias remover and Griffin-Lim need
+(stft.py:107-141).
 
 `STFT.transform` = reflect-pad by filter_length/2, frame with stride hop_length, multiply by the windowed Fourier
 basis [2*(N/2+1), N] (the reference does this as a strided conv1d), magnitude + phase.  Here the frames x basis
 product runs on the HIP GEMM (`ops.gemm`, fp32 MFMA: a 1024-tap basis is a plain [frames, 1024] x [1024, 1026]
 product); on CPU tensors it falls back to torch.matmul only so that the formula can be compared with the reference's
 own STFT on the GPU-less build box (tests/golden/make_golden_stft.py) — this module is not part of the model's hot path.
+
+`STFT.inverse` runs csrc/stft.hip's synthesis kernel: the conv_transpose1d with the inverse basis as an overlap-add GEMM
+(DESIGN.md "STFT synthesis"), magnitude * (cos, sin)(phase) formed in its loader, the window sum-square envelope, the
+N/hop scale and the trim in its epilogue: one launch.  The module-level `analysis` / `synthesis` / `pack_tables` are the
+kernels' entry points (bias_remover.py uses them; the tests drive them with bases of their own).  On CPU tensors
+`inverse` is the torch formula, for the same comparison only.
 
 The mel filterbank restates librosa.filters.mel (Slaney mel scale, Slaney area normalisation), which the reference
 calls as librosa_mel_fn(sampling_rate, filter_length, n_mel_channels, mel_fmin, mel_fmax) (layers.py:48-49).  librosa is
@@ -15,13 +22,7 @@ import numpy as np
 import torch
 from scipy.signal import get_window
 
-from .audio_processing import dynamic_range_compression, dynamic_range_decompression
-
-
-def _pad_center(data, size):
-    n = data.shape[-1]
-    lpad = (size - n) // 2
-    return np.pad(data, (lpad, size - n - lpad), mode="constant")
+from .audio_processing import _pad_center, dynamic_range_compression, dynamic_range_decompression, window_sumsquare
 
 
 def _hz_to_mel(f):
@@ -57,19 +58,126 @@ def mel_filterbank(sr, n_fft, n_mels=128, fmin=0.0, fmax=None):
     return (weights * enorm[:, np.newaxis]).astype(np.float32)
 
 
+def _check_planes(who, a, b, bins):
+    if a.dim() != 3 or a.shape != b.shape or a.shape[1] != bins:
+        raise RuntimeError(f"{who}: expected two tensors of one shape [B, {bins}, frames], got {tuple(a.shape)} and {tuple(b.shape)}")
+    if a.dtype != torch.float32 or b.dtype != torch.float32:
+        raise RuntimeError(f"{who}: the inputs must be float32, got {a.dtype} and {b.dtype}")
+    if a.device != b.device:
+        raise RuntimeError(f"{who}: the inputs are on {a.device} and {b.device}")
+    if torch.is_grad_enabled() and (a.requires_grad or b.requires_grad):
+        raise RuntimeError(f"{who} is inference only: an input requires grad and grad mode is on; call it under torch.no_grad() "
+                           "or detach the inputs")
+
+
+def pack_tables(forward_basis, inverse_basis, window_sq, filter_length, hop_length):
+    """The tables of csrc/stft.hip in the order its lanes read them (t2_stft_pack).  forward_basis, inverse_basis:
+    [2*(N/2+1), N] fp32 on the GPU; window_sq: the squared, centre-padded window [N] in fp64, or None (no window)."""
+    from . import _lib as L
+    plan = L.stft_plan(filter_length, hop_length)
+    rows = 2 * plan.bins
+    for name, t in (("forward_basis", forward_basis), ("inverse_basis", inverse_basis)):
+        if tuple(t.shape) != (rows, filter_length) or t.dtype != torch.float32:
+            raise RuntimeError(f"stft pack_tables: {name} must be float32 [{rows}, {filter_length}], got {t.dtype} {tuple(t.shape)}")
+    if window_sq is not None and (tuple(window_sq.shape) != (filter_length,) or window_sq.dtype != torch.float64):
+        raise RuntimeError(f"stft pack_tables: window_sq must be float64 [{filter_length}], got {window_sq.dtype} {tuple(window_sq.shape)}")
+    dev = forward_basis.device
+    with torch.cuda.device(dev):
+        packed = torch.empty(plan.packed_bytes // 4, device=dev, dtype=torch.float32)
+        L.check(L.lib().t2_stft_pack(filter_length, hop_length, L.ptr(forward_basis.contiguous()), L.ptr(inverse_basis.contiguous()),
+                                     L.ptr(None if window_sq is None else window_sq.contiguous()), L.ptr(packed), L.stream()))
+    return packed
+
+
+def analysis(x, packed, filter_length, hop_length, want=("re", "im")):
+    """x [B, n] fp32 on the GPU -> the tensors named in `want` (of "re", "im", "mag", "phase"), [B, N/2+1, 1 + n//hop]
+    each, from one launch of the analysis kernel; the reflect padding is the kernel's index arithmetic."""
+    from . import _lib as L
+    if x.dim() != 2 or x.dtype != torch.float32:
+        raise RuntimeError(f"stft analysis: expected a float32 signal [B, n], got {x.dtype} {tuple(x.shape)}")
+    if torch.is_grad_enabled() and x.requires_grad:
+        raise RuntimeError("stft analysis is inference only: the input requires grad and grad mode is on")
+    B, n = x.shape
+    half = filter_length // 2
+    if n <= half:        # torch's own words for F.pad(..., mode="reflect")
+        raise RuntimeError(f"Padding size should be less than the corresponding input dimension, but got: padding ({half}, {half}) "
+                           f"at dimension 1 of input {list(x.shape)}")
+    plan = L.stft_plan(filter_length, hop_length, 1 + n // hop_length)
+    x = x.detach().contiguous()
+    with torch.cuda.device(x.device):
+        out = {k: torch.empty(B, plan.bins, 1 + n // hop_length, device=x.device, dtype=torch.float32) for k in want}
+        a = L.StftAnalysisArgs(B, filter_length, hop_length, n, L.ptr(x), L.ptr(packed), *[L.ptr(out.get(k)) for k in ("re", "im", "mag", "phase")])
+        L.check(L.lib().t2_stft_analysis(a, L.stream()))
+    return tuple(out[k] for k in want)
+
+
+def synthesis(a, b, packed, filter_length, hop_length, mode=0, bias=None, strength=0.0, windowed=True):
+    """Two planes [B, N/2+1, nf] fp32 on the GPU -> audio [B, 1, hop*(nf-1)] from one launch of the synthesis kernel.
+    mode 0 (polar): a = magnitude, b = phase.  mode 1 (denoise): a = re, b = im, bias [N/2+1] and strength: the bias
+    remover's clamp(|z| - strength*bias, 0) applied as a gain.  windowed=False leaves out the envelope division and the
+    N/hop scale (STFT(window=None)): the output is then the trimmed overlap-add sum itself."""
+    from . import _lib as L
+    plan = L.stft_plan(filter_length, hop_length, max(int(a.shape[-1]), 1) if a.dim() == 3 else 1)
+    _check_planes("stft synthesis", a, b, plan.bins)
+    B, _, nf = a.shape
+    if nf < 1:
+        raise RuntimeError("stft synthesis: no frames")
+    if mode == L.STFT_DENOISE and (bias is None or bias.numel() != plan.bins or bias.dtype != torch.float32):
+        raise RuntimeError(f"stft synthesis: the denoise mode needs a float32 bias spectrum of {plan.bins} bins")
+    a, b = a.detach().contiguous(), b.detach().contiguous()
+    with torch.cuda.device(a.device):
+        y = torch.empty(B, 1, plan.out_len, device=a.device, dtype=torch.float32)
+        args = L.StftSynthesisArgs(B, filter_length, hop_length, nf, mode, int(bool(windowed)), L.ptr(a), L.ptr(b),
+                                   L.ptr(None if bias is None else bias.detach().reshape(-1).contiguous()), float(strength), L.ptr(packed), L.ptr(y))
+        L.check(L.lib().t2_stft_synthesis(args, L.stream()))
+    return y
+
+
 class STFT(torch.nn.Module):
     def __init__(self, filter_length=800, hop_length=200, win_length=800, window="hann"):
         super().__init__()
         self.filter_length, self.hop_length, self.win_length, self.window = filter_length, hop_length, win_length, window
+        scale = filter_length / hop_length
         fourier_basis = np.fft.fft(np.eye(filter_length))
         cutoff = int(filter_length / 2 + 1)
         fourier_basis = np.vstack([np.real(fourier_basis[:cutoff, :]), np.imag(fourier_basis[:cutoff, :])])
         forward_basis = torch.FloatTensor(fourier_basis[:, None, :])
+        inverse_basis = torch.FloatTensor(np.linalg.pinv(scale * fourier_basis).T[:, None, :])
         if window is not None:
             assert filter_length >= win_length
             fft_window = torch.from_numpy(_pad_center(get_window(window, win_length, fftbins=True), filter_length)).float()
             forward_basis *= fft_window
+            inverse_basis *= fft_window
         self.register_buffer("forward_basis", forward_basis.float())       # [2*cutoff, 1, N], the reference's buffer name / shape
+        self.register_buffer("inverse_basis", inverse_basis.float())       # [2*cutoff, 1, N], likewise
+        self._packed = None
+        self._packed_key = None
+
+    def _apply(self, fn, *args, **kwargs):                                  # .to() / .cuda(): the packed tables follow the buffers
+        out = super()._apply(fn, *args, **kwargs)
+        self._packed = None
+        return out
+
+    def _key(self):
+        return tuple((t.data_ptr(), t._version) for t in (self.forward_basis, self.inverse_basis))
+
+    def window_sq(self):
+        """The squared window, centre-padded to filter_length, fp64: what window_sumsquare adds per frame.  None without a window."""
+        if self.window is None:
+            return None
+        return _pad_center(get_window(self.window, self.win_length, fftbins=True) ** 2, self.filter_length)
+
+    def tables(self):
+        """The kernels' packed tables, built on first use and again after .to() / .cuda() / load_state_dict."""
+        if not self.forward_basis.is_cuda:
+            raise RuntimeError("STFT: the buffers must live on the GPU for the HIP kernels (module.cuda())")
+        if self._packed is None or self._packed_key != self._key():
+            wsq = self.window_sq()
+            dev = self.forward_basis.device
+            self._packed = pack_tables(self.forward_basis[:, 0, :], self.inverse_basis[:, 0, :],
+                                       None if wsq is None else torch.from_numpy(wsq).to(dev), self.filter_length, self.hop_length)
+            self._packed_key = self._key()
+        return self._packed
 
     def transform(self, input_data):
         B, n = input_data.shape
@@ -88,6 +196,34 @@ class STFT(torch.nn.Module):
         cutoff = int(self.filter_length / 2 + 1)
         real_part, imag_part = ft[:, :cutoff, :], ft[:, cutoff:, :]
         return torch.sqrt(real_part ** 2 + imag_part ** 2), torch.atan2(imag_part, real_part)
+
+    def inverse(self, magnitude, phase):
+        """magnitude, phase [B, N/2+1, frames] -> audio [B, 1, hop*(frames-1)] (stft.py:107-136)."""
+        cutoff = int(self.filter_length / 2 + 1)
+        _check_planes("STFT.inverse", magnitude, phase, cutoff)
+        if not magnitude.is_cuda:
+            return self._inverse_torch(magnitude, phase)
+        if self.forward_basis.device != magnitude.device:
+            raise RuntimeError(f"STFT.inverse: the input is on {magnitude.device}, the module on {self.forward_basis.device}")
+        return synthesis(magnitude, phase, self.tables(), self.filter_length, self.hop_length, windowed=self.window is not None)
+
+    def _inverse_torch(self, magnitude, phase):
+        """The reference's formula in torch ops, for CPU tensors: comparison with the reference on a box without a GPU."""
+        half = int(self.filter_length / 2)
+        x = torch.cat([magnitude * torch.cos(phase), magnitude * torch.sin(phase)], dim=1)
+        y = torch.nn.functional.conv_transpose1d(x, self.inverse_basis, stride=self.hop_length, padding=0)
+        if self.window is not None:
+            env = window_sumsquare(self.window, magnitude.size(-1), hop_length=self.hop_length, win_length=self.win_length,
+                                   n_fft=self.filter_length, dtype=np.float32)
+            nonzero = torch.from_numpy(np.where(env > np.finfo(env.dtype).tiny)[0])
+            env = torch.from_numpy(env).to(y.device)
+            y[:, :, nonzero] /= env[nonzero]
+            y *= float(self.filter_length) / self.hop_length
+        return y[:, :, half:][:, :, :-half]
+
+    def forward(self, input_data):
+        self.magnitude, self.phase = self.transform(input_data)
+        return self.inverse(self.magnitude, self.phase)
 
 
 class TacotronSTFT(torch.nn.Module):
