@@ -136,6 +136,11 @@ int t2_set_chain_bwd(int on);
  * bytes per MFMA; implicit-conv operands included).  0: always convert while staging through LDS.  Same rounding
  * of the operands either way; only the summation order inside a dot product differs. */
 int t2_set_gemm_staging(int on);
+/* 1 (default; env T2_GEMM_FOLD=0 turns it off): work that only touches a product's output is done where the product stores
+ * it: the gate term of dDOUT in t2_decoder_backward is a rank-1 addend of the mel product's stores, and t2_conv_bn_backward's
+ * weight-gradient product (or its split-K reduce) writes [Cout][Cin][K] directly.  0: the separate K = 1 product over dDOUT
+ * and the re-layout kernel.  Every result has the same bits either way; the switch lets one process compare the two. */
+int t2_set_gemm_fold(int on);
 /* Makes `stream` wait for everything the library has queued on its internal side stream of the current device
  * (t2_decoder_bwd_args.defer_weight_grads). */
 int t2_side_join(void* stream);

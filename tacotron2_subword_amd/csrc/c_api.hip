@@ -1063,6 +1063,7 @@ int t2_set_chain(int on) { g_chain = on != 0; return 0; }
 int t2_get_chain(void) { return g_chain; }
 int t2_set_chain_bwd(int on) { g_chain_bwd = on != 0; return 0; }
 int t2_set_gemm_staging(int on) { set_gemm_staging(on); return 0; }
+int t2_set_gemm_fold(int on) { set_gemm_fold(on); return 0; }
 int t2_side_join(void* stream) {
     Side* side = nullptr;
     T2_TRY(side_get(&side));
@@ -1226,11 +1227,16 @@ int t2_decoder_backward(const t2_dims* dims_in, const t2_decoder_weights* w, con
     T2_TRY(permute_rows(a->d_gate, dgate, z.B, z.T, 1, c.s));
     // ---- projections (model.py:382-388): dDOUT = d_mel . Wproj + d_gate . Wgate ; weight gradients
     {
+        // the gate term is one multiply per element: it rides on the stores of the mel product as a rank-1 addend (the
+        // same bits as the K = 1, beta = 1 product, which is a pass of its own over dDOUT; t2_set_gemm_fold(0) runs that)
         GemmDesc x = matmul_nn(dmel, z.M, w->proj_w, z.WO, c.S(BL.ddout), z.WO, BT, z.WO, z.M);
+        if (get_gemm_fold()) { x.r1_m = dgate; x.r1_n = w->gate_w; }
         T2_TRY(gemm(x, c.s));
-        GemmDesc y = matmul_nn(dgate, 1, w->gate_w, z.WO, c.S(BL.ddout), z.WO, BT, z.WO, 1);
-        y.beta = 1.f;
-        T2_TRY(gemm(y, c.s));
+        if (!get_gemm_fold()) {
+            GemmDesc y = matmul_nn(dgate, 1, w->gate_w, z.WO, c.S(BL.ddout), z.WO, BT, z.WO, 1);
+            y.beta = 1.f;
+            T2_TRY(gemm(y, c.s));
+        }
         T2_TRY(gemm(matmul_tn(c, dmel, z.M, c.W(L.dout), z.WO, g->proj_w, z.WO, z.M, z.WO, BT), c.s));
         T2_TRY(gemm(matmul_tn(c, dgate, 1, c.W(L.dout), z.WO, g->gate_w, z.WO, 1, z.WO, BT), c.s));
         T2_TRY(colsum(dmel, z.M, BT, z.M, g->proj_b, nullptr, cws, c.s));

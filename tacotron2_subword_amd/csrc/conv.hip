@@ -253,44 +253,66 @@ __global__ void embedding_fwd_kernel(const long* __restrict__ ids, const float* 
     }
 }
 // dtable[v, :] = sum over rows with ids[row] == v of dout[row, :]   (one workgroup per vocabulary entry: fixed order)
-__global__ void embedding_bwd_kernel(const long* __restrict__ ids, const float* __restrict__ dout, float* __restrict__ dtable, int rows, int D) {
+// The ordered list of the rows that hit v is built in passes of kEmbRounds * kEmbThreads rows.  A thread requests all its
+// ids of a pass at once (row = pass base + j * kEmbThreads + thread in round j) and keeps one hit bit per round, so a
+// pass costs one load latency and one barrier, not one of each per round: the 6400 tokens of a training batch are one
+// pass.  A round's hits are placed by a ballot inside the wave and the prefix over the (round, wave) counts in front of it,
+// which every thread walks in LDS: ascending rows, whatever the scheduling.
+constexpr int kEmbThreads = 256, kEmbWaves = kEmbThreads / 64, kEmbRounds = 32;
+// V = 4: a thread sums 4 adjacent columns with 16-byte requests (D % 4 == 0, 16-byte aligned arrays).  The additions of
+// a column are the same in the same order for either V: rows ascending, fp32, requested 8 at a time.
+template <int V>
+__global__ __launch_bounds__(kEmbThreads) void embedding_bwd_kernel(const long* __restrict__ ids, const float* __restrict__ dout,
+                                                                    float* __restrict__ dtable, int rows, int D) {
     const int v = blockIdx.x;
     extern __shared__ int hits[];
-    __shared__ int wave_cnt[2][16];
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, nw = blockDim.x >> 6;
-    // ordered compaction of the rows that hit v (keeps the summation order independent of scheduling): every thread
-    // carries the running count, the next block of ids is requested before the current one is processed, one barrier
-    // per block of rows
+    __shared__ __attribute__((aligned(16))) int wave_cnt[2][kEmbRounds][kEmbWaves];
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    const unsigned long long below = (1ull << lane) - 1ull;
     int run = 0;
-    long idn = (int)threadIdx.x < rows ? ids[threadIdx.x] : -1;
-    for (int r0 = 0, it = 0; r0 < rows; r0 += blockDim.x, ++it) {
-        const int r = r0 + threadIdx.x, rn = r + blockDim.x;
-        const long id = idn;
-        idn = rn < rows ? ids[rn] : -1;
-        const bool hit = r < rows && id == v;
-        const unsigned long long m = __ballot(hit);
-        int* wc = wave_cnt[it & 1];
-        if (lane == 0) wc[wave] = __popcll(m);
+    for (int r0 = 0, it = 0; r0 < rows; r0 += kEmbRounds * kEmbThreads, ++it) {
+        long id[kEmbRounds];
+#pragma unroll
+        for (int j = 0; j < kEmbRounds; ++j) {
+            const int r = r0 + j * kEmbThreads + tid;
+            id[j] = r < rows ? ids[r] : -1;
+        }
+        unsigned mine = 0;
+#pragma unroll
+        for (int j = 0; j < kEmbRounds; ++j) mine |= (id[j] == v ? 1u : 0u) << j;
+        int (*wc)[kEmbWaves] = wave_cnt[it & 1];           // (two buffers: the next pass writes while a slow wave still reads)
+#pragma unroll
+        for (int j = 0; j < kEmbRounds; ++j) {
+            const unsigned long long m = __ballot((mine >> j) & 1u);
+            if (lane == 0) wc[j][wave] = __popcll(m);
+        }
         __syncthreads();
-        int base = run, tot = 0;
-        for (int w = 0; w < nw; ++w) { const int cw = wc[w]; if (w < wave) base += cw; tot += cw; }
-        if (hit) hits[base + __popcll(m & ((1ull << lane) - 1ull))] = r;
-        run += tot;
+#pragma unroll
+        for (int j = 0; j < kEmbRounds; ++j) {
+            int base = run, tot = 0;
+#pragma unroll
+            for (int w = 0; w < kEmbWaves; ++w) { const int cw = wc[j][w]; if (w < wave) base += cw; tot += cw; }
+            const bool hit = (mine >> j) & 1u;
+            const unsigned long long m = __ballot(hit);
+            if (hit) hits[base + __popcll(m & below)] = r0 + j * kEmbThreads + tid;
+            run += tot;
+        }
     }
     __syncthreads();
     const int nhit = run;
-    for (int c = threadIdx.x; c < D; c += blockDim.x) {
-        float acc = 0.f;                                   // rows requested 8 at a time, added in row order
+    typedef float vec __attribute__((ext_vector_type(V)));
+    for (int c = tid * V; c < D; c += kEmbThreads * V) {
+        vec acc = 0.f;                                     // rows requested 8 at a time, added in row order
         int h = 0;
         for (; h + 8 <= nhit; h += 8) {
-            float x[8];
+            vec x[8];
 #pragma unroll
-            for (int j = 0; j < 8; ++j) x[j] = dout[(size_t)hits[h + j] * D + c];
+            for (int j = 0; j < 8; ++j) x[j] = *reinterpret_cast<const vec*>(dout + (size_t)hits[h + j] * D + c);
 #pragma unroll
             for (int j = 0; j < 8; ++j) acc += x[j];
         }
-        for (; h < nhit; ++h) acc += dout[(size_t)hits[h] * D + c];
-        dtable[(size_t)v * D + c] = acc;
+        for (; h < nhit; ++h) acc += *reinterpret_cast<const vec*>(dout + (size_t)hits[h] * D + c);
+        *reinterpret_cast<vec*>(dtable + (size_t)v * D + c) = acc;
     }
 }
 
@@ -373,6 +395,10 @@ int conv_bn_bwd(const ConvBnBwd& a, hipStream_t s) {
     g.B = a.x; g.conv_b = 1; g.conv_T = a.T; g.conv_C = a.Cin; g.conv_pad = (a.K - 1) / 2;
     g.C = a.wperm; g.ldc = (long)a.K * a.Cin; g.M = a.Cout; g.N = a.K * a.Cin; g.K = M;
     g.ws = a.gemm_ws; g.ws_bytes = a.gemm_ws_bytes;
+    // the product (or its split-K reduce) writes column dk*Ci + ci at ci*K + dk: the reference layout [Cout][Cin][K], straight
+    // into a.dw (set_gemm_fold(0): into wperm, and unpermute_dw_kernel copies it over)
+    const bool fold = get_gemm_fold() != 0;
+    if (fold) { g.C = a.dw; g.ccol_mod = a.Cin; g.ccol_mul = a.K; }
     // d(input) = correlation of dz with the flipped, transposed kernel
     GemmDesc h = gemm_desc();
     h.A = a.dz; h.conv_a = 1; h.conv_T = a.T; h.conv_C = a.Cout; h.conv_pad = (a.K - 1) / 2;
@@ -418,8 +444,10 @@ int conv_bn_bwd(const ConvBnBwd& a, hipStream_t s) {
     T2_TRY_RC(colsum(a.dz, a.Cout, M, a.Cout, a.dbias, nullptr, a.scratch, s));
     T2_TRY_RC(gemm(g, s));
     const size_t nw = (size_t)a.Cout * a.Cin * a.K;
-    hipLaunchKernelGGL(unpermute_dw_kernel, dim3(grid_for(nw)), dim3(256), 0, s, a.wperm, a.dw, a.Cout, a.Cin, a.K);
-    T2_LAUNCH_CHECK();
+    if (!fold) {
+        hipLaunchKernelGGL(unpermute_dw_kernel, dim3(grid_for(nw)), dim3(256), 0, s, a.wperm, a.dw, a.Cout, a.Cin, a.K);
+        T2_LAUNCH_CHECK();
+    }
     if (a.dx) {
         if (w16) hipLaunchKernelGGL(permute_w_bwd_kernel<__bf16>, dim3(grid_for(nw)), dim3(256), 0, s, a.w, reinterpret_cast<__bf16*>(a.wperm), a.Cout, a.Cin, a.K);
         else hipLaunchKernelGGL(permute_w_bwd_kernel<float>, dim3(grid_for(nw)), dim3(256), 0, s, a.w, a.wperm, a.Cout, a.Cin, a.K);
@@ -438,8 +466,11 @@ int embedding_fwd(const long* ids, const float* table, float* out, int rows, int
 int embedding_bwd(const long* ids, const float* dout, float* dtable, int rows, int D, int vocab, hipStream_t s) {
     const size_t smem = (size_t)rows * sizeof(int);
     T2_REQUIRE(smem <= 150 * 1024, "embedding_bwd: %d tokens do not fit the LDS hit list", rows);
-    T2_TRY_RC(t2_allow_dynamic_lds(reinterpret_cast<const void*>(embedding_bwd_kernel), smem));
-    hipLaunchKernelGGL(embedding_bwd_kernel, dim3(vocab), dim3(256), smem, s, ids, dout, dtable, rows, D);
+    const bool vec = cols_vectorisable(dout, D, D) && cols_vectorisable(dtable, D, D);
+    const void* fn = vec ? reinterpret_cast<const void*>(embedding_bwd_kernel<4>) : reinterpret_cast<const void*>(embedding_bwd_kernel<1>);
+    T2_TRY_RC(t2_allow_dynamic_lds(fn, smem));
+    if (vec) hipLaunchKernelGGL(embedding_bwd_kernel<4>, dim3(vocab), dim3(kEmbThreads), smem, s, ids, dout, dtable, rows, D);
+    else hipLaunchKernelGGL(embedding_bwd_kernel<1>, dim3(vocab), dim3(kEmbThreads), smem, s, ids, dout, dtable, rows, D);
     T2_LAUNCH_CHECK();
     return 0;
 }

@@ -20,6 +20,9 @@ static int g_precision = 0;       // 0: fp32 operands (parity path), 1: bf16 ope
 static int env_int(const char* name, int dflt) { const char* v = getenv(name); return v && *v ? atoi(v) : dflt; }
 static int g_stage = env_int("T2_GEMM_STAGE", 1);
 void set_gemm_staging(int on) { g_stage = on != 0; }
+static int g_fold = env_int("T2_GEMM_FOLD", 1);
+void set_gemm_fold(int on) { g_fold = on != 0; }
+int get_gemm_fold() { return g_fold; }
 constexpr int kStageMin = 256;
 // split-bf16 mode: a product whose 2*M*N*K is below this many MFLOP runs the exact fp32 kernel instead: three staged terms
 // and two staging launches cost 20 - 50 us whatever the shape, which the exact kernel beats up to about 2 GFLOP
@@ -53,7 +56,31 @@ __device__ __forceinline__ float apply_act(float v, int act) {
     return v;
 }
 
-__device__ __forceinline__ void epilogue_store(const GemmDesc& d, float* C, int m, int n, float acc, RngKey key) {
+// v + a * b as the K = 1, beta = 1 product it replaces leaves it: the product rounded on its own (the fp32 MFMA adds it
+// to a zero accumulator, so a zero product is +0), then one rounded sum.  Nothing here may be contracted into an fma, which
+// would round once.  Written with the operators under the pragma, not with __fmul_rn / __fadd_rn: the headers define those
+// as the same operators compiled with contraction allowed (unless the rounded OCML operations are switched on), so after
+// inlining they promise nothing.
+__device__ __forceinline__ float add_rank1(float v, float a, float b) {
+#pragma clang fp contract(off)
+    const float p = a * b + 0.0f;
+    return p + v;
+}
+// The column map costs an integer division per element, and left as a select on d.ccol_mod the compiler computes it for
+// every element of every product (the 25600 x 2048 x 80 product: 152 -> 211 us).  So the kernels branch once, outside their
+// store loops, into a copy of the loop compiled with the map (CMAP) or without it: with_col_map.
+template <bool CMAP>
+__device__ __forceinline__ long out_col(const GemmDesc& d, int n) {
+    if constexpr (CMAP) return (long)(n % d.ccol_mod) * d.ccol_mul + n / d.ccol_mod;
+    else return (long)n;
+}
+template <class F>
+__device__ __forceinline__ void with_col_map(const GemmDesc& d, F f) {
+    if (d.ccol_mod) f(std::true_type{}); else f(std::false_type{});
+}
+
+// the finished element (m, n) short of the beta term
+__device__ __forceinline__ float epilogue_value(const GemmDesc& d, int m, int n, float acc, RngKey key) {
     float v = d.alpha * acc;
     if (d.bias1) v += d.bias1[n];
     if (d.bias2) v += d.bias2[n];
@@ -62,8 +89,14 @@ __device__ __forceinline__ void epilogue_store(const GemmDesc& d, float* C, int 
         uint32_t idx = d.drop_base + (uint32_t)m * d.drop_mstride + (uint32_t)n;
         v = rng_keep(key, idx, d.drop_p) ? v * (1.0f / (1.0f - d.drop_p)) : 0.f;
     }
+    if (d.r1_m) v = add_rank1(v, d.r1_m[m], d.r1_n[n]);
+    return v;
+}
+template <bool CMAP>
+__device__ __forceinline__ void epilogue_store(const GemmDesc& d, float* C, int m, int n, float acc, RngKey key) {
+    float v = epilogue_value(d, m, n, acc, key);
     const long mo = d.crow_mod ? (long)(m % d.crow_mod) * d.crow_mul + m / d.crow_mod : (long)m;
-    float* p = C + mo * d.ldc + n;
+    float* p = C + mo * d.ldc + out_col<CMAP>(d, n);
     if (d.beta != 0.f) v += d.beta * (*p);
     *p = v;
 }
@@ -222,25 +255,28 @@ __global__ __launch_bounds__(256) void gemm_kernel(GemmK g) {
     const RngKey key = rng_key(d.seed, d.site);
     float* C = d.C + (long)bz * d.bsC;
     float* ws = d.splitk > 1 ? d.ws + ((long)split * d.batch + bz) * (long)d.M * d.N : nullptr;
+    with_col_map(d, [&](auto cmap) {
 #pragma unroll
-    for (int i = 0; i < TM; ++i)
+        for (int i = 0; i < TM; ++i)
 #pragma unroll
-        for (int j = 0; j < TN; ++j) {
-            const int n = n0 + wn * (BN / 2) + j * 32 + r;
-            if (n >= d.N) continue;
+            for (int j = 0; j < TN; ++j) {
+                const int n = n0 + wn * (BN / 2) + j * 32 + r;
+                if (n >= d.N) continue;
 #pragma unroll
-            for (int e = 0; e < 16; ++e) {
-                const int m = m0 + wm * (BM / 2) + i * 32 + (e & 3) + 8 * (e >> 2) + 4 * hk;
-                if (m >= d.M) continue;
-                if (ws) ws[(long)m * d.N + n] = acc[i][j][e];
-                else epilogue_store(d, C, m, n, acc[i][j][e], key);
+                for (int e = 0; e < 16; ++e) {
+                    const int m = m0 + wm * (BM / 2) + i * 32 + (e & 3) + 8 * (e >> 2) + 4 * hk;
+                    if (m >= d.M) continue;
+                    if (ws) ws[(long)m * d.N + n] = acc[i][j][e];
+                    else epilogue_store<decltype(cmap)::value>(d, C, m, n, acc[i][j][e], key);
+                }
             }
-        }
+    });
 }
 
 __global__ void splitk_reduce_kernel(GemmDesc d) {
     const long total = (long)d.batch * d.M * d.N;
     const RngKey key = rng_key(d.seed, d.site);
+    with_col_map(d, [&](auto cmap) {
     for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
         float acc = 0.f;                                   // partials requested 8 at a time, added in split order
         int s = 0;
@@ -263,8 +299,9 @@ __global__ void splitk_reduce_kernel(GemmDesc d) {
         const int bz = (int)(i / ((long)d.M * d.N));
         const long rem = i - (long)bz * d.M * d.N;
         const int m = (int)(rem / d.N), n = (int)(rem % d.N);
-        epilogue_store(d, d.C + (long)bz * d.bsC, m, n, acc, key);
+        epilogue_store<decltype(cmap)::value>(d, d.C + (long)bz * d.bsC, m, n, acc, key);
     }
+    });
 }
 
 
@@ -575,21 +612,49 @@ __global__ __launch_bounds__(256) void gemm_bf16_kernel(GemmK g) {
     }
     }
 
+    // Epilogue through LDS (free behind the loop's last barrier), as in gemm_bf16src256_kernel: each wave lays its 64 x 64
+    // sub-tile out row-major in its own 16 KB and walks it with 16-byte reads, so a row leaves as 256 contiguous bytes in
+    // 16-byte stores (16 store instructions per lane instead of 64) and the row map is resolved once per 4 elements.  The
+    // element's arithmetic is epilogue_value / epilogue_store as before; lanes whose 4 columns are not all inside N, a
+    // column map and unaligned outputs take the scalar stores.
     const RngKey key = rng_key(d.seed, d.site);
     float* C = d.C + (long)bz * d.bsC;
     float* ws = d.splitk > 1 ? d.ws + ((long)split * d.batch + bz) * (long)d.M * d.N : nullptr;
+    float* stg = reinterpret_cast<float*>(smem16) + wave * 4096;
 #pragma unroll
     for (int i = 0; i < 2; ++i)
 #pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            const int n = n0 + wn * 64 + j * 32 + r;
-            if (n >= d.N) continue;
+        for (int j = 0; j < 2; ++j)
 #pragma unroll
-            for (int e = 0; e < 16; ++e) {
-                const int m = m0 + wm * 64 + i * 32 + (e & 3) + 8 * (e >> 2) + 4 * h;
-                if (m >= d.M) continue;
-                if (ws) ws[(long)m * d.N + n] = acc[i][j][e];
-                else epilogue_store(d, C, m, n, acc[i][j][e], key);
+            for (int e = 0; e < 16; ++e) stg[(i * 32 + (e & 3) + 8 * (e >> 2) + 4 * h) * 64 + j * 32 + r] = acc[i][j][e];
+    __syncthreads();
+    const int c4 = (lane & 15) * 4, n = n0 + wn * 64 + c4;
+    const bool vec = n + 3 < d.N && (ws ? (reinterpret_cast<uintptr_t>(ws) & 15) == 0 && d.N % 4 == 0
+                                        : (reinterpret_cast<uintptr_t>(C) & 15) == 0 && d.ldc % 4 == 0 && !d.ccol_mod);
+    if (n < d.N)
+        for (int it = 0; it < 16; ++it) {
+            const int row = it * 4 + (lane >> 4);
+            const int m = m0 + wm * 64 + row;
+            if (m >= d.M) continue;
+            f32x4 v = *reinterpret_cast<const f32x4*>(stg + row * 64 + c4);
+            if (ws) {
+                float* pw = ws + (long)m * d.N + n;
+                if (vec) *reinterpret_cast<f32x4*>(pw) = v;
+                else
+#pragma unroll
+                    for (int c = 0; c < 4; ++c) if (n + c < d.N) pw[c] = v[c];
+            } else if (vec) {
+#pragma unroll
+                for (int c = 0; c < 4; ++c) v[c] = epilogue_value(d, m, n + c, v[c], key);
+                const long mo = d.crow_mod ? (long)(m % d.crow_mod) * d.crow_mul + m / d.crow_mod : (long)m;
+                float* pc = C + mo * d.ldc + n;
+                if (d.beta != 0.f) v += d.beta * *reinterpret_cast<const f32x4*>(pc);
+                *reinterpret_cast<f32x4*>(pc) = v;
+            } else {
+                with_col_map(d, [&](auto cmap) {
+#pragma unroll
+                    for (int c = 0; c < 4; ++c) if (n + c < d.N) epilogue_store<decltype(cmap)::value>(d, C, m, n + c, v[c], key);
+                });
             }
         }
 }
@@ -751,18 +816,20 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_bf16src_kernel(GemmK g, con
     const RngKey key = rng_key(d.seed, d.site);
     float* C = d.C;
     float* ws = d.splitk > 1 ? d.ws + (long)split * (long)d.M * d.N : nullptr;
+    with_col_map(d, [&](auto cmap) {
 #pragma unroll
-    for (int i = 0; i < TM; ++i)
+        for (int i = 0; i < TM; ++i)
 #pragma unroll
-        for (int j = 0; j < TN; ++j) {
-            const int n = n0 + wn * (32 * TN) + j * 32 + r;
+            for (int j = 0; j < TN; ++j) {
+                const int n = n0 + wn * (32 * TN) + j * 32 + r;
 #pragma unroll
-            for (int e = 0; e < 16; ++e) {
-                const int m = m0 + wm * (32 * TM) + i * 32 + (e & 3) + 8 * (e >> 2) + 4 * h;
-                if (ws) ws[(long)m * d.N + n] = acc[i][j][e];
-                else epilogue_store(d, C, m, n, acc[i][j][e], key);
+                for (int e = 0; e < 16; ++e) {
+                    const int m = m0 + wm * (32 * TM) + i * 32 + (e & 3) + 8 * (e >> 2) + 4 * h;
+                    if (ws) ws[(long)m * d.N + n] = acc[i][j][e];
+                    else epilogue_store<decltype(cmap)::value>(d, C, m, n, acc[i][j][e], key);
+                }
             }
-        }
+    });
 }
 
 template <bool CONV_A, int WM, int WN, int TM, int TN, int PF>
@@ -1063,15 +1130,19 @@ __global__ __launch_bounds__(512) void gemm_bf16src256_kernel(GemmK g, const __b
     const RngKey key = rng_key(d.seed, d.site);
     float* ws = d.splitk > 1 ? d.ws + (long)split * (long)d.M * d.N : nullptr;
     float* stg = reinterpret_cast<float*>(smem16) + wave * 4096;
-    const bool vec_ok = ws || ((reinterpret_cast<uintptr_t>(d.C) & 15) == 0 && d.ldc % 4 == 0);
+    const bool vec_ok = ws || ((reinterpret_cast<uintptr_t>(d.C) & 15) == 0 && d.ldc % 4 == 0 && !d.ccol_mod);
     const float inv_keep = d.drop_p > 0.f ? 1.0f / (1.0f - d.drop_p) : 1.0f;
     // (KM: wave column wc owns columns (wc >> 1) * 128 + j * 64 + (wc & 1) * 32 + r, so that a B half-tile's k-rows are whole
     // 128-byte lines in memory like the A half-tile's)
     const int c4 = (lane & 15) * 4, n = n0 + (KM ? (wc >> 1) * 128 + (c4 >> 5) * 64 + (wc & 1) * 32 + (c4 & 31) : wc * 64 + c4);
-    f32x4 bias = {0.f, 0.f, 0.f, 0.f};
+    f32x4 bias = {0.f, 0.f, 0.f, 0.f}, r1n = {0.f, 0.f, 0.f, 0.f};
     if (!ws) {
 #pragma unroll
         for (int c = 0; c < 4; ++c) bias[c] = (d.bias1 ? d.bias1[n + c] : 0.f) + (d.bias2 ? d.bias2[n + c] : 0.f);
+        if (d.r1_m) {
+#pragma unroll
+            for (int c = 0; c < 4; ++c) r1n[c] = d.r1_n[n + c];
+        }
     }
     __syncthreads();
 #pragma unroll
@@ -1095,14 +1166,25 @@ __global__ __launch_bounds__(512) void gemm_bf16src256_kernel(GemmK g, const __b
                 if (d.drop_p > 0.f) x = rng_keep(key, ibase + c, d.drop_p) ? x * inv_keep : 0.f;
                 v[c] = x;
             }
+            if (d.r1_m) {
+                const float r1m = d.r1_m[m];
+#pragma unroll
+                for (int c = 0; c < 4; ++c) v[c] = add_rank1(v[c], r1m, r1n[c]);
+            }
             const long mo = d.crow_mod ? (long)(m % d.crow_mod) * d.crow_mul + m / d.crow_mod : (long)m;
-            float* pc = d.C + mo * d.ldc + n;
+            float* pr = d.C + mo * d.ldc;
             if (vec_ok) {
+                float* pc = pr + n;
                 if (d.beta != 0.f) v += d.beta * *reinterpret_cast<const f32x4*>(pc);
                 *reinterpret_cast<f32x4*>(pc) = v;
             } else {
+                with_col_map(d, [&](auto cmap) {
 #pragma unroll
-                for (int c = 0; c < 4; ++c) pc[c] = d.beta != 0.f ? v[c] + d.beta * pc[c] : v[c];
+                    for (int c = 0; c < 4; ++c) {
+                        float* pc = pr + out_col<decltype(cmap)::value>(d, n + c);
+                        *pc = d.beta != 0.f ? v[c] + d.beta * *pc : v[c];
+                    }
+                });
             }
         }
         if (p == 0) __syncthreads();
@@ -1254,6 +1336,9 @@ int check_gemm(const GemmDesc& d) {
     }
     T2_REQUIRE(d.conv_a || d.sam == 1 || d.sak == 1, "gemm: A needs one unit stride (sam=%ld sak=%ld)", d.sam, d.sak);
     T2_REQUIRE(d.conv_b || d.sbn == 1 || d.sbk == 1, "gemm: B needs one unit stride (sbn=%ld sbk=%ld)", d.sbn, d.sbk);
+    T2_REQUIRE(d.ccol_mod >= 0 && d.ccol_mul >= 0 && (!d.ccol_mod || (d.N % d.ccol_mod == 0 && (long)d.ccol_mul * d.ccol_mod >= d.N && (long)d.ccol_mul * d.ccol_mod <= d.ldc)),
+               "gemm: bad column map (N=%d mod=%d mul=%d)", d.N, d.ccol_mod, d.ccol_mul);
+    T2_REQUIRE(!d.r1_m == !d.r1_n && (!d.r1_m || d.batch == 1), "gemm: the rank-1 addend needs both vectors and batch == 1");
     T2_REQUIRE(d.drop_p == 0.f || (d.batch == 1 && (long)d.M * d.N < (1l << 32)), "gemm: dropout epilogue needs batch==1 and M*N < 2^32");
     return 0;
 }

@@ -36,6 +36,12 @@ struct GemmDesc {
                                                   // copies are single-bf16 data and that mode ignores them
     int crow_mod; long crow_mul;                  // output row = (m % crow_mod) * crow_mul + m / crow_mod (0 = identity):
                                                   // writes time-major rows (t,b) in batch-major order (b,t) or back
+    int ccol_mod, ccol_mul;                       // output column = (n % ccol_mod) * ccol_mul + n / ccol_mod (0 = identity): the conv
+                                                  // weight gradient, computed as [Cout][K*Cin], lands as [Cout][Cin][K].  Columns of a
+                                                  // row are then no longer adjacent, so every kernel stores them one by one
+    const float* r1_m; const float* r1_n;         // optional rank-1 addend r1_m[m] * r1_n[n] (both or neither; batch == 1), added to the
+                                                  // finished element after activation and dropout and before the beta term, as a
+                                                  // rounded product and a rounded sum: the bits of a K = 1, beta = 1 product on top
 };
 inline GemmDesc gemm_desc() {
     GemmDesc d{}; d.batch = 1; d.alpha = 1.f; d.beta = 0.f; d.act = ACT_NONE; d.drop_p = 0.f; return d;
@@ -98,6 +104,11 @@ void gemm_counts(uint64_t* out, int reset);
 // split-bf16 mode: products below 2*M*N*K = mflop * 1e6 run the exact fp32 kernel (mflop < 0: the built-in default)
 void set_gemm_split_min_mflop(int mflop);
 void set_gemm_staging(int on);   // bf16 mode: stage fp32 operands as bf16 copies for the bf16-source kernel (default on)
+// 1 (default): callers fold work into a product's stores instead of running a pass of its own over the output: the gate
+// term of dDOUT as a rank-1 addend (c_api.hip), the conv weight gradient written in the reference layout through the
+// column map (conv.hip).  0: the separate K = 1 product and the unpermute kernel.  Same bits either way.
+void set_gemm_fold(int on);
+int get_gemm_fold();
 
 // ------------------------------------------------------------------ LSTM (lstm.hip)
 constexpr int kMaxSeg = 6;
