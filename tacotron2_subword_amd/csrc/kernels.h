@@ -1,4 +1,4 @@
-// Internal launcher interface between the C-ABI layer (c_api.hip) and the kernel files.
+// Internal launcher interface between the host layer (decoder.hip: decoder drivers; c_api.hip: C ABI) and the kernel files.
 // Everything takes raw device pointers and enqueues on the given stream; nothing allocates
 // or synchronises.
 #pragma once
@@ -105,7 +105,7 @@ void gemm_counts(uint64_t* out, int reset);
 void set_gemm_split_min_mflop(int mflop);
 void set_gemm_staging(int on);   // bf16 mode: stage fp32 operands as bf16 copies for the bf16-source kernel (default on)
 // 1 (default): callers fold work into a product's stores instead of running a pass of its own over the output: the gate
-// term of dDOUT as a rank-1 addend (c_api.hip), the conv weight gradient written in the reference layout through the
+// term of dDOUT as a rank-1 addend (decoder.hip), the conv weight gradient written in the reference layout through the
 // column map (conv.hip).  0: the separate K = 1 product and the unpermute kernel.  Same bits either way.
 void set_gemm_fold(int on);
 int get_gemm_fold();
@@ -221,7 +221,7 @@ struct AttnStepDesc {
     AttnStream st[2]; int nstreams; int B, A, E; int kind;   // kind 0 = SMA, 1 = LSA
     int F, Kc; float noise_std; uint64_t seed; int first;                     // kind 2 = GMM (attention_gmm_step_fwd)
     int lsa_pa;                                               // set by the launcher (MFMA path of the LSA dense projection)
-    int max_pos;                                              // > 0: valid length clamped to max_pos (ForwardAttentionV2, see c_api.hip)
+    int max_pos;                                              // > 0: valid length clamped to max_pos (ForwardAttentionV2, see decoder.hip)
 };
 int attention_step_fwd(const AttnStepDesc& d, hipStream_t s);
 
