@@ -87,46 +87,104 @@ __device__ __forceinline__ void store_rows(float* __restrict__ lds, const f32x4 
     }
 }
 
-// Forward stage: A [MT*32][PA], B [32][PA], both K-contiguous.  Wave w owns k in [w*BKT/8, (w+1)*BKT/8).
-// Lane (r, hk) reads 4 consecutive k (ds_read_b128, conflict-free at pitch BKT+4) and feeds element j
-// to MFMA j — A and B use the same k permutation, so each product pairs the same k.
-template <int MT, int BKT>
-__device__ __forceinline__ void compute_stage_fwd(const float* __restrict__ As, const float* __restrict__ Bs, int wave, int r, int hk,
-                                                  f32x16 (&acc)[MT]) {
-    constexpr int PA = BKT + 4;
+template <int MT> __device__ __forceinline__ void zero_acc(f32x16 (&acc)[MT]) {
 #pragma unroll
-    for (int kk = 0; kk < BKT / NW; kk += 8) {
-        const int k = wave * (BKT / NW) + kk + 4 * hk;
-        const f32x4 b4 = *reinterpret_cast<const f32x4*>(Bs + r * PA + k);
-        f32x4 a4[MT];
+    for (int m = 0; m < MT; ++m)
 #pragma unroll
-        for (int m = 0; m < MT; ++m) a4[m] = *reinterpret_cast<const f32x4*>(As + (m * 32 + r) * PA + k);
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-#pragma unroll
-            for (int m = 0; m < MT; ++m) acc[m] = __builtin_amdgcn_mfma_f32_32x32x2f32(a4[m][j], b4[j], acc[m], 0, 0, 0);
-    }
+        for (int e = 0; e < 16; ++e) acc[m][e] = 0.f;
 }
-// Backward stage: A as above, B [BKT k][PBN] with n contiguous.
-template <int MT, int BKT>
-__device__ __forceinline__ void compute_stage_bwd(const float* __restrict__ As, const float* __restrict__ Bs, int wave, int r, int hk,
-                                                  f32x16 (&acc)[MT]) {
-    constexpr int PA = BKT + 4, PBN = Tile<MT, BKT>::PBN;
-#pragma unroll
-    for (int kk = 0; kk < BKT / NW; kk += 8) {
-        const int k = wave * (BKT / NW) + kk + 4 * hk;
-        float b[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) b[j] = Bs[(k + j) * PBN + r];
-        f32x4 a4[MT];
-#pragma unroll
-        for (int m = 0; m < MT; ++m) a4[m] = *reinterpret_cast<const f32x4*>(As + (m * 32 + r) * PA + k);
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-#pragma unroll
-            for (int m = 0; m < MT; ++m) acc[m] = __builtin_amdgcn_mfma_f32_32x32x2f32(a4[m][j], b[j], acc[m], 0, 0, 0);
+
+// ---------------------------------------------------------------------------------------------
+// Operand families.  The step and gradient kernels below are one skeleton each; a family says what differs: the LDS
+// layout of a stage (TL, and where the tiles lie in it), the registers of a stage in flight (RegsA, RegsB), registers ->
+// LDS (store) and the MFMA sequence of one stage (compute).  Where the operand rows come from stays with the kernels, which
+// hand `load` one row-pointer functor per operand plane.
+// ---------------------------------------------------------------------------------------------
+// Exact family (fp32 operands, v_mfma_f32_32x32x2_f32), forward stage: A [MT*32][PA], B [32][PA], both K-contiguous.
+template <int MT, int BKT> struct Exact {
+    using TL = Tile<MT, BKT>;
+    static constexpr int family = LSTM_EXACT, fwd_depth = 1;
+    static constexpr bool stamps = true;
+    using RegsA = f32x4[TL::QA];
+    using RegsB = f32x4[TL::QB];
+    float *As, *Bs;
+    __device__ explicit Exact(float* smem) : As(smem), Bs(smem + TL::A_FLOATS) {}
+    template <typename RowA, typename RowB>
+    __device__ __forceinline__ static void load(int k0, RegsA& ga, RegsB& gb, RowA arow, RowB brow) {
+        load_rows<MT * 32, BKT, TL::QA>(arow, k0, ga);
+        load_rows<32, BKT, TL::QB>(brow, k0, gb);
     }
-}
+    __device__ __forceinline__ void store(const RegsA& ga, const RegsB& gb) const {
+        store_rows<BKT, TL::QA>(As, ga);
+        store_rows<BKT, TL::QB>(Bs, gb);
+    }
+    // Wave w owns k in [w*BKT/8, (w+1)*BKT/8).  Lane (r, hk) reads 4 consecutive k (ds_read_b128, conflict-free at pitch
+    // BKT+4) and feeds element j to MFMA j — A and B use the same k permutation, so each product pairs the same k.
+    __device__ __forceinline__ void compute(int wave, int r, int hk, f32x16 (&acc)[MT]) const {
+        constexpr int PA = TL::PA;
+#pragma unroll
+        for (int kk = 0; kk < BKT / NW; kk += 8) {
+            const int k = wave * (BKT / NW) + kk + 4 * hk;
+            const f32x4 b4 = *reinterpret_cast<const f32x4*>(Bs + r * PA + k);
+            f32x4 a4[MT];
+#pragma unroll
+            for (int m = 0; m < MT; ++m) a4[m] = *reinterpret_cast<const f32x4*>(As + (m * 32 + r) * PA + k);
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+#pragma unroll
+                for (int m = 0; m < MT; ++m) acc[m] = __builtin_amdgcn_mfma_f32_32x32x2f32(a4[m][j], b4[j], acc[m], 0, 0, 0);
+        }
+    }
+};
+
+// Exact family, gradient stage: A as above, B [BKT k][PBN] with n contiguous — the fp32 weights are read as they lie
+// (W rows k of the column tile), a layout of its own and not the K-contiguous rows every other stage stores.
+struct KnRows { const float* base; long ld; bool vec; };       // W[k][n0..n0+32) from row k = 0 of the K-split; vec: 16-byte loads are aligned
+template <int MT, int BKT> struct ExactKN {
+    using TL = Tile<MT, BKT>;
+    static constexpr int family = LSTM_EXACT;
+    using RegsA = f32x4[TL::QA];
+    using RegsB = f32x4[TL::QB];
+    float *As, *Bs;
+    __device__ explicit ExactKN(float* smem) : As(smem), Bs(smem + TL::A_FLOATS) {}
+    // B tile: BKT k-rows x 32 columns, n-contiguous: thread quad q -> (k = q/8, 4 n's)
+    template <typename RowA>
+    __device__ __forceinline__ static void load(int k0, RegsA& ga, RegsB& gb, RowA arow, KnRows w) {
+        load_rows<MT * 32, BKT, TL::QA>(arow, k0, ga);
+#pragma unroll
+        for (int i = 0; i < TL::QB; ++i) {
+            const int q = threadIdx.x + i * NTH, k = q >> 3, n = (q & 7) * 4;
+            const float* p = w.base + (long)(k0 + k) * w.ld + n;
+            if (w.vec) gb[i] = *reinterpret_cast<const f32x4*>(p);
+            else gb[i] = f32x4{p[0], p[1], p[2], p[3]};
+        }
+    }
+    __device__ __forceinline__ void store(const RegsA& ga, const RegsB& gb) const {
+        store_rows<BKT, TL::QA>(As, ga);
+#pragma unroll
+        for (int i = 0; i < TL::QB; ++i) {
+            const int q = threadIdx.x + i * NTH, k = q >> 3, n = (q & 7) * 4;
+            *reinterpret_cast<f32x4*>(Bs + k * TL::PBN + n) = gb[i];
+        }
+    }
+    __device__ __forceinline__ void compute(int wave, int r, int hk, f32x16 (&acc)[MT]) const {
+        constexpr int PA = TL::PA, PBN = TL::PBN;
+#pragma unroll
+        for (int kk = 0; kk < BKT / NW; kk += 8) {
+            const int k = wave * (BKT / NW) + kk + 4 * hk;
+            float b[4];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) b[j] = Bs[(k + j) * PBN + r];
+            f32x4 a4[MT];
+#pragma unroll
+            for (int m = 0; m < MT; ++m) a4[m] = *reinterpret_cast<const f32x4*>(As + (m * 32 + r) * PA + k);
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+#pragma unroll
+                for (int m = 0; m < MT; ++m) acc[m] = __builtin_amdgcn_mfma_f32_32x32x2f32(a4[m][j], b[j], acc[m], 0, 0, 0);
+        }
+    }
+};
 
 // Pointwise operands that do not depend on the GEMM — pre-activations (+ biases), previous cell state and this
 // unit group's slice of the query projection W_q — are requested right after the first operand stage so that their
@@ -248,72 +306,8 @@ __device__ __forceinline__ void lstm_tail(const LstmStepDesc& d, const LstmStrea
     }
 }
 
-template <int MT, int BKT>
-__global__ __launch_bounds__(NTH) void lstm_step_fwd_kernel(LstmStepDesc d) {
-    using TL = Tile<MT, BKT>;
-    const LstmStream& st = d.st[blockIdx.y];
-    const int B = d.B, H = d.H;
-    const int u0 = blockIdx.x * HU;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int r = lane & 31, hk = lane >> 5;
-
-    T2_STAMP(0);
-    extern __shared__ __attribute__((aligned(16))) float smem[];
-    float* As = smem;
-    float* Bs = smem + TL::A_FLOATS;
-    float* part = smem;                              // [NW][32][PP], aliases the staging area after the K loop
-    float* hs = smem + TL::FWD_FLOATS;               // [MT*32][HU]   post-dropout h of this group
-
-    f32x16 acc[MT];
-#pragma unroll
-    for (int m = 0; m < MT; ++m)
-#pragma unroll
-        for (int e = 0; e < 16; ++e) acc[m][e] = 0.f;
-
-    int nstages = 0;
-    for (int s = 0; s < st.nseg; ++s) nstages += st.seg[s].k / BKT;
-
-    f32x4 ra[TL::QA], rb[TL::QB];
-    int seg = 0, kin = 0;                            // position of the NEXT stage to load
-    auto load_next = [&]() {
-        const LstmSeg sg = st.seg[seg];
-        load_rows<MT * 32, BKT, TL::QA>([&](int row, bool& ok) { ok = row < B; return sg.x + (long)(ok ? row : 0) * sg.ldx; }, kin, ra);
-        // column n = gate*8 + unit  ->  row (n/8)*H + u0 + n%8 of W
-        load_rows<32, BKT, TL::QB>([&](int n, bool& ok) { ok = true; return sg.w + (long)((n >> 3) * H + u0 + (n & 7)) * sg.ldw; }, kin, rb);
-        kin += BKT;
-        if (kin >= sg.k) { kin = 0; ++seg; }
-    };
-    if (nstages > 0) load_next();
-    // request the tail's operands now — but AFTER the first stage's operands (vector-memory operations complete
-    // in order: stage 0 must not queue behind these cold reads)
-    TailRegs<MT> tr;
-    tail_prefetch<MT>(d, st, u0, tr);
-
-    if (nstages > 0) {
-        store_rows<BKT, TL::QA>(As, ra);
-        store_rows<BKT, TL::QB>(Bs, rb);
-    }
-    __syncthreads();
-    T2_STAMP(1);
-    for (int c = 0; c < nstages; ++c) {
-        const bool more = c + 1 < nstages;
-        if (more) load_next();                       // the whole next stage is in flight during the MFMAs
-        compute_stage_fwd<MT, BKT>(As, Bs, wave, r, hk, acc);
-        __syncthreads();
-        if (more) {
-            store_rows<BKT, TL::QA>(As, ra);
-            store_rows<BKT, TL::QB>(Bs, rb);
-            __syncthreads();
-        }
-    }
-
-    T2_STAMP(2);
-    lstm_tail<MT>(d, st, u0, wave, r, hk, acc, part, hs, tr);
-    T2_STAMP(4);
-}
-
 // ---------------------------------------------------------------------------------------------
-// bf16-operand step (t2_set_precision(1), teacher-forced passes): the recurrent operands come from
+// bf16 family (t2_set_precision(1), teacher-forced passes): the recurrent operands come from
 // bf16 shadows — weights cast once per pass ([W_hh | W_ih[:, P:]] as ONE K-contiguous matrix) and
 // the bf16 copies of h / ctx that the producing kernels write next to the fp32 ones — so a step
 // moves half the bytes and the weight slices stay resident in the per-XCD L2s.  fp32 accumulate,
@@ -327,7 +321,8 @@ template <int MT, int BKT> struct Tile16 {
     static constexpr int QA = MT * 32 * (BKT / 8) / NTH, QB = 32 * (BKT / 8) / NTH;
     static constexpr int STAGE_FLOATS = (A_ELEMS + B_ELEMS + 1) / 2;
     static constexpr int PART_FLOATS = (MT >= 2 ? 2 : 1) * NW * 32 * PP;
-    static constexpr int SMEM_FLOATS = (STAGE_FLOATS > PART_FLOATS ? STAGE_FLOATS : PART_FLOATS);
+    static constexpr int FWD_FLOATS = (STAGE_FLOATS > PART_FLOATS ? STAGE_FLOATS : PART_FLOATS);
+    static constexpr int BWD_FLOATS = FWD_FLOATS;
 };
 
 template <int BKT, int Q, typename RowPtr>
@@ -353,100 +348,45 @@ __device__ __forceinline__ void store_rows16(__bf16* __restrict__ lds, const bf1
         *reinterpret_cast<bf16x8*>(lds + row * P + k) = regs[i];
     }
 }
-template <int MT, int BKT>
-__device__ __forceinline__ void compute_stage16(const __bf16* __restrict__ As, const __bf16* __restrict__ Bs, int wave, int r, int hk,
-                                                f32x16 (&acc)[MT]) {
-    constexpr int P = BKT + 8;
-#pragma unroll
-    for (int kk = 0; kk < BKT / NW; kk += 16) {
-        const int k = wave * (BKT / NW) + kk + 8 * hk;
-        const bf16x8 b = *reinterpret_cast<const bf16x8*>(Bs + r * P + k);
-#pragma unroll
-        for (int m = 0; m < MT; ++m) {
-            const bf16x8 a = *reinterpret_cast<const bf16x8*>(As + (m * 32 + r) * P + k);
-            acc[m] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, acc[m], 0, 0, 0);
-        }
-    }
-}
 
-template <int MT, int BKT>
-__global__ __launch_bounds__(NTH) void lstm_step_fwd_bf16_kernel(LstmStepDesc d) {
+template <int MT, int BKT> struct Bf16 {
     using TL = Tile16<MT, BKT>;
-    const LstmStream& st = d.st[blockIdx.y];
-    const int B = d.B, H = d.H;
-    const int u0 = blockIdx.x * HU;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int r = lane & 31, hk = lane >> 5;
-
-    T2_STAMP(0);
-    extern __shared__ __attribute__((aligned(16))) float smem[];
-    __bf16* As = reinterpret_cast<__bf16*>(smem);
-    __bf16* Bs = As + TL::A_ELEMS;
-    float* part = smem;
-    float* hs = smem + TL::SMEM_FLOATS;
-
-    f32x16 acc[MT];
-#pragma unroll
-    for (int m = 0; m < MT; ++m)
-#pragma unroll
-        for (int e = 0; e < 16; ++e) acc[m][e] = 0.f;
-
-    // Two register stage buffers: stage c+2 is requested while stage c is computed and stage c+1 is still in
-    // flight, so a workgroup keeps two full stages (~2 x 64 KB) outstanding — the K loop is a chain of L2/MALL
-    // round trips and one stage of prefetch left the CU idle for most of each trip.
-    const int nstages = st.k16 / BKT;
-#ifdef T2_STAMPS
-    {   // latency probes: one cold weight element, one cold activation element, one more of each (warm TLB?)
-        const volatile __bf16* wp = st.w16 + (long)u0 * st.ldw16;
-        float v0 = (float)wp[0];
-        __builtin_amdgcn_s_waitcnt(0);
-        T2_STAMP(5);
-        const volatile __bf16* xp = st.x16;
-        v0 += (float)xp[0];
-        __builtin_amdgcn_s_waitcnt(0);
-        T2_STAMP(6);
-        v0 += (float)wp[4096] + (float)xp[4096];
-        __builtin_amdgcn_s_waitcnt(0);
-        T2_STAMP(7);
-        if (v0 == 123.456f) hs[0] = v0;
+    static constexpr int family = LSTM_BF16, fwd_depth = 2;
+    static constexpr bool stamps = true;
+    using RegsA = bf16x8[TL::QA];
+    using RegsB = bf16x8[TL::QB];
+    __bf16 *As, *Bs;
+    __device__ explicit Bf16(float* smem) : As(reinterpret_cast<__bf16*>(smem)), Bs(As + TL::A_ELEMS) {}
+    template <typename RowA, typename RowB>
+    __device__ __forceinline__ static void load(int k0, RegsA& ga, RegsB& gb, RowA arow, RowB brow) {
+        load_rows16<BKT, TL::QA>(arow, k0, ga);
+        load_rows16<BKT, TL::QB>(brow, k0, gb);
     }
-#endif
-    bf16x8 ra0[TL::QA], rb0[TL::QB], ra1[TL::QA], rb1[TL::QB];
-    auto load_stage = [&](int c, bf16x8 (&ra)[TL::QA], bf16x8 (&rb)[TL::QB]) {
-        load_rows16<BKT, TL::QA>([&](int row, bool& ok) { ok = row < B; return st.x16 + (long)(ok ? row : 0) * st.ldx16; }, c * BKT, ra);
-        load_rows16<BKT, TL::QB>([&](int n, bool& ok) { ok = true; return st.w16 + (long)((n >> 3) * H + u0 + (n & 7)) * st.ldw16; }, c * BKT, rb);
-    };
-    if (nstages > 0) load_stage(0, ra0, rb0);
-    if (nstages > 1) load_stage(1, ra1, rb1);
-    TailRegs<MT> tr;
-    tail_prefetch<MT>(d, st, u0, tr);
-    if (nstages > 0) { store_rows16<BKT, TL::QA>(As, ra0); store_rows16<BKT, TL::QB>(Bs, rb0); }
-    __syncthreads();
-    T2_STAMP(1);
-    for (int c = 0; c < nstages; c += 2) {
-        if (c + 2 < nstages) load_stage(c + 2, ra0, rb0);
-        compute_stage16<MT, BKT>(As, Bs, wave, r, hk, acc);
-        __syncthreads();
-        if (c + 1 < nstages) {
-            store_rows16<BKT, TL::QA>(As, ra1); store_rows16<BKT, TL::QB>(Bs, rb1);
-            __syncthreads();
-            if (c + 3 < nstages) load_stage(c + 3, ra1, rb1);
-            compute_stage16<MT, BKT>(As, Bs, wave, r, hk, acc);
-            __syncthreads();
-            if (c + 2 < nstages) { store_rows16<BKT, TL::QA>(As, ra0); store_rows16<BKT, TL::QB>(Bs, rb0); __syncthreads(); }
+    __device__ __forceinline__ void store(const RegsA& ga, const RegsB& gb) const {
+        store_rows16<BKT, TL::QA>(As, ga);
+        store_rows16<BKT, TL::QB>(Bs, gb);
+    }
+    __device__ __forceinline__ void compute(int wave, int r, int hk, f32x16 (&acc)[MT]) const {
+        constexpr int P = TL::P;
+#pragma unroll
+        for (int kk = 0; kk < BKT / NW; kk += 16) {
+            const int k = wave * (BKT / NW) + kk + 8 * hk;
+            const bf16x8 b = *reinterpret_cast<const bf16x8*>(Bs + r * P + k);
+#pragma unroll
+            for (int m = 0; m < MT; ++m) {
+                const bf16x8 a = *reinterpret_cast<const bf16x8*>(As + (m * 32 + r) * P + k);
+                acc[m] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, acc[m], 0, 0, 0);
+            }
         }
     }
-    T2_STAMP(2);
-    lstm_tail<MT>(d, st, u0, wave, r, hk, acc, part, hs, tr);
-    T2_STAMP(4);
-}
+};
 
 // ---------------------------------------------------------------------------------------------
-// split-bf16 step (t2_set_precision(2) with t2_set_split_steps(1), teacher-forced passes): the recurrent product at
+// split-bf16 family (t2_set_precision(2) with t2_set_split_steps(1), teacher-forced passes): the recurrent product at
 // fp32-grade accuracy on the bf16 matrix pipe.  Weights come from hi / lo bf16 shadows (hi = bf16(w), lo = bf16(w - hi),
 // cast once per pass: the same 4 bytes per element as fp32), activations are read as fp32 rows and split in registers
 // on their way into LDS.  Per 16-wide K step and row tile: acc += a_hi.b_hi, += a_lo.b_hi, += a_hi.b_lo, in that order
-// (lo.lo is below fp32 rounding).  Same work split, K order across waves and tail as the bf16 step.
+// (lo.lo is below fp32 rounding).  Same work split, K order across waves and tail as the bf16 family.
 // ---------------------------------------------------------------------------------------------
 typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
 
@@ -457,12 +397,11 @@ template <int MT, int BKT> struct TileS {
     static constexpr int QB = 32 * (BKT / 8) / NTH;            // bf16x8 per thread and plane, B rows
     static constexpr int STAGE_FLOATS = A_ELEMS + B_ELEMS;     // two planes each, two bf16 per float
     static constexpr int PART_FLOATS = (MT >= 2 ? 2 : 1) * NW * 32 * PP;
-    static constexpr int SMEM_FLOATS = (STAGE_FLOATS > PART_FLOATS ? STAGE_FLOATS : PART_FLOATS);
+    static constexpr int FWD_FLOATS = (STAGE_FLOATS > PART_FLOATS ? STAGE_FLOATS : PART_FLOATS);
+    static constexpr int BWD_FLOATS = FWD_FLOATS;
     static_assert(QA >= 1 && QB >= 1 && BKT % (NW * 16) == 0, "stage too narrow for 8 waves");
-    static_assert((size_t)(SMEM_FLOATS + MT * 32 * HU) * 4 <= 160 * 1024, "stage does not fit the 160 KB of LDS");
+    static_assert((size_t)(FWD_FLOATS + MT * 32 * HU) * 4 <= 160 * 1024, "stage does not fit the 160 KB of LDS");
 };
-// stage widths by row-tile count: the widest that keeps A and B (two planes each) within LDS
-template <int MT> struct SplitBkt { static constexpr int fwd = MT == 1 ? 512 : MT == 2 ? 256 : 128, bwd = MT <= 2 ? 256 : 128; };
 
 // fp32 rows -> hi / lo planes: row-major [rows][P] each, the lo plane `plane` elements behind the hi plane
 template <int BKT, int Q>
@@ -481,82 +420,155 @@ __device__ __forceinline__ void store_rows_split(__bf16* __restrict__ lds, int p
         *reinterpret_cast<bf16x4*>(lds + plane + row * P + k) = lo;
     }
 }
-template <int MT, int BKT>
-__device__ __forceinline__ void compute_stage_split(const __bf16* __restrict__ As, const __bf16* __restrict__ Bs, int wave, int r, int hk,
-                                                    f32x16 (&acc)[MT]) {
+
+template <int MT, int BKT> struct Split {
     using TL = TileS<MT, BKT>;
-    constexpr int P = TL::P;
+    static constexpr int family = LSTM_SPLIT, fwd_depth = 2;
+    static constexpr bool stamps = false;
+    using RegsA = f32x4[TL::QA];
+    using RegsB = bf16x8[2][TL::QB];                           // hi, lo
+    __bf16 *As, *Bs;                                           // [hi | lo][MT*32][P], [hi | lo][32][P]
+    __device__ explicit Split(float* smem) : As(reinterpret_cast<__bf16*>(smem)), Bs(As + 2 * TL::A_ELEMS) {}
+    template <typename RowA, typename RowH, typename RowL>
+    __device__ __forceinline__ static void load(int k0, RegsA& ga, RegsB& gb, RowA arow, RowH bhrow, RowL blrow) {
+        load_rows<MT * 32, BKT, TL::QA>(arow, k0, ga);
+        load_rows16<BKT, TL::QB>(bhrow, k0, gb[0]);
+        load_rows16<BKT, TL::QB>(blrow, k0, gb[1]);
+    }
+    __device__ __forceinline__ void store(const RegsA& ga, const RegsB& gb) const {
+        store_rows_split<BKT, TL::QA>(As, TL::A_ELEMS, ga);
+        store_rows16<BKT, TL::QB>(Bs, gb[0]);
+        store_rows16<BKT, TL::QB>(Bs + TL::B_ELEMS, gb[1]);
+    }
+    __device__ __forceinline__ void compute(int wave, int r, int hk, f32x16 (&acc)[MT]) const {
+        constexpr int P = TL::P;
 #pragma unroll
-    for (int kk = 0; kk < BKT / NW; kk += 16) {
-        const int k = wave * (BKT / NW) + kk + 8 * hk;
-        const bf16x8 bh = *reinterpret_cast<const bf16x8*>(Bs + r * P + k);
-        const bf16x8 bl = *reinterpret_cast<const bf16x8*>(Bs + TL::B_ELEMS + r * P + k);
+        for (int kk = 0; kk < BKT / NW; kk += 16) {
+            const int k = wave * (BKT / NW) + kk + 8 * hk;
+            const bf16x8 bh = *reinterpret_cast<const bf16x8*>(Bs + r * P + k);
+            const bf16x8 bl = *reinterpret_cast<const bf16x8*>(Bs + TL::B_ELEMS + r * P + k);
 #pragma unroll
-        for (int m = 0; m < MT; ++m) {
-            const bf16x8 ah = *reinterpret_cast<const bf16x8*>(As + (m * 32 + r) * P + k);
-            const bf16x8 al = *reinterpret_cast<const bf16x8*>(As + TL::A_ELEMS + (m * 32 + r) * P + k);
-            acc[m] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bh, acc[m], 0, 0, 0);
-            acc[m] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, bh, acc[m], 0, 0, 0);
-            acc[m] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bl, acc[m], 0, 0, 0);
+            for (int m = 0; m < MT; ++m) {
+                const bf16x8 ah = *reinterpret_cast<const bf16x8*>(As + (m * 32 + r) * P + k);
+                const bf16x8 al = *reinterpret_cast<const bf16x8*>(As + TL::A_ELEMS + (m * 32 + r) * P + k);
+                acc[m] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bh, acc[m], 0, 0, 0);
+                acc[m] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, bh, acc[m], 0, 0, 0);
+                acc[m] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bl, acc[m], 0, 0, 0);
+            }
         }
+    }
+};
+
+// ---------------------------------------------------------------------------------------------
+// The stage pipeline of every step and gradient kernel, over the prefetch depth.  DEPTH 1: the whole next stage is in
+// flight during the MFMAs of the current one.  DEPTH 2 (the ping-pong of the bf16 and split forward steps): stage c+2 is
+// requested while stage c is computed and stage c+1 is still in flight, so a workgroup keeps two full stages
+// (~2 x 64 KB) outstanding — their K loop is a chain of L2/MALL round trips and one stage of prefetch left the CU idle
+// for most of each trip.  `load(c, ra, rb)` requests stage c; `requested()` runs once the first DEPTH stages are requested
+// and `staged()` once stage 0 is in LDS.  nstages == 0 stores and computes nothing.
+// ---------------------------------------------------------------------------------------------
+template <int DEPTH, int MT, typename F, typename Load, typename Requested, typename Staged>
+__device__ __forceinline__ void stage_pipeline(const F& fam, int nstages, Load load, Requested requested, Staged staged,
+                                               int wave, int r, int hk, f32x16 (&acc)[MT]) {
+    static_assert(DEPTH == 1 || DEPTH == 2, "prefetch depth");
+    typename F::RegsA ra[DEPTH];                     // stage c travels in ra / rb[c % DEPTH]
+    typename F::RegsB rb[DEPTH];
+    if (nstages > 0) load(0, ra[0], rb[0]);
+    if constexpr (DEPTH == 2) if (nstages > 1) load(1, ra[1], rb[1]);
+    requested();
+    if (nstages > 0) fam.store(ra[0], rb[0]);
+    __syncthreads();
+    staged();
+    // one stage: its registers (a, b) are free for stage c + DEPTH; the next stage waits in (an, bn)
+    auto step = [&](int c, typename F::RegsA& a, typename F::RegsB& b, typename F::RegsA& an, typename F::RegsB& bn) {
+        if (c + DEPTH < nstages) load(c + DEPTH, a, b);
+        fam.compute(wave, r, hk, acc);
+        __syncthreads();
+        const bool more = c + 1 < nstages;
+        if (more) {
+            fam.store(an, bn);
+            __syncthreads();
+        }
+        return more;
+    };
+    for (int c = 0; c < nstages; c += DEPTH) {
+        if constexpr (DEPTH == 1) step(c, ra[0], rb[0], ra[0], rb[0]);
+        else if (step(c, ra[0], rb[0], ra[1], rb[1])) step(c + 1, ra[1], rb[1], ra[0], rb[0]);
     }
 }
 
-template <int MT, int BKT>
-__global__ __launch_bounds__(NTH) void lstm_step_fwd_split_kernel(LstmStepDesc d) {
-    using TL = TileS<MT, BKT>;
+// The forward step of every family.  The operand rows: exact, a list of K segments (x_seg, W_seg), walked in order;
+// bf16, the x16 / w16 shadows; split, the fp32 rows xs and the hi / lo shadows w16 / w16lo.
+template <template <int, int> class FAM, int MT, int BKT>
+__global__ __launch_bounds__(NTH) void lstm_step_fwd_kernel(LstmStepDesc d) {
+    using F = FAM<MT, BKT>;
     const LstmStream& st = d.st[blockIdx.y];
     const int B = d.B, H = d.H;
     const int u0 = blockIdx.x * HU;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int r = lane & 31, hk = lane >> 5;
+    auto stamp = [&](int i) { if constexpr (F::stamps) { T2_STAMP(i); } (void)i; };
 
+    stamp(0);
     extern __shared__ __attribute__((aligned(16))) float smem[];
-    __bf16* As = reinterpret_cast<__bf16*>(smem);              // [hi | lo][MT*32][P]
-    __bf16* Bs = As + 2 * TL::A_ELEMS;                         // [hi | lo][32][P]
-    float* part = smem;
-    float* hs = smem + TL::SMEM_FLOATS;
+    const F fam(smem);
+    float* part = smem;                              // [NW][32][PP], aliases the staging area after the K loop
+    float* hs = smem + F::TL::FWD_FLOATS;            // [MT*32][HU]   post-dropout h of this group
 
     f32x16 acc[MT];
-#pragma unroll
-    for (int m = 0; m < MT; ++m)
-#pragma unroll
-        for (int e = 0; e < 16; ++e) acc[m][e] = 0.f;
+    zero_acc(acc);
 
-    // two register stage buffers, as in the bf16 step; t = 0 has k16 = 0 and goes straight to the tail
-    const int nstages = st.k16 / BKT;
-    f32x4 ra0[TL::QA], ra1[TL::QA];
-    bf16x8 rh0[TL::QB], rl0[TL::QB], rh1[TL::QB], rl1[TL::QB];
-    auto load_stage = [&](int c, f32x4 (&ra)[TL::QA], bf16x8 (&rh)[TL::QB], bf16x8 (&rl)[TL::QB]) {
-        load_rows<MT * 32, BKT, TL::QA>([&](int row, bool& ok) { ok = row < B; return st.xs + (long)(ok ? row : 0) * st.ldxs; }, c * BKT, ra);
-        load_rows16<BKT, TL::QB>([&](int n, bool& ok) { ok = true; return st.w16 + (long)((n >> 3) * H + u0 + (n & 7)) * st.ldw16; }, c * BKT, rh);
-        load_rows16<BKT, TL::QB>([&](int n, bool& ok) { ok = true; return st.w16lo + (long)((n >> 3) * H + u0 + (n & 7)) * st.ldw16; }, c * BKT, rl);
-    };
-    auto store_stage = [&](const f32x4 (&ra)[TL::QA], const bf16x8 (&rh)[TL::QB], const bf16x8 (&rl)[TL::QB]) {
-        store_rows_split<BKT, TL::QA>(As, TL::A_ELEMS, ra);
-        store_rows16<BKT, TL::QB>(Bs, rh);
-        store_rows16<BKT, TL::QB>(Bs + TL::B_ELEMS, rl);
-    };
-    if (nstages > 0) load_stage(0, ra0, rh0, rl0);
-    if (nstages > 1) load_stage(1, ra1, rh1, rl1);
-    TailRegs<MT> tr;
-    tail_prefetch<MT>(d, st, u0, tr);
-    if (nstages > 0) store_stage(ra0, rh0, rl0);
-    __syncthreads();
-    for (int c = 0; c < nstages; c += 2) {
-        if (c + 2 < nstages) load_stage(c + 2, ra0, rh0, rl0);
-        compute_stage_split<MT, BKT>(As, Bs, wave, r, hk, acc);
-        __syncthreads();
-        if (c + 1 < nstages) {
-            store_stage(ra1, rh1, rl1);
-            __syncthreads();
-            if (c + 3 < nstages) load_stage(c + 3, ra1, rh1, rl1);
-            compute_stage_split<MT, BKT>(As, Bs, wave, r, hk, acc);
-            __syncthreads();
-            if (c + 2 < nstages) { store_stage(ra0, rh0, rl0); __syncthreads(); }
-        }
+    // t = 0 of the 16-bit families has k16 = 0 and goes straight to the tail
+    int nstages = 0;
+    if constexpr (F::family == LSTM_EXACT) for (int s = 0; s < st.nseg; ++s) nstages += st.seg[s].k / BKT;
+    else nstages = st.k16 / BKT;
+#ifdef T2_STAMPS
+    if constexpr (F::family == LSTM_BF16) {
+        // latency probes: one cold weight element, one cold activation element, one more of each (warm TLB?)
+        const volatile __bf16* wp = st.w16 + (long)u0 * st.ldw16;
+        float v0 = (float)wp[0];
+        __builtin_amdgcn_s_waitcnt(0);
+        T2_STAMP(5);
+        const volatile __bf16* xp = st.x16;
+        v0 += (float)xp[0];
+        __builtin_amdgcn_s_waitcnt(0);
+        T2_STAMP(6);
+        v0 += (float)wp[4096] + (float)xp[4096];
+        __builtin_amdgcn_s_waitcnt(0);
+        T2_STAMP(7);
+        if (v0 == 123.456f) hs[0] = v0;
     }
+#endif
+    // row sources are branch-free (load_rows): batch rows >= B are clamped to row 0 and reported invalid;
+    // column n = gate*8 + unit  ->  row (n/8)*H + u0 + n%8 of W
+    int seg = 0, kin = 0;                            // exact family: position of the NEXT stage to load
+    auto load = [&](int c, typename F::RegsA& ga, typename F::RegsB& gb) {
+        if constexpr (F::family == LSTM_EXACT) {
+            const LstmSeg sg = st.seg[seg];
+            F::load(kin, ga, gb, [&](int row, bool& ok) { ok = row < B; return sg.x + (long)(ok ? row : 0) * sg.ldx; },
+                    [&](int n, bool& ok) { ok = true; return sg.w + (long)((n >> 3) * H + u0 + (n & 7)) * sg.ldw; });
+            kin += BKT;
+            if (kin >= sg.k) { kin = 0; ++seg; }
+        } else {
+            auto x16row = [&](int row, bool& ok) { ok = row < B; return st.x16 + (long)(ok ? row : 0) * st.ldx16; };
+            auto xsrow = [&](int row, bool& ok) { ok = row < B; return st.xs + (long)(ok ? row : 0) * st.ldxs; };
+            auto whrow = [&](int n, bool& ok) { ok = true; return st.w16 + (long)((n >> 3) * H + u0 + (n & 7)) * st.ldw16; };
+            auto wlrow = [&](int n, bool& ok) { ok = true; return st.w16lo + (long)((n >> 3) * H + u0 + (n & 7)) * st.ldw16; };
+            if constexpr (F::family == LSTM_BF16) F::load(c * BKT, ga, gb, x16row, whrow);
+            else F::load(c * BKT, ga, gb, xsrow, whrow, wlrow);
+        }
+    };
+    TailRegs<MT> tr;
+    stage_pipeline<F::fwd_depth>(
+        fam, nstages, load,
+        // request the tail's operands now — but AFTER the first stages' operands (vector-memory operations complete
+        // in order: stage 0 must not queue behind these cold reads)
+        [&] { tail_prefetch<MT>(d, st, u0, tr); },
+        [&] { stamp(1); }, wave, r, hk, acc);
+
+    stamp(2);
     lstm_tail<MT>(d, st, u0, wave, r, hk, acc, part, hs, tr);
+    stamp(4);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -674,122 +686,45 @@ __global__ __launch_bounds__(256) void lstm_bwd_pointwise_q_kernel(LstmBwdPointD
 // grid = (column tiles of 32, K-splits, streams), so the whole chip works on one step; same
 // LDS-staged chunk pipeline as the forward step (A = dg rows, B = W rows k, n-contiguous).
 // ---------------------------------------------------------------------------------------------
-template <int MT, int BKT>
+// The three families differ in the operand rows: exact, A = dg(t) rows and B = W rows k of the segment that holds this
+// column tile (ExactKN); bf16, A = the bf16 copy of dg(t) and B = the transposed bf16 weight shadow wt16[n][k]
+// (K-contiguous); split, A = the fp32 dg(t) rows, split into hi / lo on their way into LDS, and B = the hi / lo
+// transposed shadows, three MFMA terms per K step as in the forward step.  K-split z covers k in [z*kspan, (z+1)*kspan).
+template <template <int, int> class FAM, int MT, int BKT>
 __global__ __launch_bounds__(NTH) void lstm_bwd_gemm_kernel(LstmBwdGemmDesc d) {
-    using TL = Tile<MT, BKT>;
-    const LstmBwdGemmStream& st = d.st[blockIdx.z];
-    const int B = d.B;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int r = lane & 31, hk = lane >> 5;
-    // locate this column tile
-    int col0 = blockIdx.x * 32, sidx = 0, cbase = 0;
-    while (sidx < st.nseg - 1 && col0 >= cbase + st.seg[sidx].ncols) { cbase += st.seg[sidx].ncols; ++sidx; }
-    const LstmBwdSeg sg = st.seg[sidx];
-    const int kspan = d.H4 / d.KS, kbeg = blockIdx.y * kspan;
-    const int nstages = kspan / BKT;
-
-    extern __shared__ __attribute__((aligned(16))) float smem[];
-    float* As = smem;
-    float* Bs = smem + TL::A_FLOATS;
-    float* part = smem;
-
-    f32x16 acc[MT];
-#pragma unroll
-    for (int m = 0; m < MT; ++m)
-#pragma unroll
-        for (int e = 0; e < 16; ++e) acc[m][e] = 0.f;
-
-    // B tile: BKT k-rows x 32 columns, n-contiguous: thread quad q -> (k = q/8, 4 n's)
-    const float* wbase = sg.w + (long)kbeg * sg.ldw + (col0 - cbase);
-    const bool wvec = (sg.ldw % 4 == 0) && ((reinterpret_cast<uintptr_t>(sg.w) & 15) == 0);
-    f32x4 ra[TL::QA], rb[TL::QB];
-    auto load_stage = [&](int c) {
-        load_rows<MT * 32, BKT, TL::QA>([&](int row, bool& ok) { ok = row < B; return st.dg + (long)(ok ? row : 0) * st.lddg + kbeg; }, c * BKT, ra);
-#pragma unroll
-        for (int i = 0; i < TL::QB; ++i) {
-            const int q = threadIdx.x + i * NTH, k = q >> 3, n = (q & 7) * 4;
-            const float* p = wbase + (long)(c * BKT + k) * sg.ldw + n;
-            if (wvec) rb[i] = *reinterpret_cast<const f32x4*>(p);
-            else rb[i] = f32x4{p[0], p[1], p[2], p[3]};
-        }
-    };
-    auto store_stage = [&]() {
-        store_rows<BKT, TL::QA>(As, ra);
-#pragma unroll
-        for (int i = 0; i < TL::QB; ++i) {
-            const int q = threadIdx.x + i * NTH, k = q >> 3, n = (q & 7) * 4;
-            *reinterpret_cast<f32x4*>(Bs + k * TL::PBN + n) = rb[i];
-        }
-    };
-    load_stage(0);
-    store_stage();
-    __syncthreads();
-    for (int c = 0; c < nstages; ++c) {
-        const bool more = c + 1 < nstages;
-        if (more) load_stage(c + 1);
-        compute_stage_bwd<MT, BKT>(As, Bs, wave, r, hk, acc);
-        __syncthreads();
-        if (more) { store_stage(); __syncthreads(); }
-    }
-
-    float* out = st.part + (long)blockIdx.y * B * d.NC;
-#pragma unroll
-    for (int m = 0; m < MT; ++m) {
-        if (m > 0) __syncthreads();
-#pragma unroll
-        for (int e = 0; e < 16; ++e)
-            part[(wave * 32 + (e & 3) + 8 * (e >> 2) + 4 * hk) * PP + r] = acc[m][e];
-        __syncthreads();
-        for (int i = threadIdx.x; i < 32 * 32; i += NTH) {
-            const int bl = i >> 5, c = i & 31, b = m * 32 + bl;
-            if (b < B) {
-                float sum = 0.f;
-#pragma unroll
-                for (int w = 0; w < NW; ++w) sum += part[(w * 32 + bl) * PP + c];
-                out[(long)b * d.NC + col0 + c] = sum;
-            }
-        }
-    }
-}
-
-// bf16-operand variant of the recurrent-input gradient: A = bf16 copy of dg(t), B = transposed bf16
-// weight shadow wt16[n][k] (K-contiguous), K-split z covers k in [z*kspan, (z+1)*kspan).
-template <int MT>
-__global__ __launch_bounds__(NTH) void lstm_bwd_gemm_bf16_kernel(LstmBwdGemmDesc d) {
-    constexpr int BKT = 256;
-    using TL = Tile16<MT, BKT>;
+    using F = FAM<MT, BKT>;
     const LstmBwdGemmStream& st = d.st[blockIdx.z];
     const int B = d.B;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int r = lane & 31, hk = lane >> 5;
     const int col0 = blockIdx.x * 32;
-    const int kspan = d.H4 / d.KS, kbeg = blockIdx.y * kspan, nstages = kspan / BKT;
+    const int H4 = d.H4, kspan = H4 / d.KS, kbeg = blockIdx.y * kspan, nstages = kspan / BKT;
 
     extern __shared__ __attribute__((aligned(16))) float smem[];
-    __bf16* As = reinterpret_cast<__bf16*>(smem);
-    __bf16* Bs = As + TL::A_ELEMS;
-    float* part = smem;
+    const F fam(smem);
+    float* part = smem;                              // [NW][32][PP], aliases the staging area after the K loop
 
     f32x16 acc[MT];
-#pragma unroll
-    for (int m = 0; m < MT; ++m)
-#pragma unroll
-        for (int e = 0; e < 16; ++e) acc[m][e] = 0.f;
-    bf16x8 ra[TL::QA], rb[TL::QB];
-    auto load_stage = [&](int c) {
-        load_rows16<BKT, TL::QA>([&](int row, bool& ok) { ok = row < B; return st.dg16 + (long)(ok ? row : 0) * d.H4 + kbeg; }, c * BKT, ra);
-        load_rows16<BKT, TL::QB>([&](int n, bool& ok) { ok = true; return st.wt16 + (long)(col0 + n) * d.H4 + kbeg; }, c * BKT, rb);
-    };
-    load_stage(0);
-    store_rows16<BKT, TL::QA>(As, ra); store_rows16<BKT, TL::QB>(Bs, rb);
-    __syncthreads();
-    for (int c = 0; c < nstages; ++c) {
-        const bool more = c + 1 < nstages;
-        if (more) load_stage(c + 1);
-        compute_stage16<MT, BKT>(As, Bs, wave, r, hk, acc);
-        __syncthreads();
-        if (more) { store_rows16<BKT, TL::QA>(As, ra); store_rows16<BKT, TL::QB>(Bs, rb); __syncthreads(); }
+    zero_acc(acc);
+
+    KnRows wkn{};
+    if constexpr (F::family == LSTM_EXACT) {
+        // locate this column tile
+        int sidx = 0, cbase = 0;
+        while (sidx < st.nseg - 1 && col0 >= cbase + st.seg[sidx].ncols) { cbase += st.seg[sidx].ncols; ++sidx; }
+        const LstmBwdSeg sg = st.seg[sidx];
+        wkn = {sg.w + (long)kbeg * sg.ldw + (col0 - cbase), sg.ldw, (sg.ldw % 4 == 0) && ((reinterpret_cast<uintptr_t>(sg.w) & 15) == 0)};
     }
+    auto dgrow = [&](auto* dg, long ld) { return [=](int row, bool& ok) { ok = row < B; return dg + (long)(ok ? row : 0) * ld + kbeg; }; };
+    auto wtrow = [&](const __bf16* wt) { return [=](int n, bool& ok) { ok = true; return wt + (long)(col0 + n) * H4 + kbeg; }; };
+    auto load = [&](int c, typename F::RegsA& ga, typename F::RegsB& gb) {
+        if constexpr (F::family == LSTM_EXACT) F::load(c * BKT, ga, gb, dgrow(st.dg, st.lddg), wkn);
+        else if constexpr (F::family == LSTM_BF16) F::load(c * BKT, ga, gb, dgrow(st.dg16, H4), wtrow(st.wt16));
+        else F::load(c * BKT, ga, gb, dgrow(st.dg, st.lddg), wtrow(st.wt16), wtrow(st.wt16lo));
+    };
+    stage_pipeline<1>(fam, nstages, load, [] {}, [] {}, wave, r, hk, acc);
+
+    // partials through LDS one row tile at a time, the 8 waves summed in fixed order: part[z][b][n]
     float* out = st.part + (long)blockIdx.y * B * d.NC;
 #pragma unroll
     for (int m = 0; m < MT; ++m) {
@@ -810,84 +745,21 @@ __global__ __launch_bounds__(NTH) void lstm_bwd_gemm_bf16_kernel(LstmBwdGemmDesc
     }
 }
 
-// split-bf16 variant of the recurrent-input gradient: A = the fp32 dg(t) rows, split into hi / lo on their way into LDS,
-// B = hi / lo transposed weight shadows wt16[n][k]; three MFMA terms per K step as in the forward split step.  Same
-// K-split grid and part[z][b][n] partials as the other two variants.
-template <int MT>
-__global__ __launch_bounds__(NTH) void lstm_bwd_gemm_split_kernel(LstmBwdGemmDesc d) {
-    constexpr int BKT = SplitBkt<MT>::bwd;
-    using TL = TileS<MT, BKT>;
-    const LstmBwdGemmStream& st = d.st[blockIdx.z];
-    const int B = d.B;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int r = lane & 31, hk = lane >> 5;
-    const int col0 = blockIdx.x * 32;
-    const int kspan = d.H4 / d.KS, kbeg = blockIdx.y * kspan, nstages = kspan / BKT;
-
-    extern __shared__ __attribute__((aligned(16))) float smem[];
-    __bf16* As = reinterpret_cast<__bf16*>(smem);
-    __bf16* Bs = As + 2 * TL::A_ELEMS;
-    float* part = smem;
-
-    f32x16 acc[MT];
-#pragma unroll
-    for (int m = 0; m < MT; ++m)
-#pragma unroll
-        for (int e = 0; e < 16; ++e) acc[m][e] = 0.f;
-    f32x4 ra[TL::QA];
-    bf16x8 rh[TL::QB], rl[TL::QB];
-    auto load_stage = [&](int c) {
-        load_rows<MT * 32, BKT, TL::QA>([&](int row, bool& ok) { ok = row < B; return st.dg + (long)(ok ? row : 0) * st.lddg + kbeg; }, c * BKT, ra);
-        load_rows16<BKT, TL::QB>([&](int n, bool& ok) { ok = true; return st.wt16 + (long)(col0 + n) * d.H4 + kbeg; }, c * BKT, rh);
-        load_rows16<BKT, TL::QB>([&](int n, bool& ok) { ok = true; return st.wt16lo + (long)(col0 + n) * d.H4 + kbeg; }, c * BKT, rl);
-    };
-    auto store_stage = [&]() {
-        store_rows_split<BKT, TL::QA>(As, TL::A_ELEMS, ra);
-        store_rows16<BKT, TL::QB>(Bs, rh);
-        store_rows16<BKT, TL::QB>(Bs + TL::B_ELEMS, rl);
-    };
-    load_stage(0);
-    store_stage();
-    __syncthreads();
-    for (int c = 0; c < nstages; ++c) {
-        const bool more = c + 1 < nstages;
-        if (more) load_stage(c + 1);
-        compute_stage_split<MT, BKT>(As, Bs, wave, r, hk, acc);
-        __syncthreads();
-        if (more) { store_stage(); __syncthreads(); }
-    }
-    float* out = st.part + (long)blockIdx.y * B * d.NC;
-#pragma unroll
-    for (int m = 0; m < MT; ++m) {
-        if (m > 0) __syncthreads();
-#pragma unroll
-        for (int e = 0; e < 16; ++e)
-            part[(wave * 32 + (e & 3) + 8 * (e >> 2) + 4 * hk) * PP + r] = acc[m][e];
-        __syncthreads();
-        for (int i = threadIdx.x; i < 32 * 32; i += NTH) {
-            const int bl = i >> 5, c = i & 31, b = m * 32 + bl;
-            if (b < B) {
-                float sum = 0.f;
-#pragma unroll
-                for (int w = 0; w < NW; ++w) sum += part[(w * 32 + bl) * PP + c];
-                out[(long)b * d.NC + col0 + c] = sum;
-            }
-        }
-    }
-}
-
-// split casts, one pass for both planes: hi[..] = bf16(x), lo[..] = bf16(x - hi), indexed as in the two kernels below
-__global__ void cast_rows_split_kernel(const float* __restrict__ src, long lds_, __bf16* __restrict__ hi, __bf16* __restrict__ lo, long ldd, int R, int C) {
+// hi[r*ldd + c] = bf16(src[r*lds + c]); SPLIT: the lo plane in the same pass, lo[..] = bf16(x - hi), indexed alike
+template <bool SPLIT>
+__global__ void cast_rows_kernel(const float* __restrict__ src, long lds_, __bf16* __restrict__ hi, __bf16* __restrict__ lo, long ldd, int R, int C) {
     const size_t n = (size_t)R * C;
     for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
         const int c = (int)(i % C); const size_t rr = i / C;
         const float x = src[rr * lds_ + c];
         const __bf16 h = (__bf16)x;
         hi[rr * ldd + c] = h;
-        lo[rr * ldd + c] = (__bf16)(x - (float)h);
+        if (SPLIT) lo[rr * ldd + c] = (__bf16)(x - (float)h);
     }
 }
-__global__ void cast_transpose_split_kernel(const float* __restrict__ src, long lds_, __bf16* __restrict__ hi, __bf16* __restrict__ lo, long ldd, int R, int C) {
+// hi[c*ldd + r] = bf16(src[r*lds + c])   (32x32 LDS tiles); SPLIT as above
+template <bool SPLIT>
+__global__ void cast_transpose_kernel(const float* __restrict__ src, long lds_, __bf16* __restrict__ hi, __bf16* __restrict__ lo, long ldd, int R, int C) {
     __shared__ float tile[32][33];
     const int r0 = blockIdx.y * 32, c0 = blockIdx.x * 32;
     const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
@@ -902,59 +774,68 @@ __global__ void cast_transpose_split_kernel(const float* __restrict__ src, long 
             const float x = tile[tx][i];
             const __bf16 h = (__bf16)x;
             hi[(size_t)c * ldd + rr] = h;
-            lo[(size_t)c * ldd + rr] = (__bf16)(x - (float)h);
+            if (SPLIT) lo[(size_t)c * ldd + rr] = (__bf16)(x - (float)h);
         }
     }
 }
 
-// dst[r*ldd + c] = bf16(src[r*lds + c])
-__global__ void cast_rows_kernel(const float* __restrict__ src, long lds_, __bf16* __restrict__ dst, long ldd, int R, int C) {
-    const size_t n = (size_t)R * C;
-    for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
-        const int c = (int)(i % C); const size_t rr = i / C;
-        dst[rr * ldd + c] = (__bf16)src[rr * lds_ + c];
-    }
-}
-// dst[c*ldd + r] = bf16(src[r*lds + c])   (32x32 LDS tiles)
-__global__ void cast_transpose_kernel(const float* __restrict__ src, long lds_, __bf16* __restrict__ dst, long ldd, int R, int C) {
-    __shared__ float tile[32][33];
-    const int r0 = blockIdx.y * 32, c0 = blockIdx.x * 32;
-    const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
-    for (int i = ty; i < 32; i += 8) {
-        const int rr = r0 + i, c = c0 + tx;
-        tile[i][tx] = (rr < R && c < C) ? src[(size_t)rr * lds_ + c] : 0.f;
-    }
-    __syncthreads();
-    for (int i = ty; i < 32; i += 8) {
-        const int c = c0 + i, rr = r0 + tx;
-        if (c < C && rr < R) dst[(size_t)c * ldd + rr] = (__bf16)tile[tx][i];
-    }
-}
-
-template <int MT, int BKT> size_t fwd_smem() { return (size_t)(Tile<MT, BKT>::FWD_FLOATS + MT * 32 * HU) * sizeof(float); }
-template <int MT, int BKT> size_t bwd_smem() { return (size_t)Tile<MT, BKT>::BWD_FLOATS * sizeof(float); }
-
-// split-bf16 kernels: the stage (or the partial tiles), + the forward step's post-dropout h rows
-template <int MT, int BKT> size_t split_smem(bool fwd) { return (size_t)(TileS<MT, BKT>::SMEM_FLOATS + (fwd ? MT * 32 * HU : 0)) * sizeof(float); }
-
 template <typename K>
 int allow_big_lds(K kernel, size_t smem) { return t2_allow_dynamic_lds(reinterpret_cast<const void*>(kernel), smem); }
 
-// stage width by batch tile count (LDS budget) when every K extent allows it, else 64
-#define LAUNCH_ONE(KERNEL, SMEM, MTV, BKV, GRID, BLOCK, STREAM, DESC)                                 \
-    do {                                                                                              \
-        const size_t sm_ = SMEM<MTV, BKV>();                                                          \
-        int rc_ = allow_big_lds(KERNEL<MTV, BKV>, sm_);                                               \
-        if (rc_) return rc_;                                                                          \
-        hipLaunchKernelGGL((KERNEL<MTV, BKV>), GRID, BLOCK, sm_, STREAM, DESC);                       \
-    } while (0)
-#define LAUNCH_MT(KERNEL, SMEM, KDIV, GRID, BLOCK, STREAM, DESC)                                      \
-    do {                                                                                              \
-        if (MT <= 1) { if ((KDIV) % 256 == 0) LAUNCH_ONE(KERNEL, SMEM, 1, 256, GRID, BLOCK, STREAM, DESC); else LAUNCH_ONE(KERNEL, SMEM, 1, 64, GRID, BLOCK, STREAM, DESC); } \
-        else if (MT <= 2) { if ((KDIV) % 256 == 0) LAUNCH_ONE(KERNEL, SMEM, 2, 256, GRID, BLOCK, STREAM, DESC); else LAUNCH_ONE(KERNEL, SMEM, 2, 64, GRID, BLOCK, STREAM, DESC); } \
-        else if (MT <= 4) { if ((KDIV) % 128 == 0) LAUNCH_ONE(KERNEL, SMEM, 4, 128, GRID, BLOCK, STREAM, DESC); else LAUNCH_ONE(KERNEL, SMEM, 4, 64, GRID, BLOCK, STREAM, DESC); } \
-        else LAUNCH_ONE(KERNEL, SMEM, 8, 64, GRID, BLOCK, STREAM, DESC);                              \
-    } while (0)
+// ---------------------------------------------------------------------------------------------
+// Launching a step or a gradient product: the rule from (family, direction, row tiles, K divisibility) to the stage
+// width, the instantiations that exist, and the one function that launches them.
+// ---------------------------------------------------------------------------------------------
+// Stage width by row-tile count mt = 1 / 2 / 4 / 8 (LDS budget): the family's widest when every K extent is a multiple
+// of it (`wide`), else its narrow one.
+constexpr int stage_width(int family, bool fwd, int mt, bool wide) {
+    switch (family) {
+    case LSTM_EXACT: return !wide || mt == 8 ? 64 : mt == 4 ? 128 : 256;
+    case LSTM_BF16: return fwd && wide && mt <= 2 ? 512 : 256;            // 65..128 rows: 256-wide stages keep the A tile within LDS
+    default:                                                              // split: the widest that keeps A and B (two planes each) within LDS;
+        return mt == 4 ? 128 : fwd && wide && mt == 1 ? 512 : 256;        // 65..128 rows: 128-wide stages
+    }
+}
+
+template <typename Desc> struct StepInst { int family, mt, bkt; void (*kernel)(Desc); size_t smem; };
+// stage (or the partial tiles) + the post-dropout h rows of the tail
+template <template <int, int> class FAM, int MT, int BKT> StepInst<LstmStepDesc> fwd_inst() {
+    using F = FAM<MT, BKT>;
+    return {F::family, MT, BKT, lstm_step_fwd_kernel<FAM, MT, BKT>, (size_t)(F::TL::FWD_FLOATS + MT * 32 * HU) * sizeof(float)};
+}
+template <template <int, int> class FAM, int MT, int BKT> StepInst<LstmBwdGemmDesc> bwd_inst() {
+    using F = FAM<MT, BKT>;
+    return {F::family, MT, BKT, lstm_bwd_gemm_kernel<FAM, MT, BKT>, (size_t)F::TL::BWD_FLOATS * sizeof(float)};
+}
+const StepInst<LstmStepDesc> kFwdInst[] = {
+    fwd_inst<Exact, 1, 256>(), fwd_inst<Exact, 1, 64>(), fwd_inst<Exact, 2, 256>(), fwd_inst<Exact, 2, 64>(),
+    fwd_inst<Exact, 4, 128>(), fwd_inst<Exact, 4, 64>(), fwd_inst<Exact, 8, 64>(),
+    fwd_inst<Bf16, 1, 512>(), fwd_inst<Bf16, 1, 256>(), fwd_inst<Bf16, 2, 512>(), fwd_inst<Bf16, 2, 256>(), fwd_inst<Bf16, 4, 256>(),
+    fwd_inst<Split, 1, 512>(), fwd_inst<Split, 1, 256>(), fwd_inst<Split, 2, 256>(), fwd_inst<Split, 4, 128>(),
+};
+const StepInst<LstmBwdGemmDesc> kBwdInst[] = {
+    bwd_inst<ExactKN, 1, 256>(), bwd_inst<ExactKN, 1, 64>(), bwd_inst<ExactKN, 2, 256>(), bwd_inst<ExactKN, 2, 64>(),
+    bwd_inst<ExactKN, 4, 128>(), bwd_inst<ExactKN, 4, 64>(), bwd_inst<ExactKN, 8, 64>(),
+    bwd_inst<Bf16, 1, 256>(), bwd_inst<Bf16, 2, 256>(), bwd_inst<Bf16, 4, 256>(),
+    bwd_inst<Split, 1, 256>(), bwd_inst<Split, 2, 256>(), bwd_inst<Split, 4, 128>(),
+};
+
+// kdiv: a common divisor of every K extent of the launch
+template <typename Desc, size_t N>
+int launch_step(const StepInst<Desc> (&insts)[N], int fam, bool fwd, int kdiv, dim3 grid, const Desc& d, hipStream_t s, int* family) {
+    const int row_tiles = (d.B + 31) / 32, mt = row_tiles <= 1 ? 1 : row_tiles <= 2 ? 2 : row_tiles <= 4 ? 4 : 8;
+    const int wide = stage_width(fam, fwd, mt, true), bkt = kdiv % wide == 0 ? wide : stage_width(fam, fwd, mt, false);
+    for (const StepInst<Desc>& in : insts) {
+        if (in.family != fam || in.mt != mt || in.bkt != bkt) continue;
+        T2_TRY_RC(allow_big_lds(in.kernel, in.smem));
+        hipLaunchKernelGGL(in.kernel, grid, dim3(NTH), in.smem, s, d);
+        T2_LAUNCH_CHECK();
+        if (family) *family = fam;
+        return 0;
+    }
+    t2_set_error("lstm: no kernel for family %d, %d row tiles, stage width %d", fam, mt, bkt);
+    return -1;
+}
 
 }  // namespace
 
@@ -974,7 +855,9 @@ int lstm_step_fwd(const LstmStepDesc& d, hipStream_t s, int* family) {
         T2_REQUIRE(!st.wq || st.A * HU <= NW * 32 * PP, "lstm_step: attention dim %d too large", st.A);
     }
     const int MT = (d.B + 31) / 32;
-    dim3 grid(d.H / HU, d.nstreams), block(NTH);
+    const dim3 grid(d.H / HU, d.nstreams);
+    // the 16-bit families: one K extent per stream, 512-wide stages when those of the first two streams allow
+    const int k16div = d.st[0].k16 % 512 == 0 && (d.nstreams < 2 || d.st[1].k16 % 512 == 0) ? 512 : 256;
     if (d.st[0].w16lo) {                                 // split-bf16 step: fp32 activation rows, hi / lo weight shadows
         for (int i = 0; i < d.nstreams; ++i) {
             const LstmStream& st = d.st[i];
@@ -983,57 +866,20 @@ int lstm_step_fwd(const LstmStepDesc& d, hipStream_t s, int* family) {
                        "lstm_step: bad split-bf16 operands");
         }
         T2_REQUIRE(MT <= 4, "lstm_step: the split-bf16 step supports B <= 128");
-        const bool wide = d.st[0].k16 % 512 == 0 && (d.nstreams < 2 || d.st[1].k16 % 512 == 0);
-        auto go = [&](auto kernel, size_t smem) -> int {
-            T2_TRY_RC(allow_big_lds(kernel, smem));
-            hipLaunchKernelGGL(kernel, grid, block, smem, s, d);
-            return 0;
-        };
-        if (MT <= 1) {
-            if (wide) T2_TRY_RC(go(lstm_step_fwd_split_kernel<1, 512>, split_smem<1, 512>(true)));
-            else T2_TRY_RC(go(lstm_step_fwd_split_kernel<1, 256>, split_smem<1, 256>(true)));
-        } else if (MT <= 2) {
-            T2_TRY_RC(go(lstm_step_fwd_split_kernel<2, SplitBkt<2>::fwd>, split_smem<2, SplitBkt<2>::fwd>(true)));
-        } else {                                         // 65..128 rows: 128-wide stages keep both planes of A within LDS
-            T2_TRY_RC(go(lstm_step_fwd_split_kernel<4, SplitBkt<4>::fwd>, split_smem<4, SplitBkt<4>::fwd>(true)));
-        }
-        T2_LAUNCH_CHECK();
-        if (family) *family = LSTM_SPLIT;
-        return 0;
+        return launch_step(kFwdInst, LSTM_SPLIT, true, k16div, grid, d, s, family);
     }
-    bool bf = d.st[0].x16 != nullptr;
-    if (bf) {
+    if (d.st[0].x16) {
         for (int i = 0; i < d.nstreams; ++i)
             T2_REQUIRE(d.st[i].x16 && d.st[i].w16 && d.st[i].k16 % 256 == 0 && d.st[i].ldx16 % 8 == 0 && d.st[i].ldw16 % 8 == 0 &&
                        ((uintptr_t)d.st[i].x16 & 15) == 0 && ((uintptr_t)d.st[i].w16 & 15) == 0, "lstm_step: bad bf16 operands");
         T2_REQUIRE(MT <= 4, "lstm_step: the bf16-operand step supports B <= 128");
-        const bool wide = d.st[0].k16 % 512 == 0 && (d.nstreams < 2 || d.st[1].k16 % 512 == 0);
-        auto go = [&](auto kernel, size_t smem) -> int {
-            T2_TRY_RC(allow_big_lds(kernel, smem));
-            hipLaunchKernelGGL(kernel, grid, block, smem, s, d);
-            return 0;
-        };
-        if (MT <= 1) {
-            if (wide) T2_TRY_RC(go(lstm_step_fwd_bf16_kernel<1, 512>, (size_t)(Tile16<1, 512>::SMEM_FLOATS + 32 * HU) * 4));
-            else T2_TRY_RC(go(lstm_step_fwd_bf16_kernel<1, 256>, (size_t)(Tile16<1, 256>::SMEM_FLOATS + 32 * HU) * 4));
-        } else if (MT <= 2) {
-            if (wide) T2_TRY_RC(go(lstm_step_fwd_bf16_kernel<2, 512>, (size_t)(Tile16<2, 512>::SMEM_FLOATS + 64 * HU) * 4));
-            else T2_TRY_RC(go(lstm_step_fwd_bf16_kernel<2, 256>, (size_t)(Tile16<2, 256>::SMEM_FLOATS + 64 * HU) * 4));
-        } else {                                         // 65..128 rows: 256-wide stages keep the A tile within LDS
-            T2_TRY_RC(go(lstm_step_fwd_bf16_kernel<4, 256>, (size_t)(Tile16<4, 256>::SMEM_FLOATS + 128 * HU) * 4));
-        }
-        T2_LAUNCH_CHECK();
-        if (family) *family = LSTM_BF16;
-        return 0;
+        return launch_step(kFwdInst, LSTM_BF16, true, k16div, grid, d, s, family);
     }
     int kdiv = 0;                                    // gcd-like: every segment width must be a multiple of the stage width
     for (int i = 0; i < d.nstreams; ++i)
         for (int j = 0; j < d.st[i].nseg; ++j) kdiv = kdiv == 0 ? d.st[i].seg[j].k : std::gcd(kdiv, d.st[i].seg[j].k);
     if (kdiv == 0) kdiv = 256;
-    LAUNCH_MT(lstm_step_fwd_kernel, fwd_smem, kdiv, grid, block, s, d);
-    T2_LAUNCH_CHECK();
-    if (family) *family = LSTM_EXACT;
-    return 0;
+    return launch_step(kFwdInst, LSTM_EXACT, true, kdiv, grid, d, s, family);
 }
 
 int lstm_bwd_pointwise(const LstmBwdPointDesc& d, hipStream_t s) {
@@ -1076,75 +922,47 @@ int lstm_bwd_gemm(const LstmBwdGemmDesc& d, hipStream_t s, int* family) {
         for (int j = 0; j < d.st[i].nseg; ++j) T2_REQUIRE(d.st[i].seg[j].ncols % 32 == 0, "lstm_bwd_gemm: segment cols %d", d.st[i].seg[j].ncols);
     }
     const int MT = (d.B + 31) / 32;
-    dim3 grid(d.NC / 32, d.KS, d.nstreams), block(NTH);
+    const dim3 grid(d.NC / 32, d.KS, d.nstreams);
     if (d.st[0].wt16lo) {                                // split-bf16 variant: fp32 dg rows, hi / lo transposed shadows
         T2_REQUIRE(MT <= 4 && (d.H4 / d.KS) % 256 == 0, "lstm_bwd_gemm: split-bf16 variant needs B <= 128 and K-split spans of 256");
         for (int i = 0; i < d.nstreams; ++i)
             T2_REQUIRE(d.st[i].wt16 && d.st[i].wt16lo && ((uintptr_t)d.st[i].wt16 & 15) == 0 && ((uintptr_t)d.st[i].wt16lo & 15) == 0,
                        "lstm_bwd_gemm: bad split-bf16 operands");
-        auto go = [&](auto kernel, size_t smem) -> int {
-            T2_TRY_RC(allow_big_lds(kernel, smem));
-            hipLaunchKernelGGL(kernel, grid, block, smem, s, d);
-            return 0;
-        };
-        if (MT <= 1) T2_TRY_RC(go(lstm_bwd_gemm_split_kernel<1>, split_smem<1, SplitBkt<1>::bwd>(false)));
-        else if (MT <= 2) T2_TRY_RC(go(lstm_bwd_gemm_split_kernel<2>, split_smem<2, SplitBkt<2>::bwd>(false)));
-        else T2_TRY_RC(go(lstm_bwd_gemm_split_kernel<4>, split_smem<4, SplitBkt<4>::bwd>(false)));
-        T2_LAUNCH_CHECK();
-        if (family) *family = LSTM_SPLIT;
-        return 0;
+        return launch_step(kBwdInst, LSTM_SPLIT, false, d.H4 / d.KS, grid, d, s, family);
     }
     if (d.st[0].dg16) {
         T2_REQUIRE(MT <= 4 && (d.H4 / d.KS) % 256 == 0, "lstm_bwd_gemm: bf16 variant needs B <= 128 and K-split spans of 256");
-        if (MT <= 1) {
-            const size_t smem = (size_t)Tile16<1, 256>::SMEM_FLOATS * 4;
-            T2_TRY_RC(allow_big_lds(lstm_bwd_gemm_bf16_kernel<1>, smem));
-            hipLaunchKernelGGL(lstm_bwd_gemm_bf16_kernel<1>, grid, block, smem, s, d);
-        } else if (MT <= 2) {
-            const size_t smem = (size_t)Tile16<2, 256>::SMEM_FLOATS * 4;
-            T2_TRY_RC(allow_big_lds(lstm_bwd_gemm_bf16_kernel<2>, smem));
-            hipLaunchKernelGGL(lstm_bwd_gemm_bf16_kernel<2>, grid, block, smem, s, d);
-        } else {
-            const size_t smem = (size_t)Tile16<4, 256>::SMEM_FLOATS * 4;
-            T2_TRY_RC(allow_big_lds(lstm_bwd_gemm_bf16_kernel<4>, smem));
-            hipLaunchKernelGGL(lstm_bwd_gemm_bf16_kernel<4>, grid, block, smem, s, d);
-        }
-        T2_LAUNCH_CHECK();
-        if (family) *family = LSTM_BF16;
-        return 0;
+        return launch_step(kBwdInst, LSTM_BF16, false, d.H4 / d.KS, grid, d, s, family);
     }
-    LAUNCH_MT(lstm_bwd_gemm_kernel, bwd_smem, d.H4 / d.KS, grid, block, s, d);
-    T2_LAUNCH_CHECK();
-    if (family) *family = LSTM_EXACT;
-    return 0;
+    return launch_step(kBwdInst, LSTM_EXACT, false, d.H4 / d.KS, grid, d, s, family);
 }
 
-
-int cast_rows_bf16(const float* src, long ld_src, __bf16* dst, long ld_dst, int R, int C, hipStream_t s) {
+template <bool SPLIT>
+static int cast_rows(const float* src, long ld_src, __bf16* hi, __bf16* lo, long ld_dst, int R, int C, hipStream_t s) {
     const size_t n = (size_t)R * C;
     size_t g = (n + 255) / 256;
     if (g > 4096) g = 4096;
-    hipLaunchKernelGGL(cast_rows_kernel, dim3((unsigned)g), dim3(256), 0, s, src, ld_src, dst, ld_dst, R, C);
+    hipLaunchKernelGGL(cast_rows_kernel<SPLIT>, dim3((unsigned)g), dim3(256), 0, s, src, ld_src, hi, lo, ld_dst, R, C);
     T2_LAUNCH_CHECK();
     return 0;
+}
+template <bool SPLIT>
+static int cast_transpose(const float* src, long ld_src, __bf16* hi, __bf16* lo, long ld_dst, int R, int C, hipStream_t s) {
+    hipLaunchKernelGGL(cast_transpose_kernel<SPLIT>, dim3((C + 31) / 32, (R + 31) / 32), dim3(256), 0, s, src, ld_src, hi, lo, ld_dst, R, C);
+    T2_LAUNCH_CHECK();
+    return 0;
+}
+int cast_rows_bf16(const float* src, long ld_src, __bf16* dst, long ld_dst, int R, int C, hipStream_t s) {
+    return cast_rows<false>(src, ld_src, dst, nullptr, ld_dst, R, C, s);
 }
 int cast_rows_split_bf16(const float* src, long ld_src, __bf16* hi, __bf16* lo, long ld_dst, int R, int C, hipStream_t s) {
-    const size_t n = (size_t)R * C;
-    size_t g = (n + 255) / 256;
-    if (g > 4096) g = 4096;
-    hipLaunchKernelGGL(cast_rows_split_kernel, dim3((unsigned)g), dim3(256), 0, s, src, ld_src, hi, lo, ld_dst, R, C);
-    T2_LAUNCH_CHECK();
-    return 0;
+    return cast_rows<true>(src, ld_src, hi, lo, ld_dst, R, C, s);
 }
 int cast_transpose_split_bf16(const float* src, long ld_src, __bf16* hi, __bf16* lo, long ld_dst, int R, int C, hipStream_t s) {
-    hipLaunchKernelGGL(cast_transpose_split_kernel, dim3((C + 31) / 32, (R + 31) / 32), dim3(256), 0, s, src, ld_src, hi, lo, ld_dst, R, C);
-    T2_LAUNCH_CHECK();
-    return 0;
+    return cast_transpose<true>(src, ld_src, hi, lo, ld_dst, R, C, s);
 }
 int cast_transpose_bf16(const float* src, long ld_src, __bf16* dst, long ld_dst, int R, int C, hipStream_t s) {
-    hipLaunchKernelGGL(cast_transpose_kernel, dim3((C + 31) / 32, (R + 31) / 32), dim3(256), 0, s, src, ld_src, dst, ld_dst, R, C);
-    T2_LAUNCH_CHECK();
-    return 0;
+    return cast_transpose<false>(src, ld_src, dst, nullptr, ld_dst, R, C, s);
 }
 
 }  // namespace t2

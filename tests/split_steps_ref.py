@@ -55,7 +55,15 @@ def error_ratio(got, x, w):
     return float(((got.double() - ref).abs() / product_bound(x, w)).max())
 
 
-def step_gates_fp64(pre, x_prev, w):
+def bf16_product_bound(x, w):
+    """Per output element [M,N], for operands that hold bf16 values (the bf16-operand steps): products of two bf16 numbers
+    are exact in fp32, so only the accumulation rounds — K additions, the sum of the NW wave partials and the addition of
+    the pre-activation, (K + 16) * 2^-23 * sum_k |x||w| (2^-23, not 2^-24: the matrix core's internal additions are not
+    promised to round to nearest)."""
+    return (x.shape[1] + 16) * 2.0 ** -23 * (x.double().abs() @ w.double().abs().T)
+
+
+def step_gates_fp64(pre, x_prev, w, bound_fn=product_bound):
     """Activated gates (i, f, g, o blocks of H columns) of one LSTM step in fp64, and the bound of the recurrent product per
     element: pre [B,4H] = the hoisted input-side pre-activations (biases included), x_prev [B,K] = the recurrent operand
     rows of step t-1 (None at t = 0), w [4H,K].  The activations' derivatives are <= 1, so the pre-activation's bound holds
@@ -64,7 +72,7 @@ def step_gates_fp64(pre, x_prev, w):
     bound = torch.zeros_like(z)
     if x_prev is not None:
         z = z + x_prev.double() @ w.double().T
-        bound = product_bound(x_prev, w)
+        bound = bound_fn(x_prev, w)
     H = z.shape[1] // 4
     g = torch.cat([torch.sigmoid(z[:, :H]), torch.sigmoid(z[:, H:2 * H]), torch.tanh(z[:, 2 * H:3 * H]), torch.sigmoid(z[:, 3 * H:])], 1)
     return g, bound

@@ -3,6 +3,7 @@ attention LSTMs and the decoder LSTM, and the recurrent-input gradients of their
 accumulation.  Yardsticks: fp64 on the CPU from the operands each run saved (the bound of tests/split_steps_ref.py, checked
 without a GPU in tests/test_split_steps_cpu.py), the CPU oracle at the project's 1e-4, fp64 oracle autograd, and the exact
 modes on the same inputs.  Every test restores the mode and the switch."""
+import contextlib
 import functools
 
 import pytest
@@ -12,7 +13,7 @@ from oracle import recipe
 from oracle import tacotron2_oracle as O
 
 from helpers import LSA, SMA, hp_for, load_golden, maxabs, to_dev
-from split_steps_ref import step_gates_fp64
+from split_steps_ref import bf16_product_bound, product_bound, step_gates_fp64
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-4
@@ -36,6 +37,17 @@ class mode:
         from tacotron2_subword_amd import _lib as L
         L.set_split_steps(False)
         L.set_precision("f32")
+
+
+@contextlib.contextmanager
+def chain_off():
+    """per-step launches instead of the persistent chains; the switch is back on afterwards, also on failure"""
+    from tacotron2_subword_amd import _lib as L
+    L.set_chain(False)
+    try:
+        yield
+    finally:
+        L.set_chain(True)
 
 
 @functools.lru_cache(maxsize=None)
@@ -86,20 +98,25 @@ def decoder_run(att, B, T, Tin, Tsub, training, seed):
     return saved, L.step_counts(), L.gemm_counts()
 
 
-def gate_errors(att, S, T):
+def gate_errors(att, S, T, family="split"):
     """Per cell (attention LSTM, its sub-word twin, decoder LSTM) and step: |saved activated gates - fp64 gates| and the bound
     of the recurrent product, both [B,4H]; the fp64 gates come from the run's OWN saved rows of step t-1 and hoisted
-    pre-activations.  Also |saved cell - fp64 cell| from the fp64 gates and the saved previous cell, with its bound."""
+    pre-activations.  Also |saved cell - fp64 cell| from the fp64 gates and the saved previous cell, with its bound.
+    family "bf16": the fp64 product is taken over the operands that kernel reads, the bf16 roundings (nearest even) of the
+    saved rows and of the weights, under bf16_product_bound."""
     Wt = weights(att)
     cells = [("att", "prea", "ga", "cna", "ca", lambda t: S["din"][t][:, :HA + E],
               torch.cat([Wt["decoder.attention_rnn.weight_hh"], Wt["decoder.attention_rnn.weight_ih"][:, P:]], 1)),
              ("att_sub", "preas", "gas", "cnas", "cas", lambda t: S["din"][t][:, HA + E:],
               torch.cat([Wt["decoder.attention_rnn_bert.weight_hh"], Wt["decoder.attention_rnn_bert.weight_ih"][:, P:]], 1)),
              ("dec", "pred", "gd", "cnd", "cd", lambda t: S["dout"][t][:, :HD], Wt["decoder.decoder_rnn.weight_hh"])]
+    operand = (lambda v: v.to(torch.bfloat16).float()) if family == "bf16" else (lambda v: v)
+    bound_fn = bf16_product_bound if family == "bf16" else product_bound
     out = []
     for name, pre, gates, cnew, cout, rows, w in cells:
+        w = operand(w)
         for t in range(T):
-            g64, bound = step_gates_fp64(S[pre][t], rows(t - 1) if t > 0 else None, w)
+            g64, bound = step_gates_fp64(S[pre][t], operand(rows(t - 1)) if t > 0 else None, w, bound_fn)
             H = g64.shape[1] // 4
             cp = S[cout][t - 1].double() if t > 0 else torch.zeros_like(g64[:, :H])
             c64 = g64[:, H:2 * H] * cp + g64[:, :H] * g64[:, 2 * H:3 * H]
@@ -109,36 +126,51 @@ def gate_errors(att, S, T):
     return out
 
 
-@pytest.mark.parametrize("training", [False, True])
-@pytest.mark.parametrize("att", [SMA, LSA])
-@pytest.mark.parametrize("B", [1, 33, 65])
-def test_forward_split_steps_against_fp64_step_by_step(B, att, training):
+# the split cases keep the ids they had before the test took a family
+@pytest.mark.parametrize("family,B,att,training", [
+    pytest.param(family, B, att, training, id=("" if family == "split" else family + "-") + f"{B}-{att}-{training}")
+    for family in ("split", "bf16") for B in (1, 33, 65) for att in (SMA, LSA) for training in (False, True)])
+def test_forward_split_steps_against_fp64_step_by_step(family, B, att, training):
     """B = 1 / 33 / 65 (one row tile; a partly filled second; four with a partly filled third), T = 3, Tin / Tsub = 7 / 5,
     ragged lengths.  Every step's activated gates (t = 0 included: no recurrent operand, same kernel) within
     8 * 2^-17 * sqrt(sum x^2 w^2) of the recurrent product + a floor of twice the largest error the MODE-0 run shows against
     the same fp64 formula in this test; the counters prove which kernels ran; with dropout on, the zeros of h and c are the
-    keep-bits of mode 0's RNG indices."""
+    keep-bits of mode 0's RNG indices.
+    family "bf16": the per-step launches of precision mode "bf16" with the persistent chains off (the bf16-operand step
+    kernel, otherwise only ever compared with the chain).  Its operands are exactly the bf16 roundings of the saved fp32
+    rows and of the weights (the shadows are cast_rows_bf16 of [W_hh | W_ih[:, P:]] / W_hh; the producing kernels store
+    (__bf16)h and (__bf16)ctx next to the fp32 values), so the fp64 product is taken over those and the bound is the
+    accumulation's alone: (K + 16) * 2^-23 * sum |x||w| + the same floor.  At the default dims the attention LSTMs run an
+    odd number of 512-wide stages (K = 1536) and the decoder LSTM an even one (1024): both exits of the two-deep stage
+    pipeline, and t = 0 runs none."""
     from tacotron2_subword_amd import _lib as L
     from tacotron2_subword_amd import ops
     T, Tin, Tsub, seed = 3, 7, 5, 20240607
     with mode("f32", False):
         S0, sc0, _ = decoder_run(att, B, T, Tin, Tsub, training, seed)
-    with mode("bf16x3", True):
-        S2, sc2, gc2 = decoder_run(att, B, T, Tin, Tsub, training, seed)
+    if family == "split":
+        with mode("bf16x3", True):
+            S2, sc2, gc2 = decoder_run(att, B, T, Tin, Tsub, training, seed)
+    else:
+        with mode("bf16", False), chain_off():
+            S2, sc2, gc2 = decoder_run(att, B, T, Tin, Tsub, training, seed)
     assert sc0 == (2 * T, 0, 0, 0, 0, 0), sc0
-    assert sc2 == (0, 0, 2 * T, 0, 0, 0), sc2                            # attention LSTMs (both streams in one launch) + decoder LSTM
-    assert gc2[1] == gc2[2] == 0, gc2
+    if family == "split":
+        assert sc2 == (0, 0, 2 * T, 0, 0, 0), sc2                        # attention LSTMs (both streams in one launch) + decoder LSTM
+        assert gc2[1] == gc2[2] == 0, gc2
+    else:
+        assert sc2 == (0, 2 * T, 0, 0, 0, 0), sc2
     e0 = gate_errors(att, S0, T)
     floor_g = 2 * max(float(eg.max()) for _, _, eg, _, _, _ in e0)
     floor_c = 2 * max(float(ec.max()) for _, _, _, _, ec, _ in e0)
     worst_g = worst_c = 0.0
-    for name, t, eg, bound, ec, cb in gate_errors(att, S2, T):
+    for name, t, eg, bound, ec, cb in gate_errors(att, S2, T, family):
         rg, rc = float((eg / (bound + floor_g)).max()), float((ec / (cb + floor_c)).max())
-        print(f"B={B} {att} training={training} {name} t={t}: gate error / bound {rg:.3f} (max error {float(eg.max()):.2e}, "
+        print(f"{family} B={B} {att} training={training} {name} t={t}: gate error / bound {rg:.3f} (max error {float(eg.max()):.2e}, "
               f"floor {floor_g:.2e})  cell error / bound {rc:.3f}")
         worst_g, worst_c = max(worst_g, rg), max(worst_c, rc)
         assert rg < 1 and rc < 1, (name, t, rg, rc)
-    print(f"B={B} {att} training={training}: worst gate error / bound {worst_g:.3f}, worst cell error / bound {worst_c:.3f}")
+    print(f"{family} B={B} {att} training={training}: worst gate error / bound {worst_g:.3f}, worst cell error / bound {worst_c:.3f}")
     if training:
         for site, p, key, cols in (("ATT_H", 0.1, "din", slice(0, HA)), ("ATT_H_SUB", 0.1, "din", slice(HA + E, 2 * HA + E)),
                                    ("DEC_H", 0.1, "dout", slice(0, HD)), ("ATT_C", 0.1, "ca", slice(0, HA)),
