@@ -141,6 +141,17 @@ int t2_set_gemm_staging(int on);
  * weight-gradient product (or its split-K reduce) writes [Cout][Cin][K] directly.  0: the separate K = 1 product over dDOUT
  * and the re-layout kernel.  Every result has the same bits either way; the switch lets one process compare the two. */
 int t2_set_gemm_fold(int on);
+/* 1 (default; env T2_BN_FUSE=0 turns it off): t2_conv_bn_forward (training) and t2_conv_bn_backward finish their column
+ * reductions in the prologue of the kernel that consumes them instead of in launches of their own: the pass over the
+ * centred squares finishes the mean, one stage-2 launch finishes var / invstd and updates the running statistics, the
+ * dz kernel finishes d(beta) / d(gamma) and leaves the slab partials of d(bias), so dz is not read again (where the
+ * re-laid-out weights have no room for them, Cin*K < 64, the separate column sum runs).  0: a stage-2 launch per
+ * reduction and one for the running statistics.  Every result has the same bits either way: the order of additions of a column sum does not change.
+ * t2_bn_fuse_counts: layer calls since the last reset that took [0] the fused forward, [1] the fused backward with the
+ * d(bias) partials, [2] the fused backward with the separate column sum (host counters). */
+int t2_set_bn_fuse(int on);
+int t2_get_bn_fuse(void);
+int t2_bn_fuse_counts(uint64_t* out_host /* [3] */, int reset);
 /* Makes `stream` wait for everything the library has queued on its internal side stream of the current device
  * (t2_decoder_bwd_args.defer_weight_grads). */
 int t2_side_join(void* stream);

@@ -241,7 +241,7 @@ STFT_POLAR, STFT_DENOISE = 0, 1
 # every symbol include/t2amd.h declares (tests/test_abi.py checks the library exports them all)
 ABI_VERSION = 4      # include/t2amd.h T2_ABI_VERSION: struct sizes below match that header and nothing else
 
-EXPORTS = ["t2_last_error", "t2_version", "t2_chain_status", "t2_chain_status_clear", "t2_debug_report_abort", "t2_debug_occupy", "t2_chain_claimed", "t2_set_precision", "t2_get_precision", "t2_gemm_counts", "t2_set_gemm_split_min_mflop", "t2_set_split_steps", "t2_get_split_steps", "t2_step_counts", "t2_set_overlap", "t2_set_chain", "t2_get_chain", "t2_set_chain_bwd", "t2_set_gemm_staging", "t2_set_gemm_fold", "t2_side_join", "t2_decoder_layout_query", "t2_decoder_forward", "t2_decoder_infer",
+EXPORTS = ["t2_last_error", "t2_version", "t2_chain_status", "t2_chain_status_clear", "t2_debug_report_abort", "t2_debug_occupy", "t2_chain_claimed", "t2_set_precision", "t2_get_precision", "t2_gemm_counts", "t2_set_gemm_split_min_mflop", "t2_set_split_steps", "t2_get_split_steps", "t2_step_counts", "t2_set_overlap", "t2_set_chain", "t2_get_chain", "t2_set_chain_bwd", "t2_set_gemm_staging", "t2_set_gemm_fold", "t2_set_bn_fuse", "t2_get_bn_fuse", "t2_bn_fuse_counts", "t2_side_join", "t2_decoder_layout_query", "t2_decoder_forward", "t2_decoder_infer",
            "t2_decoder_bwd_layout_query", "t2_decoder_backward", "t2_prof_enable", "t2_prof_collect", "t2_adam_chunks", "t2_adam_step", "t2_adam_norm",
            "t2_conv_bn_forward", "t2_conv_bn_backward", "t2_embedding_forward", "t2_embedding_backward",
            "t2_lstm_seq_forward", "t2_lstm_seq_backward", "t2_lstm_seq_chain_ws_floats", "t2_gemm_ex", "t2_prof_gemm", "t2_gemm_plan", "t2_conv_handoff_plan", "t2_colsum", "t2_mask_btc",
@@ -295,6 +295,7 @@ def lib() -> C.CDLL:
         L.t2_gemm_counts.argtypes = [C.POINTER(C.c_uint64), C.c_int]
         L.t2_set_split_steps.argtypes = [C.c_int]
         L.t2_step_counts.argtypes = [C.POINTER(C.c_uint64), C.c_int]
+        L.t2_bn_fuse_counts.argtypes = [C.POINTER(C.c_uint64), C.c_int]
         L.t2_set_gemm_split_min_mflop.argtypes = [C.c_int]
         L.t2_prof_collect.argtypes = [C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_int)]
         L.t2_finalize_bct.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_float, C.c_void_p]
@@ -577,6 +578,24 @@ def set_gemm_fold(on: bool) -> None:
     """Gate term of dDOUT and the conv weight-gradient layout folded into the products' stores (default) or as passes of
     their own; the same bits either way (include/t2amd.h t2_set_gemm_fold)."""
     check(lib().t2_set_gemm_fold(1 if on else 0))
+
+
+def set_bn_fuse(on: bool) -> None:
+    """Conv + BatchNorm layers finish their column reductions in the consuming kernel's prologue (default) or in stage-2
+    launches of their own; the same bits either way (include/t2amd.h t2_set_bn_fuse)."""
+    check(lib().t2_set_bn_fuse(1 if on else 0))
+
+
+def get_bn_fuse() -> bool:
+    return bool(lib().t2_get_bn_fuse())
+
+
+def bn_fuse_counts(reset: bool = False):
+    """Conv + BatchNorm layer calls since the last reset: (fused forward, fused backward with d(bias) partials from the dz
+    kernel, fused backward with the separate column sum)."""
+    out = (C.c_uint64 * 3)()
+    check(lib().t2_bn_fuse_counts(out, int(bool(reset))))
+    return tuple(int(v) for v in out)
 
 
 def set_gemm_split_min_mflop(mflop: int = -1) -> None:

@@ -239,6 +239,13 @@ int t2_get_chain(void) { return g_chain; }
 int t2_set_chain_bwd(int on) { g_chain_bwd = on != 0; return 0; }
 int t2_set_gemm_staging(int on) { set_gemm_staging(on); return 0; }
 int t2_set_gemm_fold(int on) { set_gemm_fold(on); return 0; }
+int t2_set_bn_fuse(int on) { set_bn_fuse(on); return 0; }
+int t2_get_bn_fuse(void) { return get_bn_fuse(); }
+int t2_bn_fuse_counts(uint64_t* out_host, int reset) {
+    T2_REQUIRE(out_host, "null argument");
+    bn_fuse_counts(out_host, reset);
+    return 0;
+}
 int t2_side_join(void* stream) {
     Side* side = nullptr;
     T2_TRY(side_get(&side));

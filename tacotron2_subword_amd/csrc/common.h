@@ -8,6 +8,7 @@
 namespace t2 {
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
+typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 constexpr int kWave = 64;
@@ -70,22 +71,28 @@ __device__ __forceinline__ float wave_max(float v) {
 // does not, so a lane owns V adjacent columns (one 16-byte load per row for V = 4), requests R rows
 // before it consumes the first, and has the next R on their way while it consumes.
 // A workgroup is 4 phases x kColLanes lanes and covers kColLanes*V columns of one slab.
+// The order leaves C/V * 4 * slabs lanes to work with: 512 waves for 512 columns at V = 4, half the
+// SIMDs of the device, so a caller picks a smaller V (and a larger R) where that fills it.
 // ---------------------------------------------------------------------------------------------
 constexpr int kColLanes = 32;
 constexpr int kColThreads = 4 * kColLanes;
 
 template <int V> struct ColVec { float v[V]; };
 template <int V> __device__ __forceinline__ ColVec<V> load_cols(const float* p) {
-    static_assert(V == 1 || V == 4, "one column or one 16-byte group per lane");
+    static_assert(V == 1 || V == 2 || V == 4, "one column, or one 8- or 16-byte group per lane");
     ColVec<V> r;
     if constexpr (V == 4) {
         const f32x4 t = *reinterpret_cast<const f32x4*>(p);
         r.v[0] = t.x; r.v[1] = t.y; r.v[2] = t.z; r.v[3] = t.w;
+    } else if constexpr (V == 2) {
+        const f32x2 t = *reinterpret_cast<const f32x2*>(p);
+        r.v[0] = t.x; r.v[1] = t.y;
     } else r.v[0] = *p;
     return r;
 }
 template <int V> __device__ __forceinline__ void store_cols(float* p, const ColVec<V>& r) {
     if constexpr (V == 4) { f32x4 t; t.x = r.v[0]; t.y = r.v[1]; t.z = r.v[2]; t.w = r.v[3]; *reinterpret_cast<f32x4*>(p) = t; }
+    else if constexpr (V == 2) { f32x2 t; t.x = r.v[0]; t.y = r.v[1]; *reinterpret_cast<f32x2*>(p) = t; }
     else *p = r.v[0];
 }
 // use(m, load(m)) for m = m, m+4, ... < m1, in that order.  The tail requests a full group too (rows past the end
@@ -121,6 +128,38 @@ __device__ __forceinline__ void rows_in_flight(int m, const int m1, Load load, U
 }
 // the partition both stages agree on
 __host__ __device__ inline int col_slabs(int M) { return M >= 64 * 64 ? 64 : (M >= 64 ? M / 64 : 1); }
+// Stage 2: sum_{s < count} p[s * stride], terms requested 16 at a time and added in index order (a dependent load per term
+// costs ~0.3 us each: 20 us for 64 slabs)
+__device__ __forceinline__ float ordered_sum16(const float* __restrict__ p, int count, long stride) {
+    float acc = 0.f;
+    int s = 0;
+    for (; s + 16 <= count; s += 16) {
+        float v[16];
+#pragma unroll
+        for (int j = 0; j < 16; ++j) v[j] = p[(long)(s + j) * stride];
+#pragma unroll
+        for (int j = 0; j < 16; ++j) acc += v[j];
+    }
+    for (; s < count; ++s) acc += p[(long)s * stride];
+    return acc;
+}
+// The same additions with all 64 terms of a full partition requested at once: in a consuming kernel's prologue the whole
+// workgroup waits for this sum, so it pays one load latency instead of four.
+__device__ __forceinline__ float ordered_sum64(const float* __restrict__ p, int count, long stride) {
+    if (count != 64) return ordered_sum16(p, count, stride);
+    float v[64];
+#pragma unroll
+    for (int j = 0; j < 64; ++j) v[j] = p[(long)j * stride];
+    float acc = 0.f;
+#pragma unroll
+    for (int j = 0; j < 64; ++j) acc += v[j];
+    return acc;
+}
+// Stage 2 in the prologue of the kernel that consumes the sums: thread j of the workgroup sums column c0 + j of the slab
+// partials part[slab][C] into out[j] (LDS, ncols entries; columns past C give 0).  The caller synchronises.
+__device__ __forceinline__ void block_ordered_sums(const float* __restrict__ part, int C, int slabs, int c0, int ncols, float* out) {
+    for (int j = threadIdx.x; j < ncols; j += blockDim.x) out[j] = c0 + j < C ? ordered_sum64(part + c0 + j, slabs, C) : 0.f;
+}
 inline bool cols_vectorisable(const void* p, long ld, int N) {
     return N % 4 == 0 && ld % 4 == 0 && (reinterpret_cast<uintptr_t>(p) & 15) == 0;
 }

@@ -16,11 +16,14 @@
 // BatchNorm statistics use two passes (mean, then centred sum of squares) over two-stage
 // fixed-order column reductions (common.h), so results are reproducible run to run.
 #include "kernels.h"
+#include <atomic>
+#include <cstdlib>
 
 namespace t2 {
 
 namespace {
 
+inline int env_int(const char* name, int dflt) { const char* v = getenv(name); return v && *v ? atoi(v) : dflt; }
 inline int grid_for(size_t n, int block = 256, int cap = 8192) {
     size_t g = (n + block - 1) / block;
     return (int)(g < 1 ? 1 : (g > (size_t)cap ? cap : g));
@@ -28,22 +31,36 @@ inline int grid_for(size_t n, int block = 256, int cap = 8192) {
 
 // The re-laid-out weights are written as fp32, or straight as the bf16 copy when the product takes one (OUT = __bf16: the
 // round-to-nearest cast the staging kernels apply to the fp32 array).
+// The element index and its three divisions are 32-bit (IDX = uint32_t) where Co*Ci*K < 2^31 (a 64-bit division by a
+// run-time value is some 100 instructions, three of them per element for 1.3 M elements a layer), size_t otherwise.
 // wp[co][dk*Ci + ci] = w[co][ci][dk]
-template <class OUT>
+template <class OUT, class IDX>
 __global__ void permute_w_fwd_kernel(const float* __restrict__ w, OUT* __restrict__ wp, int Co, int Ci, int K) {
-    const size_t n = (size_t)Co * Ci * K;
-    for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
-        const int ci = (int)(i % Ci); const size_t r = i / Ci; const int dk = (int)(r % K), co = (int)(r / K);
-        wp[i] = (OUT)w[((size_t)co * Ci + ci) * K + dk];
+    const IDX n = (IDX)Co * Ci * K;
+    for (IDX i = blockIdx.x * (IDX)blockDim.x + threadIdx.x; i < n; i += (IDX)gridDim.x * blockDim.x) {
+        const IDX ci = i % (IDX)Ci, r = i / (IDX)Ci, dk = r % (IDX)K, co = r / (IDX)K;
+        wp[i] = (OUT)w[(co * Ci + ci) * K + dk];
     }
 }
 // wt[ci][dk*Co + co] = w[co][ci][K-1-dk]     (data gradient = correlation with the flipped kernel)
-template <class OUT>
+template <class OUT, class IDX>
 __global__ void permute_w_bwd_kernel(const float* __restrict__ w, OUT* __restrict__ wt, int Co, int Ci, int K) {
+    const IDX n = (IDX)Co * Ci * K;
+    for (IDX i = blockIdx.x * (IDX)blockDim.x + threadIdx.x; i < n; i += (IDX)gridDim.x * blockDim.x) {
+        const IDX co = i % (IDX)Co, r = i / (IDX)Co, dk = r % (IDX)K, ci = r / (IDX)K;
+        wt[i] = (OUT)w[(co * Ci + ci) * K + ((IDX)K - 1 - dk)];
+    }
+}
+template <class OUT>
+void permute_w(bool bwd, const float* w, OUT* out, int Co, int Ci, int K, hipStream_t s) {
     const size_t n = (size_t)Co * Ci * K;
-    for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
-        const int co = (int)(i % Co); const size_t r = i / Co; const int dk = (int)(r % K), ci = (int)(r / K);
-        wt[i] = (OUT)w[((size_t)co * Ci + ci) * K + (K - 1 - dk)];
+    const dim3 grid(grid_for(n)), block(256);
+    if (n < (1ull << 31)) {
+        if (bwd) hipLaunchKernelGGL((permute_w_bwd_kernel<OUT, uint32_t>), grid, block, 0, s, w, out, Co, Ci, K);
+        else hipLaunchKernelGGL((permute_w_fwd_kernel<OUT, uint32_t>), grid, block, 0, s, w, out, Co, Ci, K);
+    } else {
+        if (bwd) hipLaunchKernelGGL((permute_w_bwd_kernel<OUT, size_t>), grid, block, 0, s, w, out, Co, Ci, K);
+        else hipLaunchKernelGGL((permute_w_fwd_kernel<OUT, size_t>), grid, block, 0, s, w, out, Co, Ci, K);
     }
 }
 // dw[co][ci][dk] = dwp[co][dk*Ci + ci]
@@ -85,22 +102,38 @@ __device__ __forceinline__ float colreduce_term(const BnElem& e, const BnCol& k,
     }
     return g;
 }
-template <int MODE, int V>
+// FIN (MODE 1): the mean is not read from e.mean but finished here, from the MODE 0 slab partials in `scratch`: the ordered
+// sum over the slabs, divided by M, as colreduce_stage2_kernel does it.  The workgroups of slab 0 store it to mean_out, and
+// the partials of this pass go behind the ones being read (other workgroups may still read those).
+template <int MODE, int V, bool FIN>
 __global__ void __launch_bounds__(kColThreads) colreduce_stage1_kernel(BnElem e, const float* __restrict__ dy, float* __restrict__ du,
-                                                                       int M, int slabs, float* __restrict__ scratch) {
-    constexpr int R = MODE == 2 ? 8 : 16;      // rows requested ahead: 16 x 16 bytes per lane, twice (MODE 2 reads z and dy)
+                                                                       int M, int slabs, float* scratch, float* __restrict__ mean_out) {
+    static_assert(!FIN || MODE == 1, "only the centred squares have a sum to finish");
+    // rows requested ahead: 16 x 16 bytes per lane, twice (MODE 2 reads z and dy; its narrower lanes ask for 16 rows each)
+    constexpr int R = MODE == 2 ? (V == 4 ? 8 : 16) : 16;
+    static_assert(MODE == 2 || V != 2, "the forward passes run with 16-byte groups or one column per lane");
     const int C = e.C;
     const int lane = threadIdx.x % kColLanes, sub = threadIdx.x / kColLanes;
     const int c = (blockIdx.x * kColLanes + lane) * V;
     const int rows = (M + slabs - 1) / slabs;
     const int m0 = blockIdx.y * rows, m1 = min(M, m0 + rows);
     __shared__ float p0[4][kColLanes * V], p1[4][kColLanes * V];
+    __shared__ float fin[FIN ? kColLanes * V : 1];
+    if (FIN) {
+        block_ordered_sums(scratch, C, slabs, blockIdx.x * kColLanes * V, kColLanes * V, fin);
+        __syncthreads();
+        scratch += (size_t)slabs * C;
+    }
     float a0[V] = {}, a1[V] = {};
     if (c < C) {
         BnCol col[V];
 #pragma unroll
         for (int k = 0; k < V; ++k) {
-            col[k].mean = MODE >= 1 ? e.mean[c + k] : 0.f;
+            if (FIN) {
+                col[k].mean = fin[lane * V + k] / (float)M;
+                if (blockIdx.y == 0 && sub == 0) mean_out[c + k] = col[k].mean;
+            } else
+                col[k].mean = MODE >= 1 ? e.mean[c + k] : 0.f;
             col[k].inv = MODE == 2 ? e.invstd[c + k] : 0.f; col[k].ga = MODE == 2 ? e.gamma[c + k] : 0.f; col[k].be = MODE == 2 ? e.beta[c + k] : 0.f;
         }
         const float scale = e.drop_p > 0.f ? 1.0f / (1.0f - e.drop_p) : 1.0f;
@@ -134,29 +167,30 @@ __global__ void __launch_bounds__(kColThreads) colreduce_stage1_kernel(BnElem e,
         }
     }
 }
+// running statistics (momentum 0.1, unbiased variance), model.py:42 nn.BatchNorm1d defaults.  Every product is rounded on its
+// own (what the compiler made of this line in bn_running_kernel, which multiplies in pairs): no fma, wherever it is inlined.
+__device__ __forceinline__ void bn_running_update(float mean, float var, int M, float momentum, float* rm, float* rv) {
+#pragma clang fp contract(off)
+    const float unb = var * ((float)M / (float)(M > 1 ? M - 1 : 1));
+    *rm = (1.0f - momentum) * *rm + momentum * mean;
+    *rv = (1.0f - momentum) * *rv + momentum * unb;
+}
 // out0[c] = f(sum over slabs); MODE 0: mean = s/M ; MODE 1: invstd = rsqrt(s/M + eps), var_out = s/M ; MODE 2: raw sums
+// MODE 1 with rm (the fused forward): also the running statistics, from mean[] and the variance just finished
 __global__ void colreduce_stage2_kernel(const float* __restrict__ scratch, int C, int slabs, int M, int mode, float eps,
-                                        float* out0, float* out1) {
+                                        float* out0, float* out1, const float* mean, float momentum, float* rm, float* rv) {
     const int c = blockIdx.x * blockDim.x + threadIdx.x;
     if (c >= C) return;
-    // the slab partials are requested 16 at a time and added in slab order (one dependent load per slab cost 0.3 us each)
-    auto ordered_sum = [&](const float* __restrict__ p) {
-        float acc = 0.f;
-        int s = 0;
-        for (; s + 16 <= slabs; s += 16) {
-            float v[16];
-#pragma unroll
-            for (int j = 0; j < 16; ++j) v[j] = p[(size_t)(s + j) * C];
-#pragma unroll
-            for (int j = 0; j < 16; ++j) acc += v[j];
-        }
-        for (; s < slabs; ++s) acc += p[(size_t)s * C];
-        return acc;
-    };
-    const float s0 = ordered_sum(scratch + c);
-    const float s1 = mode == 2 ? ordered_sum(scratch + (size_t)slabs * C + c) : 0.f;
+    // the slab partials are requested 16 at a time and added in slab order (common.h)
+    const float s0 = ordered_sum16(scratch + c, slabs, C);
+    const float s1 = mode == 2 ? ordered_sum16(scratch + (size_t)slabs * C + c, slabs, C) : 0.f;
     if (mode == 0) out0[c] = s0 / (float)M;
-    else if (mode == 1) { const float var = s0 / (float)M; out0[c] = 1.0f / sqrtf(var + eps); if (out1) out1[c] = var; }
+    else if (mode == 1) {
+        const float var = s0 / (float)M;
+        out0[c] = 1.0f / sqrtf(var + eps);
+        if (out1) out1[c] = var;
+        if (rm) bn_running_update(mean[c], var, M, momentum, rm + c, rv + c);
+    }
     else { out0[c] = s0; out1[c] = s1; }
 }
 
@@ -165,9 +199,11 @@ __global__ void colreduce_stage2_kernel(const float* __restrict__ scratch, int C
 // divided out once and then stepped, so the loop holds no division.  As in the reductions, the fused products are
 // written out: u = fma(xhat, gamma, beta); the two mean corrections of dz are one fma each.
 typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
+typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
 // the bf16 copy of V adjacent values for the next GEMM (round to nearest even, as the staging cast of the fp32 array)
 template <int V> __device__ __forceinline__ void store_cols16(__bf16* p, const ColVec<V>& r) {
     if constexpr (V == 4) { bf16x4 t; t[0] = (__bf16)r.v[0]; t[1] = (__bf16)r.v[1]; t[2] = (__bf16)r.v[2]; t[3] = (__bf16)r.v[3]; *reinterpret_cast<bf16x4*>(p) = t; }
+    else if constexpr (V == 2) { bf16x2 t; t[0] = (__bf16)r.v[0]; t[1] = (__bf16)r.v[1]; *reinterpret_cast<bf16x2*>(p) = t; }
     else *p = (__bf16)r.v[0];
 }
 __device__ __forceinline__ float bn_apply_term(const BnElem& e, float scale, float z, float mean, float inv, float ga, float be, uint32_t i) {
@@ -231,13 +267,80 @@ __global__ void bn_bwd_dz_kernel(BnElem e, const float* du, const float* __restr
         if (c >= e.C) c -= e.C;
     }
 }
-// running statistics (momentum 0.1, unbiased variance), model.py:42 nn.BatchNorm1d defaults
+// running statistics (bn_running_update above)
 __global__ void bn_running_kernel(const float* mean, const float* var, int C, int M, float momentum, float* rm, float* rv) {
     const int c = blockIdx.x * blockDim.x + threadIdx.x;
     if (c >= C) return;
-    const float unb = var[c] * ((float)M / (float)(M > 1 ? M - 1 : 1));
-    rm[c] = (1.0f - momentum) * rm[c] + momentum * mean[c];
-    rv[c] = (1.0f - momentum) * rv[c] + momentum * unb;
+    bn_running_update(mean[c], var[c], M, momentum, rm + c, rv + c);
+}
+
+// The dz kernel in the shape of the reductions (a workgroup is 4 row phases x kColLanes lanes, a lane owns V fixed columns),
+// so a column's statistics are registers, and what the kernel before left as slab partials is finished in the prologue:
+// thread j sums column j of the block in slab order into LDS, no launch of its own.
+// It runs on the partition of the reduction that wrote `sums` (MODE 2: slabs x C partials of sum du, then of sum du*xhat).
+// The prologue finishes both; the workgroups of slab 0 store d(beta) and d(gamma).  The rows of a slab are walked as
+// colsum_stage1_kernel walks them (4 phases, rows ascending, the slab's sum p0 + p1 + p2 + p3), so the slab partials of
+// d(bias) = sum dz fall out into dbias_part (nullable) and dz is not read again: colsum's stage 2 finishes them.
+template <int V>
+__global__ void __launch_bounds__(kColThreads) bn_bwd_dz_cols_kernel(BnElem e, const float* du, const float* __restrict__ sums, int M, int slabs,
+                                                                     int training, float* dz, __bf16* __restrict__ dz16,
+                                                                     float* __restrict__ dbeta, float* __restrict__ dgamma,
+                                                                     float* __restrict__ dbias_part) {
+    constexpr int R = V == 4 ? 8 : 16, NC = kColLanes * V;
+    const int C = e.C;
+    const int lane = threadIdx.x % kColLanes, sub = threadIdx.x / kColLanes;
+    const int c = (blockIdx.x * kColLanes + lane) * V;
+    const int rows = (M + slabs - 1) / slabs;
+    const int m0 = blockIdx.y * rows, m1 = min(M, m0 + rows);
+    __shared__ float fin[2][NC], part[4][NC];
+    for (int j = threadIdx.x; j < 2 * NC; j += kColThreads) {
+        const int w = j / NC, cc = blockIdx.x * NC + j % NC;
+        fin[w][j % NC] = cc < C ? ordered_sum64(sums + (size_t)w * slabs * C + cc, slabs, C) : 0.f;
+    }
+    __syncthreads();
+    float acc[V] = {};
+    if (c < C) {
+        BnCol col[V];
+        float s0[V], s1[V];
+#pragma unroll
+        for (int k = 0; k < V; ++k) {
+            col[k].mean = e.mean[c + k]; col[k].inv = e.invstd[c + k]; col[k].ga = e.gamma[c + k]; col[k].be = 0.f;
+            s0[k] = fin[0][lane * V + k]; s1[k] = fin[1][lane * V + k];
+            if (blockIdx.y == 0 && sub == 0) { dbeta[c + k] = s0[k]; dgamma[c + k] = s1[k]; }
+        }
+        const float invM = 1.0f / (float)M;
+        struct Row { ColVec<V> g, z; };
+        rows_in_flight<R, Row>(m0 + sub, m1,
+            [&](int m) {
+                const size_t i = (size_t)m * C + c;
+                Row r;
+                r.g = load_cols<V>(du + i);
+                if (training) r.z = load_cols<V>(e.z + i);
+                return r;
+            },
+            [&](int m, const Row& r) {
+                const size_t i = (size_t)m * C + c;
+                ColVec<V> o;
+#pragma unroll
+                for (int k = 0; k < V; ++k) {
+                    o.v[k] = bn_bwd_dz_term(r.g.v[k], training ? r.z.v[k] : 0.f, col[k].mean, col[k].inv, col[k].ga, s0[k], s1[k], invM, training);
+                    acc[k] += o.v[k];
+                }
+                store_cols<V>(dz + i, o);
+                if (dz16) store_cols16<V>(dz16 + i, o);
+            });
+    }
+    if (!dbias_part) return;
+#pragma unroll
+    for (int k = 0; k < V; ++k) part[sub][lane * V + k] = acc[k];
+    __syncthreads();
+    if (sub == 0 && c < C) {
+#pragma unroll
+        for (int k = 0; k < V; ++k) {
+            const int l = lane * V + k;
+            dbias_part[(size_t)blockIdx.y * C + c + k] = part[0][l] + part[1][l] + part[2][l] + part[3][l];
+        }
+    }
 }
 __global__ void invstd_from_var_kernel(const float* var, int C, float eps, float* invstd) {
     const int c = blockIdx.x * blockDim.x + threadIdx.x;
@@ -326,20 +429,55 @@ inline bool aligned8(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 7
 inline size_t round256(size_t n) { return (n + 255) & ~(size_t)255; }
 inline bool same_route(const GemmPlan& p, const GemmPlan& q) { return p.kernel == q.kernel && p.split == q.split && p.splitk == q.splitk && p.kchunks == q.kchunks; }
 
+std::atomic<int> g_bn_fuse{env_int("T2_BN_FUSE", 1)};
+std::atomic<uint64_t> g_bn_counts[3];
+
+inline int col_blocks(int C, int V) { return (C + V * kColLanes - 1) / (V * kColLanes); }
+// Columns per lane on the reduction partition.  16-byte groups where the arrays allow them, as ever.  narrow = the fused
+// backward: the order of additions leaves C/V * 4 * slabs lanes, 512 waves for 512 columns at V = 4, and the MODE 2 pass
+// (tanh, the dropout hash, two arrays in, one out) gains from every halving (profiles/r16_conv_widths.txt: 89 / 61 / 43 us
+// at 25600 x 512), so with (nearly) all 64 slabs it takes the widest lane that gives each of the 1024 SIMDs two waves, else
+// one column per lane.  The forward passes (one array in, an add or an fma per element) do not move with V and keep 4.
+int col_width(int C, int slabs, bool vec, bool narrow) {
+    if (!vec) return 1;
+    if (narrow && slabs >= 48) {
+        for (int v = 4; v > 1; v >>= 1)
+            if (col_blocks(C, v) * slabs * (kColThreads / kWave) >= 2048) return v;
+        return 1;
+    }
+    return 4;
+}
+
+template <int MODE, bool FIN>
+int colreduce_stage1(const BnElem& e, const float* dy, float* du, int M, float* scratch, float* mean_out, int V, hipStream_t s) {
+    const int slabs = col_slabs(M);
+    const dim3 grid(col_blocks(e.C, V), slabs), block(kColThreads);
+    if (V == 4) hipLaunchKernelGGL((colreduce_stage1_kernel<MODE, 4, FIN>), grid, block, 0, s, e, dy, du, M, slabs, scratch, mean_out);
+    else if constexpr (MODE == 2) {
+        if (V == 2) hipLaunchKernelGGL((colreduce_stage1_kernel<2, 2, false>), grid, block, 0, s, e, dy, du, M, slabs, scratch, mean_out);
+        else hipLaunchKernelGGL((colreduce_stage1_kernel<2, 1, false>), grid, block, 0, s, e, dy, du, M, slabs, scratch, mean_out);
+    } else hipLaunchKernelGGL((colreduce_stage1_kernel<MODE, 1, FIN>), grid, block, 0, s, e, dy, du, M, slabs, scratch, mean_out);
+    T2_LAUNCH_CHECK();
+    return 0;
+}
 template <int MODE>
 int colreduce(const BnElem& e, const float* dy, float* du, int M, float eps, float* out0, float* out1, float* scratch, hipStream_t s) {
     const int slabs = col_slabs(M);
-    if (cols_vectorisable(e.z, e.C, e.C) && cols_vectorisable(dy, e.C, e.C) && cols_vectorisable(du, e.C, e.C))
-        hipLaunchKernelGGL((colreduce_stage1_kernel<MODE, 4>), dim3((e.C + 4 * kColLanes - 1) / (4 * kColLanes), slabs), dim3(kColThreads), 0, s, e, dy, du, M, slabs, scratch);
-    else
-        hipLaunchKernelGGL((colreduce_stage1_kernel<MODE, 1>), dim3((e.C + kColLanes - 1) / kColLanes, slabs), dim3(kColThreads), 0, s, e, dy, du, M, slabs, scratch);
-    T2_LAUNCH_CHECK();
-    hipLaunchKernelGGL(colreduce_stage2_kernel, dim3((e.C + 255) / 256), dim3(256), 0, s, scratch, e.C, slabs, M, MODE, eps, out0, out1);
+    const bool vec = cols_vectorisable(e.z, e.C, e.C) && cols_vectorisable(dy, e.C, e.C) && cols_vectorisable(du, e.C, e.C);
+    T2_TRY_RC((colreduce_stage1<MODE, false>(e, dy, du, M, scratch, nullptr, col_width(e.C, slabs, vec, false), s)));
+    hipLaunchKernelGGL(colreduce_stage2_kernel, dim3((e.C + 255) / 256), dim3(256), 0, s, scratch, e.C, slabs, M, MODE, eps, out0, out1,
+                       (const float*)nullptr, 0.f, (float*)nullptr, (float*)nullptr);
     T2_LAUNCH_CHECK();
     return 0;
 }
 
 }  // namespace
+
+void set_bn_fuse(int on) { g_bn_fuse = on != 0; }
+int get_bn_fuse() { return g_bn_fuse; }
+void bn_fuse_counts(uint64_t* out, int reset) {
+    for (int i = 0; i < 3; ++i) { out[i] = g_bn_counts[i]; if (reset) g_bn_counts[i] = 0; }
+}
 
 int conv_bn_fwd(const ConvBnFwd& a, hipStream_t s) {
     const int M = a.B * a.T;
@@ -358,13 +496,25 @@ int conv_bn_fwd(const ConvBnFwd& a, hipStream_t s) {
     g16.B16 = reinterpret_cast<const __bf16*>(a.wperm); g16.ldb16 = (long)a.K * a.Cin;
     if (a.handoff && gemm_handoff(g, g16)) {
         g = g16;
-        hipLaunchKernelGGL(permute_w_fwd_kernel<__bf16>, dim3(grid_for(nw)), dim3(256), 0, s, a.w, reinterpret_cast<__bf16*>(a.wperm), a.Cout, a.Cin, a.K);
+        permute_w(false, a.w, reinterpret_cast<__bf16*>(a.wperm), a.Cout, a.Cin, a.K, s);
     } else
-        hipLaunchKernelGGL(permute_w_fwd_kernel<float>, dim3(grid_for(nw)), dim3(256), 0, s, a.w, a.wperm, a.Cout, a.Cin, a.K);
+        permute_w(false, a.w, a.wperm, a.Cout, a.Cin, a.K, s);
     T2_LAUNCH_CHECK();
     T2_TRY_RC(gemm(g, s));
     BnElem e{a.z, a.mean, a.invstd, a.gamma, a.beta, a.Cout, a.act, a.drop_p, rng_key(a.seed, a.site)};
-    if (a.training) {
+    const size_t n = (size_t)M * a.Cout;
+    if (a.training && get_bn_fuse()) {
+        // four launches for six: the MODE 1 pass finishes the mean from the MODE 0 partials (first half of the scratch) and
+        // leaves its own behind them; one stage 2 finishes var / invstd from those and updates the running statistics
+        const int slabs = col_slabs(M);
+        const int V = col_width(e.C, slabs, cols_vectorisable(e.z, e.C, e.C), false);
+        T2_TRY_RC((colreduce_stage1<0, false>(e, nullptr, nullptr, M, a.scratch, nullptr, V, s)));
+        T2_TRY_RC((colreduce_stage1<1, true>(e, nullptr, nullptr, M, a.scratch, a.mean, V, s)));
+        hipLaunchKernelGGL(colreduce_stage2_kernel, dim3((a.Cout + 255) / 256), dim3(256), 0, s, a.scratch + (size_t)slabs * e.C, a.Cout, slabs, M, 1,
+                           a.eps, a.invstd, a.var, a.mean, 0.1f, a.run_mean, a.run_var);
+        T2_LAUNCH_CHECK();
+        ++g_bn_counts[0];
+    } else if (a.training) {
         T2_TRY_RC(colreduce<0>(e, nullptr, nullptr, M, a.eps, a.mean, nullptr, a.scratch, s));
         T2_TRY_RC(colreduce<1>(e, nullptr, nullptr, M, a.eps, a.invstd, a.var, a.scratch, s));
         if (a.run_mean) {
@@ -376,7 +526,6 @@ int conv_bn_fwd(const ConvBnFwd& a, hipStream_t s) {
         hipLaunchKernelGGL(invstd_from_var_kernel, dim3((a.Cout + 255) / 256), dim3(256), 0, s, a.run_var, a.Cout, a.eps, a.invstd);
         T2_LAUNCH_CHECK();
     }
-    const size_t n = (size_t)M * a.Cout;
     if (bn_vectorisable(e, a.residual, a.y) && aligned8(a.y16))
         hipLaunchKernelGGL(bn_apply_kernel<4>, dim3(grid_for(n / 4)), dim3(256), 0, s, e, a.residual, a.y, a.y16, n);
     else
@@ -435,22 +584,40 @@ int conv_bn_bwd(const ConvBnBwd& a, hipStream_t s) {
         if (tw || tx) dz16 = reinterpret_cast<__bf16*>(a.gemm_ws);
     }
     // du (into a.dz) + the two column sums; d(gamma) = sum du*xhat, d(beta) = sum du
-    T2_TRY_RC(colreduce<2>(e, a.dy, a.dz, M, a.eps, a.dbeta, a.dgamma, a.scratch, s));
-    if (bn_vectorisable(e, a.dz, a.dbeta) && cols_vectorisable(a.dgamma, e.C, e.C))
-        hipLaunchKernelGGL(bn_bwd_dz_kernel<4>, dim3(grid_for(n / 4)), dim3(256), 0, s, e, a.dz, a.dbeta, a.dgamma, M, a.training, a.dz, dz16, n);
-    else
-        hipLaunchKernelGGL(bn_bwd_dz_kernel<1>, dim3(grid_for(n)), dim3(256), 0, s, e, a.dz, a.dbeta, a.dgamma, M, a.training, a.dz, dz16, n);
-    T2_LAUNCH_CHECK();
-    T2_TRY_RC(colsum(a.dz, a.Cout, M, a.Cout, a.dbias, nullptr, a.scratch, s));
-    T2_TRY_RC(gemm(g, s));
     const size_t nw = (size_t)a.Cout * a.Cin * a.K;
+    if (get_bn_fuse()) {
+        // three launches: the dz kernel finishes the two sums in its prologue and leaves the slab partials of d(bias) in wperm,
+        // which nobody uses before the products (64*Cout floats: it has them when Cin*K >= 64; a smaller layer runs colsum)
+        const int slabs = col_slabs(M);
+        const bool vec = cols_vectorisable(e.z, e.C, e.C) && cols_vectorisable(a.dy, e.C, e.C) && cols_vectorisable(a.dz, e.C, e.C);
+        const int V = col_width(e.C, slabs, vec, true);
+        T2_TRY_RC((colreduce_stage1<2, false>(e, a.dy, a.dz, M, a.scratch, nullptr, V, s)));
+        float* part = (size_t)a.Cin * a.K >= 64 ? a.wperm : nullptr;
+        const dim3 grid(col_blocks(e.C, V), slabs), block(kColThreads);
+        if (V == 4) hipLaunchKernelGGL(bn_bwd_dz_cols_kernel<4>, grid, block, 0, s, e, a.dz, a.scratch, M, slabs, a.training, a.dz, dz16, a.dbeta, a.dgamma, part);
+        else if (V == 2) hipLaunchKernelGGL(bn_bwd_dz_cols_kernel<2>, grid, block, 0, s, e, a.dz, a.scratch, M, slabs, a.training, a.dz, dz16, a.dbeta, a.dgamma, part);
+        else hipLaunchKernelGGL(bn_bwd_dz_cols_kernel<1>, grid, block, 0, s, e, a.dz, a.scratch, M, slabs, a.training, a.dz, dz16, a.dbeta, a.dgamma, part);
+        T2_LAUNCH_CHECK();
+        if (part) T2_TRY_RC(colsum_finish(part, M, a.Cout, a.dbias, s));
+        else T2_TRY_RC(colsum(a.dz, a.Cout, M, a.Cout, a.dbias, nullptr, a.scratch, s));
+        ++g_bn_counts[part ? 1 : 2];
+    } else {
+        T2_TRY_RC(colreduce<2>(e, a.dy, a.dz, M, a.eps, a.dbeta, a.dgamma, a.scratch, s));
+        if (bn_vectorisable(e, a.dz, a.dbeta) && cols_vectorisable(a.dgamma, e.C, e.C))
+            hipLaunchKernelGGL(bn_bwd_dz_kernel<4>, dim3(grid_for(n / 4)), dim3(256), 0, s, e, a.dz, a.dbeta, a.dgamma, M, a.training, a.dz, dz16, n);
+        else
+            hipLaunchKernelGGL(bn_bwd_dz_kernel<1>, dim3(grid_for(n)), dim3(256), 0, s, e, a.dz, a.dbeta, a.dgamma, M, a.training, a.dz, dz16, n);
+        T2_LAUNCH_CHECK();
+        T2_TRY_RC(colsum(a.dz, a.Cout, M, a.Cout, a.dbias, nullptr, a.scratch, s));
+    }
+    T2_TRY_RC(gemm(g, s));
     if (!fold) {
         hipLaunchKernelGGL(unpermute_dw_kernel, dim3(grid_for(nw)), dim3(256), 0, s, a.wperm, a.dw, a.Cout, a.Cin, a.K);
         T2_LAUNCH_CHECK();
     }
     if (a.dx) {
-        if (w16) hipLaunchKernelGGL(permute_w_bwd_kernel<__bf16>, dim3(grid_for(nw)), dim3(256), 0, s, a.w, reinterpret_cast<__bf16*>(a.wperm), a.Cout, a.Cin, a.K);
-        else hipLaunchKernelGGL(permute_w_bwd_kernel<float>, dim3(grid_for(nw)), dim3(256), 0, s, a.w, a.wperm, a.Cout, a.Cin, a.K);
+        if (w16) permute_w(true, a.w, reinterpret_cast<__bf16*>(a.wperm), a.Cout, a.Cin, a.K, s);
+        else permute_w(true, a.w, a.wperm, a.Cout, a.Cin, a.K, s);
         T2_LAUNCH_CHECK();
         T2_TRY_RC(gemm(h, s));
     }

@@ -118,21 +118,6 @@ __global__ void __launch_bounds__(kColThreads) colsum_stage1_kernel(const float*
         }
     }
 }
-// sum_{s < count} p[s * stride], terms requested 16 at a time and added in index order (a dependent load per term
-// costs ~0.3 us each: 20 us for 64 slabs)
-__device__ __forceinline__ float ordered_sum16(const float* __restrict__ p, int count, long stride) {
-    float acc = 0.f;
-    int s = 0;
-    for (; s + 16 <= count; s += 16) {
-        float v[16];
-#pragma unroll
-        for (int j = 0; j < 16; ++j) v[j] = p[(long)(s + j) * stride];
-#pragma unroll
-        for (int j = 0; j < 16; ++j) acc += v[j];
-    }
-    for (; s < count; ++s) acc += p[(long)s * stride];
-    return acc;
-}
 __global__ void colsum_stage2_kernel(const float* __restrict__ scratch, int N, int slabs, float* out, float* out2) {
     const int n = blockIdx.x * blockDim.x + threadIdx.x;
     if (n >= N) return;
@@ -174,6 +159,11 @@ int colsum(const float* X, long ld, int M, int N, float* out, float* out2, float
         hipLaunchKernelGGL(colsum_stage1_kernel<1>, dim3((N + kColLanes - 1) / kColLanes, slabs), dim3(kColThreads), 0, s, X, ld, M, N, slabs, scratch);
     T2_LAUNCH_CHECK();
     hipLaunchKernelGGL(colsum_stage2_kernel, dim3((N + 255) / 256), dim3(256), 0, s, scratch, N, slabs, out, out2);
+    T2_LAUNCH_CHECK();
+    return 0;
+}
+int colsum_finish(const float* partials, int M, int N, float* out, hipStream_t s) {
+    hipLaunchKernelGGL(colsum_stage2_kernel, dim3((N + 255) / 256), dim3(256), 0, s, partials, N, col_slabs(M), out, (float*)nullptr);
     T2_LAUNCH_CHECK();
     return 0;
 }

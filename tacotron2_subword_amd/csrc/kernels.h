@@ -421,6 +421,15 @@ struct ConvBnFwd {
     const __bf16* x16; __bf16* y16;              // optional: the copy of x an earlier layer wrote (used with handoff), the copy of y to write
 };
 int conv_bn_fwd(const ConvBnFwd& a, hipStream_t s);
+// 1 (default; env T2_BN_FUSE=0 turns it off): a conv + BatchNorm layer finishes its column reductions in the prologue of the
+// kernel that consumes them (forward: the mean in the pass over the centred squares, then one stage 2 for var / invstd and
+// the running statistics, 4 launches for 6; backward: 3 for 5 and no pass over dz for d(bias)).  0: every reduction has a
+// stage-2 launch of its own and the running statistics theirs.  Same bits either way.
+void set_bn_fuse(int on);
+int get_bn_fuse();
+// layer calls since the last reset: [0] forward, statistics finished in the consuming kernels; [1] backward, likewise, d(bias)
+// partials from the dz kernel; [2] backward, likewise, but d(bias) by colsum (no room for the partials: Cin*K < 64)
+void bn_fuse_counts(uint64_t* out, int reset);
 struct ConvBnBwd {
     const float* x; int B, T, Cin, Cout, K;
     const float* w; const float* gamma; const float* beta;
@@ -538,6 +547,8 @@ int permute_rows(const float* in, float* out, int R1, int R2, int W, hipStream_t
 int relu_drop_bwd(const float* dy, const float* y, float* dz, float scale, size_t n, hipStream_t s);
 // out[n] = sum_m X[m*ld + n]  (bias gradients; two fixed-order stages, scratch >= 64*N floats); out2 optional copy
 int colsum(const float* X, long ld, int M, int N, float* out, float* out2, float* scratch, hipStream_t s);
+// stage 2 alone, for a caller whose own kernel left colsum's stage-1 partials [col_slabs(M)][N] (conv.hip: the dz kernel)
+int colsum_finish(const float* partials, int M, int N, float* out, hipStream_t s);
 // X[r, 0:A] += X[r, A:2A]   (rows of 2A floats)
 int fold_halves(float* X, size_t rows, int A, hipStream_t s);
 // out[i] = sum_b X[b*n + i]
