@@ -1,6 +1,6 @@
 """Attention modules as PARAMETER CONTAINERS with the reference's constructor signature and
 state_dict keys (attention.py:7-85, 291-398).  The arithmetic runs inside the fused HIP decoder
-(csrc/attention.hip); these classes are never called step by step."""
+(csrc/attention.hip for SMA / LSA forward and SMA backward, attention_lsa_bwd.hip, attention_gmm.hip, attention_dca.hip); these classes are never called step by step."""
 from torch import nn
 
 from .layers import ConvNorm, LinearNorm

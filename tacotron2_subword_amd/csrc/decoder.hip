@@ -262,8 +262,10 @@ int cast_shadows(const Dec& c, bool split) {
     return cast_part(c.w.dec.w_hh, z.Hd, c.P16(c.L.wt16d), lod, 4 * z.Hd, 4 * z.Hd, z.Hd, true, split, c.s);
 }
 
-// attention kind of the ABI (T2_ATTN_*) -> kernel-level kind (0 SMA, 1 LSA, 2 GMM, 3 DCA)
-int kernel_kind(int kind) { return kind == T2_ATTN_GMM ? 2 : kind == T2_ATTN_DCA ? 3 : kind; }
+// attention kind of the ABI (T2_ATTN_*; ForwardAttentionV2 has become LSA by now, normalise()) -> the kernels' kind
+AttnKind kernel_kind(int kind) {
+    return kind == T2_ATTN_GMM ? AttnKind::GMM : kind == T2_ATTN_DCA ? AttnKind::DCA : kind == T2_ATTN_SMA ? AttnKind::SMA : AttnKind::LSA;
+}
 
 DcaWeights dca_weights(const t2_attention_weights& aw) {
     DcaWeights w{};
@@ -327,9 +329,10 @@ int att_lstm_step(const Dec& c, int t) {
 int attention_step(const Dec& c, int t) {
     const Sizes& z = c.z; const t2_decoder_layout& L = c.L;
     AttnStepDesc d{};
-    d.nstreams = z.NS; d.B = z.B; d.A = z.A; d.E = z.E; d.kind = c.d.attention_kind;
+    d.nstreams = z.NS; d.B = z.B; d.A = z.A; d.E = z.E;
+    const int abi_kind = c.d.attention_kind; d.kind = kernel_kind(abi_kind);
     d.F = c.d.loc_filters; d.Kc = c.d.loc_kernel; d.seed = c.seed; d.first = t == 0;
-    d.noise_std = (c.training && d.kind == T2_ATTN_SMA) ? 2.0f : 0.f;     // attention.py:315,346-348
+    d.noise_std = (c.training && abi_kind == T2_ATTN_SMA) ? 2.0f : 0.f;   // attention.py:315,346-348
     d.max_pos = c.max_pos;
     for (int s = 0; s < z.NS; ++s) {
         AttnStream& st = d.st[s]; const StreamRef& r = c.st[s];
@@ -343,13 +346,13 @@ int attention_step(const Dec& c, int t) {
         st.pm = c.P(r.pm); st.memory = r.memory; st.lengths = r.lengths;
         st.a_prev = t > 0 ? al + (long)(t - 1) * Tin : nullptr; st.lda_prev = ldA;
         st.a_out = al + (long)t * Tin; st.lda_out = ldA;
-        if (d.kind == T2_ATTN_DCA) {
+        if (abi_kind == T2_ATTN_DCA) {
             st.dca = dca_weights(aw);
-        } else if (d.kind == T2_ATTN_GMM) {
+        } else if (abi_kind == T2_ATTN_GMM) {
             float* mu = c.P(r.wcum);                    // [T,B,kGmmPad]
             st.mu_prev = t > 0 ? mu + c.R(t - 1) * kGmmPad : nullptr; st.mu_out = mu + c.R(t) * kGmmPad;
             st.gmm_b1 = aw.mlp_b1; st.gmm_w2 = aw.mlp_w2; st.gmm_b2 = aw.mlp_b2;
-        } else if (d.kind == T2_ATTN_SMA) {
+        } else if (abi_kind == T2_ATTN_SMA) {
             st.p_out = c.P(r.psel) + (long)t * Tin; st.ldp_out = ldA;
         } else {
             float* wc = c.P(r.wcum);
@@ -366,7 +369,6 @@ int attention_step(const Dec& c, int t) {
         st.site_noise = r.site_noise; st.mask_value = r.mask_value;
         st.idx_base = (uint32_t)(c.R(t) * Tin); st.idx_bstride = (uint32_t)Tin;          // logical [T,B,Tin]
     }
-    d.kind = kernel_kind(d.kind);
     ProfScope ps(PK_ATTN_FWD, c.s);
     return attention_step_fwd(d, c.s);
 }
@@ -767,7 +769,8 @@ int att_bwd_step(const Bwd& c, int t) {
     // 1. attention backward (needs dctx(t) incl. the recurrent partials of step t+1)
     AttnBwdDesc ab{};
     ab.nstreams = z.NS; ab.B = z.B; ab.A = z.A; ab.E = z.E; ab.first = first;
-    ab.kind = c.d.attention_kind; ab.F = c.d.loc_filters; ab.Kc = c.d.loc_kernel;
+    const int abi_kind = c.d.attention_kind;
+    ab.kind = kernel_kind(abi_kind); ab.F = c.d.loc_filters; ab.Kc = c.d.loc_kernel;
     ab.nsplit = attn_bwd_nsplit(c.d, z);
     for (int s = 0; s < z.NS; ++s) {
         AttnBwdStream& st = ab.st[s]; const StreamRef& r = c.st[s]; const BwdStreamRef& b = c.bst[s];
@@ -784,18 +787,18 @@ int att_bwd_step(const Bwd& c, int t) {
         if (t > 0) { st.a_prev = al + (long)(t - 1) * Tin; st.lda_prev = ldA; }
         const t2_attention_weights& aw = *r.aw;
         st.v = aw.v;
-        if (ab.kind == T2_ATTN_DCA) {
+        if (abi_kind == T2_ATTN_DCA) {
             st.w = al + (long)t * Tin; st.ldw = ldA;
             st.dca = dca_weights(aw);
             st.dca_acc = c.S(b.dldense);
-        } else if (ab.kind == T2_ATTN_GMM) {
+        } else if (abi_kind == T2_ATTN_GMM) {
             st.w = al + (long)t * Tin; st.ldw = ldA;
             st.gmm_w2 = aw.mlp_w2; st.gmm_b2 = aw.mlp_b2;
             st.mu = c.W(r.wcum) + c.R(t) * kGmmPad; st.ldmu = kGmmPad;
             st.mu_carry = c.S(b.carryc);
             st.db2_acc = c.S(b.dlconv);
             st.dw2_acc = c.S(b.dldense);
-        } else if (ab.kind == T2_ATTN_SMA) {
+        } else if (abi_kind == T2_ATTN_SMA) {
             st.p = c.W(r.psel) + (long)t * Tin; st.ldp = ldA;
         } else {
             st.w = al + (long)t * Tin; st.ldw = ldA;
@@ -806,14 +809,13 @@ int att_bwd_step(const Bwd& c, int t) {
             st.ddense_acc = c.S(b.dldense);
         }
         float* cbuf = c.S(b.carry);
-        if (ab.kind == T2_ATTN_SMA) { st.carry = cbuf + (size_t)((t + 1) & 1) * z.B * Tin; st.carry_out = cbuf + (size_t)(t & 1) * z.B * Tin; }
+        if (abi_kind == T2_ATTN_SMA) { st.carry = cbuf + (size_t)((t + 1) & 1) * z.B * Tin; st.carry_out = cbuf + (size_t)(t & 1) * z.B * Tin; }
         else st.carry = cbuf;
         st.dctx_out = c.S(b.dctx) + c.R(t) * z.E; st.lddctx_out = z.E;
         st.dq_out = c.S(b.dq) + c.R(t) * 2 * z.A; st.lddq_out = 2 * z.A;
         st.dv_acc = c.S(b.dv);
         st.dpm_acc = c.S(b.dpm);
     }
-    ab.kind = kernel_kind(ab.kind);
     { ProfScope ps(PK_ATTN_BWD, c.s); T2_TRY(attention_step_bwd(ab, c.s)); }
     // 2. LSTM pointwise backward
     LstmBwdPointDesc p{};
@@ -1144,7 +1146,7 @@ int bwd_stream_tail(const Bwd& c, int s, hipStream_t ts) {
     const bool gmm = c.d.attention_kind == T2_ATTN_GMM || dcak;       // both: no processed-memory term
     if (dcak) {
         // W.weight went through the query-projection path above; W.bias = column sums of dq; the rest from the per-item
-        // accumulators dv | dbT | dU | dT | dF | dV (attention.hip)
+        // accumulators dv | dbT | dU | dT | dF | dV (attention_dca.hip)
         T2_REQUIRE(ag.mlp_b1 && ag.mlp_w2 && ag.loc_conv && ag.loc_dense && ag.dca_T && ag.dca_bT && ag.v, "t2_decoder_backward: DCA gradient buffers missing");
         T2_TRY(colsum(DQ, 2 * z.A, BT, z.A, ag.mlp_b1, nullptr, cws, ts));
         const size_t na = dca_acc_floats(z.A);

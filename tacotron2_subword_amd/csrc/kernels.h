@@ -178,7 +178,7 @@ int cast_transpose_bf16(const float* src, long ld_src, __bf16* dst, long ld_dst,
 int cast_rows_split_bf16(const float* src, long ld_src, __bf16* hi, __bf16* lo, long ld_dst, int R, int C, hipStream_t s);
 int cast_transpose_split_bf16(const float* src, long ld_src, __bf16* hi, __bf16* lo, long ld_dst, int R, int C, hipStream_t s);
 
-// ------------------------------------------------------------------ attention (attention.hip)
+// ------------------------------------------------------------------ attention (attention*.hip)
 // DynamicConvolutionAttention (attention.py:195-289): 8 static + 8 dynamic channels, 21 taps, 11-tap prior
 constexpr int kDcaC = 8, kDcaK = 21, kDcaP = 11, kDcaPad = (kDcaK - 1) / 2;
 struct DcaWeights {                       // wq / qpart of the stream carry W (Linear Ha->A)
@@ -210,22 +210,25 @@ struct AttnStream {
     const float* loc_conv; const float* loc_dense;   // LSA: [F,2,Kc], [A,F]
     uint32_t site_noise; uint32_t idx_base, idx_bstride;   // SMA noise index = idx_base + b*idx_bstride + j
     int Tin;
-    // GMM attention (kind 2): wq / qpart carry mlp.0 (Linear Ha->A); second layer and state below
+    // GMM attention: wq / qpart carry mlp.0 (Linear Ha->A); second layer and state below
     const float* gmm_b1; const float* gmm_w2; const float* gmm_b2;   // [A], [3K, A], [3K]
     const float* mu_prev; float* mu_out;  // [B, kGmmPad] mixture means before / after this step (mu_prev null at t=0 -> 0)
-    DcaWeights dca;                       // kind 3
+    DcaWeights dca;                       // DCA
     float mask_value;                     // energy of positions past the item's length (the module's score_mask_value)
 };
 constexpr int kGmmK = 5, kGmmPad = 8;     // mixtures (attention.py:409), row pitch of the mean buffers
+// The mechanisms the per-step kernels know.  Not the ABI's numbering (T2_ATTN_*, which also has ForwardAttentionV2 = LSA
+// with a clamped length): decoder.hip translates once, through kernel_kind().
+enum class AttnKind : int { SMA = 0, LSA = 1, GMM = 2, DCA = 3 };
 struct AttnStepDesc {
-    AttnStream st[2]; int nstreams; int B, A, E; int kind;   // kind 0 = SMA, 1 = LSA
-    int F, Kc; float noise_std; uint64_t seed; int first;                     // kind 2 = GMM (attention_gmm_step_fwd)
+    AttnStream st[2]; int nstreams; int B, A, E; AttnKind kind;
+    int F, Kc; float noise_std; uint64_t seed; int first;
     int lsa_pa;                                               // set by the launcher (MFMA path of the LSA dense projection)
     int max_pos;                                              // > 0: valid length clamped to max_pos (ForwardAttentionV2, see decoder.hip)
 };
 int attention_step_fwd(const AttnStepDesc& d, hipStream_t s);
 
-// Backward of one attention step (reverse time): SMA (kind 0) or LSA (kind 1).
+// Backward of one attention step (reverse time).
 struct AttnBwdStream {
     const float* dctx[3]; long lddctx[3];  // direct gradient sources on ctx(t) [B,E] (nullable entries)
     const float* part; int nparts; long part_stride; long ldpart; int part_col;   // recurrent partials (ctx columns)
@@ -248,18 +251,18 @@ struct AttnBwdStream {
     const float* loc_conv; const float* loc_dense;   // [F,2,Kc], [A,F]
     float* carry_cum;                      // [B,Tin] gradient on the cumulative weights (in/out); `carry` holds the w_{t-1} part
     float* dconv_acc; float* ddense_acc;   // [B,F*2*Kc], [B,A*F] per-item weight gradients accumulated over steps
-    // GMM only (kind 2): q = saved pre-activation of mlp.0 (incl. bias); w = saved weights of step t
+    // GMM only: q = saved pre-activation of mlp.0 (incl. bias); w = saved weights of step t
     const float* gmm_w2; const float* gmm_b2;
     const float* mu; long ldmu;            // [B, kGmmPad] mixture means of step t
     float* mu_carry;                       // [B, kGmmPad] gradient on the means flowing in from step t+1 (in/out)
     float* dw2_acc; float* db2_acc;        // [B, 3K*A], [B, 16] per-item accumulators
-    // DCA only (kind 3): q = saved pre-activation of W (incl. bias); w = weights of step t; a_prev = weights of step t-1
+    // DCA only: q = saved pre-activation of W (incl. bias); w = weights of step t; a_prev = weights of step t-1
     // (null at t=0 -> one-hot at 0); carry = gradient on a_{t} from step t+1 (in/out)
     DcaWeights dca;
     float* dca_acc;                        // [B][A (dv) + A (dbT) + A*C (dU) + A*C (dT) + C*K (dF) + C*K*A (dV)] per-item accumulators
 };
 __host__ __device__ inline size_t dca_acc_floats(int A) { return (size_t)2 * A + 2 * (size_t)A * kDcaC + kDcaC * kDcaK + (size_t)kDcaC * kDcaK * A; }
-struct AttnBwdDesc { AttnBwdStream st[2]; int nstreams; int B, A, E; int first; int kind, F, Kc; int nsplit; };   // nsplit: SMA only
+struct AttnBwdDesc { AttnBwdStream st[2]; int nstreams; int B, A, E; int first; AttnKind kind; int F, Kc; int nsplit; };   // nsplit: SMA only
 int attention_step_bwd(const AttnBwdDesc& d, hipStream_t s);
 
 

@@ -179,7 +179,7 @@ class _DecoderFn(torch.autograd.Function):
 
 class Decoder(nn.Module):
     """model.py:128-492.  Holds the parameters under the reference's names; the step loop lives in
-    csrc/ (lstm.hip, attention.hip, decoder.hip)."""
+    csrc/ (lstm.hip, attention*.hip, decoder.hip)."""
 
     def __init__(self, hparams, single=False):
         super().__init__()

@@ -176,12 +176,16 @@ def _edge_batch(hp, B, Tin, Tsub, T, lens_in, lens_sub):
 
 
 @pytest.mark.parametrize("att", [SMA, LSA, FA2, GMM, DCA])
-@pytest.mark.parametrize("case", ["one_frame", "one_position", "length_one_items", "long_memory", "batch_130"])
+@pytest.mark.parametrize("case", ["one_frame", "one_position", "length_one_items", "long_memory", "batch_130", "attention_dim_256", "attention_dim_32"])
 def test_teacher_forced_edge_shapes(env, att, case):
     """Edge shapes of the decoder pass (tiny dims): a single frame, a single memory position, items whose valid
     length is 1, memories long enough to leave the LDS-resident fast paths (LSA falls back to the scalar location
-    layer), a batch spanning five 32-row tiles."""
+    layer), a batch spanning five 32-row tiles; attention_dim 256 (four channel groups per lane, eight MFMA channel
+    tiles) and 32 (the matrix-core LSA routes with one channel tile) over a ragged 32-position tile and a memory
+    shorter than one tile."""
     hp = tiny_hp(att)
+    if case.startswith("attention_dim"):
+        hp["attention_dim"] = int(case.rsplit("_", 1)[1])
     P = recipe.make_weights(hp, seed=4)
     if case == "one_frame":
         B, Tin, Tsub, T, li, ls = 3, 9, 6, 1, [9, 7, 5], [6, 6, 2]
@@ -191,6 +195,8 @@ def test_teacher_forced_edge_shapes(env, att, case):
         B, Tin, Tsub, T, li, ls = 3, 10, 8, 6, [10, 1, 1], [8, 1, 3]
     elif case == "long_memory":
         B, Tin, Tsub, T, li, ls = 2, 300, 170, 4, [300, 211], [170, 95]
+    elif case.startswith("attention_dim"):
+        B, Tin, Tsub, T, li, ls = 3, 37, 9, 4, [37, 20, 33], [9, 4, 1]
     else:
         B, Tin, Tsub, T = 130, 6, 5, 3
         li, ls = [6] * 100 + [3] * 30, [5] * 90 + [2] * 40

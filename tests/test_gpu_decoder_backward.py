@@ -38,12 +38,13 @@ def hip_rnd(ops, L, hp, seed, B, T, Tin, Tsub):
                 sma_noise_bert=ops.rng_normal(seed, S["NOISE_SUB"], B * T * Tsub).view(T, B, Tsub).cpu())
 
 
-@pytest.mark.parametrize("cfg", ["tiny_eval", "tiny_train", "tiny_b33", "tiny_long", "tiny_T40", "tiny_one_frame", "tiny_long_memory", "default_train", "default_align"])
+@pytest.mark.parametrize("cfg", ["tiny_eval", "tiny_train", "tiny_b33", "tiny_long", "tiny_T40", "tiny_one_frame", "tiny_long_memory", "default_train", "default_align",
+                                 "tiny_a256", "tiny_a32"])
 @pytest.mark.parametrize("att", [SMA, LSA, FA2, GMM, DCA])
 def test_decoder_backward_vs_autograd(env, cfg, att):
     L, ops = env
-    training = cfg in ("tiny_train", "default_train", "default_align", "tiny_b33", "tiny_long", "tiny_T40", "tiny_long_memory")
-    with_align = cfg in ("default_align", "tiny_b33", "tiny_long")
+    training = cfg in ("tiny_train", "default_train", "default_align", "tiny_b33", "tiny_long", "tiny_T40", "tiny_long_memory", "tiny_a256", "tiny_a32")
+    with_align = cfg in ("default_align", "tiny_b33", "tiny_long", "tiny_a256", "tiny_a32")
     if cfg == "tiny_long":                       # several 32-position chunks per attention step, ragged tails
         hp = tiny_hp(att)
         B, Tin, Tsub, T = 2, 70, 37, 6
@@ -56,6 +57,10 @@ def test_decoder_backward_vs_autograd(env, cfg, att):
     elif cfg == "tiny_T40":                      # long enough for the chunked two-stream schedule (3 chunks of 16 steps)
         hp = tiny_hp(att)
         B, Tin, Tsub, T = 3, 12, 9, 40
+    elif cfg in ("tiny_a256", "tiny_a32"):       # attention_dim 256: four 64-channel groups per lane, eight 32-channel MFMA
+        hp = tiny_hp(att)                        # tiles; 32: the matrix-core LSA routes with one tile.  A ragged 32-position
+        hp["attention_dim"] = 256 if cfg == "tiny_a256" else 32      # tile (37) and a memory shorter than one tile (9)
+        B, Tin, Tsub, T = 3, 37, 9, 4
     elif cfg.startswith("tiny"):
         hp = tiny_hp(att)
         B, Tin, Tsub, T = (33 if cfg == "tiny_b33" else 5), 11, 7, 9
