@@ -155,6 +155,9 @@ int t2_bn_fuse_counts(uint64_t* out_host /* [3] */, int reset);
 /* Makes `stream` wait for everything the library has queued on its internal side stream of the current device
  * (t2_decoder_bwd_args.defer_weight_grads). */
 int t2_side_join(void* stream);
+/* t2_decoder_backward calls since the last reset (host counters): [0] returned with the weight-gradient tail still on the
+ * side stream (defer_weight_grads in effect), [1] finished everything on the caller's stream. */
+int t2_defer_counts(uint64_t* out_host /* [2] */, int reset);
 
 /* Model dimensions (hparams.py:55-95). */
 typedef struct t2_dims {
@@ -299,10 +302,12 @@ typedef struct t2_decoder_bwd_args {
     const float* ws;           /* workspace filled by t2_decoder_forward */
     float* bws;                /* t2_decoder_bwd_layout.total_floats floats of scratch */
     int training; int prenet_dropout; uint64_t seed;   /* must equal the forward call's */
-    int defer_weight_grads;    /* 1 (with t2_set_overlap on, T >= 32): d_memory / d_memory_sub are complete on `stream` when the
-                                * call returns, the weight gradients in `g` are still being written on the library's side
-                                * stream; call t2_side_join(stream) before reading them or releasing ws / bws.  0: everything
-                                * is ordered on `stream`. */
+    int defer_weight_grads;    /* 1 (with t2_set_overlap on, T >= 32; per-step launches and persistent chains alike): d_memory /
+                                * d_memory_sub are complete on `stream` when the call returns, the weight gradients in `g` are
+                                * still being written on the library's side stream (with persistent chains the library forks
+                                * it after the chains and the decoder-LSTM weight gradients go there too); call
+                                * t2_side_join(stream) before reading them or releasing ws / bws.  0: everything is ordered on
+                                * `stream`.  t2_defer_counts tells which of the two a call did. */
 } t2_decoder_bwd_args;
 int t2_decoder_backward(const t2_dims* dims, const t2_decoder_weights* w, const t2_decoder_grads* g,
                         const t2_decoder_bwd_args* a, void* stream);

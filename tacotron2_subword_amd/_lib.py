@@ -241,7 +241,7 @@ STFT_POLAR, STFT_DENOISE = 0, 1
 # every symbol include/t2amd.h declares (tests/test_abi.py checks the library exports them all)
 ABI_VERSION = 4      # include/t2amd.h T2_ABI_VERSION: struct sizes below match that header and nothing else
 
-EXPORTS = ["t2_last_error", "t2_version", "t2_chain_status", "t2_chain_status_clear", "t2_debug_report_abort", "t2_debug_occupy", "t2_chain_claimed", "t2_set_precision", "t2_get_precision", "t2_gemm_counts", "t2_set_gemm_split_min_mflop", "t2_set_split_steps", "t2_get_split_steps", "t2_step_counts", "t2_set_overlap", "t2_set_chain", "t2_get_chain", "t2_set_chain_bwd", "t2_set_gemm_staging", "t2_set_gemm_fold", "t2_set_bn_fuse", "t2_get_bn_fuse", "t2_bn_fuse_counts", "t2_side_join", "t2_decoder_layout_query", "t2_decoder_forward", "t2_decoder_infer",
+EXPORTS = ["t2_last_error", "t2_version", "t2_chain_status", "t2_chain_status_clear", "t2_debug_report_abort", "t2_debug_occupy", "t2_chain_claimed", "t2_set_precision", "t2_get_precision", "t2_gemm_counts", "t2_set_gemm_split_min_mflop", "t2_set_split_steps", "t2_get_split_steps", "t2_step_counts", "t2_set_overlap", "t2_set_chain", "t2_get_chain", "t2_set_chain_bwd", "t2_set_gemm_staging", "t2_set_gemm_fold", "t2_set_bn_fuse", "t2_get_bn_fuse", "t2_bn_fuse_counts", "t2_side_join", "t2_defer_counts", "t2_decoder_layout_query", "t2_decoder_forward", "t2_decoder_infer",
            "t2_decoder_bwd_layout_query", "t2_decoder_backward", "t2_prof_enable", "t2_prof_collect", "t2_adam_chunks", "t2_adam_step", "t2_adam_norm",
            "t2_conv_bn_forward", "t2_conv_bn_backward", "t2_embedding_forward", "t2_embedding_backward",
            "t2_lstm_seq_forward", "t2_lstm_seq_backward", "t2_lstm_seq_chain_ws_floats", "t2_gemm_ex", "t2_prof_gemm", "t2_gemm_plan", "t2_conv_handoff_plan", "t2_colsum", "t2_mask_btc",
@@ -296,6 +296,7 @@ def lib() -> C.CDLL:
         L.t2_set_split_steps.argtypes = [C.c_int]
         L.t2_step_counts.argtypes = [C.POINTER(C.c_uint64), C.c_int]
         L.t2_bn_fuse_counts.argtypes = [C.POINTER(C.c_uint64), C.c_int]
+        L.t2_defer_counts.argtypes = [C.POINTER(C.c_uint64), C.c_int]
         L.t2_set_gemm_split_min_mflop.argtypes = [C.c_int]
         L.t2_prof_collect.argtypes = [C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_int)]
         L.t2_finalize_bct.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_float, C.c_void_p]
@@ -595,6 +596,14 @@ def bn_fuse_counts(reset: bool = False):
     kernel, fused backward with the separate column sum)."""
     out = (C.c_uint64 * 3)()
     check(lib().t2_bn_fuse_counts(out, int(bool(reset))))
+    return tuple(int(v) for v in out)
+
+
+def defer_counts(reset: bool = False):
+    """Decoder backward passes since the last reset: (weight-gradient tail left on the library's side stream, everything
+    finished on the caller's stream) (include/t2amd.h t2_defer_counts)."""
+    out = (C.c_uint64 * 2)()
+    check(lib().t2_defer_counts(out, int(bool(reset))))
     return tuple(int(v) for v in out)
 
 

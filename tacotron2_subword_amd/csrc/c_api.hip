@@ -61,6 +61,7 @@ int g_chain = getenv("T2_CHAIN") ? atoi(getenv("T2_CHAIN")) : 1;   // persistent
 int g_chain_bwd = getenv("T2_CHAIN_BWD") ? atoi(getenv("T2_CHAIN_BWD")) : 1;   // ... of the backward pass (chain_bwd.hip)
 uint64_t g_step_counts[6] = {0, 0, 0, 0, 0, 0};
 int counted(int rc, int base, int family) { if (rc == 0) ++g_step_counts[base + family]; return rc; }
+uint64_t g_defer_counts[2] = {0, 0};
 int g_split_steps = getenv("T2_SPLIT_STEPS") ? atoi(getenv("T2_SPLIT_STEPS")) != 0 : 0;   // split-bf16 recurrent steps (mode 2 only)
 int side_get(Side** out) {
     int dev = 0;
@@ -244,6 +245,11 @@ int t2_get_bn_fuse(void) { return get_bn_fuse(); }
 int t2_bn_fuse_counts(uint64_t* out_host, int reset) {
     T2_REQUIRE(out_host, "null argument");
     bn_fuse_counts(out_host, reset);
+    return 0;
+}
+int t2_defer_counts(uint64_t* out_host, int reset) {
+    T2_REQUIRE(out_host, "null argument");
+    for (int i = 0; i < 2; ++i) { out_host[i] = g_defer_counts[i]; if (reset) g_defer_counts[i] = 0; }
     return 0;
 }
 int t2_side_join(void* stream) {

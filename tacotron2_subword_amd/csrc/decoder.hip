@@ -605,6 +605,19 @@ void bwd_stream_refs(const t2_decoder_grads& g, const t2_decoder_bwd_args& a, co
     }
 }
 
+// bf16 mode: ONE row-major bf16 copy of dG ([B*T][H4], `off` bytes into the GEMM scratch) serves every product that reads
+// dG: as the k-major A operand of a weight gradient (whose dG rows start row0 rows in) or as the K-contiguous A operand of
+// an input gradient; either then works in the scratch behind the copy.  on == false: no copy, descriptors pass untouched.
+struct Dg16 {
+    bool on; __bf16* p; long H4; float* rest; size_t rest_bytes;
+    GemmDesc operand(GemmDesc m, long row0, int kmajor) const {
+        if (on) { m.A16 = p + row0 * H4; m.lda16 = H4; m.a16_kmajor = kmajor; m.ws = rest; m.ws_bytes = rest_bytes; }
+        return m;
+    }
+    GemmDesc wgrad(GemmDesc m, long row0) const { return operand(m, row0, 1); }
+    GemmDesc igrad(GemmDesc m, long row0) const { return operand(m, row0, 0); }
+};
+
 struct Bwd {
     const t2_dims& d; const t2_decoder_weights& w; const t2_decoder_grads& g; const t2_decoder_bwd_args& a;
     Sizes z; t2_decoder_layout L; t2_decoder_bwd_layout BL; hipStream_t s;
@@ -622,6 +635,10 @@ struct Bwd {
     // the reverse-time chains of this pass (bwd_chains): persistent descriptors, side stream, next free event slot
     ChainBwdDesc cab{}, cbb{}; bool chain_a = false, chain_b = false;
     Side* side = nullptr; bool overlap = false; size_t ne = 0;
+    // defer: the leaf tail stays on the side stream when the entry point returns (t2_decoder_bwd_args.defer_weight_grads).
+    // With the attention chain persistent the decoder-LSTM weight gradients wait for that fork too: bwd_chains leaves
+    // their dG copy (dgd16; dgd16_staged = already filled) instead of issuing them in front of chain A.
+    bool defer = false; Dg16 dgd16{}; bool dgd16_staged = false;
 };
 
 // C[M,N] = X[M,K] . W[K,N]   (W row-major with leading dimension ldw: "NN")
@@ -635,18 +652,6 @@ GemmDesc matmul_tn(const Bwd& c, const float* G, long ldg, const float* X, long 
     return g;
 }
 
-// bf16 mode: ONE row-major bf16 copy of dG ([B*T][H4], `off` bytes into the GEMM scratch) serves every product that reads
-// dG: as the k-major A operand of a weight gradient (whose dG rows start row0 rows in) or as the K-contiguous A operand of
-// an input gradient; either then works in the scratch behind the copy.  on == false: no copy, descriptors pass untouched.
-struct Dg16 {
-    bool on; __bf16* p; long H4; float* rest; size_t rest_bytes;
-    GemmDesc operand(GemmDesc m, long row0, int kmajor) const {
-        if (on) { m.A16 = p + row0 * H4; m.lda16 = H4; m.a16_kmajor = kmajor; m.ws = rest; m.ws_bytes = rest_bytes; }
-        return m;
-    }
-    GemmDesc wgrad(GemmDesc m, long row0) const { return operand(m, row0, 1); }
-    GemmDesc igrad(GemmDesc m, long row0) const { return operand(m, row0, 0); }
-};
 size_t dg16_bytes(const Sizes& z, int H4) { return ((size_t)H4 * z.B * z.T * sizeof(__bf16) + 255) & ~(size_t)255; }
 Dg16 dg16_carve(const Bwd& c, bool on, size_t off, int H4) {
     unsigned char* const at = reinterpret_cast<unsigned char*>(c.gemm_ws()) + off;
@@ -997,8 +1002,9 @@ int bwd_projections(const Bwd& c) {
 }
 
 // Decoder-LSTM weight gradients.  They need nothing from chain A: they run on chain B's stream `sb` once its
-// recurrence is done, underneath the rest of chain A (whose launches leave most CUs idle).  staged: the chunk loop has
-// already filled the shared bf16 copy of dG.
+// recurrence is done, underneath the rest of chain A (whose launches leave most CUs idle); next to a persistent chain A
+// there is nothing to run under, and with a deferred tail they join it on the side stream (t2_decoder_backward).
+// staged: the chunk loop has already filled the shared bf16 copy of dG.
 int bwd_dec_lstm_wgrads(const Bwd& c, const Dg16& dg, bool staged, hipStream_t sb) {
     const Sizes& z = c.z; const t2_decoder_layout& L = c.L;
     const int BT = z.B * z.T;
@@ -1073,7 +1079,10 @@ int bwd_chains(Bwd& c) {
         }
         T2_TRY(gemm(dd, sb));
         if (c.overlap) T2_TRY(stream_edge(*c.side, c.ne++, sb, c.s));
-        if (t0 == 0) T2_TRY(bwd_dec_lstm_wgrads(c, dg, chunk_cast, sb));
+        // (persistent chain A and a deferred tail: they go on the side stream after the fork, t2_decoder_backward; chain A
+        //  writes nothing into the GEMM scratch, so the bf16 copy of dG is still there)
+        if (t0 == 0 && c.chain_a && c.defer) { c.dgd16 = dg; c.dgd16_staged = chunk_cast; }
+        else if (t0 == 0) T2_TRY(bwd_dec_lstm_wgrads(c, dg, chunk_cast, sb));
         if (c.chain_a) {
             c.cab.t0 = t0; c.cab.t1 = t1;
             ProfScope ps(PK_CHAIN_A_BWD, c.s);
@@ -1085,7 +1094,7 @@ int bwd_chains(Bwd& c) {
     return 0;
 }
 
-// Tail of stream s on stream `ts`: attention-LSTM weights, prenet, attention parameters, d(memory)
+// Leaf tail of stream s on stream `ts`: attention-LSTM weights, prenet, attention parameters
 int bwd_stream_tail(const Bwd& c, int s, hipStream_t ts) {
     const Sizes& z = c.z; const t2_decoder_layout& L = c.L;
     const StreamRef& r = c.st[s]; const BwdStreamRef& b = c.bst[s];
@@ -1178,12 +1187,18 @@ int bwd_stream_tail(const Bwd& c, int s, hipStream_t ts) {
         T2_TRY(batch_sum(c.S(b.dlconv), (lsa_chain ? 2 : 1) * z.B, c.d.loc_filters * 2 * c.d.loc_kernel, ag.loc_conv, ts));
         T2_TRY(batch_sum(c.S(b.dldense), (lsa_chain ? 2 : 1) * z.B, z.A * c.d.loc_filters, ag.loc_dense, ts));
     }
-    if (!gmm) {
-        const float* DPM = c.S(b.dpm);
-        T2_TRY(gemm(matmul_tn(c, DPM, z.A, r.memory, z.E, ag.wm, z.E, z.A, z.E, z.B * r.Tin), ts));
-        // d(memory) = dPM . Wm  +  per item: align^T [Tin x T] . dctx [T x E]
-        T2_TRY(gemm(matmul_nn(DPM, z.A, r.aw->wm, z.E, b.d_memory, z.E, z.B * r.Tin, z.E, z.A), c.s));     // caller's stream: feeds the encoders
-    }
+    if (!gmm) T2_TRY(gemm(matmul_tn(c, c.S(b.dpm), z.A, r.memory, z.E, ag.wm, z.E, z.A, z.E, z.B * r.Tin), ts));
+    return 0;
+}
+
+// d(memory) of stream s = dPM . Wm  +  per item: align^T [Tin x T] . dctx [T x E], on the caller's stream: it feeds the
+// encoders.  Neither descriptor carries scratch (nothing staged, no split-K), so these products may run beside a tail
+// that works in the GEMM scratch on another stream.
+int bwd_stream_dmemory(const Bwd& c, int s) {
+    const Sizes& z = c.z;
+    const StreamRef& r = c.st[s]; const BwdStreamRef& b = c.bst[s];
+    const bool gmm = c.d.attention_kind == T2_ATTN_GMM || c.d.attention_kind == T2_ATTN_DCA;     // no processed-memory term
+    if (!gmm) T2_TRY(gemm(matmul_nn(c.S(b.dpm), z.A, r.aw->wm, z.E, b.d_memory, z.E, z.B * r.Tin, z.E, z.A), c.s));
     GemmDesc dm = gemm_desc();
     dm.A = r.align; dm.sam = 1; dm.sak = r.Tin; dm.bsA = (long)z.T * r.Tin;
     dm.B = c.S(b.dctx); dm.sbk = (long)z.B * z.E; dm.sbn = 1; dm.bsB = z.E;     // dctx is [T,B,E]
@@ -1253,21 +1268,27 @@ int t2_decoder_backward(const t2_dims* dims_in, const t2_decoder_weights* w, con
     bwd_stream_refs(*g, *a, c.BL, c.bst);
     c.use16 = use_bf16_steps(c.z);                 // must match the forward pass (the shadows live in its workspace)
     c.split = use_split_steps(c.z);                // likewise
+    c.defer = g_overlap && c.z.T >= 32 && a->defer_weight_grads != 0;
     T2_TRY(bwd_projections(c));
     T2_TRY(bwd_chains(c));
     // ---- after the chains.  Only d(memory) feeds the caller's next backward nodes (the encoders); every weight gradient
-    // is a leaf.  defer_weight_grads: the weight-gradient tail (and the decoder-LSTM weight gradients already queued
-    // there) stays on the side stream, un-joined, underneath the encoders' backward — the caller joins with
-    // t2_side_join() before it reads a gradient or releases a workspace.  Otherwise: join here, one stream.
-    const bool defer = c.overlap && a->defer_weight_grads != 0;
+    // is a leaf.  defer_weight_grads: the weight-gradient tail stays on the side stream, un-joined, underneath the
+    // encoders' backward — the caller joins with t2_side_join() before it reads a gradient or releases a workspace.
+    // The decoder-LSTM weight gradients are there too: queued by the launch path's chain B, or (persistent chains: no
+    // side stream until here) issued now, ahead of the tails, whose dG copy at the head of the scratch overwrites theirs.
+    // Otherwise: join here, one stream.
     hipStream_t ts = c.s;                                                // stream of the weight-gradient tail
-    if (defer) {
+    if (c.defer) {
+        if (!c.side) T2_TRY(side_get(&c.side));
         T2_TRY(stream_edge(*c.side, c.ne++, c.s, c.side->s));           // chain A is complete: dG, dq, d(pm) of every step
         ts = c.side->s;
+        if (c.chain_a) T2_TRY(bwd_dec_lstm_wgrads(c, c.dgd16, c.dgd16_staged, ts));
     } else if (c.overlap) {
         T2_TRY(stream_edge(*c.side, c.ne++, c.side->s, c.s));           // join (split-K scratch and colsum scratch are shared)
     }
+    for (int s = 0; s < c.z.NS; ++s) T2_TRY(bwd_stream_dmemory(c, s));
     for (int s = 0; s < c.z.NS; ++s) T2_TRY(bwd_stream_tail(c, s, ts));
+    ++g_defer_counts[c.defer ? 0 : 1];
     return 0;
 }
 

@@ -40,4 +40,7 @@ extern int g_overlap, g_chain, g_chain_bwd, g_split_steps;
 extern uint64_t g_step_counts[6];
 int counted(int rc, int base, int family);
 
+// t2_decoder_backward calls since the last reset (t2_defer_counts): [0] tail left on the side stream, [1] finished on the caller's
+extern uint64_t g_defer_counts[2];
+
 }  // namespace t2
