@@ -6,7 +6,7 @@
 
 namespace t2 {
 
-// ------------------------------------------------------------------ GEMM (gemm.hip)
+// ------------------------------------------------------------------ GEMM (gemm_dispatch.hip; kernels: gemm_f32.hip, gemm_bf16conv.hip, gemm.hip)
 enum Act : int { ACT_NONE = 0, ACT_RELU = 1, ACT_TANH = 2 };
 
 struct GemmDesc {
@@ -23,7 +23,7 @@ struct GemmDesc {
     uint32_t drop_base, drop_mstride;             // drop_mstride 0 -> N
     float* ws; size_t ws_bytes;                   // split-K scratch (nullable -> no split)
     int splitk;                                   // 0 = choose automatically
-    int conv_a, conv_b, conv_T, conv_C, conv_pad; // implicit im2col operand (gemm.hip ConvAddr): A rows / B k-rows are
+    int conv_a, conv_b, conv_T, conv_C, conv_pad; // implicit im2col operand (gemm_common.h ConvAddr): A rows / B k-rows are
                                                   // frames of X[B*T, C], the other index is dk*C + ci
     int fp32_only;                                // never use the bf16-operand kernel for this product
     const __bf16* A16; long lda16;                // optional pre-staged bf16 copies of the operands, K contiguous:
@@ -48,7 +48,7 @@ inline GemmDesc gemm_desc() {
 }
 int gemm(const GemmDesc& d, hipStream_t s);
 
-// What gemm() does with a descriptor, decided on the host before anything is launched (gemm.hip plan_gemm).
+// What gemm() does with a descriptor, decided on the host before anything is launched (gemm_dispatch.hip plan_gemm).
 enum class GemmKernel : int {
     f32_64, f32_128,    // exact fp32 kernel, 64x64 / 128x128 tiles, fp32 operands
     bf16conv,           // mode 1: bf16 MFMAs on fp32 operands converted in the kernel (128x128 tiles)
@@ -91,7 +91,7 @@ int stage_planned(const float* src, const GemmOperandPlan& o, bool split, __bf16
 // bf16 copy of an fp32 operand, K contiguous: dst[row*K + k] = src[row*ld + k] (kc) or src[k*ld + row] (!kc);
 // rows % 64 == 0, K % 64 == 0, 16-byte aligned rows.  For GemmDesc::A16 / B16 shared by several products.
 int stage_bf16(const float* src, bool kc, long ld, __bf16* dst, int rows, int K, hipStream_t s);
-// hi / lo copy of an fp32 operand for the split-bf16 mode (gemm.hip, stage_split_kc_kernel): three bf16 terms per element.
+// hi / lo copy of an fp32 operand for the split-bf16 mode (gemm.hip, stage_kc_kernel<true>): three bf16 terms per element.
 // kc && !row_group: dst[row][3K]; !kc: the same from src[k*ld + row]; row_group > 0 (kc only): dst[3 rows][K], stacked in
 // groups of row_group source rows (64 for a k-major operand).  lo_slot: 1 for an A operand, 2 for a B operand.
 int stage_split_bf16(const float* src, bool kc, long ld, __bf16* dst, int rows, int K, int lo_slot, int row_group, hipStream_t s);

@@ -1,4 +1,4 @@
-"""CPU-only: the hand-over rule of the conv stacks (csrc/gemm.hip gemm_handoff) through t2_gemm_plan / t2_conv_handoff_plan.
+"""CPU-only: the hand-over rule of the conv stacks (csrc/gemm_dispatch.hip gemm_handoff) through t2_gemm_plan / t2_conv_handoff_plan.
 
 A conv layer may hand the GEMM layer bf16 copies it wrote itself (the previous layer's output, dz, the re-laid-out weights)
 only where the product then runs exactly as it would have on copies staged by gemm(): the plan without copies stages the

@@ -1,4 +1,4 @@
-"""CPU-only: the GEMM dispatch (csrc/gemm.hip plan_gemm) through t2_gemm_plan, which launches nothing.
+"""CPU-only: the GEMM dispatch (csrc/gemm_dispatch.hip plan_gemm) through t2_gemm_plan, which launches nothing.
 
 tests/golden/gemm_plans.jsonl holds, for about 1 500 products, what the commit BEFORE plan_gemm existed decided (its first
 line says how it was recorded): kernel, split-K factor, which operands gemm() stages, or the refusal.  Every row must come
