@@ -457,6 +457,36 @@ typedef struct t2_gemm_plan_info {
     size_t stage_bytes_a, stage_bytes_b; /* scratch the staged copies take in front of the split-K partials */
 } t2_gemm_plan_info;
 int t2_gemm_plan(const t2_gemm_args* a, const t2_gemm_plan_opts* opts, t2_gemm_plan_info* out);
+/* What a pass would do with a persistent chain (csrc/chain_plan.hip), decided on the host: launches nothing, needs no device,
+ * never asks for the per-GPU claim — the three things the library asks the device and the process come as arguments (cus =
+ * compute units, claimed = this process holds the device's persistent kernels, no_resident = T2_CHAIN_NO_RESIDENT is set).
+ * kind: 0 decoder-LSTM chain, 1 SMA / 2 LSA attention chain (dec = 1: the decode loop), 3 encoder BiLSTM chain (NS =
+ * directions, H; ws_floats = the caller's exchange space).  H is the chain's own hidden size; an attention chain's shape
+ * carries the pass's P, M and Hd.  ws_floats: the exchange space of the pass (chain_floats of the layout queries), 0 = exactly
+ * what this chain needs; the offsets of the parts a chain carves from the back of the space depend on it.  A refusal is no
+ * error: covered = 0, reason / reason_text say why, and the pass takes the per-step launches.  Parts with bytes == 0 do not
+ * exist for the chain; clear_*: what every launch zeroes first; pass_clear_bytes (forward): bytes from the head of the space
+ * that the pass zeroes once, by mode (status words only / teacher-forced / decode loop). */
+enum { T2_CHAIN_LSTM = 0, T2_CHAIN_SMA, T2_CHAIN_LSA, T2_CHAIN_ENC };                                               /* kind */
+enum { T2_CHAIN_FORWARD = 0, T2_CHAIN_BACKWARD };                                                                   /* direction */
+enum { T2_CHAIN_OK = 0, T2_CHAIN_REFUSE_SHAPE, T2_CHAIN_REFUSE_NO_INSTANCE, T2_CHAIN_REFUSE_DEVICE, T2_CHAIN_REFUSE_CLAIM,
+       T2_CHAIN_REFUSE_QUERY_PART, T2_CHAIN_REFUSE_LDS, T2_CHAIN_REFUSE_LSA_RESIDENT, T2_CHAIN_REFUSE_SHORT_MEMORY,
+       T2_CHAIN_REFUSE_LSA_SPLIT, T2_CHAIN_REFUSE_NO_SAVED_TILES, T2_CHAIN_REFUSE_WORKSPACE, T2_CHAIN_REFUSALS };    /* reason */
+enum { T2_CHAIN_PARTS = 11 };               /* status, Q, X, XD, XM, cnt, PB, PBC, DQX, CARRYX, WDT (part_name) */
+typedef struct t2_chain_shape {
+    int kind, dec, NS, B, H, E, A, P, M, Hd, F, Kc, Tin[2];
+    int saved_tiles;                         /* LSA backward: the forward chain left its tanh tile and location features */
+    size_t ws_floats;
+} t2_chain_shape;
+typedef struct t2_chain_plan_info {
+    int covered, reason; const char* reason_text;            /* static strings */
+    int instance; const char* instance_name; int grid; size_t lds_bytes;
+    int UT, RT, CS, MT, lds_Tc, lds_Tin, lds_Jp, lds_Jm, Jp[2], Jm[2];
+    size_t q_bytes, total_bytes, ws_bytes;                   /* ws_bytes: the space the offsets were laid out in */
+    size_t part_off[T2_CHAIN_PARTS], part_bytes[T2_CHAIN_PARTS]; const char* part_name[T2_CHAIN_PARTS];
+    size_t clear_off, clear_bytes, pass_clear_bytes[3];
+} t2_chain_plan_info;
+int t2_chain_plan(const t2_chain_shape* shape, int direction, int cus, int claimed, int no_resident, t2_chain_plan_info* out);
 /* The hand-over rule of the conv stacks for the product (a, opts), opts->a16 / b16 naming the copies on offer: *taken = 1
  * and *out = the plan with them iff the product without copies stages every operand a copy is offered for, and with them
  * takes every copy and keeps its kernel, split-K factor and K-chunks per split; otherwise *taken = 0 and *out = the plan

@@ -162,6 +162,24 @@ class GemmPlanInfo(C.Structure):
                 ("a_src", C.c_int), ("b_src", C.c_int), ("stage_bytes_a", C.c_size_t), ("stage_bytes_b", C.c_size_t)]
 
 
+CHAIN_PARTS = 11       # T2_CHAIN_PARTS
+CHAIN_KINDS = dict(lstm=0, sma=1, lsa=2, enc=3)
+
+
+class ChainShape(C.Structure):
+    _fields_ = [(n, C.c_int) for n in ("kind", "dec", "NS", "B", "H", "E", "A", "P", "M", "Hd", "F", "Kc")] + \
+               [("Tin", C.c_int * 2), ("saved_tiles", C.c_int), ("ws_floats", C.c_size_t)]
+
+
+class ChainPlanInfo(C.Structure):
+    _fields_ = [("covered", C.c_int), ("reason", C.c_int), ("reason_text", C.c_char_p),
+                ("instance", C.c_int), ("instance_name", C.c_char_p), ("grid", C.c_int), ("lds_bytes", C.c_size_t)] + \
+               [(n, C.c_int) for n in ("UT", "RT", "CS", "MT", "lds_Tc", "lds_Tin", "lds_Jp", "lds_Jm")] + \
+               [("Jp", C.c_int * 2), ("Jm", C.c_int * 2), ("q_bytes", C.c_size_t), ("total_bytes", C.c_size_t), ("ws_bytes", C.c_size_t),
+                ("part_off", C.c_size_t * CHAIN_PARTS), ("part_bytes", C.c_size_t * CHAIN_PARTS), ("part_name", C.c_char_p * CHAIN_PARTS),
+                ("clear_off", C.c_size_t), ("clear_bytes", C.c_size_t), ("pass_clear_bytes", C.c_size_t * 3)]
+
+
 class SoftDtwPlanInfo(C.Structure):
     _fields_ = [("threads", C.c_int), ("rows_per_thread", C.c_int), ("passes", C.c_int),
                 ("d_floats", C.c_size_t), ("r_floats", C.c_size_t), ("e_floats", C.c_size_t)]
@@ -244,7 +262,7 @@ ABI_VERSION = 4      # include/t2amd.h T2_ABI_VERSION: struct sizes below match 
 EXPORTS = ["t2_last_error", "t2_version", "t2_chain_status", "t2_chain_status_clear", "t2_debug_report_abort", "t2_debug_occupy", "t2_chain_claimed", "t2_set_precision", "t2_get_precision", "t2_gemm_counts", "t2_set_gemm_split_min_mflop", "t2_set_split_steps", "t2_get_split_steps", "t2_step_counts", "t2_set_overlap", "t2_set_chain", "t2_get_chain", "t2_set_chain_bwd", "t2_set_gemm_staging", "t2_set_gemm_fold", "t2_set_bn_fuse", "t2_get_bn_fuse", "t2_bn_fuse_counts", "t2_side_join", "t2_defer_counts", "t2_decoder_layout_query", "t2_decoder_forward", "t2_decoder_infer",
            "t2_decoder_bwd_layout_query", "t2_decoder_backward", "t2_prof_enable", "t2_prof_collect", "t2_adam_chunks", "t2_adam_step", "t2_adam_norm",
            "t2_conv_bn_forward", "t2_conv_bn_backward", "t2_embedding_forward", "t2_embedding_backward",
-           "t2_lstm_seq_forward", "t2_lstm_seq_backward", "t2_lstm_seq_chain_ws_floats", "t2_gemm_ex", "t2_prof_gemm", "t2_gemm_plan", "t2_conv_handoff_plan", "t2_colsum", "t2_mask_btc",
+           "t2_lstm_seq_forward", "t2_lstm_seq_backward", "t2_lstm_seq_chain_ws_floats", "t2_gemm_ex", "t2_prof_gemm", "t2_gemm_plan", "t2_chain_plan", "t2_conv_handoff_plan", "t2_colsum", "t2_mask_btc",
            "t2_finalize_bct", "t2_mask_bt", "t2_gemm", "t2_rng_keep_mask", "t2_rng_normal",
            "t2_softdtw_plan", "t2_softdtw_dist", "t2_softdtw_forward", "t2_softdtw_backward", "t2_softdtw_dist_backward",
            "t2_hifigan_plan", "t2_hifigan_pack", "t2_hifigan_forward", "t2_vocoder_packed_floats", "t2_vocoder_conv1d", "t2_vocoder_conv_transpose1d",
@@ -288,6 +306,7 @@ def lib() -> C.CDLL:
         L.t2_gemm_ex.argtypes = [C.POINTER(GemmArgs), C.c_void_p]
         L.t2_prof_gemm.argtypes = [C.POINTER(GemmArgs), C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_void_p]
         L.t2_gemm_plan.argtypes = [C.POINTER(GemmArgs), C.POINTER(GemmPlanOpts), C.POINTER(GemmPlanInfo)]
+        L.t2_chain_plan.argtypes = [C.POINTER(ChainShape), C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(ChainPlanInfo)]
         L.t2_conv_handoff_plan.argtypes = [C.POINTER(GemmArgs), C.POINTER(GemmPlanOpts), C.POINTER(C.c_int), C.POINTER(GemmPlanInfo)]
         L.t2_colsum.argtypes = [C.c_void_p, C.c_long, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
         L.t2_mask_btc.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_float, C.c_void_p]
@@ -564,6 +583,26 @@ def gemm_plan(args: GemmArgs, **opts) -> dict:
     check(lib().t2_gemm_plan(C.byref(args), C.byref(o), C.byref(info)))
     return dict(kernel=info.kernel, name=info.name.decode(), split=bool(info.split), splitk=info.splitk, kchunks=info.kchunks,
                 a_src=info.a_src, b_src=info.b_src, stage_bytes_a=info.stage_bytes_a, stage_bytes_b=info.stage_bytes_b)
+
+
+def chain_plan(kind: str, backward: bool = False, *, cus: int = 256, claimed: bool = True, no_resident: bool = False, **shape) -> dict:
+    """What a pass would do with a persistent chain (t2_chain_plan: nothing is launched, no device needed, no claim taken).
+    kind: 'lstm', 'sma', 'lsa' or 'enc'; shape: the fields of t2_chain_shape (defaults: the decoder's fixed sizes, two
+    streams).  Returns covered and, for a refusal, reason / reason_text; for a covered plan the instance, tiling, LDS
+    residency, grid, dynamic LDS bytes and parts = {name: (offset, bytes)} of the exchange space."""
+    z = dict(dec=0, NS=2, H=1024, E=512, A=128, P=256, M=80, Hd=1024, F=32, Kc=31, Tin=(100, 60), saved_tiles=1, ws_floats=0)
+    z.update(shape)
+    z["Tin"] = (C.c_int * 2)(*z["Tin"])
+    info = ChainPlanInfo()
+    check(lib().t2_chain_plan(C.byref(ChainShape(kind=CHAIN_KINDS[kind], **z)), int(bool(backward)), cus, int(claimed), int(no_resident), C.byref(info)))
+    if not info.covered:
+        return dict(covered=False, reason=info.reason, reason_text=info.reason_text.decode())
+    out = {n: getattr(info, n) for n in ("instance", "grid", "lds_bytes", "UT", "RT", "CS", "MT", "lds_Tc", "lds_Tin", "lds_Jp", "lds_Jm",
+                                         "q_bytes", "total_bytes", "ws_bytes")}
+    out.update(covered=True, reason=0, instance_name=info.instance_name.decode(), Jp=list(info.Jp), Jm=list(info.Jm),
+               parts={info.part_name[i].decode(): (info.part_off[i], info.part_bytes[i]) for i in range(CHAIN_PARTS) if info.part_bytes[i]},
+               clear=(info.clear_off, info.clear_bytes), pass_clear_bytes=list(info.pass_clear_bytes))
+    return out
 
 
 def conv_handoff_plan(args: GemmArgs, **opts) -> dict:

@@ -11,6 +11,7 @@
 
 #include "../../include/t2amd.h"
 #include "kernels.h"
+#include "chain_plan.h"
 #include "driver.h"
 
 static thread_local char g_err[512] = "";
@@ -307,14 +308,16 @@ int t2_lstm_seq_forward(const t2_lstm_seq_args* a, void* stream) {
     const int B = a->B, T = a->T, H = a->H;
     // every step of both directions in one persistent launch (chain_enc.hip) when the shape is covered and the caller
     // gave exchange space; otherwise one launch per step
-    if (g_chain && a->ws && a->ws_floats >= enc_chain_ws_floats(a->nstreams, B, H, 0) && enc_chain_covers(a->nstreams, B, H)) {
+    ChainPlan plan{CHAIN_REFUSE_WORKSPACE};
+    if (g_chain && a->ws && a->ws_floats) plan = plan_here(plan_enc_chain, enc_chain_shape(a->nstreams, B, H, 0, a->ws_floats * sizeof(float)));
+    if (plan.refusal == CHAIN_OK) {
         EncChainDesc d{};
         d.ND = a->nstreams; d.B = B; d.T = T; d.H = H; d.lengths = a->lengths; d.ldh = a->ldh;
         for (int s = 0; s < a->nstreams; ++s) {
             d.pre[s] = a->pre[s]; d.w_hh[s] = a->w_hh[s]; d.reverse[s] = a->reverse[s];
             d.h[s] = a->h[s]; d.c[s] = a->c[s]; d.gates[s] = a->gates[s];
         }
-        return enc_chain_fwd(d, a->ws, a->ws_floats, (hipStream_t)stream);
+        return enc_chain_fwd(d, plan, a->ws, a->ws_floats, (hipStream_t)stream);
     }
     for (int step = 0; step < T; ++step) {
         LstmStepDesc d{};
@@ -351,7 +354,9 @@ int t2_lstm_seq_backward(const t2_lstm_seq_bwd_args* a, void* stream) {
     float* gws = part + align4((size_t)ns * ks * B * H);
     T2_REQUIRE(a->ws_floats >= (size_t)(gws - a->ws), "t2_lstm_seq_backward: workspace too small");
     const size_t gws_bytes = (a->ws_floats - (size_t)(gws - a->ws)) * sizeof(float);
-    const bool chain = g_chain && g_chain_bwd && a->ws_floats >= enc_chain_ws_floats(ns, B, H, 1) && enc_chain_covers(ns, B, H);
+    ChainPlan plan{CHAIN_REFUSE_WORKSPACE};
+    if (g_chain && g_chain_bwd && a->ws_floats) plan = plan_here(plan_enc_chain, enc_chain_shape(ns, B, H, 1, a->ws_floats * sizeof(float)));
+    const bool chain = plan.refusal == CHAIN_OK;
     if (chain) {                                               // whole BPTT in one persistent launch (chain_enc.hip); its exchange space = this scratch
         EncChainBwdDesc d{};
         d.ND = ns; d.B = B; d.T = T; d.H = H; d.lddh = a->lddh;
@@ -359,7 +364,7 @@ int t2_lstm_seq_backward(const t2_lstm_seq_bwd_args* a, void* stream) {
             d.w_hh[i] = a->w_hh[i]; d.reverse[i] = a->reverse[i]; d.c[i] = a->c[i]; d.gates[i] = a->gates[i];
             d.dh[i] = a->dh[i]; d.dpre[i] = a->dpre[i];
         }
-        T2_TRY(enc_chain_bwd(d, a->ws, a->ws_floats, s));
+        T2_TRY(enc_chain_bwd(d, plan, a->ws, a->ws_floats, s));
     }
     for (int step = 0; step < (chain ? 0 : T); ++step) {      // reverse of the processing order
         LstmBwdPointDesc p{};
@@ -433,6 +438,30 @@ int t2_gemm_plan(const t2_gemm_args* a, const t2_gemm_plan_opts* o, t2_gemm_plan
     GemmPlan p;
     T2_TRY(gemm_plan(desc_of(*a, o), &p));
     *out = info_of(p);
+    return 0;
+}
+int t2_chain_plan(const t2_chain_shape* z, int direction, int cus, int claimed, int no_resident, t2_chain_plan_info* out) {
+    T2_REQUIRE(z && out && (direction == T2_CHAIN_FORWARD || direction == T2_CHAIN_BACKWARD), "t2_chain_plan: null argument or bad direction");
+    ChainShape c{};
+    c.kind = z->kind; c.dec = z->dec; c.NS = z->NS; c.B = z->B; c.H = z->H; c.E = z->E; c.A = z->A; c.P = z->P; c.M = z->M; c.Hd = z->Hd; c.F = z->F; c.Kc = z->Kc;
+    c.Tin[0] = z->Tin[0]; c.Tin[1] = z->Tin[1]; c.backward = direction; c.saved_tiles = z->saved_tiles != 0; c.ws_bytes = z->ws_floats * sizeof(float);
+    const ChainEnv env{cus, claimed != 0, no_resident != 0};
+    const ChainPlan p = z->kind == T2_CHAIN_ENC ? plan_enc_chain(c, env) : direction == T2_CHAIN_BACKWARD ? plan_chain_bwd(c, env) : plan_chain_fwd(c, env);
+    t2_chain_plan_info o{};
+    o.covered = p.refusal == CHAIN_OK; o.reason = p.refusal; o.reason_text = chain_refusal_text(p.refusal);
+    if (o.covered) {
+        // (a space too small for the plan is the executors' error, not a refusal: the layouts size it; encoder chains refuse it)
+        T2_REQUIRE(p.ws_bytes >= p.total, "t2_chain_plan: exchange space too small (%zu bytes, the chain needs %zu)", p.ws_bytes, p.total);
+        o.instance = p.instance; o.instance_name = chain_instance_name(p.instance); o.grid = p.grid; o.lds_bytes = p.lds_bytes;
+        o.UT = p.UT; o.RT = p.RT; o.CS = p.CS; o.MT = p.MT; o.lds_Tc = p.lds_Tc; o.lds_Tin = p.lds_Tin; o.lds_Jp = p.lds_Jp; o.lds_Jm = p.lds_Jm;
+        for (int s = 0; s < 2; ++s) { o.Jp[s] = p.Jp[s]; o.Jm[s] = p.Jm[s]; }
+        o.q_bytes = p.q_bytes; o.total_bytes = p.total; o.ws_bytes = p.ws_bytes;
+        static_assert(CHAIN_PARTS == T2_CHAIN_PARTS, "t2_chain_plan_info carries every part");
+        for (int i = 0; i < CHAIN_PARTS; ++i) { o.part_off[i] = p.part[i].off; o.part_bytes[i] = p.part[i].bytes; o.part_name[i] = chain_part_name(i); }
+        o.clear_off = p.clear.off; o.clear_bytes = p.clear.bytes;
+        for (int w = 0; w < 3 && z->kind != T2_CHAIN_ENC && direction == T2_CHAIN_FORWARD; ++w) o.pass_clear_bytes[w] = chain_fwd_clear_range(p.ws_bytes, (ChainWsClear)w).bytes;
+    }
+    *out = o;
     return 0;
 }
 int t2_conv_handoff_plan(const t2_gemm_args* a, const t2_gemm_plan_opts* o, int* taken, t2_gemm_plan_info* out) {

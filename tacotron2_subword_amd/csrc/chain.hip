@@ -31,6 +31,7 @@
 // and the SMA sigmoid use the hardware exp (abs. error ~1e-7), and context rows resident in LDS are bf16 copies of the
 // memory (every consumer of ctx in bf16 mode rounds it to bf16 anyway).
 #include <algorithm>
+#include <cstdlib>
 #include <type_traits>
 
 #include "chain_common.h"
@@ -61,53 +62,6 @@ namespace t2 {
 namespace {
 
 using namespace chain;
-
-struct Geo {                                // derived on both sides from the descriptor
-    int MT, NRG, NUG, nL, nA, KT; unsigned xs_bytes;
-};
-__host__ __device__ inline Geo geo_of(const ChainDesc& d, int UT, int RT) {
-    Geo g;
-    g.MT = (d.B + 31) / 32; g.NRG = (g.MT + RT - 1) / RT; g.NUG = d.H / (8 * UT);
-    g.nL = d.NS * g.NUG * g.NRG; g.nA = d.kind == CHAIN_LSTM ? 0 : d.NS * d.B * d.CS;
-    g.KT = (d.H + (d.kind == CHAIN_LSTM ? 0 : d.E) + (d.dec ? d.P : 0)) / 16;
-    g.xs_bytes = (unsigned)g.KT * g.MT * 1024u;
-    return g;
-}
-
-// LDS carve (floats).  Persistent part first, then a scratch area shared by the two phases.
-struct Lds { int ab, v, ap, cum, q, e, an, cs, pm, mem, convw, dense, loc, wpad, pa, lsp, scratch, total; };
-__host__ __device__ inline Lds lds_of(const ChainDesc& d, int UT, int RT, int Tin, int Jp, int Jm) {
-    Lds m; int o = 0;
-    auto take = [&](int n) { int r = o; o += (n + 3) & ~3; return r; };
-    const int Tp = (Tin + 3) & ~3, EC = d.kind == CHAIN_LSTM ? 0 : d.E / d.CS;
-    m.ab = take(4);
-    if (d.kind != CHAIN_LSTM) {
-        m.v = take(d.A + 4); m.ap = take(Tp + 4); m.cum = take(Tp + 4); m.q = take(d.A); m.e = take(Tp + 4); m.an = take(Tp + 4); m.cs = take(EC);
-        m.pm = take(Jp * (d.kind == CHAIN_LSA ? d.A + 1 : d.A)); m.mem = take(Jm * EC / 2);    // (LSA reads pm position-major: odd pitch)
-        // decode loop: the projection / prenet workgroups keep their weight fragments (64 KB) in this area instead of the
-        // attention rows, however short the memories are
-        if (d.dec && o - m.pm < 16384) take(16384 - (o - m.pm));
-    } else { m.v = m.ap = m.cum = m.q = m.e = m.an = m.cs = m.pm = m.mem = o; }
-    m.convw = m.dense = o;
-    // location layer weights, resident, each as a bf16 hi/lo pair: conv taps [2][F][2 KP + 8] (KP = Kc rounded up to 8, zero taps
-    // behind Kc), dense layer [2][A][F + 8]
-    if (d.kind == CHAIN_LSA) { m.convw = take(d.F * (2 * ((d.Kc + 7) & ~7) + 8)); m.dense = take(d.A * (d.F + 8)); }
-    const int lpart = NWV * 32 * PPR, lhs = RT * 32 * (UT * 8 + 4), lq = d.kind == CHAIN_LSTM ? 0 : RT * 32 * (d.A + 4);
-    const int lphase = (lpart > lq ? lpart : lq) + lhs;
-    int aphase = d.kind == CHAIN_LSTM ? 0 : 16 * d.A + NWV * EC;
-    m.loc = m.wpad = m.pa = m.lsp = 0;
-    if (d.kind == CHAIN_LSA) {                               // per-step location features behind the reduction buffers
-        const int TwP = (Tin + d.Kc - 1 + 8 + 3) & ~3;
-        m.loc = aphase;                                           // (the fp32 copy of the features is gone: the bf16 pair below is what is read)
-        m.wpad = aphase; aphase += 2 * TwP;
-        m.pa = aphase; aphase += (d.A / 32) * ((Tin + 3) & ~3);   // energy partials of the channel tiles [A/32][Tp]
-        m.lsp = aphase; aphase += (Tin * (d.F + 8) + 3) & ~3;     // the features again as a bf16 hi/lo pair [2][Tin][F + 8]
-    }
-    m.scratch = take(lphase > aphase ? lphase : aphase);
-    m.loc += m.scratch; m.wpad += m.scratch; m.pa += m.scratch; m.lsp += m.scratch;
-    m.total = o;
-    return m;
-}
 
 template <int UT, int RT, int KH, int KC, int KIND, int KPN = 0>
 __global__ __launch_bounds__(NTH) void chain_fwd_kernel(ChainDesc d) {
@@ -1128,122 +1082,38 @@ int chain_device_cus() {
     return c;
 }
 
-// Exchange space of a forward pass (chain_fwd_ws_floats), every part sized for the largest tiling chain_plan can choose:
-//   [status words | query partials | fragments of the attention chain ...... fragments of the decoder-LSTM chain | mel fragments | counters]
-// The attention chain's parts are carved from the front, the decoder-LSTM chain's (decode loop: dec_h) from the back, so that each
-// chain finds its own from its descriptor; the mel fragments and the arrival counters are the decode loop's.
-static constexpr size_t kStatusBytes = 256;                                        // ChainStatus words (kernels.h)
-static constexpr size_t kXmBytes = 16 * 1024;                                      // mel fragments [2][8][1 KB]
-static constexpr size_t kCntBytes = (size_t)16 * CNT_STRIDE * sizeof(unsigned);    // counters 0-3 (h / ctx of each stream), 8 (dec_h), 9 (mel), 10-11 (prenets)
-// fragment-ordered operands of a K-wide product: [parity][stream][k tile of 16][row tile of 32][1 KB]
-static size_t x_part_bytes(int NS, int B, int K) { return (size_t)2 * NS * (K / 16) * ((B + 31) / 32) * 1024; }
-// query partials: one 32-row tile per 32 batch rows, one unit group per 8 hidden units
-static size_t q_part_bytes(int NS, int B, int H, int A) { return (size_t)NS * ((B + 31) / 32) * 32 * (H / 8) * A * sizeof(float); }
-// query partials of a tiling: [stream][row group][unit group][32 RT rows][A]
-static size_t q_bytes_of(const ChainDesc& d, const Geo& g) { return (size_t)d.NS * g.NRG * g.NUG * 32 * d.RT * d.A * sizeof(float); }
-
-size_t chain_fwd_ws_floats(int NS, int B, int Ha, int E, int P, int Hd, int A) {
-    return (kStatusBytes + q_part_bytes(NS, B, Ha, A) + x_part_bytes(NS, B, Ha + E + P) + x_part_bytes(1, B, Hd) + kXmBytes + kCntBytes) / sizeof(float);
+// The one place that asks the device and the process what a plan needs to know (chain_plan.h)
+ChainEnv chain_env(bool take_claim) {
+    return ChainEnv{chain_device_cus(), !take_claim || chain_device_claim(), getenv("T2_CHAIN_NO_RESIDENT") != nullptr};
 }
 
 int chain_fwd_ws_clear(float* ws, size_t ws_floats, ChainWsClear what, hipStream_t s) {
-    const size_t bytes = ws_floats * sizeof(float);
-    T2_REQUIRE(ws && bytes >= kStatusBytes + kXmBytes + kCntBytes, "chain_fwd_ws_clear: exchange space too small");
-    T2_CHECK_HIP(hipMemsetAsync(ws, 0, what == CHAIN_WS_STATUS ? kStatusBytes : what == CHAIN_WS_TEACHER ? bytes - kXmBytes - kCntBytes : bytes, s));
+    const ChainPart c = chain_fwd_clear_range(ws_floats * sizeof(float), what);
+    T2_REQUIRE(ws && c.bytes, "chain_fwd_ws_clear: exchange space too small");
+    T2_CHECK_HIP(hipMemsetAsync(reinterpret_cast<unsigned char*>(ws) + c.off, 0, c.bytes, s));
     return 0;
 }
 
-// Picks the tiling for a shape; returns false when the persistent kernel does not cover it.
-bool chain_plan(ChainDesc& d) {
-    if (d.H != 1024 || d.B < 1 || d.B > 128) return false;
-    if (d.kind != CHAIN_LSTM && (d.E != 512 || d.A != 128 || d.NS < 1 || d.NS > 2)) return false;
-    if (d.kind == CHAIN_LSA && (d.F + 1 > 64 || d.F % 16 != 0 || d.A % 32 != 0)) return false;
-    const int MT = (d.B + 31) / 32;
-    if (d.dec && (MT != 1 || d.NS != 2 || d.kind == CHAIN_LSTM || d.P != 256 || d.Hd != 1024 || d.M + 1 > 96 || d.M % 8 != 0)) return false;
-    // decoder-LSTM chain: one row tile per item while the items still fit the chip (B <= 64: 128 unit groups x 2 row groups = 256
-    // workgroups; with both tiles in one item half the CUs idled and every step did twice the work per workgroup)
-    if (d.kind == CHAIN_LSTM) { d.UT = 1; d.RT = (d.H / 8) * MT <= 256 ? 1 : 2; d.CS = 1; d.NS = 1; }
-    else {
-        d.RT = MT <= 2 ? 1 : 2;
-        d.UT = (d.NS * (d.H / 8) * ((MT + d.RT - 1) / d.RT) <= 256) ? 1 : 2;
-        d.CS = (!d.dec && d.NS * d.B * 4 <= 256) ? 4 : d.NS * d.B * 2 <= 256 ? 2 : 1;      // (decode: 2, see the D / P items)
-    }
-    const Geo g = geo_of(d, d.UT, d.RT);
-    if (g.nL > 256 || g.nA > 256) return false;
-    if (chain_device_cus() < 256 || !chain_device_claim()) return false;
-    // (one stream at 65-96 rows: two row groups of two row tiles pad the query partials beyond their part of the exchange space)
-    if (d.kind != CHAIN_LSTM && q_bytes_of(d, g) > q_part_bytes(d.NS, d.B, d.H, d.A)) return false;
-    // LDS residency: processed-memory rows first, then (bf16) memory rows, in what the largest stream leaves free
-    const int budget = (160 * 1024 - 256) / 4;
-    int tmax = 4;
-    for (int s = 0; s < d.NS && d.kind != CHAIN_LSTM; ++s) tmax = std::max(tmax, d.st[s].Tin);
-    d.lds_Tin = tmax; d.lds_Jp = 0; d.lds_Jm = 0;
-    const int fixed = lds_of(d, d.UT, d.RT, tmax, 0, 0).total;
-    if (fixed > budget) return false;
-    if (d.kind != CHAIN_LSTM) {
-        const int EC = d.E / d.CS;
-        int left = budget - fixed + (d.dec ? 16384 : 0);                        // (dec: `fixed` holds the 64 KB pad the rows will take the place of)
-        const int pmp = d.kind == CHAIN_LSA ? d.A + 1 : d.A;
-        d.lds_Jp = std::min(tmax, left / pmp); left -= d.lds_Jp * pmp;
-        if (d.kind == CHAIN_LSA && (d.lds_Jp < tmax || (d.dec && g.nA > 128))) return false;   // LSA energies read pm from LDS only
-        d.lds_Jm = std::min(tmax, left / (EC / 2)) & ~1;
-        for (int s = 0; s < d.NS; ++s) { d.Jp[s] = std::min(d.st[s].Tin, d.lds_Jp); d.Jm[s] = std::min(d.st[s].Tin, d.lds_Jm); }
-        if (getenv("T2_CHAIN_NO_RESIDENT")) { if (d.kind != CHAIN_LSA) d.Jp[0] = d.Jp[1] = 0; d.Jm[0] = d.Jm[1] = 0; }
-        if (lds_of(d, d.UT, d.RT, tmax, d.lds_Jp, d.lds_Jm).total > budget) return false;
-    }
-    return true;
-}
-
+// instance -> launcher, in the order of ChainInstance (chain_plan.h): a covered forward plan names an entry by construction
+using FwdLauncher = int (*)(const ChainDesc&, const ChainPlan&, float*, hipStream_t);
 template <int UT, int RT, int KC, int KIND, int KPN = 0>
-static int chain_launch(const ChainDesc& d, hipStream_t s) {
-    const Lds m = lds_of(d, UT, RT, d.lds_Tin, d.lds_Jp, d.lds_Jm);
-    const size_t smem = (size_t)m.total * sizeof(float);
-    auto kernel = chain_fwd_kernel<UT, RT, 8, KC, KIND, KPN>;
-    const Geo g = geo_of(d, UT, RT);
-    const int grid = KPN > 0 ? 256 : std::max(g.nL, g.nA);
-    T2_TRY_RC(persistent_prepare(kernel, grid, smem));
-    if (KPN > 0) T2_CHECK_HIP(hipMemsetAsync(d.cnt, 0, kCntBytes, s));         // (the decode loop's counters count the steps of one launch)
-    hipLaunchKernelGGL(kernel, dim3(grid), dim3(NTH), smem, s, d);
-    T2_LAUNCH_CHECK();
-    return 0;
+static int launch_fwd(const ChainDesc& d, const ChainPlan& p, float* ws, hipStream_t s) {
+    return launch_planned(chain_fwd_kernel<UT, RT, 8, KC, KIND, KPN>, d, p, ws, s);
 }
+static constexpr FwdLauncher kFwdLaunchers[] = {
+    launch_fwd<1, 1, 0, CHAIN_LSTM>, launch_fwd<1, 2, 0, CHAIN_LSTM>,
+    launch_fwd<1, 1, 4, CHAIN_SMA>, launch_fwd<2, 1, 4, CHAIN_SMA>, launch_fwd<2, 2, 4, CHAIN_SMA>,
+    launch_fwd<1, 1, 4, CHAIN_LSA>, launch_fwd<2, 1, 4, CHAIN_LSA>, launch_fwd<2, 2, 4, CHAIN_LSA>,
+    launch_fwd<1, 1, 4, CHAIN_SMA, 2>, launch_fwd<1, 1, 4, CHAIN_LSA, 2>,
+};
+static_assert(sizeof(kFwdLaunchers) / sizeof(kFwdLaunchers[0]) == CI_FWD_COUNT, "one launcher per forward instance");
 
-int chain_fwd(ChainDesc d, float* ws, size_t ws_floats, hipStream_t s) {
+int chain_fwd(ChainDesc d, const ChainPlan& p, float* ws, size_t ws_floats, hipStream_t s) {
     T2_REQUIRE(d.t1 > d.t0 && d.t0 >= 0, "chain_fwd: bad step range [%d,%d)", d.t0, d.t1);
-    const size_t bytes = ws_floats * sizeof(float);
-    T2_REQUIRE(ws && d.err && bytes >= kStatusBytes + kXmBytes + kCntBytes, "chain_fwd: exchange space or status word missing");
-    unsigned char* const front = reinterpret_cast<unsigned char*>(ws) + kStatusBytes;
-    unsigned char* const back = reinterpret_cast<unsigned char*>(ws) + bytes - kXmBytes - kCntBytes;
-    if (d.kind == CHAIN_LSTM) {
-        d.X = back - x_part_bytes(1, d.B, d.H);
-        T2_REQUIRE(d.X >= front, "chain_fwd: exchange space too small");
-        if (d.RT == 1) return chain_launch<1, 1, 0, CHAIN_LSTM>(d, s);
-        return chain_launch<1, 2, 0, CHAIN_LSTM>(d, s);
-    }
-    T2_REQUIRE(d.kind == CHAIN_SMA || d.kind == CHAIN_LSA, "chain_fwd: attention kind %d not covered", d.kind);
-    // (the attention chain's descriptor carries the pass's whole shape, P and Hd included: a space of at least the size
-    //  chain_fwd_ws_floats gives it keeps the parts carved below clear of the decoder-LSTM chain's part at the back)
-    T2_REQUIRE(bytes >= chain_fwd_ws_floats(d.NS, d.B, d.H, d.E, d.P, d.Hd, d.A) * sizeof(float), "chain_fwd: exchange space too small");
-    const Geo g = geo_of(d, d.UT, d.RT);
-    d.Q = reinterpret_cast<float*>(front); d.q_bytes = (unsigned)q_bytes_of(d, g);
-    d.X = front + q_part_bytes(d.NS, d.B, d.H, d.A);
-    T2_REQUIRE(d.q_bytes <= q_part_bytes(d.NS, d.B, d.H, d.A) && (size_t)2 * d.NS * g.xs_bytes <= x_part_bytes(d.NS, d.B, d.H + d.E + d.P),
-               "chain_fwd: tiling UT=%d RT=%d outgrows its exchange buffers", d.UT, d.RT);
-    if (d.dec) {
-        d.XD = back - x_part_bytes(1, d.B, d.Hd); d.XM = back; d.cnt = reinterpret_cast<unsigned*>(back + kXmBytes);
-        T2_REQUIRE(d.UT == 1 && d.RT == 1, "chain_fwd: the decode loop needs one row tile");
-        return d.kind == CHAIN_LSA ? chain_launch<1, 1, 4, CHAIN_LSA, 2>(d, s) : chain_launch<1, 1, 4, CHAIN_SMA, 2>(d, s);
-    }
-    if (d.kind == CHAIN_LSA) {
-        if (d.UT == 1 && d.RT == 1) return chain_launch<1, 1, 4, CHAIN_LSA>(d, s);
-        if (d.UT == 2 && d.RT == 1) return chain_launch<2, 1, 4, CHAIN_LSA>(d, s);
-        if (d.UT == 2 && d.RT == 2) return chain_launch<2, 2, 4, CHAIN_LSA>(d, s);
-    }
-    if (d.UT == 1 && d.RT == 1) return chain_launch<1, 1, 4, CHAIN_SMA>(d, s);
-    if (d.UT == 2 && d.RT == 1) return chain_launch<2, 1, 4, CHAIN_SMA>(d, s);
-    if (d.UT == 2 && d.RT == 2) return chain_launch<2, 2, 4, CHAIN_SMA>(d, s);
-    T2_REQUIRE(false, "chain_fwd: tiling UT=%d RT=%d not instantiated", d.UT, d.RT);
-    return -1;
+    T2_REQUIRE_PLAN(p, CI_FWD_FIRST, CI_FWD_COUNT, ws, ws_floats, "chain_fwd");
+    T2_REQUIRE(d.err, "chain_fwd: status word missing");
+    apply(p, ws, &d);
+    return kFwdLaunchers[p.instance - CI_FWD_FIRST](d, p, ws, s);
 }
 
 }  // namespace t2

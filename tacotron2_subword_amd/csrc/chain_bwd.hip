@@ -45,10 +45,6 @@ namespace {
 
 using namespace chain;
 
-constexpr int GNC = 32;          // output columns of a G item
-constexpr int GKP = 8;           // K parts
-constexpr int PU = 16;           // hidden units of a P item
-
 template <int MT>
 __global__ __launch_bounds__(NTH) void chain_bwd_lstm_kernel(ChainBwdDesc d) {
     const int wg = blockIdx.x, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, r = lane & 31, hk = lane >> 5;
@@ -274,35 +270,6 @@ __global__ __launch_bounds__(NTH) void chain_bwd_lstm_kernel(ChainBwdDesc d) {
 // write-through store per split and step); both areas are cleared per launch.  Everything that does not need step t's
 // context gradient runs in front of the poll for it (halo rows, carried gradients, d(Wc) of step t+1, the saved tile's loads).
 // ---------------------------------------------------------------------------------------------------------------
-constexpr int ANC = 64;          // output columns of a G item (attention chain)
-constexpr int AKP = 4;           // K parts = the four gate blocks
-
-struct BwdLds { int ab, v, q, dctx, g, de, ps, ap, carry, dva, dqo, wq, pm, dpm, mem, cc, convw, dloc, wpad, ut, loc, red, TwP, scratch, total; };
-__host__ __device__ inline BwdLds bwd_lds_of(int A, int E, int Tc, int MT, int kind = CHAIN_SMA, int F = 0, int Kc = 1) {
-    BwdLds m; int o = 0;
-    auto take = [&](int n) { int r = o; o += (n + 3) & ~3; return r; };
-    const bool lsa = kind == CHAIN_LSA;
-    const int pad = (Kc - 1) / 2;
-    m.ab = take(4); m.v = take(A); m.q = take(A); m.dctx = take(E);
-    m.g = take(Tc + 8); m.de = take(Tc + 8); m.ps = take(Tc + 8); m.ap = take(Tc + 8); m.carry = take(Tc + 8);
-    m.dva = take(A); m.dqo = take(A);
-    m.wq = take(PU * (A + 8));                                 // Wq slice of the P item as a bf16 hi/lo pair [2][PU][A + 8]
-    m.pm = take(lsa ? 0 : Tc * A); m.dpm = take(Tc * A); m.mem = take((Tc + 1) * E / 2);
-    // LSA: carried gradient on the cumulative weights, conv weights, dloc of the last step with `pad` halo rows on both
-    // sides (pitch F + 1, column F stays zero), [w_prev; cum_prev] of two steps (ping-pong) with the same halos
-    m.TwP = (Tc + 2 * pad + 8 + 3) & ~3;                    // (+8: the conv product's K is padded to a multiple of 16 with zero weights)
-    m.cc = take(lsa ? Tc + 8 : 0); m.convw = take(lsa ? F * ((2 * Kc + 15) & ~15) : 0); m.dloc = take(lsa ? (Tc + 2 * pad) * (F + 1) : 0);
-    m.wpad = take(lsa ? 4 * m.TwP : 0);
-    // scratch shared by the phases; LSA's A phase: tanh / dpre tile [Tc][A + 4], location features [Tc][F + 1], reduction rows
-    // (the tile's room first holds Q = dloc . Wc^T, [Tc + 2 pad][65], of the carried-gradient step)
-    const int nut = Tc * (A + 4), nq = (Tc + 2 * pad) * 65;
-    m.ut = 0; m.loc = ((nut > nq ? nut : nq) + 3) & ~3; m.red = m.loc + ((Tc * (F + 1) + 3) & ~3);
-    const int sg = NWV * 32 * PPR, sp = 32 * (A + 4) + 4 * 32 * (PU + 4) + 4 * 32 * (PU + 1), sa = lsa ? m.red + 2 * NWV * A : 2 * 32 * A;
-    m.scratch = take(sg > sp ? (sg > sa ? sg : sa) : (sp > sa ? sp : sa));
-    m.total = o;
-    return m;
-}
-
 template <int MT, int KIND>
 __global__ __launch_bounds__(NTH) void chain_bwd_att_kernel(ChainBwdDesc d) {
     const int wg = blockIdx.x, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, r = lane & 31, hk = lane >> 5;
@@ -1202,106 +1169,29 @@ __global__ __launch_bounds__(NTH) void chain_bwd_att_kernel(ChainBwdDesc d) {
     }
 }
 
-// Exchange space of the backward pass (chain_bwd_ws_floats): the attention chain's parts from the front — dg fragments, h and ctx
-// K-split partials, dq partials, boundary carries (all of them tagged), then (LSA) the bf16 Wd^T copies — and the decoder-LSTM
-// chain's from the back — dg fragments, K-split partials — so that each chain finds its own from its descriptor.
-size_t al256(size_t n) { return (n + 255) & ~(size_t)255; }
-struct AttParts { size_t x, pbh, pbc, dqx, carry, wdt; };
-AttParts att_parts(int kind, int NS, int B, int H, int E, int A, int F, int Kc) {
-    const size_t MT = (B + 31) / 32;
-    AttParts p;
-    p.x = (size_t)2 * NS * (4 * H / 16) * MT * 1024;
-    p.pbh = (size_t)2 * NS * AKP * (H / PU) * MT * 32 * PU * sizeof(float);
-    p.pbc = al256((size_t)2 * NS * AKP * B * E * sizeof(float));
-    p.dqx = al256((size_t)NS * 2 * B * A * sizeof(float));
-    // SMA: one carry per (parity, stream, item); LSA: halo rows of dloc and softmax-dot slots (rsK in chain_bwd_att_kernel)
-    p.carry = al256(kind == CHAIN_LSA ? (size_t)(((Kc - 1) / 2) * F + 2) * 2 * NS * B * 2 * sizeof(float) : (size_t)2 * NS * B * sizeof(float));
-    p.wdt = kind == CHAIN_LSA ? al256((size_t)NS * F * A * sizeof(__bf16)) : 0;
-    return p;
-}
-size_t lstm_x_bytes(int B, int H) { return (size_t)2 * (4 * H / 16) * ((B + 31) / 32) * 1024; }                           // [2][4H/16][MT][1 KB]
-size_t lstm_pb_bytes(int B, int H) { return (size_t)2 * GKP * (H / PU) * ((B + 31) / 32) * 32 * PU * sizeof(float); }     // [2][GKP][H/PU][MT][32][PU]
-
 }  // namespace
 
-size_t chain_bwd_ws_floats(int kind, int NS, int B, int Ha, int E, int A, int F, int Kc, int Hd) {
-    const AttParts p = att_parts(kind, NS, B, Ha, E, A, F, Kc);
-    return (p.x + p.pbh + p.pbc + p.dqx + p.carry + p.wdt + lstm_x_bytes(B, Hd) + lstm_pb_bytes(B, Hd)) / sizeof(float);
-}
+// instance -> launcher, in the order of ChainInstance (chain_plan.h)
+using BwdLauncher = int (*)(const ChainBwdDesc&, const ChainPlan&, float*, hipStream_t);
+template <int MT>
+static int launch_bwd_lstm(const ChainBwdDesc& d, const ChainPlan& p, float* ws, hipStream_t s) { return launch_planned(chain_bwd_lstm_kernel<MT>, d, p, ws, s); }
+template <int MT, int KIND>
+static int launch_bwd_att(const ChainBwdDesc& d, const ChainPlan& p, float* ws, hipStream_t s) { return launch_planned(chain_bwd_att_kernel<MT, KIND>, d, p, ws, s); }
+static constexpr BwdLauncher kBwdLaunchers[] = {
+    launch_bwd_lstm<1>, launch_bwd_lstm<2>, launch_bwd_att<1, CHAIN_SMA>, launch_bwd_att<2, CHAIN_SMA>, launch_bwd_att<1, CHAIN_LSA>, launch_bwd_att<2, CHAIN_LSA>,
+};
+static_assert(sizeof(kBwdLaunchers) / sizeof(kBwdLaunchers[0]) == CI_BWD_COUNT, "one launcher per backward instance");
 
-bool chain_bwd_plan(ChainBwdDesc& d) {
-    if (d.H != 1024 || d.B < 1 || d.B > 64) return false;
-    if (chain_device_cus() < 256 || !chain_device_claim()) return false;
-    if (d.kind == CHAIN_LSTM) return true;
-    if ((d.kind != CHAIN_SMA && d.kind != CHAIN_LSA) || d.E != 512 || d.A != 128 || d.NS < 1 || d.NS > 2) return false;
-    const bool lsa = d.kind == CHAIN_LSA;
-    if (lsa && (d.F != 32 || d.Kc < 3 || d.Kc > 31 || d.Kc % 2 == 0)) return false;     // (F = 32: the reference's attention_location_n_filters)
-    const int pad = lsa ? (d.Kc - 1) / 2 : 0;
-    int tc = 0;
-    for (int s = 0; s < d.NS; ++s) {
-        const int Tin = d.st[s].Tin, chunk = (((Tin + 1) / 2) + 3) & ~3;
-        if (Tin < 16) return false;                                  // (two position splits per item, as the launch path at these sizes)
-        // LSA: both splits hold at least the `pad` rows they hand to each other; one [positions x A] tile row pair per wave
-        if (lsa && (Tin - chunk < pad || chunk < pad || chunk > 64)) return false;
-        if (lsa && (!d.st[s].usave || !d.st[s].locsave)) return false;   // the forward chain's tanh tile / location features
-        tc = std::max(tc, chunk);
-    }
-    d.lds_Tc = tc;
-    return (size_t)bwd_lds_of(d.A, d.E, tc, (d.B + 31) / 32, d.kind, d.F, d.Kc).total * sizeof(float) <= 160 * 1024;
-}
-
-int chain_bwd(ChainBwdDesc d, float* ws, size_t ws_floats, hipStream_t s) {
+int chain_bwd(ChainBwdDesc d, const ChainPlan& p, float* ws, size_t ws_floats, hipStream_t s) {
     T2_REQUIRE(d.t1 > d.t0 && d.t0 >= 0, "chain_bwd: bad step range [%d,%d)", d.t0, d.t1);
-    T2_REQUIRE(ws && d.err, "chain_bwd: exchange space or status word missing");
-    const int MT = (d.B + 31) / 32;
-    unsigned char* const base = reinterpret_cast<unsigned char*>(ws);
-    const size_t bytes = ws_floats * sizeof(float);
-    if (d.kind == CHAIN_SMA || d.kind == CHAIN_LSA) {
-        T2_REQUIRE(d.t0 == 0 && d.t1 == d.T, "chain_bwd: the attention chain runs its whole step range in one launch");
-        const AttParts p = att_parts(d.kind, d.NS, d.B, d.H, d.E, d.A, d.F, d.Kc);
-        const size_t tagged = p.x + p.pbh + p.pbc + p.dqx + p.carry;
-        T2_REQUIRE(tagged + p.wdt <= bytes, "chain_bwd: exchange space too small");
-        d.X = base; d.PB = d.X + p.x; d.PBC = d.PB + p.pbh;
-        d.DQX = reinterpret_cast<float*>(d.PBC + p.pbc); d.CARRYX = reinterpret_cast<float*>(d.PBC + p.pbc + p.dqx);
-        d.pb_bytes = (unsigned)p.pbh; d.pbc_bytes = (unsigned)((size_t)2 * d.NS * AKP * d.B * d.E * sizeof(float));
-        T2_CHECK_HIP(hipMemsetAsync(base, 0, tagged, s));           // every buffer but Wd^T carries step tags (tag 0 = not written yet)
-        if (d.kind == CHAIN_LSA)
-            for (int i = 0; i < d.NS; ++i) {                            // loc_dense [A][F] -> bf16 [F][A]
-                __bf16* wdt = reinterpret_cast<__bf16*>(base + tagged) + (size_t)i * d.F * d.A;
-                T2_TRY_RC(cast_transpose_bf16(d.st[i].loc_dense, d.F, wdt, d.A, d.A, d.F, s));
-                d.st[i].wdt16 = wdt;
-            }
-        const size_t smem = (size_t)bwd_lds_of(d.A, d.E, d.lds_Tc, MT, d.kind, d.F, d.Kc).total * sizeof(float);
-        const int grid = std::max(std::max(d.NS * (d.E + d.H) / ANC * AKP, d.NS * (d.H / PU) * MT), d.NS * d.B * 2);
-        auto launch = [&](auto kernel) -> int {
-            T2_TRY_RC(persistent_prepare(kernel, grid, smem));
-            hipLaunchKernelGGL(kernel, dim3(grid), dim3(NTH), smem, s, d);
-            return 0;
-        };
-        int rc;
-        if (d.kind == CHAIN_SMA) rc = MT == 1 ? launch(chain_bwd_att_kernel<1, CHAIN_SMA>) : launch(chain_bwd_att_kernel<2, CHAIN_SMA>);
-        else rc = MT == 1 ? launch(chain_bwd_att_kernel<1, CHAIN_LSA>) : launch(chain_bwd_att_kernel<2, CHAIN_LSA>);
-        if (rc) return rc;
-        T2_LAUNCH_CHECK();
-        return 0;
-    }
-    T2_REQUIRE(d.kind == CHAIN_LSTM, "chain_bwd: kind %d not covered", d.kind);
-    T2_REQUIRE(d.t1 == d.T, "chain_bwd: the decoder-LSTM chain runs its whole step range in one launch (tagged hand-offs count steps from the launch)");
-    const size_t xb = lstm_x_bytes(d.B, d.H), pb = lstm_pb_bytes(d.B, d.H);
-    T2_REQUIRE(xb + pb <= bytes, "chain_bwd: exchange space too small");
-    d.X = base + bytes - xb - pb; d.PB = d.X + xb; d.pb_bytes = (unsigned)pb;
-    T2_CHECK_HIP(hipMemsetAsync(d.X, 0, xb + pb, s));                 // tagged hand-offs: tag 0 = invalid for the first two steps
-    const size_t smem = (size_t)(4 + NWV * MT * 32 * PPR) * sizeof(float);
-    const int grid = (d.H / GNC) * GKP;
-    if (MT == 1) {
-        T2_TRY_RC(persistent_prepare(chain_bwd_lstm_kernel<1>, grid, smem));
-        hipLaunchKernelGGL(chain_bwd_lstm_kernel<1>, dim3(grid), dim3(NTH), smem, s, d);
-    } else {
-        T2_TRY_RC(persistent_prepare(chain_bwd_lstm_kernel<2>, grid, smem));
-        hipLaunchKernelGGL(chain_bwd_lstm_kernel<2>, dim3(grid), dim3(NTH), smem, s, d);
-    }
-    T2_LAUNCH_CHECK();
-    return 0;
+    T2_REQUIRE_PLAN(p, CI_BWD_FIRST, CI_BWD_COUNT, ws, ws_floats, "chain_bwd");
+    T2_REQUIRE(d.err, "chain_bwd: status word missing");
+    // (tagged hand-offs count steps from the launch)
+    T2_REQUIRE(d.t1 == d.T && (d.kind == CHAIN_LSTM || d.t0 == 0), "chain_bwd: a backward chain runs its whole step range in one launch");
+    apply(p, ws, &d);
+    for (int i = 0; i < d.NS && d.kind == CHAIN_LSA; ++i)                // loc_dense [A][F] -> bf16 [F][A]
+        T2_TRY_RC(cast_transpose_bf16(d.st[i].loc_dense, d.F, const_cast<__bf16*>(d.st[i].wdt16), d.A, d.A, d.F, s));
+    return kBwdLaunchers[p.instance - CI_BWD_FIRST](d, p, ws, s);
 }
 
 }  // namespace t2

@@ -4,7 +4,8 @@
 // barrier, one lane signals with an agent-scope atomic; one wave polls with relaxed agent-scope loads, the other waves load
 // behind the workgroup barrier, every payload load sc1).  Step tags, in the teacher-forced decoder chains: below.
 #pragma once
-#include "kernels.h"
+#include "chain_plan.h"
+#include "chain_shape.h"
 
 namespace t2 {
 namespace chain {
@@ -14,12 +15,7 @@ typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 #define T2_RLX_AGENT __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT
 
-constexpr int NTH = 512, NWV = 8;
 constexpr int SC1 = 16;                    // buffer-instruction cache policy bit: sc1 (agent scope, bypass L1 / write through)
-constexpr int PPR = 40;                    // LDS pitch of a 32-wide partial tile row (conflict-free fixed-order reads)
-constexpr int NSH = kCntShards;            // shards of an arrival counter
-constexpr int CNT_LINE = 32;               // unsigned words per 128-byte line
-constexpr int CNT_STRIDE = NSH * CNT_LINE; // words per (sharded) arrival counter
 constexpr unsigned long long SPIN_TICKS = 100000000ull;   // 1 s of the 100 MHz realtime counter: every spin is bounded
 
 // Abort reports go to two places: the status word of the pass (in its workspace: which chain of which pass) and the
@@ -110,5 +106,20 @@ static int persistent_prepare(K kernel, int grid, size_t smem) {
                "persistent launch refused: %d workgroups cannot be co-resident (%d per CU x %d CUs with %zu bytes of LDS)", grid, per_cu, cus, smem);
     return 0;
 }
+
+// One executor for every chain: the plan's memset, then the plan's instance (`kernel`, from the file's launcher table) on
+// the plan's grid with the plan's dynamic LDS.  `d` has the plan applied.
+template <class K, class D>
+static int launch_planned(K kernel, const D& d, const ChainPlan& p, float* ws, hipStream_t s) {
+    T2_TRY_RC(persistent_prepare(kernel, p.grid, p.lds_bytes));
+    if (p.clear.bytes) T2_CHECK_HIP(hipMemsetAsync(reinterpret_cast<unsigned char*>(ws) + p.clear.off, 0, p.clear.bytes, s));
+    hipLaunchKernelGGL(kernel, dim3(p.grid), dim3(chain::NTH), p.lds_bytes, s, d);
+    T2_LAUNCH_CHECK();
+    return 0;
+}
+// what every executor checks first: a covered plan of its own file, laid out in the space it is given
+#define T2_REQUIRE_PLAN(p, first, count, ws, ws_floats, who)                                                                          \
+    T2_REQUIRE((p).refusal == CHAIN_OK && (p).instance >= (first) && (p).instance < (first) + (count), who ": no plan for this launch"); \
+    T2_REQUIRE((ws) && (ws_floats) * sizeof(float) == (p).ws_bytes && (p).ws_bytes >= (p).total, who ": exchange space too small or not the planned one")
 
 }  // namespace t2

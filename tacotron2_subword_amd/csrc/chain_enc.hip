@@ -30,11 +30,6 @@ namespace {
 
 using namespace chain;
 
-constexpr int EKW = 16;                    // K elements per lane: H = 16 * EKW = 256
-constexpr int EH = 16 * EKW;
-constexpr int EGKP = 4;                    // backward: K parts of the dx product = the four gate blocks
-constexpr int EPU = 16;                    // backward: hidden units of a P item
-
 __device__ __forceinline__ float acc_sigmoid(float x) { return 1.0f / (1.0f + expf(-x)); }
 
 // ------------------------------------------------------------------------------------------------------------ forward
@@ -284,51 +279,18 @@ __global__ __launch_bounds__(NTH) void enc_chain_bwd_kernel(EncChainBwdDesc d) {
 // ---------------------------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------------------------
-bool enc_chain_covers(int ND, int B, int H) {
-    return ND >= 1 && ND <= 2 && H == EH && B >= 1 && B <= 128 && chain_device_cus() >= 256 && chain_device_claim();
+int enc_chain_fwd(EncChainDesc d, const ChainPlan& p, float* ws, size_t ws_floats, hipStream_t s) {
+    T2_REQUIRE_PLAN(p, CI_ENC_FWD, 1, ws, ws_floats, "enc_chain_fwd");
+    T2_REQUIRE(d.T >= 1, "enc_chain_fwd: no steps");
+    apply(p, ws, &d);
+    return launch_planned(enc_chain_fwd_kernel, d, p, ws, s);
 }
 
-// floats of exchange space: [status 64 | counters | h or (dg + partials)]
-size_t enc_chain_ws_floats(int ND, int B, int H, int backward) {
-    const size_t NRG = (B + 31) / 32, Bp = NRG * 32;
-    const size_t cnt = (size_t)ND * NRG * (backward ? 1 + H / 32 : 1) * CNT_STRIDE;
-    const size_t x = backward ? (size_t)2 * ND * (4 * H * Bp + EGKP * H * Bp) : (size_t)2 * ND * H * Bp;
-    return 64 + cnt + x + 64;
-}
-
-int enc_chain_fwd(EncChainDesc d, float* ws, size_t ws_floats, hipStream_t s) {
-    T2_REQUIRE(enc_chain_covers(d.ND, d.B, d.H) && d.T >= 1, "enc_chain_fwd: shape not covered (ND=%d B=%d H=%d)", d.ND, d.B, d.H);
-    T2_REQUIRE(ws && ws_floats >= enc_chain_ws_floats(d.ND, d.B, d.H, 0), "enc_chain_fwd: exchange space too small");
-    const int NRG = (d.B + 31) / 32;
-    d.err = reinterpret_cast<unsigned*>(ws);
-    d.cnt = reinterpret_cast<unsigned*>(ws + 64);
-    d.X = ws + 64 + (size_t)d.ND * NRG * CNT_STRIDE;
-    T2_CHECK_HIP(hipMemsetAsync(ws, 0, (64 + (size_t)d.ND * NRG * CNT_STRIDE) * sizeof(float), s));
-    const int grid = d.ND * (EH / 8) * NRG;
-    const size_t smem = (size_t)(4 + NWV * 32 * PPR + 32 * 8) * sizeof(float);
-    T2_TRY_RC(persistent_prepare(enc_chain_fwd_kernel, grid, smem));
-    hipLaunchKernelGGL(enc_chain_fwd_kernel, dim3(grid), dim3(NTH), smem, s, d);
-    T2_LAUNCH_CHECK();
-    return 0;
-}
-
-int enc_chain_bwd(EncChainBwdDesc d, float* ws, size_t ws_floats, hipStream_t s) {
-    T2_REQUIRE(enc_chain_covers(d.ND, d.B, d.H) && d.T >= 1, "enc_chain_bwd: shape not covered (ND=%d B=%d H=%d)", d.ND, d.B, d.H);
-    T2_REQUIRE(ws && ws_floats >= enc_chain_ws_floats(d.ND, d.B, d.H, 1), "enc_chain_bwd: exchange space too small");
-    const int NRG = (d.B + 31) / 32, Bp = NRG * 32, NT = EH / 32;
-    const size_t ncnt = (size_t)d.ND * NRG * (1 + NT) * CNT_STRIDE;
-    d.err = reinterpret_cast<unsigned*>(ws);
-    d.cnt = reinterpret_cast<unsigned*>(ws + 64);
-    d.X = ws + 64 + ncnt;
-    d.PB = d.X + (size_t)2 * d.ND * 4 * EH * Bp;
-    T2_CHECK_HIP(hipMemsetAsync(ws, 0, (64 + ncnt) * sizeof(float), s));
-    const int ipg = std::max(NT * EGKP, EH / EPU);
-    const int grid = d.ND * NRG * ipg;
-    const size_t smem = (size_t)(4 + NWV * 32 * PPR) * sizeof(float);
-    T2_TRY_RC(persistent_prepare(enc_chain_bwd_kernel, grid, smem));
-    hipLaunchKernelGGL(enc_chain_bwd_kernel, dim3(grid), dim3(NTH), smem, s, d);
-    T2_LAUNCH_CHECK();
-    return 0;
+int enc_chain_bwd(EncChainBwdDesc d, const ChainPlan& p, float* ws, size_t ws_floats, hipStream_t s) {
+    T2_REQUIRE_PLAN(p, CI_ENC_BWD, 1, ws, ws_floats, "enc_chain_bwd");
+    T2_REQUIRE(d.T >= 1, "enc_chain_bwd: no steps");
+    apply(p, ws, &d);
+    return launch_planned(enc_chain_bwd_kernel, d, p, ws, s);
 }
 
 }  // namespace t2

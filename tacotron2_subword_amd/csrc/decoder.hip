@@ -11,6 +11,7 @@
 
 #include "../../include/t2amd.h"
 #include "kernels.h"
+#include "chain_plan.h"
 #include "driver.h"
 
 using namespace t2;
@@ -418,15 +419,16 @@ int dec_lstm_step(const Dec& c, int t) {
     return counted(lstm_step_fwd(d, sd, &family), 0, family);
 }
 
-// Persistent-kernel descriptors of the two teacher-forced chains (chain.hip).  Returns false when the shape, mode or
-// device is not covered: the caller then launches the per-step kernels.
-bool chain_a_desc(const Dec& c, ChainDesc* out) {
+// Persistent-kernel descriptors of the two teacher-forced chains (chain.hip): the pointer part here, the plan (chain_plan.h)
+// from the descriptor's shape.  Returns false when the shape, mode or device is not covered: the caller then launches the
+// per-step kernels.
+bool chain_a_desc(const Dec& c, ChainDesc* out, ChainPlan* plan) {
     const Sizes& z = c.z; const t2_decoder_layout& L = c.L;
     if (!c.use16 || !c.teacher) return false;
     if (c.d.attention_kind != T2_ATTN_SMA && c.d.attention_kind != T2_ATTN_LSA) return false;
     ChainDesc d{};
     d.NS = z.NS; d.B = z.B; d.T = z.T; d.H = z.Ha; d.E = z.E; d.A = z.A; d.WD = z.WD; d.WO = z.WO;
-    d.P = z.P; d.Hd = z.Hd;                                           // (read by the exchange-space carve only: dec = 0)
+    d.P = z.P; d.Hd = z.Hd;                                           // (read by the plan's exchange-space layout only: dec = 0)
     d.din = c.P(L.din); d.din16 = c.P16(L.din16); d.dout = c.P(L.dout);
     d.kind = c.d.attention_kind == T2_ATTN_SMA ? CHAIN_SMA : CHAIN_LSA;
     d.F = c.d.loc_filters; d.Kc = c.d.loc_kernel; d.max_pos = c.max_pos;
@@ -450,12 +452,13 @@ bool chain_a_desc(const Dec& c, ChainDesc* out) {
         st.site_h = r.site_h; st.site_c = r.site_c; st.site_noise = r.site_noise;
         st.mask_value = r.mask_value;
     }
-    if (!chain_plan(d)) return false;
+    *plan = plan_here(plan_chain_fwd, chain_shape_of(d, L.chain_floats * sizeof(float)));
+    if (plan->refusal != CHAIN_OK) return false;
     d.err = status_words(c.ws, L) + CHAIN_STATUS_FWD_ATT;
     *out = d;
     return true;
 }
-bool chain_b_desc(const Dec& c, ChainDesc* out) {
+bool chain_b_desc(const Dec& c, ChainDesc* out, ChainPlan* plan) {
     const Sizes& z = c.z; const t2_decoder_layout& L = c.L;
     if (!c.use16 || !c.teacher) return false;
     ChainDesc d{};
@@ -468,14 +471,15 @@ bool chain_b_desc(const Dec& c, ChainDesc* out) {
     st.gates = c.P(L.gd); st.c_new = c.P(L.cnd); st.c_out = c.P(L.cd);
     st.h_out = c.P(L.dout); st.ldh = z.WO; st.h16_out = c.P16(L.dh16); st.ldh16 = z.Hd;
     st.site_h = T2_SITE_DEC_H; st.site_c = T2_SITE_DEC_C; st.Tin = 4;
-    if (!chain_plan(d)) return false;
+    *plan = plan_here(plan_chain_fwd, chain_shape_of(d, L.chain_floats * sizeof(float)));
+    if (plan->refusal != CHAIN_OK) return false;
     d.err = status_words(c.ws, L) + CHAIN_STATUS_FWD_LSTM;
     *out = d;
     return true;
 }
 
 // Persistent decode loop (chain.hip, dec mode): every phase of Decoder.inference's step inside one launch per step range
-bool chain_dec_desc(const Dec& c, const t2_decoder_infer_args& a, ChainDesc* out) {
+bool chain_dec_desc(const Dec& c, const t2_decoder_infer_args& a, ChainDesc* out, ChainPlan* plan) {
     const Sizes& z = c.z; const t2_decoder_layout& L = c.L; const t2_decoder_weights& w = c.w;
     if (!c.use16 || z.NS != 2) return false;
     if (c.d.attention_kind != T2_ATTN_SMA && c.d.attention_kind != T2_ATTN_LSA) return false;
@@ -504,7 +508,8 @@ bool chain_dec_desc(const Dec& c, const t2_decoder_infer_args& a, ChainDesc* out
     d.mel_out = a.mel_out; d.ldmel = (long)z.T * z.M; d.gate_out = a.gate_out; d.ldgate = z.T;
     d.thr = a.gate_threshold; d.stop_index = a.stop_index; d.done = a.done_count;
     d.pdrop = c.prenet_dropout ? c.d.p_prenet_dropout : 0.f;
-    if (!chain_plan(d)) return false;
+    *plan = plan_here(plan_chain_fwd, chain_shape_of(d, L.chain_floats * sizeof(float)));
+    if (plan->refusal != CHAIN_OK) return false;
     d.err = status_words(c.ws, L) + CHAIN_STATUS_FWD_ATT;
     *out = d;
     return true;
@@ -633,7 +638,7 @@ struct Bwd {
     size_t gemm_ws_bytes() const { return BL.gemm_ws_floats * sizeof(float); }
     StreamRef st[2]{}; BwdStreamRef bst[2]{};
     // the reverse-time chains of this pass (bwd_chains): persistent descriptors, side stream, next free event slot
-    ChainBwdDesc cab{}, cbb{}; bool chain_a = false, chain_b = false;
+    ChainBwdDesc cab{}, cbb{}; ChainPlan pab{}, pbb{}; bool chain_a = false, chain_b = false;
     Side* side = nullptr; bool overlap = false; size_t ne = 0;
     // defer: the leaf tail stays on the side stream when the entry point returns (t2_decoder_bwd_args.defer_weight_grads).
     // With the attention chain persistent the decoder-LSTM weight gradients wait for that fork too: bwd_chains leaves
@@ -692,7 +697,7 @@ int dec_bwd_step(const Bwd& c, int t) {
 }
 
 // Persistent BPTT of the decoder LSTM (chain_bwd.hip); false = not covered, per-step launches instead
-bool chain_b_bwd_desc(const Bwd& c, ChainBwdDesc* out) {
+bool chain_b_bwd_desc(const Bwd& c, ChainBwdDesc* out, ChainPlan* plan) {
     const Sizes& z = c.z;
     if (!c.use16) return false;
     ChainBwdDesc d{};
@@ -705,7 +710,8 @@ bool chain_b_bwd_desc(const Bwd& c, ChainBwdDesc* out) {
     st.dg = c.S(c.BL.dgd); st.dc_state = c.S(c.BL.dcd);
     st.dbias_part = c.S(c.BL.partd);                                 // (the launch path's K-split scratch: idle when the chain runs) [MT][4Hd]
     st.site_h = T2_SITE_DEC_H; st.site_c = T2_SITE_DEC_C;
-    if (!chain_bwd_plan(d)) return false;
+    *plan = plan_here(plan_chain_bwd, chain_shape_of(d, c.BL.chain_floats * sizeof(float)));
+    if (plan->refusal != CHAIN_OK) return false;
     d.err = status_words(c.a.ws, c.L) + CHAIN_STATUS_BWD_LSTM;
     *out = d;
     return true;
@@ -728,7 +734,7 @@ bool saved_tiles_have(const void* ws) {
 }
 
 // Persistent BPTT of the attention chain (both attention LSTMs + SMA attention); false = not covered
-bool chain_a_bwd_desc(const Bwd& c, ChainBwdDesc* out) {
+bool chain_a_bwd_desc(const Bwd& c, ChainBwdDesc* out, ChainPlan* plan) {
     const Sizes& z = c.z;
     const bool lsa = c.d.attention_kind == T2_ATTN_LSA;
     if (!c.use16 || !(lsa || (c.d.attention_kind == T2_ATTN_SMA && attn_bwd_nsplit(c.d, z) == 2))) return false;
@@ -760,7 +766,8 @@ bool chain_a_bwd_desc(const Bwd& c, ChainBwdDesc* out) {
             st.dconv_acc = c.S(b.dlconv); st.ddense_acc = c.S(b.dldense);
         }
     }
-    if (!chain_bwd_plan(d)) return false;
+    *plan = plan_here(plan_chain_bwd, chain_shape_of(d, c.BL.chain_floats * sizeof(float)));
+    if (plan->refusal != CHAIN_OK) return false;
     d.err = status_words(c.a.ws, c.L) + CHAIN_STATUS_BWD_ATT;
     *out = d;
     return true;
@@ -921,8 +928,11 @@ int fwd_prologue(const Dec& c, const float* mels) {
 // run back to back on the caller's stream: A over all steps, one input GEMM, B over all steps.
 int fwd_chains(Dec& c) {
     const Sizes& z = c.z; const t2_decoder_layout& L = c.L;
-    ChainDesc ca{}, cb{};
-    const bool chain_a = g_chain && chain_a_desc(c, &ca), chain_b = g_chain && chain_b_desc(c, &cb);
+    ChainDesc ca{}, cb{}; ChainPlan pa{}, pb{};
+    const bool chain_a = g_chain && chain_a_desc(c, &ca, &pa);
+    // (a pass whose attention-chain tiling has no kernel instance takes the per-step launches as a whole, the decoder LSTM
+    //  included: its bits are then those of a pass with the chains off.  Before the plan existed such a pass failed.)
+    const bool chain_b = g_chain && pa.refusal != CHAIN_REFUSE_NO_INSTANCE && chain_b_desc(c, &cb, &pb);
     c.chained = chain_a || chain_b;
     saved_tiles_note(c.ws, chain_a && ca.kind == CHAIN_LSA);
     // status words always (0 = OK / not used); the tagged exchange buffers (zero state of step -1) when a chain runs
@@ -937,7 +947,7 @@ int fwd_chains(Dec& c) {
         if (chain_a) {
             ca.t0 = t0; ca.t1 = t1;
             ProfScope ps(PK_CHAIN_A_FWD, c.s);
-            T2_TRY(chain_fwd(ca, c.P(L.chain), L.chain_floats, c.s));
+            T2_TRY(chain_fwd(ca, pa, c.P(L.chain), L.chain_floats, c.s));
         } else {
             for (int t = t0; t < t1; ++t) {
                 T2_TRY(att_lstm_step(c, t));
@@ -959,7 +969,7 @@ int fwd_chains(Dec& c) {
         if (chain_b) {
             cb.t0 = t0; cb.t1 = t1;
             ProfScope ps(PK_CHAIN_B_FWD, sb);
-            T2_TRY(chain_fwd(cb, c.P(L.chain), L.chain_floats, sb));
+            T2_TRY(chain_fwd(cb, pb, c.P(L.chain), L.chain_floats, sb));
         } else {
             for (int t = t0; t < t1; ++t) T2_TRY(dec_lstm_step(c, t));
         }
@@ -1032,7 +1042,7 @@ int bwd_dec_lstm_wgrads(const Bwd& c, const Dg16& dg, bool staged, hipStream_t s
 int bwd_chains(Bwd& c) {
     const Sizes& z = c.z; const t2_decoder_bwd_layout& BL = c.BL;
     const int BT = z.B * z.T;
-    c.chain_a = g_chain && g_chain_bwd && chain_a_bwd_desc(c, &c.cab);
+    c.chain_a = g_chain && g_chain_bwd && chain_a_bwd_desc(c, &c.cab, &c.pab);
     c.overlap = g_overlap && z.T >= 32 && !c.chain_a;
     if (c.overlap) {
         T2_TRY(side_get(&c.side)); c.sd = c.side->s;
@@ -1056,13 +1066,13 @@ int bwd_chains(Bwd& c) {
     for (size_t ci = 1; ci < bounds.size(); ++ci) if (((bounds[ci] - bounds[ci - 1]) * z.B) % 64 != 0) chunk_cast = false;
     // (next to per-step launches of the attention chain a persistent decoder-LSTM grid only takes CUs away from them:
     //  measured 24.8 -> 26.3 ms; it runs when the attention chain is persistent too)
-    c.chain_b = c.chain_a && chain_b_bwd_desc(c, &c.cbb);
+    c.chain_b = c.chain_a && chain_b_bwd_desc(c, &c.cbb, &c.pbb);
     for (size_t ci = bounds.size() - 1; ci > 0; --ci) {
         const int t0 = bounds[ci - 1], t1 = bounds[ci];
         if (c.chain_b) {
             c.cbb.t0 = t0; c.cbb.t1 = t1;
             ProfScope ps(PK_CHAIN_B_BWD, sb);
-            T2_TRY(chain_bwd(c.cbb, c.S(BL.chain), BL.chain_floats, sb));
+            T2_TRY(chain_bwd(c.cbb, c.pbb, c.S(BL.chain), BL.chain_floats, sb));
         } else {
             for (int t = t1 - 1; t >= t0; --t) T2_TRY(dec_bwd_step(c, t));
         }
@@ -1086,7 +1096,7 @@ int bwd_chains(Bwd& c) {
         if (c.chain_a) {
             c.cab.t0 = t0; c.cab.t1 = t1;
             ProfScope ps(PK_CHAIN_A_BWD, c.s);
-            T2_TRY(chain_bwd(c.cab, c.S(BL.chain), BL.chain_floats, c.s));
+            T2_TRY(chain_bwd(c.cab, c.pab, c.S(BL.chain), BL.chain_floats, c.s));
         } else {
             for (int t = t1 - 1; t >= t0; --t) T2_TRY(att_bwd_step(c, t));
         }
@@ -1354,8 +1364,8 @@ int t2_decoder_infer(const t2_dims* dims_in, const t2_decoder_weights* w, const 
     int steps = 0;
     StopPoll* pl = nullptr;
     T2_TRY(stop_poll_get(&pl));
-    ChainDesc cdec{};
-    const bool chain = g_chain && chain_dec_desc(c, *a, &cdec);
+    ChainDesc cdec{}; ChainPlan pdec{};
+    const bool chain = g_chain && chain_dec_desc(c, *a, &cdec, &pdec);
     if (chain && a->poll_every <= 0) poll = 32;                      // one persistent launch per polling interval: 32 steps amortise its start-up
     // status words always; with the chain its whole exchange space (zero state of step -1: h, ctx, dec_h, go-frame prenet = 0)
     T2_TRY(chain_fwd_ws_clear(c.P(L.chain), L.chain_floats, chain ? CHAIN_WS_DECODE : CHAIN_WS_STATUS, c.s));
@@ -1365,7 +1375,7 @@ int t2_decoder_infer(const t2_dims* dims_in, const t2_decoder_weights* w, const 
             if (t % poll == 0) {                                     // one persistent launch per polling interval
                 cdec.t0 = t; cdec.t1 = std::min(T, t + poll);
                 ProfScope ps(PK_CHAIN_DEC, c.s);
-                T2_TRY(chain_fwd(cdec, c.P(L.chain), L.chain_floats, c.s));
+                T2_TRY(chain_fwd(cdec, pdec, c.P(L.chain), L.chain_floats, c.s));
             }
         } else {
             T2_TRY(att_lstm_step(c, t));

@@ -291,7 +291,7 @@ struct ChainDesc {
     int kind, F, Kc, max_pos;
     float drop_p, noise_std; uint64_t seed;
     unsigned char* X; float* Q; unsigned* cnt; unsigned* err; unsigned q_bytes;   // exchange buffers (chain_fwd; cnt: decode loop only), status word
-    int UT, RT, CS;                                // tiling chosen by chain_plan
+    int UT, RT, CS;                                // tiling (plan-owned, like X / Q / cnt / XD / XM / q_bytes and the residency fields: chain_plan.h apply)
     // decode loop (dec = 1; Decoder.inference, model.py:430-492): whole-cell shadows [W_hh | W_ih[:,P:] | W_ih[:,:P]] in st[].w16,
     // biases instead of hoisted pre-activations, and the decoder LSTM, the projections + stop rule and both prenets inside the launch
     int dec, P, M, Hd;                              // (P, Hd: set in every attention-chain descriptor, they place its exchange buffers)
@@ -307,19 +307,18 @@ struct ChainDesc {
     unsigned char* XD; unsigned char* XM;          // exchange: dec_h fragments [2][Hd/16][1 KB], mel fragments [2][6][1 KB]
     int lds_Tin, lds_Jp, lds_Jm; int Jp[2], Jm[2]; // LDS residency: processed-memory / memory rows kept on chip
 };
-bool chain_plan(ChainDesc& d);                     // fills UT/RT/CS and the residency fields; false = shape not covered
 constexpr int kCntShards = 16;                     // every arrival counter is kept as 16 shards, each on a 128-byte line of its own (chain_common.h)
 // Status words of a pass (0 = completed or not used, else the code of the hand-off that timed out): the 256-byte block at the head
 // of the forward workspace's chain region (t2amd.h t2_decoder_layout.chain, ops.DecoderPass.chain_status); the decode loop
 // reports in the attention chain's word
 enum ChainStatus : int { CHAIN_STATUS_FWD_ATT = 0, CHAIN_STATUS_FWD_LSTM = 1, CHAIN_STATUS_BWD_LSTM = 2, CHAIN_STATUS_BWD_ATT = 3 };
-// Exchange space of a pass's forward chains and decode loop, the status words at its head: sized for the largest tiling chain_plan
-// can choose; chain_fwd carves its buffers out of it.  chain_fwd_ws_clear, once per pass: the status words, + the teacher-forced
-// chains' tagged buffers (query partials, fragments), or + (decode loop) every buffer: they carry across its step-range launches.
+// Exchange space of a pass's forward chains and decode loop, the status words at its head: sized for the largest tiling the plan
+// can choose (chain_plan.hip lays the chains' buffers out in it; tests/test_chain_plan_cpu.py checks that they fit).
+// chain_fwd_ws_clear, once per pass: the status words, + the teacher-forced chains' tagged buffers (query partials, fragments),
+// or + (decode loop) every buffer: they carry across its step-range launches.  Planning and launching a chain: chain_plan.h.
 enum ChainWsClear : int { CHAIN_WS_STATUS = 0, CHAIN_WS_TEACHER = 1, CHAIN_WS_DECODE = 2 };
 size_t chain_fwd_ws_floats(int NS, int B, int Ha, int E, int P, int Hd, int A);
 int chain_fwd_ws_clear(float* ws, size_t ws_floats, ChainWsClear what, hipStream_t s);
-int chain_fwd(ChainDesc d, float* ws, size_t ws_floats, hipStream_t s);
 int chain_device_cus();
 // c_api.hip: the current device's sticky status words (page-locked host memory the device writes directly; the pointer is
 // valid on both sides), and this process's claim on the device's persistent kernels (one process per GPU)
@@ -360,13 +359,11 @@ struct ChainBwdDesc {
     float drop_p; uint64_t seed;
     unsigned char* X; unsigned char* PB; unsigned* err; unsigned pb_bytes;                   // exchange (chain_bwd): dg fragments, K-split partials; status word
     unsigned char* PBC; unsigned pbc_bytes; float* DQX; float* CARRYX;                       // attention chain: ctx partials, dq partials, boundary carry (LSA: halo rows of dloc + softmax-dot partials)
-    int lds_Tc;                                                                              // positions per split of the longest memory (LDS carve)
+    int lds_Tc;                                                                              // positions per split of the longest memory (LDS carve).  All plan-owned
 };
-bool chain_bwd_plan(ChainBwdDesc& d);
-// Exchange space of the backward chains (kind: the attention chain's, CHAIN_SMA or CHAIN_LSA); chain_bwd carves its buffers out of
-// it and clears them per launch
+// Exchange space of the backward chains (kind: the attention chain's, CHAIN_SMA or CHAIN_LSA); the plan lays their buffers out
+// in it, chain_bwd clears the tagged ones per launch
 size_t chain_bwd_ws_floats(int kind, int NS, int B, int Ha, int E, int A, int F, int Kc, int Hd);
-int chain_bwd(ChainBwdDesc d, float* ws, size_t ws_floats, hipStream_t s);
 
 // Persistent encoder BiLSTM chains (chain_enc.hip): all steps of up to two directions in one launch, exact fp32
 struct EncChainDesc {
@@ -377,7 +374,7 @@ struct EncChainDesc {
     const int* lengths;                    // [B] or null (unpacked)
     float* h[2]; long ldh;                 // h[s][(t*B + b)*ldh + u]
     float* c[2]; float* gates[2];          // [T][B][H], [T][B][4H]
-    float* X; unsigned* cnt; unsigned* err;   // filled by enc_chain_fwd from the exchange space
+    float* X; unsigned* cnt; unsigned* err;   // plan-owned: filled from the exchange space
 };
 struct EncChainBwdDesc {
     int ND, B, T, H;
@@ -387,10 +384,7 @@ struct EncChainBwdDesc {
     float* dpre[2];                        // out: [T][B][4H]
     float* X; float* PB; unsigned* cnt; unsigned* err;
 };
-bool enc_chain_covers(int ND, int B, int H);
 size_t enc_chain_ws_floats(int ND, int B, int H, int backward);
-int enc_chain_fwd(EncChainDesc d, float* ws, size_t ws_floats, hipStream_t s);
-int enc_chain_bwd(EncChainBwdDesc d, float* ws, size_t ws_floats, hipStream_t s);
 
 // ------------------------------------------------------------------ decode-step tail (infer.hip)
 // projection + stop rule of step t and both prenets of step t+1, one workgroup per batch item

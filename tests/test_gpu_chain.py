@@ -37,7 +37,14 @@ def _inputs(B, Tin, Tsub, T, seed=5, ragged=True):
     return [x.cuda() for x in (mem, mems, tl, bl, mels)]
 
 
+def _plan(L, att, backward, B, Tin, Tsub, NS=2):
+    """What the library's plan says for the attention chain of a pass on this device (t2_chain_plan: launches nothing)."""
+    return L.chain_plan("sma" if att is SMA else "lsa", backward, NS=NS, B=B, Tin=(Tin, Tsub),
+                        cus=torch.cuda.get_device_properties(0).multi_processor_count, claimed=bool(L.lib().t2_chain_claimed()))
+
+
 def _run(env, att, B, Tin, Tsub, T, chain, training, seed=11, ragged=True):
+    """-> outputs, status words, the pass's objects; _run.fwd_steps: per-step forward LSTM launches of the pass (exact, bf16, split)"""
     L, ops = env
     hp = hp_for(att)
     P = to_dev(recipe.make_weights(hp))
@@ -46,8 +53,10 @@ def _run(env, att, B, Tin, Tsub, T, chain, training, seed=11, ragged=True):
     mem, mems, tl, bl, mels = _inputs(B, Tin, Tsub, T, ragged=ragged)
     L.set_precision("bf16")
     L.set_chain(chain)
+    L.step_counts(reset=True)
     dp = ops.decoder_forward(W, dims, mem, mems, tl, bl, mels, training=training, prenet_dropout=training, seed=seed)
     torch.cuda.synchronize()
+    _run.fwd_steps = L.step_counts()[:3]
     st = dp.chain_status()
     saved = {k: dp.view(k, n).clone() for k, n in (("ga", B * T * 4096), ("ca", B * T * 1024), ("din", B * T * 3072),
                                                     ("dout", B * T * 2048), ("qs", B * T * 128), ("gd", B * T * 4096), ("cd", B * T * 1024))}
@@ -60,9 +69,15 @@ def _run(env, att, B, Tin, Tsub, T, chain, training, seed=11, ragged=True):
 @pytest.mark.parametrize("training", [False, True])
 def test_chain_matches_per_step_launches(env, att, B, Tin, Tsub, T, training):
     """Every tiling (B <= 32: one row tile, 8 units per item, context in 4 parts; B <= 64: 16 units, 2 parts; B <= 128: two
-    row tiles, whole context rows), ragged memory lengths, with and without LSTM-state dropout + SMA noise."""
+    row tiles, whole context rows), ragged memory lengths, with and without LSTM-state dropout + SMA noise.  The plan names the
+    tiling, and the per-step launch counters show which path each run took."""
+    plan = _plan(env[0], att, False, B, Tin, Tsub)
+    assert plan["covered"], plan
+    assert (plan["UT"], plan["RT"], plan["CS"]) == {3: (1, 1, 4), 33: (2, 1, 2), 64: (2, 1, 2), 128: (2, 2, 1)}[B], plan
     ref, st0, _ = _run(env, att, B, Tin, Tsub, T, chain=False, training=training)
+    assert sum(_run.fwd_steps) > 0, _run.fwd_steps                     # one launch per step
     got, st1, _ = _run(env, att, B, Tin, Tsub, T, chain=True, training=training)
+    assert _run.fwd_steps == (0, 0, 0), _run.fwd_steps                 # the persistent kernels took every step
     assert not any(st0) and not any(st1), (st0, st1)
     errs = {k: maxabs(got[k], ref[k]) for k in ref}
     print("chain vs launches, max-abs:", {k: f"{v:.2e}" for k, v in errs.items()})
@@ -71,6 +86,34 @@ def test_chain_matches_per_step_launches(env, att, B, Tin, Tsub, T, training):
     for k in ("mel", "gate", "ga", "ca", "din", "dout", "qs", "gd", "cd"):
         assert errs[k] < 3e-2, errs
     assert all(bool(torch.isfinite(v).all()) for v in got.values())
+
+
+@pytest.mark.parametrize("att", [SMA, LSA])
+def test_tiling_without_a_kernel_takes_the_per_step_launches(env, att):
+    """One stream at 97-128 rows asks for the tiling UT = 1, RT = 2, which has no kernel instance: the plan refuses it with a
+    reason of its own and the pass runs one launch per step, chains on or off, with the same bits.  (Before the plan existed the
+    tiling was accepted and the pass failed on the host, ahead of any launch: "tiling UT=1 RT=2 not instantiated".)"""
+    L, ops = env
+    B, Tin, T = 97, 20, 4
+    plan = _plan(L, att, False, B, Tin, 0, NS=1)
+    assert not plan["covered"] and plan["reason_text"] == "the tiling of this shape has no kernel instance", plan
+    hp = hp_for(att)
+    P = to_dev(recipe.make_weights(hp, single=True))
+    dims = L.dims_from_hparams(hp, n_streams=1)
+    W = L.decoder_weights(P, dims.attention_kind, single=True)
+    mem, _, tl, _, mels = _inputs(B, Tin, 4, T)
+    L.set_precision("bf16")
+    outs = {}
+    for chain in (True, False):
+        L.set_chain(chain)
+        L.step_counts(reset=True)
+        dp = ops.decoder_forward(W, dims, mem, None, tl, None, mels, training=False, prenet_dropout=False, seed=11)
+        torch.cuda.synchronize()
+        assert sum(L.step_counts()[:3]) > 0 and not any(dp.chain_status())
+        outs[chain] = dict(mel=dp.mel.clone(), gate=dp.gate.clone(), align=dp.align.clone(), dout=dp.view("dout", B * T * 1536).clone())
+    L.set_chain(True)
+    for k, v in outs[False].items():
+        assert bool(torch.isfinite(v).all()) and torch.equal(v, outs[True][k]), k
 
 
 def test_chain_without_lds_residency_is_tight(env):
@@ -130,6 +173,7 @@ def test_backward_chain_matches_per_step_backward(env, att):
     res = {}
     cases = ((8, 10, 40, 36), (64, 40 if att is SMA else 24, 100, 60))
     for B, T, Tin, Tsub in cases:
+        assert _plan(L, att, True, B, Tin, Tsub)["covered"] and _plan(L, att, False, B, Tin, Tsub)["covered"]
         for bwd in (False, True):
             L.set_chain_bwd(bwd)
             try:
@@ -140,13 +184,16 @@ def test_backward_chain_matches_per_step_backward(env, att):
                 # external gradients on the alignments too (the alignment-guide losses of loss_function.py produce them)
                 dal = 0.1 * torch.randn(B, T, Tin, device="cuda", generator=g)
                 dals = 0.1 * torch.randn(B, T, Tsub, device="cuda", generator=g)
+                assert _run.fwd_steps == (0, 0, 0), _run.fwd_steps
                 L.prof_enable(8 * T + 64)
+                L.step_counts(reset=True)
                 G, dm, dms = ops.decoder_backward(W, P, dims, dp, mem, mems, dmel, dgate, training=True, prenet_dropout=True, seed=11,
                                                   d_align=dal, d_align_sub=dals)
                 torch.cuda.synchronize()
-                prof = L.prof_collect()
+                prof, grad_steps = L.prof_collect(), L.step_counts()[3:]
                 assert not any(dp.chain_status()), dp.chain_status()
                 assert prof["chain_a_bwd"][1] == (1 if bwd else 0), prof
+                assert grad_steps == (0, 0, 0) if bwd else sum(grad_steps) > 0, grad_steps
             finally:
                 L.set_chain_bwd(True)
             res[bwd] = dict(G, d_memory=dm, d_memory_sub=dms)
@@ -166,14 +213,19 @@ def test_backward_consumes_chain_activations(env, att):
     match gradients from the per-step path."""
     L, ops = env
     res = {}
+    # (the 12-position memory is below the backward chain's 16, LSA's splits below the conv halo: forward on the chain, backward one
+    #  launch per step)
+    assert _plan(L, att, False, 8, 21, 12)["covered"] and not _plan(L, att, True, 8, 21, 12)["covered"]
     for chain in (False, True):
         out, st, (W, P, dims, dp, mem, mems) = _run(env, att, 8, 21, 12, 10, chain=chain, training=True)
-        assert not any(st)
+        assert not any(st) and (_run.fwd_steps == (0, 0, 0) if chain else sum(_run.fwd_steps) > 0), _run.fwd_steps
         g = torch.Generator(device="cuda").manual_seed(3)
         dmel = torch.randn(8, 10, 80, device="cuda", generator=g)
         dgate = torch.randn(8, 10, device="cuda", generator=g)
+        L.step_counts(reset=True)
         G, dm, dms = ops.decoder_backward(W, P, dims, dp, mem, mems, dmel, dgate, training=True, prenet_dropout=True, seed=11)
         torch.cuda.synchronize()
+        assert sum(L.step_counts()[3:]) > 0
         res[chain] = dict(G, d_memory=dm, d_memory_sub=dms)
     worst = {}
     for k, v in res[False].items():
@@ -197,11 +249,14 @@ def test_chains_are_bit_reproducible(env, att):
     dmel = torch.randn(B, T, 80, device="cuda", generator=g)
     dgate = torch.randn(B, T, device="cuda", generator=g)
     ref = None
+    assert _plan(L, att, False, B, Tin, Tsub)["covered"] and _plan(L, att, True, B, Tin, Tsub)["covered"]
     for rep in range(5):
         out, st, (W, P, dims, dp, mem, mems) = _run(env, att, B, Tin, Tsub, T, chain=True, training=True)
         assert not any(st), st
+        L.step_counts(reset=True)
         G, dm, dms = ops.decoder_backward(W, P, dims, dp, mem, mems, dmel, dgate, training=True, prenet_dropout=True, seed=11)
         torch.cuda.synchronize()
+        assert _run.fwd_steps == (0, 0, 0) and L.step_counts()[3:] == (0, 0, 0), (_run.fwd_steps, L.step_counts())
         assert not any(dp.chain_status()), dp.chain_status()
         cur = dict(out, **{"grad_" + k: v for k, v in G.items()}, d_memory=dm, d_memory_sub=dms)
         if ref is None:
