@@ -487,6 +487,50 @@ typedef struct t2_chain_plan_info {
     size_t clear_off, clear_bytes, pass_clear_bytes[3];
 } t2_chain_plan_info;
 int t2_chain_plan(const t2_chain_shape* shape, int direction, int cus, int claimed, int no_resident, t2_chain_plan_info* out);
+/* What a decoder pass would do (csrc/decoder_plan.hip), decided on the host: launches nothing, needs no device, never asks for
+ * the per-GPU claim.  Everything the library reads from the process and the device comes in env: the precision mode (0 fp32,
+ * 1 bf16, 2 split-bf16), the switches (t2_set_split_steps, t2_set_chain, t2_set_chain_bwd, t2_set_overlap), cus / claimed /
+ * no_resident as for t2_chain_plan, and (backward) saved_tiles = the forward pass ran the LSA chain, so that its workspace
+ * holds the tanh tiles.  T: frames (decode loop: max_steps); defer_weight_grads: backward only; poll_every: decode loop only.
+ * The result holds every decision of the pass (DESIGN.md section 3 has the rule of each field): both workspace layouts
+ * (bwd_layout: backward only), the recurrent steps (use16 / split), the persistent chains (chain_a: attention chain, or the
+ * whole decode loop; chain_b: decoder-LSTM chain; asked = the switches, the step mode and the attention kind let the pass plan
+ * one, on = it runs, reason / reason_text otherwise; t2_chain_plan has the chain's own details), whether the chains overlap on
+ * the side stream and the bounds of the step ranges they hand to each other, what the pass clears in its exchange space
+ * (0 status words, 1 teacher-forced, 2 decode loop), over how many status words the outputs get the abort poison, the poll
+ * interval, and the GEMM scratch as named parts in bytes from its start (bytes == 0: no such part): the bf16 copy of the
+ * decoder LSTM's W_ih or W_ih^T (pre16), the shared bf16 copy of dG (share), the rest.  Backward: scratch is the carve while
+ * the chains run (ddin_ws: what a range's dDIN product works in; chunk_cast: dG is cast range by range), tail_scratch the
+ * carve of the leaf tail (tail_share); dec_wgrads says where the decoder-LSTM weight gradients are issued (0 in the range
+ * loop on chain B's stream, 1 on the tail's stream; dec_wgrads_staged: their dG copy is already filled), tail_on_side the
+ * tail's stream, nsplit the position splits of the per-step attention backward, dq_parts the partials the tail folds. */
+enum { T2_PASS_FORWARD = 0, T2_PASS_BACKWARD, T2_PASS_INFER };                                                       /* pass */
+enum { T2_PASS_MAX_BOUNDS = 64 };
+typedef struct t2_pass_env {
+    int precision, split_steps, chain, chain_bwd, overlap, cus, claimed, no_resident, saved_tiles;
+} t2_pass_env;
+typedef struct t2_pass_chain {
+    int asked, on, reason; const char* reason_text;          /* static strings */
+    int instance; const char* instance_name; int grid;
+} t2_pass_chain;
+typedef struct t2_scratch_carve {
+    size_t w_ih16_off, w_ih16_bytes, dg16_off, dg16_bytes, rest_off, rest_bytes, total_bytes;
+} t2_scratch_carve;
+typedef struct t2_decoder_pass_plan_info {
+    t2_decoder_layout layout; t2_decoder_bwd_layout bwd_layout;
+    int use16, split, pre16;
+    t2_scratch_carve scratch;
+    t2_pass_chain chain_a, chain_b;
+    int chained, clear, saves_tiles, overlap;
+    int nbounds, bounds[T2_PASS_MAX_BOUNDS];
+    int poison_words, poll; size_t shadow_floats;            /* shadow_floats: the decode loop's weight shadows and input rows */
+    int defer, share, chunk_cast; size_t ddin_ws_off, ddin_ws_bytes;
+    int dec_wgrads, dec_wgrads_staged, tail_on_side, tail_share;
+    t2_scratch_carve tail_scratch;
+    int nsplit, lsa_chain, dq_parts;
+} t2_decoder_pass_plan_info;
+int t2_decoder_pass_plan(const t2_dims* dims, int pass, int B, int T, int Tin, int Tsub, const t2_pass_env* env, int defer_weight_grads,
+                         int poll_every, t2_decoder_pass_plan_info* out);
 /* The hand-over rule of the conv stacks for the product (a, opts), opts->a16 / b16 naming the copies on offer: *taken = 1
  * and *out = the plan with them iff the product without copies stages every operand a copy is offered for, and with them
  * takes every copy and keeps its kernel, split-K factor and K-chunks per split; otherwise *taken = 0 and *out = the plan

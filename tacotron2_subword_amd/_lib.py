@@ -180,6 +180,33 @@ class ChainPlanInfo(C.Structure):
                 ("clear_off", C.c_size_t), ("clear_bytes", C.c_size_t), ("pass_clear_bytes", C.c_size_t * 3)]
 
 
+PASS_KINDS = dict(forward=0, backward=1, infer=2)       # T2_PASS_*
+PASS_MAX_BOUNDS = 64                                    # T2_PASS_MAX_BOUNDS
+
+
+class PassEnv(C.Structure):
+    _fields_ = [(n, C.c_int) for n in ("precision", "split_steps", "chain", "chain_bwd", "overlap", "cus", "claimed", "no_resident", "saved_tiles")]
+
+
+class PassChain(C.Structure):
+    _fields_ = [("asked", C.c_int), ("on", C.c_int), ("reason", C.c_int), ("reason_text", C.c_char_p),
+                ("instance", C.c_int), ("instance_name", C.c_char_p), ("grid", C.c_int)]
+
+
+class ScratchCarve(C.Structure):
+    _fields_ = [(n, C.c_size_t) for n in ("w_ih16_off", "w_ih16_bytes", "dg16_off", "dg16_bytes", "rest_off", "rest_bytes", "total_bytes")]
+
+
+class DecoderPassPlanInfo(C.Structure):
+    _fields_ = [("layout", DecoderLayout), ("bwd_layout", DecoderBwdLayout)] + \
+               [(n, C.c_int) for n in ("use16", "split", "pre16")] + [("scratch", ScratchCarve), ("chain_a", PassChain), ("chain_b", PassChain)] + \
+               [(n, C.c_int) for n in ("chained", "clear", "saves_tiles", "overlap", "nbounds")] + [("bounds", C.c_int * PASS_MAX_BOUNDS)] + \
+               [("poison_words", C.c_int), ("poll", C.c_int), ("shadow_floats", C.c_size_t)] + \
+               [(n, C.c_int) for n in ("defer", "share", "chunk_cast")] + [("ddin_ws_off", C.c_size_t), ("ddin_ws_bytes", C.c_size_t)] + \
+               [(n, C.c_int) for n in ("dec_wgrads", "dec_wgrads_staged", "tail_on_side", "tail_share")] + [("tail_scratch", ScratchCarve)] + \
+               [(n, C.c_int) for n in ("nsplit", "lsa_chain", "dq_parts")]
+
+
 class SoftDtwPlanInfo(C.Structure):
     _fields_ = [("threads", C.c_int), ("rows_per_thread", C.c_int), ("passes", C.c_int),
                 ("d_floats", C.c_size_t), ("r_floats", C.c_size_t), ("e_floats", C.c_size_t)]
@@ -260,7 +287,7 @@ STFT_POLAR, STFT_DENOISE = 0, 1
 ABI_VERSION = 4      # include/t2amd.h T2_ABI_VERSION: struct sizes below match that header and nothing else
 
 EXPORTS = ["t2_last_error", "t2_version", "t2_chain_status", "t2_chain_status_clear", "t2_debug_report_abort", "t2_debug_occupy", "t2_chain_claimed", "t2_set_precision", "t2_get_precision", "t2_gemm_counts", "t2_set_gemm_split_min_mflop", "t2_set_split_steps", "t2_get_split_steps", "t2_step_counts", "t2_set_overlap", "t2_set_chain", "t2_get_chain", "t2_set_chain_bwd", "t2_set_gemm_staging", "t2_set_gemm_fold", "t2_set_bn_fuse", "t2_get_bn_fuse", "t2_bn_fuse_counts", "t2_side_join", "t2_defer_counts", "t2_decoder_layout_query", "t2_decoder_forward", "t2_decoder_infer",
-           "t2_decoder_bwd_layout_query", "t2_decoder_backward", "t2_prof_enable", "t2_prof_collect", "t2_adam_chunks", "t2_adam_step", "t2_adam_norm",
+           "t2_decoder_bwd_layout_query", "t2_decoder_backward", "t2_decoder_pass_plan", "t2_prof_enable", "t2_prof_collect", "t2_adam_chunks", "t2_adam_step", "t2_adam_norm",
            "t2_conv_bn_forward", "t2_conv_bn_backward", "t2_embedding_forward", "t2_embedding_backward",
            "t2_lstm_seq_forward", "t2_lstm_seq_backward", "t2_lstm_seq_chain_ws_floats", "t2_gemm_ex", "t2_prof_gemm", "t2_gemm_plan", "t2_chain_plan", "t2_conv_handoff_plan", "t2_colsum", "t2_mask_btc",
            "t2_finalize_bct", "t2_mask_bt", "t2_gemm", "t2_rng_keep_mask", "t2_rng_normal",
@@ -296,6 +323,8 @@ def lib() -> C.CDLL:
         L.t2_decoder_bwd_layout_query.argtypes = [C.POINTER(Dims), C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(DecoderBwdLayout)]
         L.t2_decoder_backward.argtypes = [C.POINTER(Dims), C.POINTER(DecoderWeights), C.POINTER(DecoderGrads),
                                           C.POINTER(DecoderBwdArgs), C.c_void_p]
+        L.t2_decoder_pass_plan.argtypes = [C.POINTER(Dims), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(PassEnv), C.c_int, C.c_int,
+                                           C.POINTER(DecoderPassPlanInfo)]
         L.t2_conv_bn_forward.argtypes = [C.POINTER(ConvBnArgs), C.c_void_p]
         L.t2_conv_bn_backward.argtypes = [C.POINTER(ConvBnBwdArgs), C.c_void_p]
         L.t2_embedding_forward.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
@@ -602,6 +631,44 @@ def chain_plan(kind: str, backward: bool = False, *, cus: int = 256, claimed: bo
     out.update(covered=True, reason=0, instance_name=info.instance_name.decode(), Jp=list(info.Jp), Jm=list(info.Jm),
                parts={info.part_name[i].decode(): (info.part_off[i], info.part_bytes[i]) for i in range(CHAIN_PARTS) if info.part_bytes[i]},
                clear=(info.clear_off, info.clear_bytes), pass_clear_bytes=list(info.pass_clear_bytes))
+    return out
+
+
+def decoder_pass_plan(dims: Dims, kind: str, B: int, T: int, Tin: int, Tsub: int, *, defer_weight_grads: bool = False, poll_every: int = 0,
+                      precision: str = "f32", split_steps: bool = False, chain: bool = True, chain_bwd: bool = True, overlap: bool = True,
+                      cus: int = 256, claimed: bool = True, no_resident: bool = False, saved_tiles: bool = False) -> dict:
+    """What a decoder pass would do (t2_decoder_pass_plan: nothing is launched, no device needed, no claim taken).  kind:
+    'forward', 'backward' or 'infer' (T = max_steps); the keyword arguments after poll_every are the environment, all of
+    it explicit: the modes and switches in force are NOT read.  Returns every decision of the pass: the layouts, use16 /
+    split, the chains (asked, on, reason_text, instance_name), overlap and the step-range bounds, the GEMM scratch as
+    parts {name: (offset, bytes)}, and for the backward the tail's carve, where the decoder-LSTM weight gradients go and
+    what the tail folds (include/t2amd.h has the fields)."""
+    env = PassEnv(PRECISION_MODES[precision], int(split_steps), int(chain), int(chain_bwd), int(overlap), cus, int(claimed), int(no_resident),
+                  int(saved_tiles))
+    info = DecoderPassPlanInfo()
+    check(lib().t2_decoder_pass_plan(C.byref(dims), PASS_KINDS[kind], B, T, Tin, Tsub, C.byref(env), int(defer_weight_grads), poll_every, C.byref(info)))
+
+    def chain_of(c):
+        out = dict(asked=bool(c.asked), on=bool(c.on), reason=c.reason, reason_text=c.reason_text.decode())
+        if c.on:
+            out.update(instance=c.instance, instance_name=c.instance_name.decode(), grid=c.grid)
+        return out
+
+    def carve_of(c):
+        return dict(w_ih16=(c.w_ih16_off, c.w_ih16_bytes), dg16=(c.dg16_off, c.dg16_bytes), rest=(c.rest_off, c.rest_bytes), total=c.total_bytes)
+
+    out = dict(kind=kind, layout=info.layout, use16=bool(info.use16), split=bool(info.split), pre16=bool(info.pre16), scratch=carve_of(info.scratch),
+               chain_a=chain_of(info.chain_a), chain_b=chain_of(info.chain_b), chained=bool(info.chained), overlap=bool(info.overlap),
+               bounds=list(info.bounds[:info.nbounds]))
+    if kind == "backward":
+        out.update(bwd_layout=info.bwd_layout, defer=bool(info.defer), share=bool(info.share), chunk_cast=bool(info.chunk_cast),
+                   ddin_ws=(info.ddin_ws_off, info.ddin_ws_bytes), dec_wgrads=("chain_b", "tail")[info.dec_wgrads],
+                   dec_wgrads_staged=bool(info.dec_wgrads_staged), tail_on_side=bool(info.tail_on_side), tail_share=bool(info.tail_share),
+                   tail_scratch=carve_of(info.tail_scratch), nsplit=info.nsplit, lsa_chain=bool(info.lsa_chain), dq_parts=info.dq_parts)
+    else:
+        out.update(clear=("status", "teacher", "decode")[info.clear], saves_tiles=bool(info.saves_tiles), poison_words=info.poison_words)
+    if kind == "infer":
+        out.update(poll=info.poll, shadow_floats=info.shadow_floats)
     return out
 
 

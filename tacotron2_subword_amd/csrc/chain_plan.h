@@ -23,9 +23,7 @@ struct ChainShape {
     size_t ws_bytes;                         // exchange space of the pass; 0 = exactly what this chain needs (ChainPlan::total)
 };
 
-// The shape fields of a descriptor (they are the caller's; everything else in it is the plan's or a pointer)
-ChainShape chain_shape_of(const ChainDesc& d, size_t ws_bytes);
-ChainShape chain_shape_of(const ChainBwdDesc& d, size_t ws_bytes);       // saved_tiles: every stream has usave and locsave
+// (the decoder's chain shapes are stated by its pass plans, decoder_plan.hip, and copied into the descriptors from there)
 ChainShape enc_chain_shape(int ND, int B, int H, int backward, size_t ws_bytes);
 
 enum ChainRefusal : int {

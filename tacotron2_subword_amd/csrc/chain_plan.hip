@@ -80,20 +80,6 @@ const char* chain_part_name(int i) {
     return i >= 0 && i < CHAIN_PARTS ? name[i] : "?";
 }
 
-ChainShape chain_shape_of(const ChainDesc& d, size_t ws_bytes) {
-    ChainShape z{};
-    z.kind = d.kind; z.dec = d.dec; z.NS = d.NS; z.B = d.B; z.H = d.H; z.E = d.E; z.A = d.A; z.P = d.P; z.M = d.M; z.Hd = d.Hd; z.F = d.F; z.Kc = d.Kc;
-    z.Tin[0] = d.st[0].Tin; z.Tin[1] = d.st[1].Tin; z.ws_bytes = ws_bytes;
-    return z;
-}
-ChainShape chain_shape_of(const ChainBwdDesc& d, size_t ws_bytes) {
-    ChainShape z{};
-    z.kind = d.kind; z.NS = d.NS; z.B = d.B; z.H = d.H; z.E = d.E; z.A = d.A; z.F = d.F; z.Kc = d.Kc;
-    z.Tin[0] = d.st[0].Tin; z.Tin[1] = d.st[1].Tin; z.ws_bytes = ws_bytes;
-    z.saved_tiles = true;
-    for (int s = 0; s < d.NS && s < 2; ++s) z.saved_tiles = z.saved_tiles && d.st[s].usave && d.st[s].locsave;
-    return z;
-}
 ChainShape enc_chain_shape(int ND, int B, int H, int backward, size_t ws_bytes) {
     ChainShape z{};
     z.kind = CHAIN_ENC; z.NS = ND; z.B = B; z.H = H; z.backward = backward; z.ws_bytes = ws_bytes;

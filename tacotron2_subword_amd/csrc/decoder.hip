@@ -1,6 +1,6 @@
-// Host drivers of the three decoder passes (t2_decoder_forward, t2_decoder_backward, t2_decoder_infer): workspace layouts,
-// per-stream tables, step and chain descriptors, the chunk schedule.  No device allocation, no synchronisation except
-// where include/t2amd.h says so.
+// Host drivers of the three decoder passes (t2_decoder_forward, t2_decoder_backward, t2_decoder_infer): per-stream tables,
+// step and chain descriptors, and the stages that execute the pass's plan (decoder_plan.h decides; nothing here does).
+// No device allocation, no synchronisation except where include/t2amd.h says so.
 #include <stdlib.h>
 #include <string.h>
 
@@ -12,6 +12,7 @@
 #include "../../include/t2amd.h"
 #include "kernels.h"
 #include "chain_plan.h"
+#include "decoder_plan.h"
 #include "driver.h"
 
 using namespace t2;
@@ -29,20 +30,6 @@ __global__ __launch_bounds__(256) void poison_if_aborted_kernel(const unsigned* 
 }
 
 namespace {
-
-struct Sizes {
-    int B, T, Tin, Tsub, M, P, E, Ha, Hd, A, WD, WO, NS;     // NS: attention streams (2 = BERT_Tacotron2, 1 = classic Tacotron2)
-};
-
-Sizes sizes_of(const t2_dims& d, int B, int T, int Tin, int Tsub) {
-    Sizes z{};
-    z.B = B; z.T = T; z.Tin = Tin; z.Tsub = Tsub;
-    z.M = d.n_mel; z.P = d.prenet_dim; z.E = d.enc_dim; z.Ha = d.att_rnn_dim; z.Hd = d.dec_rnn_dim; z.A = d.att_dim;
-    z.NS = d.n_streams == 1 ? 1 : 2;
-    z.WD = z.NS * (z.Ha + z.E);
-    z.WO = z.Hd + z.NS * z.E;
-    return z;
-}
 
 int check_dims(const t2_dims& d) {
     T2_REQUIRE(d.n_mel % 4 == 0, "n_mel %d must be a multiple of 4", d.n_mel);
@@ -70,89 +57,13 @@ int entry_dims(const t2_dims& in, t2_dims* d, int* max_pos) {
     return 0;
 }
 
-size_t align4(size_t n) { return (n + 3) & ~(size_t)3; }
-
 // score_mask_value `v` of a stream's attention module; a zero-initialised t2_dims (0.0) means the default, -inf
 float mask_value_of(const t2_dims& d, float v) {
     return (v == 0.f && !d.score_mask_given) ? -INFINITY : v;
 }
 
-// Decode loop, bf16-operand mode: whole-cell weight shadows [W_hh | W_ih[:,P:] | W_ih[:,:P]] (attention LSTMs) and
-// [W_ih | W_hh] (decoder LSTM) so that each cell is ONE K-contiguous product, plus the bf16 input rows the producing
-// kernels write: att rows [2][NS][B][Ha+E+P] = [h | ctx | prenet], dec rows [2][B][WD+Hd] = [att_h | ctx | ... | dec_h],
-// ping-pong on step parity (step t reads buffer t&1 and writes the recurrent parts into (t+1)&1).
-struct InferShadows {
-    int Ka, Kd; size_t wa[2], wd, rows_a, rows_d, total_floats;
-};
-InferShadows infer_shadows(const Sizes& z, size_t base) {
-    InferShadows m{};
-    m.Ka = z.Ha + z.E + z.P; m.Kd = z.WD + z.Hd;
-    size_t off = base;
-    auto take = [&](size_t elems) { size_t o = off; off += align4((elems + 1) / 2); return o; };
-    m.wa[0] = take((size_t)4 * z.Ha * m.Ka); m.wa[1] = take((size_t)4 * z.Ha * m.Ka);
-    m.wd = take((size_t)4 * z.Hd * m.Kd);
-    m.rows_a = take((size_t)2 * 2 * z.B * m.Ka); m.rows_d = take((size_t)2 * z.B * m.Kd);
-    m.total_floats = off - base;
-    return m;
-}
-
 // The status words of a pass (ChainStatus, kernels.h): the head of the forward workspace's chain region
 unsigned* status_words(const float* ws, const t2_decoder_layout& L) { return reinterpret_cast<unsigned*>(const_cast<float*>(ws) + L.chain); }
-
-// The layout carries lo planes for the split-bf16 steps: decided by (mode, switch) alone, whatever the batch size
-bool split_steps_layout() { return get_precision() == 2 && g_split_steps != 0; }
-// lo plane of an attention-LSTM shadow (w16a, w16as, wt16a, wt16as) / a decoder-LSTM shadow (w16d, wt16d), in floats
-size_t split_lo_a(const Sizes& z, size_t hi) { return hi + (size_t)4 * z.Ha * (z.Ha + z.E) / 2; }
-size_t split_lo_d(const Sizes& z, size_t hi) { return hi + (size_t)4 * z.Hd * z.Hd / 2; }
-
-void layout_of(const t2_dims& d, const Sizes& z, t2_decoder_layout* L) {
-    size_t off = 0;
-    auto take = [&](size_t n) { size_t o = off; off += align4(n); return o; };
-    const size_t BT = (size_t)z.B * z.T;
-    L->x = take(BT * z.M);
-    L->p1 = take(BT * z.P); L->p2 = take(BT * z.P); L->p1s = take(BT * z.P); L->p2s = take(BT * z.P);
-    L->pm = take((size_t)z.B * z.Tin * z.A); L->pms = take((size_t)z.B * z.Tsub * z.A);
-    L->prea = take(BT * 4 * z.Ha); L->preas = take(BT * 4 * z.Ha);
-    L->ga = take(BT * 4 * z.Ha); L->gas = take(BT * 4 * z.Ha);
-    L->cna = take(BT * z.Ha); L->cnas = take(BT * z.Ha); L->ca = take(BT * z.Ha); L->cas = take(BT * z.Ha);
-    L->din = take(BT * z.WD);
-    L->psel = take(BT * z.Tin); L->psels = take(BT * z.Tsub);
-    L->wcum = take(BT * std::max(z.Tin, kGmmPad)); L->wcums = take(BT * std::max(z.Tsub, kGmmPad));   // LSA cumulative weights / GMM means
-    L->pred = take(BT * 4 * z.Hd); L->gd = take(BT * 4 * z.Hd);
-    L->cnd = take(BT * z.Hd); L->cd = take(BT * z.Hd);
-    L->dout = take(BT * z.WO);
-    L->qs = take(BT * z.A); L->qss = take(BT * z.A);
-    L->qpart = take((size_t)2 * (z.Ha / 8) * z.B * z.A);
-    L->w1t = take((size_t)2 * z.M * z.P);
-    // bf16 shadow arena: teacher-forced passes keep [W_hh | W_ih[:,P:]] (+ transposes) per attention stream and W_hh of
-    // the decoder LSTM; the decode loop keeps whole-cell shadows and ping-pong input rows (InferShadows) in the same space
-    const size_t na = (size_t)4 * z.Ha * (z.Ha + z.E) / 2, nd = (size_t)4 * z.Hd * z.Hd / 2;      // bf16 pairs per float
-    // split-bf16 steps (mode 2 with t2_set_split_steps on): a lo plane of the same size right behind each of the six
-    // shadows; the fields name the hi planes (split_lo_a / split_lo_d give the lo plane)
-    const size_t planes = split_steps_layout() ? 2 : 1;
-    const size_t train16 = planes * (4 * na + 2 * nd), infer16 = infer_shadows(z, 0).total_floats;
-    const size_t arena = take(train16 > infer16 ? train16 : infer16);
-    L->w16a = arena; L->w16as = L->w16a + planes * na; L->w16d = L->w16as + planes * na;
-    L->wt16a = L->w16d + planes * nd; L->wt16as = L->wt16a + planes * na; L->wt16d = L->wt16as + planes * na;
-    L->din16 = take(BT * z.WD / 2 + 4); L->dh16 = take(BT * z.Hd / 2 + 4);
-    L->gemm_ws_floats = (size_t)16 << 20;                     // 64 MiB of split-K scratch
-    // split-bf16 mode: the hoisted LSTM-input products stage both operands as three bf16 terms (6 bytes per element; the
-    // decoder LSTM's takes up to all B*T rows when the chains are not overlapped), in front of the split-K partials
-    if (get_precision() == 2) {
-        const size_t wd = std::max(z.WD, z.P), h4 = (size_t)4 * std::max(z.Ha, z.Hd);
-        L->gemm_ws_floats += align4((6 * (BT + h4) * wd + 1024) / sizeof(float));
-    }
-    L->gemm_ws = take(L->gemm_ws_floats);
-    // exchange space of the persistent chain kernels (chain.hip), the pass's status words at its head
-    L->chain_floats = chain_fwd_ws_floats(z.NS, z.B, z.Ha, z.E, z.P, z.Hd, z.A);
-    L->chain = take(L->chain_floats);
-    // LSA: tanh tile and location features of every step, written by the forward chain for the backward chain (which then
-    // repeats neither the location conv nor the tile: 1.3 GB + 0.33 GB per stream at B = 64, T = 400 — HBM is what this part has)
-    const bool lsa = d.attention_kind == T2_ATTN_LSA;
-    L->usave = take(lsa ? BT * align4(z.Tin) * z.A : 0); L->usaves = take(lsa && z.NS > 1 ? BT * align4(z.Tsub) * z.A : 0);   // [T][B][A][Tin rounded up to 4]
-    L->locsave = take(lsa ? BT * z.Tin * d.loc_filters : 0); L->locsaves = take(lsa && z.NS > 1 ? BT * z.Tsub * d.loc_filters : 0);
-    L->total_floats = off;
-}
 
 // One attention stream of a pass (row 0: text, row 1: sub-word): everything that differs between the two.  stream_refs
 // fills both rows once per pass; with bwd_stream_refs it is the only place that names a *_sub field or an ...s offset.
@@ -184,21 +95,64 @@ void stream_refs(const t2_dims& d, const t2_decoder_weights& w, const Sizes& z, 
     }
 }
 
+// The LSA backward chain reads the tanh tile and the location features the forward CHAIN saved (layout.usave / locsave); a
+// workspace filled by the per-step launch path does not hold them.  Which workspaces do is kept here, per base pointer
+// (every forward pass notes its own; host-side only, no device round trip).
+std::mutex g_saved_mu;
+std::unordered_map<const void*, bool> g_saved_tiles;
+void saved_tiles_note(const void* ws, bool saved) {
+    std::lock_guard<std::mutex> lk(g_saved_mu);
+    if (g_saved_tiles.size() > 4096) g_saved_tiles.clear();
+    g_saved_tiles[ws] = saved;
+}
+bool saved_tiles_have(const void* ws) {
+    std::lock_guard<std::mutex> lk(g_saved_mu);
+    auto it = g_saved_tiles.find(ws);
+    return it != g_saved_tiles.end() && it->second;
+}
+
+// The one reader of the process and the device for a pass plan: the mode and the switches in force, for a backward pass
+// whether its forward workspace holds saved tiles (fwd_ws), and, for a pass that will run (device), chain_env() without the claim
+PassEnv pass_env_here(const void* fwd_ws, bool device) {
+    PassEnv env{get_precision(), g_split_steps != 0, g_chain != 0, g_chain_bwd != 0, g_overlap != 0, ChainEnv{0, false, false}, fwd_ws && saved_tiles_have(fwd_ws)};
+    if (device && env.chain) env.chain_env = chain_env(false);
+    return env;
+}
+// The plan of a pass here, in the style of plan_here: the pure plan first, with the claim taken for granted; the per-GPU claim
+// is asked for only once that plan has accepted a chain, so a process whose passes take no chain takes no claim.
+template <class Plan>
+auto pass_plan_here(PassEnv env, Plan plan) {
+    auto p = plan(env);
+    if (p.chain_a.on || p.chain_b.on) { env.chain_env = chain_env(true); p = plan(env); }
+    return p;
+}
+
+// The shape fields of a chain descriptor are the planned ones (ChainUse::shape); the builders below add T, the row widths and pointers
+void shape_into(const ChainShape& z, ChainDesc* d) {
+    d->kind = z.kind; d->dec = z.dec; d->NS = z.NS; d->B = z.B; d->H = z.H; d->E = z.E; d->A = z.A; d->P = z.P; d->M = z.M; d->Hd = z.Hd; d->F = z.F; d->Kc = z.Kc;
+    d->st[0].Tin = z.Tin[0]; d->st[1].Tin = z.Tin[1];
+}
+void shape_into(const ChainShape& z, ChainBwdDesc* d) {
+    d->kind = z.kind; d->NS = z.NS; d->B = z.B; d->H = z.H; d->E = z.E; d->A = z.A; d->F = z.F; d->Kc = z.Kc;
+    d->st[0].Tin = z.Tin[0]; d->st[1].Tin = z.Tin[1];
+}
+
+// A teacher-forced forward pass or a decode loop in execution: the plan, the caller's arguments, the streams' rows
 struct Dec {
-    const t2_dims& d; const t2_decoder_weights& w; Sizes z; float* ws;
-    bool training; bool prenet_dropout; bool teacher; uint64_t seed; hipStream_t s;
+    const t2_dims& d; const t2_decoder_weights& w; const DecPlan p; float* ws;
+    bool training; bool prenet_dropout; uint64_t seed; hipStream_t s;
     int max_pos;                                     // > 0: attention restricted to the first max_pos positions (ForwardAttentionV2)
-    t2_decoder_layout L{}; StreamRef st[2]{};
-    bool use16 = false;                              // bf16-operand recurrent steps (t2_set_precision(1))
-    bool split = false;                              // split-bf16 recurrent steps (use_split_steps; teacher-forced passes only)
+    const Sizes& z = p.z; const t2_decoder_layout& L = p.L; const InferShadows& I = p.I; const bool teacher = p.teacher;
+    StreamRef st[2]{};
     hipStream_t sd = nullptr;                        // stream of the decoder-LSTM chain (== s unless overlapped)
-    InferShadows I{};                                // decode loop only (teacher == false && use16)
-    bool pre16 = false; size_t w16_bytes = 0;        // teacher-forced, bf16 steps: a bf16 copy of the decoder LSTM's W_ih heads the GEMM scratch
-    bool chained = false;                            // a persistent chain ran (fwd_chains): the outputs get the abort poison
+    Dec(const Dec&) = delete;                        // (z, L, I refer to this object's plan)
     __bf16* RowA(int parity, int s) const { return reinterpret_cast<__bf16*>(ws + I.rows_a) + (size_t)(parity * 2 + s) * z.B * I.Ka; }
     __bf16* RowD(int parity) const { return reinterpret_cast<__bf16*>(ws + I.rows_d) + (size_t)parity * z.B * I.Kd; }
     float* P(size_t off) const { return ws + off; }
     __bf16* P16(size_t off) const { return reinterpret_cast<__bf16*>(ws + off); }
+    // a part of the GEMM scratch (ScratchCarve, decoder_plan.h): its address, a product working in it
+    unsigned char* scratch(size_t off) const { return reinterpret_cast<unsigned char*>(ws + L.gemm_ws) + off; }
+    GemmDesc in(const ScratchPart& part, GemmDesc m) const { m.ws = reinterpret_cast<float*>(scratch(part.off)); m.ws_bytes = part.bytes; return m; }
     long R(int t) const { return (long)t * z.B; }      // first row of step t in a time-major [T,B,*] buffer
 };
 
@@ -230,13 +184,6 @@ int prenet(const Dec& c, int s, const float* X, long ldx, int M, float* P1, floa
     T2_TRY(layer(X, ldx, r.prenet_w1, z.M, P1, r.site_p1));
     return layer(P1, ldp, r.prenet_w2, z.P, P2, r.site_p2);
 }
-
-// shape conditions of the bf16-operand and split-bf16 recurrent steps: B <= 128, recurrent widths multiples of 256
-bool step_shapes_ok(const Sizes& z) {
-    return z.B <= 128 && (z.Ha + z.E) % 256 == 0 && z.Hd % 256 == 0 && (4 * z.Ha) % 2048 == 0 && (4 * z.Hd) % 2048 == 0;
-}
-bool use_bf16_steps(const Sizes& z) { return get_precision() == 1 && step_shapes_ok(z); }       // precision mode 1
-bool use_split_steps(const Sizes& z) { return split_steps_layout() && step_shapes_ok(z); }      // mode 2 with t2_set_split_steps on
 
 // One part of a weight shadow: `rows` x `cols` of src, kept K-contiguous or transposed, as one bf16 plane or (split) as
 // hi / lo planes `lo` elements apart
@@ -305,18 +252,18 @@ int att_lstm_step(const Dec& c, int t) {
         st.idx_base = (uint32_t)(c.R(t) * z.Ha); st.idx_bstride = (uint32_t)z.Ha;       // logical [T,B,Ha]
         st.wq = r.aw->wq; st.A = z.A;
         st.qpart = c.P(L.qpart) + (size_t)s * (z.Ha / 8) * z.B * z.A;
-        if (c.use16 && !c.teacher) {                 // decode loop: [h | ctx | prenet] x [W_hh | W_ih[:,P:] | W_ih[:,:P]]
+        if (c.p.use16 && !c.teacher) {                 // decode loop: [h | ctx | prenet] x [W_hh | W_ih[:,P:] | W_ih[:,:P]]
             st.nseg = 0;
             st.x16 = c.RowA(t & 1, s); st.ldx16 = c.I.Ka; st.w16 = c.P16(c.I.wa[s]); st.ldw16 = c.I.Ka; st.k16 = c.I.Ka;
             st.h16_out = c.RowA((t + 1) & 1, s); st.ldh16 = c.I.Ka;
             st.h16_out2 = c.RowD(t & 1) + hoff; st.ldh16_2 = c.I.Kd;
-        } else if (c.use16) {                        // one K-contiguous bf16 segment [h | ctx] x [W_hh | W_ih[:,P:]]
+        } else if (c.p.use16) {                        // one K-contiguous bf16 segment [h | ctx] x [W_hh | W_ih[:,P:]]
             __bf16* D16 = c.P16(L.din16);
             st.nseg = 0;
             st.x16 = D16 + (t > 0 ? c.R(t - 1) * z.WD + hoff : 0); st.ldx16 = z.WD;
             st.w16 = c.P16(r.w16); st.ldw16 = z.Ha + z.E; st.k16 = t > 0 ? z.Ha + z.E : 0;
             st.h16_out = D16 + c.R(t) * z.WD + hoff; st.ldh16 = z.WD;
-        } else if (c.split && c.teacher) {           // the same product on fp32 rows [h | ctx] of DIN and hi / lo shadows
+        } else if (c.p.split && c.teacher) {           // the same product on fp32 rows [h | ctx] of DIN and hi / lo shadows
             st.nseg = 0;
             st.xs = DIN + (t > 0 ? c.R(t - 1) * z.WD + hoff : 0); st.ldxs = z.WD;
             st.w16 = c.P16(r.w16); st.w16lo = c.P16(split_lo_a(z, r.w16)); st.ldw16 = z.Ha + z.E; st.k16 = t > 0 ? z.Ha + z.E : 0;
@@ -362,10 +309,10 @@ int attention_step(const Dec& c, int t) {
         }
         st.ctx1 = c.P(L.din) + c.R(t) * z.WD + r.coff; st.ldctx1 = z.WD;
         st.ctx2 = c.P(L.dout) + c.R(t) * z.WO + r.ctx2off; st.ldctx2 = z.WO;
-        if (c.use16 && !c.teacher) {
+        if (c.p.use16 && !c.teacher) {
             st.ctx16 = c.RowA((t + 1) & 1, s) + z.Ha; st.ldctx16 = c.I.Ka;
             st.ctx16b = c.RowD(t & 1) + r.coff; st.ldctx16b = c.I.Kd;
-        } else if (c.use16) { st.ctx16 = c.P16(L.din16) + c.R(t) * z.WD + r.coff; st.ldctx16 = z.WD; }
+        } else if (c.p.use16) { st.ctx16 = c.P16(L.din16) + c.R(t) * z.WD + r.coff; st.ldctx16 = z.WD; }
         st.v = aw.v; st.loc_conv = aw.loc_conv; st.loc_dense = aw.loc_dense;
         st.site_noise = r.site_noise; st.mask_value = r.mask_value;
         st.idx_base = (uint32_t)(c.R(t) * Tin); st.idx_bstride = (uint32_t)Tin;          // logical [T,B,Tin]
@@ -398,17 +345,17 @@ int dec_lstm_step(const Dec& c, int t) {
     st.h_out = c.P(L.dout) + c.R(t) * z.WO; st.ldh_out = z.WO;
     st.site_h = T2_SITE_DEC_H; st.site_c = T2_SITE_DEC_C;
     st.idx_base = (uint32_t)(c.R(t) * z.Hd); st.idx_bstride = (uint32_t)z.Hd;             // logical [T,B,Hd]
-    if (c.use16 && !c.teacher) {                     // decode loop: [att_h | ctx | att_h_sub | ctx_sub | dec_h] x [W_ih | W_hh]
+    if (c.p.use16 && !c.teacher) {                     // decode loop: [att_h | ctx | att_h_sub | ctx_sub | dec_h] x [W_ih | W_hh]
         st.nseg = 0;
         st.x16 = c.RowD(t & 1); st.ldx16 = c.I.Kd; st.w16 = c.P16(c.I.wd); st.ldw16 = c.I.Kd; st.k16 = c.I.Kd;
         st.h16_out = c.RowD((t + 1) & 1) + z.WD; st.ldh16 = c.I.Kd;
-    } else if (c.use16) {
+    } else if (c.p.use16) {
         __bf16* H16 = c.P16(L.dh16);
         st.nseg = 0;
         st.x16 = H16 + (t > 0 ? c.R(t - 1) * z.Hd : 0); st.ldx16 = z.Hd;
         st.w16 = c.P16(L.w16d); st.ldw16 = z.Hd; st.k16 = t > 0 ? z.Hd : 0;
         st.h16_out = H16 + c.R(t) * z.Hd; st.ldh16 = z.Hd;
-    } else if (c.split && c.teacher) {               // fp32 dec_h rows of DOUT, hi / lo shadows of W_hh
+    } else if (c.p.split && c.teacher) {               // fp32 dec_h rows of DOUT, hi / lo shadows of W_hh
         st.nseg = 0;
         st.xs = c.P(L.dout) + (t > 0 ? c.R(t - 1) * z.WO : 0); st.ldxs = z.WO;
         st.w16 = c.P16(L.w16d); st.w16lo = c.P16(split_lo_d(z, L.w16d)); st.ldw16 = z.Hd; st.k16 = t > 0 ? z.Hd : 0;
@@ -419,19 +366,15 @@ int dec_lstm_step(const Dec& c, int t) {
     return counted(lstm_step_fwd(d, sd, &family), 0, family);
 }
 
-// Persistent-kernel descriptors of the two teacher-forced chains (chain.hip): the pointer part here, the plan (chain_plan.h)
-// from the descriptor's shape.  Returns false when the shape, mode or device is not covered: the caller then launches the
-// per-step kernels.
-bool chain_a_desc(const Dec& c, ChainDesc* out, ChainPlan* plan) {
+// Persistent-kernel descriptors of the two teacher-forced chains (chain.hip): the shape and the pointers.  Whether a chain
+// runs, and its ChainPlan, is the pass plan's (c.p.chain_a / chain_b): a builder is called for a chain that is on.
+ChainDesc chain_a_desc(const Dec& c) {
     const Sizes& z = c.z; const t2_decoder_layout& L = c.L;
-    if (!c.use16 || !c.teacher) return false;
-    if (c.d.attention_kind != T2_ATTN_SMA && c.d.attention_kind != T2_ATTN_LSA) return false;
     ChainDesc d{};
-    d.NS = z.NS; d.B = z.B; d.T = z.T; d.H = z.Ha; d.E = z.E; d.A = z.A; d.WD = z.WD; d.WO = z.WO;
-    d.P = z.P; d.Hd = z.Hd;                                           // (read by the plan's exchange-space layout only: dec = 0)
+    shape_into(c.p.chain_a.shape, &d);
+    d.T = z.T; d.WD = z.WD; d.WO = z.WO;
     d.din = c.P(L.din); d.din16 = c.P16(L.din16); d.dout = c.P(L.dout);
-    d.kind = c.d.attention_kind == T2_ATTN_SMA ? CHAIN_SMA : CHAIN_LSA;
-    d.F = c.d.loc_filters; d.Kc = c.d.loc_kernel; d.max_pos = c.max_pos;
+    d.max_pos = c.max_pos;
     d.drop_p = c.training ? c.d.p_att_dropout : 0.f;
     d.noise_std = (c.training && d.kind == CHAIN_SMA) ? 2.0f : 0.f;
     d.seed = c.seed;
@@ -444,7 +387,7 @@ bool chain_a_desc(const Dec& c, ChainDesc* out, ChainPlan* plan) {
         st.gates = c.P(r.ga); st.c_new = c.P(r.cna); st.c_out = c.P(r.ca);
         st.h_out = c.P(L.din) + hoff; st.ldh = z.WD; st.h16_out = c.P16(L.din16) + hoff; st.ldh16 = z.WD;
         st.coff = r.coff; st.ctx2off = r.ctx2off;
-        st.pm = c.P(r.pm); st.memory = r.memory; st.lengths = r.lengths; st.Tin = r.Tin;
+        st.pm = c.P(r.pm); st.memory = r.memory; st.lengths = r.lengths;
         st.align = r.align; st.psel = c.P(r.psel); st.wcum = c.P(r.wcum);
         st.qs = c.P(r.qs);
         st.v = aw.v; st.loc_conv = aw.loc_conv; st.loc_dense = aw.loc_dense;
@@ -452,48 +395,37 @@ bool chain_a_desc(const Dec& c, ChainDesc* out, ChainPlan* plan) {
         st.site_h = r.site_h; st.site_c = r.site_c; st.site_noise = r.site_noise;
         st.mask_value = r.mask_value;
     }
-    *plan = plan_here(plan_chain_fwd, chain_shape_of(d, L.chain_floats * sizeof(float)));
-    if (plan->refusal != CHAIN_OK) return false;
     d.err = status_words(c.ws, L) + CHAIN_STATUS_FWD_ATT;
-    *out = d;
-    return true;
+    return d;
 }
-bool chain_b_desc(const Dec& c, ChainDesc* out, ChainPlan* plan) {
+ChainDesc chain_b_desc(const Dec& c) {
     const Sizes& z = c.z; const t2_decoder_layout& L = c.L;
-    if (!c.use16 || !c.teacher) return false;
     ChainDesc d{};
-    d.NS = 1; d.B = z.B; d.T = z.T; d.H = z.Hd; d.E = 0; d.A = 0; d.WD = z.WD; d.WO = z.WO;
-    d.kind = CHAIN_LSTM;
+    shape_into(c.p.chain_b.shape, &d);
+    d.T = z.T; d.WD = z.WD; d.WO = z.WO;
     d.drop_p = c.training ? c.d.p_dec_dropout : 0.f;
     d.seed = c.seed;
     ChainStream& st = d.st[0];
     st.w16 = c.P16(L.w16d); st.ldw16 = z.Hd; st.pre = c.P(L.pred);
     st.gates = c.P(L.gd); st.c_new = c.P(L.cnd); st.c_out = c.P(L.cd);
     st.h_out = c.P(L.dout); st.ldh = z.WO; st.h16_out = c.P16(L.dh16); st.ldh16 = z.Hd;
-    st.site_h = T2_SITE_DEC_H; st.site_c = T2_SITE_DEC_C; st.Tin = 4;
-    *plan = plan_here(plan_chain_fwd, chain_shape_of(d, L.chain_floats * sizeof(float)));
-    if (plan->refusal != CHAIN_OK) return false;
+    st.site_h = T2_SITE_DEC_H; st.site_c = T2_SITE_DEC_C;
     d.err = status_words(c.ws, L) + CHAIN_STATUS_FWD_LSTM;
-    *out = d;
-    return true;
+    return d;
 }
 
 // Persistent decode loop (chain.hip, dec mode): every phase of Decoder.inference's step inside one launch per step range
-bool chain_dec_desc(const Dec& c, const t2_decoder_infer_args& a, ChainDesc* out, ChainPlan* plan) {
+ChainDesc chain_dec_desc(const Dec& c, const t2_decoder_infer_args& a) {
     const Sizes& z = c.z; const t2_decoder_layout& L = c.L; const t2_decoder_weights& w = c.w;
-    if (!c.use16 || z.NS != 2) return false;
-    if (c.d.attention_kind != T2_ATTN_SMA && c.d.attention_kind != T2_ATTN_LSA) return false;
     ChainDesc d{};
-    d.dec = 1; d.P = z.P; d.M = z.M; d.Hd = z.Hd;
-    d.NS = z.NS; d.B = z.B; d.T = z.T; d.H = z.Ha; d.E = z.E; d.A = z.A; d.WD = z.WD; d.WO = z.WO;
-    d.kind = c.d.attention_kind == T2_ATTN_SMA ? CHAIN_SMA : CHAIN_LSA;
-    d.F = c.d.loc_filters; d.Kc = c.d.loc_kernel; d.max_pos = c.max_pos;
+    shape_into(c.p.chain_a.shape, &d);
+    d.T = z.T; d.WD = z.WD; d.WO = z.WO; d.max_pos = c.max_pos;
     d.drop_p = 0.f; d.noise_std = 0.f; d.seed = c.seed;                 // inference runs in eval mode (inference.py:263)
     for (int s = 0; s < z.NS; ++s) {
         ChainStream& st = d.st[s]; const StreamRef& r = c.st[s];
         const t2_attention_weights& aw = *r.aw;
         st.w16 = c.P16(c.I.wa[s]); st.ldw16 = c.I.Ka; st.wq = aw.wq;
-        st.pm = c.P(r.pm); st.memory = r.memory; st.lengths = r.lengths; st.Tin = r.Tin;
+        st.pm = c.P(r.pm); st.memory = r.memory; st.lengths = r.lengths;
         st.align = r.align; st.wcum = c.P(r.wcum);
         st.v = aw.v; st.loc_conv = aw.loc_conv; st.loc_dense = aw.loc_dense;
         st.site_h = r.site_h; st.site_c = r.site_c; st.site_noise = r.site_noise;
@@ -508,11 +440,8 @@ bool chain_dec_desc(const Dec& c, const t2_decoder_infer_args& a, ChainDesc* out
     d.mel_out = a.mel_out; d.ldmel = (long)z.T * z.M; d.gate_out = a.gate_out; d.ldgate = z.T;
     d.thr = a.gate_threshold; d.stop_index = a.stop_index; d.done = a.done_count;
     d.pdrop = c.prenet_dropout ? c.d.p_prenet_dropout : 0.f;
-    *plan = plan_here(plan_chain_fwd, chain_shape_of(d, L.chain_floats * sizeof(float)));
-    if (plan->refusal != CHAIN_OK) return false;
     d.err = status_words(c.ws, L) + CHAIN_STATUS_FWD_ATT;
-    *out = d;
-    return true;
+    return d;
 }
 
 // mel / gate projection (model.py:382-388); permute_tb: rows come time-major, outputs are [B,T,*]
@@ -545,52 +474,6 @@ __global__ void init_stop_kernel(int32_t* stop_index, int32_t* done, int B) {
 }
 
 // ------------------------------------------------------------------------------- backward
-// SMA attention backward: two workgroups per (item, stream) when one each would leave CUs idle
-int attn_bwd_nsplit(const t2_dims& d, const Sizes& z) {
-    return (d.attention_kind == T2_ATTN_SMA && z.B * z.NS <= 128 && std::min(z.Tin, z.NS == 2 ? z.Tsub : z.Tin) >= 16) ? 2 : 1;
-}
-
-void bwd_layout_of(const t2_dims& d, const Sizes& z, t2_decoder_bwd_layout* L) {
-    size_t off = 0;
-    auto take = [&](size_t n) { size_t o = off; off += align4(n); return o; };
-    const size_t BT = (size_t)z.B * z.T;
-    const int ksd = lstm_bwd_ksplit(4 * z.Hd), ksa = lstm_bwd_ksplit(4 * z.Ha);
-    L->ddout = take(BT * z.WO); L->ddin = take(BT * z.WD);
-    L->dgd = take(BT * 4 * z.Hd); L->dga = take(BT * 4 * z.Ha); L->dgas = take(BT * 4 * z.Ha);
-    L->dctx = take(BT * z.E); L->dctxs = take(BT * z.E);
-    L->dq = take(BT * 2 * z.A); L->dqs = take(BT * 2 * z.A);              // rows [2][A]: one partial per position split
-    L->dv = take((size_t)2 * z.B * z.A); L->dvs = take((size_t)2 * z.B * z.A);
-    L->dpm = take((size_t)z.B * z.Tin * z.A); L->dpms = take((size_t)z.B * z.Tsub * z.A);
-    L->carry = take((size_t)2 * z.B * z.Tin); L->carrys = take((size_t)2 * z.B * z.Tsub);   // ping-pong by step parity
-    const bool lsa = d.attention_kind == T2_ATTN_LSA;          // LSA: cumulative-weight carry + per-item location-layer gradients
-    const bool gmm = d.attention_kind == T2_ATTN_GMM;          // GMM: mean carry [B,8] + per-item db2 [B,16] / dW2 [B,3K*A]
-    const bool dca = d.attention_kind == T2_ATTN_DCA;          // DCA: all per-item accumulators in one block (dldense)
-    // (LSA: two rows per item — the persistent backward chain keeps one accumulator per position split)
-    const size_t ncv = lsa ? (size_t)2 * z.B * d.loc_filters * 2 * d.loc_kernel : gmm ? (size_t)z.B * 16 : 0;
-    const size_t nds = lsa ? (size_t)2 * z.B * z.A * d.loc_filters : gmm ? (size_t)z.B * 3 * kGmmK * z.A : dca ? (size_t)z.B * dca_acc_floats(z.A) : 0;
-    L->carryc = take(lsa ? (size_t)z.B * z.Tin : gmm ? (size_t)z.B * kGmmPad : 0); L->carrycs = take(lsa ? (size_t)z.B * z.Tsub : gmm ? (size_t)z.B * kGmmPad : 0);
-    L->dlconv = take(ncv); L->dlconvs = take(ncv); L->dldense = take(nds); L->dldenses = take(nds);
-    L->dcd = take((size_t)z.B * z.Hd); L->dca = take((size_t)z.B * z.Ha); L->dcas = take((size_t)z.B * z.Ha);
-    L->partd = take((size_t)ksd * z.B * z.Hd);
-    L->parta = take((size_t)2 * ksa * z.B * (z.E + z.Ha));
-    L->dp2 = take(BT * z.P); L->dp2s = take(BT * z.P); L->dp1 = take(BT * z.P);
-    L->dmel_t = take(BT * z.M); L->dgate_t = take(BT);
-    L->dg16a = take((size_t)2 * z.B * 4 * z.Ha / 2 + 4); L->dg16d = take((size_t)z.B * 4 * z.Hd / 2 + 4);
-    L->colsum_ws = take((size_t)64 * 4 * (z.Ha > z.Hd ? z.Ha : z.Hd));
-    L->gemm_ws_floats = (size_t)192 << 20;                    // 768 MiB: split-K partials + bf16 operand staging (gemm.hip)
-    // split-bf16 mode: the largest weight-gradient product (dW_ih of an LSTM: K = B*T rows of dG [4H] and of its input
-    // [WD]) stages 6 bytes per operand element; 256 MiB stay for its split-K partials
-    if (get_precision() == 2) {
-        const size_t h4 = (size_t)4 * std::max(z.Ha, z.Hd), need = 6 * BT * (h4 + z.WD) + ((size_t)256 << 20);
-        L->gemm_ws_floats = std::max(L->gemm_ws_floats, align4(need / sizeof(float)));
-    }
-    L->gemm_ws = take(L->gemm_ws_floats);
-    // exchange space of the persistent backward chains (chain_bwd.hip); their status words are in the forward workspace
-    L->chain_floats = chain_bwd_ws_floats(lsa ? CHAIN_LSA : CHAIN_SMA, z.NS, z.B, z.Ha, z.E, z.A, d.loc_filters, d.loc_kernel, z.Hd);
-    L->chain = take(L->chain_floats);
-    L->total_floats = off;
-}
-
 // Backward row of a stream (bwd_stream_refs): its gradient outputs and its offsets in the backward workspace
 struct BwdStreamRef {
     const t2_lstm_grads* lg; const t2_attention_grads* ag; float *prenet_w1, *prenet_w2;
@@ -610,7 +493,7 @@ void bwd_stream_refs(const t2_decoder_grads& g, const t2_decoder_bwd_args& a, co
     }
 }
 
-// bf16 mode: ONE row-major bf16 copy of dG ([B*T][H4], `off` bytes into the GEMM scratch) serves every product that reads
+// bf16 mode: ONE row-major bf16 copy of dG ([B*T][H4], the dg16 part of a ScratchCarve) serves every product that reads
 // dG: as the k-major A operand of a weight gradient (whose dG rows start row0 rows in) or as the K-contiguous A operand of
 // an input gradient; either then works in the scratch behind the copy.  on == false: no copy, descriptors pass untouched.
 struct Dg16 {
@@ -623,27 +506,27 @@ struct Dg16 {
     GemmDesc igrad(GemmDesc m, long row0) const { return operand(m, row0, 0); }
 };
 
+// A backward pass in execution: the plan, the caller's arguments, the streams' rows, and what the stages hand on
 struct Bwd {
-    const t2_dims& d; const t2_decoder_weights& w; const t2_decoder_grads& g; const t2_decoder_bwd_args& a;
-    Sizes z; t2_decoder_layout L; t2_decoder_bwd_layout BL; hipStream_t s;
+    const t2_dims& d; const t2_decoder_weights& w; const t2_decoder_grads& g; const t2_decoder_bwd_args& a; const BwdPlan p; hipStream_t s;
+    const Sizes& z = p.z; const t2_decoder_layout& L = p.L; const t2_decoder_bwd_layout& BL = p.BL;
     const float* W(size_t off) const { return a.ws + off; }
     float* S(size_t off) const { return a.bws + off; }
     long R(int t) const { return (long)t * z.B; }
-    bool use16 = false;
-    bool split = false;                              // split-bf16 recurrent-input gradients (use_split_steps)
     hipStream_t sd = nullptr;                        // stream of the decoder-LSTM chain (== s unless overlapped)
     const __bf16* W16(size_t off) const { return reinterpret_cast<const __bf16*>(a.ws + off); }
     __bf16* S16(size_t off) const { return reinterpret_cast<__bf16*>(a.bws + off); }
-    float* gemm_ws() const { return a.bws + BL.gemm_ws; }
-    size_t gemm_ws_bytes() const { return BL.gemm_ws_floats * sizeof(float); }
+    // a part of the GEMM scratch (ScratchCarve, decoder_plan.h): its address, a product working in it, a carve's dG copy
+    unsigned char* scratch(size_t off) const { return reinterpret_cast<unsigned char*>(a.bws + BL.gemm_ws) + off; }
+    GemmDesc in(const ScratchPart& part, GemmDesc m) const { m.ws = reinterpret_cast<float*>(scratch(part.off)); m.ws_bytes = part.bytes; return m; }
+    Dg16 dg16(const ScratchCarve& cv, int H4) const {
+        return Dg16{cv.dg16.bytes != 0, reinterpret_cast<__bf16*>(scratch(cv.dg16.off)), H4, reinterpret_cast<float*>(scratch(cv.rest.off)), cv.rest.bytes};
+    }
     StreamRef st[2]{}; BwdStreamRef bst[2]{};
-    // the reverse-time chains of this pass (bwd_chains): persistent descriptors, side stream, next free event slot
-    ChainBwdDesc cab{}, cbb{}; ChainPlan pab{}, pbb{}; bool chain_a = false, chain_b = false;
-    Side* side = nullptr; bool overlap = false; size_t ne = 0;
-    // defer: the leaf tail stays on the side stream when the entry point returns (t2_decoder_bwd_args.defer_weight_grads).
-    // With the attention chain persistent the decoder-LSTM weight gradients wait for that fork too: bwd_chains leaves
-    // their dG copy (dgd16; dgd16_staged = already filled) instead of issuing them in front of chain A.
-    bool defer = false; Dg16 dgd16{}; bool dgd16_staged = false;
+    // the reverse-time chains of this pass (bwd_chains): descriptors of the persistent ones, side stream, next free event slot
+    ChainBwdDesc cab{}, cbb{};
+    Side* side = nullptr; size_t ne = 0;
+    Bwd(const Bwd&) = delete;                        // (z, L, BL refer to this object's plan)
 };
 
 // C[M,N] = X[M,K] . W[K,N]   (W row-major with leading dimension ldw: "NN")
@@ -652,16 +535,7 @@ GemmDesc matmul_nn(const float* X, long ldx, const float* W, long ldw, float* Y,
 }
 // C[M,N] = G[K,M]^T . X[K,N]   (weight gradients: K = B*T rows)
 GemmDesc matmul_tn(const Bwd& c, const float* G, long ldg, const float* X, long ldx, float* Y, long ldy, int M, int N, int K) {
-    GemmDesc g = product(G, 1, ldg, X, 1, ldx, Y, ldy, M, N, K);
-    g.ws = c.gemm_ws(); g.ws_bytes = c.gemm_ws_bytes();
-    return g;
-}
-
-size_t dg16_bytes(const Sizes& z, int H4) { return ((size_t)H4 * z.B * z.T * sizeof(__bf16) + 255) & ~(size_t)255; }
-Dg16 dg16_carve(const Bwd& c, bool on, size_t off, int H4) {
-    unsigned char* const at = reinterpret_cast<unsigned char*>(c.gemm_ws()) + off;
-    const size_t bytes = dg16_bytes(c.z, H4);
-    return Dg16{on, reinterpret_cast<__bf16*>(at), H4, reinterpret_cast<float*>(at + bytes), c.gemm_ws_bytes() - off - bytes};
+    return c.in(c.p.scratch.whole(), product(G, 1, ldg, X, 1, ldx, Y, ldy, M, N, K));
 }
 
 int dec_bwd_step(const Bwd& c, int t) {
@@ -680,7 +554,7 @@ int dec_bwd_step(const Bwd& c, int t) {
     st.dg = c.S(c.BL.dgd) + c.R(t) * 4 * z.Hd; st.lddg = 4 * z.Hd;
     st.site_h = T2_SITE_DEC_H; st.site_c = T2_SITE_DEC_C;
     st.idx_base = (uint32_t)(c.R(t) * z.Hd); st.idx_bstride = (uint32_t)z.Hd;
-    if (c.use16) st.dg16 = c.S16(c.BL.dg16d);
+    if (c.p.use16) st.dg16 = c.S16(c.BL.dg16d);
     hipStream_t sd = c.sd ? c.sd : c.s;
     { ProfScope ps(PK_LSTM_DEC_BWD_PW, sd); T2_TRY(lstm_bwd_pointwise(p, sd)); }
     if (t == 0) return 0;
@@ -689,19 +563,19 @@ int dec_bwd_step(const Bwd& c, int t) {
     g.st[0].dg = st.dg; g.st[0].lddg = st.lddg;
     g.st[0].seg[0] = LstmBwdSeg{c.w.dec.w_hh, (long)z.Hd, z.Hd}; g.st[0].nseg = 1;
     g.st[0].part = c.S(c.BL.partd);
-    if (c.use16) { g.st[0].dg16 = c.S16(c.BL.dg16d); g.st[0].wt16 = c.W16(c.L.wt16d); }
-    else if (c.split) { g.st[0].wt16 = c.W16(c.L.wt16d); g.st[0].wt16lo = c.W16(split_lo_d(z, c.L.wt16d)); }
+    if (c.p.use16) { g.st[0].dg16 = c.S16(c.BL.dg16d); g.st[0].wt16 = c.W16(c.L.wt16d); }
+    else if (c.p.split) { g.st[0].wt16 = c.W16(c.L.wt16d); g.st[0].wt16lo = c.W16(split_lo_d(z, c.L.wt16d)); }
     ProfScope ps(PK_LSTM_DEC_BWD_GEMM, sd);
     int family = 0;
     return counted(lstm_bwd_gemm(g, sd, &family), 3, family);
 }
 
-// Persistent BPTT of the decoder LSTM (chain_bwd.hip); false = not covered, per-step launches instead
-bool chain_b_bwd_desc(const Bwd& c, ChainBwdDesc* out, ChainPlan* plan) {
+// Persistent BPTT of the decoder LSTM (chain_bwd.hip): shape and pointers, for a chain the plan has on (c.p.chain_b)
+ChainBwdDesc chain_b_bwd_desc(const Bwd& c) {
     const Sizes& z = c.z;
-    if (!c.use16) return false;
     ChainBwdDesc d{};
-    d.NS = 1; d.B = z.B; d.T = z.T; d.H = z.Hd; d.kind = CHAIN_LSTM;
+    shape_into(c.p.chain_b.shape, &d);
+    d.T = z.T;
     d.drop_p = c.a.training ? c.d.p_dec_dropout : 0.f; d.seed = c.a.seed;
     ChainBwdStream& st = d.st[0];
     st.wt16 = c.W16(c.L.wt16d); st.ldwt = 4 * z.Hd;
@@ -710,38 +584,17 @@ bool chain_b_bwd_desc(const Bwd& c, ChainBwdDesc* out, ChainPlan* plan) {
     st.dg = c.S(c.BL.dgd); st.dc_state = c.S(c.BL.dcd);
     st.dbias_part = c.S(c.BL.partd);                                 // (the launch path's K-split scratch: idle when the chain runs) [MT][4Hd]
     st.site_h = T2_SITE_DEC_H; st.site_c = T2_SITE_DEC_C;
-    *plan = plan_here(plan_chain_bwd, chain_shape_of(d, c.BL.chain_floats * sizeof(float)));
-    if (plan->refusal != CHAIN_OK) return false;
     d.err = status_words(c.a.ws, c.L) + CHAIN_STATUS_BWD_LSTM;
-    *out = d;
-    return true;
+    return d;
 }
 
-// The LSA backward chain reads the tanh tile and the location features the forward CHAIN saved (layout.usave / locsave); a
-// workspace filled by the per-step launch path does not hold them.  Which workspaces do is kept here, per base pointer
-// (every forward pass notes its own; host-side only, no device round trip).
-std::mutex g_saved_mu;
-std::unordered_map<const void*, bool> g_saved_tiles;
-void saved_tiles_note(const void* ws, bool saved) {
-    std::lock_guard<std::mutex> lk(g_saved_mu);
-    if (g_saved_tiles.size() > 4096) g_saved_tiles.clear();
-    g_saved_tiles[ws] = saved;
-}
-bool saved_tiles_have(const void* ws) {
-    std::lock_guard<std::mutex> lk(g_saved_mu);
-    auto it = g_saved_tiles.find(ws);
-    return it != g_saved_tiles.end() && it->second;
-}
-
-// Persistent BPTT of the attention chain (both attention LSTMs + SMA attention); false = not covered
-bool chain_a_bwd_desc(const Bwd& c, ChainBwdDesc* out, ChainPlan* plan) {
+// Persistent BPTT of the attention chain (both attention LSTMs + SMA or LSA attention), for a chain the plan has on (c.p.chain_a)
+ChainBwdDesc chain_a_bwd_desc(const Bwd& c) {
     const Sizes& z = c.z;
     const bool lsa = c.d.attention_kind == T2_ATTN_LSA;
-    if (!c.use16 || !(lsa || (c.d.attention_kind == T2_ATTN_SMA && attn_bwd_nsplit(c.d, z) == 2))) return false;
-    if (lsa && !saved_tiles_have(c.a.ws)) return false;              // forward ran on the launch path: its workspace has no tanh tile
     ChainBwdDesc d{};
-    d.NS = z.NS; d.B = z.B; d.T = z.T; d.H = z.Ha; d.E = z.E; d.A = z.A; d.kind = lsa ? CHAIN_LSA : CHAIN_SMA;
-    d.F = c.d.loc_filters; d.Kc = c.d.loc_kernel;
+    shape_into(c.p.chain_a.shape, &d);
+    d.T = z.T;
     d.drop_p = c.a.training ? c.d.p_att_dropout : 0.f; d.seed = c.a.seed;
     for (int s = 0; s < z.NS; ++s) {
         ChainBwdStream& st = d.st[s]; const StreamRef& r = c.st[s]; const BwdStreamRef& b = c.bst[s];
@@ -755,7 +608,7 @@ bool chain_a_bwd_desc(const Bwd& c, ChainBwdDesc* out, ChainPlan* plan) {
         st.dctx_a = c.S(c.BL.ddout) + r.ctx2off; st.lddctx_a = z.WO;
         st.dctx_b = c.S(c.BL.ddin) + r.coff; st.lddctx_b = z.WD;
         st.dalign = b.d_align;
-        st.qs = c.W(r.qs); st.pm = c.W(r.pm); st.memory = r.memory; st.Tin = r.Tin;
+        st.qs = c.W(r.qs); st.pm = c.W(r.pm); st.memory = r.memory;
         st.psel = c.W(r.psel); st.align = r.align;
         st.v = aw.v; st.wq = aw.wq;
         st.dctx_out = c.S(b.dctx); st.dq_out = c.S(b.dq);
@@ -766,11 +619,8 @@ bool chain_a_bwd_desc(const Bwd& c, ChainBwdDesc* out, ChainPlan* plan) {
             st.dconv_acc = c.S(b.dlconv); st.ddense_acc = c.S(b.dldense);
         }
     }
-    *plan = plan_here(plan_chain_bwd, chain_shape_of(d, c.BL.chain_floats * sizeof(float)));
-    if (plan->refusal != CHAIN_OK) return false;
     d.err = status_words(c.a.ws, c.L) + CHAIN_STATUS_BWD_ATT;
-    *out = d;
-    return true;
+    return d;
 }
 
 int att_bwd_step(const Bwd& c, int t) {
@@ -783,7 +633,7 @@ int att_bwd_step(const Bwd& c, int t) {
     ab.nstreams = z.NS; ab.B = z.B; ab.A = z.A; ab.E = z.E; ab.first = first;
     const int abi_kind = c.d.attention_kind;
     ab.kind = kernel_kind(abi_kind); ab.F = c.d.loc_filters; ab.Kc = c.d.loc_kernel;
-    ab.nsplit = attn_bwd_nsplit(c.d, z);
+    ab.nsplit = c.p.nsplit;
     for (int s = 0; s < z.NS; ++s) {
         AttnBwdStream& st = ab.st[s]; const StreamRef& r = c.st[s]; const BwdStreamRef& b = c.bst[s];
         const int Tin = r.Tin;
@@ -846,7 +696,7 @@ int att_bwd_step(const Bwd& c, int t) {
         st.dg = c.S(b.dg) + c.R(t) * 4 * z.Ha; st.lddg = 4 * z.Ha;
         st.site_h = r.site_h; st.site_c = r.site_c;
         st.idx_base = (uint32_t)(c.R(t) * z.Ha); st.idx_bstride = (uint32_t)z.Ha;
-        if (c.use16) st.dg16 = c.S16(c.BL.dg16a) + (size_t)s * z.B * 4 * z.Ha;
+        if (c.p.use16) st.dg16 = c.S16(c.BL.dg16a) + (size_t)s * z.B * 4 * z.Ha;
     }
     { ProfScope ps(PK_LSTM_ATT_BWD_PW, c.s); T2_TRY(lstm_bwd_pointwise(p, c.s)); }
     if (t == 0) return 0;
@@ -861,39 +711,20 @@ int att_bwd_step(const Bwd& c, int t) {
         g.st[s].seg[1] = LstmBwdSeg{lw.w_hh, (long)z.Ha, z.Ha};
         g.st[s].nseg = 2;
         g.st[s].part = c.S(c.BL.parta) + (size_t)s * ks * z.B * NC;
-        if (c.use16) { g.st[s].dg16 = c.S16(c.BL.dg16a) + (size_t)s * z.B * 4 * z.Ha; g.st[s].wt16 = c.W16(r.wt16); }
-        else if (c.split) { g.st[s].wt16 = c.W16(r.wt16); g.st[s].wt16lo = c.W16(split_lo_a(z, r.wt16)); }
+        if (c.p.use16) { g.st[s].dg16 = c.S16(c.BL.dg16a) + (size_t)s * z.B * 4 * z.Ha; g.st[s].wt16 = c.W16(r.wt16); }
+        else if (c.p.split) { g.st[s].wt16 = c.W16(r.wt16); g.st[s].wt16lo = c.W16(split_lo_a(z, r.wt16)); }
     }
     ProfScope ps(PK_LSTM_ATT_BWD_GEMM, c.s);
     int family = 0;
     return counted(lstm_bwd_gemm(g, c.s, &family), 3, family);
 }
 
-// Step ranges handed from one chain to the other.  One range when the chains share a stream; otherwise about eight,
-// with short ranges (16, 32 steps) at the END of time: that is where the forward pass's decoder-LSTM chain finishes
-// after the attention chain, and where the backward pass's attention chain waits for the first decoder-LSTM range,
-// so whatever the last range holds is exposed.  Even boundaries keep rows-per-range a multiple of 128 at B = 64.
-std::vector<int> chunk_bounds(int T, bool overlap) {
-    std::vector<int> b{0};
-    if (!overlap) { b.push_back(T); return b; }
-    const int CH = std::max(16, (T + 7) / 8);
-    std::vector<int> tail;
-    int rem = T;
-    for (int s = 16; s < CH && rem - s >= CH; s *= 2) { tail.push_back(s); rem -= s; }
-    const int n = std::max(1, rem / CH);
-    for (int i = 1; i < n; ++i) {
-        const int e = (int)((long)rem * i / n) & ~1;
-        if (e > b.back()) b.push_back(e);
-    }
-    b.push_back(rem);
-    for (auto it = tail.rbegin(); it != tail.rend(); ++it) b.push_back(b.back() + *it);
-    return b;
-}
-
-// An aborted chain must not pass for data: NaN over the pass's outputs when one of its first `nwords` status words is set
-int poison_if_aborted(const Dec& c, int nwords, float* mel_out, float* gate_out) {
+// An aborted chain must not pass for data: NaN over the pass's outputs when one of the status words of its chains
+// (the first c.p.poison_words) is set; nothing for a pass without a chain
+int poison_if_aborted(const Dec& c, float* mel_out, float* gate_out) {
     const size_t BT = (size_t)c.z.B * c.z.T;
-    hipLaunchKernelGGL(poison_if_aborted_kernel, dim3(64), dim3(256), 0, c.s, status_words(c.ws, c.L), nwords, mel_out, BT * c.z.M, gate_out, BT);
+    if (!c.p.poison_words) return 0;
+    hipLaunchKernelGGL(poison_if_aborted_kernel, dim3(64), dim3(256), 0, c.s, status_words(c.ws, c.L), c.p.poison_words, mel_out, BT * c.z.M, gate_out, BT);
     T2_LAUNCH_CHECK();
     return 0;
 }
@@ -903,7 +734,7 @@ int poison_if_aborted(const Dec& c, int nwords, float* mel_out, float* gate_out)
 int fwd_prologue(const Dec& c, const float* mels) {
     const Sizes& z = c.z; const t2_decoder_layout& L = c.L;
     const int BT = z.B * z.T;
-    if (c.use16 || c.split) T2_TRY(cast_shadows(c, c.split));
+    if (c.p.use16 || c.p.split) T2_TRY(cast_shadows(c, c.p.split));
     // teacher inputs and both prenets over all frames (model.py:407-413)
     T2_TRY(teacher_inputs(mels, c.P(L.x), z.B, z.M, z.T, c.s));
     for (int s = 0; s < z.NS; ++s) T2_TRY(prenet(c, s, c.P(L.x), z.M, BT, c.P(c.st[s].p1), c.P(c.st[s].p2), z.P, 0, 0));      // rows time-major: (t,b)
@@ -912,10 +743,9 @@ int fwd_prologue(const Dec& c, const float* mels) {
         const StreamRef& r = c.st[s];
         GemmDesc g = linear(c.P(r.p2), z.P, r.lw->w_ih, z.P + z.E, c.P(r.prea), 4 * z.Ha, BT, 4 * z.Ha, z.P);
         g.bias1 = r.lw->b_ih; g.bias2 = r.lw->b_hh;
-        g.ws = c.P(L.gemm_ws); g.ws_bytes = L.gemm_ws_floats * sizeof(float);       // bf16 staging (gemm.hip)
-        T2_TRY(gemm(g, c.s));
+        T2_TRY(gemm(c.in(c.p.scratch.whole(), g), c.s));                              // bf16 staging (gemm.hip)
     }
-    if (c.pre16) T2_TRY(stage_bf16(c.w.dec.w_ih, true, z.WD, c.P16(L.gemm_ws), 4 * z.Hd, z.WD, c.s));
+    if (c.p.pre16) T2_TRY(stage_bf16(c.w.dec.w_ih, true, z.WD, reinterpret_cast<__bf16*>(c.scratch(c.p.scratch.w_ih16.off)), 4 * z.Hd, z.WD, c.s));
     return 0;
 }
 
@@ -928,19 +758,16 @@ int fwd_prologue(const Dec& c, const float* mels) {
 // run back to back on the caller's stream: A over all steps, one input GEMM, B over all steps.
 int fwd_chains(Dec& c) {
     const Sizes& z = c.z; const t2_decoder_layout& L = c.L;
-    ChainDesc ca{}, cb{}; ChainPlan pa{}, pb{};
-    const bool chain_a = g_chain && chain_a_desc(c, &ca, &pa);
-    // (a pass whose attention-chain tiling has no kernel instance takes the per-step launches as a whole, the decoder LSTM
-    //  included: its bits are then those of a pass with the chains off.  Before the plan existed such a pass failed.)
-    const bool chain_b = g_chain && pa.refusal != CHAIN_REFUSE_NO_INSTANCE && chain_b_desc(c, &cb, &pb);
-    c.chained = chain_a || chain_b;
-    saved_tiles_note(c.ws, chain_a && ca.kind == CHAIN_LSA);
-    // status words always (0 = OK / not used); the tagged exchange buffers (zero state of step -1) when a chain runs
-    T2_TRY(chain_fwd_ws_clear(c.P(L.chain), L.chain_floats, c.chained ? CHAIN_WS_TEACHER : CHAIN_WS_STATUS, c.s));
+    const bool chain_a = c.p.chain_a.on, chain_b = c.p.chain_b.on, overlap = c.p.overlap;
+    const ChainPlan &pa = c.p.chain_a.plan, &pb = c.p.chain_b.plan;
+    const std::vector<int>& bounds = c.p.bounds;
+    ChainDesc ca{}, cb{};
+    if (chain_a) ca = chain_a_desc(c);
+    if (chain_b) cb = chain_b_desc(c);
+    saved_tiles_note(c.ws, c.p.saves_tiles);
+    T2_TRY(chain_fwd_ws_clear(c.P(L.chain), L.chain_floats, c.p.clear, c.s));
     Side* side = nullptr;
-    const bool overlap = g_overlap && z.T >= 32 && !c.chained;
     if (overlap) { T2_TRY(side_get(&side)); c.sd = side->s; }
-    const std::vector<int> bounds = chunk_bounds(z.T, overlap);
     size_t ne = 0;
     for (size_t ci = 0; ci + 1 < bounds.size(); ++ci) {
         const int t0 = bounds[ci], t1 = bounds[ci + 1];
@@ -959,13 +786,11 @@ int fwd_chains(Dec& c) {
         GemmDesc g = linear(c.P(L.din) + c.R(t0) * z.WD, z.WD, c.w.dec.w_ih, z.WD, c.P(L.pred) + c.R(t0) * 4 * z.Hd, 4 * z.Hd,
                             (t1 - t0) * z.B, 4 * z.Hd, z.WD);
         g.bias1 = c.w.dec.b_ih; g.bias2 = c.w.dec.b_hh;
-        g.ws = c.P(L.gemm_ws); g.ws_bytes = L.gemm_ws_floats * sizeof(float);       // chain A launches no GEMM: the scratch is chain B's
-        if (c.pre16) {
+        if (c.p.pre16) {
             g.A16 = c.P16(L.din16) + c.R(t0) * z.WD; g.lda16 = z.WD;
-            g.B16 = c.P16(L.gemm_ws); g.ldb16 = z.WD;
-            g.ws = reinterpret_cast<float*>(reinterpret_cast<unsigned char*>(g.ws) + c.w16_bytes); g.ws_bytes -= c.w16_bytes;
+            g.B16 = reinterpret_cast<const __bf16*>(c.scratch(c.p.scratch.w_ih16.off)); g.ldb16 = z.WD;
         }
-        T2_TRY(gemm(g, sb));
+        T2_TRY(gemm(c.in(c.p.scratch.rest, g), sb));                                  // chain A launches no GEMM: the scratch is chain B's
         if (chain_b) {
             cb.t0 = t0; cb.t1 = t1;
             ProfScope ps(PK_CHAIN_B_FWD, sb);
@@ -982,7 +807,7 @@ int fwd_chains(Dec& c) {
 int fwd_outputs(const Dec& c, float* mel_out, float* gate_out) {
     const Sizes& z = c.z;
     T2_TRY(projection(c, c.P(c.L.dout), z.WO, z.B * z.T, mel_out, z.M, gate_out, 1, true));
-    return c.chained ? poison_if_aborted(c, CHAIN_STATUS_FWD_LSTM + 1, mel_out, gate_out) : 0;
+    return poison_if_aborted(c, mel_out, gate_out);
 }
 
 // ------------------------------------------------------------------------------- backward, stage by stage
@@ -1011,23 +836,23 @@ int bwd_projections(const Bwd& c) {
     return colsum(dgate, 1, BT, 1, c.g.gate_b, nullptr, cws, c.s);
 }
 
-// Decoder-LSTM weight gradients.  They need nothing from chain A: they run on chain B's stream `sb` once its
-// recurrence is done, underneath the rest of chain A (whose launches leave most CUs idle); next to a persistent chain A
-// there is nothing to run under, and with a deferred tail they join it on the side stream (t2_decoder_backward).
-// staged: the chunk loop has already filled the shared bf16 copy of dG.
-int bwd_dec_lstm_wgrads(const Bwd& c, const Dg16& dg, bool staged, hipStream_t sb) {
+// Decoder-LSTM weight gradients on stream `sb`.  They need nothing from chain A; where they are issued is the plan's
+// (BwdPlan::dec_wgrads): in the step-range loop on chain B's stream, or with a deferred tail on the side stream.
+// dec_wgrads_staged: the step-range loop has already filled the shared bf16 copy of dG.
+int bwd_dec_lstm_wgrads(const Bwd& c, hipStream_t sb) {
     const Sizes& z = c.z; const t2_decoder_layout& L = c.L;
     const int BT = z.B * z.T;
     const float* DG = c.S(c.BL.dgd);
-    if (dg.on && !staged) T2_TRY(stage_bf16(DG, true, 4 * z.Hd, dg.p, BT, 4 * z.Hd, sb));
+    const Dg16 dg = c.dg16(c.p.scratch, 4 * z.Hd);
+    if (dg.on && !c.p.dec_wgrads_staged) T2_TRY(stage_bf16(DG, true, 4 * z.Hd, dg.p, BT, 4 * z.Hd, sb));
     // dW_ih = dG^T . DIN (bf16 steps: the forward pass left DIN's bf16 shadow) ; recurrent half: dW_hh = dG^T . dec_h(t-1)
     GemmDesc mih = dg.wgrad(matmul_tn(c, DG, 4 * z.Hd, c.W(L.din), z.WD, c.g.dec.w_ih, z.WD, 4 * z.Hd, z.WD, BT), 0);
-    if (dg.on && c.use16) { mih.B16 = c.W16(L.din16); mih.ldb16 = z.WD; mih.b16_kmajor = 1; }
+    if (dg.on && c.p.use16) { mih.B16 = c.W16(L.din16); mih.ldb16 = z.WD; mih.b16_kmajor = 1; }
     T2_TRY(gemm(mih, sb));
     // h(t-1) pairs with dG(t): drop the first step's rows of dG and the last step's rows of dec_h
     if (z.T > 1) T2_TRY(gemm(dg.wgrad(matmul_tn(c, DG + (long)z.B * 4 * z.Hd, 4 * z.Hd, c.W(L.dout), z.WO, c.g.dec.w_hh, z.Hd, 4 * z.Hd, z.Hd, BT - z.B), z.B), sb));
     else T2_TRY(fill_f32(c.g.dec.w_hh, 0.f, (size_t)4 * z.Hd * z.Hd, sb));
-    if (c.chain_b) {                                                  // the chain summed dG over steps and rows: add the row tiles
+    if (c.p.chain_b.on) {                                             // the chain summed dG over steps and rows: add the row tiles
         T2_TRY(batch_sum(c.cbb.st[0].dbias_part, (z.B + 31) / 32, 4 * z.Hd, c.g.dec.b_ih, sb));
         T2_CHECK_HIP(hipMemcpyAsync(c.g.dec.b_hh, c.g.dec.b_ih, (size_t)4 * z.Hd * sizeof(float), hipMemcpyDeviceToDevice, sb));
     } else T2_TRY(colsum(DG, 4 * z.Hd, BT, 4 * z.Hd, c.g.dec.b_ih, c.g.dec.b_hh, c.S(c.BL.colsum_ws), sb));
@@ -1040,63 +865,45 @@ int bwd_dec_lstm_wgrads(const Bwd& c, const Dg16& dg, bool staged, hipStream_t s
 // Persistent chains (chain_bwd.hip): a persistent grid needs the whole device, and two of them must never be in flight
 // together, so with the attention chain persistent everything runs on the caller's stream, one step range per chain.
 int bwd_chains(Bwd& c) {
-    const Sizes& z = c.z; const t2_decoder_bwd_layout& BL = c.BL;
-    const int BT = z.B * z.T;
-    c.chain_a = g_chain && g_chain_bwd && chain_a_bwd_desc(c, &c.cab, &c.pab);
-    c.overlap = g_overlap && z.T >= 32 && !c.chain_a;
-    if (c.overlap) {
+    const Sizes& z = c.z; const t2_decoder_bwd_layout& BL = c.BL; const BwdPlan& p = c.p;
+    const std::vector<int>& bounds = p.bounds;
+    if (p.chain_a.on) c.cab = chain_a_bwd_desc(c);
+    if (p.chain_b.on) c.cbb = chain_b_bwd_desc(c);
+    if (p.overlap) {
         T2_TRY(side_get(&c.side)); c.sd = c.side->s;
         T2_TRY(stream_edge(*c.side, c.ne++, c.s, c.side->s));           // fork: dDOUT is complete
     }
-    const std::vector<int> bounds = chunk_bounds(z.T, c.overlap);
-    const hipStream_t sb = c.overlap ? c.side->s : c.s;
+    const hipStream_t sb = p.overlap ? c.side->s : c.s;
     const float* DGd = c.S(BL.dgd);
-    // bf16 mode: W_ih^T ([WD][4Hd], K contiguous) is staged once at the head of the scratch for all dDIN chunks
-    unsigned char* const ws8 = reinterpret_cast<unsigned char*>(c.gemm_ws());
-    const size_t wt_bytes = ((size_t)4 * z.Hd * z.WD * sizeof(__bf16) + 255) & ~(size_t)255;
-    const bool pre16 = get_precision() == 1 && (4 * z.Hd) % 64 == 0 && z.WD % 64 == 0 && c.gemm_ws_bytes() > 2 * wt_bytes;
-    if (pre16) T2_TRY(stage_bf16(c.w.dec.w_ih, false, z.WD, reinterpret_cast<__bf16*>(ws8), z.WD, 4 * z.Hd, sb));
-    // bf16 mode: the shared bf16 copy of dG ([BT][4Hd], behind W_ih^T) serves both of its consumers: the dDIN product of
-    // each chunk and the two weight-gradient products (the shifted one starts B rows in)
-    const size_t dg16_off = pre16 ? wt_bytes : 0;
-    const bool share = get_precision() == 1 && BT % 64 == 0 && z.B % 8 == 0 && (4 * z.Hd) % 128 == 0 && z.T > 1 &&
-                       c.gemm_ws_bytes() >= dg16_off + dg16_bytes(z, 4 * z.Hd) + ((size_t)z.WD * BT * sizeof(__bf16) + 256);
-    const Dg16 dg = dg16_carve(c, share, dg16_off, 4 * z.Hd);
-    bool chunk_cast = share && pre16;                                     // cast chunk by chunk, in front of each dDIN product
-    for (size_t ci = 1; ci < bounds.size(); ++ci) if (((bounds[ci] - bounds[ci - 1]) * z.B) % 64 != 0) chunk_cast = false;
-    // (next to per-step launches of the attention chain a persistent decoder-LSTM grid only takes CUs away from them:
-    //  measured 24.8 -> 26.3 ms; it runs when the attention chain is persistent too)
-    c.chain_b = c.chain_a && chain_b_bwd_desc(c, &c.cbb, &c.pbb);
+    // bf16 mode: W_ih^T ([WD][4Hd], K contiguous) is staged once at the head of the scratch for all dDIN ranges; the shared
+    // bf16 copy of dG behind it serves the dDIN product of each range and the two weight-gradient products
+    __bf16* const wt16 = reinterpret_cast<__bf16*>(c.scratch(p.scratch.w_ih16.off));
+    if (p.pre16) T2_TRY(stage_bf16(c.w.dec.w_ih, false, z.WD, wt16, z.WD, 4 * z.Hd, sb));
+    const Dg16 dg = c.dg16(p.scratch, 4 * z.Hd);
     for (size_t ci = bounds.size() - 1; ci > 0; --ci) {
         const int t0 = bounds[ci - 1], t1 = bounds[ci];
-        if (c.chain_b) {
+        if (p.chain_b.on) {
             c.cbb.t0 = t0; c.cbb.t1 = t1;
             ProfScope ps(PK_CHAIN_B_BWD, sb);
-            T2_TRY(chain_bwd(c.cbb, c.pbb, c.S(BL.chain), BL.chain_floats, sb));
+            T2_TRY(chain_bwd(c.cbb, p.chain_b.plan, c.S(BL.chain), BL.chain_floats, sb));
         } else {
             for (int t = t1 - 1; t >= t0; --t) T2_TRY(dec_bwd_step(c, t));
         }
         GemmDesc dd = matmul_nn(DGd + c.R(t0) * 4 * z.Hd, 4 * z.Hd, c.w.dec.w_ih, z.WD, c.S(BL.ddin) + c.R(t0) * z.WD, z.WD,
                                 (t1 - t0) * z.B, z.WD, 4 * z.Hd);
-        dd.ws = c.gemm_ws(); dd.ws_bytes = c.gemm_ws_bytes();             // between fork and join the scratch is chain B's
-        if (pre16) {
-            dd.B16 = reinterpret_cast<const __bf16*>(ws8); dd.ldb16 = 4 * z.Hd;
-            dd.ws = reinterpret_cast<float*>(ws8 + wt_bytes); dd.ws_bytes -= wt_bytes;
-        }
-        if (chunk_cast) {
+        dd = c.in(p.ddin_ws, dd);                                         // between fork and join the scratch is chain B's
+        if (p.pre16) { dd.B16 = wt16; dd.ldb16 = 4 * z.Hd; }
+        if (p.chunk_cast) {                                               // dG of the range cast in front of its dDIN product
             T2_TRY(stage_bf16(DGd + c.R(t0) * 4 * z.Hd, true, 4 * z.Hd, dg.p + c.R(t0) * 4 * z.Hd, (t1 - t0) * z.B, 4 * z.Hd, sb));
             dd = dg.igrad(dd, c.R(t0));
         }
         T2_TRY(gemm(dd, sb));
-        if (c.overlap) T2_TRY(stream_edge(*c.side, c.ne++, sb, c.s));
-        // (persistent chain A and a deferred tail: they go on the side stream after the fork, t2_decoder_backward; chain A
-        //  writes nothing into the GEMM scratch, so the bf16 copy of dG is still there)
-        if (t0 == 0 && c.chain_a && c.defer) { c.dgd16 = dg; c.dgd16_staged = chunk_cast; }
-        else if (t0 == 0) T2_TRY(bwd_dec_lstm_wgrads(c, dg, chunk_cast, sb));
-        if (c.chain_a) {
+        if (p.overlap) T2_TRY(stream_edge(*c.side, c.ne++, sb, c.s));
+        if (t0 == 0 && p.dec_wgrads == WGRADS_CHAIN_B) T2_TRY(bwd_dec_lstm_wgrads(c, sb));
+        if (p.chain_a.on) {
             c.cab.t0 = t0; c.cab.t1 = t1;
             ProfScope ps(PK_CHAIN_A_BWD, c.s);
-            T2_TRY(chain_bwd(c.cab, c.pab, c.S(BL.chain), BL.chain_floats, c.s));
+            T2_TRY(chain_bwd(c.cab, p.chain_a.plan, c.S(BL.chain), BL.chain_floats, c.s));
         } else {
             for (int t = t1 - 1; t >= t0; --t) T2_TRY(att_bwd_step(c, t));
         }
@@ -1120,11 +927,9 @@ int bwd_stream_tail(const Bwd& c, int s, hipStream_t ts) {
     // the head of the scratch) is the k-major A operand of the three weight-gradient products (the shifted ones start
     // B rows in) and the K-contiguous A operand of the prenet's input gradient below; the ctx / h operands are read
     // from DIN's bf16 shadow where the forward pass left one
-    const bool share = get_precision() == 1 && BT % 64 == 0 && z.B % 8 == 0 && (4 * z.Ha) % 128 == 0 && z.T > 1 &&
-                       c.gemm_ws_bytes() >= 2 * dg16_bytes(z, 4 * z.Ha);
-    const Dg16 dg = dg16_carve(c, share, 0, 4 * z.Ha);
-    if (share) T2_TRY(stage_bf16(DG, true, 4 * z.Ha, dg.p, BT, 4 * z.Ha, ts));
-    const __bf16* DIN16 = share && c.use16 ? c.W16(L.din16) : nullptr;
+    const Dg16 dg = c.dg16(c.p.tail_scratch, 4 * z.Ha);
+    if (dg.on) T2_TRY(stage_bf16(DG, true, 4 * z.Ha, dg.p, BT, 4 * z.Ha, ts));
+    const __bf16* DIN16 = dg.on && c.p.use16 ? c.W16(L.din16) : nullptr;
     auto dw_gemm = [&](const float* G, long row0, const float* X, const __bf16* X16, long ldx, float* Y, long ldy, int N, int K) -> int {
         GemmDesc m = dg.wgrad(matmul_tn(c, G, 4 * z.Ha, X, ldx, Y, ldy, 4 * z.Ha, N, K), row0);
         if (X16) { m.B16 = X16; m.ldb16 = ldx; m.b16_kmajor = 1; }
@@ -1141,14 +946,13 @@ int bwd_stream_tail(const Bwd& c, int s, hipStream_t ts) {
         T2_TRY(gemm(zc, ts));
         T2_TRY(fill_f32(lg.w_hh, 0.f, (size_t)4 * z.Ha * z.Ha, ts));
     }
-    if (c.chain_a) {
+    if (c.p.chain_a.on) {
         T2_TRY(batch_sum(c.cab.st[s].dbias_part, (z.B + 31) / 32, 4 * z.Ha, lg.b_ih, ts));
         T2_CHECK_HIP(hipMemcpyAsync(lg.b_hh, lg.b_ih, (size_t)4 * z.Ha * sizeof(float), hipMemcpyDeviceToDevice, ts));
     } else T2_TRY(colsum(DG, 4 * z.Ha, BT, 4 * z.Ha, lg.b_ih, lg.b_hh, cws, ts));
     // prenet (model.py:13-24): dP2 = dG . W_ih[:, :P] ; through ReLU+dropout ; layer 2 ; layer 1
     const float scale = c.a.prenet_dropout ? 1.0f / (1.0f - c.d.p_prenet_dropout) : 1.0f;
-    GemmDesc gp = matmul_nn(DG, 4 * z.Ha, r.lw->w_ih, ldw, dP2, z.P, BT, z.P, 4 * z.Ha);
-    gp.ws = c.gemm_ws(); gp.ws_bytes = c.gemm_ws_bytes();
+    const GemmDesc gp = c.in(c.p.tail_scratch.whole(), matmul_nn(DG, 4 * z.Ha, r.lw->w_ih, ldw, dP2, z.P, BT, z.P, 4 * z.Ha));
     T2_TRY(gemm(dg.igrad(gp, 0), ts));
     T2_TRY(relu_drop_bwd(dP2, P2, dP2, scale, (size_t)BT * z.P, ts));
     T2_TRY(gemm(matmul_tn(c, dP2, z.P, P1, z.P, b.prenet_w2, z.P, z.P, z.P, BT), ts));
@@ -1156,8 +960,8 @@ int bwd_stream_tail(const Bwd& c, int s, hipStream_t ts) {
     T2_TRY(relu_drop_bwd(dP1, P1, dP1, scale, (size_t)BT * z.P, ts));
     T2_TRY(gemm(matmul_tn(c, dP1, z.P, c.W(L.x), z.M, b.prenet_w1, z.M, z.P, z.M, BT), ts));
     // attention parameters
-    const bool lsa_chain = c.chain_a && c.cab.kind == CHAIN_LSA;        // the persistent LSA backward: one partial per position split
-    const int nsp = lsa_chain ? 2 : attn_bwd_nsplit(c.d, z);
+    const bool lsa_chain = c.p.lsa_chain;                             // the persistent LSA backward: one partial per position split
+    const int nsp = c.p.dq_parts;
     float* DQ = c.S(b.dq);
     if (nsp == 2) T2_TRY(fold_halves(DQ, BT, z.A, ts));               // dq row = partial 0 + partial 1
     T2_TRY(gemm(matmul_tn(c, DQ, 2 * z.A, DIN + hoff, z.WD, ag.wq, z.Ha, z.A, z.Ha, BT), ts));
@@ -1169,8 +973,8 @@ int bwd_stream_tail(const Bwd& c, int s, hipStream_t ts) {
         T2_REQUIRE(ag.mlp_b1 && ag.mlp_w2 && ag.loc_conv && ag.loc_dense && ag.dca_T && ag.dca_bT && ag.v, "t2_decoder_backward: DCA gradient buffers missing");
         T2_TRY(colsum(DQ, 2 * z.A, BT, z.A, ag.mlp_b1, nullptr, cws, ts));
         const size_t na = dca_acc_floats(z.A);
-        float* full = c.gemm_ws();                                   // [na] floats of the split-K scratch (idle here)
-        T2_REQUIRE(na * sizeof(float) <= c.gemm_ws_bytes(), "t2_decoder_backward: scratch too small");
+        float* full = reinterpret_cast<float*>(c.scratch(0));        // [na] floats of the split-K scratch (idle here)
+        T2_REQUIRE(c.p.dca_acc_fits, "t2_decoder_backward: scratch too small");
         T2_TRY(batch_sum(c.S(b.dldense), z.B, (int)na, full, ts));
         auto cp = [&](float* dst, size_t off, size_t n) { return hipMemcpyAsync(dst, full + off, n * sizeof(float), hipMemcpyDeviceToDevice, ts); };
         size_t off = 0;
@@ -1226,7 +1030,7 @@ int t2_decoder_layout_query(const t2_dims* dims_in, int B, int T, int Tin, int T
     t2_dims d; int max_pos = 0;
     T2_TRY(entry_dims(*dims_in, &d, &max_pos));
     T2_REQUIRE(B >= 1 && B <= 256 && T >= 1 && Tin >= 1 && Tsub >= 1, "bad shape B=%d T=%d Tin=%d Tsub=%d", B, T, Tin, Tsub);
-    layout_of(d, sizes_of(d, B, T, Tin, Tsub), out);
+    layout_of(d, sizes_of(d, B, T, Tin, Tsub), pass_env_here(nullptr, false), out);
     return 0;
 }
 
@@ -1236,17 +1040,13 @@ int t2_decoder_forward(const t2_dims* dims_in, const t2_decoder_weights* w, cons
     T2_TRY(entry_dims(*dims_in, &d, &max_pos));
     T2_REQUIRE(a->B >= 1 && a->B <= 256 && a->T >= 1, "bad shape B=%d T=%d", a->B, a->T);
     T2_REQUIRE((long)a->B * a->T * 4 * d.att_rnn_dim < (1l << 32), "B*T too large for 32-bit RNG indices");
-    Dec c{d, *w, sizes_of(d, a->B, a->T, a->Tin, a->Tsub), a->ws, a->training != 0, a->prenet_dropout != 0, true, a->seed, (hipStream_t)stream, max_pos};
-    layout_of(d, c.z, &c.L);
-    stream_refs(d, *w, c.z, c.L, a->memory, a->memory_sub, a->mem_lengths, a->sub_lengths, a->align, a->align_sub, c.st);
-    const Sizes& z = c.z;
     T2_REQUIRE(a->phase >= 0 && a->phase <= 2, "t2_decoder_forward: phase must be 0, 1 or 2");
-    c.use16 = use_bf16_steps(z);
-    c.split = use_split_steps(z);
-    // bf16 steps keep a bf16 shadow of every DIN row (din16): with one bf16 copy of W_ih at the head of the scratch the
-    // decoder-LSTM input GEMMs of the chains read both operands as bf16 and stage nothing
-    c.w16_bytes = ((size_t)4 * z.Hd * z.WD * sizeof(__bf16) + 255) & ~(size_t)255;
-    c.pre16 = c.use16 && (4 * z.Hd) % 64 == 0 && z.WD % 64 == 0 && c.L.gemm_ws_floats * sizeof(float) > c.w16_bytes;
+    const Sizes z = sizes_of(d, a->B, a->T, a->Tin, a->Tsub);
+    PassEnv env = pass_env_here(nullptr, true);
+    if (a->phase == 1) env.chain = false;                           // the prologue alone launches no chain: it asks for none (and for no claim)
+    Dec c{d, *w, pass_plan_here(env, [&](const PassEnv& e) { return plan_decoder_fwd(d, z, e); }), a->ws, a->training != 0, a->prenet_dropout != 0,
+          a->seed, (hipStream_t)stream, max_pos};
+    stream_refs(d, *w, c.z, c.L, a->memory, a->memory_sub, a->mem_lengths, a->sub_lengths, a->align, a->align_sub, c.st);
     if (a->phase != 2) {
         T2_TRY(fwd_prologue(c, a->mels));
         if (a->phase == 1) return 0;
@@ -1261,7 +1061,7 @@ int t2_decoder_bwd_layout_query(const t2_dims* dims_in, int B, int T, int Tin, i
     t2_dims d; int max_pos = 0;
     T2_TRY(entry_dims(*dims_in, &d, &max_pos));
     T2_REQUIRE(B >= 1 && B <= 256 && T >= 1 && Tin >= 1 && Tsub >= 1, "bad shape B=%d T=%d Tin=%d Tsub=%d", B, T, Tin, Tsub);
-    bwd_layout_of(d, sizes_of(d, B, T, Tin, Tsub), out);
+    bwd_layout_of(d, sizes_of(d, B, T, Tin, Tsub), pass_env_here(nullptr, false), out);
     return 0;
 }
 
@@ -1270,35 +1070,80 @@ int t2_decoder_backward(const t2_dims* dims_in, const t2_decoder_weights* w, con
     T2_REQUIRE(dims_in && w && g && a, "null argument");
     t2_dims d; int max_pos = 0;
     T2_TRY(entry_dims(*dims_in, &d, &max_pos));
-    Bwd c{d, *w, *g, *a, sizes_of(d, a->B, a->T, a->Tin, a->Tsub), {}, {}, (hipStream_t)stream};
-    layout_of(d, c.z, &c.L);
-    bwd_layout_of(d, c.z, &c.BL);
+    const Sizes z = sizes_of(d, a->B, a->T, a->Tin, a->Tsub);
+    Bwd c{d, *w, *g, *a, pass_plan_here(pass_env_here(a->ws, true), [&](const PassEnv& e) { return plan_decoder_bwd(d, z, e, a->defer_weight_grads != 0); }), (hipStream_t)stream};
     // (no lengths: the masks are in the saved alignments, which this pass only reads)
     stream_refs(d, *w, c.z, c.L, a->memory, a->memory_sub, nullptr, nullptr, const_cast<float*>(a->align), const_cast<float*>(a->align_sub), c.st);
     bwd_stream_refs(*g, *a, c.BL, c.bst);
-    c.use16 = use_bf16_steps(c.z);                 // must match the forward pass (the shadows live in its workspace)
-    c.split = use_split_steps(c.z);                // likewise
-    c.defer = g_overlap && c.z.T >= 32 && a->defer_weight_grads != 0;
     T2_TRY(bwd_projections(c));
     T2_TRY(bwd_chains(c));
     // ---- after the chains.  Only d(memory) feeds the caller's next backward nodes (the encoders); every weight gradient
     // is a leaf.  defer_weight_grads: the weight-gradient tail stays on the side stream, un-joined, underneath the
     // encoders' backward — the caller joins with t2_side_join() before it reads a gradient or releases a workspace.
-    // The decoder-LSTM weight gradients are there too: queued by the launch path's chain B, or (persistent chains: no
-    // side stream until here) issued now, ahead of the tails, whose dG copy at the head of the scratch overwrites theirs.
-    // Otherwise: join here, one stream.
+    // The decoder-LSTM weight gradients are there too: queued by the launch path's chain B, or (WGRADS_TAIL: persistent
+    // chains, no side stream until here) issued now, ahead of the tails, whose dG copy at the head of the scratch
+    // overwrites theirs.  Otherwise: join here, one stream.
     hipStream_t ts = c.s;                                                // stream of the weight-gradient tail
-    if (c.defer) {
+    if (c.p.tail_on_side) {
         if (!c.side) T2_TRY(side_get(&c.side));
         T2_TRY(stream_edge(*c.side, c.ne++, c.s, c.side->s));           // chain A is complete: dG, dq, d(pm) of every step
         ts = c.side->s;
-        if (c.chain_a) T2_TRY(bwd_dec_lstm_wgrads(c, c.dgd16, c.dgd16_staged, ts));
-    } else if (c.overlap) {
+        if (c.p.dec_wgrads == WGRADS_TAIL) T2_TRY(bwd_dec_lstm_wgrads(c, ts));
+    } else if (c.p.overlap) {
         T2_TRY(stream_edge(*c.side, c.ne++, c.side->s, c.s));           // join (split-K scratch and colsum scratch are shared)
     }
     for (int s = 0; s < c.z.NS; ++s) T2_TRY(bwd_stream_dmemory(c, s));
     for (int s = 0; s < c.z.NS; ++s) T2_TRY(bwd_stream_tail(c, s, ts));
-    ++g_defer_counts[c.defer ? 0 : 1];
+    ++g_defer_counts[c.p.defer ? 0 : 1];
+    return 0;
+}
+
+// The plan of a pass for an explicit environment, in the ABI's terms: pure, no device, no claim
+static t2_pass_chain pass_chain_info(const ChainUse& u) {
+    t2_pass_chain o{};
+    o.asked = u.asked; o.on = u.on; o.reason = u.plan.refusal;
+    o.reason_text = !u.asked ? "not asked for" : chain_refusal_text(u.plan.refusal);
+    if (u.on) { o.instance = u.plan.instance; o.instance_name = chain_instance_name(u.plan.instance); o.grid = u.plan.grid; }
+    return o;
+}
+static t2_scratch_carve carve_info(const ScratchCarve& c) {
+    return t2_scratch_carve{c.w_ih16.off, c.w_ih16.bytes, c.dg16.off, c.dg16.bytes, c.rest.off, c.rest.bytes, c.total};
+}
+static int bounds_info(const std::vector<int>& b, t2_decoder_pass_plan_info* o) {
+    T2_REQUIRE(b.size() <= T2_PASS_MAX_BOUNDS, "t2_decoder_pass_plan: %zu step-range bounds", b.size());
+    o->nbounds = (int)b.size();
+    std::copy(b.begin(), b.end(), o->bounds);
+    return 0;
+}
+int t2_decoder_pass_plan(const t2_dims* dims_in, int pass, int B, int T, int Tin, int Tsub, const t2_pass_env* e, int defer_weight_grads,
+                         int poll_every, t2_decoder_pass_plan_info* out) {
+    T2_REQUIRE(dims_in && e && out && pass >= T2_PASS_FORWARD && pass <= T2_PASS_INFER, "t2_decoder_pass_plan: null argument or bad pass");
+    t2_dims d; int max_pos = 0;
+    T2_TRY(entry_dims(*dims_in, &d, &max_pos));
+    T2_REQUIRE(B >= 1 && B <= 256 && T >= 1 && Tin >= 1 && Tsub >= 1, "bad shape B=%d T=%d Tin=%d Tsub=%d", B, T, Tin, Tsub);
+    const PassEnv env{e->precision, e->split_steps != 0, e->chain != 0, e->chain_bwd != 0, e->overlap != 0,
+                      ChainEnv{e->cus, e->claimed != 0, e->no_resident != 0}, e->saved_tiles != 0};
+    const Sizes z = sizes_of(d, B, T, Tin, Tsub);
+    t2_decoder_pass_plan_info o{};
+    if (pass == T2_PASS_BACKWARD) {
+        const BwdPlan p = plan_decoder_bwd(d, z, env, defer_weight_grads != 0);
+        o.layout = p.L; o.bwd_layout = p.BL; o.use16 = p.use16; o.split = p.split; o.pre16 = p.pre16;
+        o.scratch = carve_info(p.scratch); o.chain_a = pass_chain_info(p.chain_a); o.chain_b = pass_chain_info(p.chain_b);
+        o.chained = p.chain_a.on || p.chain_b.on; o.overlap = p.overlap;
+        T2_TRY(bounds_info(p.bounds, &o));
+        o.defer = p.defer; o.share = p.share; o.chunk_cast = p.chunk_cast; o.ddin_ws_off = p.ddin_ws.off; o.ddin_ws_bytes = p.ddin_ws.bytes;
+        o.dec_wgrads = p.dec_wgrads; o.dec_wgrads_staged = p.dec_wgrads_staged; o.tail_on_side = p.tail_on_side;
+        o.tail_share = p.tail_share; o.tail_scratch = carve_info(p.tail_scratch);
+        o.nsplit = p.nsplit; o.lsa_chain = p.lsa_chain; o.dq_parts = p.dq_parts;
+    } else {
+        const DecPlan p = pass == T2_PASS_FORWARD ? plan_decoder_fwd(d, z, env) : plan_decoder_infer(d, z, env, poll_every);
+        o.layout = p.L; o.use16 = p.use16; o.split = p.split; o.pre16 = p.pre16;
+        o.scratch = carve_info(p.scratch); o.chain_a = pass_chain_info(p.chain_a); o.chain_b = pass_chain_info(p.chain_b);
+        o.chained = p.chained; o.clear = p.clear; o.saves_tiles = p.saves_tiles; o.overlap = p.overlap;
+        T2_TRY(bounds_info(p.bounds, &o));
+        o.poison_words = p.poison_words; o.poll = p.poll; o.shadow_floats = p.I.total_floats;
+    }
+    *out = o;
     return 0;
 }
 
@@ -1307,21 +1152,20 @@ int t2_decoder_infer(const t2_dims* dims_in, const t2_decoder_weights* w, const 
     t2_dims d; int max_pos = 0;
     T2_TRY(entry_dims(*dims_in, &d, &max_pos));
     T2_REQUIRE(a->B >= 1 && a->B <= 256 && a->max_steps >= 1, "bad shape B=%d max_steps=%d", a->B, a->max_steps);
-    Dec c{d, *w, sizes_of(d, a->B, a->max_steps, a->Tin, a->Tsub), a->ws, false, a->prenet_dropout != 0, false, a->seed, (hipStream_t)stream, max_pos};
-    layout_of(d, c.z, &c.L);
+    const Sizes zs = sizes_of(d, a->B, a->max_steps, a->Tin, a->Tsub);
+    Dec c{d, *w, pass_plan_here(pass_env_here(nullptr, true), [&](const PassEnv& e) { return plan_decoder_infer(d, zs, e, a->poll_every); }), a->ws, false,
+          a->prenet_dropout != 0, a->seed, (hipStream_t)stream, max_pos};
     stream_refs(d, *w, c.z, c.L, a->memory, a->memory_sub, a->mem_lengths, a->sub_lengths, a->align, a->align_sub, c.st);
     const Sizes& z = c.z; const t2_decoder_layout& L = c.L;
-    const int T = z.T;
-    int poll = a->poll_every > 0 ? a->poll_every : 16;
+    const int T = z.T, poll = c.p.poll;
+    const bool chain = c.p.chained;
 
     hipLaunchKernelGGL(init_stop_kernel, dim3((z.B + 63) / 64), dim3(64), 0, c.s, a->stop_index, a->done_count, z.B);
     T2_LAUNCH_CHECK();
     T2_TRY(processed_memory(c));
     for (int s = 0; s < z.NS; ++s)                                   // W1 [P,M] -> [M,P]: coalesced thread-per-output reads
         T2_TRY(permute_rows(c.st[s].prenet_w1, c.P(L.w1t) + (size_t)s * z.M * z.P, z.P, z.M, 1, c.s));
-    c.I = infer_shadows(z, L.w16a);
-    c.use16 = get_precision() == 1 && z.B <= 128 && c.I.Ka % 256 == 0 && c.I.Kd % 256 == 0;
-    if (c.use16) {
+    if (c.p.use16) {
         const long ldi = z.P + z.E;
         for (int s = 0; s < z.NS; ++s) {
             const t2_lstm_weights& lw = *c.st[s].lw;
@@ -1356,7 +1200,7 @@ int t2_decoder_infer(const t2_dims* dims_in, const t2_decoder_weights* w, const 
             d.site1[s] = r.site_p1; d.site2[s] = r.site_p2;
         }
         d.ldp = z.P;
-        if (c.use16) { for (int s = 0; s < z.NS; ++s) d.p2_16[s] = c.RowA(tn & 1, s) + z.Ha + z.E; d.ldp16 = c.I.Ka; }
+        if (c.p.use16) { for (int s = 0; s < z.NS; ++s) d.p2_16[s] = c.RowA(tn & 1, s) + z.Ha + z.E; d.ldp16 = c.I.Ka; }
         d.drop_p = c.prenet_dropout ? c.d.p_prenet_dropout : 0.f; d.seed = c.seed;
         d.drop_base = (uint32_t)(c.R(tn) * z.P); d.drop_mstride = (uint32_t)z.P;      // logical [T,B,P]
         return step_tail(d, c.s);
@@ -1364,18 +1208,16 @@ int t2_decoder_infer(const t2_dims* dims_in, const t2_decoder_weights* w, const 
     int steps = 0;
     StopPoll* pl = nullptr;
     T2_TRY(stop_poll_get(&pl));
-    ChainDesc cdec{}; ChainPlan pdec{};
-    const bool chain = g_chain && chain_dec_desc(c, *a, &cdec, &pdec);
-    if (chain && a->poll_every <= 0) poll = 32;                      // one persistent launch per polling interval: 32 steps amortise its start-up
-    // status words always; with the chain its whole exchange space (zero state of step -1: h, ctx, dec_h, go-frame prenet = 0)
-    T2_TRY(chain_fwd_ws_clear(c.P(L.chain), L.chain_floats, chain ? CHAIN_WS_DECODE : CHAIN_WS_STATUS, c.s));
+    ChainDesc cdec{};
+    if (chain) cdec = chain_dec_desc(c, *a);
+    T2_TRY(chain_fwd_ws_clear(c.P(L.chain), L.chain_floats, c.p.clear, c.s));
     if (!chain) T2_TRY(tail(0, false));                              // prenet of the go frame (model.py:444-450)
     for (int t = 0; t < T; ++t) {
         if (chain) {
             if (t % poll == 0) {                                     // one persistent launch per polling interval
                 cdec.t0 = t; cdec.t1 = std::min(T, t + poll);
                 ProfScope ps(PK_CHAIN_DEC, c.s);
-                T2_TRY(chain_fwd(cdec, pdec, c.P(L.chain), L.chain_floats, c.s));
+                T2_TRY(chain_fwd(cdec, c.p.chain_a.plan, c.P(L.chain), L.chain_floats, c.s));
             }
         } else {
             T2_TRY(att_lstm_step(c, t));
@@ -1400,7 +1242,7 @@ int t2_decoder_infer(const t2_dims* dims_in, const t2_decoder_weights* w, const 
         }
     }
     *a->steps_run_host = steps;
-    return chain ? poison_if_aborted(c, CHAIN_STATUS_FWD_ATT + 1, a->mel_out, a->gate_out) : 0;
+    return poison_if_aborted(c, a->mel_out, a->gate_out);
 }
 
 }  // extern "C"
