@@ -729,6 +729,103 @@ typedef struct t2_stft_synthesis_args {
 } t2_stft_synthesis_args;
 int t2_stft_synthesis(const t2_stft_synthesis_args* a, void* stream);
 
+/* ---- WaveGlow inference (mel spectrogram -> waveform) ------------------------------------------------
+ * Replaces the reference's glow.py: WaveGlow.infer (:251-293), WN.forward (:153-175) and
+ * Invertible1x1Conv.forward(reverse=True) (:88-97), as inference.py:160-170 and best_checkpoint.py:179-189 call them and as
+ * bias_remover.py:38-74 (waveglowBiasRemover) does.  torch's [B, C, L] layout, time contiguous; always exact fp32 on the
+ * matrix cores, whatever t2_set_precision says.  No atomics, a fixed order for every sum: bit-identical from run to run
+ * and for an item alone or inside a batch.  Ordinary launches on `stream`.  Inference only, fp32 only.
+ * With G = n_group, L = T*256/G and nc = n_channels, per flow k = n_flows-1 .. 0 (a0 / a1 = the halves of `audio`):
+ *   x = start(a0); per layer i: acts = tanh(.)*sigmoid(.) of in_layers[i](x) + cond_layer(spect)[2nc*i : 2nc*(i+1)], the
+ *   conditioning folded into the same GEMM (no [B, 2*nc*n_layers, L] tensor exists); x += / out += res_skip_layers[i](acts);
+ *   a1 = (a1 - b) / exp(s) with (b, s) = end(out); audio = W^-1 cat(a0, a1); early flows prepend sigma * z.
+ * Weights are the folded ones (g * v / ||v||) in torch layout; W^-1 is computed by the caller, once, in fp32 (glow.py:91).
+ * Supported: kernel_size 3; n_layers 1..8; n_channels a multiple of 8 from 8 to 512; n_group even, 2..8; n_early_size
+ * even; n_mel_channels * n_group a multiple of 8; B <= 65535.  Everything else is refused with the offending value in
+ * t2_last_error; nothing else is ever computed in its place. */
+#define T2_WAVEGLOW_MAX_LAYERS 8
+#define T2_WAVEGLOW_KERNELS 5 /* kernel kinds of kernel_ms_host: upsample, start, gated conv, res_skip, coupling */
+typedef struct t2_waveglow_config {      /* the constructor arguments of glow.py:179-180 and WN_config */
+    int n_mel_channels, n_flows, n_group, n_early_every, n_early_size;
+    int n_layers, n_channels, kernel_size;
+} t2_waveglow_config;
+typedef struct t2_waveglow_plan_info {
+    long L;                  /* columns of every activation: T * 256 / n_group */
+    long out_len;            /* samples per item: L * n_group (= T * 256 where n_group divides 256) */
+    int n_remaining_channels;/* channels of the first noise plane (glow.py:205) */
+    int n_noise_planes;      /* 1 + the number of early flows: [B, n_remaining, L], then [B, n_early_size, L] each, k descending */
+    int n_tensors;           /* what t2_waveglow_pack takes: 2 + n_flows * (7 + 4 * n_layers) */
+    int time_tile;           /* T2_VOCODER_TIME_TILE */
+    size_t workspace_bytes;  /* spect, x, out, acts and two audio buffers */
+    size_t packed_bytes;
+} t2_waveglow_plan_info;
+/* Pure host call (no device): validates cfg, B >= 1 and T >= 1 and sizes the buffers. */
+int t2_waveglow_plan(const t2_waveglow_config* cfg, int B, int T, t2_waveglow_plan_info* out);
+/* tensors_host: HOST array of n_tensors DEVICE pointers: upsample.weight [n_mel][n_mel][1024], upsample.bias, then per flow
+ * k ascending: start.weight [nc][n_half], start.bias, cond_layer.weight [2*nc*n_layers][n_mel*G], cond_layer.bias,
+ * (in_layers[i].weight [2nc][nc][3], .bias) for every i, (res_skip_layers[i].weight [2nc or nc][nc], .bias) for every i,
+ * end.weight [2*n_half][nc], end.bias, W_inverse [c][c].  Writes `packed` (packed_bytes); once per set of weights. */
+int t2_waveglow_pack(const t2_waveglow_config* cfg, const float* const* tensors_host, int n_tensors, float* packed, void* stream);
+typedef struct t2_waveglow_infer_args {
+    int B, T, n_mel;         /* n_mel: channels of the tensor given, checked against cfg */
+    const float* packed;
+    const float* mel;        /* [B, n_mel, T] */
+    const float* const* noise_host;   /* HOST array of n_noise DEVICE pointers, the planes in the order of the plan */
+    int n_noise;
+    float sigma;
+    float* workspace;        /* workspace_bytes */
+    float* audio;            /* [B, out_len] */
+    float* spect;            /* debug output, nullable: the upsampled, regrouped mel [B, n_mel*G, L] (glow.py:252-258) */
+    float* flow_audio;       /* debug output, nullable: `audio` after the last-executed flow (k = 0), [B, G, L] */
+    double* kernel_ms_host;  /* debug output, nullable: T2_WAVEGLOW_KERNELS totals in ms, every launch bracketed by events */
+} t2_waveglow_infer_args;
+int t2_waveglow_infer(const t2_waveglow_config* cfg, const t2_waveglow_infer_args* a, void* stream);
+/* Single kernels, for the tests only (t2_waveglow_infer runs the same ones).  Weights in torch layout; packed_ws receives
+ * the packed weights first: t2_waveglow_packed_floats(kind, ...) floats with kind 0 = gated conv (rows = nc, k0 = nc,
+ * k1 = conditioning channels), 1 = res_skip (rows = 2nc or nc, k0 = nc), 2 = upsample (rows = k0 = n_mel). */
+size_t t2_waveglow_packed_floats(int kind, int rows, int k0, int k1);
+/* y [B, nc, L] = tanh(u[:nc]) * sigmoid(u[nc:]), u = conv(x; w_in, dilation d, "same") + b_in + w_cond spect + b_cond
+ * (glow.py:160-166 with glow.py:28-40).  raw != 0 skips the gate: y [B, 2*nc, L] = u.  d in 1, 2, 4 .. 128. */
+typedef struct t2_waveglow_gated_args {
+    int B, nc, n_cond, L, d, raw;
+    const float* x;          /* [B, nc, L] */
+    const float* spect;      /* [B, n_cond, L] */
+    const float* w_in; const float* b_in;       /* [2nc][nc][3], [2nc] */
+    const float* w_cond; const float* b_cond;   /* the layer's rows of cond_layer: [2nc][n_cond], [2nc] */
+    float* packed_ws; float* y;
+} t2_waveglow_gated_args;
+int t2_waveglow_gated_conv(const t2_waveglow_gated_args* a, void* stream);
+/* rs = w acts + bias.  last == 0 (w [2nc][nc]): x += rs[:nc], out += rs[nc:];  last != 0 (w [nc][nc]): out += rs
+ * (glow.py:168-173).  first != 0: `out` is taken as zero and not read (glow.py:156). */
+typedef struct t2_waveglow_res_skip_args {
+    int B, nc, L, first, last;
+    const float* acts; const float* w; const float* bias;
+    float* packed_ws; float* x; float* out;     /* [B, nc, L] each; x unused when last */
+} t2_waveglow_res_skip_args;
+int t2_waveglow_res_skip(const t2_waveglow_res_skip_args* a, void* stream);
+/* spect [B, n_mel*G, L], L = T*256/G: spect[b, m*G + g, l] = ConvTranspose1d(n_mel, n_mel, 1024, stride=256)(mel)[b, m, l*G + g]
+ * (glow.py:252-258); the 768 trailing samples are never computed. */
+typedef struct t2_waveglow_upsample_args {
+    int B, n_mel, T, n_group;
+    const float* mel; const float* w; const float* bias;    /* [B, n_mel, T], [n_mel][n_mel][1024], [n_mel] */
+    float* packed_ws; float* spect;
+} t2_waveglow_upsample_args;
+int t2_waveglow_upsample(const t2_waveglow_upsample_args* a, void* stream);
+/* One flow's tail (glow.py:276-289): (b, s) = end(out); a1 = (in_scale*a1 - b) / exp(s); y = W_inverse cat(in_scale*a0, a1);
+ * audio_out [B, n_early + 2*n_half, L] = cat(sigma * z, y).  audio_interleaved (nullable) [B, L, 2*n_half] receives y in
+ * the order of the waveform (glow.py:291); audio_out is nullable when it is given. */
+typedef struct t2_waveglow_couple_args {
+    int B, nc, n_half, L, n_early;
+    float in_scale, sigma;
+    const float* out;        /* [B, nc, L] */
+    const float* w_end; const float* b_end;     /* [2*n_half][nc], [2*n_half] */
+    const float* audio_in;   /* [B, 2*n_half, L] */
+    const float* w_inverse;  /* [2*n_half][2*n_half] */
+    const float* z;          /* [B, n_early, L], unused when n_early == 0 */
+    float* audio_out; float* audio_interleaved;
+} t2_waveglow_couple_args;
+int t2_waveglow_couple(const t2_waveglow_couple_args* a, void* stream);
+
 /* Gradient-norm clipping + Adam over a list of fp32 tensors — replaces torch.nn.utils.clip_grad_norm_ +
  * torch.optim.Adam.step of the training loop (train.py:322-330; Adam with weight decay added to the gradient).
  * `table` is a DEVICE array of n_tensors rows; row i covers chunks [first_chunk, first_chunk + t2_adam_chunks(numel))

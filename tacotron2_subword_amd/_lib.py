@@ -283,6 +283,48 @@ class StftSynthesisArgs(C.Structure):
 STFT_FRAME_TILE = 32         # include/t2amd.h T2_STFT_FRAME_TILE
 STFT_POLAR, STFT_DENOISE = 0, 1
 
+class WaveglowConfig(C.Structure):
+    _fields_ = [("n_mel_channels", C.c_int), ("n_flows", C.c_int), ("n_group", C.c_int), ("n_early_every", C.c_int), ("n_early_size", C.c_int),
+                ("n_layers", C.c_int), ("n_channels", C.c_int), ("kernel_size", C.c_int)]
+
+
+class WaveglowPlanInfo(C.Structure):
+    _fields_ = [("L", C.c_long), ("out_len", C.c_long), ("n_remaining_channels", C.c_int), ("n_noise_planes", C.c_int), ("n_tensors", C.c_int),
+                ("time_tile", C.c_int), ("workspace_bytes", C.c_size_t), ("packed_bytes", C.c_size_t)]
+
+
+class WaveglowInferArgs(C.Structure):
+    _fields_ = [("B", C.c_int), ("T", C.c_int), ("n_mel", C.c_int), ("packed", C.c_void_p), ("mel", C.c_void_p),
+                ("noise_host", C.POINTER(C.c_void_p)), ("n_noise", C.c_int), ("sigma", C.c_float),
+                ("workspace", C.c_void_p), ("audio", C.c_void_p), ("spect", C.c_void_p), ("flow_audio", C.c_void_p),
+                ("kernel_ms_host", C.POINTER(C.c_double))]
+
+
+class WaveglowGatedArgs(C.Structure):
+    _fields_ = [("B", C.c_int), ("nc", C.c_int), ("n_cond", C.c_int), ("L", C.c_int), ("d", C.c_int), ("raw", C.c_int),
+                ("x", C.c_void_p), ("spect", C.c_void_p), ("w_in", C.c_void_p), ("b_in", C.c_void_p), ("w_cond", C.c_void_p), ("b_cond", C.c_void_p),
+                ("packed_ws", C.c_void_p), ("y", C.c_void_p)]
+
+
+class WaveglowResSkipArgs(C.Structure):
+    _fields_ = [("B", C.c_int), ("nc", C.c_int), ("L", C.c_int), ("first", C.c_int), ("last", C.c_int),
+                ("acts", C.c_void_p), ("w", C.c_void_p), ("bias", C.c_void_p), ("packed_ws", C.c_void_p), ("x", C.c_void_p), ("out", C.c_void_p)]
+
+
+class WaveglowUpsampleArgs(C.Structure):
+    _fields_ = [("B", C.c_int), ("n_mel", C.c_int), ("T", C.c_int), ("n_group", C.c_int),
+                ("mel", C.c_void_p), ("w", C.c_void_p), ("bias", C.c_void_p), ("packed_ws", C.c_void_p), ("spect", C.c_void_p)]
+
+
+class WaveglowCoupleArgs(C.Structure):
+    _fields_ = [("B", C.c_int), ("nc", C.c_int), ("n_half", C.c_int), ("L", C.c_int), ("n_early", C.c_int), ("in_scale", C.c_float), ("sigma", C.c_float),
+                ("out", C.c_void_p), ("w_end", C.c_void_p), ("b_end", C.c_void_p), ("audio_in", C.c_void_p), ("w_inverse", C.c_void_p), ("z", C.c_void_p),
+                ("audio_out", C.c_void_p), ("audio_interleaved", C.c_void_p)]
+
+
+WAVEGLOW_KERNELS = ("upsample", "start", "gated_conv", "res_skip", "couple")      # include/t2amd.h T2_WAVEGLOW_KERNELS
+WAVEGLOW_GATED, WAVEGLOW_RES_SKIP, WAVEGLOW_UPSAMPLE = 0, 1, 2                      # kinds of t2_waveglow_packed_floats
+
 # every symbol include/t2amd.h declares (tests/test_abi.py checks the library exports them all)
 ABI_VERSION = 4      # include/t2amd.h T2_ABI_VERSION: struct sizes below match that header and nothing else
 
@@ -293,7 +335,9 @@ EXPORTS = ["t2_last_error", "t2_version", "t2_chain_status", "t2_chain_status_cl
            "t2_finalize_bct", "t2_mask_bt", "t2_gemm", "t2_rng_keep_mask", "t2_rng_normal",
            "t2_softdtw_plan", "t2_softdtw_dist", "t2_softdtw_forward", "t2_softdtw_backward", "t2_softdtw_dist_backward",
            "t2_hifigan_plan", "t2_hifigan_pack", "t2_hifigan_forward", "t2_vocoder_packed_floats", "t2_vocoder_conv1d", "t2_vocoder_conv_transpose1d",
-           "t2_stft_plan", "t2_stft_pack", "t2_stft_analysis", "t2_stft_synthesis"]
+           "t2_stft_plan", "t2_stft_pack", "t2_stft_analysis", "t2_stft_synthesis",
+           "t2_waveglow_plan", "t2_waveglow_pack", "t2_waveglow_infer", "t2_waveglow_packed_floats", "t2_waveglow_gated_conv", "t2_waveglow_res_skip",
+           "t2_waveglow_upsample", "t2_waveglow_couple"]
 
 _lib = None
 
@@ -364,6 +408,14 @@ def lib() -> C.CDLL:
         L.t2_stft_pack.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.t2_stft_analysis.argtypes = [C.POINTER(StftAnalysisArgs), C.c_void_p]
         L.t2_stft_synthesis.argtypes = [C.POINTER(StftSynthesisArgs), C.c_void_p]
+        L.t2_waveglow_plan.argtypes = [C.POINTER(WaveglowConfig), C.c_int, C.c_int, C.POINTER(WaveglowPlanInfo)]
+        L.t2_waveglow_pack.argtypes = [C.POINTER(WaveglowConfig), C.POINTER(C.c_void_p), C.c_int, C.c_void_p, C.c_void_p]
+        L.t2_waveglow_infer.argtypes = [C.POINTER(WaveglowConfig), C.POINTER(WaveglowInferArgs), C.c_void_p]
+        L.t2_waveglow_packed_floats.argtypes, L.t2_waveglow_packed_floats.restype = [C.c_int, C.c_int, C.c_int, C.c_int], C.c_size_t
+        L.t2_waveglow_gated_conv.argtypes = [C.POINTER(WaveglowGatedArgs), C.c_void_p]
+        L.t2_waveglow_res_skip.argtypes = [C.POINTER(WaveglowResSkipArgs), C.c_void_p]
+        L.t2_waveglow_upsample.argtypes = [C.POINTER(WaveglowUpsampleArgs), C.c_void_p]
+        L.t2_waveglow_couple.argtypes = [C.POINTER(WaveglowCoupleArgs), C.c_void_p]
         _lib = L
     return _lib
 
@@ -767,4 +819,18 @@ def stft_plan(N: int, hop: int, nf: int = 1) -> StftPlanInfo:
     the reason for odd N, N % hop != 0 and sizes the kernels do not take."""
     info = StftPlanInfo()
     check(lib().t2_stft_plan(N, hop, nf, C.byref(info)))
+    return info
+
+
+def waveglow_config(n_mel_channels, n_flows, n_group, n_early_every, n_early_size, WN_config) -> WaveglowConfig:
+    """The constructor arguments of the reference's WaveGlow as the C struct; t2_waveglow_plan judges them."""
+    return WaveglowConfig(int(n_mel_channels), int(n_flows), int(n_group), int(n_early_every), int(n_early_size),
+                          int(WN_config["n_layers"]), int(WN_config["n_channels"]), int(WN_config["kernel_size"]))
+
+
+def waveglow_plan(cfg: WaveglowConfig, B: int, T: int) -> WaveglowPlanInfo:
+    """Output length, noise planes and buffer sizes of an infer call (t2_waveglow_plan: pure host, no device needed); raises with
+    the library's message for what is not supported."""
+    info = WaveglowPlanInfo()
+    check(lib().t2_waveglow_plan(C.byref(cfg), B, T, C.byref(info)))
     return info

@@ -1,0 +1,597 @@
+// WaveGlow (Prenger et al. 2018), inference: mel spectrogram -> waveform.  Replaces the reference's glow.py: WaveGlow.infer
+// (:251-293), WN.forward (:153-175), Invertible1x1Conv.forward(reverse=True) (:88-97).
+//
+// Activations are [B][C][L] with time contiguous, L = T*256/n_group; arithmetic is exact fp32 on the matrix cores
+// (v_mfma_f32_32x32x2_f32), whatever t2_set_precision says.  Three of the five kernels are one GEMM kernel in the style of
+// vocoder.hip (lanes along time, a slab [16 channels][128 + halo] of the operand in LDS, weights packed once into the order the
+// lanes read them, a wave computing 32 rows x 64 columns), with three epilogues:
+//   gated conv   Y = tanh(U[:nc]) * sigmoid(U[nc:]),  U = in_layers[i](x) + cond_layer(spect)[2nc*i : 2nc*(i+1)] as ONE GEMM with
+//                K = 3*nc (the taps read x at -d, 0, +d from the slab) + n_mel*G (spect at the same column).  Tanh row c and
+//                sigmoid row c + nc are two accumulators of the same wave: same lane, same element, same column, so the gate is
+//                applied in registers and only [B, nc, L] is written.  The conditioning tensor [B, 2*nc*n_layers, L] never exists.
+//   res_skip     the 1x1 conv; its epilogue does x += rs[:nc] and out += rs[nc:] in place (acts is a buffer of its own).
+//   upsample     ConvTranspose1d(n_mel, n_mel, 1024, stride 256) as a polyphase GEMM: output sample 256q + r reads taps r + 256m
+//                (m = 0..3) of frames q - m, so rows = (channel, phase r), columns = frames q, K = n_mel * 4; the epilogue writes
+//                spect[b, ch*G + g, l] at 256q + r = l*G + g and never computes the 768 trailing samples.  Each element once.
+// `start` (K <= 4) and the coupling (end: <= 8 rows reduced over nc with lanes along time, then (a1 - b)/exp(s), the c x c inverse
+// mix and the early-noise prepend in one pass) are plain VALU.  No atomics, every sum in a fixed order, 64-bit element offsets.
+#include <algorithm>
+#include <vector>
+
+#include "../../include/t2amd.h"
+#include "kernels.h"
+
+namespace t2 {
+
+constexpr int kWgCK = 16;                         // operand channels per slab
+constexpr int kWgMaxD = 128;                      // dilation of layer 7
+constexpr int kWgStride = 416;                    // slab row stride in floats: = 32 mod 64 banks, >= kVocTT + 2*kWgMaxD
+static_assert(kWgStride % 64 == 32 && kWgStride >= kVocTT + 2 * kWgMaxD, "slab row stride");
+static_assert(T2_WAVEGLOW_MAX_LAYERS == 8 && (1 << (T2_WAVEGLOW_MAX_LAYERS - 1)) == kWgMaxD, "the deepest layer's dilation fits the slab");
+enum { kWgGated = 0, kWgResSkip = 1, kWgUpsample = 2 };
+constexpr int kWgUpK = 1024, kWgUpStride = 256, kWgUpTaps = kWgUpK / kWgUpStride;
+
+// Y[row][q] = sum over segment 0 (C0 channels x taps, tap j at slab column q + coff0 + j*cstep) and segment 1 (C1 channels, one
+// tap at q) of packed weight x operand.  N = columns (row length of both operands and, but for the upsample, of the output).
+struct WgGemm {
+    const float* x0; const float* x1; const float* wp; const float* bias0; const float* bias1;
+    float* y0; float* y1;
+    int C0, C1, N;
+    int taps, coff0, cstep, halo;
+    int rows, mtiles, nch0, nch1;
+    int first, last, raw, G; long Lg;             // res_skip: first, last; gated: raw; upsample: G, Lg = columns of spect
+};
+
+template <int WM, int MODE>
+__global__ void __launch_bounds__(WM * 128) wg_gemm_kernel(WgGemm p) {
+    constexpr int GATES = MODE == kWgGated ? 2 : 1;
+    __shared__ float slab[kWgCK * kWgStride];
+    constexpr int kWaves = WM * 2;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int wm = wave % WM, wt = wave / WM;
+    const int mt = blockIdx.y * WM + wm;
+    const bool active = mt < p.mtiles;            // uniform over the wave
+    const int b = blockIdx.z;
+    const long t0 = (long)blockIdx.x * kVocTT;
+    const int nsteps = p.nch0 * p.taps + p.nch1;
+    const f32x4* wp = reinterpret_cast<const f32x4*>(p.wp) + (size_t)(active ? mt : 0) * nsteps * GATES * 128;
+    const int tc = wt * 64 + (lane & 31), hk = lane >> 5;
+    f32x16 acc[GATES][2];
+#pragma unroll
+    for (int g = 0; g < GATES; ++g) { acc[g][0] = f32x16{0}; acc[g][1] = f32x16{0}; }
+
+    for (int c = 0; c < p.nch0 + p.nch1; ++c) {
+        const bool seg0 = c < p.nch0;
+        const int C = seg0 ? p.C0 : p.C1, ci0 = (seg0 ? c : c - p.nch0) * kWgCK;
+        const int halo = seg0 ? p.halo : 0, sw = kVocTT + 2 * halo;
+        const float* xb = (seg0 ? p.x0 : p.x1) + (size_t)b * C * p.N;
+        if (c) __syncthreads();                    // every wave is done reading the previous slab
+        for (int row = wave; row < kWgCK; row += kWaves) {
+            const int ci = ci0 + row;
+            const float* xr = xb + (size_t)ci * p.N;
+            for (int col = lane; col < sw; col += 64) {
+                const long t = t0 + col - halo;
+                slab[row * kWgStride + col] = (ci < C && t >= 0 && t < p.N) ? xr[t] : 0.f;
+            }
+        }
+        __syncthreads();
+        if (active) {
+            const int taps = seg0 ? p.taps : 1;
+            const size_t step0 = seg0 ? (size_t)c * p.taps : (size_t)p.nch0 * p.taps + (c - p.nch0);
+            for (int j = 0; j < taps; ++j) {
+                const float* sb = slab + hk * kWgStride + tc + (seg0 ? p.coff0 + j * p.cstep : 0);
+                const f32x4* wj = wp + (step0 + j) * GATES * 128 + lane;
+#pragma unroll
+                for (int pg = 0; pg < 2; ++pg) {
+                    f32x4 a[GATES];
+#pragma unroll
+                    for (int g = 0; g < GATES; ++g) a[g] = wj[g * 128 + pg * 64];
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) {
+                        const float* s2 = sb + (pg * 4 + i) * 2 * kWgStride;
+                        const float b0 = s2[0], b1 = s2[32];
+#pragma unroll
+                        for (int g = 0; g < GATES; ++g) {
+                            acc[g][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[g][i], b0, acc[g][0], 0, 0, 0);
+                            acc[g][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[g][i], b1, acc[g][1], 0, 0, 0);
+                        }
+                    }
+                }
+            }
+        }
+    }
+    if (!active) return;
+    // lane holds column lane & 31 and rows (e&3) + 8*(e>>2) + 4*hk of each 32x32 tile
+#pragma unroll
+    for (int n = 0; n < 2; ++n) {
+        const long q = t0 + wt * 64 + n * 32 + (lane & 31);
+        if (q >= p.N) continue;
+#pragma unroll
+        for (int e = 0; e < 16; ++e) {
+            const int r = mt * 32 + (e & 3) + 8 * (e >> 2) + 4 * hk;
+            if (r >= p.rows) continue;
+            if constexpr (MODE == kWgGated) {
+                const float ua = (acc[0][n][e] + p.bias0[r]) + p.bias1[r];
+                const float ub = (acc[1][n][e] + p.bias0[r + p.rows]) + p.bias1[r + p.rows];
+                if (p.raw) {
+                    p.y0[((size_t)b * 2 * p.rows + r) * p.N + q] = ua;
+                    p.y0[((size_t)b * 2 * p.rows + p.rows + r) * p.N + q] = ub;
+                } else {
+                    p.y0[((size_t)b * p.rows + r) * p.N + q] = tanhf(ua) * (1.f / (1.f + expf(-ub)));
+                }
+            } else if constexpr (MODE == kWgResSkip) {
+                const float v = acc[0][n][e] + p.bias0[r];
+                const int nc = p.C0;
+                if (!p.last && r < nc) {
+                    const size_t o = ((size_t)b * nc + r) * p.N + q;
+                    p.y0[o] = p.y0[o] + v;
+                } else {
+                    const size_t o = ((size_t)b * nc + (p.last ? r : r - nc)) * p.N + q;
+                    p.y1[o] = p.first ? v : p.y1[o] + v;
+                }
+            } else {
+                const int ch = r / kWgUpStride;
+                const long t = q * kWgUpStride + (r % kWgUpStride), l = t / p.G;
+                if (l < p.Lg) p.y0[(((size_t)b * p.C0 + ch) * p.G + (int)(t % p.G)) * p.Lg + l] = acc[0][n][e] + p.bias0[ch];
+            }
+        }
+    }
+}
+
+// packed[mtile][step][gate][pg][lane][i] = W[row = 32*mtile + (lane & 31) (+ gate * rows)][k = 16*chunk + 2*(4*pg + i) + (lane >> 5)]
+// (zero outside the matrix); step = chunk * taps + tap over segment 0, then the chunks of segment 1.
+struct WgPack { const float* w0; const float* w1; float* out; int mode, rows, K0, K1, taps, nch0, nch1; size_t total; };
+__global__ void __launch_bounds__(256) wg_pack_kernel(WgPack p) {
+    const size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= p.total) return;
+    const int gates = p.mode == kWgGated ? 2 : 1, nsteps = p.nch0 * p.taps + p.nch1;
+    const int i = idx & 3, lane = (idx >> 2) & 63, pg = (idx >> 8) & 1;
+    size_t rest = idx >> 9;
+    const int gate = rest % gates; rest /= gates;
+    const int step = rest % nsteps;
+    const int mt = (int)(rest / nsteps);
+    const int r = mt * 32 + (lane & 31), kloc = 2 * (4 * pg + i) + (lane >> 5);
+    float v = 0.f;
+    if (r < p.rows) {
+        if (step < p.nch0 * p.taps) {
+            const int kk = (step / p.taps) * kWgCK + kloc, j = step % p.taps;
+            if (kk < p.K0) {
+                if (p.mode == kWgGated) v = p.w0[((size_t)(gate * p.rows + r) * p.K0 + kk) * 3 + j];          // Conv1d [2nc][nc][3]
+                else if (p.mode == kWgResSkip) v = p.w0[(size_t)r * p.K0 + kk];                                // Conv1d [rows][nc][1]
+                else v = p.w0[((size_t)kk * p.K0 + r / kWgUpStride) * kWgUpK + r % kWgUpStride + kWgUpStride * j];   // ConvTranspose1d [Cin][Cout][1024]
+            }
+        } else {
+            const int kk = (step - p.nch0 * p.taps) * kWgCK + kloc;
+            if (kk < p.K1) v = p.w1[(size_t)(gate * p.rows + r) * p.K1 + kk];
+        }
+    }
+    p.out[idx] = v;
+}
+
+// x[b, c, t] = bias[c] + sum_h w[c][h] * (scale * audio[b, h, t]), h ascending; 32 channels per workgroup row
+__global__ void __launch_bounds__(256) wg_start_kernel(const float* __restrict__ audio, int ctot, int n_half, float scale, const float* __restrict__ w,
+                                                      const float* __restrict__ bias, float* __restrict__ x, int nc, long L) {
+    const long t = (long)blockIdx.x * 256 + threadIdx.x;
+    if (t >= L) return;
+    const int b = blockIdx.z;
+    float a[4];
+#pragma unroll
+    for (int h = 0; h < 4; ++h) a[h] = h < n_half ? audio[((size_t)b * ctot + h) * L + t] * scale : 0.f;
+    const int c1 = min(nc, (int)(blockIdx.y + 1) * 32);
+    for (int c = blockIdx.y * 32; c < c1; ++c) {
+        float acc = 0.f;
+#pragma unroll
+        for (int h = 0; h < 4; ++h)
+            if (h < n_half) acc = fmaf(w[c * n_half + h], a[h], acc);
+        x[((size_t)b * nc + c) * L + t] = acc + bias[c];
+    }
+}
+
+struct WgCouple {
+    const float* out; const float* w_end; const float* b_end; const float* in; const float* winv; const float* z;
+    float* dst; float* inter;
+    int nc, n_half, n_early; long L; float in_scale, sigma;
+};
+// one thread per (item, column): end as <= 8 fmaf chains over nc (ascending), the affine inverse, the c x c mix (ascending)
+__global__ void __launch_bounds__(256) wg_couple_kernel(WgCouple p) {
+    __shared__ float we[8 * 512], be[8], wi[64];
+    const int nh = p.n_half, C = 2 * nh;
+    for (int i = threadIdx.x; i < C * p.nc; i += 256) we[i] = p.w_end[i];
+    if (threadIdx.x < C) be[threadIdx.x] = p.b_end[threadIdx.x];
+    if (threadIdx.x < C * C) wi[threadIdx.x] = p.winv[threadIdx.x];
+    __syncthreads();
+    const long t = (long)blockIdx.x * 256 + threadIdx.x;
+    if (t >= p.L) return;
+    const int b = blockIdx.y;
+    float o[8];
+#pragma unroll
+    for (int r = 0; r < 8; ++r) o[r] = 0.f;
+    const float* ob = p.out + (size_t)b * p.nc * p.L + t;
+    for (int c = 0; c < p.nc; ++c) {
+        const float v = ob[(size_t)c * p.L];
+#pragma unroll
+        for (int r = 0; r < 8; ++r)
+            if (r < C) o[r] = fmaf(we[r * p.nc + c], v, o[r]);
+    }
+    float v[8];
+    const float* ib = p.in + (size_t)b * C * p.L + t;
+#pragma unroll
+    for (int h = 0; h < 4; ++h) {
+        if (h < nh) {
+            const float a0 = ib[(size_t)h * p.L] * p.in_scale, a1 = ib[(size_t)(nh + h) * p.L] * p.in_scale;
+            float bb = 0.f, s = 0.f;
+#pragma unroll
+            for (int r = 0; r < 8; ++r) {           // o[h] and o[nh + h] without a dynamic register index
+                if (r == h) bb = o[r] + be[r];
+                if (r == nh + h) s = o[r] + be[r];
+            }
+            const float y1 = (a1 - bb) / expf(s);
+#pragma unroll
+            for (int r = 0; r < 8; ++r) {
+                if (r == h) v[r] = a0;
+                if (r == nh + h) v[r] = y1;
+            }
+        }
+    }
+    const int Cn = C + p.n_early;
+#pragma unroll
+    for (int r = 0; r < 8; ++r) {
+        if (r < C) {
+            float y = 0.f;
+#pragma unroll
+            for (int c = 0; c < 8; ++c)
+                if (c < C) y = fmaf(wi[r * C + c], v[c], y);
+            if (p.dst) p.dst[((size_t)b * Cn + p.n_early + r) * p.L + t] = y;
+            if (p.inter) p.inter[((size_t)b * p.L + t) * C + r] = y;
+        }
+    }
+    if (p.dst)
+        for (int j = 0; j < p.n_early; ++j) p.dst[((size_t)b * Cn + j) * p.L + t] = p.sigma * p.z[((size_t)b * p.n_early + j) * p.L + t];
+}
+
+// ------------------------------------------------------------------------------------------------------------------
+// host
+// ------------------------------------------------------------------------------------------------------------------
+static size_t round4(size_t n) { return (n + 3) / 4 * 4; }
+static int chunks(int k) { return (k + kWgCK - 1) / kWgCK; }
+
+static size_t wg_packed_floats(int kind, int rows, int k0, int k1) {
+    if (kind == kWgGated) return (size_t)((rows + 31) / 32) * (chunks(k0) * 3 + chunks(k1)) * 2 * 512;
+    if (kind == kWgResSkip) return (size_t)((rows + 31) / 32) * chunks(k0) * 512;
+    return (size_t)rows * kWgUpStride / 32 * chunks(k0) * kWgUpTaps * 512;
+}
+
+static int wg_pack(int kind, const float* w0, const float* w1, float* out, int rows, int k0, int k1, hipStream_t s) {
+    T2_REQUIRE(w0 && out && (kind != kWgGated || w1), "waveglow pack: null pointer");
+    WgPack p{w0, w1, out, kind, kind == kWgUpsample ? rows * kWgUpStride : rows, k0, kind == kWgGated ? k1 : 0,
+             kind == kWgGated ? 3 : (kind == kWgUpsample ? kWgUpTaps : 1), chunks(k0), kind == kWgGated ? chunks(k1) : 0,
+             wg_packed_floats(kind, rows, k0, k1)};
+    hipLaunchKernelGGL(wg_pack_kernel, dim3((unsigned)((p.total + 255) / 256)), dim3(256), 0, s, p);
+    T2_LAUNCH_CHECK();
+    return 0;
+}
+
+template <int MODE>
+static int wg_launch(const WgGemm& p, int B, hipStream_t s) {
+    const int wm = p.mtiles >= 4 ? 4 : (p.mtiles >= 2 ? 2 : 1);
+    dim3 grid((unsigned)((p.N + kVocTT - 1) / kVocTT), (unsigned)((p.mtiles + wm - 1) / wm), (unsigned)B);
+    if (wm == 4) hipLaunchKernelGGL((wg_gemm_kernel<4, MODE>), grid, dim3(512), 0, s, p);
+    else if (wm == 2) hipLaunchKernelGGL((wg_gemm_kernel<2, MODE>), grid, dim3(256), 0, s, p);
+    else hipLaunchKernelGGL((wg_gemm_kernel<1, MODE>), grid, dim3(128), 0, s, p);
+    T2_LAUNCH_CHECK();
+    return 0;
+}
+
+static int wg_check_common(const char* who, int B, long L) {
+    T2_REQUIRE(B >= 1 && B <= 65535, "%s: B=%d outside 1..65535", who, B);
+    T2_REQUIRE(L >= 1, "%s: L=%ld must be at least 1", who, L);
+    T2_REQUIRE(L <= (long)INT32_MAX / 2, "%s: L=%ld exceeds the limit of %d columns per row", who, L, INT32_MAX / 2);
+    return 0;
+}
+static int wg_check_nc(const char* who, int nc) {
+    T2_REQUIRE(nc >= 8 && nc <= 512 && nc % 8 == 0, "%s: n_channels=%d, must be a multiple of 8 from 8 to 512", who, nc);
+    return 0;
+}
+
+static int wg_gated_check(int B, int nc, int n_cond, long L, int d) {
+    const char* who = "waveglow gated conv";
+    T2_TRY_RC(wg_check_common(who, B, L));
+    T2_TRY_RC(wg_check_nc(who, nc));
+    T2_REQUIRE(n_cond >= 8 && n_cond % 8 == 0, "%s: %d conditioning channels (n_mel_channels * n_group), must be a positive multiple of 8", who, n_cond);
+    T2_REQUIRE(d >= 1 && d <= kWgMaxD && (d & (d - 1)) == 0, "%s: dilation %d is not a power of two from 1 to %d", who, d, kWgMaxD);
+    return 0;
+}
+
+static int wg_gated(int B, int nc, int n_cond, long L, int d, int raw, const float* x, const float* spect, const float* packed, const float* b_in,
+                    const float* b_cond, float* y, hipStream_t s) {
+    T2_TRY_RC(wg_gated_check(B, nc, n_cond, L, d));
+    T2_REQUIRE(x && spect && packed && b_in && b_cond && y, "waveglow gated conv: null pointer");
+    WgGemm p{};
+    p.x0 = x; p.x1 = spect; p.wp = packed; p.bias0 = b_in; p.bias1 = b_cond; p.y0 = y;
+    p.C0 = nc; p.C1 = n_cond; p.N = (int)L; p.taps = 3; p.coff0 = 0; p.cstep = d; p.halo = d;
+    p.rows = nc; p.mtiles = (nc + 31) / 32; p.nch0 = chunks(nc); p.nch1 = chunks(n_cond); p.raw = raw;
+    return wg_launch<kWgGated>(p, B, s);
+}
+
+static int wg_res_skip(int B, int nc, long L, int first, int last, const float* acts, const float* packed, const float* bias, float* x, float* out,
+                       hipStream_t s) {
+    const char* who = "waveglow res_skip";
+    T2_TRY_RC(wg_check_common(who, B, L));
+    T2_TRY_RC(wg_check_nc(who, nc));
+    T2_REQUIRE(acts && packed && bias && out && (last || x), "%s: null pointer", who);
+    WgGemm p{};
+    p.x0 = acts; p.wp = packed; p.bias0 = bias; p.y0 = x; p.y1 = out;
+    p.C0 = nc; p.N = (int)L; p.taps = 1;
+    p.rows = last ? nc : 2 * nc; p.mtiles = (p.rows + 31) / 32; p.nch0 = chunks(nc); p.first = first; p.last = last;
+    return wg_launch<kWgResSkip>(p, B, s);
+}
+
+static int wg_upsample(int B, int n_mel, int T, int G, const float* mel, const float* packed, const float* bias, float* spect, hipStream_t s) {
+    const char* who = "waveglow upsample";
+    T2_TRY_RC(wg_check_common(who, B, T));
+    T2_REQUIRE(n_mel >= 1 && n_mel <= 512, "%s: n_mel_channels=%d outside 1..512", who, n_mel);
+    T2_REQUIRE(G >= 2 && G <= 8 && G % 2 == 0, "%s: n_group=%d is not even and from 2 to 8", who, G);
+    T2_REQUIRE((long)T * kWgUpStride / G >= 1, "%s: T=%d frames give no whole group of %d samples", who, T, G);
+    T2_REQUIRE(mel && packed && bias && spect, "%s: null pointer", who);
+    WgGemm p{};
+    p.x0 = mel; p.wp = packed; p.bias0 = bias; p.y0 = spect;
+    p.C0 = n_mel; p.N = T; p.taps = kWgUpTaps; p.coff0 = kWgUpTaps - 1; p.cstep = -1; p.halo = kWgUpTaps - 1;
+    p.rows = n_mel * kWgUpStride; p.mtiles = p.rows / 32; p.nch0 = chunks(n_mel); p.G = G; p.Lg = (long)T * kWgUpStride / G;
+    return wg_launch<kWgUpsample>(p, B, s);
+}
+
+static int wg_start(int B, int nc, int ctot, int n_half, long L, float scale, const float* audio, const float* w, const float* bias, float* x, hipStream_t s) {
+    hipLaunchKernelGGL(wg_start_kernel, dim3((unsigned)((L + 255) / 256), (unsigned)((nc + 31) / 32), (unsigned)B), dim3(256), 0, s, audio, ctot, n_half,
+                       scale, w, bias, x, nc, L);
+    T2_LAUNCH_CHECK();
+    return 0;
+}
+
+static int wg_couple(int B, const WgCouple& p, hipStream_t s) {
+    const char* who = "waveglow coupling";
+    T2_TRY_RC(wg_check_common(who, B, p.L));
+    T2_TRY_RC(wg_check_nc(who, p.nc));
+    T2_REQUIRE(p.n_half >= 1 && p.n_half <= 4, "%s: n_half=%d outside 1..4", who, p.n_half);
+    T2_REQUIRE(p.n_early >= 0 && p.n_early + 2 * p.n_half <= 8, "%s: %d early channels on top of %d exceed 8", who, p.n_early, 2 * p.n_half);
+    T2_REQUIRE(p.out && p.w_end && p.b_end && p.in && p.winv && (p.dst || p.inter) && (p.n_early == 0 || (p.z && p.dst)), "%s: null pointer", who);
+    hipLaunchKernelGGL(wg_couple_kernel, dim3((unsigned)((p.L + 255) / 256), (unsigned)B), dim3(256), 0, s, p);
+    T2_LAUNCH_CHECK();
+    return 0;
+}
+
+// ------------------------------------------------------------------------------------------------------------------
+// the model
+// ------------------------------------------------------------------------------------------------------------------
+struct WgFlow {
+    int c, n_half, early;                          // channels of `audio` in this flow; early: sigma * z is prepended after it
+    size_t start_w, start_b, cond_b, end_w, end_b, winv;
+    size_t gated[T2_WAVEGLOW_MAX_LAYERS], in_b[T2_WAVEGLOW_MAX_LAYERS], rs[T2_WAVEGLOW_MAX_LAYERS], rs_b[T2_WAVEGLOW_MAX_LAYERS];
+};
+struct WgLayout { std::vector<WgFlow> flows; size_t up_w, up_b, total; int n_remaining, n_planes, n_tensors; };
+
+static int wg_layout(const t2_waveglow_config& c, WgLayout* out) {
+    T2_REQUIRE(c.kernel_size == 3, "waveglow: kernel_size=%d, only 3 is implemented", c.kernel_size);
+    T2_REQUIRE(c.n_layers >= 1 && c.n_layers <= T2_WAVEGLOW_MAX_LAYERS, "waveglow: n_layers=%d outside 1..%d", c.n_layers, T2_WAVEGLOW_MAX_LAYERS);
+    T2_TRY_RC(wg_check_nc("waveglow", c.n_channels));
+    T2_REQUIRE(c.n_group >= 2 && c.n_group <= 8 && c.n_group % 2 == 0, "waveglow: n_group=%d is not even and from 2 to 8", c.n_group);
+    T2_REQUIRE(c.n_early_size >= 0 && c.n_early_size % 2 == 0, "waveglow: n_early_size=%d is not even and non-negative", c.n_early_size);
+    T2_REQUIRE(c.n_early_every >= 1, "waveglow: n_early_every=%d must be at least 1", c.n_early_every);
+    T2_REQUIRE(c.n_flows >= 1 && c.n_flows <= 64, "waveglow: n_flows=%d outside 1..64", c.n_flows);
+    T2_REQUIRE(c.n_mel_channels >= 1 && c.n_mel_channels <= 512, "waveglow: n_mel_channels=%d outside 1..512", c.n_mel_channels);
+    const int n_cond = c.n_mel_channels * c.n_group, nc = c.n_channels;
+    T2_REQUIRE(n_cond % 8 == 0, "waveglow: n_mel_channels * n_group = %d is not a multiple of 8", n_cond);
+    WgLayout L;
+    size_t off = 0;
+    auto take = [&](size_t n) { const size_t o = off; off += round4(n); return o; };
+    L.up_w = take(wg_packed_floats(kWgUpsample, c.n_mel_channels, c.n_mel_channels, 0));
+    L.up_b = take(c.n_mel_channels);
+    int ch = c.n_group;
+    L.n_planes = 1;
+    for (int k = 0; k < c.n_flows; ++k) {
+        WgFlow f{};
+        f.early = k % c.n_early_every == 0 && k > 0;
+        if (f.early) { ch -= c.n_early_size; ++L.n_planes; }
+        T2_REQUIRE(ch >= 2, "waveglow: flow %d is left with %d channels: n_early_size=%d is taken too often from n_group=%d", k, ch, c.n_early_size, c.n_group);
+        f.c = ch; f.n_half = ch / 2;
+        f.start_w = take((size_t)nc * f.n_half); f.start_b = take(nc);
+        f.cond_b = take((size_t)2 * nc * c.n_layers);
+        for (int i = 0; i < c.n_layers; ++i) {
+            const int rows = i < c.n_layers - 1 ? 2 * nc : nc;
+            f.gated[i] = take(wg_packed_floats(kWgGated, nc, nc, n_cond)); f.in_b[i] = take(2 * nc);
+            f.rs[i] = take(wg_packed_floats(kWgResSkip, rows, nc, 0)); f.rs_b[i] = take(rows);
+        }
+        f.end_w = take((size_t)ch * nc); f.end_b = take(ch); f.winv = take((size_t)ch * ch);
+        L.flows.push_back(f);
+    }
+    L.n_remaining = ch; L.total = off; L.n_tensors = 2 + c.n_flows * (7 + 4 * c.n_layers);
+    if (out) *out = L;
+    return 0;
+}
+
+static int wg_plan(const t2_waveglow_config& c, int B, int T, t2_waveglow_plan_info* out, WgLayout* lay) {
+    WgLayout L;
+    T2_TRY_RC(wg_layout(c, &L));
+    T2_REQUIRE(B >= 1 && B <= 65535, "waveglow: B=%d outside 1..65535", B);
+    T2_REQUIRE(T >= 1, "waveglow: T=%d frames, must be at least 1", T);
+    const long cols = (long)T * kWgUpStride / c.n_group;
+    T2_REQUIRE(cols >= 1, "waveglow: T=%d frames give no whole group of %d samples", T, c.n_group);
+    T2_REQUIRE(cols <= (long)INT32_MAX / 2, "waveglow: L=%ld exceeds the limit of %d columns per row", cols, INT32_MAX / 2);
+    if (out) {
+        out->L = cols; out->out_len = cols * c.n_group;
+        out->n_remaining_channels = L.n_remaining; out->n_noise_planes = L.n_planes; out->n_tensors = L.n_tensors; out->time_tile = kVocTT;
+        const size_t per = round4((size_t)B * cols);
+        out->workspace_bytes = per * ((size_t)c.n_mel_channels * c.n_group + 3 * (size_t)c.n_channels + 2 * (size_t)c.n_group) * sizeof(float);
+        out->packed_bytes = L.total * sizeof(float);
+    }
+    if (lay) *lay = L;
+    return 0;
+}
+
+static int wg_copy(float* dst, const float* src, size_t n, hipStream_t s) {
+    T2_CHECK_HIP(hipMemcpyAsync(dst, src, n * sizeof(float), hipMemcpyDeviceToDevice, s));
+    return 0;
+}
+
+static int wg_pack_model(const t2_waveglow_config& c, const float* const* t, int n, float* packed, hipStream_t s) {
+    WgLayout L;
+    T2_TRY_RC(wg_layout(c, &L));
+    T2_REQUIRE(t && packed, "t2_waveglow_pack: null pointer");
+    T2_REQUIRE(n == L.n_tensors, "t2_waveglow_pack: %d tensors given, the configuration has %d", n, L.n_tensors);
+    for (int i = 0; i < n; ++i) T2_REQUIRE(t[i], "t2_waveglow_pack: tensor %d is null", i);
+    const int nc = c.n_channels, n_cond = c.n_mel_channels * c.n_group;
+    T2_TRY_RC(wg_pack(kWgUpsample, t[0], nullptr, packed + L.up_w, c.n_mel_channels, c.n_mel_channels, 0, s));
+    T2_TRY_RC(wg_copy(packed + L.up_b, t[1], c.n_mel_channels, s));
+    int at = 2;
+    for (int k = 0; k < c.n_flows; ++k) {
+        const WgFlow& f = L.flows[k];
+        T2_TRY_RC(wg_copy(packed + f.start_w, t[at], (size_t)nc * f.n_half, s));
+        T2_TRY_RC(wg_copy(packed + f.start_b, t[at + 1], nc, s));
+        const float* cond_w = t[at + 2];
+        T2_TRY_RC(wg_copy(packed + f.cond_b, t[at + 3], (size_t)2 * nc * c.n_layers, s));
+        at += 4;
+        for (int i = 0; i < c.n_layers; ++i, at += 2) {
+            T2_TRY_RC(wg_pack(kWgGated, t[at], cond_w + (size_t)2 * nc * i * n_cond, packed + f.gated[i], nc, nc, n_cond, s));
+            T2_TRY_RC(wg_copy(packed + f.in_b[i], t[at + 1], 2 * nc, s));
+        }
+        for (int i = 0; i < c.n_layers; ++i, at += 2) {
+            const int rows = i < c.n_layers - 1 ? 2 * nc : nc;
+            T2_TRY_RC(wg_pack(kWgResSkip, t[at], nullptr, packed + f.rs[i], rows, nc, 0, s));
+            T2_TRY_RC(wg_copy(packed + f.rs_b[i], t[at + 1], rows, s));
+        }
+        T2_TRY_RC(wg_copy(packed + f.end_w, t[at], (size_t)f.c * nc, s));
+        T2_TRY_RC(wg_copy(packed + f.end_b, t[at + 1], f.c, s));
+        T2_TRY_RC(wg_copy(packed + f.winv, t[at + 2], (size_t)f.c * f.c, s));
+        at += 3;
+    }
+    T2_REQUIRE(at == n, "t2_waveglow_pack: tensor table out of step");
+    return 0;
+}
+
+static int wg_infer(const t2_waveglow_config& c, const t2_waveglow_infer_args& a, hipStream_t s) {
+    WgLayout lay;
+    t2_waveglow_plan_info pl;
+    T2_TRY_RC(wg_layout(c, nullptr));
+    T2_REQUIRE(a.n_mel == c.n_mel_channels, "t2_waveglow_infer: the mel has %d channels, the model takes %d", a.n_mel, c.n_mel_channels);
+    T2_TRY_RC(wg_plan(c, a.B, a.T, &pl, &lay));
+    T2_REQUIRE(a.packed && a.mel && a.workspace && a.audio && a.noise_host, "t2_waveglow_infer: null pointer");
+    T2_REQUIRE(a.n_noise == lay.n_planes, "t2_waveglow_infer: %d noise planes given, the model draws %d", a.n_noise, lay.n_planes);
+    for (int i = 0; i < a.n_noise; ++i) T2_REQUIRE(a.noise_host[i], "t2_waveglow_infer: noise plane %d is null", i);
+    const int B = a.B, nc = c.n_channels, G = c.n_group, n_cond = c.n_mel_channels * G;
+    const long L = pl.L;
+    const size_t per = round4((size_t)B * L);
+    float* spect = a.workspace; float* x = spect + per * n_cond; float* out = x + per * nc; float* acts = out + per * nc;
+    float* bufs[2] = {acts + per * nc, acts + per * nc + per * G};
+
+    std::vector<hipEvent_t> ev;
+    std::vector<int> kinds;
+    int rc = 0;
+    auto timed = [&](int kind, int r) {            // kernel_ms_host: an event in front of (mark) and behind (timed) every launch
+        if (a.kernel_ms_host && r == 0) {
+            hipEvent_t e;
+            if (hipEventCreate(&e) != hipSuccess || hipEventRecord(e, s) != hipSuccess) { t2_set_error("t2_waveglow_infer: event failed"); return -2; }
+            ev.push_back(e); kinds.push_back(kind);
+        }
+        return r;
+    };
+    auto mark = [&]() {
+        if (a.kernel_ms_host) {
+            hipEvent_t e;
+            if (hipEventCreate(&e) == hipSuccess && hipEventRecord(e, s) == hipSuccess) ev.push_back(e);
+        }
+        return 0;
+    };
+#define WG_RUN(kind, call)                      \
+    do {                                        \
+        mark();                                 \
+        rc = timed(kind, call);                 \
+        if (rc != 0) goto done;                 \
+    } while (0)
+
+    {
+        WG_RUN(0, wg_upsample(B, c.n_mel_channels, a.T, G, a.mel, a.packed + lay.up_w, a.packed + lay.up_b, spect, s));
+        const float* src = a.noise_host[0];
+        float scale = a.sigma;
+        int plane = 1, cur = 0;
+        for (int k = c.n_flows - 1; k >= 0; --k) {
+            const WgFlow& f = lay.flows[k];
+            WG_RUN(1, wg_start(B, nc, f.c, f.n_half, L, scale, src, a.packed + f.start_w, a.packed + f.start_b, x, s));
+            for (int i = 0; i < c.n_layers; ++i) {
+                WG_RUN(2, wg_gated(B, nc, n_cond, L, 1 << i, 0, x, spect, a.packed + f.gated[i], a.packed + f.in_b[i],
+                                   a.packed + f.cond_b + (size_t)2 * nc * i, acts, s));
+                WG_RUN(3, wg_res_skip(B, nc, L, i == 0, i == c.n_layers - 1, acts, a.packed + f.rs[i], a.packed + f.rs_b[i], x, out, s));
+            }
+            WgCouple p{out, a.packed + f.end_w, a.packed + f.end_b, src, a.packed + f.winv, f.early ? a.noise_host[plane] : nullptr,
+                       k == 0 ? a.flow_audio : bufs[cur], k == 0 ? a.audio : nullptr, nc, f.n_half, f.early ? c.n_early_size : 0, L, scale, a.sigma};
+            if (f.early) ++plane;
+            WG_RUN(4, wg_couple(B, p, s));
+            src = bufs[cur]; cur ^= 1; scale = 1.f;
+        }
+        if (a.spect) rc = wg_copy(a.spect, spect, (size_t)B * n_cond * L, s);
+    }
+done:
+#undef WG_RUN
+    if (a.kernel_ms_host) {
+        for (int i = 0; i < T2_WAVEGLOW_KERNELS; ++i) a.kernel_ms_host[i] = 0.0;
+        if (rc == 0 && hipStreamSynchronize(s) != hipSuccess) { t2_set_error("t2_waveglow_infer: synchronising for the kernel times failed"); rc = -2; }
+        for (size_t i = 0; rc == 0 && i + 1 < ev.size() && i / 2 < kinds.size(); i += 2) {
+            float ms = 0.f;
+            if (hipEventElapsedTime(&ms, ev[i], ev[i + 1]) == hipSuccess) a.kernel_ms_host[kinds[i / 2]] += ms;
+        }
+        for (hipEvent_t e : ev) (void)hipEventDestroy(e);
+    }
+    return rc;
+}
+
+}  // namespace t2
+
+// ------------------------------------------------------------------------------------------------------------------
+// C ABI (include/t2amd.h)
+// ------------------------------------------------------------------------------------------------------------------
+using namespace t2;
+static_assert(T2_VOCODER_TIME_TILE == kVocTT, "t2amd.h mirrors the time tile");
+
+extern "C" {
+
+int t2_waveglow_plan(const t2_waveglow_config* cfg, int B, int T, t2_waveglow_plan_info* out) {
+    T2_REQUIRE(cfg && out, "t2_waveglow_plan: null pointer");
+    return wg_plan(*cfg, B, T, out, nullptr);
+}
+int t2_waveglow_pack(const t2_waveglow_config* cfg, const float* const* tensors_host, int n_tensors, float* packed, void* stream) {
+    T2_REQUIRE(cfg, "t2_waveglow_pack: null configuration");
+    return wg_pack_model(*cfg, tensors_host, n_tensors, packed, (hipStream_t)stream);
+}
+int t2_waveglow_infer(const t2_waveglow_config* cfg, const t2_waveglow_infer_args* a, void* stream) {
+    T2_REQUIRE(cfg && a, "t2_waveglow_infer: null pointer");
+    return wg_infer(*cfg, *a, (hipStream_t)stream);
+}
+size_t t2_waveglow_packed_floats(int kind, int rows, int k0, int k1) {
+    return kind >= kWgGated && kind <= kWgUpsample && rows > 0 && k0 > 0 && k1 >= 0 ? wg_packed_floats(kind, rows, k0, k1) : 0;
+}
+int t2_waveglow_gated_conv(const t2_waveglow_gated_args* a, void* stream) {
+    T2_REQUIRE(a, "t2_waveglow_gated_conv: null arguments");
+    T2_TRY_RC(wg_gated_check(a->B, a->nc, a->n_cond, a->L, a->d));
+    T2_REQUIRE(a->w_in && a->w_cond && a->packed_ws, "t2_waveglow_gated_conv: null weights or packing scratch");
+    T2_TRY_RC(wg_pack(kWgGated, a->w_in, a->w_cond, a->packed_ws, a->nc, a->nc, a->n_cond, (hipStream_t)stream));
+    return wg_gated(a->B, a->nc, a->n_cond, a->L, a->d, a->raw, a->x, a->spect, a->packed_ws, a->b_in, a->b_cond, a->y, (hipStream_t)stream);
+}
+int t2_waveglow_res_skip(const t2_waveglow_res_skip_args* a, void* stream) {
+    T2_REQUIRE(a, "t2_waveglow_res_skip: null arguments");
+    T2_TRY_RC(wg_check_nc("waveglow res_skip", a->nc));
+    T2_REQUIRE(a->w && a->packed_ws, "t2_waveglow_res_skip: null weights or packing scratch");
+    T2_TRY_RC(wg_pack(kWgResSkip, a->w, nullptr, a->packed_ws, a->last ? a->nc : 2 * a->nc, a->nc, 0, (hipStream_t)stream));
+    return wg_res_skip(a->B, a->nc, a->L, a->first, a->last, a->acts, a->packed_ws, a->bias, a->x, a->out, (hipStream_t)stream);
+}
+int t2_waveglow_upsample(const t2_waveglow_upsample_args* a, void* stream) {
+    T2_REQUIRE(a, "t2_waveglow_upsample: null arguments");
+    T2_REQUIRE(a->n_mel >= 1 && a->n_mel <= 512, "waveglow upsample: n_mel_channels=%d outside 1..512", a->n_mel);
+    T2_REQUIRE(a->w && a->packed_ws, "t2_waveglow_upsample: null weights or packing scratch");
+    T2_TRY_RC(wg_pack(kWgUpsample, a->w, nullptr, a->packed_ws, a->n_mel, a->n_mel, 0, (hipStream_t)stream));
+    return wg_upsample(a->B, a->n_mel, a->T, a->n_group, a->mel, a->packed_ws, a->bias, a->spect, (hipStream_t)stream);
+}
+int t2_waveglow_couple(const t2_waveglow_couple_args* a, void* stream) {
+    T2_REQUIRE(a, "t2_waveglow_couple: null arguments");
+    return wg_couple(a->B, WgCouple{a->out, a->w_end, a->b_end, a->audio_in, a->w_inverse, a->z, a->audio_out, a->audio_interleaved, a->nc, a->n_half,
+                                    a->n_early, (long)a->L, a->in_scale, a->sigma}, (hipStream_t)stream);
+}
+
+}  // extern "C"

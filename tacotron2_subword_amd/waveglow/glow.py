@@ -1,0 +1,271 @@
+"""Drop-in for the reference's ``glow.WaveGlow`` (glow.py:178-310) on the MI355X: inference only.
+
+The modules below only hold parameters, under the names and shapes the reference's checkpoints use; ``WaveGlow.infer``
+folds the weight norm (g * v / ||v||), inverts the 1x1 mixes once in fp32 (glow.py:91), hands everything to the HIP library
+(csrc/waveglow.hip) packed into the order its kernels read, and then runs the whole model through ``t2_waveglow_infer``.
+So the reference's lines work verbatim::
+
+    waveglow = torch.load(path)['model']      # or WaveGlow(**waveglow_config) + load_state_dict
+    waveglow.cuda().eval()
+    with torch.no_grad():
+        audio = waveglow.infer(mel, sigma=0.666)      # mel [B, 80, T] fp32 on the GPU -> [B, T * 256]
+
+A module that was pickled whole by the reference (its classes live in a top-level ``glow``) loads once
+``sys.modules['glow']`` points at this module; its children are then torch's own Conv1d / ConvTranspose1d, weight-normed or
+not, which ``infer`` reads just the same.  Always fp32 (``set_precision`` does not reach the vocoder), no CPU path, no
+training (``forward``, WaveGlowLoss)."""
+from __future__ import annotations
+
+import ctypes as C
+import math
+
+import torch
+from torch import nn
+
+from .. import _lib as L
+
+
+class _Conv(nn.Module):
+    """Parameters of a Conv1d [cout, cin, k] (ConvTranspose1d: [cin, cout, k]) under torch's default initialisation.  With
+    weight_norm they are ``bias``, ``weight_g`` [cout, 1, 1], ``weight_v``, as torch.nn.utils.weight_norm leaves them; without,
+    ``weight``, ``bias``."""
+
+    def __init__(self, cin, cout, k, weight_norm=True, bias=True, transposed=False, dilation=1, stride=1):
+        super().__init__()
+        self.in_channels, self.out_channels = cin, cout
+        self.kernel_size, self.dilation, self.stride = (k,), (dilation,), (stride,)
+        w = torch.empty((cin, cout, k) if transposed else (cout, cin, k))
+        nn.init.kaiming_uniform_(w, a=math.sqrt(5))
+        bound = 1.0 / math.sqrt(w.shape[1] * k)
+        if not weight_norm:
+            self.weight = nn.Parameter(w)
+        if bias:
+            self.bias = nn.Parameter(torch.empty(cout).uniform_(-bound, bound))
+        if weight_norm:
+            self.weight_g = nn.Parameter(w.flatten(1).norm(dim=1).view(-1, 1, 1))
+            self.weight_v = nn.Parameter(w)
+
+    def forward(self, x):
+        raise RuntimeError("this module only holds parameters: WaveGlow.infer runs the layers in HIP")
+
+
+def _weight_normed(mod) -> bool:
+    return "weight_g" in mod._parameters
+
+
+def _folded(mod) -> torch.Tensor:
+    """g * v / ||v|| over dim 0, as weight_norm computes it; the plain weight once the norm is removed.  Folded on the host,
+    wherever the parameters live: the norm's bits then do not depend on the device, so a module gives the same audio before
+    and after remove_weightnorm, whether that ran before or after .cuda()."""
+    if _weight_normed(mod):
+        v = mod.weight_v.detach()
+        return torch._weight_norm(v.cpu(), mod.weight_g.detach().cpu(), 0).to(v.device)
+    return mod.weight.detach()
+
+
+def _remove_weight_norm(mod):
+    if not _weight_normed(mod):
+        raise ValueError("weight_norm of 'weight' not found in {}".format(mod))
+    if not isinstance(mod, _Conv):                  # torch's own module, from a checkpoint pickled by the reference
+        return torch.nn.utils.remove_weight_norm(mod)
+    w = _folded(mod)
+    del mod._parameters["weight_g"], mod._parameters["weight_v"]
+    mod.weight = nn.Parameter(w)                     # the reference's order after removal: bias, weight
+    return mod
+
+
+class Invertible1x1Conv(nn.Module):
+    """Parameters of glow.py:62-80: ``conv.weight`` [c, c, 1], a random orthonormal matrix of determinant 1."""
+
+    def __init__(self, c):
+        super().__init__()
+        self.conv = _Conv(c, c, 1, weight_norm=False, bias=False)
+        W = torch.linalg.qr(torch.empty(c, c).normal_())[0]
+        if torch.det(W) < 0:
+            W[:, 0] = -1 * W[:, 0]
+        self.conv.weight.data = W.view(c, c, 1).contiguous()
+
+    def forward(self, z, reverse=False):
+        raise RuntimeError("this module only holds parameters: WaveGlow.infer applies the inverse in HIP")
+
+
+class WN(nn.Module):
+    """Parameters of glow.py:105-151, registered in the reference's order."""
+
+    def __init__(self, n_in_channels, n_mel_channels, n_layers, n_channels, kernel_size):
+        super().__init__()
+        assert kernel_size % 2 == 1
+        assert n_channels % 2 == 0
+        self.n_layers = n_layers
+        self.n_channels = n_channels
+        self.in_layers = nn.ModuleList()
+        self.res_skip_layers = nn.ModuleList()
+        self.start = _Conv(n_in_channels, n_channels, 1)
+        # the reference starts `end` at zero, so that a fresh coupling is the identity
+        self.end = _Conv(n_channels, 2 * n_in_channels, 1, weight_norm=False)
+        self.end.weight.data.zero_()
+        self.end.bias.data.zero_()
+        self.cond_layer = _Conv(n_mel_channels, 2 * n_channels * n_layers, 1)
+        for i in range(n_layers):
+            self.in_layers.append(_Conv(n_channels, 2 * n_channels, kernel_size, dilation=2 ** i))
+            self.res_skip_layers.append(_Conv(n_channels, 2 * n_channels if i < n_layers - 1 else n_channels, 1))
+
+    def forward(self, forward_input):
+        raise RuntimeError("this module only holds parameters: WaveGlow.infer runs the layers in HIP")
+
+
+class WaveGlow(nn.Module):
+    def __init__(self, n_mel_channels, n_flows, n_group, n_early_every, n_early_size, WN_config):
+        super().__init__()
+        assert n_group % 2 == 0
+        L.waveglow_plan(L.waveglow_config(n_mel_channels, n_flows, n_group, n_early_every, n_early_size, WN_config), 1, 1)   # refuses here, by name
+        self.upsample = _Conv(n_mel_channels, n_mel_channels, 1024, weight_norm=False, transposed=True, stride=256)
+        self.n_flows = n_flows
+        self.n_group = n_group
+        self.n_early_every = n_early_every
+        self.n_early_size = n_early_size
+        self.WN = nn.ModuleList()
+        self.convinv = nn.ModuleList()
+        n_half = int(n_group / 2)
+        n_remaining_channels = n_group
+        for k in range(n_flows):
+            if k % self.n_early_every == 0 and k > 0:
+                n_half = n_half - int(self.n_early_size / 2)
+                n_remaining_channels = n_remaining_channels - self.n_early_size
+            self.convinv.append(Invertible1x1Conv(n_remaining_channels))
+            self.WN.append(WN(n_half, n_mel_channels * n_group, **WN_config))
+        self.n_remaining_channels = n_remaining_channels
+
+    # ---- the cache of packed weights lives outside the pickled state and outside what __init__ sets, so that a module
+    # unpickled from a checkpoint (no __init__) works too
+    def __getstate__(self):
+        state = dict(self.__dict__)
+        state.pop("_packed", None), state.pop("_packed_key", None)
+        return state
+
+    def _config(self) -> L.WaveglowConfig:
+        wn = self.WN[0]
+        if not hasattr(wn, "cond_layer"):
+            raise RuntimeError("WaveGlow: this module keeps one cond_layer per layer (WN.cond_layers), the older layout of the "
+                               "reference's waveglow/glow.py; convert it to the single cond_layer of glow.py:132 first")
+        k = wn.in_layers[0].kernel_size
+        return L.waveglow_config(self.upsample.in_channels, self.n_flows, self.n_group, self.n_early_every, self.n_early_size,
+                                 dict(n_layers=wn.n_layers, n_channels=wn.n_channels, kernel_size=k[0] if isinstance(k, (tuple, list)) else k))
+
+    def forward(self, forward_input):
+        raise RuntimeError("WaveGlow is inference only here: forward (the training direction, audio -> z) is not built; call infer")
+
+    @staticmethod
+    def remove_weightnorm(model):
+        waveglow = model
+        for wn in waveglow.WN:
+            _remove_weight_norm(wn.start)
+            for l in list(wn.in_layers) + list(wn.res_skip_layers):
+                _remove_weight_norm(l)
+            _remove_weight_norm(wn.cond_layer)
+        waveglow._packed = None
+        return waveglow
+
+    def load_state_dict(self, *args, **kwargs):
+        out = super().load_state_dict(*args, **kwargs)
+        self._packed = None
+        return out
+
+    def _apply(self, fn, *args, **kwargs):               # .to() / .cuda() / .float()
+        out = super()._apply(fn, *args, **kwargs)
+        self._packed = None
+        return out
+
+    def _key(self):
+        return tuple((p.data_ptr(), p._version) for p in self.parameters())
+
+    def _tensors(self):
+        """The folded weights in the order t2_waveglow_pack takes them."""
+        f32 = lambda t: t.detach().to(torch.float32).contiguous()
+        out = [f32(self.upsample.weight), f32(self.upsample.bias)]
+        for wn, inv in zip(self.WN, self.convinv):
+            out += [f32(_folded(wn.start)), f32(wn.start.bias), f32(_folded(wn.cond_layer)), f32(wn.cond_layer.bias)]
+            for l in wn.in_layers:
+                out += [f32(_folded(l)), f32(l.bias)]
+            for l in wn.res_skip_layers:
+                out += [f32(_folded(l)), f32(l.bias)]
+            W = inv.conv.weight.detach().squeeze(-1)
+            out += [f32(wn.end.weight), f32(wn.end.bias), f32(W.float().inverse())]     # glow.py:91
+        return out
+
+    def repack(self):
+        """Fold, invert and pack the weights again.  infer() does this by itself after load_state_dict, remove_weightnorm,
+        .to() and in-place updates that autograd sees; call it after editing parameters behind autograd's back (``.data``)."""
+        dev = self.upsample.weight.device
+        if dev.type != "cuda":
+            raise RuntimeError("WaveGlow: the parameters must live on the GPU (the product path has no CPU fallback)")
+        cfg = self._config()
+        plan = L.waveglow_plan(cfg, 1, 1)
+        with torch.no_grad():
+            ts = self._tensors()
+        packed = torch.empty(plan.packed_bytes // 4, device=dev, dtype=torch.float32)
+        tp = (C.c_void_p * len(ts))(*[L.ptr(t) for t in ts])
+        with torch.cuda.device(dev):
+            L.check(L.lib().t2_waveglow_pack(C.byref(cfg), tp, len(ts), L.ptr(packed), L.stream()))
+        self._packed, self._packed_key = packed, self._key()
+        return self
+
+    def infer(self, spect, sigma=1.0, noise=None):
+        """mel [B, n_mel_channels, T], fp32, on the GPU -> audio [B, T * 256] (glow.py:251-293).  The noise planes are drawn
+        on the device in the reference's order -- [B, n_remaining_channels, L] first, then one [B, n_early_size, L] per early
+        flow, k descending -- also when sigma == 0, so that a seeded script consumes the generator as the reference does.
+        ``noise`` (an addition) supplies them instead."""
+        return self.infer_debug(spect, sigma, noise)[0]
+
+    def infer_debug(self, spect, sigma=1.0, noise=None, debug=False, kernel_times=False):
+        """infer, returning (audio, info).  debug: info holds ``spect`` [B, n_mel*G, L] (the upsampled, regrouped mel) and
+        ``flow_audio`` [B, G, L] (the tensor after the last flow).  kernel_times: info holds ``kernel_ms``, the time spent in
+        every kind of kernel (each launch bracketed by events: slower than a plain call)."""
+        if not spect.is_cuda:
+            raise RuntimeError("WaveGlow.infer: the mel must live on the GPU, as the reference's torch.cuda.FloatTensor noise "
+                               "requires (the product path has no CPU fallback)")
+        if torch.is_grad_enabled() and (spect.requires_grad or any(p.requires_grad for p in self.parameters())):
+            raise RuntimeError("WaveGlow.infer is inference only: grad mode is on and the mel or the parameters require grad; "
+                               "call it under torch.no_grad(), as inference.py:166 does")
+        cfg = self._config()
+        if spect.dim() != 3 or spect.shape[1] != cfg.n_mel_channels:
+            raise RuntimeError(f"WaveGlow.infer: expected a mel of shape [B, {cfg.n_mel_channels}, T] (upsample takes "
+                               f"{cfg.n_mel_channels} channels), got {tuple(spect.shape)}")
+        if spect.dtype != torch.float32:
+            raise RuntimeError(f"WaveGlow.infer: the mel must be float32, got {spect.dtype} (fp16 inference is not built)")
+        packed = getattr(self, "_packed", None)
+        if packed is None or packed.device != spect.device or getattr(self, "_packed_key", None) != self._key():
+            self.repack()
+            packed = self._packed
+            if packed.device != spect.device:
+                raise RuntimeError(f"WaveGlow.infer: the mel is on {spect.device}, the parameters on {packed.device}")
+        B, n_mel, T = spect.shape
+        plan = L.waveglow_plan(cfg, B, T)
+        shapes = [(B, plan.n_remaining_channels, plan.L)] + [(B, cfg.n_early_size, plan.L)] * (plan.n_noise_planes - 1)
+        with torch.cuda.device(spect.device):
+            if noise is None:
+                noise = [torch.empty(s, device=spect.device, dtype=torch.float32).normal_() for s in shapes]
+            else:
+                noise = list(noise)
+                if len(noise) != len(shapes):
+                    raise RuntimeError(f"WaveGlow.infer: {len(noise)} noise planes given, the model draws {len(shapes)}")
+                for z, s in zip(noise, shapes):
+                    if tuple(z.shape) != s or z.dtype != torch.float32 or z.device != spect.device:
+                        raise RuntimeError(f"WaveGlow.infer: a noise plane is {tuple(z.shape)} {z.dtype} on {z.device}, "
+                                           f"expected {s} float32 on {spect.device}")
+                noise = [z.detach().contiguous() for z in noise]
+            mel = spect.detach().contiguous()
+            ws = torch.empty(plan.workspace_bytes // 4, device=spect.device, dtype=torch.float32)
+            audio = torch.empty(B, plan.out_len, device=spect.device, dtype=torch.float32)
+            info = {}
+            if debug:
+                info["spect"] = torch.empty(B, n_mel * cfg.n_group, plan.L, device=spect.device, dtype=torch.float32)
+                info["flow_audio"] = torch.empty(B, cfg.n_group, plan.L, device=spect.device, dtype=torch.float32)
+            ms = (C.c_double * len(L.WAVEGLOW_KERNELS))() if kernel_times else None
+            planes = (C.c_void_p * len(noise))(*[L.ptr(z) for z in noise])
+            a = L.WaveglowInferArgs(B, T, n_mel, L.ptr(packed), L.ptr(mel), planes, len(noise), float(sigma), L.ptr(ws), L.ptr(audio),
+                                    L.ptr(info.get("spect")), L.ptr(info.get("flow_audio")), ms)
+            L.check(L.lib().t2_waveglow_infer(C.byref(cfg), C.byref(a), L.stream()))
+        if kernel_times:
+            info["kernel_ms"] = dict(zip(L.WAVEGLOW_KERNELS, ms))
+        return audio, info
