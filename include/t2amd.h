@@ -729,6 +729,58 @@ typedef struct t2_stft_synthesis_args {
 } t2_stft_synthesis_args;
 int t2_stft_synthesis(const t2_stft_synthesis_args* a, void* stream);
 
+/* ---- Log-mel front end (ragged waveforms -> log-mel spectrograms) -----------------------------------
+ * Replaces the reference's layers.py: TacotronSTFT.mel_spectrogram (:60-80) with stft.py: STFT.transform (:77-105) and
+ * audio_processing.py: dynamic_range_compression (:78-84); utils.py: mel_spectrogram's pad, torch.stft(center=False),
+ * sqrt(re^2 + im^2 + 1e-9), mel matmul and log (:73-79); and so the mel extraction of Audio/tools.py: get_mel (:30-42),
+ * GTA.py:48, softdtw.py:78-79 and best_checkpoint.py:426-427.  One kernel:
+ *   out[b][m][f] = log(max(clip_val, sum_bin mel[m][bin] * sqrt(re^2 + im^2 + mag_eps)) * C),
+ *   (re, im)[bin][f] = sum_k forward_basis[.][k] * xpad_b[f*hop + k],
+ * xpad_b = the first len_b samples of row b reflect-padded by `pad` per side (index arithmetic, no copy); an item has
+ * nf_b = (len_b + 2*pad - N) / hop + 1 frames, or none when len_b <= pad or len_b + 2*pad < N.
+ *   pad = N/2, mag_eps = 0:          the TacotronSTFT convention (layers.py:76-79, stft.py:84-103), 1 + len/hop frames;
+ *   pad = (N - hop)/2, mag_eps = 1e-9: the utils.mel_spectrogram convention (utils.py:73-79).
+ * Always exact fp32 on the matrix cores, whatever t2_set_precision says.  The magnitudes never reach memory.  The mel sum
+ * is formed per pass of 64 bins from zero and the passes are added in ascending order, one rounded add each: the bits do not
+ * depend on the launch shape (splits), and an item alone equals the item inside a batch.  No atomics.
+ * Supported: even N up to 4096, 1 <= hop <= N, 0 <= pad <= N/2, n_mels up to 128, n + 2*pad >= N, n <= INT32_MAX/2.
+ * Everything else is refused with the offending name and value in t2_last_error. */
+typedef struct t2_melspec_plan_info {
+    int bins;                     /* N/2 + 1 */
+    int passes;                   /* ceil(bins / 64): bins whose magnitudes one pass holds on the chip */
+    int frame_tile;               /* T2_STFT_FRAME_TILE frames per workgroup */
+    int row_tiles;                /* ceil(n_mels / 32) */
+    int splits;                   /* contiguous pass ranges the plan spreads over workgroups (1: one launch, no scratch) */
+    long nf_max;                  /* frames of a full row: (n + 2*pad - N) / hop + 1 */
+    long frame_tiles;
+    size_t fwd_floats;            /* packed forward basis (t2_stft_pack's order) */
+    size_t mel_floats;            /* packed mel table */
+    size_t packed_bytes;          /* both, in that order */
+    size_t scratch_floats;        /* what t2_melspec needs with force_splits = 0: 0 when splits == 1 */
+    size_t split_scratch_floats;  /* what any split launch needs: passes * B * nf_max * n_mels */
+} t2_melspec_plan_info;
+/* Pure host call (no device).  n: samples per row of x. */
+int t2_melspec_plan(int N, int hop, int pad, int n_mels, long n, int B, t2_melspec_plan_info* out);
+/* forward_basis [2*(N/2+1)][N] (the STFT module's windowed buffer, stft.py:74), mel_basis [n_mels][N/2+1]
+ * (layers.py:48-51).  Device pointers.  Writes `packed` (packed_bytes); once per module, not per call. */
+int t2_melspec_pack(int N, int n_mels, const float* forward_basis, const float* mel_basis, float* packed, void* stream);
+typedef struct t2_melspec_args {
+    int B, N, hop, pad, n_mels;
+    long n;                       /* samples per row of x */
+    const float* x;               /* [B, n] */
+    const int* lengths;           /* [B] int32 on the device, or NULL (every item has n samples); clamped to [0, n] */
+    const float* packed;
+    float* out;                   /* [B, n_mels, nf_max], or [B, nf_max, n_mels] with time_major; frames >= nf_b hold pad_value */
+    float* scratch;               /* split launches only */
+    size_t scratch_floats;
+    int* frame_lengths;           /* [B] int32: nf_b, or NULL */
+    float mag_eps, clip_val, C, pad_value;
+    int time_major;
+    int return_power;             /* tests: magnitude^2 instead of the magnitude and no clamp / log: out = sum_bin mel * (re^2 + im^2 + mag_eps) */
+    int force_splits;             /* 0: the plan's splits; 1..passes: that many (tests: the bits do not depend on it) */
+} t2_melspec_args;
+int t2_melspec(const t2_melspec_args* a, void* stream);
+
 /* ---- WaveGlow inference (mel spectrogram -> waveform) ------------------------------------------------
  * Replaces the reference's glow.py: WaveGlow.infer (:251-293), WN.forward (:153-175) and
  * Invertible1x1Conv.forward(reverse=True) (:88-97), as inference.py:160-170 and best_checkpoint.py:179-189 call them and as

@@ -283,6 +283,21 @@ class StftSynthesisArgs(C.Structure):
 STFT_FRAME_TILE = 32         # include/t2amd.h T2_STFT_FRAME_TILE
 STFT_POLAR, STFT_DENOISE = 0, 1
 
+
+class MelspecPlanInfo(C.Structure):
+    _fields_ = [("bins", C.c_int), ("passes", C.c_int), ("frame_tile", C.c_int), ("row_tiles", C.c_int), ("splits", C.c_int),
+                ("nf_max", C.c_long), ("frame_tiles", C.c_long), ("fwd_floats", C.c_size_t), ("mel_floats", C.c_size_t),
+                ("packed_bytes", C.c_size_t), ("scratch_floats", C.c_size_t), ("split_scratch_floats", C.c_size_t)]
+
+
+class MelspecArgs(C.Structure):
+    _fields_ = [("B", C.c_int), ("N", C.c_int), ("hop", C.c_int), ("pad", C.c_int), ("n_mels", C.c_int), ("n", C.c_long),
+                ("x", C.c_void_p), ("lengths", C.c_void_p), ("packed", C.c_void_p), ("out", C.c_void_p), ("scratch", C.c_void_p),
+                ("scratch_floats", C.c_size_t), ("frame_lengths", C.c_void_p),
+                ("mag_eps", C.c_float), ("clip_val", C.c_float), ("C", C.c_float), ("pad_value", C.c_float),
+                ("time_major", C.c_int), ("return_power", C.c_int), ("force_splits", C.c_int)]
+
+
 class WaveglowConfig(C.Structure):
     _fields_ = [("n_mel_channels", C.c_int), ("n_flows", C.c_int), ("n_group", C.c_int), ("n_early_every", C.c_int), ("n_early_size", C.c_int),
                 ("n_layers", C.c_int), ("n_channels", C.c_int), ("kernel_size", C.c_int)]
@@ -335,7 +350,7 @@ EXPORTS = ["t2_last_error", "t2_version", "t2_chain_status", "t2_chain_status_cl
            "t2_finalize_bct", "t2_mask_bt", "t2_gemm", "t2_rng_keep_mask", "t2_rng_normal",
            "t2_softdtw_plan", "t2_softdtw_dist", "t2_softdtw_forward", "t2_softdtw_backward", "t2_softdtw_dist_backward",
            "t2_hifigan_plan", "t2_hifigan_pack", "t2_hifigan_forward", "t2_vocoder_packed_floats", "t2_vocoder_conv1d", "t2_vocoder_conv_transpose1d",
-           "t2_stft_plan", "t2_stft_pack", "t2_stft_analysis", "t2_stft_synthesis",
+           "t2_stft_plan", "t2_stft_pack", "t2_stft_analysis", "t2_stft_synthesis", "t2_melspec_plan", "t2_melspec_pack", "t2_melspec",
            "t2_waveglow_plan", "t2_waveglow_pack", "t2_waveglow_infer", "t2_waveglow_packed_floats", "t2_waveglow_gated_conv", "t2_waveglow_res_skip",
            "t2_waveglow_upsample", "t2_waveglow_couple"]
 
@@ -408,6 +423,9 @@ def lib() -> C.CDLL:
         L.t2_stft_pack.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.t2_stft_analysis.argtypes = [C.POINTER(StftAnalysisArgs), C.c_void_p]
         L.t2_stft_synthesis.argtypes = [C.POINTER(StftSynthesisArgs), C.c_void_p]
+        L.t2_melspec_plan.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_long, C.c_int, C.POINTER(MelspecPlanInfo)]
+        L.t2_melspec_pack.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.t2_melspec.argtypes = [C.POINTER(MelspecArgs), C.c_void_p]
         L.t2_waveglow_plan.argtypes = [C.POINTER(WaveglowConfig), C.c_int, C.c_int, C.POINTER(WaveglowPlanInfo)]
         L.t2_waveglow_pack.argtypes = [C.POINTER(WaveglowConfig), C.POINTER(C.c_void_p), C.c_int, C.c_void_p, C.c_void_p]
         L.t2_waveglow_infer.argtypes = [C.POINTER(WaveglowConfig), C.POINTER(WaveglowInferArgs), C.c_void_p]
@@ -819,6 +837,14 @@ def stft_plan(N: int, hop: int, nf: int = 1) -> StftPlanInfo:
     the reason for odd N, N % hop != 0 and sizes the kernels do not take."""
     info = StftPlanInfo()
     check(lib().t2_stft_plan(N, hop, nf, C.byref(info)))
+    return info
+
+
+def melspec_plan(N: int, hop: int, pad: int, n_mels: int, n: int, B: int = 1) -> MelspecPlanInfo:
+    """Bins, passes, frames of a full row, the splits the launch takes and the table and scratch sizes (t2_melspec_plan: pure
+    host, no device needed); raises with the name and value of what the kernel does not take."""
+    info = MelspecPlanInfo()
+    check(lib().t2_melspec_plan(N, hop, pad, n_mels, n, B, C.byref(info)))
     return info
 
 

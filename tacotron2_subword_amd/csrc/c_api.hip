@@ -610,6 +610,25 @@ int t2_stft_synthesis(const t2_stft_synthesis_args* a, void* stream) {
     return stft_synthesis(StftSynthesis{a->B, a->N, a->hop, a->nf, a->mode, a->windowed, a->a, a->b, a->bias, a->strength, a->packed, a->y}, (hipStream_t)stream);
 }
 
+int t2_melspec_plan(int N, int hop, int pad, int n_mels, long n, int B, t2_melspec_plan_info* out) {
+    T2_REQUIRE(out, "t2_melspec_plan: null pointer");
+    MelPlan p;
+    T2_TRY(melspec_plan(N, hop, pad, n_mels, n, B, &p));
+    out->bins = p.cutoff; out->passes = p.passes; out->frame_tile = kStftTile; out->row_tiles = p.row_tiles; out->splits = p.splits;
+    out->nf_max = p.nf_max; out->frame_tiles = p.frame_tiles; out->fwd_floats = p.fwd_floats; out->mel_floats = p.mel_floats;
+    out->packed_bytes = (p.fwd_floats + p.mel_floats) * sizeof(float);
+    out->scratch_floats = p.splits > 1 ? p.split_scratch_floats : 0; out->split_scratch_floats = p.split_scratch_floats;
+    return 0;
+}
+int t2_melspec_pack(int N, int n_mels, const float* forward_basis, const float* mel_basis, float* packed, void* stream) {
+    return melspec_pack(N, n_mels, forward_basis, mel_basis, packed, (hipStream_t)stream);
+}
+int t2_melspec(const t2_melspec_args* a, void* stream) {
+    T2_REQUIRE(a, "t2_melspec: null arguments");
+    return melspec(MelSpecArgs{a->B, a->N, a->hop, a->pad, a->n_mels, a->n, a->x, a->lengths, a->packed, a->out, a->scratch, a->scratch_floats, a->frame_lengths,
+                               a->mag_eps, a->clip_val, a->C, a->pad_value, a->time_major, a->return_power, a->force_splits}, (hipStream_t)stream);
+}
+
 int t2_prof_enable(int max_launches) {
     if (max_launches <= 0) { g_prof.on = false; return 0; }
     const size_t need = (size_t)max_launches * 2;

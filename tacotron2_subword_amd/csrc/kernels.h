@@ -517,6 +517,34 @@ int stft_analysis(const StftAnalysis& a, hipStream_t s);
 // y [B, 1, hop*(nf-1)].  windowed = 0 skips the envelope division and the N/hop scale (STFT(window=None), stft.py:117).
 struct StftSynthesis { int B, N, hop, nf, mode, windowed; const float* a; const float* b; const float* bias; float strength; const float* packed; float* y; };
 int stft_synthesis(const StftSynthesis& a, hipStream_t s);
+// the forward part of stft_pack alone (any hop): fwd [2*(N/2+1)][N] -> packed, ((N/2+1 + 15)/16) * ((N + 31)/32) * 1024 floats
+int stft_pack_forward(int N, const float* fwd, float* packed, hipStream_t s);
+
+// ------------------------------------------------------------------ log-mel front end (melspec.hip)
+constexpr int kMelMaxMels = 128;                 // four waves x 32 mel rows
+constexpr int kMelPassBins = 64;                 // bins whose magnitudes one pass holds in LDS: four waves x 16
+// Measured (profiles/README.md "Log-mel front end"): a frame tile alone on its CU takes 0.30 ms at 1024/513, and every launch
+// of fewer than 3 workgroups per CU ran faster with its passes split, fastest with one pass per workgroup (an uneven split,
+// 7 ranges over 9 passes, was slower than 3 even ones).
+constexpr int kMelSplitBelow = 768;              // frame tiles x B below which every pass gets a workgroup of its own
+// frames of an item of `len` samples: reflect padding needs len > pad, a frame needs len + 2*pad >= N
+__host__ __device__ inline long mel_frames(long len, int N, int hop, int pad) {
+    return (len > pad && len + 2L * pad >= N) ? (len + 2L * pad - N) / hop + 1 : 0;
+}
+// Sizes in floats; the packed buffer is [forward (stft_pack's order) | mel].
+struct MelPlan { int cutoff, bin_tiles, kchunks, passes, row_tiles, splits; long nf_max, frame_tiles; size_t fwd_floats, mel_floats, split_scratch_floats; };
+int melspec_plan(int N, int hop, int pad, int n_mels, long n, int B, MelPlan* out);   // validates; no device
+// fwd: the windowed forward basis [2*(N/2+1)][N]; melb [n_mels][N/2+1]
+int melspec_pack(int N, int n_mels, const float* fwd, const float* melb, float* packed, hipStream_t s);
+// x [B, n], lengths [B] int32 nullable -> out [B, n_mels, nf_max] or time-major [B, nf_max, n_mels]; frame_lengths [B] int32 nullable.
+// scratch: split_scratch_floats floats when the launch splits (force_splits > 1, or 0 and the plan's splits > 1).
+struct MelSpecArgs {
+    int B, N, hop, pad, n_mels; long n;
+    const float* x; const int* lengths; const float* packed; float* out; float* scratch; size_t scratch_floats; int* frame_lengths;
+    float mag_eps, clip_val, C, pad_value;
+    int time_major, return_power, force_splits;
+};
+int melspec(const MelSpecArgs& a, hipStream_t s);
 
 // ------------------------------------------------------------------ optimizer (optim.hip)
 struct AdamTensor { float* p; const float* g; float* m; float* v; long numel; int first_chunk; int pad_; };   // 48 bytes, mirrors t2_adam_tensor

@@ -230,12 +230,20 @@ int stft_plan(int N, int hop, int nf, StftPlan* out) {
     return 0;
 }
 
+int stft_pack_forward(int N, const float* fwd, float* packed, hipStream_t s) {
+    StftPlan pl;
+    T2_TRY_RC(stft_plan(N, N, 1, &pl));                         // the forward table does not depend on the hop
+    T2_REQUIRE(fwd && packed, "stft_pack_forward: null pointer");
+    hipLaunchKernelGGL(stft_pack_fwd_kernel, dim3((unsigned)((pl.fwd_floats + 255) / 256)), dim3(256), 0, s, fwd, packed, N, pl.cutoff, pl.kchunks, pl.fwd_floats);
+    T2_LAUNCH_CHECK();
+    return 0;
+}
+
 int stft_pack(int N, int hop, const float* fwd, const float* inv, const double* wsq, float* packed, hipStream_t s) {
     StftPlan pl;
     T2_TRY_RC(stft_plan(N, hop, 1, &pl));
     T2_REQUIRE(fwd && inv && packed, "stft_pack: null pointer");
-    hipLaunchKernelGGL(stft_pack_fwd_kernel, dim3((unsigned)((pl.fwd_floats + 255) / 256)), dim3(256), 0, s, fwd, packed, N, pl.cutoff, pl.kchunks, pl.fwd_floats);
-    T2_LAUNCH_CHECK();
+    T2_TRY_RC(stft_pack_forward(N, fwd, packed, s));
     hipLaunchKernelGGL(stft_pack_inv_kernel, dim3((unsigned)((pl.inv_floats + 255) / 256)), dim3(256), 0, s, inv, packed + pl.fwd_floats, N, hop, pl.cutoff,
                        pl.bin_tiles, pl.inv_floats);
     T2_LAUNCH_CHECK();

@@ -14,6 +14,12 @@ N/hop scale and the trim in its epilogue: one launch.  The module-level `analysi
 kernels' entry points (bias_remover.py uses them; the tests drive them with bases of their own).  On CPU tensors
 `inverse` is the torch formula, for the same comparison only.
 
+`log_mel` is the whole mel front end in one launch of csrc/melspec.hip (DESIGN.md "Log-mel front end"): framing with
+reflect padding as index arithmetic on each item's own length, the Fourier and the mel product on the fp32 matrix cores
+with the magnitudes kept in LDS between them, clamp and log in the epilogue.  `TacotronSTFT.mel_spectrogram` goes through
+it for CUDA tensors (layers.py:60-80), `utils.mel_spectrogram` with the HiFi-GAN convention's padding (utils.py:73-79);
+`STFT.transform` itself is unchanged.
+
 The mel filterbank restates librosa.filters.mel (Slaney mel scale, Slaney area normalisation), which the reference
 calls as librosa_mel_fn(sampling_rate, filter_length, n_mel_channels, mel_fmin, mel_fmax) (layers.py:48-49).  librosa is
 not installed here, so the filterbank itself is "parity unpinned" (property tests only); the STFT magnitudes are pinned
@@ -133,6 +139,97 @@ def synthesis(a, b, packed, filter_length, hop_length, mode=0, bias=None, streng
     return y
 
 
+def pack_mel_tables(forward_basis, mel_basis, filter_length):
+    """The tables of csrc/melspec.hip (t2_melspec_pack): forward_basis [2*(N/2+1), N] and mel_basis [n_mels, N/2+1], fp32
+    on the GPU."""
+    from . import _lib as L
+    bins = filter_length // 2 + 1
+    if tuple(forward_basis.shape) != (2 * bins, filter_length) or forward_basis.dtype != torch.float32:
+        raise RuntimeError(f"log_mel: forward_basis must be float32 [{2 * bins}, {filter_length}], got {forward_basis.dtype} {tuple(forward_basis.shape)}")
+    if mel_basis.dim() != 2 or mel_basis.shape[1] != bins or mel_basis.dtype != torch.float32:
+        raise RuntimeError(f"log_mel: mel_basis must be float32 [n_mels, {bins}], got {mel_basis.dtype} {tuple(mel_basis.shape)}")
+    if mel_basis.device != forward_basis.device:
+        raise RuntimeError(f"log_mel: mel_basis is on {mel_basis.device}, the STFT module on {forward_basis.device}")
+    n_mels = int(mel_basis.shape[0])
+    plan = L.melspec_plan(filter_length, filter_length, filter_length // 2, n_mels, filter_length)
+    dev = forward_basis.device
+    with torch.cuda.device(dev):
+        packed = torch.empty(plan.packed_bytes // 4, device=dev, dtype=torch.float32)
+        L.check(L.lib().t2_melspec_pack(filter_length, n_mels, L.ptr(forward_basis.detach().contiguous()), L.ptr(mel_basis.detach().contiguous()),
+                                        L.ptr(packed), L.stream()))
+    return packed
+
+
+def log_mel(x, stft_module, mel_basis, lengths=None, pad=None, mag_eps=0.0, clip_val=1e-5, C=1, time_major=False, pad_value=0.0,
+            *, force_splits=0, return_power=False, out=None, scratch=None):
+    """x [B, n] fp32 on the GPU -> (mel, frame_lengths) from one launch of csrc/melspec.hip:
+        mel[b, m, f] = log(max(clip_val, sum_bin mel_basis[m, bin] * sqrt(re^2 + im^2 + mag_eps)) * C)
+    over the frames of x[b, :lengths[b]] reflect-padded by `pad` per side.  pad=None is filter_length/2 (TacotronSTFT,
+    layers.py:76-79); pad=(N - hop)/2 with mag_eps=1e-9 is utils.mel_spectrogram's torch.stft(center=False) (utils.py:73-79).
+    mel is [B, n_mels, nf_max], or [B, nf_max, n_mels] with time_major (what SoftDTW takes); nf_max follows from n.  Frames
+    past an item's own count hold pad_value.  lengths: None, an int32 device tensor [B] (clamped to [0, n] by the kernel, no
+    host sync; an item of <= pad samples has no frames), or Python ints, which are checked here: a too-short item raises in
+    torch's reflect-pad words.  frame_lengths is an int32 device tensor [B], or None when lengths is.
+    The keyword-only arguments are for the tests: force_splits (the launch shape; the bits do not depend on it), return_power
+    (the mel sum over re^2 + im^2 + mag_eps, no clamp and no log), and caller-owned out / scratch buffers."""
+    from . import _lib as L
+    N, hop = stft_module.filter_length, stft_module.hop_length
+    pad = N // 2 if pad is None else int(pad)
+    if not isinstance(x, torch.Tensor) or x.dim() != 2 or x.dtype != torch.float32:
+        raise RuntimeError(f"log_mel: expected a float32 signal [B, n], got {getattr(x, 'dtype', type(x))} {tuple(getattr(x, 'shape', ()))}")
+    if not x.is_cuda:
+        raise RuntimeError("log_mel: the signal must live on the GPU (there is no CPU path; TacotronSTFT.mel_spectrogram keeps the torch formula for CPU tensors)")
+    if torch.is_grad_enabled() and x.requires_grad:
+        raise RuntimeError("log_mel is inference only: the input requires grad and grad mode is on; call it under torch.no_grad() or detach the input")
+    if stft_module.forward_basis.device != x.device:
+        raise RuntimeError(f"log_mel: the input is on {x.device}, the STFT module on {stft_module.forward_basis.device}")
+    B, n = x.shape
+    n_mels = int(mel_basis.shape[0])
+
+    def too_short(what, length):
+        return RuntimeError(f"Padding size should be less than the corresponding input dimension, but got: padding ({pad}, {pad}) "
+                            f"at dimension 1 of {what} of {length} samples")
+
+    if n <= pad:
+        raise too_short(f"input {list(x.shape)}", n)
+    plan = L.melspec_plan(N, hop, pad, n_mels, n, B)
+    dev = x.device
+    if lengths is not None and not isinstance(lengths, torch.Tensor):
+        lengths = [int(v) for v in lengths]
+        if len(lengths) != B:
+            raise RuntimeError(f"log_mel: {len(lengths)} lengths for a batch of {B}")
+        for i, v in enumerate(lengths):
+            if v > n:
+                raise RuntimeError(f"log_mel: lengths[{i}]={v} exceeds the {n} samples of a row")
+            if v <= pad:
+                raise too_short(f"item {i}", v)
+            if v + 2 * pad < N:
+                raise RuntimeError(f"log_mel: lengths[{i}]={v} with pad={pad} per side does not fill one frame of filter_length={N}")
+        lengths = torch.tensor(lengths, dtype=torch.int32).to(dev)
+    if lengths is not None:
+        if lengths.dtype != torch.int32 or tuple(lengths.shape) != (B,) or lengths.device != dev:
+            raise RuntimeError(f"log_mel: lengths must be int32 [{B}] on {dev}, got {lengths.dtype} {tuple(lengths.shape)} on {lengths.device}")
+        lengths = lengths.contiguous()
+    splits = int(force_splits) if force_splits else plan.splits
+    shape = (B, plan.nf_max, n_mels) if time_major else (B, n_mels, plan.nf_max)
+    x = x.detach().contiguous()
+    with torch.cuda.device(dev):
+        if out is None:
+            out = torch.empty(shape, device=dev, dtype=torch.float32)
+        elif tuple(out.shape) != shape or out.dtype != torch.float32 or out.device != dev:
+            raise RuntimeError(f"log_mel: out must be float32 {shape} on {dev}, got {out.dtype} {tuple(out.shape)} on {out.device}")
+        if splits > 1 and scratch is None:
+            scratch = torch.empty(plan.split_scratch_floats, device=dev, dtype=torch.float32)
+        if scratch is not None and (scratch.dtype != torch.float32 or scratch.device != dev):
+            raise RuntimeError(f"log_mel: scratch must be float32 on {dev}, got {scratch.dtype} on {scratch.device}")
+        frame_lengths = None if lengths is None else torch.empty(B, device=dev, dtype=torch.int32)
+        a = L.MelspecArgs(B, N, hop, pad, n_mels, n, L.ptr(x), L.ptr(lengths), L.ptr(stft_module.mel_tables(mel_basis)), L.ptr(out),
+                          L.ptr(scratch), 0 if scratch is None else scratch.numel(), L.ptr(frame_lengths),
+                          float(mag_eps), float(clip_val), float(C), float(pad_value), int(bool(time_major)), int(bool(return_power)), int(force_splits))
+        L.check(L.lib().t2_melspec(a, L.stream()))
+    return out, frame_lengths
+
+
 class STFT(torch.nn.Module):
     def __init__(self, filter_length=800, hop_length=200, win_length=800, window="hann"):
         super().__init__()
@@ -152,10 +249,14 @@ class STFT(torch.nn.Module):
         self.register_buffer("inverse_basis", inverse_basis.float())       # [2*cutoff, 1, N], likewise
         self._packed = None
         self._packed_key = None
+        self._mel_packed = None
+        self._mel_basis = None
+        self._mel_key = None
 
     def _apply(self, fn, *args, **kwargs):                                  # .to() / .cuda(): the packed tables follow the buffers
         out = super()._apply(fn, *args, **kwargs)
         self._packed = None
+        self._mel_packed = None
         return out
 
     def _key(self):
@@ -178,6 +279,18 @@ class STFT(torch.nn.Module):
                                        None if wsq is None else torch.from_numpy(wsq).to(dev), self.filter_length, self.hop_length)
             self._packed_key = self._key()
         return self._packed
+
+    def mel_tables(self, mel_basis):
+        """The log-mel kernel's packed tables for this module's forward basis and `mel_basis` [n_mels, N/2+1], built on first
+        use and again after .to() / .cuda() / load_state_dict of either (the last mel basis is the one kept)."""
+        if not self.forward_basis.is_cuda:
+            raise RuntimeError("STFT: the buffers must live on the GPU for the HIP kernels (module.cuda())")
+        # the mel basis is the caller's: its address alone could be that of an earlier, freed tensor, so the key holds the tensor
+        key = (self.forward_basis.data_ptr(), self.forward_basis._version, mel_basis._version)
+        if self._mel_packed is None or self._mel_basis is not mel_basis or self._mel_key != key:
+            self._mel_packed = pack_mel_tables(self.forward_basis[:, 0, :], mel_basis, self.filter_length)
+            self._mel_basis, self._mel_key = mel_basis, key
+        return self._mel_packed
 
     def transform(self, input_data):
         B, n = input_data.shape
@@ -240,9 +353,18 @@ class TacotronSTFT(torch.nn.Module):
     def spectral_de_normalize(self, magnitudes):
         return dynamic_range_decompression(magnitudes)
 
-    def mel_spectrogram(self, y):
-        """y: [B, T] in [-1, 1] -> log-mel [B, n_mel_channels, frames] (layers.py:60-80)."""
+    def mel_spectrogram(self, y, lengths=None, time_major=False):
+        """y: [B, T] in [-1, 1] -> log-mel [B, n_mel_channels, frames] (layers.py:60-80).  CUDA tensors go through the log-mel
+        kernel (`log_mel`: one launch, no frame matrix, no phase); CPU tensors keep the torch formula, for comparison.
+        lengths (an addition): per-item sample counts, see `log_mel`; the result is then (mel, frame_lengths) and frames
+        past an item's own hold 0, what the collate function pads mels with.  time_major gives [B, frames, n_mel_channels]."""
         assert torch.min(y.data) >= -1
         assert torch.max(y.data) <= 1
+        if y.is_cuda:
+            mel, frame_lengths = log_mel(y, self.stft_fn, self.mel_basis, lengths=lengths, time_major=time_major)
+            return mel if lengths is None else (mel, frame_lengths)
+        if lengths is not None:
+            raise RuntimeError("TacotronSTFT.mel_spectrogram: per-item lengths need the HIP kernel (CUDA tensors)")
         magnitudes, _ = self.stft_fn.transform(y)
-        return self.spectral_normalize(torch.matmul(self.mel_basis, magnitudes.data))
+        mel = self.spectral_normalize(torch.matmul(self.mel_basis, magnitudes.data))
+        return mel.transpose(1, 2).contiguous() if time_major else mel

@@ -1,4 +1,6 @@
-"""utils.py:10-14,28-33 of the reference, device-agnostic."""
+"""utils.py of the reference: the mask and device helpers (:10-14, :28-33), device-agnostic; the wav, filelist and
+range-compression helpers (:17-25, :38-54); mel_spectrogram(filename, ...) (:55-80) on the log-mel kernel; the alignment
+generator (:92-117).  scipy is imported inside the functions that read wav files, so importing the model stays light."""
 import os
 
 import torch
@@ -53,6 +55,87 @@ def to_gpu(x):
     if torch.cuda.is_available():
         x = x.cuda(non_blocking=True)
     return x
+
+
+def load_wav_to_torch(full_path):
+    """utils.py:17-19: (samples as a float32 tensor, in the file's own scale; sampling rate)."""
+    import numpy as np
+    from scipy.io.wavfile import read                    # lazy: importing the model does not pull in scipy
+    sampling_rate, data = read(full_path)
+    return torch.FloatTensor(data.astype(np.float32)), sampling_rate
+
+
+def load_wav(full_path):
+    """utils.py:38-40: (samples as the numpy array the file holds, sampling rate)."""
+    from scipy.io.wavfile import read
+    sampling_rate, data = read(full_path)
+    return data, sampling_rate
+
+
+def load_filepaths_and_text(filename, split="|"):
+    """utils.py:22-25: one list of fields per line of a filelist."""
+    with open(filename, encoding="utf-8") as f:
+        return [line.strip().split(split) for line in f]
+
+
+def dynamic_range_compression_torch(x, C=1, clip_val=1e-5):
+    return torch.log(torch.clamp(x, min=clip_val) * C)
+
+
+def dynamic_range_decompression_torch(x, C=1):
+    return torch.exp(x) / C
+
+
+def spectral_normalize_torch(magnitudes):
+    return dynamic_range_compression_torch(magnitudes)
+
+
+def spectral_de_normalize_torch(magnitudes):
+    return dynamic_range_decompression_torch(magnitudes)
+
+
+_mel_front = {}     # (n_fft, num_mels, sampling_rate, hop_size, win_size, fmin, fmax, device) -> (STFT module, mel basis)
+
+
+def mel_spectrogram(filename, n_fft=1024, num_mels=80, sampling_rate=22050, hop_size=256, win_size=1024, fmin=0.0, fmax=8000.0,
+                    center=False, stftTaco=False, stftCUDA=False, device=None):
+    """utils.py:55-80, the HiFi-GAN convention: wav / 32768, peak-normalised to 0.95 (librosa.util.normalize restated as
+    x / max|x|), reflect-padded by (n_fft - hop_size)/2 per side, torch.stft(center=False) with a periodic Hann window,
+    sqrt(re^2 + im^2 + 1e-9), mel filterbank, log(clamp(., 1e-5)) -> [1, num_mels, frames] on `device`.
+    device=None (an addition) is the GPU when there is one: the whole formula is then one launch of the log-mel kernel
+    (stft.log_mel with pad=(n_fft - hop_size)/2, mag_eps=1e-9); on the CPU it is torch.stft.  As in the reference the file's
+    own sampling rate replaces `sampling_rate`, and stftTaco / stftCUDA are accepted and ignored."""
+    import numpy as np
+    audio, sampling_rate = load_wav(filename)
+    audio = audio / 32768.0
+    peak = np.max(np.abs(audio)) if audio.size else 0.0
+    audio = audio / (peak if peak >= np.finfo(audio.dtype).tiny else 1.0) * 0.95
+    y = torch.FloatTensor(audio).unsqueeze(0)
+    if torch.min(y) < -1.:
+        print('min value is ', torch.min(y))
+    if torch.max(y) > 1.:
+        print('max value is ', torch.max(y))
+    device = torch.device(("cuda" if torch.cuda.is_available() else "cpu") if device is None else device)
+    if device.type == "cuda" and device.index is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    pad = int((n_fft - hop_size) / 2)
+    key = (n_fft, num_mels, sampling_rate, hop_size, win_size, fmin, fmax, str(device))
+    if key not in _mel_front:
+        from .stft import STFT, mel_filterbank             # lazy: scipy.signal
+        basis = torch.from_numpy(mel_filterbank(sampling_rate, n_fft, num_mels, fmin, fmax)).float().to(device)
+        _mel_front[key] = ((STFT(n_fft, hop_size, win_size).to(device) if device.type == "cuda" else None), basis)
+    front, basis = _mel_front[key]
+    if device.type == "cuda":
+        if center:
+            raise NotImplementedError("mel_spectrogram: center=True pads twice (the reference never passes it); the log-mel kernel takes one reflect "
+                                      "padding of at most n_fft/2: use device='cpu'")
+        from .stft import log_mel
+        return log_mel(y.to(device), front, basis, pad=pad, mag_eps=1e-9)[0]
+    y = torch.nn.functional.pad(y.unsqueeze(1), (pad, pad), mode="reflect").squeeze(1)
+    spec = torch.stft(y, n_fft, hop_length=hop_size, win_length=win_size, window=torch.hann_window(win_size), center=center,
+                      pad_mode="reflect", normalized=False, onesided=True, return_complex=True)
+    spec = torch.sqrt(spec.real.pow(2) + spec.imag.pow(2) + 1e-9)
+    return spectral_normalize_torch(torch.matmul(basis, spec))
 
 
 def create_alignment(base_mat, duration_predictor_output):
