@@ -786,7 +786,8 @@ int t2_melspec(const t2_melspec_args* a, void* stream);
  * Invertible1x1Conv.forward(reverse=True) (:88-97), as inference.py:160-170 and best_checkpoint.py:179-189 call them and as
  * bias_remover.py:38-74 (waveglowBiasRemover) does.  torch's [B, C, L] layout, time contiguous; always exact fp32 on the
  * matrix cores, whatever t2_set_precision says.  No atomics, a fixed order for every sum: bit-identical from run to run
- * and for an item alone or inside a batch.  Ordinary launches on `stream`.  Inference only, fp32 only.
+ * and for an item alone or inside a batch.  Ordinary launches on `stream`.  fp32 only; the other direction of the flow
+ * (waveform -> latent and log-likelihood) follows below.
  * With G = n_group, L = T*256/G and nc = n_channels, per flow k = n_flows-1 .. 0 (a0 / a1 = the halves of `audio`):
  *   x = start(a0); per layer i: acts = tanh(.)*sigmoid(.) of in_layers[i](x) + cond_layer(spect)[2nc*i : 2nc*(i+1)], the
  *   conditioning folded into the same GEMM (no [B, 2*nc*n_layers, L] tensor exists); x += / out += res_skip_layers[i](acts);
@@ -877,6 +878,76 @@ typedef struct t2_waveglow_couple_args {
     float* audio_out; float* audio_interleaved;
 } t2_waveglow_couple_args;
 int t2_waveglow_couple(const t2_waveglow_couple_args* a, void* stream);
+
+/* ---- WaveGlow analysis (waveform -> latent and log-likelihood) -----------------------------------------
+ * Replaces the reference's glow.py: WaveGlow.forward (:207-249), Invertible1x1Conv.forward (:98-102) and WaveGlowLoss
+ * (:48-59), as waveglow/train.py:125-127 calls them -- the values only, no gradient.  The WN of a flow is the same in both
+ * directions, so the upsample, start, gated conv and res_skip kernels are the ones above; around them, per flow
+ * k = 0 .. n_flows-1 on audio regrouped to [B, G, L], L = n_samples / G (a tail of n_samples % G samples is dropped):
+ *   if k % n_early_every == 0 and k > 0: the first n_early_size channels leave for z;  audio = W_k audio;
+ *   (b, s) = end(WN_k(a0, spect));  a1 = exp(s) * a1 + b;  log_s[k] = s.
+ * z [B, G, L] = the early outputs, k ascending, then the last flow's audio.  n_samples may exceed T*256 by up to 768: the
+ * trailing samples of the transposed conv are then computed too (glow.py:215-218).  Sums are formed without atomics in a
+ * fixed order and in fp64 from the first add: z, log_s, every sum and nll_item are bit-identical from run to run and for
+ * an item alone or inside a batch. */
+#define T2_WAVEGLOW_FORWARD_KERNELS 7 /* kinds of kernel_ms_host: upsample, start, gated conv, res_skip, head, tail, sums */
+typedef struct t2_waveglow_forward_info {
+    long L;                  /* columns of every activation: n_samples / n_group */
+    int n_log_s_rows;        /* sum over the flows of n_half_k: log_s[k] is [B, n_half_k, L] */
+    int n_tensors;           /* what t2_waveglow_pack takes */
+    long n_blocks;           /* column blocks of 256 per item: one partial sum per (flow, item, block) and kind */
+    size_t n_partials;       /* 2 * n_flows * B * n_blocks fp64 slots inside the workspace */
+    size_t workspace_bytes;  /* spect, x, out, acts, two audio buffers, the partial sums, the per-item results */
+    size_t packed_bytes;
+} t2_waveglow_forward_info;
+/* Pure host call (no device): validates cfg, B >= 1, T >= 1 and n_group <= n_samples <= (T-1)*256 + 1024 (glow.py:216). */
+int t2_waveglow_forward_plan(const t2_waveglow_config* cfg, int B, int T, long n_samples, t2_waveglow_forward_info* out);
+/* logdet [n_flows] = log |det W_k| of the matrices inside `packed` (packed with W_k where inference has W_k^-1): LU with
+ * partial pivoting in fp64, rounded to fp32; NaN for a negative determinant, as torch.logdet.  Once per set of weights. */
+int t2_waveglow_logdet(const t2_waveglow_config* cfg, const float* packed, float* logdet, void* stream);
+typedef struct t2_waveglow_forward_args {
+    int B, T, n_mel;         /* n_mel: channels of the mel given, checked against cfg */
+    long n_samples;          /* N: samples per item of `audio` */
+    const float* packed;     /* t2_waveglow_pack with W_k in the place of W_k^-1 */
+    const float* logdet_w;   /* [n_flows], from t2_waveglow_logdet on the same buffer; nullable when neither logdet nor a sum is asked for */
+    const float* mel;        /* [B, n_mel, T] */
+    const float* audio;      /* [B, N] */
+    float* workspace;        /* workspace_bytes */
+    float* z;                /* [B, G, L]; nullable when a sum is asked for */
+    float* const* log_s_host;/* nullable: HOST array of n_flows DEVICE pointers, log_s[k] [B, n_half_k, L] */
+    float* logdet;           /* nullable: [n_flows], B * L * logdet_w[k] (glow.py:100) */
+    float sigma;             /* of WaveGlowLoss; read only when a sum is asked for */
+    double* sums;            /* nullable: [B][n_flows + 1], per item the sum of log_s[k] for every k, then the sum of z^2 */
+    float* nll_item;         /* nullable: [B], (sum z^2 / (2 sigma^2) - sum log_s - L * sum logdet_w) / (G * L) */
+    float* loss;             /* nullable: [1], the mean of the above over the items = WaveGlowLoss(sigma) */
+    double* kernel_ms_host;  /* debug output, nullable: T2_WAVEGLOW_FORWARD_KERNELS totals in ms */
+} t2_waveglow_forward_args;
+int t2_waveglow_forward(const t2_waveglow_config* cfg, const t2_waveglow_forward_args* a, void* stream);
+/* Single kernels, for the tests only (t2_waveglow_forward runs the same ones).
+ * out[m] = log |det w[m]| of n matrices [c][c], c <= 8. */
+int t2_waveglow_logdet_matrices(const float* w, int c, int n, float* out, void* stream);
+/* audio_out [B, G, L] = w x regrouped audio: audio_out[b, r, l] = sum_g w[r][g] * audio[b, l*G + g] (glow.py:223, :233 at k = 0). */
+typedef struct t2_waveglow_head_args {
+    int B, n_group; long n_samples;
+    const float* audio;      /* [B, n_samples] */
+    const float* w;          /* [G][G] */
+    float* audio_out;        /* [B, G, n_samples / G] */
+} t2_waveglow_head_args;
+int t2_waveglow_head(const t2_waveglow_head_args* a, void* stream);
+/* One flow's tail (glow.py:240-246, then :229-233 of the next flow): (b, s) = end(out); v = cat(a0, exp(s) * a1 + b);
+ * z[:, z_offset : z_offset + n_peel] = v[:n_peel]; audio_out [B, 2*n_half - n_peel, L] = w_next v[n_peel:].  On the last
+ * flow n_peel = 2*n_half and w_next, audio_out are unused.  part_s, part_z (nullable, together) [B][ceil(L/256)]: the sums
+ * of s and of the z^2 written, per item and block of 256 columns. */
+typedef struct t2_waveglow_tail_args {
+    int B, nc, n_half, L, n_peel, n_group, z_offset;
+    const float* out;        /* [B, nc, L] */
+    const float* w_end; const float* b_end;     /* [2*n_half][nc], [2*n_half] */
+    const float* audio_in;   /* [B, 2*n_half, L] */
+    const float* w_next;     /* [2*n_half - n_peel][2*n_half - n_peel] */
+    float* audio_out; float* z; float* log_s;   /* z [B, n_group, L]; log_s (nullable) [B, n_half, L] */
+    double* part_s; double* part_z;
+} t2_waveglow_tail_args;
+int t2_waveglow_tail(const t2_waveglow_tail_args* a, void* stream);
 
 /* Gradient-norm clipping + Adam over a list of fp32 tensors — replaces torch.nn.utils.clip_grad_norm_ +
  * torch.optim.Adam.step of the training loop (train.py:322-330; Adam with weight decay added to the gradient).

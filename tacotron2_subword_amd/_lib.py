@@ -337,7 +337,30 @@ class WaveglowCoupleArgs(C.Structure):
                 ("audio_out", C.c_void_p), ("audio_interleaved", C.c_void_p)]
 
 
+class WaveglowForwardInfo(C.Structure):
+    _fields_ = [("L", C.c_long), ("n_log_s_rows", C.c_int), ("n_tensors", C.c_int), ("n_blocks", C.c_long), ("n_partials", C.c_size_t),
+                ("workspace_bytes", C.c_size_t), ("packed_bytes", C.c_size_t)]
+
+
+class WaveglowForwardArgs(C.Structure):
+    _fields_ = [("B", C.c_int), ("T", C.c_int), ("n_mel", C.c_int), ("n_samples", C.c_long), ("packed", C.c_void_p), ("logdet_w", C.c_void_p),
+                ("mel", C.c_void_p), ("audio", C.c_void_p), ("workspace", C.c_void_p), ("z", C.c_void_p), ("log_s_host", C.POINTER(C.c_void_p)),
+                ("logdet", C.c_void_p), ("sigma", C.c_float), ("sums", C.c_void_p), ("nll_item", C.c_void_p), ("loss", C.c_void_p),
+                ("kernel_ms_host", C.POINTER(C.c_double))]
+
+
+class WaveglowHeadArgs(C.Structure):
+    _fields_ = [("B", C.c_int), ("n_group", C.c_int), ("n_samples", C.c_long), ("audio", C.c_void_p), ("w", C.c_void_p), ("audio_out", C.c_void_p)]
+
+
+class WaveglowTailArgs(C.Structure):
+    _fields_ = [("B", C.c_int), ("nc", C.c_int), ("n_half", C.c_int), ("L", C.c_int), ("n_peel", C.c_int), ("n_group", C.c_int), ("z_offset", C.c_int),
+                ("out", C.c_void_p), ("w_end", C.c_void_p), ("b_end", C.c_void_p), ("audio_in", C.c_void_p), ("w_next", C.c_void_p),
+                ("audio_out", C.c_void_p), ("z", C.c_void_p), ("log_s", C.c_void_p), ("part_s", C.c_void_p), ("part_z", C.c_void_p)]
+
+
 WAVEGLOW_KERNELS = ("upsample", "start", "gated_conv", "res_skip", "couple")      # include/t2amd.h T2_WAVEGLOW_KERNELS
+WAVEGLOW_FORWARD_KERNELS = ("upsample", "start", "gated_conv", "res_skip", "head", "tail", "sums")      # T2_WAVEGLOW_FORWARD_KERNELS
 WAVEGLOW_GATED, WAVEGLOW_RES_SKIP, WAVEGLOW_UPSAMPLE = 0, 1, 2                      # kinds of t2_waveglow_packed_floats
 
 # every symbol include/t2amd.h declares (tests/test_abi.py checks the library exports them all)
@@ -352,7 +375,8 @@ EXPORTS = ["t2_last_error", "t2_version", "t2_chain_status", "t2_chain_status_cl
            "t2_hifigan_plan", "t2_hifigan_pack", "t2_hifigan_forward", "t2_vocoder_packed_floats", "t2_vocoder_conv1d", "t2_vocoder_conv_transpose1d",
            "t2_stft_plan", "t2_stft_pack", "t2_stft_analysis", "t2_stft_synthesis", "t2_melspec_plan", "t2_melspec_pack", "t2_melspec",
            "t2_waveglow_plan", "t2_waveglow_pack", "t2_waveglow_infer", "t2_waveglow_packed_floats", "t2_waveglow_gated_conv", "t2_waveglow_res_skip",
-           "t2_waveglow_upsample", "t2_waveglow_couple"]
+           "t2_waveglow_upsample", "t2_waveglow_couple", "t2_waveglow_forward_plan", "t2_waveglow_forward", "t2_waveglow_logdet",
+           "t2_waveglow_logdet_matrices", "t2_waveglow_head", "t2_waveglow_tail"]
 
 _lib = None
 
@@ -434,6 +458,12 @@ def lib() -> C.CDLL:
         L.t2_waveglow_res_skip.argtypes = [C.POINTER(WaveglowResSkipArgs), C.c_void_p]
         L.t2_waveglow_upsample.argtypes = [C.POINTER(WaveglowUpsampleArgs), C.c_void_p]
         L.t2_waveglow_couple.argtypes = [C.POINTER(WaveglowCoupleArgs), C.c_void_p]
+        L.t2_waveglow_forward_plan.argtypes = [C.POINTER(WaveglowConfig), C.c_int, C.c_int, C.c_long, C.POINTER(WaveglowForwardInfo)]
+        L.t2_waveglow_forward.argtypes = [C.POINTER(WaveglowConfig), C.POINTER(WaveglowForwardArgs), C.c_void_p]
+        L.t2_waveglow_logdet.argtypes = [C.POINTER(WaveglowConfig), C.c_void_p, C.c_void_p, C.c_void_p]
+        L.t2_waveglow_logdet_matrices.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+        L.t2_waveglow_head.argtypes = [C.POINTER(WaveglowHeadArgs), C.c_void_p]
+        L.t2_waveglow_tail.argtypes = [C.POINTER(WaveglowTailArgs), C.c_void_p]
         _lib = L
     return _lib
 
@@ -859,4 +889,12 @@ def waveglow_plan(cfg: WaveglowConfig, B: int, T: int) -> WaveglowPlanInfo:
     the library's message for what is not supported."""
     info = WaveglowPlanInfo()
     check(lib().t2_waveglow_plan(C.byref(cfg), B, T, C.byref(info)))
+    return info
+
+
+def waveglow_forward_plan(cfg: WaveglowConfig, B: int, T: int, n_samples: int) -> WaveglowForwardInfo:
+    """Columns, log_s rows and buffer sizes of an analyze / nll call (t2_waveglow_forward_plan: pure host, no device needed);
+    raises with the library's message for what is refused."""
+    info = WaveglowForwardInfo()
+    check(lib().t2_waveglow_forward_plan(C.byref(cfg), B, T, n_samples, C.byref(info)))
     return info

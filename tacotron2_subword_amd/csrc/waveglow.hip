@@ -1,5 +1,10 @@
-// WaveGlow (Prenger et al. 2018), inference: mel spectrogram -> waveform.  Replaces the reference's glow.py: WaveGlow.infer
-// (:251-293), WN.forward (:153-175), Invertible1x1Conv.forward(reverse=True) (:88-97).
+// WaveGlow (Prenger et al. 2018), both directions of the flow.  Inference, mel spectrogram -> waveform, replaces the reference's
+// glow.py: WaveGlow.infer (:251-293), WN.forward (:153-175), Invertible1x1Conv.forward(reverse=True) (:88-97).  Analysis,
+// waveform -> z with log_s, log det W and the negative log-likelihood (values only, no gradient), replaces WaveGlow.forward
+// (:207-249), Invertible1x1Conv.forward (:98-102) and WaveGlowLoss (:48-59): the WN is the same in both directions, so it runs
+// the same upsample / start / gated conv / res_skip kernels, with a head kernel (regroup + W_0), one tail kernel per flow (end,
+// exp(s) * a1 + b, the early-output split, the next flow's W, fp64 partial sums of s and z^2) and two small kernels that finish
+// the sums in a fixed order.  log |det W_k| comes from an fp64 LU, once per set of weights.
 //
 // Activations are [B][C][L] with time contiguous, L = T*256/n_group; arithmetic is exact fp32 on the matrix cores
 // (v_mfma_f32_32x32x2_f32), whatever t2_set_precision says.  Three of the five kernels are one GEMM kernel in the style of
@@ -12,7 +17,8 @@
 //   res_skip     the 1x1 conv; its epilogue does x += rs[:nc] and out += rs[nc:] in place (acts is a buffer of its own).
 //   upsample     ConvTranspose1d(n_mel, n_mel, 1024, stride 256) as a polyphase GEMM: output sample 256q + r reads taps r + 256m
 //                (m = 0..3) of frames q - m, so rows = (channel, phase r), columns = frames q, K = n_mel * 4; the epilogue writes
-//                spect[b, ch*G + g, l] at 256q + r = l*G + g and never computes the 768 trailing samples.  Each element once.
+//                spect[b, ch*G + g, l] at 256q + r = l*G + g.  Each element once.  Inference never computes the 768 trailing
+//                samples; the forward direction, whose audio may reach into them, asks for up to three more columns q.
 // `start` (K <= 4) and the coupling (end: <= 8 rows reduced over nc with lanes along time, then (a1 - b)/exp(s), the c x c inverse
 // mix and the early-noise prepend in one pass) are plain VALU.  No atomics, every sum in a fixed order, 64-bit element offsets.
 #include <algorithm>
@@ -40,6 +46,7 @@ struct WgGemm {
     int taps, coff0, cstep, halo;
     int rows, mtiles, nch0, nch1;
     int first, last, raw, G; long Lg;             // res_skip: first, last; gated: raw; upsample: G, Lg = columns of spect
+    int Nq;                                       // output columns: N, but for an upsample that keeps trailing samples (up to N + 3)
 };
 
 template <int WM, int MODE>
@@ -105,7 +112,7 @@ __global__ void __launch_bounds__(WM * 128) wg_gemm_kernel(WgGemm p) {
 #pragma unroll
     for (int n = 0; n < 2; ++n) {
         const long q = t0 + wt * 64 + n * 32 + (lane & 31);
-        if (q >= p.N) continue;
+        if (q >= p.Nq) continue;
 #pragma unroll
         for (int e = 0; e < 16; ++e) {
             const int r = mt * 32 + (e & 3) + 8 * (e >> 2) + 4 * hk;
@@ -249,6 +256,199 @@ __global__ void __launch_bounds__(256) wg_couple_kernel(WgCouple p) {
         for (int j = 0; j < p.n_early; ++j) p.dst[((size_t)b * Cn + j) * p.L + t] = p.sigma * p.z[((size_t)b * p.n_early + j) * p.L + t];
 }
 
+// ---- the forward direction (audio -> z, glow.py:207-249): the kernels around the WN, which is the one above
+// fixed-order sum of one double per lane over the wave, in every lane
+__device__ __forceinline__ double wg_wave_sum(double v) {
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
+    return v;
+}
+
+// dst[b, r, l] = sum_g w[r][g] * audio[b, l*G + g] (g ascending): the regroup of glow.py:223 and flow 0's mix; one thread per (b, l)
+__global__ void __launch_bounds__(256) wg_head_kernel(const float* __restrict__ audio, const float* __restrict__ w, float* __restrict__ dst, int G, long N,
+                                                     long L) {
+    __shared__ float wi[64];
+    if (threadIdx.x < G * G) wi[threadIdx.x] = w[threadIdx.x];
+    __syncthreads();
+    const long l = (long)blockIdx.x * 256 + threadIdx.x;
+    if (l >= L) return;
+    const int b = blockIdx.y;
+    const float* ab = audio + (size_t)b * N + (size_t)l * G;
+    float v[8];
+#pragma unroll
+    for (int g = 0; g < 8; ++g) v[g] = g < G ? ab[g] : 0.f;
+#pragma unroll
+    for (int r = 0; r < 8; ++r) {
+        if (r < G) {
+            float y = 0.f;
+#pragma unroll
+            for (int g = 0; g < 8; ++g)
+                if (g < G) y = fmaf(wi[r * G + g], v[g], y);
+            dst[((size_t)b * G + r) * L + l] = y;
+        }
+    }
+}
+
+struct WgTail {
+    const float* out; const float* w_end; const float* b_end; const float* in; const float* wnext;
+    float* dst; float* z; float* log_s; double* part_s; double* part_z;
+    int nc, n_half, n_peel, G, zoff; long L;
+};
+// One flow's tail, one thread per (item, column): (b, s) = end(out) as <= 8 fmaf chains over nc (ascending), a1' = exp(s) * a1 + b,
+// v = cat(a0, a1').  v[:n_peel] goes to z[:, zoff:] (the next flow's early output; on the last flow all of v), the rest is mixed by
+// the next flow's W (ascending) into dst.  part_s / part_z [item][column block] receive the workgroup's sums of s and of the z^2 it
+// wrote, added in fp64 from the first term: per thread in channel order, then a xor tree over the wave, then the waves in order.
+__global__ void __launch_bounds__(256) wg_tail_kernel(WgTail p) {
+    __shared__ __align__(8) float we[8 * 512];
+    __shared__ float be[8], wi[64];
+    const int nh = p.n_half, C = 2 * nh, Cn = C - p.n_peel;
+    for (int i = threadIdx.x; i < C * p.nc; i += 256) we[i] = p.w_end[i];
+    if (threadIdx.x < C) be[threadIdx.x] = p.b_end[threadIdx.x];
+    if (threadIdx.x < Cn * Cn) wi[threadIdx.x] = p.wnext[threadIdx.x];
+    __syncthreads();
+    const long t = (long)blockIdx.x * 256 + threadIdx.x;
+    const bool valid = t < p.L;
+    const int b = blockIdx.y;
+    double sum_s = 0.0, sum_z = 0.0;
+    if (valid) {
+        float o[8];
+#pragma unroll
+        for (int r = 0; r < 8; ++r) o[r] = 0.f;
+        const float* ob = p.out + (size_t)b * p.nc * p.L + t;
+        for (int c = 0; c < p.nc; ++c) {
+            const float x = ob[(size_t)c * p.L];
+#pragma unroll
+            for (int r = 0; r < 8; ++r)
+                if (r < C) o[r] = fmaf(we[r * p.nc + c], x, o[r]);
+        }
+        float v[8];
+#pragma unroll
+        for (int r = 0; r < 8; ++r) v[r] = 0.f;
+        const float* ib = p.in + (size_t)b * C * p.L + t;
+#pragma unroll
+        for (int h = 0; h < 4; ++h) {
+            if (h < nh) {
+                const float a0 = ib[(size_t)h * p.L], a1 = ib[(size_t)(nh + h) * p.L];
+                float bb = 0.f, s = 0.f;
+#pragma unroll
+                for (int r = 0; r < 8; ++r) {       // o[h] and o[nh + h] without a dynamic register index
+                    if (r == h) bb = o[r] + be[r];
+                    if (r == nh + h) s = o[r] + be[r];
+                }
+                const float y1 = fmaf(expf(s), a1, bb);
+                if (p.log_s) p.log_s[((size_t)b * nh + h) * p.L + t] = s;
+                sum_s += (double)s;
+#pragma unroll
+                for (int r = 0; r < 8; ++r) {
+                    if (r == h) v[r] = a0;
+                    if (r == nh + h) v[r] = y1;
+                }
+            }
+        }
+#pragma unroll
+        for (int r = 0; r < 8; ++r) {
+            if (r < p.n_peel) {
+                if (p.z) p.z[((size_t)b * p.G + p.zoff + r) * p.L + t] = v[r];
+                sum_z += (double)v[r] * (double)v[r];
+            }
+        }
+#pragma unroll
+        for (int r = 0; r < 8; ++r) {
+            if (r < Cn) {
+                float y = 0.f;
+#pragma unroll
+                for (int c = 0; c < 8; ++c)
+                    if (c >= p.n_peel && c < C) y = fmaf(wi[r * Cn + c - p.n_peel], v[c], y);
+                p.dst[((size_t)b * Cn + r) * p.L + t] = y;
+            }
+        }
+    }
+    if (!p.part_s) return;                         // uniform
+    sum_s = wg_wave_sum(sum_s);
+    sum_z = wg_wave_sum(sum_z);
+    __syncthreads();                               // every thread is done with `we`: its first 64 bytes carry the waves' sums
+    double* red = reinterpret_cast<double*>(we);
+    if ((threadIdx.x & 63) == 0) { red[threadIdx.x >> 6] = sum_s; red[4 + (threadIdx.x >> 6)] = sum_z; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const size_t slot = (size_t)b * gridDim.x + blockIdx.x;
+        p.part_s[slot] = ((red[0] + red[1]) + red[2]) + red[3];
+        p.part_z[slot] = ((red[4] + red[5]) + red[6]) + red[7];
+    }
+}
+
+// Per item (one wave each): sums[b][k] = sum of flow k's partials (lane j takes blocks j, j + 64, .. ascending, then the xor tree),
+// sums[b][n_flows] = sum z^2 (flows ascending), item[b] = (sum z^2 / (2 sigma^2) - sum_k sums[b][k] - L * sum_k logdet W_k) / (G * L).
+__global__ void __launch_bounds__(64) wg_nll_item_kernel(const double* __restrict__ part_s, const double* __restrict__ part_z, int n_flows, int B, int nblk,
+                                                        long L, int G, float sigma, const float* __restrict__ logdet_w, double* __restrict__ sums,
+                                                        double* __restrict__ item, float* __restrict__ nll_item) {
+    const int b = blockIdx.x, lane = threadIdx.x;
+    double z2 = 0.0, stot = 0.0, ld = 0.0;
+    for (int k = 0; k < n_flows; ++k) {
+        const size_t base = ((size_t)k * B + b) * nblk;
+        double ps = 0.0, pz = 0.0;
+        for (int j = lane; j < nblk; j += 64) { ps += part_s[base + j]; pz += part_z[base + j]; }
+        ps = wg_wave_sum(ps);
+        pz = wg_wave_sum(pz);
+        if (lane == 0) sums[(size_t)b * (n_flows + 1) + k] = ps;
+        stot += ps; z2 += pz; ld += (double)logdet_w[k];
+    }
+    if (lane != 0) return;
+    sums[(size_t)b * (n_flows + 1) + n_flows] = z2;
+    const double nll = (z2 / (2.0 * (double)sigma * (double)sigma) - stot - (double)L * ld) / ((double)G * (double)L);
+    item[b] = nll;
+    if (nll_item) nll_item[b] = (float)nll;
+}
+
+// logdet[k] = B * L * logdet W_k (glow.py:100), and loss = mean over the items of item[b] (thread j takes items j, j + 256, ..
+// ascending, then a tree in LDS): WaveGlowLoss (glow.py:48-59) from the sums above.
+__global__ void __launch_bounds__(256) wg_nll_loss_kernel(const double* __restrict__ item, int B, long L, int n_flows, const float* __restrict__ logdet_w,
+                                                         float* __restrict__ logdet, float* __restrict__ loss) {
+    __shared__ double red[256];
+    if (logdet && threadIdx.x < n_flows) logdet[threadIdx.x] = (float)((double)B * (double)L * (double)logdet_w[threadIdx.x]);
+    if (!loss) return;                             // uniform
+    double acc = 0.0;
+    for (int b = threadIdx.x; b < B; b += 256) acc += item[b];
+    red[threadIdx.x] = acc;
+    __syncthreads();
+    for (int w = 128; w >= 1; w >>= 1) {
+        if (threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) loss[0] = (float)(red[0] / (double)B);
+}
+
+// out[m] = log |det w[m]| of n matrices [c][c], c <= 8: LU with partial pivoting in fp64, sum of log |u_ii| rounded to fp32; NaN
+// for a negative determinant and -inf for a singular matrix, as torch.logdet gives.  One workgroup per matrix, the matrix in LDS.
+__global__ void __launch_bounds__(64) wg_logdet_kernel(const float* __restrict__ w, int c, float* __restrict__ out) {
+    __shared__ double m[64];
+    if ((int)threadIdx.x < c * c) m[threadIdx.x] = (double)w[(size_t)blockIdx.x * c * c + threadIdx.x];
+    __syncthreads();
+    if (threadIdx.x != 0) return;
+    double acc = 0.0;
+    bool negative = false, singular = false;
+    for (int i = 0; i < c && !singular; ++i) {
+        int piv = i;                                // `>` is false for a NaN: one off the diagonal is never chosen here, it spreads
+        for (int r = i + 1; r < c; ++r)             // through the elimination below and is met as a pivot (or in the sum) later
+            if (fabs(m[r * c + i]) > fabs(m[piv * c + i])) piv = r;
+        if (piv != i) {
+            for (int j = 0; j < c; ++j) { const double tmp = m[i * c + j]; m[i * c + j] = m[piv * c + j]; m[piv * c + j] = tmp; }
+            negative = !negative;
+        }
+        const double u = m[i * c + i];
+        if (u != u) { negative = true; break; }     // a NaN in the matrix gives NaN
+        if (u == 0.0) { singular = true; break; }
+        if (u < 0.0) negative = !negative;
+        acc += log(fabs(u));
+        for (int r = i + 1; r < c; ++r) {
+            const double f = m[r * c + i] / u;
+            for (int j = i + 1; j < c; ++j) m[r * c + j] -= f * m[i * c + j];
+        }
+    }
+    const double inf = __builtin_inf();
+    out[blockIdx.x] = singular ? (float)-inf : (negative ? __builtin_nanf("") : (float)acc);
+}
+
 // ------------------------------------------------------------------------------------------------------------------
 // host
 // ------------------------------------------------------------------------------------------------------------------
@@ -274,7 +474,7 @@ static int wg_pack(int kind, const float* w0, const float* w1, float* out, int r
 template <int MODE>
 static int wg_launch(const WgGemm& p, int B, hipStream_t s) {
     const int wm = p.mtiles >= 4 ? 4 : (p.mtiles >= 2 ? 2 : 1);
-    dim3 grid((unsigned)((p.N + kVocTT - 1) / kVocTT), (unsigned)((p.mtiles + wm - 1) / wm), (unsigned)B);
+    dim3 grid((unsigned)((p.Nq + kVocTT - 1) / kVocTT), (unsigned)((p.mtiles + wm - 1) / wm), (unsigned)B);
     if (wm == 4) hipLaunchKernelGGL((wg_gemm_kernel<4, MODE>), grid, dim3(512), 0, s, p);
     else if (wm == 2) hipLaunchKernelGGL((wg_gemm_kernel<2, MODE>), grid, dim3(256), 0, s, p);
     else hipLaunchKernelGGL((wg_gemm_kernel<1, MODE>), grid, dim3(128), 0, s, p);
@@ -308,7 +508,7 @@ static int wg_gated(int B, int nc, int n_cond, long L, int d, int raw, const flo
     T2_REQUIRE(x && spect && packed && b_in && b_cond && y, "waveglow gated conv: null pointer");
     WgGemm p{};
     p.x0 = x; p.x1 = spect; p.wp = packed; p.bias0 = b_in; p.bias1 = b_cond; p.y0 = y;
-    p.C0 = nc; p.C1 = n_cond; p.N = (int)L; p.taps = 3; p.coff0 = 0; p.cstep = d; p.halo = d;
+    p.C0 = nc; p.C1 = n_cond; p.N = p.Nq = (int)L; p.taps = 3; p.coff0 = 0; p.cstep = d; p.halo = d;
     p.rows = nc; p.mtiles = (nc + 31) / 32; p.nch0 = chunks(nc); p.nch1 = chunks(n_cond); p.raw = raw;
     return wg_launch<kWgGated>(p, B, s);
 }
@@ -321,22 +521,27 @@ static int wg_res_skip(int B, int nc, long L, int first, int last, const float* 
     T2_REQUIRE(acts && packed && bias && out && (last || x), "%s: null pointer", who);
     WgGemm p{};
     p.x0 = acts; p.wp = packed; p.bias0 = bias; p.y0 = x; p.y1 = out;
-    p.C0 = nc; p.N = (int)L; p.taps = 1;
+    p.C0 = nc; p.N = p.Nq = (int)L; p.taps = 1;
     p.rows = last ? nc : 2 * nc; p.mtiles = (p.rows + 31) / 32; p.nch0 = chunks(nc); p.first = first; p.last = last;
     return wg_launch<kWgResSkip>(p, B, s);
 }
 
-static int wg_upsample(int B, int n_mel, int T, int G, const float* mel, const float* packed, const float* bias, float* spect, hipStream_t s) {
+// n_samples: the samples of the transposed conv that are regrouped, T*256 for inference; up to T*256 + 768 (the trailing ones,
+// frames q = T .. T+2 whose taps reach back into the mel) for the forward direction.  The loader zero-fills past the row.
+static int wg_upsample(int B, int n_mel, int T, int G, long n_samples, const float* mel, const float* packed, const float* bias, float* spect, hipStream_t s) {
     const char* who = "waveglow upsample";
     T2_TRY_RC(wg_check_common(who, B, T));
     T2_REQUIRE(n_mel >= 1 && n_mel <= 512, "%s: n_mel_channels=%d outside 1..512", who, n_mel);
     T2_REQUIRE(G >= 2 && G <= 8 && G % 2 == 0, "%s: n_group=%d is not even and from 2 to 8", who, G);
-    T2_REQUIRE((long)T * kWgUpStride / G >= 1, "%s: T=%d frames give no whole group of %d samples", who, T, G);
+    T2_REQUIRE(n_samples / G >= 1, "%s: %ld samples give no whole group of %d", who, n_samples, G);
+    T2_REQUIRE(n_samples <= (long)T * kWgUpStride + kWgUpK - kWgUpStride, "%s: %ld samples, %d frames give %ld", who, n_samples, T,
+               (long)T * kWgUpStride + kWgUpK - kWgUpStride);
     T2_REQUIRE(mel && packed && bias && spect, "%s: null pointer", who);
     WgGemm p{};
     p.x0 = mel; p.wp = packed; p.bias0 = bias; p.y0 = spect;
     p.C0 = n_mel; p.N = T; p.taps = kWgUpTaps; p.coff0 = kWgUpTaps - 1; p.cstep = -1; p.halo = kWgUpTaps - 1;
-    p.rows = n_mel * kWgUpStride; p.mtiles = p.rows / 32; p.nch0 = chunks(n_mel); p.G = G; p.Lg = (long)T * kWgUpStride / G;
+    p.rows = n_mel * kWgUpStride; p.mtiles = p.rows / 32; p.nch0 = chunks(n_mel); p.G = G; p.Lg = n_samples / G;
+    p.Nq = (int)std::max((long)T, (p.Lg * G + kWgUpStride - 1) / kWgUpStride);
     return wg_launch<kWgUpsample>(p, B, s);
 }
 
@@ -355,6 +560,53 @@ static int wg_couple(int B, const WgCouple& p, hipStream_t s) {
     T2_REQUIRE(p.n_early >= 0 && p.n_early + 2 * p.n_half <= 8, "%s: %d early channels on top of %d exceed 8", who, p.n_early, 2 * p.n_half);
     T2_REQUIRE(p.out && p.w_end && p.b_end && p.in && p.winv && (p.dst || p.inter) && (p.n_early == 0 || (p.z && p.dst)), "%s: null pointer", who);
     hipLaunchKernelGGL(wg_couple_kernel, dim3((unsigned)((p.L + 255) / 256), (unsigned)B), dim3(256), 0, s, p);
+    T2_LAUNCH_CHECK();
+    return 0;
+}
+
+static int wg_head(int B, int G, long N, const float* audio, const float* w, float* dst, hipStream_t s) {
+    const char* who = "waveglow head";
+    T2_REQUIRE(G >= 2 && G <= 8 && G % 2 == 0, "%s: n_group=%d is not even and from 2 to 8", who, G);
+    T2_REQUIRE(N >= G, "%s: n_samples=%ld is shorter than one group of %d", who, N, G);
+    T2_TRY_RC(wg_check_common(who, B, N / G));
+    T2_REQUIRE(audio && w && dst, "%s: null pointer", who);
+    hipLaunchKernelGGL(wg_head_kernel, dim3((unsigned)((N / G + 255) / 256), (unsigned)B), dim3(256), 0, s, audio, w, dst, G, N, N / G);
+    T2_LAUNCH_CHECK();
+    return 0;
+}
+
+static int wg_tail(int B, const WgTail& p, hipStream_t s) {
+    const char* who = "waveglow forward tail";
+    const int C = 2 * p.n_half;
+    T2_TRY_RC(wg_check_common(who, B, p.L));
+    T2_TRY_RC(wg_check_nc(who, p.nc));
+    T2_REQUIRE(p.n_half >= 1 && p.n_half <= 4, "%s: n_half=%d outside 1..4", who, p.n_half);
+    T2_REQUIRE(p.n_peel >= 0 && p.n_peel <= C && p.n_peel != C - 1, "%s: %d of %d channels peeled leave no whole flow", who, p.n_peel, C);
+    T2_REQUIRE(p.zoff >= 0 && p.zoff + p.n_peel <= p.G && p.G <= 8, "%s: channels %d..%d of z lie outside its %d", who, p.zoff, p.zoff + p.n_peel, p.G);
+    T2_REQUIRE(p.out && p.w_end && p.b_end && p.in && (p.n_peel == C || (p.wnext && p.dst)) && (p.n_peel == 0 || p.z || p.part_z) &&
+               !p.part_s == !p.part_z, "%s: null pointer", who);
+    hipLaunchKernelGGL(wg_tail_kernel, dim3((unsigned)((p.L + 255) / 256), (unsigned)B), dim3(256), 0, s, p);
+    T2_LAUNCH_CHECK();
+    return 0;
+}
+
+static int wg_logdet(const float* w, int c, int n, float* out, hipStream_t s) {
+    T2_REQUIRE(c >= 1 && c <= 8, "waveglow logdet: matrices of %d x %d, at most 8 x 8 are taken", c, c);
+    T2_REQUIRE(n >= 1 && w && out, "waveglow logdet: %d matrices or a null pointer", n);
+    hipLaunchKernelGGL(wg_logdet_kernel, dim3((unsigned)n), dim3(64), 0, s, w, c, out);
+    T2_LAUNCH_CHECK();
+    return 0;
+}
+
+static int wg_nll_item(int n_flows, int B, int nblk, long L, int G, float sigma, const double* part_s, const double* part_z, const float* logdet_w,
+                       double* sums, double* item, float* nll_item, hipStream_t s) {
+    hipLaunchKernelGGL(wg_nll_item_kernel, dim3((unsigned)B), dim3(64), 0, s, part_s, part_z, n_flows, B, nblk, L, G, sigma, logdet_w, sums, item, nll_item);
+    T2_LAUNCH_CHECK();
+    return 0;
+}
+
+static int wg_nll_loss(int n_flows, int B, long L, const double* item, const float* logdet_w, float* logdet, float* loss, hipStream_t s) {
+    hipLaunchKernelGGL(wg_nll_loss_kernel, dim3(1), dim3(256), 0, s, item, B, L, n_flows, logdet_w, logdet, loss);
     T2_LAUNCH_CHECK();
     return 0;
 }
@@ -467,6 +719,45 @@ static int wg_pack_model(const t2_waveglow_config& c, const float* const* t, int
     return 0;
 }
 
+// kernel_ms_host: an event in front of (mark) and behind (timed) every launch, added up per kernel kind at the end (finish)
+struct WgTimer {
+    double* ms; int n_kinds; hipStream_t s; const char* who;
+    std::vector<hipEvent_t> ev;
+    std::vector<int> kinds;
+    void mark() {
+        if (ms) {
+            hipEvent_t e;
+            if (hipEventCreate(&e) == hipSuccess && hipEventRecord(e, s) == hipSuccess) ev.push_back(e);
+        }
+    }
+    int timed(int kind, int r) {
+        if (ms && r == 0) {
+            hipEvent_t e;
+            if (hipEventCreate(&e) != hipSuccess || hipEventRecord(e, s) != hipSuccess) { t2_set_error("%s: event failed", who); return -2; }
+            ev.push_back(e); kinds.push_back(kind);
+        }
+        return r;
+    }
+    int finish(int rc) {
+        if (ms) {
+            for (int i = 0; i < n_kinds; ++i) ms[i] = 0.0;
+            if (rc == 0 && hipStreamSynchronize(s) != hipSuccess) { t2_set_error("%s: synchronising for the kernel times failed", who); rc = -2; }
+            for (size_t i = 0; rc == 0 && i + 1 < ev.size() && i / 2 < kinds.size(); i += 2) {
+                float t = 0.f;
+                if (hipEventElapsedTime(&t, ev[i], ev[i + 1]) == hipSuccess) ms[kinds[i / 2]] += t;
+            }
+            for (hipEvent_t e : ev) (void)hipEventDestroy(e);
+        }
+        return rc;
+    }
+};
+#define WG_RUN(kind, call)                      \
+    do {                                        \
+        tm.mark();                              \
+        rc = tm.timed(kind, call);              \
+        if (rc != 0) goto done;                 \
+    } while (0)
+
 static int wg_infer(const t2_waveglow_config& c, const t2_waveglow_infer_args& a, hipStream_t s) {
     WgLayout lay;
     t2_waveglow_plan_info pl;
@@ -482,33 +773,11 @@ static int wg_infer(const t2_waveglow_config& c, const t2_waveglow_infer_args& a
     float* spect = a.workspace; float* x = spect + per * n_cond; float* out = x + per * nc; float* acts = out + per * nc;
     float* bufs[2] = {acts + per * nc, acts + per * nc + per * G};
 
-    std::vector<hipEvent_t> ev;
-    std::vector<int> kinds;
+    WgTimer tm{a.kernel_ms_host, T2_WAVEGLOW_KERNELS, s, "t2_waveglow_infer"};
     int rc = 0;
-    auto timed = [&](int kind, int r) {            // kernel_ms_host: an event in front of (mark) and behind (timed) every launch
-        if (a.kernel_ms_host && r == 0) {
-            hipEvent_t e;
-            if (hipEventCreate(&e) != hipSuccess || hipEventRecord(e, s) != hipSuccess) { t2_set_error("t2_waveglow_infer: event failed"); return -2; }
-            ev.push_back(e); kinds.push_back(kind);
-        }
-        return r;
-    };
-    auto mark = [&]() {
-        if (a.kernel_ms_host) {
-            hipEvent_t e;
-            if (hipEventCreate(&e) == hipSuccess && hipEventRecord(e, s) == hipSuccess) ev.push_back(e);
-        }
-        return 0;
-    };
-#define WG_RUN(kind, call)                      \
-    do {                                        \
-        mark();                                 \
-        rc = timed(kind, call);                 \
-        if (rc != 0) goto done;                 \
-    } while (0)
-
     {
-        WG_RUN(0, wg_upsample(B, c.n_mel_channels, a.T, G, a.mel, a.packed + lay.up_w, a.packed + lay.up_b, spect, s));
+        WG_RUN(0, wg_upsample(B, c.n_mel_channels, a.T, G, (long)a.T * kWgUpStride, a.mel, a.packed + lay.up_w, a.packed + lay.up_b,
+                              spect, s));
         const float* src = a.noise_host[0];
         float scale = a.sigma;
         int plane = 1, cur = 0;
@@ -529,18 +798,94 @@ static int wg_infer(const t2_waveglow_config& c, const t2_waveglow_infer_args& a
         if (a.spect) rc = wg_copy(a.spect, spect, (size_t)B * n_cond * L, s);
     }
 done:
-#undef WG_RUN
-    if (a.kernel_ms_host) {
-        for (int i = 0; i < T2_WAVEGLOW_KERNELS; ++i) a.kernel_ms_host[i] = 0.0;
-        if (rc == 0 && hipStreamSynchronize(s) != hipSuccess) { t2_set_error("t2_waveglow_infer: synchronising for the kernel times failed"); rc = -2; }
-        for (size_t i = 0; rc == 0 && i + 1 < ev.size() && i / 2 < kinds.size(); i += 2) {
-            float ms = 0.f;
-            if (hipEventElapsedTime(&ms, ev[i], ev[i + 1]) == hipSuccess) a.kernel_ms_host[kinds[i / 2]] += ms;
-        }
-        for (hipEvent_t e : ev) (void)hipEventDestroy(e);
-    }
-    return rc;
+    return tm.finish(rc);
 }
+
+// ------------------------------------------------------------------------------------------------------------------
+// the forward direction: audio -> z, log_s, log det W and the negative log-likelihood (glow.py:207-249, :48-59)
+// ------------------------------------------------------------------------------------------------------------------
+static int wg_forward_plan(const t2_waveglow_config& c, int B, int T, long N, t2_waveglow_forward_info* out, WgLayout* lay) {
+    WgLayout L;
+    T2_TRY_RC(wg_layout(c, &L));
+    T2_REQUIRE(B >= 1 && B <= 65535, "waveglow forward: B=%d outside 1..65535", B);
+    T2_REQUIRE(T >= 1, "waveglow forward: T=%d frames, must be at least 1", T);
+    T2_REQUIRE(N >= c.n_group, "waveglow forward: n_samples=%ld is shorter than one group of n_group=%d", N, c.n_group);
+    const long have = ((long)T - 1) * kWgUpStride + kWgUpK;
+    T2_REQUIRE(N <= have, "waveglow forward: n_samples=%ld, but the upsampled mel of T=%d frames has only %ld (glow.py:216)", N, T, have);
+    const long cols = N / c.n_group;
+    T2_REQUIRE(cols <= (long)INT32_MAX / 2, "waveglow forward: L=%ld exceeds the limit of %d columns per row", cols, INT32_MAX / 2);
+    if (out) {
+        int rows = 0;
+        for (const WgFlow& f : L.flows) rows += f.n_half;
+        out->L = cols; out->n_log_s_rows = rows; out->n_tensors = L.n_tensors;
+        out->n_blocks = (cols + 255) / 256;
+        out->n_partials = (size_t)2 * c.n_flows * B * out->n_blocks;
+        const size_t per = round4((size_t)B * cols);
+        out->workspace_bytes = per * ((size_t)c.n_mel_channels * c.n_group + 3 * (size_t)c.n_channels + 2 * (size_t)c.n_group) * sizeof(float) +
+                               (out->n_partials + (size_t)B * (c.n_flows + 2)) * sizeof(double);
+        out->packed_bytes = L.total * sizeof(float);
+    }
+    if (lay) *lay = L;
+    return 0;
+}
+
+static int wg_logdet_model(const t2_waveglow_config& c, const float* packed, float* logdet, hipStream_t s) {
+    WgLayout lay;
+    T2_TRY_RC(wg_layout(c, &lay));
+    T2_REQUIRE(packed && logdet, "t2_waveglow_logdet: null pointer");
+    for (int k = 0; k < c.n_flows; ++k) T2_TRY_RC(wg_logdet(packed + lay.flows[k].winv, lay.flows[k].c, 1, logdet + k, s));
+    return 0;
+}
+
+static int wg_forward(const t2_waveglow_config& c, const t2_waveglow_forward_args& a, hipStream_t s) {
+    WgLayout lay;
+    t2_waveglow_forward_info pl;
+    T2_TRY_RC(wg_forward_plan(c, a.B, a.T, a.n_samples, &pl, &lay));      // judges the configuration first
+    T2_REQUIRE(a.n_mel == c.n_mel_channels, "t2_waveglow_forward: the mel has %d channels, the model takes %d", a.n_mel, c.n_mel_channels);
+    const bool want_sums = a.sums || a.nll_item || a.loss;
+    T2_REQUIRE(a.packed && a.mel && a.audio && a.workspace && (a.z || want_sums), "t2_waveglow_forward: null pointer");
+    T2_REQUIRE(a.logdet_w || !(want_sums || a.logdet), "t2_waveglow_forward: logdet_w is null, but a sum or logdet is asked for");
+    T2_REQUIRE(!want_sums || a.sigma > 0.f, "t2_waveglow_forward: sigma=%g must be positive", (double)a.sigma);
+    for (int k = 0; a.log_s_host && k < c.n_flows; ++k) T2_REQUIRE(a.log_s_host[k], "t2_waveglow_forward: log_s pointer %d is null", k);
+    const int B = a.B, nc = c.n_channels, G = c.n_group, n_cond = c.n_mel_channels * G, nblk = (int)pl.n_blocks;
+    const long L = pl.L;
+    const size_t per = round4((size_t)B * L);
+    float* spect = a.workspace; float* x = spect + per * n_cond; float* out = x + per * nc; float* acts = out + per * nc;
+    float* bufs[2] = {acts + per * nc, acts + per * nc + per * G};
+    double* part = reinterpret_cast<double*>(bufs[1] + per * G);          // the floats before it are a multiple of 4: 16-byte aligned
+    double* part_z = part + (size_t)c.n_flows * B * nblk;
+    double* item = part + pl.n_partials;
+    double* sums = a.sums ? a.sums : item + B;
+
+    WgTimer tm{a.kernel_ms_host, T2_WAVEGLOW_FORWARD_KERNELS, s, "t2_waveglow_forward"};
+    int rc = 0;
+    {
+        WG_RUN(0, wg_upsample(B, c.n_mel_channels, a.T, G, L * G, a.mel, a.packed + lay.up_w, a.packed + lay.up_b, spect, s));
+        WG_RUN(4, wg_head(B, G, a.n_samples, a.audio, a.packed + lay.flows[0].winv, bufs[0], s));
+        int cur = 0, zoff = 0;
+        for (int k = 0; k < c.n_flows; ++k) {
+            const WgFlow& f = lay.flows[k];
+            const WgFlow* next = k + 1 < c.n_flows ? &lay.flows[k + 1] : nullptr;
+            WG_RUN(1, wg_start(B, nc, f.c, f.n_half, L, 1.f, bufs[cur], a.packed + f.start_w, a.packed + f.start_b, x, s));
+            for (int i = 0; i < c.n_layers; ++i) {
+                WG_RUN(2, wg_gated(B, nc, n_cond, L, 1 << i, 0, x, spect, a.packed + f.gated[i], a.packed + f.in_b[i],
+                                   a.packed + f.cond_b + (size_t)2 * nc * i, acts, s));
+                WG_RUN(3, wg_res_skip(B, nc, L, i == 0, i == c.n_layers - 1, acts, a.packed + f.rs[i], a.packed + f.rs_b[i], x, out, s));
+            }
+            WgTail p{out, a.packed + f.end_w, a.packed + f.end_b, bufs[cur], next ? a.packed + next->winv : nullptr,
+                     next ? bufs[cur ^ 1] : nullptr, a.z, a.log_s_host ? a.log_s_host[k] : nullptr,
+                     want_sums ? part + (size_t)k * B * nblk : nullptr, want_sums ? part_z + (size_t)k * B * nblk : nullptr,
+                     nc, f.n_half, next ? f.c - next->c : f.c, G, zoff, L};
+            WG_RUN(5, wg_tail(B, p, s));
+            zoff += p.n_peel; cur ^= 1;
+        }
+        if (want_sums) WG_RUN(6, wg_nll_item(c.n_flows, B, nblk, L, G, a.sigma, part, part_z, a.logdet_w, sums, item, a.nll_item, s));
+        if (a.logdet || a.loss) WG_RUN(6, wg_nll_loss(c.n_flows, B, L, item, a.logdet_w, a.logdet, a.loss, s));
+    }
+done:
+    return tm.finish(rc);
+}
+#undef WG_RUN
 
 }  // namespace t2
 
@@ -586,12 +931,35 @@ int t2_waveglow_upsample(const t2_waveglow_upsample_args* a, void* stream) {
     T2_REQUIRE(a->n_mel >= 1 && a->n_mel <= 512, "waveglow upsample: n_mel_channels=%d outside 1..512", a->n_mel);
     T2_REQUIRE(a->w && a->packed_ws, "t2_waveglow_upsample: null weights or packing scratch");
     T2_TRY_RC(wg_pack(kWgUpsample, a->w, nullptr, a->packed_ws, a->n_mel, a->n_mel, 0, (hipStream_t)stream));
-    return wg_upsample(a->B, a->n_mel, a->T, a->n_group, a->mel, a->packed_ws, a->bias, a->spect, (hipStream_t)stream);
+    return wg_upsample(a->B, a->n_mel, a->T, a->n_group, (long)a->T * kWgUpStride, a->mel, a->packed_ws, a->bias, a->spect, (hipStream_t)stream);
 }
 int t2_waveglow_couple(const t2_waveglow_couple_args* a, void* stream) {
     T2_REQUIRE(a, "t2_waveglow_couple: null arguments");
     return wg_couple(a->B, WgCouple{a->out, a->w_end, a->b_end, a->audio_in, a->w_inverse, a->z, a->audio_out, a->audio_interleaved, a->nc, a->n_half,
                                     a->n_early, (long)a->L, a->in_scale, a->sigma}, (hipStream_t)stream);
+}
+int t2_waveglow_forward_plan(const t2_waveglow_config* cfg, int B, int T, long n_samples, t2_waveglow_forward_info* out) {
+    T2_REQUIRE(cfg && out, "t2_waveglow_forward_plan: null pointer");
+    return wg_forward_plan(*cfg, B, T, n_samples, out, nullptr);
+}
+int t2_waveglow_forward(const t2_waveglow_config* cfg, const t2_waveglow_forward_args* a, void* stream) {
+    T2_REQUIRE(cfg && a, "t2_waveglow_forward: null pointer");
+    return wg_forward(*cfg, *a, (hipStream_t)stream);
+}
+int t2_waveglow_logdet(const t2_waveglow_config* cfg, const float* packed, float* logdet, void* stream) {
+    T2_REQUIRE(cfg, "t2_waveglow_logdet: null configuration");
+    return wg_logdet_model(*cfg, packed, logdet, (hipStream_t)stream);
+}
+int t2_waveglow_logdet_matrices(const float* w, int c, int n, float* out, void* stream) { return wg_logdet(w, c, n, out, (hipStream_t)stream); }
+int t2_waveglow_head(const t2_waveglow_head_args* a, void* stream) {
+    T2_REQUIRE(a, "t2_waveglow_head: null arguments");
+    return wg_head(a->B, a->n_group, a->n_samples, a->audio, a->w, a->audio_out, (hipStream_t)stream);
+}
+int t2_waveglow_tail(const t2_waveglow_tail_args* a, void* stream) {
+    T2_REQUIRE(a, "t2_waveglow_tail: null arguments");
+    T2_REQUIRE(!a->part_s == !a->part_z, "t2_waveglow_tail: part_s and part_z go together");
+    return wg_tail(a->B, WgTail{a->out, a->w_end, a->b_end, a->audio_in, a->w_next, a->audio_out, a->z, a->log_s, a->part_s, a->part_z, a->nc, a->n_half,
+                                a->n_peel, a->n_group, a->z_offset, (long)a->L}, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -1,4 +1,5 @@
-"""Drop-in for the reference's ``glow.WaveGlow`` (glow.py:178-310) on the MI355X: inference only.
+"""Drop-in for the reference's ``glow.WaveGlow`` (glow.py:178-310) and ``glow.WaveGlowLoss`` (glow.py:43-59) on the MI355X:
+inference, and the values of the training direction (no gradient).
 
 The modules below only hold parameters, under the names and shapes the reference's checkpoints use; ``WaveGlow.infer``
 folds the weight norm (g * v / ||v||), inverts the 1x1 mixes once in fp32 (glow.py:91), hands everything to the HIP library
@@ -12,8 +13,17 @@ So the reference's lines work verbatim::
 
 A module that was pickled whole by the reference (its classes live in a top-level ``glow``) loads once
 ``sys.modules['glow']`` points at this module; its children are then torch's own Conv1d / ConvTranspose1d, weight-normed or
-not, which ``infer`` reads just the same.  Always fp32 (``set_precision`` does not reach the vocoder), no CPU path, no
-training (``forward``, WaveGlowLoss)."""
+not, which ``infer`` reads just the same.  Always fp32 (``set_precision`` does not reach the vocoder), no CPU path.
+
+The other direction of the flow, audio -> z (glow.py:207-249, what waveglow/train.py:125-127 calls on every batch), is there as
+values without a gradient: ``analyze((mel, audio))`` returns the reference's ``(z, log_s_list, log_det_W_list)``,
+``WaveGlowLoss(sigma)`` turns such a tuple into the negative log-likelihood per sample, and ``nll(mel, audio, sigma)`` gives
+that number (or one per item) straight from sums the kernels form, for a validation or scoring loop::
+
+    with torch.no_grad():
+        loss = waveglow.nll(mel, audio, sigma=1.0)                  # == WaveGlowLoss(1.0)(waveglow.analyze((mel, audio)))
+
+``forward`` / ``__call__`` still refuse: inside a training loop a forward without a backward would silently train nothing."""
 from __future__ import annotations
 
 import ctypes as C
@@ -23,6 +33,29 @@ import torch
 from torch import nn
 
 from .. import _lib as L
+
+
+# what WaveGlow caches outside its pickled state: inference's packed weights, the analysis direction's and their log|det W_k|
+_CACHES = ("_packed", "_packed_key", "_packed_fwd", "_packed_fwd_key", "_logdet_fwd")
+
+
+class WaveGlowLoss(nn.Module):
+    """glow.py:43-59: the negative log-likelihood per sample of ``(z, log_s_list, log_det_W_list)``, in torch ops on any such
+    tuple (what ``WaveGlow.analyze`` returns, or the reference's own forward).  ``WaveGlow.nll`` gives the same value from sums
+    the kernels make, without the log_s tensors."""
+
+    def __init__(self, sigma=1.0):
+        super().__init__()
+        self.sigma = sigma
+
+    def forward(self, model_output):
+        z, log_s_list, log_det_W_list = model_output
+        # the terms are added flow by flow, k ascending, as the reference adds them; its += on log_det_W_list[0] is not repeated
+        log_s_total, log_det_total = torch.sum(log_s_list[0]), log_det_W_list[0]
+        for log_s, log_det in zip(log_s_list[1:], log_det_W_list[1:]):
+            log_s_total, log_det_total = log_s_total + torch.sum(log_s), log_det_total + log_det
+        gaussian = torch.sum(z * z) / (2 * self.sigma * self.sigma)
+        return (gaussian - log_s_total - log_det_total) / z.numel()
 
 
 class _Conv(nn.Module):
@@ -140,8 +173,13 @@ class WaveGlow(nn.Module):
     # unpickled from a checkpoint (no __init__) works too
     def __getstate__(self):
         state = dict(self.__dict__)
-        state.pop("_packed", None), state.pop("_packed_key", None)
+        for name in _CACHES:
+            state.pop(name, None)
         return state
+
+    def _drop_caches(self):
+        for name in _CACHES:
+            self.__dict__.pop(name, None)
 
     def _config(self) -> L.WaveglowConfig:
         wn = self.WN[0]
@@ -153,7 +191,8 @@ class WaveGlow(nn.Module):
                                  dict(n_layers=wn.n_layers, n_channels=wn.n_channels, kernel_size=k[0] if isinstance(k, (tuple, list)) else k))
 
     def forward(self, forward_input):
-        raise RuntimeError("WaveGlow is inference only here: forward (the training direction, audio -> z) is not built; call infer")
+        raise RuntimeError("WaveGlow is inference only here: forward (the training direction, audio -> z) has no backward, so it stays "
+                           "refused; call infer, or analyze / nll for the values of that direction under torch.no_grad()")
 
     @staticmethod
     def remove_weightnorm(model):
@@ -163,24 +202,24 @@ class WaveGlow(nn.Module):
             for l in list(wn.in_layers) + list(wn.res_skip_layers):
                 _remove_weight_norm(l)
             _remove_weight_norm(wn.cond_layer)
-        waveglow._packed = None
+        waveglow._drop_caches()
         return waveglow
 
     def load_state_dict(self, *args, **kwargs):
         out = super().load_state_dict(*args, **kwargs)
-        self._packed = None
+        self._drop_caches()
         return out
 
     def _apply(self, fn, *args, **kwargs):               # .to() / .cuda() / .float()
         out = super()._apply(fn, *args, **kwargs)
-        self._packed = None
+        self._drop_caches()
         return out
 
     def _key(self):
         return tuple((p.data_ptr(), p._version) for p in self.parameters())
 
-    def _tensors(self):
-        """The folded weights in the order t2_waveglow_pack takes them."""
+    def _tensors(self, forward=False):
+        """The folded weights in the order t2_waveglow_pack takes them; forward: W_k itself where inference has its inverse."""
         f32 = lambda t: t.detach().to(torch.float32).contiguous()
         out = [f32(self.upsample.weight), f32(self.upsample.bias)]
         for wn, inv in zip(self.WN, self.convinv):
@@ -190,25 +229,39 @@ class WaveGlow(nn.Module):
             for l in wn.res_skip_layers:
                 out += [f32(_folded(l)), f32(l.bias)]
             W = inv.conv.weight.detach().squeeze(-1)
-            out += [f32(wn.end.weight), f32(wn.end.bias), f32(W.float().inverse())]     # glow.py:91
+            out += [f32(wn.end.weight), f32(wn.end.bias), f32(W) if forward else f32(W.float().inverse())]     # glow.py:91
         return out
 
     def repack(self):
-        """Fold, invert and pack the weights again.  infer() does this by itself after load_state_dict, remove_weightnorm,
-        .to() and in-place updates that autograd sees; call it after editing parameters behind autograd's back (``.data``)."""
+        """Fold, invert and pack the weights again (and, once analyze / nll have run, their buffer too).  infer(), analyze() and
+        nll() do this by themselves after load_state_dict, remove_weightnorm, .to() and in-place updates that autograd sees; call
+        it after editing parameters behind autograd's back (``.data``)."""
+        forward = getattr(self, "_packed_fwd", None) is not None
+        self._pack(False)
+        if forward:
+            self._pack(True)
+        return self
+
+    def _pack(self, forward):
+        """One packed buffer: inference's (the inverse mixes) or, forward, the analysis direction's (W_k itself, and log|det W_k|)."""
         dev = self.upsample.weight.device
         if dev.type != "cuda":
             raise RuntimeError("WaveGlow: the parameters must live on the GPU (the product path has no CPU fallback)")
         cfg = self._config()
         plan = L.waveglow_plan(cfg, 1, 1)
         with torch.no_grad():
-            ts = self._tensors()
+            ts = self._tensors(forward)
         packed = torch.empty(plan.packed_bytes // 4, device=dev, dtype=torch.float32)
         tp = (C.c_void_p * len(ts))(*[L.ptr(t) for t in ts])
         with torch.cuda.device(dev):
             L.check(L.lib().t2_waveglow_pack(C.byref(cfg), tp, len(ts), L.ptr(packed), L.stream()))
-        self._packed, self._packed_key = packed, self._key()
-        return self
+            if forward:
+                logdet = torch.empty(cfg.n_flows, device=dev, dtype=torch.float32)
+                L.check(L.lib().t2_waveglow_logdet(C.byref(cfg), L.ptr(packed), L.ptr(logdet), L.stream()))
+        if forward:
+            self._packed_fwd, self._logdet_fwd, self._packed_fwd_key = packed, logdet, self._key()
+        else:
+            self._packed, self._packed_key = packed, self._key()
 
     def infer(self, spect, sigma=1.0, noise=None):
         """mel [B, n_mel_channels, T], fp32, on the GPU -> audio [B, T * 256] (glow.py:251-293).  The noise planes are drawn
@@ -269,3 +322,79 @@ class WaveGlow(nn.Module):
         if kernel_times:
             info["kernel_ms"] = dict(zip(L.WAVEGLOW_KERNELS, ms))
         return audio, info
+
+    # ---- the analysis direction: audio -> z, log_s, log det W (glow.py:207-249), values only
+    def analyze(self, forward_input):
+        """``(spect [B, n_mel_channels, T], audio [B, N])``, fp32 on the GPU -> ``(z, log_s_list, log_det_W_list)`` as the
+        reference's ``forward`` returns them: z [B, n_group, L] with L = N // n_group (early outputs first, k ascending, then the
+        last flow's audio; a tail of N % n_group samples is dropped, as ``unfold`` drops it), log_s_list[k] [B, n_half_k, L] and
+        log_det_W_list[k] = B * L * logdet(W_k), a 0-dim tensor.  N may reach (T - 1) * 256 + 1024, the length of the transposed
+        conv's output.  Values only: no gradient flows, which is why ``forward`` still refuses."""
+        return self._forward_direction(forward_input, "analyze", want_outputs=True)[:3]
+
+    def nll(self, spect, audio, sigma=1.0, per_item=False):
+        """``WaveGlowLoss(sigma)(analyze((spect, audio)))`` as a device scalar, from sums the kernels form in fp64 in a fixed
+        order; no log_s tensor is written.  per_item: [B], every item's own mean negative log-likelihood per sample (their
+        mean is the scalar)."""
+        out = self._forward_direction((spect, audio), "nll", want_outputs=False, sigma=sigma)
+        return out[4] if per_item else out[3]
+
+    def analyze_debug(self, forward_input, sigma=1.0, kernel_times=False):
+        """analyze, returning (z, log_s_list, log_det_W_list, info): info holds ``loss``, ``nll_item`` [B] and ``sums``
+        [B, n_flows + 1] fp64 (per item the sum of every log_s[k], then the sum of z^2) and, kernel_times, ``kernel_ms``."""
+        z, log_s, logdet, loss, item, sums, ms = self._forward_direction(forward_input, "analyze", want_outputs=True, sigma=sigma, want_sums=True,
+                                                                         kernel_times=kernel_times)
+        info = dict(loss=loss, nll_item=item, sums=sums)
+        if kernel_times:
+            info["kernel_ms"] = ms
+        return z, log_s, logdet, info
+
+    def _forward_direction(self, forward_input, who, want_outputs, sigma=1.0, want_sums=None, kernel_times=False):
+        spect, audio = forward_input
+        who = "WaveGlow." + who
+        if not (spect.is_cuda and audio.is_cuda):
+            raise RuntimeError(f"{who}: the mel and the audio must live on the GPU (the product path has no CPU fallback)")
+        if torch.is_grad_enabled() and (spect.requires_grad or audio.requires_grad or any(p.requires_grad for p in self.parameters())):
+            raise RuntimeError(f"{who} computes values only, the backward is not built: grad mode is on and the inputs or the "
+                               "parameters require grad; call it under torch.no_grad()")
+        cfg = self._config()
+        if spect.dim() != 3 or spect.shape[1] != cfg.n_mel_channels:
+            raise RuntimeError(f"{who}: expected a mel of shape [B, {cfg.n_mel_channels}, T] (upsample takes "
+                               f"{cfg.n_mel_channels} channels), got {tuple(spect.shape)}")
+        if audio.dim() != 2 or audio.shape[0] != spect.shape[0]:
+            raise RuntimeError(f"{who}: expected audio of shape [B, N] with B = {spect.shape[0]}, got {tuple(audio.shape)}")
+        if spect.dtype != torch.float32 or audio.dtype != torch.float32:
+            raise RuntimeError(f"{who}: the mel and the audio must be float32, got {spect.dtype} and {audio.dtype} (fp16 is not built)")
+        if audio.device != spect.device:
+            raise RuntimeError(f"{who}: the mel is on {spect.device}, the audio on {audio.device}")
+        want_sums = (not want_outputs) if want_sums is None else want_sums
+        if want_sums and not float(sigma) > 0.0:
+            raise RuntimeError(f"{who}: sigma={sigma} must be positive")
+        packed = getattr(self, "_packed_fwd", None)
+        if packed is None or packed.device != spect.device or getattr(self, "_packed_fwd_key", None) != self._key():
+            self._pack(True)
+            packed = self._packed_fwd
+            if packed.device != spect.device:
+                raise RuntimeError(f"{who}: the mel is on {spect.device}, the parameters on {packed.device}")
+        (B, n_mel, T), N = spect.shape, audio.shape[1]
+        plan = L.waveglow_forward_plan(cfg, B, T, N)               # refuses N < n_group and N > (T - 1) * 256 + 1024, by value
+        dev, f32 = spect.device, torch.float32
+        with torch.cuda.device(dev):
+            mel, wave = spect.detach().contiguous(), audio.detach().contiguous()
+            ws = torch.empty(plan.workspace_bytes // 4, device=dev, dtype=f32)
+            z = log_s = logdet = loss = item = sums = table = None
+            if want_outputs:
+                z = torch.empty(B, cfg.n_group, plan.L, device=dev, dtype=f32)
+                log_s = [torch.empty(B, inv.conv.weight.shape[0] // 2, plan.L, device=dev, dtype=f32) for inv in self.convinv]
+                assert sum(t.shape[1] for t in log_s) == plan.n_log_s_rows
+                table = (C.c_void_p * len(log_s))(*[L.ptr(t) for t in log_s])
+                logdet = torch.empty(cfg.n_flows, device=dev, dtype=f32)
+            if want_sums:
+                loss, item = torch.empty((), device=dev, dtype=f32), torch.empty(B, device=dev, dtype=f32)
+                sums = torch.empty(B, cfg.n_flows + 1, device=dev, dtype=torch.float64)
+            ms = (C.c_double * len(L.WAVEGLOW_FORWARD_KERNELS))() if kernel_times else None
+            a = L.WaveglowForwardArgs(B, T, n_mel, N, L.ptr(packed), L.ptr(self._logdet_fwd), L.ptr(mel), L.ptr(wave), L.ptr(ws), L.ptr(z), table,
+                                      L.ptr(logdet), float(sigma), L.ptr(sums), L.ptr(item), L.ptr(loss), ms)
+            L.check(L.lib().t2_waveglow_forward(C.byref(cfg), C.byref(a), L.stream()))
+        return (z, log_s, None if logdet is None else list(logdet.unbind(0)), loss, item, sums,
+                dict(zip(L.WAVEGLOW_FORWARD_KERNELS, ms)) if kernel_times else None)
