@@ -949,6 +949,121 @@ typedef struct t2_waveglow_tail_args {
 } t2_waveglow_tail_args;
 int t2_waveglow_tail(const t2_waveglow_tail_args* a, void* stream);
 
+/* ---- WaveGlow training: the forward that keeps what the backward reads, and the backward ----------------
+ * What waveglow/train.py:125-137 does on every batch.  t2_waveglow_train_forward is t2_waveglow_forward (the same launches,
+ * the same bits for the same `packed`) that leaves in `saved`: spect once; per flow the mixed audio_in [B, c_k, L] and out
+ * [B, nc, L]; per flow and layer x_i, tanh(u_a), sigmoid(u_b), [B, nc, L] each (acts = t * g is recomputed):
+ *   saved floats = per * (n_mel*G + sum_k (c_k + nc * (1 + 3 * n_layers))),  per = B * L rounded up to a multiple of 4.
+ * t2_waveglow_backward turns upstream gradients on z and on every log_s[k] (each nullable = zero) into the gradient of
+ * every folded tensor, in t2_waveglow_pack's tensor order and torch layout, densely packed into `grad` (grad_floats =
+ * the parameter count of the folded model; t2_waveglow_grad_offsets gives each tensor's offset).  Gradients with respect
+ * to the mel and the audio are not formed.  Exact fp32 on the matrix cores, every sum in a fixed order that depends on
+ * the shape alone, no atomics: `grad` is bit-identical from run to run. */
+#define T2_WAVEGLOW_BACKWARD_KERNELS 8 /* kinds of kernel_ms_host: tail backward (+ its sums, the head), gate backward, conv backward, conditioning backward, weight gradient, its reduce, start backward, upsample backward */
+typedef struct t2_waveglow_backward_info {
+    long L;
+    int n_tensors;
+    size_t saved_bytes;      /* what t2_waveglow_train_forward writes (formula above) */
+    size_t workspace_bytes;  /* of t2_waveglow_backward */
+    size_t grad_floats;
+    size_t packed_bwd_bytes; /* of t2_waveglow_pack_backward */
+    size_t n_slots;          /* fp64 partial-sum slots of the tail backward: B * ceil(L / 256) * 4 */
+} t2_waveglow_backward_info;
+/* Pure host call: validates as t2_waveglow_forward_plan does. */
+int t2_waveglow_backward_plan(const t2_waveglow_config* cfg, int B, int T, long n_samples, t2_waveglow_backward_info* out);
+int t2_waveglow_grad_offsets(const t2_waveglow_config* cfg, size_t* offsets_host, int n_tensors);
+/* The transposed operands of the data gradients, packed once per step from the tensors t2_waveglow_pack takes (W_k itself):
+ * per flow and layer W_in with taps flipped and in/out swapped [nc] x [3 * 2nc], W_cond,i^T [n_mel*G] x [2nc], W_rs^T [nc] x [2nc | nc]. */
+int t2_waveglow_pack_backward(const t2_waveglow_config* cfg, const float* const* tensors_host, int n_tensors, float* packed_bwd, void* stream);
+typedef struct t2_waveglow_train_forward_args {
+    t2_waveglow_forward_args fwd;
+    float* saved;            /* saved_bytes of t2_waveglow_backward_plan */
+} t2_waveglow_train_forward_args;
+int t2_waveglow_train_forward(const t2_waveglow_config* cfg, const t2_waveglow_train_forward_args* a, void* stream);
+typedef struct t2_waveglow_backward_args {
+    int B, T, n_mel;
+    long n_samples;
+    const float* packed;     /* as given to t2_waveglow_train_forward */
+    const float* packed_bwd;
+    const float* saved;
+    const float* mel;        /* [B, n_mel, T] */
+    const float* audio;      /* [B, N] */
+    const float* dz;         /* nullable: [B, G, L] */
+    const float* const* dlog_s_host; /* nullable: HOST array of n_flows DEVICE pointers [B, n_half_k, L], each nullable */
+    float* workspace;
+    float* grad;             /* grad_floats */
+    double* kernel_ms_host;  /* debug output, nullable: T2_WAVEGLOW_BACKWARD_KERNELS totals in ms */
+} t2_waveglow_backward_args;
+int t2_waveglow_backward(const t2_waveglow_config* cfg, const t2_waveglow_backward_args* a, void* stream);
+/* Single kernels, for the tests only (t2_waveglow_backward runs the same ones).
+ * Weight gradient: dw_x[m][c][j] = sum_{b,l} a[b,m,l] * x[b,c,l + (j - taps/2) d] (columns outside the row contribute nothing),
+ * dw_spect[m][c] = sum a * spect (n_cond = 0: none), db[m] = sum a.  workspace: t2_waveglow_weight_grad_ws_floats floats. */
+typedef struct t2_waveglow_weight_grad_args {
+    int B, M, nc, n_cond, L, taps, d;   /* taps 3 with d >= 1, or taps 1 with d = 0 */
+    int a_rows, x_rows;      /* rows per item of the buffers a and x lie in (their first M and nc rows are read); 0: M and nc */
+    const float* a;          /* [B, a_rows, L] */
+    const float* x;          /* [B, x_rows, L] */
+    const float* spect;      /* [B, n_cond, L] */
+    float* dw_x; float* dw_spect; float* db; float* workspace;
+    float* db2;              /* nullable: a second destination of db, as cond_layer.bias's slice is */
+} t2_waveglow_weight_grad_args;
+size_t t2_waveglow_weight_grad_ws_floats(int M, int nc, int n_cond, int taps, int B, int L);
+int t2_waveglow_weight_grad(const t2_waveglow_weight_grad_args* a, void* stream);
+/* d_acts = w_rs^T [dx; d_out] (last: w_rs [nc][nc], d_out alone); du [B, 2nc, L] = [d_acts g (1 - t^2); d_acts t g (1 - g)],
+ * acts [B, nc, L] = t g.  packed_ws: 2 * t2_waveglow_packed_floats(1, nc, nc, 0) floats. */
+typedef struct t2_waveglow_gate_backward_args {
+    int B, nc, L, last;
+    const float* dx; const float* d_out; const float* w_rs; const float* t; const float* g;
+    float* packed_ws; float* du; float* acts;
+} t2_waveglow_gate_backward_args;
+int t2_waveglow_gate_backward(const t2_waveglow_gate_backward_args* a, void* stream);
+/* dx [B, nc, L] (+)= conv^T(du) through w_in [2nc][nc][3] at dilation d, d_spect [B, n_cond, L] (+)= w_cond^T du with w_cond
+ * [2nc][n_cond]; first_*: store, else accumulate.  packed_ws: t2_waveglow_conv_backward_packed_floats floats. */
+typedef struct t2_waveglow_conv_backward_args {
+    int B, nc, n_cond, L, d, first_dx, first_spect;
+    const float* du; const float* w_in; const float* w_cond;
+    float* packed_ws; float* dx; float* d_spect;
+} t2_waveglow_conv_backward_args;
+size_t t2_waveglow_conv_backward_packed_floats(int nc, int n_cond);
+int t2_waveglow_conv_backward(const t2_waveglow_conv_backward_args* a, void* stream);
+/* One flow's tail backwards (see t2_waveglow_tail): d_next [B, C - n_peel, L] is the gradient on audio_out, dz / dlog_s the
+ * upstream ones (nullable).  d_out [B, nc, L] = w_end^T [db; ds]; d_in [B, C, L] = (dV[:n_half], db exp(s)); dw_end [C][nc],
+ * db_end [C], dw_next [C - n_peel]^2 from fp64 partials in `part` (B * ceil(L/256) * 4 * (C*nc + C + (C - n_peel)^2) doubles). */
+typedef struct t2_waveglow_tail_backward_args {
+    int B, nc, n_half, L, n_peel, n_group, z_offset;
+    const float* out; const float* w_end; const float* b_end; const float* audio_in; const float* w_next; const float* d_next;
+    const float* dz; const float* dlog_s;
+    float* d_out; float* d_in; double* part; float* dw_end; float* db_end; float* dw_next;
+} t2_waveglow_tail_backward_args;
+int t2_waveglow_tail_backward(const t2_waveglow_tail_backward_args* a, void* stream);
+/* Start backward: d_in[b, h, l] += sum_c w_start[c][h] * dx[b, c, l] for h < n_half (rows n_half.. of d_in [B, c, L] stay), and
+ * dw_start [nc][n_half] = sum dx * audio_in[:, :n_half]^T, db_start [nc] = sum dx through the weight-gradient kernel (workspace:
+ * t2_waveglow_weight_grad_ws_floats(nc, n_half, 0, 1, B, L) floats). */
+typedef struct t2_waveglow_start_backward_args {
+    int B, nc, c, n_half, L;
+    const float* dx;         /* [B, nc, L] */
+    const float* w_start;    /* [nc][n_half] */
+    const float* audio_in;   /* [B, c, L] */
+    float* d_in;             /* [B, c, L] */
+    float* dw_start; float* db_start; float* workspace;
+} t2_waveglow_start_backward_args;
+int t2_waveglow_start_backward(const t2_waveglow_start_backward_args* a, void* stream);
+/* Head backward: dw [G][G] = sum_{b,l} d_in[b, r, l] * audio[b, l*G + g], from fp64 partials in `part`
+ * (B * ceil(L/256) * 4 * G*G doubles, L = n_samples / G). */
+typedef struct t2_waveglow_head_backward_args {
+    int B, n_group; long n_samples;
+    const float* d_in;       /* [B, G, L] */
+    const float* audio;      /* [B, n_samples] */
+    double* part; float* dw;
+} t2_waveglow_head_backward_args;
+int t2_waveglow_head_backward(const t2_waveglow_head_backward_args* a, void* stream);
+/* dw [n_mel][n_mel][1024], db [n_mel] of the transposed conv from d_spect [B, n_mel*G, n_samples / G]. */
+typedef struct t2_waveglow_upsample_backward_args {
+    int B, n_mel, T, n_group; long n_samples;
+    const float* mel; const float* d_spect; float* dw; float* db;
+} t2_waveglow_upsample_backward_args;
+int t2_waveglow_upsample_backward(const t2_waveglow_upsample_backward_args* a, void* stream);
+
 /* Gradient-norm clipping + Adam over a list of fp32 tensors — replaces torch.nn.utils.clip_grad_norm_ +
  * torch.optim.Adam.step of the training loop (train.py:322-330; Adam with weight decay added to the gradient).
  * `table` is a DEVICE array of n_tensors rows; row i covers chunks [first_chunk, first_chunk + t2_adam_chunks(numel))

@@ -359,8 +359,64 @@ class WaveglowTailArgs(C.Structure):
                 ("audio_out", C.c_void_p), ("z", C.c_void_p), ("log_s", C.c_void_p), ("part_s", C.c_void_p), ("part_z", C.c_void_p)]
 
 
+class WaveglowBackwardInfo(C.Structure):
+    _fields_ = [("L", C.c_long), ("n_tensors", C.c_int), ("saved_bytes", C.c_size_t), ("workspace_bytes", C.c_size_t), ("grad_floats", C.c_size_t),
+                ("packed_bwd_bytes", C.c_size_t), ("n_slots", C.c_size_t)]
+
+
+class WaveglowTrainForwardArgs(C.Structure):
+    _fields_ = [("fwd", WaveglowForwardArgs), ("saved", C.c_void_p)]
+
+
+class WaveglowBackwardArgs(C.Structure):
+    _fields_ = [("B", C.c_int), ("T", C.c_int), ("n_mel", C.c_int), ("n_samples", C.c_long), ("packed", C.c_void_p), ("packed_bwd", C.c_void_p),
+                ("saved", C.c_void_p), ("mel", C.c_void_p), ("audio", C.c_void_p), ("dz", C.c_void_p), ("dlog_s_host", C.POINTER(C.c_void_p)),
+                ("workspace", C.c_void_p), ("grad", C.c_void_p), ("kernel_ms_host", C.POINTER(C.c_double))]
+
+
+class WaveglowWeightGradArgs(C.Structure):
+    _fields_ = [("B", C.c_int), ("M", C.c_int), ("nc", C.c_int), ("n_cond", C.c_int), ("L", C.c_int), ("taps", C.c_int), ("d", C.c_int),
+                ("a_rows", C.c_int), ("x_rows", C.c_int),
+                ("a", C.c_void_p), ("x", C.c_void_p), ("spect", C.c_void_p), ("dw_x", C.c_void_p), ("dw_spect", C.c_void_p), ("db", C.c_void_p),
+                ("workspace", C.c_void_p), ("db2", C.c_void_p)]
+
+
+class WaveglowStartBackwardArgs(C.Structure):
+    _fields_ = [("B", C.c_int), ("nc", C.c_int), ("c", C.c_int), ("n_half", C.c_int), ("L", C.c_int), ("dx", C.c_void_p), ("w_start", C.c_void_p),
+                ("audio_in", C.c_void_p), ("d_in", C.c_void_p), ("dw_start", C.c_void_p), ("db_start", C.c_void_p), ("workspace", C.c_void_p)]
+
+
+class WaveglowHeadBackwardArgs(C.Structure):
+    _fields_ = [("B", C.c_int), ("n_group", C.c_int), ("n_samples", C.c_long), ("d_in", C.c_void_p), ("audio", C.c_void_p), ("part", C.c_void_p),
+                ("dw", C.c_void_p)]
+
+
+class WaveglowGateBackwardArgs(C.Structure):
+    _fields_ = [("B", C.c_int), ("nc", C.c_int), ("L", C.c_int), ("last", C.c_int), ("dx", C.c_void_p), ("d_out", C.c_void_p), ("w_rs", C.c_void_p),
+                ("t", C.c_void_p), ("g", C.c_void_p), ("packed_ws", C.c_void_p), ("du", C.c_void_p), ("acts", C.c_void_p)]
+
+
+class WaveglowConvBackwardArgs(C.Structure):
+    _fields_ = [("B", C.c_int), ("nc", C.c_int), ("n_cond", C.c_int), ("L", C.c_int), ("d", C.c_int), ("first_dx", C.c_int), ("first_spect", C.c_int),
+                ("du", C.c_void_p), ("w_in", C.c_void_p), ("w_cond", C.c_void_p), ("packed_ws", C.c_void_p), ("dx", C.c_void_p), ("d_spect", C.c_void_p)]
+
+
+class WaveglowTailBackwardArgs(C.Structure):
+    _fields_ = [("B", C.c_int), ("nc", C.c_int), ("n_half", C.c_int), ("L", C.c_int), ("n_peel", C.c_int), ("n_group", C.c_int), ("z_offset", C.c_int),
+                ("out", C.c_void_p), ("w_end", C.c_void_p), ("b_end", C.c_void_p), ("audio_in", C.c_void_p), ("w_next", C.c_void_p), ("d_next", C.c_void_p),
+                ("dz", C.c_void_p), ("dlog_s", C.c_void_p), ("d_out", C.c_void_p), ("d_in", C.c_void_p), ("part", C.c_void_p), ("dw_end", C.c_void_p),
+                ("db_end", C.c_void_p), ("dw_next", C.c_void_p)]
+
+
+class WaveglowUpsampleBackwardArgs(C.Structure):
+    _fields_ = [("B", C.c_int), ("n_mel", C.c_int), ("T", C.c_int), ("n_group", C.c_int), ("n_samples", C.c_long),
+                ("mel", C.c_void_p), ("d_spect", C.c_void_p), ("dw", C.c_void_p), ("db", C.c_void_p)]
+
+
 WAVEGLOW_KERNELS = ("upsample", "start", "gated_conv", "res_skip", "couple")      # include/t2amd.h T2_WAVEGLOW_KERNELS
 WAVEGLOW_FORWARD_KERNELS = ("upsample", "start", "gated_conv", "res_skip", "head", "tail", "sums")      # T2_WAVEGLOW_FORWARD_KERNELS
+WAVEGLOW_BACKWARD_KERNELS = ("tail_backward", "gate_backward", "conv_backward", "cond_backward", "weight_grad", "weight_grad_reduce", "start_backward",
+                             "upsample_backward")      # T2_WAVEGLOW_BACKWARD_KERNELS
 WAVEGLOW_GATED, WAVEGLOW_RES_SKIP, WAVEGLOW_UPSAMPLE = 0, 1, 2                      # kinds of t2_waveglow_packed_floats
 
 # every symbol include/t2amd.h declares (tests/test_abi.py checks the library exports them all)
@@ -376,7 +432,10 @@ EXPORTS = ["t2_last_error", "t2_version", "t2_chain_status", "t2_chain_status_cl
            "t2_stft_plan", "t2_stft_pack", "t2_stft_analysis", "t2_stft_synthesis", "t2_melspec_plan", "t2_melspec_pack", "t2_melspec",
            "t2_waveglow_plan", "t2_waveglow_pack", "t2_waveglow_infer", "t2_waveglow_packed_floats", "t2_waveglow_gated_conv", "t2_waveglow_res_skip",
            "t2_waveglow_upsample", "t2_waveglow_couple", "t2_waveglow_forward_plan", "t2_waveglow_forward", "t2_waveglow_logdet",
-           "t2_waveglow_logdet_matrices", "t2_waveglow_head", "t2_waveglow_tail"]
+           "t2_waveglow_logdet_matrices", "t2_waveglow_head", "t2_waveglow_tail",
+           "t2_waveglow_backward_plan", "t2_waveglow_grad_offsets", "t2_waveglow_pack_backward", "t2_waveglow_train_forward", "t2_waveglow_backward",
+           "t2_waveglow_weight_grad_ws_floats", "t2_waveglow_weight_grad", "t2_waveglow_gate_backward", "t2_waveglow_conv_backward_packed_floats",
+           "t2_waveglow_conv_backward", "t2_waveglow_tail_backward", "t2_waveglow_upsample_backward", "t2_waveglow_start_backward", "t2_waveglow_head_backward"]
 
 _lib = None
 
@@ -464,6 +523,20 @@ def lib() -> C.CDLL:
         L.t2_waveglow_logdet_matrices.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
         L.t2_waveglow_head.argtypes = [C.POINTER(WaveglowHeadArgs), C.c_void_p]
         L.t2_waveglow_tail.argtypes = [C.POINTER(WaveglowTailArgs), C.c_void_p]
+        L.t2_waveglow_backward_plan.argtypes = [C.POINTER(WaveglowConfig), C.c_int, C.c_int, C.c_long, C.POINTER(WaveglowBackwardInfo)]
+        L.t2_waveglow_grad_offsets.argtypes = [C.POINTER(WaveglowConfig), C.POINTER(C.c_size_t), C.c_int]
+        L.t2_waveglow_pack_backward.argtypes = [C.POINTER(WaveglowConfig), C.POINTER(C.c_void_p), C.c_int, C.c_void_p, C.c_void_p]
+        L.t2_waveglow_train_forward.argtypes = [C.POINTER(WaveglowConfig), C.POINTER(WaveglowTrainForwardArgs), C.c_void_p]
+        L.t2_waveglow_backward.argtypes = [C.POINTER(WaveglowConfig), C.POINTER(WaveglowBackwardArgs), C.c_void_p]
+        L.t2_waveglow_weight_grad_ws_floats.argtypes, L.t2_waveglow_weight_grad_ws_floats.restype = [C.c_int] * 6, C.c_size_t
+        L.t2_waveglow_weight_grad.argtypes = [C.POINTER(WaveglowWeightGradArgs), C.c_void_p]
+        L.t2_waveglow_gate_backward.argtypes = [C.POINTER(WaveglowGateBackwardArgs), C.c_void_p]
+        L.t2_waveglow_conv_backward_packed_floats.argtypes, L.t2_waveglow_conv_backward_packed_floats.restype = [C.c_int, C.c_int], C.c_size_t
+        L.t2_waveglow_conv_backward.argtypes = [C.POINTER(WaveglowConvBackwardArgs), C.c_void_p]
+        L.t2_waveglow_tail_backward.argtypes = [C.POINTER(WaveglowTailBackwardArgs), C.c_void_p]
+        L.t2_waveglow_upsample_backward.argtypes = [C.POINTER(WaveglowUpsampleBackwardArgs), C.c_void_p]
+        L.t2_waveglow_start_backward.argtypes = [C.POINTER(WaveglowStartBackwardArgs), C.c_void_p]
+        L.t2_waveglow_head_backward.argtypes = [C.POINTER(WaveglowHeadBackwardArgs), C.c_void_p]
         _lib = L
     return _lib
 
@@ -898,3 +971,18 @@ def waveglow_forward_plan(cfg: WaveglowConfig, B: int, T: int, n_samples: int) -
     info = WaveglowForwardInfo()
     check(lib().t2_waveglow_forward_plan(C.byref(cfg), B, T, n_samples, C.byref(info)))
     return info
+
+
+def waveglow_backward_plan(cfg: WaveglowConfig, B: int, T: int, n_samples: int) -> WaveglowBackwardInfo:
+    """Buffer sizes of a training step (t2_waveglow_backward_plan: pure host, no device needed); raises with the library's message
+    for what t2_waveglow_forward_plan refuses."""
+    info = WaveglowBackwardInfo()
+    check(lib().t2_waveglow_backward_plan(C.byref(cfg), B, T, n_samples, C.byref(info)))
+    return info
+
+
+def waveglow_grad_offsets(cfg: WaveglowConfig, n_tensors: int):
+    """Offset in floats of every folded tensor's gradient inside the arena of t2_waveglow_backward, in t2_waveglow_pack's order."""
+    out = (C.c_size_t * n_tensors)()
+    check(lib().t2_waveglow_grad_offsets(C.byref(cfg), out, n_tensors))
+    return list(out)

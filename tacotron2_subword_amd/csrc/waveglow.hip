@@ -21,6 +21,13 @@
 //                samples; the forward direction, whose audio may reach into them, asks for up to three more columns q.
 // `start` (K <= 4) and the coupling (end: <= 8 rows reduced over nc with lanes along time, then (a1 - b)/exp(s), the c x c inverse
 // mix and the early-noise prepend in one pass) are plain VALU.  No atomics, every sum in a fixed order, 64-bit element offsets.
+//
+// Training (waveglow/train.py:125-137): the forward direction with the activations the backward reads kept in a caller-owned
+// buffer (per flow audio_in and out, per layer x_i, tanh(u_a), sigmoid(u_b): one more store in the gated epilogue, a separate
+// destination in res_skip's), and the backward.  Its data gradients are the same GEMM kernel on transposed packs with two more
+// epilogues (gate backward: W_rs^T [dx; d_out] times the gate's derivative from the kept halves; accumulate: dx += conv^T(du),
+// d_spect += W_cond^T du); its weight gradients are a second GEMM, wg_wgrad_kernel, whose reduction runs along time and is split
+// over (item, time chunk) into partial planes added in a fixed order; the tail, start, head and upsample backward are VALU.
 #include <algorithm>
 #include <vector>
 
@@ -34,7 +41,7 @@ constexpr int kWgMaxD = 128;                      // dilation of layer 7
 constexpr int kWgStride = 416;                    // slab row stride in floats: = 32 mod 64 banks, >= kVocTT + 2*kWgMaxD
 static_assert(kWgStride % 64 == 32 && kWgStride >= kVocTT + 2 * kWgMaxD, "slab row stride");
 static_assert(T2_WAVEGLOW_MAX_LAYERS == 8 && (1 << (T2_WAVEGLOW_MAX_LAYERS - 1)) == kWgMaxD, "the deepest layer's dilation fits the slab");
-enum { kWgGated = 0, kWgResSkip = 1, kWgUpsample = 2 };
+enum { kWgGated = 0, kWgResSkip = 1, kWgUpsample = 2, kWgGateBwd = 3, kWgAccum = 4 };   // the last two: epilogues of the backward (below)
 constexpr int kWgUpK = 1024, kWgUpStride = 256, kWgUpTaps = kWgUpK / kWgUpStride;
 
 // Y[row][q] = sum over segment 0 (C0 channels x taps, tap j at slab column q + coff0 + j*cstep) and segment 1 (C1 channels, one
@@ -47,6 +54,8 @@ struct WgGemm {
     int rows, mtiles, nch0, nch1;
     int first, last, raw, G; long Lg;             // res_skip: first, last; gated: raw; upsample: G, Lg = columns of spect
     int Nq;                                       // output columns: N, but for an upsample that keeps trailing samples (up to N + 3)
+    const float* res;                             // res_skip: the x that rs[:nc] is added to (y0 receives the sum; the same buffer unless x_i is kept)
+    float* s0; float* s1;                         // gated: nullable, receive tanh(u_a) and sigmoid(u_b) [B, nc, L]; gate backward: read as such
 };
 
 template <int WM, int MODE>
@@ -124,18 +133,31 @@ __global__ void __launch_bounds__(WM * 128) wg_gemm_kernel(WgGemm p) {
                     p.y0[((size_t)b * 2 * p.rows + r) * p.N + q] = ua;
                     p.y0[((size_t)b * 2 * p.rows + p.rows + r) * p.N + q] = ub;
                 } else {
-                    p.y0[((size_t)b * p.rows + r) * p.N + q] = tanhf(ua) * (1.f / (1.f + expf(-ub)));
+                    const float tv = tanhf(ua), gv = 1.f / (1.f + expf(-ub));
+                    const size_t o = ((size_t)b * p.rows + r) * p.N + q;
+                    if (p.s0) { p.s0[o] = tv; p.s1[o] = gv; }
+                    p.y0[o] = tv * gv;
                 }
             } else if constexpr (MODE == kWgResSkip) {
                 const float v = acc[0][n][e] + p.bias0[r];
                 const int nc = p.C0;
                 if (!p.last && r < nc) {
                     const size_t o = ((size_t)b * nc + r) * p.N + q;
-                    p.y0[o] = p.y0[o] + v;
+                    p.y0[o] = p.res[o] + v;
                 } else {
                     const size_t o = ((size_t)b * nc + (p.last ? r : r - nc)) * p.N + q;
                     p.y1[o] = p.first ? v : p.y1[o] + v;
                 }
+            } else if constexpr (MODE == kWgGateBwd) {
+                // d_acts = acc; du = [d_acts * g * (1 - t^2); d_acts * t * g * (1 - g)] [B, 2*rows, L], acts = t * g recomputed
+                const size_t o = ((size_t)b * p.rows + r) * p.N + q, o2 = ((size_t)b * 2 * p.rows + r) * p.N + q;
+                const float tv = p.s0[o], gv = p.s1[o], da = acc[0][n][e];
+                p.y0[o2] = da * gv * (1.f - tv * tv);
+                p.y0[o2 + (size_t)p.rows * p.N] = da * tv * gv * (1.f - gv);
+                p.y1[o] = tv * gv;
+            } else if constexpr (MODE == kWgAccum) {
+                const size_t o = ((size_t)b * p.rows + r) * p.N + q;
+                p.y0[o] = p.first ? acc[0][n][e] : p.y0[o] + acc[0][n][e];
             } else {
                 const int ch = r / kWgUpStride;
                 const long t = q * kWgUpStride + (r % kWgUpStride), l = t / p.G;
@@ -503,24 +525,24 @@ static int wg_gated_check(int B, int nc, int n_cond, long L, int d) {
 }
 
 static int wg_gated(int B, int nc, int n_cond, long L, int d, int raw, const float* x, const float* spect, const float* packed, const float* b_in,
-                    const float* b_cond, float* y, hipStream_t s) {
+                    const float* b_cond, float* y, hipStream_t s, float* keep_t = nullptr, float* keep_g = nullptr) {
     T2_TRY_RC(wg_gated_check(B, nc, n_cond, L, d));
     T2_REQUIRE(x && spect && packed && b_in && b_cond && y, "waveglow gated conv: null pointer");
     WgGemm p{};
     p.x0 = x; p.x1 = spect; p.wp = packed; p.bias0 = b_in; p.bias1 = b_cond; p.y0 = y;
     p.C0 = nc; p.C1 = n_cond; p.N = p.Nq = (int)L; p.taps = 3; p.coff0 = 0; p.cstep = d; p.halo = d;
-    p.rows = nc; p.mtiles = (nc + 31) / 32; p.nch0 = chunks(nc); p.nch1 = chunks(n_cond); p.raw = raw;
+    p.rows = nc; p.mtiles = (nc + 31) / 32; p.nch0 = chunks(nc); p.nch1 = chunks(n_cond); p.raw = raw; p.s0 = keep_t; p.s1 = keep_g;
     return wg_launch<kWgGated>(p, B, s);
 }
 
 static int wg_res_skip(int B, int nc, long L, int first, int last, const float* acts, const float* packed, const float* bias, float* x, float* out,
-                       hipStream_t s) {
+                       hipStream_t s, const float* x_from = nullptr) {
     const char* who = "waveglow res_skip";
     T2_TRY_RC(wg_check_common(who, B, L));
     T2_TRY_RC(wg_check_nc(who, nc));
     T2_REQUIRE(acts && packed && bias && out && (last || x), "%s: null pointer", who);
     WgGemm p{};
-    p.x0 = acts; p.wp = packed; p.bias0 = bias; p.y0 = x; p.y1 = out;
+    p.x0 = acts; p.wp = packed; p.bias0 = bias; p.y0 = x; p.y1 = out; p.res = x_from ? x_from : x;
     p.C0 = nc; p.N = p.Nq = (int)L; p.taps = 1;
     p.rows = last ? nc : 2 * nc; p.mtiles = (p.rows + 31) / 32; p.nch0 = chunks(nc); p.first = first; p.last = last;
     return wg_launch<kWgResSkip>(p, B, s);
@@ -837,7 +859,35 @@ static int wg_logdet_model(const t2_waveglow_config& c, const float* packed, flo
     return 0;
 }
 
-static int wg_forward(const t2_waveglow_config& c, const t2_waveglow_forward_args& a, hipStream_t s) {
+// What the training forward keeps for the backward, in floats from the start of `saved` (per = B * L rounded up to 4):
+// spect [B, n_mel*G, L] once; per flow the mixed audio_in [B, c_k, L] and out [B, nc, L]; per flow and layer x_i, tanh(u_a),
+// sigmoid(u_b), [B, nc, L] each.  The pre-mix audio of flow k > 0 is cat(a0, a1')[n_peel:] of flow k - 1, which the tail backward
+// recomputes anyway; flow 0's is the regrouped audio itself.
+struct WgSaved {
+    size_t per, nc, nl, n_cond;
+    std::vector<size_t> base, ch;
+    size_t total;
+    size_t ain(int k) const { return base[k]; }
+    size_t out(int k) const { return base[k] + per * ch[k]; }
+    size_t x(int k, int i) const { return out(k) + per * nc * (1 + 3 * (size_t)i); }
+    size_t t(int k, int i) const { return x(k, i) + per * nc; }
+    size_t g(int k, int i) const { return x(k, i) + 2 * per * nc; }
+};
+static WgSaved wg_saved(const t2_waveglow_config& c, const WgLayout& lay, int B, long L) {
+    WgSaved sv;
+    sv.per = round4((size_t)B * L); sv.nc = c.n_channels; sv.nl = c.n_layers; sv.n_cond = (size_t)c.n_mel_channels * c.n_group;
+    size_t off = sv.per * sv.n_cond;
+    for (const WgFlow& f : lay.flows) {
+        sv.base.push_back(off); sv.ch.push_back(f.c);
+        off += sv.per * ((size_t)f.c + sv.nc * (1 + 3 * sv.nl));
+    }
+    sv.total = off;
+    return sv;
+}
+
+// saved: null for analyze / nll; the training forward's buffer of wg_saved(..).total floats otherwise: the same launches in the
+// same order on the same packed weights, with the activations the backward reads left in `saved` instead of the workspace.
+static int wg_forward(const t2_waveglow_config& c, const t2_waveglow_forward_args& a, hipStream_t s, float* saved = nullptr) {
     WgLayout lay;
     t2_waveglow_forward_info pl;
     T2_TRY_RC(wg_forward_plan(c, a.B, a.T, a.n_samples, &pl, &lay));      // judges the configuration first
@@ -857,20 +907,29 @@ static int wg_forward(const t2_waveglow_config& c, const t2_waveglow_forward_arg
     double* item = part + pl.n_partials;
     double* sums = a.sums ? a.sums : item + B;
 
+    WgSaved sv;
+    if (saved) { sv = wg_saved(c, lay, B, L); spect = saved; }
+
     WgTimer tm{a.kernel_ms_host, T2_WAVEGLOW_FORWARD_KERNELS, s, "t2_waveglow_forward"};
     int rc = 0;
     {
         WG_RUN(0, wg_upsample(B, c.n_mel_channels, a.T, G, L * G, a.mel, a.packed + lay.up_w, a.packed + lay.up_b, spect, s));
+        if (saved) bufs[0] = saved + sv.ain(0);
         WG_RUN(4, wg_head(B, G, a.n_samples, a.audio, a.packed + lay.flows[0].winv, bufs[0], s));
         int cur = 0, zoff = 0;
         for (int k = 0; k < c.n_flows; ++k) {
             const WgFlow& f = lay.flows[k];
             const WgFlow* next = k + 1 < c.n_flows ? &lay.flows[k + 1] : nullptr;
+            if (saved) { x = saved + sv.x(k, 0); out = saved + sv.out(k); if (next) bufs[cur ^ 1] = saved + sv.ain(k + 1); }
             WG_RUN(1, wg_start(B, nc, f.c, f.n_half, L, 1.f, bufs[cur], a.packed + f.start_w, a.packed + f.start_b, x, s));
             for (int i = 0; i < c.n_layers; ++i) {
-                WG_RUN(2, wg_gated(B, nc, n_cond, L, 1 << i, 0, x, spect, a.packed + f.gated[i], a.packed + f.in_b[i],
-                                   a.packed + f.cond_b + (size_t)2 * nc * i, acts, s));
-                WG_RUN(3, wg_res_skip(B, nc, L, i == 0, i == c.n_layers - 1, acts, a.packed + f.rs[i], a.packed + f.rs_b[i], x, out, s));
+                const bool last = i == c.n_layers - 1;
+                float* xi = saved ? saved + sv.x(k, i) : x;                        // kept: layer i reads x_i and writes x_{i+1}
+                float* xn = saved && !last ? saved + sv.x(k, i + 1) : xi;
+                WG_RUN(2, wg_gated(B, nc, n_cond, L, 1 << i, 0, xi, spect, a.packed + f.gated[i], a.packed + f.in_b[i],
+                                   a.packed + f.cond_b + (size_t)2 * nc * i, acts, s, saved ? saved + sv.t(k, i) : nullptr,
+                                   saved ? saved + sv.g(k, i) : nullptr));
+                WG_RUN(3, wg_res_skip(B, nc, L, i == 0, last, acts, a.packed + f.rs[i], a.packed + f.rs_b[i], xn, out, s, xi));
             }
             WgTail p{out, a.packed + f.end_w, a.packed + f.end_b, bufs[cur], next ? a.packed + next->winv : nullptr,
                      next ? bufs[cur ^ 1] : nullptr, a.z, a.log_s_host ? a.log_s_host[k] : nullptr,
@@ -881,6 +940,652 @@ static int wg_forward(const t2_waveglow_config& c, const t2_waveglow_forward_arg
         }
         if (want_sums) WG_RUN(6, wg_nll_item(c.n_flows, B, nblk, L, G, a.sigma, part, part_z, a.logdet_w, sums, item, a.nll_item, s));
         if (a.logdet || a.loss) WG_RUN(6, wg_nll_loss(c.n_flows, B, L, item, a.logdet_w, a.logdet, a.loss, s));
+    }
+done:
+    return tm.finish(rc);
+}
+// ------------------------------------------------------------------------------------------------------------------
+// the backward of the forward direction: gradients of every folded tensor from dz and the dlog_s[k]
+// ------------------------------------------------------------------------------------------------------------------
+// Weight gradient  C[m][n] = sum_b sum_l A[b][m][l] * Bop[b][n][l + shift_n]: both operands are contiguous along the reduction, so
+// a workgroup stages 128 rows of each over 32 time steps in LDS (coalesced along time, guarded at both ends) and the MFMA reads
+// its 32 rows at one time step: lanes stride by the row stride, 34 floats, which puts rows 0..31 of both k-halves on 64 distinct
+// banks.  The columns n come in segments (x at three shifts, spect, a row of ones whose column is the bias gradient); a tile of
+// 128 columns lies inside one segment.  The reduction over (item, chunk of 32 steps) is split into `nsplit` contiguous runs that
+// depend on the shape alone; every run writes a partial plane, which wg_wgrad_reduce_kernel adds in ascending order in fp64.
+constexpr int kWgGradTile = 128, kWgGradTL = 32, kWgGradStride = 34, kWgGradMaxSeg = 5, kWgGradMaxSplit = 64;
+static_assert(kWgGradStride % 4 == 2 && kWgGradStride >= kWgGradTL, "rows 0..31 x 2 k-halves on 64 distinct banks");
+struct WgGradSeg { const float* src; int C, Cbuf, shift, tile0, col0, vec; }; // src null: ones; Cbuf: channels per item of the buffer; vec: 16-byte loads
+struct WgGradDst { float* dst; float* dst2; long rs, cs; };                 // element (m, ch) of a segment goes to dst[m*rs + ch*cs]
+struct WgGrad {
+    const float* a; float* part;
+    WgGradSeg seg[kWgGradMaxSeg]; WgGradDst dst[kWgGradMaxSeg];
+    int nseg, M, Mbuf, B, mtiles, ntiles, Ntot, nchunk, per, nsplit, avec; long L;
+};
+
+__global__ void __launch_bounds__(256) wg_wgrad_kernel(WgGrad p) {
+    __shared__ float As[kWgGradTile * kWgGradStride], Bs[kWgGradTile * kWgGradStride];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, wm = wave & 1, wn = wave >> 1, hk = lane >> 5;
+    const int mt = blockIdx.x % p.mtiles, nt = blockIdx.x / p.mtiles;
+    int si = 0;
+    for (int s = 1; s < p.nseg; ++s)
+        if (nt >= p.seg[s].tile0) si = s;
+    const WgGradSeg sg = p.seg[si];
+    const int ch0 = (nt - sg.tile0) * kWgGradTile, m0 = mt * kWgGradTile;
+    const int total = p.B * p.nchunk, u0 = blockIdx.y * p.per, u1 = min(total, u0 + p.per);
+    f32x16 acc[2][2];
+#pragma unroll
+    for (int i = 0; i < 2; ++i) { acc[i][0] = f32x16{0}; acc[i][1] = f32x16{0}; }
+    for (int u = u0; u < u1; ++u) {
+        const int b = u / p.nchunk;
+        const long l0 = (long)(u % p.nchunk) * kWgGradTL;
+        if (u > u0) __syncthreads();               // every wave is done reading the previous slabs
+        // 16-byte loads where L, the shift and the base address are multiples of four floats (a quad is then inside the row or
+        // outside it as a whole); element by element otherwise.  Both branches are uniform over the workgroup.
+        if (p.avec) {
+            for (int idx = threadIdx.x; idx < kWgGradTile * kWgGradTL / 4; idx += 256) {
+                const int row = idx / (kWgGradTL / 4), col = idx % (kWgGradTL / 4) * 4, m = m0 + row;
+                const long t = l0 + col;
+                f32x4 v = {0.f, 0.f, 0.f, 0.f};
+                if (m < p.M && t < p.L) v = *reinterpret_cast<const f32x4*>(p.a + ((size_t)b * p.Mbuf + m) * p.L + t);
+                float* d = As + row * kWgGradStride + col;
+                d[0] = v.x; d[1] = v.y; d[2] = v.z; d[3] = v.w;
+            }
+        } else {
+            for (int idx = threadIdx.x; idx < kWgGradTile * kWgGradTL; idx += 256) {
+                const int row = idx / kWgGradTL, col = idx % kWgGradTL, m = m0 + row;
+                const long t = l0 + col;
+                As[row * kWgGradStride + col] = (m < p.M && t < p.L) ? p.a[((size_t)b * p.Mbuf + m) * p.L + t] : 0.f;
+            }
+        }
+        if (sg.vec) {
+            for (int idx = threadIdx.x; idx < kWgGradTile * kWgGradTL / 4; idx += 256) {
+                const int row = idx / (kWgGradTL / 4), col = idx % (kWgGradTL / 4) * 4, ch = ch0 + row;
+                const long t = l0 + col, tb = t + sg.shift;
+                f32x4 v = {0.f, 0.f, 0.f, 0.f};
+                if (ch < sg.C && t < p.L && tb >= 0 && tb < p.L) {
+                    if (sg.src) v = *reinterpret_cast<const f32x4*>(sg.src + ((size_t)b * sg.Cbuf + ch) * p.L + tb);
+                    else v = f32x4{1.f, 1.f, 1.f, 1.f};
+                }
+                float* d = Bs + row * kWgGradStride + col;
+                d[0] = v.x; d[1] = v.y; d[2] = v.z; d[3] = v.w;
+            }
+        } else {
+            for (int idx = threadIdx.x; idx < kWgGradTile * kWgGradTL; idx += 256) {
+                const int row = idx / kWgGradTL, col = idx % kWgGradTL, ch = ch0 + row;
+                const long t = l0 + col, tb = t + sg.shift;
+                float v = 0.f;
+                if (ch < sg.C && t < p.L && tb >= 0 && tb < p.L) v = sg.src ? sg.src[((size_t)b * sg.Cbuf + ch) * p.L + tb] : 1.f;
+                Bs[row * kWgGradStride + col] = v;
+            }
+        }
+        __syncthreads();
+        const float* ap = As + (wm * 64 + (lane & 31)) * kWgGradStride + hk;
+        const float* bp = Bs + (wn * 64 + (lane & 31)) * kWgGradStride + hk;
+#pragma unroll
+        for (int kk = 0; kk < kWgGradTL / 2; ++kk) {
+            const float a0 = ap[2 * kk], a1 = ap[32 * kWgGradStride + 2 * kk], b0 = bp[2 * kk], b1 = bp[32 * kWgGradStride + 2 * kk];
+            acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b0, acc[0][0], 0, 0, 0);
+            acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b1, acc[0][1], 0, 0, 0);
+            acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b0, acc[1][0], 0, 0, 0);
+            acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b1, acc[1][1], 0, 0, 0);
+        }
+    }
+    // lane holds column (of C) lane & 31 and rows (e&3) + 8*(e>>2) + 4*hk of each 32x32 tile
+    float* pp = p.part + (size_t)blockIdx.y * p.M * p.Ntot;
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            const int ch = ch0 + wn * 64 + j * 32 + (lane & 31);
+            if (ch >= sg.C) continue;
+#pragma unroll
+            for (int e = 0; e < 16; ++e) {
+                const int m = m0 + wm * 64 + i * 32 + (e & 3) + 8 * (e >> 2) + 4 * hk;
+                if (m < p.M) pp[(size_t)m * p.Ntot + sg.col0 + ch] = acc[i][j][e];
+            }
+        }
+}
+
+__global__ void __launch_bounds__(256) wg_wgrad_reduce_kernel(WgGrad p) {
+    const size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x, plane = (size_t)p.M * p.Ntot;
+    if (idx >= plane) return;
+    const int m = (int)(idx / p.Ntot), n = (int)(idx % p.Ntot);
+    double acc = 0.0;
+    for (int y = 0; y < p.nsplit; ++y) acc += (double)p.part[(size_t)y * plane + idx];
+    int si = 0;
+    for (int s = 1; s < p.nseg; ++s)
+        if (n >= p.seg[s].col0) si = s;
+    const WgGradDst d = p.dst[si];
+    const size_t o = (size_t)m * d.rs + (size_t)(n - p.seg[si].col0) * d.cs;
+    d.dst[o] = (float)acc;
+    if (d.dst2) d.dst2[o] = (float)acc;
+}
+
+// sums of the products dn[r] * v[c] (r, c < Cn) over the wave, in fp64 from exact products, to part[r * Cn + c] (lane 0 writes)
+__device__ __forceinline__ void wg_mix_grad(const float (&dn)[8], const float (&vn)[8], int Cn, double* part) {
+#pragma unroll
+    for (int r = 0; r < 8; ++r)
+#pragma unroll
+        for (int c = 0; c < 8; ++c)
+            if (r < Cn && c < Cn) {
+                const double v = wg_wave_sum((double)dn[r] * (double)vn[c]);
+                if ((threadIdx.x & 63) == 0) part[r * Cn + c] = v;
+            }
+}
+
+struct WgTailBwd {
+    const float* out; const float* w_end; const float* b_end; const float* in;        // kept by the forward: out, audio_in of this flow
+    const float* wnext; const float* dnext;        // W_{k+1} [Cn][Cn] and d(audio_in_{k+1}) [B, Cn, L]; unused on the last flow
+    const float* dz; const float* dlog_s;          // nullable: upstream gradients on z [B, G, L] and on log_s[k] [B, n_half, L]
+    float* d_out; float* d_in;                     // [B, nc, L]; [B, C, L]: d(audio_in) but for W_start^T dx, which wg_start_bwd adds
+    double* part;                                  // [B * blocks * 4 waves][C*nc + C + Cn*Cn]: dW_end, db_end, dW_{k+1}
+    int nc, n_half, n_peel, G, zoff; long L;
+};
+// One flow's tail backwards, one thread per (item, column).  dV, the gradient on cat(a0, a1'), is dz for the channels that left
+// for z and W_{k+1}^T d(audio_in_{k+1}) for the rest; (b, s) = end(out) is recomputed as the forward computes it;
+// db = dV[n_half:], ds = db * exp(s) * a1 + dlog_s, da1 = db * exp(s), d_out = W_end^T [db; ds].  The sums over (item, column)
+// -- dW_end = [db; ds] out^T, db_end, dW_{k+1} = d(audio_in_{k+1}) v[n_peel:]^T -- leave as one fp64 partial per wave.
+__global__ void __launch_bounds__(256) wg_tail_bwd_kernel(WgTailBwd p) {
+    __shared__ float we[8 * 512], be[8], wi[64];
+    const int nh = p.n_half, C = 2 * nh, Cn = C - p.n_peel;
+    for (int i = threadIdx.x; i < C * p.nc; i += 256) we[i] = p.w_end[i];
+    if (threadIdx.x < C) be[threadIdx.x] = p.b_end[threadIdx.x];
+    if (threadIdx.x < Cn * Cn) wi[threadIdx.x] = p.wnext[threadIdx.x];
+    __syncthreads();
+    const long t = (long)blockIdx.x * 256 + threadIdx.x;
+    const bool valid = t < p.L;
+    const int b = blockIdx.y;
+    const float* ob = p.out + (size_t)b * p.nc * p.L + (valid ? t : 0);
+    float e[8], v[8], dn[8], dV[8];
+#pragma unroll
+    for (int r = 0; r < 8; ++r) { e[r] = 0.f; v[r] = 0.f; dn[r] = 0.f; dV[r] = 0.f; }
+    if (valid) {
+        float o[8];
+#pragma unroll
+        for (int r = 0; r < 8; ++r) o[r] = 0.f;
+        for (int c = 0; c < p.nc; ++c) {
+            const float x = ob[(size_t)c * p.L];
+#pragma unroll
+            for (int r = 0; r < 8; ++r)
+                if (r < C) o[r] = fmaf(we[r * p.nc + c], x, o[r]);
+        }
+#pragma unroll
+        for (int r = 0; r < 8; ++r)
+            if (r < Cn) dn[r] = p.dnext[((size_t)b * Cn + r) * p.L + t];
+#pragma unroll
+        for (int r = 0; r < 8; ++r) {
+            if (r < p.n_peel) {
+                dV[r] = p.dz ? p.dz[((size_t)b * p.G + p.zoff + r) * p.L + t] : 0.f;
+            } else if (r < C) {
+                float y = 0.f;
+#pragma unroll
+                for (int q = 0; q < 8; ++q)
+                    if (q < Cn) y = fmaf(wi[q * Cn + r - p.n_peel], dn[q], y);
+                dV[r] = y;
+            }
+        }
+        const float* ib = p.in + (size_t)b * C * p.L + t;
+#pragma unroll
+        for (int h = 0; h < 4; ++h) {
+            if (h < nh) {
+                const float a0 = ib[(size_t)h * p.L], a1 = ib[(size_t)(nh + h) * p.L];
+                float bb = 0.f, s = 0.f, db = 0.f, da0 = 0.f;
+#pragma unroll
+                for (int r = 0; r < 8; ++r) {       // o[h], dV[h] and o[nh + h], dV[nh + h] without a dynamic register index
+                    if (r == h) { bb = o[r] + be[r]; da0 = dV[r]; }
+                    if (r == nh + h) { s = o[r] + be[r]; db = dV[r]; }
+                }
+                const float es = expf(s), da1 = db * es;
+                const float ds = fmaf(da1, a1, p.dlog_s ? p.dlog_s[((size_t)b * nh + h) * p.L + t] : 0.f);
+                const float y1 = fmaf(es, a1, bb);
+                p.d_in[((size_t)b * C + h) * p.L + t] = da0;
+                p.d_in[((size_t)b * C + nh + h) * p.L + t] = da1;
+#pragma unroll
+                for (int r = 0; r < 8; ++r) {
+                    if (r == h) { v[r] = a0; e[r] = db; }
+                    if (r == nh + h) { v[r] = y1; e[r] = ds; }
+                }
+            }
+        }
+    }
+    const int lane = threadIdx.x & 63;
+    double* part = p.part + (((size_t)b * gridDim.x + blockIdx.x) * 4 + (threadIdx.x >> 6)) * ((size_t)C * p.nc + C + Cn * Cn);
+    for (int c = 0; c < p.nc; ++c) {
+        const float x = valid ? ob[(size_t)c * p.L] : 0.f;
+        float d = 0.f;
+#pragma unroll
+        for (int r = 0; r < 8; ++r)
+            if (r < C) d = fmaf(we[r * p.nc + c], e[r], d);
+        if (valid) p.d_out[((size_t)b * p.nc + c) * p.L + t] = d;
+#pragma unroll
+        for (int r = 0; r < 8; ++r)
+            if (r < C) {
+                const double w = wg_wave_sum((double)e[r] * (double)x);
+                if (lane == 0) part[(size_t)r * p.nc + c] = w;
+            }
+    }
+#pragma unroll
+    for (int r = 0; r < 8; ++r)
+        if (r < C) {
+            const double w = wg_wave_sum((double)e[r]);
+            if (lane == 0) part[(size_t)C * p.nc + r] = w;
+        }
+    float vn[8];
+#pragma unroll
+    for (int c = 0; c < 8; ++c) {
+        vn[c] = 0.f;
+#pragma unroll
+        for (int r = 0; r < 8; ++r)
+            if (r == p.n_peel + c) vn[c] = v[r];
+    }
+    wg_mix_grad(dn, vn, Cn, part + (size_t)C * p.nc + C);
+}
+
+// dW_0 [G][G] = sum d(audio_in_0)[b, r, l] * audio[b, l*G + g]: the partials of flow 0's mix, whose input is the regrouped audio
+__global__ void __launch_bounds__(256) wg_head_bwd_kernel(const float* __restrict__ d_in, const float* __restrict__ audio, int G, long N, long L,
+                                                         double* __restrict__ part) {
+    const long l = (long)blockIdx.x * 256 + threadIdx.x;
+    const int b = blockIdx.y;
+    float dn[8], vn[8];
+#pragma unroll
+    for (int g = 0; g < 8; ++g) {
+        const bool ok = l < L && g < G;
+        dn[g] = ok ? d_in[((size_t)b * G + g) * L + l] : 0.f;
+        vn[g] = ok ? audio[(size_t)b * N + (size_t)l * G + g] : 0.f;
+    }
+    wg_mix_grad(dn, vn, G, part + (((size_t)b * gridDim.x + blockIdx.x) * 4 + (threadIdx.x >> 6)) * ((size_t)G * G));
+}
+
+// dst_j[i] = sum over the slots (ascending, fp64) of part[slot][off_j + i], rounded to fp32 once: finishes the partials above
+struct WgFinish { const double* part; size_t nslots, stride; float* dst[3]; int n[3]; };
+__global__ void __launch_bounds__(256) wg_finish_kernel(WgFinish p) {
+    int idx = blockIdx.x * 256 + threadIdx.x;
+    const int at = idx;
+    int j = 0;
+    while (j < 3 && idx >= p.n[j]) { idx -= p.n[j]; ++j; }
+    if (j == 3) return;
+    double acc = 0.0;
+    for (size_t sl = 0; sl < p.nslots; ++sl) acc += p.part[sl * p.stride + at];
+    if (p.dst[j]) p.dst[j][idx] = (float)acc;
+}
+
+// d(audio_in)[b, h, t] += sum_c w_start[c][h] * dx[b, c, t] (c ascending), h < n_half: the rows of a0 that fed `start`
+__global__ void __launch_bounds__(256) wg_start_bwd_kernel(const float* __restrict__ dx, const float* __restrict__ w, float* __restrict__ d_in, int nc,
+                                                          int ctot, int n_half, long L) {
+    __shared__ float ws[512 * 4];
+    for (int i = threadIdx.x; i < nc * n_half; i += 256) ws[i] = w[i];
+    __syncthreads();
+    const long t = (long)blockIdx.x * 256 + threadIdx.x;
+    if (t >= L) return;
+    const int b = blockIdx.y;
+    float a[4] = {0.f, 0.f, 0.f, 0.f};
+    for (int c = 0; c < nc; ++c) {
+        const float d = dx[((size_t)b * nc + c) * L + t];
+#pragma unroll
+        for (int h = 0; h < 4; ++h)
+            if (h < n_half) a[h] = fmaf(ws[c * n_half + h], d, a[h]);
+    }
+#pragma unroll
+    for (int h = 0; h < 4; ++h)
+        if (h < n_half) d_in[((size_t)b * ctot + h) * L + t] += a[h];
+}
+
+// The upsample's weight gradient: dW_up[ci][co][r + 256 m] = sum_b sum_q mel[b, ci, q - m] * d_up[b, co, 256 q + r] with
+// d_up[b, co, s] = d_spect[b, co*G + s % G, s / G] for s < Lg*G (the frames q past T, whose taps reach back into the mel, included).
+// One thread per (ci, co, tap), b then q ascending, in fp64: K is only B * (T + 3).
+__global__ void __launch_bounds__(256) wg_up_bwd_kernel(const float* __restrict__ mel, const float* __restrict__ d_spect, float* __restrict__ dw, int B,
+                                                       int n_mel, int T, int G, long Lg, int Nq) {
+    const int j = blockIdx.x * 256 + threadIdx.x, co = blockIdx.y, ci = blockIdx.z;      // j < 1024: one workgroup row per m
+    const int r = j % kWgUpStride, m = j / kWgUpStride;
+    double acc = 0.0;
+    for (int b = 0; b < B; ++b) {
+        const float* mb = mel + ((size_t)b * n_mel + ci) * T;
+        const float* db = d_spect + (size_t)b * n_mel * G * Lg + (size_t)co * G * Lg;
+        for (int q = m; q < Nq && q - m < T; ++q) {
+            const long s = (long)q * kWgUpStride + r, l = s / G;
+            if (l < Lg) acc += (double)mb[q - m] * (double)db[(size_t)(s % G) * Lg + l];
+        }
+    }
+    dw[((size_t)ci * n_mel + co) * kWgUpK + j] = (float)acc;
+}
+// db_up[co] = sum over b, the G rows of co and l of d_spect: thread j takes elements j, j + 256, .. ascending, then a tree in LDS
+__global__ void __launch_bounds__(256) wg_up_bias_bwd_kernel(const float* __restrict__ d_spect, float* __restrict__ db, int B, int n_mel, int G, long Lg) {
+    __shared__ double red[256];
+    const int co = blockIdx.x;
+    const size_t row = (size_t)G * Lg;
+    double acc = 0.0;
+    for (int b = 0; b < B; ++b) {
+        const float* p = d_spect + ((size_t)b * n_mel + co) * row;
+        for (size_t i = threadIdx.x; i < row; i += 256) acc += (double)p[i];
+    }
+    red[threadIdx.x] = acc;
+    __syncthreads();
+    for (int w = 128; w >= 1; w >>= 1) {
+        if (threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) db[co] = (float)red[0];
+}
+
+// ---- host
+// packed[mtile][step][pg][lane][i] as wg_pack_kernel lays it out, from strided reads: segment 0 element (row, k, tap) is
+// w0[base0 + row*r0 + k*k0 + tap*j0], segment 1 element (row, k) is w1[row*r1 + k*k1]: the transposed operands of the data gradients
+struct WgPackT { const float* w0; const float* w1; float* out; int rows, K0, K1, taps, nch0, nch1; long base0, r0, k0, j0, r1, k1; size_t total; };
+__global__ void __launch_bounds__(256) wg_pack_t_kernel(WgPackT p) {
+    const size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= p.total) return;
+    const int nsteps = p.nch0 * p.taps + p.nch1;
+    const int i = idx & 3, lane = (idx >> 2) & 63, pg = (idx >> 8) & 1;
+    const size_t rest = idx >> 9;
+    const int step = rest % nsteps, mt = (int)(rest / nsteps);
+    const int r = mt * 32 + (lane & 31), kloc = 2 * (4 * pg + i) + (lane >> 5);
+    float v = 0.f;
+    if (r < p.rows) {
+        if (step < p.nch0 * p.taps) {
+            const int kk = (step / p.taps) * kWgCK + kloc, j = step % p.taps;
+            if (kk < p.K0) v = p.w0[p.base0 + (long)r * p.r0 + (long)kk * p.k0 + (long)j * p.j0];
+        } else {
+            const int kk = (step - p.nch0 * p.taps) * kWgCK + kloc;
+            if (kk < p.K1) v = p.w1[(long)r * p.r1 + (long)kk * p.k1];
+        }
+    }
+    p.out[idx] = v;
+}
+static size_t wg_packed_t_floats(int rows, int k0, int taps, int k1) { return (size_t)((rows + 31) / 32) * (chunks(k0) * taps + chunks(k1)) * 512; }
+static int wg_pack_t(WgPackT p, hipStream_t s) {
+    p.nch0 = chunks(p.K0); p.nch1 = p.K1 ? chunks(p.K1) : 0;
+    p.total = wg_packed_t_floats(p.rows, p.K0, p.taps, p.K1);
+    hipLaunchKernelGGL(wg_pack_t_kernel, dim3((unsigned)((p.total + 255) / 256)), dim3(256), 0, s, p);
+    T2_LAUNCH_CHECK();
+    return 0;
+}
+// conv^T: rows c < nc, k = r < 2nc, tap j' reads du at l + (j' - 1) d, which W_in[r][c][2 - j'] multiplies
+static int wg_pack_conv_t(const float* w_in, float* out, int nc, hipStream_t s) {
+    WgPackT p{}; p.w0 = w_in; p.out = out; p.rows = nc; p.K0 = 2 * nc; p.taps = 3; p.base0 = 2; p.r0 = 3; p.k0 = (long)nc * 3; p.j0 = -1;
+    return wg_pack_t(p, s);
+}
+static int wg_pack_cond_t(const float* w_cond_i, float* out, int nc, int n_cond, hipStream_t s) {      // [2nc][n_cond] -> rows n_cond, K = 2nc
+    WgPackT p{}; p.w0 = w_cond_i; p.out = out; p.rows = n_cond; p.K0 = 2 * nc; p.taps = 1; p.r0 = 1; p.k0 = n_cond;
+    return wg_pack_t(p, s);
+}
+static int wg_pack_rs_t(const float* w_rs, float* out, int nc, int last, hipStream_t s) {             // [2nc | nc][nc] -> rows nc, K = nc (x part) | nc (out part)
+    WgPackT p{}; p.w0 = w_rs; p.out = out; p.rows = nc; p.K0 = nc; p.taps = 1; p.r0 = 1; p.k0 = nc;
+    if (!last) { p.w1 = w_rs + (size_t)nc * nc; p.K1 = nc; p.r1 = 1; p.k1 = nc; }
+    return wg_pack_t(p, s);
+}
+
+struct WgBwdFlow { size_t conv_t[T2_WAVEGLOW_MAX_LAYERS], cond_t[T2_WAVEGLOW_MAX_LAYERS], rs_t[T2_WAVEGLOW_MAX_LAYERS]; };
+struct WgBwdLayout { std::vector<WgBwdFlow> flows; size_t total; std::vector<size_t> grad; size_t grad_total; };   // grad: offset per tensor, pack order
+static int wg_bwd_layout(const t2_waveglow_config& c, const WgLayout& lay, WgBwdLayout* out) {
+    const int nc = c.n_channels, n_cond = c.n_mel_channels * c.n_group, nl = c.n_layers;
+    WgBwdLayout L;
+    size_t off = 0, g = 0;
+    auto grad = [&](size_t n) { L.grad.push_back(g); g += n; };
+    grad((size_t)c.n_mel_channels * c.n_mel_channels * kWgUpK); grad(c.n_mel_channels);
+    for (const WgFlow& f : lay.flows) {
+        WgBwdFlow bf{};
+        for (int i = 0; i < nl; ++i) {
+            bf.conv_t[i] = off; off += wg_packed_t_floats(nc, 2 * nc, 3, 0);
+            bf.cond_t[i] = off; off += wg_packed_t_floats(n_cond, 2 * nc, 1, 0);
+            bf.rs_t[i] = off; off += wg_packed_t_floats(nc, nc, 1, i < nl - 1 ? nc : 0);
+        }
+        L.flows.push_back(bf);
+        grad((size_t)nc * f.n_half); grad(nc); grad((size_t)2 * nc * nl * n_cond); grad((size_t)2 * nc * nl);
+        for (int i = 0; i < nl; ++i) { grad((size_t)2 * nc * nc * 3); grad(2 * nc); }
+        for (int i = 0; i < nl; ++i) { const size_t rows = i < nl - 1 ? 2 * nc : nc; grad(rows * nc); grad(rows); }
+        grad((size_t)f.c * nc); grad(f.c); grad((size_t)f.c * f.c);
+    }
+    L.total = off; L.grad_total = g;
+    *out = L;
+    return 0;
+}
+
+// the shape of one weight-gradient launch: tiles, the columns' segments and the split of the reduction, from the sizes alone
+static void wg_grad_shape(WgGrad* p, int M, int nseg, const int* C, int B, long L) {
+    p->M = M; p->nseg = nseg; p->B = B; p->L = L;
+    p->mtiles = (M + kWgGradTile - 1) / kWgGradTile;
+    int tiles = 0, col = 0;
+    for (int s = 0; s < nseg; ++s) {
+        p->seg[s].C = C[s]; p->seg[s].tile0 = tiles; p->seg[s].col0 = col;
+        tiles += (C[s] + kWgGradTile - 1) / kWgGradTile; col += C[s];
+    }
+    p->ntiles = tiles; p->Ntot = col;
+    p->nchunk = (int)((L + kWgGradTL - 1) / kWgGradTL);
+    const long total = (long)B * p->nchunk;
+    // at most 1024 workgroups, what 256 CUs hold at once at 4 per CU (34 816 bytes of LDS, 88 registers): one more would wait a whole round
+    long nsplit = std::min<long>(std::min<long>(kWgGradMaxSplit, total), std::max<long>(1, 1024 / (p->mtiles * tiles)));
+    p->per = (int)((total + nsplit - 1) / nsplit);
+    p->nsplit = (int)((total + p->per - 1) / p->per);
+}
+static size_t wg_grad_part_floats(int M, int nseg, const int* C, int B, long L) {
+    WgGrad p{};
+    wg_grad_shape(&p, M, nseg, C, B, L);
+    return round4((size_t)p.nsplit * M * p.Ntot);
+}
+// src / Cbuf / shift / dst of every segment are the caller's; a, Mbuf, part too
+static int wg_grad_launch(WgGrad& p, hipStream_t s, WgTimer& tm) {
+    T2_REQUIRE(p.a && p.part && (long)p.B * p.nchunk <= INT32_MAX, "waveglow weight gradient: null pointer or too many chunks");
+    auto quads = [&](const float* q, int shift) { return p.L % 4 == 0 && shift % 4 == 0 && (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
+    p.avec = quads(p.a, 0);
+    for (int i = 0; i < p.nseg; ++i) p.seg[i].vec = quads(p.seg[i].src, p.seg[i].shift);
+    int rc = 0;
+    tm.mark();
+    hipLaunchKernelGGL(wg_wgrad_kernel, dim3((unsigned)(p.mtiles * p.ntiles), (unsigned)p.nsplit), dim3(256), 0, s, p);
+    rc = tm.timed(4, hipGetLastError() == hipSuccess ? 0 : -2);
+    if (rc) { t2_set_error("waveglow weight gradient: launch failed"); return rc; }
+    tm.mark();
+    hipLaunchKernelGGL(wg_wgrad_reduce_kernel, dim3((unsigned)(((size_t)p.M * p.Ntot + 255) / 256)), dim3(256), 0, s, p);
+    rc = tm.timed(5, hipGetLastError() == hipSuccess ? 0 : -2);
+    if (rc) t2_set_error("waveglow weight gradient: reduce launch failed");
+    return rc;
+}
+
+static int wg_gate_bwd(int B, int nc, long L, int last, const float* dx, const float* d_out, const float* packed_t, const float* t, const float* g, float* du,
+                       float* acts, hipStream_t s) {
+    const char* who = "waveglow gate backward";
+    T2_TRY_RC(wg_check_common(who, B, L));
+    T2_TRY_RC(wg_check_nc(who, nc));
+    T2_REQUIRE(d_out && (last || dx) && packed_t && t && g && du && acts, "%s: null pointer", who);
+    WgGemm p{};
+    p.x0 = last ? d_out : dx; p.x1 = last ? nullptr : d_out; p.wp = packed_t; p.y0 = du; p.y1 = acts;
+    p.s0 = const_cast<float*>(t); p.s1 = const_cast<float*>(g);
+    p.C0 = nc; p.C1 = last ? 0 : nc; p.N = p.Nq = (int)L; p.taps = 1;
+    p.rows = nc; p.mtiles = (nc + 31) / 32; p.nch0 = chunks(nc); p.nch1 = last ? 0 : chunks(nc);
+    return wg_launch<kWgGateBwd>(p, B, s);
+}
+// y [B, rows, L] (+)= W^T du: rows = nc with the flipped taps at distance d (dx), or rows = n_cond with one tap (d_spect)
+static int wg_data_bwd(int B, int rows, int nc, long L, int taps, int d, int first, const float* du, const float* packed_t, float* y, hipStream_t s) {
+    const char* who = "waveglow conv backward";
+    T2_TRY_RC(wg_check_common(who, B, L));
+    T2_TRY_RC(wg_check_nc(who, nc));
+    T2_REQUIRE(rows >= 1 && (taps == 1 || (taps == 3 && d >= 1 && d <= kWgMaxD && (d & (d - 1)) == 0)), "%s: rows=%d, taps=%d, d=%d", who, rows, taps, d);
+    T2_REQUIRE(du && packed_t && y, "%s: null pointer", who);
+    WgGemm p{};
+    p.x0 = du; p.wp = packed_t; p.y0 = y; p.first = first;
+    p.C0 = 2 * nc; p.N = p.Nq = (int)L; p.taps = taps; p.coff0 = 0; p.cstep = taps == 3 ? d : 0; p.halo = taps == 3 ? d : 0;
+    p.rows = rows; p.mtiles = (rows + 31) / 32; p.nch0 = chunks(2 * nc);
+    return wg_launch<kWgAccum>(p, B, s);
+}
+
+static int wg_tail_bwd(int B, const WgTailBwd& p, hipStream_t s) {
+    const char* who = "waveglow tail backward";
+    const int C = 2 * p.n_half;
+    T2_TRY_RC(wg_check_common(who, B, p.L));
+    T2_TRY_RC(wg_check_nc(who, p.nc));
+    T2_REQUIRE(p.n_half >= 1 && p.n_half <= 4, "%s: n_half=%d outside 1..4", who, p.n_half);
+    T2_REQUIRE(p.n_peel >= 0 && p.n_peel <= C && p.n_peel != C - 1, "%s: %d of %d channels peeled leave no whole flow", who, p.n_peel, C);
+    T2_REQUIRE(p.zoff >= 0 && p.zoff + p.n_peel <= p.G && p.G <= 8, "%s: channels %d..%d of z lie outside its %d", who, p.zoff, p.zoff + p.n_peel, p.G);
+    T2_REQUIRE(p.out && p.w_end && p.b_end && p.in && p.d_out && p.d_in && p.part && (p.n_peel == C || (p.wnext && p.dnext)), "%s: null pointer", who);
+    hipLaunchKernelGGL(wg_tail_bwd_kernel, dim3((unsigned)((p.L + 255) / 256), (unsigned)B), dim3(256), 0, s, p);
+    T2_LAUNCH_CHECK();
+    return 0;
+}
+static int wg_finish(const double* part, size_t nslots, size_t stride, float* d0, int n0, float* d1, int n1, float* d2, int n2, hipStream_t s) {
+    WgFinish p{part, nslots, stride, {d0, d1, d2}, {n0, n1, n2}};
+    if (n0 + n1 + n2 == 0) return 0;
+    hipLaunchKernelGGL(wg_finish_kernel, dim3((unsigned)((n0 + n1 + n2 + 255) / 256)), dim3(256), 0, s, p);
+    T2_LAUNCH_CHECK();
+    return 0;
+}
+static int wg_head_bwd(int B, int G, long N, const float* d_in, const float* audio, double* part, float* dw, hipStream_t s) {
+    const long L = N / G;
+    const unsigned nblk = (unsigned)((L + 255) / 256);
+    hipLaunchKernelGGL(wg_head_bwd_kernel, dim3(nblk, (unsigned)B), dim3(256), 0, s, d_in, audio, G, N, L, part);
+    T2_LAUNCH_CHECK();
+    return wg_finish(part, (size_t)B * nblk * 4, (size_t)G * G, dw, G * G, nullptr, 0, nullptr, 0, s);
+}
+static int wg_start_bwd(int B, int nc, int ctot, int n_half, long L, const float* dx, const float* w, float* d_in, hipStream_t s) {
+    hipLaunchKernelGGL(wg_start_bwd_kernel, dim3((unsigned)((L + 255) / 256), (unsigned)B), dim3(256), 0, s, dx, w, d_in, nc, ctot, n_half, L);
+    T2_LAUNCH_CHECK();
+    return 0;
+}
+static int wg_up_bwd(int B, int n_mel, int T, int G, long n_samples, const float* mel, const float* d_spect, float* dw, float* db, hipStream_t s) {
+    const char* who = "waveglow upsample backward";
+    T2_TRY_RC(wg_check_common(who, B, T));
+    T2_REQUIRE(n_mel >= 1 && n_mel <= 512, "%s: n_mel_channels=%d outside 1..512", who, n_mel);
+    T2_REQUIRE(G >= 2 && G <= 8 && G % 2 == 0, "%s: n_group=%d is not even and from 2 to 8", who, G);
+    T2_REQUIRE(n_samples / G >= 1 && n_samples <= (long)T * kWgUpStride + kWgUpK - kWgUpStride, "%s: %ld samples, %d frames", who, n_samples, T);
+    T2_REQUIRE(mel && d_spect && dw && db, "%s: null pointer", who);
+    const long Lg = n_samples / G;
+    const int Nq = (int)std::max((long)T, (Lg * G + kWgUpStride - 1) / kWgUpStride);
+    hipLaunchKernelGGL(wg_up_bwd_kernel, dim3(kWgUpK / 256, (unsigned)n_mel, (unsigned)n_mel), dim3(256), 0, s, mel, d_spect, dw, B, n_mel, T, G, Lg, Nq);
+    T2_LAUNCH_CHECK();
+    hipLaunchKernelGGL(wg_up_bias_bwd_kernel, dim3((unsigned)n_mel), dim3(256), 0, s, d_spect, db, B, n_mel, G, Lg);
+    T2_LAUNCH_CHECK();
+    return 0;
+}
+
+static int wg_backward_plan(const t2_waveglow_config& c, int B, int T, long N, t2_waveglow_backward_info* out, WgLayout* lay_out, WgBwdLayout* bl_out) {
+    WgLayout lay;
+    t2_waveglow_forward_info fp;
+    T2_TRY_RC(wg_forward_plan(c, B, T, N, &fp, &lay));
+    WgBwdLayout bl;
+    T2_TRY_RC(wg_bwd_layout(c, lay, &bl));
+    if (out) {
+        const int nc = c.n_channels, G = c.n_group, n_cond = c.n_mel_channels * G;
+        const size_t per = round4((size_t)B * fp.L);
+        const int c_du[5] = {nc, nc, nc, n_cond, 1}, c_rs[2] = {nc, 1}, c_st[2] = {G / 2, 1};
+        const size_t part = std::max(wg_grad_part_floats(2 * nc, 5, c_du, B, fp.L), std::max(wg_grad_part_floats(nc, 2, c_rs, B, fp.L),
+                                                                                            wg_grad_part_floats(nc, 2, c_st, B, fp.L)));
+        out->L = fp.L; out->n_tensors = lay.n_tensors;
+        out->saved_bytes = wg_saved(c, lay, B, fp.L).total * sizeof(float);
+        out->grad_floats = bl.grad_total;
+        out->packed_bwd_bytes = bl.total * sizeof(float);
+        out->n_slots = (size_t)B * fp.n_blocks * 4;
+        out->workspace_bytes = (per * ((size_t)5 * nc + n_cond + 2 * G) + part) * sizeof(float) + out->n_slots * ((size_t)G * nc + G + G * G) * sizeof(double);
+    }
+    if (lay_out) *lay_out = lay;
+    if (bl_out) *bl_out = bl;
+    return 0;
+}
+
+static int wg_pack_backward(const t2_waveglow_config& c, const float* const* t, int n, float* packed, hipStream_t s) {
+    WgLayout lay;
+    WgBwdLayout bl;
+    T2_TRY_RC(wg_layout(c, &lay));
+    T2_TRY_RC(wg_bwd_layout(c, lay, &bl));
+    T2_REQUIRE(t && packed, "t2_waveglow_pack_backward: null pointer");
+    T2_REQUIRE(n == lay.n_tensors, "t2_waveglow_pack_backward: %d tensors given, the configuration has %d", n, lay.n_tensors);
+    for (int i = 0; i < n; ++i) T2_REQUIRE(t[i], "t2_waveglow_pack_backward: tensor %d is null", i);
+    const int nc = c.n_channels, n_cond = c.n_mel_channels * c.n_group, nl = c.n_layers;
+    int at = 2;
+    for (int k = 0; k < c.n_flows; ++k, at += 7 + 4 * nl) {
+        const float* cond_w = t[at + 2];
+        for (int i = 0; i < nl; ++i) {
+            T2_TRY_RC(wg_pack_conv_t(t[at + 4 + 2 * i], packed + bl.flows[k].conv_t[i], nc, s));
+            T2_TRY_RC(wg_pack_cond_t(cond_w + (size_t)2 * nc * i * n_cond, packed + bl.flows[k].cond_t[i], nc, n_cond, s));
+            T2_TRY_RC(wg_pack_rs_t(t[at + 4 + 2 * nl + 2 * i], packed + bl.flows[k].rs_t[i], nc, i == nl - 1, s));
+        }
+    }
+    return 0;
+}
+
+static int wg_backward(const t2_waveglow_config& c, const t2_waveglow_backward_args& a, hipStream_t s) {
+    WgLayout lay;
+    WgBwdLayout bl;
+    t2_waveglow_backward_info pl;
+    T2_TRY_RC(wg_backward_plan(c, a.B, a.T, a.n_samples, &pl, &lay, &bl));
+    T2_REQUIRE(a.n_mel == c.n_mel_channels, "t2_waveglow_backward: the mel has %d channels, the model takes %d", a.n_mel, c.n_mel_channels);
+    T2_REQUIRE(a.packed && a.packed_bwd && a.saved && a.mel && a.audio && a.workspace && a.grad, "t2_waveglow_backward: null pointer");
+    const int B = a.B, nc = c.n_channels, G = c.n_group, n_cond = c.n_mel_channels * G, nl = c.n_layers, nf = c.n_flows;
+    const long L = pl.L;
+    const WgSaved sv = wg_saved(c, lay, B, L);
+    const size_t per = sv.per;
+    float* dx = a.workspace; float* d_out = dx + per * nc; float* du = d_out + per * nc; float* acts = du + per * 2 * nc;
+    float* d_spect = acts + per * nc;
+    float* dbuf[2] = {d_spect + per * n_cond, d_spect + per * n_cond + per * G};
+    float* gpart = dbuf[1] + per * G;
+    double* tpart = reinterpret_cast<double*>(a.workspace + (pl.workspace_bytes - pl.n_slots * ((size_t)G * nc + G + G * G) * sizeof(double)) / sizeof(float));
+    const float* spect = a.saved;
+    std::vector<int> zoff(nf, 0);
+    for (int k = 0, z = 0; k < nf; ++k) { zoff[k] = z; z += k + 1 < nf ? lay.flows[k].c - lay.flows[k + 1].c : lay.flows[k].c; }
+
+    WgTimer tm{a.kernel_ms_host, T2_WAVEGLOW_BACKWARD_KERNELS, s, "t2_waveglow_backward"};
+    int rc = 0;
+    {
+        for (int k = nf - 1; k >= 0; --k) {
+            const WgFlow& f = lay.flows[k];
+            const WgBwdFlow& bf = bl.flows[k];
+            const WgFlow* next = k + 1 < nf ? &lay.flows[k + 1] : nullptr;
+            const int t0 = 2 + k * (7 + 4 * nl), Cn = next ? next->c : 0;      // this flow's first tensor in pack order
+            float* g_end = a.grad + bl.grad[t0 + 4 + 4 * nl];
+            float* d_in = dbuf[k & 1];
+            WgTailBwd tp{a.saved + sv.out(k), a.packed + f.end_w, a.packed + f.end_b, a.saved + sv.ain(k), next ? a.packed + next->winv : nullptr,
+                         next ? dbuf[(k + 1) & 1] : nullptr, a.dz, a.dlog_s_host ? a.dlog_s_host[k] : nullptr, d_out, d_in, tpart,
+                         nc, f.n_half, next ? f.c - next->c : f.c, G, zoff[k], L};
+            WG_RUN(0, wg_tail_bwd(B, tp, s));
+            WG_RUN(0, wg_finish(tpart, pl.n_slots, (size_t)f.c * nc + f.c + Cn * Cn, g_end, f.c * nc, a.grad + bl.grad[t0 + 5 + 4 * nl], f.c,
+                                next ? a.grad + bl.grad[t0 + 7 + 4 * nl + 6 + 4 * nl] : nullptr, Cn * Cn, s));
+            for (int i = nl - 1; i >= 0; --i) {
+                const bool last = i == nl - 1;
+                WG_RUN(1, wg_gate_bwd(B, nc, L, last, dx, d_out, a.packed_bwd + bf.rs_t[i], a.saved + sv.t(k, i), a.saved + sv.g(k, i), du, acts, s));
+                float* g_rs = a.grad + bl.grad[t0 + 4 + 2 * nl + 2 * i];
+                float* g_rsb = a.grad + bl.grad[t0 + 5 + 2 * nl + 2 * i];
+                const int c_rs[2] = {nc, 1};
+                for (int half = last ? 1 : 0; half < 2; ++half) {        // rows [:nc] of res_skip take dx, rows [nc:] (all, on the last layer) d_out
+                    WgGrad gp{};
+                    wg_grad_shape(&gp, nc, 2, c_rs, B, L);
+                    const size_t row0 = half && !last ? nc : 0;
+                    gp.a = half ? d_out : dx; gp.Mbuf = nc; gp.part = gpart;
+                    gp.seg[0].src = acts; gp.seg[0].Cbuf = nc; gp.dst[0] = WgGradDst{g_rs + row0 * nc, nullptr, nc, 1};
+                    gp.dst[1] = WgGradDst{g_rsb + row0, nullptr, 1, 0};
+                    rc = wg_grad_launch(gp, s, tm);
+                    if (rc != 0) goto done;
+                }
+                {
+                    const int c_du[5] = {nc, nc, nc, n_cond, 1};
+                    WgGrad gp{};
+                    wg_grad_shape(&gp, 2 * nc, 5, c_du, B, L);
+                    gp.a = du; gp.Mbuf = 2 * nc; gp.part = gpart;
+                    float* g_in = a.grad + bl.grad[t0 + 4 + 2 * i];
+                    for (int j = 0; j < 3; ++j) {
+                        gp.seg[j].src = a.saved + sv.x(k, i); gp.seg[j].Cbuf = nc; gp.seg[j].shift = (j - 1) * (1 << i);
+                        gp.dst[j] = WgGradDst{g_in + j, nullptr, (long)nc * 3, 3};
+                    }
+                    gp.seg[3].src = spect; gp.seg[3].Cbuf = n_cond;
+                    gp.dst[3] = WgGradDst{a.grad + bl.grad[t0 + 2] + (size_t)2 * nc * i * n_cond, nullptr, n_cond, 1};
+                    gp.dst[4] = WgGradDst{a.grad + bl.grad[t0 + 5 + 2 * i], a.grad + bl.grad[t0 + 3] + (size_t)2 * nc * i, 1, 0};
+                    rc = wg_grad_launch(gp, s, tm);
+                    if (rc != 0) goto done;
+                }
+                WG_RUN(2, wg_data_bwd(B, nc, nc, L, 3, 1 << i, last, du, a.packed_bwd + bf.conv_t[i], dx, s));
+                WG_RUN(3, wg_data_bwd(B, n_cond, nc, L, 1, 0, k == nf - 1 && last, du, a.packed_bwd + bf.cond_t[i], d_spect, s));
+            }
+            WG_RUN(6, wg_start_bwd(B, nc, f.c, f.n_half, L, dx, a.packed + f.start_w, d_in, s));
+            {
+                const int c_st[2] = {f.n_half, 1};
+                WgGrad gp{};
+                wg_grad_shape(&gp, nc, 2, c_st, B, L);
+                gp.a = dx; gp.Mbuf = nc; gp.part = gpart;
+                gp.seg[0].src = a.saved + sv.ain(k); gp.seg[0].Cbuf = f.c; gp.dst[0] = WgGradDst{a.grad + bl.grad[t0], nullptr, f.n_half, 1};
+                gp.dst[1] = WgGradDst{a.grad + bl.grad[t0 + 1], nullptr, 1, 0};
+                rc = wg_grad_launch(gp, s, tm);
+                if (rc != 0) goto done;
+            }
+        }
+        WG_RUN(0, wg_head_bwd(B, G, a.n_samples, dbuf[0], a.audio, tpart, a.grad + bl.grad[2 + 6 + 4 * nl], s));
+        WG_RUN(7, wg_up_bwd(B, c.n_mel_channels, a.T, G, L * G, a.mel, d_spect, a.grad + bl.grad[0], a.grad + bl.grad[1], s));
     }
 done:
     return tm.finish(rc);
@@ -960,6 +1665,127 @@ int t2_waveglow_tail(const t2_waveglow_tail_args* a, void* stream) {
     T2_REQUIRE(!a->part_s == !a->part_z, "t2_waveglow_tail: part_s and part_z go together");
     return wg_tail(a->B, WgTail{a->out, a->w_end, a->b_end, a->audio_in, a->w_next, a->audio_out, a->z, a->log_s, a->part_s, a->part_z, a->nc, a->n_half,
                                 a->n_peel, a->n_group, a->z_offset, (long)a->L}, (hipStream_t)stream);
+}
+
+int t2_waveglow_backward_plan(const t2_waveglow_config* cfg, int B, int T, long n_samples, t2_waveglow_backward_info* out) {
+    T2_REQUIRE(cfg && out, "t2_waveglow_backward_plan: null pointer");
+    return wg_backward_plan(*cfg, B, T, n_samples, out, nullptr, nullptr);
+}
+int t2_waveglow_grad_offsets(const t2_waveglow_config* cfg, size_t* offsets_host, int n_tensors) {
+    T2_REQUIRE(cfg && offsets_host, "t2_waveglow_grad_offsets: null pointer");
+    WgLayout lay;
+    WgBwdLayout bl;
+    T2_TRY_RC(wg_layout(*cfg, &lay));
+    T2_TRY_RC(wg_bwd_layout(*cfg, lay, &bl));
+    T2_REQUIRE(n_tensors == lay.n_tensors, "t2_waveglow_grad_offsets: room for %d tensors, the configuration has %d", n_tensors, lay.n_tensors);
+    for (int i = 0; i < n_tensors; ++i) offsets_host[i] = bl.grad[i];
+    return 0;
+}
+int t2_waveglow_pack_backward(const t2_waveglow_config* cfg, const float* const* tensors_host, int n_tensors, float* packed_bwd, void* stream) {
+    T2_REQUIRE(cfg, "t2_waveglow_pack_backward: null configuration");
+    return wg_pack_backward(*cfg, tensors_host, n_tensors, packed_bwd, (hipStream_t)stream);
+}
+int t2_waveglow_train_forward(const t2_waveglow_config* cfg, const t2_waveglow_train_forward_args* a, void* stream) {
+    T2_REQUIRE(cfg && a && a->saved, "t2_waveglow_train_forward: null pointer");
+    return wg_forward(*cfg, a->fwd, (hipStream_t)stream, a->saved);
+}
+int t2_waveglow_backward(const t2_waveglow_config* cfg, const t2_waveglow_backward_args* a, void* stream) {
+    T2_REQUIRE(cfg && a, "t2_waveglow_backward: null pointer");
+    return wg_backward(*cfg, *a, (hipStream_t)stream);
+}
+size_t t2_waveglow_weight_grad_ws_floats(int M, int nc, int n_cond, int taps, int B, int L) {
+    if (M < 1 || nc < 1 || n_cond < 0 || (taps != 1 && taps != 3) || B < 1 || L < 1) return 0;
+    int C[5], n = 0;
+    for (int j = 0; j < taps; ++j) C[n++] = nc;
+    if (n_cond) C[n++] = n_cond;
+    C[n++] = 1;
+    return wg_grad_part_floats(M, n, C, B, L);
+}
+int t2_waveglow_weight_grad(const t2_waveglow_weight_grad_args* a, void* stream) {
+    const char* who = "waveglow weight gradient";
+    T2_REQUIRE(a, "t2_waveglow_weight_grad: null arguments");
+    T2_TRY_RC(wg_check_common(who, a->B, a->L));
+    T2_REQUIRE(a->M >= 1 && a->M <= 1024 && a->nc >= 1 && a->nc <= 512 && a->n_cond >= 0, "%s: M=%d, nc=%d, n_cond=%d", who, a->M, a->nc, a->n_cond);
+    T2_REQUIRE((a->taps == 1 && a->d == 0) || (a->taps == 3 && a->d >= 1 && a->d <= kWgMaxD), "%s: taps=%d, d=%d", who, a->taps, a->d);
+    T2_REQUIRE(a->a && a->x && a->dw_x && a->db && a->workspace && (a->n_cond == 0 || (a->spect && a->dw_spect)), "%s: null pointer", who);
+    int C[5], n = 0;
+    for (int j = 0; j < a->taps; ++j) C[n++] = a->nc;
+    if (a->n_cond) C[n++] = a->n_cond;
+    C[n++] = 1;
+    WgGrad gp{};
+    wg_grad_shape(&gp, a->M, n, C, a->B, a->L);
+    T2_REQUIRE((a->a_rows == 0 || a->a_rows >= a->M) && (a->x_rows == 0 || a->x_rows >= a->nc), "%s: a_rows=%d, x_rows=%d are fewer than M=%d, nc=%d", who,
+               a->a_rows, a->x_rows, a->M, a->nc);
+    gp.a = a->a; gp.Mbuf = a->a_rows ? a->a_rows : a->M; gp.part = a->workspace;
+    for (int j = 0; j < a->taps; ++j) {
+        gp.seg[j].src = a->x; gp.seg[j].Cbuf = a->x_rows ? a->x_rows : a->nc; gp.seg[j].shift = (j - a->taps / 2) * a->d;
+        gp.dst[j] = WgGradDst{a->dw_x + j, nullptr, (long)a->nc * a->taps, a->taps};
+    }
+    if (a->n_cond) { gp.seg[a->taps].src = a->spect; gp.seg[a->taps].Cbuf = a->n_cond; gp.dst[a->taps] = WgGradDst{a->dw_spect, nullptr, a->n_cond, 1}; }
+    gp.dst[n - 1] = WgGradDst{a->db, a->db2, 1, 0};
+    WgTimer tm{nullptr, 0, (hipStream_t)stream, who};
+    return wg_grad_launch(gp, (hipStream_t)stream, tm);
+}
+int t2_waveglow_gate_backward(const t2_waveglow_gate_backward_args* a, void* stream) {
+    T2_REQUIRE(a, "t2_waveglow_gate_backward: null arguments");
+    T2_TRY_RC(wg_check_nc("waveglow gate backward", a->nc));
+    T2_REQUIRE(a->w_rs && a->packed_ws, "t2_waveglow_gate_backward: null weights or packing scratch");
+    T2_TRY_RC(wg_pack_rs_t(a->w_rs, a->packed_ws, a->nc, a->last, (hipStream_t)stream));
+    return wg_gate_bwd(a->B, a->nc, a->L, a->last, a->dx, a->d_out, a->packed_ws, a->t, a->g, a->du, a->acts, (hipStream_t)stream);
+}
+int t2_waveglow_conv_backward(const t2_waveglow_conv_backward_args* a, void* stream) {
+    T2_REQUIRE(a, "t2_waveglow_conv_backward: null arguments");
+    T2_TRY_RC(wg_check_nc("waveglow conv backward", a->nc));
+    T2_REQUIRE(a->n_cond >= 8 && a->n_cond % 8 == 0, "waveglow conv backward: %d conditioning channels, must be a positive multiple of 8", a->n_cond);
+    T2_REQUIRE(a->w_in && a->w_cond && a->packed_ws, "t2_waveglow_conv_backward: null weights or packing scratch");
+    float* pc = a->packed_ws + wg_packed_t_floats(a->nc, 2 * a->nc, 3, 0);
+    T2_TRY_RC(wg_pack_conv_t(a->w_in, a->packed_ws, a->nc, (hipStream_t)stream));
+    T2_TRY_RC(wg_pack_cond_t(a->w_cond, pc, a->nc, a->n_cond, (hipStream_t)stream));
+    T2_TRY_RC(wg_data_bwd(a->B, a->nc, a->nc, a->L, 3, a->d, a->first_dx, a->du, a->packed_ws, a->dx, (hipStream_t)stream));
+    return wg_data_bwd(a->B, a->n_cond, a->nc, a->L, 1, 0, a->first_spect, a->du, pc, a->d_spect, (hipStream_t)stream);
+}
+size_t t2_waveglow_conv_backward_packed_floats(int nc, int n_cond) {
+    return nc > 0 && n_cond > 0 ? wg_packed_t_floats(nc, 2 * nc, 3, 0) + wg_packed_t_floats(n_cond, 2 * nc, 1, 0) : 0;
+}
+int t2_waveglow_tail_backward(const t2_waveglow_tail_backward_args* a, void* stream) {
+    T2_REQUIRE(a, "t2_waveglow_tail_backward: null arguments");
+    T2_REQUIRE(a->dw_end && a->db_end, "t2_waveglow_tail_backward: null pointer");
+    const int C = 2 * a->n_half, Cn = C - a->n_peel;
+    T2_TRY_RC(wg_tail_bwd(a->B, WgTailBwd{a->out, a->w_end, a->b_end, a->audio_in, a->w_next, a->d_next, a->dz, a->dlog_s, a->d_out, a->d_in, a->part, a->nc,
+                                         a->n_half, a->n_peel, a->n_group, a->z_offset, (long)a->L}, (hipStream_t)stream));
+    T2_REQUIRE(Cn == 0 || a->dw_next, "t2_waveglow_tail_backward: dw_next is null");
+    return wg_finish(a->part, (size_t)a->B * ((a->L + 255) / 256) * 4, (size_t)C * a->nc + C + Cn * Cn, a->dw_end, C * a->nc, a->db_end, C, a->dw_next, Cn * Cn,
+                     (hipStream_t)stream);
+}
+int t2_waveglow_start_backward(const t2_waveglow_start_backward_args* a, void* stream) {
+    const char* who = "waveglow start backward";
+    T2_REQUIRE(a, "t2_waveglow_start_backward: null arguments");
+    T2_TRY_RC(wg_check_common(who, a->B, a->L));
+    T2_TRY_RC(wg_check_nc(who, a->nc));
+    T2_REQUIRE(a->n_half >= 1 && a->n_half <= 4 && a->c >= 2 * a->n_half && a->c <= 8, "%s: n_half=%d outside 1..4 or c=%d outside 2*n_half..8", who, a->n_half, a->c);
+    T2_REQUIRE(a->dx && a->w_start && a->audio_in && a->d_in && a->dw_start && a->db_start && a->workspace, "%s: null pointer", who);
+    T2_TRY_RC(wg_start_bwd(a->B, a->nc, a->c, a->n_half, a->L, a->dx, a->w_start, a->d_in, (hipStream_t)stream));
+    const int c_st[2] = {a->n_half, 1};
+    WgGrad gp{};
+    wg_grad_shape(&gp, a->nc, 2, c_st, a->B, a->L);
+    gp.a = a->dx; gp.Mbuf = a->nc; gp.part = a->workspace;
+    gp.seg[0].src = a->audio_in; gp.seg[0].Cbuf = a->c; gp.dst[0] = WgGradDst{a->dw_start, nullptr, a->n_half, 1};
+    gp.dst[1] = WgGradDst{a->db_start, nullptr, 1, 0};
+    WgTimer tm{nullptr, 0, (hipStream_t)stream, who};
+    return wg_grad_launch(gp, (hipStream_t)stream, tm);
+}
+int t2_waveglow_head_backward(const t2_waveglow_head_backward_args* a, void* stream) {
+    const char* who = "waveglow head backward";
+    T2_REQUIRE(a, "t2_waveglow_head_backward: null arguments");
+    T2_REQUIRE(a->n_group >= 2 && a->n_group <= 8 && a->n_group % 2 == 0, "%s: n_group=%d is not even and from 2 to 8", who, a->n_group);
+    T2_REQUIRE(a->n_samples >= a->n_group, "%s: n_samples=%ld is shorter than one group of %d", who, a->n_samples, a->n_group);
+    T2_TRY_RC(wg_check_common(who, a->B, a->n_samples / a->n_group));
+    T2_REQUIRE(a->d_in && a->audio && a->part && a->dw, "%s: null pointer", who);
+    return wg_head_bwd(a->B, a->n_group, a->n_samples, a->d_in, a->audio, a->part, a->dw, (hipStream_t)stream);
+}
+int t2_waveglow_upsample_backward(const t2_waveglow_upsample_backward_args* a, void* stream) {
+    T2_REQUIRE(a, "t2_waveglow_upsample_backward: null arguments");
+    return wg_up_bwd(a->B, a->n_mel, a->T, a->n_group, a->n_samples, a->mel, a->d_spect, a->dw, a->db, (hipStream_t)stream);
 }
 
 }  // extern "C"

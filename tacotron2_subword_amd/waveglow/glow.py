@@ -1,5 +1,5 @@
 """Drop-in for the reference's ``glow.WaveGlow`` (glow.py:178-310) and ``glow.WaveGlowLoss`` (glow.py:43-59) on the MI355X:
-inference, and the values of the training direction (no gradient).
+inference, the values of the training direction, and -- as an opt-in -- training.
 
 The modules below only hold parameters, under the names and shapes the reference's checkpoints use; ``WaveGlow.infer``
 folds the weight norm (g * v / ||v||), inverts the 1x1 mixes once in fp32 (glow.py:91), hands everything to the HIP library
@@ -23,7 +23,18 @@ that number (or one per item) straight from sums the kernels form, for a validat
     with torch.no_grad():
         loss = waveglow.nll(mel, audio, sigma=1.0)                  # == WaveGlowLoss(1.0)(waveglow.analyze((mel, audio)))
 
-``forward`` / ``__call__`` still refuse: inside a training loop a forward without a backward would silently train nothing."""
+``forward`` / ``__call__`` refuse on a module that has not opted in.  ``WaveGlow.trainable()`` opts in: ``model((mel, audio))`` then
+is the reference's forward with a backward (t2_waveglow_train_forward / t2_waveglow_backward), so waveglow/train.py:125-137 runs
+with one changed line::
+
+    model = WaveGlow(**waveglow_config).cuda().trainable()
+    loss = WaveGlowLoss(sigma)(model((mel, audio)));  loss.backward()     # .grad on every parameter, weight-normed or not
+
+Two things differ from ``analyze`` on that path.  The weight norm is folded on the device by torch's own ``_weight_norm`` (whose
+autograd carries the folded gradient on to ``weight_g`` / ``weight_v``), so ``z`` may differ from ``analyze``'s, folded on the host,
+in the last bits.  And the parameters change every step, so the weights are packed on every call into a buffer of their own: the
+``_key()`` cache is not consulted and ``_packed`` / ``_packed_fwd`` are left alone.  ``B * L * logdet(W_k)`` is torch's autograd too.
+Gradients with respect to the mel and the audio, fp16 and amp are not built and refused by name."""
 from __future__ import annotations
 
 import ctypes as C
@@ -105,6 +116,75 @@ def _remove_weight_norm(mod):
     del mod._parameters["weight_g"], mod._parameters["weight_v"]
     mod.weight = nn.Parameter(w)                     # the reference's order after removal: bias, weight
     return mod
+
+
+class _FlowFunction(torch.autograd.Function):
+    """(z, log_s[0], .., log_s[n_flows-1]) from the folded fp32 tensors in the order ``WaveGlow._tensors(forward=True)`` lists
+    them: t2_waveglow_train_forward, and t2_waveglow_backward for arbitrary upstream gradients (a missing one counts as zero).
+    The backward returns one gradient per folded tensor, as views into one arena.  No host synchronisation on the stream, except
+    under kernel_times.  ``keep`` is the caller's word on whether a backward can follow (grad mode on and a parameter requiring
+    grad; ``needs_input_grad`` cannot tell, it ignores grad mode): without it nothing is kept and the plain t2_waveglow_forward runs
+    on the same packed weights.  Upstream gradients are not materialised: an output the loss does not use reaches the driver as a
+    null pointer, not as a tensor of zeros."""
+
+    @staticmethod
+    def forward(ctx, cfg, kernel_times, keep, mel, audio, *tensors):
+        dev, f32 = mel.device, torch.float32
+        (B, n_mel, T), N = mel.shape, audio.shape[1]
+        need = bool(keep)
+        ctx.set_materialize_grads(False)
+        plan = L.waveglow_forward_plan(cfg, B, T, N)               # refuses N < n_group and N > (T - 1) * 256 + 1024, by value
+        with torch.cuda.device(dev):
+            ts = [t.detach().to(f32).contiguous() for t in tensors]
+            mel, audio = mel.contiguous(), audio.contiguous()
+            packed = torch.empty(plan.packed_bytes // 4, device=dev, dtype=f32)
+            tp = (C.c_void_p * len(ts))(*[L.ptr(t) for t in ts])
+            L.check(L.lib().t2_waveglow_pack(C.byref(cfg), tp, len(ts), L.ptr(packed), L.stream()))
+            ws = torch.empty(plan.workspace_bytes // 4, device=dev, dtype=f32)
+            z = torch.empty(B, cfg.n_group, plan.L, device=dev, dtype=f32)
+            log_s = [torch.empty(B, t.shape[0] // 2, plan.L, device=dev, dtype=f32) for t in ts[2 + 6 + 4 * cfg.n_layers::7 + 4 * cfg.n_layers]]
+            assert len(log_s) == cfg.n_flows and sum(t.shape[1] for t in log_s) == plan.n_log_s_rows
+            table = (C.c_void_p * len(log_s))(*[L.ptr(t) for t in log_s])
+            ms = (C.c_double * len(L.WAVEGLOW_FORWARD_KERNELS))() if kernel_times is not None else None
+            a = L.WaveglowForwardArgs(B, T, n_mel, N, L.ptr(packed), None, L.ptr(mel), L.ptr(audio), L.ptr(ws), L.ptr(z), table, None, 1.0, None, None,
+                                      None, ms)
+            if need:
+                bplan = L.waveglow_backward_plan(cfg, B, T, N)
+                saved = torch.empty(bplan.saved_bytes // 4, device=dev, dtype=f32)
+                L.check(L.lib().t2_waveglow_train_forward(C.byref(cfg), C.byref(L.WaveglowTrainForwardArgs(a, L.ptr(saved))), L.stream()))
+                ctx.cfg, ctx.kernel_times, ctx.packed, ctx.saved, ctx.shape = cfg, kernel_times, packed, saved, (B, T, N)
+                ctx.save_for_backward(mel, audio, *ts)
+            else:
+                L.check(L.lib().t2_waveglow_forward(C.byref(cfg), C.byref(a), L.stream()))
+        if kernel_times is not None:
+            kernel_times["forward"] = dict(zip(L.WAVEGLOW_FORWARD_KERNELS, ms))
+        return (z, *log_s)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dz, *dlog_s):
+        cfg, (B, T, N) = ctx.cfg, ctx.shape
+        mel, audio, *ts = ctx.saved_tensors
+        dev, f32 = mel.device, torch.float32
+        plan = L.waveglow_backward_plan(cfg, B, T, N)
+        with torch.cuda.device(dev):
+            ups = [None if g is None else g.to(f32).contiguous() for g in (dz, *dlog_s)]
+            packed_bwd = torch.empty(plan.packed_bwd_bytes // 4, device=dev, dtype=f32)
+            tp = (C.c_void_p * len(ts))(*[L.ptr(t) for t in ts])
+            L.check(L.lib().t2_waveglow_pack_backward(C.byref(cfg), tp, len(ts), L.ptr(packed_bwd), L.stream()))
+            ws = torch.empty(plan.workspace_bytes // 4, device=dev, dtype=f32)
+            arena = torch.empty(plan.grad_floats, device=dev, dtype=f32)
+            table = (C.c_void_p * cfg.n_flows)(*[L.ptr(g) for g in ups[1:]])
+            ms = (C.c_double * len(L.WAVEGLOW_BACKWARD_KERNELS))() if ctx.kernel_times is not None else None
+            a = L.WaveglowBackwardArgs(B, T, mel.shape[1], N, L.ptr(ctx.packed), L.ptr(packed_bwd), L.ptr(ctx.saved), L.ptr(mel), L.ptr(audio), L.ptr(ups[0]),
+                                       table, L.ptr(ws), L.ptr(arena), ms)
+            L.check(L.lib().t2_waveglow_backward(C.byref(cfg), C.byref(a), L.stream()))
+        if ctx.kernel_times is not None:
+            ctx.kernel_times["backward"] = dict(zip(L.WAVEGLOW_BACKWARD_KERNELS, ms))
+            ctx.kernel_times["arena"] = arena
+        offs = L.waveglow_grad_offsets(cfg, len(ts))
+        assert offs[-1] + ts[-1].numel() == plan.grad_floats
+        return (None, None, None, None, None, *[arena[o:o + t.numel()].view(t.shape) for o, t in zip(offs, ts)])
 
 
 class Invertible1x1Conv(nn.Module):
@@ -190,9 +270,66 @@ class WaveGlow(nn.Module):
         return L.waveglow_config(self.upsample.in_channels, self.n_flows, self.n_group, self.n_early_every, self.n_early_size,
                                  dict(n_layers=wn.n_layers, n_channels=wn.n_channels, kernel_size=k[0] if isinstance(k, (tuple, list)) else k))
 
+    def trainable(self, on=True):
+        """Opt in to training: ``model((mel, audio))`` then runs the forward that keeps what the backward reads, and
+        ``WaveGlowLoss(sigma)(outputs).backward()`` leaves ``.grad`` on every parameter.  A plain attribute, read with
+        ``getattr(..., False)``: a module pickled by the reference lacks it and stays refused.  Returns self."""
+        self._trainable = bool(on)
+        return self
+
     def forward(self, forward_input):
-        raise RuntimeError("WaveGlow is inference only here: forward (the training direction, audio -> z) has no backward, so it stays "
-                           "refused; call infer, or analyze / nll for the values of that direction under torch.no_grad()")
+        if not getattr(self, "_trainable", False):
+            raise RuntimeError("WaveGlow is inference only here: forward (the training direction, audio -> z) has no backward, so it stays "
+                               "refused; call infer, or analyze / nll for the values of that direction under torch.no_grad()")
+        return self._train_forward(forward_input)
+
+    def _train_tensors(self):
+        """``_tensors(forward=True)`` as differentiable fp32 tensors: the weight norm is folded on the device by torch's own
+        ``_weight_norm``, so autograd carries a folded tensor's gradient on to ``weight_g`` / ``weight_v`` (or ``weight``)."""
+        fold = lambda m: torch._weight_norm(m.weight_v, m.weight_g, 0) if _weight_normed(m) else m.weight
+        out = [self.upsample.weight, self.upsample.bias]
+        for wn, inv in zip(self.WN, self.convinv):
+            out += [fold(wn.start), wn.start.bias, fold(wn.cond_layer), wn.cond_layer.bias]
+            for l in wn.in_layers:
+                out += [fold(l), l.bias]
+            for l in wn.res_skip_layers:
+                out += [fold(l), l.bias]
+            out += [wn.end.weight, wn.end.bias, inv.conv.weight.squeeze(-1)]
+        return out
+
+    def _train_forward(self, forward_input, kernel_times=None):
+        """The reference's ``forward`` (glow.py:207-249) with a backward.  Two differences from ``analyze``: the weight norm is
+        folded on the device, so z may differ from analyze's (host fold) in the last bits; and, the parameters changing every
+        step, the weights are packed on every call into a buffer of their own -- the ``_key()`` cache and ``_packed`` /
+        ``_packed_fwd`` are neither read nor written.  kernel_times: a dict that receives ``forward`` and ``backward``, the time
+        per kind of kernel (synchronises; for scripts/time_waveglow_train.py)."""
+        spect, audio = forward_input
+        who = "WaveGlow.forward"
+        dev = self.upsample.weight.device
+        if dev.type != "cuda" or not (spect.is_cuda and audio.is_cuda):
+            raise RuntimeError(f"{who}: the parameters, the mel and the audio must live on the GPU (the product path has no CPU fallback)")
+        if torch.is_grad_enabled() and spect.requires_grad:
+            raise RuntimeError(f"{who}: the mel requires grad, but the gradient with respect to the mel is not built")
+        if torch.is_grad_enabled() and audio.requires_grad:
+            raise RuntimeError(f"{who}: the audio requires grad, but the gradient with respect to the audio is not built")
+        cfg = self._config()
+        if spect.dim() != 3 or spect.shape[1] != cfg.n_mel_channels:
+            raise RuntimeError(f"{who}: expected a mel of shape [B, {cfg.n_mel_channels}, T] (upsample takes "
+                               f"{cfg.n_mel_channels} channels), got {tuple(spect.shape)}")
+        if audio.dim() != 2 or audio.shape[0] != spect.shape[0]:
+            raise RuntimeError(f"{who}: expected audio of shape [B, N] with B = {spect.shape[0]}, got {tuple(audio.shape)}")
+        if spect.dtype != torch.float32 or audio.dtype != torch.float32 or any(p.dtype != torch.float32 for p in self.parameters()):
+            raise RuntimeError(f"{who}: the mel, the audio and the parameters must be float32 (fp16 and amp are not built)")
+        if torch.is_autocast_enabled():
+            raise RuntimeError(f"{who}: autocast is on, but fp16 and amp are not built")
+        if audio.device != spect.device or dev != spect.device:
+            raise RuntimeError(f"{who}: the mel is on {spect.device}, the audio on {audio.device}, the parameters on {dev}")
+        B, L_ = spect.shape[0], audio.shape[1] // cfg.n_group
+        tensors = self._train_tensors()
+        keep = torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters())
+        outs = _FlowFunction.apply(cfg, kernel_times, keep, spect.detach(), audio.detach(), *tensors)
+        logdet = [B * L_ * torch.logdet(inv.conv.weight.squeeze(-1)) for inv in self.convinv]            # glow.py:100, torch's own autograd
+        return outs[0], list(outs[1:]), logdet
 
     @staticmethod
     def remove_weightnorm(model):
