@@ -609,6 +609,60 @@ typedef struct t2_softdtw_dist_bwd_args {
 } t2_softdtw_dist_bwd_args;
 int t2_softdtw_dist_backward(const t2_softdtw_dist_bwd_args* a, void* stream);
 
+/* ---- SSIM (the loss term of loss_function.py:10,24) -------------------------------------------------
+ * Replaces the reference's ssim.py:17-37 (_ssim: five grouped conv2d with a Gaussian window under zero padding of ws/2,
+ * the element-wise algebra of S and its mean) and the autograd graph behind it.  Images are N = B*C planes of H x W
+ * fp32; every image carries its plane, row and column strides in elements, and one of its two inner strides must be 1
+ * (an axis of size 1 counts).  The lane axis of the kernels is the one along which x is contiguous, so [B,1,80,T] and
+ * the transposed view of a [B,T,80] buffer both run without a copy.  taps: the ws 1-D taps (ssim.py:7-9 as it rounds
+ * them); ws odd, 1..31.  Moments, the subtraction E[xx] - mu^2 and the algebra of S and its derivatives are fp64, so
+ * value and gradient stay accurate where the reference's fp32 statement cancels (log-mel silence).  Sums are taken in a
+ * fixed order without atomics: results are bit-identical from run to run.  No call synchronises with the host.
+ * The coefficient maps a forward call stores for the backward are fp64 too: the three terms of the gradient cancel.
+ *
+ * t2_ssim_plan (ssim.py:17-37) is pure (no device): the tiling and the scratch the calls need.  need_grad: 0 = none,
+ * 1 = dx, 2 = dy, 3 = both.  Fails, naming the argument, for an even ws, ws > 31, need_grad outside 0..3, non-positive
+ * sizes, and N*H*W beyond 2^31-1. */
+typedef struct t2_ssim_plan_info {
+    int tile_h, tile_w;       /* outputs per workgroup: rows x lane-axis columns */
+    int tiles_h, tiles_w;     /* tiles per plane with W as the lane axis */
+    long partials;            /* N * tiles_h * tiles_w: one fp64 partial sum per tile and plane */
+    long partials_t;          /* the same count when H is the lane axis (x contiguous along H) */
+    size_t partial_bytes;     /* scratch for the partials: 8 * max(partials, partials_t) */
+    size_t map_bytes;         /* stored fp64 coefficient maps for the backward: 8 * N*H*W * (0, 3 for one gradient, 4 for both) */
+    size_t lds_fwd_bytes, lds_bwd_bytes;   /* LDS per workgroup of the two kernels */
+} t2_ssim_plan_info;
+int t2_ssim_plan(int N, int H, int W, int ws, int need_grad, t2_ssim_plan_info* out);
+typedef struct t2_ssim_image {
+    float* p;
+    long plane_stride, row_stride, col_stride;   /* in elements */
+} t2_ssim_image;
+/* ssim.py:17-37.  S per pixel, then value[0] = mean of S over everything (size_average=True, :34-35) and / or
+ * items[b] = mean over C*H*W of item b (:36-37); map (nullable p) receives S itself.  need_grad != 0 also stores the
+ * coefficient maps (coef, map_bytes) that t2_ssim_backward filters. */
+typedef struct t2_ssim_fwd_args {
+    int B, C, H, W, ws, need_grad;
+    t2_ssim_image x, y, map;
+    const float* taps;        /* [ws] */
+    void* partial;            /* partial_bytes */
+    void* coef;               /* map_bytes; NULL iff need_grad == 0 */
+    float* value;             /* [1] or NULL */
+    float* items;             /* [B] or NULL */
+} t2_ssim_fwd_args;
+int t2_ssim_forward(const t2_ssim_fwd_args* a, void* stream);
+/* Gradient of ssim.py:17-37 from the coef a forward call with the same x, y, ws and need_grad stored:
+ * dx(p) = g * (F[a - 2 b mu1 - c mu2](p) + 2 x(p) F[b](p) + y(p) F[c](p)), F the same zero-padded window, a, b, c the
+ * derivatives of S by mu1, sigma1^2 and sigma12; dy the same with the images' roles swapped.  g = grad[0] / (N*H*W)
+ * (per_item == 0) or grad[b] / (C*H*W) (per_item != 0), read on the device.  dx.p or dy.p may be NULL (not both). */
+typedef struct t2_ssim_bwd_args {
+    int B, C, H, W, ws, need_grad, per_item;
+    t2_ssim_image x, y, dx, dy;
+    const float* taps;
+    const void* coef;         /* map_bytes, as the forward call left them */
+    const float* grad;        /* [1], or [B] with per_item */
+} t2_ssim_bwd_args;
+int t2_ssim_backward(const t2_ssim_bwd_args* a, void* stream);
+
 /* ---- HiFi-GAN generator (mel spectrogram -> waveform) ----------------------------------------------
  * Replaces the reference's hifigan_infer/hifigan_model.py: Generator.forward (:100-116), ResBlock1.forward (:35-42),
  * ResBlock2.forward (:63-68), as inference.py:172-206, best_checkpoint.py:191-228, streamlitNews.py:115-160 and

@@ -234,6 +234,28 @@ class SoftDtwDistBwdArgs(C.Structure):
                 ("dX", C.c_void_p), ("dY", C.c_void_p)]
 
 
+class SsimPlanInfo(C.Structure):
+    _fields_ = [("tile_h", C.c_int), ("tile_w", C.c_int), ("tiles_h", C.c_int), ("tiles_w", C.c_int),
+                ("partials", C.c_long), ("partials_t", C.c_long), ("partial_bytes", C.c_size_t), ("map_bytes", C.c_size_t),
+                ("lds_fwd_bytes", C.c_size_t), ("lds_bwd_bytes", C.c_size_t)]
+
+
+class SsimImage(C.Structure):
+    _fields_ = [("p", C.c_void_p), ("plane_stride", C.c_long), ("row_stride", C.c_long), ("col_stride", C.c_long)]
+
+
+class SsimFwdArgs(C.Structure):
+    _fields_ = [(n, C.c_int) for n in ("B", "C", "H", "W", "ws", "need_grad")] + \
+               [("x", SsimImage), ("y", SsimImage), ("map", SsimImage), ("taps", C.c_void_p), ("partial", C.c_void_p),
+                ("coef", C.c_void_p), ("value", C.c_void_p), ("items", C.c_void_p)]
+
+
+class SsimBwdArgs(C.Structure):
+    _fields_ = [(n, C.c_int) for n in ("B", "C", "H", "W", "ws", "need_grad", "per_item")] + \
+               [("x", SsimImage), ("y", SsimImage), ("dx", SsimImage), ("dy", SsimImage), ("taps", C.c_void_p), ("coef", C.c_void_p),
+                ("grad", C.c_void_p)]
+
+
 _I6 = C.c_int * 6
 
 
@@ -428,6 +450,7 @@ EXPORTS = ["t2_last_error", "t2_version", "t2_chain_status", "t2_chain_status_cl
            "t2_lstm_seq_forward", "t2_lstm_seq_backward", "t2_lstm_seq_chain_ws_floats", "t2_gemm_ex", "t2_prof_gemm", "t2_gemm_plan", "t2_chain_plan", "t2_conv_handoff_plan", "t2_colsum", "t2_mask_btc",
            "t2_finalize_bct", "t2_mask_bt", "t2_gemm", "t2_rng_keep_mask", "t2_rng_normal",
            "t2_softdtw_plan", "t2_softdtw_dist", "t2_softdtw_forward", "t2_softdtw_backward", "t2_softdtw_dist_backward",
+           "t2_ssim_plan", "t2_ssim_forward", "t2_ssim_backward",
            "t2_hifigan_plan", "t2_hifigan_pack", "t2_hifigan_forward", "t2_vocoder_packed_floats", "t2_vocoder_conv1d", "t2_vocoder_conv_transpose1d",
            "t2_stft_plan", "t2_stft_pack", "t2_stft_analysis", "t2_stft_synthesis", "t2_melspec_plan", "t2_melspec_pack", "t2_melspec",
            "t2_waveglow_plan", "t2_waveglow_pack", "t2_waveglow_infer", "t2_waveglow_packed_floats", "t2_waveglow_gated_conv", "t2_waveglow_res_skip",
@@ -496,6 +519,9 @@ def lib() -> C.CDLL:
         L.t2_softdtw_forward.argtypes = [C.POINTER(SoftDtwFwdArgs), C.c_void_p]
         L.t2_softdtw_backward.argtypes = [C.POINTER(SoftDtwBwdArgs), C.c_void_p]
         L.t2_softdtw_dist_backward.argtypes = [C.POINTER(SoftDtwDistBwdArgs), C.c_void_p]
+        L.t2_ssim_plan.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(SsimPlanInfo)]
+        L.t2_ssim_forward.argtypes = [C.POINTER(SsimFwdArgs), C.c_void_p]
+        L.t2_ssim_backward.argtypes = [C.POINTER(SsimBwdArgs), C.c_void_p]
         L.t2_hifigan_plan.argtypes = [C.POINTER(HifiganConfig), C.c_int, C.c_int, C.POINTER(HifiganPlanInfo)]
         L.t2_hifigan_pack.argtypes = [C.POINTER(HifiganConfig), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_int, C.c_void_p, C.c_void_p]
         L.t2_hifigan_forward.argtypes = [C.POINTER(HifiganConfig), C.POINTER(HifiganFwdArgs), C.c_void_p]
@@ -897,6 +923,36 @@ def softdtw_plan(B: int, N: int, M: int, gamma: float = 1.0, need_grad: bool = F
     info = SoftDtwPlanInfo()
     check(lib().t2_softdtw_plan(B, N, M, gamma, int(bool(need_grad)), C.byref(info)))
     return info
+
+
+def ssim_plan(N: int, H: int, W: int, ws: int = 11, need_grad: int = 0) -> SsimPlanInfo:
+    """The tiling and scratch sizes of an SSIM call on N planes of H x W (t2_ssim_plan: nothing is launched, no device
+    needed).  need_grad: 0 none, 1 dx, 2 dy, 3 both.  Raises for an even or too wide window and for sizes out of range."""
+    info = SsimPlanInfo()
+    check(lib().t2_ssim_plan(N, H, W, ws, int(need_grad), C.byref(info)))
+    return info
+
+
+def ssim_image(t: torch.Tensor | None) -> SsimImage:
+    """A [B,C,H,W] fp32 device tensor as t2_ssim_image: its pointer and strides as they are (no copy); None -> NULL.
+    The planes must be evenly spaced (B and C collapse to one plane axis)."""
+    if t is None:
+        return SsimImage(None, 0, 0, 0)
+    if not t.is_cuda or t.dtype != torch.float32 or t.dim() != 4:
+        raise RuntimeError("t2amd: an SSIM image must be a 4-D fp32 tensor on the GPU")
+    B, Cn = t.shape[0], t.shape[1]
+    sb, sc, sh, sw = t.stride()
+    if B > 1 and Cn > 1 and sb != Cn * sc:
+        raise RuntimeError("t2amd: SSIM image planes must be evenly spaced over batch and channel")
+    return SsimImage(t.data_ptr(), sc if Cn > 1 else sb, sh, sw)
+
+
+def ssim_forward(args: SsimFwdArgs) -> None:
+    check(lib().t2_ssim_forward(C.byref(args), stream()))
+
+
+def ssim_backward(args: SsimBwdArgs) -> None:
+    check(lib().t2_ssim_backward(C.byref(args), stream()))
 
 
 def hifigan_config(h) -> HifiganConfig:

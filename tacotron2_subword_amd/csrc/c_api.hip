@@ -550,6 +550,27 @@ int t2_softdtw_dist_backward(const t2_softdtw_dist_bwd_args* a, void* stream) {
                             (hipStream_t)stream);
 }
 
+int t2_ssim_plan(int N, int H, int W, int ws, int need_grad, t2_ssim_plan_info* out) {
+    SsimPlan p;
+    T2_TRY(ssim_plan(N, H, W, ws, need_grad, &p));
+    T2_REQUIRE(out, "t2_ssim_plan: null output");
+    out->tile_h = p.tile_h; out->tile_w = p.tile_w; out->tiles_h = p.tiles_h; out->tiles_w = p.tiles_w;
+    out->partials = p.partials; out->partials_t = p.partials_t; out->partial_bytes = p.partial_bytes; out->map_bytes = p.map_bytes;
+    out->lds_fwd_bytes = p.lds_fwd_bytes; out->lds_bwd_bytes = p.lds_bwd_bytes;
+    return 0;
+}
+static SsimImage ssim_image(const t2_ssim_image& im) { return SsimImage{im.p, im.plane_stride, im.row_stride, im.col_stride}; }
+int t2_ssim_forward(const t2_ssim_fwd_args* a, void* stream) {
+    T2_REQUIRE(a, "t2_ssim_forward: null arguments");
+    return ssim_fwd(SsimFwd{a->B, a->C, a->H, a->W, a->ws, a->need_grad, ssim_image(a->x), ssim_image(a->y), ssim_image(a->map), a->taps,
+                            static_cast<double*>(a->partial), static_cast<double*>(a->coef), a->value, a->items}, (hipStream_t)stream);
+}
+int t2_ssim_backward(const t2_ssim_bwd_args* a, void* stream) {
+    T2_REQUIRE(a, "t2_ssim_backward: null arguments");
+    return ssim_bwd(SsimBwd{a->B, a->C, a->H, a->W, a->ws, a->need_grad, a->per_item, ssim_image(a->x), ssim_image(a->y), ssim_image(a->dx),
+                            ssim_image(a->dy), a->taps, static_cast<const double*>(a->coef), a->grad}, (hipStream_t)stream);
+}
+
 static_assert(sizeof(t2_hifigan_config) == sizeof(HifiganConfig) && T2_HIFIGAN_MAX_UPS == kHifiganMaxUps && T2_HIFIGAN_MAX_KERNELS == kHifiganMaxKernels &&
               T2_HIFIGAN_MAX_DILATIONS == kHifiganMaxDilations && T2_VOCODER_TIME_TILE == kVocTT, "t2_hifigan_config mirrors HifiganConfig");
 int t2_hifigan_plan(const t2_hifigan_config* cfg, int B, int T, t2_hifigan_plan_info* out) {

@@ -469,6 +469,31 @@ struct SoftDtwDistBwd {
 };
 int softdtw_dist_bwd(const SoftDtwDistBwd& a, hipStream_t s);
 
+// ------------------------------------------------------------------ SSIM (ssim.hip)
+constexpr int kSsimTileH = 16, kSsimTileW = 64;  // outputs per workgroup: 4 waves x 4 rows, a wave across the lane axis
+constexpr int kSsimMaxWs = 31;
+// The tiling of N planes of H x W with W as the lane axis (tiles_h x tiles_w tiles of tile_h x tile_w per plane, one fp64
+// partial per tile and plane), decided on the host.  partials_t is the count when the launcher takes H as the lane axis
+// (x contiguous along H); partial_bytes covers the larger.  map_bytes: the stored fp64 coefficient maps, 3 per pixel for
+// one gradient, 4 for both, 0 without.  need_grad: 0, 1 = dx, 2 = dy, 3 = both.
+struct SsimPlan { int tile_h, tile_w, tiles_h, tiles_w; long partials, partials_t; size_t partial_bytes, map_bytes, lds_fwd_bytes, lds_bwd_bytes; };
+int ssim_plan(long N, long H, long W, int ws, int need_grad, SsimPlan* out);
+struct SsimImage { float* p; long sn, sr, sc; }; // plane, row and column strides in elements
+struct SsimFwd {
+    int B, C, H, W, ws, need_grad;
+    SsimImage x, y, map;                         // map.p nullable: S itself, [N,H,W] through its strides
+    const float* taps;                           // [ws]
+    double* partial; double* coef;               // scratch of the plan; coef nullable iff need_grad == 0
+    float* value; float* items;                  // [1] mean over everything, [B] mean per item; each nullable
+};
+int ssim_fwd(const SsimFwd& a, hipStream_t s);
+struct SsimBwd {
+    int B, C, H, W, ws, need_grad, per_item;     // per_item: grad is [B] and scales item b's mean; else [1] and the whole mean
+    SsimImage x, y, dx, dy;                      // dx.p, dy.p nullable (not both)
+    const float* taps; const double* coef; const float* grad;
+};
+int ssim_bwd(const SsimBwd& a, hipStream_t s);
+
 // ------------------------------------------------------------------ HiFi-GAN vocoder (vocoder.hip)
 constexpr int kVocTT = 128;                      // time positions per workgroup
 constexpr int kVocMaxPad = 60;                   // (k*d - d)/2 at k = 11, d = 12

@@ -1,0 +1,333 @@
+// SSIM (Wang et al. 2004) as the reference's ssim.py:17-37 states it: five Gaussian-window moments of two images under
+// zero padding, S = (2 mu1 mu2 + C1)(2 s12 + C2) / ((mu1^2 + mu2^2 + C1)(s1 + s2 + C2)), and its mean.  One fused
+// forward launch + a finishing launch, one backward launch; replaces 5 grouped conv2d and ~20 element-wise launches.
+//
+// Why fp64 inside: the reference forms conv(x*x) - conv(x)^2 in fp32.  On a log-mel, silence sits at -11.5 with small
+// deviations, so E[x^2] ~ 132 against s + C2 ~ 1e-3 and the subtraction keeps 2-3 digits.  Here the products of the
+// fp32 inputs (exact in fp64), the window sums, the subtraction and the algebra of S and of its derivatives run in
+// fp64; results are rounded to fp32 once, where they are stored.  The work is ~0.2 GFLOP at B = 64, 80 x 400.
+//
+// A workgroup owns a 16 x 64 tile of one plane.  It stages x and y with a halo of r = ws/2 in LDS (zeros outside the
+// image), then per moment: row pass (staged rows x 64 columns, lanes on adjacent columns) into one fp64 LDS plane,
+// column pass from that plane into 4 registers per thread (a thread owns 4 consecutive rows of one column).  One
+// moment at a time keeps LDS at 28 KB for ws = 11 (58 KB at ws = 31); every LDS access has the 64 lanes on adjacent
+// 4- or 8-byte words (no bank conflicts), the taps are broadcast reads.
+//
+// The lane axis is whichever inner axis of x is contiguous (the window is symmetric): the launcher swaps H and W and
+// every image's two inner strides, so [B,1,80,T] and the transposed view of a [B,T,80] buffer both run without a copy.
+// Every image is addressed through its own three strides; loads are 4 bytes per lane, guarded at the edges.
+//
+// Backward: the forward stores, per pixel, the coefficients P = a1 - 2 b mu1 - c mu2 (and Q, with the roles of the
+// images swapped), b = dS/ds1 = -S/B2 and c = dS/ds12 = 2 A1/(B1 B2); dx = g (F[P] + 2 x F[b] + y F[c]) with the same
+// zero-padded filter F.  The three terms cancel (|b| is up to 1/C2 ~ 1e3, the net often 1e-2 of a term), so the maps
+// are stored, filtered and combined in fp64: as fp32 they would put the gradient back at the fp32 statement's error.
+// Sums are in a fixed order everywhere, no atomics.
+#include "kernels.h"
+
+namespace t2 {
+
+constexpr int kSsimThreads = 256;
+constexpr int kSsimRowsPerThread = kSsimTileH / (kSsimThreads / kWave);
+static_assert(kSsimTileW == kWave && kSsimRowsPerThread * (kSsimThreads / kWave) == kSsimTileH, "a wave spans a tile row, a thread owns whole rows");
+constexpr double kSsimC1 = 0.01 * 0.01, kSsimC2 = 0.03 * 0.03;        // ssim.py:29-30
+
+static size_t ssim_lds_bytes(int ws, size_t staged_bytes_per_element) {     // forward: x and y as fp32; backward: one fp64 map
+    const int SH = kSsimTileH + ws - 1, SW = kSsimTileW + ws - 1;
+    return (size_t)(32 + 4 + SH * kSsimTileW) * sizeof(double) + staged_bytes_per_element * SH * SW;
+}
+
+int ssim_plan(long N, long H, long W, int ws, int need_grad, SsimPlan* out) {
+    T2_REQUIRE(out, "ssim: null plan");
+    T2_REQUIRE(ws >= 1 && ws % 2 == 1, "ssim: ws=%d must be odd and at least 1 (even windows are not built)", ws);
+    T2_REQUIRE(ws <= kSsimMaxWs, "ssim: ws=%d exceeds the limit of %d taps", ws, kSsimMaxWs);
+    T2_REQUIRE(N >= 1, "ssim: N=%ld planes must be at least 1", N);
+    T2_REQUIRE(H >= 1 && W >= 1, "ssim: H=%ld and W=%ld must be at least 1", H, W);
+    T2_REQUIRE(need_grad >= 0 && need_grad <= 3, "ssim: need_grad=%d must be 0, 1 (dx), 2 (dy) or 3 (both)", need_grad);
+    T2_REQUIRE(N <= INT32_MAX && H <= INT32_MAX && W <= INT32_MAX && N * H <= INT32_MAX && N * H * W <= INT32_MAX,
+               "ssim: N*H*W = %ld*%ld*%ld exceeds the 2^31-1 elements that 32-bit tile indexing takes", N, H, W);
+    auto cdiv = [](long a, long b) { return (a + b - 1) / b; };
+    out->tile_h = kSsimTileH; out->tile_w = kSsimTileW;
+    out->tiles_h = (int)cdiv(H, kSsimTileH); out->tiles_w = (int)cdiv(W, kSsimTileW);
+    out->partials = N * out->tiles_h * out->tiles_w;
+    out->partials_t = N * cdiv(W, kSsimTileH) * cdiv(H, kSsimTileW);
+    out->partial_bytes = sizeof(double) * (size_t)(out->partials > out->partials_t ? out->partials : out->partials_t);
+    out->map_bytes = sizeof(double) * (size_t)(need_grad == 3 ? 4 : need_grad ? 3 : 0) * (size_t)(N * H * W);
+    out->lds_fwd_bytes = ssim_lds_bytes(ws, 2 * sizeof(float));
+    out->lds_bwd_bytes = ssim_lds_bytes(ws, sizeof(double));
+    return 0;
+}
+
+// ------------------------------------------------------------------------------------------------------------------
+// the tile passes
+// ------------------------------------------------------------------------------------------------------------------
+struct SsimLds { double* taps; double* red; double* buf; float* sa; float* sb; int r, SH, SW; };
+__device__ __forceinline__ SsimLds ssim_lds(double* base, int ws) {
+    SsimLds l;
+    l.r = ws / 2; l.SH = kSsimTileH + ws - 1; l.SW = kSsimTileW + ws - 1;
+    l.taps = base; l.red = base + 32; l.buf = base + 36;
+    l.sa = reinterpret_cast<float*>(l.buf + l.SH * kSsimTileW);
+    l.sb = l.sa + l.SH * l.SW;
+    return l;
+}
+// s[rr][cc] = the plane at base (row stride sr, column stride sc) at (r0 + rr - r, c0 + cc - r), 0 outside the image: a
+// wave per staged row
+template <class T>
+__device__ __forceinline__ void ssim_stage(T* s, const T* base, long sr, long sc, int r0, int c0, int H, int W, const SsimLds& l) {
+    const int lane = threadIdx.x & (kWave - 1), w = threadIdx.x / kWave;
+    for (int rr = w; rr < l.SH; rr += kSsimThreads / kWave) {
+        const int gr = r0 + rr - l.r;
+        const bool rin = gr >= 0 && gr < H;
+        for (int cc = lane; cc < l.SW; cc += kWave) {
+            const int gc = c0 + cc - l.r;
+            s[rr * l.SW + cc] = (rin && gc >= 0 && gc < W) ? base[(long)gr * sr + (long)gc * sc] : T(0);
+        }
+    }
+}
+// buf[rr][j] = sum_k taps[k] * v[rr][j + k], k ascending; v = a or the exact product a * b
+template <int WS, bool PROD, class T>
+__device__ __forceinline__ void ssim_rows(const SsimLds& l, const T* sa, const T* sb, int ws_rt) {
+    const int ws = WS ? WS : ws_rt;
+    const int lane = threadIdx.x & (kWave - 1), w = threadIdx.x / kWave;
+    for (int rr = w; rr < l.SH; rr += kSsimThreads / kWave) {
+        const T* pa = sa + rr * l.SW + lane;
+        const T* pb = sb + rr * l.SW + lane;
+        double acc = 0.0;
+#pragma unroll
+        for (int k = 0; k < ws; ++k) {
+            double v = (double)pa[k];
+            if (PROD) v *= (double)pb[k];
+            acc = fma(l.taps[k], v, acc);
+        }
+        l.buf[rr * kSsimTileW + lane] = acc;
+    }
+}
+// out[o] = sum_k taps[k] * buf[i0 + o + k][lane], k ascending, for the thread's rows i0 .. i0 + 3
+template <int WS>
+__device__ __forceinline__ void ssim_cols(double (&out)[kSsimRowsPerThread], const SsimLds& l, int ws_rt) {
+    const int ws = WS ? WS : ws_rt;
+    const int lane = threadIdx.x & (kWave - 1), i0 = threadIdx.x / kWave * kSsimRowsPerThread;
+#pragma unroll
+    for (int o = 0; o < kSsimRowsPerThread; ++o) {
+        const double* p = l.buf + (i0 + o) * kSsimTileW + lane;
+        double acc = 0.0;
+#pragma unroll
+        for (int k = 0; k < ws; ++k) acc = fma(l.taps[k], p[k * kSsimTileW], acc);
+        out[o] = acc;
+    }
+}
+__device__ __forceinline__ double ssim_wave_sum(double v) {       // a fixed tree: the same bits every run
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+
+struct SsimFwdK {
+    SsimImage x, y, map;          // canonical orientation (lane axis = W); map.p nullable
+    double* coef;                 // nullable; [slots][N][H][W]
+    const float* taps;
+    double* partial;
+    long nhw;                     // N * H * W, the stride between coefficient slots
+    int need, H, W, tiles_w, tiles, ws;
+};
+
+template <int WS>
+__global__ void __launch_bounds__(kSsimThreads) ssim_fwd_kernel(const SsimFwdK a) {
+    extern __shared__ double ssim_smem[];
+    const int ws = WS ? WS : a.ws;
+    const SsimLds l = ssim_lds(ssim_smem, ws);
+    const int tile = blockIdx.x % a.tiles;
+    const long n = blockIdx.x / a.tiles;
+    const int r0 = tile / a.tiles_w * kSsimTileH, c0 = tile % a.tiles_w * kSsimTileW;
+    if (threadIdx.x < ws) l.taps[threadIdx.x] = (double)a.taps[threadIdx.x];
+    ssim_stage<float>(l.sa, a.x.p + n * a.x.sn, a.x.sr, a.x.sc, r0, c0, a.H, a.W, l);
+    ssim_stage<float>(l.sb, a.y.p + n * a.y.sn, a.y.sr, a.y.sc, r0, c0, a.H, a.W, l);
+    __syncthreads();
+    double mu1[kSsimRowsPerThread], mu2[kSsimRowsPerThread], exx[kSsimRowsPerThread], eyy[kSsimRowsPerThread], exy[kSsimRowsPerThread];
+    ssim_rows<WS, false>(l, l.sa, l.sa, ws); __syncthreads(); ssim_cols<WS>(mu1, l, ws); __syncthreads();
+    ssim_rows<WS, false>(l, l.sb, l.sb, ws); __syncthreads(); ssim_cols<WS>(mu2, l, ws); __syncthreads();
+    ssim_rows<WS, true>(l, l.sa, l.sa, ws); __syncthreads(); ssim_cols<WS>(exx, l, ws); __syncthreads();
+    ssim_rows<WS, true>(l, l.sb, l.sb, ws); __syncthreads(); ssim_cols<WS>(eyy, l, ws); __syncthreads();
+    ssim_rows<WS, true>(l, l.sa, l.sb, ws); __syncthreads(); ssim_cols<WS>(exy, l, ws);
+
+    const int lane = threadIdx.x & (kWave - 1), w = threadIdx.x / kWave;
+    const int gc = c0 + lane;
+    double sum = 0.0;
+#pragma unroll
+    for (int o = 0; o < kSsimRowsPerThread; ++o) {
+        const int gr = r0 + w * kSsimRowsPerThread + o;
+        if (gr >= a.H || gc >= a.W) continue;
+        const double m1 = mu1[o], m2 = mu2[o];
+        const double s1 = exx[o] - m1 * m1, s2 = eyy[o] - m2 * m2, s12 = exy[o] - m1 * m2;
+        const double A1 = 2.0 * m1 * m2 + kSsimC1, A2 = 2.0 * s12 + kSsimC2;
+        const double iB1 = 1.0 / (m1 * m1 + m2 * m2 + kSsimC1), iB2 = 1.0 / (s1 + s2 + kSsimC2);
+        const double S = A1 * A2 * iB1 * iB2;
+        sum += S;
+        if (a.map.p) a.map.p[n * a.map.sn + (long)gr * a.map.sr + (long)gc * a.map.sc] = (float)S;
+        if (a.need) {
+            const double b = -S * iB2, c = 2.0 * A1 * iB1 * iB2;
+            const double t = 2.0 * A2 * iB1 * iB2, u = 2.0 * S * iB1;       // dS/dmu1 = t mu2 - u mu1 at fixed s
+            const double P = (t * m2 - u * m1) - 2.0 * b * m1 - c * m2;
+            const double Q = (t * m1 - u * m2) - 2.0 * b * m2 - c * m1;
+            double* cf = a.coef + (n * a.H + gr) * (long)a.W + gc;
+            cf[0] = a.need == 2 ? Q : P;
+            cf[a.nhw] = b;
+            cf[2 * a.nhw] = c;
+            if (a.need == 3) cf[3 * a.nhw] = Q;
+        }
+    }
+    sum = ssim_wave_sum(sum);
+    if (lane == 0) l.red[w] = sum;
+    __syncthreads();
+    if (threadIdx.x == 0) a.partial[blockIdx.x] = ((l.red[0] + l.red[1]) + l.red[2]) + l.red[3];
+}
+
+// items[b] = (sum of item b's partials, ascending) / (C H W); value = (sum of the item sums, b ascending) / (N H W)
+__global__ void __launch_bounds__(kSsimThreads) ssim_finish_kernel(const double* __restrict__ partial, int B, int per_item, double inv_item,
+                                                                  double inv_all, float* __restrict__ value, float* __restrict__ items) {
+    __shared__ double s[kSsimThreads];
+    double total = 0.0;
+    for (int base = 0; base < B; base += kSsimThreads) {
+        const int b = base + threadIdx.x;
+        double acc = 0.0;
+        if (b < B) {
+            const double* p = partial + (long)b * per_item;
+            for (int i = 0; i < per_item; ++i) acc += p[i];
+            if (items) items[b] = (float)(acc * inv_item);
+        }
+        s[threadIdx.x] = acc;
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            const int m = B - base < kSsimThreads ? B - base : kSsimThreads;
+            for (int i = 0; i < m; ++i) total += s[i];
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0 && value) value[0] = (float)(total * inv_all);
+}
+
+struct SsimBwdK {
+    SsimImage x, y, dx, dy;       // canonical orientation; dx.p, dy.p nullable
+    const double* coef;
+    const float* taps;
+    const float* grad;            // [1] or [B]
+    double inv_count;             // 1 / (N H W), or 1 / (C H W) with per-item weights
+    long nhw;
+    int need, per_item, C, H, W, tiles_w, tiles, ws;
+};
+
+template <int WS>
+__global__ void __launch_bounds__(kSsimThreads) ssim_bwd_kernel(const SsimBwdK a) {
+    extern __shared__ double ssim_smem[];
+    const int ws = WS ? WS : a.ws;
+    const SsimLds l = ssim_lds(ssim_smem, ws);
+    const int tile = blockIdx.x % a.tiles;
+    const long n = blockIdx.x / a.tiles;
+    const int r0 = tile / a.tiles_w * kSsimTileH, c0 = tile % a.tiles_w * kSsimTileW;
+    if (threadIdx.x < ws) l.taps[threadIdx.x] = (double)a.taps[threadIdx.x];
+    double f[4][kSsimRowsPerThread];
+#pragma unroll
+    for (int slot = 0; slot < 4; ++slot) {
+        if (slot == 3 && a.need != 3) {
+#pragma unroll
+            for (int o = 0; o < kSsimRowsPerThread; ++o) f[3][o] = 0.0;
+            continue;
+        }
+        double* sd = reinterpret_cast<double*>(l.sa);
+        ssim_stage<double>(sd, a.coef + slot * a.nhw + n * a.H * (long)a.W, a.W, 1, r0, c0, a.H, a.W, l);
+        __syncthreads();
+        ssim_rows<WS, false>(l, sd, sd, ws);
+        __syncthreads();
+        ssim_cols<WS>(f[slot], l, ws);
+        __syncthreads();
+    }
+    const int lane = threadIdx.x & (kWave - 1), w = threadIdx.x / kWave;
+    const int gc = c0 + lane;
+    const double g = (double)a.grad[a.per_item ? n / a.C : 0] * a.inv_count;
+#pragma unroll
+    for (int o = 0; o < kSsimRowsPerThread; ++o) {
+        const int gr = r0 + w * kSsimRowsPerThread + o;
+        if (gr >= a.H || gc >= a.W) continue;
+        const double xv = (double)a.x.p[n * a.x.sn + (long)gr * a.x.sr + (long)gc * a.x.sc];
+        const double yv = (double)a.y.p[n * a.y.sn + (long)gr * a.y.sr + (long)gc * a.y.sc];
+        const double fb = f[1][o], fc = f[2][o];
+        if (a.dx.p) a.dx.p[n * a.dx.sn + (long)gr * a.dx.sr + (long)gc * a.dx.sc] = (float)(g * (f[0][o] + 2.0 * xv * fb + yv * fc));
+        if (a.dy.p) {
+            const double fq = a.need == 3 ? f[3][o] : f[0][o];
+            a.dy.p[n * a.dy.sn + (long)gr * a.dy.sr + (long)gc * a.dy.sc] = (float)(g * (fq + 2.0 * yv * fb + xv * fc));
+        }
+    }
+}
+
+// ------------------------------------------------------------------------------------------------------------------
+// launchers
+// ------------------------------------------------------------------------------------------------------------------
+static bool ssim_inner_ok(const SsimImage& im, int H, int W) { return im.sc == 1 || W == 1 || im.sr == 1 || H == 1; }
+// The lane axis: W where x is contiguous along it, else H (the launcher then swaps the two axes of every image).
+static bool ssim_lane_is_h(const SsimImage& x, int H, int W) { return !(x.sc == 1 && W > 1) && x.sr == 1 && H > 1; }
+static SsimImage ssim_swapped(SsimImage im) { const long t = im.sr; im.sr = im.sc; im.sc = t; return im; }
+
+int ssim_fwd(const SsimFwd& a, hipStream_t s) {
+    SsimPlan p;
+    T2_TRY_RC(ssim_plan((long)a.B * a.C, a.H, a.W, a.ws, a.need_grad, &p));
+    T2_REQUIRE(a.B >= 1 && a.C >= 1, "ssim_forward: B=%d and C=%d must be at least 1", a.B, a.C);
+    T2_REQUIRE(a.x.p && a.y.p, "ssim_forward: x and y must not be null");
+    T2_REQUIRE(a.taps, "ssim_forward: taps must not be null");
+    T2_REQUIRE(a.partial, "ssim_forward: partial (the plan's partial_bytes of scratch) must not be null");
+    T2_REQUIRE(a.value || a.items || a.map.p, "ssim_forward: value, items and map are all null");
+    T2_REQUIRE(!a.need_grad || a.coef, "ssim_forward: need_grad=%d needs coef (the plan's map_bytes of scratch)", a.need_grad);
+    T2_REQUIRE(ssim_inner_ok(a.x, a.H, a.W), "ssim_forward: x has row stride %ld and column stride %ld: one of them must be 1", a.x.sr, a.x.sc);
+    T2_REQUIRE(ssim_inner_ok(a.y, a.H, a.W), "ssim_forward: y has row stride %ld and column stride %ld: one of them must be 1", a.y.sr, a.y.sc);
+    const bool swap = ssim_lane_is_h(a.x, a.H, a.W);
+    SsimFwdK k;
+    k.x = swap ? ssim_swapped(a.x) : a.x; k.y = swap ? ssim_swapped(a.y) : a.y; k.map = swap ? ssim_swapped(a.map) : a.map;
+    k.H = swap ? a.W : a.H; k.W = swap ? a.H : a.W;
+    k.coef = a.coef; k.taps = a.taps; k.partial = a.partial; k.need = a.need_grad; k.ws = a.ws;
+    k.nhw = (long)a.B * a.C * a.H * a.W;
+    k.tiles_w = (k.W + kSsimTileW - 1) / kSsimTileW;
+    k.tiles = k.tiles_w * ((k.H + kSsimTileH - 1) / kSsimTileH);
+    const long blocks = (long)a.B * a.C * k.tiles;                      // = partials or partials_t of the plan
+    const size_t smem = p.lds_fwd_bytes;
+    if (a.ws == 11) ssim_fwd_kernel<11><<<dim3((unsigned)blocks), dim3(kSsimThreads), smem, s>>>(k);
+    else ssim_fwd_kernel<0><<<dim3((unsigned)blocks), dim3(kSsimThreads), smem, s>>>(k);
+    T2_LAUNCH_CHECK();
+    if (a.value || a.items) {
+        const double chw = (double)a.C * a.H * a.W;
+        ssim_finish_kernel<<<dim3(1), dim3(kSsimThreads), 0, s>>>(a.partial, a.B, a.C * k.tiles, 1.0 / chw, 1.0 / (chw * a.B), a.value, a.items);
+        T2_LAUNCH_CHECK();
+    }
+    return 0;
+}
+
+int ssim_bwd(const SsimBwd& a, hipStream_t s) {
+    SsimPlan p;
+    T2_TRY_RC(ssim_plan((long)a.B * a.C, a.H, a.W, a.ws, a.need_grad, &p));
+    T2_REQUIRE(a.B >= 1 && a.C >= 1, "ssim_backward: B=%d and C=%d must be at least 1", a.B, a.C);
+    T2_REQUIRE(a.x.p && a.y.p, "ssim_backward: x and y must not be null");
+    T2_REQUIRE(a.taps, "ssim_backward: taps must not be null");
+    T2_REQUIRE(a.need_grad && a.coef, "ssim_backward: needs the coef a forward call with need_grad != 0 stored");
+    T2_REQUIRE(a.grad, "ssim_backward: grad must not be null");
+    T2_REQUIRE(a.dx.p || a.dy.p, "ssim_backward: dx and dy are both null");
+    T2_REQUIRE(!a.dx.p || (a.need_grad & 1), "ssim_backward: dx asked, but the forward ran with need_grad=%d", a.need_grad);
+    T2_REQUIRE(!a.dy.p || (a.need_grad & 2), "ssim_backward: dy asked, but the forward ran with need_grad=%d", a.need_grad);
+    T2_REQUIRE(ssim_inner_ok(a.x, a.H, a.W), "ssim_backward: x has row stride %ld and column stride %ld: one of them must be 1", a.x.sr, a.x.sc);
+    T2_REQUIRE(ssim_inner_ok(a.y, a.H, a.W), "ssim_backward: y has row stride %ld and column stride %ld: one of them must be 1", a.y.sr, a.y.sc);
+    const bool swap = ssim_lane_is_h(a.x, a.H, a.W);                    // the forward's choice: coef is in that orientation
+    SsimBwdK k;
+    k.x = swap ? ssim_swapped(a.x) : a.x; k.y = swap ? ssim_swapped(a.y) : a.y;
+    k.dx = swap ? ssim_swapped(a.dx) : a.dx; k.dy = swap ? ssim_swapped(a.dy) : a.dy;
+    k.H = swap ? a.W : a.H; k.W = swap ? a.H : a.W;
+    k.coef = a.coef; k.taps = a.taps; k.grad = a.grad; k.need = a.need_grad; k.ws = a.ws; k.per_item = a.per_item; k.C = a.C;
+    const double chw = (double)a.C * a.H * a.W;
+    k.inv_count = 1.0 / (a.per_item ? chw : chw * a.B);
+    k.nhw = (long)a.B * a.C * a.H * a.W;
+    k.tiles_w = (k.W + kSsimTileW - 1) / kSsimTileW;
+    k.tiles = k.tiles_w * ((k.H + kSsimTileH - 1) / kSsimTileH);
+    const long blocks = (long)a.B * a.C * k.tiles;
+    const size_t smem = p.lds_bwd_bytes;
+    if (a.ws == 11) ssim_bwd_kernel<11><<<dim3((unsigned)blocks), dim3(kSsimThreads), smem, s>>>(k);
+    else ssim_bwd_kernel<0><<<dim3((unsigned)blocks), dim3(kSsimThreads), smem, s>>>(k);
+    T2_LAUNCH_CHECK();
+    return 0;
+}
+
+}  // namespace t2

@@ -26,7 +26,7 @@ _DEFAULTS = dict(
     max_wav_value=32768.0, sampling_rate=22050, filter_length=1024, hop_length=256, win_length=1024,
     n_mel_channels=80, mel_fmin=0.0, mel_fmax=8000.0,
     # model (hparams.py:62-95)
-    n_symbols=313, sub_n_symbols=5500, symbols_embedding_dim=512, alignloss="", attention="StepwiseMonotonicAttention",
+    n_symbols=313, sub_n_symbols=5500, symbols_embedding_dim=512, alignloss="", ssim_weight=0.0, attention="StepwiseMonotonicAttention",
     encoder_kernel_size=5, encoder_n_convolutions=3, encoder_embedding_dim=512, BERT_embedding_dim=768,
     n_frames_per_step=1, decoder_rnn_dim=1024, prenet_dim=256, max_decoder_steps=1000, gate_threshold=0.001,
     p_attention_dropout=0.1, p_decoder_dropout=0.1, attention_rnn_dim=1024, attention_dim=128,

@@ -10,16 +10,26 @@ The reference's quirks are kept because callers can observe them:
     uses max_input_len for item 0 and max_output_len for item 1;
   * KL replaces exact zeros by 1e-6.  The reference does that in place on the model outputs and on the target; here
     the edit is made on copies (same loss, same gradients) because the decoder's alignment buffer doubles as the
-    saved recurrent state of the HIP backward."""
+    saved recurrent state of the HIP backward.
+
+ssim_weight > 0 switches on the term the reference keeps one commented line away (loss_function.py:10,24):
+ssim_loss = -SSIM(11, True)(mel_out.unsqueeze(1), mel_target.unsqueeze(1)), on mel_out only, added to the total as
+ssim_weight * ssim_loss; the detached term is left in self.ssim_loss for logging.  With the default 0.0 nothing is
+constructed or launched."""
 import torch
 from torch import nn
 from torch.nn import functional as F
 
 
 class Tacotron2Loss(nn.Module):
-    def __init__(self, alignloss=""):
+    def __init__(self, alignloss="", ssim_weight=0.0):
         super().__init__()
         self.alignloss = alignloss
+        self.ssim_weight = float(ssim_weight)
+        self.ssim_loss = None
+        if self.ssim_weight > 0:
+            from .ssim import SSIM
+            self.ssim = SSIM(window_size=11, size_average=True)
 
     def forward(self, model_output, targets, x=None, iters=0):
         mel_target, gate_target = targets[0], targets[1]
@@ -49,4 +59,8 @@ class Tacotron2Loss(nn.Module):
         total = mel_loss + gate_loss
         if align_loss is not None:
             total = total + align_loss + align_bert_loss
+        if self.ssim_weight > 0:
+            ssim_loss = -self.ssim(mel_out.unsqueeze(1), mel_target.unsqueeze(1))
+            total = total + self.ssim_weight * ssim_loss
+            self.ssim_loss = ssim_loss.detach()
         return total, mel_loss, gate_loss, align_loss, align_bert_loss

@@ -146,5 +146,5 @@ def make_training_objects(hparams):
     model = load_model(hparams)
     # train.py:210-211 builds torch.optim.Adam(lr, weight_decay); FusedAdam is that optimizer with a HIP step()
     optimizer = FusedAdam(model.parameters(), lr=hparams.learning_rate, weight_decay=hparams.weight_decay)
-    criterion = Tacotron2Loss(hparams.alignloss)
+    criterion = Tacotron2Loss(hparams.alignloss, ssim_weight=getattr(hparams, "ssim_weight", 0.0))
     return model, optimizer, criterion
