@@ -423,7 +423,9 @@ typedef struct t2_lstm_seq_bwd_args {
 int t2_lstm_seq_backward(const t2_lstm_seq_bwd_args* a, void* stream);
 
 /* General GEMM with the full descriptor (see t2_gemm); crow_mod/crow_mul permute output rows:
- * row m is written to (m % crow_mod) * crow_mul + m / crow_mod (0 = identity). */
+ * row m is written to (m % crow_mod) * crow_mul + m / crow_mod (0 = identity).
+ * act: 0 none, 1 relu, 2 tanh, 3 gelu (the exact form 0.5 x (1 + erf(x / sqrt 2)), forward only: the conv / BatchNorm
+ * layers above take 0..2); any other value is refused. */
 typedef struct t2_gemm_args {
     const float* A; const float* B; float* C; int M, N, K;
     long sam, sak, sbn, sbk, ldc; int batch; long bsA, bsB, bsC;
@@ -662,6 +664,79 @@ typedef struct t2_ssim_bwd_args {
     const float* grad;        /* [1], or [B] with per_item */
 } t2_ssim_bwd_args;
 int t2_ssim_backward(const t2_ssim_bwd_args* a, void* stream);
+
+/* ---- BERT sentence encoder (text ids -> [CLS] vector) -----------------------------------------------
+ * Replaces the CPU forward behind the reference's data_utils.py: get_embedding_cls (:28-46): BertModel (embeddings,
+ * `layers` post-LayerNorm transformer layers, last hidden state; the pooler is not part of it), inference only.  What is
+ * computed is BertModel(input_ids, attention_mask = the sentence's own tokens, token_type_ids = 0): every token attends
+ * to every token of its own sentence (INTEGRATION.md says why this and not the positional call as the installed
+ * transformers release reads it).  Exact fp32 on the matrix cores, whatever t2_set_precision says.
+ *
+ * A ragged batch is packed, not padded: token rows [total, hidden] addressed through cu_seqlens [B+1] (int32, device;
+ * cu_seqlens[0] = 0, cu_seqlens[B] = total).  No mask tensor exists; keys beyond a sentence's length are never read.
+ * Sums are taken in a fixed order without atomics, and a sentence's result does not depend on its place in the batch.
+ * The kernels do not check ids against the tables: callers validate 0 <= id < vocab on the host (bert.py does).
+ *
+ * Packed weights, one device buffer of packed_floats floats, made by t2_bert_pack from 5 + 16 * layers device tensors in
+ * this order (state-dict names, row-major [out, in] matrices as torch keeps them):
+ *   embeddings.word_embeddings.weight [vocab, H], embeddings.position_embeddings.weight [max_pos, H],
+ *   embeddings.token_type_embeddings.weight [type_vocab, H], embeddings.LayerNorm.weight, embeddings.LayerNorm.bias,
+ *   then per layer i (encoder.layer.i.): attention.self.query.weight, .bias, attention.self.key.weight, .bias,
+ *   attention.self.value.weight, .bias, attention.output.dense.weight, .bias, attention.output.LayerNorm.weight, .bias,
+ *   intermediate.dense.weight [I, H], .bias, output.dense.weight [H, I], .bias, output.LayerNorm.weight, .bias.
+ * Query, key and value are stored as one [3H, H] matrix with a [3H] bias. */
+typedef struct t2_bert_config {
+    int hidden, layers, heads, intermediate, vocab, max_pos, type_vocab;
+    float ln_eps;             /* 1e-12 for BERT: the LayerNorms centre before they square */
+} t2_bert_config;
+typedef struct t2_bert_plan_info {
+    size_t packed_floats;     /* the packed weight buffer */
+    size_t workspace_bytes;   /* residual stream, fused QKV rows, context rows, FFN rows; the [B, .] rows of the CLS tail */
+    int launches;             /* kernel launches of one forward call, each product counted as one */
+} t2_bert_plan_info;
+/* Pure (no device).  cls_only: the forward will be called without out_hidden, so the last layer runs its query
+ * projection, attention, output projection, FFN and LayerNorms for the B [CLS] rows only.  Fails, naming the argument,
+ * for a head dimension other than 64, hidden not a multiple of 64 or above 1024, intermediate not a multiple of 64,
+ * max_len outside 1..min(512, max_pos), B < 1, and total_tokens outside B..B*max_len. */
+int t2_bert_plan(const t2_bert_config* cfg, int B, long total_tokens, int max_len, int cls_only, t2_bert_plan_info* out);
+int t2_bert_pack(const t2_bert_config* cfg, const float* const* tensors_dev, int n_tensors, float* packed, void* stream);
+typedef struct t2_bert_fwd_args {
+    int B; int total_tokens; int max_len;   /* max_len: an upper bound of every sentence's length (sizes grids and LDS) */
+    const float* packed;
+    const int32_t* ids;                     /* [total_tokens] */
+    const int32_t* cu_seqlens;              /* [B + 1] */
+    float* out_hidden;                      /* [total_tokens, H] last hidden state, or NULL: the CLS-only last layer */
+    float* out_cls;                         /* [B, H] row cu_seqlens[b] of the last hidden state; NULL only with out_hidden */
+    void* ws; size_t ws_bytes;              /* workspace_bytes of the plan with cls_only = (out_hidden == NULL) */
+} t2_bert_fwd_args;
+int t2_bert_forward(const t2_bert_config* cfg, const t2_bert_fwd_args* a, void* stream);
+/* The kernels one by one (tests).  out[row] = LayerNorm(word[ids[row]] + type[0] + pos[row - cu_seqlens[b]]) for the rows
+ * of sentence b; one wave per row, H a multiple of 64 up to 1024. */
+typedef struct t2_bert_embed_ln_args {
+    int B, total_tokens, max_len, H; float eps;
+    const int32_t* ids; const int32_t* cu_seqlens;
+    const float* word; const float* pos; const float* type; const float* ln_w; const float* ln_b;
+    float* out;                             /* [total_tokens, H] */
+} t2_bert_embed_ln_args;
+int t2_bert_embed_ln(const t2_bert_embed_ln_args* a, void* stream);
+/* out[row] = LayerNorm(x[row]) over H, rows [rows, H] contiguous; out == x runs in place. */
+typedef struct t2_bert_layernorm_args {
+    int rows, H; float eps;
+    const float* x; const float* ln_w; const float* ln_b; float* out;
+} t2_bert_layernorm_args;
+int t2_bert_layernorm(const t2_bert_layernorm_args* a, void* stream);
+/* out = softmax(Q K^T / 8) V per sentence and head, head dimension 64, sentence lengths 1..max_len <= 512.  q, k, v: the
+ * first element of head 0 in row 0, row strides ldq, ldk, ldv in floats (multiples of 4, pointers 16-byte aligned): the
+ * fused rows [total, 3H] are q = qkv, k = qkv + H, v = qkv + 2H, all with stride 3H.  nq_first_only == 0: q holds the
+ * packed rows, out [total, ldo] too.  nq_first_only != 0: one query per sentence; q holds B rows (row b = the query of
+ * sentence b, against the keys and values of the packed rows) and out is [B, ldo]. */
+typedef struct t2_bert_attention_args {
+    int B, heads, total_tokens, max_len, nq_first_only;
+    const float* q; const float* k; const float* v; long ldq, ldk, ldv;
+    const int32_t* cu_seqlens;
+    float* out; long ldo;
+} t2_bert_attention_args;
+int t2_bert_attention(const t2_bert_attention_args* a, void* stream);
 
 /* ---- HiFi-GAN generator (mel spectrogram -> waveform) ----------------------------------------------
  * Replaces the reference's hifigan_infer/hifigan_model.py: Generator.forward (:100-116), ResBlock1.forward (:35-42),

@@ -259,6 +259,37 @@ class SsimBwdArgs(C.Structure):
 _I6 = C.c_int * 6
 
 
+class BertConfig(C.Structure):
+    _fields_ = [("hidden", C.c_int), ("layers", C.c_int), ("heads", C.c_int), ("intermediate", C.c_int), ("vocab", C.c_int),
+                ("max_pos", C.c_int), ("type_vocab", C.c_int), ("ln_eps", C.c_float)]
+
+
+class BertPlanInfo(C.Structure):
+    _fields_ = [("packed_floats", C.c_size_t), ("workspace_bytes", C.c_size_t), ("launches", C.c_int)]
+
+
+class BertFwdArgs(C.Structure):
+    _fields_ = [("B", C.c_int), ("total_tokens", C.c_int), ("max_len", C.c_int), ("packed", C.c_void_p), ("ids", C.c_void_p),
+                ("cu_seqlens", C.c_void_p), ("out_hidden", C.c_void_p), ("out_cls", C.c_void_p), ("ws", C.c_void_p), ("ws_bytes", C.c_size_t)]
+
+
+class BertEmbedLnArgs(C.Structure):
+    _fields_ = [("B", C.c_int), ("total_tokens", C.c_int), ("max_len", C.c_int), ("H", C.c_int), ("eps", C.c_float),
+                ("ids", C.c_void_p), ("cu_seqlens", C.c_void_p), ("word", C.c_void_p), ("pos", C.c_void_p), ("type", C.c_void_p),
+                ("ln_w", C.c_void_p), ("ln_b", C.c_void_p), ("out", C.c_void_p)]
+
+
+class BertLayernormArgs(C.Structure):
+    _fields_ = [("rows", C.c_int), ("H", C.c_int), ("eps", C.c_float), ("x", C.c_void_p), ("ln_w", C.c_void_p), ("ln_b", C.c_void_p),
+                ("out", C.c_void_p)]
+
+
+class BertAttentionArgs(C.Structure):
+    _fields_ = [("B", C.c_int), ("heads", C.c_int), ("total_tokens", C.c_int), ("max_len", C.c_int), ("nq_first_only", C.c_int),
+                ("q", C.c_void_p), ("k", C.c_void_p), ("v", C.c_void_p), ("ldq", C.c_long), ("ldk", C.c_long), ("ldv", C.c_long),
+                ("cu_seqlens", C.c_void_p), ("out", C.c_void_p), ("ldo", C.c_long)]
+
+
 class HifiganConfig(C.Structure):
     _fields_ = [("resblock", C.c_int), ("n_mel", C.c_int), ("upsample_initial_channel", C.c_int),
                 ("num_upsamples", C.c_int), ("upsample_rates", _I6), ("upsample_kernel_sizes", _I6),
@@ -451,6 +482,7 @@ EXPORTS = ["t2_last_error", "t2_version", "t2_chain_status", "t2_chain_status_cl
            "t2_finalize_bct", "t2_mask_bt", "t2_gemm", "t2_rng_keep_mask", "t2_rng_normal",
            "t2_softdtw_plan", "t2_softdtw_dist", "t2_softdtw_forward", "t2_softdtw_backward", "t2_softdtw_dist_backward",
            "t2_ssim_plan", "t2_ssim_forward", "t2_ssim_backward",
+           "t2_bert_plan", "t2_bert_pack", "t2_bert_forward", "t2_bert_embed_ln", "t2_bert_layernorm", "t2_bert_attention",
            "t2_hifigan_plan", "t2_hifigan_pack", "t2_hifigan_forward", "t2_vocoder_packed_floats", "t2_vocoder_conv1d", "t2_vocoder_conv_transpose1d",
            "t2_stft_plan", "t2_stft_pack", "t2_stft_analysis", "t2_stft_synthesis", "t2_melspec_plan", "t2_melspec_pack", "t2_melspec",
            "t2_waveglow_plan", "t2_waveglow_pack", "t2_waveglow_infer", "t2_waveglow_packed_floats", "t2_waveglow_gated_conv", "t2_waveglow_res_skip",
@@ -522,6 +554,12 @@ def lib() -> C.CDLL:
         L.t2_ssim_plan.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(SsimPlanInfo)]
         L.t2_ssim_forward.argtypes = [C.POINTER(SsimFwdArgs), C.c_void_p]
         L.t2_ssim_backward.argtypes = [C.POINTER(SsimBwdArgs), C.c_void_p]
+        L.t2_bert_plan.argtypes = [C.POINTER(BertConfig), C.c_int, C.c_long, C.c_int, C.c_int, C.POINTER(BertPlanInfo)]
+        L.t2_bert_pack.argtypes = [C.POINTER(BertConfig), C.POINTER(C.c_void_p), C.c_int, C.c_void_p, C.c_void_p]
+        L.t2_bert_forward.argtypes = [C.POINTER(BertConfig), C.POINTER(BertFwdArgs), C.c_void_p]
+        L.t2_bert_embed_ln.argtypes = [C.POINTER(BertEmbedLnArgs), C.c_void_p]
+        L.t2_bert_layernorm.argtypes = [C.POINTER(BertLayernormArgs), C.c_void_p]
+        L.t2_bert_attention.argtypes = [C.POINTER(BertAttentionArgs), C.c_void_p]
         L.t2_hifigan_plan.argtypes = [C.POINTER(HifiganConfig), C.c_int, C.c_int, C.POINTER(HifiganPlanInfo)]
         L.t2_hifigan_pack.argtypes = [C.POINTER(HifiganConfig), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_int, C.c_void_p, C.c_void_p]
         L.t2_hifigan_forward.argtypes = [C.POINTER(HifiganConfig), C.POINTER(HifiganFwdArgs), C.c_void_p]
@@ -953,6 +991,21 @@ def ssim_forward(args: SsimFwdArgs) -> None:
 
 def ssim_backward(args: SsimBwdArgs) -> None:
     check(lib().t2_ssim_backward(C.byref(args), stream()))
+
+
+def bert_config(cfg) -> BertConfig:
+    """t2_bert_config from a transformers BertConfig or a dict with its field names."""
+    g = (lambda k, d=None: cfg.get(k, d)) if isinstance(cfg, dict) else (lambda k, d=None: getattr(cfg, k, d))
+    return BertConfig(int(g("hidden_size")), int(g("num_hidden_layers")), int(g("num_attention_heads")), int(g("intermediate_size")),
+                      int(g("vocab_size")), int(g("max_position_embeddings")), int(g("type_vocab_size", 2)), float(g("layer_norm_eps", 1e-12)))
+
+
+def bert_plan(cfg: BertConfig, B: int, total_tokens: int, max_len: int, cls_only: bool = True) -> BertPlanInfo:
+    """Packed-weight floats, workspace bytes and launch count of an encoder call (t2_bert_plan: pure host, no device needed);
+    raises with the library's message for a configuration or a batch it refuses."""
+    info = BertPlanInfo()
+    check(lib().t2_bert_plan(C.byref(cfg), B, total_tokens, max_len, int(cls_only), C.byref(info)))
+    return info
 
 
 def hifigan_config(h) -> HifiganConfig:

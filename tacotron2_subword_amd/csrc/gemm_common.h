@@ -29,6 +29,7 @@ int launch_gemm_bf16src(const GemmK& g, GemmKernel kernel, const __bf16* pa, lon
 __device__ __forceinline__ float apply_act(float v, int act) {
     if (act == ACT_RELU) return fmaxf(v, 0.f);
     if (act == ACT_TANH) return tanhf(v);
+    if (act == ACT_GELU) return 0.5f * v * (1.0f + erff(v * 0.70710678118654752440f));
     return v;
 }
 

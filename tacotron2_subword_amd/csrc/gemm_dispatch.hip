@@ -69,6 +69,7 @@ inline size_t round256(size_t n) { return (n + 255) & ~(size_t)255; }
 
 int check_gemm(const GemmDesc& d) {
     T2_REQUIRE(d.M > 0 && d.N > 0 && d.K > 0 && d.batch > 0, "gemm: bad shape M=%d N=%d K=%d batch=%d", d.M, d.N, d.K, d.batch);
+    T2_REQUIRE(d.act >= ACT_NONE && d.act <= ACT_GELU, "gemm: unknown activation act=%d (0 none, 1 relu, 2 tanh, 3 gelu)", d.act);
     if (d.conv_a || d.conv_b) {
         T2_REQUIRE(d.conv_T > 0 && d.conv_C > 0 && d.conv_C % 4 == 0 && !(d.conv_a && d.conv_b), "gemm: bad implicit-conv operand (T=%d C=%d)", d.conv_T, d.conv_C);
         T2_REQUIRE(d.batch == 1, "gemm: implicit-conv operands need batch == 1");

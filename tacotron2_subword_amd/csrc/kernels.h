@@ -7,7 +7,7 @@
 namespace t2 {
 
 // ------------------------------------------------------------------ GEMM (gemm_dispatch.hip; kernels: gemm_f32.hip, gemm_bf16conv.hip, gemm.hip)
-enum Act : int { ACT_NONE = 0, ACT_RELU = 1, ACT_TANH = 2 };
+enum Act : int { ACT_NONE = 0, ACT_RELU = 1, ACT_TANH = 2, ACT_GELU = 3 };   // GELU: the exact form, 0.5 x (1 + erf(x / sqrt 2))
 
 struct GemmDesc {
     const float* A; const float* B; float* C;

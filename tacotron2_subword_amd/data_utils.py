@@ -312,3 +312,65 @@ def batch_to_device(data_of_batch, device="cuda"):
         hm = (int(max(np.max(np.asarray(raw("length_text"))), np.max(np.asarray(raw("length_bert"))))), int(np.max(np.asarray(raw("length_mel")))))
     out.host_max = (int(hm[0]), int(hm[1]))
     return out
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# Text -> the model's BERT inputs (data_utils.py:15-46 of the reference).  A BertEncoder (bert.py), or a BertModel whose
+# parameters are on the GPU, takes the HIP path: the whole encoder runs on the device, a batch of sentences in one call.
+# A CPU BertModel runs as the reference ran it, with the arguments by keyword: the reference passes the all-zero segment
+# ids positionally, where every transformers release takes `attention_mask`; releases of its time turned that into a
+# uniform shift of the scores (ordinary full attention), the current ones into uniform attention weights.  Full attention
+# over the sentence's own tokens with token_type_ids = 0 is what was meant and what both paths here compute
+# (INTEGRATION.md).  transformers is not imported: the model and the tokenizer are the caller's.
+# ---------------------------------------------------------------------------------------------------------------
+def add_cls_sep(text):
+    return "[CLS] " + text + " [SEP]"
+
+
+def _strip_en(text):
+    return text.replace("<en>", "").replace("</en>", "")
+
+
+def get_embedding(text, bert_model, tokenizer):
+    """data_utils.py:18-26: the sub-word ids of a `tokenizers.Tokenizer` without its first and last (special) token."""
+    return torch.IntTensor(tokenizer.encode(_strip_en(text)).ids[1:-1])
+
+
+def _cls_ids(text, tokenizer):
+    return tokenizer.convert_tokens_to_ids(tokenizer.tokenize(add_cls_sep(_strip_en(text))))
+
+
+def _hip_encoder(bert_model):
+    """The BertEncoder behind bert_model, or None for a CPU BertModel.  Built once per model and kept on it as
+    `_t2_bert_encoder`: the packed copy does not follow later changes of the model's weights (delete the attribute then)."""
+    from .bert import BertEncoder
+    if isinstance(bert_model, BertEncoder):
+        return bert_model
+    if not next(bert_model.parameters()).is_cuda:
+        return None
+    enc = getattr(bert_model, "_t2_bert_encoder", None)
+    if enc is None:
+        enc = BertEncoder.from_model(bert_model)
+        bert_model._t2_bert_encoder = enc
+    return enc
+
+
+def get_embedding_cls_batch(texts, bert_model, tokenizer):
+    """[B, H]: the [CLS] vectors of a list of sentences in one forward, on the model's device."""
+    ids = [_cls_ids(t, tokenizer) for t in texts]
+    enc = _hip_encoder(bert_model)
+    if enc is not None:
+        return enc.cls(ids)
+    n = max(len(s) for s in ids)
+    tok = torch.zeros(len(ids), n, dtype=torch.long)
+    mask = torch.zeros(len(ids), n, dtype=torch.long)
+    for b, s in enumerate(ids):
+        tok[b, :len(s)] = torch.tensor(s)
+        mask[b, :len(s)] = 1
+    with torch.no_grad():
+        return bert_model(input_ids=tok, attention_mask=mask, token_type_ids=torch.zeros_like(tok))[0][:, 0]
+
+
+def get_embedding_cls(text, bert_model, tokenizer):
+    """data_utils.py:28-46: the [CLS] vector of one sentence, [1, H] on the model's device."""
+    return get_embedding_cls_batch([text], bert_model, tokenizer)
