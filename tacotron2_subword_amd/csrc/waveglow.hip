@@ -6,700 +6,15 @@
 // exp(s) * a1 + b, the early-output split, the next flow's W, fp64 partial sums of s and z^2) and two small kernels that finish
 // the sums in a fixed order.  log |det W_k| comes from an fp64 LU, once per set of weights.
 //
-// Activations are [B][C][L] with time contiguous, L = T*256/n_group; arithmetic is exact fp32 on the matrix cores
-// (v_mfma_f32_32x32x2_f32), whatever t2_set_precision says.  Three of the five kernels are one GEMM kernel in the style of
-// vocoder.hip (lanes along time, a slab [16 channels][128 + halo] of the operand in LDS, weights packed once into the order the
-// lanes read them, a wave computing 32 rows x 64 columns), with three epilogues:
-//   gated conv   Y = tanh(U[:nc]) * sigmoid(U[nc:]),  U = in_layers[i](x) + cond_layer(spect)[2nc*i : 2nc*(i+1)] as ONE GEMM with
-//                K = 3*nc (the taps read x at -d, 0, +d from the slab) + n_mel*G (spect at the same column).  Tanh row c and
-//                sigmoid row c + nc are two accumulators of the same wave: same lane, same element, same column, so the gate is
-//                applied in registers and only [B, nc, L] is written.  The conditioning tensor [B, 2*nc*n_layers, L] never exists.
-//   res_skip     the 1x1 conv; its epilogue does x += rs[:nc] and out += rs[nc:] in place (acts is a buffer of its own).
-//   upsample     ConvTranspose1d(n_mel, n_mel, 1024, stride 256) as a polyphase GEMM: output sample 256q + r reads taps r + 256m
-//                (m = 0..3) of frames q - m, so rows = (channel, phase r), columns = frames q, K = n_mel * 4; the epilogue writes
-//                spect[b, ch*G + g, l] at 256q + r = l*G + g.  Each element once.  Inference never computes the 768 trailing
-//                samples; the forward direction, whose audio may reach into them, asks for up to three more columns q.
-// `start` (K <= 4) and the coupling (end: <= 8 rows reduced over nc with lanes along time, then (a1 - b)/exp(s), the c x c inverse
-// mix and the early-noise prepend in one pass) are plain VALU.  No atomics, every sum in a fixed order, 64-bit element offsets.
-//
 // Training (waveglow/train.py:125-137): the forward direction with the activations the backward reads kept in a caller-owned
-// buffer (per flow audio_in and out, per layer x_i, tanh(u_a), sigmoid(u_b): one more store in the gated epilogue, a separate
-// destination in res_skip's), and the backward.  Its data gradients are the same GEMM kernel on transposed packs with two more
-// epilogues (gate backward: W_rs^T [dx; d_out] times the gate's derivative from the kept halves; accumulate: dx += conv^T(du),
-// d_spect += W_cond^T du); its weight gradients are a second GEMM, wg_wgrad_kernel, whose reduction runs along time and is split
-// over (item, time chunk) into partial planes added in a fixed order; the tail, start, head and upsample backward are VALU.
-#include <algorithm>
-#include <vector>
-
-#include "../../include/t2amd.h"
-#include "kernels.h"
+// buffer (per flow audio_in and out, per layer x_i, tanh(u_a), sigmoid(u_b)), and the backward.
+//
+// Here: the drivers and the C ABI.  A driver takes its plan, checks the pointers, places its buffers from the plan's carve and
+// runs the launch sequence, every launch through WG_RUN.  The kernels and their launchers are in waveglow_kernels.hip; the tensor
+// table, the layouts, the carves, the weight-gradient descriptor and the plans in waveglow_plan.hip.
+#include "waveglow.h"
 
 namespace t2 {
-
-constexpr int kWgCK = 16;                         // operand channels per slab
-constexpr int kWgMaxD = 128;                      // dilation of layer 7
-constexpr int kWgStride = 416;                    // slab row stride in floats: = 32 mod 64 banks, >= kVocTT + 2*kWgMaxD
-static_assert(kWgStride % 64 == 32 && kWgStride >= kVocTT + 2 * kWgMaxD, "slab row stride");
-static_assert(T2_WAVEGLOW_MAX_LAYERS == 8 && (1 << (T2_WAVEGLOW_MAX_LAYERS - 1)) == kWgMaxD, "the deepest layer's dilation fits the slab");
-enum { kWgGated = 0, kWgResSkip = 1, kWgUpsample = 2, kWgGateBwd = 3, kWgAccum = 4 };   // the last two: epilogues of the backward (below)
-constexpr int kWgUpK = 1024, kWgUpStride = 256, kWgUpTaps = kWgUpK / kWgUpStride;
-
-// Y[row][q] = sum over segment 0 (C0 channels x taps, tap j at slab column q + coff0 + j*cstep) and segment 1 (C1 channels, one
-// tap at q) of packed weight x operand.  N = columns (row length of both operands and, but for the upsample, of the output).
-struct WgGemm {
-    const float* x0; const float* x1; const float* wp; const float* bias0; const float* bias1;
-    float* y0; float* y1;
-    int C0, C1, N;
-    int taps, coff0, cstep, halo;
-    int rows, mtiles, nch0, nch1;
-    int first, last, raw, G; long Lg;             // res_skip: first, last; gated: raw; upsample: G, Lg = columns of spect
-    int Nq;                                       // output columns: N, but for an upsample that keeps trailing samples (up to N + 3)
-    const float* res;                             // res_skip: the x that rs[:nc] is added to (y0 receives the sum; the same buffer unless x_i is kept)
-    float* s0; float* s1;                         // gated: nullable, receive tanh(u_a) and sigmoid(u_b) [B, nc, L]; gate backward: read as such
-};
-
-template <int WM, int MODE>
-__global__ void __launch_bounds__(WM * 128) wg_gemm_kernel(WgGemm p) {
-    constexpr int GATES = MODE == kWgGated ? 2 : 1;
-    __shared__ float slab[kWgCK * kWgStride];
-    constexpr int kWaves = WM * 2;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int wm = wave % WM, wt = wave / WM;
-    const int mt = blockIdx.y * WM + wm;
-    const bool active = mt < p.mtiles;            // uniform over the wave
-    const int b = blockIdx.z;
-    const long t0 = (long)blockIdx.x * kVocTT;
-    const int nsteps = p.nch0 * p.taps + p.nch1;
-    const f32x4* wp = reinterpret_cast<const f32x4*>(p.wp) + (size_t)(active ? mt : 0) * nsteps * GATES * 128;
-    const int tc = wt * 64 + (lane & 31), hk = lane >> 5;
-    f32x16 acc[GATES][2];
-#pragma unroll
-    for (int g = 0; g < GATES; ++g) { acc[g][0] = f32x16{0}; acc[g][1] = f32x16{0}; }
-
-    for (int c = 0; c < p.nch0 + p.nch1; ++c) {
-        const bool seg0 = c < p.nch0;
-        const int C = seg0 ? p.C0 : p.C1, ci0 = (seg0 ? c : c - p.nch0) * kWgCK;
-        const int halo = seg0 ? p.halo : 0, sw = kVocTT + 2 * halo;
-        const float* xb = (seg0 ? p.x0 : p.x1) + (size_t)b * C * p.N;
-        if (c) __syncthreads();                    // every wave is done reading the previous slab
-        for (int row = wave; row < kWgCK; row += kWaves) {
-            const int ci = ci0 + row;
-            const float* xr = xb + (size_t)ci * p.N;
-            for (int col = lane; col < sw; col += 64) {
-                const long t = t0 + col - halo;
-                slab[row * kWgStride + col] = (ci < C && t >= 0 && t < p.N) ? xr[t] : 0.f;
-            }
-        }
-        __syncthreads();
-        if (active) {
-            const int taps = seg0 ? p.taps : 1;
-            const size_t step0 = seg0 ? (size_t)c * p.taps : (size_t)p.nch0 * p.taps + (c - p.nch0);
-            for (int j = 0; j < taps; ++j) {
-                const float* sb = slab + hk * kWgStride + tc + (seg0 ? p.coff0 + j * p.cstep : 0);
-                const f32x4* wj = wp + (step0 + j) * GATES * 128 + lane;
-#pragma unroll
-                for (int pg = 0; pg < 2; ++pg) {
-                    f32x4 a[GATES];
-#pragma unroll
-                    for (int g = 0; g < GATES; ++g) a[g] = wj[g * 128 + pg * 64];
-#pragma unroll
-                    for (int i = 0; i < 4; ++i) {
-                        const float* s2 = sb + (pg * 4 + i) * 2 * kWgStride;
-                        const float b0 = s2[0], b1 = s2[32];
-#pragma unroll
-                        for (int g = 0; g < GATES; ++g) {
-                            acc[g][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[g][i], b0, acc[g][0], 0, 0, 0);
-                            acc[g][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[g][i], b1, acc[g][1], 0, 0, 0);
-                        }
-                    }
-                }
-            }
-        }
-    }
-    if (!active) return;
-    // lane holds column lane & 31 and rows (e&3) + 8*(e>>2) + 4*hk of each 32x32 tile
-#pragma unroll
-    for (int n = 0; n < 2; ++n) {
-        const long q = t0 + wt * 64 + n * 32 + (lane & 31);
-        if (q >= p.Nq) continue;
-#pragma unroll
-        for (int e = 0; e < 16; ++e) {
-            const int r = mt * 32 + (e & 3) + 8 * (e >> 2) + 4 * hk;
-            if (r >= p.rows) continue;
-            if constexpr (MODE == kWgGated) {
-                const float ua = (acc[0][n][e] + p.bias0[r]) + p.bias1[r];
-                const float ub = (acc[1][n][e] + p.bias0[r + p.rows]) + p.bias1[r + p.rows];
-                if (p.raw) {
-                    p.y0[((size_t)b * 2 * p.rows + r) * p.N + q] = ua;
-                    p.y0[((size_t)b * 2 * p.rows + p.rows + r) * p.N + q] = ub;
-                } else {
-                    const float tv = tanhf(ua), gv = 1.f / (1.f + expf(-ub));
-                    const size_t o = ((size_t)b * p.rows + r) * p.N + q;
-                    if (p.s0) { p.s0[o] = tv; p.s1[o] = gv; }
-                    p.y0[o] = tv * gv;
-                }
-            } else if constexpr (MODE == kWgResSkip) {
-                const float v = acc[0][n][e] + p.bias0[r];
-                const int nc = p.C0;
-                if (!p.last && r < nc) {
-                    const size_t o = ((size_t)b * nc + r) * p.N + q;
-                    p.y0[o] = p.res[o] + v;
-                } else {
-                    const size_t o = ((size_t)b * nc + (p.last ? r : r - nc)) * p.N + q;
-                    p.y1[o] = p.first ? v : p.y1[o] + v;
-                }
-            } else if constexpr (MODE == kWgGateBwd) {
-                // d_acts = acc; du = [d_acts * g * (1 - t^2); d_acts * t * g * (1 - g)] [B, 2*rows, L], acts = t * g recomputed
-                const size_t o = ((size_t)b * p.rows + r) * p.N + q, o2 = ((size_t)b * 2 * p.rows + r) * p.N + q;
-                const float tv = p.s0[o], gv = p.s1[o], da = acc[0][n][e];
-                p.y0[o2] = da * gv * (1.f - tv * tv);
-                p.y0[o2 + (size_t)p.rows * p.N] = da * tv * gv * (1.f - gv);
-                p.y1[o] = tv * gv;
-            } else if constexpr (MODE == kWgAccum) {
-                const size_t o = ((size_t)b * p.rows + r) * p.N + q;
-                p.y0[o] = p.first ? acc[0][n][e] : p.y0[o] + acc[0][n][e];
-            } else {
-                const int ch = r / kWgUpStride;
-                const long t = q * kWgUpStride + (r % kWgUpStride), l = t / p.G;
-                if (l < p.Lg) p.y0[(((size_t)b * p.C0 + ch) * p.G + (int)(t % p.G)) * p.Lg + l] = acc[0][n][e] + p.bias0[ch];
-            }
-        }
-    }
-}
-
-// packed[mtile][step][gate][pg][lane][i] = W[row = 32*mtile + (lane & 31) (+ gate * rows)][k = 16*chunk + 2*(4*pg + i) + (lane >> 5)]
-// (zero outside the matrix); step = chunk * taps + tap over segment 0, then the chunks of segment 1.
-struct WgPack { const float* w0; const float* w1; float* out; int mode, rows, K0, K1, taps, nch0, nch1; size_t total; };
-__global__ void __launch_bounds__(256) wg_pack_kernel(WgPack p) {
-    const size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (idx >= p.total) return;
-    const int gates = p.mode == kWgGated ? 2 : 1, nsteps = p.nch0 * p.taps + p.nch1;
-    const int i = idx & 3, lane = (idx >> 2) & 63, pg = (idx >> 8) & 1;
-    size_t rest = idx >> 9;
-    const int gate = rest % gates; rest /= gates;
-    const int step = rest % nsteps;
-    const int mt = (int)(rest / nsteps);
-    const int r = mt * 32 + (lane & 31), kloc = 2 * (4 * pg + i) + (lane >> 5);
-    float v = 0.f;
-    if (r < p.rows) {
-        if (step < p.nch0 * p.taps) {
-            const int kk = (step / p.taps) * kWgCK + kloc, j = step % p.taps;
-            if (kk < p.K0) {
-                if (p.mode == kWgGated) v = p.w0[((size_t)(gate * p.rows + r) * p.K0 + kk) * 3 + j];          // Conv1d [2nc][nc][3]
-                else if (p.mode == kWgResSkip) v = p.w0[(size_t)r * p.K0 + kk];                                // Conv1d [rows][nc][1]
-                else v = p.w0[((size_t)kk * p.K0 + r / kWgUpStride) * kWgUpK + r % kWgUpStride + kWgUpStride * j];   // ConvTranspose1d [Cin][Cout][1024]
-            }
-        } else {
-            const int kk = (step - p.nch0 * p.taps) * kWgCK + kloc;
-            if (kk < p.K1) v = p.w1[(size_t)(gate * p.rows + r) * p.K1 + kk];
-        }
-    }
-    p.out[idx] = v;
-}
-
-// x[b, c, t] = bias[c] + sum_h w[c][h] * (scale * audio[b, h, t]), h ascending; 32 channels per workgroup row
-__global__ void __launch_bounds__(256) wg_start_kernel(const float* __restrict__ audio, int ctot, int n_half, float scale, const float* __restrict__ w,
-                                                      const float* __restrict__ bias, float* __restrict__ x, int nc, long L) {
-    const long t = (long)blockIdx.x * 256 + threadIdx.x;
-    if (t >= L) return;
-    const int b = blockIdx.z;
-    float a[4];
-#pragma unroll
-    for (int h = 0; h < 4; ++h) a[h] = h < n_half ? audio[((size_t)b * ctot + h) * L + t] * scale : 0.f;
-    const int c1 = min(nc, (int)(blockIdx.y + 1) * 32);
-    for (int c = blockIdx.y * 32; c < c1; ++c) {
-        float acc = 0.f;
-#pragma unroll
-        for (int h = 0; h < 4; ++h)
-            if (h < n_half) acc = fmaf(w[c * n_half + h], a[h], acc);
-        x[((size_t)b * nc + c) * L + t] = acc + bias[c];
-    }
-}
-
-struct WgCouple {
-    const float* out; const float* w_end; const float* b_end; const float* in; const float* winv; const float* z;
-    float* dst; float* inter;
-    int nc, n_half, n_early; long L; float in_scale, sigma;
-};
-// one thread per (item, column): end as <= 8 fmaf chains over nc (ascending), the affine inverse, the c x c mix (ascending)
-__global__ void __launch_bounds__(256) wg_couple_kernel(WgCouple p) {
-    __shared__ float we[8 * 512], be[8], wi[64];
-    const int nh = p.n_half, C = 2 * nh;
-    for (int i = threadIdx.x; i < C * p.nc; i += 256) we[i] = p.w_end[i];
-    if (threadIdx.x < C) be[threadIdx.x] = p.b_end[threadIdx.x];
-    if (threadIdx.x < C * C) wi[threadIdx.x] = p.winv[threadIdx.x];
-    __syncthreads();
-    const long t = (long)blockIdx.x * 256 + threadIdx.x;
-    if (t >= p.L) return;
-    const int b = blockIdx.y;
-    float o[8];
-#pragma unroll
-    for (int r = 0; r < 8; ++r) o[r] = 0.f;
-    const float* ob = p.out + (size_t)b * p.nc * p.L + t;
-    for (int c = 0; c < p.nc; ++c) {
-        const float v = ob[(size_t)c * p.L];
-#pragma unroll
-        for (int r = 0; r < 8; ++r)
-            if (r < C) o[r] = fmaf(we[r * p.nc + c], v, o[r]);
-    }
-    float v[8];
-    const float* ib = p.in + (size_t)b * C * p.L + t;
-#pragma unroll
-    for (int h = 0; h < 4; ++h) {
-        if (h < nh) {
-            const float a0 = ib[(size_t)h * p.L] * p.in_scale, a1 = ib[(size_t)(nh + h) * p.L] * p.in_scale;
-            float bb = 0.f, s = 0.f;
-#pragma unroll
-            for (int r = 0; r < 8; ++r) {           // o[h] and o[nh + h] without a dynamic register index
-                if (r == h) bb = o[r] + be[r];
-                if (r == nh + h) s = o[r] + be[r];
-            }
-            const float y1 = (a1 - bb) / expf(s);
-#pragma unroll
-            for (int r = 0; r < 8; ++r) {
-                if (r == h) v[r] = a0;
-                if (r == nh + h) v[r] = y1;
-            }
-        }
-    }
-    const int Cn = C + p.n_early;
-#pragma unroll
-    for (int r = 0; r < 8; ++r) {
-        if (r < C) {
-            float y = 0.f;
-#pragma unroll
-            for (int c = 0; c < 8; ++c)
-                if (c < C) y = fmaf(wi[r * C + c], v[c], y);
-            if (p.dst) p.dst[((size_t)b * Cn + p.n_early + r) * p.L + t] = y;
-            if (p.inter) p.inter[((size_t)b * p.L + t) * C + r] = y;
-        }
-    }
-    if (p.dst)
-        for (int j = 0; j < p.n_early; ++j) p.dst[((size_t)b * Cn + j) * p.L + t] = p.sigma * p.z[((size_t)b * p.n_early + j) * p.L + t];
-}
-
-// ---- the forward direction (audio -> z, glow.py:207-249): the kernels around the WN, which is the one above
-// fixed-order sum of one double per lane over the wave, in every lane
-__device__ __forceinline__ double wg_wave_sum(double v) {
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
-    return v;
-}
-
-// dst[b, r, l] = sum_g w[r][g] * audio[b, l*G + g] (g ascending): the regroup of glow.py:223 and flow 0's mix; one thread per (b, l)
-__global__ void __launch_bounds__(256) wg_head_kernel(const float* __restrict__ audio, const float* __restrict__ w, float* __restrict__ dst, int G, long N,
-                                                     long L) {
-    __shared__ float wi[64];
-    if (threadIdx.x < G * G) wi[threadIdx.x] = w[threadIdx.x];
-    __syncthreads();
-    const long l = (long)blockIdx.x * 256 + threadIdx.x;
-    if (l >= L) return;
-    const int b = blockIdx.y;
-    const float* ab = audio + (size_t)b * N + (size_t)l * G;
-    float v[8];
-#pragma unroll
-    for (int g = 0; g < 8; ++g) v[g] = g < G ? ab[g] : 0.f;
-#pragma unroll
-    for (int r = 0; r < 8; ++r) {
-        if (r < G) {
-            float y = 0.f;
-#pragma unroll
-            for (int g = 0; g < 8; ++g)
-                if (g < G) y = fmaf(wi[r * G + g], v[g], y);
-            dst[((size_t)b * G + r) * L + l] = y;
-        }
-    }
-}
-
-struct WgTail {
-    const float* out; const float* w_end; const float* b_end; const float* in; const float* wnext;
-    float* dst; float* z; float* log_s; double* part_s; double* part_z;
-    int nc, n_half, n_peel, G, zoff; long L;
-};
-// One flow's tail, one thread per (item, column): (b, s) = end(out) as <= 8 fmaf chains over nc (ascending), a1' = exp(s) * a1 + b,
-// v = cat(a0, a1').  v[:n_peel] goes to z[:, zoff:] (the next flow's early output; on the last flow all of v), the rest is mixed by
-// the next flow's W (ascending) into dst.  part_s / part_z [item][column block] receive the workgroup's sums of s and of the z^2 it
-// wrote, added in fp64 from the first term: per thread in channel order, then a xor tree over the wave, then the waves in order.
-__global__ void __launch_bounds__(256) wg_tail_kernel(WgTail p) {
-    __shared__ __align__(8) float we[8 * 512];
-    __shared__ float be[8], wi[64];
-    const int nh = p.n_half, C = 2 * nh, Cn = C - p.n_peel;
-    for (int i = threadIdx.x; i < C * p.nc; i += 256) we[i] = p.w_end[i];
-    if (threadIdx.x < C) be[threadIdx.x] = p.b_end[threadIdx.x];
-    if (threadIdx.x < Cn * Cn) wi[threadIdx.x] = p.wnext[threadIdx.x];
-    __syncthreads();
-    const long t = (long)blockIdx.x * 256 + threadIdx.x;
-    const bool valid = t < p.L;
-    const int b = blockIdx.y;
-    double sum_s = 0.0, sum_z = 0.0;
-    if (valid) {
-        float o[8];
-#pragma unroll
-        for (int r = 0; r < 8; ++r) o[r] = 0.f;
-        const float* ob = p.out + (size_t)b * p.nc * p.L + t;
-        for (int c = 0; c < p.nc; ++c) {
-            const float x = ob[(size_t)c * p.L];
-#pragma unroll
-            for (int r = 0; r < 8; ++r)
-                if (r < C) o[r] = fmaf(we[r * p.nc + c], x, o[r]);
-        }
-        float v[8];
-#pragma unroll
-        for (int r = 0; r < 8; ++r) v[r] = 0.f;
-        const float* ib = p.in + (size_t)b * C * p.L + t;
-#pragma unroll
-        for (int h = 0; h < 4; ++h) {
-            if (h < nh) {
-                const float a0 = ib[(size_t)h * p.L], a1 = ib[(size_t)(nh + h) * p.L];
-                float bb = 0.f, s = 0.f;
-#pragma unroll
-                for (int r = 0; r < 8; ++r) {       // o[h] and o[nh + h] without a dynamic register index
-                    if (r == h) bb = o[r] + be[r];
-                    if (r == nh + h) s = o[r] + be[r];
-                }
-                const float y1 = fmaf(expf(s), a1, bb);
-                if (p.log_s) p.log_s[((size_t)b * nh + h) * p.L + t] = s;
-                sum_s += (double)s;
-#pragma unroll
-                for (int r = 0; r < 8; ++r) {
-                    if (r == h) v[r] = a0;
-                    if (r == nh + h) v[r] = y1;
-                }
-            }
-        }
-#pragma unroll
-        for (int r = 0; r < 8; ++r) {
-            if (r < p.n_peel) {
-                if (p.z) p.z[((size_t)b * p.G + p.zoff + r) * p.L + t] = v[r];
-                sum_z += (double)v[r] * (double)v[r];
-            }
-        }
-#pragma unroll
-        for (int r = 0; r < 8; ++r) {
-            if (r < Cn) {
-                float y = 0.f;
-#pragma unroll
-                for (int c = 0; c < 8; ++c)
-                    if (c >= p.n_peel && c < C) y = fmaf(wi[r * Cn + c - p.n_peel], v[c], y);
-                p.dst[((size_t)b * Cn + r) * p.L + t] = y;
-            }
-        }
-    }
-    if (!p.part_s) return;                         // uniform
-    sum_s = wg_wave_sum(sum_s);
-    sum_z = wg_wave_sum(sum_z);
-    __syncthreads();                               // every thread is done with `we`: its first 64 bytes carry the waves' sums
-    double* red = reinterpret_cast<double*>(we);
-    if ((threadIdx.x & 63) == 0) { red[threadIdx.x >> 6] = sum_s; red[4 + (threadIdx.x >> 6)] = sum_z; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        const size_t slot = (size_t)b * gridDim.x + blockIdx.x;
-        p.part_s[slot] = ((red[0] + red[1]) + red[2]) + red[3];
-        p.part_z[slot] = ((red[4] + red[5]) + red[6]) + red[7];
-    }
-}
-
-// Per item (one wave each): sums[b][k] = sum of flow k's partials (lane j takes blocks j, j + 64, .. ascending, then the xor tree),
-// sums[b][n_flows] = sum z^2 (flows ascending), item[b] = (sum z^2 / (2 sigma^2) - sum_k sums[b][k] - L * sum_k logdet W_k) / (G * L).
-__global__ void __launch_bounds__(64) wg_nll_item_kernel(const double* __restrict__ part_s, const double* __restrict__ part_z, int n_flows, int B, int nblk,
-                                                        long L, int G, float sigma, const float* __restrict__ logdet_w, double* __restrict__ sums,
-                                                        double* __restrict__ item, float* __restrict__ nll_item) {
-    const int b = blockIdx.x, lane = threadIdx.x;
-    double z2 = 0.0, stot = 0.0, ld = 0.0;
-    for (int k = 0; k < n_flows; ++k) {
-        const size_t base = ((size_t)k * B + b) * nblk;
-        double ps = 0.0, pz = 0.0;
-        for (int j = lane; j < nblk; j += 64) { ps += part_s[base + j]; pz += part_z[base + j]; }
-        ps = wg_wave_sum(ps);
-        pz = wg_wave_sum(pz);
-        if (lane == 0) sums[(size_t)b * (n_flows + 1) + k] = ps;
-        stot += ps; z2 += pz; ld += (double)logdet_w[k];
-    }
-    if (lane != 0) return;
-    sums[(size_t)b * (n_flows + 1) + n_flows] = z2;
-    const double nll = (z2 / (2.0 * (double)sigma * (double)sigma) - stot - (double)L * ld) / ((double)G * (double)L);
-    item[b] = nll;
-    if (nll_item) nll_item[b] = (float)nll;
-}
-
-// logdet[k] = B * L * logdet W_k (glow.py:100), and loss = mean over the items of item[b] (thread j takes items j, j + 256, ..
-// ascending, then a tree in LDS): WaveGlowLoss (glow.py:48-59) from the sums above.
-__global__ void __launch_bounds__(256) wg_nll_loss_kernel(const double* __restrict__ item, int B, long L, int n_flows, const float* __restrict__ logdet_w,
-                                                         float* __restrict__ logdet, float* __restrict__ loss) {
-    __shared__ double red[256];
-    if (logdet && threadIdx.x < n_flows) logdet[threadIdx.x] = (float)((double)B * (double)L * (double)logdet_w[threadIdx.x]);
-    if (!loss) return;                             // uniform
-    double acc = 0.0;
-    for (int b = threadIdx.x; b < B; b += 256) acc += item[b];
-    red[threadIdx.x] = acc;
-    __syncthreads();
-    for (int w = 128; w >= 1; w >>= 1) {
-        if (threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) loss[0] = (float)(red[0] / (double)B);
-}
-
-// out[m] = log |det w[m]| of n matrices [c][c], c <= 8: LU with partial pivoting in fp64, sum of log |u_ii| rounded to fp32; NaN
-// for a negative determinant and -inf for a singular matrix, as torch.logdet gives.  One workgroup per matrix, the matrix in LDS.
-__global__ void __launch_bounds__(64) wg_logdet_kernel(const float* __restrict__ w, int c, float* __restrict__ out) {
-    __shared__ double m[64];
-    if ((int)threadIdx.x < c * c) m[threadIdx.x] = (double)w[(size_t)blockIdx.x * c * c + threadIdx.x];
-    __syncthreads();
-    if (threadIdx.x != 0) return;
-    double acc = 0.0;
-    bool negative = false, singular = false;
-    for (int i = 0; i < c && !singular; ++i) {
-        int piv = i;                                // `>` is false for a NaN: one off the diagonal is never chosen here, it spreads
-        for (int r = i + 1; r < c; ++r)             // through the elimination below and is met as a pivot (or in the sum) later
-            if (fabs(m[r * c + i]) > fabs(m[piv * c + i])) piv = r;
-        if (piv != i) {
-            for (int j = 0; j < c; ++j) { const double tmp = m[i * c + j]; m[i * c + j] = m[piv * c + j]; m[piv * c + j] = tmp; }
-            negative = !negative;
-        }
-        const double u = m[i * c + i];
-        if (u != u) { negative = true; break; }     // a NaN in the matrix gives NaN
-        if (u == 0.0) { singular = true; break; }
-        if (u < 0.0) negative = !negative;
-        acc += log(fabs(u));
-        for (int r = i + 1; r < c; ++r) {
-            const double f = m[r * c + i] / u;
-            for (int j = i + 1; j < c; ++j) m[r * c + j] -= f * m[i * c + j];
-        }
-    }
-    const double inf = __builtin_inf();
-    out[blockIdx.x] = singular ? (float)-inf : (negative ? __builtin_nanf("") : (float)acc);
-}
-
-// ------------------------------------------------------------------------------------------------------------------
-// host
-// ------------------------------------------------------------------------------------------------------------------
-static size_t round4(size_t n) { return (n + 3) / 4 * 4; }
-static int chunks(int k) { return (k + kWgCK - 1) / kWgCK; }
-
-static size_t wg_packed_floats(int kind, int rows, int k0, int k1) {
-    if (kind == kWgGated) return (size_t)((rows + 31) / 32) * (chunks(k0) * 3 + chunks(k1)) * 2 * 512;
-    if (kind == kWgResSkip) return (size_t)((rows + 31) / 32) * chunks(k0) * 512;
-    return (size_t)rows * kWgUpStride / 32 * chunks(k0) * kWgUpTaps * 512;
-}
-
-static int wg_pack(int kind, const float* w0, const float* w1, float* out, int rows, int k0, int k1, hipStream_t s) {
-    T2_REQUIRE(w0 && out && (kind != kWgGated || w1), "waveglow pack: null pointer");
-    WgPack p{w0, w1, out, kind, kind == kWgUpsample ? rows * kWgUpStride : rows, k0, kind == kWgGated ? k1 : 0,
-             kind == kWgGated ? 3 : (kind == kWgUpsample ? kWgUpTaps : 1), chunks(k0), kind == kWgGated ? chunks(k1) : 0,
-             wg_packed_floats(kind, rows, k0, k1)};
-    hipLaunchKernelGGL(wg_pack_kernel, dim3((unsigned)((p.total + 255) / 256)), dim3(256), 0, s, p);
-    T2_LAUNCH_CHECK();
-    return 0;
-}
-
-template <int MODE>
-static int wg_launch(const WgGemm& p, int B, hipStream_t s) {
-    const int wm = p.mtiles >= 4 ? 4 : (p.mtiles >= 2 ? 2 : 1);
-    dim3 grid((unsigned)((p.Nq + kVocTT - 1) / kVocTT), (unsigned)((p.mtiles + wm - 1) / wm), (unsigned)B);
-    if (wm == 4) hipLaunchKernelGGL((wg_gemm_kernel<4, MODE>), grid, dim3(512), 0, s, p);
-    else if (wm == 2) hipLaunchKernelGGL((wg_gemm_kernel<2, MODE>), grid, dim3(256), 0, s, p);
-    else hipLaunchKernelGGL((wg_gemm_kernel<1, MODE>), grid, dim3(128), 0, s, p);
-    T2_LAUNCH_CHECK();
-    return 0;
-}
-
-static int wg_check_common(const char* who, int B, long L) {
-    T2_REQUIRE(B >= 1 && B <= 65535, "%s: B=%d outside 1..65535", who, B);
-    T2_REQUIRE(L >= 1, "%s: L=%ld must be at least 1", who, L);
-    T2_REQUIRE(L <= (long)INT32_MAX / 2, "%s: L=%ld exceeds the limit of %d columns per row", who, L, INT32_MAX / 2);
-    return 0;
-}
-static int wg_check_nc(const char* who, int nc) {
-    T2_REQUIRE(nc >= 8 && nc <= 512 && nc % 8 == 0, "%s: n_channels=%d, must be a multiple of 8 from 8 to 512", who, nc);
-    return 0;
-}
-
-static int wg_gated_check(int B, int nc, int n_cond, long L, int d) {
-    const char* who = "waveglow gated conv";
-    T2_TRY_RC(wg_check_common(who, B, L));
-    T2_TRY_RC(wg_check_nc(who, nc));
-    T2_REQUIRE(n_cond >= 8 && n_cond % 8 == 0, "%s: %d conditioning channels (n_mel_channels * n_group), must be a positive multiple of 8", who, n_cond);
-    T2_REQUIRE(d >= 1 && d <= kWgMaxD && (d & (d - 1)) == 0, "%s: dilation %d is not a power of two from 1 to %d", who, d, kWgMaxD);
-    return 0;
-}
-
-static int wg_gated(int B, int nc, int n_cond, long L, int d, int raw, const float* x, const float* spect, const float* packed, const float* b_in,
-                    const float* b_cond, float* y, hipStream_t s, float* keep_t = nullptr, float* keep_g = nullptr) {
-    T2_TRY_RC(wg_gated_check(B, nc, n_cond, L, d));
-    T2_REQUIRE(x && spect && packed && b_in && b_cond && y, "waveglow gated conv: null pointer");
-    WgGemm p{};
-    p.x0 = x; p.x1 = spect; p.wp = packed; p.bias0 = b_in; p.bias1 = b_cond; p.y0 = y;
-    p.C0 = nc; p.C1 = n_cond; p.N = p.Nq = (int)L; p.taps = 3; p.coff0 = 0; p.cstep = d; p.halo = d;
-    p.rows = nc; p.mtiles = (nc + 31) / 32; p.nch0 = chunks(nc); p.nch1 = chunks(n_cond); p.raw = raw; p.s0 = keep_t; p.s1 = keep_g;
-    return wg_launch<kWgGated>(p, B, s);
-}
-
-static int wg_res_skip(int B, int nc, long L, int first, int last, const float* acts, const float* packed, const float* bias, float* x, float* out,
-                       hipStream_t s, const float* x_from = nullptr) {
-    const char* who = "waveglow res_skip";
-    T2_TRY_RC(wg_check_common(who, B, L));
-    T2_TRY_RC(wg_check_nc(who, nc));
-    T2_REQUIRE(acts && packed && bias && out && (last || x), "%s: null pointer", who);
-    WgGemm p{};
-    p.x0 = acts; p.wp = packed; p.bias0 = bias; p.y0 = x; p.y1 = out; p.res = x_from ? x_from : x;
-    p.C0 = nc; p.N = p.Nq = (int)L; p.taps = 1;
-    p.rows = last ? nc : 2 * nc; p.mtiles = (p.rows + 31) / 32; p.nch0 = chunks(nc); p.first = first; p.last = last;
-    return wg_launch<kWgResSkip>(p, B, s);
-}
-
-// n_samples: the samples of the transposed conv that are regrouped, T*256 for inference; up to T*256 + 768 (the trailing ones,
-// frames q = T .. T+2 whose taps reach back into the mel) for the forward direction.  The loader zero-fills past the row.
-static int wg_upsample(int B, int n_mel, int T, int G, long n_samples, const float* mel, const float* packed, const float* bias, float* spect, hipStream_t s) {
-    const char* who = "waveglow upsample";
-    T2_TRY_RC(wg_check_common(who, B, T));
-    T2_REQUIRE(n_mel >= 1 && n_mel <= 512, "%s: n_mel_channels=%d outside 1..512", who, n_mel);
-    T2_REQUIRE(G >= 2 && G <= 8 && G % 2 == 0, "%s: n_group=%d is not even and from 2 to 8", who, G);
-    T2_REQUIRE(n_samples / G >= 1, "%s: %ld samples give no whole group of %d", who, n_samples, G);
-    T2_REQUIRE(n_samples <= (long)T * kWgUpStride + kWgUpK - kWgUpStride, "%s: %ld samples, %d frames give %ld", who, n_samples, T,
-               (long)T * kWgUpStride + kWgUpK - kWgUpStride);
-    T2_REQUIRE(mel && packed && bias && spect, "%s: null pointer", who);
-    WgGemm p{};
-    p.x0 = mel; p.wp = packed; p.bias0 = bias; p.y0 = spect;
-    p.C0 = n_mel; p.N = T; p.taps = kWgUpTaps; p.coff0 = kWgUpTaps - 1; p.cstep = -1; p.halo = kWgUpTaps - 1;
-    p.rows = n_mel * kWgUpStride; p.mtiles = p.rows / 32; p.nch0 = chunks(n_mel); p.G = G; p.Lg = n_samples / G;
-    p.Nq = (int)std::max((long)T, (p.Lg * G + kWgUpStride - 1) / kWgUpStride);
-    return wg_launch<kWgUpsample>(p, B, s);
-}
-
-static int wg_start(int B, int nc, int ctot, int n_half, long L, float scale, const float* audio, const float* w, const float* bias, float* x, hipStream_t s) {
-    hipLaunchKernelGGL(wg_start_kernel, dim3((unsigned)((L + 255) / 256), (unsigned)((nc + 31) / 32), (unsigned)B), dim3(256), 0, s, audio, ctot, n_half,
-                       scale, w, bias, x, nc, L);
-    T2_LAUNCH_CHECK();
-    return 0;
-}
-
-static int wg_couple(int B, const WgCouple& p, hipStream_t s) {
-    const char* who = "waveglow coupling";
-    T2_TRY_RC(wg_check_common(who, B, p.L));
-    T2_TRY_RC(wg_check_nc(who, p.nc));
-    T2_REQUIRE(p.n_half >= 1 && p.n_half <= 4, "%s: n_half=%d outside 1..4", who, p.n_half);
-    T2_REQUIRE(p.n_early >= 0 && p.n_early + 2 * p.n_half <= 8, "%s: %d early channels on top of %d exceed 8", who, p.n_early, 2 * p.n_half);
-    T2_REQUIRE(p.out && p.w_end && p.b_end && p.in && p.winv && (p.dst || p.inter) && (p.n_early == 0 || (p.z && p.dst)), "%s: null pointer", who);
-    hipLaunchKernelGGL(wg_couple_kernel, dim3((unsigned)((p.L + 255) / 256), (unsigned)B), dim3(256), 0, s, p);
-    T2_LAUNCH_CHECK();
-    return 0;
-}
-
-static int wg_head(int B, int G, long N, const float* audio, const float* w, float* dst, hipStream_t s) {
-    const char* who = "waveglow head";
-    T2_REQUIRE(G >= 2 && G <= 8 && G % 2 == 0, "%s: n_group=%d is not even and from 2 to 8", who, G);
-    T2_REQUIRE(N >= G, "%s: n_samples=%ld is shorter than one group of %d", who, N, G);
-    T2_TRY_RC(wg_check_common(who, B, N / G));
-    T2_REQUIRE(audio && w && dst, "%s: null pointer", who);
-    hipLaunchKernelGGL(wg_head_kernel, dim3((unsigned)((N / G + 255) / 256), (unsigned)B), dim3(256), 0, s, audio, w, dst, G, N, N / G);
-    T2_LAUNCH_CHECK();
-    return 0;
-}
-
-static int wg_tail(int B, const WgTail& p, hipStream_t s) {
-    const char* who = "waveglow forward tail";
-    const int C = 2 * p.n_half;
-    T2_TRY_RC(wg_check_common(who, B, p.L));
-    T2_TRY_RC(wg_check_nc(who, p.nc));
-    T2_REQUIRE(p.n_half >= 1 && p.n_half <= 4, "%s: n_half=%d outside 1..4", who, p.n_half);
-    T2_REQUIRE(p.n_peel >= 0 && p.n_peel <= C && p.n_peel != C - 1, "%s: %d of %d channels peeled leave no whole flow", who, p.n_peel, C);
-    T2_REQUIRE(p.zoff >= 0 && p.zoff + p.n_peel <= p.G && p.G <= 8, "%s: channels %d..%d of z lie outside its %d", who, p.zoff, p.zoff + p.n_peel, p.G);
-    T2_REQUIRE(p.out && p.w_end && p.b_end && p.in && (p.n_peel == C || (p.wnext && p.dst)) && (p.n_peel == 0 || p.z || p.part_z) &&
-               !p.part_s == !p.part_z, "%s: null pointer", who);
-    hipLaunchKernelGGL(wg_tail_kernel, dim3((unsigned)((p.L + 255) / 256), (unsigned)B), dim3(256), 0, s, p);
-    T2_LAUNCH_CHECK();
-    return 0;
-}
-
-static int wg_logdet(const float* w, int c, int n, float* out, hipStream_t s) {
-    T2_REQUIRE(c >= 1 && c <= 8, "waveglow logdet: matrices of %d x %d, at most 8 x 8 are taken", c, c);
-    T2_REQUIRE(n >= 1 && w && out, "waveglow logdet: %d matrices or a null pointer", n);
-    hipLaunchKernelGGL(wg_logdet_kernel, dim3((unsigned)n), dim3(64), 0, s, w, c, out);
-    T2_LAUNCH_CHECK();
-    return 0;
-}
-
-static int wg_nll_item(int n_flows, int B, int nblk, long L, int G, float sigma, const double* part_s, const double* part_z, const float* logdet_w,
-                       double* sums, double* item, float* nll_item, hipStream_t s) {
-    hipLaunchKernelGGL(wg_nll_item_kernel, dim3((unsigned)B), dim3(64), 0, s, part_s, part_z, n_flows, B, nblk, L, G, sigma, logdet_w, sums, item, nll_item);
-    T2_LAUNCH_CHECK();
-    return 0;
-}
-
-static int wg_nll_loss(int n_flows, int B, long L, const double* item, const float* logdet_w, float* logdet, float* loss, hipStream_t s) {
-    hipLaunchKernelGGL(wg_nll_loss_kernel, dim3(1), dim3(256), 0, s, item, B, L, n_flows, logdet_w, logdet, loss);
-    T2_LAUNCH_CHECK();
-    return 0;
-}
-
-// ------------------------------------------------------------------------------------------------------------------
-// the model
-// ------------------------------------------------------------------------------------------------------------------
-struct WgFlow {
-    int c, n_half, early;                          // channels of `audio` in this flow; early: sigma * z is prepended after it
-    size_t start_w, start_b, cond_b, end_w, end_b, winv;
-    size_t gated[T2_WAVEGLOW_MAX_LAYERS], in_b[T2_WAVEGLOW_MAX_LAYERS], rs[T2_WAVEGLOW_MAX_LAYERS], rs_b[T2_WAVEGLOW_MAX_LAYERS];
-};
-struct WgLayout { std::vector<WgFlow> flows; size_t up_w, up_b, total; int n_remaining, n_planes, n_tensors; };
-
-static int wg_layout(const t2_waveglow_config& c, WgLayout* out) {
-    T2_REQUIRE(c.kernel_size == 3, "waveglow: kernel_size=%d, only 3 is implemented", c.kernel_size);
-    T2_REQUIRE(c.n_layers >= 1 && c.n_layers <= T2_WAVEGLOW_MAX_LAYERS, "waveglow: n_layers=%d outside 1..%d", c.n_layers, T2_WAVEGLOW_MAX_LAYERS);
-    T2_TRY_RC(wg_check_nc("waveglow", c.n_channels));
-    T2_REQUIRE(c.n_group >= 2 && c.n_group <= 8 && c.n_group % 2 == 0, "waveglow: n_group=%d is not even and from 2 to 8", c.n_group);
-    T2_REQUIRE(c.n_early_size >= 0 && c.n_early_size % 2 == 0, "waveglow: n_early_size=%d is not even and non-negative", c.n_early_size);
-    T2_REQUIRE(c.n_early_every >= 1, "waveglow: n_early_every=%d must be at least 1", c.n_early_every);
-    T2_REQUIRE(c.n_flows >= 1 && c.n_flows <= 64, "waveglow: n_flows=%d outside 1..64", c.n_flows);
-    T2_REQUIRE(c.n_mel_channels >= 1 && c.n_mel_channels <= 512, "waveglow: n_mel_channels=%d outside 1..512", c.n_mel_channels);
-    const int n_cond = c.n_mel_channels * c.n_group, nc = c.n_channels;
-    T2_REQUIRE(n_cond % 8 == 0, "waveglow: n_mel_channels * n_group = %d is not a multiple of 8", n_cond);
-    WgLayout L;
-    size_t off = 0;
-    auto take = [&](size_t n) { const size_t o = off; off += round4(n); return o; };
-    L.up_w = take(wg_packed_floats(kWgUpsample, c.n_mel_channels, c.n_mel_channels, 0));
-    L.up_b = take(c.n_mel_channels);
-    int ch = c.n_group;
-    L.n_planes = 1;
-    for (int k = 0; k < c.n_flows; ++k) {
-        WgFlow f{};
-        f.early = k % c.n_early_every == 0 && k > 0;
-        if (f.early) { ch -= c.n_early_size; ++L.n_planes; }
-        T2_REQUIRE(ch >= 2, "waveglow: flow %d is left with %d channels: n_early_size=%d is taken too often from n_group=%d", k, ch, c.n_early_size, c.n_group);
-        f.c = ch; f.n_half = ch / 2;
-        f.start_w = take((size_t)nc * f.n_half); f.start_b = take(nc);
-        f.cond_b = take((size_t)2 * nc * c.n_layers);
-        for (int i = 0; i < c.n_layers; ++i) {
-            const int rows = i < c.n_layers - 1 ? 2 * nc : nc;
-            f.gated[i] = take(wg_packed_floats(kWgGated, nc, nc, n_cond)); f.in_b[i] = take(2 * nc);
-            f.rs[i] = take(wg_packed_floats(kWgResSkip, rows, nc, 0)); f.rs_b[i] = take(rows);
-        }
-        f.end_w = take((size_t)ch * nc); f.end_b = take(ch); f.winv = take((size_t)ch * ch);
-        L.flows.push_back(f);
-    }
-    L.n_remaining = ch; L.total = off; L.n_tensors = 2 + c.n_flows * (7 + 4 * c.n_layers);
-    if (out) *out = L;
-    return 0;
-}
-
-static int wg_plan(const t2_waveglow_config& c, int B, int T, t2_waveglow_plan_info* out, WgLayout* lay) {
-    WgLayout L;
-    T2_TRY_RC(wg_layout(c, &L));
-    T2_REQUIRE(B >= 1 && B <= 65535, "waveglow: B=%d outside 1..65535", B);
-    T2_REQUIRE(T >= 1, "waveglow: T=%d frames, must be at least 1", T);
-    const long cols = (long)T * kWgUpStride / c.n_group;
-    T2_REQUIRE(cols >= 1, "waveglow: T=%d frames give no whole group of %d samples", T, c.n_group);
-    T2_REQUIRE(cols <= (long)INT32_MAX / 2, "waveglow: L=%ld exceeds the limit of %d columns per row", cols, INT32_MAX / 2);
-    if (out) {
-        out->L = cols; out->out_len = cols * c.n_group;
-        out->n_remaining_channels = L.n_remaining; out->n_noise_planes = L.n_planes; out->n_tensors = L.n_tensors; out->time_tile = kVocTT;
-        const size_t per = round4((size_t)B * cols);
-        out->workspace_bytes = per * ((size_t)c.n_mel_channels * c.n_group + 3 * (size_t)c.n_channels + 2 * (size_t)c.n_group) * sizeof(float);
-        out->packed_bytes = L.total * sizeof(float);
-    }
-    if (lay) *lay = L;
-    return 0;
-}
 
 static int wg_copy(float* dst, const float* src, size_t n, hipStream_t s) {
     T2_CHECK_HIP(hipMemcpyAsync(dst, src, n * sizeof(float), hipMemcpyDeviceToDevice, s));
@@ -709,35 +24,58 @@ static int wg_copy(float* dst, const float* src, size_t n, hipStream_t s) {
 static int wg_pack_model(const t2_waveglow_config& c, const float* const* t, int n, float* packed, hipStream_t s) {
     WgLayout L;
     T2_TRY_RC(wg_layout(c, &L));
+    const WgTensors& tt = L.tt;
     T2_REQUIRE(t && packed, "t2_waveglow_pack: null pointer");
-    T2_REQUIRE(n == L.n_tensors, "t2_waveglow_pack: %d tensors given, the configuration has %d", n, L.n_tensors);
+    T2_REQUIRE(n == tt.count(), "t2_waveglow_pack: %d tensors given, the configuration has %d", n, tt.count());
     for (int i = 0; i < n; ++i) T2_REQUIRE(t[i], "t2_waveglow_pack: tensor %d is null", i);
     const int nc = c.n_channels, n_cond = c.n_mel_channels * c.n_group;
-    T2_TRY_RC(wg_pack(kWgUpsample, t[0], nullptr, packed + L.up_w, c.n_mel_channels, c.n_mel_channels, 0, s));
-    T2_TRY_RC(wg_copy(packed + L.up_b, t[1], c.n_mel_channels, s));
-    int at = 2;
+    auto copy = [&](size_t dst, int tensor) { return wg_copy(packed + dst, t[tensor], wg_tensor_floats(c, L, tensor), s); };
+    T2_TRY_RC(wg_pack(kWgUpsample, t[tt.up_w()], nullptr, packed + L.up_w, c.n_mel_channels, c.n_mel_channels, 0, s));
+    T2_TRY_RC(copy(L.up_b, tt.up_b()));
     for (int k = 0; k < c.n_flows; ++k) {
         const WgFlow& f = L.flows[k];
-        T2_TRY_RC(wg_copy(packed + f.start_w, t[at], (size_t)nc * f.n_half, s));
-        T2_TRY_RC(wg_copy(packed + f.start_b, t[at + 1], nc, s));
-        const float* cond_w = t[at + 2];
-        T2_TRY_RC(wg_copy(packed + f.cond_b, t[at + 3], (size_t)2 * nc * c.n_layers, s));
-        at += 4;
-        for (int i = 0; i < c.n_layers; ++i, at += 2) {
-            T2_TRY_RC(wg_pack(kWgGated, t[at], cond_w + (size_t)2 * nc * i * n_cond, packed + f.gated[i], nc, nc, n_cond, s));
-            T2_TRY_RC(wg_copy(packed + f.in_b[i], t[at + 1], 2 * nc, s));
+        T2_TRY_RC(copy(f.start_w, tt.start_w(k)));
+        T2_TRY_RC(copy(f.start_b, tt.start_b(k)));
+        T2_TRY_RC(copy(f.cond_b, tt.cond_b(k)));
+        for (int i = 0; i < c.n_layers; ++i) {
+            T2_TRY_RC(wg_pack(kWgGated, t[tt.in_w(k, i)], t[tt.cond_w(k)] + (size_t)2 * nc * i * n_cond, packed + f.gated[i], nc, nc, n_cond, s));
+            T2_TRY_RC(copy(f.in_b[i], tt.in_b(k, i)));
         }
-        for (int i = 0; i < c.n_layers; ++i, at += 2) {
-            const int rows = i < c.n_layers - 1 ? 2 * nc : nc;
-            T2_TRY_RC(wg_pack(kWgResSkip, t[at], nullptr, packed + f.rs[i], rows, nc, 0, s));
-            T2_TRY_RC(wg_copy(packed + f.rs_b[i], t[at + 1], rows, s));
+        for (int i = 0; i < c.n_layers; ++i) {
+            T2_TRY_RC(wg_pack(kWgResSkip, t[tt.rs_w(k, i)], nullptr, packed + f.rs[i], i < c.n_layers - 1 ? 2 * nc : nc, nc, 0, s));
+            T2_TRY_RC(copy(f.rs_b[i], tt.rs_b(k, i)));
         }
-        T2_TRY_RC(wg_copy(packed + f.end_w, t[at], (size_t)f.c * nc, s));
-        T2_TRY_RC(wg_copy(packed + f.end_b, t[at + 1], f.c, s));
-        T2_TRY_RC(wg_copy(packed + f.winv, t[at + 2], (size_t)f.c * f.c, s));
-        at += 3;
+        T2_TRY_RC(copy(f.end_w, tt.end_w(k)));
+        T2_TRY_RC(copy(f.end_b, tt.end_b(k)));
+        T2_TRY_RC(copy(f.winv, tt.mix(k)));
     }
-    T2_REQUIRE(at == n, "t2_waveglow_pack: tensor table out of step");
+    return 0;
+}
+
+static int wg_pack_backward(const t2_waveglow_config& c, const float* const* t, int n, float* packed, hipStream_t s) {
+    WgLayout lay;
+    WgBwdLayout bl;
+    T2_TRY_RC(wg_layout(c, &lay));
+    wg_bwd_layout(c, lay, &bl);
+    const WgTensors& tt = lay.tt;
+    T2_REQUIRE(t && packed, "t2_waveglow_pack_backward: null pointer");
+    T2_REQUIRE(n == tt.count(), "t2_waveglow_pack_backward: %d tensors given, the configuration has %d", n, tt.count());
+    for (int i = 0; i < n; ++i) T2_REQUIRE(t[i], "t2_waveglow_pack_backward: tensor %d is null", i);
+    const int nc = c.n_channels, n_cond = c.n_mel_channels * c.n_group, nl = c.n_layers;
+    for (int k = 0; k < c.n_flows; ++k)
+        for (int i = 0; i < nl; ++i) {
+            T2_TRY_RC(wg_pack_conv_t(t[tt.in_w(k, i)], packed + bl.flows[k].conv_t[i], nc, s));
+            T2_TRY_RC(wg_pack_cond_t(t[tt.cond_w(k)] + (size_t)2 * nc * i * n_cond, packed + bl.flows[k].cond_t[i], nc, n_cond, s));
+            T2_TRY_RC(wg_pack_rs_t(t[tt.rs_w(k, i)], packed + bl.flows[k].rs_t[i], nc, i == nl - 1, s));
+        }
+    return 0;
+}
+
+static int wg_logdet_model(const t2_waveglow_config& c, const float* packed, float* logdet, hipStream_t s) {
+    WgLayout lay;
+    T2_TRY_RC(wg_layout(c, &lay));
+    T2_REQUIRE(packed && logdet, "t2_waveglow_logdet: null pointer");
+    for (int k = 0; k < c.n_flows; ++k) T2_TRY_RC(wg_logdet(packed + lay.flows[k].winv, lay.flows[k].c, 1, logdet + k, s));
     return 0;
 }
 
@@ -782,18 +120,18 @@ struct WgTimer {
 
 static int wg_infer(const t2_waveglow_config& c, const t2_waveglow_infer_args& a, hipStream_t s) {
     WgLayout lay;
-    t2_waveglow_plan_info pl;
-    T2_TRY_RC(wg_layout(c, nullptr));
+    WgInferPlan pl;
+    T2_TRY_RC(wg_layout(c, &lay));
     T2_REQUIRE(a.n_mel == c.n_mel_channels, "t2_waveglow_infer: the mel has %d channels, the model takes %d", a.n_mel, c.n_mel_channels);
-    T2_TRY_RC(wg_plan(c, a.B, a.T, &pl, &lay));
+    T2_TRY_RC(wg_plan(c, lay, a.B, a.T, &pl));
     T2_REQUIRE(a.packed && a.mel && a.workspace && a.audio && a.noise_host, "t2_waveglow_infer: null pointer");
     T2_REQUIRE(a.n_noise == lay.n_planes, "t2_waveglow_infer: %d noise planes given, the model draws %d", a.n_noise, lay.n_planes);
     for (int i = 0; i < a.n_noise; ++i) T2_REQUIRE(a.noise_host[i], "t2_waveglow_infer: noise plane %d is null", i);
     const int B = a.B, nc = c.n_channels, G = c.n_group, n_cond = c.n_mel_channels * G;
-    const long L = pl.L;
-    const size_t per = round4((size_t)B * L);
-    float* spect = a.workspace; float* x = spect + per * n_cond; float* out = x + per * nc; float* acts = out + per * nc;
-    float* bufs[2] = {acts + per * nc, acts + per * nc + per * G};
+    const long L = pl.info.L;
+    const WgFlowWs& ws = pl.ws;
+    float* spect = a.workspace + ws.spect; float* x = a.workspace + ws.x; float* out = a.workspace + ws.out; float* acts = a.workspace + ws.acts;
+    float* bufs[2] = {a.workspace + ws.bufs[0], a.workspace + ws.bufs[1]};
 
     WgTimer tm{a.kernel_ms_host, T2_WAVEGLOW_KERNELS, s, "t2_waveglow_infer"};
     int rc = 0;
@@ -823,89 +161,27 @@ done:
     return tm.finish(rc);
 }
 
-// ------------------------------------------------------------------------------------------------------------------
-// the forward direction: audio -> z, log_s, log det W and the negative log-likelihood (glow.py:207-249, :48-59)
-// ------------------------------------------------------------------------------------------------------------------
-static int wg_forward_plan(const t2_waveglow_config& c, int B, int T, long N, t2_waveglow_forward_info* out, WgLayout* lay) {
-    WgLayout L;
-    T2_TRY_RC(wg_layout(c, &L));
-    T2_REQUIRE(B >= 1 && B <= 65535, "waveglow forward: B=%d outside 1..65535", B);
-    T2_REQUIRE(T >= 1, "waveglow forward: T=%d frames, must be at least 1", T);
-    T2_REQUIRE(N >= c.n_group, "waveglow forward: n_samples=%ld is shorter than one group of n_group=%d", N, c.n_group);
-    const long have = ((long)T - 1) * kWgUpStride + kWgUpK;
-    T2_REQUIRE(N <= have, "waveglow forward: n_samples=%ld, but the upsampled mel of T=%d frames has only %ld (glow.py:216)", N, T, have);
-    const long cols = N / c.n_group;
-    T2_REQUIRE(cols <= (long)INT32_MAX / 2, "waveglow forward: L=%ld exceeds the limit of %d columns per row", cols, INT32_MAX / 2);
-    if (out) {
-        int rows = 0;
-        for (const WgFlow& f : L.flows) rows += f.n_half;
-        out->L = cols; out->n_log_s_rows = rows; out->n_tensors = L.n_tensors;
-        out->n_blocks = (cols + 255) / 256;
-        out->n_partials = (size_t)2 * c.n_flows * B * out->n_blocks;
-        const size_t per = round4((size_t)B * cols);
-        out->workspace_bytes = per * ((size_t)c.n_mel_channels * c.n_group + 3 * (size_t)c.n_channels + 2 * (size_t)c.n_group) * sizeof(float) +
-                               (out->n_partials + (size_t)B * (c.n_flows + 2)) * sizeof(double);
-        out->packed_bytes = L.total * sizeof(float);
-    }
-    if (lay) *lay = L;
-    return 0;
-}
-
-static int wg_logdet_model(const t2_waveglow_config& c, const float* packed, float* logdet, hipStream_t s) {
-    WgLayout lay;
-    T2_TRY_RC(wg_layout(c, &lay));
-    T2_REQUIRE(packed && logdet, "t2_waveglow_logdet: null pointer");
-    for (int k = 0; k < c.n_flows; ++k) T2_TRY_RC(wg_logdet(packed + lay.flows[k].winv, lay.flows[k].c, 1, logdet + k, s));
-    return 0;
-}
-
-// What the training forward keeps for the backward, in floats from the start of `saved` (per = B * L rounded up to 4):
-// spect [B, n_mel*G, L] once; per flow the mixed audio_in [B, c_k, L] and out [B, nc, L]; per flow and layer x_i, tanh(u_a),
-// sigmoid(u_b), [B, nc, L] each.  The pre-mix audio of flow k > 0 is cat(a0, a1')[n_peel:] of flow k - 1, which the tail backward
-// recomputes anyway; flow 0's is the regrouped audio itself.
-struct WgSaved {
-    size_t per, nc, nl, n_cond;
-    std::vector<size_t> base, ch;
-    size_t total;
-    size_t ain(int k) const { return base[k]; }
-    size_t out(int k) const { return base[k] + per * ch[k]; }
-    size_t x(int k, int i) const { return out(k) + per * nc * (1 + 3 * (size_t)i); }
-    size_t t(int k, int i) const { return x(k, i) + per * nc; }
-    size_t g(int k, int i) const { return x(k, i) + 2 * per * nc; }
-};
-static WgSaved wg_saved(const t2_waveglow_config& c, const WgLayout& lay, int B, long L) {
-    WgSaved sv;
-    sv.per = round4((size_t)B * L); sv.nc = c.n_channels; sv.nl = c.n_layers; sv.n_cond = (size_t)c.n_mel_channels * c.n_group;
-    size_t off = sv.per * sv.n_cond;
-    for (const WgFlow& f : lay.flows) {
-        sv.base.push_back(off); sv.ch.push_back(f.c);
-        off += sv.per * ((size_t)f.c + sv.nc * (1 + 3 * sv.nl));
-    }
-    sv.total = off;
-    return sv;
-}
-
 // saved: null for analyze / nll; the training forward's buffer of wg_saved(..).total floats otherwise: the same launches in the
 // same order on the same packed weights, with the activations the backward reads left in `saved` instead of the workspace.
 static int wg_forward(const t2_waveglow_config& c, const t2_waveglow_forward_args& a, hipStream_t s, float* saved = nullptr) {
-    WgLayout lay;
-    t2_waveglow_forward_info pl;
-    T2_TRY_RC(wg_forward_plan(c, a.B, a.T, a.n_samples, &pl, &lay));      // judges the configuration first
+    WgForwardPlan pl;
+    T2_TRY_RC(wg_forward_plan(c, a.B, a.T, a.n_samples, &pl));      // judges the configuration first
     T2_REQUIRE(a.n_mel == c.n_mel_channels, "t2_waveglow_forward: the mel has %d channels, the model takes %d", a.n_mel, c.n_mel_channels);
     const bool want_sums = a.sums || a.nll_item || a.loss;
     T2_REQUIRE(a.packed && a.mel && a.audio && a.workspace && (a.z || want_sums), "t2_waveglow_forward: null pointer");
     T2_REQUIRE(a.logdet_w || !(want_sums || a.logdet), "t2_waveglow_forward: logdet_w is null, but a sum or logdet is asked for");
     T2_REQUIRE(!want_sums || a.sigma > 0.f, "t2_waveglow_forward: sigma=%g must be positive", (double)a.sigma);
     for (int k = 0; a.log_s_host && k < c.n_flows; ++k) T2_REQUIRE(a.log_s_host[k], "t2_waveglow_forward: log_s pointer %d is null", k);
-    const int B = a.B, nc = c.n_channels, G = c.n_group, n_cond = c.n_mel_channels * G, nblk = (int)pl.n_blocks;
-    const long L = pl.L;
-    const size_t per = round4((size_t)B * L);
-    float* spect = a.workspace; float* x = spect + per * n_cond; float* out = x + per * nc; float* acts = out + per * nc;
-    float* bufs[2] = {acts + per * nc, acts + per * nc + per * G};
-    double* part = reinterpret_cast<double*>(bufs[1] + per * G);          // the floats before it are a multiple of 4: 16-byte aligned
-    double* part_z = part + (size_t)c.n_flows * B * nblk;
-    double* item = part + pl.n_partials;
-    double* sums = a.sums ? a.sums : item + B;
+    const WgLayout& lay = pl.lay;
+    const int B = a.B, nc = c.n_channels, G = c.n_group, n_cond = c.n_mel_channels * G, nblk = (int)pl.info.n_blocks;
+    const long L = pl.info.L;
+    const WgFlowWs& ws = pl.ws;
+    float* spect = a.workspace + ws.spect; float* x = a.workspace + ws.x; float* out = a.workspace + ws.out; float* acts = a.workspace + ws.acts;
+    float* bufs[2] = {a.workspace + ws.bufs[0], a.workspace + ws.bufs[1]};
+    double* part = reinterpret_cast<double*>(a.workspace + ws.part_s);
+    double* part_z = reinterpret_cast<double*>(a.workspace + ws.part_z);
+    double* item = reinterpret_cast<double*>(a.workspace + ws.item);
+    double* sums = a.sums ? a.sums : reinterpret_cast<double*>(a.workspace + ws.sums);
 
     WgSaved sv;
     if (saved) { sv = wg_saved(c, lay, B, L); spect = saved; }
@@ -944,580 +220,26 @@ static int wg_forward(const t2_waveglow_config& c, const t2_waveglow_forward_arg
 done:
     return tm.finish(rc);
 }
-// ------------------------------------------------------------------------------------------------------------------
+
 // the backward of the forward direction: gradients of every folded tensor from dz and the dlog_s[k]
-// ------------------------------------------------------------------------------------------------------------------
-// Weight gradient  C[m][n] = sum_b sum_l A[b][m][l] * Bop[b][n][l + shift_n]: both operands are contiguous along the reduction, so
-// a workgroup stages 128 rows of each over 32 time steps in LDS (coalesced along time, guarded at both ends) and the MFMA reads
-// its 32 rows at one time step: lanes stride by the row stride, 34 floats, which puts rows 0..31 of both k-halves on 64 distinct
-// banks.  The columns n come in segments (x at three shifts, spect, a row of ones whose column is the bias gradient); a tile of
-// 128 columns lies inside one segment.  The reduction over (item, chunk of 32 steps) is split into `nsplit` contiguous runs that
-// depend on the shape alone; every run writes a partial plane, which wg_wgrad_reduce_kernel adds in ascending order in fp64.
-constexpr int kWgGradTile = 128, kWgGradTL = 32, kWgGradStride = 34, kWgGradMaxSeg = 5, kWgGradMaxSplit = 64;
-static_assert(kWgGradStride % 4 == 2 && kWgGradStride >= kWgGradTL, "rows 0..31 x 2 k-halves on 64 distinct banks");
-struct WgGradSeg { const float* src; int C, Cbuf, shift, tile0, col0, vec; }; // src null: ones; Cbuf: channels per item of the buffer; vec: 16-byte loads
-struct WgGradDst { float* dst; float* dst2; long rs, cs; };                 // element (m, ch) of a segment goes to dst[m*rs + ch*cs]
-struct WgGrad {
-    const float* a; float* part;
-    WgGradSeg seg[kWgGradMaxSeg]; WgGradDst dst[kWgGradMaxSeg];
-    int nseg, M, Mbuf, B, mtiles, ntiles, Ntot, nchunk, per, nsplit, avec; long L;
-};
-
-__global__ void __launch_bounds__(256) wg_wgrad_kernel(WgGrad p) {
-    __shared__ float As[kWgGradTile * kWgGradStride], Bs[kWgGradTile * kWgGradStride];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, wm = wave & 1, wn = wave >> 1, hk = lane >> 5;
-    const int mt = blockIdx.x % p.mtiles, nt = blockIdx.x / p.mtiles;
-    int si = 0;
-    for (int s = 1; s < p.nseg; ++s)
-        if (nt >= p.seg[s].tile0) si = s;
-    const WgGradSeg sg = p.seg[si];
-    const int ch0 = (nt - sg.tile0) * kWgGradTile, m0 = mt * kWgGradTile;
-    const int total = p.B * p.nchunk, u0 = blockIdx.y * p.per, u1 = min(total, u0 + p.per);
-    f32x16 acc[2][2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i) { acc[i][0] = f32x16{0}; acc[i][1] = f32x16{0}; }
-    for (int u = u0; u < u1; ++u) {
-        const int b = u / p.nchunk;
-        const long l0 = (long)(u % p.nchunk) * kWgGradTL;
-        if (u > u0) __syncthreads();               // every wave is done reading the previous slabs
-        // 16-byte loads where L, the shift and the base address are multiples of four floats (a quad is then inside the row or
-        // outside it as a whole); element by element otherwise.  Both branches are uniform over the workgroup.
-        if (p.avec) {
-            for (int idx = threadIdx.x; idx < kWgGradTile * kWgGradTL / 4; idx += 256) {
-                const int row = idx / (kWgGradTL / 4), col = idx % (kWgGradTL / 4) * 4, m = m0 + row;
-                const long t = l0 + col;
-                f32x4 v = {0.f, 0.f, 0.f, 0.f};
-                if (m < p.M && t < p.L) v = *reinterpret_cast<const f32x4*>(p.a + ((size_t)b * p.Mbuf + m) * p.L + t);
-                float* d = As + row * kWgGradStride + col;
-                d[0] = v.x; d[1] = v.y; d[2] = v.z; d[3] = v.w;
-            }
-        } else {
-            for (int idx = threadIdx.x; idx < kWgGradTile * kWgGradTL; idx += 256) {
-                const int row = idx / kWgGradTL, col = idx % kWgGradTL, m = m0 + row;
-                const long t = l0 + col;
-                As[row * kWgGradStride + col] = (m < p.M && t < p.L) ? p.a[((size_t)b * p.Mbuf + m) * p.L + t] : 0.f;
-            }
-        }
-        if (sg.vec) {
-            for (int idx = threadIdx.x; idx < kWgGradTile * kWgGradTL / 4; idx += 256) {
-                const int row = idx / (kWgGradTL / 4), col = idx % (kWgGradTL / 4) * 4, ch = ch0 + row;
-                const long t = l0 + col, tb = t + sg.shift;
-                f32x4 v = {0.f, 0.f, 0.f, 0.f};
-                if (ch < sg.C && t < p.L && tb >= 0 && tb < p.L) {
-                    if (sg.src) v = *reinterpret_cast<const f32x4*>(sg.src + ((size_t)b * sg.Cbuf + ch) * p.L + tb);
-                    else v = f32x4{1.f, 1.f, 1.f, 1.f};
-                }
-                float* d = Bs + row * kWgGradStride + col;
-                d[0] = v.x; d[1] = v.y; d[2] = v.z; d[3] = v.w;
-            }
-        } else {
-            for (int idx = threadIdx.x; idx < kWgGradTile * kWgGradTL; idx += 256) {
-                const int row = idx / kWgGradTL, col = idx % kWgGradTL, ch = ch0 + row;
-                const long t = l0 + col, tb = t + sg.shift;
-                float v = 0.f;
-                if (ch < sg.C && t < p.L && tb >= 0 && tb < p.L) v = sg.src ? sg.src[((size_t)b * sg.Cbuf + ch) * p.L + tb] : 1.f;
-                Bs[row * kWgGradStride + col] = v;
-            }
-        }
-        __syncthreads();
-        const float* ap = As + (wm * 64 + (lane & 31)) * kWgGradStride + hk;
-        const float* bp = Bs + (wn * 64 + (lane & 31)) * kWgGradStride + hk;
-#pragma unroll
-        for (int kk = 0; kk < kWgGradTL / 2; ++kk) {
-            const float a0 = ap[2 * kk], a1 = ap[32 * kWgGradStride + 2 * kk], b0 = bp[2 * kk], b1 = bp[32 * kWgGradStride + 2 * kk];
-            acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b0, acc[0][0], 0, 0, 0);
-            acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b1, acc[0][1], 0, 0, 0);
-            acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b0, acc[1][0], 0, 0, 0);
-            acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b1, acc[1][1], 0, 0, 0);
-        }
-    }
-    // lane holds column (of C) lane & 31 and rows (e&3) + 8*(e>>2) + 4*hk of each 32x32 tile
-    float* pp = p.part + (size_t)blockIdx.y * p.M * p.Ntot;
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            const int ch = ch0 + wn * 64 + j * 32 + (lane & 31);
-            if (ch >= sg.C) continue;
-#pragma unroll
-            for (int e = 0; e < 16; ++e) {
-                const int m = m0 + wm * 64 + i * 32 + (e & 3) + 8 * (e >> 2) + 4 * hk;
-                if (m < p.M) pp[(size_t)m * p.Ntot + sg.col0 + ch] = acc[i][j][e];
-            }
-        }
-}
-
-__global__ void __launch_bounds__(256) wg_wgrad_reduce_kernel(WgGrad p) {
-    const size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x, plane = (size_t)p.M * p.Ntot;
-    if (idx >= plane) return;
-    const int m = (int)(idx / p.Ntot), n = (int)(idx % p.Ntot);
-    double acc = 0.0;
-    for (int y = 0; y < p.nsplit; ++y) acc += (double)p.part[(size_t)y * plane + idx];
-    int si = 0;
-    for (int s = 1; s < p.nseg; ++s)
-        if (n >= p.seg[s].col0) si = s;
-    const WgGradDst d = p.dst[si];
-    const size_t o = (size_t)m * d.rs + (size_t)(n - p.seg[si].col0) * d.cs;
-    d.dst[o] = (float)acc;
-    if (d.dst2) d.dst2[o] = (float)acc;
-}
-
-// sums of the products dn[r] * v[c] (r, c < Cn) over the wave, in fp64 from exact products, to part[r * Cn + c] (lane 0 writes)
-__device__ __forceinline__ void wg_mix_grad(const float (&dn)[8], const float (&vn)[8], int Cn, double* part) {
-#pragma unroll
-    for (int r = 0; r < 8; ++r)
-#pragma unroll
-        for (int c = 0; c < 8; ++c)
-            if (r < Cn && c < Cn) {
-                const double v = wg_wave_sum((double)dn[r] * (double)vn[c]);
-                if ((threadIdx.x & 63) == 0) part[r * Cn + c] = v;
-            }
-}
-
-struct WgTailBwd {
-    const float* out; const float* w_end; const float* b_end; const float* in;        // kept by the forward: out, audio_in of this flow
-    const float* wnext; const float* dnext;        // W_{k+1} [Cn][Cn] and d(audio_in_{k+1}) [B, Cn, L]; unused on the last flow
-    const float* dz; const float* dlog_s;          // nullable: upstream gradients on z [B, G, L] and on log_s[k] [B, n_half, L]
-    float* d_out; float* d_in;                     // [B, nc, L]; [B, C, L]: d(audio_in) but for W_start^T dx, which wg_start_bwd adds
-    double* part;                                  // [B * blocks * 4 waves][C*nc + C + Cn*Cn]: dW_end, db_end, dW_{k+1}
-    int nc, n_half, n_peel, G, zoff; long L;
-};
-// One flow's tail backwards, one thread per (item, column).  dV, the gradient on cat(a0, a1'), is dz for the channels that left
-// for z and W_{k+1}^T d(audio_in_{k+1}) for the rest; (b, s) = end(out) is recomputed as the forward computes it;
-// db = dV[n_half:], ds = db * exp(s) * a1 + dlog_s, da1 = db * exp(s), d_out = W_end^T [db; ds].  The sums over (item, column)
-// -- dW_end = [db; ds] out^T, db_end, dW_{k+1} = d(audio_in_{k+1}) v[n_peel:]^T -- leave as one fp64 partial per wave.
-__global__ void __launch_bounds__(256) wg_tail_bwd_kernel(WgTailBwd p) {
-    __shared__ float we[8 * 512], be[8], wi[64];
-    const int nh = p.n_half, C = 2 * nh, Cn = C - p.n_peel;
-    for (int i = threadIdx.x; i < C * p.nc; i += 256) we[i] = p.w_end[i];
-    if (threadIdx.x < C) be[threadIdx.x] = p.b_end[threadIdx.x];
-    if (threadIdx.x < Cn * Cn) wi[threadIdx.x] = p.wnext[threadIdx.x];
-    __syncthreads();
-    const long t = (long)blockIdx.x * 256 + threadIdx.x;
-    const bool valid = t < p.L;
-    const int b = blockIdx.y;
-    const float* ob = p.out + (size_t)b * p.nc * p.L + (valid ? t : 0);
-    float e[8], v[8], dn[8], dV[8];
-#pragma unroll
-    for (int r = 0; r < 8; ++r) { e[r] = 0.f; v[r] = 0.f; dn[r] = 0.f; dV[r] = 0.f; }
-    if (valid) {
-        float o[8];
-#pragma unroll
-        for (int r = 0; r < 8; ++r) o[r] = 0.f;
-        for (int c = 0; c < p.nc; ++c) {
-            const float x = ob[(size_t)c * p.L];
-#pragma unroll
-            for (int r = 0; r < 8; ++r)
-                if (r < C) o[r] = fmaf(we[r * p.nc + c], x, o[r]);
-        }
-#pragma unroll
-        for (int r = 0; r < 8; ++r)
-            if (r < Cn) dn[r] = p.dnext[((size_t)b * Cn + r) * p.L + t];
-#pragma unroll
-        for (int r = 0; r < 8; ++r) {
-            if (r < p.n_peel) {
-                dV[r] = p.dz ? p.dz[((size_t)b * p.G + p.zoff + r) * p.L + t] : 0.f;
-            } else if (r < C) {
-                float y = 0.f;
-#pragma unroll
-                for (int q = 0; q < 8; ++q)
-                    if (q < Cn) y = fmaf(wi[q * Cn + r - p.n_peel], dn[q], y);
-                dV[r] = y;
-            }
-        }
-        const float* ib = p.in + (size_t)b * C * p.L + t;
-#pragma unroll
-        for (int h = 0; h < 4; ++h) {
-            if (h < nh) {
-                const float a0 = ib[(size_t)h * p.L], a1 = ib[(size_t)(nh + h) * p.L];
-                float bb = 0.f, s = 0.f, db = 0.f, da0 = 0.f;
-#pragma unroll
-                for (int r = 0; r < 8; ++r) {       // o[h], dV[h] and o[nh + h], dV[nh + h] without a dynamic register index
-                    if (r == h) { bb = o[r] + be[r]; da0 = dV[r]; }
-                    if (r == nh + h) { s = o[r] + be[r]; db = dV[r]; }
-                }
-                const float es = expf(s), da1 = db * es;
-                const float ds = fmaf(da1, a1, p.dlog_s ? p.dlog_s[((size_t)b * nh + h) * p.L + t] : 0.f);
-                const float y1 = fmaf(es, a1, bb);
-                p.d_in[((size_t)b * C + h) * p.L + t] = da0;
-                p.d_in[((size_t)b * C + nh + h) * p.L + t] = da1;
-#pragma unroll
-                for (int r = 0; r < 8; ++r) {
-                    if (r == h) { v[r] = a0; e[r] = db; }
-                    if (r == nh + h) { v[r] = y1; e[r] = ds; }
-                }
-            }
-        }
-    }
-    const int lane = threadIdx.x & 63;
-    double* part = p.part + (((size_t)b * gridDim.x + blockIdx.x) * 4 + (threadIdx.x >> 6)) * ((size_t)C * p.nc + C + Cn * Cn);
-    for (int c = 0; c < p.nc; ++c) {
-        const float x = valid ? ob[(size_t)c * p.L] : 0.f;
-        float d = 0.f;
-#pragma unroll
-        for (int r = 0; r < 8; ++r)
-            if (r < C) d = fmaf(we[r * p.nc + c], e[r], d);
-        if (valid) p.d_out[((size_t)b * p.nc + c) * p.L + t] = d;
-#pragma unroll
-        for (int r = 0; r < 8; ++r)
-            if (r < C) {
-                const double w = wg_wave_sum((double)e[r] * (double)x);
-                if (lane == 0) part[(size_t)r * p.nc + c] = w;
-            }
-    }
-#pragma unroll
-    for (int r = 0; r < 8; ++r)
-        if (r < C) {
-            const double w = wg_wave_sum((double)e[r]);
-            if (lane == 0) part[(size_t)C * p.nc + r] = w;
-        }
-    float vn[8];
-#pragma unroll
-    for (int c = 0; c < 8; ++c) {
-        vn[c] = 0.f;
-#pragma unroll
-        for (int r = 0; r < 8; ++r)
-            if (r == p.n_peel + c) vn[c] = v[r];
-    }
-    wg_mix_grad(dn, vn, Cn, part + (size_t)C * p.nc + C);
-}
-
-// dW_0 [G][G] = sum d(audio_in_0)[b, r, l] * audio[b, l*G + g]: the partials of flow 0's mix, whose input is the regrouped audio
-__global__ void __launch_bounds__(256) wg_head_bwd_kernel(const float* __restrict__ d_in, const float* __restrict__ audio, int G, long N, long L,
-                                                         double* __restrict__ part) {
-    const long l = (long)blockIdx.x * 256 + threadIdx.x;
-    const int b = blockIdx.y;
-    float dn[8], vn[8];
-#pragma unroll
-    for (int g = 0; g < 8; ++g) {
-        const bool ok = l < L && g < G;
-        dn[g] = ok ? d_in[((size_t)b * G + g) * L + l] : 0.f;
-        vn[g] = ok ? audio[(size_t)b * N + (size_t)l * G + g] : 0.f;
-    }
-    wg_mix_grad(dn, vn, G, part + (((size_t)b * gridDim.x + blockIdx.x) * 4 + (threadIdx.x >> 6)) * ((size_t)G * G));
-}
-
-// dst_j[i] = sum over the slots (ascending, fp64) of part[slot][off_j + i], rounded to fp32 once: finishes the partials above
-struct WgFinish { const double* part; size_t nslots, stride; float* dst[3]; int n[3]; };
-__global__ void __launch_bounds__(256) wg_finish_kernel(WgFinish p) {
-    int idx = blockIdx.x * 256 + threadIdx.x;
-    const int at = idx;
-    int j = 0;
-    while (j < 3 && idx >= p.n[j]) { idx -= p.n[j]; ++j; }
-    if (j == 3) return;
-    double acc = 0.0;
-    for (size_t sl = 0; sl < p.nslots; ++sl) acc += p.part[sl * p.stride + at];
-    if (p.dst[j]) p.dst[j][idx] = (float)acc;
-}
-
-// d(audio_in)[b, h, t] += sum_c w_start[c][h] * dx[b, c, t] (c ascending), h < n_half: the rows of a0 that fed `start`
-__global__ void __launch_bounds__(256) wg_start_bwd_kernel(const float* __restrict__ dx, const float* __restrict__ w, float* __restrict__ d_in, int nc,
-                                                          int ctot, int n_half, long L) {
-    __shared__ float ws[512 * 4];
-    for (int i = threadIdx.x; i < nc * n_half; i += 256) ws[i] = w[i];
-    __syncthreads();
-    const long t = (long)blockIdx.x * 256 + threadIdx.x;
-    if (t >= L) return;
-    const int b = blockIdx.y;
-    float a[4] = {0.f, 0.f, 0.f, 0.f};
-    for (int c = 0; c < nc; ++c) {
-        const float d = dx[((size_t)b * nc + c) * L + t];
-#pragma unroll
-        for (int h = 0; h < 4; ++h)
-            if (h < n_half) a[h] = fmaf(ws[c * n_half + h], d, a[h]);
-    }
-#pragma unroll
-    for (int h = 0; h < 4; ++h)
-        if (h < n_half) d_in[((size_t)b * ctot + h) * L + t] += a[h];
-}
-
-// The upsample's weight gradient: dW_up[ci][co][r + 256 m] = sum_b sum_q mel[b, ci, q - m] * d_up[b, co, 256 q + r] with
-// d_up[b, co, s] = d_spect[b, co*G + s % G, s / G] for s < Lg*G (the frames q past T, whose taps reach back into the mel, included).
-// One thread per (ci, co, tap), b then q ascending, in fp64: K is only B * (T + 3).
-__global__ void __launch_bounds__(256) wg_up_bwd_kernel(const float* __restrict__ mel, const float* __restrict__ d_spect, float* __restrict__ dw, int B,
-                                                       int n_mel, int T, int G, long Lg, int Nq) {
-    const int j = blockIdx.x * 256 + threadIdx.x, co = blockIdx.y, ci = blockIdx.z;      // j < 1024: one workgroup row per m
-    const int r = j % kWgUpStride, m = j / kWgUpStride;
-    double acc = 0.0;
-    for (int b = 0; b < B; ++b) {
-        const float* mb = mel + ((size_t)b * n_mel + ci) * T;
-        const float* db = d_spect + (size_t)b * n_mel * G * Lg + (size_t)co * G * Lg;
-        for (int q = m; q < Nq && q - m < T; ++q) {
-            const long s = (long)q * kWgUpStride + r, l = s / G;
-            if (l < Lg) acc += (double)mb[q - m] * (double)db[(size_t)(s % G) * Lg + l];
-        }
-    }
-    dw[((size_t)ci * n_mel + co) * kWgUpK + j] = (float)acc;
-}
-// db_up[co] = sum over b, the G rows of co and l of d_spect: thread j takes elements j, j + 256, .. ascending, then a tree in LDS
-__global__ void __launch_bounds__(256) wg_up_bias_bwd_kernel(const float* __restrict__ d_spect, float* __restrict__ db, int B, int n_mel, int G, long Lg) {
-    __shared__ double red[256];
-    const int co = blockIdx.x;
-    const size_t row = (size_t)G * Lg;
-    double acc = 0.0;
-    for (int b = 0; b < B; ++b) {
-        const float* p = d_spect + ((size_t)b * n_mel + co) * row;
-        for (size_t i = threadIdx.x; i < row; i += 256) acc += (double)p[i];
-    }
-    red[threadIdx.x] = acc;
-    __syncthreads();
-    for (int w = 128; w >= 1; w >>= 1) {
-        if (threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) db[co] = (float)red[0];
-}
-
-// ---- host
-// packed[mtile][step][pg][lane][i] as wg_pack_kernel lays it out, from strided reads: segment 0 element (row, k, tap) is
-// w0[base0 + row*r0 + k*k0 + tap*j0], segment 1 element (row, k) is w1[row*r1 + k*k1]: the transposed operands of the data gradients
-struct WgPackT { const float* w0; const float* w1; float* out; int rows, K0, K1, taps, nch0, nch1; long base0, r0, k0, j0, r1, k1; size_t total; };
-__global__ void __launch_bounds__(256) wg_pack_t_kernel(WgPackT p) {
-    const size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (idx >= p.total) return;
-    const int nsteps = p.nch0 * p.taps + p.nch1;
-    const int i = idx & 3, lane = (idx >> 2) & 63, pg = (idx >> 8) & 1;
-    const size_t rest = idx >> 9;
-    const int step = rest % nsteps, mt = (int)(rest / nsteps);
-    const int r = mt * 32 + (lane & 31), kloc = 2 * (4 * pg + i) + (lane >> 5);
-    float v = 0.f;
-    if (r < p.rows) {
-        if (step < p.nch0 * p.taps) {
-            const int kk = (step / p.taps) * kWgCK + kloc, j = step % p.taps;
-            if (kk < p.K0) v = p.w0[p.base0 + (long)r * p.r0 + (long)kk * p.k0 + (long)j * p.j0];
-        } else {
-            const int kk = (step - p.nch0 * p.taps) * kWgCK + kloc;
-            if (kk < p.K1) v = p.w1[(long)r * p.r1 + (long)kk * p.k1];
-        }
-    }
-    p.out[idx] = v;
-}
-static size_t wg_packed_t_floats(int rows, int k0, int taps, int k1) { return (size_t)((rows + 31) / 32) * (chunks(k0) * taps + chunks(k1)) * 512; }
-static int wg_pack_t(WgPackT p, hipStream_t s) {
-    p.nch0 = chunks(p.K0); p.nch1 = p.K1 ? chunks(p.K1) : 0;
-    p.total = wg_packed_t_floats(p.rows, p.K0, p.taps, p.K1);
-    hipLaunchKernelGGL(wg_pack_t_kernel, dim3((unsigned)((p.total + 255) / 256)), dim3(256), 0, s, p);
-    T2_LAUNCH_CHECK();
-    return 0;
-}
-// conv^T: rows c < nc, k = r < 2nc, tap j' reads du at l + (j' - 1) d, which W_in[r][c][2 - j'] multiplies
-static int wg_pack_conv_t(const float* w_in, float* out, int nc, hipStream_t s) {
-    WgPackT p{}; p.w0 = w_in; p.out = out; p.rows = nc; p.K0 = 2 * nc; p.taps = 3; p.base0 = 2; p.r0 = 3; p.k0 = (long)nc * 3; p.j0 = -1;
-    return wg_pack_t(p, s);
-}
-static int wg_pack_cond_t(const float* w_cond_i, float* out, int nc, int n_cond, hipStream_t s) {      // [2nc][n_cond] -> rows n_cond, K = 2nc
-    WgPackT p{}; p.w0 = w_cond_i; p.out = out; p.rows = n_cond; p.K0 = 2 * nc; p.taps = 1; p.r0 = 1; p.k0 = n_cond;
-    return wg_pack_t(p, s);
-}
-static int wg_pack_rs_t(const float* w_rs, float* out, int nc, int last, hipStream_t s) {             // [2nc | nc][nc] -> rows nc, K = nc (x part) | nc (out part)
-    WgPackT p{}; p.w0 = w_rs; p.out = out; p.rows = nc; p.K0 = nc; p.taps = 1; p.r0 = 1; p.k0 = nc;
-    if (!last) { p.w1 = w_rs + (size_t)nc * nc; p.K1 = nc; p.r1 = 1; p.k1 = nc; }
-    return wg_pack_t(p, s);
-}
-
-struct WgBwdFlow { size_t conv_t[T2_WAVEGLOW_MAX_LAYERS], cond_t[T2_WAVEGLOW_MAX_LAYERS], rs_t[T2_WAVEGLOW_MAX_LAYERS]; };
-struct WgBwdLayout { std::vector<WgBwdFlow> flows; size_t total; std::vector<size_t> grad; size_t grad_total; };   // grad: offset per tensor, pack order
-static int wg_bwd_layout(const t2_waveglow_config& c, const WgLayout& lay, WgBwdLayout* out) {
-    const int nc = c.n_channels, n_cond = c.n_mel_channels * c.n_group, nl = c.n_layers;
-    WgBwdLayout L;
-    size_t off = 0, g = 0;
-    auto grad = [&](size_t n) { L.grad.push_back(g); g += n; };
-    grad((size_t)c.n_mel_channels * c.n_mel_channels * kWgUpK); grad(c.n_mel_channels);
-    for (const WgFlow& f : lay.flows) {
-        WgBwdFlow bf{};
-        for (int i = 0; i < nl; ++i) {
-            bf.conv_t[i] = off; off += wg_packed_t_floats(nc, 2 * nc, 3, 0);
-            bf.cond_t[i] = off; off += wg_packed_t_floats(n_cond, 2 * nc, 1, 0);
-            bf.rs_t[i] = off; off += wg_packed_t_floats(nc, nc, 1, i < nl - 1 ? nc : 0);
-        }
-        L.flows.push_back(bf);
-        grad((size_t)nc * f.n_half); grad(nc); grad((size_t)2 * nc * nl * n_cond); grad((size_t)2 * nc * nl);
-        for (int i = 0; i < nl; ++i) { grad((size_t)2 * nc * nc * 3); grad(2 * nc); }
-        for (int i = 0; i < nl; ++i) { const size_t rows = i < nl - 1 ? 2 * nc : nc; grad(rows * nc); grad(rows); }
-        grad((size_t)f.c * nc); grad(f.c); grad((size_t)f.c * f.c);
-    }
-    L.total = off; L.grad_total = g;
-    *out = L;
-    return 0;
-}
-
-// the shape of one weight-gradient launch: tiles, the columns' segments and the split of the reduction, from the sizes alone
-static void wg_grad_shape(WgGrad* p, int M, int nseg, const int* C, int B, long L) {
-    p->M = M; p->nseg = nseg; p->B = B; p->L = L;
-    p->mtiles = (M + kWgGradTile - 1) / kWgGradTile;
-    int tiles = 0, col = 0;
-    for (int s = 0; s < nseg; ++s) {
-        p->seg[s].C = C[s]; p->seg[s].tile0 = tiles; p->seg[s].col0 = col;
-        tiles += (C[s] + kWgGradTile - 1) / kWgGradTile; col += C[s];
-    }
-    p->ntiles = tiles; p->Ntot = col;
-    p->nchunk = (int)((L + kWgGradTL - 1) / kWgGradTL);
-    const long total = (long)B * p->nchunk;
-    // at most 1024 workgroups, what 256 CUs hold at once at 4 per CU (34 816 bytes of LDS, 88 registers): one more would wait a whole round
-    long nsplit = std::min<long>(std::min<long>(kWgGradMaxSplit, total), std::max<long>(1, 1024 / (p->mtiles * tiles)));
-    p->per = (int)((total + nsplit - 1) / nsplit);
-    p->nsplit = (int)((total + p->per - 1) / p->per);
-}
-static size_t wg_grad_part_floats(int M, int nseg, const int* C, int B, long L) {
-    WgGrad p{};
-    wg_grad_shape(&p, M, nseg, C, B, L);
-    return round4((size_t)p.nsplit * M * p.Ntot);
-}
-// src / Cbuf / shift / dst of every segment are the caller's; a, Mbuf, part too
-static int wg_grad_launch(WgGrad& p, hipStream_t s, WgTimer& tm) {
-    T2_REQUIRE(p.a && p.part && (long)p.B * p.nchunk <= INT32_MAX, "waveglow weight gradient: null pointer or too many chunks");
-    auto quads = [&](const float* q, int shift) { return p.L % 4 == 0 && shift % 4 == 0 && (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
-    p.avec = quads(p.a, 0);
-    for (int i = 0; i < p.nseg; ++i) p.seg[i].vec = quads(p.seg[i].src, p.seg[i].shift);
-    int rc = 0;
-    tm.mark();
-    hipLaunchKernelGGL(wg_wgrad_kernel, dim3((unsigned)(p.mtiles * p.ntiles), (unsigned)p.nsplit), dim3(256), 0, s, p);
-    rc = tm.timed(4, hipGetLastError() == hipSuccess ? 0 : -2);
-    if (rc) { t2_set_error("waveglow weight gradient: launch failed"); return rc; }
-    tm.mark();
-    hipLaunchKernelGGL(wg_wgrad_reduce_kernel, dim3((unsigned)(((size_t)p.M * p.Ntot + 255) / 256)), dim3(256), 0, s, p);
-    rc = tm.timed(5, hipGetLastError() == hipSuccess ? 0 : -2);
-    if (rc) t2_set_error("waveglow weight gradient: reduce launch failed");
-    return rc;
-}
-
-static int wg_gate_bwd(int B, int nc, long L, int last, const float* dx, const float* d_out, const float* packed_t, const float* t, const float* g, float* du,
-                       float* acts, hipStream_t s) {
-    const char* who = "waveglow gate backward";
-    T2_TRY_RC(wg_check_common(who, B, L));
-    T2_TRY_RC(wg_check_nc(who, nc));
-    T2_REQUIRE(d_out && (last || dx) && packed_t && t && g && du && acts, "%s: null pointer", who);
-    WgGemm p{};
-    p.x0 = last ? d_out : dx; p.x1 = last ? nullptr : d_out; p.wp = packed_t; p.y0 = du; p.y1 = acts;
-    p.s0 = const_cast<float*>(t); p.s1 = const_cast<float*>(g);
-    p.C0 = nc; p.C1 = last ? 0 : nc; p.N = p.Nq = (int)L; p.taps = 1;
-    p.rows = nc; p.mtiles = (nc + 31) / 32; p.nch0 = chunks(nc); p.nch1 = last ? 0 : chunks(nc);
-    return wg_launch<kWgGateBwd>(p, B, s);
-}
-// y [B, rows, L] (+)= W^T du: rows = nc with the flipped taps at distance d (dx), or rows = n_cond with one tap (d_spect)
-static int wg_data_bwd(int B, int rows, int nc, long L, int taps, int d, int first, const float* du, const float* packed_t, float* y, hipStream_t s) {
-    const char* who = "waveglow conv backward";
-    T2_TRY_RC(wg_check_common(who, B, L));
-    T2_TRY_RC(wg_check_nc(who, nc));
-    T2_REQUIRE(rows >= 1 && (taps == 1 || (taps == 3 && d >= 1 && d <= kWgMaxD && (d & (d - 1)) == 0)), "%s: rows=%d, taps=%d, d=%d", who, rows, taps, d);
-    T2_REQUIRE(du && packed_t && y, "%s: null pointer", who);
-    WgGemm p{};
-    p.x0 = du; p.wp = packed_t; p.y0 = y; p.first = first;
-    p.C0 = 2 * nc; p.N = p.Nq = (int)L; p.taps = taps; p.coff0 = 0; p.cstep = taps == 3 ? d : 0; p.halo = taps == 3 ? d : 0;
-    p.rows = rows; p.mtiles = (rows + 31) / 32; p.nch0 = chunks(2 * nc);
-    return wg_launch<kWgAccum>(p, B, s);
-}
-
-static int wg_tail_bwd(int B, const WgTailBwd& p, hipStream_t s) {
-    const char* who = "waveglow tail backward";
-    const int C = 2 * p.n_half;
-    T2_TRY_RC(wg_check_common(who, B, p.L));
-    T2_TRY_RC(wg_check_nc(who, p.nc));
-    T2_REQUIRE(p.n_half >= 1 && p.n_half <= 4, "%s: n_half=%d outside 1..4", who, p.n_half);
-    T2_REQUIRE(p.n_peel >= 0 && p.n_peel <= C && p.n_peel != C - 1, "%s: %d of %d channels peeled leave no whole flow", who, p.n_peel, C);
-    T2_REQUIRE(p.zoff >= 0 && p.zoff + p.n_peel <= p.G && p.G <= 8, "%s: channels %d..%d of z lie outside its %d", who, p.zoff, p.zoff + p.n_peel, p.G);
-    T2_REQUIRE(p.out && p.w_end && p.b_end && p.in && p.d_out && p.d_in && p.part && (p.n_peel == C || (p.wnext && p.dnext)), "%s: null pointer", who);
-    hipLaunchKernelGGL(wg_tail_bwd_kernel, dim3((unsigned)((p.L + 255) / 256), (unsigned)B), dim3(256), 0, s, p);
-    T2_LAUNCH_CHECK();
-    return 0;
-}
-static int wg_finish(const double* part, size_t nslots, size_t stride, float* d0, int n0, float* d1, int n1, float* d2, int n2, hipStream_t s) {
-    WgFinish p{part, nslots, stride, {d0, d1, d2}, {n0, n1, n2}};
-    if (n0 + n1 + n2 == 0) return 0;
-    hipLaunchKernelGGL(wg_finish_kernel, dim3((unsigned)((n0 + n1 + n2 + 255) / 256)), dim3(256), 0, s, p);
-    T2_LAUNCH_CHECK();
-    return 0;
-}
-static int wg_head_bwd(int B, int G, long N, const float* d_in, const float* audio, double* part, float* dw, hipStream_t s) {
-    const long L = N / G;
-    const unsigned nblk = (unsigned)((L + 255) / 256);
-    hipLaunchKernelGGL(wg_head_bwd_kernel, dim3(nblk, (unsigned)B), dim3(256), 0, s, d_in, audio, G, N, L, part);
-    T2_LAUNCH_CHECK();
-    return wg_finish(part, (size_t)B * nblk * 4, (size_t)G * G, dw, G * G, nullptr, 0, nullptr, 0, s);
-}
-static int wg_start_bwd(int B, int nc, int ctot, int n_half, long L, const float* dx, const float* w, float* d_in, hipStream_t s) {
-    hipLaunchKernelGGL(wg_start_bwd_kernel, dim3((unsigned)((L + 255) / 256), (unsigned)B), dim3(256), 0, s, dx, w, d_in, nc, ctot, n_half, L);
-    T2_LAUNCH_CHECK();
-    return 0;
-}
-static int wg_up_bwd(int B, int n_mel, int T, int G, long n_samples, const float* mel, const float* d_spect, float* dw, float* db, hipStream_t s) {
-    const char* who = "waveglow upsample backward";
-    T2_TRY_RC(wg_check_common(who, B, T));
-    T2_REQUIRE(n_mel >= 1 && n_mel <= 512, "%s: n_mel_channels=%d outside 1..512", who, n_mel);
-    T2_REQUIRE(G >= 2 && G <= 8 && G % 2 == 0, "%s: n_group=%d is not even and from 2 to 8", who, G);
-    T2_REQUIRE(n_samples / G >= 1 && n_samples <= (long)T * kWgUpStride + kWgUpK - kWgUpStride, "%s: %ld samples, %d frames", who, n_samples, T);
-    T2_REQUIRE(mel && d_spect && dw && db, "%s: null pointer", who);
-    const long Lg = n_samples / G;
-    const int Nq = (int)std::max((long)T, (Lg * G + kWgUpStride - 1) / kWgUpStride);
-    hipLaunchKernelGGL(wg_up_bwd_kernel, dim3(kWgUpK / 256, (unsigned)n_mel, (unsigned)n_mel), dim3(256), 0, s, mel, d_spect, dw, B, n_mel, T, G, Lg, Nq);
-    T2_LAUNCH_CHECK();
-    hipLaunchKernelGGL(wg_up_bias_bwd_kernel, dim3((unsigned)n_mel), dim3(256), 0, s, d_spect, db, B, n_mel, G, Lg);
-    T2_LAUNCH_CHECK();
-    return 0;
-}
-
-static int wg_backward_plan(const t2_waveglow_config& c, int B, int T, long N, t2_waveglow_backward_info* out, WgLayout* lay_out, WgBwdLayout* bl_out) {
-    WgLayout lay;
-    t2_waveglow_forward_info fp;
-    T2_TRY_RC(wg_forward_plan(c, B, T, N, &fp, &lay));
-    WgBwdLayout bl;
-    T2_TRY_RC(wg_bwd_layout(c, lay, &bl));
-    if (out) {
-        const int nc = c.n_channels, G = c.n_group, n_cond = c.n_mel_channels * G;
-        const size_t per = round4((size_t)B * fp.L);
-        const int c_du[5] = {nc, nc, nc, n_cond, 1}, c_rs[2] = {nc, 1}, c_st[2] = {G / 2, 1};
-        const size_t part = std::max(wg_grad_part_floats(2 * nc, 5, c_du, B, fp.L), std::max(wg_grad_part_floats(nc, 2, c_rs, B, fp.L),
-                                                                                            wg_grad_part_floats(nc, 2, c_st, B, fp.L)));
-        out->L = fp.L; out->n_tensors = lay.n_tensors;
-        out->saved_bytes = wg_saved(c, lay, B, fp.L).total * sizeof(float);
-        out->grad_floats = bl.grad_total;
-        out->packed_bwd_bytes = bl.total * sizeof(float);
-        out->n_slots = (size_t)B * fp.n_blocks * 4;
-        out->workspace_bytes = (per * ((size_t)5 * nc + n_cond + 2 * G) + part) * sizeof(float) + out->n_slots * ((size_t)G * nc + G + G * G) * sizeof(double);
-    }
-    if (lay_out) *lay_out = lay;
-    if (bl_out) *bl_out = bl;
-    return 0;
-}
-
-static int wg_pack_backward(const t2_waveglow_config& c, const float* const* t, int n, float* packed, hipStream_t s) {
-    WgLayout lay;
-    WgBwdLayout bl;
-    T2_TRY_RC(wg_layout(c, &lay));
-    T2_TRY_RC(wg_bwd_layout(c, lay, &bl));
-    T2_REQUIRE(t && packed, "t2_waveglow_pack_backward: null pointer");
-    T2_REQUIRE(n == lay.n_tensors, "t2_waveglow_pack_backward: %d tensors given, the configuration has %d", n, lay.n_tensors);
-    for (int i = 0; i < n; ++i) T2_REQUIRE(t[i], "t2_waveglow_pack_backward: tensor %d is null", i);
-    const int nc = c.n_channels, n_cond = c.n_mel_channels * c.n_group, nl = c.n_layers;
-    int at = 2;
-    for (int k = 0; k < c.n_flows; ++k, at += 7 + 4 * nl) {
-        const float* cond_w = t[at + 2];
-        for (int i = 0; i < nl; ++i) {
-            T2_TRY_RC(wg_pack_conv_t(t[at + 4 + 2 * i], packed + bl.flows[k].conv_t[i], nc, s));
-            T2_TRY_RC(wg_pack_cond_t(cond_w + (size_t)2 * nc * i * n_cond, packed + bl.flows[k].cond_t[i], nc, n_cond, s));
-            T2_TRY_RC(wg_pack_rs_t(t[at + 4 + 2 * nl + 2 * i], packed + bl.flows[k].rs_t[i], nc, i == nl - 1, s));
-        }
-    }
-    return 0;
-}
-
 static int wg_backward(const t2_waveglow_config& c, const t2_waveglow_backward_args& a, hipStream_t s) {
-    WgLayout lay;
-    WgBwdLayout bl;
-    t2_waveglow_backward_info pl;
-    T2_TRY_RC(wg_backward_plan(c, a.B, a.T, a.n_samples, &pl, &lay, &bl));
+    WgBackwardPlan pl;
+    T2_TRY_RC(wg_backward_plan(c, a.B, a.T, a.n_samples, &pl));
     T2_REQUIRE(a.n_mel == c.n_mel_channels, "t2_waveglow_backward: the mel has %d channels, the model takes %d", a.n_mel, c.n_mel_channels);
     T2_REQUIRE(a.packed && a.packed_bwd && a.saved && a.mel && a.audio && a.workspace && a.grad, "t2_waveglow_backward: null pointer");
+    const WgLayout& lay = pl.lay;
+    const WgTensors& tt = lay.tt;
+    const WgSaved& sv = pl.sv;
+    const WgBwdWs& ws = pl.ws;
     const int B = a.B, nc = c.n_channels, G = c.n_group, n_cond = c.n_mel_channels * G, nl = c.n_layers, nf = c.n_flows;
-    const long L = pl.L;
-    const WgSaved sv = wg_saved(c, lay, B, L);
-    const size_t per = sv.per;
-    float* dx = a.workspace; float* d_out = dx + per * nc; float* du = d_out + per * nc; float* acts = du + per * 2 * nc;
-    float* d_spect = acts + per * nc;
-    float* dbuf[2] = {d_spect + per * n_cond, d_spect + per * n_cond + per * G};
-    float* gpart = dbuf[1] + per * G;
-    double* tpart = reinterpret_cast<double*>(a.workspace + (pl.workspace_bytes - pl.n_slots * ((size_t)G * nc + G + G * G) * sizeof(double)) / sizeof(float));
+    const long L = pl.info.L;
+    float* dx = a.workspace + ws.dx; float* d_out = a.workspace + ws.d_out; float* du = a.workspace + ws.du; float* acts = a.workspace + ws.acts;
+    float* d_spect = a.workspace + ws.d_spect;
+    float* dbuf[2] = {a.workspace + ws.dbuf[0], a.workspace + ws.dbuf[1]};
+    float* gpart = a.workspace + ws.gpart;
+    double* tpart = reinterpret_cast<double*>(a.workspace + ws.tpart);
     const float* spect = a.saved;
+    auto grad = [&](int tensor) { return a.grad + pl.bl.grad[tensor]; };
     std::vector<int> zoff(nf, 0);
     for (int k = 0, z = 0; k < nf; ++k) { zoff[k] = z; z += k + 1 < nf ? lay.flows[k].c - lay.flows[k + 1].c : lay.flows[k].c; }
 
@@ -1526,66 +248,45 @@ static int wg_backward(const t2_waveglow_config& c, const t2_waveglow_backward_a
     {
         for (int k = nf - 1; k >= 0; --k) {
             const WgFlow& f = lay.flows[k];
-            const WgBwdFlow& bf = bl.flows[k];
+            const WgBwdFlow& bf = pl.bl.flows[k];
             const WgFlow* next = k + 1 < nf ? &lay.flows[k + 1] : nullptr;
-            const int t0 = 2 + k * (7 + 4 * nl), Cn = next ? next->c : 0;      // this flow's first tensor in pack order
-            float* g_end = a.grad + bl.grad[t0 + 4 + 4 * nl];
+            const int Cn = next ? next->c : 0;
             float* d_in = dbuf[k & 1];
             WgTailBwd tp{a.saved + sv.out(k), a.packed + f.end_w, a.packed + f.end_b, a.saved + sv.ain(k), next ? a.packed + next->winv : nullptr,
                          next ? dbuf[(k + 1) & 1] : nullptr, a.dz, a.dlog_s_host ? a.dlog_s_host[k] : nullptr, d_out, d_in, tpart,
                          nc, f.n_half, next ? f.c - next->c : f.c, G, zoff[k], L};
             WG_RUN(0, wg_tail_bwd(B, tp, s));
-            WG_RUN(0, wg_finish(tpart, pl.n_slots, (size_t)f.c * nc + f.c + Cn * Cn, g_end, f.c * nc, a.grad + bl.grad[t0 + 5 + 4 * nl], f.c,
-                                next ? a.grad + bl.grad[t0 + 7 + 4 * nl + 6 + 4 * nl] : nullptr, Cn * Cn, s));
+            WG_RUN(0, wg_finish(tpart, pl.info.n_slots, (size_t)f.c * nc + f.c + Cn * Cn, grad(tt.end_w(k)), f.c * nc, grad(tt.end_b(k)), f.c,
+                                next ? grad(tt.mix(k + 1)) : nullptr, Cn * Cn, s));
             for (int i = nl - 1; i >= 0; --i) {
                 const bool last = i == nl - 1;
                 WG_RUN(1, wg_gate_bwd(B, nc, L, last, dx, d_out, a.packed_bwd + bf.rs_t[i], a.saved + sv.t(k, i), a.saved + sv.g(k, i), du, acts, s));
-                float* g_rs = a.grad + bl.grad[t0 + 4 + 2 * nl + 2 * i];
-                float* g_rsb = a.grad + bl.grad[t0 + 5 + 2 * nl + 2 * i];
-                const int c_rs[2] = {nc, 1};
                 for (int half = last ? 1 : 0; half < 2; ++half) {        // rows [:nc] of res_skip take dx, rows [nc:] (all, on the last layer) d_out
-                    WgGrad gp{};
-                    wg_grad_shape(&gp, nc, 2, c_rs, B, L);
                     const size_t row0 = half && !last ? nc : 0;
-                    gp.a = half ? d_out : dx; gp.Mbuf = nc; gp.part = gpart;
-                    gp.seg[0].src = acts; gp.seg[0].Cbuf = nc; gp.dst[0] = WgGradDst{g_rs + row0 * nc, nullptr, nc, 1};
-                    gp.dst[1] = WgGradDst{g_rsb + row0, nullptr, 1, 0};
-                    rc = wg_grad_launch(gp, s, tm);
-                    if (rc != 0) goto done;
+                    const WgGrad gp = wg_grad_desc(wg_site_res_skip(nc), half ? d_out : dx, nc, acts, nc, 0, nullptr,
+                                                   WgGradOut{grad(tt.rs_w(k, i)) + row0 * nc, nullptr, grad(tt.rs_b(k, i)) + row0, nullptr}, B, L, gpart);
+                    WG_RUN(4, wg_wgrad(gp, s));
+                    WG_RUN(5, wg_wgrad_reduce(gp, s));
                 }
                 {
-                    const int c_du[5] = {nc, nc, nc, n_cond, 1};
-                    WgGrad gp{};
-                    wg_grad_shape(&gp, 2 * nc, 5, c_du, B, L);
-                    gp.a = du; gp.Mbuf = 2 * nc; gp.part = gpart;
-                    float* g_in = a.grad + bl.grad[t0 + 4 + 2 * i];
-                    for (int j = 0; j < 3; ++j) {
-                        gp.seg[j].src = a.saved + sv.x(k, i); gp.seg[j].Cbuf = nc; gp.seg[j].shift = (j - 1) * (1 << i);
-                        gp.dst[j] = WgGradDst{g_in + j, nullptr, (long)nc * 3, 3};
-                    }
-                    gp.seg[3].src = spect; gp.seg[3].Cbuf = n_cond;
-                    gp.dst[3] = WgGradDst{a.grad + bl.grad[t0 + 2] + (size_t)2 * nc * i * n_cond, nullptr, n_cond, 1};
-                    gp.dst[4] = WgGradDst{a.grad + bl.grad[t0 + 5 + 2 * i], a.grad + bl.grad[t0 + 3] + (size_t)2 * nc * i, 1, 0};
-                    rc = wg_grad_launch(gp, s, tm);
-                    if (rc != 0) goto done;
+                    const WgGradOut to{grad(tt.in_w(k, i)), grad(tt.cond_w(k)) + (size_t)2 * nc * i * n_cond, grad(tt.in_b(k, i)), grad(tt.cond_b(k)) + (size_t)2 * nc * i};
+                    const WgGrad gp = wg_grad_desc(wg_site_conv(nc, n_cond), du, 2 * nc, a.saved + sv.x(k, i), nc, 1 << i, spect, to, B, L, gpart);
+                    WG_RUN(4, wg_wgrad(gp, s));
+                    WG_RUN(5, wg_wgrad_reduce(gp, s));
                 }
                 WG_RUN(2, wg_data_bwd(B, nc, nc, L, 3, 1 << i, last, du, a.packed_bwd + bf.conv_t[i], dx, s));
                 WG_RUN(3, wg_data_bwd(B, n_cond, nc, L, 1, 0, k == nf - 1 && last, du, a.packed_bwd + bf.cond_t[i], d_spect, s));
             }
             WG_RUN(6, wg_start_bwd(B, nc, f.c, f.n_half, L, dx, a.packed + f.start_w, d_in, s));
             {
-                const int c_st[2] = {f.n_half, 1};
-                WgGrad gp{};
-                wg_grad_shape(&gp, nc, 2, c_st, B, L);
-                gp.a = dx; gp.Mbuf = nc; gp.part = gpart;
-                gp.seg[0].src = a.saved + sv.ain(k); gp.seg[0].Cbuf = f.c; gp.dst[0] = WgGradDst{a.grad + bl.grad[t0], nullptr, f.n_half, 1};
-                gp.dst[1] = WgGradDst{a.grad + bl.grad[t0 + 1], nullptr, 1, 0};
-                rc = wg_grad_launch(gp, s, tm);
-                if (rc != 0) goto done;
+                const WgGrad gp = wg_grad_desc(wg_site_start(nc, f.n_half), dx, nc, a.saved + sv.ain(k), f.c, 0, nullptr,
+                                               WgGradOut{grad(tt.start_w(k)), nullptr, grad(tt.start_b(k)), nullptr}, B, L, gpart);
+                WG_RUN(4, wg_wgrad(gp, s));
+                WG_RUN(5, wg_wgrad_reduce(gp, s));
             }
         }
-        WG_RUN(0, wg_head_bwd(B, G, a.n_samples, dbuf[0], a.audio, tpart, a.grad + bl.grad[2 + 6 + 4 * nl], s));
-        WG_RUN(7, wg_up_bwd(B, c.n_mel_channels, a.T, G, L * G, a.mel, d_spect, a.grad + bl.grad[0], a.grad + bl.grad[1], s));
+        WG_RUN(0, wg_head_bwd(B, G, a.n_samples, dbuf[0], a.audio, tpart, grad(tt.mix(0)), s));
+        WG_RUN(7, wg_up_bwd(B, c.n_mel_channels, a.T, G, L * G, a.mel, d_spect, grad(tt.up_w()), grad(tt.up_b()), s));
     }
 done:
     return tm.finish(rc);
@@ -1594,9 +295,7 @@ done:
 
 }  // namespace t2
 
-// ------------------------------------------------------------------------------------------------------------------
-// C ABI (include/t2amd.h)
-// ------------------------------------------------------------------------------------------------------------------
+// ---- C ABI (include/t2amd.h)
 using namespace t2;
 static_assert(T2_VOCODER_TIME_TILE == kVocTT, "t2amd.h mirrors the time tile");
 
@@ -1604,7 +303,12 @@ extern "C" {
 
 int t2_waveglow_plan(const t2_waveglow_config* cfg, int B, int T, t2_waveglow_plan_info* out) {
     T2_REQUIRE(cfg && out, "t2_waveglow_plan: null pointer");
-    return wg_plan(*cfg, B, T, out, nullptr);
+    WgLayout lay;
+    WgInferPlan pl;
+    T2_TRY_RC(wg_layout(*cfg, &lay));
+    T2_TRY_RC(wg_plan(*cfg, lay, B, T, &pl));
+    *out = pl.info;
+    return 0;
 }
 int t2_waveglow_pack(const t2_waveglow_config* cfg, const float* const* tensors_host, int n_tensors, float* packed, void* stream) {
     T2_REQUIRE(cfg, "t2_waveglow_pack: null configuration");
@@ -1645,7 +349,10 @@ int t2_waveglow_couple(const t2_waveglow_couple_args* a, void* stream) {
 }
 int t2_waveglow_forward_plan(const t2_waveglow_config* cfg, int B, int T, long n_samples, t2_waveglow_forward_info* out) {
     T2_REQUIRE(cfg && out, "t2_waveglow_forward_plan: null pointer");
-    return wg_forward_plan(*cfg, B, T, n_samples, out, nullptr);
+    WgForwardPlan pl;
+    T2_TRY_RC(wg_forward_plan(*cfg, B, T, n_samples, &pl));
+    *out = pl.info;
+    return 0;
 }
 int t2_waveglow_forward(const t2_waveglow_config* cfg, const t2_waveglow_forward_args* a, void* stream) {
     T2_REQUIRE(cfg && a, "t2_waveglow_forward: null pointer");
@@ -1669,15 +376,18 @@ int t2_waveglow_tail(const t2_waveglow_tail_args* a, void* stream) {
 
 int t2_waveglow_backward_plan(const t2_waveglow_config* cfg, int B, int T, long n_samples, t2_waveglow_backward_info* out) {
     T2_REQUIRE(cfg && out, "t2_waveglow_backward_plan: null pointer");
-    return wg_backward_plan(*cfg, B, T, n_samples, out, nullptr, nullptr);
+    WgBackwardPlan pl;
+    T2_TRY_RC(wg_backward_plan(*cfg, B, T, n_samples, &pl));
+    *out = pl.info;
+    return 0;
 }
 int t2_waveglow_grad_offsets(const t2_waveglow_config* cfg, size_t* offsets_host, int n_tensors) {
     T2_REQUIRE(cfg && offsets_host, "t2_waveglow_grad_offsets: null pointer");
     WgLayout lay;
     WgBwdLayout bl;
     T2_TRY_RC(wg_layout(*cfg, &lay));
-    T2_TRY_RC(wg_bwd_layout(*cfg, lay, &bl));
-    T2_REQUIRE(n_tensors == lay.n_tensors, "t2_waveglow_grad_offsets: room for %d tensors, the configuration has %d", n_tensors, lay.n_tensors);
+    wg_bwd_layout(*cfg, lay, &bl);
+    T2_REQUIRE(n_tensors == lay.tt.count(), "t2_waveglow_grad_offsets: room for %d tensors, the configuration has %d", n_tensors, lay.tt.count());
     for (int i = 0; i < n_tensors; ++i) offsets_host[i] = bl.grad[i];
     return 0;
 }
@@ -1695,11 +405,7 @@ int t2_waveglow_backward(const t2_waveglow_config* cfg, const t2_waveglow_backwa
 }
 size_t t2_waveglow_weight_grad_ws_floats(int M, int nc, int n_cond, int taps, int B, int L) {
     if (M < 1 || nc < 1 || n_cond < 0 || (taps != 1 && taps != 3) || B < 1 || L < 1) return 0;
-    int C[5], n = 0;
-    for (int j = 0; j < taps; ++j) C[n++] = nc;
-    if (n_cond) C[n++] = n_cond;
-    C[n++] = 1;
-    return wg_grad_part_floats(M, n, C, B, L);
+    return wg_grad_part_floats(WgGradSite{M, nc, taps, n_cond}, B, L);
 }
 int t2_waveglow_weight_grad(const t2_waveglow_weight_grad_args* a, void* stream) {
     const char* who = "waveglow weight gradient";
@@ -1708,23 +414,12 @@ int t2_waveglow_weight_grad(const t2_waveglow_weight_grad_args* a, void* stream)
     T2_REQUIRE(a->M >= 1 && a->M <= 1024 && a->nc >= 1 && a->nc <= 512 && a->n_cond >= 0, "%s: M=%d, nc=%d, n_cond=%d", who, a->M, a->nc, a->n_cond);
     T2_REQUIRE((a->taps == 1 && a->d == 0) || (a->taps == 3 && a->d >= 1 && a->d <= kWgMaxD), "%s: taps=%d, d=%d", who, a->taps, a->d);
     T2_REQUIRE(a->a && a->x && a->dw_x && a->db && a->workspace && (a->n_cond == 0 || (a->spect && a->dw_spect)), "%s: null pointer", who);
-    int C[5], n = 0;
-    for (int j = 0; j < a->taps; ++j) C[n++] = a->nc;
-    if (a->n_cond) C[n++] = a->n_cond;
-    C[n++] = 1;
-    WgGrad gp{};
-    wg_grad_shape(&gp, a->M, n, C, a->B, a->L);
     T2_REQUIRE((a->a_rows == 0 || a->a_rows >= a->M) && (a->x_rows == 0 || a->x_rows >= a->nc), "%s: a_rows=%d, x_rows=%d are fewer than M=%d, nc=%d", who,
                a->a_rows, a->x_rows, a->M, a->nc);
-    gp.a = a->a; gp.Mbuf = a->a_rows ? a->a_rows : a->M; gp.part = a->workspace;
-    for (int j = 0; j < a->taps; ++j) {
-        gp.seg[j].src = a->x; gp.seg[j].Cbuf = a->x_rows ? a->x_rows : a->nc; gp.seg[j].shift = (j - a->taps / 2) * a->d;
-        gp.dst[j] = WgGradDst{a->dw_x + j, nullptr, (long)a->nc * a->taps, a->taps};
-    }
-    if (a->n_cond) { gp.seg[a->taps].src = a->spect; gp.seg[a->taps].Cbuf = a->n_cond; gp.dst[a->taps] = WgGradDst{a->dw_spect, nullptr, a->n_cond, 1}; }
-    gp.dst[n - 1] = WgGradDst{a->db, a->db2, 1, 0};
-    WgTimer tm{nullptr, 0, (hipStream_t)stream, who};
-    return wg_grad_launch(gp, (hipStream_t)stream, tm);
+    const WgGrad gp = wg_grad_desc(WgGradSite{a->M, a->nc, a->taps, a->n_cond}, a->a, a->a_rows ? a->a_rows : a->M, a->x, a->x_rows ? a->x_rows : a->nc, a->d,
+                                   a->spect, WgGradOut{a->dw_x, a->dw_spect, a->db, a->db2}, a->B, a->L, a->workspace);
+    T2_TRY_RC(wg_wgrad(gp, (hipStream_t)stream));
+    return wg_wgrad_reduce(gp, (hipStream_t)stream);
 }
 int t2_waveglow_gate_backward(const t2_waveglow_gate_backward_args* a, void* stream) {
     T2_REQUIRE(a, "t2_waveglow_gate_backward: null arguments");
@@ -1765,14 +460,10 @@ int t2_waveglow_start_backward(const t2_waveglow_start_backward_args* a, void* s
     T2_REQUIRE(a->n_half >= 1 && a->n_half <= 4 && a->c >= 2 * a->n_half && a->c <= 8, "%s: n_half=%d outside 1..4 or c=%d outside 2*n_half..8", who, a->n_half, a->c);
     T2_REQUIRE(a->dx && a->w_start && a->audio_in && a->d_in && a->dw_start && a->db_start && a->workspace, "%s: null pointer", who);
     T2_TRY_RC(wg_start_bwd(a->B, a->nc, a->c, a->n_half, a->L, a->dx, a->w_start, a->d_in, (hipStream_t)stream));
-    const int c_st[2] = {a->n_half, 1};
-    WgGrad gp{};
-    wg_grad_shape(&gp, a->nc, 2, c_st, a->B, a->L);
-    gp.a = a->dx; gp.Mbuf = a->nc; gp.part = a->workspace;
-    gp.seg[0].src = a->audio_in; gp.seg[0].Cbuf = a->c; gp.dst[0] = WgGradDst{a->dw_start, nullptr, a->n_half, 1};
-    gp.dst[1] = WgGradDst{a->db_start, nullptr, 1, 0};
-    WgTimer tm{nullptr, 0, (hipStream_t)stream, who};
-    return wg_grad_launch(gp, (hipStream_t)stream, tm);
+    const WgGrad gp = wg_grad_desc(wg_site_start(a->nc, a->n_half), a->dx, a->nc, a->audio_in, a->c, 0, nullptr, WgGradOut{a->dw_start, nullptr, a->db_start, nullptr},
+                                   a->B, a->L, a->workspace);
+    T2_TRY_RC(wg_wgrad(gp, (hipStream_t)stream));
+    return wg_wgrad_reduce(gp, (hipStream_t)stream);
 }
 int t2_waveglow_head_backward(const t2_waveglow_head_backward_args* a, void* stream) {
     const char* who = "waveglow head backward";
