@@ -494,6 +494,15 @@ struct SsimBwd {
 };
 int ssim_bwd(const SsimBwd& a, hipStream_t s);
 
+inline size_t round4(size_t n) { return (n + 3) / 4 * 4; }        // buffer sizes in floats, kept to 16 bytes (several files)
+
+// ------------------------------------------------------------------ slab GEMM of the vocoder and WaveGlow (slab_gemm.h, slab_gemm.hip)
+constexpr int kSlabCK = 16;                      // operand channels per slab
+__host__ __device__ inline int slab_chunks(int k) { return (k + kSlabCK - 1) / kSlabCK; }
+inline size_t slab_packed_floats(int gates, int rows, int K0, int taps, int K1) {      // one packed operand, layout in slab_gemm.h
+    return (size_t)((rows + 31) / 32) * (slab_chunks(K0) * taps + slab_chunks(K1)) * gates * 512;
+}
+
 // ------------------------------------------------------------------ HiFi-GAN vocoder (vocoder.hip)
 constexpr int kVocTT = 128;                      // time positions per workgroup
 constexpr int kVocMaxPad = 60;                   // (k*d - d)/2 at k = 11, d = 12

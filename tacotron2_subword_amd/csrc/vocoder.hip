@@ -10,22 +10,17 @@
 //   ConvTranspose1d (stride u, kernel k = 2u, padding u/2), polyphase: output sample u*q + r reads only the taps
 //     j = (r + pad) % u + m*u (m = 0, 1) at input q + (r + pad)/u - m, so phase r is a two-tap GEMM of its own whose
 //     outputs land u apart.  No zero-stuffed input, no atomics: every output element is written once.
-// A workgroup owns kVocTT = 128 time positions of up to 128 output channels of one batch item (and one phase).  Per chunk
-// of 16 input channels it stages the slab [16][128 + halo] of the input in LDS once, with the leaky ReLU applied and zeros
-// outside [0, L); every tap reads that slab at a shifted column: lanes along time, the two k-rows of an MFMA step 288
-// floats apart (32 banks), so the reads are conflict-free, and each global load is used by all taps.  A wave computes a
-// 32 (channels) x 64 (time) tile: two accumulators share each weight fragment.  The weights are packed once (voc_pack_kernel)
-// into the order the lanes consume them, four k-steps per 16-byte load, zero-padded to whole 32-channel tiles / 16-channel
-// chunks (Cout = 8 wastes three quarters of its tile: accepted).  Epilogue: bias, optional residual, optional
-// accumulate-into-destination, scale.  The order of every sum is fixed: same bits from run to run and for an item alone
-// or in a batch.  Element offsets are 64-bit throughout.
+// The tiling, the slab staging (here with the leaky ReLU applied), the MFMA step, the epilogue's walk, the launcher and the weight
+// pack are slab_gemm.h's.  This file adds the walk over chunks and taps, the polyphase term (phase from blockIdx.y, coff0 =
+// (phase + pad)/u + 1, cstep = -1, output offset q*ostride + phase) and the epilogue: bias, optional residual, optional
+// accumulate-into-destination, scale.  Cout = 8 wastes three quarters of its 32-channel tile: accepted.  The order of every sum
+// is fixed: same bits from run to run and for an item alone or in a batch.  Element offsets are 64-bit throughout.
 #include <algorithm>
 
-#include "kernels.h"
+#include "slab_gemm.h"
 
 namespace t2 {
 
-constexpr int kVocCK = 16;                        // input channels per slab
 constexpr int kVocStride = 288;                   // slab row stride in floats: = 32 mod 64 banks, >= kVocTT + 2*kVocMaxPad
 static_assert(kVocStride % 64 == 32 && kVocStride >= kVocTT + 2 * kVocMaxPad, "slab row stride");
 
@@ -33,101 +28,45 @@ struct VocGemm {
     const float* x; const float* wp; const float* bias; const float* res; float* y;
     int Cin, Cout, Lin;                           // outputs per phase = Lin; the output row has Lin * ostride elements
     int taps, d, pad, u, transposed;              // transposed: taps = 2, phases = ostride = u
-    int halo_lo, sw;                              // slab column c holds input t0 + c - halo_lo; sw columns are staged
+    int halo_lo;                                  // slab column c holds input t0 + c - halo_lo
     int mtiles, nchunks, ostride;
     float slope, scale; int accumulate;
 };
 
 template <int WM>
 __global__ void __launch_bounds__(WM * 128) voc_gemm_kernel(VocGemm p) {
-    __shared__ float slab[kVocCK * kVocStride];
-    constexpr int kWaves = WM * 2;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int wm = wave % WM, wt = wave / WM;
+    __shared__ float slab[kSlabCK * kVocStride];
+    const int wm = (threadIdx.x >> 6) % WM;
     const int mblocks = (p.mtiles + WM - 1) / WM;
     const int phase = blockIdx.y / mblocks, mt = (blockIdx.y % mblocks) * WM + wm;
     const bool active = mt < p.mtiles;             // uniform over the wave
     const int b = blockIdx.z;
-    const long t0 = (long)blockIdx.x * kVocTT;
     // slab column of tap j for output q = t0 + c: c + coff0 + j*cstep
     const int coff0 = p.transposed ? (phase + p.pad) / p.u + 1 : 0, cstep = p.transposed ? -1 : p.d;
-    const float* xb = p.x + (size_t)b * p.Cin * p.Lin;
     const f32x4* wp = reinterpret_cast<const f32x4*>(p.wp) + (size_t)(phase * p.mtiles + (active ? mt : 0)) * p.nchunks * p.taps * 128;
-    const int tc = wt * 64 + (lane & 31), hk = lane >> 5;
-    f32x16 acc0 = {0}, acc1 = {0};
-
+    const float* xb = p.x + (size_t)b * p.Cin * p.Lin;
+    const int lane = threadIdx.x & 63, wt = (threadIdx.x >> 6) / WM, tc = wt * 64 + (lane & 31), hk = lane >> 5;
+    const long t0 = (long)blockIdx.x * kVocTT;
+    const float slope = p.slope;
+    f32x16 acc[1][2] = {{f32x16{0}, f32x16{0}}};
     for (int c = 0; c < p.nchunks; ++c) {
         if (c) __syncthreads();                    // every wave is done reading the previous slab
-        for (int row = wave; row < kVocCK; row += kWaves) {
-            const int ci = c * kVocCK + row;
-            const float* xr = xb + (size_t)ci * p.Lin;
-            for (int col = lane; col < p.sw; col += 64) {
-                const long t = t0 + col - p.halo_lo;
-                float v = 0.f;
-                if (ci < p.Cin && t >= 0 && t < p.Lin) {
-                    v = xr[t];
-                    v = v > 0.f ? v : v * p.slope;
-                }
-                slab[row * kVocStride + col] = v;
-            }
-        }
+        slab_stage<kVocStride, WM * 2>(slab, xb, p.Cin, c * kSlabCK, p.Lin, t0, p.halo_lo, [slope](float v) { return v > 0.f ? v : v * slope; });
         __syncthreads();
-        if (active) {
-            for (int j = 0; j < p.taps; ++j) {
-                const float* sb = slab + hk * kVocStride + tc + coff0 + j * cstep;
-                const f32x4* wj = wp + ((size_t)c * p.taps + j) * 128 + lane;
-#pragma unroll
-                for (int pg = 0; pg < 2; ++pg) {
-                    const f32x4 a = wj[pg * 64];
-#pragma unroll
-                    for (int i = 0; i < 4; ++i) {
-                        const float* s2 = sb + (pg * 4 + i) * 2 * kVocStride;
-                        const float b0 = s2[0], b1 = s2[32];
-                        acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(a[i], b0, acc0, 0, 0, 0);
-                        acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(a[i], b1, acc1, 0, 0, 0);
-                    }
-                }
-            }
-        }
+        if (active)
+            for (int j = 0; j < p.taps; ++j)
+                slab_mfma_step<kVocStride, 1>(slab + hk * kVocStride + tc + coff0 + j * cstep, wp + ((size_t)c * p.taps + j) * 128 + lane, acc);
     }
     if (!active) return;
-    // lane holds time column lane & 31 and rows (e&3) + 8*(e>>2) + 4*hk of each 32x32 tile
     const size_t lout = (size_t)p.Lin * p.ostride;
-#pragma unroll
-    for (int n = 0; n < 2; ++n) {
-        const long q = t0 + wt * 64 + n * 32 + (lane & 31);
-        if (q >= p.Lin) continue;
-#pragma unroll
-        for (int e = 0; e < 16; ++e) {
-            const int co = mt * 32 + (e & 3) + 8 * (e >> 2) + 4 * hk;
-            if (co >= p.Cout) continue;
-            const size_t o = ((size_t)b * p.Cout + co) * lout + (size_t)q * p.ostride + phase;
-            float v = n == 0 ? acc0[e] : acc1[e];
-            if (p.bias) v += p.bias[co];
-            if (p.res) v += p.res[o];
-            if (p.accumulate) v = p.y[o] + v;
-            p.y[o] = v * p.scale;
-        }
-    }
-}
-
-// packed[phase][mtile][chunk][tap][pg][lane][i] = W[co = 32*mtile + (lane & 31)][ci = 16*chunk + 2*(4*pg + i) + (lane >> 5)][tap]
-// (zero outside the matrix); torch layouts: Conv1d [Cout][Cin][k], ConvTranspose1d [Cin][Cout][k]
-__global__ void __launch_bounds__(256) voc_pack_kernel(const float* __restrict__ w, float* __restrict__ out, int cin, int cout, int k,
-                                                      int transposed, int u, int pad, int mtiles, int nchunks, int taps, size_t total) {
-    const size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (idx >= total) return;
-    const int i = idx & 3, lane = (idx >> 2) & 63, pg = (idx >> 8) & 1;
-    size_t rest = idx >> 9;
-    const int j = rest % taps; rest /= taps;
-    const int c = rest % nchunks; rest /= nchunks;
-    const int mt = rest % mtiles;
-    const int phase = (int)(rest / mtiles);
-    const int co = mt * 32 + (lane & 31), ci = c * kVocCK + 2 * (4 * pg + i) + (lane >> 5);
-    float v = 0.f;
-    if (co < cout && ci < cin)
-        v = transposed ? w[((size_t)ci * cout + co) * k + (phase + pad) % u + j * u] : w[((size_t)co * cin + ci) * k + j];
-    out[idx] = v;
+    slab_walk<WM, 1>(acc, mt, p.Cout, p.Lin, [=](int co, long q, const float (&a)[1]) {
+        const size_t o = ((size_t)b * p.Cout + co) * lout + (size_t)q * p.ostride + phase;
+        float v = a[0];
+        if (p.bias) v += p.bias[co];
+        if (p.res) v += p.res[o];
+        if (p.accumulate) v = p.y[o] + v;
+        p.y[o] = v * p.scale;
+    });
 }
 
 // conv_post: y[b,0,t] = tanh(bias + sum_ci sum_j w[ci][j] * lrelu(x[b,ci,t+j-3])), ci then j ascending, one fused multiply-add
@@ -177,17 +116,24 @@ static int voc_shape_check(const char* who, int Cin, int Cout, int k, int d, int
 }
 
 size_t voc_packed_floats(int Cin, int Cout, int k, int u) {
-    const size_t mtiles = (Cout + 31) / 32, nchunks = (Cin + kVocCK - 1) / kVocCK;
-    return u ? (size_t)u * mtiles * nchunks * 2 * 512 : mtiles * nchunks * k * 512;
+    return u ? (size_t)u * slab_packed_floats(1, Cout, Cin, 2, 0) : slab_packed_floats(1, Cout, Cin, k, 0);
 }
 
+// packed[phase][mtile][chunk][tap]...: Conv1d [Cout][Cin][k] is one phase; ConvTranspose1d [Cin][Cout][k] one pack per phase r (taps (r + pad) % u + j*u)
 int voc_pack(const float* w, float* packed, int Cin, int Cout, int k, int u, hipStream_t s) {
     T2_TRY_RC(voc_shape_check("vocoder pack", Cin, Cout, k, 1, u));
     T2_REQUIRE(w && packed, "vocoder pack: null pointer");
-    const size_t total = voc_packed_floats(Cin, Cout, k, u);
-    hipLaunchKernelGGL(voc_pack_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, w, packed, Cin, Cout, k, u != 0, u ? u : 1,
-                       u ? (k - u) / 2 : 0, (Cout + 31) / 32, (Cin + kVocCK - 1) / kVocCK, u ? 2 : k, total);
-    T2_LAUNCH_CHECK();
+    SlabPack p{};
+    p.gates = 1; p.rows = Cout; p.split = 1; p.s0.w = w; p.s0.K = Cin; p.out = packed;
+    if (!u) {
+        p.s0.taps = k; p.s0.rhi = (long)Cin * k; p.s0.ks = k; p.s0.ts = 1;
+        return slab_pack(p, s);
+    }
+    p.s0.taps = 2; p.s0.rhi = k; p.s0.ks = (long)Cout * k; p.s0.ts = u;
+    for (int r = 0; r < u; ++r, p.out += slab_packed_floats(1, Cout, Cin, 2, 0)) {
+        p.s0.base = (r + (k - u) / 2) % u;
+        T2_TRY_RC(slab_pack(p, s));
+    }
     return 0;
 }
 
@@ -204,26 +150,16 @@ int voc_conv(const VocConv& a, hipStream_t s) {
     p.Cin = a.Cin; p.Cout = a.Cout; p.Lin = (int)a.L;
     p.transposed = a.u != 0; p.u = a.u ? a.u : 1; p.ostride = p.u;
     p.taps = a.u ? 2 : a.k; p.d = a.u ? 1 : a.d; p.pad = a.u ? (a.k - a.u) / 2 : (a.k * a.d - a.d) / 2;
-    p.halo_lo = a.u ? 1 : p.pad; p.sw = kVocTT + 2 * p.halo_lo;
-    p.mtiles = (a.Cout + 31) / 32; p.nchunks = (a.Cin + kVocCK - 1) / kVocCK;
+    p.halo_lo = a.u ? 1 : p.pad;
+    p.mtiles = (a.Cout + 31) / 32; p.nchunks = slab_chunks(a.Cin);
     p.slope = a.slope; p.scale = a.scale; p.accumulate = a.accumulate;
-    T2_REQUIRE(p.sw <= kVocStride, "%s: halo %d does not fit the slab", who, p.halo_lo);
-    const int wm = p.mtiles >= 4 ? 4 : (p.mtiles >= 2 ? 2 : 1);
-    const long tiles = (a.L + kVocTT - 1) / kVocTT;
-    const int mblocks = (p.mtiles + wm - 1) / wm;
-    dim3 grid((unsigned)tiles, (unsigned)(mblocks * p.u), (unsigned)a.B);
-    if (wm == 4) hipLaunchKernelGGL(voc_gemm_kernel<4>, grid, dim3(512), 0, s, p);
-    else if (wm == 2) hipLaunchKernelGGL(voc_gemm_kernel<2>, grid, dim3(256), 0, s, p);
-    else hipLaunchKernelGGL(voc_gemm_kernel<1>, grid, dim3(128), 0, s, p);
-    T2_LAUNCH_CHECK();
-    return 0;
+    T2_REQUIRE(kVocTT + 2 * p.halo_lo <= kVocStride, "%s: halo %d does not fit the slab", who, p.halo_lo);
+    return slab_launch(voc_gemm_kernel<4>, voc_gemm_kernel<2>, voc_gemm_kernel<1>, p, p.mtiles, a.L, p.u, a.B, s);
 }
 
 // ------------------------------------------------------------------------------------------------------------------
 // the generator
 // ------------------------------------------------------------------------------------------------------------------
-static size_t round4(size_t n) { return (n + 3) / 4 * 4; }
-
 int hifigan_layers(const HifiganConfig& c, std::vector<HifiganLayer>* out, size_t* packed_floats) {
     T2_REQUIRE(c.resblock == 1 || c.resblock == 2, "hifigan: resblock \"%d\" is not \"1\" or \"2\"", c.resblock);
     T2_REQUIRE(c.n_mel == 80, "hifigan: %d mel channels, conv_pre takes 80", c.n_mel);

@@ -9,15 +9,11 @@
 
 namespace t2 {
 
-constexpr int kWgCK = 16;                         // operand channels per slab
 constexpr int kWgMaxD = 128;                      // dilation of layer 7
 static_assert(T2_WAVEGLOW_MAX_LAYERS == 8 && (1 << (T2_WAVEGLOW_MAX_LAYERS - 1)) == kWgMaxD, "the deepest layer's dilation fits the slab");
 enum { kWgGated = 0, kWgResSkip = 1, kWgUpsample = 2, kWgGateBwd = 3, kWgAccum = 4 };   // the last two: epilogues of the backward
 constexpr int kWgUpK = 1024, kWgUpStride = 256, kWgUpTaps = kWgUpK / kWgUpStride;
 constexpr int kWgGradTile = 128, kWgGradTL = 32, kWgGradMaxSeg = 5, kWgGradMaxSplit = 64;
-
-inline size_t round4(size_t n) { return (n + 3) / 4 * 4; }
-inline int chunks(int k) { return (k + kWgCK - 1) / kWgCK; }
 
 // ---- arguments of the kernels the drivers fill in themselves (waveglow_kernels.hip says what each field is)
 struct WgCouple {
@@ -49,6 +45,9 @@ struct WgGrad {
 // ---- waveglow_plan.hip
 int wg_check_common(const char* who, int B, long L);
 int wg_check_nc(const char* who, int nc);
+int wg_check_group(const char* who, int G);
+int wg_check_half(const char* who, int n_half);
+int wg_check_peel(const char* who, int n_peel, int C, int zoff, int G);
 int wg_gated_check(int B, int nc, int n_cond, long L, int d);
 size_t wg_packed_floats(int kind, int rows, int k0, int k1);
 size_t wg_packed_t_floats(int rows, int k0, int taps, int k1);

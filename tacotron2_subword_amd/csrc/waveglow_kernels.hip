@@ -2,9 +2,9 @@
 // them, waveglow_plan.hip says where their operands lie).
 //
 // Activations are [B][C][L] with time contiguous, L = T*256/n_group; arithmetic is exact fp32 on the matrix cores
-// (v_mfma_f32_32x32x2_f32), whatever t2_set_precision says.  Three of the five kernels of the WN are one GEMM kernel in the style of
-// vocoder.hip (lanes along time, a slab [16 channels][128 + halo] of the operand in LDS, weights packed once into the order the
-// lanes read them, a wave computing 32 rows x 64 columns), with three epilogues:
+// (v_mfma_f32_32x32x2_f32), whatever t2_set_precision says.  Three of the five kernels of the WN are one GEMM kernel on the pieces
+// that slab_gemm.h holds for this file and vocoder.hip (staging, MFMA step, epilogue walk, launcher, pack): here no transform while
+// staging, two operand segments, two accumulator pairs for the gate, and three epilogues:
 //   gated conv   Y = tanh(U[:nc]) * sigmoid(U[nc:]),  U = in_layers[i](x) + cond_layer(spect)[2nc*i : 2nc*(i+1)] as ONE GEMM with
 //                K = 3*nc (the taps read x at -d, 0, +d from the slab) + n_mel*G (spect at the same column).  Tanh row c and
 //                sigmoid row c + nc are two accumulators of the same wave: same lane, same element, same column, so the gate is
@@ -23,6 +23,7 @@
 // order; the tail, start, head and upsample backward are VALU.  No atomics, every sum in a fixed order, 64-bit element offsets.
 #include <algorithm>
 
+#include "slab_gemm.h"
 #include "waveglow.h"
 
 namespace t2 {
@@ -47,140 +48,71 @@ struct WgGemm {
 template <int WM, int MODE>
 __global__ void __launch_bounds__(WM * 128) wg_gemm_kernel(WgGemm p) {
     constexpr int GATES = MODE == kWgGated ? 2 : 1;
-    __shared__ float slab[kWgCK * kWgStride];
-    constexpr int kWaves = WM * 2;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int wm = wave % WM, wt = wave / WM;
-    const int mt = blockIdx.y * WM + wm;
+    __shared__ float slab[kSlabCK * kWgStride];
+    const int mt = blockIdx.y * WM + (threadIdx.x >> 6) % WM;
     const bool active = mt < p.mtiles;            // uniform over the wave
     const int b = blockIdx.z;
+    const f32x4* wp = reinterpret_cast<const f32x4*>(p.wp) + (size_t)(active ? mt : 0) * (p.nch0 * p.taps + p.nch1) * GATES * 128;
+    const int lane = threadIdx.x & 63, wt = (threadIdx.x >> 6) / WM, tc = wt * 64 + (lane & 31), hk = lane >> 5;
     const long t0 = (long)blockIdx.x * kVocTT;
-    const int nsteps = p.nch0 * p.taps + p.nch1;
-    const f32x4* wp = reinterpret_cast<const f32x4*>(p.wp) + (size_t)(active ? mt : 0) * nsteps * GATES * 128;
-    const int tc = wt * 64 + (lane & 31), hk = lane >> 5;
     f32x16 acc[GATES][2];
 #pragma unroll
     for (int g = 0; g < GATES; ++g) { acc[g][0] = f32x16{0}; acc[g][1] = f32x16{0}; }
-
     for (int c = 0; c < p.nch0 + p.nch1; ++c) {
         const bool seg0 = c < p.nch0;
-        const int C = seg0 ? p.C0 : p.C1, ci0 = (seg0 ? c : c - p.nch0) * kWgCK;
-        const int halo = seg0 ? p.halo : 0, sw = kVocTT + 2 * halo;
+        const int C = seg0 ? p.C0 : p.C1, ci0 = (seg0 ? c : c - p.nch0) * kSlabCK;
+        const int halo = seg0 ? p.halo : 0;
         const float* xb = (seg0 ? p.x0 : p.x1) + (size_t)b * C * p.N;
         if (c) __syncthreads();                    // every wave is done reading the previous slab
-        for (int row = wave; row < kWgCK; row += kWaves) {
-            const int ci = ci0 + row;
-            const float* xr = xb + (size_t)ci * p.N;
-            for (int col = lane; col < sw; col += 64) {
-                const long t = t0 + col - halo;
-                slab[row * kWgStride + col] = (ci < C && t >= 0 && t < p.N) ? xr[t] : 0.f;
-            }
-        }
+        slab_stage<kWgStride, WM * 2>(slab, xb, C, ci0, p.N, t0, halo, [](float v) { return v; });
         __syncthreads();
         if (active) {
             const int taps = seg0 ? p.taps : 1;
             const size_t step0 = seg0 ? (size_t)c * p.taps : (size_t)p.nch0 * p.taps + (c - p.nch0);
-            for (int j = 0; j < taps; ++j) {
-                const float* sb = slab + hk * kWgStride + tc + (seg0 ? p.coff0 + j * p.cstep : 0);
-                const f32x4* wj = wp + (step0 + j) * GATES * 128 + lane;
-#pragma unroll
-                for (int pg = 0; pg < 2; ++pg) {
-                    f32x4 a[GATES];
-#pragma unroll
-                    for (int g = 0; g < GATES; ++g) a[g] = wj[g * 128 + pg * 64];
-#pragma unroll
-                    for (int i = 0; i < 4; ++i) {
-                        const float* s2 = sb + (pg * 4 + i) * 2 * kWgStride;
-                        const float b0 = s2[0], b1 = s2[32];
-#pragma unroll
-                        for (int g = 0; g < GATES; ++g) {
-                            acc[g][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[g][i], b0, acc[g][0], 0, 0, 0);
-                            acc[g][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[g][i], b1, acc[g][1], 0, 0, 0);
-                        }
-                    }
-                }
-            }
+            for (int j = 0; j < taps; ++j)
+                slab_mfma_step<kWgStride, GATES>(slab + hk * kWgStride + tc + (seg0 ? p.coff0 + j * p.cstep : 0), wp + (step0 + j) * GATES * 128 + lane, acc);
         }
     }
     if (!active) return;
-    // lane holds column lane & 31 and rows (e&3) + 8*(e>>2) + 4*hk of each 32x32 tile
-#pragma unroll
-    for (int n = 0; n < 2; ++n) {
-        const long q = t0 + wt * 64 + n * 32 + (lane & 31);
-        if (q >= p.Nq) continue;
-#pragma unroll
-        for (int e = 0; e < 16; ++e) {
-            const int r = mt * 32 + (e & 3) + 8 * (e >> 2) + 4 * hk;
-            if (r >= p.rows) continue;
-            if constexpr (MODE == kWgGated) {
-                const float ua = (acc[0][n][e] + p.bias0[r]) + p.bias1[r];
-                const float ub = (acc[1][n][e] + p.bias0[r + p.rows]) + p.bias1[r + p.rows];
-                if (p.raw) {
-                    p.y0[((size_t)b * 2 * p.rows + r) * p.N + q] = ua;
-                    p.y0[((size_t)b * 2 * p.rows + p.rows + r) * p.N + q] = ub;
-                } else {
-                    const float tv = tanhf(ua), gv = 1.f / (1.f + expf(-ub));
-                    const size_t o = ((size_t)b * p.rows + r) * p.N + q;
-                    if (p.s0) { p.s0[o] = tv; p.s1[o] = gv; }
-                    p.y0[o] = tv * gv;
-                }
-            } else if constexpr (MODE == kWgResSkip) {
-                const float v = acc[0][n][e] + p.bias0[r];
-                const int nc = p.C0;
-                if (!p.last && r < nc) {
-                    const size_t o = ((size_t)b * nc + r) * p.N + q;
-                    p.y0[o] = p.res[o] + v;
-                } else {
-                    const size_t o = ((size_t)b * nc + (p.last ? r : r - nc)) * p.N + q;
-                    p.y1[o] = p.first ? v : p.y1[o] + v;
-                }
-            } else if constexpr (MODE == kWgGateBwd) {
-                // d_acts = acc; du = [d_acts * g * (1 - t^2); d_acts * t * g * (1 - g)] [B, 2*rows, L], acts = t * g recomputed
-                const size_t o = ((size_t)b * p.rows + r) * p.N + q, o2 = ((size_t)b * 2 * p.rows + r) * p.N + q;
-                const float tv = p.s0[o], gv = p.s1[o], da = acc[0][n][e];
-                p.y0[o2] = da * gv * (1.f - tv * tv);
-                p.y0[o2 + (size_t)p.rows * p.N] = da * tv * gv * (1.f - gv);
-                p.y1[o] = tv * gv;
-            } else if constexpr (MODE == kWgAccum) {
-                const size_t o = ((size_t)b * p.rows + r) * p.N + q;
-                p.y0[o] = p.first ? acc[0][n][e] : p.y0[o] + acc[0][n][e];
+    slab_walk<WM, GATES>(acc, mt, p.rows, p.Nq, [=](int r, long q, const float (&a)[GATES]) {
+        if constexpr (MODE == kWgGated) {
+            const float ua = (a[0] + p.bias0[r]) + p.bias1[r];
+            const float ub = (a[1] + p.bias0[r + p.rows]) + p.bias1[r + p.rows];
+            if (p.raw) {
+                p.y0[((size_t)b * 2 * p.rows + r) * p.N + q] = ua;
+                p.y0[((size_t)b * 2 * p.rows + p.rows + r) * p.N + q] = ub;
             } else {
-                const int ch = r / kWgUpStride;
-                const long t = q * kWgUpStride + (r % kWgUpStride), l = t / p.G;
-                if (l < p.Lg) p.y0[(((size_t)b * p.C0 + ch) * p.G + (int)(t % p.G)) * p.Lg + l] = acc[0][n][e] + p.bias0[ch];
+                const float tv = tanhf(ua), gv = 1.f / (1.f + expf(-ub));
+                const size_t o = ((size_t)b * p.rows + r) * p.N + q;
+                if (p.s0) { p.s0[o] = tv; p.s1[o] = gv; }
+                p.y0[o] = tv * gv;
             }
-        }
-    }
-}
-
-// packed[mtile][step][gate][pg][lane][i] = W[row = 32*mtile + (lane & 31) (+ gate * rows)][k = 16*chunk + 2*(4*pg + i) + (lane >> 5)]
-// (zero outside the matrix); step = chunk * taps + tap over segment 0, then the chunks of segment 1.
-struct WgPack { const float* w0; const float* w1; float* out; int mode, rows, K0, K1, taps, nch0, nch1; size_t total; };
-__global__ void __launch_bounds__(256) wg_pack_kernel(WgPack p) {
-    const size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (idx >= p.total) return;
-    const int gates = p.mode == kWgGated ? 2 : 1, nsteps = p.nch0 * p.taps + p.nch1;
-    const int i = idx & 3, lane = (idx >> 2) & 63, pg = (idx >> 8) & 1;
-    size_t rest = idx >> 9;
-    const int gate = rest % gates; rest /= gates;
-    const int step = rest % nsteps;
-    const int mt = (int)(rest / nsteps);
-    const int r = mt * 32 + (lane & 31), kloc = 2 * (4 * pg + i) + (lane >> 5);
-    float v = 0.f;
-    if (r < p.rows) {
-        if (step < p.nch0 * p.taps) {
-            const int kk = (step / p.taps) * kWgCK + kloc, j = step % p.taps;
-            if (kk < p.K0) {
-                if (p.mode == kWgGated) v = p.w0[((size_t)(gate * p.rows + r) * p.K0 + kk) * 3 + j];          // Conv1d [2nc][nc][3]
-                else if (p.mode == kWgResSkip) v = p.w0[(size_t)r * p.K0 + kk];                                // Conv1d [rows][nc][1]
-                else v = p.w0[((size_t)kk * p.K0 + r / kWgUpStride) * kWgUpK + r % kWgUpStride + kWgUpStride * j];   // ConvTranspose1d [Cin][Cout][1024]
+        } else if constexpr (MODE == kWgResSkip) {
+            const float v = a[0] + p.bias0[r];
+            const int nc = p.C0;
+            if (!p.last && r < nc) {
+                const size_t o = ((size_t)b * nc + r) * p.N + q;
+                p.y0[o] = p.res[o] + v;
+            } else {
+                const size_t o = ((size_t)b * nc + (p.last ? r : r - nc)) * p.N + q;
+                p.y1[o] = p.first ? v : p.y1[o] + v;
             }
+        } else if constexpr (MODE == kWgGateBwd) {
+            // d_acts = a[0]; du = [d_acts * g * (1 - t^2); d_acts * t * g * (1 - g)] [B, 2*rows, L], acts = t * g recomputed
+            const size_t o = ((size_t)b * p.rows + r) * p.N + q, o2 = ((size_t)b * 2 * p.rows + r) * p.N + q;
+            const float tv = p.s0[o], gv = p.s1[o], da = a[0];
+            p.y0[o2] = da * gv * (1.f - tv * tv);
+            p.y0[o2 + (size_t)p.rows * p.N] = da * tv * gv * (1.f - gv);
+            p.y1[o] = tv * gv;
+        } else if constexpr (MODE == kWgAccum) {
+            const size_t o = ((size_t)b * p.rows + r) * p.N + q;
+            p.y0[o] = p.first ? a[0] : p.y0[o] + a[0];
         } else {
-            const int kk = (step - p.nch0 * p.taps) * kWgCK + kloc;
-            if (kk < p.K1) v = p.w1[(size_t)(gate * p.rows + r) * p.K1 + kk];
+            const int ch = r / kWgUpStride;
+            const long t = q * kWgUpStride + (r % kWgUpStride), l = t / p.G;
+            if (l < p.Lg) p.y0[(((size_t)b * p.C0 + ch) * p.G + (int)(t % p.G)) * p.Lg + l] = a[0] + p.bias0[ch];
         }
-    }
-    p.out[idx] = v;
+    });
 }
 
 // x[b, c, t] = bias[c] + sum_h w[c][h] * (scale * audio[b, h, t]), h ascending; 32 channels per workgroup row
@@ -202,45 +134,72 @@ __global__ void __launch_bounds__(256) wg_start_kernel(const float* __restrict__
     }
 }
 
+// ---- what the coupling and the tail backward open with (the forward tail measured 1 % slower on them and keeps its own text; the
+// `end` reduction stays a loop in each kernel, a shared one cost 3 %): w_end [C][nc], b_end [C], a mix [Cm][Cm] to LDS (256 threads)
+__device__ __forceinline__ void wg_load_end(float* we, float* be, float* wi, const float* w_end, const float* b_end, const float* mix, int C, int nc,
+                                            int Cm) {
+    for (int i = threadIdx.x; i < C * nc; i += 256) we[i] = w_end[i];
+    if (threadIdx.x < C) be[threadIdx.x] = b_end[threadIdx.x];
+    if (threadIdx.x < Cm * Cm) wi[threadIdx.x] = mix[threadIdx.x];
+    __syncthreads();
+}
+// a[h] and a[nh + h] without a dynamic register index: read, read with be[.] added (be: 8 floats), write
+__device__ __forceinline__ void wg_get_pair(const float (&a)[8], int h, int nh, float& lo, float& hi) {
+#pragma unroll
+    for (int r = 0; r < 8; ++r) {
+        lo = r == h ? a[r] : lo;
+        hi = r == nh + h ? a[r] : hi;
+    }
+}
+__device__ __forceinline__ void wg_get_pair_plus(const float (&a)[8], const float* be, int h, int nh, float& lo, float& hi) {
+#pragma unroll
+    for (int r = 0; r < 8; ++r) {
+        const float t = a[r] + be[r];
+        lo = r == h ? t : lo;
+        hi = r == nh + h ? t : hi;
+    }
+}
+__device__ __forceinline__ void wg_put_pair(float (&a)[8], int h, int nh, float lo, float hi) {
+#pragma unroll
+    for (int r = 0; r < 8; ++r) a[r] = r == h ? lo : (r == nh + h ? hi : a[r]);
+}
+// sum over the 256 threads, thread j's term at red[j]: a tree in LDS, in every run the same order
+__device__ __forceinline__ double wg_tree_sum(double* red, double v) {
+    red[threadIdx.x] = v;
+    __syncthreads();
+    for (int w = 128; w >= 1; w >>= 1) {
+        if (threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
+        __syncthreads();
+    }
+    return red[0];
+}
+
 // one thread per (item, column): end as <= 8 fmaf chains over nc (ascending), the affine inverse, the c x c mix (ascending)
 __global__ void __launch_bounds__(256) wg_couple_kernel(WgCouple p) {
     __shared__ float we[8 * 512], be[8], wi[64];
     const int nh = p.n_half, C = 2 * nh;
-    for (int i = threadIdx.x; i < C * p.nc; i += 256) we[i] = p.w_end[i];
-    if (threadIdx.x < C) be[threadIdx.x] = p.b_end[threadIdx.x];
-    if (threadIdx.x < C * C) wi[threadIdx.x] = p.winv[threadIdx.x];
-    __syncthreads();
+    wg_load_end(we, be, wi, p.w_end, p.b_end, p.winv, C, p.nc, C);
     const long t = (long)blockIdx.x * 256 + threadIdx.x;
     if (t >= p.L) return;
     const int b = blockIdx.y;
-    float o[8];
+    float o[8], v[8];
 #pragma unroll
-    for (int r = 0; r < 8; ++r) o[r] = 0.f;
+    for (int r = 0; r < 8; ++r) { o[r] = 0.f; v[r] = 0.f; }
     const float* ob = p.out + (size_t)b * p.nc * p.L + t;
     for (int c = 0; c < p.nc; ++c) {
-        const float v = ob[(size_t)c * p.L];
+        const float x = ob[(size_t)c * p.L];
 #pragma unroll
         for (int r = 0; r < 8; ++r)
-            if (r < C) o[r] = fmaf(we[r * p.nc + c], v, o[r]);
+            if (r < C) o[r] = fmaf(we[r * p.nc + c], x, o[r]);
     }
-    float v[8];
     const float* ib = p.in + (size_t)b * C * p.L + t;
 #pragma unroll
     for (int h = 0; h < 4; ++h) {
         if (h < nh) {
             const float a0 = ib[(size_t)h * p.L] * p.in_scale, a1 = ib[(size_t)(nh + h) * p.L] * p.in_scale;
             float bb = 0.f, s = 0.f;
-#pragma unroll
-            for (int r = 0; r < 8; ++r) {           // o[h] and o[nh + h] without a dynamic register index
-                if (r == h) bb = o[r] + be[r];
-                if (r == nh + h) s = o[r] + be[r];
-            }
-            const float y1 = (a1 - bb) / expf(s);
-#pragma unroll
-            for (int r = 0; r < 8; ++r) {
-                if (r == h) v[r] = a0;
-                if (r == nh + h) v[r] = y1;
-            }
+            wg_get_pair_plus(o, be, h, nh, bb, s);
+            wg_put_pair(v, h, nh, a0, (a1 - bb) / expf(s));
         }
     }
     const int Cn = C + p.n_early;
@@ -407,13 +366,8 @@ __global__ void __launch_bounds__(256) wg_nll_loss_kernel(const double* __restri
     if (!loss) return;                             // uniform
     double acc = 0.0;
     for (int b = threadIdx.x; b < B; b += 256) acc += item[b];
-    red[threadIdx.x] = acc;
-    __syncthreads();
-    for (int w = 128; w >= 1; w >>= 1) {
-        if (threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) loss[0] = (float)(red[0] / (double)B);
+    const double sum = wg_tree_sum(red, acc);
+    if (threadIdx.x == 0) loss[0] = (float)(sum / (double)B);
 }
 
 // out[m] = log |det w[m]| of n matrices [c][c], c <= 8: LU with partial pivoting in fp64, sum of log |u_ii| rounded to fp32; NaN
@@ -447,27 +401,28 @@ __global__ void __launch_bounds__(64) wg_logdet_kernel(const float* __restrict__
     out[blockIdx.x] = singular ? (float)-inf : (negative ? __builtin_nanf("") : (float)acc);
 }
 
+// the torch layouts of the forward's packs: gated Conv1d [2nc][nc][3] + the layer's rows of cond [2nc][n_cond], two gates rows
+// apart; res_skip Conv1d [rows][nc][1]; upsample ConvTranspose1d [Cin][Cout][1024], row = channel * 256 + phase, tap j at phase + 256 j
 int wg_pack(int kind, const float* w0, const float* w1, float* out, int rows, int k0, int k1, hipStream_t s) {
     T2_REQUIRE(w0 && out && (kind != kWgGated || w1), "waveglow pack: null pointer");
-    WgPack p{w0, w1, out, kind, kind == kWgUpsample ? rows * kWgUpStride : rows, k0, kind == kWgGated ? k1 : 0,
-             kind == kWgGated ? 3 : (kind == kWgUpsample ? kWgUpTaps : 1), chunks(k0), kind == kWgGated ? chunks(k1) : 0,
-             wg_packed_floats(kind, rows, k0, k1)};
-    hipLaunchKernelGGL(wg_pack_kernel, dim3((unsigned)((p.total + 255) / 256)), dim3(256), 0, s, p);
-    T2_LAUNCH_CHECK();
-    return 0;
+    SlabPack p{};
+    p.out = out; p.gates = 1; p.rows = rows; p.split = 1; p.s0.w = w0; p.s0.K = k0; p.s0.taps = 1;
+    if (kind == kWgGated) {
+        p.gates = 2; p.s0.taps = 3; p.s0.gs = (long)rows * k0 * 3; p.s0.rhi = (long)k0 * 3; p.s0.ks = 3; p.s0.ts = 1;
+        p.s1.w = w1; p.s1.K = k1; p.s1.gs = (long)rows * k1; p.s1.rhi = k1; p.s1.ks = 1;
+    } else if (kind == kWgResSkip) {
+        p.s0.rhi = k0; p.s0.ks = 1;
+    } else {
+        p.rows = rows * kWgUpStride; p.split = kWgUpStride; p.s0.taps = kWgUpTaps;
+        p.s0.rhi = kWgUpK; p.s0.rlo = 1; p.s0.ks = (long)k0 * kWgUpK; p.s0.ts = kWgUpStride;
+    }
+    return slab_pack(p, s);
 }
 
 template <int MODE>
 static int wg_launch(const WgGemm& p, int B, hipStream_t s) {
-    const int wm = p.mtiles >= 4 ? 4 : (p.mtiles >= 2 ? 2 : 1);
-    dim3 grid((unsigned)((p.Nq + kVocTT - 1) / kVocTT), (unsigned)((p.mtiles + wm - 1) / wm), (unsigned)B);
-    if (wm == 4) hipLaunchKernelGGL((wg_gemm_kernel<4, MODE>), grid, dim3(512), 0, s, p);
-    else if (wm == 2) hipLaunchKernelGGL((wg_gemm_kernel<2, MODE>), grid, dim3(256), 0, s, p);
-    else hipLaunchKernelGGL((wg_gemm_kernel<1, MODE>), grid, dim3(128), 0, s, p);
-    T2_LAUNCH_CHECK();
-    return 0;
+    return slab_launch(wg_gemm_kernel<4, MODE>, wg_gemm_kernel<2, MODE>, wg_gemm_kernel<1, MODE>, p, p.mtiles, p.Nq, 1, B, s);
 }
-
 
 int wg_gated(int B, int nc, int n_cond, long L, int d, int raw, const float* x, const float* spect, const float* packed, const float* b_in,
                     const float* b_cond, float* y, hipStream_t s, float* keep_t, float* keep_g) {
@@ -476,7 +431,7 @@ int wg_gated(int B, int nc, int n_cond, long L, int d, int raw, const float* x, 
     WgGemm p{};
     p.x0 = x; p.x1 = spect; p.wp = packed; p.bias0 = b_in; p.bias1 = b_cond; p.y0 = y;
     p.C0 = nc; p.C1 = n_cond; p.N = p.Nq = (int)L; p.taps = 3; p.coff0 = 0; p.cstep = d; p.halo = d;
-    p.rows = nc; p.mtiles = (nc + 31) / 32; p.nch0 = chunks(nc); p.nch1 = chunks(n_cond); p.raw = raw; p.s0 = keep_t; p.s1 = keep_g;
+    p.rows = nc; p.mtiles = (nc + 31) / 32; p.nch0 = slab_chunks(nc); p.nch1 = slab_chunks(n_cond); p.raw = raw; p.s0 = keep_t; p.s1 = keep_g;
     return wg_launch<kWgGated>(p, B, s);
 }
 
@@ -489,7 +444,7 @@ int wg_res_skip(int B, int nc, long L, int first, int last, const float* acts, c
     WgGemm p{};
     p.x0 = acts; p.wp = packed; p.bias0 = bias; p.y0 = x; p.y1 = out; p.res = x_from ? x_from : x;
     p.C0 = nc; p.N = p.Nq = (int)L; p.taps = 1;
-    p.rows = last ? nc : 2 * nc; p.mtiles = (p.rows + 31) / 32; p.nch0 = chunks(nc); p.first = first; p.last = last;
+    p.rows = last ? nc : 2 * nc; p.mtiles = (p.rows + 31) / 32; p.nch0 = slab_chunks(nc); p.first = first; p.last = last;
     return wg_launch<kWgResSkip>(p, B, s);
 }
 
@@ -499,7 +454,7 @@ int wg_upsample(int B, int n_mel, int T, int G, long n_samples, const float* mel
     const char* who = "waveglow upsample";
     T2_TRY_RC(wg_check_common(who, B, T));
     T2_REQUIRE(n_mel >= 1 && n_mel <= 512, "%s: n_mel_channels=%d outside 1..512", who, n_mel);
-    T2_REQUIRE(G >= 2 && G <= 8 && G % 2 == 0, "%s: n_group=%d is not even and from 2 to 8", who, G);
+    T2_TRY_RC(wg_check_group(who, G));
     T2_REQUIRE(n_samples / G >= 1, "%s: %ld samples give no whole group of %d", who, n_samples, G);
     T2_REQUIRE(n_samples <= (long)T * kWgUpStride + kWgUpK - kWgUpStride, "%s: %ld samples, %d frames give %ld", who, n_samples, T,
                (long)T * kWgUpStride + kWgUpK - kWgUpStride);
@@ -507,7 +462,7 @@ int wg_upsample(int B, int n_mel, int T, int G, long n_samples, const float* mel
     WgGemm p{};
     p.x0 = mel; p.wp = packed; p.bias0 = bias; p.y0 = spect;
     p.C0 = n_mel; p.N = T; p.taps = kWgUpTaps; p.coff0 = kWgUpTaps - 1; p.cstep = -1; p.halo = kWgUpTaps - 1;
-    p.rows = n_mel * kWgUpStride; p.mtiles = p.rows / 32; p.nch0 = chunks(n_mel); p.G = G; p.Lg = n_samples / G;
+    p.rows = n_mel * kWgUpStride; p.mtiles = p.rows / 32; p.nch0 = slab_chunks(n_mel); p.G = G; p.Lg = n_samples / G;
     p.Nq = (int)std::max((long)T, (p.Lg * G + kWgUpStride - 1) / kWgUpStride);
     return wg_launch<kWgUpsample>(p, B, s);
 }
@@ -523,7 +478,7 @@ int wg_couple(int B, const WgCouple& p, hipStream_t s) {
     const char* who = "waveglow coupling";
     T2_TRY_RC(wg_check_common(who, B, p.L));
     T2_TRY_RC(wg_check_nc(who, p.nc));
-    T2_REQUIRE(p.n_half >= 1 && p.n_half <= 4, "%s: n_half=%d outside 1..4", who, p.n_half);
+    T2_TRY_RC(wg_check_half(who, p.n_half));
     T2_REQUIRE(p.n_early >= 0 && p.n_early + 2 * p.n_half <= 8, "%s: %d early channels on top of %d exceed 8", who, p.n_early, 2 * p.n_half);
     T2_REQUIRE(p.out && p.w_end && p.b_end && p.in && p.winv && (p.dst || p.inter) && (p.n_early == 0 || (p.z && p.dst)), "%s: null pointer", who);
     hipLaunchKernelGGL(wg_couple_kernel, dim3((unsigned)((p.L + 255) / 256), (unsigned)B), dim3(256), 0, s, p);
@@ -533,7 +488,7 @@ int wg_couple(int B, const WgCouple& p, hipStream_t s) {
 
 int wg_head(int B, int G, long N, const float* audio, const float* w, float* dst, hipStream_t s) {
     const char* who = "waveglow head";
-    T2_REQUIRE(G >= 2 && G <= 8 && G % 2 == 0, "%s: n_group=%d is not even and from 2 to 8", who, G);
+    T2_TRY_RC(wg_check_group(who, G));
     T2_REQUIRE(N >= G, "%s: n_samples=%ld is shorter than one group of %d", who, N, G);
     T2_TRY_RC(wg_check_common(who, B, N / G));
     T2_REQUIRE(audio && w && dst, "%s: null pointer", who);
@@ -547,9 +502,8 @@ int wg_tail(int B, const WgTail& p, hipStream_t s) {
     const int C = 2 * p.n_half;
     T2_TRY_RC(wg_check_common(who, B, p.L));
     T2_TRY_RC(wg_check_nc(who, p.nc));
-    T2_REQUIRE(p.n_half >= 1 && p.n_half <= 4, "%s: n_half=%d outside 1..4", who, p.n_half);
-    T2_REQUIRE(p.n_peel >= 0 && p.n_peel <= C && p.n_peel != C - 1, "%s: %d of %d channels peeled leave no whole flow", who, p.n_peel, C);
-    T2_REQUIRE(p.zoff >= 0 && p.zoff + p.n_peel <= p.G && p.G <= 8, "%s: channels %d..%d of z lie outside its %d", who, p.zoff, p.zoff + p.n_peel, p.G);
+    T2_TRY_RC(wg_check_half(who, p.n_half));
+    T2_TRY_RC(wg_check_peel(who, p.n_peel, C, p.zoff, p.G));
     T2_REQUIRE(p.out && p.w_end && p.b_end && p.in && (p.n_peel == C || (p.wnext && p.dst)) && (p.n_peel == 0 || p.z || p.part_z) &&
                !p.part_s == !p.part_z, "%s: null pointer", who);
     hipLaunchKernelGGL(wg_tail_kernel, dim3((unsigned)((p.L + 255) / 256), (unsigned)B), dim3(256), 0, s, p);
@@ -705,10 +659,7 @@ __device__ __forceinline__ void wg_mix_grad(const float (&dn)[8], const float (&
 __global__ void __launch_bounds__(256) wg_tail_bwd_kernel(WgTailBwd p) {
     __shared__ float we[8 * 512], be[8], wi[64];
     const int nh = p.n_half, C = 2 * nh, Cn = C - p.n_peel;
-    for (int i = threadIdx.x; i < C * p.nc; i += 256) we[i] = p.w_end[i];
-    if (threadIdx.x < C) be[threadIdx.x] = p.b_end[threadIdx.x];
-    if (threadIdx.x < Cn * Cn) wi[threadIdx.x] = p.wnext[threadIdx.x];
-    __syncthreads();
+    wg_load_end(we, be, wi, p.w_end, p.b_end, p.wnext, C, p.nc, Cn);
     const long t = (long)blockIdx.x * 256 + threadIdx.x;
     const bool valid = t < p.L;
     const int b = blockIdx.y;
@@ -747,21 +698,15 @@ __global__ void __launch_bounds__(256) wg_tail_bwd_kernel(WgTailBwd p) {
             if (h < nh) {
                 const float a0 = ib[(size_t)h * p.L], a1 = ib[(size_t)(nh + h) * p.L];
                 float bb = 0.f, s = 0.f, db = 0.f, da0 = 0.f;
-#pragma unroll
-                for (int r = 0; r < 8; ++r) {       // o[h], dV[h] and o[nh + h], dV[nh + h] without a dynamic register index
-                    if (r == h) { bb = o[r] + be[r]; da0 = dV[r]; }
-                    if (r == nh + h) { s = o[r] + be[r]; db = dV[r]; }
-                }
+                wg_get_pair_plus(o, be, h, nh, bb, s);
+                wg_get_pair(dV, h, nh, da0, db);
                 const float es = expf(s), da1 = db * es;
                 const float ds = fmaf(da1, a1, p.dlog_s ? p.dlog_s[((size_t)b * nh + h) * p.L + t] : 0.f);
                 const float y1 = fmaf(es, a1, bb);
                 p.d_in[((size_t)b * C + h) * p.L + t] = da0;
                 p.d_in[((size_t)b * C + nh + h) * p.L + t] = da1;
-#pragma unroll
-                for (int r = 0; r < 8; ++r) {
-                    if (r == h) { v[r] = a0; e[r] = db; }
-                    if (r == nh + h) { v[r] = y1; e[r] = ds; }
-                }
+                wg_put_pair(v, h, nh, a0, y1);
+                wg_put_pair(e, h, nh, db, ds);
             }
         }
     }
@@ -875,60 +820,27 @@ __global__ void __launch_bounds__(256) wg_up_bias_bwd_kernel(const float* __rest
         const float* p = d_spect + ((size_t)b * n_mel + co) * row;
         for (size_t i = threadIdx.x; i < row; i += 256) acc += (double)p[i];
     }
-    red[threadIdx.x] = acc;
-    __syncthreads();
-    for (int w = 128; w >= 1; w >>= 1) {
-        if (threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) db[co] = (float)red[0];
+    const double sum = wg_tree_sum(red, acc);
+    if (threadIdx.x == 0) db[co] = (float)sum;
 }
 
-// packed[mtile][step][pg][lane][i] as wg_pack_kernel lays it out, from strided reads: segment 0 element (row, k, tap) is
-// w0[base0 + row*r0 + k*k0 + tap*j0], segment 1 element (row, k) is w1[row*r1 + k*k1]: the transposed operands of the data gradients
-struct WgPackT { const float* w0; const float* w1; float* out; int rows, K0, K1, taps, nch0, nch1; long base0, r0, k0, j0, r1, k1; size_t total; };
-__global__ void __launch_bounds__(256) wg_pack_t_kernel(WgPackT p) {
-    const size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (idx >= p.total) return;
-    const int nsteps = p.nch0 * p.taps + p.nch1;
-    const int i = idx & 3, lane = (idx >> 2) & 63, pg = (idx >> 8) & 1;
-    const size_t rest = idx >> 9;
-    const int step = rest % nsteps, mt = (int)(rest / nsteps);
-    const int r = mt * 32 + (lane & 31), kloc = 2 * (4 * pg + i) + (lane >> 5);
-    float v = 0.f;
-    if (r < p.rows) {
-        if (step < p.nch0 * p.taps) {
-            const int kk = (step / p.taps) * kWgCK + kloc, j = step % p.taps;
-            if (kk < p.K0) v = p.w0[p.base0 + (long)r * p.r0 + (long)kk * p.k0 + (long)j * p.j0];
-        } else {
-            const int kk = (step - p.nch0 * p.taps) * kWgCK + kloc;
-            if (kk < p.K1) v = p.w1[(long)r * p.r1 + (long)kk * p.k1];
-        }
-    }
-    p.out[idx] = v;
-}
-static int wg_pack_t(WgPackT p, hipStream_t s) {
-    p.nch0 = chunks(p.K0); p.nch1 = p.K1 ? chunks(p.K1) : 0;
-    p.total = wg_packed_t_floats(p.rows, p.K0, p.taps, p.K1);
-    hipLaunchKernelGGL(wg_pack_t_kernel, dim3((unsigned)((p.total + 255) / 256)), dim3(256), 0, s, p);
-    T2_LAUNCH_CHECK();
-    return 0;
-}
-// conv^T: rows c < nc, k = r < 2nc, tap j' reads du at l + (j' - 1) d, which W_in[r][c][2 - j'] multiplies
+// the transposed operands of the data gradients.  conv^T: rows c < nc, k = r < 2nc, tap j' reads du at l + (j' - 1) d, which W_in[r][c][2 - j'] multiplies
 int wg_pack_conv_t(const float* w_in, float* out, int nc, hipStream_t s) {
-    WgPackT p{}; p.w0 = w_in; p.out = out; p.rows = nc; p.K0 = 2 * nc; p.taps = 3; p.base0 = 2; p.r0 = 3; p.k0 = (long)nc * 3; p.j0 = -1;
-    return wg_pack_t(p, s);
+    SlabPack p{}; p.out = out; p.gates = 1; p.rows = nc; p.split = 1;
+    p.s0.w = w_in; p.s0.K = 2 * nc; p.s0.taps = 3; p.s0.base = 2; p.s0.rhi = 3; p.s0.ks = (long)nc * 3; p.s0.ts = -1;
+    return slab_pack(p, s);
 }
 int wg_pack_cond_t(const float* w_cond_i, float* out, int nc, int n_cond, hipStream_t s) {      // [2nc][n_cond] -> rows n_cond, K = 2nc
-    WgPackT p{}; p.w0 = w_cond_i; p.out = out; p.rows = n_cond; p.K0 = 2 * nc; p.taps = 1; p.r0 = 1; p.k0 = n_cond;
-    return wg_pack_t(p, s);
+    SlabPack p{}; p.out = out; p.gates = 1; p.rows = n_cond; p.split = 1;
+    p.s0.w = w_cond_i; p.s0.K = 2 * nc; p.s0.taps = 1; p.s0.rhi = 1; p.s0.ks = n_cond;
+    return slab_pack(p, s);
 }
 int wg_pack_rs_t(const float* w_rs, float* out, int nc, int last, hipStream_t s) {             // [2nc | nc][nc] -> rows nc, K = nc (x part) | nc (out part)
-    WgPackT p{}; p.w0 = w_rs; p.out = out; p.rows = nc; p.K0 = nc; p.taps = 1; p.r0 = 1; p.k0 = nc;
-    if (!last) { p.w1 = w_rs + (size_t)nc * nc; p.K1 = nc; p.r1 = 1; p.k1 = nc; }
-    return wg_pack_t(p, s);
+    SlabPack p{}; p.out = out; p.gates = 1; p.rows = nc; p.split = 1;
+    p.s0.w = w_rs; p.s0.K = nc; p.s0.taps = 1; p.s0.rhi = 1; p.s0.ks = nc;
+    if (!last) { p.s1.w = w_rs + (size_t)nc * nc; p.s1.K = nc; p.s1.rhi = 1; p.s1.ks = nc; }
+    return slab_pack(p, s);
 }
-
 
 int wg_wgrad(const WgGrad& p, hipStream_t s) {
     T2_REQUIRE(p.a && p.part && (long)p.B * p.nchunk <= INT32_MAX, "waveglow weight gradient: null pointer or too many chunks");
@@ -951,7 +863,7 @@ int wg_gate_bwd(int B, int nc, long L, int last, const float* dx, const float* d
     p.x0 = last ? d_out : dx; p.x1 = last ? nullptr : d_out; p.wp = packed_t; p.y0 = du; p.y1 = acts;
     p.s0 = const_cast<float*>(t); p.s1 = const_cast<float*>(g);
     p.C0 = nc; p.C1 = last ? 0 : nc; p.N = p.Nq = (int)L; p.taps = 1;
-    p.rows = nc; p.mtiles = (nc + 31) / 32; p.nch0 = chunks(nc); p.nch1 = last ? 0 : chunks(nc);
+    p.rows = nc; p.mtiles = (nc + 31) / 32; p.nch0 = slab_chunks(nc); p.nch1 = last ? 0 : slab_chunks(nc);
     return wg_launch<kWgGateBwd>(p, B, s);
 }
 // y [B, rows, L] (+)= W^T du: rows = nc with the flipped taps at distance d (dx), or rows = n_cond with one tap (d_spect)
@@ -964,7 +876,7 @@ int wg_data_bwd(int B, int rows, int nc, long L, int taps, int d, int first, con
     WgGemm p{};
     p.x0 = du; p.wp = packed_t; p.y0 = y; p.first = first;
     p.C0 = 2 * nc; p.N = p.Nq = (int)L; p.taps = taps; p.coff0 = 0; p.cstep = taps == 3 ? d : 0; p.halo = taps == 3 ? d : 0;
-    p.rows = rows; p.mtiles = (rows + 31) / 32; p.nch0 = chunks(2 * nc);
+    p.rows = rows; p.mtiles = (rows + 31) / 32; p.nch0 = slab_chunks(2 * nc);
     return wg_launch<kWgAccum>(p, B, s);
 }
 
@@ -973,9 +885,8 @@ int wg_tail_bwd(int B, const WgTailBwd& p, hipStream_t s) {
     const int C = 2 * p.n_half;
     T2_TRY_RC(wg_check_common(who, B, p.L));
     T2_TRY_RC(wg_check_nc(who, p.nc));
-    T2_REQUIRE(p.n_half >= 1 && p.n_half <= 4, "%s: n_half=%d outside 1..4", who, p.n_half);
-    T2_REQUIRE(p.n_peel >= 0 && p.n_peel <= C && p.n_peel != C - 1, "%s: %d of %d channels peeled leave no whole flow", who, p.n_peel, C);
-    T2_REQUIRE(p.zoff >= 0 && p.zoff + p.n_peel <= p.G && p.G <= 8, "%s: channels %d..%d of z lie outside its %d", who, p.zoff, p.zoff + p.n_peel, p.G);
+    T2_TRY_RC(wg_check_half(who, p.n_half));
+    T2_TRY_RC(wg_check_peel(who, p.n_peel, C, p.zoff, p.G));
     T2_REQUIRE(p.out && p.w_end && p.b_end && p.in && p.d_out && p.d_in && p.part && (p.n_peel == C || (p.wnext && p.dnext)), "%s: null pointer", who);
     hipLaunchKernelGGL(wg_tail_bwd_kernel, dim3((unsigned)((p.L + 255) / 256), (unsigned)B), dim3(256), 0, s, p);
     T2_LAUNCH_CHECK();
@@ -1004,7 +915,7 @@ int wg_up_bwd(int B, int n_mel, int T, int G, long n_samples, const float* mel, 
     const char* who = "waveglow upsample backward";
     T2_TRY_RC(wg_check_common(who, B, T));
     T2_REQUIRE(n_mel >= 1 && n_mel <= 512, "%s: n_mel_channels=%d outside 1..512", who, n_mel);
-    T2_REQUIRE(G >= 2 && G <= 8 && G % 2 == 0, "%s: n_group=%d is not even and from 2 to 8", who, G);
+    T2_TRY_RC(wg_check_group(who, G));
     T2_REQUIRE(n_samples / G >= 1 && n_samples <= (long)T * kWgUpStride + kWgUpK - kWgUpStride, "%s: %ld samples, %d frames", who, n_samples, T);
     T2_REQUIRE(mel && d_spect && dw && db, "%s: null pointer", who);
     const long Lg = n_samples / G;

@@ -22,6 +22,20 @@ int wg_check_nc(const char* who, int nc) {
     T2_REQUIRE(nc >= 8 && nc <= 512 && nc % 8 == 0, "%s: n_channels=%d, must be a multiple of 8 from 8 to 512", who, nc);
     return 0;
 }
+int wg_check_group(const char* who, int G) {
+    T2_REQUIRE(G >= 2 && G <= 8 && G % 2 == 0, "%s: n_group=%d is not even and from 2 to 8", who, G);
+    return 0;
+}
+int wg_check_half(const char* who, int n_half) {
+    T2_REQUIRE(n_half >= 1 && n_half <= 4, "%s: n_half=%d outside 1..4", who, n_half);
+    return 0;
+}
+// a tail peels n_peel of its C channels off to z[:, zoff:] (G channels)
+int wg_check_peel(const char* who, int n_peel, int C, int zoff, int G) {
+    T2_REQUIRE(n_peel >= 0 && n_peel <= C && n_peel != C - 1, "%s: %d of %d channels peeled leave no whole flow", who, n_peel, C);
+    T2_REQUIRE(zoff >= 0 && zoff + n_peel <= G && G <= 8, "%s: channels %d..%d of z lie outside its %d", who, zoff, zoff + n_peel, G);
+    return 0;
+}
 int wg_gated_check(int B, int nc, int n_cond, long L, int d) {
     const char* who = "waveglow gated conv";
     T2_TRY_RC(wg_check_common(who, B, L));
@@ -31,13 +45,13 @@ int wg_gated_check(int B, int nc, int n_cond, long L, int d) {
     return 0;
 }
 
-// ---- the packs: floats of one packed operand (wg_pack_kernel's and wg_pack_t_kernel's order)
+// ---- the packs: floats of one packed operand (slab_gemm.h's order)
 size_t wg_packed_floats(int kind, int rows, int k0, int k1) {
-    if (kind == kWgGated) return (size_t)((rows + 31) / 32) * (chunks(k0) * 3 + chunks(k1)) * 2 * 512;
-    if (kind == kWgResSkip) return (size_t)((rows + 31) / 32) * chunks(k0) * 512;
-    return (size_t)rows * kWgUpStride / 32 * chunks(k0) * kWgUpTaps * 512;
+    if (kind == kWgGated) return slab_packed_floats(2, rows, k0, 3, k1);
+    if (kind == kWgResSkip) return slab_packed_floats(1, rows, k0, 1, 0);
+    return slab_packed_floats(1, rows * kWgUpStride, k0, kWgUpTaps, 0);
 }
-size_t wg_packed_t_floats(int rows, int k0, int taps, int k1) { return (size_t)((rows + 31) / 32) * (chunks(k0) * taps + chunks(k1)) * 512; }
+size_t wg_packed_t_floats(int rows, int k0, int taps, int k1) { return slab_packed_floats(1, rows, k0, taps, k1); }
 
 static int rs_rows(const t2_waveglow_config& c, int i) { return i < c.n_layers - 1 ? 2 * c.n_channels : c.n_channels; }      // the last layer has no residual half
 
@@ -61,7 +75,7 @@ int wg_layout(const t2_waveglow_config& c, WgLayout* out) {
     T2_REQUIRE(c.kernel_size == 3, "waveglow: kernel_size=%d, only 3 is implemented", c.kernel_size);
     T2_REQUIRE(c.n_layers >= 1 && c.n_layers <= T2_WAVEGLOW_MAX_LAYERS, "waveglow: n_layers=%d outside 1..%d", c.n_layers, T2_WAVEGLOW_MAX_LAYERS);
     T2_TRY_RC(wg_check_nc("waveglow", c.n_channels));
-    T2_REQUIRE(c.n_group >= 2 && c.n_group <= 8 && c.n_group % 2 == 0, "waveglow: n_group=%d is not even and from 2 to 8", c.n_group);
+    T2_TRY_RC(wg_check_group("waveglow", c.n_group));
     T2_REQUIRE(c.n_early_size >= 0 && c.n_early_size % 2 == 0, "waveglow: n_early_size=%d is not even and non-negative", c.n_early_size);
     T2_REQUIRE(c.n_early_every >= 1, "waveglow: n_early_every=%d must be at least 1", c.n_early_every);
     T2_REQUIRE(c.n_flows >= 1 && c.n_flows <= 64, "waveglow: n_flows=%d outside 1..64", c.n_flows);
