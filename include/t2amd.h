@@ -784,6 +784,25 @@ typedef struct t2_hifigan_fwd_args {
     float* pre_tanh;         /* debug output, nullable: conv_post's output before the tanh, [B, 1, out_len] */
 } t2_hifigan_fwd_args;
 int t2_hifigan_forward(const t2_hifigan_config* cfg, const t2_hifigan_fwd_args* a, void* stream);
+/* A padded batch of mels of different lengths.  frames [B] (device, int32): item b's frame count.  It is read by the kernels
+ * only, never by the host, and clamped there to [0, T], so that no value of it moves a load or a store out of a row.  Item b
+ * is computed as if mel[b, :, :frames[b]] were run alone through t2_hifigan_forward: at every layer its row ends at
+ * frames[b] * (the rates so far), with the zeros of the "same" padding behind it, and the time tiles, the order of every
+ * sum and so the bits are those of that run.  What the mel holds at or behind frames[b] is never loaded (NaN and Inf
+ * included).  audio and pre_tanh are exact zeros from frames[b] * prod(rates) on; sample_lengths [B] (device, int32,
+ * nullable) receives that count.  frames[b] = 0 is legal: an all-zero row of length 0.  Workgroups whose tile lies behind
+ * their item's end return at once, so the cost follows sum(frames), not B * T. */
+typedef struct t2_hifigan_ragged_args {
+    int B, T, n_mel;
+    const float* packed;
+    const float* mel;            /* [B, n_mel, T] */
+    float* workspace;            /* workspace_bytes of t2_hifigan_plan(cfg, B, T) */
+    float* audio;                /* [B, 1, out_len] */
+    float* pre_tanh;             /* nullable, as in t2_hifigan_fwd_args */
+    const int32_t* frames;       /* [B] */
+    int32_t* sample_lengths;     /* [B], nullable */
+} t2_hifigan_ragged_args;
+int t2_hifigan_forward_ragged(const t2_hifigan_config* cfg, const t2_hifigan_ragged_args* a, void* stream);
 /* Single layers, for the tests only (the generator runs the same kernels).  w in torch layout; packed_ws receives the
  * packed weights first: t2_vocoder_packed_floats(Cin, Cout, k, u) floats, u = 0 for Conv1d.
  * conv1d (stride 1, padding (k*d - d)/2): y = ((accumulate ? y : 0) + conv(leaky_relu(x, slope)) + bias + residual) * scale,
@@ -798,6 +817,15 @@ typedef struct t2_vocoder_conv_args {
 size_t t2_vocoder_packed_floats(int Cin, int Cout, int k, int u);
 int t2_vocoder_conv1d(const t2_vocoder_conv_args* a, void* stream);              /* a->u must be 0 */
 int t2_vocoder_conv_transpose1d(const t2_vocoder_conv_args* a, void* stream);    /* a->d, residual, accumulate unused */
+/* Either layer (conv.u = 0: Conv1d, conv.u > 0: ConvTranspose1d) with per-item input lengths [B] (device, int32, clamped to
+ * [0, L] in the kernel), for the tests only.  Item b's rows are taken to end at lengths[b]: x, residual and (with accumulate)
+ * y are not read at or behind it, and y is LEFT UNTOUCHED from lengths[b] (Conv1d) or lengths[b] * u (ConvTranspose1d) on.
+ * Inside, the bits are those of the item alone at L = lengths[b]. */
+typedef struct t2_vocoder_conv_ragged_args {
+    t2_vocoder_conv_args conv;
+    const int32_t* lengths;
+} t2_vocoder_conv_ragged_args;
+int t2_vocoder_conv_ragged(const t2_vocoder_conv_ragged_args* a, void* stream);
 
 /* ---- STFT analysis / synthesis and vocoder bias removal ---------------------------------------------
  * Replaces the reference's stft.py: STFT.transform (:77-105), STFT.inverse (:107-136) and STFT.forward (:138-141), with
@@ -857,6 +885,34 @@ typedef struct t2_stft_synthesis_args {
     float* y;
 } t2_stft_synthesis_args;
 int t2_stft_synthesis(const t2_stft_synthesis_args* a, void* stream);
+/* The two calls for a padded batch of rows of different lengths.  The counts are int32 device arrays [B], read by the kernels
+ * only (nothing synchronises) and clamped there to the row, so that no value of them moves a load or a store out of bounds.
+ * Every item's bits are those of its run alone; what the inputs hold behind an item's count is never loaded (NaN and Inf
+ * included); workgroups whose tile lies behind their item's end only write zeros.
+ * analysis: lengths[b] samples of row b count.  The reflection is the item's own, it has nf_b = 1 + lengths[b] / hop frames,
+ *   the planes keep the layout [B, N/2+1, 1 + n/hop] with exact zeros at frames >= nf_b, and frame_lengths (nullable)
+ *   receives nf_b.  A row of lengths[b] <= N/2 samples, for which the reflect padding is undefined, has no frames: all zero,
+ *   count 0.
+ * synthesis: frame_lengths[b] frames of item b count (clamped to [0, nf]).  y keeps the layout [B, 1, hop*(nf-1)] with exact
+ *   zeros from out_len_b = hop * (frame_lengths[b] - 1) on; sample_lengths (nullable) receives out_len_b.  A count below 1
+ *   gives an all-zero row of length 0.  Both modes and windowed = 0 as in t2_stft_synthesis. */
+typedef struct t2_stft_analysis_ragged_args {
+    int B, N, hop; long n;
+    const float* x; const float* packed;
+    float* re; float* im; float* mag; float* phase;
+    const int32_t* lengths;      /* [B] */
+    int32_t* frame_lengths;      /* [B], nullable */
+} t2_stft_analysis_ragged_args;
+int t2_stft_analysis_ragged(const t2_stft_analysis_ragged_args* a, void* stream);
+typedef struct t2_stft_synthesis_ragged_args {
+    int B, N, hop, nf, mode, windowed;
+    const float* a; const float* b; const float* bias; float strength;
+    const float* packed;
+    float* y;
+    const int32_t* frame_lengths; /* [B] */
+    int32_t* sample_lengths;      /* [B], nullable */
+} t2_stft_synthesis_ragged_args;
+int t2_stft_synthesis_ragged(const t2_stft_synthesis_ragged_args* a, void* stream);
 
 /* ---- Log-mel front end (ragged waveforms -> log-mel spectrograms) -----------------------------------
  * Replaces the reference's layers.py: TacotronSTFT.mel_spectrogram (:60-80) with stft.py: STFT.transform (:77-105) and

@@ -314,6 +314,14 @@ class VocoderConvArgs(C.Structure):
                 ("slope", C.c_float), ("accumulate", C.c_int), ("scale", C.c_float)]
 
 
+class HifiganRaggedArgs(C.Structure):
+    _fields_ = HifiganFwdArgs._fields_ + [("frames", C.c_void_p), ("sample_lengths", C.c_void_p)]
+
+
+class VocoderConvRaggedArgs(C.Structure):
+    _fields_ = [("conv", VocoderConvArgs), ("lengths", C.c_void_p)]
+
+
 VOCODER_TIME_TILE = 128      # include/t2amd.h T2_VOCODER_TIME_TILE
 
 
@@ -331,6 +339,14 @@ class StftSynthesisArgs(C.Structure):
     _fields_ = [("B", C.c_int), ("N", C.c_int), ("hop", C.c_int), ("nf", C.c_int), ("mode", C.c_int), ("windowed", C.c_int),
                 ("a", C.c_void_p), ("b", C.c_void_p), ("bias", C.c_void_p), ("strength", C.c_float),
                 ("packed", C.c_void_p), ("y", C.c_void_p)]
+
+
+class StftAnalysisRaggedArgs(C.Structure):
+    _fields_ = StftAnalysisArgs._fields_ + [("lengths", C.c_void_p), ("frame_lengths", C.c_void_p)]
+
+
+class StftSynthesisRaggedArgs(C.Structure):
+    _fields_ = StftSynthesisArgs._fields_ + [("frame_lengths", C.c_void_p), ("sample_lengths", C.c_void_p)]
 
 
 STFT_FRAME_TILE = 32         # include/t2amd.h T2_STFT_FRAME_TILE
@@ -483,7 +499,8 @@ EXPORTS = ["t2_last_error", "t2_version", "t2_chain_status", "t2_chain_status_cl
            "t2_softdtw_plan", "t2_softdtw_dist", "t2_softdtw_forward", "t2_softdtw_backward", "t2_softdtw_dist_backward",
            "t2_ssim_plan", "t2_ssim_forward", "t2_ssim_backward",
            "t2_bert_plan", "t2_bert_pack", "t2_bert_forward", "t2_bert_embed_ln", "t2_bert_layernorm", "t2_bert_attention",
-           "t2_hifigan_plan", "t2_hifigan_pack", "t2_hifigan_forward", "t2_vocoder_packed_floats", "t2_vocoder_conv1d", "t2_vocoder_conv_transpose1d",
+           "t2_hifigan_plan", "t2_hifigan_pack", "t2_hifigan_forward", "t2_hifigan_forward_ragged", "t2_vocoder_packed_floats", "t2_vocoder_conv1d", "t2_vocoder_conv_transpose1d",
+           "t2_vocoder_conv_ragged", "t2_stft_analysis_ragged", "t2_stft_synthesis_ragged",
            "t2_stft_plan", "t2_stft_pack", "t2_stft_analysis", "t2_stft_synthesis", "t2_melspec_plan", "t2_melspec_pack", "t2_melspec",
            "t2_waveglow_plan", "t2_waveglow_pack", "t2_waveglow_infer", "t2_waveglow_packed_floats", "t2_waveglow_gated_conv", "t2_waveglow_res_skip",
            "t2_waveglow_upsample", "t2_waveglow_couple", "t2_waveglow_forward_plan", "t2_waveglow_forward", "t2_waveglow_logdet",
@@ -570,6 +587,10 @@ def lib() -> C.CDLL:
         L.t2_stft_pack.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.t2_stft_analysis.argtypes = [C.POINTER(StftAnalysisArgs), C.c_void_p]
         L.t2_stft_synthesis.argtypes = [C.POINTER(StftSynthesisArgs), C.c_void_p]
+        L.t2_hifigan_forward_ragged.argtypes = [C.POINTER(HifiganConfig), C.POINTER(HifiganRaggedArgs), C.c_void_p]
+        L.t2_vocoder_conv_ragged.argtypes = [C.POINTER(VocoderConvRaggedArgs), C.c_void_p]
+        L.t2_stft_analysis_ragged.argtypes = [C.POINTER(StftAnalysisRaggedArgs), C.c_void_p]
+        L.t2_stft_synthesis_ragged.argtypes = [C.POINTER(StftSynthesisRaggedArgs), C.c_void_p]
         L.t2_melspec_plan.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_long, C.c_int, C.POINTER(MelspecPlanInfo)]
         L.t2_melspec_pack.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.t2_melspec.argtypes = [C.POINTER(MelspecArgs), C.c_void_p]
@@ -623,6 +644,28 @@ def ptr(t: torch.Tensor | None) -> int | None:
 
 def stream() -> int:
     return torch.cuda.current_stream().cuda_stream
+
+
+def lengths_arg(who: str, lengths, B: int, hi: int, dev, lo: int = 0, too_short=None) -> torch.Tensor:
+    """Per-item lengths in the convention of stft.log_mel, as the int32 device tensor [B] the kernels take.  Python ints are
+    checked here against [lo, hi] and an offender raises with its index and value (below lo: `too_short(i, v)` where given);
+    a device tensor is not read back, so nothing synchronises: the kernels clamp it to the row."""
+    if isinstance(lengths, torch.Tensor):
+        if lengths.dtype != torch.int32 or tuple(lengths.shape) != (B,) or lengths.device != dev:
+            raise RuntimeError(f"{who}: lengths must be int32 [{B}] on {dev}, got {lengths.dtype} {tuple(lengths.shape)} on {lengths.device}")
+        return lengths.detach().contiguous()
+    try:
+        vals = [int(v) for v in lengths]
+    except TypeError:
+        raise RuntimeError(f"{who}: lengths must be None, a list of {B} ints or an int32 tensor [{B}] on {dev}, got {lengths!r}") from None
+    if len(vals) != B:
+        raise RuntimeError(f"{who}: {len(vals)} lengths for a batch of {B}")
+    for i, v in enumerate(vals):
+        if v > hi:
+            raise RuntimeError(f"{who}: lengths[{i}]={v} exceeds the {hi} a row holds")
+        if v < lo:
+            raise too_short(i, v) if too_short else RuntimeError(f"{who}: lengths[{i}]={v} is below {lo}")
+    return torch.tensor(vals, dtype=torch.int32).to(dev)
 
 
 def dims_from_hparams(hp, n_streams: int = 2) -> Dims:

@@ -28,16 +28,25 @@ class hifiganBiasRemover(torch.nn.Module):
             spec, _ = self.stft.transform(model(mel).float().squeeze(0))    # what the vocoder emits for that mel: [1, 1, T] -> [1, N/2+1, frames]
         self.register_buffer("bias_spec", spec[:, :, :1].clone())            # the first frame, [1, N/2+1, 1]
 
-    def forward(self, audio, strength=0.1):
-        """audio [B, T] -> [B, 1, hop * (T // hop)]."""
+    def forward(self, audio, strength=0.1, lengths=None):
+        """audio [B, T] -> [B, 1, hop * (T // hop)].  lengths (an addition): per-item sample counts of a padded batch, in the
+        convention of stft.log_mel (Python ints or an int32 device tensor, e.g. what Generator.forward(mel, lengths=...) returns).
+        Item b is then denoised as audio[b, :lengths[b]] alone would be, bit for bit, the result is zero behind its
+        hop * (lengths[b] // hop) samples, and (audio, lengths) is returned with those counts as an int32 device tensor."""
         audio = audio.to(self.bias_spec.device).float()
         if not audio.is_cuda:
+            if lengths is not None:
+                raise RuntimeError("hifiganBiasRemover: per-item lengths need the HIP kernels (CUDA tensors)")
             spec, angles = self.stft.transform(audio)
             return self.stft.inverse(torch.clamp(spec - self.bias_spec * strength, 0.0), angles)
         s = self.stft
-        re, im = _stft.analysis(audio, s.tables(), s.filter_length, s.hop_length, want=("re", "im"))
+        if lengths is None:
+            re, im = _stft.analysis(audio, s.tables(), s.filter_length, s.hop_length, want=("re", "im"))
+            return _stft.synthesis(re, im, s.tables(), s.filter_length, s.hop_length, mode=1, bias=self.bias_spec, strength=strength,
+                                   windowed=s.window is not None)
+        re, im, frames = _stft.analysis(audio, s.tables(), s.filter_length, s.hop_length, want=("re", "im"), lengths=lengths)
         return _stft.synthesis(re, im, s.tables(), s.filter_length, s.hop_length, mode=1, bias=self.bias_spec, strength=strength,
-                               windowed=s.window is not None)
+                               windowed=s.window is not None, lengths=frames)
 
 
 class waveglowBiasRemover(torch.nn.Module):

@@ -128,8 +128,15 @@ class _ConvStackFn(torch.autograd.Function):
         n = len(cfg["acts"])
         dev = x.device
         saved, cur, cur16 = [], x, None
-        handoff = CONV_HANDOFF and L.get_precision() == "bf16"
+        lengths = cfg.get("lengths")
+        # with lengths every layer reads its input zeroed behind each item's end: the fp32 tensor is masked in place, so the
+        # bf16 hand-off copy, which the mask does not reach, is left out
+        handoff = CONV_HANDOFF and L.get_precision() == "bf16" and lengths is None
+        if lengths is not None:
+            x = cur = x.clone()                                             # the caller's tensor stays as it is
         for i in range(n):
+            if lengths is not None:
+                L.check(L.lib().t2_mask_btc(L.ptr(cur), B, T, cur.shape[2], L.ptr(lengths), 0.0, L.stream()))
             w, bias, gamma, beta = params[4 * i:4 * i + 4]
             rm, rv = cfg["buffers"][i]
             Cout, Cin, K = w.shape
@@ -149,6 +156,8 @@ class _ConvStackFn(torch.autograd.Function):
             L.check(L.lib().t2_conv_bn_forward(C.byref(a), L.stream()))
             saved.append((cur, z, st, cur16))
             cur, cur16 = y, y16
+        if lengths is not None:
+            L.check(L.lib().t2_mask_btc(L.ptr(cur), B, T, cur.shape[2], L.ptr(lengths), 0.0, L.stream()))
         ctx.cfg, ctx.saved_acts, ctx.params, ctx.handoff = cfg, saved, [p.detach() for p in params], handoff
         return cur
 
@@ -185,8 +194,19 @@ class _ConvStackFn(torch.autograd.Function):
         return (dy, None) + tuple(grads)
 
 
-def conv_bn_stack(x, layers, acts, *, training, drop_p, seed, site0, residual=False):
-    """layers: list of (conv_module, bn_module) pairs (ConvNorm.conv, nn.BatchNorm1d)."""
+def conv_bn_stack(x, layers, acts, *, training, drop_p, seed, site0, residual=False, lengths=None):
+    """layers: list of (conv_module, bn_module) pairs (ConvNorm.conv, nn.BatchNorm1d).
+    lengths (int32 [B] on x's device, eval mode and inference only): item b counts lengths[b] frames.  Every layer's input is
+    zeroed at frames >= lengths[b] (t2_mask_btc) before the layer runs, and so is the result: inside its length an item sees
+    the zero padding it would see alone, whatever x holds behind it.  The call then runs under no_grad."""
+    if lengths is not None:
+        if training:
+            raise RuntimeError("conv_bn_stack: lengths are for eval mode only: in training mode the reference's BatchNorm statistics "
+                               "run over the padding too")
+        B = x.shape[0]
+        if not isinstance(lengths, torch.Tensor) or lengths.dtype != torch.int32 or tuple(lengths.shape) != (B,) or lengths.device != x.device:
+            got = f"{lengths.dtype} {tuple(lengths.shape)} on {lengths.device}" if isinstance(lengths, torch.Tensor) else repr(lengths)
+            raise RuntimeError(f"conv_bn_stack: lengths must be an int32 tensor [{B}] on {x.device}, got {got}")
     params, buffers = [], []
     for conv, bn in layers:
         params += [conv.weight, conv.bias, bn.weight, bn.bias]
@@ -195,6 +215,10 @@ def conv_bn_stack(x, layers, acts, *, training, drop_p, seed, site0, residual=Fa
             bn.num_batches_tracked += 1
     cfg = dict(acts=list(acts), buffers=buffers, training=bool(training), drop_p=float(drop_p), seed=int(seed), site0=int(site0),
                residual=bool(residual))
+    if lengths is not None:
+        cfg["lengths"] = lengths.contiguous()
+        with torch.no_grad():
+            return _ConvStackFn.apply(x, cfg, *params)
     return _ConvStackFn.apply(x, cfg, *params)
 
 

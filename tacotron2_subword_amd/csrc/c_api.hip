@@ -591,22 +591,35 @@ int t2_hifigan_forward(const t2_hifigan_config* cfg, const t2_hifigan_fwd_args* 
     return hifigan_forward(*reinterpret_cast<const HifiganConfig*>(cfg),
                            HifiganFwd{a->B, a->T, a->n_mel, a->packed, a->mel, a->workspace, a->audio, a->pre_tanh}, (hipStream_t)stream);
 }
+int t2_hifigan_forward_ragged(const t2_hifigan_config* cfg, const t2_hifigan_ragged_args* a, void* stream) {
+    T2_REQUIRE(cfg && a, "t2_hifigan_forward_ragged: null pointer");
+    T2_REQUIRE(a->frames, "t2_hifigan_forward_ragged: null frame counts (t2_hifigan_forward is the call without them)");
+    return hifigan_forward(*reinterpret_cast<const HifiganConfig*>(cfg),
+                           HifiganFwd{a->B, a->T, a->n_mel, a->packed, a->mel, a->workspace, a->audio, a->pre_tanh, a->frames, a->sample_lengths},
+                           (hipStream_t)stream);
+}
 size_t t2_vocoder_packed_floats(int Cin, int Cout, int k, int u) { return voc_packed_floats(Cin, Cout, k, u); }
-static int vocoder_layer(const t2_vocoder_conv_args* a, int u, void* stream) {
+static int vocoder_layer(const t2_vocoder_conv_args* a, int u, const int32_t* lengths, void* stream) {
     T2_REQUIRE(a->w && a->packed_ws, "t2_vocoder: null weights or packing scratch");
     T2_TRY(voc_pack(a->w, a->packed_ws, a->Cin, a->Cout, a->k, u, (hipStream_t)stream));
     return voc_conv(VocConv{a->B, a->Cin, a->Cout, (long)a->L, a->k, a->d, u, a->x, a->packed_ws, a->bias, u ? nullptr : a->residual, a->y,
-                            a->slope, u ? 0 : a->accumulate, u ? 1.f : a->scale}, (hipStream_t)stream);
+                            a->slope, u ? 0 : a->accumulate, u ? 1.f : a->scale, lengths, lengths ? a->L : 0, lengths ? 1 : 0}, (hipStream_t)stream);
+}
+int t2_vocoder_conv_ragged(const t2_vocoder_conv_ragged_args* a, void* stream) {
+    T2_REQUIRE(a, "t2_vocoder_conv_ragged: null arguments");
+    T2_REQUIRE(a->lengths, "t2_vocoder_conv_ragged: null lengths (t2_vocoder_conv1d / t2_vocoder_conv_transpose1d are the calls without them)");
+    T2_REQUIRE(a->conv.u >= 0, "t2_vocoder_conv_ragged: stride u=%d must not be negative", a->conv.u);
+    return vocoder_layer(&a->conv, a->conv.u, a->lengths, stream);
 }
 int t2_vocoder_conv1d(const t2_vocoder_conv_args* a, void* stream) {
     T2_REQUIRE(a, "t2_vocoder_conv1d: null arguments");
     T2_REQUIRE(a->u == 0, "t2_vocoder_conv1d: stride u=%d given, a Conv1d has none", a->u);
-    return vocoder_layer(a, 0, stream);
+    return vocoder_layer(a, 0, nullptr, stream);
 }
 int t2_vocoder_conv_transpose1d(const t2_vocoder_conv_args* a, void* stream) {
     T2_REQUIRE(a, "t2_vocoder_conv_transpose1d: null arguments");
     T2_REQUIRE(a->u >= 1, "t2_vocoder_conv_transpose1d: stride u=%d must be positive", a->u);
-    return vocoder_layer(a, a->u, stream);
+    return vocoder_layer(a, a->u, nullptr, stream);
 }
 
 static_assert(T2_STFT_FRAME_TILE == kStftTile, "t2amd.h mirrors the STFT frame tile");
@@ -625,6 +638,18 @@ int t2_stft_pack(int N, int hop, const float* forward_basis, const float* invers
 int t2_stft_analysis(const t2_stft_analysis_args* a, void* stream) {
     T2_REQUIRE(a, "t2_stft_analysis: null arguments");
     return stft_analysis(StftAnalysis{a->B, a->N, a->hop, a->n, a->x, a->packed, a->re, a->im, a->mag, a->phase}, (hipStream_t)stream);
+}
+int t2_stft_analysis_ragged(const t2_stft_analysis_ragged_args* a, void* stream) {
+    T2_REQUIRE(a, "t2_stft_analysis_ragged: null arguments");
+    T2_REQUIRE(a->lengths, "t2_stft_analysis_ragged: null lengths (t2_stft_analysis is the call without them)");
+    return stft_analysis(StftAnalysis{a->B, a->N, a->hop, a->n, a->x, a->packed, a->re, a->im, a->mag, a->phase, a->lengths, a->frame_lengths},
+                         (hipStream_t)stream);
+}
+int t2_stft_synthesis_ragged(const t2_stft_synthesis_ragged_args* a, void* stream) {
+    T2_REQUIRE(a, "t2_stft_synthesis_ragged: null arguments");
+    T2_REQUIRE(a->frame_lengths, "t2_stft_synthesis_ragged: null frame counts (t2_stft_synthesis is the call without them)");
+    return stft_synthesis(StftSynthesis{a->B, a->N, a->hop, a->nf, a->mode, a->windowed, a->a, a->b, a->bias, a->strength, a->packed, a->y,
+                                        a->frame_lengths, a->sample_lengths}, (hipStream_t)stream);
 }
 int t2_stft_synthesis(const t2_stft_synthesis_args* a, void* stream) {
     T2_REQUIRE(a, "t2_stft_synthesis: null arguments");

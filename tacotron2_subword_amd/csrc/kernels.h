@@ -514,6 +514,9 @@ struct VocConv {
     int B, Cin, Cout; long L; int k, d, u;
     const float* x; const float* packed; const float* bias; const float* res; float* y;
     float slope; int accumulate; float scale;
+    // nullable, device: item b's rows hold clamp(frames[b], 0, T) * factor inputs (L = T * factor).  What x, res and (accumulate) y
+    // hold behind that is never read; y behind it is left as it was
+    const int32_t* frames = nullptr; int T = 0, factor = 0;
 };
 size_t voc_packed_floats(int Cin, int Cout, int k, int u);
 int voc_pack(const float* w, float* packed, int Cin, int Cout, int k, int u, hipStream_t s);     // w in torch layout
@@ -531,7 +534,12 @@ struct HifiganPlan { long out_len; size_t buf_floats, workspace_bytes, packed_by
 int hifigan_layers(const HifiganConfig& c, std::vector<HifiganLayer>* out, size_t* packed_floats);   // validates; no device
 int hifigan_plan(const HifiganConfig& c, int B, int T, HifiganPlan* out);
 int hifigan_pack(const HifiganConfig& c, const float* const* weights, const float* const* biases, int n_layers, float* packed, hipStream_t s);
-struct HifiganFwd { int B, T, n_mel; const float* packed; const float* mel; float* workspace; float* audio; float* pre_tanh; };
+// frames (nullable, device [B]): per-item frame counts, clamped to [0, T] in the kernels; item b is then computed as if it were
+// mel[b, :, :frames[b]] alone, audio and pre_tanh are zero behind frames[b] * prod(rates), which sample_lengths (nullable) receives
+struct HifiganFwd {
+    int B, T, n_mel; const float* packed; const float* mel; float* workspace; float* audio; float* pre_tanh;
+    const int32_t* frames = nullptr; int32_t* sample_lengths = nullptr;
+};
 int hifigan_forward(const HifiganConfig& c, const HifiganFwd& a, hipStream_t s);
 
 // ------------------------------------------------------------------ STFT analysis / synthesis (stft.hip)
@@ -545,11 +553,23 @@ int stft_plan(int N, int hop, int nf, StftPlan* out);   // validates; no device
 // centre-padded window [N] in fp64, nullable (no window: synthesis must then run with windowed = 0)
 int stft_pack(int N, int hop, const float* fwd, const float* inv, const double* wsq, float* packed, hipStream_t s);
 // x [B, n] -> re, im, mag, phase [B, N/2+1, 1 + n/hop], each nullable
-struct StftAnalysis { int B, N, hop; long n; const float* x; const float* packed; float* re; float* im; float* mag; float* phase; };
+// lengths (nullable, device [B]): per-item sample counts, clamped to [0, n] in the kernel.  Item b is then x[b, :lengths[b]] alone:
+// its own reflection, 1 + lengths[b]/hop frames (none where lengths[b] <= N/2), zeros in the planes behind them; frame_lengths
+// (nullable) receives the counts
+struct StftAnalysis {
+    int B, N, hop; long n; const float* x; const float* packed; float* re; float* im; float* mag; float* phase;
+    const int32_t* lengths = nullptr; int32_t* frame_lengths = nullptr;
+};
 int stft_analysis(const StftAnalysis& a, hipStream_t s);
 // mode 0 (polar): a = magnitude, b = phase;  mode 1 (denoise): a = re, b = im, bias [N/2+1], strength.  a, b [B, N/2+1, nf] ->
 // y [B, 1, hop*(nf-1)].  windowed = 0 skips the envelope division and the N/hop scale (STFT(window=None), stft.py:117).
-struct StftSynthesis { int B, N, hop, nf, mode, windowed; const float* a; const float* b; const float* bias; float strength; const float* packed; float* y; };
+// frame_lengths (nullable, device [B]): per-item frame counts, clamped to [0, nf] in the kernel.  Item b is then its first
+// frame_lengths[b] frames alone; y is zero from hop*(frame_lengths[b]-1) on (from 0 for a count below 1), which sample_lengths
+// (nullable) receives
+struct StftSynthesis {
+    int B, N, hop, nf, mode, windowed; const float* a; const float* b; const float* bias; float strength; const float* packed; float* y;
+    const int32_t* frame_lengths = nullptr; int32_t* sample_lengths = nullptr;
+};
 int stft_synthesis(const StftSynthesis& a, hipStream_t s);
 // the forward part of stft_pack alone (any hop): fwd [2*(N/2+1)][N] -> packed, ((N/2+1 + 15)/16) * ((N + 31)/32) * 1024 floats
 int stft_pack_forward(int N, const float* fwd, float* packed, hipStream_t s);

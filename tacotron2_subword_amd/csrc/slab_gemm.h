@@ -31,6 +31,22 @@ __device__ __forceinline__ void slab_stage(float* slab, const float* xb, int C, 
     }
 }
 
+// the same for rows that lie `ld` apart and hold N <= ld valid columns (the vocoder's per-item lengths): what lies at or behind
+// N is never loaded and stages as zero, as for a row that ends there.  A function of its own, so that the one above and the
+// instances built on it stay as they are
+template <int STRIDE, int WAVES, class Act>
+__device__ __forceinline__ void slab_stage_ld(float* slab, const float* xb, int C, int ci0, int ld, int N, long t0, int halo, Act act) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, sw = kVocTT + 2 * halo;
+    for (int row = wave; row < kSlabCK; row += WAVES) {
+        const int ci = ci0 + row;
+        const float* xr = xb + (size_t)ci * ld;
+        for (int col = lane; col < sw; col += 64) {
+            const long t = t0 + col - halo;
+            slab[row * STRIDE + col] = (ci < C && t >= 0 && t < N) ? act(xr[t]) : 0.f;
+        }
+    }
+}
+
 // one (chunk, tap): 16 k-steps; sb = the lane's column in slab row hk, wj = the lane's fragment of the step's first gate
 template <int STRIDE, int GATES>
 __device__ __forceinline__ void slab_mfma_step(const float* sb, const f32x4* wj, f32x16 (&acc)[GATES][2]) {

@@ -19,6 +19,10 @@
 //   (re, im) with the bias remover's gain  g = max(|z| - strength*bias, 0) / |z|.  The epilogue divides by the window
 //   sum-square envelope where it exceeds FLT_MIN, scales by N/hop and writes only the samples the reference keeps.
 // The order of every sum is fixed: same bits from run to run and for an item alone or in a batch.  Offsets are 64-bit.
+// Per-item counts (padded batches): the analysis takes sample counts n_b (its own reflection, 1 + n_b/hop frames, none where
+// n_b <= N/2), the synthesis frame counts nf_b (loads, envelope and hop*(nf_b - 1) samples bounded by it).  Strides and tiles
+// stay those of the padded tensors, so an item has the bits of its run alone; behind an item's count the outputs are zeros,
+// and a tile wholly behind it runs no chunk.  The counts are read in the kernels only and clamped to the row.
 #include <cfloat>
 
 #include "kernels.h"
@@ -33,6 +37,7 @@ static_assert(kStftSynStride >= kStftTile + kStftMaxOverlap - 1, "the slab holds
 struct StftAna {
     const float* x; const float* pf; float* re; float* im; float* mag; float* phase;
     long n; int nf, N, hop, cutoff, bin_tiles, kchunks;
+    const int32_t* lens; int32_t* nf_out;                      // nullable: per-item sample counts (clamped to [0, n]) and the frame counts they give
 };
 
 __global__ void __launch_bounds__(256) stft_analysis_kernel(StftAna p) {
@@ -45,9 +50,20 @@ __global__ void __launch_bounds__(256) stft_analysis_kernel(StftAna p) {
     const float* xb = p.x + (size_t)b * p.n;
     const f32x4* pf = reinterpret_cast<const f32x4*>(p.pf) + (size_t)(active ? mt : 0) * p.kchunks * 256;
     const int half = p.N / 2;
+    // the item's own samples and frames: rows keep the stride n and the planes the stride nf, the reflection and the frame bound
+    // are the item's.  A row of <= N/2 samples, where the reflect pad is undefined, has no frames
+    long n = p.n;
+    int nf = p.nf;
+    if (p.lens) {
+        const int l = p.lens[b];
+        n = l < 0 ? 0 : (l > p.n ? p.n : (long)l);
+        nf = n > half ? 1 + (int)(n / p.hop) : 0;
+        if (p.nf_out && blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) p.nf_out[b] = nf;
+    }
     f32x16 acc = {0};
 
-    for (int c = 0; c < p.kchunks; ++c) {
+    // a tile wholly behind the item's frames stages nothing and writes zeros: uniform over the workgroup
+    for (int c = 0; c < (f0 < nf ? p.kchunks : 0); ++c) {
         if (c) __syncthreads();                                // every wave is done reading the previous slab
         const int kl = threadIdx.x & 31, k = c * kStftKC + kl;
 #pragma unroll
@@ -55,10 +71,10 @@ __global__ void __launch_bounds__(256) stft_analysis_kernel(StftAna p) {
             const int fl = (threadIdx.x >> 5) + 8 * i;
             const long f = f0 + fl;
             float v = 0.f;
-            if (f < p.nf && k < p.N) {
+            if (f < nf && k < p.N) {
                 long t = f * p.hop + k - half;                 // reflect padding: n > N/2 keeps both mirrors inside [0, n)
                 if (t < 0) t = -t;
-                else if (t >= p.n) t = 2 * (p.n - 1) - t;
+                else if (t >= n) t = 2 * (n - 1) - t;
                 v = xb[t];
             }
             slab[kl * kStftAnaStride + fl] = v;
@@ -79,6 +95,7 @@ __global__ void __launch_bounds__(256) stft_analysis_kernel(StftAna p) {
     // element e (bit 2 clear) is re, e + 4 is im of bin 8*(e>>3) + 4*hk + (e&3)
     const long f = f0 + (lane & 31);
     if (f >= p.nf) return;
+    const bool inside = f < nf;                                // frames at or past the item's count read as exact zeros
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
 #pragma unroll
@@ -86,11 +103,11 @@ __global__ void __launch_bounds__(256) stft_analysis_kernel(StftAna p) {
             const int bin = mt * 16 + 8 * h + 4 * hk + i;
             if (bin >= p.cutoff) continue;
             const size_t o = ((size_t)b * p.cutoff + bin) * p.nf + f;
-            const float re = acc[8 * h + i], im = acc[8 * h + i + 4];
+            const float re = inside ? acc[8 * h + i] : 0.f, im = inside ? acc[8 * h + i + 4] : 0.f;
             if (p.re) p.re[o] = re;
             if (p.im) p.im[o] = im;
-            if (p.mag) p.mag[o] = sqrtf(__fadd_rn(__fmul_rn(re, re), __fmul_rn(im, im)));   // torch.sqrt(re**2 + im**2), no contraction
-            if (p.phase) p.phase[o] = atan2f(im, re);
+            if (p.mag) p.mag[o] = inside ? sqrtf(__fadd_rn(__fmul_rn(re, re), __fmul_rn(im, im))) : 0.f;   // torch.sqrt(re**2 + im**2), no contraction
+            if (p.phase) p.phase[o] = inside ? atan2f(im, re) : 0.f;
         }
     }
 }
@@ -100,6 +117,7 @@ struct StftSyn {
     int nf, N, hop, R, cutoff, nchunks, col_tiles, mode, windowed;
     long qbase, out_len;
     float strength, scale;
+    const int32_t* nfs; int32_t* len_out;                      // nullable: per-item frame counts (clamped to [0, nf]) and the sample counts they give
 };
 
 template <int WN>
@@ -115,16 +133,27 @@ __global__ void __launch_bounds__(WN * 64) stft_synthesis_kernel(StftSyn p) {
     const float* pa = p.a + (size_t)bi * p.cutoff * p.nf;
     const float* pb = p.b + (size_t)bi * p.cutoff * p.nf;
     const f32x4* pi = reinterpret_cast<const f32x4*>(p.pi) + (size_t)(active ? ct : 0) * p.nchunks * p.R * 256;
+    // the item's own frames: the planes keep the stride nf and the output the stride out_len, the loads, the envelope and the
+    // samples written are bounded by the item's count
+    int nf = p.nf;
+    long out_len = p.out_len;
+    if (p.nfs) {
+        const int l = p.nfs[bi];
+        nf = l < 0 ? 0 : (l > p.nf ? p.nf : l);
+        out_len = nf >= 1 ? (long)p.hop * (nf - 1) : 0;
+        if (p.len_out && blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) p.len_out[bi] = (int32_t)out_len;
+    }
     f32x16 acc = {0};
 
-    for (int c = 0; c < p.nchunks; ++c) {
+    // a tile whose first sample lies behind the item's end stages nothing and writes zeros: uniform over the workgroup
+    for (int c = 0; c < (q0 * p.hop - p.N / 2 < out_len ? p.nchunks : 0); ++c) {
         if (c) __syncthreads();
         for (int item = threadIdx.x; item < 16 * W; item += WN * 64) {
             const int bl = item / W, col = item - bl * W;
             const int bin = c * 16 + bl;
             const long f = fbase + col;
             float xr = 0.f, xi = 0.f;
-            if (bin < p.cutoff && f >= 0 && f < p.nf) {
+            if (bin < p.cutoff && f >= 0 && f < nf) {
                 const size_t o = (size_t)bin * p.nf + f;
                 const float u = pa[o], v = pb[o];
                 if (p.mode == 0) {                             // polar: u = magnitude, v = phase
@@ -165,9 +194,10 @@ __global__ void __launch_bounds__(WN * 64) stft_synthesis_kernel(StftSyn p) {
         const long t = q * p.hop + r, o = t - p.N / 2;          // stft.py:133-134: N/2 samples dropped at each end
         if (o < 0 || o >= p.out_len) continue;
         float v = acc[e];
-        if (p.windowed) {
+        if (o >= out_len) v = 0.f;                             // behind the item's own end
+        else if (p.windowed) {
             // window_sumsquare: frames i*hop <= t < i*hop + N in ascending order, each "+=" a float64 add rounded to float32
-            const long lo = q - (p.R - 1) > 0 ? q - (p.R - 1) : 0, hi = q < p.nf - 1 ? q : p.nf - 1;
+            const long lo = q - (p.R - 1) > 0 ? q - (p.R - 1) : 0, hi = q < nf - 1 ? q : nf - 1;
             float env = 0.f;
             for (long i = lo; i <= hi; ++i) env = (float)((double)env + p.wsq[t - i * p.hop]);
             if (env > FLT_MIN) v = v / env;                    // tiny(window_sum), stft.py:123-128
@@ -255,6 +285,7 @@ int stft_pack(int N, int hop, const float* fwd, const float* inv, const double* 
 
 int stft_analysis(const StftAnalysis& a, hipStream_t s) {
     T2_REQUIRE(a.B >= 1 && a.B <= 65535, "stft analysis: B=%d outside 1..65535", a.B);
+    T2_REQUIRE(a.lengths || !a.frame_lengths, "stft analysis: frame counts asked for without sample counts");
     T2_REQUIRE(a.N >= 2 && a.N % 2 == 0, "stft analysis: filter_length=%d must be even", a.N);
     T2_REQUIRE(a.n > a.N / 2, "stft analysis: Padding size should be less than the corresponding input dimension, but got: padding (%d, %d) at dimension 1 "
                "of a signal of %ld samples", a.N / 2, a.N / 2, a.n);
@@ -267,6 +298,7 @@ int stft_analysis(const StftAnalysis& a, hipStream_t s) {
     StftAna p;
     p.x = a.x; p.pf = a.packed; p.re = a.re; p.im = a.im; p.mag = a.mag; p.phase = a.phase;
     p.n = a.n; p.nf = nf; p.N = a.N; p.hop = a.hop; p.cutoff = pl.cutoff; p.bin_tiles = pl.bin_tiles; p.kchunks = pl.kchunks;
+    p.lens = a.lengths; p.nf_out = a.frame_lengths;
     dim3 grid((unsigned)((nf + kStftTile - 1) / kStftTile), (unsigned)((pl.bin_tiles + 3) / 4), (unsigned)a.B);
     hipLaunchKernelGGL(stft_analysis_kernel, grid, dim3(256), 0, s, p);
     T2_LAUNCH_CHECK();
@@ -280,7 +312,11 @@ int stft_synthesis(const StftSynthesis& a, hipStream_t s) {
     T2_REQUIRE(a.mode == 0 || a.mode == 1, "stft synthesis: mode %d is neither polar (0) nor denoise (1)", a.mode);
     T2_REQUIRE(a.a && a.b && a.packed, "stft synthesis: null pointer");
     T2_REQUIRE(a.mode == 0 || a.bias, "stft synthesis: the denoise mode needs the bias spectrum");
-    if (pl.out_len == 0) return 0;                             // a single frame: everything falls into the trimmed margins
+    T2_REQUIRE(a.frame_lengths || !a.sample_lengths, "stft synthesis: sample counts asked for without frame counts");
+    if (pl.out_len == 0) {                                     // a single frame: everything falls into the trimmed margins
+        if (a.sample_lengths) T2_CHECK_HIP(hipMemsetAsync(a.sample_lengths, 0, (size_t)a.B * sizeof(int32_t), s));
+        return 0;
+    }
     T2_REQUIRE(a.y, "stft synthesis: null output");
     StftSyn p;
     p.a = a.a; p.b = a.b; p.bias = a.bias; p.pi = a.packed + pl.fwd_floats; p.y = a.y;
@@ -289,6 +325,7 @@ int stft_synthesis(const StftSynthesis& a, hipStream_t s) {
     p.mode = a.mode; p.windowed = a.windowed != 0;
     p.qbase = (a.N / 2) / a.hop; p.out_len = pl.out_len;
     p.strength = a.strength; p.scale = (float)a.N / (float)a.hop;
+    p.nfs = a.frame_lengths; p.len_out = a.sample_lengths;
     const long qlast = (a.N / 2 + pl.out_len - 1) / a.hop;
     const int wn = pl.col_tiles >= 8 ? 8 : (pl.col_tiles >= 4 ? 4 : (pl.col_tiles >= 2 ? 2 : 1));
     dim3 grid((unsigned)((qlast - p.qbase) / kStftTile + 1), (unsigned)((pl.col_tiles + wn - 1) / wn), (unsigned)a.B);

@@ -15,6 +15,13 @@
 // (phase + pad)/u + 1, cstep = -1, output offset q*ostride + phase) and the epilogue: bias, optional residual, optional
 // accumulate-into-destination, scale.  Cout = 8 wastes three quarters of its 32-channel tile: accepted.  The order of every sum
 // is fixed: same bits from run to run and for an item alone or in a batch.  Element offsets are 64-bit throughout.
+//
+// Per-item lengths (a padded batch of mels of different lengths): with a `frames` pointer item b's rows at a stage hold
+// clamp(frames[b], 0, T) * factor inputs, factor being the stage's cumulative upsampling.  That length bounds the slab staging
+// (zeros from it on, as for a row that ends there), the epilogue's walk (so the residual and accumulate reads and the stores)
+// and conv_post, which writes zeros behind it.  Grid, tiles and the order of every sum stay, so an item has the bits of its
+// run alone; a workgroup whose tile lies behind its item's end returns before its first barrier.  The count is only read
+// in the kernels, clamped: no value of it moves a load or a store out of a row.
 #include <algorithm>
 
 #include "slab_gemm.h"
@@ -31,7 +38,15 @@ struct VocGemm {
     int halo_lo;                                  // slab column c holds input t0 + c - halo_lo
     int mtiles, nchunks, ostride;
     float slope, scale; int accumulate;
+    const int32_t* frames; int T, factor;         // nullable: item b's rows hold clamp(frames[b], 0, T) * factor inputs, Lin = T * factor
 };
+
+// the inputs item b's rows hold; a count from the device is clamped, so that no value of it moves a load or a store out of the row
+__device__ __forceinline__ int voc_row_len(const int32_t* frames, int b, int T, int factor, int full) {
+    if (!frames) return full;
+    const int f = frames[b];
+    return (f < 0 ? 0 : (f > T ? T : f)) * factor;
+}
 
 template <int WM>
 __global__ void __launch_bounds__(WM * 128) voc_gemm_kernel(VocGemm p) {
@@ -47,11 +62,13 @@ __global__ void __launch_bounds__(WM * 128) voc_gemm_kernel(VocGemm p) {
     const float* xb = p.x + (size_t)b * p.Cin * p.Lin;
     const int lane = threadIdx.x & 63, wt = (threadIdx.x >> 6) / WM, tc = wt * 64 + (lane & 31), hk = lane >> 5;
     const long t0 = (long)blockIdx.x * kVocTT;
+    const int N = voc_row_len(p.frames, b, p.T, p.factor, p.Lin);
+    if (t0 >= N) return;                           // the tile lies behind the item's end: uniform over the workgroup, before any barrier
     const float slope = p.slope;
     f32x16 acc[1][2] = {{f32x16{0}, f32x16{0}}};
     for (int c = 0; c < p.nchunks; ++c) {
         if (c) __syncthreads();                    // every wave is done reading the previous slab
-        slab_stage<kVocStride, WM * 2>(slab, xb, p.Cin, c * kSlabCK, p.Lin, t0, p.halo_lo, [slope](float v) { return v > 0.f ? v : v * slope; });
+        slab_stage_ld<kVocStride, WM * 2>(slab, xb, p.Cin, c * kSlabCK, p.Lin, N, t0, p.halo_lo, [slope](float v) { return v > 0.f ? v : v * slope; });
         __syncthreads();
         if (active)
             for (int j = 0; j < p.taps; ++j)
@@ -59,7 +76,7 @@ __global__ void __launch_bounds__(WM * 128) voc_gemm_kernel(VocGemm p) {
     }
     if (!active) return;
     const size_t lout = (size_t)p.Lin * p.ostride;
-    slab_walk<WM, 1>(acc, mt, p.Cout, p.Lin, [=](int co, long q, const float (&a)[1]) {
+    slab_walk<WM, 1>(acc, mt, p.Cout, N, [=](int co, long q, const float (&a)[1]) {
         const size_t o = ((size_t)b * p.Cout + co) * lout + (size_t)q * p.ostride + phase;
         float v = a[0];
         if (p.bias) v += p.bias[co];
@@ -73,13 +90,25 @@ __global__ void __launch_bounds__(WM * 128) voc_gemm_kernel(VocGemm p) {
 // per term.  Cout = 1 makes it a reduction: one thread per output sample, the weights in LDS, loads coalesced along time.
 constexpr int kVocPostK = 7;
 __global__ void __launch_bounds__(256) voc_post_kernel(const float* __restrict__ x, const float* __restrict__ w, const float* __restrict__ bias,
-                                                      float* __restrict__ audio, float* __restrict__ pre, int C, long L, float slope) {
+                                                      float* __restrict__ audio, float* __restrict__ pre, int C, long L, float slope,
+                                                      const int32_t* __restrict__ frames, int T, int factor, int32_t* __restrict__ sample_lengths) {
     extern __shared__ float ws[];
-    for (int i = threadIdx.x; i < C * kVocPostK; i += 256) ws[i] = w[i];
-    __syncthreads();
-    const long t = (long)blockIdx.x * 256 + threadIdx.x;
-    if (t >= L) return;
     const int b = blockIdx.y;
+    const long t = (long)blockIdx.x * 256 + threadIdx.x;
+    // with per-item frame counts the row ends at N: tanh inside, exact zeros behind it, in audio and in pre alike
+    const long N = voc_row_len(frames, b, T, factor, (int)L);
+    if (sample_lengths && blockIdx.x == 0 && threadIdx.x == 0) sample_lengths[b] = (int32_t)N;
+    if ((long)blockIdx.x * 256 < N) {              // uniform over the workgroup: a block wholly behind the end only writes zeros
+        for (int i = threadIdx.x; i < C * kVocPostK; i += 256) ws[i] = w[i];
+        __syncthreads();
+    }
+    if (t >= L) return;
+    if (t >= N) {
+        const size_t o = (size_t)b * L + t;
+        if (pre) pre[o] = 0.f;
+        audio[o] = 0.f;
+        return;
+    }
     const float* xb = x + (size_t)b * C * L;
     float acc = 0.f;
     for (int ci = 0; ci < C; ++ci) {
@@ -87,7 +116,7 @@ __global__ void __launch_bounds__(256) voc_post_kernel(const float* __restrict__
 #pragma unroll
         for (int j = 0; j < kVocPostK; ++j) {
             const long tt = t + j - kVocPostK / 2;
-            float v = (tt >= 0 && tt < L) ? xr[tt] : 0.f;
+            float v = (tt >= 0 && tt < N) ? xr[tt] : 0.f;
             v = v > 0.f ? v : v * slope;
             acc = fmaf(ws[ci * kVocPostK + j], v, acc);
         }
@@ -145,6 +174,8 @@ int voc_conv(const VocConv& a, hipStream_t s) {
     T2_REQUIRE(a.L <= (long)INT32_MAX / 2, "%s: L=%ld exceeds the limit of %d samples per row", who, a.L, INT32_MAX / 2);
     T2_REQUIRE(a.x && a.packed && a.y, "%s: null pointer", who);
     T2_REQUIRE(!(a.u && (a.res || a.accumulate)), "%s: residual / accumulate are Conv1d fusions", who);
+    T2_REQUIRE(!a.frames || (a.factor >= 1 && a.T >= 1 && (long)a.T * a.factor == a.L), "%s: per-item counts of up to T=%d at factor %d do not span rows of L=%ld",
+               who, a.T, a.factor, a.L);
     VocGemm p;
     p.x = a.x; p.wp = a.packed; p.bias = a.bias; p.res = a.res; p.y = a.y;
     p.Cin = a.Cin; p.Cout = a.Cout; p.Lin = (int)a.L;
@@ -153,6 +184,7 @@ int voc_conv(const VocConv& a, hipStream_t s) {
     p.halo_lo = a.u ? 1 : p.pad;
     p.mtiles = (a.Cout + 31) / 32; p.nchunks = slab_chunks(a.Cin);
     p.slope = a.slope; p.scale = a.scale; p.accumulate = a.accumulate;
+    p.frames = a.frames; p.T = a.T; p.factor = a.factor;
     T2_REQUIRE(kVocTT + 2 * p.halo_lo <= kVocStride, "%s: halo %d does not fit the slab", who, p.halo_lo);
     return slab_launch(voc_gemm_kernel<4>, voc_gemm_kernel<2>, voc_gemm_kernel<1>, p, p.mtiles, a.L, p.u, a.B, s);
 }
@@ -240,10 +272,12 @@ int hifigan_forward(const HifiganConfig& c, const HifiganFwd& a, hipStream_t s) 
     T2_REQUIRE(a.n_mel == c.n_mel, "hifigan_forward: the mel has %d channels, the generator takes %d", a.n_mel, c.n_mel);
     T2_TRY_RC(hifigan_plan(c, a.B, a.T, &pl));
     T2_REQUIRE(a.packed && a.mel && a.workspace && a.audio, "hifigan_forward: null pointer");
+    T2_REQUIRE(a.frames || !a.sample_lengths, "hifigan_forward: sample lengths asked for without frame counts");
     float* XS = a.workspace; float* X = XS + pl.buf_floats; float* Tb = X + pl.buf_floats; float* P = Tb + pl.buf_floats; float* Q = P + pl.buf_floats;
     const float kSlope = 0.1f;                                       // LRELU_SLOPE, hifigan_model.py:8
     auto run = [&](const HifiganLayer& l, const float* x, float* y, long len, float slope, const float* res, int accumulate, float scale) {
-        return voc_conv(VocConv{a.B, l.cin, l.cout, len, l.k, l.d, l.u, x, a.packed + l.w_off, a.packed + l.b_off, res, y, slope, accumulate, scale}, s);
+        return voc_conv(VocConv{a.B, l.cin, l.cout, len, l.k, l.d, l.u, x, a.packed + l.w_off, a.packed + l.b_off, res, y, slope, accumulate, scale,
+                                a.frames, a.T, (int)(len / a.T)}, s);
     };
     size_t li = 0;
     long len = a.T;
@@ -277,7 +311,7 @@ int hifigan_forward(const HifiganConfig& c, const HifiganFwd& a, hipStream_t s) 
     // F.leaky_relu(x) in front of conv_post is torch's default slope 0.01, not LRELU_SLOPE (hifigan_model.py:112)
     dim3 grid((unsigned)((len + 255) / 256), (unsigned)a.B);
     hipLaunchKernelGGL(voc_post_kernel, grid, dim3(256), (size_t)post.cin * kVocPostK * sizeof(float), s, XS, a.packed + post.w_off,
-                       a.packed + post.b_off, a.audio, a.pre_tanh, post.cin, len, 0.01f);
+                       a.packed + post.b_off, a.audio, a.pre_tanh, post.cin, len, 0.01f, a.frames, a.T, (int)(len / a.T), a.sample_lengths);
     T2_LAUNCH_CHECK();
     return 0;
 }

@@ -177,9 +177,14 @@ class Generator(nn.Module):
         self._packed, self._packed_key = packed, self._key()
         return self
 
-    def forward(self, x, return_pre_tanh=False):
+    def forward(self, x, return_pre_tanh=False, lengths=None):
         """mel [B, 80, T], fp32, on the GPU -> audio [B, 1, T * prod(upsample_rates)].  return_pre_tanh=True (a debug output,
-        used by the tests) also returns conv_post's output before the tanh, same shape."""
+        used by the tests) also returns conv_post's output before the tanh, same shape.
+        lengths (an addition): per-item frame counts of a padded batch, in the convention of stft.log_mel: Python ints, checked
+        here against [0, T], or an int32 device tensor [B], which is not read back and is clamped to [0, T] by the kernels.
+        Item b is then computed as mel[b, :, :lengths[b]] alone would be, with the same bits; what the mel holds behind its
+        length is never read, audio (and pre) are zero behind lengths[b] * prod(upsample_rates), and the result is
+        (audio, sample_lengths) or (audio, pre, sample_lengths), sample_lengths an int32 device tensor [B]."""
         if not x.is_cuda:
             raise RuntimeError("hifigan Generator: the mel must live on the GPU (the product path has no CPU fallback)")
         if torch.is_grad_enabled() and x.requires_grad:
@@ -196,10 +201,18 @@ class Generator(nn.Module):
         B, n_mel, T = x.shape
         mel = x.detach().contiguous()
         plan = L.hifigan_plan(self._cfg, B, T)
+        if lengths is not None:
+            lengths = L.lengths_arg("hifigan Generator", lengths, B, T, x.device)
         with torch.cuda.device(x.device):
             ws = torch.empty(plan.workspace_bytes // 4, device=x.device, dtype=torch.float32)
             audio = torch.empty(B, 1, plan.out_len, device=x.device, dtype=torch.float32)
             pre = torch.empty_like(audio) if return_pre_tanh else None
-            a = L.HifiganFwdArgs(B, T, n_mel, L.ptr(self._packed), L.ptr(mel), L.ptr(ws), L.ptr(audio), L.ptr(pre))
-            L.check(L.lib().t2_hifigan_forward(C.byref(self._cfg), C.byref(a), L.stream()))
-        return (audio, pre) if return_pre_tanh else audio
+            if lengths is None:
+                a = L.HifiganFwdArgs(B, T, n_mel, L.ptr(self._packed), L.ptr(mel), L.ptr(ws), L.ptr(audio), L.ptr(pre))
+                L.check(L.lib().t2_hifigan_forward(C.byref(self._cfg), C.byref(a), L.stream()))
+                return (audio, pre) if return_pre_tanh else audio
+            sample_lengths = torch.empty(B, device=x.device, dtype=torch.int32)
+            a = L.HifiganRaggedArgs(B, T, n_mel, L.ptr(self._packed), L.ptr(mel), L.ptr(ws), L.ptr(audio), L.ptr(pre), L.ptr(lengths),
+                                    L.ptr(sample_lengths))
+            L.check(L.lib().t2_hifigan_forward_ragged(C.byref(self._cfg), C.byref(a), L.stream()))
+        return (audio, pre, sample_lengths) if return_pre_tanh else (audio, sample_lengths)

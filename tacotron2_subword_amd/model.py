@@ -50,12 +50,14 @@ class Postnet(nn.Module):
                          w_init_gain="tanh" if i < n - 1 else "linear"),
                 nn.BatchNorm1d(dims[i + 1])))
 
-    def forward_btc(self, x_btc, seed, residual=True):
-        """x [B,T,n_mel] channels-last -> x + postnet(x) (model.py:557-558) as one fused stack."""
+    def forward_btc(self, x_btc, seed, residual=True, lengths=None):
+        """x [B,T,n_mel] channels-last -> x + postnet(x) (model.py:557-558) as one fused stack.  lengths (int32 [B] on the
+        device, eval mode only): every item is computed as its first lengths[b] frames alone would be, zero behind them
+        (blocks.conv_bn_stack)."""
         n = len(self.convolutions)
         layers = [(blk[0].conv, blk[1]) for blk in self.convolutions]
         return blocks.conv_bn_stack(x_btc, layers, [blocks.ACT_TANH] * (n - 1) + [blocks.ACT_NONE], training=self.training,
-                                    drop_p=0.5, seed=seed, site0=L.SITE["POSTNET0"], residual=residual)
+                                    drop_p=0.5, seed=seed, site0=L.SITE["POSTNET0"], residual=residual, lengths=lengths)
 
     def forward(self, x):
         """Reference signature: [B,n_mel,T] -> [B,n_mel,T] (without the residual)."""
@@ -300,6 +302,9 @@ class Decoder(nn.Module):
         flag = bool((stop >= 0).all())
         n = int(stop.max()) + 1 if flag else steps
         self.last_stop_index = stop
+        # frames each item holds: up to and with its stop frame, or all that were decoded where it never stopped; on the device,
+        # int32: what Postnet.forward_btc and the vocoder take as lengths
+        self.last_mel_lengths = torch.where(stop >= 0, stop + 1, torch.full_like(stop, n)).to(dtype=torch.int32).to(memory.device)
         # decoder steps actually run / run past the last stop (the stop test is polled without draining the queue:
         # include/t2amd.h t2_decoder_infer); what a latency-sensitive caller pays beyond the frames it gets
         self.last_steps_run, self.last_overshoot = steps, steps - n
@@ -404,13 +409,21 @@ class BERT_Tacotron2(nn.Module):
             post = _FinalizeFn.apply(post_btc, None, 0.0)
         return [mel, post, gate, al, alb]
 
-    def inference(self, inputs, embeddings, phoneme_embeddings_cls, bert_embeddings_cls):
+    def inference(self, inputs, embeddings, phoneme_embeddings_cls, bert_embeddings_cls, per_item=False):
+        """per_item (an addition): at B > 1 an item that stops early is otherwise post-processed together with what the decoder
+        put out after its stop.  With per_item=True the postnet runs with decoder.last_mel_lengths, so that every item's
+        mel_postnet is what its B = 1 run gives, mel and mel_postnet are zero behind each item's length, and
+        self.last_mel_lengths (int32, on the device) is what the vocoder takes as lengths."""
         seed = _next_seed(self)
         memory, memory_sub = self._fronts(inputs, None, phoneme_embeddings_cls, embeddings, None, bert_embeddings_cls, seed)
         mel_btc, gate, al, alb, flag = self.decoder.inference(memory, memory_sub, channels_last=True)
         mel_btc = mel_btc.contiguous()
-        post_btc = self.postnet.forward_btc(mel_btc, seed)
-        return [ops.finalize_bct(mel_btc, None, 0.0), ops.finalize_bct(post_btc, None, 0.0), gate, al, alb, flag]
+        if not per_item:
+            post_btc = self.postnet.forward_btc(mel_btc, seed)
+            return [ops.finalize_bct(mel_btc, None, 0.0), ops.finalize_bct(post_btc, None, 0.0), gate, al, alb, flag]
+        self.last_mel_lengths = lengths = self.decoder.last_mel_lengths
+        post_btc = self.postnet.forward_btc(mel_btc, seed, lengths=lengths)
+        return [ops.finalize_bct(mel_btc, lengths, 0.0), ops.finalize_bct(post_btc, lengths, 0.0), gate, al, alb, flag]
 
 
 class Tacotron2(nn.Module):

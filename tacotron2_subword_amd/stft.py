@@ -95,9 +95,14 @@ def pack_tables(forward_basis, inverse_basis, window_sq, filter_length, hop_leng
     return packed
 
 
-def analysis(x, packed, filter_length, hop_length, want=("re", "im")):
+def analysis(x, packed, filter_length, hop_length, want=("re", "im"), lengths=None):
     """x [B, n] fp32 on the GPU -> the tensors named in `want` (of "re", "im", "mag", "phase"), [B, N/2+1, 1 + n//hop]
-    each, from one launch of the analysis kernel; the reflect padding is the kernel's index arithmetic."""
+    each, from one launch of the analysis kernel; the reflect padding is the kernel's index arithmetic.
+    lengths: per-item sample counts in the convention of `log_mel` (Python ints, checked here, or an int32 device tensor [B],
+    clamped to [0, n] by the kernel, no host sync).  Item b is then x[b, :lengths[b]] alone, bit for bit: its own reflection,
+    1 + lengths[b]//hop frames, zeros behind them; what the row holds behind its length is never read.  The int32 device
+    tensor of those frame counts is returned after the tensors of `want`.  An item of <= N/2 samples raises in torch's
+    reflect-pad words when given as a Python int; in a device tensor it has no frames: all zero, count 0."""
     from . import _lib as L
     if x.dim() != 2 or x.dtype != torch.float32:
         raise RuntimeError(f"stft analysis: expected a float32 signal [B, n], got {x.dtype} {tuple(x.shape)}")
@@ -110,18 +115,34 @@ def analysis(x, packed, filter_length, hop_length, want=("re", "im")):
                            f"at dimension 1 of input {list(x.shape)}")
     plan = L.stft_plan(filter_length, hop_length, 1 + n // hop_length)
     x = x.detach().contiguous()
+    if lengths is not None:
+        def too_short(i, v):
+            return RuntimeError(f"Padding size should be less than the corresponding input dimension, but got: padding ({half}, {half}) "
+                                f"at dimension 1 of item {i} of {v} samples")
+        lengths = L.lengths_arg("stft analysis", lengths, B, n, x.device, lo=half + 1, too_short=too_short)
     with torch.cuda.device(x.device):
         out = {k: torch.empty(B, plan.bins, 1 + n // hop_length, device=x.device, dtype=torch.float32) for k in want}
-        a = L.StftAnalysisArgs(B, filter_length, hop_length, n, L.ptr(x), L.ptr(packed), *[L.ptr(out.get(k)) for k in ("re", "im", "mag", "phase")])
-        L.check(L.lib().t2_stft_analysis(a, L.stream()))
-    return tuple(out[k] for k in want)
+        planes = [L.ptr(out.get(k)) for k in ("re", "im", "mag", "phase")]
+        if lengths is None:
+            a = L.StftAnalysisArgs(B, filter_length, hop_length, n, L.ptr(x), L.ptr(packed), *planes)
+            L.check(L.lib().t2_stft_analysis(a, L.stream()))
+            return tuple(out[k] for k in want)
+        frame_lengths = torch.empty(B, device=x.device, dtype=torch.int32)
+        a = L.StftAnalysisRaggedArgs(B, filter_length, hop_length, n, L.ptr(x), L.ptr(packed), *planes, L.ptr(lengths), L.ptr(frame_lengths))
+        L.check(L.lib().t2_stft_analysis_ragged(a, L.stream()))
+    return tuple(out[k] for k in want) + (frame_lengths,)
 
 
-def synthesis(a, b, packed, filter_length, hop_length, mode=0, bias=None, strength=0.0, windowed=True):
+def synthesis(a, b, packed, filter_length, hop_length, mode=0, bias=None, strength=0.0, windowed=True, lengths=None):
     """Two planes [B, N/2+1, nf] fp32 on the GPU -> audio [B, 1, hop*(nf-1)] from one launch of the synthesis kernel.
     mode 0 (polar): a = magnitude, b = phase.  mode 1 (denoise): a = re, b = im, bias [N/2+1] and strength: the bias
     remover's clamp(|z| - strength*bias, 0) applied as a gain.  windowed=False leaves out the envelope division and the
-    N/hop scale (STFT(window=None)): the output is then the trimmed overlap-add sum itself."""
+    N/hop scale (STFT(window=None)): the output is then the trimmed overlap-add sum itself.
+    lengths: per-item frame counts in the convention of `log_mel` (Python ints in [1, nf], checked here, or an int32 device
+    tensor [B], clamped to [0, nf] by the kernel, no host sync).  Item b is then its first lengths[b] frames alone, bit for
+    bit; the planes behind them are never read, the audio is zero from hop*(lengths[b]-1) on, and the result is
+    (audio, sample_lengths) with those counts as an int32 device tensor.  A count below 1 in a device tensor gives an
+    all-zero row of length 0."""
     from . import _lib as L
     plan = L.stft_plan(filter_length, hop_length, max(int(a.shape[-1]), 1) if a.dim() == 3 else 1)
     _check_planes("stft synthesis", a, b, plan.bins)
@@ -131,12 +152,20 @@ def synthesis(a, b, packed, filter_length, hop_length, mode=0, bias=None, streng
     if mode == L.STFT_DENOISE and (bias is None or bias.numel() != plan.bins or bias.dtype != torch.float32):
         raise RuntimeError(f"stft synthesis: the denoise mode needs a float32 bias spectrum of {plan.bins} bins")
     a, b = a.detach().contiguous(), b.detach().contiguous()
+    if lengths is not None:
+        def no_frames(i, v):
+            return RuntimeError(f"stft synthesis: no frames: lengths[{i}]={v}")
+        lengths = L.lengths_arg("stft synthesis", lengths, B, nf, a.device, lo=1, too_short=no_frames)
     with torch.cuda.device(a.device):
         y = torch.empty(B, 1, plan.out_len, device=a.device, dtype=torch.float32)
-        args = L.StftSynthesisArgs(B, filter_length, hop_length, nf, mode, int(bool(windowed)), L.ptr(a), L.ptr(b),
-                                   L.ptr(None if bias is None else bias.detach().reshape(-1).contiguous()), float(strength), L.ptr(packed), L.ptr(y))
-        L.check(L.lib().t2_stft_synthesis(args, L.stream()))
-    return y
+        common = (B, filter_length, hop_length, nf, mode, int(bool(windowed)), L.ptr(a), L.ptr(b),
+                  L.ptr(None if bias is None else bias.detach().reshape(-1).contiguous()), float(strength), L.ptr(packed), L.ptr(y))
+        if lengths is None:
+            L.check(L.lib().t2_stft_synthesis(L.StftSynthesisArgs(*common), L.stream()))
+            return y
+        sample_lengths = torch.empty(B, device=a.device, dtype=torch.int32)
+        L.check(L.lib().t2_stft_synthesis_ragged(L.StftSynthesisRaggedArgs(*common, L.ptr(lengths), L.ptr(sample_lengths)), L.stream()))
+    return y, sample_lengths
 
 
 def pack_mel_tables(forward_basis, mel_basis, filter_length):
