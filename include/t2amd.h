@@ -966,6 +966,58 @@ typedef struct t2_melspec_args {
 } t2_melspec_args;
 int t2_melspec(const t2_melspec_args* a, void* stream);
 
+/* ---- Silence trim (leading and trailing silence of ragged 16-bit audio) ------------------------------
+ * Replaces the reference's pydub trim: remove_silence.py:7-36 (detect_leading_silence and the loop around it) and
+ * best_checkpoint.py:319-333, 495-520 (the same function and loop, with the start_silence / limit_silence counters), for mono
+ * 16-bit audio that stays on the device.  What pydub's AudioSegment computes there, restated; N frames at `rate` Hz,
+ * r = rate / 1000.0 as a double:
+ *   len(sound)      len_ms = round(1000 * (double(N) / rate)), half to even;
+ *   sound[a:b]      (ms, both clamped to len_ms) = frames [int(a * r), int(b * r)), zero frames appended where the data ends
+ *                   before int(b * r) (at most int(0.5 * r) + 1 of them, when len_ms was rounded up); empty if b <= a;
+ *   .dBFS           of n frames: rms = (unsigned) sqrt(sum x^2 / n) (audioop.rms; 0 for n = 0); -inf when rms == 0, else
+ *                   20 * log10(rms / 32768);
+ *   detect_leading_silence(sound, thr, chunk): trim = 0; while sound[trim : trim + chunk].dBFS < thr: trim += chunk, and None
+ *                   as soon as trim > len_ms; the trailing silence is the same on the reversed frames;
+ *   the cut         sound[start : len_ms - end]: up to int(0.5 * r) + 1 frames longer than the input, those frames zero.
+ * The kernels decide in integers: R = the smallest rms in 1..32768 whose level is not below thr (host, the same log10), and a
+ * chunk is silent iff S < n * R^2 with S the exact 64-bit sum of squares.  start = chunk * (first loud k with
+ * chunk * k < len_ms).  Two kernels and a memset of the scratch on `stream`, no synchronisation, no float atomics (one integer
+ * atomicMin per scan workgroup): bit-identical from run to run and for an item alone or inside a batch.
+ * Stated differences: an item whose leading silence is found but whose trailing silence is None (possible because the
+ * forward and the reversed chunk grid differ; the reference's `duration - None` raises there and its `except` drops the file)
+ * gets length 0, its start_ms and end_ms = -1; fp32 input is clamped to [-32768, 32767] (NaN -> 0) before it is truncated
+ * toward zero, where numpy's out-of-range cast is undefined. */
+typedef struct t2_silence_plan_info {
+    int R;                        /* threshold as an rms: 0 = nothing is silent (thr = -inf), 32769 = everything is (thr > 0) */
+    int len_ms;                   /* len() of a full row of n frames */
+    int chunks;                   /* chunks of a full row: ceil(len_ms / chunk_ms) */
+    int chunks_per_group;         /* chunks one scan workgroup owns */
+    int scan_grid[3];             /* chunk groups, B, 2 directions; scan_grid[0] == 0: no scan launch */
+    int cut_grid[2];              /* column tiles of 1024 outputs, B */
+    int block;                    /* threads per workgroup of both kernels */
+    long out_width;               /* n + int(0.5 * r) + 1: samples per output row */
+    size_t scratch_bytes;         /* the first-loud-chunk words, a 128-byte line each: 2 * B * 128 */
+} t2_silence_plan_info;
+/* Pure host call (no device).  n: samples per row.  Refuses, naming the argument: sample_rate < 4000, chunk_ms < 1, a NaN
+ * threshold_db, n < 0, n > INT32_MAX / 2 (32-bit frame indices), B outside 1..65535. */
+int t2_silence_plan(int sample_rate, int chunk_ms, double threshold_db, long n, int B, t2_silence_plan_info* out);
+typedef struct t2_silence_args {
+    int B; long n;                /* rows, samples per row of x */
+    int sample_rate, chunk_ms;
+    double threshold_db;
+    const void* x;                /* [B, n] int16, or fp32 in int16 units with x_float (best_checkpoint.py:216-224 before astype) */
+    int x_float;
+    const int32_t* lengths;       /* [B] on the device, or NULL (every item has n frames); clamped to [0, n] */
+    void* out;                    /* [B, out_width] int16, or fp32 = int16 * scale with out_float; zero from new_lengths[b] on; not x */
+    int out_float; float scale;
+    int32_t* new_lengths;         /* [B]: frames kept, 0 for a dropped item */
+    int32_t* start_ms;            /* [B]: leading silence in ms, -1 for None */
+    int32_t* end_ms;              /* [B]: trailing silence in ms, -1 for None or a dropped item */
+    void* scratch; size_t scratch_bytes;
+    int leading_only;             /* detect_leading_silence alone: only start_ms is written; out, new_lengths, end_ms may be NULL */
+} t2_silence_args;
+int t2_silence_trim(const t2_silence_args* a, void* stream);
+
 /* ---- WaveGlow inference (mel spectrogram -> waveform) ------------------------------------------------
  * Replaces the reference's glow.py: WaveGlow.infer (:251-293), WN.forward (:153-175) and
  * Invertible1x1Conv.forward(reverse=True) (:88-97), as inference.py:160-170 and best_checkpoint.py:179-189 call them and as

@@ -367,6 +367,21 @@ class MelspecArgs(C.Structure):
                 ("time_major", C.c_int), ("return_power", C.c_int), ("force_splits", C.c_int)]
 
 
+class SilencePlanInfo(C.Structure):
+    _fields_ = [("R", C.c_int), ("len_ms", C.c_int), ("chunks", C.c_int), ("chunks_per_group", C.c_int), ("scan_grid", C.c_int * 3),
+                ("cut_grid", C.c_int * 2), ("block", C.c_int), ("out_width", C.c_long), ("scratch_bytes", C.c_size_t)]
+
+
+class SilenceArgs(C.Structure):
+    _fields_ = [("B", C.c_int), ("n", C.c_long), ("sample_rate", C.c_int), ("chunk_ms", C.c_int), ("threshold_db", C.c_double),
+                ("x", C.c_void_p), ("x_float", C.c_int), ("lengths", C.c_void_p), ("out", C.c_void_p), ("out_float", C.c_int), ("scale", C.c_float),
+                ("new_lengths", C.c_void_p), ("start_ms", C.c_void_p), ("end_ms", C.c_void_p), ("scratch", C.c_void_p), ("scratch_bytes", C.c_size_t),
+                ("leading_only", C.c_int)]
+
+
+SILENCE_NONE_SILENT, SILENCE_ALL_SILENT = 0, 32769      # t2_silence_plan_info.R for a threshold of -inf / above 0 dBFS
+
+
 class WaveglowConfig(C.Structure):
     _fields_ = [("n_mel_channels", C.c_int), ("n_flows", C.c_int), ("n_group", C.c_int), ("n_early_every", C.c_int), ("n_early_size", C.c_int),
                 ("n_layers", C.c_int), ("n_channels", C.c_int), ("kernel_size", C.c_int)]
@@ -502,6 +517,7 @@ EXPORTS = ["t2_last_error", "t2_version", "t2_chain_status", "t2_chain_status_cl
            "t2_hifigan_plan", "t2_hifigan_pack", "t2_hifigan_forward", "t2_hifigan_forward_ragged", "t2_vocoder_packed_floats", "t2_vocoder_conv1d", "t2_vocoder_conv_transpose1d",
            "t2_vocoder_conv_ragged", "t2_stft_analysis_ragged", "t2_stft_synthesis_ragged",
            "t2_stft_plan", "t2_stft_pack", "t2_stft_analysis", "t2_stft_synthesis", "t2_melspec_plan", "t2_melspec_pack", "t2_melspec",
+           "t2_silence_plan", "t2_silence_trim",
            "t2_waveglow_plan", "t2_waveglow_pack", "t2_waveglow_infer", "t2_waveglow_packed_floats", "t2_waveglow_gated_conv", "t2_waveglow_res_skip",
            "t2_waveglow_upsample", "t2_waveglow_couple", "t2_waveglow_forward_plan", "t2_waveglow_forward", "t2_waveglow_logdet",
            "t2_waveglow_logdet_matrices", "t2_waveglow_head", "t2_waveglow_tail",
@@ -594,6 +610,8 @@ def lib() -> C.CDLL:
         L.t2_melspec_plan.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_long, C.c_int, C.POINTER(MelspecPlanInfo)]
         L.t2_melspec_pack.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.t2_melspec.argtypes = [C.POINTER(MelspecArgs), C.c_void_p]
+        L.t2_silence_plan.argtypes = [C.c_int, C.c_int, C.c_double, C.c_long, C.c_int, C.POINTER(SilencePlanInfo)]
+        L.t2_silence_trim.argtypes = [C.POINTER(SilenceArgs), C.c_void_p]
         L.t2_waveglow_plan.argtypes = [C.POINTER(WaveglowConfig), C.c_int, C.c_int, C.POINTER(WaveglowPlanInfo)]
         L.t2_waveglow_pack.argtypes = [C.POINTER(WaveglowConfig), C.POINTER(C.c_void_p), C.c_int, C.c_void_p, C.c_void_p]
         L.t2_waveglow_infer.argtypes = [C.POINTER(WaveglowConfig), C.POINTER(WaveglowInferArgs), C.c_void_p]
@@ -1100,6 +1118,14 @@ def melspec_plan(N: int, hop: int, pad: int, n_mels: int, n: int, B: int = 1) ->
     host, no device needed); raises with the name and value of what the kernel does not take."""
     info = MelspecPlanInfo()
     check(lib().t2_melspec_plan(N, hop, pad, n_mels, n, B, C.byref(info)))
+    return info
+
+
+def silence_plan(sample_rate: int, chunk_ms: int, threshold_db: float, n: int, B: int = 1) -> SilencePlanInfo:
+    """The threshold as an integer rms, the chunk count and output width of a full row, the scratch size and the launch shapes
+    of a silence trim (t2_silence_plan: pure host arithmetic, no device needed)."""
+    info = SilencePlanInfo()
+    check(lib().t2_silence_plan(sample_rate, chunk_ms, threshold_db, n, B, C.byref(info)))
     return info
 
 

@@ -675,6 +675,22 @@ int t2_melspec(const t2_melspec_args* a, void* stream) {
                                a->mag_eps, a->clip_val, a->C, a->pad_value, a->time_major, a->return_power, a->force_splits}, (hipStream_t)stream);
 }
 
+int t2_silence_plan(int sample_rate, int chunk_ms, double threshold_db, long n, int B, t2_silence_plan_info* out) {
+    T2_REQUIRE(out, "t2_silence_plan: null pointer");
+    SilPlan p;
+    T2_TRY(silence_plan(sample_rate, chunk_ms, threshold_db, n, B, &p));
+    out->R = p.R; out->len_ms = p.len_ms; out->chunks = p.chunks; out->chunks_per_group = kSilChunksPerGroup;
+    out->scan_grid[0] = p.R == kSilNoneSilent ? 0 : p.groups; out->scan_grid[1] = B; out->scan_grid[2] = 2;
+    out->cut_grid[0] = (int)((p.out_width + 3 + kSilCutSpan - 1) / kSilCutSpan); out->cut_grid[1] = B;
+    out->block = 256; out->out_width = p.out_width; out->scratch_bytes = p.scratch_bytes;
+    return 0;
+}
+int t2_silence_trim(const t2_silence_args* a, void* stream) {
+    T2_REQUIRE(a, "t2_silence_trim: null arguments");
+    return silence_trim(SilenceArgs{a->B, a->n, a->sample_rate, a->chunk_ms, a->threshold_db, a->x, a->x_float, a->lengths, a->out, a->out_float, a->scale,
+                                    a->new_lengths, a->start_ms, a->end_ms, a->scratch, a->scratch_bytes, a->leading_only}, (hipStream_t)stream);
+}
+
 int t2_prof_enable(int max_launches) {
     if (max_launches <= 0) { g_prof.on = false; return 0; }
     const size_t need = (size_t)max_launches * 2;

@@ -600,6 +600,30 @@ struct MelSpecArgs {
 };
 int melspec(const MelSpecArgs& a, hipStream_t s);
 
+// ------------------------------------------------------------------ silence trim (silence.hip)
+constexpr int kSilChunksPerGroup = 8;            // chunks a scan workgroup owns: two per wave
+constexpr int kSilWordStride = 32;               // ints between two first-loud-chunk words: a 128-byte line each
+constexpr int kSilCutSpan = 1024;                // output samples a cut workgroup writes: four per thread
+constexpr int kSilNoneSilent = 0;                // R for a threshold of -inf: S < n * 0 never holds
+constexpr int kSilAllSilent = 32769;             // R for a threshold above 0 dBFS: S <= n * 2^30 < n * 32769^2 always holds
+// len(sound) of N frames: round(1000 * (float(N) / rate)), half to even on the double
+__host__ __device__ inline int sil_len_ms(int N, int rate) { return (int)rint(1000.0 * ((double)N / (double)rate)); }
+// the frame a millisecond maps to: int(ms * r), one double multiply, truncated
+__host__ __device__ inline int sil_frame(int ms, double r) { return (int)((double)ms * r); }
+struct SilPlan { int R, len_ms, chunks, groups; long out_width; size_t scratch_bytes; };
+int silence_plan(int rate, int chunk_ms, double thr, long n, int B, SilPlan* out);   // validates; no device
+// x [B, n] int16 or fp32 (x_float) -> out [B, out_width] int16 or fp32 (out_float: int16 * scale), zero from new_lengths[b] on.
+// lengths [B] int32 nullable.  start_ms / end_ms / new_lengths [B] int32.  leading_only: only start_ms is written (forward scan).
+struct SilenceArgs {
+    int B; long n; int rate, chunk_ms; double thr;
+    const void* x; int x_float; const int* lengths;
+    void* out; int out_float; float scale;
+    int* new_lengths; int* start_ms; int* end_ms;
+    void* scratch; size_t scratch_bytes;
+    int leading_only;
+};
+int silence_trim(const SilenceArgs& a, hipStream_t s);
+
 // ------------------------------------------------------------------ optimizer (optim.hip)
 struct AdamTensor { float* p; const float* g; float* m; float* v; long numel; int first_chunk; int pad_; };   // 48 bytes, mirrors t2_adam_tensor
 int adam_chunks(long numel);
