@@ -414,7 +414,8 @@ typedef struct t2_lstm_seq_bwd_args {
     int nstreams, B, T, H;
     const float* w_hh[4]; int reverse[4];
     const float* h[4]; long ldh; const float* c[4]; const float* gates[4];
-    const float* dh[4]; long lddh;   /* gradient on the outputs, [T,B,*] with row stride lddh */
+    const float* dh[4]; long lddh;   /* gradient on the outputs, [T,B,*] with row stride lddh; dh past an item's length must be
+                                        finite: it is multiplied by the zero saved gates, not masked */
     float* dpre[4];                  /* out: gradient wrt pre-activations [T,B,4H] */
     float* dw_hh[4];                 /* out: [4H,H] */
     float* ws; size_t ws_floats;     /* scratch >= nstreams*(B*H + 8*B*H) + split-K space; also the persistent chain's exchange
