@@ -964,8 +964,70 @@ typedef struct t2_melspec_args {
     int time_major;
     int return_power;             /* tests: magnitude^2 instead of the magnitude and no clamp / log: out = sum_bin mel * (re^2 + im^2 + mag_eps) */
     int force_splits;             /* 0: the plan's splits; 1..passes: that many (tests: the bits do not depend on it) */
+    float* mel_sum;               /* NULL, or [B, nf_max, n_mels]: receives the mel sum before clamp and log at frames < nf_b (what
+                                   * t2_melspec_backward takes); out's bits do not depend on it */
 } t2_melspec_args;
 int t2_melspec(const t2_melspec_args* a, void* stream);
+
+/* ---- Log-mel and STFT analysis: backward with respect to the samples ---------------------------------
+ * Replaces what torch autograd derives from the reference's layers.py: TacotronSTFT.mel_spectrogram (:60-80), stft.py:
+ * STFT.transform (:77-105) and utils.py: mel_spectrogram (:73-79): the gradient of a loss on the log-mel (or on re, im)
+ * with respect to the waveform.  With g = dL/dout and s the mel sum the forward kept:
+ *   ds[m][f]  = g[m][f] / s[m][f] where s >= clip_val (torch.clamp's mask), else 0;
+ *   dmag[bin] = sum_m mel[m][bin] * ds[m];
+ *   dz        = dmag * z / mag where mag > 0, else exactly 0 (torch's sqrt backward gives 0 * inf = NaN at digital silence
+ *               with mag_eps = 0; a clipped frame contributes exactly 0 here whatever z is);
+ *   dxpad[t]  = sum_{f*hop + k = t} sum_c forward_basis[c][k] * dz[c][f]   (the synthesis kernel's overlap-add GEMM);
+ *   dx[i]     = dxpad[pad+i] + [1 <= i <= pad] dxpad[pad-i] + [L-1-pad <= i <= L-2] dxpad[pad+2(L-1)-i] for i < L = len_b, else 0.
+ * z is recomputed from x with the forward's table (the forward's bits), never stored by the forward.  Exact fp32 on the
+ * matrix cores, no atomics, every sum in a fixed order: bit-identical from run to run and for an item alone or in a batch.
+ * g at frames >= nf_b and x behind len_b are never read.  Beyond the forward's limits the backward needs hop dividing N
+ * and N / hop <= 64; refused by name in t2_last_error otherwise.  No gradient for the bases. */
+typedef struct t2_melspec_grad_plan_info {
+    int bins, passes, row_tiles, overlap;
+    long nf_max;
+    long grid_x, grid_y, grid_z;  /* the bins-side kernel: 32-frame tiles, passes of 64 bins, items */
+    long fold_grid_x, fold_grid_y;/* the samples-side GEMM: tiles of 32 hop-blocks over nf_max - 1 + N/hop, column groups of hop */
+    size_t melt_floats;           /* packed transposed mel table */
+    size_t basis_floats;          /* forward basis in the synthesis kernel's order (t2_stft_plan's inv_floats) */
+    size_t packed_bytes;          /* both, in that order: what t2_melspec_grad_pack writes */
+    size_t dz_floats;             /* workspace: d_re and d_im, B * bins * nf_max each */
+    size_t dxpad_floats;          /* workspace: B * (n + 2*pad) */
+    size_t workspace_floats;      /* both, in that order */
+} t2_melspec_grad_plan_info;
+/* Pure host call (no device). */
+int t2_melspec_grad_plan(int N, int hop, int pad, int n_mels, long n, int B, t2_melspec_grad_plan_info* out);
+/* forward_basis, mel_basis as for t2_melspec_pack.  Writes `packed` (packed_bytes); once per module and mel basis. */
+int t2_melspec_grad_pack(int N, int hop, int n_mels, const float* forward_basis, const float* mel_basis, float* packed, void* stream);
+typedef struct t2_melspec_backward_args {
+    int B, N, hop, pad, n_mels;
+    long n;
+    const float* x;               /* [B, n], the forward's input */
+    const int* lengths;           /* as the forward's */
+    const float* packed;          /* t2_melspec_pack's */
+    const float* grad_packed;     /* t2_melspec_grad_pack's */
+    const float* mel_sum;         /* [B, nf_max, n_mels] from the forward */
+    const float* g;               /* dL/dout in out's layout: [B, n_mels, nf_max], or [B, nf_max, n_mels] with g_time_major */
+    float* workspace; size_t workspace_floats;
+    float* dx;                    /* [B, n]; zero from len_b on */
+    float mag_eps, clip_val;
+    int g_time_major;
+} t2_melspec_backward_args;
+int t2_melspec_backward(const t2_melspec_backward_args* a, void* stream);
+/* The samples side alone: the backward of t2_stft_analysis(_ragged) for gradients d_re, d_im [B, N/2+1, 1 + n/hop] of its re
+ * and im outputs (either may be NULL: zeros), pad = N/2 (stft.py:84-99 under autograd).  basis_table: the forward basis in
+ * the synthesis kernel's order: the second part of t2_melspec_grad_pack's buffer, or the inverse part of t2_stft_pack's when
+ * it was handed the forward basis as its inverse_basis.  lengths: NULL, or sample counts as t2_stft_analysis_ragged takes
+ * them.  dxpad: B * (n + N) floats of scratch.  dx [B, n]. */
+typedef struct t2_stft_analysis_backward_args {
+    int B, N, hop; long n;
+    const float* d_re; const float* d_im;
+    const float* basis_table;
+    const int32_t* lengths;
+    float* dxpad;
+    float* dx;
+} t2_stft_analysis_backward_args;
+int t2_stft_analysis_backward(const t2_stft_analysis_backward_args* a, void* stream);
 
 /* ---- Silence trim (leading and trailing silence of ragged 16-bit audio) ------------------------------
  * Replaces the reference's pydub trim: remove_silence.py:7-36 (detect_leading_silence and the loop around it) and

@@ -16,7 +16,17 @@ the command):
 Then the launch shapes: the kernel alone (stft.log_mel into a caller's buffers) for B utterances of --seconds at every
 split count, which is what the plan's threshold (kernels.h kMelSplitBelow) is chosen from.
 The kernel's useful work is 2 * 2*(N/2+1) * N FLOP per frame (the mel product adds 2 * n_mels * (N/2+1), 4 %, not counted);
-each kernel line gives that over its time and the share of the 157.3 TFLOP/s fp32 matrix peak.  A run without a GPU fails."""
+each kernel line gives that over its time and the share of the 157.3 TFLOP/s fp32 matrix peak.  A run without a GPU fails.
+
+  python scripts/time_melspec.py --grad [--seconds 9] [--warmup 5] [--reps 50] [--rounds 3]
+
+times instead the spectral loss  sum |mel(y_hat) - mel(y)|  in utils.mel_spectrogram's convention, forward and backward down
+to y_hat.grad, at 16 x 8192 samples (HiFi-GAN's training segment) and at one utterance of --seconds: this package's path
+(utils.mel_spectrogram_from_audio(differentiable=True): melspec_kernel keeping the mel sum, melspec_grad_kernel, the overlap-add
+GEMM, the fold) against the same formula in torch ops under autograd on the same GPU (reflect pad, torch.stft, sqrt, matmul,
+clamp, log).  Then the HIP path's two C calls alone on buffers of this script: the forward keeping the mel sum (t2_melspec) and
+the whole backward (t2_melspec_backward).  The split of the backward by kernel comes from running this command under
+rocprofv3 --kernel-trace --stats (profiles/README.md)."""
 import argparse, os, statistics, sys, tempfile
 ap = argparse.ArgumentParser()
 ap.add_argument("--seconds", type=float, default=9.0)
@@ -24,6 +34,7 @@ ap.add_argument("--warmup", type=int, default=5)
 ap.add_argument("--reps", type=int, default=50)
 ap.add_argument("--rounds", type=int, default=3)
 ap.add_argument("--pairs", type=int, default=32)
+ap.add_argument("--grad", action="store_true")
 a = ap.parse_args()
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -80,6 +91,62 @@ def report(name, o, t, os_, ts_, note=""):
     print(f"  {name:44s} kernel path {o:8.3f} ms   replaced path {t:8.3f} ms  = {t / o:6.2f} x   (rounds: {', '.join(f'{v:.3f}' for v in os_)} | "
           f"{', '.join(f'{v:.3f}' for v in ts_)}){note}", flush=True)
 
+
+def grad_times():
+    from tacotron2_subword_amd import utils
+    pad = (N - HOP) // 2
+    front, basis = utils._front(N, NMEL, SR, HOP, WIN, 0.0, 8000.0, torch.device("cuda", torch.cuda.current_device()))
+    window = torch.hann_window(WIN, device="cuda")
+
+    def torch_mel(y):
+        yp = torch.nn.functional.pad(y.unsqueeze(1), (pad, pad), mode="reflect").squeeze(1)
+        spec = torch.stft(yp, N, hop_length=HOP, win_length=WIN, window=window, center=False, return_complex=True)
+        return torch.log(torch.clamp(torch.matmul(basis, torch.sqrt(spec.real.pow(2) + spec.imag.pow(2) + 1e-9)), min=1e-5))
+
+    print(f"spectral loss sum|mel(y_hat) - mel(y)|, forward + backward to y_hat.grad, {N}/{HOP}/{WIN}, {NMEL} mel bands, pad {pad}, fp32; "
+          f"{a.warmup} warm-up + {a.reps} timed calls per figure, median of {a.rounds} alternating rounds", flush=True)
+    for name, B, n in (("16 x 8192 samples", 16, 8192), (f"1 x {a.seconds:g} s", 1, int(a.seconds * SR))):
+        y = torch.stack([signal(n, i) for i in range(B)]).cuda()
+        y_hat = (0.9 * torch.stack([signal(n, 50 + i) for i in range(B)])).cuda().requires_grad_(True)
+        with torch.no_grad():
+            target = utils.mel_spectrogram_from_audio(y)
+
+        def ours():
+            y_hat.grad = None
+            (utils.mel_spectrogram_from_audio(y_hat, differentiable=True) - target).abs().sum().backward()
+
+        def theirs():
+            y_hat.grad = None
+            (torch_mel(y_hat) - target).abs().sum().backward()
+
+        ours()
+        g_ours = y_hat.grad.clone()
+        theirs()
+        diff = float((g_ours - y_hat.grad).abs().max() / y_hat.grad.abs().max())
+        o, t, os_, ts_ = alternating(ours, theirs, a.reps)
+        report(name, o, t, os_, ts_, f"  gradients differ by {diff:.2e} of the largest")
+        # the split by kernel, through the C entries on buffers of this script
+        plan, gplan = L.melspec_plan(N, HOP, pad, NMEL, n, B), L.melspec_grad_plan(N, HOP, pad, NMEL, n, B)
+        x = y_hat.detach().contiguous()
+        out = torch.empty(B, NMEL, plan.nf_max, device="cuda")
+        sums = torch.empty(B, plan.nf_max, NMEL, device="cuda")
+        scratch = torch.empty(max(plan.split_scratch_floats, 1), device="cuda")
+        g = torch.sign(torch.randn(B, NMEL, plan.nf_max, device="cuda"))
+        ws, dx = torch.empty(gplan.workspace_floats, device="cuda"), torch.empty_like(x)
+        tables, gtables = front.mel_tables(basis), front.mel_grad_tables(basis)
+        fa = L.MelspecArgs(B, N, HOP, pad, NMEL, n, L.ptr(x), None, L.ptr(tables), L.ptr(out), L.ptr(scratch), scratch.numel(), None,
+                           1e-9, 1e-5, 1.0, 0.0, 0, 0, 0, L.ptr(sums))
+        ba = L.MelspecBackwardArgs(B, N, HOP, pad, NMEL, n, L.ptr(x), None, L.ptr(tables), L.ptr(gtables), L.ptr(sums), L.ptr(g), L.ptr(ws), ws.numel(),
+                                   L.ptr(dx), 1e-9, 1e-5, 0)
+        f_ms = event_ms(lambda: L.check(L.lib().t2_melspec(fa, L.stream())), a.warmup, a.reps)
+        b_ms = event_ms(lambda: L.check(L.lib().t2_melspec_backward(ba, L.stream())), a.warmup, a.reps)
+        print(f"    C calls alone: forward keeping the mel sum (plan splits {plan.splits}) {f_ms:.3f} ms   backward {b_ms:.3f} ms   "
+              f"grids: bins ({gplan.grid_x}, {gplan.grid_y}, {gplan.grid_z}), GEMM ({gplan.fold_grid_x}, {gplan.fold_grid_y}, {B})", flush=True)
+
+
+if a.grad:
+    grad_times()
+    sys.exit(0)
 
 with torch.no_grad():
     m = S.TacotronSTFT(N, HOP, WIN, NMEL, SR, 0.0, 8000.0).cuda()

@@ -364,7 +364,26 @@ class MelspecArgs(C.Structure):
                 ("x", C.c_void_p), ("lengths", C.c_void_p), ("packed", C.c_void_p), ("out", C.c_void_p), ("scratch", C.c_void_p),
                 ("scratch_floats", C.c_size_t), ("frame_lengths", C.c_void_p),
                 ("mag_eps", C.c_float), ("clip_val", C.c_float), ("C", C.c_float), ("pad_value", C.c_float),
-                ("time_major", C.c_int), ("return_power", C.c_int), ("force_splits", C.c_int)]
+                ("time_major", C.c_int), ("return_power", C.c_int), ("force_splits", C.c_int), ("mel_sum", C.c_void_p)]
+
+
+class MelspecGradPlanInfo(C.Structure):
+    _fields_ = [("bins", C.c_int), ("passes", C.c_int), ("row_tiles", C.c_int), ("overlap", C.c_int), ("nf_max", C.c_long),
+                ("grid_x", C.c_long), ("grid_y", C.c_long), ("grid_z", C.c_long), ("fold_grid_x", C.c_long), ("fold_grid_y", C.c_long),
+                ("melt_floats", C.c_size_t), ("basis_floats", C.c_size_t), ("packed_bytes", C.c_size_t),
+                ("dz_floats", C.c_size_t), ("dxpad_floats", C.c_size_t), ("workspace_floats", C.c_size_t)]
+
+
+class MelspecBackwardArgs(C.Structure):
+    _fields_ = [("B", C.c_int), ("N", C.c_int), ("hop", C.c_int), ("pad", C.c_int), ("n_mels", C.c_int), ("n", C.c_long),
+                ("x", C.c_void_p), ("lengths", C.c_void_p), ("packed", C.c_void_p), ("grad_packed", C.c_void_p), ("mel_sum", C.c_void_p),
+                ("g", C.c_void_p), ("workspace", C.c_void_p), ("workspace_floats", C.c_size_t), ("dx", C.c_void_p),
+                ("mag_eps", C.c_float), ("clip_val", C.c_float), ("g_time_major", C.c_int)]
+
+
+class StftAnalysisBackwardArgs(C.Structure):
+    _fields_ = [("B", C.c_int), ("N", C.c_int), ("hop", C.c_int), ("n", C.c_long), ("d_re", C.c_void_p), ("d_im", C.c_void_p),
+                ("basis_table", C.c_void_p), ("lengths", C.c_void_p), ("dxpad", C.c_void_p), ("dx", C.c_void_p)]
 
 
 class SilencePlanInfo(C.Structure):
@@ -517,6 +536,7 @@ EXPORTS = ["t2_last_error", "t2_version", "t2_chain_status", "t2_chain_status_cl
            "t2_hifigan_plan", "t2_hifigan_pack", "t2_hifigan_forward", "t2_hifigan_forward_ragged", "t2_vocoder_packed_floats", "t2_vocoder_conv1d", "t2_vocoder_conv_transpose1d",
            "t2_vocoder_conv_ragged", "t2_stft_analysis_ragged", "t2_stft_synthesis_ragged",
            "t2_stft_plan", "t2_stft_pack", "t2_stft_analysis", "t2_stft_synthesis", "t2_melspec_plan", "t2_melspec_pack", "t2_melspec",
+           "t2_melspec_grad_plan", "t2_melspec_grad_pack", "t2_melspec_backward", "t2_stft_analysis_backward",
            "t2_silence_plan", "t2_silence_trim",
            "t2_waveglow_plan", "t2_waveglow_pack", "t2_waveglow_infer", "t2_waveglow_packed_floats", "t2_waveglow_gated_conv", "t2_waveglow_res_skip",
            "t2_waveglow_upsample", "t2_waveglow_couple", "t2_waveglow_forward_plan", "t2_waveglow_forward", "t2_waveglow_logdet",
@@ -610,6 +630,10 @@ def lib() -> C.CDLL:
         L.t2_melspec_plan.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_long, C.c_int, C.POINTER(MelspecPlanInfo)]
         L.t2_melspec_pack.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.t2_melspec.argtypes = [C.POINTER(MelspecArgs), C.c_void_p]
+        L.t2_melspec_grad_plan.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_long, C.c_int, C.POINTER(MelspecGradPlanInfo)]
+        L.t2_melspec_grad_pack.argtypes = [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.t2_melspec_backward.argtypes = [C.POINTER(MelspecBackwardArgs), C.c_void_p]
+        L.t2_stft_analysis_backward.argtypes = [C.POINTER(StftAnalysisBackwardArgs), C.c_void_p]
         L.t2_silence_plan.argtypes = [C.c_int, C.c_int, C.c_double, C.c_long, C.c_int, C.POINTER(SilencePlanInfo)]
         L.t2_silence_trim.argtypes = [C.POINTER(SilenceArgs), C.c_void_p]
         L.t2_waveglow_plan.argtypes = [C.POINTER(WaveglowConfig), C.c_int, C.c_int, C.POINTER(WaveglowPlanInfo)]
@@ -1118,6 +1142,14 @@ def melspec_plan(N: int, hop: int, pad: int, n_mels: int, n: int, B: int = 1) ->
     host, no device needed); raises with the name and value of what the kernel does not take."""
     info = MelspecPlanInfo()
     check(lib().t2_melspec_plan(N, hop, pad, n_mels, n, B, C.byref(info)))
+    return info
+
+
+def melspec_grad_plan(N: int, hop: int, pad: int, n_mels: int, n: int, B: int = 1) -> MelspecGradPlanInfo:
+    """Table and workspace sizes and the grids of the log-mel backward (t2_melspec_grad_plan: pure host, no device needed);
+    raises with the name and value of what the backward does not take (hop not dividing N, N / hop > 64)."""
+    info = MelspecGradPlanInfo()
+    check(lib().t2_melspec_grad_plan(N, hop, pad, n_mels, n, B, C.byref(info)))
     return info
 
 

@@ -672,7 +672,30 @@ int t2_melspec_pack(int N, int n_mels, const float* forward_basis, const float* 
 int t2_melspec(const t2_melspec_args* a, void* stream) {
     T2_REQUIRE(a, "t2_melspec: null arguments");
     return melspec(MelSpecArgs{a->B, a->N, a->hop, a->pad, a->n_mels, a->n, a->x, a->lengths, a->packed, a->out, a->scratch, a->scratch_floats, a->frame_lengths,
-                               a->mag_eps, a->clip_val, a->C, a->pad_value, a->time_major, a->return_power, a->force_splits}, (hipStream_t)stream);
+                               a->mag_eps, a->clip_val, a->C, a->pad_value, a->time_major, a->return_power, a->force_splits, a->mel_sum}, (hipStream_t)stream);
+}
+int t2_melspec_grad_plan(int N, int hop, int pad, int n_mels, long n, int B, t2_melspec_grad_plan_info* out) {
+    T2_REQUIRE(out, "t2_melspec_grad_plan: null pointer");
+    MelGradPlan p;
+    T2_TRY(melspec_grad_plan(N, hop, pad, n_mels, n, B, &p));
+    out->bins = p.cutoff; out->passes = p.passes; out->row_tiles = p.row_tiles; out->overlap = p.overlap; out->nf_max = p.nf_max;
+    out->grid_x = p.frame_tiles; out->grid_y = p.passes; out->grid_z = B;
+    out->fold_grid_x = p.q_tiles; out->fold_grid_y = (p.col_tiles + p.wave_cols - 1) / p.wave_cols;
+    out->melt_floats = p.melt_floats; out->basis_floats = p.basis_floats; out->packed_bytes = (p.melt_floats + p.basis_floats) * sizeof(float);
+    out->dz_floats = p.dz_floats; out->dxpad_floats = p.dxpad_floats; out->workspace_floats = p.dz_floats + p.dxpad_floats;
+    return 0;
+}
+int t2_melspec_grad_pack(int N, int hop, int n_mels, const float* forward_basis, const float* mel_basis, float* packed, void* stream) {
+    return melspec_grad_pack(N, hop, n_mels, forward_basis, mel_basis, packed, (hipStream_t)stream);
+}
+int t2_melspec_backward(const t2_melspec_backward_args* a, void* stream) {
+    T2_REQUIRE(a, "t2_melspec_backward: null arguments");
+    return melspec_backward(MelSpecBwd{a->B, a->N, a->hop, a->pad, a->n_mels, a->n, a->x, a->lengths, a->packed, a->grad_packed, a->mel_sum, a->g,
+                                       a->workspace, a->workspace_floats, a->dx, a->mag_eps, a->clip_val, a->g_time_major}, (hipStream_t)stream);
+}
+int t2_stft_analysis_backward(const t2_stft_analysis_backward_args* a, void* stream) {
+    T2_REQUIRE(a, "t2_stft_analysis_backward: null arguments");
+    return stft_analysis_backward(StftAnalysisBwd{a->B, a->N, a->hop, a->N / 2, a->n, a->d_re, a->d_im, a->basis_table, a->lengths, a->dxpad, a->dx}, (hipStream_t)stream);
 }
 
 int t2_silence_plan(int sample_rate, int chunk_ms, double threshold_db, long n, int B, t2_silence_plan_info* out) {

@@ -573,6 +573,20 @@ struct StftSynthesis {
 int stft_synthesis(const StftSynthesis& a, hipStream_t s);
 // the forward part of stft_pack alone (any hop): fwd [2*(N/2+1)][N] -> packed, ((N/2+1 + 15)/16) * ((N + 31)/32) * 1024 floats
 int stft_pack_forward(int N, const float* fwd, float* packed, hipStream_t s);
+// the synthesis-order part of stft_pack alone, for whatever basis [2*(N/2+1)][N] it is handed -> packed, inv_floats floats
+int stft_pack_overlap(int N, int hop, const float* basis, float* packed, hipStream_t s);
+// The analysis' backward with respect to the samples: the synthesis kernel's overlap-add GEMM with the forward basis (table:
+// stft_pack_overlap of it), the planes taken as they are, nothing scaled and nothing trimmed, then the fold of the reflect
+// padding.  d_re, d_im [B][N/2+1][nf_max] (each nullable: zeros), nf_max = (n + 2*pad - N)/hop + 1, read at frames below the
+// item's own count only; lengths (nullable, device [B]): sample counts, clamped to [0, n]; dxpad: B * (n + 2*pad) floats of
+// scratch; dx [B][n], zero from the item's length on
+// Waves (32-column tiles of r < hop) per workgroup of that GEMM, as the synthesis launch chooses them; the plan reports the grid from it.
+// The bits do not depend on it.
+inline int stft_backward_wave_cols(int col_tiles) { return col_tiles >= 8 ? 8 : (col_tiles >= 4 ? 4 : (col_tiles >= 2 ? 2 : 1)); }
+struct StftAnalysisBwd {
+    int B, N, hop, pad; long n; const float* d_re; const float* d_im; const float* table; const int32_t* lengths; float* dxpad; float* dx;
+};
+int stft_analysis_backward(const StftAnalysisBwd& a, hipStream_t s);
 
 // ------------------------------------------------------------------ log-mel front end (melspec.hip)
 constexpr int kMelMaxMels = 128;                 // four waves x 32 mel rows
@@ -597,8 +611,28 @@ struct MelSpecArgs {
     const float* x; const int* lengths; const float* packed; float* out; float* scratch; size_t scratch_floats; int* frame_lengths;
     float mag_eps, clip_val, C, pad_value;
     int time_major, return_power, force_splits;
+    float* mel_sum = nullptr;                    // [B][nf_max][n_mels], nullable: the mel sum before clamp and log, frames below the item's count only
 };
 int melspec(const MelSpecArgs& a, hipStream_t s);
+
+// The backward of the log-mel front end with respect to the samples.  Two tables beside the forward's: the mel
+// basis in the order the transposed product consumes it, and the forward basis in the synthesis kernel's order.
+// Workspace, in floats: [d_re | d_im : B * bins * nf_max each][dxpad : B * (n + 2*pad)].
+struct MelGradPlan {
+    int cutoff, bin_tiles, kchunks, passes, row_tiles, overlap, col_tiles, wave_cols; long nf_max, frame_tiles, q_tiles;
+    size_t melt_floats, basis_floats, dz_floats, dxpad_floats;
+};
+int melspec_grad_plan(int N, int hop, int pad, int n_mels, long n, int B, MelGradPlan* out);   // validates; no device
+int melspec_grad_pack(int N, int hop, int n_mels, const float* fwd, const float* melb, float* packed, hipStream_t s);
+// g: the gradient with respect to out, in out's layout (g_time_major: [B][nf_max][n_mels]); read at frames below the item's count only
+struct MelSpecBwd {
+    int B, N, hop, pad, n_mels; long n;
+    const float* x; const int* lengths; const float* packed; const float* grad_packed; const float* mel_sum; const float* g;
+    float* workspace; size_t workspace_floats; float* dx;
+    float mag_eps, clip_val;
+    int g_time_major;
+};
+int melspec_backward(const MelSpecBwd& a, hipStream_t s);
 
 // ------------------------------------------------------------------ silence trim (silence.hip)
 constexpr int kSilChunksPerGroup = 8;            // chunks a scan workgroup owns: two per wave

@@ -35,6 +35,7 @@ struct MelSpec {
     long n, nf_max;
     int B, N, hop, pad, cutoff, bin_tiles, kchunks, passes, n_mels, row_tiles, splits, time_major, power;
     float mag_eps, clip, C, pad_value;
+    float* sums;                                               // nullable: the mel sum [B][nf_max][n_mels] kept for the backward
 };
 
 struct MelChunk { float x[4]; f32x4 a[4]; int live; };   // what a thread holds of one chunk: 4 samples for the slab (bit i of live: sample i counts), 16 table values
@@ -74,7 +75,8 @@ __device__ __forceinline__ void mel_store_time_major(float* lds, const f32x16& v
     }
 }
 
-// three waves per SIMD: 149 registers with the accumulators among them instead of 154 + 16 (two waves), still nothing spilled
+// three waves per SIMD: 160 registers with the accumulators among them (149 before the optional store of the mel sum) instead of
+// 154 + 16 (two waves), still nothing spilled
 __global__ void __launch_bounds__(256, 3) melspec_kernel(MelSpec p) {
     __shared__ float lds[kMelLdsFloats];
     float* slab = lds;
@@ -187,6 +189,7 @@ __global__ void __launch_bounds__(256, 3) melspec_kernel(MelSpec p) {
         if (++c == p.kchunks) { c = 0; ++ps; }
     }
     if (p.splits > 1) return;
+    if (p.sums) mel_store_time_major(lds, total, p.sums + ((size_t)b * p.nf_max + f0) * p.n_mels, p.n_mels, p.row_tiles, nf - f0, nf - f0, 0.f);
 #pragma unroll
     for (int e = 0; e < 16; ++e) total[e] = mel_finish(p, total[e]);
     if (p.time_major) {
@@ -218,6 +221,7 @@ __global__ void __launch_bounds__(256) melspec_finish_kernel(MelSpec p, size_t c
             total = total + p.scratch[(size_t)ps * plane + idx];
         }
         v = mel_finish(p, total);
+        if (p.sums) p.sums[idx] = total;
     }
     p.out[p.time_major ? idx : ((size_t)b * p.n_mels + m) * p.nf_max + f] = v;
 }
@@ -294,6 +298,7 @@ int melspec(const MelSpecArgs& a, hipStream_t s) {
     p.B = a.B; p.N = a.N; p.hop = a.hop; p.pad = a.pad; p.cutoff = pl.cutoff; p.bin_tiles = pl.bin_tiles; p.kchunks = pl.kchunks; p.passes = pl.passes;
     p.n_mels = a.n_mels; p.row_tiles = pl.row_tiles; p.splits = S; p.time_major = a.time_major != 0; p.power = a.return_power != 0;
     p.mag_eps = a.mag_eps; p.clip = a.clip_val; p.C = a.C; p.pad_value = a.pad_value;
+    p.sums = a.mel_sum;
     hipLaunchKernelGGL(melspec_kernel, dim3((unsigned)pl.frame_tiles, (unsigned)S, (unsigned)a.B), dim3(256), 0, s, p);
     T2_LAUNCH_CHECK();
     if (S > 1) {
@@ -302,6 +307,182 @@ int melspec(const MelSpecArgs& a, hipStream_t s) {
         T2_LAUNCH_CHECK();
     }
     return 0;
+}
+
+// ------------------------------------------------------------------------------------------------------------------
+// backward with respect to the samples (layers.py:60-80, stft.py:77-105, utils.py:73-79 under torch autograd)
+//
+//   ds[m][f]  = g[m][f] / s[m][f]  where s >= clip, else 0          (s: the mel sum the forward kept)
+//   dmag[bin] = sum_m melb[m][bin] * ds[m]
+//   dz        = dmag * z / mag     where mag > 0, else exactly 0    (torch's sqrt gives 0 * inf = NaN there)
+// A workgroup owns (32 frames, one pass of 64 bins, item).  Wave w recomputes re, im of bin tile 4*pass + w with the forward's
+// table and chain, so z has the forward's bits and is never stored by it.  ds of every mel row is staged once in LDS, and
+// the transposed mel product runs on the matrix cores from a table whose 32-row tile repeats each bin in its re and its im
+// row: the wave's second accumulator then holds dmag of a bin in the very elements where the first holds its re and im.
+// The k of that chain is the mel row, ascending.  dz goes to two planes [B][bins][nf_max]; stft_analysis_backward turns them
+// into dx.  Frames at or behind the item's count are neither read nor written.
+// ------------------------------------------------------------------------------------------------------------------
+constexpr int kMelGradStride = kStftTile + 1;
+constexpr int kMelGradLdsFloats = kMelMaxMels * kMelGradStride;   // ds [mel row][frame]; the recompute's slab uses its head before
+static_assert(kMelKC * kMelSlabStride <= kMelGradLdsFloats, "the slab fits into the ds stage");
+
+struct MelGrad {
+    const float* x; const int* lengths; const f32x4* pf; const f32x4* pt; const float* sums; const float* g; float* d_re; float* d_im;
+    long n, nf_max;
+    int N, hop, pad, cutoff, bin_tiles, kchunks, n_mels, row_tiles, g_time_major;
+    float mag_eps, clip;
+};
+
+__global__ void __launch_bounds__(256) melspec_grad_kernel(MelGrad p) {
+    __shared__ float lds[kMelGradLdsFloats];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, hk = lane >> 5;
+    const int b = blockIdx.z;
+    const long f0 = (long)blockIdx.x * kStftTile;
+    long ilen = p.n;
+    if (p.lengths) {
+        const long l = p.lengths[b];
+        ilen = l < 0 ? 0 : (l > p.n ? p.n : l);
+    }
+    const long nf = mel_frames(ilen, p.N, p.hop, p.pad);
+    if (f0 >= nf) return;                                      // uniform over the workgroup: a tile behind the item's frames
+    const int mt = blockIdx.y * 4 + wave;
+    const bool active = mt < p.bin_tiles;                      // uniform over the wave
+    const float* xb = p.x + (size_t)b * p.n;
+    const f32x4* pf = p.pf + (size_t)(active ? mt : 0) * p.kchunks * 256;
+    f32x16 acc = {0};
+    for (int c = 0; c < p.kchunks; ++c) {
+        if (c) __syncthreads();
+        const int kl = threadIdx.x & 31, k = c * kMelKC + kl;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int fl = (threadIdx.x >> 5) + 8 * i;
+            const long f = f0 + fl;
+            float v = 0.f;
+            if (f < nf && k < p.N) {
+                long t = f * p.hop + k - p.pad;                // reflect padding: ilen > pad keeps both mirrors inside [0, ilen)
+                if (t < 0) t = -t;
+                else if (t >= ilen) t = 2 * (ilen - 1) - t;
+                v = xb[t];
+            }
+            lds[kl * kMelSlabStride + fl] = v;
+        }
+        __syncthreads();
+        if (active) {
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+                const f32x4 a = pf[(size_t)c * 256 + g * 64 + lane];
+#pragma unroll
+                for (int i = 0; i < 4; ++i)
+                    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[i], lds[(8 * g + 2 * i + hk) * kMelSlabStride + (lane & 31)], acc, 0, 0, 0);
+            }
+        }
+    }
+    __syncthreads();                                           // the slab is read; ds takes its place
+    const int rows = 32 * p.row_tiles;
+    for (int idx = threadIdx.x; idx < rows * kStftTile; idx += 256) {
+        const int m = idx % rows, fl = idx / rows;             // lanes along the mel row, as s lies in memory
+        const long f = f0 + fl;
+        float v = 0.f;
+        if (m < p.n_mels && f < nf) {
+            const size_t ot = ((size_t)b * p.nf_max + f) * p.n_mels + m;
+            const float sv = p.sums[ot];
+            if (sv >= p.clip) v = p.g[p.g_time_major ? ot : ((size_t)b * p.n_mels + m) * p.nf_max + f] / sv;   // torch.clamp's mask
+        }
+        lds[m * kMelGradStride + fl] = v;
+    }
+    __syncthreads();
+    if (!active) return;
+    f32x16 dm = {0};
+    const f32x4* pt = p.pt + (size_t)mt * p.row_tiles * 256 + lane;
+    for (int kc = 0; kc < p.row_tiles; ++kc) {
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+            const f32x4 a = pt[(size_t)kc * 256 + g * 64];
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+                dm = __builtin_amdgcn_mfma_f32_32x32x2f32(a[i], lds[(32 * kc + 8 * g + 2 * i + hk) * kMelGradStride + (lane & 31)], dm, 0, 0, 0);
+        }
+    }
+    const long f = f0 + (lane & 31);
+    if (f >= nf) return;
+    // element e (bit 2 clear) is re, e + 4 is im of bin 16*mt + 8*(e>>3) + 4*hk + (e&3); dm holds that bin's dmag in both
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int bin = mt * 16 + 8 * h + 4 * hk + i;
+            if (bin >= p.cutoff) continue;
+            const float re = acc[8 * h + i], im = acc[8 * h + i + 4], d = dm[8 * h + i];
+            const float mg = sqrtf(__fadd_rn(__fadd_rn(__fmul_rn(re, re), __fmul_rn(im, im)), p.mag_eps));   // the forward's magnitude
+            const size_t o = ((size_t)b * p.cutoff + bin) * p.nf_max + f;
+            p.d_re[o] = mg > 0.f ? __fmul_rn(d, re / mg) : 0.f;
+            p.d_im[o] = mg > 0.f ? __fmul_rn(d, im / mg) : 0.f;
+        }
+    }
+}
+
+// transposed mel table:  [bin_tile][row_tile][g][lane][i] = melb[32*row_tile + 8*g + 2*i + (lane >> 5)][bin],  tile row r = lane & 31:
+//                        bin = 16*bin_tile + 8*(r>>4) + (r&7), whatever (r>>3)&1 says: the re row and the im row of a bin hold the same
+__global__ void __launch_bounds__(256) melspec_pack_t_kernel(const float* __restrict__ melb, float* __restrict__ out, int n_mels, int cutoff, int row_tiles, size_t total) {
+    const size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= total) return;
+    const int i = idx & 3, lane = (idx >> 2) & 63, g = (idx >> 8) & 3;
+    const size_t rest = idx >> 10;
+    const int kc = (int)(rest % row_tiles), bt = (int)(rest / row_tiles);
+    const int r = lane & 31, bin = bt * 16 + 8 * (r >> 4) + (r & 7), m = 32 * kc + 8 * g + 2 * i + (lane >> 5);
+    out[idx] = (bin < cutoff && m < n_mels) ? melb[(size_t)m * cutoff + bin] : 0.f;
+}
+
+int melspec_grad_plan(int N, int hop, int pad, int n_mels, long n, int B, MelGradPlan* out) {
+    T2_REQUIRE(out, "melspec backward: null plan");
+    MelPlan f;
+    T2_TRY_RC(melspec_plan(N, hop, pad, n_mels, n, B, &f));
+    T2_REQUIRE(N % hop == 0, "melspec backward: filter_length=%d is not a multiple of hop_length=%d: the overlap-add GEMM needs whole overlaps", N, hop);
+    T2_REQUIRE(N / hop <= kStftMaxOverlap, "melspec backward: filter_length=%d over hop_length=%d is %d overlaps, at most %d", N, hop, N / hop, kStftMaxOverlap);
+    T2_REQUIRE(f.nf_max <= INT32_MAX / 2 / hop, "melspec backward: %ld frames exceed the limit at hop_length=%d", f.nf_max, hop);
+    StftPlan sp;
+    T2_TRY_RC(stft_plan(N, hop, (int)f.nf_max, &sp));
+    MelGradPlan p;
+    p.cutoff = f.cutoff; p.bin_tiles = f.bin_tiles; p.kchunks = f.kchunks; p.passes = f.passes; p.row_tiles = f.row_tiles;
+    p.overlap = sp.overlap; p.col_tiles = sp.col_tiles;
+    p.wave_cols = stft_backward_wave_cols(sp.col_tiles);
+    p.nf_max = f.nf_max; p.frame_tiles = f.frame_tiles;
+    p.q_tiles = (f.nf_max - 1 + sp.overlap + kStftTile - 1) / kStftTile;
+    p.melt_floats = (size_t)f.bin_tiles * f.row_tiles * 1024;
+    p.basis_floats = sp.inv_floats;
+    p.dz_floats = 2 * (size_t)B * f.cutoff * f.nf_max;
+    p.dxpad_floats = (size_t)B * (size_t)(n + 2L * pad);
+    *out = p;
+    return 0;
+}
+
+int melspec_grad_pack(int N, int hop, int n_mels, const float* fwd, const float* melb, float* packed, hipStream_t s) {
+    MelGradPlan pl;
+    T2_TRY_RC(melspec_grad_plan(N, hop, N / 2, n_mels, N, 1, &pl));
+    T2_REQUIRE(fwd && melb && packed, "melspec_grad_pack: null pointer");
+    hipLaunchKernelGGL(melspec_pack_t_kernel, dim3((unsigned)((pl.melt_floats + 255) / 256)), dim3(256), 0, s, melb, packed, n_mels, pl.cutoff, pl.row_tiles,
+                       pl.melt_floats);
+    T2_LAUNCH_CHECK();
+    return stft_pack_overlap(N, hop, fwd, packed + pl.melt_floats, s);
+}
+
+int melspec_backward(const MelSpecBwd& a, hipStream_t s) {
+    MelGradPlan pl;
+    T2_TRY_RC(melspec_grad_plan(a.N, a.hop, a.pad, a.n_mels, a.n, a.B, &pl));
+    T2_REQUIRE(a.x && a.packed && a.grad_packed && a.mel_sum && a.g && a.dx, "melspec backward: null pointer");
+    T2_REQUIRE(a.clip_val > 0.f && a.mag_eps >= 0.f, "melspec backward: clip_val=%g must be positive, mag_eps=%g not negative", a.clip_val, a.mag_eps);
+    T2_REQUIRE(a.workspace && a.workspace_floats >= pl.dz_floats + pl.dxpad_floats, "melspec backward: the workspace needs %zu floats, got %zu",
+               pl.dz_floats + pl.dxpad_floats, a.workspace ? a.workspace_floats : (size_t)0);
+    MelGrad p;
+    p.x = a.x; p.lengths = a.lengths; p.pf = reinterpret_cast<const f32x4*>(a.packed); p.pt = reinterpret_cast<const f32x4*>(a.grad_packed);
+    p.sums = a.mel_sum; p.g = a.g; p.d_re = a.workspace; p.d_im = a.workspace + pl.dz_floats / 2;
+    p.n = a.n; p.nf_max = pl.nf_max;
+    p.N = a.N; p.hop = a.hop; p.pad = a.pad; p.cutoff = pl.cutoff; p.bin_tiles = pl.bin_tiles; p.kchunks = pl.kchunks; p.n_mels = a.n_mels; p.row_tiles = pl.row_tiles;
+    p.g_time_major = a.g_time_major != 0;
+    p.mag_eps = a.mag_eps; p.clip = a.clip_val;
+    hipLaunchKernelGGL(melspec_grad_kernel, dim3((unsigned)pl.frame_tiles, (unsigned)pl.passes, (unsigned)a.B), dim3(256), 0, s, p);
+    T2_LAUNCH_CHECK();
+    return stft_analysis_backward(StftAnalysisBwd{a.B, a.N, a.hop, a.pad, a.n, p.d_re, p.d_im, a.grad_packed + pl.melt_floats, a.lengths, a.workspace + pl.dz_floats, a.dx}, s);
 }
 
 }  // namespace t2

@@ -118,9 +118,13 @@ struct StftSyn {
     long qbase, out_len;
     float strength, scale;
     const int32_t* nfs; int32_t* len_out;                      // nullable: per-item frame counts (clamped to [0, nf]) and the sample counts they give
+    const int32_t* lens; long n, row; int pad;                 // RAW: nullable per-item sample counts (clamped to [0, n]), the stride n + 2*pad of y's rows
 };
 
-template <int WN>
+// RAW (the analysis' backward, stft_analysis_backward): a = d_re, b = d_im taken as they are (a null plane reads as zeros),
+// the basis table is the forward one, and y is the gradient of the padded signal, dxpad[b][q*hop + r] for every sample that a
+// frame of the item covers: no envelope, no scale, no trim.  The item's frames follow from its sample count.
+template <int WN, bool RAW>
 __global__ void __launch_bounds__(WN * 64) stft_synthesis_kernel(StftSyn p) {
     __shared__ float slab[kStftKC * kStftSynStride];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, hk = lane >> 5;
@@ -137,7 +141,15 @@ __global__ void __launch_bounds__(WN * 64) stft_synthesis_kernel(StftSyn p) {
     // samples written are bounded by the item's count
     int nf = p.nf;
     long out_len = p.out_len;
-    if (p.nfs) {
+    if constexpr (RAW) {
+        long len = p.n;
+        if (p.lens) {
+            const int l = p.lens[bi];
+            len = l < 0 ? 0 : (l > p.n ? p.n : (long)l);
+        }
+        nf = (int)mel_frames(len, p.N, p.hop, p.pad);
+        out_len = nf >= 1 ? (long)p.hop * (nf - 1) + p.N : 0;  // padded samples under a frame
+    } else if (p.nfs) {
         const int l = p.nfs[bi];
         nf = l < 0 ? 0 : (l > p.nf ? p.nf : l);
         out_len = nf >= 1 ? (long)p.hop * (nf - 1) : 0;
@@ -146,7 +158,7 @@ __global__ void __launch_bounds__(WN * 64) stft_synthesis_kernel(StftSyn p) {
     f32x16 acc = {0};
 
     // a tile whose first sample lies behind the item's end stages nothing and writes zeros: uniform over the workgroup
-    for (int c = 0; c < (q0 * p.hop - p.N / 2 < out_len ? p.nchunks : 0); ++c) {
+    for (int c = 0; c < (q0 * p.hop - (RAW ? 0 : p.N / 2) < out_len ? p.nchunks : 0); ++c) {
         if (c) __syncthreads();
         for (int item = threadIdx.x; item < 16 * W; item += WN * 64) {
             const int bl = item / W, col = item - bl * W;
@@ -155,8 +167,10 @@ __global__ void __launch_bounds__(WN * 64) stft_synthesis_kernel(StftSyn p) {
             float xr = 0.f, xi = 0.f;
             if (bin < p.cutoff && f >= 0 && f < nf) {
                 const size_t o = (size_t)bin * p.nf + f;
-                const float u = pa[o], v = pb[o];
-                if (p.mode == 0) {                             // polar: u = magnitude, v = phase
+                const float u = RAW && !p.a ? 0.f : pa[o], v = RAW && !p.b ? 0.f : pb[o];
+                if constexpr (RAW) {
+                    xr = u; xi = v;
+                } else if (p.mode == 0) {                             // polar: u = magnitude, v = phase
                     float sn, cs;
                     sincosf(v, &sn, &cs);
                     xr = u * cs; xi = u * sn;
@@ -191,6 +205,11 @@ __global__ void __launch_bounds__(WN * 64) stft_synthesis_kernel(StftSyn p) {
 #pragma unroll
     for (int e = 0; e < 16; ++e) {
         const long q = q0 + (e & 3) + 8 * (e >> 2) + 4 * hk;
+        if constexpr (RAW) {
+            const long tp = q * p.hop + r;
+            if (tp < out_len) p.y[(size_t)bi * p.row + tp] = acc[e];
+            continue;
+        }
         const long t = q * p.hop + r, o = t - p.N / 2;          // stft.py:133-134: N/2 samples dropped at each end
         if (o < 0 || o >= p.out_len) continue;
         float v = acc[e];
@@ -269,14 +288,22 @@ int stft_pack_forward(int N, const float* fwd, float* packed, hipStream_t s) {
     return 0;
 }
 
+int stft_pack_overlap(int N, int hop, const float* basis, float* packed, hipStream_t s) {
+    StftPlan pl;
+    T2_TRY_RC(stft_plan(N, hop, 1, &pl));
+    T2_REQUIRE(basis && packed, "stft_pack_overlap: null pointer");
+    hipLaunchKernelGGL(stft_pack_inv_kernel, dim3((unsigned)((pl.inv_floats + 255) / 256)), dim3(256), 0, s, basis, packed, N, hop, pl.cutoff, pl.bin_tiles,
+                       pl.inv_floats);
+    T2_LAUNCH_CHECK();
+    return 0;
+}
+
 int stft_pack(int N, int hop, const float* fwd, const float* inv, const double* wsq, float* packed, hipStream_t s) {
     StftPlan pl;
     T2_TRY_RC(stft_plan(N, hop, 1, &pl));
     T2_REQUIRE(fwd && inv && packed, "stft_pack: null pointer");
     T2_TRY_RC(stft_pack_forward(N, fwd, packed, s));
-    hipLaunchKernelGGL(stft_pack_inv_kernel, dim3((unsigned)((pl.inv_floats + 255) / 256)), dim3(256), 0, s, inv, packed + pl.fwd_floats, N, hop, pl.cutoff,
-                       pl.bin_tiles, pl.inv_floats);
-    T2_LAUNCH_CHECK();
+    T2_TRY_RC(stft_pack_overlap(N, hop, inv, packed + pl.fwd_floats, s));
     float* w = packed + pl.fwd_floats + pl.inv_floats;
     if (wsq) T2_CHECK_HIP(hipMemcpyAsync(w, wsq, (size_t)N * sizeof(double), hipMemcpyDeviceToDevice, s));
     else T2_CHECK_HIP(hipMemsetAsync(w, 0, pl.wsq_floats * sizeof(float), s));
@@ -326,13 +353,70 @@ int stft_synthesis(const StftSynthesis& a, hipStream_t s) {
     p.qbase = (a.N / 2) / a.hop; p.out_len = pl.out_len;
     p.strength = a.strength; p.scale = (float)a.N / (float)a.hop;
     p.nfs = a.frame_lengths; p.len_out = a.sample_lengths;
+    p.lens = nullptr; p.n = 0; p.row = 0; p.pad = 0;
     const long qlast = (a.N / 2 + pl.out_len - 1) / a.hop;
     const int wn = pl.col_tiles >= 8 ? 8 : (pl.col_tiles >= 4 ? 4 : (pl.col_tiles >= 2 ? 2 : 1));
     dim3 grid((unsigned)((qlast - p.qbase) / kStftTile + 1), (unsigned)((pl.col_tiles + wn - 1) / wn), (unsigned)a.B);
-    if (wn == 8) hipLaunchKernelGGL(stft_synthesis_kernel<8>, grid, dim3(512), 0, s, p);
-    else if (wn == 4) hipLaunchKernelGGL(stft_synthesis_kernel<4>, grid, dim3(256), 0, s, p);
-    else if (wn == 2) hipLaunchKernelGGL(stft_synthesis_kernel<2>, grid, dim3(128), 0, s, p);
-    else hipLaunchKernelGGL(stft_synthesis_kernel<1>, grid, dim3(64), 0, s, p);
+    if (wn == 8) hipLaunchKernelGGL((stft_synthesis_kernel<8, false>), grid, dim3(512), 0, s, p);
+    else if (wn == 4) hipLaunchKernelGGL((stft_synthesis_kernel<4, false>), grid, dim3(256), 0, s, p);
+    else if (wn == 2) hipLaunchKernelGGL((stft_synthesis_kernel<2, false>), grid, dim3(128), 0, s, p);
+    else hipLaunchKernelGGL((stft_synthesis_kernel<1, false>), grid, dim3(64), 0, s, p);
+    T2_LAUNCH_CHECK();
+    return 0;
+}
+
+// dx[b][i] = dxpad[pad + i] + [1 <= i <= pad] dxpad[pad - i] + [L-1-pad <= i <= L-2] dxpad[pad + 2(L-1) - i] for i < L = the item's
+// length, three rounded adds in that order; zero from L on.  dxpad holds nothing behind the item's last frame: zero there.
+struct StftFold { const float* dxpad; float* dx; const int32_t* lens; long n, row; int N, hop, pad; };
+
+__global__ void __launch_bounds__(256) stft_fold_kernel(StftFold p) {
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= p.n) return;
+    const int b = blockIdx.y;
+    long L = p.n;
+    if (p.lens) {
+        const int l = p.lens[b];
+        L = l < 0 ? 0 : (l > p.n ? p.n : (long)l);
+    }
+    const long nf = mel_frames(L, p.N, p.hop, p.pad);
+    const long covered = nf >= 1 ? (long)p.hop * (nf - 1) + p.N : 0;
+    const float* src = p.dxpad + (size_t)b * p.row;
+    auto at = [&](long t) { return t < covered ? src[t] : 0.f; };
+    float v = 0.f;
+    if (i < L && nf >= 1) {
+#pragma clang fp contract(off)
+        v = at(p.pad + i);
+        if (i >= 1 && i <= p.pad) v = v + at(p.pad - i);
+        if (i >= L - 1 - p.pad && i <= L - 2) v = v + at(p.pad + 2 * (L - 1) - i);
+    }
+    p.dx[(size_t)b * p.n + i] = v;
+}
+
+int stft_analysis_backward(const StftAnalysisBwd& a, hipStream_t s) {
+    T2_REQUIRE(a.B >= 1 && a.B <= 65535, "stft analysis backward: B=%d outside 1..65535", a.B);
+    T2_REQUIRE(a.hop >= 1 && a.N >= 2 && a.N % 2 == 0, "stft analysis backward: filter_length=%d must be even and hop_length=%d positive", a.N, a.hop);
+    T2_REQUIRE(a.pad >= 0 && a.pad <= a.N / 2, "stft analysis backward: pad=%d outside 0..filter_length/2=%d", a.pad, a.N / 2);
+    T2_REQUIRE(a.n > a.pad && a.n + 2L * a.pad >= a.N && a.n <= INT32_MAX / 2, "stft analysis backward: n=%ld samples with pad=%d per side outside what filter_length=%d takes",
+               a.n, a.pad, a.N);
+    const long nf = (a.n + 2L * a.pad - a.N) / a.hop + 1;
+    T2_REQUIRE(nf <= INT32_MAX / 2 / a.hop, "stft analysis backward: %ld frames exceed the limit at hop_length=%d", nf, a.hop);
+    StftPlan pl;
+    T2_TRY_RC(stft_plan(a.N, a.hop, (int)nf, &pl));
+    T2_REQUIRE((a.d_re || a.d_im) && a.table && a.dxpad && a.dx, "stft analysis backward: null pointer");
+    StftSyn p{};
+    p.a = a.d_re; p.b = a.d_im; p.pi = a.table; p.y = a.dxpad;
+    p.nf = (int)nf; p.N = a.N; p.hop = a.hop; p.R = pl.overlap; p.cutoff = pl.cutoff; p.nchunks = pl.bin_tiles; p.col_tiles = pl.col_tiles;
+    p.qbase = 0; p.out_len = 0;
+    p.lens = a.lengths; p.n = a.n; p.row = a.n + 2L * a.pad; p.pad = a.pad;
+    const int wn = stft_backward_wave_cols(pl.col_tiles);
+    dim3 grid((unsigned)((nf - 1 + pl.overlap + kStftTile - 1) / kStftTile), (unsigned)((pl.col_tiles + wn - 1) / wn), (unsigned)a.B);
+    if (wn == 8) hipLaunchKernelGGL((stft_synthesis_kernel<8, true>), grid, dim3(512), 0, s, p);
+    else if (wn == 4) hipLaunchKernelGGL((stft_synthesis_kernel<4, true>), grid, dim3(256), 0, s, p);
+    else if (wn == 2) hipLaunchKernelGGL((stft_synthesis_kernel<2, true>), grid, dim3(128), 0, s, p);
+    else hipLaunchKernelGGL((stft_synthesis_kernel<1, true>), grid, dim3(64), 0, s, p);
+    T2_LAUNCH_CHECK();
+    StftFold f{a.dxpad, a.dx, a.lengths, a.n, p.row, a.N, a.hop, a.pad};
+    hipLaunchKernelGGL(stft_fold_kernel, dim3((unsigned)((a.n + 255) / 256), (unsigned)a.B), dim3(256), 0, s, f);
     T2_LAUNCH_CHECK();
     return 0;
 }

@@ -95,42 +95,87 @@ def pack_tables(forward_basis, inverse_basis, window_sq, filter_length, hop_leng
     return packed
 
 
-def analysis(x, packed, filter_length, hop_length, want=("re", "im"), lengths=None):
+class _AnalysisFn(torch.autograd.Function):
+    """`analysis` for want within (re, im) with a backward: csrc/stft.hip's overlap-add GEMM with the forward basis and the
+    fold of the reflect padding (t2_stft_analysis_backward).  Saves the lengths only: the gradient does not depend on x."""
+
+    @staticmethod
+    def forward(ctx, x, launch, grad_packed, lengths, cfg):
+        ctx.cfg = cfg
+        ctx.save_for_backward(grad_packed, lengths)
+        return launch()
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, *grads):
+        from . import _lib as L
+        N, hop, want, B, n, fwd_floats = ctx.cfg
+        packed, lengths = ctx.saved_tensors
+        dev = packed.device
+        g = {k: (None if v is None else v.contiguous()) for k, v in zip(want, grads)}
+        with torch.cuda.device(dev):
+            dx = torch.empty(B, n, device=dev, dtype=torch.float32)
+            if g.get("re") is None and g.get("im") is None:
+                return (dx.zero_(),) + (None,) * 4
+            dxpad = torch.empty(B * (n + N), device=dev, dtype=torch.float32)
+            a = L.StftAnalysisBackwardArgs(B, N, hop, n, L.ptr(g.get("re")), L.ptr(g.get("im")), packed.data_ptr() + 4 * fwd_floats,
+                                           L.ptr(lengths), L.ptr(dxpad), L.ptr(dx))
+            L.check(L.lib().t2_stft_analysis_backward(a, L.stream()))
+        return (dx,) + (None,) * 4
+
+
+def analysis(x, packed, filter_length, hop_length, want=("re", "im"), lengths=None, differentiable=False, grad_packed=None):
     """x [B, n] fp32 on the GPU -> the tensors named in `want` (of "re", "im", "mag", "phase"), [B, N/2+1, 1 + n//hop]
     each, from one launch of the analysis kernel; the reflect padding is the kernel's index arithmetic.
     lengths: per-item sample counts in the convention of `log_mel` (Python ints, checked here, or an int32 device tensor [B],
     clamped to [0, n] by the kernel, no host sync).  Item b is then x[b, :lengths[b]] alone, bit for bit: its own reflection,
     1 + lengths[b]//hop frames, zeros behind them; what the row holds behind its length is never read.  The int32 device
     tensor of those frame counts is returned after the tensors of `want`.  An item of <= N/2 samples raises in torch's
-    reflect-pad words when given as a Python int; in a device tensor it has no frames: all zero, count 0."""
+    reflect-pad words when given as a Python int; in a device tensor it has no frames: all zero, count 0.
+    differentiable=True (opt-in): an x that requires grad under grad mode gives re / im with a grad_fn (once differentiable,
+    no gradient for the bases); grad_packed is then `pack_tables` of (forward_basis, forward_basis, None), whose synthesis-order
+    part is the backward's table (STFT.grad_tables()).  "mag" and "phase" have no backward."""
     from . import _lib as L
     if x.dim() != 2 or x.dtype != torch.float32:
         raise RuntimeError(f"stft analysis: expected a float32 signal [B, n], got {x.dtype} {tuple(x.shape)}")
-    if torch.is_grad_enabled() and x.requires_grad:
+    track = torch.is_grad_enabled() and x.requires_grad
+    if track and not differentiable:
         raise RuntimeError("stft analysis is inference only: the input requires grad and grad mode is on")
+    if differentiable:
+        for k in want:
+            if k not in ("re", "im"):
+                raise RuntimeError(f'stft analysis: differentiable=True has no backward for "{k}": only "re" and "im" are differentiable')
+        if grad_packed is None:
+            raise RuntimeError("stft analysis: differentiable=True needs grad_packed (STFT.grad_tables())")
     B, n = x.shape
     half = filter_length // 2
     if n <= half:        # torch's own words for F.pad(..., mode="reflect")
         raise RuntimeError(f"Padding size should be less than the corresponding input dimension, but got: padding ({half}, {half}) "
                            f"at dimension 1 of input {list(x.shape)}")
     plan = L.stft_plan(filter_length, hop_length, 1 + n // hop_length)
-    x = x.detach().contiguous()
+    x_in, x = x, x.detach().contiguous()
     if lengths is not None:
         def too_short(i, v):
             return RuntimeError(f"Padding size should be less than the corresponding input dimension, but got: padding ({half}, {half}) "
                                 f"at dimension 1 of item {i} of {v} samples")
         lengths = L.lengths_arg("stft analysis", lengths, B, n, x.device, lo=half + 1, too_short=too_short)
-    with torch.cuda.device(x.device):
-        out = {k: torch.empty(B, plan.bins, 1 + n // hop_length, device=x.device, dtype=torch.float32) for k in want}
-        planes = [L.ptr(out.get(k)) for k in ("re", "im", "mag", "phase")]
-        if lengths is None:
-            a = L.StftAnalysisArgs(B, filter_length, hop_length, n, L.ptr(x), L.ptr(packed), *planes)
-            L.check(L.lib().t2_stft_analysis(a, L.stream()))
-            return tuple(out[k] for k in want)
-        frame_lengths = torch.empty(B, device=x.device, dtype=torch.int32)
-        a = L.StftAnalysisRaggedArgs(B, filter_length, hop_length, n, L.ptr(x), L.ptr(packed), *planes, L.ptr(lengths), L.ptr(frame_lengths))
-        L.check(L.lib().t2_stft_analysis_ragged(a, L.stream()))
-    return tuple(out[k] for k in want) + (frame_lengths,)
+    box = {}
+
+    def launch():
+        with torch.cuda.device(x.device):
+            out = {k: torch.empty(B, plan.bins, 1 + n // hop_length, device=x.device, dtype=torch.float32) for k in want}
+            planes = [L.ptr(out.get(k)) for k in ("re", "im", "mag", "phase")]
+            if lengths is None:
+                a = L.StftAnalysisArgs(B, filter_length, hop_length, n, L.ptr(x), L.ptr(packed), *planes)
+                L.check(L.lib().t2_stft_analysis(a, L.stream()))
+            else:
+                box["frame_lengths"] = torch.empty(B, device=x.device, dtype=torch.int32)
+                a = L.StftAnalysisRaggedArgs(B, filter_length, hop_length, n, L.ptr(x), L.ptr(packed), *planes, L.ptr(lengths), L.ptr(box["frame_lengths"]))
+                L.check(L.lib().t2_stft_analysis_ragged(a, L.stream()))
+        return tuple(out[k] for k in want)
+
+    res = _AnalysisFn.apply(x_in, launch, grad_packed, lengths, (filter_length, hop_length, tuple(want), B, n, plan.fwd_floats)) if track else launch()
+    return tuple(res) if lengths is None else tuple(res) + (box["frame_lengths"],)
 
 
 def synthesis(a, b, packed, filter_length, hop_length, mode=0, bias=None, strength=0.0, windowed=True, lengths=None):
@@ -189,8 +234,56 @@ def pack_mel_tables(forward_basis, mel_basis, filter_length):
     return packed
 
 
+def pack_mel_grad_tables(forward_basis, mel_basis, filter_length, hop_length):
+    """The backward's tables (t2_melspec_grad_pack): the mel basis in the transposed product's order, then the forward basis in
+    the synthesis kernel's order.  Arguments as `pack_mel_tables`."""
+    from . import _lib as L
+    n_mels = int(mel_basis.shape[0])
+    plan = L.melspec_grad_plan(filter_length, hop_length, filter_length // 2, n_mels, filter_length)
+    dev = forward_basis.device
+    with torch.cuda.device(dev):
+        packed = torch.empty(plan.packed_bytes // 4, device=dev, dtype=torch.float32)
+        L.check(L.lib().t2_melspec_grad_pack(filter_length, hop_length, n_mels, L.ptr(forward_basis.detach().contiguous()),
+                                             L.ptr(mel_basis.detach().contiguous()), L.ptr(packed), L.stream()))
+    return packed
+
+
+class _LogMelFn(torch.autograd.Function):
+    """`log_mel` with a backward (csrc/melspec.hip melspec_grad_kernel, csrc/stft.hip stft_analysis_backward).  Keeps x, the
+    lengths and the mel sum s; re and im are recomputed.  Once differentiable; no gradient for the bases."""
+
+    @staticmethod
+    def forward(ctx, x, launch, cfg, box):
+        xc, lengths, mel, frame_lengths, s = launch()
+        box["frame_lengths"] = frame_lengths
+        ctx.cfg = cfg
+        ctx.save_for_backward(xc, lengths, s)
+        return mel
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        from . import _lib as L
+        stft_module, mel_basis, pad, mag_eps, clip_val, time_major = ctx.cfg
+        x, lengths, s = ctx.saved_tensors
+        N, hop = stft_module.filter_length, stft_module.hop_length
+        B, n = x.shape
+        n_mels = int(mel_basis.shape[0])
+        plan = L.melspec_grad_plan(N, hop, pad, n_mels, n, B)
+        dev = x.device
+        with torch.cuda.device(dev):
+            g = g.contiguous()
+            ws = torch.empty(plan.workspace_floats, device=dev, dtype=torch.float32)
+            dx = torch.empty_like(x)
+            a = L.MelspecBackwardArgs(B, N, hop, pad, n_mels, n, L.ptr(x), L.ptr(lengths), L.ptr(stft_module.mel_tables(mel_basis)),
+                                      L.ptr(stft_module.mel_grad_tables(mel_basis)), L.ptr(s), L.ptr(g), L.ptr(ws), ws.numel(), L.ptr(dx),
+                                      float(mag_eps), float(clip_val), int(bool(time_major)))
+            L.check(L.lib().t2_melspec_backward(a, L.stream()))
+        return dx, None, None, None
+
+
 def log_mel(x, stft_module, mel_basis, lengths=None, pad=None, mag_eps=0.0, clip_val=1e-5, C=1, time_major=False, pad_value=0.0,
-            *, force_splits=0, return_power=False, out=None, scratch=None):
+            *, force_splits=0, return_power=False, out=None, scratch=None, differentiable=False):
     """x [B, n] fp32 on the GPU -> (mel, frame_lengths) from one launch of csrc/melspec.hip:
         mel[b, m, f] = log(max(clip_val, sum_bin mel_basis[m, bin] * sqrt(re^2 + im^2 + mag_eps)) * C)
     over the frames of x[b, :lengths[b]] reflect-padded by `pad` per side.  pad=None is filter_length/2 (TacotronSTFT,
@@ -200,7 +293,11 @@ def log_mel(x, stft_module, mel_basis, lengths=None, pad=None, mag_eps=0.0, clip
     host sync; an item of <= pad samples has no frames), or Python ints, which are checked here: a too-short item raises in
     torch's reflect-pad words.  frame_lengths is an int32 device tensor [B], or None when lengths is.
     The keyword-only arguments are for the tests: force_splits (the launch shape; the bits do not depend on it), return_power
-    (the mel sum over re^2 + im^2 + mag_eps, no clamp and no log), and caller-owned out / scratch buffers."""
+    (the mel sum over re^2 + im^2 + mag_eps, no clamp and no log), and caller-owned out / scratch buffers.
+    differentiable=True (opt-in): an x that requires grad under grad mode gives a mel with a grad_fn, the same bits as
+    without; its backward is HIP as well, once differentiable, with no gradient for the bases and no host
+    synchronisation.  Where the magnitude is exactly 0 the gradient is 0, not torch's NaN; frames at the clip contribute 0.
+    It needs hop_length dividing filter_length with at most 64 overlaps, and refuses return_power, out= and scratch=."""
     from . import _lib as L
     N, hop = stft_module.filter_length, stft_module.hop_length
     pad = N // 2 if pad is None else int(pad)
@@ -208,8 +305,11 @@ def log_mel(x, stft_module, mel_basis, lengths=None, pad=None, mag_eps=0.0, clip
         raise RuntimeError(f"log_mel: expected a float32 signal [B, n], got {getattr(x, 'dtype', type(x))} {tuple(getattr(x, 'shape', ()))}")
     if not x.is_cuda:
         raise RuntimeError("log_mel: the signal must live on the GPU (there is no CPU path; TacotronSTFT.mel_spectrogram keeps the torch formula for CPU tensors)")
-    if torch.is_grad_enabled() and x.requires_grad:
+    track = torch.is_grad_enabled() and x.requires_grad
+    if track and not differentiable:
         raise RuntimeError("log_mel is inference only: the input requires grad and grad mode is on; call it under torch.no_grad() or detach the input")
+    if differentiable and (return_power or out is not None or scratch is not None):
+        raise RuntimeError("log_mel: differentiable=True does not go with return_power, out= or scratch=")
     if stft_module.forward_basis.device != x.device:
         raise RuntimeError(f"log_mel: the input is on {x.device}, the STFT module on {stft_module.forward_basis.device}")
     B, n = x.shape
@@ -222,6 +322,8 @@ def log_mel(x, stft_module, mel_basis, lengths=None, pad=None, mag_eps=0.0, clip
     if n <= pad:
         raise too_short(f"input {list(x.shape)}", n)
     plan = L.melspec_plan(N, hop, pad, n_mels, n, B)
+    if track:
+        L.melspec_grad_plan(N, hop, pad, n_mels, n, B)         # what the backward refuses is refused here, by name
     dev = x.device
     if lengths is not None and not isinstance(lengths, torch.Tensor):
         lengths = [int(v) for v in lengths]
@@ -241,7 +343,25 @@ def log_mel(x, stft_module, mel_basis, lengths=None, pad=None, mag_eps=0.0, clip
         lengths = lengths.contiguous()
     splits = int(force_splits) if force_splits else plan.splits
     shape = (B, plan.nf_max, n_mels) if time_major else (B, n_mels, plan.nf_max)
-    x = x.detach().contiguous()
+    xc = x.detach().contiguous()
+
+    def launch(out=out, scratch=scratch):
+        return _log_mel_launch(xc, stft_module, mel_basis, lengths, plan, shape, splits, out, scratch, track,
+                               (B, N, hop, pad, n_mels, n, mag_eps, clip_val, C, pad_value, time_major, return_power, force_splits))
+
+    if track:
+        box = {}
+        mel = _LogMelFn.apply(x, launch, (stft_module, mel_basis, pad, mag_eps, clip_val, time_major), box)
+        return mel, box["frame_lengths"]
+    _, _, out, frame_lengths, _ = launch()
+    return out, frame_lengths
+
+
+def _log_mel_launch(x, stft_module, mel_basis, lengths, plan, shape, splits, out, scratch, keep_sum, cfg):
+    """The launch of `log_mel`: -> (x, lengths, out, frame_lengths, mel_sum); mel_sum [B, nf_max, n_mels] only with keep_sum."""
+    from . import _lib as L
+    B, N, hop, pad, n_mels, n, mag_eps, clip_val, C, pad_value, time_major, return_power, force_splits = cfg
+    dev = x.device
     with torch.cuda.device(dev):
         if out is None:
             out = torch.empty(shape, device=dev, dtype=torch.float32)
@@ -252,11 +372,13 @@ def log_mel(x, stft_module, mel_basis, lengths=None, pad=None, mag_eps=0.0, clip
         if scratch is not None and (scratch.dtype != torch.float32 or scratch.device != dev):
             raise RuntimeError(f"log_mel: scratch must be float32 on {dev}, got {scratch.dtype} on {scratch.device}")
         frame_lengths = None if lengths is None else torch.empty(B, device=dev, dtype=torch.int32)
+        mel_sum = torch.empty(B, plan.nf_max, n_mels, device=dev, dtype=torch.float32) if keep_sum else None
         a = L.MelspecArgs(B, N, hop, pad, n_mels, n, L.ptr(x), L.ptr(lengths), L.ptr(stft_module.mel_tables(mel_basis)), L.ptr(out),
                           L.ptr(scratch), 0 if scratch is None else scratch.numel(), L.ptr(frame_lengths),
-                          float(mag_eps), float(clip_val), float(C), float(pad_value), int(bool(time_major)), int(bool(return_power)), int(force_splits))
+                          float(mag_eps), float(clip_val), float(C), float(pad_value), int(bool(time_major)), int(bool(return_power)), int(force_splits),
+                          L.ptr(mel_sum))
         L.check(L.lib().t2_melspec(a, L.stream()))
-    return out, frame_lengths
+    return x, lengths, out, frame_lengths, mel_sum
 
 
 class STFT(torch.nn.Module):
@@ -281,11 +403,18 @@ class STFT(torch.nn.Module):
         self._mel_packed = None
         self._mel_basis = None
         self._mel_key = None
+        self._mel_grad_packed = None
+        self._mel_grad_basis = None
+        self._mel_grad_key = None
+        self._grad_packed = None
+        self._grad_key = None
 
     def _apply(self, fn, *args, **kwargs):                                  # .to() / .cuda(): the packed tables follow the buffers
         out = super()._apply(fn, *args, **kwargs)
         self._packed = None
         self._mel_packed = None
+        self._mel_grad_packed = None
+        self._grad_packed = None
         return out
 
     def _key(self):
@@ -320,6 +449,28 @@ class STFT(torch.nn.Module):
             self._mel_packed = pack_mel_tables(self.forward_basis[:, 0, :], mel_basis, self.filter_length)
             self._mel_basis, self._mel_key = mel_basis, key
         return self._mel_packed
+
+    def mel_grad_tables(self, mel_basis):
+        """The log-mel backward's packed tables, kept like `mel_tables`."""
+        if not self.forward_basis.is_cuda:
+            raise RuntimeError("STFT: the buffers must live on the GPU for the HIP kernels (module.cuda())")
+        key = (self.forward_basis.data_ptr(), self.forward_basis._version, mel_basis._version)
+        if self._mel_grad_packed is None or self._mel_grad_basis is not mel_basis or self._mel_grad_key != key:
+            self._mel_grad_packed = pack_mel_grad_tables(self.forward_basis[:, 0, :], mel_basis, self.filter_length, self.hop_length)
+            self._mel_grad_basis, self._mel_grad_key = mel_basis, key
+        return self._mel_grad_packed
+
+    def grad_tables(self):
+        """What `analysis(..., differentiable=True)` takes as grad_packed: `pack_tables` with the forward basis in the inverse
+        basis' place, so that its synthesis-order part drives the backward's overlap-add."""
+        if not self.forward_basis.is_cuda:
+            raise RuntimeError("STFT: the buffers must live on the GPU for the HIP kernels (module.cuda())")
+        key = (self.forward_basis.data_ptr(), self.forward_basis._version)
+        if self._grad_packed is None or self._grad_key != key:
+            fwd = self.forward_basis[:, 0, :]
+            self._grad_packed = pack_tables(fwd, fwd, None, self.filter_length, self.hop_length)
+            self._grad_key = key
+        return self._grad_packed
 
     def transform(self, input_data):
         B, n = input_data.shape
@@ -375,6 +526,13 @@ class TacotronSTFT(torch.nn.Module):
         self.n_mel_channels, self.sampling_rate = n_mel_channels, sampling_rate
         self.stft_fn = STFT(filter_length, hop_length, win_length)
         self.register_buffer("mel_basis", torch.from_numpy(mel_filterbank(sampling_rate, filter_length, n_mel_channels, mel_fmin, mel_fmax)).float())
+        self._differentiable = False
+
+    def differentiable(self, flag=True):
+        """Opt in to a backward from the mel to the waveform on the GPU (`log_mel(..., differentiable=True)`); returns self,
+        like WaveGlow.trainable()."""
+        self._differentiable = bool(flag)
+        return self
 
     def spectral_normalize(self, magnitudes):
         return dynamic_range_compression(magnitudes)
@@ -390,7 +548,7 @@ class TacotronSTFT(torch.nn.Module):
         assert torch.min(y.data) >= -1
         assert torch.max(y.data) <= 1
         if y.is_cuda:
-            mel, frame_lengths = log_mel(y, self.stft_fn, self.mel_basis, lengths=lengths, time_major=time_major)
+            mel, frame_lengths = log_mel(y, self.stft_fn, self.mel_basis, lengths=lengths, time_major=time_major, differentiable=self._differentiable)
             return mel if lengths is None else (mel, frame_lengths)
         if lengths is not None:
             raise RuntimeError("TacotronSTFT.mel_spectrogram: per-item lengths need the HIP kernel (CUDA tensors)")

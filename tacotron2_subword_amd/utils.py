@@ -97,6 +97,41 @@ def spectral_de_normalize_torch(magnitudes):
 _mel_front = {}     # (n_fft, num_mels, sampling_rate, hop_size, win_size, fmin, fmax, device) -> (STFT module, mel basis)
 
 
+def _front(n_fft, num_mels, sampling_rate, hop_size, win_size, fmin, fmax, device):
+    key = (n_fft, num_mels, sampling_rate, hop_size, win_size, fmin, fmax, str(device))
+    if key not in _mel_front:
+        from .stft import STFT, mel_filterbank             # lazy: scipy.signal
+        basis = torch.from_numpy(mel_filterbank(sampling_rate, n_fft, num_mels, fmin, fmax)).float().to(device)
+        _mel_front[key] = ((STFT(n_fft, hop_size, win_size).to(device) if device.type == "cuda" else None), basis)
+    return _mel_front[key]
+
+
+def mel_spectrogram_from_audio(y, n_fft=1024, num_mels=80, sampling_rate=22050, hop_size=256, win_size=1024, fmin=0.0, fmax=8000.0,
+                               lengths=None, differentiable=False):
+    """The tensor-in form of `mel_spectrogram` (utils.py:73-79, HiFi-GAN's meldataset convention): y [B, T] float32 in
+    [-1, 1] -> log-mel [B, num_mels, frames], or (mel, frame_lengths) with per-item `lengths` (see stft.log_mel).  No file, no
+    normalisation.  On the GPU it is one launch of the log-mel kernel, and with differentiable=True a y that requires grad gets
+    its gradient from the HIP backward: the spectral term 45 * L1(mel(y), mel(y_hat)) of a vocoder recipe is
+        F.l1_loss(mel_spectrogram_from_audio(y_hat, differentiable=True), mel_spectrogram_from_audio(y)) * 45
+    On the CPU it is the torch.stft formula (lengths are then refused)."""
+    if y.dim() != 2:
+        raise RuntimeError(f"mel_spectrogram_from_audio: expected audio [B, T], got {tuple(y.shape)}")
+    device = y.device
+    pad = int((n_fft - hop_size) / 2)
+    front, basis = _front(n_fft, num_mels, sampling_rate, hop_size, win_size, fmin, fmax, device)
+    if device.type == "cuda":
+        from .stft import log_mel
+        mel, frame_lengths = log_mel(y, front, basis, lengths=lengths, pad=pad, mag_eps=1e-9, differentiable=differentiable)
+        return mel if lengths is None else (mel, frame_lengths)
+    if lengths is not None:
+        raise RuntimeError("mel_spectrogram_from_audio: per-item lengths need the HIP kernel (CUDA tensors)")
+    y = torch.nn.functional.pad(y.unsqueeze(1), (pad, pad), mode="reflect").squeeze(1)
+    spec = torch.stft(y, n_fft, hop_length=hop_size, win_length=win_size, window=torch.hann_window(win_size), center=False,
+                      pad_mode="reflect", normalized=False, onesided=True, return_complex=True)
+    spec = torch.sqrt(spec.real.pow(2) + spec.imag.pow(2) + 1e-9)
+    return spectral_normalize_torch(torch.matmul(basis, spec))
+
+
 def mel_spectrogram(filename, n_fft=1024, num_mels=80, sampling_rate=22050, hop_size=256, win_size=1024, fmin=0.0, fmax=8000.0,
                     center=False, stftTaco=False, stftCUDA=False, device=None):
     """utils.py:55-80, the HiFi-GAN convention: wav / 32768, peak-normalised to 0.95 (librosa.util.normalize restated as
@@ -119,12 +154,7 @@ def mel_spectrogram(filename, n_fft=1024, num_mels=80, sampling_rate=22050, hop_
     if device.type == "cuda" and device.index is None:
         device = torch.device("cuda", torch.cuda.current_device())
     pad = int((n_fft - hop_size) / 2)
-    key = (n_fft, num_mels, sampling_rate, hop_size, win_size, fmin, fmax, str(device))
-    if key not in _mel_front:
-        from .stft import STFT, mel_filterbank             # lazy: scipy.signal
-        basis = torch.from_numpy(mel_filterbank(sampling_rate, n_fft, num_mels, fmin, fmax)).float().to(device)
-        _mel_front[key] = ((STFT(n_fft, hop_size, win_size).to(device) if device.type == "cuda" else None), basis)
-    front, basis = _mel_front[key]
+    front, basis = _front(n_fft, num_mels, sampling_rate, hop_size, win_size, fmin, fmax, device)
     if device.type == "cuda":
         if center:
             raise NotImplementedError("mel_spectrogram: center=True pads twice (the reference never passes it); the log-mel kernel takes one reflect "
