@@ -164,6 +164,7 @@ class GemmPlanInfo(C.Structure):
 
 CHAIN_PARTS = 11       # T2_CHAIN_PARTS
 CHAIN_KINDS = dict(lstm=0, sma=1, lsa=2, enc=3)
+CHAIN_REFUSE_SHAPE, CHAIN_REFUSE_NO_SAVED_TILES = 1, 10      # T2_CHAIN_REFUSE_*: the reasons the tests ask for by value
 
 
 class ChainShape(C.Structure):
@@ -516,14 +517,22 @@ class WaveglowUpsampleBackwardArgs(C.Structure):
                 ("mel", C.c_void_p), ("d_spect", C.c_void_p), ("dw", C.c_void_p), ("db", C.c_void_p)]
 
 
+class AdamTensor(C.Structure):       # one row of the optimizer's device table (optim.py writes them)
+    _fields_ = [("p", C.c_void_p), ("g", C.c_void_p), ("m", C.c_void_p), ("v", C.c_void_p), ("numel", C.c_long),
+                ("first_chunk", C.c_int), ("pad_", C.c_int)]
+
+
 WAVEGLOW_KERNELS = ("upsample", "start", "gated_conv", "res_skip", "couple")      # include/t2amd.h T2_WAVEGLOW_KERNELS
 WAVEGLOW_FORWARD_KERNELS = ("upsample", "start", "gated_conv", "res_skip", "head", "tail", "sums")      # T2_WAVEGLOW_FORWARD_KERNELS
 WAVEGLOW_BACKWARD_KERNELS = ("tail_backward", "gate_backward", "conv_backward", "cond_backward", "weight_grad", "weight_grad_reduce", "start_backward",
                              "upsample_backward")      # T2_WAVEGLOW_BACKWARD_KERNELS
 WAVEGLOW_GATED, WAVEGLOW_RES_SKIP, WAVEGLOW_UPSAMPLE = 0, 1, 2                      # kinds of t2_waveglow_packed_floats
 
-# every symbol include/t2amd.h declares (tests/test_abi.py checks the library exports them all)
-ABI_VERSION = 4      # include/t2amd.h T2_ABI_VERSION: struct sizes below match that header and nothing else
+# include/t2amd.h T2_ABI_VERSION.  tests/test_abi.py compiles the header and holds every struct above (size, field offsets,
+# field count), every mirrored constant and every prototype below against it, and checks that the library exports each symbol.
+ABI_VERSION = 4
+
+# every symbol include/t2amd.h declares
 
 EXPORTS = ["t2_last_error", "t2_version", "t2_chain_status", "t2_chain_status_clear", "t2_debug_report_abort", "t2_debug_occupy", "t2_chain_claimed", "t2_set_precision", "t2_get_precision", "t2_gemm_counts", "t2_set_gemm_split_min_mflop", "t2_set_split_steps", "t2_get_split_steps", "t2_step_counts", "t2_set_overlap", "t2_set_chain", "t2_get_chain", "t2_set_chain_bwd", "t2_set_gemm_staging", "t2_set_gemm_fold", "t2_set_bn_fuse", "t2_get_bn_fuse", "t2_bn_fuse_counts", "t2_side_join", "t2_defer_counts", "t2_decoder_layout_query", "t2_decoder_forward", "t2_decoder_infer",
            "t2_decoder_bwd_layout_query", "t2_decoder_backward", "t2_decoder_pass_plan", "t2_prof_enable", "t2_prof_collect", "t2_adam_chunks", "t2_adam_step", "t2_adam_norm",
@@ -559,7 +568,14 @@ def lib() -> C.CDLL:
         if L.t2_version() != ABI_VERSION:
             raise RuntimeError(f"{LIB_PATH} speaks ABI version {L.t2_version()}, this binding {ABI_VERSION}: rebuild the library "
                                "(the argument structs differ in size between versions)")
+        # argtypes for every function with a parameter that is not a plain int (an untyped Python int is passed as a C int:
+        # a 64-bit stream handle or pointer would arrive truncated), restype where it is not int
         L.t2_chain_status.argtypes = [C.POINTER(C.c_uint32)]
+        L.t2_side_join.argtypes = [C.c_void_p]
+        L.t2_adam_chunks.argtypes = [C.c_long]
+        L.t2_adam_step.argtypes = [C.POINTER(AdamTensor), C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_float, C.c_float,
+                                   C.c_float, C.c_float, C.c_int, C.c_void_p]
+        L.t2_adam_norm.argtypes = [C.POINTER(AdamTensor), C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p]
         L.t2_debug_report_abort.argtypes = [C.c_uint32, C.c_void_p]
         L.t2_debug_occupy.argtypes = [C.c_int, C.c_int, C.c_void_p]
         L.t2_gemm.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_long, C.c_long, C.c_long,
@@ -686,6 +702,11 @@ def ptr(t: torch.Tensor | None) -> int | None:
 
 def stream() -> int:
     return torch.cuda.current_stream().cuda_stream
+
+
+def adam_table(address: int):
+    """The `table` argument of t2_adam_norm / t2_adam_step: rows of AdamTensor at a device address."""
+    return C.cast(address, C.POINTER(AdamTensor))
 
 
 def lengths_arg(who: str, lengths, B: int, hi: int, dev, lo: int = 0, too_short=None) -> torch.Tensor:

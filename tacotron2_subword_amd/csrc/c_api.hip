@@ -1,5 +1,7 @@
-// C ABI (include/t2amd.h): the thin wrappers over the launchers of kernels.h, and the process-wide host state (error
-// string, profiler, side stream, status block, switches; driver.h) that the decoder drivers in decoder.hip share.
+// C ABI (include/t2amd.h) of the GEMM layer, the conv / BatchNorm layers, the LSTM sequences, the chain plans and the small
+// element-wise calls: thin wrappers over the launchers of kernels.h; and the process-wide host state (error string, profiler,
+// side stream, status block, switches; driver.h) that the decoder drivers in decoder.hip share.  The other families keep
+// their entry points at the end of their own files.
 // No device allocation, no synchronisation except where the header says so.
 #include <fcntl.h>
 #include <stdarg.h>
@@ -9,7 +11,6 @@
 #include <stdlib.h>
 #include <string.h>
 
-#include "../../include/t2amd.h"
 #include "kernels.h"
 #include "chain_plan.h"
 #include "driver.h"
@@ -522,198 +523,6 @@ int t2_mask_btc(float* x, int B, int T, int C, const int32_t* lengths, float fil
     return mask_btc(x, B, T, C, lengths, fill, (hipStream_t)stream);
 }
 
-int t2_softdtw_plan(int B, int N, int M, float gamma, int need_grad, t2_softdtw_plan_info* out) {
-    SoftDtwPlan p;
-    T2_TRY(softdtw_plan(B, N, M, gamma, need_grad, &p));
-    T2_REQUIRE(out, "t2_softdtw_plan: null output");
-    out->threads = p.threads; out->rows_per_thread = p.rows_per_thread; out->passes = p.passes;
-    out->d_floats = p.d_floats; out->r_floats = p.r_floats; out->e_floats = p.e_floats;
-    return 0;
-}
-int t2_softdtw_dist(const t2_softdtw_dist_args* a, void* stream) {
-    T2_REQUIRE(a, "t2_softdtw_dist: null arguments");
-    return softdtw_dist(SoftDtwDist{a->B, a->N, a->M, a->d, a->x, a->y, a->Ds}, (hipStream_t)stream);
-}
-int t2_softdtw_forward(const t2_softdtw_fwd_args* a, void* stream) {
-    T2_REQUIRE(a, "t2_softdtw_forward: null arguments");
-    return softdtw_fwd(SoftDtwArgs{a->B, a->N, a->M, a->gamma, a->bandwidth, a->D, a->Ds, a->x_lengths, a->y_lengths, a->R, a->value, nullptr},
-                       (hipStream_t)stream);
-}
-int t2_softdtw_backward(const t2_softdtw_bwd_args* a, void* stream) {
-    T2_REQUIRE(a, "t2_softdtw_backward: null arguments");
-    return softdtw_bwd(SoftDtwArgs{a->B, a->N, a->M, a->gamma, a->bandwidth, a->D, a->Ds, a->x_lengths, a->y_lengths,
-                                   const_cast<float*>(a->R), nullptr, a->E}, (hipStream_t)stream);
-}
-int t2_softdtw_dist_backward(const t2_softdtw_dist_bwd_args* a, void* stream) {
-    T2_REQUIRE(a, "t2_softdtw_dist_backward: null arguments");
-    return softdtw_dist_bwd(SoftDtwDistBwd{a->B, a->N, a->M, a->d, a->x, a->y, a->E, a->grad_out, a->x_lengths, a->y_lengths, a->dX, a->dY},
-                            (hipStream_t)stream);
-}
-
-int t2_ssim_plan(int N, int H, int W, int ws, int need_grad, t2_ssim_plan_info* out) {
-    SsimPlan p;
-    T2_TRY(ssim_plan(N, H, W, ws, need_grad, &p));
-    T2_REQUIRE(out, "t2_ssim_plan: null output");
-    out->tile_h = p.tile_h; out->tile_w = p.tile_w; out->tiles_h = p.tiles_h; out->tiles_w = p.tiles_w;
-    out->partials = p.partials; out->partials_t = p.partials_t; out->partial_bytes = p.partial_bytes; out->map_bytes = p.map_bytes;
-    out->lds_fwd_bytes = p.lds_fwd_bytes; out->lds_bwd_bytes = p.lds_bwd_bytes;
-    return 0;
-}
-static SsimImage ssim_image(const t2_ssim_image& im) { return SsimImage{im.p, im.plane_stride, im.row_stride, im.col_stride}; }
-int t2_ssim_forward(const t2_ssim_fwd_args* a, void* stream) {
-    T2_REQUIRE(a, "t2_ssim_forward: null arguments");
-    return ssim_fwd(SsimFwd{a->B, a->C, a->H, a->W, a->ws, a->need_grad, ssim_image(a->x), ssim_image(a->y), ssim_image(a->map), a->taps,
-                            static_cast<double*>(a->partial), static_cast<double*>(a->coef), a->value, a->items}, (hipStream_t)stream);
-}
-int t2_ssim_backward(const t2_ssim_bwd_args* a, void* stream) {
-    T2_REQUIRE(a, "t2_ssim_backward: null arguments");
-    return ssim_bwd(SsimBwd{a->B, a->C, a->H, a->W, a->ws, a->need_grad, a->per_item, ssim_image(a->x), ssim_image(a->y), ssim_image(a->dx),
-                            ssim_image(a->dy), a->taps, static_cast<const double*>(a->coef), a->grad}, (hipStream_t)stream);
-}
-
-static_assert(sizeof(t2_hifigan_config) == sizeof(HifiganConfig) && T2_HIFIGAN_MAX_UPS == kHifiganMaxUps && T2_HIFIGAN_MAX_KERNELS == kHifiganMaxKernels &&
-              T2_HIFIGAN_MAX_DILATIONS == kHifiganMaxDilations && T2_VOCODER_TIME_TILE == kVocTT, "t2_hifigan_config mirrors HifiganConfig");
-int t2_hifigan_plan(const t2_hifigan_config* cfg, int B, int T, t2_hifigan_plan_info* out) {
-    T2_REQUIRE(cfg && out, "t2_hifigan_plan: null pointer");
-    HifiganPlan p;
-    T2_TRY(hifigan_plan(*reinterpret_cast<const HifiganConfig*>(cfg), B, T, &p));
-    out->out_len = p.out_len; out->workspace_bytes = p.workspace_bytes; out->packed_bytes = p.packed_bytes;
-    out->n_layers = p.n_layers; out->time_tile = kVocTT;
-    return 0;
-}
-int t2_hifigan_pack(const t2_hifigan_config* cfg, const float* const* weights_host, const float* const* biases_host, int n_layers,
-                    float* packed, void* stream) {
-    T2_REQUIRE(cfg, "t2_hifigan_pack: null configuration");
-    return hifigan_pack(*reinterpret_cast<const HifiganConfig*>(cfg), weights_host, biases_host, n_layers, packed, (hipStream_t)stream);
-}
-int t2_hifigan_forward(const t2_hifigan_config* cfg, const t2_hifigan_fwd_args* a, void* stream) {
-    T2_REQUIRE(cfg && a, "t2_hifigan_forward: null pointer");
-    return hifigan_forward(*reinterpret_cast<const HifiganConfig*>(cfg),
-                           HifiganFwd{a->B, a->T, a->n_mel, a->packed, a->mel, a->workspace, a->audio, a->pre_tanh}, (hipStream_t)stream);
-}
-int t2_hifigan_forward_ragged(const t2_hifigan_config* cfg, const t2_hifigan_ragged_args* a, void* stream) {
-    T2_REQUIRE(cfg && a, "t2_hifigan_forward_ragged: null pointer");
-    T2_REQUIRE(a->frames, "t2_hifigan_forward_ragged: null frame counts (t2_hifigan_forward is the call without them)");
-    return hifigan_forward(*reinterpret_cast<const HifiganConfig*>(cfg),
-                           HifiganFwd{a->B, a->T, a->n_mel, a->packed, a->mel, a->workspace, a->audio, a->pre_tanh, a->frames, a->sample_lengths},
-                           (hipStream_t)stream);
-}
-size_t t2_vocoder_packed_floats(int Cin, int Cout, int k, int u) { return voc_packed_floats(Cin, Cout, k, u); }
-static int vocoder_layer(const t2_vocoder_conv_args* a, int u, const int32_t* lengths, void* stream) {
-    T2_REQUIRE(a->w && a->packed_ws, "t2_vocoder: null weights or packing scratch");
-    T2_TRY(voc_pack(a->w, a->packed_ws, a->Cin, a->Cout, a->k, u, (hipStream_t)stream));
-    return voc_conv(VocConv{a->B, a->Cin, a->Cout, (long)a->L, a->k, a->d, u, a->x, a->packed_ws, a->bias, u ? nullptr : a->residual, a->y,
-                            a->slope, u ? 0 : a->accumulate, u ? 1.f : a->scale, lengths, lengths ? a->L : 0, lengths ? 1 : 0}, (hipStream_t)stream);
-}
-int t2_vocoder_conv_ragged(const t2_vocoder_conv_ragged_args* a, void* stream) {
-    T2_REQUIRE(a, "t2_vocoder_conv_ragged: null arguments");
-    T2_REQUIRE(a->lengths, "t2_vocoder_conv_ragged: null lengths (t2_vocoder_conv1d / t2_vocoder_conv_transpose1d are the calls without them)");
-    T2_REQUIRE(a->conv.u >= 0, "t2_vocoder_conv_ragged: stride u=%d must not be negative", a->conv.u);
-    return vocoder_layer(&a->conv, a->conv.u, a->lengths, stream);
-}
-int t2_vocoder_conv1d(const t2_vocoder_conv_args* a, void* stream) {
-    T2_REQUIRE(a, "t2_vocoder_conv1d: null arguments");
-    T2_REQUIRE(a->u == 0, "t2_vocoder_conv1d: stride u=%d given, a Conv1d has none", a->u);
-    return vocoder_layer(a, 0, nullptr, stream);
-}
-int t2_vocoder_conv_transpose1d(const t2_vocoder_conv_args* a, void* stream) {
-    T2_REQUIRE(a, "t2_vocoder_conv_transpose1d: null arguments");
-    T2_REQUIRE(a->u >= 1, "t2_vocoder_conv_transpose1d: stride u=%d must be positive", a->u);
-    return vocoder_layer(a, a->u, nullptr, stream);
-}
-
-static_assert(T2_STFT_FRAME_TILE == kStftTile, "t2amd.h mirrors the STFT frame tile");
-int t2_stft_plan(int N, int hop, int nf, t2_stft_plan_info* out) {
-    T2_REQUIRE(out, "t2_stft_plan: null pointer");
-    StftPlan p;
-    T2_TRY(stft_plan(N, hop, nf, &p));
-    out->bins = p.cutoff; out->overlap = p.overlap; out->frame_tile = kStftTile; out->bin_tile = 16; out->out_len = p.out_len;
-    out->fwd_floats = p.fwd_floats; out->inv_floats = p.inv_floats; out->wsq_floats = p.wsq_floats;
-    out->packed_bytes = (p.fwd_floats + p.inv_floats + p.wsq_floats) * sizeof(float);
-    return 0;
-}
-int t2_stft_pack(int N, int hop, const float* forward_basis, const float* inverse_basis, const double* window_sq, float* packed, void* stream) {
-    return stft_pack(N, hop, forward_basis, inverse_basis, window_sq, packed, (hipStream_t)stream);
-}
-int t2_stft_analysis(const t2_stft_analysis_args* a, void* stream) {
-    T2_REQUIRE(a, "t2_stft_analysis: null arguments");
-    return stft_analysis(StftAnalysis{a->B, a->N, a->hop, a->n, a->x, a->packed, a->re, a->im, a->mag, a->phase}, (hipStream_t)stream);
-}
-int t2_stft_analysis_ragged(const t2_stft_analysis_ragged_args* a, void* stream) {
-    T2_REQUIRE(a, "t2_stft_analysis_ragged: null arguments");
-    T2_REQUIRE(a->lengths, "t2_stft_analysis_ragged: null lengths (t2_stft_analysis is the call without them)");
-    return stft_analysis(StftAnalysis{a->B, a->N, a->hop, a->n, a->x, a->packed, a->re, a->im, a->mag, a->phase, a->lengths, a->frame_lengths},
-                         (hipStream_t)stream);
-}
-int t2_stft_synthesis_ragged(const t2_stft_synthesis_ragged_args* a, void* stream) {
-    T2_REQUIRE(a, "t2_stft_synthesis_ragged: null arguments");
-    T2_REQUIRE(a->frame_lengths, "t2_stft_synthesis_ragged: null frame counts (t2_stft_synthesis is the call without them)");
-    return stft_synthesis(StftSynthesis{a->B, a->N, a->hop, a->nf, a->mode, a->windowed, a->a, a->b, a->bias, a->strength, a->packed, a->y,
-                                        a->frame_lengths, a->sample_lengths}, (hipStream_t)stream);
-}
-int t2_stft_synthesis(const t2_stft_synthesis_args* a, void* stream) {
-    T2_REQUIRE(a, "t2_stft_synthesis: null arguments");
-    return stft_synthesis(StftSynthesis{a->B, a->N, a->hop, a->nf, a->mode, a->windowed, a->a, a->b, a->bias, a->strength, a->packed, a->y}, (hipStream_t)stream);
-}
-
-int t2_melspec_plan(int N, int hop, int pad, int n_mels, long n, int B, t2_melspec_plan_info* out) {
-    T2_REQUIRE(out, "t2_melspec_plan: null pointer");
-    MelPlan p;
-    T2_TRY(melspec_plan(N, hop, pad, n_mels, n, B, &p));
-    out->bins = p.cutoff; out->passes = p.passes; out->frame_tile = kStftTile; out->row_tiles = p.row_tiles; out->splits = p.splits;
-    out->nf_max = p.nf_max; out->frame_tiles = p.frame_tiles; out->fwd_floats = p.fwd_floats; out->mel_floats = p.mel_floats;
-    out->packed_bytes = (p.fwd_floats + p.mel_floats) * sizeof(float);
-    out->scratch_floats = p.splits > 1 ? p.split_scratch_floats : 0; out->split_scratch_floats = p.split_scratch_floats;
-    return 0;
-}
-int t2_melspec_pack(int N, int n_mels, const float* forward_basis, const float* mel_basis, float* packed, void* stream) {
-    return melspec_pack(N, n_mels, forward_basis, mel_basis, packed, (hipStream_t)stream);
-}
-int t2_melspec(const t2_melspec_args* a, void* stream) {
-    T2_REQUIRE(a, "t2_melspec: null arguments");
-    return melspec(MelSpecArgs{a->B, a->N, a->hop, a->pad, a->n_mels, a->n, a->x, a->lengths, a->packed, a->out, a->scratch, a->scratch_floats, a->frame_lengths,
-                               a->mag_eps, a->clip_val, a->C, a->pad_value, a->time_major, a->return_power, a->force_splits, a->mel_sum}, (hipStream_t)stream);
-}
-int t2_melspec_grad_plan(int N, int hop, int pad, int n_mels, long n, int B, t2_melspec_grad_plan_info* out) {
-    T2_REQUIRE(out, "t2_melspec_grad_plan: null pointer");
-    MelGradPlan p;
-    T2_TRY(melspec_grad_plan(N, hop, pad, n_mels, n, B, &p));
-    out->bins = p.cutoff; out->passes = p.passes; out->row_tiles = p.row_tiles; out->overlap = p.overlap; out->nf_max = p.nf_max;
-    out->grid_x = p.frame_tiles; out->grid_y = p.passes; out->grid_z = B;
-    out->fold_grid_x = p.q_tiles; out->fold_grid_y = (p.col_tiles + p.wave_cols - 1) / p.wave_cols;
-    out->melt_floats = p.melt_floats; out->basis_floats = p.basis_floats; out->packed_bytes = (p.melt_floats + p.basis_floats) * sizeof(float);
-    out->dz_floats = p.dz_floats; out->dxpad_floats = p.dxpad_floats; out->workspace_floats = p.dz_floats + p.dxpad_floats;
-    return 0;
-}
-int t2_melspec_grad_pack(int N, int hop, int n_mels, const float* forward_basis, const float* mel_basis, float* packed, void* stream) {
-    return melspec_grad_pack(N, hop, n_mels, forward_basis, mel_basis, packed, (hipStream_t)stream);
-}
-int t2_melspec_backward(const t2_melspec_backward_args* a, void* stream) {
-    T2_REQUIRE(a, "t2_melspec_backward: null arguments");
-    return melspec_backward(MelSpecBwd{a->B, a->N, a->hop, a->pad, a->n_mels, a->n, a->x, a->lengths, a->packed, a->grad_packed, a->mel_sum, a->g,
-                                       a->workspace, a->workspace_floats, a->dx, a->mag_eps, a->clip_val, a->g_time_major}, (hipStream_t)stream);
-}
-int t2_stft_analysis_backward(const t2_stft_analysis_backward_args* a, void* stream) {
-    T2_REQUIRE(a, "t2_stft_analysis_backward: null arguments");
-    return stft_analysis_backward(StftAnalysisBwd{a->B, a->N, a->hop, a->N / 2, a->n, a->d_re, a->d_im, a->basis_table, a->lengths, a->dxpad, a->dx}, (hipStream_t)stream);
-}
-
-int t2_silence_plan(int sample_rate, int chunk_ms, double threshold_db, long n, int B, t2_silence_plan_info* out) {
-    T2_REQUIRE(out, "t2_silence_plan: null pointer");
-    SilPlan p;
-    T2_TRY(silence_plan(sample_rate, chunk_ms, threshold_db, n, B, &p));
-    out->R = p.R; out->len_ms = p.len_ms; out->chunks = p.chunks; out->chunks_per_group = kSilChunksPerGroup;
-    out->scan_grid[0] = p.R == kSilNoneSilent ? 0 : p.groups; out->scan_grid[1] = B; out->scan_grid[2] = 2;
-    out->cut_grid[0] = (int)((p.out_width + 3 + kSilCutSpan - 1) / kSilCutSpan); out->cut_grid[1] = B;
-    out->block = 256; out->out_width = p.out_width; out->scratch_bytes = p.scratch_bytes;
-    return 0;
-}
-int t2_silence_trim(const t2_silence_args* a, void* stream) {
-    T2_REQUIRE(a, "t2_silence_trim: null arguments");
-    return silence_trim(SilenceArgs{a->B, a->n, a->sample_rate, a->chunk_ms, a->threshold_db, a->x, a->x_float, a->lengths, a->out, a->out_float, a->scale,
-                                    a->new_lengths, a->start_ms, a->end_ms, a->scratch, a->scratch_bytes, a->leading_only}, (hipStream_t)stream);
-}
-
 int t2_prof_enable(int max_launches) {
     if (max_launches <= 0) { g_prof.on = false; return 0; }
     const size_t need = (size_t)max_launches * 2;
@@ -742,18 +551,6 @@ int t2_prof_collect(int n_kinds, double* total_ms_host, int* launches_host) {
     }
     g_prof.used = 0;
     return 0;
-}
-
-int t2_adam_chunks(long numel) { return adam_chunks(numel); }
-int t2_adam_step(const t2_adam_tensor* table, int n_tensors, int n_chunks, float* partial, float* norm_out, float max_norm,
-                 float lr, float beta1, float beta2, float eps, float weight_decay, int step, void* stream) {
-    static_assert(sizeof(t2_adam_tensor) == sizeof(AdamTensor), "table row layout");
-    return adam_step(reinterpret_cast<const AdamTensor*>(table), n_tensors, n_chunks, partial, norm_out, max_norm, lr, beta1, beta2, eps,
-                     weight_decay, step, (hipStream_t)stream);
-}
-
-int t2_adam_norm(const t2_adam_tensor* table, int n_tensors, int n_chunks, float* partial, float* norm_out, float max_norm, void* stream) {
-    return adam_norm(reinterpret_cast<const AdamTensor*>(table), n_tensors, n_chunks, partial, norm_out, max_norm, (hipStream_t)stream);
 }
 
 int t2_finalize_bct(const float* in_btc, float* out_bct, int B, int T, int C, const int32_t* lengths, float fill, void* stream) {

@@ -1,7 +1,9 @@
 // Internal launcher interface between the host layer (decoder.hip: decoder drivers; c_api.hip: C ABI) and the kernel files.
+// A call that the C ABI carries whole takes its argument struct of include/t2amd.h: there is no second copy of it here.
 // Everything takes raw device pointers and enqueues on the given stream; nothing allocates
 // or synchronises.
 #pragma once
+#include "../../include/t2amd.h"
 #include "common.h"
 
 namespace t2 {
@@ -444,56 +446,6 @@ int conv_bn_bwd(const ConvBnBwd& a, hipStream_t s);
 int embedding_fwd(const long* ids, const float* table, float* out, int rows, int D, hipStream_t s);
 int embedding_bwd(const long* ids, const float* dout, float* dtable, int rows, int D, int vocab, hipStream_t s);
 
-// ------------------------------------------------------------------ soft-DTW (softdtw.hip)
-constexpr int kSoftDtwMaxLen = 8192;             // frames per sequence: 1024 threads x 8 rows
-// The partition of one pair's recurrence, decided on the host (no device needed): `threads` per workgroup (whole waves),
-// each owning rows_per_thread consecutive rows (1, 2, 4 or 8: the smallest that fits N into 1024 threads), `passes` of the
-// skewed wavefront (M + owning threads - 1), and the floats of the internal D / R scratch ([B][passes][threads][rows]) and
-// of E ([B,N,M]); R and E are zero-sized without gradient.
-struct SoftDtwPlan { int threads, rows_per_thread, passes; size_t d_floats, r_floats, e_floats; };
-int softdtw_plan(int B, int N, int M, float gamma, int need_grad, SoftDtwPlan* out);
-struct SoftDtwDist { int B, N, M, d; const float* x; const float* y; float* Ds; };     // x [B,N,d], y [B,M,d] -> Ds (d_floats)
-int softdtw_dist(const SoftDtwDist& a, hipStream_t s);
-// forward: value[b] = R[n_b, m_b]; R != null stores the whole R (r_floats) for softdtw_bwd.  backward: E [B,N,M] (zeroed
-// here first).  Exactly one of D (caller's row-major [B,N,M]) and Ds (softdtw_dist's output) is given; lengths nullable.
-struct SoftDtwArgs {
-    int B, N, M; float gamma, bandwidth;
-    const float* D; const float* Ds; const int* x_lengths; const int* y_lengths;
-    float* R; float* value; float* E;
-};
-int softdtw_fwd(const SoftDtwArgs& a, hipStream_t s);
-int softdtw_bwd(const SoftDtwArgs& a, hipStream_t s);
-struct SoftDtwDistBwd {
-    int B, N, M, d; const float* x; const float* y; const float* E; const float* grad_out;
-    const int* x_lengths; const int* y_lengths; float* dX; float* dY;
-};
-int softdtw_dist_bwd(const SoftDtwDistBwd& a, hipStream_t s);
-
-// ------------------------------------------------------------------ SSIM (ssim.hip)
-constexpr int kSsimTileH = 16, kSsimTileW = 64;  // outputs per workgroup: 4 waves x 4 rows, a wave across the lane axis
-constexpr int kSsimMaxWs = 31;
-// The tiling of N planes of H x W with W as the lane axis (tiles_h x tiles_w tiles of tile_h x tile_w per plane, one fp64
-// partial per tile and plane), decided on the host.  partials_t is the count when the launcher takes H as the lane axis
-// (x contiguous along H); partial_bytes covers the larger.  map_bytes: the stored fp64 coefficient maps, 3 per pixel for
-// one gradient, 4 for both, 0 without.  need_grad: 0, 1 = dx, 2 = dy, 3 = both.
-struct SsimPlan { int tile_h, tile_w, tiles_h, tiles_w; long partials, partials_t; size_t partial_bytes, map_bytes, lds_fwd_bytes, lds_bwd_bytes; };
-int ssim_plan(long N, long H, long W, int ws, int need_grad, SsimPlan* out);
-struct SsimImage { float* p; long sn, sr, sc; }; // plane, row and column strides in elements
-struct SsimFwd {
-    int B, C, H, W, ws, need_grad;
-    SsimImage x, y, map;                         // map.p nullable: S itself, [N,H,W] through its strides
-    const float* taps;                           // [ws]
-    double* partial; double* coef;               // scratch of the plan; coef nullable iff need_grad == 0
-    float* value; float* items;                  // [1] mean over everything, [B] mean per item; each nullable
-};
-int ssim_fwd(const SsimFwd& a, hipStream_t s);
-struct SsimBwd {
-    int B, C, H, W, ws, need_grad, per_item;     // per_item: grad is [B] and scales item b's mean; else [1] and the whole mean
-    SsimImage x, y, dx, dy;                      // dx.p, dy.p nullable (not both)
-    const float* taps; const double* coef; const float* grad;
-};
-int ssim_bwd(const SsimBwd& a, hipStream_t s);
-
 inline size_t round4(size_t n) { return (n + 3) / 4 * 4; }        // buffer sizes in floats, kept to 16 bytes (several files)
 
 // ------------------------------------------------------------------ slab GEMM of the vocoder and WaveGlow (slab_gemm.h, slab_gemm.hip)
@@ -503,169 +455,33 @@ inline size_t slab_packed_floats(int gates, int rows, int K0, int taps, int K1) 
     return (size_t)((rows + 31) / 32) * (slab_chunks(K0) * taps + slab_chunks(K1)) * gates * 512;
 }
 
-// ------------------------------------------------------------------ HiFi-GAN vocoder (vocoder.hip)
+// ------------------------------------------------------------------ HiFi-GAN vocoder (vocoder.hip; waveglow_kernels.hip)
 constexpr int kVocTT = 128;                      // time positions per workgroup
-constexpr int kVocMaxPad = 60;                   // (k*d - d)/2 at k = 11, d = 12
-constexpr int kHifiganMaxUps = 6, kHifiganMaxKernels = 6, kHifiganMaxDilations = 3;
-// One layer on packed weights.  u == 0: Conv1d, kernel k, dilation d, stride 1, padding (k*d - d)/2, x [B,Cin,L] ->
-// y [B,Cout,L];  y = ((accumulate ? y : 0) + conv(lrelu(x, slope)) + bias + res) * scale, bias and res nullable.
-// u > 0: ConvTranspose1d, kernel k = 2u, stride u, padding (k - u)/2, x [B,Cin,L] -> y [B,Cout,L*u]; no res / accumulate.
-struct VocConv {
-    int B, Cin, Cout; long L; int k, d, u;
-    const float* x; const float* packed; const float* bias; const float* res; float* y;
-    float slope; int accumulate; float scale;
-    // nullable, device: item b's rows hold clamp(frames[b], 0, T) * factor inputs (L = T * factor).  What x, res and (accumulate) y
-    // hold behind that is never read; y behind it is left as it was
-    const int32_t* frames = nullptr; int T = 0, factor = 0;
-};
-size_t voc_packed_floats(int Cin, int Cout, int k, int u);
-int voc_pack(const float* w, float* packed, int Cin, int Cout, int k, int u, hipStream_t s);     // w in torch layout
-int voc_conv(const VocConv& a, hipStream_t s);
-struct HifiganConfig {                           // mirrors t2_hifigan_config
-    int resblock, n_mel, upsample_initial_channel;
-    int num_upsamples, upsample_rates[kHifiganMaxUps], upsample_kernel_sizes[kHifiganMaxUps];
-    int num_kernels, resblock_kernel_sizes[kHifiganMaxKernels];
-    int num_dilations, resblock_dilation_sizes[kHifiganMaxKernels][kHifiganMaxDilations];
-};
-// kind 0 Conv1d, 1 ConvTranspose1d, 2 conv_post; offsets in floats into the packed weights.  Order: conv_pre, ups[i],
-// resblocks[n] (ResBlock1: convs1[m] then convs2[m]; ResBlock2: convs[m]), conv_post: the order of the state dict.
-struct HifiganLayer { int kind, cin, cout, k, d, u; size_t w_off, b_off; };
-struct HifiganPlan { long out_len; size_t buf_floats, workspace_bytes, packed_bytes; int n_layers; };
-int hifigan_layers(const HifiganConfig& c, std::vector<HifiganLayer>* out, size_t* packed_floats);   // validates; no device
-int hifigan_plan(const HifiganConfig& c, int B, int T, HifiganPlan* out);
-int hifigan_pack(const HifiganConfig& c, const float* const* weights, const float* const* biases, int n_layers, float* packed, hipStream_t s);
-// frames (nullable, device [B]): per-item frame counts, clamped to [0, T] in the kernels; item b is then computed as if it were
-// mel[b, :, :frames[b]] alone, audio and pre_tanh are zero behind frames[b] * prod(rates), which sample_lengths (nullable) receives
-struct HifiganFwd {
-    int B, T, n_mel; const float* packed; const float* mel; float* workspace; float* audio; float* pre_tanh;
-    const int32_t* frames = nullptr; int32_t* sample_lengths = nullptr;
-};
-int hifigan_forward(const HifiganConfig& c, const HifiganFwd& a, hipStream_t s);
 
-// ------------------------------------------------------------------ STFT analysis / synthesis (stft.hip)
+// ------------------------------------------------------------------ STFT pieces the log-mel front end shares (stft.hip)
 constexpr int kStftTile = 32;                    // frames (analysis) / hop-blocks q (synthesis) per workgroup
 constexpr int kStftMaxN = 4096;                  // filter_length
 constexpr int kStftMaxOverlap = 64;              // filter_length / hop_length
 // Sizes in floats; the packed buffer is [forward | inverse | window^2 as N doubles].
 struct StftPlan { int cutoff, overlap, bin_tiles, kchunks, col_tiles; long out_len; size_t fwd_floats, inv_floats, wsq_floats; };
 int stft_plan(int N, int hop, int nf, StftPlan* out);   // validates; no device
-// fwd, inv: the windowed bases [2*(N/2+1)][N] (the module's buffers without their middle dimension); wsq: the squared,
-// centre-padded window [N] in fp64, nullable (no window: synthesis must then run with windowed = 0)
-int stft_pack(int N, int hop, const float* fwd, const float* inv, const double* wsq, float* packed, hipStream_t s);
-// x [B, n] -> re, im, mag, phase [B, N/2+1, 1 + n/hop], each nullable
-// lengths (nullable, device [B]): per-item sample counts, clamped to [0, n] in the kernel.  Item b is then x[b, :lengths[b]] alone:
-// its own reflection, 1 + lengths[b]/hop frames (none where lengths[b] <= N/2), zeros in the planes behind them; frame_lengths
-// (nullable) receives the counts
-struct StftAnalysis {
-    int B, N, hop; long n; const float* x; const float* packed; float* re; float* im; float* mag; float* phase;
-    const int32_t* lengths = nullptr; int32_t* frame_lengths = nullptr;
-};
-int stft_analysis(const StftAnalysis& a, hipStream_t s);
-// mode 0 (polar): a = magnitude, b = phase;  mode 1 (denoise): a = re, b = im, bias [N/2+1], strength.  a, b [B, N/2+1, nf] ->
-// y [B, 1, hop*(nf-1)].  windowed = 0 skips the envelope division and the N/hop scale (STFT(window=None), stft.py:117).
-// frame_lengths (nullable, device [B]): per-item frame counts, clamped to [0, nf] in the kernel.  Item b is then its first
-// frame_lengths[b] frames alone; y is zero from hop*(frame_lengths[b]-1) on (from 0 for a count below 1), which sample_lengths
-// (nullable) receives
-struct StftSynthesis {
-    int B, N, hop, nf, mode, windowed; const float* a; const float* b; const float* bias; float strength; const float* packed; float* y;
-    const int32_t* frame_lengths = nullptr; int32_t* sample_lengths = nullptr;
-};
-int stft_synthesis(const StftSynthesis& a, hipStream_t s);
-// the forward part of stft_pack alone (any hop): fwd [2*(N/2+1)][N] -> packed, ((N/2+1 + 15)/16) * ((N + 31)/32) * 1024 floats
+// the forward part of the packed tables alone (any hop): fwd [2*(N/2+1)][N] -> packed, ((N/2+1 + 15)/16) * ((N + 31)/32) * 1024 floats
 int stft_pack_forward(int N, const float* fwd, float* packed, hipStream_t s);
-// the synthesis-order part of stft_pack alone, for whatever basis [2*(N/2+1)][N] it is handed -> packed, inv_floats floats
+// the synthesis-order part alone, for whatever basis [2*(N/2+1)][N] it is handed -> packed, inv_floats floats
 int stft_pack_overlap(int N, int hop, const float* basis, float* packed, hipStream_t s);
-// The analysis' backward with respect to the samples: the synthesis kernel's overlap-add GEMM with the forward basis (table:
-// stft_pack_overlap of it), the planes taken as they are, nothing scaled and nothing trimmed, then the fold of the reflect
-// padding.  d_re, d_im [B][N/2+1][nf_max] (each nullable: zeros), nf_max = (n + 2*pad - N)/hop + 1, read at frames below the
-// item's own count only; lengths (nullable, device [B]): sample counts, clamped to [0, n]; dxpad: B * (n + 2*pad) floats of
-// scratch; dx [B][n], zero from the item's length on
-// Waves (32-column tiles of r < hop) per workgroup of that GEMM, as the synthesis launch chooses them; the plan reports the grid from it.
-// The bits do not depend on it.
-inline int stft_backward_wave_cols(int col_tiles) { return col_tiles >= 8 ? 8 : (col_tiles >= 4 ? 4 : (col_tiles >= 2 ? 2 : 1)); }
-struct StftAnalysisBwd {
-    int B, N, hop, pad; long n; const float* d_re; const float* d_im; const float* table; const int32_t* lengths; float* dxpad; float* dx;
-};
-int stft_analysis_backward(const StftAnalysisBwd& a, hipStream_t s);
-
-// ------------------------------------------------------------------ log-mel front end (melspec.hip)
-constexpr int kMelMaxMels = 128;                 // four waves x 32 mel rows
-constexpr int kMelPassBins = 64;                 // bins whose magnitudes one pass holds in LDS: four waves x 16
-// Measured (profiles/README.md "Log-mel front end"): a frame tile alone on its CU takes 0.30 ms at 1024/513, and every launch
-// of fewer than 3 workgroups per CU ran faster with its passes split, fastest with one pass per workgroup (an uneven split,
-// 7 ranges over 9 passes, was slower than 3 even ones).
-constexpr int kMelSplitBelow = 768;              // frame tiles x B below which every pass gets a workgroup of its own
 // frames of an item of `len` samples: reflect padding needs len > pad, a frame needs len + 2*pad >= N
 __host__ __device__ inline long mel_frames(long len, int N, int hop, int pad) {
     return (len > pad && len + 2L * pad >= N) ? (len + 2L * pad - N) / hop + 1 : 0;
 }
-// Sizes in floats; the packed buffer is [forward (stft_pack's order) | mel].
-struct MelPlan { int cutoff, bin_tiles, kchunks, passes, row_tiles, splits; long nf_max, frame_tiles; size_t fwd_floats, mel_floats, split_scratch_floats; };
-int melspec_plan(int N, int hop, int pad, int n_mels, long n, int B, MelPlan* out);   // validates; no device
-// fwd: the windowed forward basis [2*(N/2+1)][N]; melb [n_mels][N/2+1]
-int melspec_pack(int N, int n_mels, const float* fwd, const float* melb, float* packed, hipStream_t s);
-// x [B, n], lengths [B] int32 nullable -> out [B, n_mels, nf_max] or time-major [B, nf_max, n_mels]; frame_lengths [B] int32 nullable.
-// scratch: split_scratch_floats floats when the launch splits (force_splits > 1, or 0 and the plan's splits > 1).
-struct MelSpecArgs {
-    int B, N, hop, pad, n_mels; long n;
-    const float* x; const int* lengths; const float* packed; float* out; float* scratch; size_t scratch_floats; int* frame_lengths;
-    float mag_eps, clip_val, C, pad_value;
-    int time_major, return_power, force_splits;
-    float* mel_sum = nullptr;                    // [B][nf_max][n_mels], nullable: the mel sum before clamp and log, frames below the item's count only
-};
-int melspec(const MelSpecArgs& a, hipStream_t s);
-
-// The backward of the log-mel front end with respect to the samples.  Two tables beside the forward's: the mel
-// basis in the order the transposed product consumes it, and the forward basis in the synthesis kernel's order.
-// Workspace, in floats: [d_re | d_im : B * bins * nf_max each][dxpad : B * (n + 2*pad)].
-struct MelGradPlan {
-    int cutoff, bin_tiles, kchunks, passes, row_tiles, overlap, col_tiles, wave_cols; long nf_max, frame_tiles, q_tiles;
-    size_t melt_floats, basis_floats, dz_floats, dxpad_floats;
-};
-int melspec_grad_plan(int N, int hop, int pad, int n_mels, long n, int B, MelGradPlan* out);   // validates; no device
-int melspec_grad_pack(int N, int hop, int n_mels, const float* fwd, const float* melb, float* packed, hipStream_t s);
-// g: the gradient with respect to out, in out's layout (g_time_major: [B][nf_max][n_mels]); read at frames below the item's count only
-struct MelSpecBwd {
-    int B, N, hop, pad, n_mels; long n;
-    const float* x; const int* lengths; const float* packed; const float* grad_packed; const float* mel_sum; const float* g;
-    float* workspace; size_t workspace_floats; float* dx;
-    float mag_eps, clip_val;
-    int g_time_major;
-};
-int melspec_backward(const MelSpecBwd& a, hipStream_t s);
-
-// ------------------------------------------------------------------ silence trim (silence.hip)
-constexpr int kSilChunksPerGroup = 8;            // chunks a scan workgroup owns: two per wave
-constexpr int kSilWordStride = 32;               // ints between two first-loud-chunk words: a 128-byte line each
-constexpr int kSilCutSpan = 1024;                // output samples a cut workgroup writes: four per thread
-constexpr int kSilNoneSilent = 0;                // R for a threshold of -inf: S < n * 0 never holds
-constexpr int kSilAllSilent = 32769;             // R for a threshold above 0 dBFS: S <= n * 2^30 < n * 32769^2 always holds
-// len(sound) of N frames: round(1000 * (float(N) / rate)), half to even on the double
-__host__ __device__ inline int sil_len_ms(int N, int rate) { return (int)rint(1000.0 * ((double)N / (double)rate)); }
-// the frame a millisecond maps to: int(ms * r), one double multiply, truncated
-__host__ __device__ inline int sil_frame(int ms, double r) { return (int)((double)ms * r); }
-struct SilPlan { int R, len_ms, chunks, groups; long out_width; size_t scratch_bytes; };
-int silence_plan(int rate, int chunk_ms, double thr, long n, int B, SilPlan* out);   // validates; no device
-// x [B, n] int16 or fp32 (x_float) -> out [B, out_width] int16 or fp32 (out_float: int16 * scale), zero from new_lengths[b] on.
-// lengths [B] int32 nullable.  start_ms / end_ms / new_lengths [B] int32.  leading_only: only start_ms is written (forward scan).
-struct SilenceArgs {
-    int B; long n; int rate, chunk_ms; double thr;
-    const void* x; int x_float; const int* lengths;
-    void* out; int out_float; float scale;
-    int* new_lengths; int* start_ms; int* end_ms;
-    void* scratch; size_t scratch_bytes;
-    int leading_only;
-};
-int silence_trim(const SilenceArgs& a, hipStream_t s);
-
-// ------------------------------------------------------------------ optimizer (optim.hip)
-struct AdamTensor { float* p; const float* g; float* m; float* v; long numel; int first_chunk; int pad_; };   // 48 bytes, mirrors t2_adam_tensor
-int adam_chunks(long numel);
-// norm_out: 4 floats — [0] total norm, [1] clip coefficient, [2] 1 = update skipped (the device's sticky status word was
-// set: an earlier persistent kernel aborted and the gradients are invalid), [3] unused
-int adam_norm(const AdamTensor* table_dev, int n_tensors, int n_chunks, float* partial, float* norm_out, float max_norm, hipStream_t s);
-int adam_step(const AdamTensor* table_dev, int n_tensors, int n_chunks, float* partial, float* norm_out, float max_norm,
-              float lr, float b1, float b2, float eps, float wd, int step, hipStream_t s);
+// Waves (32-column tiles of r < hop) per workgroup of the backward's GEMM, as the synthesis launch chooses them; the plan reports
+// the grid from it.  The bits do not depend on it.
+inline int stft_backward_wave_cols(int col_tiles) { return col_tiles >= 8 ? 8 : (col_tiles >= 4 ? 4 : (col_tiles >= 2 ? 2 : 1)); }
+// The analysis' backward with respect to the samples: the synthesis kernel's overlap-add GEMM with the forward basis (basis_table:
+// stft_pack_overlap of it), the planes taken as they are, nothing scaled and nothing trimmed, then the fold of the reflect
+// padding.  d_re, d_im [B][N/2+1][nf_max] (each nullable: zeros), nf_max = (n + 2*pad - N)/hop + 1, read at frames below the
+// item's own count only; lengths (nullable, device [B]): sample counts, clamped to [0, n]; dxpad: B * (n + 2*pad) floats of
+// scratch; dx [B][n], zero from the item's length on.  pad: the reflect padding per side (the ABI call's is N/2, the log-mel's its own)
+int stft_analysis_backward(const t2_stft_analysis_backward_args& a, int pad, hipStream_t s);
 
 // ------------------------------------------------------------------ elementwise (elementwise.hip)
 int rng_keep_mask(uint64_t seed, uint32_t site, uint32_t n, float p, uint8_t* out, hipStream_t s);

@@ -21,6 +21,22 @@
 
 namespace t2 {
 
+constexpr int kMelMaxMels = 128;                 // four waves x 32 mel rows
+constexpr int kMelPassBins = 64;                 // bins whose magnitudes one pass holds in LDS: four waves x 16
+// Measured (profiles/README.md "Log-mel front end"): a frame tile alone on its CU takes 0.30 ms at 1024/513, and every launch
+// of fewer than 3 workgroups per CU ran faster with its passes split, fastest with one pass per workgroup (an uneven split,
+// 7 ranges over 9 passes, was slower than 3 even ones).
+constexpr int kMelSplitBelow = 768;              // frame tiles x B below which every pass gets a workgroup of its own
+// Sizes in floats; the packed buffer is [forward (stft_pack_forward's order) | mel].
+struct MelPlan { int cutoff, bin_tiles, kchunks, passes, row_tiles, splits; long nf_max, frame_tiles; size_t fwd_floats, mel_floats, split_scratch_floats; };
+// The backward of the log-mel front end with respect to the samples.  Two tables beside the forward's: the mel
+// basis in the order the transposed product consumes it, and the forward basis in the synthesis kernel's order.
+// Workspace, in floats: [d_re | d_im : B * bins * nf_max each][dxpad : B * (n + 2*pad)].
+struct MelGradPlan {
+    int cutoff, bin_tiles, kchunks, passes, row_tiles, overlap, col_tiles, wave_cols; long nf_max, frame_tiles, q_tiles;
+    size_t melt_floats, basis_floats, dz_floats, dxpad_floats;
+};
+
 constexpr int kMelKC = 32;                                    // k per slab, as the analysis kernel
 constexpr int kMelSlabStride = kStftTile + 1;                 // odd: the loader's lanes run along k, one bank each
 constexpr int kMelMagStride = kStftTile + 1;
@@ -240,7 +256,7 @@ __global__ void __launch_bounds__(256) melspec_pack_kernel(const float* __restri
 // ------------------------------------------------------------------------------------------------------------------
 // host
 // ------------------------------------------------------------------------------------------------------------------
-int melspec_plan(int N, int hop, int pad, int n_mels, long n, int B, MelPlan* out) {
+static int melspec_plan(int N, int hop, int pad, int n_mels, long n, int B, MelPlan* out) {   // validates; no device
     T2_REQUIRE(out, "melspec: null plan");
     T2_REQUIRE(N >= 2 && N <= kStftMaxN, "melspec: filter_length=%d outside 2..%d", N, kStftMaxN);
     T2_REQUIRE(N % 2 == 0, "melspec: filter_length=%d is odd: the reflect padding takes N/2 samples per side", N);
@@ -271,7 +287,8 @@ int melspec_plan(int N, int hop, int pad, int n_mels, long n, int B, MelPlan* ou
     return 0;
 }
 
-int melspec_pack(int N, int n_mels, const float* fwd, const float* melb, float* packed, hipStream_t s) {
+// fwd: the windowed forward basis [2*(N/2+1)][N]; melb [n_mels][N/2+1]
+static int melspec_pack(int N, int n_mels, const float* fwd, const float* melb, float* packed, hipStream_t s) {
     MelPlan pl;
     T2_TRY_RC(melspec_plan(N, N, N / 2, n_mels, N, 1, &pl));
     T2_REQUIRE(fwd && melb && packed, "melspec_pack: null pointer");
@@ -282,7 +299,7 @@ int melspec_pack(int N, int n_mels, const float* fwd, const float* melb, float* 
     return 0;
 }
 
-int melspec(const MelSpecArgs& a, hipStream_t s) {
+static int melspec(const t2_melspec_args& a, hipStream_t s) {
     MelPlan pl;
     T2_TRY_RC(melspec_plan(a.N, a.hop, a.pad, a.n_mels, a.n, a.B, &pl));
     T2_REQUIRE(a.x && a.packed && a.out, "melspec: null pointer");
@@ -433,7 +450,7 @@ __global__ void __launch_bounds__(256) melspec_pack_t_kernel(const float* __rest
     out[idx] = (bin < cutoff && m < n_mels) ? melb[(size_t)m * cutoff + bin] : 0.f;
 }
 
-int melspec_grad_plan(int N, int hop, int pad, int n_mels, long n, int B, MelGradPlan* out) {
+static int melspec_grad_plan(int N, int hop, int pad, int n_mels, long n, int B, MelGradPlan* out) {
     T2_REQUIRE(out, "melspec backward: null plan");
     MelPlan f;
     T2_TRY_RC(melspec_plan(N, hop, pad, n_mels, n, B, &f));
@@ -456,7 +473,7 @@ int melspec_grad_plan(int N, int hop, int pad, int n_mels, long n, int B, MelGra
     return 0;
 }
 
-int melspec_grad_pack(int N, int hop, int n_mels, const float* fwd, const float* melb, float* packed, hipStream_t s) {
+static int melspec_grad_pack(int N, int hop, int n_mels, const float* fwd, const float* melb, float* packed, hipStream_t s) {
     MelGradPlan pl;
     T2_TRY_RC(melspec_grad_plan(N, hop, N / 2, n_mels, N, 1, &pl));
     T2_REQUIRE(fwd && melb && packed, "melspec_grad_pack: null pointer");
@@ -466,7 +483,7 @@ int melspec_grad_pack(int N, int hop, int n_mels, const float* fwd, const float*
     return stft_pack_overlap(N, hop, fwd, packed + pl.melt_floats, s);
 }
 
-int melspec_backward(const MelSpecBwd& a, hipStream_t s) {
+static int melspec_backward(const t2_melspec_backward_args& a, hipStream_t s) {
     MelGradPlan pl;
     T2_TRY_RC(melspec_grad_plan(a.N, a.hop, a.pad, a.n_mels, a.n, a.B, &pl));
     T2_REQUIRE(a.x && a.packed && a.grad_packed && a.mel_sum && a.g && a.dx, "melspec backward: null pointer");
@@ -482,7 +499,54 @@ int melspec_backward(const MelSpecBwd& a, hipStream_t s) {
     p.mag_eps = a.mag_eps; p.clip = a.clip_val;
     hipLaunchKernelGGL(melspec_grad_kernel, dim3((unsigned)pl.frame_tiles, (unsigned)pl.passes, (unsigned)a.B), dim3(256), 0, s, p);
     T2_LAUNCH_CHECK();
-    return stft_analysis_backward(StftAnalysisBwd{a.B, a.N, a.hop, a.pad, a.n, p.d_re, p.d_im, a.grad_packed + pl.melt_floats, a.lengths, a.workspace + pl.dz_floats, a.dx}, s);
+    t2_stft_analysis_backward_args f{};
+    f.B = a.B; f.N = a.N; f.hop = a.hop; f.n = a.n;
+    f.d_re = p.d_re; f.d_im = p.d_im; f.basis_table = a.grad_packed + pl.melt_floats; f.lengths = a.lengths;
+    f.dxpad = a.workspace + pl.dz_floats; f.dx = a.dx;
+    return stft_analysis_backward(f, a.pad, s);
 }
 
 }  // namespace t2
+
+// ---- C ABI (include/t2amd.h)
+using namespace t2;
+
+extern "C" {
+
+int t2_melspec_plan(int N, int hop, int pad, int n_mels, long n, int B, t2_melspec_plan_info* out) {
+    T2_REQUIRE(out, "t2_melspec_plan: null pointer");
+    MelPlan p;
+    T2_TRY_RC(melspec_plan(N, hop, pad, n_mels, n, B, &p));
+    out->bins = p.cutoff; out->passes = p.passes; out->frame_tile = kStftTile; out->row_tiles = p.row_tiles; out->splits = p.splits;
+    out->nf_max = p.nf_max; out->frame_tiles = p.frame_tiles; out->fwd_floats = p.fwd_floats; out->mel_floats = p.mel_floats;
+    out->packed_bytes = (p.fwd_floats + p.mel_floats) * sizeof(float);
+    out->scratch_floats = p.splits > 1 ? p.split_scratch_floats : 0; out->split_scratch_floats = p.split_scratch_floats;
+    return 0;
+}
+int t2_melspec_pack(int N, int n_mels, const float* forward_basis, const float* mel_basis, float* packed, void* stream) {
+    return melspec_pack(N, n_mels, forward_basis, mel_basis, packed, (hipStream_t)stream);
+}
+int t2_melspec(const t2_melspec_args* a, void* stream) {
+    T2_REQUIRE(a, "t2_melspec: null arguments");
+    return melspec(*a, (hipStream_t)stream);
+}
+int t2_melspec_grad_plan(int N, int hop, int pad, int n_mels, long n, int B, t2_melspec_grad_plan_info* out) {
+    T2_REQUIRE(out, "t2_melspec_grad_plan: null pointer");
+    MelGradPlan p;
+    T2_TRY_RC(melspec_grad_plan(N, hop, pad, n_mels, n, B, &p));
+    out->bins = p.cutoff; out->passes = p.passes; out->row_tiles = p.row_tiles; out->overlap = p.overlap; out->nf_max = p.nf_max;
+    out->grid_x = p.frame_tiles; out->grid_y = p.passes; out->grid_z = B;
+    out->fold_grid_x = p.q_tiles; out->fold_grid_y = (p.col_tiles + p.wave_cols - 1) / p.wave_cols;
+    out->melt_floats = p.melt_floats; out->basis_floats = p.basis_floats; out->packed_bytes = (p.melt_floats + p.basis_floats) * sizeof(float);
+    out->dz_floats = p.dz_floats; out->dxpad_floats = p.dxpad_floats; out->workspace_floats = p.dz_floats + p.dxpad_floats;
+    return 0;
+}
+int t2_melspec_grad_pack(int N, int hop, int n_mels, const float* forward_basis, const float* mel_basis, float* packed, void* stream) {
+    return melspec_grad_pack(N, hop, n_mels, forward_basis, mel_basis, packed, (hipStream_t)stream);
+}
+int t2_melspec_backward(const t2_melspec_backward_args* a, void* stream) {
+    T2_REQUIRE(a, "t2_melspec_backward: null arguments");
+    return melspec_backward(*a, (hipStream_t)stream);
+}
+
+}  // extern "C"

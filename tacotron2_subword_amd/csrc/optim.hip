@@ -13,7 +13,7 @@ namespace {
 
 constexpr int kChunk = 8192;          // elements per workgroup
 
-__device__ __forceinline__ int find_tensor(const AdamTensor* __restrict__ tab, int n, int chunk) {
+__device__ __forceinline__ int find_tensor(const t2_adam_tensor* __restrict__ tab, int n, int chunk) {
     int lo = 0, hi = n - 1;
     while (lo < hi) {                                  // last row with first_chunk <= chunk
         const int mid = (lo + hi + 1) >> 1;
@@ -22,9 +22,9 @@ __device__ __forceinline__ int find_tensor(const AdamTensor* __restrict__ tab, i
     return lo;
 }
 
-__global__ __launch_bounds__(256) void sumsq_kernel(const AdamTensor* __restrict__ tab, int n, float* __restrict__ partial) {
+__global__ __launch_bounds__(256) void sumsq_kernel(const t2_adam_tensor* __restrict__ tab, int n, float* __restrict__ partial) {
     const int chunk = blockIdx.x;
-    const AdamTensor t = tab[find_tensor(tab, n, chunk)];
+    const t2_adam_tensor t = tab[find_tensor(tab, n, chunk)];
     const long off = (long)(chunk - t.first_chunk) * kChunk;
     const long cnt = min((long)kChunk, t.numel - off);
     const float* g = t.g + off;
@@ -69,10 +69,10 @@ __global__ __launch_bounds__(1024) void norm_finish_kernel(const float* __restri
     }
 }
 
-__global__ __launch_bounds__(256) void adam_kernel(const AdamTensor* __restrict__ tab, int n, const float* __restrict__ coef,
+__global__ __launch_bounds__(256) void adam_kernel(const t2_adam_tensor* __restrict__ tab, int n, const float* __restrict__ coef,
                                                    float lr_over_bc1, float inv_sqrt_bc2, float b1, float b2, float eps, float wd) {
     const int chunk = blockIdx.x + tab[0].first_chunk;       // a sub-table (rows of one step count) starts at its own first chunk
-    const AdamTensor t = tab[find_tensor(tab, n, chunk)];
+    const t2_adam_tensor t = tab[find_tensor(tab, n, chunk)];
     const long off = (long)(chunk - t.first_chunk) * kChunk;
     const long cnt = min((long)kChunk, t.numel - off);
     const float clip = coef ? coef[1] : 1.0f;
@@ -105,9 +105,11 @@ __global__ __launch_bounds__(256) void adam_kernel(const AdamTensor* __restrict_
 
 }  // namespace
 
-int adam_chunks(long numel) { return (int)((numel + kChunk - 1) / kChunk); }
+static int adam_chunks(long numel) { return (int)((numel + kChunk - 1) / kChunk); }
 
-int adam_norm(const AdamTensor* table_dev, int n_tensors, int n_chunks, float* partial, float* norm_out, float max_norm, hipStream_t s) {
+// norm_out: 4 floats — [0] total norm, [1] clip coefficient, [2] 1 = update skipped (the device's sticky status word was
+// set: an earlier persistent kernel aborted and the gradients are invalid), [3] unused
+static int adam_norm(const t2_adam_tensor* table_dev, int n_tensors, int n_chunks, float* partial, float* norm_out, float max_norm, hipStream_t s) {
     T2_REQUIRE(table_dev && n_tensors >= 1 && n_chunks >= 1 && partial && norm_out, "adam_norm: bad arguments");
     hipLaunchKernelGGL(sumsq_kernel, dim3(n_chunks), dim3(256), 0, s, table_dev, n_tensors, partial);
     hipLaunchKernelGGL(norm_finish_kernel, dim3(1), dim3(1024), 0, s, partial, n_chunks, max_norm, norm_out, chain_sticky_words());
@@ -117,8 +119,8 @@ int adam_norm(const AdamTensor* table_dev, int n_tensors, int n_chunks, float* p
 
 // max_norm >= 0: norm + clip coefficient over this table, then the update.  max_norm < 0: update only, with the
 // coefficient adam_norm left in norm_out[1]; the table may then be a run of rows of a larger table (n_chunks = its chunks).
-int adam_step(const AdamTensor* table_dev, int n_tensors, int n_chunks, float* partial, float* norm_out, float max_norm,
-              float lr, float b1, float b2, float eps, float wd, int step, hipStream_t s) {
+static int adam_step(const t2_adam_tensor* table_dev, int n_tensors, int n_chunks, float* partial, float* norm_out, float max_norm,
+                     float lr, float b1, float b2, float eps, float wd, int step, hipStream_t s) {
     T2_REQUIRE(table_dev && n_tensors >= 1 && n_chunks >= 1 && partial && norm_out && step >= 1, "adam_step: bad arguments");
     if (max_norm >= 0.f) T2_TRY_RC(adam_norm(table_dev, n_tensors, n_chunks, partial, norm_out, max_norm, s));
     const double bc1 = 1.0 - pow((double)b1, step), bc2 = 1.0 - pow((double)b2, step);
@@ -129,3 +131,19 @@ int adam_step(const AdamTensor* table_dev, int n_tensors, int n_chunks, float* p
 }
 
 }  // namespace t2
+
+// ---- C ABI (include/t2amd.h)
+using namespace t2;
+
+extern "C" {
+
+int t2_adam_chunks(long numel) { return adam_chunks(numel); }
+int t2_adam_step(const t2_adam_tensor* table, int n_tensors, int n_chunks, float* partial, float* norm_out, float max_norm,
+                 float lr, float beta1, float beta2, float eps, float weight_decay, int step, void* stream) {
+    return adam_step(table, n_tensors, n_chunks, partial, norm_out, max_norm, lr, beta1, beta2, eps, weight_decay, step, (hipStream_t)stream);
+}
+int t2_adam_norm(const t2_adam_tensor* table, int n_tensors, int n_chunks, float* partial, float* norm_out, float max_norm, void* stream) {
+    return adam_norm(table, n_tensors, n_chunks, partial, norm_out, max_norm, (hipStream_t)stream);
+}
+
+}  // extern "C"

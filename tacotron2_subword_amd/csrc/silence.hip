@@ -24,6 +24,17 @@
 
 namespace t2 {
 
+constexpr int kSilChunksPerGroup = 8;            // chunks a scan workgroup owns: two per wave
+constexpr int kSilWordStride = 32;               // ints between two first-loud-chunk words: a 128-byte line each
+constexpr int kSilCutSpan = 1024;                // output samples a cut workgroup writes: four per thread
+constexpr int kSilNoneSilent = 0;                // R for a threshold of -inf: S < n * 0 never holds
+constexpr int kSilAllSilent = 32769;             // R for a threshold above 0 dBFS: S <= n * 2^30 < n * 32769^2 always holds
+// len(sound) of N frames: round(1000 * (float(N) / rate)), half to even on the double
+__host__ __device__ inline int sil_len_ms(int N, int rate) { return (int)rint(1000.0 * ((double)N / (double)rate)); }
+// the frame a millisecond maps to: int(ms * r), one double multiply, truncated
+__host__ __device__ inline int sil_frame(int ms, double r) { return (int)((double)ms * r); }
+struct SilPlan { int R, len_ms, chunks, groups; long out_width; size_t scratch_bytes; };
+
 constexpr int kSilNone = 0x7f7f7f7f;             // "no loud chunk": what hipMemsetAsync(0x7f) leaves, above every chunk index
 
 typedef short s16x8 __attribute__((ext_vector_type(8)));
@@ -224,7 +235,7 @@ static int sil_threshold_rms(double thr) {
     return hi;
 }
 
-int silence_plan(int rate, int chunk_ms, double thr, long n, int B, SilPlan* out) {
+static int silence_plan(int rate, int chunk_ms, double thr, long n, int B, SilPlan* out) {   // validates; no device
     T2_REQUIRE(out, "silence: null plan");
     T2_REQUIRE(rate >= 4000 && rate <= 1000000, "silence: sample_rate=%d outside 4000..1000000", rate);
     T2_REQUIRE(chunk_ms >= 1 && chunk_ms <= 1000000, "silence: chunk_ms=%d outside 1..1000000", chunk_ms);
@@ -250,9 +261,11 @@ static void sil_launch_cut(const SilCut& c, int out_float, dim3 grid, hipStream_
     else hipLaunchKernelGGL((silence_cut_kernel<Tin, short>), grid, dim3(256), 0, s, c);
 }
 
-int silence_trim(const SilenceArgs& a, hipStream_t s) {
+// x [B, n] int16 or fp32 (x_float) -> out [B, out_width] int16 or fp32 (out_float: int16 * scale), zero from new_lengths[b] on.
+// lengths [B] int32 nullable.  start_ms / end_ms / new_lengths [B] int32.  leading_only: only start_ms is written (forward scan).
+static int silence_trim(const t2_silence_args& a, hipStream_t s) {
     SilPlan pl;
-    T2_TRY_RC(silence_plan(a.rate, a.chunk_ms, a.thr, a.n, a.B, &pl));
+    T2_TRY_RC(silence_plan(a.sample_rate, a.chunk_ms, a.threshold_db, a.n, a.B, &pl));
     T2_REQUIRE(a.x || a.n == 0, "silence: null input");
     T2_REQUIRE(a.start_ms, "silence: null start_ms");
     T2_REQUIRE(a.leading_only || (a.out && a.new_lengths && a.end_ms), "silence: null out, new_lengths or end_ms");
@@ -261,14 +274,14 @@ int silence_trim(const SilenceArgs& a, hipStream_t s) {
     T2_REQUIRE(reinterpret_cast<uintptr_t>(a.scratch) % sizeof(int) == 0, "silence: scratch is not aligned to 4 bytes");
     T2_REQUIRE(reinterpret_cast<uintptr_t>(a.x) % (a.x_float ? 4 : 2) == 0, "silence: input is not aligned to its element size");
     T2_REQUIRE(a.leading_only || reinterpret_cast<uintptr_t>(a.out) % (a.out_float ? 4 : 2) == 0, "silence: output is not aligned to its element size");
-    const double r = a.rate / 1000.0;
+    const double r = a.sample_rate / 1000.0;
     int* first = static_cast<int*>(a.scratch);
     if (pl.R != kSilNoneSilent) {
         T2_CHECK_HIP(hipMemsetAsync(first, 0x7f, pl.scratch_bytes, s));
         if (pl.groups > 0) {
             SilScan p;
             p.x = a.x; p.lengths = a.lengths; p.first = first; p.n = a.n; p.r = r; p.R2 = (unsigned long long)pl.R * pl.R;
-            p.B = a.B; p.rate = a.rate; p.chunk_ms = a.chunk_ms;
+            p.B = a.B; p.rate = a.sample_rate; p.chunk_ms = a.chunk_ms;
             const dim3 grid((unsigned)pl.groups, (unsigned)a.B, a.leading_only ? 1u : 2u);
             if (a.x_float) hipLaunchKernelGGL(silence_scan_kernel<float>, grid, dim3(256), 0, s, p);
             else hipLaunchKernelGGL(silence_scan_kernel<short>, grid, dim3(256), 0, s, p);
@@ -279,7 +292,7 @@ int silence_trim(const SilenceArgs& a, hipStream_t s) {
     c.x = a.x; c.lengths = a.lengths; c.first = first; c.out = a.leading_only ? nullptr : a.out;
     c.new_lengths = a.new_lengths; c.start_ms = a.start_ms; c.end_ms = a.end_ms;
     c.n = a.n; c.W = pl.out_width; c.r = r; c.scale = a.scale;
-    c.B = a.B; c.rate = a.rate; c.chunk_ms = a.chunk_ms; c.R = pl.R; c.leading_only = a.leading_only != 0;
+    c.B = a.B; c.rate = a.sample_rate; c.chunk_ms = a.chunk_ms; c.R = pl.R; c.leading_only = a.leading_only != 0;
     const dim3 grid(a.leading_only ? 1u : (unsigned)((pl.out_width + 3 + kSilCutSpan - 1) / kSilCutSpan), (unsigned)a.B);
     if (a.x_float) sil_launch_cut<float>(c, a.out_float, grid, s);
     else sil_launch_cut<short>(c, a.out_float, grid, s);
@@ -288,3 +301,25 @@ int silence_trim(const SilenceArgs& a, hipStream_t s) {
 }
 
 }  // namespace t2
+
+// ---- C ABI (include/t2amd.h)
+using namespace t2;
+
+extern "C" {
+
+int t2_silence_plan(int sample_rate, int chunk_ms, double threshold_db, long n, int B, t2_silence_plan_info* out) {
+    T2_REQUIRE(out, "t2_silence_plan: null pointer");
+    SilPlan p;
+    T2_TRY_RC(silence_plan(sample_rate, chunk_ms, threshold_db, n, B, &p));
+    out->R = p.R; out->len_ms = p.len_ms; out->chunks = p.chunks; out->chunks_per_group = kSilChunksPerGroup;
+    out->scan_grid[0] = p.R == kSilNoneSilent ? 0 : p.groups; out->scan_grid[1] = B; out->scan_grid[2] = 2;
+    out->cut_grid[0] = (int)((p.out_width + 3 + kSilCutSpan - 1) / kSilCutSpan); out->cut_grid[1] = B;
+    out->block = 256; out->out_width = p.out_width; out->scratch_bytes = p.scratch_bytes;
+    return 0;
+}
+int t2_silence_trim(const t2_silence_args* a, void* stream) {
+    T2_REQUIRE(a, "t2_silence_trim: null arguments");
+    return silence_trim(*a, (hipStream_t)stream);
+}
+
+}  // extern "C"

@@ -18,12 +18,15 @@
 
 namespace t2 {
 
+constexpr int kSoftDtwMaxLen = 8192;             // frames per sequence: 1024 threads x 8 rows
+
 constexpr int kSdtwMaxThreads = 1024;
 constexpr int kSdtwMaxRpt = 8;                       // ladder 1, 2, 4, 8: N up to 8192
 constexpr int kSdtwMaxWaves = kSdtwMaxThreads / kWave;
 static_assert(kSdtwMaxThreads * kSdtwMaxRpt == kSoftDtwMaxLen, "the ladder covers exactly the advertised limit");
 
-int softdtw_plan(int B, int N, int M, float gamma, int need_grad, SoftDtwPlan* out) {
+// The partition of one pair's recurrence, decided on the host (no device needed; t2amd.h t2_softdtw_plan_info has the fields)
+static int softdtw_plan(int B, int N, int M, float gamma, int need_grad, t2_softdtw_plan_info* out) {
     T2_REQUIRE(out, "softdtw: null plan");
     T2_REQUIRE(B >= 1, "softdtw: B=%d must be at least 1", B);
     T2_REQUIRE(N >= 1 && M >= 1, "softdtw: N=%d and M=%d must be at least 1", N, M);
@@ -320,10 +323,10 @@ __global__ void __launch_bounds__(256) softdtw_dist_bwd_kernel(const float* __re
 }
 
 // ------------------------------------------------------------------------------------------------------------------
-// host
+// host: every call takes its argument struct of t2amd.h
 // ------------------------------------------------------------------------------------------------------------------
-int softdtw_dist(const SoftDtwDist& a, hipStream_t s) {
-    SoftDtwPlan pl;
+static int softdtw_dist(const t2_softdtw_dist_args& a, hipStream_t s) {
+    t2_softdtw_plan_info pl;
     T2_TRY_RC(softdtw_plan(a.B, a.N, a.M, 1.f, 0, &pl));
     T2_REQUIRE(a.d >= 1, "softdtw: feature dimension d=%d must be at least 1", a.d);
     T2_REQUIRE(a.x && a.y && a.Ds, "softdtw_dist: null pointer");
@@ -335,7 +338,8 @@ int softdtw_dist(const SoftDtwDist& a, hipStream_t s) {
     return 0;
 }
 
-static int softdtw_check(const SoftDtwArgs& a, const char* who) {
+template <class Args>   // t2_softdtw_fwd_args or t2_softdtw_bwd_args
+static int softdtw_check(const Args& a, const char* who) {
     T2_REQUIRE((a.D != nullptr) != (a.Ds != nullptr), "%s: exactly one of D (row-major) and Ds (from softdtw_dist) must be given", who);
     T2_REQUIRE(a.bandwidth >= 0.f, "%s: bandwidth=%g must not be negative (0 = off)", who, (double)a.bandwidth);
     T2_REQUIRE((a.x_lengths == nullptr) == (a.y_lengths == nullptr), "%s: give both length arrays or neither", who);
@@ -343,7 +347,7 @@ static int softdtw_check(const SoftDtwArgs& a, const char* who) {
 }
 
 template <int RPT>
-static void softdtw_fwd_launch(const SoftDtwArgs& a, const SoftDtwPlan& pl, hipStream_t s) {
+static void softdtw_fwd_launch(const t2_softdtw_fwd_args& a, const t2_softdtw_plan_info& pl, hipStream_t s) {
     const bool skew = a.Ds != nullptr, grad = a.R != nullptr;
     const float* src = skew ? a.Ds : a.D;
     auto go = [&](auto kern) {
@@ -354,8 +358,9 @@ static void softdtw_fwd_launch(const SoftDtwArgs& a, const SoftDtwPlan& pl, hipS
     else      { if (grad) go(softdtw_fwd_kernel<RPT, false, true>); else go(softdtw_fwd_kernel<RPT, false, false>); }
 }
 
-int softdtw_fwd(const SoftDtwArgs& a, hipStream_t s) {
-    SoftDtwPlan pl;
+// value[b] = R[n_b, m_b]; R != null stores the whole R (r_floats) for softdtw_bwd
+static int softdtw_fwd(const t2_softdtw_fwd_args& a, hipStream_t s) {
+    t2_softdtw_plan_info pl;
     T2_TRY_RC(softdtw_plan(a.B, a.N, a.M, a.gamma, a.R != nullptr, &pl));
     T2_TRY_RC(softdtw_check(a, "softdtw_forward"));
     T2_REQUIRE(a.value, "softdtw_forward: null output");
@@ -370,7 +375,7 @@ int softdtw_fwd(const SoftDtwArgs& a, hipStream_t s) {
 }
 
 template <int RPT>
-static void softdtw_bwd_launch(const SoftDtwArgs& a, const SoftDtwPlan& pl, hipStream_t s) {
+static void softdtw_bwd_launch(const t2_softdtw_bwd_args& a, const t2_softdtw_plan_info& pl, hipStream_t s) {
     if (a.Ds)
         hipLaunchKernelGGL((softdtw_bwd_kernel<RPT, true>), dim3(a.B), dim3(pl.threads), 0, s, a.Ds, a.R, a.E, a.x_lengths, a.y_lengths,
                            a.N, a.M, pl.threads, pl.passes, a.gamma, a.bandwidth);
@@ -379,8 +384,9 @@ static void softdtw_bwd_launch(const SoftDtwArgs& a, const SoftDtwPlan& pl, hipS
                            a.N, a.M, pl.threads, pl.passes, a.gamma, a.bandwidth);
 }
 
-int softdtw_bwd(const SoftDtwArgs& a, hipStream_t s) {
-    SoftDtwPlan pl;
+// E [B,N,M], zeroed here first
+static int softdtw_bwd(const t2_softdtw_bwd_args& a, hipStream_t s) {
+    t2_softdtw_plan_info pl;
     T2_TRY_RC(softdtw_plan(a.B, a.N, a.M, a.gamma, 1, &pl));
     T2_TRY_RC(softdtw_check(a, "softdtw_backward"));
     T2_REQUIRE(a.R && a.E, "softdtw_backward: R (stored by the forward call) and E must be given");
@@ -395,8 +401,8 @@ int softdtw_bwd(const SoftDtwArgs& a, hipStream_t s) {
     return 0;
 }
 
-int softdtw_dist_bwd(const SoftDtwDistBwd& a, hipStream_t s) {
-    SoftDtwPlan pl;
+static int softdtw_dist_bwd(const t2_softdtw_dist_bwd_args& a, hipStream_t s) {
+    t2_softdtw_plan_info pl;
     T2_TRY_RC(softdtw_plan(a.B, a.N, a.M, 1.f, 1, &pl));
     T2_REQUIRE(a.d >= 1, "softdtw: feature dimension d=%d must be at least 1", a.d);
     T2_REQUIRE(a.x && a.y && a.E && a.grad_out && a.dX && a.dY, "softdtw_dist_backward: null pointer");
@@ -410,3 +416,34 @@ int softdtw_dist_bwd(const SoftDtwDistBwd& a, hipStream_t s) {
 }
 
 }  // namespace t2
+
+// ---- C ABI (include/t2amd.h)
+using namespace t2;
+
+extern "C" {
+
+int t2_softdtw_plan(int B, int N, int M, float gamma, int need_grad, t2_softdtw_plan_info* out) {
+    t2_softdtw_plan_info p;
+    T2_TRY_RC(softdtw_plan(B, N, M, gamma, need_grad, &p));
+    T2_REQUIRE(out, "t2_softdtw_plan: null output");
+    *out = p;
+    return 0;
+}
+int t2_softdtw_dist(const t2_softdtw_dist_args* a, void* stream) {
+    T2_REQUIRE(a, "t2_softdtw_dist: null arguments");
+    return softdtw_dist(*a, (hipStream_t)stream);
+}
+int t2_softdtw_forward(const t2_softdtw_fwd_args* a, void* stream) {
+    T2_REQUIRE(a, "t2_softdtw_forward: null arguments");
+    return softdtw_fwd(*a, (hipStream_t)stream);
+}
+int t2_softdtw_backward(const t2_softdtw_bwd_args* a, void* stream) {
+    T2_REQUIRE(a, "t2_softdtw_backward: null arguments");
+    return softdtw_bwd(*a, (hipStream_t)stream);
+}
+int t2_softdtw_dist_backward(const t2_softdtw_dist_bwd_args* a, void* stream) {
+    T2_REQUIRE(a, "t2_softdtw_dist_backward: null arguments");
+    return softdtw_dist_bwd(*a, (hipStream_t)stream);
+}
+
+}  // extern "C"

@@ -26,6 +26,9 @@
 
 namespace t2 {
 
+constexpr int kSsimTileH = 16, kSsimTileW = 64;  // outputs per workgroup: 4 waves x 4 rows, a wave across the lane axis
+constexpr int kSsimMaxWs = 31;
+
 constexpr int kSsimThreads = 256;
 constexpr int kSsimRowsPerThread = kSsimTileH / (kSsimThreads / kWave);
 static_assert(kSsimTileW == kWave && kSsimRowsPerThread * (kSsimThreads / kWave) == kSsimTileH, "a wave spans a tile row, a thread owns whole rows");
@@ -36,7 +39,8 @@ static size_t ssim_lds_bytes(int ws, size_t staged_bytes_per_element) {     // f
     return (size_t)(32 + 4 + SH * kSsimTileW) * sizeof(double) + staged_bytes_per_element * SH * SW;
 }
 
-int ssim_plan(long N, long H, long W, int ws, int need_grad, SsimPlan* out) {
+// The tiling of N planes of H x W with W as the lane axis, decided on the host (t2amd.h t2_ssim_plan_info has the fields).
+static int ssim_plan(long N, long H, long W, int ws, int need_grad, t2_ssim_plan_info* out) {
     T2_REQUIRE(out, "ssim: null plan");
     T2_REQUIRE(ws >= 1 && ws % 2 == 1, "ssim: ws=%d must be odd and at least 1 (even windows are not built)", ws);
     T2_REQUIRE(ws <= kSsimMaxWs, "ssim: ws=%d exceeds the limit of %d taps", ws, kSsimMaxWs);
@@ -122,7 +126,7 @@ __device__ __forceinline__ double ssim_wave_sum(double v) {       // a fixed tre
 }
 
 struct SsimFwdK {
-    SsimImage x, y, map;          // canonical orientation (lane axis = W); map.p nullable
+    t2_ssim_image x, y, map;          // canonical orientation (lane axis = W); map.p nullable
     double* coef;                 // nullable; [slots][N][H][W]
     const float* taps;
     double* partial;
@@ -139,8 +143,8 @@ __global__ void __launch_bounds__(kSsimThreads) ssim_fwd_kernel(const SsimFwdK a
     const long n = blockIdx.x / a.tiles;
     const int r0 = tile / a.tiles_w * kSsimTileH, c0 = tile % a.tiles_w * kSsimTileW;
     if (threadIdx.x < ws) l.taps[threadIdx.x] = (double)a.taps[threadIdx.x];
-    ssim_stage<float>(l.sa, a.x.p + n * a.x.sn, a.x.sr, a.x.sc, r0, c0, a.H, a.W, l);
-    ssim_stage<float>(l.sb, a.y.p + n * a.y.sn, a.y.sr, a.y.sc, r0, c0, a.H, a.W, l);
+    ssim_stage<float>(l.sa, a.x.p + n * a.x.plane_stride, a.x.row_stride, a.x.col_stride, r0, c0, a.H, a.W, l);
+    ssim_stage<float>(l.sb, a.y.p + n * a.y.plane_stride, a.y.row_stride, a.y.col_stride, r0, c0, a.H, a.W, l);
     __syncthreads();
     double mu1[kSsimRowsPerThread], mu2[kSsimRowsPerThread], exx[kSsimRowsPerThread], eyy[kSsimRowsPerThread], exy[kSsimRowsPerThread];
     ssim_rows<WS, false>(l, l.sa, l.sa, ws); __syncthreads(); ssim_cols<WS>(mu1, l, ws); __syncthreads();
@@ -162,7 +166,7 @@ __global__ void __launch_bounds__(kSsimThreads) ssim_fwd_kernel(const SsimFwdK a
         const double iB1 = 1.0 / (m1 * m1 + m2 * m2 + kSsimC1), iB2 = 1.0 / (s1 + s2 + kSsimC2);
         const double S = A1 * A2 * iB1 * iB2;
         sum += S;
-        if (a.map.p) a.map.p[n * a.map.sn + (long)gr * a.map.sr + (long)gc * a.map.sc] = (float)S;
+        if (a.map.p) a.map.p[n * a.map.plane_stride + (long)gr * a.map.row_stride + (long)gc * a.map.col_stride] = (float)S;
         if (a.need) {
             const double b = -S * iB2, c = 2.0 * A1 * iB1 * iB2;
             const double t = 2.0 * A2 * iB1 * iB2, u = 2.0 * S * iB1;       // dS/dmu1 = t mu2 - u mu1 at fixed s
@@ -206,7 +210,7 @@ __global__ void __launch_bounds__(kSsimThreads) ssim_finish_kernel(const double*
 }
 
 struct SsimBwdK {
-    SsimImage x, y, dx, dy;       // canonical orientation; dx.p, dy.p nullable
+    t2_ssim_image x, y, dx, dy;       // canonical orientation; dx.p, dy.p nullable
     const double* coef;
     const float* taps;
     const float* grad;            // [1] or [B]
@@ -247,13 +251,13 @@ __global__ void __launch_bounds__(kSsimThreads) ssim_bwd_kernel(const SsimBwdK a
     for (int o = 0; o < kSsimRowsPerThread; ++o) {
         const int gr = r0 + w * kSsimRowsPerThread + o;
         if (gr >= a.H || gc >= a.W) continue;
-        const double xv = (double)a.x.p[n * a.x.sn + (long)gr * a.x.sr + (long)gc * a.x.sc];
-        const double yv = (double)a.y.p[n * a.y.sn + (long)gr * a.y.sr + (long)gc * a.y.sc];
+        const double xv = (double)a.x.p[n * a.x.plane_stride + (long)gr * a.x.row_stride + (long)gc * a.x.col_stride];
+        const double yv = (double)a.y.p[n * a.y.plane_stride + (long)gr * a.y.row_stride + (long)gc * a.y.col_stride];
         const double fb = f[1][o], fc = f[2][o];
-        if (a.dx.p) a.dx.p[n * a.dx.sn + (long)gr * a.dx.sr + (long)gc * a.dx.sc] = (float)(g * (f[0][o] + 2.0 * xv * fb + yv * fc));
+        if (a.dx.p) a.dx.p[n * a.dx.plane_stride + (long)gr * a.dx.row_stride + (long)gc * a.dx.col_stride] = (float)(g * (f[0][o] + 2.0 * xv * fb + yv * fc));
         if (a.dy.p) {
             const double fq = a.need == 3 ? f[3][o] : f[0][o];
-            a.dy.p[n * a.dy.sn + (long)gr * a.dy.sr + (long)gc * a.dy.sc] = (float)(g * (fq + 2.0 * yv * fb + xv * fc));
+            a.dy.p[n * a.dy.plane_stride + (long)gr * a.dy.row_stride + (long)gc * a.dy.col_stride] = (float)(g * (fq + 2.0 * yv * fb + xv * fc));
         }
     }
 }
@@ -261,13 +265,13 @@ __global__ void __launch_bounds__(kSsimThreads) ssim_bwd_kernel(const SsimBwdK a
 // ------------------------------------------------------------------------------------------------------------------
 // launchers
 // ------------------------------------------------------------------------------------------------------------------
-static bool ssim_inner_ok(const SsimImage& im, int H, int W) { return im.sc == 1 || W == 1 || im.sr == 1 || H == 1; }
+static bool ssim_inner_ok(const t2_ssim_image& im, int H, int W) { return im.col_stride == 1 || W == 1 || im.row_stride == 1 || H == 1; }
 // The lane axis: W where x is contiguous along it, else H (the launcher then swaps the two axes of every image).
-static bool ssim_lane_is_h(const SsimImage& x, int H, int W) { return !(x.sc == 1 && W > 1) && x.sr == 1 && H > 1; }
-static SsimImage ssim_swapped(SsimImage im) { const long t = im.sr; im.sr = im.sc; im.sc = t; return im; }
+static bool ssim_lane_is_h(const t2_ssim_image& x, int H, int W) { return !(x.col_stride == 1 && W > 1) && x.row_stride == 1 && H > 1; }
+static t2_ssim_image ssim_swapped(t2_ssim_image im) { const long t = im.row_stride; im.row_stride = im.col_stride; im.col_stride = t; return im; }
 
-int ssim_fwd(const SsimFwd& a, hipStream_t s) {
-    SsimPlan p;
+static int ssim_fwd(const t2_ssim_fwd_args& a, hipStream_t s) {
+    t2_ssim_plan_info p;
     T2_TRY_RC(ssim_plan((long)a.B * a.C, a.H, a.W, a.ws, a.need_grad, &p));
     T2_REQUIRE(a.B >= 1 && a.C >= 1, "ssim_forward: B=%d and C=%d must be at least 1", a.B, a.C);
     T2_REQUIRE(a.x.p && a.y.p, "ssim_forward: x and y must not be null");
@@ -275,13 +279,13 @@ int ssim_fwd(const SsimFwd& a, hipStream_t s) {
     T2_REQUIRE(a.partial, "ssim_forward: partial (the plan's partial_bytes of scratch) must not be null");
     T2_REQUIRE(a.value || a.items || a.map.p, "ssim_forward: value, items and map are all null");
     T2_REQUIRE(!a.need_grad || a.coef, "ssim_forward: need_grad=%d needs coef (the plan's map_bytes of scratch)", a.need_grad);
-    T2_REQUIRE(ssim_inner_ok(a.x, a.H, a.W), "ssim_forward: x has row stride %ld and column stride %ld: one of them must be 1", a.x.sr, a.x.sc);
-    T2_REQUIRE(ssim_inner_ok(a.y, a.H, a.W), "ssim_forward: y has row stride %ld and column stride %ld: one of them must be 1", a.y.sr, a.y.sc);
+    T2_REQUIRE(ssim_inner_ok(a.x, a.H, a.W), "ssim_forward: x has row stride %ld and column stride %ld: one of them must be 1", a.x.row_stride, a.x.col_stride);
+    T2_REQUIRE(ssim_inner_ok(a.y, a.H, a.W), "ssim_forward: y has row stride %ld and column stride %ld: one of them must be 1", a.y.row_stride, a.y.col_stride);
     const bool swap = ssim_lane_is_h(a.x, a.H, a.W);
     SsimFwdK k;
     k.x = swap ? ssim_swapped(a.x) : a.x; k.y = swap ? ssim_swapped(a.y) : a.y; k.map = swap ? ssim_swapped(a.map) : a.map;
     k.H = swap ? a.W : a.H; k.W = swap ? a.H : a.W;
-    k.coef = a.coef; k.taps = a.taps; k.partial = a.partial; k.need = a.need_grad; k.ws = a.ws;
+    k.coef = static_cast<double*>(a.coef); k.taps = a.taps; k.partial = static_cast<double*>(a.partial); k.need = a.need_grad; k.ws = a.ws;
     k.nhw = (long)a.B * a.C * a.H * a.W;
     k.tiles_w = (k.W + kSsimTileW - 1) / kSsimTileW;
     k.tiles = k.tiles_w * ((k.H + kSsimTileH - 1) / kSsimTileH);
@@ -292,14 +296,14 @@ int ssim_fwd(const SsimFwd& a, hipStream_t s) {
     T2_LAUNCH_CHECK();
     if (a.value || a.items) {
         const double chw = (double)a.C * a.H * a.W;
-        ssim_finish_kernel<<<dim3(1), dim3(kSsimThreads), 0, s>>>(a.partial, a.B, a.C * k.tiles, 1.0 / chw, 1.0 / (chw * a.B), a.value, a.items);
+        ssim_finish_kernel<<<dim3(1), dim3(kSsimThreads), 0, s>>>(k.partial, a.B, a.C * k.tiles, 1.0 / chw, 1.0 / (chw * a.B), a.value, a.items);
         T2_LAUNCH_CHECK();
     }
     return 0;
 }
 
-int ssim_bwd(const SsimBwd& a, hipStream_t s) {
-    SsimPlan p;
+static int ssim_bwd(const t2_ssim_bwd_args& a, hipStream_t s) {
+    t2_ssim_plan_info p;
     T2_TRY_RC(ssim_plan((long)a.B * a.C, a.H, a.W, a.ws, a.need_grad, &p));
     T2_REQUIRE(a.B >= 1 && a.C >= 1, "ssim_backward: B=%d and C=%d must be at least 1", a.B, a.C);
     T2_REQUIRE(a.x.p && a.y.p, "ssim_backward: x and y must not be null");
@@ -309,14 +313,14 @@ int ssim_bwd(const SsimBwd& a, hipStream_t s) {
     T2_REQUIRE(a.dx.p || a.dy.p, "ssim_backward: dx and dy are both null");
     T2_REQUIRE(!a.dx.p || (a.need_grad & 1), "ssim_backward: dx asked, but the forward ran with need_grad=%d", a.need_grad);
     T2_REQUIRE(!a.dy.p || (a.need_grad & 2), "ssim_backward: dy asked, but the forward ran with need_grad=%d", a.need_grad);
-    T2_REQUIRE(ssim_inner_ok(a.x, a.H, a.W), "ssim_backward: x has row stride %ld and column stride %ld: one of them must be 1", a.x.sr, a.x.sc);
-    T2_REQUIRE(ssim_inner_ok(a.y, a.H, a.W), "ssim_backward: y has row stride %ld and column stride %ld: one of them must be 1", a.y.sr, a.y.sc);
+    T2_REQUIRE(ssim_inner_ok(a.x, a.H, a.W), "ssim_backward: x has row stride %ld and column stride %ld: one of them must be 1", a.x.row_stride, a.x.col_stride);
+    T2_REQUIRE(ssim_inner_ok(a.y, a.H, a.W), "ssim_backward: y has row stride %ld and column stride %ld: one of them must be 1", a.y.row_stride, a.y.col_stride);
     const bool swap = ssim_lane_is_h(a.x, a.H, a.W);                    // the forward's choice: coef is in that orientation
     SsimBwdK k;
     k.x = swap ? ssim_swapped(a.x) : a.x; k.y = swap ? ssim_swapped(a.y) : a.y;
     k.dx = swap ? ssim_swapped(a.dx) : a.dx; k.dy = swap ? ssim_swapped(a.dy) : a.dy;
     k.H = swap ? a.W : a.H; k.W = swap ? a.H : a.W;
-    k.coef = a.coef; k.taps = a.taps; k.grad = a.grad; k.need = a.need_grad; k.ws = a.ws; k.per_item = a.per_item; k.C = a.C;
+    k.coef = static_cast<const double*>(a.coef); k.taps = a.taps; k.grad = a.grad; k.need = a.need_grad; k.ws = a.ws; k.per_item = a.per_item; k.C = a.C;
     const double chw = (double)a.C * a.H * a.W;
     k.inv_count = 1.0 / (a.per_item ? chw : chw * a.B);
     k.nhw = (long)a.B * a.C * a.H * a.W;
@@ -331,3 +335,26 @@ int ssim_bwd(const SsimBwd& a, hipStream_t s) {
 }
 
 }  // namespace t2
+
+// ---- C ABI (include/t2amd.h)
+using namespace t2;
+
+extern "C" {
+
+int t2_ssim_plan(int N, int H, int W, int ws, int need_grad, t2_ssim_plan_info* out) {
+    t2_ssim_plan_info p;
+    T2_TRY_RC(ssim_plan(N, H, W, ws, need_grad, &p));
+    T2_REQUIRE(out, "t2_ssim_plan: null output");
+    *out = p;
+    return 0;
+}
+int t2_ssim_forward(const t2_ssim_fwd_args* a, void* stream) {
+    T2_REQUIRE(a, "t2_ssim_forward: null arguments");
+    return ssim_fwd(*a, (hipStream_t)stream);
+}
+int t2_ssim_backward(const t2_ssim_bwd_args* a, void* stream) {
+    T2_REQUIRE(a, "t2_ssim_backward: null arguments");
+    return ssim_bwd(*a, (hipStream_t)stream);
+}
+
+}  // extern "C"

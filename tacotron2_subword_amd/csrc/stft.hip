@@ -298,7 +298,9 @@ int stft_pack_overlap(int N, int hop, const float* basis, float* packed, hipStre
     return 0;
 }
 
-int stft_pack(int N, int hop, const float* fwd, const float* inv, const double* wsq, float* packed, hipStream_t s) {
+// fwd, inv: the windowed bases [2*(N/2+1)][N] (the module's buffers without their middle dimension); wsq: the squared,
+// centre-padded window [N] in fp64, nullable (no window: synthesis must then run with windowed = 0)
+static int stft_pack(int N, int hop, const float* fwd, const float* inv, const double* wsq, float* packed, hipStream_t s) {
     StftPlan pl;
     T2_TRY_RC(stft_plan(N, hop, 1, &pl));
     T2_REQUIRE(fwd && inv && packed, "stft_pack: null pointer");
@@ -310,9 +312,13 @@ int stft_pack(int N, int hop, const float* fwd, const float* inv, const double* 
     return 0;
 }
 
-int stft_analysis(const StftAnalysis& a, hipStream_t s) {
+// x [B, n] -> re, im, mag, phase [B, N/2+1, 1 + n/hop], each nullable
+// lengths (nullable, device [B]): per-item sample counts, clamped to [0, n] in the kernel.  Item b is then x[b, :lengths[b]] alone:
+// its own reflection, 1 + lengths[b]/hop frames (none where lengths[b] <= N/2), zeros in the planes behind them; frame_lengths
+// (nullable) receives the counts
+static int stft_analysis(const t2_stft_analysis_args& a, const int32_t* lengths, int32_t* frame_lengths, hipStream_t s) {
     T2_REQUIRE(a.B >= 1 && a.B <= 65535, "stft analysis: B=%d outside 1..65535", a.B);
-    T2_REQUIRE(a.lengths || !a.frame_lengths, "stft analysis: frame counts asked for without sample counts");
+    T2_REQUIRE(lengths || !frame_lengths, "stft analysis: frame counts asked for without sample counts");
     T2_REQUIRE(a.N >= 2 && a.N % 2 == 0, "stft analysis: filter_length=%d must be even", a.N);
     T2_REQUIRE(a.n > a.N / 2, "stft analysis: Padding size should be less than the corresponding input dimension, but got: padding (%d, %d) at dimension 1 "
                "of a signal of %ld samples", a.N / 2, a.N / 2, a.n);
@@ -325,23 +331,27 @@ int stft_analysis(const StftAnalysis& a, hipStream_t s) {
     StftAna p;
     p.x = a.x; p.pf = a.packed; p.re = a.re; p.im = a.im; p.mag = a.mag; p.phase = a.phase;
     p.n = a.n; p.nf = nf; p.N = a.N; p.hop = a.hop; p.cutoff = pl.cutoff; p.bin_tiles = pl.bin_tiles; p.kchunks = pl.kchunks;
-    p.lens = a.lengths; p.nf_out = a.frame_lengths;
+    p.lens = lengths; p.nf_out = frame_lengths;
     dim3 grid((unsigned)((nf + kStftTile - 1) / kStftTile), (unsigned)((pl.bin_tiles + 3) / 4), (unsigned)a.B);
     hipLaunchKernelGGL(stft_analysis_kernel, grid, dim3(256), 0, s, p);
     T2_LAUNCH_CHECK();
     return 0;
 }
 
-int stft_synthesis(const StftSynthesis& a, hipStream_t s) {
+// a, b [B, N/2+1, nf] -> y [B, 1, hop*(nf-1)]; modes and windowed as t2amd.h states them.
+// frame_lengths (nullable, device [B]): per-item frame counts, clamped to [0, nf] in the kernel.  Item b is then its first
+// frame_lengths[b] frames alone; y is zero from hop*(frame_lengths[b]-1) on (from 0 for a count below 1), which sample_lengths
+// (nullable) receives
+static int stft_synthesis(const t2_stft_synthesis_args& a, const int32_t* frame_lengths, int32_t* sample_lengths, hipStream_t s) {
     T2_REQUIRE(a.B >= 1 && a.B <= 65535, "stft synthesis: B=%d outside 1..65535", a.B);
     StftPlan pl;
     T2_TRY_RC(stft_plan(a.N, a.hop, a.nf, &pl));
-    T2_REQUIRE(a.mode == 0 || a.mode == 1, "stft synthesis: mode %d is neither polar (0) nor denoise (1)", a.mode);
+    T2_REQUIRE(a.mode == T2_STFT_POLAR || a.mode == T2_STFT_DENOISE, "stft synthesis: mode %d is neither polar (0) nor denoise (1)", a.mode);
     T2_REQUIRE(a.a && a.b && a.packed, "stft synthesis: null pointer");
-    T2_REQUIRE(a.mode == 0 || a.bias, "stft synthesis: the denoise mode needs the bias spectrum");
-    T2_REQUIRE(a.frame_lengths || !a.sample_lengths, "stft synthesis: sample counts asked for without frame counts");
+    T2_REQUIRE(a.mode == T2_STFT_POLAR || a.bias, "stft synthesis: the denoise mode needs the bias spectrum");
+    T2_REQUIRE(frame_lengths || !sample_lengths, "stft synthesis: sample counts asked for without frame counts");
     if (pl.out_len == 0) {                                     // a single frame: everything falls into the trimmed margins
-        if (a.sample_lengths) T2_CHECK_HIP(hipMemsetAsync(a.sample_lengths, 0, (size_t)a.B * sizeof(int32_t), s));
+        if (sample_lengths) T2_CHECK_HIP(hipMemsetAsync(sample_lengths, 0, (size_t)a.B * sizeof(int32_t), s));
         return 0;
     }
     T2_REQUIRE(a.y, "stft synthesis: null output");
@@ -352,7 +362,7 @@ int stft_synthesis(const StftSynthesis& a, hipStream_t s) {
     p.mode = a.mode; p.windowed = a.windowed != 0;
     p.qbase = (a.N / 2) / a.hop; p.out_len = pl.out_len;
     p.strength = a.strength; p.scale = (float)a.N / (float)a.hop;
-    p.nfs = a.frame_lengths; p.len_out = a.sample_lengths;
+    p.nfs = frame_lengths; p.len_out = sample_lengths;
     p.lens = nullptr; p.n = 0; p.row = 0; p.pad = 0;
     const long qlast = (a.N / 2 + pl.out_len - 1) / a.hop;
     const int wn = pl.col_tiles >= 8 ? 8 : (pl.col_tiles >= 4 ? 4 : (pl.col_tiles >= 2 ? 2 : 1));
@@ -392,22 +402,22 @@ __global__ void __launch_bounds__(256) stft_fold_kernel(StftFold p) {
     p.dx[(size_t)b * p.n + i] = v;
 }
 
-int stft_analysis_backward(const StftAnalysisBwd& a, hipStream_t s) {
+int stft_analysis_backward(const t2_stft_analysis_backward_args& a, int pad, hipStream_t s) {
     T2_REQUIRE(a.B >= 1 && a.B <= 65535, "stft analysis backward: B=%d outside 1..65535", a.B);
     T2_REQUIRE(a.hop >= 1 && a.N >= 2 && a.N % 2 == 0, "stft analysis backward: filter_length=%d must be even and hop_length=%d positive", a.N, a.hop);
-    T2_REQUIRE(a.pad >= 0 && a.pad <= a.N / 2, "stft analysis backward: pad=%d outside 0..filter_length/2=%d", a.pad, a.N / 2);
-    T2_REQUIRE(a.n > a.pad && a.n + 2L * a.pad >= a.N && a.n <= INT32_MAX / 2, "stft analysis backward: n=%ld samples with pad=%d per side outside what filter_length=%d takes",
-               a.n, a.pad, a.N);
-    const long nf = (a.n + 2L * a.pad - a.N) / a.hop + 1;
+    T2_REQUIRE(pad >= 0 && pad <= a.N / 2, "stft analysis backward: pad=%d outside 0..filter_length/2=%d", pad, a.N / 2);
+    T2_REQUIRE(a.n > pad && a.n + 2L * pad >= a.N && a.n <= INT32_MAX / 2, "stft analysis backward: n=%ld samples with pad=%d per side outside what filter_length=%d takes",
+               a.n, pad, a.N);
+    const long nf = (a.n + 2L * pad - a.N) / a.hop + 1;
     T2_REQUIRE(nf <= INT32_MAX / 2 / a.hop, "stft analysis backward: %ld frames exceed the limit at hop_length=%d", nf, a.hop);
     StftPlan pl;
     T2_TRY_RC(stft_plan(a.N, a.hop, (int)nf, &pl));
-    T2_REQUIRE((a.d_re || a.d_im) && a.table && a.dxpad && a.dx, "stft analysis backward: null pointer");
+    T2_REQUIRE((a.d_re || a.d_im) && a.basis_table && a.dxpad && a.dx, "stft analysis backward: null pointer");
     StftSyn p{};
-    p.a = a.d_re; p.b = a.d_im; p.pi = a.table; p.y = a.dxpad;
+    p.a = a.d_re; p.b = a.d_im; p.pi = a.basis_table; p.y = a.dxpad;
     p.nf = (int)nf; p.N = a.N; p.hop = a.hop; p.R = pl.overlap; p.cutoff = pl.cutoff; p.nchunks = pl.bin_tiles; p.col_tiles = pl.col_tiles;
     p.qbase = 0; p.out_len = 0;
-    p.lens = a.lengths; p.n = a.n; p.row = a.n + 2L * a.pad; p.pad = a.pad;
+    p.lens = a.lengths; p.n = a.n; p.row = a.n + 2L * pad; p.pad = pad;
     const int wn = stft_backward_wave_cols(pl.col_tiles);
     dim3 grid((unsigned)((nf - 1 + pl.overlap + kStftTile - 1) / kStftTile), (unsigned)((pl.col_tiles + wn - 1) / wn), (unsigned)a.B);
     if (wn == 8) hipLaunchKernelGGL((stft_synthesis_kernel<8, true>), grid, dim3(512), 0, s, p);
@@ -415,10 +425,59 @@ int stft_analysis_backward(const StftAnalysisBwd& a, hipStream_t s) {
     else if (wn == 2) hipLaunchKernelGGL((stft_synthesis_kernel<2, true>), grid, dim3(128), 0, s, p);
     else hipLaunchKernelGGL((stft_synthesis_kernel<1, true>), grid, dim3(64), 0, s, p);
     T2_LAUNCH_CHECK();
-    StftFold f{a.dxpad, a.dx, a.lengths, a.n, p.row, a.N, a.hop, a.pad};
+    StftFold f{a.dxpad, a.dx, a.lengths, a.n, p.row, a.N, a.hop, pad};
     hipLaunchKernelGGL(stft_fold_kernel, dim3((unsigned)((a.n + 255) / 256), (unsigned)a.B), dim3(256), 0, s, f);
     T2_LAUNCH_CHECK();
     return 0;
 }
 
 }  // namespace t2
+
+// ---- C ABI (include/t2amd.h)
+using namespace t2;
+static_assert(T2_STFT_FRAME_TILE == kStftTile, "t2amd.h mirrors the STFT frame tile");
+
+extern "C" {
+
+int t2_stft_plan(int N, int hop, int nf, t2_stft_plan_info* out) {
+    T2_REQUIRE(out, "t2_stft_plan: null pointer");
+    StftPlan p;
+    T2_TRY_RC(stft_plan(N, hop, nf, &p));
+    out->bins = p.cutoff; out->overlap = p.overlap; out->frame_tile = kStftTile; out->bin_tile = 16; out->out_len = p.out_len;
+    out->fwd_floats = p.fwd_floats; out->inv_floats = p.inv_floats; out->wsq_floats = p.wsq_floats;
+    out->packed_bytes = (p.fwd_floats + p.inv_floats + p.wsq_floats) * sizeof(float);
+    return 0;
+}
+int t2_stft_pack(int N, int hop, const float* forward_basis, const float* inverse_basis, const double* window_sq, float* packed, void* stream) {
+    return stft_pack(N, hop, forward_basis, inverse_basis, window_sq, packed, (hipStream_t)stream);
+}
+int t2_stft_analysis(const t2_stft_analysis_args* a, void* stream) {
+    T2_REQUIRE(a, "t2_stft_analysis: null arguments");
+    return stft_analysis(*a, nullptr, nullptr, (hipStream_t)stream);
+}
+int t2_stft_analysis_ragged(const t2_stft_analysis_ragged_args* a, void* stream) {
+    T2_REQUIRE(a, "t2_stft_analysis_ragged: null arguments");
+    T2_REQUIRE(a->lengths, "t2_stft_analysis_ragged: null lengths (t2_stft_analysis is the call without them)");
+    t2_stft_analysis_args p{};
+    p.B = a->B; p.N = a->N; p.hop = a->hop; p.n = a->n; p.x = a->x; p.packed = a->packed;
+    p.re = a->re; p.im = a->im; p.mag = a->mag; p.phase = a->phase;
+    return stft_analysis(p, a->lengths, a->frame_lengths, (hipStream_t)stream);
+}
+int t2_stft_synthesis(const t2_stft_synthesis_args* a, void* stream) {
+    T2_REQUIRE(a, "t2_stft_synthesis: null arguments");
+    return stft_synthesis(*a, nullptr, nullptr, (hipStream_t)stream);
+}
+int t2_stft_synthesis_ragged(const t2_stft_synthesis_ragged_args* a, void* stream) {
+    T2_REQUIRE(a, "t2_stft_synthesis_ragged: null arguments");
+    T2_REQUIRE(a->frame_lengths, "t2_stft_synthesis_ragged: null frame counts (t2_stft_synthesis is the call without them)");
+    t2_stft_synthesis_args p{};
+    p.B = a->B; p.N = a->N; p.hop = a->hop; p.nf = a->nf; p.mode = a->mode; p.windowed = a->windowed;
+    p.a = a->a; p.b = a->b; p.bias = a->bias; p.strength = a->strength; p.packed = a->packed; p.y = a->y;
+    return stft_synthesis(p, a->frame_lengths, a->sample_lengths, (hipStream_t)stream);
+}
+int t2_stft_analysis_backward(const t2_stft_analysis_backward_args* a, void* stream) {
+    T2_REQUIRE(a, "t2_stft_analysis_backward: null arguments");
+    return stft_analysis_backward(*a, a->N / 2, (hipStream_t)stream);
+}
+
+}  // extern "C"

@@ -23,10 +23,28 @@
 // run alone; a workgroup whose tile lies behind its item's end returns before its first barrier.  The count is only read
 // in the kernels, clamped: no value of it moves a load or a store out of a row.
 #include <algorithm>
+#include <vector>
 
 #include "slab_gemm.h"
 
 namespace t2 {
+
+constexpr int kVocMaxPad = 60;                   // (k*d - d)/2 at k = 11, d = 12
+// One layer on packed weights.  u == 0: Conv1d, kernel k, dilation d, stride 1, padding (k*d - d)/2, x [B,Cin,L] ->
+// y [B,Cout,L];  y = ((accumulate ? y : 0) + conv(lrelu(x, slope)) + bias + res) * scale, bias and res nullable.
+// u > 0: ConvTranspose1d, kernel k = 2u, stride u, padding (k - u)/2, x [B,Cin,L] -> y [B,Cout,L*u]; no res / accumulate.
+struct VocConv {
+    int B, Cin, Cout; long L; int k, d, u;
+    const float* x; const float* packed; const float* bias; const float* res; float* y;
+    float slope; int accumulate; float scale;
+    // nullable, device: item b's rows hold clamp(frames[b], 0, T) * factor inputs (L = T * factor).  What x, res and (accumulate) y
+    // hold behind that is never read; y behind it is left as it was
+    const int32_t* frames = nullptr; int T = 0, factor = 0;
+};
+// kind 0 Conv1d, 1 ConvTranspose1d, 2 conv_post; offsets in floats into the packed weights.  Order: conv_pre, ups[i],
+// resblocks[n] (ResBlock1: convs1[m] then convs2[m]; ResBlock2: convs[m]), conv_post: the order of the state dict.
+struct HifiganLayer { int kind, cin, cout, k, d, u; size_t w_off, b_off; };
+struct HifiganPlan { long out_len; size_t buf_floats, workspace_bytes, packed_bytes; int n_layers; };
 
 constexpr int kVocStride = 288;                   // slab row stride in floats: = 32 mod 64 banks, >= kVocTT + 2*kVocMaxPad
 static_assert(kVocStride % 64 == 32 && kVocStride >= kVocTT + 2 * kVocMaxPad, "slab row stride");
@@ -144,12 +162,12 @@ static int voc_shape_check(const char* who, int Cin, int Cout, int k, int d, int
     return 0;
 }
 
-size_t voc_packed_floats(int Cin, int Cout, int k, int u) {
+static size_t voc_packed_floats(int Cin, int Cout, int k, int u) {
     return u ? (size_t)u * slab_packed_floats(1, Cout, Cin, 2, 0) : slab_packed_floats(1, Cout, Cin, k, 0);
 }
 
 // packed[phase][mtile][chunk][tap]...: Conv1d [Cout][Cin][k] is one phase; ConvTranspose1d [Cin][Cout][k] one pack per phase r (taps (r + pad) % u + j*u)
-int voc_pack(const float* w, float* packed, int Cin, int Cout, int k, int u, hipStream_t s) {
+static int voc_pack(const float* w, float* packed, int Cin, int Cout, int k, int u, hipStream_t s) {   // w in torch layout
     T2_TRY_RC(voc_shape_check("vocoder pack", Cin, Cout, k, 1, u));
     T2_REQUIRE(w && packed, "vocoder pack: null pointer");
     SlabPack p{};
@@ -166,7 +184,7 @@ int voc_pack(const float* w, float* packed, int Cin, int Cout, int k, int u, hip
     return 0;
 }
 
-int voc_conv(const VocConv& a, hipStream_t s) {
+static int voc_conv(const VocConv& a, hipStream_t s) {
     const char* who = a.u ? "vocoder conv_transpose1d" : "vocoder conv1d";
     T2_TRY_RC(voc_shape_check(who, a.Cin, a.Cout, a.k, a.u ? 1 : a.d, a.u));
     T2_REQUIRE(a.B >= 1 && a.B <= 65535, "%s: B=%d outside 1..65535", who, a.B);
@@ -192,11 +210,11 @@ int voc_conv(const VocConv& a, hipStream_t s) {
 // ------------------------------------------------------------------------------------------------------------------
 // the generator
 // ------------------------------------------------------------------------------------------------------------------
-int hifigan_layers(const HifiganConfig& c, std::vector<HifiganLayer>* out, size_t* packed_floats) {
+static int hifigan_layers(const t2_hifigan_config& c, std::vector<HifiganLayer>* out, size_t* packed_floats) {   // validates; no device
     T2_REQUIRE(c.resblock == 1 || c.resblock == 2, "hifigan: resblock \"%d\" is not \"1\" or \"2\"", c.resblock);
     T2_REQUIRE(c.n_mel == 80, "hifigan: %d mel channels, conv_pre takes 80", c.n_mel);
-    T2_REQUIRE(c.num_upsamples >= 1 && c.num_upsamples <= kHifiganMaxUps, "hifigan: %d upsampling stages outside 1..%d", c.num_upsamples, kHifiganMaxUps);
-    T2_REQUIRE(c.num_kernels >= 1 && c.num_kernels <= kHifiganMaxKernels, "hifigan: %d resblock kernels outside 1..%d", c.num_kernels, kHifiganMaxKernels);
+    T2_REQUIRE(c.num_upsamples >= 1 && c.num_upsamples <= T2_HIFIGAN_MAX_UPS, "hifigan: %d upsampling stages outside 1..%d", c.num_upsamples, T2_HIFIGAN_MAX_UPS);
+    T2_REQUIRE(c.num_kernels >= 1 && c.num_kernels <= T2_HIFIGAN_MAX_KERNELS, "hifigan: %d resblock kernels outside 1..%d", c.num_kernels, T2_HIFIGAN_MAX_KERNELS);
     const int want_d = c.resblock == 1 ? 3 : 2;
     T2_REQUIRE(c.num_dilations == want_d, "hifigan: %d dilations per resblock, ResBlock%d takes %d", c.num_dilations, c.resblock, want_d);
     const int c0 = c.upsample_initial_channel;
@@ -228,7 +246,7 @@ int hifigan_layers(const HifiganConfig& c, std::vector<HifiganLayer>* out, size_
     return 0;
 }
 
-int hifigan_plan(const HifiganConfig& c, int B, int T, HifiganPlan* out) {
+static int hifigan_plan(const t2_hifigan_config& c, int B, int T, HifiganPlan* out) {
     T2_REQUIRE(out, "hifigan: null plan");
     std::vector<HifiganLayer> L;
     size_t packed = 0;
@@ -250,7 +268,7 @@ int hifigan_plan(const HifiganConfig& c, int B, int T, HifiganPlan* out) {
     return 0;
 }
 
-int hifigan_pack(const HifiganConfig& c, const float* const* weights, const float* const* biases, int n_layers, float* packed, hipStream_t s) {
+static int hifigan_pack(const t2_hifigan_config& c, const float* const* weights, const float* const* biases, int n_layers, float* packed, hipStream_t s) {
     std::vector<HifiganLayer> L;
     T2_TRY_RC(hifigan_layers(c, &L, nullptr));
     T2_REQUIRE(weights && biases && packed, "hifigan_pack: null pointer");
@@ -265,19 +283,21 @@ int hifigan_pack(const HifiganConfig& c, const float* const* weights, const floa
     return 0;
 }
 
-int hifigan_forward(const HifiganConfig& c, const HifiganFwd& a, hipStream_t s) {
+// frames (nullable, device [B]): per-item frame counts, clamped to [0, T] in the kernels; item b is then computed as if it were
+// mel[b, :, :frames[b]] alone, audio and pre_tanh are zero behind frames[b] * prod(rates), which sample_lengths (nullable) receives
+static int hifigan_forward(const t2_hifigan_config& c, const t2_hifigan_fwd_args& a, const int32_t* frames, int32_t* sample_lengths, hipStream_t s) {
     std::vector<HifiganLayer> L;
     HifiganPlan pl;
     T2_TRY_RC(hifigan_layers(c, &L, nullptr));
     T2_REQUIRE(a.n_mel == c.n_mel, "hifigan_forward: the mel has %d channels, the generator takes %d", a.n_mel, c.n_mel);
     T2_TRY_RC(hifigan_plan(c, a.B, a.T, &pl));
     T2_REQUIRE(a.packed && a.mel && a.workspace && a.audio, "hifigan_forward: null pointer");
-    T2_REQUIRE(a.frames || !a.sample_lengths, "hifigan_forward: sample lengths asked for without frame counts");
+    T2_REQUIRE(frames || !sample_lengths, "hifigan_forward: sample lengths asked for without frame counts");
     float* XS = a.workspace; float* X = XS + pl.buf_floats; float* Tb = X + pl.buf_floats; float* P = Tb + pl.buf_floats; float* Q = P + pl.buf_floats;
     const float kSlope = 0.1f;                                       // LRELU_SLOPE, hifigan_model.py:8
     auto run = [&](const HifiganLayer& l, const float* x, float* y, long len, float slope, const float* res, int accumulate, float scale) {
         return voc_conv(VocConv{a.B, l.cin, l.cout, len, l.k, l.d, l.u, x, a.packed + l.w_off, a.packed + l.b_off, res, y, slope, accumulate, scale,
-                                a.frames, a.T, (int)(len / a.T)}, s);
+                                frames, a.T, (int)(len / a.T)}, s);
     };
     size_t li = 0;
     long len = a.T;
@@ -311,9 +331,66 @@ int hifigan_forward(const HifiganConfig& c, const HifiganFwd& a, hipStream_t s) 
     // F.leaky_relu(x) in front of conv_post is torch's default slope 0.01, not LRELU_SLOPE (hifigan_model.py:112)
     dim3 grid((unsigned)((len + 255) / 256), (unsigned)a.B);
     hipLaunchKernelGGL(voc_post_kernel, grid, dim3(256), (size_t)post.cin * kVocPostK * sizeof(float), s, XS, a.packed + post.w_off,
-                       a.packed + post.b_off, a.audio, a.pre_tanh, post.cin, len, 0.01f, a.frames, a.T, (int)(len / a.T), a.sample_lengths);
+                       a.packed + post.b_off, a.audio, a.pre_tanh, post.cin, len, 0.01f, frames, a.T, (int)(len / a.T), sample_lengths);
     T2_LAUNCH_CHECK();
     return 0;
 }
 
 }  // namespace t2
+
+// ---- C ABI (include/t2amd.h)
+using namespace t2;
+static_assert(T2_VOCODER_TIME_TILE == kVocTT, "t2amd.h mirrors the time tile");
+
+extern "C" {
+
+int t2_hifigan_plan(const t2_hifigan_config* cfg, int B, int T, t2_hifigan_plan_info* out) {
+    T2_REQUIRE(cfg && out, "t2_hifigan_plan: null pointer");
+    HifiganPlan p;
+    T2_TRY_RC(hifigan_plan(*cfg, B, T, &p));
+    out->out_len = p.out_len; out->workspace_bytes = p.workspace_bytes; out->packed_bytes = p.packed_bytes;
+    out->n_layers = p.n_layers; out->time_tile = kVocTT;
+    return 0;
+}
+int t2_hifigan_pack(const t2_hifigan_config* cfg, const float* const* weights_host, const float* const* biases_host, int n_layers,
+                    float* packed, void* stream) {
+    T2_REQUIRE(cfg, "t2_hifigan_pack: null configuration");
+    return hifigan_pack(*cfg, weights_host, biases_host, n_layers, packed, (hipStream_t)stream);
+}
+int t2_hifigan_forward(const t2_hifigan_config* cfg, const t2_hifigan_fwd_args* a, void* stream) {
+    T2_REQUIRE(cfg && a, "t2_hifigan_forward: null pointer");
+    return hifigan_forward(*cfg, *a, nullptr, nullptr, (hipStream_t)stream);
+}
+int t2_hifigan_forward_ragged(const t2_hifigan_config* cfg, const t2_hifigan_ragged_args* a, void* stream) {
+    T2_REQUIRE(cfg && a, "t2_hifigan_forward_ragged: null pointer");
+    T2_REQUIRE(a->frames, "t2_hifigan_forward_ragged: null frame counts (t2_hifigan_forward is the call without them)");
+    t2_hifigan_fwd_args f{};
+    f.B = a->B; f.T = a->T; f.n_mel = a->n_mel;
+    f.packed = a->packed; f.mel = a->mel; f.workspace = a->workspace; f.audio = a->audio; f.pre_tanh = a->pre_tanh;
+    return hifigan_forward(*cfg, f, a->frames, a->sample_lengths, (hipStream_t)stream);
+}
+size_t t2_vocoder_packed_floats(int Cin, int Cout, int k, int u) { return voc_packed_floats(Cin, Cout, k, u); }
+static int vocoder_layer(const t2_vocoder_conv_args* a, int u, const int32_t* lengths, void* stream) {
+    T2_REQUIRE(a->w && a->packed_ws, "t2_vocoder: null weights or packing scratch");
+    T2_TRY_RC(voc_pack(a->w, a->packed_ws, a->Cin, a->Cout, a->k, u, (hipStream_t)stream));
+    return voc_conv(VocConv{a->B, a->Cin, a->Cout, (long)a->L, a->k, a->d, u, a->x, a->packed_ws, a->bias, u ? nullptr : a->residual, a->y,
+                            a->slope, u ? 0 : a->accumulate, u ? 1.f : a->scale, lengths, lengths ? a->L : 0, lengths ? 1 : 0}, (hipStream_t)stream);
+}
+int t2_vocoder_conv_ragged(const t2_vocoder_conv_ragged_args* a, void* stream) {
+    T2_REQUIRE(a, "t2_vocoder_conv_ragged: null arguments");
+    T2_REQUIRE(a->lengths, "t2_vocoder_conv_ragged: null lengths (t2_vocoder_conv1d / t2_vocoder_conv_transpose1d are the calls without them)");
+    T2_REQUIRE(a->conv.u >= 0, "t2_vocoder_conv_ragged: stride u=%d must not be negative", a->conv.u);
+    return vocoder_layer(&a->conv, a->conv.u, a->lengths, stream);
+}
+int t2_vocoder_conv1d(const t2_vocoder_conv_args* a, void* stream) {
+    T2_REQUIRE(a, "t2_vocoder_conv1d: null arguments");
+    T2_REQUIRE(a->u == 0, "t2_vocoder_conv1d: stride u=%d given, a Conv1d has none", a->u);
+    return vocoder_layer(a, 0, nullptr, stream);
+}
+int t2_vocoder_conv_transpose1d(const t2_vocoder_conv_args* a, void* stream) {
+    T2_REQUIRE(a, "t2_vocoder_conv_transpose1d: null arguments");
+    T2_REQUIRE(a->u >= 1, "t2_vocoder_conv_transpose1d: stride u=%d must be positive", a->u);
+    return vocoder_layer(a, a->u, nullptr, stream);
+}
+
+}  // extern "C"

@@ -18,9 +18,11 @@ import torch
 from . import _lib as L
 
 
-class _AdamTensor(C.Structure):
-    _fields_ = [("p", C.c_void_p), ("g", C.c_void_p), ("m", C.c_void_p), ("v", C.c_void_p), ("numel", C.c_long),
-                ("first_chunk", C.c_int), ("pad_", C.c_int)]
+_AdamTensor = L.AdamTensor
+_ROW = C.sizeof(_AdamTensor)          # bytes of one table row
+# _fast_step fills the table as an int64 matrix: one column per field, first_chunk in the low half of the last one (little endian)
+_COL = {name: getattr(_AdamTensor, name).offset // 8 for name in ("p", "g", "m", "v", "numel", "first_chunk")}
+assert _ROW % 8 == 0 and all(getattr(_AdamTensor, name).offset == 8 * c for name, c in _COL.items())
 
 
 class FusedAdam(torch.optim.Adam):
@@ -69,11 +71,12 @@ class FusedAdam(torch.optim.Adam):
             steps = {int(self.state[p]["step"].item()) for p in ps}
             if len(steps) != 1:
                 return None
-            rows, chunk = np.zeros((len(ps), 6), dtype=np.int64), 0
+            rows, chunk = np.zeros((len(ps), _ROW // 8), dtype=np.int64), 0
             for i, p in enumerate(ps):
                 st = self.state[p]
-                rows[i, 0], rows[i, 2], rows[i, 3], rows[i, 4] = p.data_ptr(), st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr(), p.numel()
-                rows[i, 5] = chunk                                        # first_chunk in the low 32 bits, pad in the high ones
+                rows[i, _COL["p"]], rows[i, _COL["m"]], rows[i, _COL["v"]] = p.data_ptr(), st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr()
+                rows[i, _COL["numel"]] = p.numel()
+                rows[i, _COL["first_chunk"]] = chunk                      # first_chunk in the low 32 bits, pad in the high ones
                 chunk += lib.t2_adam_chunks(p.numel())
             c = self._fast = dict(n=len(ps), live=live, rows=rows, chunks=chunk, step=steps.pop(), ids=[(id(p), id(self.state[p]["exp_avg"])) for p in ps],
                                   steps=[self.state[p]["step"] for p in ps])
@@ -83,31 +86,29 @@ class FusedAdam(torch.optim.Adam):
         # the live ones every step
         # (.get: a state emptied by a partial load_state_dict has no moments; it invalidates like a replaced one)
         if any(id(p) != a or id(self.state[p].get("exp_avg")) != b for p, (a, b) in zip(ps, c["ids"])) or \
-                [p.data_ptr() for p in ps] != c["rows"][:, 0].tolist() or \
-                [self.state[p]["exp_avg"].data_ptr() for p in ps] != c["rows"][:, 2].tolist() or \
-                [self.state[p]["exp_avg_sq"].data_ptr() for p in ps] != c["rows"][:, 3].tolist():
+                [p.data_ptr() for p in ps] != c["rows"][:, _COL["p"]].tolist() or \
+                [self.state[p]["exp_avg"].data_ptr() for p in ps] != c["rows"][:, _COL["m"]].tolist() or \
+                [self.state[p]["exp_avg_sq"].data_ptr() for p in ps] != c["rows"][:, _COL["v"]].tolist():
             self._fast = None
             return self._fast_step(lib, max_norm)                       # rebuilt from the live addresses (equal by construction: no second retry)
         if not all(g.is_contiguous() and not g.is_sparse and g.dtype == torch.float32 for g in grads):
             raise RuntimeError("FusedAdam: dense contiguous fp32 CUDA parameters only")
         n = c["n"]
-        c["rows"][:, 1] = [g.data_ptr() for g in grads]
+        c["rows"][:, _COL["g"]] = [g.data_ptr() for g in grads]
         torch._foreach_add_(c["steps"], 1)
         c["step"] += 1
-        slot = self._table(n * 48)
-        slot["host"][:n * 48].numpy().view(np.int64).reshape(n, 6)[:] = c["rows"]
-        if self._dev is None or self._dev.numel() < n * 48:
-            self._dev = torch.empty(n * 48, dtype=torch.uint8, device="cuda")
-        self._dev[:n * 48].copy_(slot["host"][:n * 48], non_blocking=True)
+        slot = self._table(n * _ROW)
+        slot["host"][:n * _ROW].numpy().view(np.int64).reshape(n, _ROW // 8)[:] = c["rows"]
+        if self._dev is None or self._dev.numel() < n * _ROW:
+            self._dev = torch.empty(n * _ROW, dtype=torch.uint8, device="cuda")
+        self._dev[:n * _ROW].copy_(slot["host"][:n * _ROW], non_blocking=True)
         slot["event"] = torch.cuda.Event()
         slot["event"].record()
         if self._partial is None or self._partial.numel() < c["chunks"] + 2:
             self._partial = torch.empty(c["chunks"] + 2, dtype=torch.float32, device="cuda")
         norm_out = torch.empty(4, dtype=torch.float32, device="cuda")
-        lib.t2_adam_step.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_float, C.c_float,
-                                     C.c_float, C.c_float, C.c_int, C.c_void_p]
         b1, b2 = group["betas"]
-        L.check(lib.t2_adam_step(self._dev.data_ptr(), n, c["chunks"], self._partial.data_ptr(), norm_out.data_ptr(),
+        L.check(lib.t2_adam_step(L.adam_table(self._dev.data_ptr()), n, c["chunks"], self._partial.data_ptr(), norm_out.data_ptr(),
                                  float(max_norm) if max_norm else 0.0, float(group["lr"]), float(b1), float(b2),
                                  float(group["eps"]), float(group["weight_decay"]), c["step"], L.stream()))
         self.last_norm, self.last_clip = norm_out[0], norm_out[1]
@@ -120,7 +121,6 @@ class FusedAdam(torch.optim.Adam):
             with torch.enable_grad():
                 loss = closure()
         lib = L.lib()
-        lib.t2_adam_chunks.argtypes, lib.t2_adam_chunks.restype = [C.c_long], C.c_int
         # an aborted persistent kernel the host has already seen: raise before anything else (the kernels below read the same
         # status word on the device and skip the update on their own when the host has not seen it yet)
         from . import ops
@@ -159,30 +159,27 @@ class FusedAdam(torch.optim.Adam):
                 chunk += lib.t2_adam_chunks(p.numel())
             spans.append((first, len(rows) - first, chunk - chunk0))
         n = len(rows)
-        slot = self._table(n * 48)
-        tab = (_AdamTensor * n).from_buffer(memoryview(slot["host"].numpy())[:n * 48])
+        slot = self._table(n * _ROW)
+        tab = (_AdamTensor * n).from_buffer(memoryview(slot["host"].numpy())[:n * _ROW])
         for i, r in enumerate(rows):
             tab[i].p, tab[i].g, tab[i].m, tab[i].v, tab[i].numel, tab[i].first_chunk = r
-        if self._dev is None or self._dev.numel() < n * 48:
-            self._dev = torch.empty(n * 48, dtype=torch.uint8, device="cuda")
-        self._dev[:n * 48].copy_(slot["host"][:n * 48], non_blocking=True)
+        if self._dev is None or self._dev.numel() < n * _ROW:
+            self._dev = torch.empty(n * _ROW, dtype=torch.uint8, device="cuda")
+        self._dev[:n * _ROW].copy_(slot["host"][:n * _ROW], non_blocking=True)
         slot["event"] = torch.cuda.Event()
         slot["event"].record()
         if self._partial is None or self._partial.numel() < chunk + 2:
             self._partial = torch.empty(chunk + 2, dtype=torch.float32, device="cuda")
         norm_out = torch.empty(4, dtype=torch.float32, device="cuda")
-        lib.t2_adam_step.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_float, C.c_float,
-                                     C.c_float, C.c_float, C.c_int, C.c_void_p]
-        lib.t2_adam_norm.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p]
         single = len(order) == 1
         if not single:       # norm + clip coefficient over every row first, then one update launch per (group, step)
-            L.check(lib.t2_adam_norm(self._dev.data_ptr(), n, chunk, self._partial.data_ptr(), norm_out.data_ptr(),
+            L.check(lib.t2_adam_norm(L.adam_table(self._dev.data_ptr()), n, chunk, self._partial.data_ptr(), norm_out.data_ptr(),
                                      float(max_norm) if max_norm else 0.0, L.stream()))
         for (gi, step), (first, cnt, nchunks) in zip(order, spans):
             group = self.param_groups[gi]
             b1, b2 = group["betas"]
             # single batch: norm and update in one call; otherwise max_norm < 0 = "use the coefficient already in norm_out"
-            L.check(lib.t2_adam_step(self._dev.data_ptr() + first * 48, cnt, nchunks, self._partial.data_ptr(), norm_out.data_ptr(),
+            L.check(lib.t2_adam_step(L.adam_table(self._dev.data_ptr() + first * _ROW), cnt, nchunks, self._partial.data_ptr(), norm_out.data_ptr(),
                                      (float(max_norm) if max_norm else 0.0) if single else -1.0, float(group["lr"]), float(b1), float(b2),
                                      float(group["eps"]), float(group["weight_decay"]), step, L.stream()))
         self.last_norm, self.last_clip = norm_out[0], norm_out[1]

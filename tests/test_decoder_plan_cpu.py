@@ -17,7 +17,6 @@ DEFAULTS = dict(dims="default", att="sma", NS=2, B=8, T=12, Tin=40, Tsub=20, pre
                 cus=256, claimed=1, no_resident=0, saved=1, defer=0, poll=0)
 ATT = dict(sma=SMA, lsa=LSA, fwd2=FA2, gmm=GMM, dca=DCA)
 CLEAR = ("status", "teacher", "decode")
-NO_SAVED_TILES = 10                                                        # T2_CHAIN_REFUSE_NO_SAVED_TILES
 
 
 def load_rows():
@@ -40,8 +39,9 @@ def chain_as_recorded(c, exp_reason):
     """(on, refusal, instance) of a chain as the parent had them.  The parent planned a chain only behind its own early returns
     (switch, step mode, attention kind, and for the LSA backward the saved tiles) and had no reason otherwise (0); the plan now
     states the one reason the parent had no word for, the missing tiles."""
+    from tacotron2_subword_amd._lib import CHAIN_REFUSE_NO_SAVED_TILES
     reason = c["reason"] if c["asked"] else 0
-    if not c["on"] and exp_reason == 0 and reason == NO_SAVED_TILES:
+    if not c["on"] and exp_reason == 0 and reason == CHAIN_REFUSE_NO_SAVED_TILES:
         reason = 0
     return int(c["on"]), reason, c.get("instance", -1)
 

@@ -48,7 +48,6 @@ pytestmark = pytest.mark.gpu
 
 DEV = "cuda"
 SENTINEL = 12345.0
-T2_CHAIN_REFUSE_SHAPE = 1                                                 # include/t2amd.h
 WORST = {}
 
 
@@ -187,7 +186,7 @@ def test_per_step_route(name):
     if z.chain:                                                           # the switch stays on: the plan refuses the shape
         for backward in (False, True):
             p = plan(len(z.reverse), z.B, z.H, backward)
-            assert not p["covered"] and p["reason"] == T2_CHAIN_REFUSE_SHAPE, p
+            assert not p["covered"] and p["reason"] == env()[0].CHAIN_REFUSE_SHAPE, p
     got, padcols = run_case(name, z.chain)
     compare("per_step", name, got)
     assert bool((padcols == SENTINEL).all())

@@ -12,7 +12,6 @@ Bounds (derived in adam_ref.py, u = 2^-24): norm within 32u relative; the coeffi
 share of its bounds.  Measured on an MI355X (profiles/r11_adam_tests.txt): the norm uses at most 4 % of 32u, p at most
 0.50 of bp (the rounding of p itself), m 0.16 of bm, v 0.46 of bv; the coefficient is bit for bit the float32 formula."""
 import copy
-import ctypes as C
 import functools
 
 import numpy as np
@@ -37,12 +36,7 @@ def bits(a):
 
 def lib():
     from tacotron2_subword_amd import _lib as L
-    l = L.lib()
-    l.t2_adam_chunks.argtypes, l.t2_adam_chunks.restype = [C.c_long], C.c_int
-    l.t2_adam_step.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_float, C.c_float,
-                               C.c_float, C.c_float, C.c_int, C.c_void_p]
-    l.t2_adam_norm.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p]
-    return l
+    return L.lib()
 
 
 class Table:
@@ -105,14 +99,14 @@ class Table:
 
     def norm(self, max_norm):
         from tacotron2_subword_amd import _lib as L
-        L.check(self.lib.t2_adam_norm(self.tab.data_ptr(), self.n, self.chunks, self.partial.data_ptr(), self.norm_out.data_ptr(),
+        L.check(self.lib.t2_adam_norm(L.adam_table(self.tab.data_ptr()), self.n, self.chunks, self.partial.data_ptr(), self.norm_out.data_ptr(),
                                       float(max_norm), L.stream()))
 
     def step(self, max_norm, t, hp=HP, rows=None):
         """t2_adam_step over rows [r0, r1) (default: all), as FusedAdam calls it: a pointer to row r0 and those rows' chunks."""
         from tacotron2_subword_amd import _lib as L
         r0, r1 = rows or (0, self.n)
-        L.check(self.lib.t2_adam_step(self.tab.data_ptr() + 48 * r0, r1 - r0, int(self.first_chunk[r1] - self.first_chunk[r0]),
+        L.check(self.lib.t2_adam_step(L.adam_table(self.tab.data_ptr() + 48 * r0), r1 - r0, int(self.first_chunk[r1] - self.first_chunk[r0]),
                                       self.partial.data_ptr(), self.norm_out.data_ptr(), float(max_norm), hp["lr"], hp["b1"], hp["b2"],
                                       hp["eps"], hp["wd"], int(t), L.stream()))
 
