@@ -152,6 +152,19 @@ int t2_set_gemm_fold(int on);
 int t2_set_bn_fuse(int on);
 int t2_get_bn_fuse(void);
 int t2_bn_fuse_counts(uint64_t* out_host /* [3] */, int reset);
+/* 1 (default; env T2_DG_HANDOFF=0 turns it off): in bf16 mode, where t2_decoder_backward runs a persistent backward chain and
+ * the products behind it share one row-major bf16 copy of the chain's gate gradients dG, the chain stores those bf16 rows itself
+ * (round to nearest even, what the cast produces) at the head of the stream's own dG region of the backward workspace, writes
+ * no fp32 rows, and the cast of dG into the copy is not launched; the plan decides per pass (t2_decoder_pass_plan: dg_rows_d,
+ * dg_rows_a).  0: fp32 rows and the casts.  Every gradient has the same bits either way.
+ * t2_dg_handoff_counts: casts of a dG buffer since the last reset that [0] were skipped because the chain had stored the rows,
+ * [1] ran (host counters; a pass without a shared copy counts nothing). */
+int t2_set_dg_handoff(int on);
+int t2_get_dg_handoff(void);
+int t2_dg_handoff_counts(uint64_t* out_host /* [2] */, int reset);
+/* dst[row*K + k] (bf16) = src[row*ld + k] rounded to nearest even: the cast the library makes of an fp32 operand before a bf16
+ * product.  rows and K multiples of 64, ld a multiple of 4, both pointers 16-byte aligned. */
+int t2_stage_bf16(const float* src, long ld, void* dst, int rows, int K, void* stream);
 /* Makes `stream` wait for everything the library has queued on its internal side stream of the current device
  * (t2_decoder_bwd_args.defer_weight_grads). */
 int t2_side_join(void* stream);
@@ -506,11 +519,15 @@ int t2_chain_plan(const t2_chain_shape* shape, int direction, int cus, int claim
  * the chains run (ddin_ws: what a range's dDIN product works in; chunk_cast: dG is cast range by range), tail_scratch the
  * carve of the leaf tail (tail_share); dec_wgrads says where the decoder-LSTM weight gradients are issued (0 in the range
  * loop on chain B's stream, 1 on the tail's stream; dec_wgrads_staged: their dG copy is already filled), tail_on_side the
- * tail's stream, nsplit the position splits of the per-step attention backward, dq_parts the partials the tail folds. */
+ * tail's stream, nsplit the position splits of the per-step attention backward, dq_parts the partials the tail folds.
+ * env.dg_handoff (t2_set_dg_handoff), env.gemm_staging (t2_set_gemm_staging) and dg_rows_d / dg_rows_a: the decoder-LSTM chain /
+ * the attention chain stores its dG as bf16 rows at the head of bwd_layout.dgd / dga and dgas and the cast into the shared copy
+ * is skipped: the switch on, the chain on, chunk_cast / tail_share, and every product that reads that dG takes the copy (whole
+ * tiles, also of the products over B*T - B rows: B a multiple of 64); the carves are the same either way. */
 enum { T2_PASS_FORWARD = 0, T2_PASS_BACKWARD, T2_PASS_INFER };                                                       /* pass */
 enum { T2_PASS_MAX_BOUNDS = 64 };
 typedef struct t2_pass_env {
-    int precision, split_steps, chain, chain_bwd, overlap, cus, claimed, no_resident, saved_tiles;
+    int precision, split_steps, chain, chain_bwd, overlap, cus, claimed, no_resident, saved_tiles, dg_handoff, gemm_staging;
 } t2_pass_env;
 typedef struct t2_pass_chain {
     int asked, on, reason; const char* reason_text;          /* static strings */
@@ -531,6 +548,7 @@ typedef struct t2_decoder_pass_plan_info {
     int dec_wgrads, dec_wgrads_staged, tail_on_side, tail_share;
     t2_scratch_carve tail_scratch;
     int nsplit, lsa_chain, dq_parts;
+    int dg_rows_d, dg_rows_a;                                /* backward: a chain stores dG as bf16 rows, no cast (t2_set_dg_handoff) */
 } t2_decoder_pass_plan_info;
 int t2_decoder_pass_plan(const t2_dims* dims, int pass, int B, int T, int Tin, int Tsub, const t2_pass_env* env, int defer_weight_grads,
                          int poll_every, t2_decoder_pass_plan_info* out);

@@ -186,7 +186,7 @@ PASS_MAX_BOUNDS = 64                                    # T2_PASS_MAX_BOUNDS
 
 
 class PassEnv(C.Structure):
-    _fields_ = [(n, C.c_int) for n in ("precision", "split_steps", "chain", "chain_bwd", "overlap", "cus", "claimed", "no_resident", "saved_tiles")]
+    _fields_ = [(n, C.c_int) for n in ("precision", "split_steps", "chain", "chain_bwd", "overlap", "cus", "claimed", "no_resident", "saved_tiles", "dg_handoff", "gemm_staging")]
 
 
 class PassChain(C.Structure):
@@ -205,7 +205,7 @@ class DecoderPassPlanInfo(C.Structure):
                [("poison_words", C.c_int), ("poll", C.c_int), ("shadow_floats", C.c_size_t)] + \
                [(n, C.c_int) for n in ("defer", "share", "chunk_cast")] + [("ddin_ws_off", C.c_size_t), ("ddin_ws_bytes", C.c_size_t)] + \
                [(n, C.c_int) for n in ("dec_wgrads", "dec_wgrads_staged", "tail_on_side", "tail_share")] + [("tail_scratch", ScratchCarve)] + \
-               [(n, C.c_int) for n in ("nsplit", "lsa_chain", "dq_parts")]
+               [(n, C.c_int) for n in ("nsplit", "lsa_chain", "dq_parts", "dg_rows_d", "dg_rows_a")]
 
 
 class SoftDtwPlanInfo(C.Structure):
@@ -534,7 +534,7 @@ ABI_VERSION = 4
 
 # every symbol include/t2amd.h declares
 
-EXPORTS = ["t2_last_error", "t2_version", "t2_chain_status", "t2_chain_status_clear", "t2_debug_report_abort", "t2_debug_occupy", "t2_chain_claimed", "t2_set_precision", "t2_get_precision", "t2_gemm_counts", "t2_set_gemm_split_min_mflop", "t2_set_split_steps", "t2_get_split_steps", "t2_step_counts", "t2_set_overlap", "t2_set_chain", "t2_get_chain", "t2_set_chain_bwd", "t2_set_gemm_staging", "t2_set_gemm_fold", "t2_set_bn_fuse", "t2_get_bn_fuse", "t2_bn_fuse_counts", "t2_side_join", "t2_defer_counts", "t2_decoder_layout_query", "t2_decoder_forward", "t2_decoder_infer",
+EXPORTS = ["t2_last_error", "t2_version", "t2_chain_status", "t2_chain_status_clear", "t2_debug_report_abort", "t2_debug_occupy", "t2_chain_claimed", "t2_set_precision", "t2_get_precision", "t2_gemm_counts", "t2_set_gemm_split_min_mflop", "t2_set_split_steps", "t2_get_split_steps", "t2_step_counts", "t2_set_overlap", "t2_set_chain", "t2_get_chain", "t2_set_chain_bwd", "t2_set_gemm_staging", "t2_set_gemm_fold", "t2_set_bn_fuse", "t2_get_bn_fuse", "t2_bn_fuse_counts", "t2_set_dg_handoff", "t2_get_dg_handoff", "t2_dg_handoff_counts", "t2_stage_bf16", "t2_side_join", "t2_defer_counts", "t2_decoder_layout_query", "t2_decoder_forward", "t2_decoder_infer",
            "t2_decoder_bwd_layout_query", "t2_decoder_backward", "t2_decoder_pass_plan", "t2_prof_enable", "t2_prof_collect", "t2_adam_chunks", "t2_adam_step", "t2_adam_norm",
            "t2_conv_bn_forward", "t2_conv_bn_backward", "t2_embedding_forward", "t2_embedding_backward",
            "t2_lstm_seq_forward", "t2_lstm_seq_backward", "t2_lstm_seq_chain_ws_floats", "t2_gemm_ex", "t2_prof_gemm", "t2_gemm_plan", "t2_chain_plan", "t2_conv_handoff_plan", "t2_colsum", "t2_mask_btc",
@@ -611,6 +611,8 @@ def lib() -> C.CDLL:
         L.t2_step_counts.argtypes = [C.POINTER(C.c_uint64), C.c_int]
         L.t2_bn_fuse_counts.argtypes = [C.POINTER(C.c_uint64), C.c_int]
         L.t2_defer_counts.argtypes = [C.POINTER(C.c_uint64), C.c_int]
+        L.t2_dg_handoff_counts.argtypes = [C.POINTER(C.c_uint64), C.c_int]
+        L.t2_stage_bf16.argtypes = [C.c_void_p, C.c_long, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
         L.t2_set_gemm_split_min_mflop.argtypes = [C.c_int]
         L.t2_prof_collect.argtypes = [C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_int)]
         L.t2_finalize_bct.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_float, C.c_void_p]
@@ -979,7 +981,7 @@ def chain_plan(kind: str, backward: bool = False, *, cus: int = 256, claimed: bo
 
 def decoder_pass_plan(dims: Dims, kind: str, B: int, T: int, Tin: int, Tsub: int, *, defer_weight_grads: bool = False, poll_every: int = 0,
                       precision: str = "f32", split_steps: bool = False, chain: bool = True, chain_bwd: bool = True, overlap: bool = True,
-                      cus: int = 256, claimed: bool = True, no_resident: bool = False, saved_tiles: bool = False) -> dict:
+                      cus: int = 256, claimed: bool = True, no_resident: bool = False, saved_tiles: bool = False, dg_handoff: bool = True, gemm_staging: bool = True) -> dict:
     """What a decoder pass would do (t2_decoder_pass_plan: nothing is launched, no device needed, no claim taken).  kind:
     'forward', 'backward' or 'infer' (T = max_steps); the keyword arguments after poll_every are the environment, all of
     it explicit: the modes and switches in force are NOT read.  Returns every decision of the pass: the layouts, use16 /
@@ -987,7 +989,7 @@ def decoder_pass_plan(dims: Dims, kind: str, B: int, T: int, Tin: int, Tsub: int
     parts {name: (offset, bytes)}, and for the backward the tail's carve, where the decoder-LSTM weight gradients go and
     what the tail folds (include/t2amd.h has the fields)."""
     env = PassEnv(PRECISION_MODES[precision], int(split_steps), int(chain), int(chain_bwd), int(overlap), cus, int(claimed), int(no_resident),
-                  int(saved_tiles))
+                  int(saved_tiles), int(dg_handoff), int(gemm_staging))
     info = DecoderPassPlanInfo()
     check(lib().t2_decoder_pass_plan(C.byref(dims), PASS_KINDS[kind], B, T, Tin, Tsub, C.byref(env), int(defer_weight_grads), poll_every, C.byref(info)))
 
@@ -1007,7 +1009,8 @@ def decoder_pass_plan(dims: Dims, kind: str, B: int, T: int, Tin: int, Tsub: int
         out.update(bwd_layout=info.bwd_layout, defer=bool(info.defer), share=bool(info.share), chunk_cast=bool(info.chunk_cast),
                    ddin_ws=(info.ddin_ws_off, info.ddin_ws_bytes), dec_wgrads=("chain_b", "tail")[info.dec_wgrads],
                    dec_wgrads_staged=bool(info.dec_wgrads_staged), tail_on_side=bool(info.tail_on_side), tail_share=bool(info.tail_share),
-                   tail_scratch=carve_of(info.tail_scratch), nsplit=info.nsplit, lsa_chain=bool(info.lsa_chain), dq_parts=info.dq_parts)
+                   tail_scratch=carve_of(info.tail_scratch), nsplit=info.nsplit, lsa_chain=bool(info.lsa_chain), dq_parts=info.dq_parts,
+                   dg_rows_d=bool(info.dg_rows_d), dg_rows_a=bool(info.dg_rows_a))
     else:
         out.update(clear=("status", "teacher", "decode")[info.clear], saves_tiles=bool(info.saves_tiles), poison_words=info.poison_words)
     if kind == "infer":
@@ -1046,6 +1049,31 @@ def bn_fuse_counts(reset: bool = False):
     out = (C.c_uint64 * 3)()
     check(lib().t2_bn_fuse_counts(out, int(bool(reset))))
     return tuple(int(v) for v in out)
+
+
+def set_dg_handoff(on: bool) -> None:
+    """bf16 mode: the persistent backward chains store dG as bf16 rows and the casts into the shared copies are skipped
+    (default), or fp32 rows and the casts; the same bits either way (include/t2amd.h t2_set_dg_handoff)."""
+    check(lib().t2_set_dg_handoff(1 if on else 0))
+
+
+def get_dg_handoff() -> bool:
+    return bool(lib().t2_get_dg_handoff())
+
+
+def dg_handoff_counts(reset: bool = False):
+    """Casts of a dG buffer into its shared bf16 copy since the last reset: (skipped: the chain stored the rows, ran)."""
+    out = (C.c_uint64 * 2)()
+    check(lib().t2_dg_handoff_counts(out, int(bool(reset))))
+    return tuple(int(v) for v in out)
+
+
+def stage_bf16(src: torch.Tensor) -> torch.Tensor:
+    """The library's cast of a row-major fp32 matrix into a bf16 operand (t2_stage_bf16): [rows, K] -> [rows, K] bf16."""
+    rows, K = src.shape
+    out = torch.empty(rows, K, dtype=torch.bfloat16, device=src.device)
+    check(lib().t2_stage_bf16(ptr(src), src.stride(0), ptr(out), rows, K, stream()))
+    return out
 
 
 def defer_counts(reset: bool = False):

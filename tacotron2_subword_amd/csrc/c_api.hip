@@ -64,6 +64,8 @@ int g_chain_bwd = getenv("T2_CHAIN_BWD") ? atoi(getenv("T2_CHAIN_BWD")) : 1;   /
 uint64_t g_step_counts[6] = {0, 0, 0, 0, 0, 0};
 int counted(int rc, int base, int family) { if (rc == 0) ++g_step_counts[base + family]; return rc; }
 uint64_t g_defer_counts[2] = {0, 0};
+int g_dg_handoff = getenv("T2_DG_HANDOFF") ? atoi(getenv("T2_DG_HANDOFF")) != 0 : 1;   // backward chains leave dG as bf16 rows (chain_bwd.hip)
+uint64_t g_dg_cast_counts[2] = {0, 0};
 int g_split_steps = getenv("T2_SPLIT_STEPS") ? atoi(getenv("T2_SPLIT_STEPS")) != 0 : 0;   // split-bf16 recurrent steps (mode 2 only)
 int side_get(Side** out) {
     int dev = 0;
@@ -253,6 +255,17 @@ int t2_defer_counts(uint64_t* out_host, int reset) {
     T2_REQUIRE(out_host, "null argument");
     for (int i = 0; i < 2; ++i) { out_host[i] = g_defer_counts[i]; if (reset) g_defer_counts[i] = 0; }
     return 0;
+}
+int t2_set_dg_handoff(int on) { g_dg_handoff = on != 0; return 0; }
+int t2_get_dg_handoff(void) { return g_dg_handoff; }
+int t2_dg_handoff_counts(uint64_t* out_host, int reset) {
+    T2_REQUIRE(out_host, "null argument");
+    for (int i = 0; i < 2; ++i) { out_host[i] = g_dg_cast_counts[i]; if (reset) g_dg_cast_counts[i] = 0; }
+    return 0;
+}
+int t2_stage_bf16(const float* src, long ld, void* dst, int rows, int K, void* stream) {
+    T2_REQUIRE(src && dst, "null argument");
+    return stage_bf16(src, true, ld, static_cast<__bf16*>(dst), rows, K, (hipStream_t)stream);
 }
 int t2_side_join(void* stream) {
     Side* side = nullptr;

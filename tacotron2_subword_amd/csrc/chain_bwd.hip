@@ -11,8 +11,9 @@
 //       as one K-split partial (write-through, 16 B per lane) in the layout the consumer reads contiguously.
 //   P item (ug, rg): 16 hidden units x 32 batch rows, one (row, unit) per thread: sums the 8 K-split partials of dx(t+1)
 //       in fixed order, adds the direct gradient, dropout masks, gate derivatives; keeps dL/dc in a register across
-//       steps; publishes dg(t) as four bf16 MFMA fragments (one per gate) and stores the fp32 dg(t) rows the
-//       weight-gradient GEMMs read afterwards.
+//       steps; publishes dg(t) as four bf16 MFMA fragments (one per gate) and stores the dg(t) rows the weight-gradient
+//       GEMMs read afterwards: fp32, or (ChainBwdStream::dg16rows, where every such product reads a bf16 copy anyway) the
+//       fragment's own eight bf16 values per lane, untagged, as 16 bytes of a [T*B][4H] bf16 row — the copy itself, no cast.
 // Hand-offs: no arrival counters (round 3) — dg fragments and K-split partial words carry step tags (chain_common.h: step_tag,
 // tag_f32), the exchange buffers are cleared per launch, consumers load until the tags are this step's.  Two all-to-all hops
 // per step instead of two launches; numerics = the launch path (lstm.hip) up to summation order.
@@ -154,10 +155,10 @@ __global__ __launch_bounds__(NTH) void chain_bwd_lstm_kernel(ChainBwdDesc d) {
             for (int g = 0; g < 4; ++g) dgL[(g * 32 + (tid >> 4)) * (PU + 4) + (tid & 15)] = dgv[g];
             __syncthreads();
             // dg(t) as four bf16 fragments: gate g covers k tile (g*H + u0)/16; lane (row r, half hk) holds 8 units
+            bf16x8 o;                                                 // (untagged: the same eight values are the lane's piece of a bf16 row below)
             if (wave < 4) {
                 const float* hp = dgL + (wave * 32 + r) * (PU + 4) + hk * 8;
                 const f32x4 lo = *reinterpret_cast<const f32x4*>(hp), hi = *reinterpret_cast<const f32x4*>(hp + 4);
-                bf16x8 o;
 #pragma unroll
                 for (int j = 0; j < 4; ++j) { o[j] = (__bf16)lo[j]; o[4 + j] = (__bf16)hi[j]; }
                 u32x4 ow = __builtin_bit_cast(u32x4, o);
@@ -167,11 +168,19 @@ __global__ __launch_bounds__(NTH) void chain_bwd_lstm_kernel(ChainBwdDesc d) {
             }
             __syncthreads();                                          // (dgL is read; G's partial tiles alias it)
             if (*abortw) return;
-            {   // fp32 dg(t) rows for the weight-gradient GEMMs, then next step's operands (cold HBM rows) behind them
-                const int b = rt * 32 + (tv >> 4), u = u0 + (tv & 15);
-                if (b < B) {
-                    float* gp = S.dg + ((long)t * B + b) * K4 + u;
-                    gp[0] = dgv[0]; gp[H] = dgv[1]; gp[2 * H] = dgv[2]; gp[3 * H] = dgv[3];
+            {   // dg(t) rows for the weight-gradient GEMMs, then next step's operands (cold HBM rows) behind them.  dg16rows set
+                // (one scalar branch): the fragment lanes store their eight bf16 values, 16 bytes of row rt*32 + r at gate `wave`,
+                // and no fp32 row is written; else the fp32 rows, four dwords per thread
+                if (S.dg16rows) {
+                    const int w = tv >> 6, br = rt * 32 + (tv & 31);
+                    if (w < 4 && br < B)
+                        *reinterpret_cast<bf16x8*>(S.dg16rows + ((long)t * B + br) * K4 + w * H + u0 + 8 * ((tv >> 5) & 1)) = o;
+                } else {
+                    const int b = rt * 32 + (tv >> 4), u = u0 + (tv & 15);
+                    if (b < B) {
+                        float* gp = S.dg + ((long)t * B + b) * K4 + u;
+                        gp[0] = dgv[0]; gp[H] = dgv[1]; gp[2 * H] = dgv[2]; gp[3 * H] = dgv[3];
+                    }
                 }
                 if (t > d.t0) load_pin(t - 1, tv);
             }
@@ -974,10 +983,10 @@ __global__ __launch_bounds__(NTH) void chain_bwd_att_kernel(ChainBwdDesc d) {
 #pragma unroll
             for (int g = 0; g < 4; ++g) { dgL[(g * 32 + (tid >> 4)) * (PU + 4) + (tid & 15)] = dgv[g]; bacc[g] += dgv[g]; }
             __syncthreads();
+            bf16x8 o;                                                    // (untagged: the lane's piece of a bf16 row below)
             if (wave < 4) {
                 const float* hp = dgL + (wave * 32 + r) * (PU + 4) + hk * 8;
                 const f32x4 lo = *reinterpret_cast<const f32x4*>(hp), hi = *reinterpret_cast<const f32x4*>(hp + 4);
-                bf16x8 o;
 #pragma unroll
                 for (int j = 0; j < 4; ++j) { o[j] = (__bf16)lo[j]; o[4 + j] = (__bf16)hi[j]; }
                 u32x4 ow = __builtin_bit_cast(u32x4, o);
@@ -988,11 +997,17 @@ __global__ __launch_bounds__(NTH) void chain_bwd_att_kernel(ChainBwdDesc d) {
             T2_BSTAMP(6);
             __syncthreads();                                             // (no arrival counter: the fragments carry the step's tag)
             T2_BSTAMP(7);
-            {
-                const int b = rt * 32 + (tv >> 4), u = u0 + (tv & 15);
-                if (b < B) {
-                    float* gp = PS.dg + ((long)t * B + b) * K4 + u;
-                    gp[0] = dgv[0]; gp[H] = dgv[1]; gp[2 * H] = dgv[2]; gp[3 * H] = dgv[3];
+            {   // dg(t) rows for the weight-gradient GEMMs (as in chain_bwd_lstm_kernel): bf16 pieces from the fragment lanes, or fp32
+                if (PS.dg16rows) {
+                    const int w = tv >> 6, br = rt * 32 + (tv & 31);
+                    if (w < 4 && br < B)
+                        *reinterpret_cast<bf16x8*>(PS.dg16rows + ((long)t * B + br) * K4 + w * H + u0 + 8 * ((tv >> 5) & 1)) = o;
+                } else {
+                    const int b = rt * 32 + (tv >> 4), u = u0 + (tv & 15);
+                    if (b < B) {
+                        float* gp = PS.dg + ((long)t * B + b) * K4 + u;
+                        gp[0] = dgv[0]; gp[H] = dgv[1]; gp[2 * H] = dgv[2]; gp[3 * H] = dgv[3];
+                    }
                 }
                 if (t > d.t0) load_pin(t - 1, tv);
             }

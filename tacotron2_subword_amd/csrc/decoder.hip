@@ -114,7 +114,8 @@ bool saved_tiles_have(const void* ws) {
 // The one reader of the process and the device for a pass plan: the mode and the switches in force, for a backward pass
 // whether its forward workspace holds saved tiles (fwd_ws), and, for a pass that will run (device), chain_env() without the claim
 PassEnv pass_env_here(const void* fwd_ws, bool device) {
-    PassEnv env{get_precision(), g_split_steps != 0, g_chain != 0, g_chain_bwd != 0, g_overlap != 0, ChainEnv{0, false, false}, fwd_ws && saved_tiles_have(fwd_ws)};
+    PassEnv env{get_precision(), g_split_steps != 0, g_chain != 0, g_chain_bwd != 0, g_overlap != 0, ChainEnv{0, false, false}, fwd_ws && saved_tiles_have(fwd_ws),
+                g_dg_handoff != 0, gemm_env_here().stage, gemm_env_here().tiles256};
     if (device && env.chain) env.chain_env = chain_env(false);
     return env;
 }
@@ -519,8 +520,26 @@ struct Bwd {
     // a part of the GEMM scratch (ScratchCarve, decoder_plan.h): its address, a product working in it, a carve's dG copy
     unsigned char* scratch(size_t off) const { return reinterpret_cast<unsigned char*>(a.bws + BL.gemm_ws) + off; }
     GemmDesc in(const ScratchPart& part, GemmDesc m) const { m.ws = reinterpret_cast<float*>(scratch(part.off)); m.ws_bytes = part.bytes; return m; }
-    Dg16 dg16(const ScratchCarve& cv, int H4) const {
-        return Dg16{cv.dg16.bytes != 0, reinterpret_cast<__bf16*>(scratch(cv.dg16.off)), H4, reinterpret_cast<float*>(scratch(cv.rest.off)), cv.rest.bytes};
+    // rows: the dG region whose head holds the bf16 rows a chain stored (BwdPlan::dg_rows_d / dg_rows_a) — they are the copy
+    // then, and the carve's own part stays unused so that the products keep their scratch; null: the carve's copy
+    Dg16 dg16(const ScratchCarve& cv, int H4, const float* rows = nullptr) const {
+        __bf16* p = rows ? reinterpret_cast<__bf16*>(const_cast<float*>(rows)) : reinterpret_cast<__bf16*>(scratch(cv.dg16.off));
+        return Dg16{cv.dg16.bytes != 0, p, H4, reinterpret_cast<float*>(scratch(cv.rest.off)), cv.rest.bytes};
+    }
+    // a cast of dG into its shared copy, or its place where a chain stored the rows (t2_dg_handoff_counts)
+    int dg_cast(bool stored, const float* src, const Dg16& dg, long row0, int rows, hipStream_t st) const {
+        ++g_dg_cast_counts[stored ? 0 : 1];
+        return stored ? 0 : stage_bf16(src + row0 * dg.H4, true, dg.H4, dg.p + row0 * dg.H4, rows, (int)dg.H4, st);
+    }
+    // a product that reads dG.  stored: the fp32 rows do not exist, so a product that would not take the copy is an error (the
+    // plan has asked plan_gemm about each of them: BwdPlan::dg_rows_d / dg_rows_a)
+    int dg_gemm(bool stored, const GemmDesc& m, hipStream_t st) const {
+        if (stored) {
+            GemmPlan gp;
+            T2_TRY(gemm_plan(m, &gp));
+            T2_REQUIRE(gp.a.src == GemmSrc::caller, "t2_decoder_backward: a product over dG (M=%d N=%d K=%d) does not take the bf16 rows the chain stored", m.M, m.N, m.K);
+        }
+        return gemm(m, st);
     }
     StreamRef st[2]{}; BwdStreamRef bst[2]{};
     // the reverse-time chains of this pass (bwd_chains): descriptors of the persistent ones, side stream, next free event slot
@@ -582,6 +601,7 @@ ChainBwdDesc chain_b_bwd_desc(const Bwd& c) {
     st.dh1 = c.S(c.BL.ddout); st.lddh1 = z.WO;
     st.gates = c.W(c.L.gd); st.c_new = c.W(c.L.cnd); st.c_out = c.W(c.L.cd);
     st.dg = c.S(c.BL.dgd); st.dc_state = c.S(c.BL.dcd);
+    if (c.p.dg_rows_d) st.dg16rows = c.S16(c.BL.dgd);
     st.dbias_part = c.S(c.BL.partd);                                 // (the launch path's K-split scratch: idle when the chain runs) [MT][4Hd]
     st.site_h = T2_SITE_DEC_H; st.site_c = T2_SITE_DEC_C;
     d.err = status_words(c.a.ws, c.L) + CHAIN_STATUS_BWD_LSTM;
@@ -603,6 +623,7 @@ ChainBwdDesc chain_a_bwd_desc(const Bwd& c) {
         st.dh1 = c.S(c.BL.ddin) + r.hoff; st.lddh1 = z.WD;
         st.gates = c.W(r.ga); st.c_new = c.W(r.cna); st.c_out = c.W(r.ca);
         st.dg = c.S(b.dg); st.dc_state = c.S(b.dc);
+        if (c.p.dg_rows_a) st.dg16rows = c.S16(b.dg);
         st.dbias_part = c.S(c.BL.parta) + (size_t)s * 2 * 4 * z.Ha;     // [MT][4Ha] per stream (the launch path's K-split scratch)
         st.site_h = r.site_h; st.site_c = r.site_c;
         st.dctx_a = c.S(c.BL.ddout) + r.ctx2off; st.lddctx_a = z.WO;
@@ -843,14 +864,14 @@ int bwd_dec_lstm_wgrads(const Bwd& c, hipStream_t sb) {
     const Sizes& z = c.z; const t2_decoder_layout& L = c.L;
     const int BT = z.B * z.T;
     const float* DG = c.S(c.BL.dgd);
-    const Dg16 dg = c.dg16(c.p.scratch, 4 * z.Hd);
-    if (dg.on && !c.p.dec_wgrads_staged) T2_TRY(stage_bf16(DG, true, 4 * z.Hd, dg.p, BT, 4 * z.Hd, sb));
+    const Dg16 dg = c.dg16(c.p.scratch, 4 * z.Hd, c.p.dg_rows_d ? DG : nullptr);
+    if (dg.on && !c.p.dec_wgrads_staged) T2_TRY(c.dg_cast(false, DG, dg, 0, BT, sb));
     // dW_ih = dG^T . DIN (bf16 steps: the forward pass left DIN's bf16 shadow) ; recurrent half: dW_hh = dG^T . dec_h(t-1)
     GemmDesc mih = dg.wgrad(matmul_tn(c, DG, 4 * z.Hd, c.W(L.din), z.WD, c.g.dec.w_ih, z.WD, 4 * z.Hd, z.WD, BT), 0);
     if (dg.on && c.p.use16) { mih.B16 = c.W16(L.din16); mih.ldb16 = z.WD; mih.b16_kmajor = 1; }
-    T2_TRY(gemm(mih, sb));
+    T2_TRY(c.dg_gemm(c.p.dg_rows_d, mih, sb));
     // h(t-1) pairs with dG(t): drop the first step's rows of dG and the last step's rows of dec_h
-    if (z.T > 1) T2_TRY(gemm(dg.wgrad(matmul_tn(c, DG + (long)z.B * 4 * z.Hd, 4 * z.Hd, c.W(L.dout), z.WO, c.g.dec.w_hh, z.Hd, 4 * z.Hd, z.Hd, BT - z.B), z.B), sb));
+    if (z.T > 1) T2_TRY(c.dg_gemm(c.p.dg_rows_d, dg.wgrad(matmul_tn(c, DG + (long)z.B * 4 * z.Hd, 4 * z.Hd, c.W(L.dout), z.WO, c.g.dec.w_hh, z.Hd, 4 * z.Hd, z.Hd, BT - z.B), z.B), sb));
     else T2_TRY(fill_f32(c.g.dec.w_hh, 0.f, (size_t)4 * z.Hd * z.Hd, sb));
     if (c.p.chain_b.on) {                                             // the chain summed dG over steps and rows: add the row tiles
         T2_TRY(batch_sum(c.cbb.st[0].dbias_part, (z.B + 31) / 32, 4 * z.Hd, c.g.dec.b_ih, sb));
@@ -879,7 +900,7 @@ int bwd_chains(Bwd& c) {
     // bf16 copy of dG behind it serves the dDIN product of each range and the two weight-gradient products
     __bf16* const wt16 = reinterpret_cast<__bf16*>(c.scratch(p.scratch.w_ih16.off));
     if (p.pre16) T2_TRY(stage_bf16(c.w.dec.w_ih, false, z.WD, wt16, z.WD, 4 * z.Hd, sb));
-    const Dg16 dg = c.dg16(p.scratch, 4 * z.Hd);
+    const Dg16 dg = c.dg16(p.scratch, 4 * z.Hd, p.dg_rows_d ? DGd : nullptr);
     for (size_t ci = bounds.size() - 1; ci > 0; --ci) {
         const int t0 = bounds[ci - 1], t1 = bounds[ci];
         if (p.chain_b.on) {
@@ -893,11 +914,11 @@ int bwd_chains(Bwd& c) {
                                 (t1 - t0) * z.B, z.WD, 4 * z.Hd);
         dd = c.in(p.ddin_ws, dd);                                         // between fork and join the scratch is chain B's
         if (p.pre16) { dd.B16 = wt16; dd.ldb16 = 4 * z.Hd; }
-        if (p.chunk_cast) {                                               // dG of the range cast in front of its dDIN product
-            T2_TRY(stage_bf16(DGd + c.R(t0) * 4 * z.Hd, true, 4 * z.Hd, dg.p + c.R(t0) * 4 * z.Hd, (t1 - t0) * z.B, 4 * z.Hd, sb));
+        if (p.chunk_cast) {                                               // dG of the range cast in front of its dDIN product (or stored by the chain)
+            T2_TRY(c.dg_cast(p.dg_rows_d, DGd, dg, c.R(t0), (t1 - t0) * z.B, sb));
             dd = dg.igrad(dd, c.R(t0));
         }
-        T2_TRY(gemm(dd, sb));
+        T2_TRY(c.dg_gemm(p.dg_rows_d, dd, sb));
         if (p.overlap) T2_TRY(stream_edge(*c.side, c.ne++, sb, c.s));
         if (t0 == 0 && p.dec_wgrads == WGRADS_CHAIN_B) T2_TRY(bwd_dec_lstm_wgrads(c, sb));
         if (p.chain_a.on) {
@@ -927,13 +948,13 @@ int bwd_stream_tail(const Bwd& c, int s, hipStream_t ts) {
     // the head of the scratch) is the k-major A operand of the three weight-gradient products (the shifted ones start
     // B rows in) and the K-contiguous A operand of the prenet's input gradient below; the ctx / h operands are read
     // from DIN's bf16 shadow where the forward pass left one
-    const Dg16 dg = c.dg16(c.p.tail_scratch, 4 * z.Ha);
-    if (dg.on) T2_TRY(stage_bf16(DG, true, 4 * z.Ha, dg.p, BT, 4 * z.Ha, ts));
+    const Dg16 dg = c.dg16(c.p.tail_scratch, 4 * z.Ha, c.p.dg_rows_a ? DG : nullptr);
+    if (dg.on) T2_TRY(c.dg_cast(c.p.dg_rows_a, DG, dg, 0, BT, ts));
     const __bf16* DIN16 = dg.on && c.p.use16 ? c.W16(L.din16) : nullptr;
     auto dw_gemm = [&](const float* G, long row0, const float* X, const __bf16* X16, long ldx, float* Y, long ldy, int N, int K) -> int {
         GemmDesc m = dg.wgrad(matmul_tn(c, G, 4 * z.Ha, X, ldx, Y, ldy, 4 * z.Ha, N, K), row0);
         if (X16) { m.B16 = X16; m.ldb16 = ldx; m.b16_kmajor = 1; }
-        return gemm(m, ts);
+        return c.dg_gemm(c.p.dg_rows_a, m, ts);
     };
     T2_TRY(dw_gemm(DG, 0, P2, nullptr, z.P, lg.w_ih, ldw, z.P, BT));
     if (z.T > 1) {
@@ -953,7 +974,7 @@ int bwd_stream_tail(const Bwd& c, int s, hipStream_t ts) {
     // prenet (model.py:13-24): dP2 = dG . W_ih[:, :P] ; through ReLU+dropout ; layer 2 ; layer 1
     const float scale = c.a.prenet_dropout ? 1.0f / (1.0f - c.d.p_prenet_dropout) : 1.0f;
     const GemmDesc gp = c.in(c.p.tail_scratch.whole(), matmul_nn(DG, 4 * z.Ha, r.lw->w_ih, ldw, dP2, z.P, BT, z.P, 4 * z.Ha));
-    T2_TRY(gemm(dg.igrad(gp, 0), ts));
+    T2_TRY(c.dg_gemm(c.p.dg_rows_a, dg.igrad(gp, 0), ts));
     T2_TRY(relu_drop_bwd(dP2, P2, dP2, scale, (size_t)BT * z.P, ts));
     T2_TRY(gemm(matmul_tn(c, dP2, z.P, P1, z.P, b.prenet_w2, z.P, z.P, z.P, BT), ts));
     T2_TRY(gemm(matmul_nn(dP2, z.P, r.prenet_w2, z.P, dP1, z.P, BT, z.P, z.P), ts));
@@ -1122,7 +1143,8 @@ int t2_decoder_pass_plan(const t2_dims* dims_in, int pass, int B, int T, int Tin
     T2_TRY(entry_dims(*dims_in, &d, &max_pos));
     T2_REQUIRE(B >= 1 && B <= 256 && T >= 1 && Tin >= 1 && Tsub >= 1, "bad shape B=%d T=%d Tin=%d Tsub=%d", B, T, Tin, Tsub);
     const PassEnv env{e->precision, e->split_steps != 0, e->chain != 0, e->chain_bwd != 0, e->overlap != 0,
-                      ChainEnv{e->cus, e->claimed != 0, e->no_resident != 0}, e->saved_tiles != 0};
+                      ChainEnv{e->cus, e->claimed != 0, e->no_resident != 0}, e->saved_tiles != 0, e->dg_handoff != 0,
+                      e->gemm_staging != 0, gemm_env_here().tiles256};
     const Sizes z = sizes_of(d, B, T, Tin, Tsub);
     t2_decoder_pass_plan_info o{};
     if (pass == T2_PASS_BACKWARD) {
@@ -1135,6 +1157,7 @@ int t2_decoder_pass_plan(const t2_dims* dims_in, int pass, int B, int T, int Tin
         o.dec_wgrads = p.dec_wgrads; o.dec_wgrads_staged = p.dec_wgrads_staged; o.tail_on_side = p.tail_on_side;
         o.tail_share = p.tail_share; o.tail_scratch = carve_info(p.tail_scratch);
         o.nsplit = p.nsplit; o.lsa_chain = p.lsa_chain; o.dq_parts = p.dq_parts;
+        o.dg_rows_d = p.dg_rows_d; o.dg_rows_a = p.dg_rows_a;
     } else {
         const DecPlan p = pass == T2_PASS_FORWARD ? plan_decoder_fwd(d, z, env) : plan_decoder_infer(d, z, env, poll_every);
         o.layout = p.L; o.use16 = p.use16; o.split = p.split; o.pre16 = p.pre16;

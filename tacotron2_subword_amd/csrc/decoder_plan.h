@@ -24,6 +24,8 @@ struct PassEnv {
     bool chain, chain_bwd, overlap;          // t2_set_chain, t2_set_chain_bwd, t2_set_overlap
     ChainEnv chain_env;
     bool saved_tiles;                        // backward: the forward workspace holds the LSA chain's tanh tiles and location features
+    bool dg_handoff;                         // t2_set_dg_handoff: the backward chains may leave dG as bf16 rows
+    bool gemm_staging, gemm_tiles256;        // t2_set_gemm_staging, T2_GEMM_256: what plan_gemm is asked with (which products take a copy of dG)
 };
 
 // Decode loop, bf16-operand mode: whole-cell weight shadows [W_hh | W_ih[:,P:] | W_ih[:,:P]] (attention LSTMs) and
@@ -114,6 +116,12 @@ struct BwdPlan {
     int nsplit;                                      // position splits of the per-step attention backward
     bool lsa_chain; int dq_parts;                    // partials per dq row / per accumulator that the tail folds
     bool dca_acc_fits;                               // DCA: the per-item accumulators' sum fits the scratch
+    // dG hand-off: a persistent chain writes dG as bf16 rows [BT][4H] at the head of the stream's own dG region (BL.dgd / dga /
+    // dgas) in place of the fp32 rows; the shared copy is then that region, its cast is skipped, and the carves stay as they are
+    // Only where EVERY product that reads that dG takes the copy (plan_gemm: whole tiles, K % 64 — also of the shifted products,
+    // K = B*T - B, so B % 64 == 0 — and both operands k-major for the 256-tile weight gradients): a product that ignores the copy
+    // reads the fp32 rows, which are then not there
+    bool dg_rows_d, dg_rows_a;                       // decoder LSTM (chain B, chunk_cast) / both attention streams (chain A, tail_share)
 };
 BwdPlan plan_decoder_bwd(const t2_dims& d, const Sizes& z, const PassEnv& env, bool defer_weight_grads);
 

@@ -2,6 +2,7 @@
 // the decisions recorded before this file existed (tests/golden/decoder_pass_plans.jsonl).  Every rule of a pass is stated
 // here once; where two rules look alike and differ (the two pre16 conditions, the decode loop's use16), both are kept and named.
 #include <algorithm>
+#include <cstdint>
 
 #include "decoder_plan.h"
 
@@ -37,6 +38,25 @@ ChainShape lstm_chain_shape(const Sizes& z, size_t ws_floats) {
     ChainShape s{};
     s.kind = CHAIN_LSTM; s.NS = 1; s.B = z.B; s.H = z.Hd; s.ws_bytes = ws_floats * sizeof(float);
     return s;
+}
+
+// Does a product take the shared bf16 copy of dG ([rows][H4], row-major) as its A operand?  The descriptor is the one the drivers
+// build (decoder.hip: bwd_chains, bwd_dec_lstm_wgrads, bwd_stream_tail), with stand-in addresses — plan_gemm reads their
+// alignment only — and the scratch behind the copy; the answer is plan_gemm's, so the rule is stated there and nowhere else.
+//   weight gradient dW[H4][N] = dG^T . X, K = rows: the copy is its k-major A operand; X[rows][ldx] fp32, or (x16) its bf16 shadow
+//   input gradient  dX[rows][N] = dG . W, K = H4: the copy is its K-contiguous A operand; W fp32 [H4][ldx], or (x16) W^T as bf16 [N][H4]
+bool takes_dg_copy(const PassEnv& env, bool wgrad, int rows, int H4, int N, long ldx, bool x16, const ScratchPart& ws) {
+    if (rows <= 0) return true;                                       // (no such product)
+    const float* at = reinterpret_cast<const float*>((uintptr_t)4096);
+    GemmDesc m = gemm_desc();
+    m.A = at; m.B = at; m.C = const_cast<float*>(at); m.ldc = N;
+    m.A16 = reinterpret_cast<const __bf16*>(at); m.lda16 = H4; m.a16_kmajor = wgrad;
+    m.sbn = 1; m.sbk = ldx; m.N = N;
+    if (wgrad) { m.sam = 1; m.sak = H4; m.M = H4; m.K = rows; }
+    else { m.sam = H4; m.sak = 1; m.M = rows; m.K = H4; }
+    if (x16) { m.B16 = reinterpret_cast<const __bf16*>(at); m.ldb16 = wgrad ? ldx : H4; m.b16_kmajor = wgrad; }
+    m.ws = const_cast<float*>(at); m.ws_bytes = ws.bytes;
+    return plan_gemm(m, GemmEnv{env.precision, env.gemm_staging, env.gemm_tiles256, 0.0}).a.src == GemmSrc::caller;
 }
 
 }  // namespace
@@ -304,6 +324,25 @@ BwdPlan plan_decoder_bwd(const t2_dims& d, const Sizes& z, const PassEnv& env, b
     p.lsa_chain = p.chain_a.on && lsa;                              // the persistent LSA backward: one partial per position split
     p.dq_parts = p.lsa_chain ? 2 : p.nsplit;
     p.dca_acc_fits = d.attention_kind != T2_ATTN_DCA || dca_acc_floats(z.A) * sizeof(float) <= total;
+    // ---- dG hand-off: where a persistent chain produces dG and its only reader would be the cast into the shared copy (the
+    // bias gradients are the chain's own), the chain stores the bf16 rows itself, at the head of the stream's fp32 dG region
+    // (half of it: no product's scratch moves, so every product keeps its kernel, split-K factor and K chunks).  Not in the
+    // carve: chain A runs while the decoder LSTM's copy is still needed, and the two tails share one carve.  Every other case
+    // (no shared copy, a chain off or refused, per-step launches, fp32 and split-bf16 modes) keeps the fp32 rows and the casts
+    // ... and only where no product is left that reads the fp32 rows: each must take the copy (a product that is no whole number
+    // of tiles, or a shifted one whose K = BT - B is no multiple of 64, ignores it and converts the fp32 operand itself)
+    const int H4d = 4 * z.Hd, H4a = 4 * z.Ha, shifted = (int)BT - z.B;
+    bool all_d = true, all_a = true;
+    for (size_t ci = 1; ci < p.bounds.size(); ++ci)                   // dDIN of each range, then dW_ih and dW_hh
+        all_d = all_d && takes_dg_copy(env, false, (p.bounds[ci] - p.bounds[ci - 1]) * z.B, H4d, z.WD, z.WD, p.pre16, p.scratch.rest);
+    all_d = all_d && takes_dg_copy(env, true, (int)BT, H4d, z.WD, z.WD, p.use16, p.scratch.rest) &&
+            takes_dg_copy(env, true, shifted, H4d, z.Hd, z.WO, false, p.scratch.rest);
+    all_a = takes_dg_copy(env, true, (int)BT, H4a, z.P, z.P, false, p.tail_scratch.rest) &&
+            takes_dg_copy(env, true, shifted, H4a, z.E, z.WD, p.use16, p.tail_scratch.rest) &&
+            takes_dg_copy(env, true, shifted, H4a, z.Ha, z.WD, p.use16, p.tail_scratch.rest) &&
+            takes_dg_copy(env, false, (int)BT, H4a, z.P, z.P + z.E, false, p.tail_scratch.rest);
+    p.dg_rows_d = env.dg_handoff && p.chain_b.on && p.chunk_cast && all_d;
+    p.dg_rows_a = env.dg_handoff && p.chain_a.on && p.tail_share && all_a;
     return p;
 }
 

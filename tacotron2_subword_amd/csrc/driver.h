@@ -32,8 +32,8 @@ int stream_edge(Side& sd, size_t i, hipStream_t from, hipStream_t to);      // r
 struct StopPoll { hipEvent_t ev[4] = {}; int32_t* host = nullptr; };
 int stop_poll_get(StopPoll** out);
 
-// Switches (t2_set_overlap, t2_set_chain, t2_set_chain_bwd, t2_set_split_steps)
-extern int g_overlap, g_chain, g_chain_bwd, g_split_steps;
+// Switches (t2_set_overlap, t2_set_chain, t2_set_chain_bwd, t2_set_split_steps, t2_set_dg_handoff)
+extern int g_overlap, g_chain, g_chain_bwd, g_split_steps, g_dg_handoff;
 
 // per-step LSTM launches of the decoder drivers since the last reset (t2_step_counts): forward step {exact, bf16, split},
 // recurrent-input gradient {exact, bf16, split}, as the launchers report them
@@ -42,5 +42,9 @@ int counted(int rc, int base, int family);
 
 // t2_decoder_backward calls since the last reset (t2_defer_counts): [0] tail left on the side stream, [1] finished on the caller's
 extern uint64_t g_defer_counts[2];
+
+// casts of a dG buffer into its shared bf16 copy since the last reset (t2_dg_handoff_counts): [0] skipped, the chain stored
+// the bf16 rows itself, [1] ran
+extern uint64_t g_dg_cast_counts[2];
 
 }  // namespace t2

@@ -26,6 +26,10 @@ static double g_split_min_flop = 1e6 * kSplitMinMflopDefault;
 void set_gemm_split_min_mflop(int mflop) { g_split_min_flop = 1e6 * (mflop < 0 ? kSplitMinMflopDefault : mflop); }
 void set_precision(int p) { g_precision = p; }
 int get_precision() { return g_precision; }
+GemmEnv gemm_env_here() {
+    static const int t256 = env_int("T2_GEMM_256", 1);
+    return GemmEnv{g_precision, g_stage != 0, t256 != 0, g_split_min_flop};
+}
 // calls of gemm() by kernel family: exact fp32, converting bf16, bf16-source on single-bf16 operands, bf16-source on split operands
 static uint64_t g_counts[4] = {0, 0, 0, 0};
 void gemm_counts(uint64_t* out, int reset) {
@@ -154,7 +158,9 @@ const char* gemm_plan_name(const GemmPlan& p) {
     return names[(int)p.kernel + (p.split ? 3 : 0)];
 }
 
-GemmPlan plan_gemm(const GemmDesc& d) {
+GemmPlan plan_gemm(const GemmDesc& d) { return plan_gemm(d, gemm_env_here()); }
+
+GemmPlan plan_gemm(const GemmDesc& d, const GemmEnv& e) {
     GemmPlan p{};
     const bool conv_any = d.conv_a || d.conv_b;
     const bool akc = d.conv_a || d.sak == 1, bkc = !d.conv_b && d.sbk == 1;   // K is the contiguous stride (conv: A's frames are rows, B's are k-rows)
@@ -166,21 +172,20 @@ GemmPlan plan_gemm(const GemmDesc& d) {
 
     // bf16-operand mode: large GEMMs only (both extents >= 64), conv operands need C % 8 == 0
     const bool large = !d.fp32_only && d.M >= 64 && d.N >= 64 && d.K >= 64 && (!conv_any || d.conv_C % 8 == 0);
-    const bool use_bf16 = g_precision == 1 && large;
+    const bool use_bf16 = e.precision == 1 && large;
     // split-bf16 mode: only the bf16-source kernels, on operands staged as hi / lo parts (K' = 3K, see the staging casts of gemm.hip);
     // whatever does not qualify for them below runs exactly what mode 0 runs.  Single-bf16 copies from the caller are not
     // used; split16 marks copies that are already in the split layout of this product (t2_prof_gemm).
-    const bool want_split = g_precision == 2 && large && 2.0 * d.M * d.N * d.K >= g_split_min_flop;
+    const bool want_split = e.precision == 2 && large && 2.0 * d.M * d.N * d.K >= e.split_min_flop;
     const int kmul = want_split ? 3 : 1;
-    const bool copies = g_precision != 2 || (want_split && d.split16);
+    const bool copies = e.precision != 2 || (want_split && d.split16);
     bool a_caller = copies && d.A16, b_caller = copies && d.B16;
     // 256 x 256 tiles (gemm_bf16src256_kernel) when the staged operands are whole 256-tiles and K splits into an even
     // number of 64-wide K-tiles.  Its k-major variant reads both operands as they lie in memory when BOTH are k-major
     // (the weight-gradient products): they are staged by the plain cast, [K][M] and [K][N]; an implicit-conv B operand
     // is then the bf16 copy of the frames [K][C] alone.  A bf16 copy the caller hands over in the layout the product
     // does not take is ignored (the fp32 operand is staged instead).
-    static const int g_t256 = env_int("T2_GEMM_256", 1);
-    const bool shape256 = g_t256 && d.M % 256 == 0 && d.N % 256 == 0 && d.K >= 128;
+    const bool shape256 = e.tiles256 && d.M % 256 == 0 && d.N % 256 == 0 && d.K >= 128;
     const long ld_km = std::max(std::max((long)d.M, a_caller && d.a16_kmajor ? d.lda16 : 0l), std::max((long)(d.conv_b ? d.conv_C : d.N), b_caller && d.b16_kmajor ? d.ldb16 : 0l));
     const bool km = shape256 && !akc && !bkc && !d.conv_a && (!d.conv_b || d.conv_C % 256 == 0) && (long)d.K * kmul * ld_km * 2 < (1l << 31);
     a_caller = a_caller && (d.a16_kmajor != 0) == km;
@@ -196,7 +201,7 @@ GemmPlan plan_gemm(const GemmDesc& d) {
     // pays when each staged element is reused by many tiles, i.e. when both extents are large
     bool staged = false;
     size_t ws_bytes = d.ws_bytes;                           // what is left for the split-K partials
-    if ((use_bf16 || want_split) && g_stage && conv_ok && d.batch == 1 && d.M % 128 == 0 && d.N % 128 == 0 && d.K % 64 == 0) {
+    if ((use_bf16 || want_split) && e.stage && conv_ok && d.batch == 1 && d.M % 128 == 0 && d.N % 128 == 0 && d.K % 64 == 0) {
         // implicit-conv operands: only the frames [rows][C] are staged (the kernel shifts rows per tap)
         const size_t a_elems = d.conv_a ? (size_t)d.M * d.conv_C : (size_t)d.M * d.K;
         const size_t b_elems = d.conv_b ? (size_t)d.K * d.conv_C : (size_t)d.N * d.K;

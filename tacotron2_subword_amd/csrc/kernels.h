@@ -80,6 +80,10 @@ struct GemmPlan {
 // T2_GEMM_256), touches no device.  The descriptor must have passed gemm()'s checks: gemm_plan() runs them first and
 // returns what gemm() would return for a descriptor it refuses.
 GemmPlan plan_gemm(const GemmDesc& d);
+// ... and the same with the switches as an argument: what another pure plan asks (decoder_plan.hip).  gemm_env_here: those in force
+struct GemmEnv { int precision; bool stage, tiles256; double split_min_flop; };   // mode, t2_set_gemm_staging, T2_GEMM_256, split threshold in FLOP
+GemmEnv gemm_env_here();
+GemmPlan plan_gemm(const GemmDesc& d, const GemmEnv& e);
 int gemm_plan(const GemmDesc& d, GemmPlan* out);
 // The hand-over rule for bf16 copies a caller could write itself instead of letting gemm() cast them (conv.hip).  `plain` is
 // the product without copies, `offered` the same product with the copies in A16 / B16 and the scratch it would be left
@@ -333,6 +337,7 @@ struct ChainBwdStream {
     const float* dh1; long lddh1;         // direct gradient on h_out(t): dh1[(t*B + b)*lddh1 + u]
     const float* gates; const float* c_new; const float* c_out;   // saved by the forward pass: [T][B][4H], [T][B][H] x2
     float* dg;                            // out: gate pre-activation gradients [T][B][4H]
+    __bf16* dg16rows;                     // set: dg leaves as bf16 rows [T][B][4H] (what the products read) and the fp32 rows are not written
     float* dc_state;                      // [B][H] dL/dc carried between launches of one pass (chunked ranges)
     float* dbias_part;                    // [row tiles][4H] sum over steps and the tile's rows of dg: the bias gradients (nullable)
     uint32_t site_h, site_c;

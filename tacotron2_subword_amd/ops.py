@@ -164,11 +164,12 @@ def side_join() -> None:
 
 def decoder_backward(W: L.DecoderWeights, P: dict, dims: L.Dims, dp: DecoderPass, memory, memory_sub, d_mel, d_gate, *,
                      training: bool, prenet_dropout: bool, seed: int, d_align=None, d_align_sub=None, prefix="decoder.",
-                     defer: Optional[list] = None):
+                     defer: Optional[list] = None, bws: Optional[torch.Tensor] = None):
     """Backward of decoder_forward.  P: the (reference-keyed) weight dict, used for gradient shapes.
     Returns (grads dict keyed like P, d_memory, d_memory_sub).  defer: a list -> the weight gradients are left on the
     library's side stream (d_memory* are complete on the current stream); the tensors that stream still uses are appended
-    to the list and the caller must call side_join() before reading a gradient or dropping the list."""
+    to the list and the caller must call side_join() before reading a gradient or dropping the list.
+    bws: the backward workspace to work in (fp32, at least decoder_bwd_layout().total_floats; tests look into it), else a fresh one."""
     check_chain_status()
     dp.check_precision("decoder_backward")
     single = dims.n_streams == 1
@@ -176,7 +177,9 @@ def decoder_backward(W: L.DecoderWeights, P: dict, dims: L.Dims, dp: DecoderPass
     G = {prefix + k: torch.empty_like(P[prefix + k]) for k in L.decoder_param_keys(dims.attention_kind, single)}
     GS = L.decoder_grads(G, prefix, single, dims.attention_kind)
     bl = L.decoder_bwd_layout(dims, dp.B, dp.T, dp.Tin, dp.Tsub)
-    bws = torch.empty(bl.total_floats, dtype=torch.float32, device=dev)
+    if bws is None:
+        bws = torch.empty(bl.total_floats, dtype=torch.float32, device=dev)
+    assert bws.dtype == torch.float32 and bws.is_contiguous() and bws.numel() >= bl.total_floats and bws.device == dev
     d_mem = torch.empty_like(memory)
     d_mem_sub = None if single else torch.empty_like(memory_sub)
     a = L.DecoderBwdArgs(dp.B, dp.T, dp.Tin, dp.Tsub, L.ptr(memory), L.ptr(memory_sub), L.ptr(dp.align), L.ptr(dp.align_sub),
