@@ -846,6 +846,84 @@ typedef struct t2_vocoder_conv_ragged_args {
 } t2_vocoder_conv_ragged_args;
 int t2_vocoder_conv_ragged(const t2_vocoder_conv_ragged_args* a, void* stream);
 
+/* ---- HiFi-GAN generator, training ------------------------------------------------------------------
+ * The backward of hifigan_infer/hifigan_model.py: Generator.forward (:100-116), ResBlock1.forward (:35-42) and
+ * ResBlock2.forward (:63-68), which the reference leaves to torch's autograd, and a forward that keeps what it reads.  Same
+ * layouts, limits and arithmetic as above: exact fp32 on the matrix cores whatever t2_set_precision says, no atomics, every
+ * sum in a fixed order and partial sums added ascending in fp64, so the bits repeat from run to run.  Fixed-length batches
+ * only.  The discriminators and the GAN losses are not built. */
+#define T2_HIFIGAN_TRAIN_OPS 5 /* kinds of launch-list entry: conv, conv_post, conv_post backward, weight gradient, data gradient */
+typedef struct t2_hifigan_train_plan_info {
+    long out_len;                /* samples per item */
+    size_t tape_bytes;           /* the pre-activation input of every conv: conv_pre's output; per stage X and XS; per block r_m, t_m */
+    size_t workspace_bytes;      /* backward: five gradient buffers of the widest stage, partial planes, conv_post's fp64 partials */
+    size_t packed_bytes;         /* as t2_hifigan_plan */
+    size_t packed_bwd_bytes;     /* the data-gradient packs of every layer but conv_post */
+    size_t grad_floats;          /* the gradient arena: per layer dw (torch layout) then db, at t2_hifigan_grad_offsets */
+    size_t part_bytes;           /* the largest layer's partial planes (inside workspace_bytes) */
+    int n_layers;
+    int n_forward_launches, n_backward_launches;      /* kernels per call, the mel's gradient included */
+    int launches[T2_HIFIGAN_TRAIN_OPS];               /* launch-list entries per kind, forward and backward together */
+} t2_hifigan_train_plan_info;
+/* Pure host call (no device): the tape, the scratch and the launch list from cfg, B and T alone. */
+int t2_hifigan_train_plan(const t2_hifigan_config* cfg, int B, int T, t2_hifigan_train_plan_info* out);
+/* Offsets in floats of every layer's dw and db in the gradient arena; pure host. */
+int t2_hifigan_grad_offsets(const t2_hifigan_config* cfg, size_t* w_offsets, size_t* b_offsets, int n_layers);
+/* weights_host: a HOST array of n_layers DEVICE pointers (folded weights, torch layout, layer order).  Writes packed_bwd. */
+int t2_hifigan_pack_backward(const t2_hifigan_config* cfg, const float* const* weights_host, int n_layers, float* packed_bwd, void* stream);
+typedef struct t2_hifigan_train_fwd_args {
+    int B, T, n_mel;
+    const float* packed;         /* t2_hifigan_pack */
+    const float* mel;            /* [B, n_mel, T] */
+    float* tape;                 /* tape_bytes */
+    float* audio;                /* [B, 1, out_len]: the bits of t2_hifigan_forward */
+} t2_hifigan_train_fwd_args;
+int t2_hifigan_forward_train(const t2_hifigan_config* cfg, const t2_hifigan_train_fwd_args* a, void* stream);
+typedef struct t2_hifigan_bwd_args {
+    int B, T, n_mel;
+    const float* packed; const float* packed_bwd;
+    const float* mel; const float* tape; const float* audio;     /* as t2_hifigan_forward_train read and wrote them */
+    const float* d_audio;        /* [B, 1, out_len]: the gradient on the audio */
+    float* workspace;            /* workspace_bytes */
+    float* grads;                /* grad_floats; every dw and db is written.  Nullable (then d_mel must be given): no weight gradient is launched */
+    float* d_mel;                /* nullable: [B, n_mel, T], conv_pre's data gradient */
+} t2_hifigan_bwd_args;
+int t2_hifigan_backward(const t2_hifigan_config* cfg, const t2_hifigan_bwd_args* a, void* stream);
+/* Single kernels, for the tests only (the backward runs the same ones).  L is the layer's INPUT length throughout.
+ * Data gradient of conv(leaky_relu(x, slope)) (Conv1d.forward as ResBlock1.forward :37-41 calls it; ConvTranspose1d as
+ * Generator.forward :103-104): dx = (accumulate ? dx : 0) + (residual + lrelu'(x) * W^T dy) * scale, lrelu'(0) = slope as torch
+ * has it; x nullable (no activation in front: conv_pre), residual nullable; dx, x, residual [B, Cin, L]; dy [B, Cout, L] or
+ * [B, Cout, L*u]; dx must not overlap dy or residual (refused, before anything is written).  packed_ws: t2_vocoder_dgrad_packed_floats(Cin, Cout, k, u) floats. */
+typedef struct t2_vocoder_dgrad_args {
+    int B, Cin, Cout, L, k, d, u;
+    const float* dy; const float* w; const float* x; const float* residual;
+    float* dx; float* packed_ws;
+    float slope; int accumulate; float scale;
+} t2_vocoder_dgrad_args;
+size_t t2_vocoder_dgrad_packed_floats(int Cin, int Cout, int k, int u);
+int t2_vocoder_conv1d_dgrad(const t2_vocoder_dgrad_args* a, void* stream);             /* a->u must be 0 */
+int t2_vocoder_conv_transpose1d_dgrad(const t2_vocoder_dgrad_args* a, void* stream);   /* a->d unused */
+/* Weight and bias gradient of the same layers (u = 0: Conv1d, u > 0: ConvTranspose1d): dw in torch's layout, db [Cout]
+ * nullable, both written; part: t2_vocoder_wgrad_part_floats(...) floats of scratch for the partial planes. */
+typedef struct t2_vocoder_wgrad_args {
+    int B, Cin, Cout, L, k, d, u;
+    const float* x; const float* dy;
+    float* dw; float* db; float* part;
+    float slope;
+} t2_vocoder_wgrad_args;
+size_t t2_vocoder_wgrad_part_floats(int B, int Cin, int Cout, int L, int k, int d, int u);
+int t2_vocoder_wgrad(const t2_vocoder_wgrad_args* a, void* stream);
+/* conv_post and the tanh backwards (Generator.forward :112-114): d_pre = d_audio * (1 - audio^2); dx [B, C, L] = lrelu'(x; 0.01) *
+ * w^T d_pre * scale; dw [C, 7], db [1].  part: t2_vocoder_post_part_doubles(B, C, L) doubles, 8-byte aligned. */
+typedef struct t2_vocoder_post_bwd_args {
+    int B, C, L;
+    const float* x; const float* w; const float* audio; const float* d_audio;
+    float* dx; float* dw; float* db; double* part;
+    float scale;
+} t2_vocoder_post_bwd_args;
+size_t t2_vocoder_post_part_doubles(int B, int C, int L);
+int t2_vocoder_post_backward(const t2_vocoder_post_bwd_args* a, void* stream);
+
 /* ---- STFT analysis / synthesis and vocoder bias removal ---------------------------------------------
  * Replaces the reference's stft.py: STFT.transform (:77-105), STFT.inverse (:107-136) and STFT.forward (:138-141), with
  * audio_processing.py: window_sumsquare (:7-56), and the element-wise middle of bias_remover.py:

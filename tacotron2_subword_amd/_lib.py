@@ -323,6 +323,46 @@ class VocoderConvRaggedArgs(C.Structure):
     _fields_ = [("conv", VocoderConvArgs), ("lengths", C.c_void_p)]
 
 
+HIFIGAN_TRAIN_OPS = ("conv", "conv_post", "conv_post_backward", "weight_gradient", "data_gradient")
+
+
+class HifiganTrainPlanInfo(C.Structure):
+    _fields_ = [("out_len", C.c_long), ("tape_bytes", C.c_size_t), ("workspace_bytes", C.c_size_t), ("packed_bytes", C.c_size_t),
+                ("packed_bwd_bytes", C.c_size_t), ("grad_floats", C.c_size_t), ("part_bytes", C.c_size_t), ("n_layers", C.c_int),
+                ("n_forward_launches", C.c_int), ("n_backward_launches", C.c_int), ("launches", C.c_int * len(HIFIGAN_TRAIN_OPS))]
+
+
+class HifiganTrainFwdArgs(C.Structure):
+    _fields_ = [("B", C.c_int), ("T", C.c_int), ("n_mel", C.c_int), ("packed", C.c_void_p), ("mel", C.c_void_p),
+                ("tape", C.c_void_p), ("audio", C.c_void_p)]
+
+
+class HifiganBwdArgs(C.Structure):
+    _fields_ = [("B", C.c_int), ("T", C.c_int), ("n_mel", C.c_int), ("packed", C.c_void_p), ("packed_bwd", C.c_void_p),
+                ("mel", C.c_void_p), ("tape", C.c_void_p), ("audio", C.c_void_p), ("d_audio", C.c_void_p),
+                ("workspace", C.c_void_p), ("grads", C.c_void_p), ("d_mel", C.c_void_p)]
+
+
+class VocoderDgradArgs(C.Structure):
+    _fields_ = [("B", C.c_int), ("Cin", C.c_int), ("Cout", C.c_int), ("L", C.c_int), ("k", C.c_int), ("d", C.c_int), ("u", C.c_int),
+                ("dy", C.c_void_p), ("w", C.c_void_p), ("x", C.c_void_p), ("residual", C.c_void_p),
+                ("dx", C.c_void_p), ("packed_ws", C.c_void_p),
+                ("slope", C.c_float), ("accumulate", C.c_int), ("scale", C.c_float)]
+
+
+class VocoderWgradArgs(C.Structure):
+    _fields_ = [("B", C.c_int), ("Cin", C.c_int), ("Cout", C.c_int), ("L", C.c_int), ("k", C.c_int), ("d", C.c_int), ("u", C.c_int),
+                ("x", C.c_void_p), ("dy", C.c_void_p), ("dw", C.c_void_p), ("db", C.c_void_p), ("part", C.c_void_p),
+                ("slope", C.c_float)]
+
+
+class VocoderPostBwdArgs(C.Structure):
+    _fields_ = [("B", C.c_int), ("C", C.c_int), ("L", C.c_int),
+                ("x", C.c_void_p), ("w", C.c_void_p), ("audio", C.c_void_p), ("d_audio", C.c_void_p),
+                ("dx", C.c_void_p), ("dw", C.c_void_p), ("db", C.c_void_p), ("part", C.c_void_p),
+                ("scale", C.c_float)]
+
+
 VOCODER_TIME_TILE = 128      # include/t2amd.h T2_VOCODER_TIME_TILE
 
 
@@ -543,7 +583,9 @@ EXPORTS = ["t2_last_error", "t2_version", "t2_chain_status", "t2_chain_status_cl
            "t2_ssim_plan", "t2_ssim_forward", "t2_ssim_backward",
            "t2_bert_plan", "t2_bert_pack", "t2_bert_forward", "t2_bert_embed_ln", "t2_bert_layernorm", "t2_bert_attention",
            "t2_hifigan_plan", "t2_hifigan_pack", "t2_hifigan_forward", "t2_hifigan_forward_ragged", "t2_vocoder_packed_floats", "t2_vocoder_conv1d", "t2_vocoder_conv_transpose1d",
-           "t2_vocoder_conv_ragged", "t2_stft_analysis_ragged", "t2_stft_synthesis_ragged",
+           "t2_vocoder_conv_ragged", "t2_hifigan_train_plan", "t2_hifigan_grad_offsets", "t2_hifigan_pack_backward", "t2_hifigan_forward_train", "t2_hifigan_backward",
+           "t2_vocoder_dgrad_packed_floats", "t2_vocoder_conv1d_dgrad", "t2_vocoder_conv_transpose1d_dgrad", "t2_vocoder_wgrad_part_floats", "t2_vocoder_wgrad",
+           "t2_vocoder_post_part_doubles", "t2_vocoder_post_backward", "t2_stft_analysis_ragged", "t2_stft_synthesis_ragged",
            "t2_stft_plan", "t2_stft_pack", "t2_stft_analysis", "t2_stft_synthesis", "t2_melspec_plan", "t2_melspec_pack", "t2_melspec",
            "t2_melspec_grad_plan", "t2_melspec_grad_pack", "t2_melspec_backward", "t2_stft_analysis_backward",
            "t2_silence_plan", "t2_silence_trim",
@@ -643,6 +685,18 @@ def lib() -> C.CDLL:
         L.t2_stft_synthesis.argtypes = [C.POINTER(StftSynthesisArgs), C.c_void_p]
         L.t2_hifigan_forward_ragged.argtypes = [C.POINTER(HifiganConfig), C.POINTER(HifiganRaggedArgs), C.c_void_p]
         L.t2_vocoder_conv_ragged.argtypes = [C.POINTER(VocoderConvRaggedArgs), C.c_void_p]
+        L.t2_hifigan_train_plan.argtypes = [C.POINTER(HifiganConfig), C.c_int, C.c_int, C.POINTER(HifiganTrainPlanInfo)]
+        L.t2_hifigan_grad_offsets.argtypes = [C.POINTER(HifiganConfig), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), C.c_int]
+        L.t2_hifigan_pack_backward.argtypes = [C.POINTER(HifiganConfig), C.POINTER(C.c_void_p), C.c_int, C.c_void_p, C.c_void_p]
+        L.t2_hifigan_forward_train.argtypes = [C.POINTER(HifiganConfig), C.POINTER(HifiganTrainFwdArgs), C.c_void_p]
+        L.t2_hifigan_backward.argtypes = [C.POINTER(HifiganConfig), C.POINTER(HifiganBwdArgs), C.c_void_p]
+        L.t2_vocoder_dgrad_packed_floats.argtypes, L.t2_vocoder_dgrad_packed_floats.restype = [C.c_int] * 4, C.c_size_t
+        L.t2_vocoder_conv1d_dgrad.argtypes = [C.POINTER(VocoderDgradArgs), C.c_void_p]
+        L.t2_vocoder_conv_transpose1d_dgrad.argtypes = [C.POINTER(VocoderDgradArgs), C.c_void_p]
+        L.t2_vocoder_wgrad_part_floats.argtypes, L.t2_vocoder_wgrad_part_floats.restype = [C.c_int] * 7, C.c_size_t
+        L.t2_vocoder_wgrad.argtypes = [C.POINTER(VocoderWgradArgs), C.c_void_p]
+        L.t2_vocoder_post_part_doubles.argtypes, L.t2_vocoder_post_part_doubles.restype = [C.c_int] * 3, C.c_size_t
+        L.t2_vocoder_post_backward.argtypes = [C.POINTER(VocoderPostBwdArgs), C.c_void_p]
         L.t2_stft_analysis_ragged.argtypes = [C.POINTER(StftAnalysisRaggedArgs), C.c_void_p]
         L.t2_stft_synthesis_ragged.argtypes = [C.POINTER(StftSynthesisRaggedArgs), C.c_void_p]
         L.t2_melspec_plan.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_long, C.c_int, C.POINTER(MelspecPlanInfo)]
@@ -1176,6 +1230,20 @@ def hifigan_plan(cfg: HifiganConfig, B: int, T: int) -> HifiganPlanInfo:
     info = HifiganPlanInfo()
     check(lib().t2_hifigan_plan(C.byref(cfg), B, T, C.byref(info)))
     return info
+
+
+def hifigan_train_plan(cfg: HifiganConfig, B: int, T: int) -> HifiganTrainPlanInfo:
+    """Tape, scratch and launch counts of a training step of the generator (t2_hifigan_train_plan: pure host, no device needed)."""
+    info = HifiganTrainPlanInfo()
+    check(lib().t2_hifigan_train_plan(C.byref(cfg), B, T, C.byref(info)))
+    return info
+
+
+def hifigan_grad_offsets(cfg: HifiganConfig, n_layers: int):
+    """(offsets of dw, offsets of db) per layer in the gradient arena of t2_hifigan_backward, in floats."""
+    w, b = (C.c_size_t * n_layers)(), (C.c_size_t * n_layers)()
+    check(lib().t2_hifigan_grad_offsets(C.byref(cfg), w, b, n_layers))
+    return list(w), list(b)
 
 
 def stft_plan(N: int, hop: int, nf: int = 1) -> StftPlanInfo:

@@ -26,28 +26,9 @@
 #include <vector>
 
 #include "slab_gemm.h"
+#include "vocoder.h"
 
 namespace t2 {
-
-constexpr int kVocMaxPad = 60;                   // (k*d - d)/2 at k = 11, d = 12
-// One layer on packed weights.  u == 0: Conv1d, kernel k, dilation d, stride 1, padding (k*d - d)/2, x [B,Cin,L] ->
-// y [B,Cout,L];  y = ((accumulate ? y : 0) + conv(lrelu(x, slope)) + bias + res) * scale, bias and res nullable.
-// u > 0: ConvTranspose1d, kernel k = 2u, stride u, padding (k - u)/2, x [B,Cin,L] -> y [B,Cout,L*u]; no res / accumulate.
-struct VocConv {
-    int B, Cin, Cout; long L; int k, d, u;
-    const float* x; const float* packed; const float* bias; const float* res; float* y;
-    float slope; int accumulate; float scale;
-    // nullable, device: item b's rows hold clamp(frames[b], 0, T) * factor inputs (L = T * factor).  What x, res and (accumulate) y
-    // hold behind that is never read; y behind it is left as it was
-    const int32_t* frames = nullptr; int T = 0, factor = 0;
-};
-// kind 0 Conv1d, 1 ConvTranspose1d, 2 conv_post; offsets in floats into the packed weights.  Order: conv_pre, ups[i],
-// resblocks[n] (ResBlock1: convs1[m] then convs2[m]; ResBlock2: convs[m]), conv_post: the order of the state dict.
-struct HifiganLayer { int kind, cin, cout, k, d, u; size_t w_off, b_off; };
-struct HifiganPlan { long out_len; size_t buf_floats, workspace_bytes, packed_bytes; int n_layers; };
-
-constexpr int kVocStride = 288;                   // slab row stride in floats: = 32 mod 64 banks, >= kVocTT + 2*kVocMaxPad
-static_assert(kVocStride % 64 == 32 && kVocStride >= kVocTT + 2 * kVocMaxPad, "slab row stride");
 
 struct VocGemm {
     const float* x; const float* wp; const float* bias; const float* res; float* y;
@@ -106,7 +87,6 @@ __global__ void __launch_bounds__(WM * 128) voc_gemm_kernel(VocGemm p) {
 
 // conv_post: y[b,0,t] = tanh(bias + sum_ci sum_j w[ci][j] * lrelu(x[b,ci,t+j-3])), ci then j ascending, one fused multiply-add
 // per term.  Cout = 1 makes it a reduction: one thread per output sample, the weights in LDS, loads coalesced along time.
-constexpr int kVocPostK = 7;
 __global__ void __launch_bounds__(256) voc_post_kernel(const float* __restrict__ x, const float* __restrict__ w, const float* __restrict__ bias,
                                                       float* __restrict__ audio, float* __restrict__ pre, int C, long L, float slope,
                                                       const int32_t* __restrict__ frames, int T, int factor, int32_t* __restrict__ sample_lengths) {
@@ -148,7 +128,7 @@ __global__ void __launch_bounds__(256) voc_post_kernel(const float* __restrict__
 // ------------------------------------------------------------------------------------------------------------------
 // host
 // ------------------------------------------------------------------------------------------------------------------
-static int voc_shape_check(const char* who, int Cin, int Cout, int k, int d, int u) {
+int voc_shape_check(const char* who, int Cin, int Cout, int k, int d, int u) {
     T2_REQUIRE(Cin >= 8 && Cin <= 512 && Cin % 8 == 0, "%s: %d input channels, must be a multiple of 8 from 8 to 512", who, Cin);
     T2_REQUIRE(Cout >= 8 && Cout <= 512 && Cout % 8 == 0, "%s: %d output channels, must be a multiple of 8 from 8 to 512", who, Cout);
     if (u == 0) {
@@ -184,7 +164,7 @@ static int voc_pack(const float* w, float* packed, int Cin, int Cout, int k, int
     return 0;
 }
 
-static int voc_conv(const VocConv& a, hipStream_t s) {
+int voc_conv(const VocConv& a, hipStream_t s) {
     const char* who = a.u ? "vocoder conv_transpose1d" : "vocoder conv1d";
     T2_TRY_RC(voc_shape_check(who, a.Cin, a.Cout, a.k, a.u ? 1 : a.d, a.u));
     T2_REQUIRE(a.B >= 1 && a.B <= 65535, "%s: B=%d outside 1..65535", who, a.B);
@@ -210,7 +190,7 @@ static int voc_conv(const VocConv& a, hipStream_t s) {
 // ------------------------------------------------------------------------------------------------------------------
 // the generator
 // ------------------------------------------------------------------------------------------------------------------
-static int hifigan_layers(const t2_hifigan_config& c, std::vector<HifiganLayer>* out, size_t* packed_floats) {   // validates; no device
+int hifigan_layers(const t2_hifigan_config& c, std::vector<HifiganLayer>* out, size_t* packed_floats) {   // validates; no device
     T2_REQUIRE(c.resblock == 1 || c.resblock == 2, "hifigan: resblock \"%d\" is not \"1\" or \"2\"", c.resblock);
     T2_REQUIRE(c.n_mel == 80, "hifigan: %d mel channels, conv_pre takes 80", c.n_mel);
     T2_REQUIRE(c.num_upsamples >= 1 && c.num_upsamples <= T2_HIFIGAN_MAX_UPS, "hifigan: %d upsampling stages outside 1..%d", c.num_upsamples, T2_HIFIGAN_MAX_UPS);
@@ -246,7 +226,7 @@ static int hifigan_layers(const t2_hifigan_config& c, std::vector<HifiganLayer>*
     return 0;
 }
 
-static int hifigan_plan(const t2_hifigan_config& c, int B, int T, HifiganPlan* out) {
+int hifigan_plan(const t2_hifigan_config& c, int B, int T, HifiganPlan* out) {
     T2_REQUIRE(out, "hifigan: null plan");
     std::vector<HifiganLayer> L;
     size_t packed = 0;
@@ -329,9 +309,14 @@ static int hifigan_forward(const t2_hifigan_config& c, const t2_hifigan_fwd_args
     const HifiganLayer& post = L.back();
     T2_REQUIRE(rb + 1 == L.size(), "hifigan_forward: layer table out of step");
     // F.leaky_relu(x) in front of conv_post is torch's default slope 0.01, not LRELU_SLOPE (hifigan_model.py:112)
-    dim3 grid((unsigned)((len + 255) / 256), (unsigned)a.B);
-    hipLaunchKernelGGL(voc_post_kernel, grid, dim3(256), (size_t)post.cin * kVocPostK * sizeof(float), s, XS, a.packed + post.w_off,
-                       a.packed + post.b_off, a.audio, a.pre_tanh, post.cin, len, 0.01f, frames, a.T, (int)(len / a.T), sample_lengths);
+    return voc_post(XS, a.packed + post.w_off, a.packed + post.b_off, a.audio, a.pre_tanh, a.B, post.cin, len, frames, a.T, (int)(len / a.T), sample_lengths, s);
+}
+
+int voc_post(const float* x, const float* w, const float* bias, float* audio, float* pre, int B, int C, long len, const int32_t* frames, int T, int factor,
+             int32_t* sample_lengths, hipStream_t s) {
+    dim3 grid((unsigned)((len + 255) / 256), (unsigned)B);
+    hipLaunchKernelGGL(voc_post_kernel, grid, dim3(256), (size_t)C * kVocPostK * sizeof(float), s, x, w, bias, audio, pre, C, len, 0.01f, frames, T, factor,
+                       sample_lengths);
     T2_LAUNCH_CHECK();
     return 0;
 }

@@ -9,7 +9,14 @@ runs the whole generator through ``t2_hifigan_forward``.  So the reference's thr
     generator.eval(); generator.remove_weight_norm()
     audio = generator(mel)            # mel [B, 80, T] fp32 on the GPU -> [B, 1, T * prod(upsample_rates)]
 
-Inference only and always fp32 (``set_precision`` does not reach the vocoder); no CPU path; no discriminators."""
+Inference only unless ``Generator.trainable()`` opts in; always fp32 (``set_precision`` does not reach the vocoder); no CPU
+path; no discriminators.  Opted in, ``forward`` keeps every conv's pre-activation input and registers one autograd node whose
+backward is HIP (csrc/vocoder_bwd.hip)::
+
+    gen = Generator(h).cuda().trainable()
+    y_hat = gen(mel)                                   # [B, 1, T * prod(rates)], carries grad
+    loss = F.l1_loss(mel_spectrogram_from_audio(y_hat.squeeze(1), differentiable=True), mel_target) * 45
+    loss.backward()                                    # .grad on every bias / weight_g / weight_v (or weight, once folded)"""
 from __future__ import annotations
 
 import ctypes as C
@@ -69,6 +76,64 @@ class _WNConv(nn.Module):
 def _resconv(channels, k, d):
     assert get_padding(k, d) * 2 == k * d - d
     return _WNConv(channels, channels, k, dilation=d)
+
+
+class _GeneratorFunction(torch.autograd.Function):
+    """audio from the mel and the folded fp32 tensors (weight, bias per layer, in ``Generator._layers()`` order).  The weights are
+    packed here, on every call, into buffers of the call's own (the forward pack and the data-gradient packs): the parameters
+    change between calls, and an optimizer that writes through raw pointers (``optim.FusedAdam``) leaves no trace in a parameter's
+    version.  t2_hifigan_forward_train, then t2_hifigan_backward for an arbitrary gradient on the audio.  The backward returns one
+    gradient per folded tensor, as views into one arena, and the mel's where it is asked for; where no folded tensor asks for a
+    gradient the weight gradients are not launched and the arena is not allocated."""
+
+    @staticmethod
+    def forward(ctx, cfg, mel, *tensors):
+        dev, f32 = mel.device, torch.float32
+        B, n_mel, T = mel.shape
+        plan = L.hifigan_train_plan(cfg, B, T)
+        n = plan.n_layers
+        with torch.cuda.device(dev):
+            ts = [t.detach().to(f32).contiguous() for t in tensors]
+            mel = mel.detach().contiguous()
+            packed = torch.empty(plan.packed_bytes // 4, device=dev, dtype=f32)
+            packed_bwd = torch.empty(plan.packed_bwd_bytes // 4, device=dev, dtype=f32)
+            wp = (C.c_void_p * n)(*[L.ptr(w) for w in ts[0::2]])
+            bp = (C.c_void_p * n)(*[L.ptr(b) for b in ts[1::2]])
+            L.check(L.lib().t2_hifigan_pack(C.byref(cfg), wp, bp, n, L.ptr(packed), L.stream()))
+            L.check(L.lib().t2_hifigan_pack_backward(C.byref(cfg), wp, n, L.ptr(packed_bwd), L.stream()))
+            tape = torch.empty(plan.tape_bytes // 4, device=dev, dtype=f32)
+            audio = torch.empty(B, 1, plan.out_len, device=dev, dtype=f32)
+            a = L.HifiganTrainFwdArgs(B, T, n_mel, L.ptr(packed), L.ptr(mel), L.ptr(tape), L.ptr(audio))
+            L.check(L.lib().t2_hifigan_forward_train(C.byref(cfg), C.byref(a), L.stream()))
+        ctx.cfg, ctx.packed, ctx.packed_bwd, ctx.tape = cfg, packed, packed_bwd, tape
+        ctx.shapes = [t.shape for t in tensors]
+        ctx.save_for_backward(mel, audio)
+        return audio
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, d_audio):
+        cfg = ctx.cfg
+        mel, audio = ctx.saved_tensors
+        dev, f32 = mel.device, torch.float32
+        B, n_mel, T = mel.shape
+        plan = L.hifigan_train_plan(cfg, B, T)
+        want_w = any(ctx.needs_input_grad[2:])
+        with torch.cuda.device(dev):
+            d_audio = d_audio.to(f32).contiguous()
+            ws = torch.empty(plan.workspace_bytes // 4, device=dev, dtype=f32)
+            arena = torch.empty(plan.grad_floats, device=dev, dtype=f32) if want_w else None
+            d_mel = torch.empty_like(mel) if ctx.needs_input_grad[1] else None
+            a = L.HifiganBwdArgs(B, T, n_mel, L.ptr(ctx.packed), L.ptr(ctx.packed_bwd), L.ptr(mel), L.ptr(ctx.tape), L.ptr(audio), L.ptr(d_audio),
+                                 L.ptr(ws), L.ptr(arena), L.ptr(d_mel))
+            L.check(L.lib().t2_hifigan_backward(C.byref(cfg), C.byref(a), L.stream()))
+        grads = [None] * len(ctx.shapes)
+        if want_w:
+            woff, boff = L.hifigan_grad_offsets(cfg, plan.n_layers)
+            for i in range(plan.n_layers):
+                ws_, bs_ = ctx.shapes[2 * i], ctx.shapes[2 * i + 1]
+                grads[2 * i], grads[2 * i + 1] = arena[woff[i]:woff[i] + ws_.numel()].view(ws_), arena[boff[i]:boff[i] + bs_.numel()].view(bs_)
+        return (None, d_mel, *grads)
 
 
 class ResBlock1(nn.Module):
@@ -154,6 +219,38 @@ class Generator(nn.Module):
         self._packed = None
         return out
 
+    def trainable(self, on=True):
+        """Opt in to training: ``forward`` then keeps what the backward reads whenever grad mode is on and a parameter or the mel
+        requires grad, and ``loss.backward()`` leaves ``.grad`` on every parameter (and on the mel, if it asks).  A plain
+        attribute, read with ``getattr(..., False)``.  ``trainable(False)`` restores the inference-only behaviour.  Returns self."""
+        self._trainable = bool(on)
+        return self
+
+    def _train_forward(self, x, lengths):
+        """The generator with a backward.  The weight norm is folded on the device by torch's own ``_weight_norm``, so autograd carries a
+        folded tensor's gradient on to ``weight_g`` / ``weight_v`` (or ``weight``).  The parameters changing every step, the folded
+        tensors are packed on every call into buffers of the call's own (as ``WaveGlow._train_forward`` does): the ``_key()`` cache is
+        not read, and it is dropped, so that the next inference call packs the parameters as they then are -- also after an
+        optimizer that writes through raw pointers and bumps no version (``optim.FusedAdam``)."""
+        who = "hifigan Generator"
+        if lengths is not None:
+            raise RuntimeError(f"{who}: lengths= together with a gradient is not built: training runs on fixed-length segments; "
+                               "call it under torch.no_grad() for a ragged batch")
+        if not x.is_cuda:
+            raise RuntimeError(f"{who}: the mel must live on the GPU (the product path has no CPU fallback)")
+        if x.dim() != 3:
+            raise RuntimeError(f"{who}: expected a mel of shape [B, 80, T], got {tuple(x.shape)}")
+        if x.dtype != torch.float32:
+            raise RuntimeError(f"{who}: the mel must be float32, got {x.dtype}")
+        layers = self._layers()
+        if layers[0].bias.device != x.device:
+            raise RuntimeError(f"{who}: the mel is on {x.device}, the parameters on {layers[0].bias.device}")
+        tensors = []
+        for l in layers:
+            tensors += [torch._weight_norm(l.weight_v, l.weight_g, 0) if l.weight_normed else l.weight, l.bias]
+        self._packed = None
+        return _GeneratorFunction.apply(self._cfg, x, *tensors)
+
     def _key(self):
         return tuple((p.data_ptr(), p._version) for p in self.parameters())
 
@@ -185,6 +282,10 @@ class Generator(nn.Module):
         Item b is then computed as mel[b, :, :lengths[b]] alone would be, with the same bits; what the mel holds behind its
         length is never read, audio (and pre) are zero behind lengths[b] * prod(upsample_rates), and the result is
         (audio, sample_lengths) or (audio, pre, sample_lengths), sample_lengths an int32 device tensor [B]."""
+        if getattr(self, "_trainable", False) and torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters())):
+            if return_pre_tanh:
+                raise RuntimeError("hifigan Generator: return_pre_tanh is a debug output of the inference path; it has no gradient")
+            return self._train_forward(x, lengths)
         if not x.is_cuda:
             raise RuntimeError("hifigan Generator: the mel must live on the GPU (the product path has no CPU fallback)")
         if torch.is_grad_enabled() and x.requires_grad:
