@@ -851,7 +851,8 @@ int t2_vocoder_conv_ragged(const t2_vocoder_conv_ragged_args* a, void* stream);
  * ResBlock2.forward (:63-68), which the reference leaves to torch's autograd, and a forward that keeps what it reads.  Same
  * layouts, limits and arithmetic as above: exact fp32 on the matrix cores whatever t2_set_precision says, no atomics, every
  * sum in a fixed order and partial sums added ascending in fp64, so the bits repeat from run to run.  Fixed-length batches
- * only.  The discriminators and the GAN losses are not built. */
+ * only.  The multi-period discriminator is the next section; the GAN losses are element-wise torch in hifigan_infer/hifigan_model.py.
+ * MultiScaleDiscriminator is not built. */
 #define T2_HIFIGAN_TRAIN_OPS 5 /* kinds of launch-list entry: conv, conv_post, conv_post backward, weight gradient, data gradient */
 typedef struct t2_hifigan_train_plan_info {
     long out_len;                /* samples per item */
@@ -923,6 +924,54 @@ typedef struct t2_vocoder_post_bwd_args {
 } t2_vocoder_post_bwd_args;
 size_t t2_vocoder_post_part_doubles(int B, int C, int L);
 int t2_vocoder_post_backward(const t2_vocoder_post_bwd_args* a, void* stream);
+
+/* ---- HiFi-GAN multi-period discriminator, forward and backward -------------------------------------
+ * Replaces hifigan_infer/hifigan_model.py: DiscriminatorP.forward (:141-160), as MultiPeriodDiscriminator.forward (:174-187)
+ * calls it, and its backward, which the reference leaves to torch's autograd.  One call runs one period discriminator over B
+ * items: real and generated audio go in together as one batch, so the weights are read once.  Layout as torch has it: audio
+ * [B, 1, T], feature map i [B, C[i+1], H[i+1], period]; conv i = convs[i] (:132-138) for i < 5, conv 5 = conv_post (:139).  The
+ * reflect padding (:146-149) is index arithmetic; T with period - T % period > T - 1 is refused, where torch raises.  Weights are
+ * the folded ones in torch layout [Cout][Cin][k][1].  Exact fp32 on the matrix cores whatever t2_set_precision says, no atomics,
+ * every sum in a fixed order, partial sums added ascending in fp64: the bits repeat from run to run, and an item's feature maps
+ * are those of the item run alone.  Periods 2..11; the reference's kernel size 5, stride 3 and widths only. */
+#define T2_HIFIGAN_MPD_LAYERS 6
+typedef struct t2_hifigan_mpd_plan_info {
+    int period, B, T, pad;                                               /* pad: samples reflected on the right */
+    int H[T2_HIFIGAN_MPD_LAYERS + 1], C[T2_HIFIGAN_MPD_LAYERS + 1];      /* [0]: the padded audio as [1][H][period]; [i + 1]: feature map i */
+    int tiles[T2_HIFIGAN_MPD_LAYERS];        /* 128-column tiles per item of conv i's GEMM over the H * period positions; 0: not a GEMM */
+    int splits[T2_HIFIGAN_MPD_LAYERS];       /* runs (partial planes) of conv i's weight gradient */
+    size_t fmap_floats[T2_HIFIGAN_MPD_LAYERS];
+    size_t w_offsets[T2_HIFIGAN_MPD_LAYERS], b_offsets[T2_HIFIGAN_MPD_LAYERS];   /* dw (torch layout) and db of conv i in the gradient arena, in floats */
+    size_t packed_bytes;         /* forward pack: every conv's weights (GEMM layers in fragment order) and biases */
+    size_t packed_bwd_bytes;     /* data-gradient packs of convs 1..4: three polyphase packs per strided conv */
+    size_t workspace_bytes;      /* backward: two buffers of the largest feature map and the partial planes */
+    size_t part_bytes;           /* the largest weight gradient's partial planes (inside workspace_bytes) */
+    size_t grad_floats;          /* the gradient arena */
+    int n_forward_launches, n_backward_launches;      /* kernels per call with every gradient asked for */
+} t2_hifigan_mpd_plan_info;
+/* Pure host call (no device): shapes, tiles, scratch and launch counts from (period, B, T) alone. */
+int t2_hifigan_mpd_plan(int period, int B, int T, t2_hifigan_mpd_plan_info* out);
+/* weights_host / biases_host: HOST arrays of T2_HIFIGAN_MPD_LAYERS DEVICE pointers.  The packs do not depend on period, B or T. */
+int t2_hifigan_mpd_pack(const float* const* weights_host, const float* const* biases_host, float* packed, void* stream);
+int t2_hifigan_mpd_pack_backward(const float* const* weights_host, float* packed_bwd, void* stream);
+typedef struct t2_hifigan_mpd_fwd_args {
+    int period, B, T;
+    const float* packed;
+    const float* audio;                          /* [B, 1, T] */
+    float* fmap[T2_HIFIGAN_MPD_LAYERS];          /* every one written: leaky_relu(conv i) for i < 5, conv_post's output (the score) at 5 */
+} t2_hifigan_mpd_fwd_args;
+int t2_hifigan_mpd_forward(const t2_hifigan_mpd_fwd_args* a, void* stream);
+typedef struct t2_hifigan_mpd_bwd_args {
+    int period, B, T;
+    const float* packed; const float* packed_bwd;
+    const float* audio;
+    const float* fmap[T2_HIFIGAN_MPD_LAYERS];    /* as t2_hifigan_mpd_forward wrote them: the tape (a map's sign gives lrelu') */
+    const float* g_fmap[T2_HIFIGAN_MPD_LAYERS];  /* the upstream gradient on each feature map; [0..4] nullable, [5] (the score's) required */
+    float* workspace;                            /* workspace_bytes */
+    float* grads;                                /* grad_floats, every dw and db written.  Nullable: no weight gradient is launched */
+    float* d_audio;                              /* [B, 1, T].  Nullable: the audio's gradient is not launched */
+} t2_hifigan_mpd_bwd_args;
+int t2_hifigan_mpd_backward(const t2_hifigan_mpd_bwd_args* a, void* stream);
 
 /* ---- STFT analysis / synthesis and vocoder bias removal ---------------------------------------------
  * Replaces the reference's stft.py: STFT.transform (:77-105), STFT.inverse (:107-136) and STFT.forward (:138-141), with

@@ -343,6 +343,29 @@ class HifiganBwdArgs(C.Structure):
                 ("workspace", C.c_void_p), ("grads", C.c_void_p), ("d_mel", C.c_void_p)]
 
 
+HIFIGAN_MPD_LAYERS = 6
+
+
+class HifiganMpdPlanInfo(C.Structure):
+    _fields_ = [("period", C.c_int), ("B", C.c_int), ("T", C.c_int), ("pad", C.c_int), ("H", C.c_int * (HIFIGAN_MPD_LAYERS + 1)),
+                ("C", C.c_int * (HIFIGAN_MPD_LAYERS + 1)), ("tiles", C.c_int * HIFIGAN_MPD_LAYERS), ("splits", C.c_int * HIFIGAN_MPD_LAYERS),
+                ("fmap_floats", C.c_size_t * HIFIGAN_MPD_LAYERS), ("w_offsets", C.c_size_t * HIFIGAN_MPD_LAYERS),
+                ("b_offsets", C.c_size_t * HIFIGAN_MPD_LAYERS), ("packed_bytes", C.c_size_t), ("packed_bwd_bytes", C.c_size_t),
+                ("workspace_bytes", C.c_size_t), ("part_bytes", C.c_size_t), ("grad_floats", C.c_size_t),
+                ("n_forward_launches", C.c_int), ("n_backward_launches", C.c_int)]
+
+
+class HifiganMpdFwdArgs(C.Structure):
+    _fields_ = [("period", C.c_int), ("B", C.c_int), ("T", C.c_int), ("packed", C.c_void_p), ("audio", C.c_void_p),
+                ("fmap", C.c_void_p * HIFIGAN_MPD_LAYERS)]
+
+
+class HifiganMpdBwdArgs(C.Structure):
+    _fields_ = [("period", C.c_int), ("B", C.c_int), ("T", C.c_int), ("packed", C.c_void_p), ("packed_bwd", C.c_void_p), ("audio", C.c_void_p),
+                ("fmap", C.c_void_p * HIFIGAN_MPD_LAYERS), ("g_fmap", C.c_void_p * HIFIGAN_MPD_LAYERS),
+                ("workspace", C.c_void_p), ("grads", C.c_void_p), ("d_audio", C.c_void_p)]
+
+
 class VocoderDgradArgs(C.Structure):
     _fields_ = [("B", C.c_int), ("Cin", C.c_int), ("Cout", C.c_int), ("L", C.c_int), ("k", C.c_int), ("d", C.c_int), ("u", C.c_int),
                 ("dy", C.c_void_p), ("w", C.c_void_p), ("x", C.c_void_p), ("residual", C.c_void_p),
@@ -585,6 +608,7 @@ EXPORTS = ["t2_last_error", "t2_version", "t2_chain_status", "t2_chain_status_cl
            "t2_hifigan_plan", "t2_hifigan_pack", "t2_hifigan_forward", "t2_hifigan_forward_ragged", "t2_vocoder_packed_floats", "t2_vocoder_conv1d", "t2_vocoder_conv_transpose1d",
            "t2_vocoder_conv_ragged", "t2_hifigan_train_plan", "t2_hifigan_grad_offsets", "t2_hifigan_pack_backward", "t2_hifigan_forward_train", "t2_hifigan_backward",
            "t2_vocoder_dgrad_packed_floats", "t2_vocoder_conv1d_dgrad", "t2_vocoder_conv_transpose1d_dgrad", "t2_vocoder_wgrad_part_floats", "t2_vocoder_wgrad",
+           "t2_hifigan_mpd_plan", "t2_hifigan_mpd_pack", "t2_hifigan_mpd_pack_backward", "t2_hifigan_mpd_forward", "t2_hifigan_mpd_backward",
            "t2_vocoder_post_part_doubles", "t2_vocoder_post_backward", "t2_stft_analysis_ragged", "t2_stft_synthesis_ragged",
            "t2_stft_plan", "t2_stft_pack", "t2_stft_analysis", "t2_stft_synthesis", "t2_melspec_plan", "t2_melspec_pack", "t2_melspec",
            "t2_melspec_grad_plan", "t2_melspec_grad_pack", "t2_melspec_backward", "t2_stft_analysis_backward",
@@ -697,6 +721,11 @@ def lib() -> C.CDLL:
         L.t2_vocoder_wgrad.argtypes = [C.POINTER(VocoderWgradArgs), C.c_void_p]
         L.t2_vocoder_post_part_doubles.argtypes, L.t2_vocoder_post_part_doubles.restype = [C.c_int] * 3, C.c_size_t
         L.t2_vocoder_post_backward.argtypes = [C.POINTER(VocoderPostBwdArgs), C.c_void_p]
+        L.t2_hifigan_mpd_plan.argtypes = [C.c_int, C.c_int, C.c_int, C.POINTER(HifiganMpdPlanInfo)]
+        L.t2_hifigan_mpd_pack.argtypes = [C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p]
+        L.t2_hifigan_mpd_pack_backward.argtypes = [C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p]
+        L.t2_hifigan_mpd_forward.argtypes = [C.POINTER(HifiganMpdFwdArgs), C.c_void_p]
+        L.t2_hifigan_mpd_backward.argtypes = [C.POINTER(HifiganMpdBwdArgs), C.c_void_p]
         L.t2_stft_analysis_ragged.argtypes = [C.POINTER(StftAnalysisRaggedArgs), C.c_void_p]
         L.t2_stft_synthesis_ragged.argtypes = [C.POINTER(StftSynthesisRaggedArgs), C.c_void_p]
         L.t2_melspec_plan.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_long, C.c_int, C.POINTER(MelspecPlanInfo)]
@@ -1236,6 +1265,14 @@ def hifigan_train_plan(cfg: HifiganConfig, B: int, T: int) -> HifiganTrainPlanIn
     """Tape, scratch and launch counts of a training step of the generator (t2_hifigan_train_plan: pure host, no device needed)."""
     info = HifiganTrainPlanInfo()
     check(lib().t2_hifigan_train_plan(C.byref(cfg), B, T, C.byref(info)))
+    return info
+
+
+def hifigan_mpd_plan(period: int, B: int, T: int) -> HifiganMpdPlanInfo:
+    """Shapes, tiles, scratch and launch counts of one period discriminator over B items of T samples (t2_hifigan_mpd_plan: pure
+    host, no device needed); raises with the library's message for a T too short for the reflect padding."""
+    info = HifiganMpdPlanInfo()
+    check(lib().t2_hifigan_mpd_plan(period, B, T, C.byref(info)))
     return info
 
 

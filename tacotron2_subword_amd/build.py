@@ -8,7 +8,7 @@ import subprocess
 _HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(_HERE, "csrc")
 OUT = os.path.join(_HERE, "libt2amd.so")
-SOURCES = ["gemm.hip", "gemm_f32.hip", "gemm_bf16conv.hip", "gemm_dispatch.hip", "lstm.hip", "chain_plan.hip", "chain.hip", "chain_bwd.hip", "chain_enc.hip", "attention.hip", "attention_lsa_bwd.hip", "attention_gmm.hip", "attention_dca.hip", "conv.hip", "elementwise.hip", "infer.hip", "optim.hip", "softdtw.hip", "ssim.hip", "bert.hip", "slab_gemm.hip", "vocoder.hip", "vocoder_bwd.hip", "waveglow_kernels.hip", "waveglow_plan.hip", "waveglow.hip", "stft.hip", "melspec.hip", "silence.hip", "decoder_plan.hip", "decoder.hip", "c_api.hip"]
+SOURCES = ["gemm.hip", "gemm_f32.hip", "gemm_bf16conv.hip", "gemm_dispatch.hip", "lstm.hip", "chain_plan.hip", "chain.hip", "chain_bwd.hip", "chain_enc.hip", "attention.hip", "attention_lsa_bwd.hip", "attention_gmm.hip", "attention_dca.hip", "conv.hip", "elementwise.hip", "infer.hip", "optim.hip", "softdtw.hip", "ssim.hip", "bert.hip", "slab_gemm.hip", "vocoder.hip", "vocoder_bwd.hip", "vocoder_disc.hip", "waveglow_kernels.hip", "waveglow_plan.hip", "waveglow.hip", "stft.hip", "melspec.hip", "silence.hip", "decoder_plan.hip", "decoder.hip", "c_api.hip"]
 
 
 def _newest(paths):

@@ -10,7 +10,9 @@ runs the whole generator through ``t2_hifigan_forward``.  So the reference's thr
     audio = generator(mel)            # mel [B, 80, T] fp32 on the GPU -> [B, 1, T * prod(upsample_rates)]
 
 Inference only unless ``Generator.trainable()`` opts in; always fp32 (``set_precision`` does not reach the vocoder); no CPU
-path; no discriminators.  Opted in, ``forward`` keeps every conv's pre-activation input and registers one autograd node whose
+path.  The adversarial side is below: ``DiscriminatorP`` / ``MultiPeriodDiscriminator`` (hifigan_model.py:127-187) in HIP
+(csrc/vocoder_disc.hip) and ``feature_loss`` / ``discriminator_loss`` / ``generator_loss`` (:250-281); ``MultiScaleDiscriminator`` is
+not built.  Opted in, ``forward`` keeps every conv's pre-activation input and registers one autograd node whose
 backward is HIP (csrc/vocoder_bwd.hip)::
 
     gen = Generator(h).cuda().trainable()
@@ -317,3 +319,198 @@ class Generator(nn.Module):
                                     L.ptr(sample_lengths))
             L.check(L.lib().t2_hifigan_forward_ragged(C.byref(self._cfg), C.byref(a), L.stream()))
         return (audio, pre, sample_lengths) if return_pre_tanh else (audio, sample_lengths)
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# the multi-period discriminator and the GAN losses
+# ----------------------------------------------------------------------------------------------------------------------
+_MPD_WIDTHS = (1, 32, 128, 512, 1024, 1024, 1)
+_MSD_NOT_BUILT = ("only the multi-period discriminator's own convolutions are built (kernel_size=5, stride=3, weight norm); "
+                  "the multi-scale discriminator (MultiScaleDiscriminator / DiscriminatorS, spectral norm) is not built")
+
+
+class _WNConv2d(nn.Module):
+    """Parameters of a weight-normed ``Conv2d(cin, cout, (k, 1))`` as torch.nn.utils.weight_norm leaves them: ``bias``,
+    ``weight_g`` [cout, 1, 1, 1], ``weight_v`` [cout, cin, k, 1], initialised by Conv2d's defaults (the reference applies no
+    init_weights to the discriminators)."""
+
+    def __init__(self, cin, cout, k):
+        super().__init__()
+        self.in_channels, self.out_channels, self.kernel_size = cin, cout, (k, 1)
+        v = torch.empty(cout, cin, k, 1)
+        nn.init.kaiming_uniform_(v, a=math.sqrt(5))
+        bound = 1.0 / math.sqrt(cin * k)
+        self.bias = nn.Parameter(torch.empty(cout).uniform_(-bound, bound))
+        self.weight_g = nn.Parameter(v.flatten(1).norm(dim=1).view(-1, 1, 1, 1))
+        self.weight_v = nn.Parameter(v)
+
+    def forward(self, x):
+        raise RuntimeError("this module only holds parameters: DiscriminatorP.forward runs the layers in HIP")
+
+
+def _mpd_launch(period, audio, tensors, backward_pack):
+    """Packs the folded tensors (weight, bias per conv) and runs t2_hifigan_mpd_forward: the six feature maps, and the packs."""
+    dev, f32 = audio.device, torch.float32
+    B, _, T = audio.shape
+    plan = L.hifigan_mpd_plan(period, B, T)
+    n = L.HIFIGAN_MPD_LAYERS
+    with torch.cuda.device(dev):
+        ts = [t.detach().to(f32).contiguous() for t in tensors]
+        wp = (C.c_void_p * n)(*[L.ptr(w) for w in ts[0::2]])
+        bp = (C.c_void_p * n)(*[L.ptr(b) for b in ts[1::2]])
+        packed = torch.empty(plan.packed_bytes // 4, device=dev, dtype=f32)
+        L.check(L.lib().t2_hifigan_mpd_pack(wp, bp, L.ptr(packed), L.stream()))
+        packed_bwd = None
+        if backward_pack:
+            packed_bwd = torch.empty(plan.packed_bwd_bytes // 4, device=dev, dtype=f32)
+            L.check(L.lib().t2_hifigan_mpd_pack_backward(wp, L.ptr(packed_bwd), L.stream()))
+        fmaps = [torch.empty(B, plan.C[i + 1], plan.H[i + 1], period, device=dev, dtype=f32) for i in range(n)]
+        a = L.HifiganMpdFwdArgs(period, B, T, L.ptr(packed), L.ptr(audio), (C.c_void_p * n)(*[L.ptr(f) for f in fmaps]))
+        L.check(L.lib().t2_hifigan_mpd_forward(C.byref(a), L.stream()))
+    return fmaps, packed, packed_bwd
+
+
+class _DiscriminatorPFunction(torch.autograd.Function):
+    """The six feature maps of one period discriminator from the audio [B, 1, T] (real and generated items together) and the folded
+    fp32 tensors (weight, bias per conv).  The weights are packed on every call: the parameters change between calls, and an optimizer
+    that writes through raw pointers leaves no trace in a parameter's version.  The feature maps are the tape.  The backward takes
+    whatever gradient autograd has for each map (none is a null pointer), launches the weight gradients only where a folded tensor
+    asks for one and the audio's only where the audio does, and returns the parameters' as views into one arena."""
+
+    @staticmethod
+    def forward(ctx, period, audio, *tensors):
+        audio = audio.detach().contiguous()
+        fmaps, packed, packed_bwd = _mpd_launch(period, audio, tensors, True)
+        ctx.period, ctx.packed, ctx.packed_bwd = period, packed, packed_bwd
+        ctx.shapes = [t.shape for t in tensors]
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(audio, *fmaps)
+        return tuple(fmaps)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, *g):
+        audio, *fmaps = ctx.saved_tensors
+        dev, f32 = audio.device, torch.float32
+        B, _, T = audio.shape
+        n = L.HIFIGAN_MPD_LAYERS
+        plan = L.hifigan_mpd_plan(ctx.period, B, T)
+        want_w, want_x = any(ctx.needs_input_grad[2:]), ctx.needs_input_grad[1]
+        grads = [None] * len(ctx.shapes)
+        if not (want_w or want_x) or all(x is None for x in g):
+            return (None, None, *grads)
+        with torch.cuda.device(dev):
+            g = [None if x is None else x.to(f32).contiguous() for x in g]
+            if g[n - 1] is None:
+                g[n - 1] = torch.zeros_like(fmaps[n - 1])
+            ws = torch.empty(plan.workspace_bytes // 4, device=dev, dtype=f32)
+            arena = torch.empty(plan.grad_floats, device=dev, dtype=f32) if want_w else None
+            d_audio = torch.empty_like(audio) if want_x else None
+            a = L.HifiganMpdBwdArgs(ctx.period, B, T, L.ptr(ctx.packed), L.ptr(ctx.packed_bwd), L.ptr(audio),
+                                    (C.c_void_p * n)(*[L.ptr(f) for f in fmaps]), (C.c_void_p * n)(*[L.ptr(x) for x in g]),
+                                    L.ptr(ws), L.ptr(arena), L.ptr(d_audio))
+            L.check(L.lib().t2_hifigan_mpd_backward(C.byref(a), L.stream()))
+        if want_w:
+            for i in range(n):
+                ws_, bs_ = ctx.shapes[2 * i], ctx.shapes[2 * i + 1]
+                wo, bo = plan.w_offsets[i], plan.b_offsets[i]
+                # the weight's gradient is consumed by _weight_norm's backward; the bias's goes to the parameter, and a view kept as
+                # .grad would pin the whole arena (33 MB per discriminator) for 4 KB: it is a copy of its own
+                grads[2 * i], grads[2 * i + 1] = arena[wo:wo + ws_.numel()].view(ws_), arena[bo:bo + bs_.numel()].view(bs_).clone()
+        return (None, d_audio, *grads)
+
+
+class DiscriminatorP(nn.Module):
+    """hifigan_model.py:127-160 with the reference's parameter names and shapes; ``forward`` runs csrc/vocoder_disc.hip."""
+
+    def __init__(self, period, kernel_size=5, stride=3, use_spectral_norm=False):
+        super().__init__()
+        if use_spectral_norm:
+            raise NotImplementedError("DiscriminatorP(use_spectral_norm=True): " + _MSD_NOT_BUILT)
+        if kernel_size != 5 or stride != 3:
+            raise NotImplementedError(f"DiscriminatorP(kernel_size={kernel_size}, stride={stride}): " + _MSD_NOT_BUILT)
+        self.period = int(period)
+        L.hifigan_mpd_plan(self.period, 1, self.period)  # refuses an unsupported period here, by name
+        self.convs = nn.ModuleList([_WNConv2d(_MPD_WIDTHS[i], _MPD_WIDTHS[i + 1], 5) for i in range(5)])
+        self.conv_post = _WNConv2d(_MPD_WIDTHS[5], 1, 3)
+
+    def _maps(self, x):
+        """The six feature maps for x [B, 1, T]: with a gradient wherever grad mode is on and x or a parameter asks for one."""
+        who = "hifigan DiscriminatorP"
+        if not x.is_cuda:
+            raise RuntimeError(f"{who}: the audio must live on the GPU (the product path has no CPU fallback)")
+        if x.dim() != 3 or x.shape[1] != 1:
+            raise RuntimeError(f"{who}: expected audio of shape [B, 1, T], got {tuple(x.shape)}")
+        if x.dtype != torch.float32:
+            raise RuntimeError(f"{who}: the audio must be float32, got {x.dtype}")
+        layers = list(self.convs) + [self.conv_post]
+        if layers[0].bias.device != x.device:
+            raise RuntimeError(f"{who}: the audio is on {x.device}, the parameters on {layers[0].bias.device}")
+        if torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters())):
+            tensors = []
+            for l in layers:
+                tensors += [torch._weight_norm(l.weight_v, l.weight_g, 0), l.bias]
+            return list(_DiscriminatorPFunction.apply(self.period, x, *tensors))
+        with torch.no_grad():                            # only the forward runs and nothing is kept
+            tensors = []
+            for l in layers:
+                tensors += [torch._weight_norm(l.weight_v, l.weight_g, 0), l.bias]
+            return _mpd_launch(self.period, x.detach().contiguous(), tensors, False)[0]
+
+    def forward(self, x):
+        fmap = self._maps(x)
+        return torch.flatten(fmap[-1], 1, -1), fmap
+
+
+class MultiPeriodDiscriminator(nn.Module):
+    """hifigan_model.py:163-187.  Real and generated audio run through each period discriminator as one batch of 2B items, so the
+    weights are read once; an item's feature maps have the bits of the item run alone."""
+
+    def __init__(self):
+        super().__init__()
+        self.discriminators = nn.ModuleList([DiscriminatorP(p) for p in (2, 3, 5, 7, 11)])
+
+    def forward(self, y, y_hat):
+        if y.shape != y_hat.shape:
+            raise RuntimeError(f"hifigan MultiPeriodDiscriminator: y is {tuple(y.shape)}, y_hat {tuple(y_hat.shape)}")
+        B = y.shape[0]
+        both = torch.cat([y, y_hat], dim=0)
+        y_d_rs, y_d_gs, fmap_rs, fmap_gs = [], [], [], []
+        for d in self.discriminators:
+            maps = d._maps(both)
+            fmap_r, fmap_g = [m[:B] for m in maps], [m[B:] for m in maps]
+            y_d_rs.append(torch.flatten(fmap_r[-1], 1, -1))
+            y_d_gs.append(torch.flatten(fmap_g[-1], 1, -1))
+            fmap_rs.append(fmap_r)
+            fmap_gs.append(fmap_g)
+        return y_d_rs, y_d_gs, fmap_rs, fmap_gs
+
+
+def feature_loss(fmap_r, fmap_g):
+    """hifigan_model.py:250-256: twice the sum over every feature map of the mean absolute difference."""
+    total = 0
+    for maps_r, maps_g in zip(fmap_r, fmap_g):
+        for r, g in zip(maps_r, maps_g):
+            total = total + (r - g).abs().mean()
+    return total * 2
+
+
+def discriminator_loss(disc_real_outputs, disc_generated_outputs):
+    """hifigan_model.py:259-270: least squares, real scores towards 1 and generated towards 0; the per-discriminator terms as floats."""
+    total, r_losses, g_losses = 0, [], []
+    for real, fake in zip(disc_real_outputs, disc_generated_outputs):
+        r_term, g_term = ((1 - real) ** 2).mean(), (fake ** 2).mean()
+        total = total + (r_term + g_term)
+        r_losses.append(r_term.item())
+        g_losses.append(g_term.item())
+    return total, r_losses, g_losses
+
+
+def generator_loss(disc_outputs):
+    """hifigan_model.py:273-281: least squares, generated scores towards 1; the per-discriminator terms stay tensors."""
+    total, gen_losses = 0, []
+    for fake in disc_outputs:
+        term = ((1 - fake) ** 2).mean()
+        gen_losses.append(term)
+        total = total + term
+    return total, gen_losses
